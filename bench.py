@@ -12,12 +12,16 @@ scene and photon map already resident in HBM, then ONE all-gather (RCCL over xGM
 RenderImage on every rank.  value = rays actually traced by all ranks / max-over-ranks time.
 Prints one JSON line on rank 0 (see the task contract).
 
+A plain run sets up, warms up, times the --steps frames and prints the line.  --dump-outputs DIR also
+writes the last timed frame (rgb, z, sample_count) as DIR/<name>.npy in float32.  --full adds what
+takes runs of its own:
 roofline: after the timed region the same frame is rendered --profile-frames more times with ONE chunk
 in flight (RT_STREAMS=1), so that the HIP-event intervals around each kernel class are exclusive kernel
 times; the line is quoted for the kernel that takes the most of them and says which of three ceilings
 that kernel sits closest to -- HBM bytes (PMC counters, profiles/), L2-side bytes (what the kernel asks
 its caches for), VALU issue slots (SQ counters, profiles/) -- see DESIGN.md section 6.
-cpu_baseline: the plain-C oracle timed on a bounded tile sample (rank 0, N=1 only).
+cpu_baseline: the plain-C oracle timed on a bounded tile sample (rank 0, N=1 only), and the last timed
+frame checked against the oracle's pixels (parity_check); with N>1 the gathered frame is checked.
 """
 import argparse
 import json
@@ -68,17 +72,42 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--photons", type=int, default=1000000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline frames, the CPU baseline with the parity check of the timed frame, and the multi-GPU frame checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the parity check")
     ap.add_argument("--sync-steps", action="store_true", help="wait for every timed frame on the host before the next one is started")
     ap.add_argument("--synthetic-photons", action="store_true", help="wall-sprinkled photons instead of the GPU photon pass")
     ap.add_argument("--cpu-seconds", type=float, default=30.0)
-    ap.add_argument("--profile-frames", type=int, default=2, help="frames of the RT_STREAMS=1 pass behind the timed region (0: no roofline)")
+    ap.add_argument("--profile-frames", type=int, default=2, help="(--full) frames of the RT_STREAMS=1 pass behind the timed region (0: no roofline)")
     ap.add_argument("--workload", choices=["cornell", "balls", "gi"], default="cornell",
                     help="cornell = the headline (BASELINE C4); balls = stand-in for the absent christmas_balls scene (C5): "
                          "128 tessellated spheres, 102 402 triangles, half of them mirrors, no photon map -- a BVH-bound "
                          "frame, reported for insight only; gi = BASELINE C3: the Cornell box with the live path-traced GI of "
                          "RayTracingProj12 (its Shade, bounce 8, one hemisphere ray per hit), 800x600, 64 spp, no photon map")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(frame, directory):
+    """The frame a caller of the timed path receives -- rgb (H,W,3), z (H,W), sample_count (H,W) -- as float32 .npy files.
+    A frame too large for DUMP_LIMIT_BYTES is cut to a fixed seeded sample of pixels, listed in pixel_index.npy."""
+    rgb, z, cnt = (t.cpu().numpy() for t in frame)
+    arrays = {"rgb": rgb, "z": z, "sample_count": cnt}
+    h, w = z.shape
+    if h * w * 5 * 4 > DUMP_LIMIT_BYTES:                    # 5 float32 per pixel
+        n = (DUMP_LIMIT_BYTES - 4096) // (5 * 4 + 8)          # (+ its float64 index; 4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+        arrays = {k: v.reshape((h * w,) + v.shape[2:])[idx] for k, v in arrays.items()}
+        arrays["pixel_index"] = idx
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), v.astype(np.float64 if name == "pixel_index" else np.float32))
 
 
 PARITY_GATE = {"frac_within_1": 0.995, "z_equal_frac": 0.999}       # SURVEY 8(c): >= 99.5 % of pixels within 1 level, z equal
@@ -378,6 +407,7 @@ def main():
     elif a.synthetic_photons:
         balanced = photons.synth_cornell_photon_map(a.photons, seed=20171203)
     setup_ms, dump_path = None, None
+    cpu_leg = a.full and world == 1 and not a.no_cpu_baseline
     if a.workload == "cornell" and not a.synthetic_photons:
         # generatePhotonMap as a whole on the GPU (FIN/main.cpp:350-402; counter RNG, seed 20171203): photon pass ->
         # compaction -> the few photons balancing would put out of LocatePhotons' reach (host) -> gather structure; identical
@@ -385,7 +415,7 @@ def main():
         # viewport.cpp:442).  Run twice: the first call also pays the one-time allocations.
         s.generate_photons(a.photons, 8, seed=20171203, device=local)
         setup_ms = s.generate_photons(a.photons, 8, seed=20171203, device=local).as_dict()
-        if world == 1 and not a.no_cpu_baseline:
+        if cpu_leg:
             # once more with the dump generatePhotonMap leaves behind (FIN/main.cpp:397-400): the CPU leg feeds it to the
             # reference's own binary
             import tempfile
@@ -434,8 +464,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     timed_counts = s.render_counters(local).as_dict() if async_steps else None     # ONE read-back behind the timed region: what the K timed frames really traced
-    if a.steps > 0:
-        frame = tuple(t.clone() for t in frame)        # the last TIMED frame (the roofline leg below renders into the same buffers)
+    frame = tuple(t.clone() for t in frame)            # the last TIMED frame (the roofline leg below renders into the same buffers)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(frame, a.dump_outputs)
 
     keys = ["rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "photon_queries", "photons_visited",
             "bvh_nodes_visited", "tris_tested", "instance_visits", "gather_rounds", "gather_slow", "gather_leaf_reads"]
@@ -454,7 +485,7 @@ def main():
     # ---- roofline leg: the same frame with ONE chunk in flight, so that event intervals are exclusive kernel times.
     # Every rank takes part (same number of renders everywhere); only rank 0's figures are quoted.
     prof = []
-    if a.profile_frames > 0:
+    if a.full and a.profile_frames > 0:
         old_streams = os.environ.get("RT_STREAMS")
         os.environ["RT_STREAMS"] = "1"
         for _ in range(a.profile_frames):
@@ -599,7 +630,7 @@ def main():
             "roofline": roof,
         }
         failed = False
-        if world == 1 and not a.no_cpu_baseline:
+        if cpu_leg:
             # the checker needs the reference's balanced heap (its LocatePhotons walks it): made from the same photons on request
             out["cpu_baseline"], kept = cpu_baseline(s.export(), s.get_photons() if n_photons else None, cam, p, a.cpu_seconds)
             out["cpu_baseline"]["as_shipped_multi_worker"] = cpu_baseline_threads(s.export(), s.get_photons() if n_photons else None, cam, p)
@@ -610,7 +641,7 @@ def main():
             # the frame that was timed is the frame that is checked: the oracle's pixels against the last timed step's image
             out["parity_check"] = parity_check(kept, frame)
             failed = not out["parity_check"]["pass"]
-        if world > 1:
+        if a.full and world > 1:
             # the gathered frame must equal what the tiles say: spot-check against rank 0's own tiles
             frgb, fz, fcnt = frame
             own = R.rgb.cpu() if rehearsal else R.rgb

@@ -243,7 +243,10 @@ def test_cpp_multi_gpu_driver_builds_against_rccl_and_fails_loudly_without_a_gpu
     with an error instead of rendering anything on the CPU"""
     exe = scenes_mod().build_dist_driver(tmp_path)
     r = subprocess.run([exe, scenes_mod().CORNELL, "64", "48", "2", "1000", str(tmp_path / "x.png")], capture_output=True, text=True)
-    assert r.returncode != 0 and "no gfx950 device" in r.stderr and not (tmp_path / "x.png").exists()
+    if capi.device_count() == 0:
+        assert r.returncode != 0 and "no gfx950 device" in r.stderr and not (tmp_path / "x.png").exists()
+    else:
+        assert r.returncode == 0 and "devices " in r.stdout and (tmp_path / "x.png").exists(), r.stderr[-2000:]
 
 
 def test_reference_side_binding_links_into_the_reference_program_and_fails_loudly_without_a_gpu(tmp_path):
@@ -258,7 +261,11 @@ def test_reference_side_binding_links_into_the_reference_program_and_fails_loudl
     for f in ("cornell.xml", "teapot_tri.obj"):
         shutil.copy(os.path.join(data, f), tmp_path / f)
     r = subprocess.run([exe, "cornell.xml", "out.bin", "32", "24"], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 5 and "no HIP device" in r.stderr and not (tmp_path / "out.bin").exists()
+    if capi.device_count() == 0:
+        assert r.returncode == 5 and "no HIP device" in r.stderr and not (tmp_path / "out.bin").exists()
+    else:
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert tuple(np.frombuffer(open(tmp_path / "out.bin", "rb").read(), np.int32, 3)) == (32, 24, 32 * 24)
 
 
 def scenes_mod():
