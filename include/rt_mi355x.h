@@ -380,6 +380,24 @@ rt_status rt_photon_pass(rt_scene *s, int device, uint32_t max_photons, int phot
 rt_status rt_caustic_pass(rt_scene *s, int device, uint32_t max_diffuse_hits, int photon_bounce, uint32_t seed,
                           rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out);
 
+/* ---- render flags (per scene; additive to ABI 4: a caller detects the feature by the presence of the
+ *      rt_scene_set_render_flags symbol, RT_ABI_VERSION and the struct sizes are unchanged) ------------------------
+ * RT_RENDER_REPRODUCIBLE: every render entry point -- rt_render_begin, rt_render_tiles_device,
+ * rt_render_tiles_packed_device, rt_shade_rays and rt_estimate_irradiance -- is a deterministic function of (scene,
+ * photon maps, camera, params, tiles).  Promised: byte-identical RGB8, z and count planes (and rt_shade_rays'
+ * hit / rgb / z) for identical inputs on the same library build, whatever the tiling, RT_CHUNK_SAMPLES, RT_STREAMS,
+ * RT_FRAME_PIPELINE, the rays that overflow k_wavefront's LDS stacks into the global queues, sync or async, job /
+ * device / packed path, and (rt_shade_rays) whichever other rays share the call.  Not promised: the same bytes as
+ * the default mode (flags 0, whose secondary contributions are float atomics in scheduling order: identical renders
+ * agree to the 2e-5 colour gate, an 8-bit channel may move by one level), nor the same bytes across builds.
+ * How: every contribution of a sample other than its primary one is added as a 32.32 fixed-point integer (integer
+ * adds are associative), and the photon gathers run without their per-cell hints; design, cost and precision: DESIGN.md
+ * sections 3 and 4.  The default is 0.  Setting touches no GPU.  Unknown bits: RT_ERR_ARG, flags unchanged.  While an
+ * rt_render_begin job on the scene is live: RT_ERR_STATE.  The flags survive scene edits; a render reads them when it
+ * is called, so asynchronous renders already enqueued keep the mode they were enqueued with. */
+#define RT_RENDER_REPRODUCIBLE 1u
+rt_status rt_scene_set_render_flags(rt_scene *s, uint32_t flags);
+rt_status rt_scene_get_render_flags(const rt_scene *s, uint32_t *flags);
 
 /* ---- rendering: replaces BeginRender/StopRender + RenderPixel + RenderImage progress
  *      (FIN/main.cpp:202-344,984-1012; FIN/include/scene.h:586-589) ---------------------- */

@@ -90,7 +90,11 @@ SYMBOLS = [
     "rt_render_tiles_device", "rt_render_tiles_packed_device", "rt_tiles_packed_size", "rt_tiles_unpack_device", "rt_render_check", "rt_render_counters", "rt_render_progress", "rt_render_stop", "rt_render_wait",
     "rt_job_stats", "rt_job_setup_ms", "rt_job_destroy", "rt_trace_rays", "rt_estimate_irradiance", "rt_shade_rays",
     "rt_scene_generate_photons", "rt_scene_set_photon_dump", "rt_scene_get_photons", "rt_photon_unreachable", "rt_photon_unreachable_device",
+    "rt_scene_set_render_flags", "rt_scene_get_render_flags",
 ]
+
+# rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
+RENDER_REPRODUCIBLE = 1
 
 
 class RtError(RuntimeError):
@@ -118,6 +122,10 @@ def lib():
         for name in SYMBOLS:
             getattr(_lib, name)          # AttributeError here = header/library mismatch
         _lib.rt_render_progress.restype = C.c_int
+        _lib.rt_scene_set_render_flags.argtypes = [C.c_void_p, C.c_uint32]
+        _lib.rt_scene_set_render_flags.restype = C.c_int
+        _lib.rt_scene_get_render_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        _lib.rt_scene_get_render_flags.restype = C.c_int
     return _lib
 
 
@@ -345,6 +353,15 @@ class Scene:
         _check(lib().rt_scene_generate_photons(self._h, int(device), C.c_uint32(int(max_photons)), int(photon_bounce), C.c_uint32(int(seed)),
                                                os.fsencode(dat_path) if dat_path else None, C.byref(ms)))
         return ms
+
+    def set_render_flags(self, flags):
+        """RENDER_REPRODUCIBLE or 0 (the default); refused while a job on this scene is live"""
+        _check(lib().rt_scene_set_render_flags(self._h, C.c_uint32(int(flags))))
+
+    def render_flags(self):
+        f = C.c_uint32()
+        _check(lib().rt_scene_get_render_flags(self._h, C.byref(f)))
+        return f.value
 
     def set_photon_dump(self, dat_path):
         _check(lib().rt_scene_set_photon_dump(self._h, os.fsencode(dat_path) if dat_path else None))

@@ -21,15 +21,20 @@
 #include "rt_dev.h"
 
 // launch wrappers defined in rt_kernels.hip
+// (the trailing `fx`: the secondary plane of a reproducible render, RT_RENDER_REPRODUCIBLE; NULL selects the default instantiations)
 void rtk_launch_primary(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &, uint32_t *,
-                        const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int, int, int, const float *, int);
+                        const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int, int, int, const float *, int,
+                        unsigned long long *fx = nullptr);
 void rtk_launch_bounce(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &,
-                       const DevRayQueue &, uint32_t *, int, int);
+                       const DevRayQueue &, uint32_t *, int, int, unsigned long long *fx = nullptr);
 void rtk_launch_trace(hipStream_t, const DevScene &, int, const float *, long long, uint8_t *, float *, float *, float *, int32_t *, uint8_t *);
 bool rtk_launch_wavefront_queue(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &, const uint32_t *,
-                                const DevRayQueue &, uint32_t *, const DevCamera &, const DevTiles &, uint32_t, int, int);
+                                const DevRayQueue &, uint32_t *, const DevCamera &, const DevTiles &, uint32_t, int, int,
+                                unsigned long long *fx = nullptr);
 void rtk_launch_gather(hipStream_t, const DevPhotonMap &, const float4 *, const float4 *, const float4 *, const uint32_t *,
-                       uint32_t, int, float, float *, float *, float *, int, unsigned long long *, int, uint32_t *, float *);
+                       uint32_t, int, float, float *, float *, float *, int, unsigned long long *, int, uint32_t *, float *,
+                       unsigned long long *fx = nullptr);
+void rtk_launch_fold_fx(hipStream_t, float *sample_rgb, unsigned long long *fx, size_t samples);
 bool rtk_wavefront_usable(const DevScene &, const rt_params &);
 void rtk_launch_resolve(hipStream_t, const DevScene &, const DevWork &, const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int,
                         float, float, int, const float *, uint8_t *, float *, uint8_t *, void *, int);
@@ -144,11 +149,12 @@ struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
 struct Workspace {
     DevBuf sample_rgb, sample_z, sample_hit, rq[2][5], pq[3], cq[3], counts, pixel_list;
     DevBuf bvh_spill;                   // traversal-stack entries beyond the kernels' LDS stacks (only for scenes whose BVHs can need them)
+    DevBuf sample_fx;                   // reproducible renders only: 3 x int64 fixed-point secondary colour per sample (allocated on first use)
     size_t samples = 0; uint32_t rq_cap = 0, pq_cap = 0;
     hipStream_t stream = nullptr;       // slot 0 runs on the caller's / the device's main stream instead
     void release()
     {
-        for (DevBuf *b : {&sample_rgb, &sample_z, &sample_hit, &counts, &pixel_list, &bvh_spill}) b->release();
+        for (DevBuf *b : {&sample_rgb, &sample_z, &sample_hit, &counts, &pixel_list, &bvh_spill, &sample_fx}) b->release();
         for (int i = 0; i < 2; i++) for (int k = 0; k < 5; k++) rq[i][k].release();
         for (int k = 0; k < 3; k++) { pq[k].release(); cq[k].release(); }
         if (stream) (void)hipStreamDestroy(stream);
@@ -236,6 +242,7 @@ struct rt_scene {
     std::mutex mu;
     std::vector<DeviceState *> devs;
     std::atomic<int> live_jobs{0};
+    std::atomic<uint32_t> render_flags{0};      // RT_RENDER_*: read once at the start of every render call
     uint32_t photon_count() const { return gen_n ? gen_n : (!photons_raw.empty() ? (uint32_t)photons_raw.size() - 1 : (data.photons.empty() ? 0u : (uint32_t)data.photons.size() - 1)); }
     void drop_generated() { photons_raw.clear(); photons_skip.clear(); gen.valid = false; gen_dev = nullptr; gen_n = 0; }
     void invalidate(bool scene, bool photons, bool caustic = false)
@@ -291,6 +298,23 @@ static rt_status check_idle(rt_scene *s, const char *who)
 {
     if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", who);
     if (s->live_jobs.load() > 0) return fail(RT_ERR_STATE, "%s: a render job is still live on this scene", who);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_set_render_flags(rt_scene *s, uint32_t flags)
+{
+    if (!s) return fail(RT_ERR_ARG, "rt_scene_set_render_flags: scene is NULL");
+    if (flags & ~(uint32_t)RT_RENDER_REPRODUCIBLE) return fail(RT_ERR_ARG, "rt_scene_set_render_flags: unknown flag bits 0x%x", flags & ~(uint32_t)RT_RENDER_REPRODUCIBLE);
+    rt_status st = check_idle(s, "rt_scene_set_render_flags");
+    if (st) return st;
+    s->render_flags.store(flags);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_get_render_flags(const rt_scene *s, uint32_t *flags)
+{
+    if (!s || !flags) return fail(RT_ERR_ARG, "rt_scene_get_render_flags: NULL argument");
+    *flags = s->render_flags.load();
     return RT_OK;
 }
 
@@ -1193,7 +1217,7 @@ static int render_streams(uint64_t n_chunks)
 // ray_factor / query_factor: queue entries per sample to provide (<= 0: the worst case, every hit spawning `fan` rays level
 // after level); an overflow is detected on the device and reported, never silent
 static rt_status ensure_workspace(DeviceState *D, int slot, size_t samples, int bounce, size_t list_pixels, int fan = 2, bool caustic = false,
-                                  double ray_factor = 0, double query_factor = 0)
+                                  double ray_factor = 0, double query_factor = 0, bool reproducible = false)
 {
     rt_status st;
     Workspace &w = D->ws[slot];
@@ -1218,6 +1242,7 @@ static rt_status ensure_workspace(DeviceState *D, int slot, size_t samples, int 
     if ((st = w.sample_rgb.ensure(samples * 12))) return st;
     if ((st = w.sample_z.ensure(samples * 4))) return st;
     if ((st = w.sample_hit.ensure(samples))) return st;
+    if (reproducible && (st = w.sample_fx.ensure(samples * 24))) return st;
     for (int i = 0; i < 2; i++) for (int k = 0; k < 5; k++) if ((st = w.rq[i][k].ensure((size_t)rq_cap * 16))) return st;
     for (int k = 0; k < 3; k++) if ((st = w.pq[k].ensure((size_t)pq_cap * 16))) return st;
     if (caustic) for (int k = 0; k < 3; k++) if ((st = w.cq[k].ensure((size_t)pq_cap * 16))) return st;
@@ -1350,7 +1375,7 @@ struct Timing { std::vector<hipEvent_t> ev; std::vector<int> cls; };
 
 static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const DevWork &W, const rt_params &P, Timing *tm,
                               const DevCamera &dc, const DevTiles &dt, uint32_t q0, uint32_t npix, int j0, int ns,
-                              int max_sample, int mode, const float *rays_dev)
+                              int max_sample, int mode, const float *rays_dev, unsigned long long *fx = nullptr)
 {
     const int max_blocks = 256 * 5;
     static_assert(256 * 5 <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
@@ -1365,8 +1390,12 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
     rt_status s;
     // queue counters for levels 0..15 and the photon queue are reset; the pixel list count survives
     HIP_TRY(hipMemsetAsync(W.counts, 0, CNT_RESET * 4, st));
+    // reproducible mode (fx != NULL): the secondary plane of the chunk's slots starts at zero with the chunk's first pass; every
+    // pass folds it into sample_rgb at its end and leaves it zero behind (k_fold_fx), which is where a second pass finds it
+    const size_t chunk_slots = (size_t)npix * (size_t)max_sample;
+    if (fx && mode != 1) HIP_TRY(hipMemsetAsync(fx, 0, chunk_slots * 24, st));
     if ((s = mark(-1))) return s;
-    rtk_launch_primary(st, D->scene, W, P, W.rq[1], W.counts + 1, dc, dt, q0, npix, j0, ns, max_sample, mode, rays_dev, max_blocks);
+    rtk_launch_primary(st, D->scene, W, P, W.rq[1], W.counts + 1, dc, dt, q0, npix, j0, ns, max_sample, mode, rays_dev, max_blocks, fx);
     if ((s = mark(0))) return s;
     // P6: a side ray is spawned when its refraction ray ARRIVES, one queue level later than a sibling
     // would be, so a path can take up to two levels per bounce
@@ -1374,26 +1403,29 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
     // k_wavefront's overflow (level-1 queue) first goes through a second k_wavefront pass; what overflows again, and the
     // models without that kernel, take one launch per level
     int first_level = 1;
-    if (max_level >= 2 && rtk_launch_wavefront_queue(st, D->scene, W, P, W.rq[1], W.counts + 1, W.rq[0], W.counts + 2, dc, dt, q0, max_sample, mode)) first_level = 2;
+    if (max_level >= 2 && rtk_launch_wavefront_queue(st, D->scene, W, P, W.rq[1], W.counts + 1, W.rq[0], W.counts + 2, dc, dt, q0, max_sample, mode, fx)) first_level = 2;
     // (further passes of the same kernel over what the second one could not keep were measured: 1 / 2 / 3 / 4 queue passes, tracer ms behind
     // the first pass, Cornell 0.34 / 0.36 / 0.40 / 0.44, C3 13.0 / 13.0 / 13.1 / 13.1 -- the second pass takes everything that matters)
     for (int level = first_level; level <= max_level && level < 15; level++)
-        rtk_launch_bounce(st, D->scene, W, P, W.rq[level & 1], W.rq[(level + 1) & 1], W.counts + level + 1, level, max_blocks);
+        rtk_launch_bounce(st, D->scene, W, P, W.rq[level & 1], W.rq[(level + 1) & 1], W.counts + level + 1, level, max_blocks, fx);
     if ((s = mark(1))) return s;
     rt_status cs;
     if ((cs = ensure_cell_start(D, false, P.knn_k, P.knn_radius, st))) return cs;
     if (D->scene.pm.n_leaves) {
         rtk_launch_gather(st, D->scene.pm, W.pq.qa, W.pq.qb, W.pq.qc, W.counts + CNT_PHOTONQ, W.pq.cap, P.knn_k, P.knn_radius,
-                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT, (float *)D->cell_rk2.p);
+                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT, fx ? nullptr : (float *)D->cell_rk2.p, fx);
         if ((s = mark(2))) return s;
     }
     if (D->scene.cm.n_leaves && P.caustic_k > 0 && W.cq.cap && (cs = ensure_cell_start(D, true, P.caustic_k, P.caustic_radius, st))) return cs;
     if (D->scene.cm.n_leaves && P.caustic_k > 0 && W.cq.cap) {
         // the P13-family models queued their caustic lookups separately: same kernel on the second map
         rtk_launch_gather(st, D->scene.cm, W.cq.qa, W.cq.qb, W.cq.qc, W.counts + CNT_CAUSTICQ, W.cq.cap, P.caustic_k, P.caustic_radius,
-                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT2, (float *)D->ccell_rk2.p);
+                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT2, fx ? nullptr : (float *)D->ccell_rk2.p, fx);
         if ((s = mark(2))) return s;
     }
+    // reproducible mode: the per-cell hints above are off (they pick which of two exact paths, with two summation orders, a query
+    // takes, from whichever query of the cell was answered last); the secondary plane goes into the samples before k_resolve
+    if (fx) rtk_launch_fold_fx(st, W.sample_rgb, fx, chunk_slots);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -1512,7 +1544,10 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         }
     }
     D->qhist_used = ray_factor > 0 || query_factor > 0;
+    // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
+    const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
     DevWork Ws[RT_STREAMS];
+    unsigned long long *Fx[RT_STREAMS] = {};
     int n_ready = 0;
     for (int i = 0; i < n_slots; i++) {
         if (i > 0 && D->ws[i].samples < (size_t)ppc * p->max_sample) {
@@ -1524,8 +1559,10 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                                  3 * D->ws[0].pq[0].bytes;
             if (free_b < first + first / 4 + (total_b >> 3)) break;
         }
-        if ((st = ensure_workspace(D, i, (size_t)ppc * p->max_sample, p->bounce, (size_t)ppc, fan, use_caustic, ray_factor, query_factor))) return st;
+        if ((st = ensure_workspace(D, i, (size_t)ppc * p->max_sample, p->bounce, (size_t)ppc, fan, use_caustic, ray_factor, query_factor,
+                                   reproducible))) return st;
         Ws[i] = make_work(D, i);
+        if (reproducible) Fx[i] = (unsigned long long *)D->ws[i].sample_fx.p;
         n_ready++;
     }
     n_slots = n_ready;
@@ -1654,7 +1691,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         Timing *tmp = want_stats ? &tm[slot] : nullptr;
         const uint32_t npix = (uint32_t)std::min<uint64_t>(ppc, total_px - q0);
         HIP_TRY(hipMemsetAsync(W.counts + CNT_PIXLIST, 0, 4, cs));
-        if ((st = run_pipeline(D, slot, cs, W, *p, tmp, dc, dt, (uint32_t)q0, npix, 0, p->min_sample, p->max_sample, 0, nullptr))) return st;
+        if ((st = run_pipeline(D, slot, cs, W, *p, tmp, dc, dt, (uint32_t)q0, npix, 0, p->min_sample, p->max_sample, 0, nullptr, Fx[slot]))) return st;
         auto timed_resolve = [&](int phase) -> rt_status {
             hipEvent_t r0 = nullptr, r1 = nullptr;
             if (want_stats) { HIP_TRY(hipEventCreate(&r0)); HIP_TRY(hipEventCreate(&r1)); HIP_TRY(hipEventRecord(r0, cs)); }
@@ -1667,7 +1704,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         if ((st = timed_resolve(0))) return st;
         if (p->max_sample > p->min_sample) {
             if ((st = run_pipeline(D, slot, cs, W, *p, tmp, dc, dt, (uint32_t)q0, npix, p->min_sample,
-                                   p->max_sample - p->min_sample, p->max_sample, 1, nullptr))) return st;
+                                   p->max_sample - p->min_sample, p->max_sample, 1, nullptr, Fx[slot]))) return st;
             if ((st = timed_resolve(1))) return st;
         }
         HIP_TRY(hipGetLastError());
@@ -2057,8 +2094,10 @@ extern "C" rt_status rt_shade_rays(rt_scene *s, const rt_params *p, int device, 
     if ((st = order_after_pending(D, D->stream))) return st;
     const size_t limit = chunk_samples_limit(true);
     const size_t chunk = (size_t)std::min<int64_t>(n, (int64_t)limit);
-    if ((st = ensure_workspace(D, 0, chunk, pv.bounce, 1, 2, pv.caustic_k > 0 && D->scene.cm.n_leaves != 0))) return st;
+    const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
+    if ((st = ensure_workspace(D, 0, chunk, pv.bounce, 1, 2, pv.caustic_k > 0 && D->scene.cm.n_leaves != 0, 0, 0, reproducible))) return st;
     const DevWork W = make_work(D, 0);
+    unsigned long long *fx = reproducible ? (unsigned long long *)D->ws[0].sample_fx.p : nullptr;     // run_pipeline folds it before the copy back
     DevCamera dc; camera_setup(cam, dc);
     DevTiles dt; memset(&dt, 0, sizeof dt);
     HIP_TRY(stats_zero(W.stats, 0, ST_COUNT, D->stream));
@@ -2067,7 +2106,7 @@ extern "C" rt_status rt_shade_rays(rt_scene *s, const rt_params *p, int device, 
         if ((st = D->t_in.upload(rays + 6 * off, (size_t)m * 24))) return st;
         HIP_TRY(hipMemsetAsync(W.sample_hit, 0, m, D->stream));
         HIP_TRY(hipMemsetAsync(W.sample_rgb, 0, (size_t)m * 12, D->stream));
-        if ((st = run_pipeline(D, 0, D->stream, W, pv, nullptr, dc, dt, (uint32_t)off, m, 0, 1, 1, 2, (const float *)D->t_in.p))) return st;
+        if ((st = run_pipeline(D, 0, D->stream, W, pv, nullptr, dc, dt, (uint32_t)off, m, 0, 1, 1, 2, (const float *)D->t_in.p, fx))) return st;
         HIP_TRY(hipStreamSynchronize(D->stream));
         HIP_TRY(hipMemcpy(hit + off, W.sample_hit, m, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(rgb + 3 * off, W.sample_rgb, (size_t)m * 12, hipMemcpyDeviceToHost));

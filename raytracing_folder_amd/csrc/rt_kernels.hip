@@ -574,6 +574,9 @@ struct ShadeCtx {
     // full.  NULL in the per-level kernels.
     float4 *lds_a, *lds_b, *lds_c; uint32_t *lds_count; uint32_t lds_cap;
     SlotMap sm;
+    // reproducible instantiations only (FX = true): the secondary plane, three int64 fixed-point values per sample (fx_encode);
+    // last member, so that the default instantiations' argument layout does not move
+    unsigned long long *fx;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -750,10 +753,29 @@ __device__ V3 illuminate(const DevScene &S, const rt_params &P, const rt_light &
     return (I * shadow) / len2(p - position);
 }
 
+// Reproducible mode (RT_RENDER_REPRODUCIBLE): a contribution that is not a sample's primary one goes into the secondary plane as
+// a 32.32 fixed-point integer, rounded to nearest-even, saturated at +-2^31, NaN as 0.  Integer adds are associative, so the
+// sum does not depend on the order the atomics arrive in; the plane is folded into sample_rgb once per pass (k_fold_fx).
+#define RT_FX_ONE 4294967296.0f          /* 2^32: 32 fractional bits */
+__device__ __forceinline__ unsigned long long fx_encode(float c)
+{
+    const float x = rintf(c * RT_FX_ONE);                 // exact scaling (a power of two), then round to an integer
+    if (!(x == x)) return 0ull;
+    if (x >= 9223372036854775807.0f) return 0x7FFFFFFFFFFFFFFFull;       // 2^63 as a float
+    if (x <= -9223372036854775808.0f) return 0x8000000000000000ull;
+    return (unsigned long long)(long long)x;
+}
+__device__ __forceinline__ void fx_add(unsigned long long *dst, float r, float g, float b)
+{
+    atomicAdd(dst, fx_encode(r)); atomicAdd(dst + 1, fx_encode(g)); atomicAdd(dst + 2, fx_encode(b));    // global_atomic_add_u64
+}
+
+template <bool FX = false>
 __device__ __forceinline__ void add_sample(const ShadeCtx &C, uint32_t slot, V3 c, bool primary)
 {
     float *dst = C.W.sample_rgb + 3 * (size_t)slot;
     if (primary) { dst[0] = c.x; dst[1] = c.y; dst[2] = c.z; }
+    else if constexpr (FX) fx_add(C.fx + 3 * (size_t)slot, c.x, c.y, c.z);
     else { atomicAdd(dst, c.x); atomicAdd(dst + 1, c.y); atomicAdd(dst + 2, c.z); }
 }
 
@@ -1146,7 +1168,7 @@ __device__ void shade_p6(const DevScene &S, const rt_params &P, const Hit &h, V3
 // factors above it and adds thr*local colour to its sample; the part of a child's K that depends on
 // the child's own hit (FIN: Attenuation(parent absorption, z) on a back-face hit, FIN/main.cpp:620,
 // 632; P13: exp(-absorption.r*z) on the refraction child, P13/main.cpp:728) is applied on arrival.
-template <int MODEL, bool TEX>
+template <int MODEL, bool TEX, bool FX = false>
 __device__ void shade_path(const ShadeCtx &C, const PathIn &in, bool active, const BvhStack &stack, Counters &cnt)
 {
     const DevScene &S = C.S;
@@ -1178,7 +1200,7 @@ __device__ void shade_path(const ShadeCtx &C, const PathIn &in, bool active, con
         if (in.primary) C.W.sample_hit[in.slot] = 0;
         // a refraction ray that leaves the scene sees the environment (FIN/main.cpp:635); in P13 so
         // does a reflection ray (P13/main.cpp:660-662)
-        else if (!p6 && !p3 && (in.kind != KIND_REFLECT || p13)) add_sample(C, in.slot, thr * environment_color<TEX>(S, in.d), false);
+        else if (!p6 && !p3 && (in.kind != KIND_REFLECT || p13)) add_sample<FX>(C, in.slot, thr * environment_color<TEX>(S, in.d), false);
     }
     if (active && hit) {
         if (in.primary) { C.W.sample_hit[in.slot] = 1; C.W.sample_z[in.slot] = h.z; }
@@ -1187,7 +1209,7 @@ __device__ void shade_path(const ShadeCtx &C, const PathIn &in, bool active, con
         else if (p6) shade_p6<TEX>(S, P, h, in.d, in.bounce, rc, o, stack, cnt);
         else if (p13) shade_p13<MODEL, TEX>(S, P, h, in.d, in.bounce, rc, o, stack, cnt, in.spec);
         else shade_fin<TEX>(S, P, h, in.d, in.bounce, rc, o, stack, cnt);
-        add_sample(C, in.slot, thr * o.color, in.primary);
+        add_sample<FX>(C, in.slot, thr * o.color, in.primary);
         // a child (or query) whose accumulated weight is exactly zero cannot change the pixel
         const V3 wr = thr * o.rK, wt = thr * o.tK, wp = thr * o.kd;
         o.want_refl = o.want_refl && (wr.x != 0.f || wr.y != 0.f || wr.z != 0.f);
@@ -1350,7 +1372,7 @@ __device__ __forceinline__ bool primary_setup(const ShadeCtx &C, const PrimaryAr
 }
 
 #define RT_TRACE_OCC __attribute__((amdgpu_waves_per_eu(TEX ? 2 : 3)))
-template <int MODEL, bool TEX>
+template <int MODEL, bool TEX, bool FX = false>
 RT_TRACE_OCC __global__ __launch_bounds__(RT_BLOCK) void k_primary(ShadeCtx C, PrimaryArgs A)
 {
     __shared__ uint32_t s_stack[RT_BVH_STACK * RT_BLOCK];
@@ -1371,13 +1393,13 @@ RT_TRACE_OCC __global__ __launch_bounds__(RT_BLOCK) void k_primary(ShadeCtx C, P
         PathIn in;
         const bool active = primary_setup(C, A, base + threadIdx.x, total, h_table, s_h2, s_h3, in);
         if (active) nprim++;
-        shade_path<MODEL, TEX>(C, in, active, stack, cnt);
+        shade_path<MODEL, TEX, FX>(C, in, active, stack, cnt);
     }
     flush_counters(C.W.stats, cnt, nprim, 0, 0);
 }
 
 // K2-K4 for one level of the ray tree: reads queue `qin` (count in counts[level]).
-template <int MODEL, bool TEX>
+template <int MODEL, bool TEX, bool FX = false>
 RT_TRACE_OCC __global__ __launch_bounds__(RT_BLOCK) void k_bounce(ShadeCtx C, DevRayQueue qin, int level)
 {
     __shared__ uint32_t s_stack[RT_BVH_STACK * RT_BLOCK];
@@ -1408,7 +1430,7 @@ RT_TRACE_OCC __global__ __launch_bounds__(RT_BLOCK) void k_bounce(ShadeCtx C, De
             }
             if (in.kind == KIND_REFLECT) nrefl++; else nrefr++;
         }
-        shade_path<MODEL, TEX>(C, in, active, stack, cnt);
+        shade_path<MODEL, TEX, FX>(C, in, active, stack, cnt);
     }
     flush_counters(C.W.stats, cnt, 0, nrefl, nrefr);
 }
@@ -1461,7 +1483,7 @@ __device__ __forceinline__ uint32_t sample_of_slot(const SlotMap &M, uint32_t sl
     pixel_of(M.tiles, cam, M.q0 + ql, x, y);
     return ((uint32_t)y * (uint32_t)M.width + (uint32_t)x) * (uint32_t)M.max_sample + j;
 }
-template <int MODEL, bool TEX>
+template <int MODEL, bool TEX, bool FX = false>
 __attribute__((amdgpu_waves_per_eu(TEX ? RT_WF_TEX_WAVES : RT_WF_WAVES, TEX ? RT_WF_TEX_WAVES : RT_WF_WAVES))) __global__ __launch_bounds__(RT_BLOCK) void k_wavefront(ShadeCtx C, PrimaryArgs A)
 {
     using Cfg = WfCfg<TEX>;
@@ -1555,7 +1577,7 @@ __attribute__((amdgpu_waves_per_eu(TEX ? RT_WF_TEX_WAVES : RT_WF_WAVES, TEX ? RT
             }
         }
         wsync();                                          // the count is settled before this round's pushes
-        shade_path<MODEL, TEX>(C, in, active, stack, cnt);
+        shade_path<MODEL, TEX, FX>(C, in, active, stack, cnt);
     }
     flush_counters(C.W.stats, cnt, nprim, nrefl, nrefr);
   } else {
@@ -1652,7 +1674,7 @@ __attribute__((amdgpu_waves_per_eu(TEX ? RT_WF_TEX_WAVES : RT_WF_WAVES, TEX ? RT
             }
         }
         __syncthreads();                                  // s_count settled before this round's pushes
-        shade_path<MODEL, TEX>(C, in, active, stack, cnt);
+        shade_path<MODEL, TEX, FX>(C, in, active, stack, cnt);
     }
     flush_counters(C.W.stats, cnt, nprim, nrefl, nrefr);
   }
@@ -1917,6 +1939,7 @@ struct GatherArgs {
     int mode;
     unsigned long long *stats;
     float *cell_rk2;                 // per density-grid cell: the k-th squared distance of the last query answered there (0 = none yet); may be NULL
+    unsigned long long *fx;          // reproducible instantiation, mode 0: deposit into this secondary plane (fx_add) instead of sample_rgb
 };
 
 // Wave-wide inclusive scans on the DPP path (row_shr 1/2/4/8 inside each row of 16 lanes, then
@@ -2114,6 +2137,7 @@ __device__ __forceinline__ void scan_subleaves(const DevPhotonMap &pm, const uin
 #ifndef RT_GATHER_WAVES_PER_EU
 #define RT_GATHER_WAVES_PER_EU 5     // 96 registers: five waves per SIMD is what the LDS footprint allows too
 #endif
+template <bool FX = false>
 __attribute__((amdgpu_waves_per_eu(RT_GATHER_WAVES_PER_EU, RT_GATHER_WAVES_PER_EU)))
 __global__ __launch_bounds__(64 * RT_GATHER_WAVES) void k_gather(GatherArgs G)
 {
@@ -2588,10 +2612,13 @@ __global__ __launch_bounds__(64 * RT_GATHER_WAVES) void k_gather(GatherArgs G)
                     const uint32_t slot = __float_as_uint(c.y);
                     float theta = nx * (-dx) + ny * (-dy) + nz * (-dz);
                     theta = theta > 0.0f ? theta : 0.0f;
-                    float *dst = G.sample_rgb + 3 * (size_t)slot;
-                    atomicAdd(dst, (wr * irr_r) * theta);
-                    atomicAdd(dst + 1, (wg * irr_g) * theta);
-                    atomicAdd(dst + 2, (wb * irr_b) * theta);
+                    if constexpr (FX) fx_add(G.fx + 3 * (size_t)slot, (wr * irr_r) * theta, (wg * irr_g) * theta, (wb * irr_b) * theta);
+                    else {
+                        float *dst = G.sample_rgb + 3 * (size_t)slot;
+                        atomicAdd(dst, (wr * irr_r) * theta);
+                        atomicAdd(dst + 1, (wg * irr_g) * theta);
+                        atomicAdd(dst + 2, (wb * irr_b) * theta);
+                    }
                 }
                 finish = false;
             }
@@ -2840,12 +2867,31 @@ bool rtk_wavefront_usable(const DevScene &S, const rt_params &P)
     return wavefront_usable(S, P, S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE);
 }
 
+// the instantiation of k_wavefront for (model, textures, reproducible mode)
+template <int MODEL>
+static void launch_wavefront_model(hipStream_t st, bool tex, bool fx, int wgrid, const ShadeCtx &C, const PrimaryArgs &A)
+{
+    if (fx) {
+        if (tex) hipLaunchKernelGGL((k_wavefront<MODEL, true, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
+        else hipLaunchKernelGGL((k_wavefront<MODEL, false, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
+    } else {
+        if (tex) hipLaunchKernelGGL((k_wavefront<MODEL, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
+        else hipLaunchKernelGGL((k_wavefront<MODEL, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
+    }
+}
+static void launch_wavefront(hipStream_t st, int model, bool tex, bool fx, int wgrid, const ShadeCtx &C, const PrimaryArgs &A)
+{
+    if (model == RT_SHADE_FIN) launch_wavefront_model<RT_SHADE_FIN>(st, tex, fx, wgrid, C, A);
+    else if (model == RT_SHADE_P12) launch_wavefront_model<RT_SHADE_P12>(st, tex, fx, wgrid, C, A);
+    else launch_wavefront_model<RT_SHADE_P13>(st, tex, fx, wgrid, C, A);
+}
+
 void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
                         const DevRayQueue &qout, uint32_t *qout_count, const DevCamera &cam,
                         const DevTiles &tiles, uint32_t q0, uint32_t npix, int j0, int ns,
-                        int max_sample, int mode, const float *rays, int max_blocks)
+                        int max_sample, int mode, const float *rays, int max_blocks, unsigned long long *fx)
 {
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count;
+    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
     PrimaryArgs A; A.cam = cam; A.tiles = tiles; A.q0 = q0; A.npix = npix; A.j0 = j0; A.ns = ns;
     A.max_sample = max_sample; A.mode = mode; A.rays = rays; A.lds_rays = wf_lds_rays();
     tiles_prepare(A.tiles);
@@ -2858,19 +2904,12 @@ void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, con
     // launch per level of the tree (round 1's structure, kept for the other models and for A/B: DESIGN.md section 3)
     if (wavefront_usable(S, P, tex)) {
         const int wgrid = grid_for((unsigned long long)npix * ns, RT_BLOCK, 256 * (tex ? RT_WF_TEX_WAVES : RT_WF_WAVES));      // resident workgroups per CU (LDS)
-        if (P.shade_model == RT_SHADE_FIN) {
-            if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_FIN, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-            else hipLaunchKernelGGL((k_wavefront<RT_SHADE_FIN, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        } else if (P.shade_model == RT_SHADE_P12) {
-            if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_P12, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-            else hipLaunchKernelGGL((k_wavefront<RT_SHADE_P12, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        } else {
-            if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_P13, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-            else hipLaunchKernelGGL((k_wavefront<RT_SHADE_P13, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        }
+        launch_wavefront(st, P.shade_model, tex, fx != nullptr, wgrid, C, A);
         return;
     }
-#define RT_LAUNCH_PRIMARY(M) do { if (tex) hipLaunchKernelGGL((k_primary<M, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); \
+#define RT_LAUNCH_PRIMARY(M) do { if (fx) { if (tex) hipLaunchKernelGGL((k_primary<M, true, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); \
+                                            else hipLaunchKernelGGL((k_primary<M, false, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); } \
+                                  else if (tex) hipLaunchKernelGGL((k_primary<M, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); \
                                   else hipLaunchKernelGGL((k_primary<M, false>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); } while (0)
     switch (P.shade_model) {
     case RT_SHADE_P13: RT_LAUNCH_PRIMARY(RT_SHADE_P13); break;
@@ -2887,13 +2926,13 @@ void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, con
 // launches).  Returns false when the model has no wavefront kernel (the caller then starts the level launches at qin).
 bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
                                 const DevRayQueue &qin, const uint32_t *qin_count, const DevRayQueue &qout, uint32_t *qout_count,
-                                const DevCamera &cam, const DevTiles &tiles, uint32_t q0, int max_sample, int mode)
+                                const DevCamera &cam, const DevTiles &tiles, uint32_t q0, int max_sample, int mode, unsigned long long *fx)
 {
     static int queue_pass = -1;
     if (queue_pass < 0) { const char *q = getenv("RT_WF_QUEUE_PASS"); queue_pass = (q && q[0] == '0') ? 0 : 1; }
     const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
     if (!queue_pass || !wavefront_usable(S, P, tex)) return false;
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count;
+    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
     C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
     DevTiles tp = tiles;
     tiles_prepare(tp);
@@ -2903,28 +2942,21 @@ bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork
     A.mode = 3; A.ns = 1; A.qsrc = qin; A.qsrc_count = qin_count; A.lds_rays = wf_lds_rays();
     A.div_ns = fastdiv_make(1u);
     const int wgrid = 256 * (tex ? RT_WF_TEX_WAVES : RT_WF_WAVES);       // the count is on the device: a full persistent grid, idle workgroups leave at once
-    if (P.shade_model == RT_SHADE_FIN) {
-        if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_FIN, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        else hipLaunchKernelGGL((k_wavefront<RT_SHADE_FIN, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-    } else if (P.shade_model == RT_SHADE_P12) {
-        if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_P12, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        else hipLaunchKernelGGL((k_wavefront<RT_SHADE_P12, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-    } else {
-        if (tex) hipLaunchKernelGGL((k_wavefront<RT_SHADE_P13, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        else hipLaunchKernelGGL((k_wavefront<RT_SHADE_P13, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-    }
+    launch_wavefront(st, P.shade_model, tex, fx != nullptr, wgrid, C, A);
     return true;
 }
 
 void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
                        const DevRayQueue &qin, const DevRayQueue &qout, uint32_t *qout_count,
-                       int level, int max_blocks)
+                       int level, int max_blocks, unsigned long long *fx)
 {
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count;
+    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
     C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
     memset(&C.sm, 0, sizeof C.sm);
     const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
-#define RT_LAUNCH_BOUNCE(M) do { if (tex) hipLaunchKernelGGL((k_bounce<M, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); \
+#define RT_LAUNCH_BOUNCE(M) do { if (fx) { if (tex) hipLaunchKernelGGL((k_bounce<M, true, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); \
+                                           else hipLaunchKernelGGL((k_bounce<M, false, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); } \
+                                 else if (tex) hipLaunchKernelGGL((k_bounce<M, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); \
                                  else hipLaunchKernelGGL((k_bounce<M, false>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); } while (0)
     switch (P.shade_model) {
     case RT_SHADE_P13: RT_LAUNCH_BOUNCE(RT_SHADE_P13); break;
@@ -2948,11 +2980,31 @@ void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float 
 void rtk_launch_gather(hipStream_t st, const DevPhotonMap &pm, const float4 *qa, const float4 *qb,
                        const float4 *qc, const uint32_t *count_ptr, uint32_t count_cap, int k,
                        float radius, float *sample_rgb, float *out_irr, float *out_dir, int mode,
-                       unsigned long long *stats, int blocks, uint32_t *next_batch, float *cell_rk2)
+                       unsigned long long *stats, int blocks, uint32_t *next_batch, float *cell_rk2, unsigned long long *fx)
 {
-    GatherArgs G; G.pm = pm; G.cell_rk2 = cell_rk2; G.qa = qa; G.qb = qb; G.qc = qc; G.count_ptr = count_ptr; G.count_cap = count_cap;
+    GatherArgs G; G.pm = pm; G.cell_rk2 = cell_rk2; G.fx = fx; G.qa = qa; G.qb = qb; G.qc = qc; G.count_ptr = count_ptr; G.count_cap = count_cap;
     G.k = k; G.radius = radius; G.sample_rgb = sample_rgb; G.out_irr = out_irr; G.out_dir = out_dir; G.mode = mode; G.stats = stats; G.next_batch = next_batch;
-    hipLaunchKernelGGL(k_gather, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
+    if (fx && mode == 0) hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
+    else hipLaunchKernelGGL(k_gather<false>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
+}
+
+// Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
+// Slots the pass did not touch hold zero in the plane and are left alone.
+__global__ __launch_bounds__(256) void k_fold_fx(float *sample_rgb, unsigned long long *fx, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const long long q = (long long)fx[i];
+        if (q == 0) continue;
+        sample_rgb[i] += (float)((double)q * (1.0 / 4294967296.0));
+        fx[i] = 0ull;
+    }
+}
+
+void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *fx, size_t samples)
+{
+    const size_t n = 3 * samples;
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 256 * 8);
+    hipLaunchKernelGGL(k_fold_fx, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, sample_rgb, fx, n);
 }
 
 // Un-interleave an all-gathered frame: rank r contributed its tiles r, r+R, r+2R, ... as `per_rank` packed tiles of
