@@ -305,6 +305,13 @@ rt_status rt_image_write_png(const char *path, const uint8_t *data, int32_t w, i
  * integer 255*(c-smin)/(smax-smin), all zero when smax == smin).  Bit-exact integer maps; *smax (may be
  * NULL) receives ComputeSampleCountImage's return value.  Host code, no GPU involved. */
 rt_status rt_image_zbuffer(const float *zbuffer, int32_t w, int32_t h, uint8_t *zbuffer_img);
+/* The linear plane as a file (additive to ABI 4): PFM, 3 channels ("PF\n<w> <h>\n-1.0\n", then little-endian f32 RGB
+ * triples, scanlines stored BOTTOM to top as the format requires).  rgb is row-major, row 0 = top, like every image here.
+ * rt_image_read_pfm accepts either sign of the scale (negative: little-endian, positive: big-endian samples); rgb == NULL
+ * only reports the size; cap counts floats (3*w*h needed).  A malformed or truncated file is RT_ERR_IO, a too small cap
+ * RT_ERR_ARG. */
+rt_status rt_image_write_pfm(const char *path, const float *rgb, int32_t w, int32_t h);
+rt_status rt_image_read_pfm(const char *path, int32_t *w, int32_t *h, float *rgb, uint64_t cap);
 rt_status rt_image_sample_count(const uint8_t *sample_count, int32_t w, int32_t h, uint8_t *sample_count_img, int32_t *smax);
 
 /* generatePhotonMap as a whole (FIN/main.cpp:350-402) on the GPU: the photon pass (rt_photon_pass), ScalePhotonPowers,
@@ -443,6 +450,36 @@ rt_status rt_tiles_packed_size(int32_t width, int32_t height, const rt_tile_rang
 rt_status rt_tiles_unpack_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
                                  int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
                                  uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev);
+
+/* ---- the linear plane (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs are
+ *      unchanged) -----------------------------------------------------------------------------------------------------
+ * An optional fourth output: float rgb_linear[width*height*3], row-major like rgb8, the pixel's colour BEFORE gamma.
+ *   - a pixel with n >= 1 hit samples: the float32 average k_resolve computes, c += rgb_j * (1/(float)n) over the hit
+ *     samples in sample order, with the same n and batch as the other planes (the first min_sample samples, or all
+ *     max_sample for pixels the variance gate sent to the second batch).  On the device
+ *     rgb8 == Color24(powf(rgb_linear, (float)(1.0/gamma))) by construction.
+ *   - an all-miss pixel: the linear background, background.Sample(x/W, y/H) (FIN/main.cpp:326-328).
+ *   - pixels of tiles the call does not own, and of chunks not reached before rt_render_stop, keep the caller's values.
+ *   - RT_RENDER_REPRODUCIBLE: byte-identical for identical inputs whatever the chunking, streams, tiling, sync / async and
+ *     entry point; in the default mode it inherits the float-atomic last-ulp variation of the samples.
+ *   - asking for it changes nothing in the other three planes (under RT_RENDER_REPRODUCIBLE: the same bytes as without).
+ * The _linear entry points are the ones above with the plane added; a NULL rgb_linear is RT_ERR_ARG.  Nothing is allocated
+ * for the plane unless it is asked for.
+ * Packed (_packed_linear_device / rt_tiles_unpack_linear_device): ONE 24-byte record per pixel at packed_dev + 24*q --
+ * bytes 0-7 the 8-byte record of rt_render_tiles_packed_device, bytes 8-19 linear r, g, b as little-endian f32, bytes 20-23
+ * zero; ragged-tile slots outside the image are all zero.  packed_bytes must be at least 3 x what rt_tiles_packed_size
+ * reports. */
+rt_status rt_render_begin_linear(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                 uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out);
+rt_status rt_render_tiles_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                        int device, void *hip_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
+                                        float *rgb_linear_dev, int sync, rt_stats *stats_out);
+rt_status rt_render_tiles_packed_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                               int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, int sync,
+                                               rt_stats *stats_out);
+rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
+                                        int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
+                                        uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev);
 /* Waits for the asynchronous renders (sync == 0) issued so far on (scene, device) and returns
  * RT_ERR_LIMIT if any of them dropped rays or photon queries, RT_OK otherwise. */
 rt_status rt_render_check(rt_scene *s, int device);

@@ -91,6 +91,8 @@ SYMBOLS = [
     "rt_job_stats", "rt_job_setup_ms", "rt_job_destroy", "rt_trace_rays", "rt_estimate_irradiance", "rt_shade_rays",
     "rt_scene_generate_photons", "rt_scene_set_photon_dump", "rt_scene_get_photons", "rt_photon_unreachable", "rt_photon_unreachable_device",
     "rt_scene_set_render_flags", "rt_scene_get_render_flags",
+    "rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device", "rt_tiles_unpack_linear_device",
+    "rt_image_write_pfm", "rt_image_read_pfm",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -126,6 +128,17 @@ def lib():
         _lib.rt_scene_set_render_flags.restype = C.c_int
         _lib.rt_scene_get_render_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.rt_scene_get_render_flags.restype = C.c_int
+        # the linear plane (rt_mi355x.h: "the linear plane")
+        vp, i32 = C.c_void_p, C.c_int32
+        _lib.rt_render_begin_linear.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        _lib.rt_render_tiles_linear_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+        _lib.rt_render_tiles_packed_linear_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_uint64, C.c_int, vp]
+        _lib.rt_tiles_unpack_linear_device.argtypes = [C.c_int, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+        _lib.rt_image_write_pfm.argtypes = [C.c_char_p, vp, i32, i32]
+        _lib.rt_image_read_pfm.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), vp, C.c_uint64]
+        for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
+                     "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm"):
+            getattr(_lib, name).restype = C.c_int
     return _lib
 
 
@@ -204,18 +217,41 @@ def sample_count_image(cnt):
     return out, smax.value
 
 
-def tiles_packed_size(width, height, tiles):
+def tiles_packed_size(width, height, tiles, linear=False):
+    """(bytes, tiles) of this call's packed records: 8 bytes per tile pixel, 24 with the linear plane (linear=True)"""
     nbytes, n = C.c_uint64(), C.c_int32()
     _check(lib().rt_tiles_packed_size(int(width), int(height), C.byref(tiles), C.byref(nbytes), C.byref(n)))
-    return nbytes.value, n.value
+    return nbytes.value * (3 if linear else 1), n.value
 
 
-def tiles_unpack_device(device, stream, gathered_ptr, world, tiles_per_rank, width, height, tile_w, tile_h, rgb_ptr, z_ptr, cnt_ptr):
+def tiles_unpack_device(device, stream, gathered_ptr, world, tiles_per_rank, width, height, tile_w, tile_h, rgb_ptr, z_ptr, cnt_ptr,
+                        linear_ptr=None):
     """gathered packed tiles of `world` ranks -> RenderImage planes, one HIP kernel on `stream` (an explicit stream's
-    handle; None = the null stream of the device)"""
+    handle; None = the null stream of the device).  linear_ptr: the records are 24-byte ones and the linear plane
+    (float32 (H, W, 3)) is written there too."""
     handle = _stream_handle(stream)
-    _check(lib().rt_tiles_unpack_device(int(device), handle, C.c_void_p(gathered_ptr), int(world), int(tiles_per_rank), int(width),
-                                        int(height), int(tile_w), int(tile_h), C.c_void_p(rgb_ptr), C.c_void_p(z_ptr), C.c_void_p(cnt_ptr)))
+    args = (int(device), handle, C.c_void_p(gathered_ptr), int(world), int(tiles_per_rank), int(width), int(height), int(tile_w),
+            int(tile_h), C.c_void_p(rgb_ptr), C.c_void_p(z_ptr), C.c_void_p(cnt_ptr))
+    if linear_ptr is None:
+        _check(lib().rt_tiles_unpack_device(*args))
+    else:
+        _check(lib().rt_tiles_unpack_linear_device(*args, C.c_void_p(linear_ptr)))
+
+
+def image_write_pfm(path, rgb):
+    """float (H, W, 3) -> PFM (little-endian, scanlines bottom to top)"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    _check(lib().rt_image_write_pfm(os.fsencode(path), _p(rgb), rgb.shape[1], rgb.shape[0]))
+
+
+def image_read_pfm(path):
+    """a 3-channel PFM -> float32 (H, W, 3), row 0 = top"""
+    w, h = C.c_int32(), C.c_int32()
+    _check(lib().rt_image_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), None, 0))
+    rgb = np.zeros((h.value, w.value, 3), np.float32)
+    _check(lib().rt_image_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), _p(rgb), rgb.size))
+    return rgb
 
 
 def identity_map(texture=MAP_NONE):
@@ -474,6 +510,16 @@ class Scene:
         """Blocking render through the asynchronous job API (rt_render_begin + rt_render_wait).  photon_pass=False (the
         tests' default) renders the scene's photon map as it is: params.photon_count is taken as 0 for this call;
         photon_pass=True leaves it alone, so that rt_render_begin first runs generatePhotonMap like BeginRender does."""
+        return self._render(cam, params, tiles, device, photon_pass, None)
+
+    def render_linear(self, cam, params, tiles=None, device=0, photon_pass=False, fill=0.0):
+        """render() plus the linear (pre-gamma) float RGB plane, through rt_render_begin_linear:
+        (rgb, z, cnt, linear (H, W, 3) float32, stats, progress).  Pixels outside `tiles` keep `fill`."""
+        linear = np.full((cam.height, cam.width, 3), fill, np.float32)
+        rgb, z, cnt, st, progress = self._render(cam, params, tiles, device, photon_pass, linear)
+        return rgb, z, cnt, linear, st, progress
+
+    def _render(self, cam, params, tiles, device, photon_pass, linear):
         if not photon_pass and params.photon_count != 0:
             q = Params()
             C.memmove(C.byref(q), C.byref(params), C.sizeof(Params))
@@ -483,8 +529,12 @@ class Scene:
         rgb, z, cnt = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32), np.zeros((h, w), np.uint8)
         tiles = tiles or TileRange(32, 8, 0, 1)
         job = C.c_void_p()
-        _check(lib().rt_render_begin(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
-                                     _p(rgb), _p(z), _p(cnt), C.byref(job)))
+        if linear is None:
+            _check(lib().rt_render_begin(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                         _p(rgb), _p(z), _p(cnt), C.byref(job)))
+        else:
+            _check(lib().rt_render_begin_linear(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                _p(rgb), _p(z), _p(cnt), _p(linear), C.byref(job)))
         try:
             _check(lib().rt_render_wait(job))
             st = Stats()
@@ -495,13 +545,15 @@ class Scene:
         return rgb, z, cnt, st, progress
 
     def render_tiles_packed_device(self, cam, params, tiles, device, packed_ptr, packed_bytes, stream=None, sync=True,
-                                   want_stats=True):
-        """This call's tiles as packed 8-byte pixel records (the all-gather contribution of a rank), see the header."""
+                                   want_stats=True, linear=False):
+        """This call's tiles as packed 8-byte pixel records (the all-gather contribution of a rank), see the header.
+        linear=True: 24-byte records that also hold the linear plane (tiles_packed_size(..., linear=True) bytes)."""
         st = Stats()
         handle = _stream_handle(stream)
-        _check(lib().rt_render_tiles_packed_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device), handle,
-                                                   C.c_void_p(packed_ptr), C.c_uint64(int(packed_bytes)), 1 if sync else 0,
-                                                   C.byref(st) if want_stats else None))
+        fn = lib().rt_render_tiles_packed_linear_device if linear else lib().rt_render_tiles_packed_device
+        _check(fn(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device), handle,
+                  C.c_void_p(packed_ptr), C.c_uint64(int(packed_bytes)), 1 if sync else 0,
+                  C.byref(st) if want_stats else None))
         return st
 
     def render_counters(self, device=0, reset=False):
@@ -515,16 +567,23 @@ class Scene:
         _check(lib().rt_render_check(self._h, int(device)))
 
     def render_tiles_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,
-                            want_stats=True):
+                            want_stats=True, linear_ptr=None):
         """Render this call's tiles into DEVICE buffers (e.g. torch tensors' data_ptr()).
         stream: None = the library's own stream; otherwise the handle of an EXPLICIT hipStream_t.  0 -- what torch
         reports for its legacy default stream -- is refused: through this argument NULL means "the library's
         stream", so work on the default stream would silently not be ordered with the render; run the caller's
-        side under a torch.cuda.Stream and pass its handle (raytracing_folder_amd.dist does)."""
+        side under a torch.cuda.Stream and pass its handle (raytracing_folder_amd.dist does).
+        linear_ptr: also the linear plane (float32 (H, W, 3) on the device), through rt_render_tiles_linear_device."""
         st = Stats()
         handle = _stream_handle(stream)
-        _check(lib().rt_render_tiles_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
-                                            handle, C.c_void_p(rgb_ptr),
-                                            C.c_void_p(z_ptr), C.c_void_p(cnt_ptr), 1 if sync else 0,
-                                            C.byref(st) if want_stats else None))
+        if linear_ptr is None:
+            _check(lib().rt_render_tiles_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                handle, C.c_void_p(rgb_ptr),
+                                                C.c_void_p(z_ptr), C.c_void_p(cnt_ptr), 1 if sync else 0,
+                                                C.byref(st) if want_stats else None))
+        else:
+            _check(lib().rt_render_tiles_linear_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                       handle, C.c_void_p(rgb_ptr), C.c_void_p(z_ptr), C.c_void_p(cnt_ptr),
+                                                       C.c_void_p(linear_ptr), 1 if sync else 0,
+                                                       C.byref(st) if want_stats else None))
         return st

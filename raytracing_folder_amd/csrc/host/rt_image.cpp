@@ -302,4 +302,74 @@ bool ReadImageRGB(const char *filename, int &w, int &h, std::vector<uint8_t> &rg
     return false;
 }
 
+// PFM, the portable float map: "PF\n<w> <h>\n<scale>\n", then w*h RGB triples of f32, the BOTTOM scanline first; a negative
+// scale means little-endian samples.  Written as "-1.0" (this library only writes little-endian).
+bool WritePFM(const char *filename, const float *rgb, int width, int height)
+{
+    if (width <= 0 || height <= 0) return false;
+    FILE *fp = fopen(filename, "wb");
+    if (!fp) return false;
+    bool ok = fprintf(fp, "PF\n%d %d\n-1.0\n", width, height) > 0;
+    const size_t row = (size_t)width * 3;
+    std::vector<uint8_t> buf(row * 4);
+    for (int y = height - 1; ok && y >= 0; y--) {
+        const float *src = rgb + (size_t)y * row;
+        for (size_t i = 0; i < row; i++) {
+            uint32_t u;
+            memcpy(&u, &src[i], 4);
+            buf[4 * i] = (uint8_t)u; buf[4 * i + 1] = (uint8_t)(u >> 8); buf[4 * i + 2] = (uint8_t)(u >> 16); buf[4 * i + 3] = (uint8_t)(u >> 24);
+        }
+        ok = fwrite(buf.data(), 1, buf.size(), fp) == buf.size();
+    }
+    return fclose(fp) == 0 && ok;
+}
+
+// Reads a 3-channel PFM of either byte order (the sign of the scale) back into row-major, top-row-first floats.
+bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std::string *err)
+{
+    w = h = 0;
+    rgb.clear();
+    FILE *fp = fopen(filename, "rb");
+    if (!fp) { if (err) *err = std::string("cannot open ") + filename; return false; }
+    std::vector<uint8_t> f;
+    uint8_t buf[65536];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, fp)) > 0) f.insert(f.end(), buf, buf + n);
+    fclose(fp);
+    if (f.size() < 3 || f[0] != 'P' || f[1] != 'F' || !isspace(f[2])) { if (err) *err = "not a 3-channel PFM (magic \"PF\")"; return false; }
+    // three header tokens after the magic, each ended by one whitespace character
+    size_t pos = 3;
+    std::string tok[3];
+    for (int t = 0; t < 3; t++) {
+        while (pos < f.size() && isspace(f[pos])) pos++;
+        while (pos < f.size() && !isspace(f[pos]) && tok[t].size() < 32) tok[t] += (char)f[pos++];
+        if (tok[t].empty() || pos >= f.size() || !isspace(f[pos])) { if (err) *err = "truncated or malformed PFM header"; return false; }
+    }
+    pos++;                                                      // the single whitespace character before the samples
+    char *end = nullptr;
+    const long iw = strtol(tok[0].c_str(), &end, 10);
+    if (*end) { if (err) *err = "bad PFM width"; return false; }
+    const long ih = strtol(tok[1].c_str(), &end, 10);
+    if (*end) { if (err) *err = "bad PFM height"; return false; }
+    const double scale = strtod(tok[2].c_str(), &end);
+    if (*end || !(scale == scale) || scale == 0) { if (err) *err = "bad PFM scale"; return false; }
+    if (iw <= 0 || ih <= 0 || iw > (1 << 20) || ih > (1 << 20)) { if (err) *err = "bad PFM size"; return false; }
+    const size_t row = (size_t)iw * 3, count = row * (size_t)ih;
+    if (f.size() - pos < count * 4) { if (err) *err = "truncated PFM samples"; return false; }
+    const bool little = scale < 0;
+    rgb.resize(count);
+    for (long y = 0; y < ih; y++) {
+        const uint8_t *src = f.data() + pos + (size_t)y * row * 4;      // stored row y is image row ih - 1 - y
+        float *dst = rgb.data() + (size_t)(ih - 1 - y) * row;
+        for (size_t i = 0; i < row; i++) {
+            const uint8_t *b = src + 4 * i;
+            const uint32_t u = little ? ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24))
+                                      : ((uint32_t)b[3] | ((uint32_t)b[2] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[0] << 24));
+            memcpy(&dst[i], &u, 4);
+        }
+    }
+    w = (int)iw; h = (int)ih;
+    return true;
+}
+
 }  // namespace rt

@@ -12,7 +12,14 @@ void RenderImage::Init(int w, int h)
     zbuffer.assign((size_t)w * h, 0.0f);
     sampleCount.assign((size_t)w * h, 0);
     zbufferImg.clear(); sampleCountImg.clear();
+    if (linearEnabled) linear.assign((size_t)w * h * 3, 0.0f);
     finalPixels = 0;
+}
+
+void RenderImage::EnableLinear()
+{
+    if (!linearEnabled) linear.assign((size_t)width * height * 3, 0.0f);
+    linearEnabled = true;
 }
 
 int RenderImage::GetNumRenderedPixels() const
@@ -94,8 +101,12 @@ bool Renderer::BeginRender()
     for (int r = 0; r < N; r++) {
         const rt_tile_range mine = {32, 8, r, N};
         rt_job *job = nullptr;
-        st = rt_render_begin(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
-                             renderImage.GetSampleCount(), &job);
+        if (renderImage.LinearEnabled())
+            st = rt_render_begin_linear(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
+                                        renderImage.GetSampleCount(), renderImage.GetLinearPixels(), &job);
+        else
+            st = rt_render_begin(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
+                                 renderImage.GetSampleCount(), &job);
         if (st != RT_OK) {
             error = rt_last_error();
             for (rt_job *j : jobs) { rt_render_stop(j); rt_render_wait(j); }

@@ -20,6 +20,8 @@ class RenderImage {
     std::vector<uint8_t> img;          // Color24[width*height]
     std::vector<float> zbuffer;
     std::vector<uint8_t> zbufferImg, sampleCount, sampleCountImg;
+    std::vector<float> linear;         // opt-in (EnableLinear): pre-gamma float RGB[width*height*3]
+    bool linearEnabled = false;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -32,6 +34,12 @@ public:
     uint8_t *GetZBufferImage() { return zbufferImg.data(); }
     uint8_t *GetSampleCount() { return sampleCount.data(); }
     uint8_t *GetSampleCountImage() { return sampleCountImg.data(); }
+    // the linear (pre-gamma) float RGB plane, row-major like GetPixels(); nothing is allocated until EnableLinear(), and
+    // GetLinearPixels() is NULL without it.  Renderer::BeginRender fills it through rt_render_begin_linear.
+    void EnableLinear();
+    bool LinearEnabled() const { return linearEnabled; }
+    float *GetLinearPixels() { return linearEnabled ? linear.data() : nullptr; }
+    bool SaveLinearImage(const char *filename) const { return linearEnabled && WritePFM(filename, linear.data(), width, height); }   // PFM
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

@@ -37,8 +37,9 @@ void rtk_launch_gather(hipStream_t, const DevPhotonMap &, const float4 *, const 
 void rtk_launch_fold_fx(hipStream_t, float *sample_rgb, unsigned long long *fx, size_t samples);
 bool rtk_wavefront_usable(const DevScene &, const rt_params &);
 void rtk_launch_resolve(hipStream_t, const DevScene &, const DevWork &, const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int,
-                        float, float, int, const float *, uint8_t *, float *, uint8_t *, void *, int);
-void rtk_launch_unpack_tiles(hipStream_t, const void *, int, int, int, int, int, int, uint8_t *, float *, uint8_t *);
+                        float, float, int, const float *, uint8_t *, float *, uint8_t *, void *, int, bool linear = false,
+                        float *rgb_linear = nullptr);
+void rtk_launch_unpack_tiles(hipStream_t, const void *, int, int, int, int, int, int, uint8_t *, float *, uint8_t *, float *rgb_linear = nullptr);
 
 // k_gather is a persistent grid that pulls query batches from a counter: enough workgroups to fill
 // every CU at the kernel's occupancy (256 CUs x 5 resident workgroups of 4 waves)
@@ -270,6 +271,7 @@ struct rt_job {
     // viewer that polls rt_render_progress can show the frame as it fills (viewport.cpp:367 reads
     // renderImage.GetPixels() while the workers run)
     uint8_t *host_rgb = nullptr, *host_count = nullptr; float *host_z = nullptr;
+    float *host_linear = nullptr;       // rt_render_begin_linear: the linear plane, copied back like the others
     rt_setup_ms setup{};                // the photon pass this job ran first (all zero when it did not)
 };
 
@@ -514,6 +516,28 @@ extern "C" rt_status rt_image_write_png(const char *path, const uint8_t *data, i
 {
     if (!path || !data || w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_image_write_png: bad argument");
     if (!rt::WritePNG(path, data, w, h, comps)) return fail(RT_ERR_IO, "rt_image_write_png(%s): cannot write (comps must be 1 or 3)", path);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_image_write_pfm(const char *path, const float *rgb, int32_t w, int32_t h)
+{
+    if (!path || !rgb || w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_image_write_pfm: bad argument");
+    if (!rt::WritePFM(path, rgb, w, h)) return fail(RT_ERR_IO, "rt_image_write_pfm(%s): cannot write", path);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_image_read_pfm(const char *path, int32_t *w, int32_t *h, float *rgb, uint64_t cap)
+{
+    if (!path || !w || !h) return fail(RT_ERR_ARG, "rt_image_read_pfm: NULL argument");
+    int iw = 0, ih = 0;
+    std::vector<float> d;
+    std::string err;
+    if (!rt::ReadPFM(path, iw, ih, d, &err)) return fail(RT_ERR_IO, "rt_image_read_pfm(%s): %s", path, err.c_str());
+    *w = iw; *h = ih;
+    if (rgb) {
+        if (cap < d.size()) return fail(RT_ERR_ARG, "rt_image_read_pfm: room for %llu floats, need %zu", (unsigned long long)cap, d.size());
+        memcpy(rgb, d.data(), d.size() * sizeof(float));
+    }
     return RT_OK;
 }
 
@@ -1433,24 +1457,27 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
 #define RT_ERR_OVERFLOW_RETRY (-1000)     /* internal: queues sized from history overflowed; render again with worst-case queues */
 static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                    hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case);
+                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
+                                   float *lin_dev);
 
 // Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
 // half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
 // if that ever overflows, a synchronous render
 // is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
 // library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
+// `linear`: the linear plane is wanted -- into lin_dev (device planes; a job's host copy follows), or as 24-byte packed records.
 static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                               hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                              bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev = nullptr)
+                              bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev = nullptr, bool linear = false,
+                              float *lin_dev = nullptr)
 {
     rt_status st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                                     packed_dev, false);
+                                     packed_dev, false, linear, lin_dev);
     int attempts = 1;
     if (st == RT_ERR_OVERFLOW_RETRY) {
         attempts = 2;
         st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                               packed_dev, true);
+                               packed_dev, true, linear, lin_dev);
     }
     if (st == RT_OK && stats_out) stats_out->attempts = (uint64_t)attempts;
     if (st == RT_OK && job) job->stats.attempts = (uint64_t)attempts;
@@ -1459,7 +1486,8 @@ static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params
 
 static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                    hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case)
+                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
+                                   float *lin_dev)
 {
     rt_status st = validate_render(s, cam, p, tiles);
     if (st) return st;
@@ -1568,10 +1596,12 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     n_slots = n_ready;
     // a job that owns only some of the tiles renders into packed records of its own (see finish_oldest)
     const bool job_packed = job != nullptr && tiles->stride != 1;
+    // bytes per packed record: 8, or 24 with the linear plane (the 8-byte record, linear r, g, b, 4 zero bytes)
+    const size_t rec_bytes = linear ? 24 : 8;
     DevBuf job_packed_buf;
     struct Release { DevBuf &b; ~Release() { b.release(); } } job_packed_release{job_packed_buf};
     if (job_packed) {
-        if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * 8))) return st;
+        if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * rec_bytes))) return st;
         packed_dev = job_packed_buf.p;
     }
     const bool want_stats = stats_out != nullptr || job != nullptr;
@@ -1646,10 +1676,11 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         }
         if (job->host_rgb && job_packed) {
             // a strided tile range (one job per device on the same caller-owned image): rows are shared with other jobs' tiles,
-            // so only this job's pixels may be written -- the chunk's packed 8-byte records come back in one copy and are
-            // scattered on the host
-            std::vector<uint2> rec(f.npix);
-            HIP_TRY(hipMemcpy(rec.data(), (const uint2 *)packed_dev + f.q0, (size_t)f.npix * 8, hipMemcpyDeviceToHost));
+            // so only this job's pixels may be written -- the chunk's packed 8-byte (24-byte: linear) records come back in one
+            // copy and are scattered on the host
+            const size_t words = rec_bytes / 8;
+            std::vector<uint2> rec((size_t)f.npix * words);
+            HIP_TRY(hipMemcpy(rec.data(), (const uint2 *)packed_dev + f.q0 * words, (size_t)f.npix * rec_bytes, hipMemcpyDeviceToHost));
             for (uint32_t i = 0; i < f.npix; i++) {
                 const uint64_t q = f.q0 + i;
                 const int t = dt.first + (int)(q / tile_px) * dt.stride;
@@ -1657,11 +1688,12 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                 const int x = (t % dt.tiles_x) * dt.tile_w + w % dt.tile_w, y = (t / dt.tiles_x) * dt.tile_h + w / dt.tile_w;
                 if (x >= cam->width || y >= cam->height) continue;
                 const size_t o = (size_t)y * cam->width + x;
-                const uint2 v = rec[i];
+                const uint2 v = rec[i * words];
                 job->host_rgb[3 * o] = (uint8_t)(v.x & 255u); job->host_rgb[3 * o + 1] = (uint8_t)((v.x >> 8) & 255u); job->host_rgb[3 * o + 2] = (uint8_t)((v.x >> 16) & 255u);
                 const uint32_t zb = (v.x >> 24) | (v.y << 8);
                 memcpy(&job->host_z[o], &zb, 4);
                 job->host_count[o] = (uint8_t)(v.y >> 24);
+                if (linear && job->host_linear) memcpy(&job->host_linear[3 * o], &rec[i * words + 1], 12);
             }
         } else if (job->host_rgb) {
             // rows spanned by this chunk's tiles (tile-major order: a contiguous band of tile rows; a row shared
@@ -1674,6 +1706,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                 HIP_TRY(hipMemcpy(job->host_rgb + 3 * o, rgb8_dev + 3 * o, 3 * n, hipMemcpyDeviceToHost));
                 HIP_TRY(hipMemcpy(job->host_z + o, z_dev + o, 4 * n, hipMemcpyDeviceToHost));
                 HIP_TRY(hipMemcpy(job->host_count + o, count_dev + o, n, hipMemcpyDeviceToHost));
+                if (lin_dev && job->host_linear) HIP_TRY(hipMemcpy(job->host_linear + 3 * o, lin_dev + 3 * o, 12 * n, hipMemcpyDeviceToHost));
             }
         }
         // monotone also when the frame is rendered a second time with larger queues (RT_ERR_OVERFLOW_RETRY)
@@ -1696,7 +1729,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
             hipEvent_t r0 = nullptr, r1 = nullptr;
             if (want_stats) { HIP_TRY(hipEventCreate(&r0)); HIP_TRY(hipEventCreate(&r1)); HIP_TRY(hipEventRecord(r0, cs)); }
             rtk_launch_resolve(cs, D->scene, W, dc, dt, (uint32_t)q0, npix, p->min_sample, p->max_sample, p->threshold, inv_gamma, phase,
-                               D->scene.bg, rgb8_dev, z_dev, count_dev, packed_dev, 2048);
+                               D->scene.bg, rgb8_dev, z_dev, count_dev, packed_dev, 2048, linear, lin_dev);
             if (want_stats) { HIP_TRY(hipEventRecord(r1, cs)); resolve_ev.emplace_back(r0, r1); }
             return RT_OK;
         };
@@ -1809,20 +1842,47 @@ extern "C" rt_status rt_render_tiles_device(rt_scene *s, const rt_camera *cam, c
                         sync != 0, stats_out, nullptr);
 }
 
-extern "C" rt_status rt_render_tiles_packed_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                                                   int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes,
-                                                   int sync, rt_stats *stats_out)
+extern "C" rt_status rt_render_tiles_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                   int device, void *hip_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
+                                                   float *rgb_linear_dev, int sync, rt_stats *stats_out)
 {
-    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_packed_device: scene is NULL");
-    if (!packed_dev) return fail(RT_ERR_ARG, "rt_render_tiles_packed_device: the packed buffer is required");
+    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_linear_device: scene is NULL");
+    if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_render_tiles_linear_device: the linear plane is required");
+    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, rgb8_dev, z_dev, count_dev,
+                        sync != 0, stats_out, nullptr, nullptr, true, rgb_linear_dev);
+}
+
+// both packed entry points: 8-byte records, or 24-byte ones with the linear plane (linear)
+static rt_status render_packed(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                               int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, int sync, rt_stats *stats_out,
+                               bool linear)
+{
+    if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", name);
+    if (!packed_dev) return fail(RT_ERR_ARG, "%s: the packed buffer is required", name);
     rt_status st = validate_render(s, cam, p, tiles);
     if (st) return st;
     uint64_t need = 0;
     if ((st = rt_tiles_packed_size(cam->width, cam->height, tiles, &need, nullptr))) return st;
-    if (packed_bytes < need) return fail(RT_ERR_ARG, "rt_render_tiles_packed_device: buffer of %llu bytes, this call's tiles need %llu",
+    if (linear) need *= 3;
+    if (packed_bytes < need) return fail(RT_ERR_ARG, "%s: buffer of %llu bytes, this call's tiles need %llu", name,
                                          (unsigned long long)packed_bytes, (unsigned long long)need);
     return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, nullptr, nullptr, nullptr,
-                        sync != 0, stats_out, nullptr, packed_dev);
+                        sync != 0, stats_out, nullptr, packed_dev, linear);
+}
+
+extern "C" rt_status rt_render_tiles_packed_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                   int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes,
+                                                   int sync, rt_stats *stats_out)
+{
+    return render_packed("rt_render_tiles_packed_device", s, cam, p, tiles, device, hip_stream, packed_dev, packed_bytes, sync, stats_out, false);
+}
+
+extern "C" rt_status rt_render_tiles_packed_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                          int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes,
+                                                          int sync, rt_stats *stats_out)
+{
+    return render_packed("rt_render_tiles_packed_linear_device", s, cam, p, tiles, device, hip_stream, packed_dev, packed_bytes, sync,
+                         stats_out, true);
 }
 
 extern "C" rt_status rt_tiles_packed_size(int32_t width, int32_t height, const rt_tile_range *t, uint64_t *bytes, int32_t *n_tiles)
@@ -1837,20 +1897,39 @@ extern "C" rt_status rt_tiles_packed_size(int32_t width, int32_t height, const r
     return RT_OK;
 }
 
+// both unpack entry points: rgb_linear_dev == NULL reads 8-byte records, otherwise 24-byte ones
+static rt_status tiles_unpack(const char *name, int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
+                              int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
+                              uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev)
+{
+    if (!gathered_dev || !rgb8_dev || !z_dev || !count_dev) return fail(RT_ERR_ARG, "%s: NULL buffer", name);
+    if (world <= 0 || width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0) return fail(RT_ERR_ARG, "%s: bad geometry", name);
+    const int64_t total = (int64_t)((width + tile_w - 1) / tile_w) * ((height + tile_h - 1) / tile_h);
+    if ((int64_t)tiles_per_rank * world < total || tiles_per_rank < (total + world - 1) / world)
+        return fail(RT_ERR_ARG, "%s: %d tiles per rank x %d ranks cannot hold %lld tiles", name, tiles_per_rank, world, (long long)total);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+    HIP_TRY(hipSetDevice(device));
+    rtk_launch_unpack_tiles((hipStream_t)hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h, rgb8_dev, z_dev, count_dev,
+                            rgb_linear_dev);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 extern "C" rt_status rt_tiles_unpack_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
                                             int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
                                             uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev)
 {
-    if (!gathered_dev || !rgb8_dev || !z_dev || !count_dev) return fail(RT_ERR_ARG, "rt_tiles_unpack_device: NULL buffer");
-    if (world <= 0 || width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0) return fail(RT_ERR_ARG, "rt_tiles_unpack_device: bad geometry");
-    const int64_t total = (int64_t)((width + tile_w - 1) / tile_w) * ((height + tile_h - 1) / tile_h);
-    if ((int64_t)tiles_per_rank * world < total || tiles_per_rank < (total + world - 1) / world)
-        return fail(RT_ERR_ARG, "rt_tiles_unpack_device: %d tiles per rank x %d ranks cannot hold %lld tiles", tiles_per_rank, world, (long long)total);
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_tiles_unpack_device: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    rtk_launch_unpack_tiles((hipStream_t)hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h, rgb8_dev, z_dev, count_dev);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return tiles_unpack("rt_tiles_unpack_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
+                        rgb8_dev, z_dev, count_dev, nullptr);
+}
+
+extern "C" rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
+                                                   int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
+                                                   uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev)
+{
+    if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_tiles_unpack_linear_device: the linear plane is required");
+    return tiles_unpack("rt_tiles_unpack_linear_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
+                        rgb8_dev, z_dev, count_dev, rgb_linear_dev);
 }
 
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
@@ -1917,24 +1996,25 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
 static rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
                                   rt_setup_ms *ms_out, bool own_job);
 
-extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                     uint8_t *rgb8, float *z, uint8_t *count, rt_job **out)
+// rt_render_begin and rt_render_begin_linear (rgb_linear != NULL: the linear plane as a fourth output)
+static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                              uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out)
 {
-    if (!s || !out) return fail(RT_ERR_ARG, "rt_render_begin: scene/out is NULL");
+    if (!s || !out) return fail(RT_ERR_ARG, "%s: scene/out is NULL", name);
     rt_status st = validate_render(s, cam, p, tiles);
     if (st) return st;
-    if (!rgb8 || !z || !count) return fail(RT_ERR_ARG, "rt_render_begin: output buffers are required");
+    if (!rgb8 || !z || !count) return fail(RT_ERR_ARG, "%s: output buffers are required", name);
     DeviceState *D = nullptr;
     if ((st = prepare_device(s, device, &D))) return st;      // fail early (and loudly) when there is no GPU
     rt_job *job = new rt_job;
     job->scene = s;
-    job->host_rgb = rgb8; job->host_z = z; job->host_count = count;
+    job->host_rgb = rgb8; job->host_z = z; job->host_count = count; job->host_linear = rgb_linear;
     s->live_jobs.fetch_add(1);
     const rt_camera camv = *cam; const rt_params pv = *p; const rt_tile_range tv = *tiles;
     job->worker = std::thread([=]() {
         rt_status r = RT_OK;
         const size_t npx = (size_t)camv.width * camv.height;
-        uint8_t *d_rgb = nullptr, *d_cnt = nullptr; float *d_z = nullptr;
+        uint8_t *d_rgb = nullptr, *d_cnt = nullptr; float *d_z = nullptr, *d_lin = nullptr;
         auto body = [&]() -> rt_status {
             HIP_TRY(hipSetDevice(device));
             // BeginRender calls generatePhotonMap() before it spawns its workers (FIN/main.cpp:984-998, :350-402); here the
@@ -1961,13 +2041,20 @@ extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt
             HIP_TRY(hipMemcpy(d_rgb, rgb8, npx * 3, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(d_z, z, npx * 4, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(d_cnt, count, npx, hipMemcpyHostToDevice));
+            // the linear plane lives on the device only when it is asked for (a strided job takes it in its packed records)
+            if (rgb_linear && tv.stride == 1) {
+                HIP_TRY(hipMalloc((void **)&d_lin, npx * 12));
+                HIP_TRY(hipMemcpy(d_lin, rgb_linear, npx * 12, hipMemcpyHostToDevice));
+            }
             // render_tiles copies every finished band of rows back into the caller's buffers
-            return render_tiles(s, &camv, &pv, &tv, device, nullptr, false, d_rgb, d_z, d_cnt, true, nullptr, job);
+            return render_tiles(s, &camv, &pv, &tv, device, nullptr, false, d_rgb, d_z, d_cnt, true, nullptr, job, nullptr,
+                                rgb_linear != nullptr, d_lin);
         };
         r = body();
         if (d_rgb) (void)hipFree(d_rgb);
         if (d_z) (void)hipFree(d_z);
         if (d_cnt) (void)hipFree(d_cnt);
+        if (d_lin) (void)hipFree(d_lin);
         job->status = r;
         if (r) job->error = g_err;
         job->done.store(true);
@@ -1975,6 +2062,19 @@ extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt
     });
     *out = job;
     return RT_OK;
+}
+
+extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                     uint8_t *rgb8, float *z, uint8_t *count, rt_job **out)
+{
+    return render_begin("rt_render_begin", s, cam, p, tiles, device, rgb8, z, count, nullptr, out);
+}
+
+extern "C" rt_status rt_render_begin_linear(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                            uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out)
+{
+    if (!rgb_linear) return fail(RT_ERR_ARG, "rt_render_begin_linear: the linear plane is required");
+    return render_begin("rt_render_begin_linear", s, cam, p, tiles, device, rgb8, z, count, rgb_linear, out);
 }
 
 extern "C" int rt_render_progress(rt_job *j) { return j ? j->progress.load() : 0; }

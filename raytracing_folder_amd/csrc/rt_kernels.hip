@@ -2667,6 +2667,9 @@ struct ResolveArgs {
     // buffer a rank contributes to the all-gather, written here coalesced instead of being re-packed afterwards
     uint2 *packed;
     int direct_mode;            // rt_shade_rays: no image, leave samples as they are
+    // linear plane (k_resolve<true> only): the pre-gamma float RGB of the pixel, row-major like rgb8; in packed mode the
+    // record grows to 24 bytes instead -- {the 8-byte record, linear r, g, b as f32, 4 zero bytes} at packed + 24*q
+    float *rgb_linear;
 };
 
 __device__ __forceinline__ uint8_t float_to_byte(float r)
@@ -2682,6 +2685,9 @@ __device__ __forceinline__ uint8_t float_to_byte(float r)
 #ifndef RT_RESOLVE_TILE
 #define RT_RESOLVE_TILE 8            // samples per pixel staged through LDS at a time
 #endif
+// LIN: also the linear plane (ResolveArgs::rgb_linear), or 24-byte packed records; the default instantiation is the kernel
+// as it was
+template <bool LIN = false>
 __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
 {
     // A pixel's samples are contiguous (max_sample slots of 12 B), so a thread walking its own pixel reads 12 B
@@ -2711,7 +2717,14 @@ __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
         int x = 0, y = 0;
         const bool valid = in_range && pixel_of(A.tiles, A.cam, A.q0 + ql, x, y);
         // packed mode: slots of a ragged tile that lie outside the image are part of the exchanged buffer -> zero
-        if (A.packed && in_range && !valid && A.phase == 0) A.packed[(size_t)A.q0 + ql] = make_uint2(0u, 0u);
+        if (A.packed && in_range && !valid && A.phase == 0) {
+            if constexpr (LIN) {
+                uint2 *rec = A.packed + 3 * ((size_t)A.q0 + ql);
+                rec[0] = make_uint2(0u, 0u); rec[1] = make_uint2(0u, 0u); rec[2] = make_uint2(0u, 0u);
+            } else {
+                A.packed[(size_t)A.q0 + ql] = make_uint2(0u, 0u);
+            }
+        }
         if (!staged && !valid) continue;
         const size_t index = (size_t)y * A.cam.width + x;
         const float *rgb = W.sample_rgb + 3 * (size_t)ql * A.max_sample;
@@ -2806,15 +2819,26 @@ __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
             // background.Sample(Point3(x/W, y/H, 0)), FIN/main.cpp:326-328
             const V3 bgc = textured_color(A.S, ld3(A.bg), A.S.bg_map, mk((float)x / A.cam.width, (float)y / A.cam.height, 0));
             g[0] = powf(bgc.x, A.inv_gamma); g[1] = powf(bgc.y, A.inv_gamma); g[2] = powf(bgc.z, A.inv_gamma);
+            if constexpr (LIN) { c0 = bgc.x; c1 = bgc.y; c2 = bgc.z; }        // the linear plane holds the linear background
         }
         const uint32_t r8 = float_to_byte(g[0]), g8 = float_to_byte(g[1]), b8 = float_to_byte(g[2]);
         if (A.packed) {
             const uint32_t zb = __float_as_uint(zval);
-            A.packed[(size_t)A.q0 + ql] = make_uint2(r8 | (g8 << 8) | (b8 << 16) | (zb << 24), (zb >> 8) | ((uint32_t)cnt_byte << 24));
+            const uint2 v = make_uint2(r8 | (g8 << 8) | (b8 << 16) | (zb << 24), (zb >> 8) | ((uint32_t)cnt_byte << 24));
+            if constexpr (LIN) {
+                // three 8-byte stores: the record of a wave is one contiguous 1536-byte run
+                uint2 *rec = A.packed + 3 * ((size_t)A.q0 + ql);
+                rec[0] = v;
+                rec[1] = make_uint2(__float_as_uint(c0), __float_as_uint(c1));
+                rec[2] = make_uint2(__float_as_uint(c2), 0u);
+            } else {
+                A.packed[(size_t)A.q0 + ql] = v;
+            }
         } else {
             A.count[index] = cnt_byte;
             A.z[index] = zval;
             A.rgb8[3 * index] = (uint8_t)r8; A.rgb8[3 * index + 1] = (uint8_t)g8; A.rgb8[3 * index + 2] = (uint8_t)b8;
+            if constexpr (LIN) { A.rgb_linear[3 * index] = c0; A.rgb_linear[3 * index + 1] = c1; A.rgb_linear[3 * index + 2] = c2; }
         }
     }
 }
@@ -3009,9 +3033,12 @@ void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *f
 
 // Un-interleave an all-gathered frame: rank r contributed its tiles r, r+R, r+2R, ... as `per_rank` packed tiles of
 // tile_w*tile_h 8-byte pixel records (see ResolveArgs::packed); one thread per image pixel reads its record (8-byte
-// loads, contiguous along a tile row) and writes the three planes of the RenderImage.
+// loads, contiguous along a tile row) and writes the three planes of the RenderImage.  LIN: 24-byte records (three 8-byte
+// loads) and the linear plane as a fourth.
+template <bool LIN = false>
 __global__ __launch_bounds__(256) void k_unpack_tiles(const uint2 *gathered, int world, int per_rank, int width, int height,
-                                                      int tile_w, int tile_h, int tiles_x, uint8_t *rgb8, float *z, uint8_t *count)
+                                                      int tile_w, int tile_h, int tiles_x, uint8_t *rgb8, float *z, uint8_t *count,
+                                                      float *rgb_linear = nullptr)
 {
     const size_t n = (size_t)width * height;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -3019,32 +3046,44 @@ __global__ __launch_bounds__(256) void k_unpack_tiles(const uint2 *gathered, int
         const int tx = x / tile_w, ty = y / tile_h;
         const int t = ty * tiles_x + tx;
         const int r = t % world, k = t / world;
-        const uint2 v = gathered[((size_t)r * per_rank + k) * (size_t)(tile_w * tile_h) + (size_t)(y - ty * tile_h) * tile_w + (x - tx * tile_w)];
+        const size_t q = ((size_t)r * per_rank + k) * (size_t)(tile_w * tile_h) + (size_t)(y - ty * tile_h) * tile_w + (x - tx * tile_w);
+        const uint2 v = gathered[LIN ? 3 * q : q];
         rgb8[3 * i] = (uint8_t)(v.x & 255u); rgb8[3 * i + 1] = (uint8_t)((v.x >> 8) & 255u); rgb8[3 * i + 2] = (uint8_t)((v.x >> 16) & 255u);
         z[i] = __uint_as_float((v.x >> 24) | (v.y << 8));
         count[i] = (uint8_t)(v.y >> 24);
+        if constexpr (LIN) {
+            const uint2 a = gathered[3 * q + 1], b = gathered[3 * q + 2];
+            rgb_linear[3 * i] = __uint_as_float(a.x); rgb_linear[3 * i + 1] = __uint_as_float(a.y); rgb_linear[3 * i + 2] = __uint_as_float(b.x);
+        }
     }
 }
 
 void rtk_launch_unpack_tiles(hipStream_t st, const void *gathered, int world, int per_rank, int width, int height, int tile_w, int tile_h,
-                             uint8_t *rgb8, float *z, uint8_t *count)
+                             uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear)
 {
     const int tiles_x = (width + tile_w - 1) / tile_w;
     const size_t n = (size_t)width * height;
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_unpack_tiles, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)gathered, world, per_rank, width, height,
-                       tile_w, tile_h, tiles_x, rgb8, z, count);
+    if (rgb_linear)
+        hipLaunchKernelGGL(k_unpack_tiles<true>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)gathered, world, per_rank, width,
+                           height, tile_w, tile_h, tiles_x, rgb8, z, count, rgb_linear);
+    else
+        hipLaunchKernelGGL(k_unpack_tiles<false>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)gathered, world, per_rank, width,
+                           height, tile_w, tile_h, tiles_x, rgb8, z, count, nullptr);
 }
 
+// linear: the LIN instantiation of k_resolve -- the linear plane rgb_linear, or 24-byte records when `packed` is set
 void rtk_launch_resolve(hipStream_t st, const DevScene &S, const DevWork &W, const DevCamera &cam, const DevTiles &tiles,
                         uint32_t q0, uint32_t npix, int min_sample, int max_sample, float threshold,
                         float inv_gamma, int phase, const float bg[3], uint8_t *rgb8, float *z,
-                        uint8_t *count, void *packed, int max_blocks)
+                        uint8_t *count, void *packed, int max_blocks, bool linear, float *rgb_linear)
 {
     ResolveArgs A; A.cam = cam; A.tiles = tiles; A.q0 = q0; A.npix = npix; A.min_sample = min_sample;
     A.max_sample = max_sample; A.threshold = threshold; A.inv_gamma = inv_gamma; A.phase = phase;
     A.bg[0] = bg[0]; A.bg[1] = bg[1]; A.bg[2] = bg[2]; A.rgb8 = rgb8; A.z = z; A.count = count; A.packed = (uint2 *)packed; A.direct_mode = 0; A.S = S;
+    A.rgb_linear = rgb_linear;
     tiles_prepare(A.tiles);
     const int grid = grid_for(npix, 256, max_blocks);
-    hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, W, A);
+    if (linear) hipLaunchKernelGGL(k_resolve<true>, dim3(grid), dim3(256), 0, st, W, A);
+    else hipLaunchKernelGGL(k_resolve<false>, dim3(grid), dim3(256), 0, st, W, A);
 }

@@ -14,6 +14,7 @@ import torch.distributed as dist
 from . import capi
 
 BYTES_PER_PIXEL = 8          # 3 (Color24) + 4 (float z) + 1 (sample count)
+BYTES_PER_PIXEL_LINEAR = 24  # the 8-byte record + the linear plane's 3 floats + 4 zero bytes (ShardedRenderer(linear=True))
 
 
 def tile_grid(width, height, tile_w=32, tile_h=8):
@@ -81,9 +82,11 @@ class ShardedRenderer:
     all-gather (rt_render_tiles_packed_device: k_resolve writes the 8-byte pixel records tile by tile), ONE
     all_gather_into_tensor moves them (RCCL over xGMI), and one small HIP kernel (rt_tiles_unpack_device)
     un-interleaves the gathered tiles into the RenderImage planes -- no Python-side packing in the step.
-    `gather_ms` collects, per step, the time from the end of this rank's render to the finished frame."""
+    `gather_ms` collects, per step, the time from the end of this rank's render to the finished frame.
+    linear=True: the frame also carries the linear (pre-gamma) float RGB plane `lin` (H, W, 3): the records grow to 24 bytes
+    (still one all-gather) and step() returns (rgb, z, cnt, lin) as its frame."""
 
-    def __init__(self, scene, cam, params, rank, world, device_index, tile_w=32, tile_h=8, host_gather=False):
+    def __init__(self, scene, cam, params, rank, world, device_index, tile_w=32, tile_h=8, host_gather=False, linear=False):
         self.scene, self.cam, self.params = scene, cam, params
         self.host_gather = host_gather          # gather over CPU tensors (gloo rehearsal on one GPU)
         self.rank, self.world, self.device_index = rank, world, device_index
@@ -93,11 +96,14 @@ class ShardedRenderer:
         self.rgb = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
         self.z = torch.zeros((h, w), dtype=torch.float32, device=dev)
         self.cnt = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+        self.linear = linear
+        self.lin = torch.zeros((h, w, 3), dtype=torch.float32, device=dev) if linear else None
+        bpp = BYTES_PER_PIXEL_LINEAR if linear else BYTES_PER_PIXEL
         _, _, n = tile_grid(w, h, tile_w, tile_h)
         self.per_rank = (n + world - 1) // world
         # ranks whose share is one tile short leave the last slot zero: every rank contributes the same bytes
-        self.packed = torch.zeros((self.per_rank, tile_h, tile_w, BYTES_PER_PIXEL), dtype=torch.uint8, device=dev)
-        self.gathered = torch.zeros((world * self.per_rank, tile_h, tile_w, BYTES_PER_PIXEL), dtype=torch.uint8, device=dev)
+        self.packed = torch.zeros((self.per_rank, tile_h, tile_w, bpp), dtype=torch.uint8, device=dev)
+        self.gathered = torch.zeros((world * self.per_rank, tile_h, tile_w, bpp), dtype=torch.uint8, device=dev)
         self.gather_ms = []
         # everything of a step -- render, all-gather, un-interleave -- is ordered on ONE explicit stream (torch's legacy
         # default stream has handle 0, which the C ABI reads as "the library's own stream": not ordered with ours)
@@ -111,12 +117,16 @@ class ShardedRenderer:
         tiles = capi.TileRange(self.tile_w, self.tile_h, self.rank, self.world)
         return self.scene.render_tiles_device(self.cam, self.params, tiles, self.device_index, self.rgb.data_ptr(),
                                               self.z.data_ptr(), self.cnt.data_ptr(), stream=self._stream(), sync=sync,
-                                              want_stats=want_stats)
+                                              want_stats=want_stats, linear_ptr=self.lin.data_ptr() if self.linear else None)
 
     def render_own_tiles_packed(self, want_stats=True, sync=True):
         tiles = capi.TileRange(self.tile_w, self.tile_h, self.rank, self.world)
         return self.scene.render_tiles_packed_device(self.cam, self.params, tiles, self.device_index, self.packed.data_ptr(),
-                                                     self.packed.numel(), stream=self._stream(), sync=sync, want_stats=want_stats)
+                                                     self.packed.numel(), stream=self._stream(), sync=sync, want_stats=want_stats,
+                                                     linear=self.linear)
+
+    def _frame(self):
+        return (self.rgb, self.z, self.cnt, self.lin) if self.linear else (self.rgb, self.z, self.cnt)
 
     def step(self, sync=True):
         """One frame.  sync=True: the call returns with the finished frame and this rank's statistics (the host waits for the
@@ -128,7 +138,7 @@ class ShardedRenderer:
         if self.world == 1:
             st = self.render_own_tiles(want_stats=sync, sync=sync)
             self.gather_ms.append(0.0)
-            return (st if sync else None), (self.rgb, self.z, self.cnt)
+            return (st if sync else None), self._frame()
         import time
         with torch.cuda.stream(self.stream):
             st = self.render_own_tiles_packed(want_stats=sync, sync=sync)       # sync: this rank's tiles are final
@@ -143,12 +153,13 @@ class ShardedRenderer:
                 dist.all_gather_into_tensor(self.gathered, self.packed)     # rank r's tiles land in rows [r*per_rank, (r+1)*per_rank)
             capi.tiles_unpack_device(self.device_index, self._stream(), self.gathered.data_ptr(), self.world, self.per_rank,
                                      self.cam.width, self.cam.height, self.tile_w, self.tile_h,
-                                     self.rgb.data_ptr(), self.z.data_ptr(), self.cnt.data_ptr())
+                                     self.rgb.data_ptr(), self.z.data_ptr(), self.cnt.data_ptr(),
+                                     linear_ptr=self.lin.data_ptr() if self.linear else None)
             if sync:
                 self.stream.synchronize()
         if sync:
             self.gather_ms.append((time.perf_counter() - t0) * 1e3)
-        return (st if sync else None), (self.rgb, self.z, self.cnt)
+        return (st if sync else None), self._frame()
 
     def finish(self):
         """wait for the frames enqueued with step(sync=False) and collect their verdict (raises if a queue overflowed)"""

@@ -1,0 +1,366 @@
+"""The linear (pre-gamma) float RGB plane: an opt-in fourth output of every render entry point, the 24-byte packed
+records of the multi-GPU exchange, rt::RenderImage's EnableLinear(), and PFM files.  The plane holds the float32 average
+k_resolve computes before powf(c, 1/gamma), so it is checked against the oracle's per-sample colours in float, against
+the RGB8 plane it is gamma-encoded into, and (reproducible mode) byte for byte across entry points."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import orc
+from raytracing_folder_amd import capi, photons
+from tests import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIG = np.float32(1e30)
+PAD = dict(min_sample=4, max_sample=8, threshold=1e-3)          # adaptive 4 -> 8 (the variance gate)
+BG = (0.25, 0.5, 0.75)                                          # a background that shows in the linear plane
+
+
+# ---- CPU: PFM files and packed sizes ------------------------------------------------------------------------
+def test_pfm_round_trip_and_header(tmp_path):
+    rng = np.random.default_rng(1)
+    img = rng.normal(0, 3, (5, 7, 3)).astype(np.float32)
+    img[0, 0] = (0.0, 1e30, -2.5)
+    path = str(tmp_path / "a.pfm")
+    capi.image_write_pfm(path, img)
+    raw = open(path, "rb").read()
+    head = b"PF\n7 5\n-1.0\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 5 * 7 * 3 * 4
+    body = np.frombuffer(raw[len(head):], "<f4").reshape(5, 7, 3)
+    assert body.tobytes() == img[::-1].tobytes()              # bottom scanline first
+    back = capi.image_read_pfm(path)
+    assert back.shape == (5, 7, 3) and back.tobytes() == img.tobytes()
+
+
+def test_pfm_reader_stores_rows_bottom_to_top_in_either_byte_order(tmp_path):
+    # hand-written files: 2 wide, 3 high; stored row k is image row 2 - k
+    rows = np.arange(3 * 2 * 3, dtype=np.float32).reshape(3, 2, 3)          # rows as stored in the file
+    for scale, dt in ((b"-1.0", "<f4"), (b"1.0", ">f4"), (b"-0.5", "<f4")):
+        path = str(tmp_path / "h.pfm")
+        with open(path, "wb") as f:
+            f.write(b"PF\n2 3\n" + scale + b"\n" + rows.astype(dt).tobytes())
+        img = capi.image_read_pfm(path)
+        assert img.dtype == np.float32 and img.shape == (3, 2, 3)
+        assert (img[0] == rows[2]).all() and (img[2] == rows[0]).all() and (img[1] == rows[1]).all(), scale
+
+
+def test_pfm_reader_refuses_bad_files_and_small_buffers(tmp_path):
+    good = b"PF\n2 2\n-1.0\n" + np.ones(12, "<f4").tobytes()
+    cases = {"truncated.pfm": good[:-1], "magic.pfm": b"Pf\n2 2\n-1.0\n" + good[12:], "grey.pfm": b"Pf" + good[2:],
+             "header.pfm": b"PF\n2 x\n-1.0\n" + good[12:], "short.pfm": b"PF\n2 2\n", "zero.pfm": b"PF\n2 2\n0\n" + good[12:],
+             "empty.pfm": b""}
+    for name, data in cases.items():
+        path = str(tmp_path / name)
+        open(path, "wb").write(data)
+        with pytest.raises(capi.RtError) as e:
+            capi.image_read_pfm(path)
+        assert e.value.status == -5, name                      # RT_ERR_IO
+    with pytest.raises(capi.RtError) as e:
+        capi.image_read_pfm(str(tmp_path / "missing.pfm"))
+    assert e.value.status == -5
+    path = str(tmp_path / "good.pfm")
+    open(path, "wb").write(good)
+    w, h = C.c_int32(), C.c_int32()
+    out = np.zeros(12, np.float32)
+    L = capi.lib()
+    assert L.rt_image_read_pfm(path.encode(), C.byref(w), C.byref(h), capi._p(out), 11) == -1        # RT_ERR_ARG
+    assert L.rt_image_read_pfm(path.encode(), C.byref(w), C.byref(h), capi._p(out), 12) == 0 and (out == 1).all()
+    assert (w.value, h.value) == (2, 2)
+    assert L.rt_image_write_pfm(str(tmp_path / "x.pfm").encode(), None, 2, 2) == -1
+    assert L.rt_image_write_pfm(str(tmp_path / "x.pfm").encode(), capi._p(out), 0, 2) == -1
+
+
+@pytest.mark.parametrize("w,h,tw,th,first,stride", [(100, 37, 32, 8, 1, 3), (33, 9, 32, 8, 0, 1), (1920, 1080, 32, 8, 7, 29),
+                                                     (5, 5, 4, 4, 3, 2), (64, 48, 16, 16, 9, 1)])
+def test_packed_linear_sizes_are_three_times_the_8_byte_ones(w, h, tw, th, first, stride):
+    t = capi.TileRange(tw, th, first, stride)
+    b8, n8 = capi.tiles_packed_size(w, h, t)
+    b24, n24 = capi.tiles_packed_size(w, h, t, linear=True)
+    tiles_total = ((w + tw - 1) // tw) * ((h + th - 1) // th)
+    n = len(range(first, tiles_total, stride))
+    assert n8 == n24 == n and b8 == n * tw * th * 8 and b24 == 3 * b8
+
+
+def test_linear_entry_points_refuse_a_null_plane():
+    s, cam = scenes.load_cornell(64, 48)
+    p = capi.default_params()
+    t = capi.TileRange(32, 8, 0, 1)
+    L = capi.lib()
+    buf = np.zeros(64 * 48 * 4, np.uint8)
+    job = C.c_void_p()
+    assert L.rt_render_begin_linear(s._h, C.byref(cam), C.byref(p), C.byref(t), 0, capi._p(buf), capi._p(buf), capi._p(buf),
+                                    None, C.byref(job)) == -1
+    assert L.rt_render_tiles_linear_device(s._h, C.byref(cam), C.byref(p), C.byref(t), 0, None, capi._p(buf), capi._p(buf),
+                                           capi._p(buf), None, 1, None) == -1
+    assert L.rt_tiles_unpack_linear_device(0, None, capi._p(buf), 1, 12, 64, 48, 32, 8, capi._p(buf), capi._p(buf), capi._p(buf),
+                                           None) == -1
+    # a buffer of the 8-byte size is too small for 24-byte records (refused before anything is rendered)
+    nbytes, _ = capi.tiles_packed_size(64, 48, t)
+    assert L.rt_render_tiles_packed_linear_device(s._h, C.byref(cam), C.byref(p), C.byref(t), 0, None, capi._p(buf),
+                                                  nbytes, 1, None) == -1
+    assert b"need" in L.rt_last_error()
+
+
+# ---- GPU ----------------------------------------------------------------------------------------------------
+def _view(cam):
+    """a wider view of the box: its open front and the outside show, so some pixels miss everything"""
+    cam.fov = 70.0
+    return cam
+
+
+def _expected_linear(osc, ocam, op, x, y, cnt_byte):
+    """k_resolve's float sum over the oracle's per-sample colours: the batch the GPU's count byte names.  A pixel of the
+    second batch with at most min_sample hits also carries count 0, so that batch is returned as an alternative."""
+    ms = op.max_sample
+    rgb, hm, zz = np.zeros(3 * ms, np.float32), np.zeros(ms, np.uint8), C.c_float()
+    orc.lib().orc_pixel_samples(C.byref(osc.c), C.byref(ocam), C.byref(op), int(x), int(y), 0, ms,
+                                rgb.ctypes.data_as(C.c_void_p), hm.ctypes.data_as(C.c_void_p), C.byref(zz))
+    rgb = rgb.reshape(ms, 3)
+
+    def avg(ns):
+        hits = [j for j in range(ns) if hm[j]]
+        if not hits:
+            return None, 0
+        inv = np.float32(1) / np.float32(len(hits))
+        c = np.zeros(3, np.float32)
+        for j in hits:
+            c = (c + rgb[j] * inv).astype(np.float32)
+        return c, len(hits)
+
+    if cnt_byte == 255:
+        return [avg(ms)[0]]
+    first, _ = avg(op.min_sample)
+    alt, n_all = avg(ms)
+    return [first] + ([alt] if alt is not None and n_all <= op.min_sample else [])
+
+
+def _check_against_oracle(s, cam, p, lin, cnt, z, bal=None, n_pick=160, seed=0):
+    """(relative error, within-the-2e-5-gate flag) of each picked hit pixel, and how many second-batch pixels there were"""
+    osc = scenes.oracle_scene(s.export(), bal)
+    ocam, op = scenes.oracle_camera(cam), scenes.oracle_params(p)
+    rng = np.random.default_rng(seed)
+    ys, xs = np.nonzero(z != BIG)
+    second = np.flatnonzero(cnt[ys, xs] == 255)
+    pick = np.concatenate([rng.choice(second, min(len(second), n_pick // 4), replace=False),
+                           rng.choice(len(ys), n_pick - min(len(second), n_pick // 4), replace=False)])
+    rels, tight = [], []
+    for i in pick:
+        x, y = int(xs[i]), int(ys[i])
+        got = lin[y, x]
+        cands = [c for c in _expected_linear(osc, ocam, op, x, y, int(cnt[y, x])) if c is not None]
+        assert cands, (x, y)
+        errs = [np.abs(got - c) for c in cands]
+        k = int(np.argmin([e.max() for e in errs]))
+        want = cands[k]
+        tight.append(bool((errs[k] <= 2e-5 * np.abs(want) + 1e-6).all()))
+        rels.append(float(errs[k].max() / (np.abs(want).max() + 1e-30)))
+    # all-miss pixels: the linear background (the oracle's first batch has no hit there either)
+    my, mx = np.nonzero(z == BIG)
+    assert len(my) > 0
+    for i in rng.choice(len(my), min(24, len(my)), replace=False):
+        x, y = int(mx[i]), int(my[i])
+        assert (lin[y, x] == np.asarray(BG, np.float32)).all(), (x, y, lin[y, x])
+        assert _expected_linear(osc, ocam, op, x, y, 0)[0] is None
+    return np.array(rels), np.array(tight), len(second)
+
+
+def _encode(lin, gamma):
+    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte)"""
+    g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
+    s = (g * np.float32(255)).astype(np.float32)
+    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
+    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
+
+
+def _assert_consistent_with_rgb8(lin, rgb, gamma):
+    enc = _encode(lin, gamma)
+    d = np.abs(enc.astype(int) - rgb.astype(int))
+    assert (d == 0).mean() >= 0.999, (d != 0).sum()
+    assert d.max() <= 1
+
+
+def _scene(w, h, bal=None):
+    s, cam = scenes.load_cornell(w, h)
+    s.set_environment((0, 0, 0), BG)
+    if bal is not None:
+        s.set_photons(bal)
+    return s, _view(cam)
+
+
+@pytest.mark.gpu
+def test_p13_linear_plane_against_the_oracle_in_float():
+    s, cam = _scene(64, 48)
+    p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, **PAD)
+    rgb, z, cnt, lin, st, progress = s.render_linear(cam, p)
+    assert progress == 64 * 48 and st.photon_queries == 0
+    assert np.isfinite(lin).all() and (lin >= 0).all()
+    rels, tight, n_second = _check_against_oracle(s, cam, p, lin, cnt, z)
+    assert n_second > 0                                           # the second batch is covered
+    assert tight.all(), (rels.max(), (~tight).sum())
+    _assert_consistent_with_rgb8(lin, rgb, p.gamma)
+
+
+@pytest.mark.gpu
+def test_fin_linear_plane_with_a_photon_map_against_the_oracle():
+    bal = photons.synth_cornell_photon_map(4000, seed=1)
+    s, cam = _scene(64, 48, bal)
+    p = capi.default_params(**PAD)
+    rgb, z, cnt, lin, st, progress = s.render_linear(cam, p)
+    assert st.photon_queries > 0
+    rels, tight, n_second = _check_against_oracle(s, cam, p, lin, cnt, z, bal, seed=1)
+    assert n_second > 0
+    # summation order everywhere but the queries the reference heap's first replacement touches: the allowance of the
+    # irradiance tests (2.5 / k relative), which bounds the pixel too since every term of it is non-negative
+    assert tight.mean() > 0.9, (~tight).sum()
+    assert (rels < 2.5 / p.knn_k + 2e-5).all(), rels.max()
+    _assert_consistent_with_rgb8(lin, rgb, p.gamma)
+
+
+@pytest.fixture(scope="module")
+def repro():
+    """a reproducible Cornell frame with a photon map, adaptive 4 -> 8, rendered once through the plain job path and once
+    with the linear plane"""
+    bal = photons.synth_cornell_photon_map(20000, seed=3)
+    s, cam = _scene(96, 72, bal)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    p = capi.default_params(**PAD)
+    plain = s.render(cam, p)[:3]
+    rgb, z, cnt, lin, st, _ = s.render_linear(cam, p)
+    assert (cnt == 255).any() and (z == BIG).any() and st.photon_queries > 0
+    return s, cam, p, plain, (rgb, z, cnt, lin)
+
+
+def _same(a, b, names=("rgb", "z", "count", "linear")):
+    for x, y, name in zip(a, b, names):
+        x, y = np.asarray(x), np.asarray(y)
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), f"{name}: {(x != y).sum()} values differ"
+
+
+@pytest.mark.gpu
+def test_asking_for_the_plane_moves_nothing_else(repro):
+    s, cam, p, plain, ref = repro
+    _same(ref[:3], plain)
+    _assert_consistent_with_rgb8(ref[3], ref[0], p.gamma)
+
+
+@pytest.mark.gpu
+def test_linear_plane_is_the_same_bytes_on_every_entry_point(repro, monkeypatch):
+    import torch
+    s, cam, p, plain, ref = repro
+    W, H = cam.width, cam.height
+    # job path, strided tile sets (packed 24-byte records scattered on the host) composed into one frame
+    acc = [np.zeros_like(a) for a in ref]
+    for rank in range(2):
+        r = s.render_linear(cam, p, capi.TileRange(32, 8, rank, 2))
+        mine = r[1] != 0
+        for a, b in zip(acc, r[:4]):
+            a[mine] = b[mine]
+    _same(acc, ref)
+    # job path, many chunks
+    monkeypatch.setenv("RT_CHUNK_SAMPLES", "8192")
+    _same(s.render_linear(cam, p)[:4], ref)
+    # device path: several chunks, then one stream
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(device=dev)
+
+    def device_frame(tiles=capi.TileRange(32, 8, 0, 1), fill=0.0):
+        planes = (torch.zeros((H, W, 3), dtype=torch.uint8, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev),
+                  torch.zeros((H, W), dtype=torch.uint8, device=dev), torch.full((H, W, 3), fill, dtype=torch.float32, device=dev))
+        torch.cuda.synchronize()
+        s.render_tiles_device(cam, p, tiles, 0, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
+                              stream=side.cuda_stream, sync=True, want_stats=False, linear_ptr=planes[3].data_ptr())
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in planes]
+
+    _same(device_frame(), ref)
+    monkeypatch.setenv("RT_STREAMS", "1")
+    _same(device_frame(), ref)
+    monkeypatch.delenv("RT_STREAMS")
+    monkeypatch.delenv("RT_CHUNK_SAMPLES")
+    # two ranks' 24-byte packed records in one gathered buffer, unpacked on the GPU
+    world = 2
+    n_tiles = ((W + 31) // 32) * ((H + 7) // 8)
+    per_rank = (n_tiles + world - 1) // world
+    g24 = torch.zeros((world, per_rank, 8, 32, 24), dtype=torch.uint8, device=dev)
+    g8 = torch.zeros((world, per_rank, 8, 32, 8), dtype=torch.uint8, device=dev)
+    for rank in range(world):
+        tiles = capi.TileRange(32, 8, rank, world)
+        nbytes, k = capi.tiles_packed_size(W, H, tiles, linear=True)
+        assert k <= per_rank and nbytes == k * 256 * 24
+        s.render_tiles_packed_device(cam, p, tiles, 0, g24[rank].data_ptr(), nbytes, stream=None, sync=True, want_stats=False,
+                                     linear=True)
+        n8, _ = capi.tiles_packed_size(W, H, tiles)
+        s.render_tiles_packed_device(cam, p, tiles, 0, g8[rank].data_ptr(), n8, stream=None, sync=True, want_stats=False)
+    torch.cuda.synchronize()
+    r24, r8 = g24.cpu().numpy(), g8.cpu().numpy()
+    assert r24[..., :8].tobytes() == r8.tobytes()                 # bytes 0-7: the 8-byte record
+    assert (r24[..., 20:] == 0).all()                              # bytes 20-23: zero
+    out = [torch.zeros((H, W, 3), dtype=torch.uint8, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev),
+           torch.zeros((H, W), dtype=torch.uint8, device=dev), torch.zeros((H, W, 3), dtype=torch.float32, device=dev)]
+    torch.cuda.synchronize()
+    capi.tiles_unpack_device(0, side.cuda_stream, g24.data_ptr(), world, per_rank, W, H, 32, 8,
+                             out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), linear_ptr=out[3].data_ptr())
+    torch.cuda.synchronize()
+    _same([t.cpu().numpy() for t in out], ref)
+
+
+@pytest.mark.gpu
+def test_sharded_renderer_carries_the_linear_plane_on_one_rank(repro):
+    from raytracing_folder_amd import dist
+    s, cam, p, plain, ref = repro
+    sr = dist.ShardedRenderer(s, cam, p, 0, 1, 0, linear=True)
+    st, frame = sr.step(sync=True)
+    assert len(frame) == 4
+    _same([t.cpu().numpy() for t in frame], ref)
+    st, frame = dist.ShardedRenderer(s, cam, p, 0, 1, 0).step(sync=True)
+    assert len(frame) == 3
+
+
+@pytest.mark.gpu
+def test_pixels_of_tiles_not_rendered_keep_the_callers_linear_values(repro):
+    import torch
+    s, cam, p, plain, ref = repro
+    W, H = cam.width, cam.height
+    SENT = np.float32(-7.25)
+    tr = capi.TileRange(32, 8, 1, 3)
+    tiles_x = (W + 31) // 32
+    own = np.zeros((H, W), bool)
+    for t in range(1, tiles_x * ((H + 7) // 8), 3):
+        ty, tx = divmod(t, tiles_x)
+        own[ty * 8:ty * 8 + 8, tx * 32:tx * 32 + 32] = True
+    rgb, z, cnt, lin, st, progress = s.render_linear(cam, p, tr, fill=SENT)
+    assert progress == own.sum()
+    assert (lin[~own] == SENT).all() and lin[own].tobytes() == ref[3][own].tobytes()
+    # the device path
+    dev = torch.device("cuda", 0)
+    planes = [torch.zeros((H, W, 3), dtype=torch.uint8, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev),
+              torch.zeros((H, W), dtype=torch.uint8, device=dev), torch.full((H, W, 3), float(SENT), dtype=torch.float32, device=dev)]
+    side = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    s.render_tiles_device(cam, p, tr, 0, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), stream=side.cuda_stream,
+                          sync=True, want_stats=False, linear_ptr=planes[3].data_ptr())
+    torch.cuda.synchronize()
+    dl = planes[3].cpu().numpy()
+    assert (dl[~own] == SENT).all() and dl[own].tobytes() == ref[3][own].tobytes()
+
+
+@pytest.mark.gpu
+def test_cpp_shim_enable_linear_writes_a_pfm_consistent_with_its_png(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_linear_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_linear_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    png, pfm = str(tmp_path / "img.png"), str(tmp_path / "lin.pfm")
+    r = subprocess.run([exe, scenes.CORNELL, png, pfm, "photons=20000"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    fields = r.stdout.split()
+    assert fields[fields.index("untouched") + 1] == "0", r.stdout
+    lin = capi.image_read_pfm(pfm)
+    rgb = capi.image_read_rgb(png)
+    assert lin.shape == rgb.shape == (600, 800, 3)
+    assert np.isfinite(lin).all() and (lin > 0).any()
+    _assert_consistent_with_rgb8(lin, rgb, capi.default_params().gamma)
