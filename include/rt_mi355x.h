@@ -312,6 +312,10 @@ rt_status rt_image_zbuffer(const float *zbuffer, int32_t w, int32_t h, uint8_t *
  * RT_ERR_ARG. */
 rt_status rt_image_write_pfm(const char *path, const float *rgb, int32_t w, int32_t h);
 rt_status rt_image_read_pfm(const char *path, int32_t *w, int32_t *h, float *rgb, uint64_t cap);
+/* The same for a one-channel float plane (alpha): "Pf\n<w> <h>\n-1.0\n", one f32 per pixel, scanlines bottom to top.  Each
+ * reader takes its own kind only: rt_image_read_pfm refuses "Pf" files, rt_image_read_pfm1 refuses "PF" files (RT_ERR_IO). */
+rt_status rt_image_write_pfm1(const char *path, const float *v, int32_t w, int32_t h);
+rt_status rt_image_read_pfm1(const char *path, int32_t *w, int32_t *h, float *v, uint64_t cap);
 rt_status rt_image_sample_count(const uint8_t *sample_count, int32_t w, int32_t h, uint8_t *sample_count_img, int32_t *smax);
 
 /* generatePhotonMap as a whole (FIN/main.cpp:350-402) on the GPU: the photon pass (rt_photon_pass), ScalePhotonPowers,
@@ -480,6 +484,40 @@ rt_status rt_render_tiles_packed_linear_device(rt_scene *s, const rt_camera *cam
 rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
                                         int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
                                         uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev);
+
+/* ---- first-hit feature planes and the plane descriptor (additive to ABI 4: detected by the presence of the symbols;
+ *      RT_ABI_VERSION and the structs above are unchanged) ---------------------------------------------------------------
+ * What a caller needs AFTER the render: coverage for compositing, normal and albedo as denoising guides, an object id for
+ * picking and masking.  All planes are row-major and image-sized like rgb8.  For a pixel let J be the samples its final
+ * resolve used (0..min_sample-1, or 0..max_sample-1 when the variance gate sent it to the second batch), H the samples of J
+ * whose primary ray hit something, in increasing sample index, n = |H| -- the samples, mask and n the colour is averaged over
+ * (RenderPixel averages the hit samples only, FIN/main.cpp:273-338):
+ *   normal    float[W*H*3]  sum over H of N_j * (1/n), in float, in sample order; N_j is the world-space normal of the
+ *                           primary hit as the tracer returns it (what rt_trace_rays reports); NOT renormalised
+ *   albedo    float[W*H*3]  the same average of kd_j: the hit material's diffuse colour times its diffuse map at the hit's
+ *                           uvw (diffuse.Sample(uvw), FIN/main.cpp:531); the same definition for every shading model
+ *   alpha     float[W*H]    (float)n / (float)|J|
+ *   object_id int32[W*H]    the node (index into the scene's node array) of the LAST hit sample -- the sample z is taken
+ *                           from, so (z, object_id) describe one surface point
+ * An all-miss pixel holds 0, 0, 0 / 0, 0, 0 / 0 / -1.  Only the first hit is described: a mirror shows its own normal, albedo
+ * and id.  Pixels of tiles the call does not own, and of chunks not reached before rt_render_stop, keep the caller's values.
+ * The feature planes are byte-identical for identical inputs whatever the chunking, streams, tile range and entry point, in
+ * the default mode as well as under RT_RENDER_REPRODUCIBLE (one thread sums a pixel's samples in order; no atomics), and
+ * asking for them changes nothing in the other planes.  They cost a second trace of the hit primary rays (k_features, once
+ * per chunk); nothing is allocated or launched for a plane that is NULL.
+ * rt_outputs: struct_size must be sizeof(rt_outputs) of the caller (anything else: RT_ERR_ARG, so the struct can grow);
+ * rgb8, z, count are required (NULL: RT_ERR_ARG), every other plane is optional, NULL = not wanted.  With all of them NULL
+ * the two entry points are rt_render_begin / rt_render_tiles_device. */
+typedef struct rt_outputs {
+    uint32_t struct_size;
+    uint8_t *rgb8; float *z; uint8_t *count;
+    float *rgb_linear;
+    float *normal; float *albedo; float *alpha; int32_t *object_id;
+} rt_outputs;
+rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                  const rt_outputs *host_planes, rt_job **out);
+rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                         int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out);
 /* Waits for the asynchronous renders (sync == 0) issued so far on (scene, device) and returns
  * RT_ERR_LIMIT if any of them dropped rays or photon queries, RT_OK otherwise. */
 rt_status rt_render_check(rt_scene *s, int device);

@@ -51,6 +51,22 @@ class Params(C.Structure):
                 ("caustic_k", C.c_int32), ("caustic_radius", C.c_float), ("photon_count", C.c_int32), ("photon_bounce", C.c_int32)]
 
 
+class Outputs(C.Structure):
+    """rt_outputs: the planes of a render.  rgb8, z, count are required; the others are optional (NULL = not wanted)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb8", C.c_void_p), ("z", C.c_void_p), ("count", C.c_void_p),
+                ("rgb_linear", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("alpha", C.c_void_p),
+                ("object_id", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(Outputs), **planes)
+
+
+# the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels)
+OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
+                 "alpha": ("alpha", np.float32, 1), "object_id": ("object_id", np.int32, 1)}
+FEATURE_PLANES = ("normal", "albedo", "alpha", "object_id")
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -93,6 +109,7 @@ SYMBOLS = [
     "rt_scene_set_render_flags", "rt_scene_get_render_flags",
     "rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device", "rt_tiles_unpack_linear_device",
     "rt_image_write_pfm", "rt_image_read_pfm",
+    "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -136,8 +153,14 @@ def lib():
         _lib.rt_tiles_unpack_linear_device.argtypes = [C.c_int, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         _lib.rt_image_write_pfm.argtypes = [C.c_char_p, vp, i32, i32]
         _lib.rt_image_read_pfm.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), vp, C.c_uint64]
+        # the plane descriptor and the first-hit feature planes (rt_mi355x.h: "first-hit feature planes")
+        _lib.rt_render_begin_outputs.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
+        _lib.rt_render_tiles_outputs_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]
+        _lib.rt_image_write_pfm1.argtypes = [C.c_char_p, vp, i32, i32]
+        _lib.rt_image_read_pfm1.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), vp, C.c_uint64]
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
-                     "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm"):
+                     "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
+                     "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
             getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -252,6 +275,22 @@ def image_read_pfm(path):
     rgb = np.zeros((h.value, w.value, 3), np.float32)
     _check(lib().rt_image_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), _p(rgb), rgb.size))
     return rgb
+
+
+def image_write_pfm1(path, v):
+    """float (H, W) -> one-channel PFM ("Pf", little-endian, scanlines bottom to top)"""
+    v = np.ascontiguousarray(v, np.float32)
+    assert v.ndim == 2
+    _check(lib().rt_image_write_pfm1(os.fsencode(path), _p(v), v.shape[1], v.shape[0]))
+
+
+def image_read_pfm1(path):
+    """a one-channel PFM ("Pf") -> float32 (H, W), row 0 = top"""
+    w, h = C.c_int32(), C.c_int32()
+    _check(lib().rt_image_read_pfm1(os.fsencode(path), C.byref(w), C.byref(h), None, 0))
+    v = np.zeros((h.value, w.value), np.float32)
+    _check(lib().rt_image_read_pfm1(os.fsencode(path), C.byref(w), C.byref(h), _p(v), v.size))
+    return v
 
 
 def identity_map(texture=MAP_NONE):
@@ -519,7 +558,33 @@ class Scene:
         rgb, z, cnt, st, progress = self._render(cam, params, tiles, device, photon_pass, linear)
         return rgb, z, cnt, linear, st, progress
 
-    def _render(self, cam, params, tiles, device, photon_pass, linear):
+    def render_outputs(self, cam, params, planes=FEATURE_PLANES, tiles=None, device=0, photon_pass=False, fill=0.0, id_fill=-1):
+        """render() with the optional planes named in `planes` (any of linear, normal, albedo, alpha, object_id), through
+        rt_render_begin_outputs: a dict with rgb, z, count, stats, progress and one array per plane asked for -- float32
+        (H, W, 3) for linear / normal / albedo, float32 (H, W) for alpha, int32 (H, W) for object_id.  Pixels outside
+        `tiles` keep `fill` (object_id: `id_fill`)."""
+        h, w = cam.height, cam.width
+        out = {}
+        for name in planes:
+            _, dtype, ch = OUTPUT_PLANES[name]          # KeyError: no such plane
+            out[name] = np.full((h, w, 3) if ch == 3 else (h, w), id_fill if name == "object_id" else fill, dtype)
+        out["rgb"], out["z"], out["count"], out["stats"], out["progress"] = self._render(cam, params, tiles, device, photon_pass, None, dict(out))
+        return out
+
+    def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,
+                                    want_stats=True, linear_ptr=None, normal_ptr=None, albedo_ptr=None, alpha_ptr=None,
+                                    object_id_ptr=None):
+        """render_tiles_device through rt_render_tiles_outputs_device: every *_ptr that is not None names an image-sized
+        DEVICE plane to fill (float32 x 3 for linear / normal / albedo, float32 for alpha, int32 for object_id)."""
+        st = Stats()
+        o = Outputs(rgb8=rgb_ptr, z=z_ptr, count=cnt_ptr, rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr,
+                    alpha=alpha_ptr, object_id=object_id_ptr)
+        _check(lib().rt_render_tiles_outputs_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                    _stream_handle(stream), C.byref(o), 1 if sync else 0,
+                                                    C.byref(st) if want_stats else None))
+        return st
+
+    def _render(self, cam, params, tiles, device, photon_pass, linear, planes=None):
         if not photon_pass and params.photon_count != 0:
             q = Params()
             C.memmove(C.byref(q), C.byref(params), C.sizeof(Params))
@@ -529,7 +594,12 @@ class Scene:
         rgb, z, cnt = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32), np.zeros((h, w), np.uint8)
         tiles = tiles or TileRange(32, 8, 0, 1)
         job = C.c_void_p()
-        if linear is None:
+        if planes is not None:
+            o = Outputs(rgb8=rgb.ctypes.data, z=z.ctypes.data, count=cnt.ctypes.data,
+                        **{OUTPUT_PLANES[name][0]: a.ctypes.data for name, a in planes.items()})
+            _check(lib().rt_render_begin_outputs(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                 C.byref(o), C.byref(job)))
+        elif linear is None:
             _check(lib().rt_render_begin(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
                                          _p(rgb), _p(z), _p(cnt), C.byref(job)))
         else:

@@ -303,14 +303,15 @@ bool ReadImageRGB(const char *filename, int &w, int &h, std::vector<uint8_t> &rg
 }
 
 // PFM, the portable float map: "PF\n<w> <h>\n<scale>\n", then w*h RGB triples of f32, the BOTTOM scanline first; a negative
-// scale means little-endian samples.  Written as "-1.0" (this library only writes little-endian).
-bool WritePFM(const char *filename, const float *rgb, int width, int height)
+// scale means little-endian samples.  Written as "-1.0" (this library only writes little-endian).  channels == 1: the grey
+// variant, magic "Pf", one f32 per pixel.
+bool WritePFM(const char *filename, const float *rgb, int width, int height, int channels)
 {
-    if (width <= 0 || height <= 0) return false;
+    if (width <= 0 || height <= 0 || (channels != 1 && channels != 3)) return false;
     FILE *fp = fopen(filename, "wb");
     if (!fp) return false;
-    bool ok = fprintf(fp, "PF\n%d %d\n-1.0\n", width, height) > 0;
-    const size_t row = (size_t)width * 3;
+    bool ok = fprintf(fp, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height) > 0;
+    const size_t row = (size_t)width * channels;
     std::vector<uint8_t> buf(row * 4);
     for (int y = height - 1; ok && y >= 0; y--) {
         const float *src = rgb + (size_t)y * row;
@@ -324,9 +325,12 @@ bool WritePFM(const char *filename, const float *rgb, int width, int height)
     return fclose(fp) == 0 && ok;
 }
 
-// Reads a 3-channel PFM of either byte order (the sign of the scale) back into row-major, top-row-first floats.
-bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std::string *err)
+// Reads a 3-channel PFM ("PF"; channels == 1: a one-channel "Pf", and only that) of either byte order (the sign of the scale)
+// back into row-major, top-row-first floats.
+bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std::string *err, int channels)
 {
+    if (channels != 1 && channels != 3) { if (err) *err = "PFM files have 1 or 3 channels"; return false; }
+    const uint8_t magic = channels == 3 ? 'F' : 'f';
     w = h = 0;
     rgb.clear();
     FILE *fp = fopen(filename, "rb");
@@ -336,7 +340,10 @@ bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std:
     size_t n;
     while ((n = fread(buf, 1, sizeof buf, fp)) > 0) f.insert(f.end(), buf, buf + n);
     fclose(fp);
-    if (f.size() < 3 || f[0] != 'P' || f[1] != 'F' || !isspace(f[2])) { if (err) *err = "not a 3-channel PFM (magic \"PF\")"; return false; }
+    if (f.size() < 3 || f[0] != 'P' || f[1] != magic || !isspace(f[2])) {
+        if (err) *err = channels == 3 ? "not a 3-channel PFM (magic \"PF\")" : "not a 1-channel PFM (magic \"Pf\")";
+        return false;
+    }
     // three header tokens after the magic, each ended by one whitespace character
     size_t pos = 3;
     std::string tok[3];
@@ -354,7 +361,7 @@ bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std:
     const double scale = strtod(tok[2].c_str(), &end);
     if (*end || !(scale == scale) || scale == 0) { if (err) *err = "bad PFM scale"; return false; }
     if (iw <= 0 || ih <= 0 || iw > (1 << 20) || ih > (1 << 20)) { if (err) *err = "bad PFM size"; return false; }
-    const size_t row = (size_t)iw * 3, count = row * (size_t)ih;
+    const size_t row = (size_t)iw * channels, count = row * (size_t)ih;
     if (f.size() - pos < count * 4) { if (err) *err = "truncated PFM samples"; return false; }
     const bool little = scale < 0;
     rgb.resize(count);

@@ -350,9 +350,10 @@ int SampleCountImage(const uint8_t *sampleCount, size_t size, uint8_t *sampleCou
 bool ReadImageRGB(const char *filename, int &w, int &h, std::vector<uint8_t> &rgb, std::string *err);
 // minimal PNG writer (8-bit grey or RGB, stored deflate blocks) for RenderImage::SavePNG
 bool WritePNG(const char *filename, const uint8_t *data, int width, int height, int comps);
-// PFM ("PF": 3 channels of little-endian f32, scanlines bottom to top) of a row-major, top-row-first float RGB image
-bool WritePFM(const char *filename, const float *rgb, int width, int height);
-bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std::string *err);
+// PFM ("PF": 3 channels of little-endian f32, scanlines bottom to top) of a row-major, top-row-first float RGB image;
+// channels == 1: the one-channel variant "Pf" (a reader asked for one kind refuses the other)
+bool WritePFM(const char *filename, const float *rgb, int width, int height, int channels = 3);
+bool ReadPFM(const char *filename, int &w, int &h, std::vector<float> &rgb, std::string *err, int channels = 3);
 
 }  // namespace rt
 #endif

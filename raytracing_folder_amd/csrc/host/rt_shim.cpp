@@ -13,7 +13,35 @@ void RenderImage::Init(int w, int h)
     sampleCount.assign((size_t)w * h, 0);
     zbufferImg.clear(); sampleCountImg.clear();
     if (linearEnabled) linear.assign((size_t)w * h * 3, 0.0f);
+    if (featuresEnabled) { featuresEnabled = false; EnableFeatures(); }
     finalPixels = 0;
+}
+
+void RenderImage::EnableFeatures()
+{
+    if (!featuresEnabled) {
+        const size_t n = (size_t)width * height;
+        normals.assign(n * 3, 0.0f); albedo.assign(n * 3, 0.0f); alpha.assign(n, 0.0f); objectIds.assign(n, -1);
+    }
+    featuresEnabled = true;
+}
+
+// a multiplicative hash of id + 1, so that neighbouring ids get unrelated colours; every channel at least 64: no object is black
+void RenderImage::ObjectIdColor(int32_t id, uint8_t rgb[3])
+{
+    if (id < 0) { rgb[0] = rgb[1] = rgb[2] = 0; return; }
+    const uint32_t h = ((uint32_t)id + 1u) * 2654435761u;
+    rgb[0] = (uint8_t)(64u + ((h >> 8) & 0xFFu) % 192u); rgb[1] = (uint8_t)(64u + ((h >> 16) & 0xFFu) % 192u); rgb[2] = (uint8_t)(64u + ((h >> 24) & 0xFFu) % 192u);
+}
+
+bool RenderImage::SaveFeatureImages(const char *prefix) const
+{
+    if (!featuresEnabled || !prefix) return false;
+    const std::string p(prefix);
+    std::vector<uint8_t> ids(objectIds.size() * 3);
+    for (size_t i = 0; i < objectIds.size(); i++) ObjectIdColor(objectIds[i], &ids[3 * i]);
+    return WritePFM((p + "_normal.pfm").c_str(), normals.data(), width, height) && WritePFM((p + "_albedo.pfm").c_str(), albedo.data(), width, height) &&
+           WritePFM((p + "_alpha.pfm").c_str(), alpha.data(), width, height, 1) && WritePNG((p + "_id.png").c_str(), ids.data(), width, height, 3);
 }
 
 void RenderImage::EnableLinear()
@@ -101,7 +129,16 @@ bool Renderer::BeginRender()
     for (int r = 0; r < N; r++) {
         const rt_tile_range mine = {32, 8, r, N};
         rt_job *job = nullptr;
-        if (renderImage.LinearEnabled())
+        if (renderImage.FeaturesEnabled()) {
+            rt_outputs o;
+            memset(&o, 0, sizeof o);
+            o.struct_size = (uint32_t)sizeof o;
+            o.rgb8 = renderImage.GetPixels(); o.z = renderImage.GetZBuffer(); o.count = renderImage.GetSampleCount();
+            o.rgb_linear = renderImage.GetLinearPixels();           // NULL unless EnableLinear()
+            o.normal = renderImage.GetNormals(); o.albedo = renderImage.GetAlbedo(); o.alpha = renderImage.GetAlpha();
+            o.object_id = renderImage.GetObjectIds();
+            st = rt_render_begin_outputs(handle, &d.camera, &params, &mine, devs[r], &o, &job);
+        } else if (renderImage.LinearEnabled())
             st = rt_render_begin_linear(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
                                         renderImage.GetSampleCount(), renderImage.GetLinearPixels(), &job);
         else

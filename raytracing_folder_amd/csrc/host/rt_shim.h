@@ -22,6 +22,10 @@ class RenderImage {
     std::vector<uint8_t> zbufferImg, sampleCount, sampleCountImg;
     std::vector<float> linear;         // opt-in (EnableLinear): pre-gamma float RGB[width*height*3]
     bool linearEnabled = false;
+    // opt-in (EnableFeatures): the first-hit planes of rt_outputs -- normal, albedo (float RGB), alpha (float), object id
+    std::vector<float> normals, albedo, alpha;
+    std::vector<int32_t> objectIds;
+    bool featuresEnabled = false;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -40,6 +44,18 @@ public:
     bool LinearEnabled() const { return linearEnabled; }
     float *GetLinearPixels() { return linearEnabled ? linear.data() : nullptr; }
     bool SaveLinearImage(const char *filename) const { return linearEnabled && WritePFM(filename, linear.data(), width, height); }   // PFM
+    // the first-hit feature planes (rt_outputs in rt_mi355x.h: normal, albedo, alpha, object id), row-major like GetPixels();
+    // nothing is allocated until EnableFeatures() and the getters are NULL without it.  Renderer::BeginRender fills them
+    // through rt_render_begin_outputs.  SaveFeatureImages writes <prefix>_normal.pfm, <prefix>_albedo.pfm (PFM),
+    // <prefix>_alpha.pfm (one-channel PFM) and <prefix>_id.png (ObjectIdColor of the id).
+    void EnableFeatures();
+    bool FeaturesEnabled() const { return featuresEnabled; }
+    float *GetNormals() { return featuresEnabled ? normals.data() : nullptr; }
+    float *GetAlbedo() { return featuresEnabled ? albedo.data() : nullptr; }
+    float *GetAlpha() { return featuresEnabled ? alpha.data() : nullptr; }
+    int32_t *GetObjectIds() { return featuresEnabled ? objectIds.data() : nullptr; }
+    static void ObjectIdColor(int32_t id, uint8_t rgb[3]);      // a fixed colour per id; -1 (no object) is black
+    bool SaveFeatureImages(const char *prefix) const;
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

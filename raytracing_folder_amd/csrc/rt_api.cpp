@@ -40,6 +40,8 @@ void rtk_launch_resolve(hipStream_t, const DevScene &, const DevWork &, const De
                         float, float, int, const float *, uint8_t *, float *, uint8_t *, void *, int, bool linear = false,
                         float *rgb_linear = nullptr);
 void rtk_launch_unpack_tiles(hipStream_t, const void *, int, int, int, int, int, int, uint8_t *, float *, uint8_t *, float *rgb_linear = nullptr);
+void rtk_launch_features(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevCamera &, const DevTiles &, uint32_t, uint32_t,
+                         uint8_t *second, const DevFeatures &, bool by_walk);
 
 // k_gather is a persistent grid that pulls query batches from a counter: enough workgroups to fill
 // every CU at the kernel's occupancy (256 CUs x 5 resident workgroups of 4 waves)
@@ -151,11 +153,12 @@ struct Workspace {
     DevBuf sample_rgb, sample_z, sample_hit, rq[2][5], pq[3], cq[3], counts, pixel_list;
     DevBuf bvh_spill;                   // traversal-stack entries beyond the kernels' LDS stacks (only for scenes whose BVHs can need them)
     DevBuf sample_fx;                   // reproducible renders only: 3 x int64 fixed-point secondary colour per sample (allocated on first use)
+    DevBuf feat_second;                 // renders with feature planes only: one byte per chunk pixel, 1 = it took the second batch (k_mark_second)
     size_t samples = 0; uint32_t rq_cap = 0, pq_cap = 0;
     hipStream_t stream = nullptr;       // slot 0 runs on the caller's / the device's main stream instead
     void release()
     {
-        for (DevBuf *b : {&sample_rgb, &sample_z, &sample_hit, &counts, &pixel_list, &bvh_spill, &sample_fx}) b->release();
+        for (DevBuf *b : {&sample_rgb, &sample_z, &sample_hit, &counts, &pixel_list, &bvh_spill, &sample_fx, &feat_second}) b->release();
         for (int i = 0; i < 2; i++) for (int k = 0; k < 5; k++) rq[i][k].release();
         for (int k = 0; k < 3; k++) { pq[k].release(); cq[k].release(); }
         if (stream) (void)hipStreamDestroy(stream);
@@ -272,6 +275,9 @@ struct rt_job {
     // renderImage.GetPixels() while the workers run)
     uint8_t *host_rgb = nullptr, *host_count = nullptr; float *host_z = nullptr;
     float *host_linear = nullptr;       // rt_render_begin_linear: the linear plane, copied back like the others
+    // rt_render_begin_outputs: the first-hit feature planes that were asked for, copied back like the others
+    float *host_normal = nullptr, *host_albedo = nullptr, *host_alpha = nullptr; int32_t *host_id = nullptr;
+    bool wants_features() const { return host_normal || host_albedo || host_alpha || host_id; }
     rt_setup_ms setup{};                // the photon pass this job ran first (all zero when it did not)
 };
 
@@ -537,6 +543,28 @@ extern "C" rt_status rt_image_read_pfm(const char *path, int32_t *w, int32_t *h,
     if (rgb) {
         if (cap < d.size()) return fail(RT_ERR_ARG, "rt_image_read_pfm: room for %llu floats, need %zu", (unsigned long long)cap, d.size());
         memcpy(rgb, d.data(), d.size() * sizeof(float));
+    }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_image_write_pfm1(const char *path, const float *v, int32_t w, int32_t h)
+{
+    if (!path || !v || w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_image_write_pfm1: bad argument");
+    if (!rt::WritePFM(path, v, w, h, 1)) return fail(RT_ERR_IO, "rt_image_write_pfm1(%s): cannot write", path);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_image_read_pfm1(const char *path, int32_t *w, int32_t *h, float *v, uint64_t cap)
+{
+    if (!path || !w || !h) return fail(RT_ERR_ARG, "rt_image_read_pfm1: NULL argument");
+    int iw = 0, ih = 0;
+    std::vector<float> d;
+    std::string err;
+    if (!rt::ReadPFM(path, iw, ih, d, &err, 1)) return fail(RT_ERR_IO, "rt_image_read_pfm1(%s): %s", path, err.c_str());
+    *w = iw; *h = ih;
+    if (v) {
+        if (cap < d.size()) return fail(RT_ERR_ARG, "rt_image_read_pfm1: room for %llu floats, need %zu", (unsigned long long)cap, d.size());
+        memcpy(v, d.data(), d.size() * sizeof(float));
     }
     return RT_OK;
 }
@@ -1458,7 +1486,7 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
 static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                    hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
                                    bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
-                                   float *lin_dev);
+                                   float *lin_dev, const DevFeatures *feat);
 
 // Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
 // half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
@@ -1466,18 +1494,19 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
 // is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
 // library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
 // `linear`: the linear plane is wanted -- into lin_dev (device planes; a job's host copy follows), or as 24-byte packed records.
+// `feat`: the image-sized device planes of the first-hit features that are wanted (NULL: none; a strided job stages its own).
 static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                               hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
                               bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev = nullptr, bool linear = false,
-                              float *lin_dev = nullptr)
+                              float *lin_dev = nullptr, const DevFeatures *feat = nullptr)
 {
     rt_status st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                                     packed_dev, false, linear, lin_dev);
+                                     packed_dev, false, linear, lin_dev, feat);
     int attempts = 1;
     if (st == RT_ERR_OVERFLOW_RETRY) {
         attempts = 2;
         st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                               packed_dev, true, linear, lin_dev);
+                               packed_dev, true, linear, lin_dev, feat);
     }
     if (st == RT_OK && stats_out) stats_out->attempts = (uint64_t)attempts;
     if (st == RT_OK && job) job->stats.attempts = (uint64_t)attempts;
@@ -1487,7 +1516,7 @@ static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params
 static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                    hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
                                    bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
-                                   float *lin_dev)
+                                   float *lin_dev, const DevFeatures *feat)
 {
     rt_status st = validate_render(s, cam, p, tiles);
     if (st) return st;
@@ -1574,6 +1603,8 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     D->qhist_used = ray_factor > 0 || query_factor > 0;
     // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
     const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
+    // first-hit feature planes (k_features after each chunk's last resolve): only when a plane was asked for
+    const bool features = (feat && feat->any()) || (job && job->wants_features());
     DevWork Ws[RT_STREAMS];
     unsigned long long *Fx[RT_STREAMS] = {};
     int n_ready = 0;
@@ -1591,6 +1622,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                                    reproducible))) return st;
         Ws[i] = make_work(D, i);
         if (reproducible) Fx[i] = (unsigned long long *)D->ws[i].sample_fx.p;
+        if (features && (st = D->ws[i].feat_second.ensure(std::max<uint64_t>(ppc, 1)))) return st;
         n_ready++;
     }
     n_slots = n_ready;
@@ -1603,6 +1635,21 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     if (job_packed) {
         if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * rec_bytes))) return st;
         packed_dev = job_packed_buf.p;
+    }
+    // where k_features writes: the caller's image-sized device planes, or -- a strided job, whose rows are shared with other jobs --
+    // staging planes indexed by this call's tile walk, scattered on the host like the packed records (finish_oldest)
+    DevFeatures fdev;
+    if (feat) fdev = *feat;
+    DevBuf feat_stage[4];
+    struct ReleaseStage { DevBuf *b; ~ReleaseStage() { for (int i = 0; i < 4; i++) b[i].release(); } } feat_stage_release{feat_stage};
+    const bool feat_by_walk = features && job_packed;
+    if (feat_by_walk) {
+        const uint64_t n = std::max<uint64_t>(total_px, 1);
+        fdev = DevFeatures();
+        if (job->host_normal) { if ((st = feat_stage[0].ensure(n * 12))) return st; fdev.normal = (float *)feat_stage[0].p; }
+        if (job->host_albedo) { if ((st = feat_stage[1].ensure(n * 12))) return st; fdev.albedo = (float *)feat_stage[1].p; }
+        if (job->host_alpha) { if ((st = feat_stage[2].ensure(n * 4))) return st; fdev.alpha = (float *)feat_stage[2].p; }
+        if (job->host_id) { if ((st = feat_stage[3].ensure(n * 4))) return st; fdev.object_id = (int32_t *)feat_stage[3].p; }
     }
     const bool want_stats = stats_out != nullptr || job != nullptr;
     Timing tm[RT_STREAMS];
@@ -1695,6 +1742,26 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                 job->host_count[o] = (uint8_t)(v.y >> 24);
                 if (linear && job->host_linear) memcpy(&job->host_linear[3 * o], &rec[i * words + 1], 12);
             }
+            if (feat_by_walk) {
+                // the chunk's run of each staged feature plane, scattered the same way
+                auto scatter = [&](const void *stage, void *host, size_t elem) -> rt_status {
+                    if (!stage || !host) return RT_OK;
+                    std::vector<uint8_t> run((size_t)f.npix * elem);
+                    HIP_TRY(hipMemcpy(run.data(), (const uint8_t *)stage + f.q0 * elem, run.size(), hipMemcpyDeviceToHost));
+                    for (uint32_t i = 0; i < f.npix; i++) {
+                        const uint64_t q = f.q0 + i;
+                        const int t = dt.first + (int)(q / tile_px) * dt.stride;
+                        const int w = (int)(q % tile_px);
+                        const int x = (t % dt.tiles_x) * dt.tile_w + w % dt.tile_w, y = (t / dt.tiles_x) * dt.tile_h + w / dt.tile_w;
+                        if (x >= cam->width || y >= cam->height) continue;
+                        memcpy((uint8_t *)host + ((size_t)y * cam->width + x) * elem, run.data() + (size_t)i * elem, elem);
+                    }
+                    return RT_OK;
+                };
+                rt_status fs;
+                if ((fs = scatter(fdev.normal, job->host_normal, 12)) || (fs = scatter(fdev.albedo, job->host_albedo, 12)) ||
+                    (fs = scatter(fdev.alpha, job->host_alpha, 4)) || (fs = scatter(fdev.object_id, job->host_id, 4))) return fs;
+            }
         } else if (job->host_rgb) {
             // rows spanned by this chunk's tiles (tile-major order: a contiguous band of tile rows; a row shared
             // with a chunk still in flight may arrive torn and is copied again when that chunk finishes)
@@ -1707,6 +1774,10 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                 HIP_TRY(hipMemcpy(job->host_z + o, z_dev + o, 4 * n, hipMemcpyDeviceToHost));
                 HIP_TRY(hipMemcpy(job->host_count + o, count_dev + o, n, hipMemcpyDeviceToHost));
                 if (lin_dev && job->host_linear) HIP_TRY(hipMemcpy(job->host_linear + 3 * o, lin_dev + 3 * o, 12 * n, hipMemcpyDeviceToHost));
+                if (fdev.normal && job->host_normal) HIP_TRY(hipMemcpy(job->host_normal + 3 * o, fdev.normal + 3 * o, 12 * n, hipMemcpyDeviceToHost));
+                if (fdev.albedo && job->host_albedo) HIP_TRY(hipMemcpy(job->host_albedo + 3 * o, fdev.albedo + 3 * o, 12 * n, hipMemcpyDeviceToHost));
+                if (fdev.alpha && job->host_alpha) HIP_TRY(hipMemcpy(job->host_alpha + o, fdev.alpha + o, 4 * n, hipMemcpyDeviceToHost));
+                if (fdev.object_id && job->host_id) HIP_TRY(hipMemcpy(job->host_id + o, fdev.object_id + o, 4 * n, hipMemcpyDeviceToHost));
             }
         }
         // monotone also when the frame is rendered a second time with larger queues (RT_ERR_OVERFLOW_RETRY)
@@ -1740,6 +1811,9 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
                                    p->max_sample - p->min_sample, p->max_sample, 1, nullptr, Fx[slot]))) return st;
             if ((st = timed_resolve(1))) return st;
         }
+        // the feature planes of the chunk, from its finished working set (hit flags, pixel list) on the same stream
+        if (features && fdev.any())
+            rtk_launch_features(cs, D->scene, W, *p, dc, dt, (uint32_t)q0, npix, (uint8_t *)D->ws[slot].feat_second.p, fdev, feat_by_walk);
         HIP_TRY(hipGetLastError());
         if (job) {
             InFlight f; f.q0 = q0; f.npix = npix;
@@ -1850,6 +1924,31 @@ extern "C" rt_status rt_render_tiles_linear_device(rt_scene *s, const rt_camera 
     if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_render_tiles_linear_device: the linear plane is required");
     return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, rgb8_dev, z_dev, count_dev,
                         sync != 0, stats_out, nullptr, nullptr, true, rgb_linear_dev);
+}
+
+// rt_outputs: the caller's sizeof first, then the three required planes
+static rt_status check_outputs(const char *name, const rt_outputs *o)
+{
+    if (!o) return fail(RT_ERR_ARG, "%s: the plane descriptor is NULL", name);
+    if (o->struct_size != (uint32_t)sizeof(rt_outputs))
+        return fail(RT_ERR_ARG, "%s: rt_outputs.struct_size is %u, this library's is %zu", name, o->struct_size, sizeof(rt_outputs));
+    if (!o->rgb8 || !o->z || !o->count) return fail(RT_ERR_ARG, "%s: rgb8, z and count are required", name);
+    return RT_OK;
+}
+
+// RenderPixel's outputs (FIN/main.cpp:273-338) into device planes, with the optional ones of rt_outputs: the linear colour and
+// the first hit's normal, albedo, coverage and node (k_features)
+extern "C" rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                    int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out)
+{
+    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_outputs_device: scene is NULL");
+    rt_status st = check_outputs("rt_render_tiles_outputs_device", device_planes);
+    if (st) return st;
+    DevFeatures f;
+    f.normal = device_planes->normal; f.albedo = device_planes->albedo; f.alpha = device_planes->alpha; f.object_id = device_planes->object_id;
+    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, device_planes->rgb8, device_planes->z,
+                        device_planes->count, sync != 0, stats_out, nullptr, nullptr, device_planes->rgb_linear != nullptr,
+                        device_planes->rgb_linear, &f);
 }
 
 // both packed entry points: 8-byte records, or 24-byte ones with the linear plane (linear)
@@ -1996,9 +2095,11 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
 static rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
                                   rt_setup_ms *ms_out, bool own_job);
 
-// rt_render_begin and rt_render_begin_linear (rgb_linear != NULL: the linear plane as a fourth output)
+// rt_render_begin, rt_render_begin_linear (rgb_linear != NULL: the linear plane as a fourth output) and rt_render_begin_outputs
+// (feat: the host planes of the first-hit features that are wanted)
+struct HostFeatures { float *normal = nullptr, *albedo = nullptr, *alpha = nullptr; int32_t *object_id = nullptr; };
 static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out)
+                              uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out, const HostFeatures &feat = HostFeatures())
 {
     if (!s || !out) return fail(RT_ERR_ARG, "%s: scene/out is NULL", name);
     rt_status st = validate_render(s, cam, p, tiles);
@@ -2009,12 +2110,14 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
     rt_job *job = new rt_job;
     job->scene = s;
     job->host_rgb = rgb8; job->host_z = z; job->host_count = count; job->host_linear = rgb_linear;
+    job->host_normal = feat.normal; job->host_albedo = feat.albedo; job->host_alpha = feat.alpha; job->host_id = feat.object_id;
     s->live_jobs.fetch_add(1);
     const rt_camera camv = *cam; const rt_params pv = *p; const rt_tile_range tv = *tiles;
     job->worker = std::thread([=]() {
         rt_status r = RT_OK;
         const size_t npx = (size_t)camv.width * camv.height;
         uint8_t *d_rgb = nullptr, *d_cnt = nullptr; float *d_z = nullptr, *d_lin = nullptr;
+        DevFeatures d_feat;
         auto body = [&]() -> rt_status {
             HIP_TRY(hipSetDevice(device));
             // BeginRender calls generatePhotonMap() before it spawns its workers (FIN/main.cpp:984-998, :350-402); here the
@@ -2046,15 +2149,28 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
                 HIP_TRY(hipMalloc((void **)&d_lin, npx * 12));
                 HIP_TRY(hipMemcpy(d_lin, rgb_linear, npx * 12, hipMemcpyHostToDevice));
             }
+            // and so do the feature planes (a strided job stages them by its tile walk instead: render_tiles_once)
+            if (tv.stride == 1) {
+                auto plane = [&](void **d, const void *h, size_t bytes) -> rt_status {
+                    if (!h) return RT_OK;
+                    HIP_TRY(hipMalloc(d, bytes));
+                    HIP_TRY(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+                    return RT_OK;
+                };
+                rt_status fs;
+                if ((fs = plane((void **)&d_feat.normal, feat.normal, npx * 12)) || (fs = plane((void **)&d_feat.albedo, feat.albedo, npx * 12)) ||
+                    (fs = plane((void **)&d_feat.alpha, feat.alpha, npx * 4)) || (fs = plane((void **)&d_feat.object_id, feat.object_id, npx * 4))) return fs;
+            }
             // render_tiles copies every finished band of rows back into the caller's buffers
             return render_tiles(s, &camv, &pv, &tv, device, nullptr, false, d_rgb, d_z, d_cnt, true, nullptr, job, nullptr,
-                                rgb_linear != nullptr, d_lin);
+                                rgb_linear != nullptr, d_lin, &d_feat);
         };
         r = body();
         if (d_rgb) (void)hipFree(d_rgb);
         if (d_z) (void)hipFree(d_z);
         if (d_cnt) (void)hipFree(d_cnt);
         if (d_lin) (void)hipFree(d_lin);
+        for (void *d : {(void *)d_feat.normal, (void *)d_feat.albedo, (void *)d_feat.alpha, (void *)d_feat.object_id}) if (d) (void)hipFree(d);
         job->status = r;
         if (r) job->error = g_err;
         job->done.store(true);
@@ -2075,6 +2191,19 @@ extern "C" rt_status rt_render_begin_linear(rt_scene *s, const rt_camera *cam, c
 {
     if (!rgb_linear) return fail(RT_ERR_ARG, "rt_render_begin_linear: the linear plane is required");
     return render_begin("rt_render_begin_linear", s, cam, p, tiles, device, rgb8, z, count, rgb_linear, out);
+}
+
+// BeginRender (FIN/main.cpp:984-1010) with the planes RenderPixel (:273-338) could have kept: its colour before gamma, and the
+// first hit's normal, albedo, coverage and node
+extern "C" rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                             const rt_outputs *host_planes, rt_job **out)
+{
+    rt_status st = check_outputs("rt_render_begin_outputs", host_planes);
+    if (st) return st;
+    HostFeatures f;
+    f.normal = host_planes->normal; f.albedo = host_planes->albedo; f.alpha = host_planes->alpha; f.object_id = host_planes->object_id;
+    return render_begin("rt_render_begin_outputs", s, cam, p, tiles, device, host_planes->rgb8, host_planes->z, host_planes->count,
+                        host_planes->rgb_linear, out, f);
 }
 
 extern "C" int rt_render_progress(rt_job *j) { return j ? j->progress.load() : 0; }

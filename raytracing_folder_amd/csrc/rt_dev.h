@@ -237,6 +237,11 @@ struct DevWork {
     unsigned long long *stats;
     uint32_t *bvh_spill;      // DevScene::bvh_spill of this working set's launches
 };
+// the first-hit feature planes of a render (k_features), device pointers; a NULL plane is not wanted
+struct DevFeatures {
+    float *normal = nullptr, *albedo = nullptr, *alpha = nullptr; int32_t *object_id = nullptr;
+    bool any() const { return normal || albedo || alpha || object_id; }
+};
 // The hot ones -- work counters and queue tails that every wave of a launch adds to -- sit RT_CTR_STRIDE uint32s apart: device-scope
 // atomics are executed at the memory side, one after the other per channel (about 15-20 ns each), so counters that share a line queue
 // behind each other (r4: the end of a k_gather launch was 41 000 failing grabs on eight adjacent counters = 0.8 ms).  4 KB + 256 B

@@ -2844,6 +2844,96 @@ __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
 }
 
 // ------------------------------------------------------------------------------------------------
+// First-hit feature planes (opt-in): normal, albedo, alpha, object id of every pixel of a chunk, from the chunk's finished
+// working set.  The reference averages a pixel over its HIT samples only (RenderPixel, FIN/main.cpp:273-338), so with J the
+// samples the final resolve used and H the hit ones among them (n = |H|, in sample order):
+//   normal = sum_H N_j * (1/n)        N_j = Hit::N of the primary ray as trace<>() returns it; not renormalised
+//   albedo = sum_H kd_j * (1/n)       kd of material_colors<TEX>(): diffuse x its map at the hit's uvw (FIN/main.cpp:531)
+//   alpha  = n / |J|                  the coverage k_resolve knows and drops
+//   object_id = Hit::node of the LAST hit sample, the one the z plane is taken from
+// and 0, 0, 0, -1 for an all-miss pixel.  Run once per chunk after its last k_resolve, never in a default render.
+//
+// The primary Hit is not kept per sample (28 B x samples) and the tracing kernels carry no feature template: this kernel
+// traces the hit primary samples again, closest hit only, through primary_setup + trace<false, MODEL, TEX> -- the same ray,
+// the same intersection code, hence the same Hit bit for bit.  ONE LANE PER PIXEL walks its samples in index order, so the
+// sums have one order by construction (no atomics): the planes are byte-identical whatever the chunking, streams, tiles and
+// entry point.  Lanes of a wave hold consecutive pixels of a tile row and trace the same sample index together.
+// ------------------------------------------------------------------------------------------------
+struct FeatureArgs {
+    DevCamera cam; DevTiles tiles;
+    uint32_t q0, npix;
+    int min_sample, max_sample;
+    FastDiv div_ms;
+    const uint8_t *second;      // [npix] 1: the pixel took the second batch (k_mark_second), so J is all max_sample samples
+    int by_walk;                // 0: planes are image-sized, pixel (x, y) at y*width + x; 1: indexed by the tile walk, q0 + ql
+    float *normal, *albedo, *alpha; int32_t *object_id;      // any of them may be NULL
+};
+
+// second[ql] = 1 for the pixels k_resolve's first phase put on the chunk's pixel list (the list survives the second phase)
+__global__ __launch_bounds__(256) void k_mark_second(DevWork W, uint8_t *second, uint32_t npix)
+{
+    const uint32_t n = W.counts[CNT_PIXLIST];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t ql = W.pixel_list[i];
+        if (ql < npix) second[ql] = 1;
+    }
+}
+
+// LDS: the traversal stack of k_primary (32 entries x 256 lanes = 32 KB) + 2 KB of Halton tables: four workgroups, i.e. four
+// waves per SIMD, fit a CU's 160 KB, which the 128-VGPR budget of four waves matches -- the kernel only traces, it does not
+// shade (120 VGPRs, no scratch).  With textures the bilinear lookups do not fit that budget (60 VGPRs spilled at four waves,
+// 20 at three): three waves per SIMD there.
+template <int MODEL, bool TEX>
+__attribute__((amdgpu_waves_per_eu(TEX ? 3 : 4, TEX ? 3 : 4))) __global__ __launch_bounds__(RT_BLOCK) void k_features(ShadeCtx C, FeatureArgs F)
+{
+    __shared__ uint32_t s_stack[RT_BVH_STACK * RT_BLOCK];
+    const BvhStack stack = bvh_stack(s_stack, RT_BVH_STACK, C.S.bvh_spill);
+    Counters cnt = {0, 0, 0, 0, 0};                 // trace<>() counts into it; never flushed: the statistics are the render's
+    // primary_setup as k_primary calls it for samples 0..max_sample-1 of every pixel: gid = ql*max_sample + j
+    PrimaryArgs A;
+    A.cam = F.cam; A.tiles = F.tiles; A.q0 = F.q0; A.npix = F.npix; A.j0 = 0; A.ns = F.max_sample; A.max_sample = F.max_sample; A.mode = 0;
+    A.rays = nullptr; A.div_ns = F.div_ms; A.lds_rays = 0; A.qsrc_count = nullptr;
+    const unsigned long long total = (unsigned long long)F.npix * (unsigned long long)F.max_sample;
+    __shared__ float s_h2[RT_BLOCK], s_h3[RT_BLOCK];
+    const bool h_table = F.max_sample <= RT_BLOCK;
+    if (h_table && (int)threadIdx.x < F.max_sample) { s_h2[threadIdx.x] = halton((int)threadIdx.x, 2); s_h3[threadIdx.x] = halton((int)threadIdx.x, 3); }
+    __syncthreads();
+    const bool need_trace = F.normal != nullptr || F.albedo != nullptr || F.object_id != nullptr;
+    for (uint32_t ql = blockIdx.x * blockDim.x + threadIdx.x; ql < F.npix; ql += gridDim.x * blockDim.x) {
+        int x = 0, y = 0;
+        if (!pixel_of(F.tiles, F.cam, F.q0 + ql, x, y)) continue;
+        const int ns = F.second[ql] ? F.max_sample : F.min_sample;
+        const uint8_t *hitf = C.W.sample_hit + (size_t)ql * F.max_sample;
+        int n = 0;
+        for (int j = 0; j < ns; j++) n += hitf[j] ? 1 : 0;
+        V3 nrm = mk(0, 0, 0), alb = mk(0, 0, 0);
+        int id = -1;
+        if (n > 0 && need_trace) {
+            const float inv = 1 / (float)n;
+            for (int j = 0; j < ns; j++) {
+                if (!hitf[j]) continue;
+                PathIn in;
+                if (!primary_setup(C, A, (unsigned long long)ql * (unsigned)F.max_sample + (unsigned)j, total, h_table, s_h2, s_h3, in)) continue;
+                Hit h;
+                if (!trace<false, MODEL, TEX>(C.S, in.o, in.d, BIGFLOAT, h, stack, cnt)) continue;
+                nrm = nrm + h.N * inv;
+                if (F.albedo) {
+                    V3 kd, ks;
+                    material_colors<TEX>(C.S, h, C.S.materials[C.S.node_material[h.node]], kd, ks);
+                    alb = alb + kd * inv;
+                }
+                id = h.node;
+            }
+        }
+        const size_t o = F.by_walk ? (size_t)F.q0 + ql : (size_t)y * F.cam.width + x;
+        if (F.normal) { F.normal[3 * o] = nrm.x; F.normal[3 * o + 1] = nrm.y; F.normal[3 * o + 2] = nrm.z; }
+        if (F.albedo) { F.albedo[3 * o] = alb.x; F.albedo[3 * o + 1] = alb.y; F.albedo[3 * o + 2] = alb.z; }
+        if (F.alpha) F.alpha[o] = (float)n / (float)ns;
+        if (F.object_id) F.object_id[o] = id;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-callable launch wrappers (C++ linkage, used by rt_api.cpp)
 // ------------------------------------------------------------------------------------------------
 static inline int grid_for(unsigned long long work, int block, int max_blocks)
@@ -3010,6 +3100,40 @@ void rtk_launch_gather(hipStream_t st, const DevPhotonMap &pm, const float4 *qa,
     G.k = k; G.radius = radius; G.sample_rgb = sample_rgb; G.out_irr = out_irr; G.out_dir = out_dir; G.mode = mode; G.stats = stats; G.next_batch = next_batch;
     if (fx && mode == 0) hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
     else hipLaunchKernelGGL(k_gather<false>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
+}
+
+// The feature planes of one chunk, after its last k_resolve on the same stream: the second-batch flags from the chunk's pixel
+// list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when features are on);
+// by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by image pixel.
+// The grid stays within RT_SPILL_BLOCKS, like every launch that uses the spill part of the traversal stack.
+void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const DevCamera &cam, const DevTiles &tiles,
+                         uint32_t q0, uint32_t npix, uint8_t *second, const DevFeatures &out, bool by_walk)
+{
+    if (npix == 0) return;
+    (void)hipMemsetAsync(second, 0, npix, st);
+    if (P.max_sample > P.min_sample) hipLaunchKernelGGL(k_mark_second, dim3(grid_for(npix, 256, 1024)), dim3(256), 0, st, W, second, npix);
+    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.fx = nullptr;
+    memset(&C.qout, 0, sizeof C.qout); C.qout_count = nullptr;
+    C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
+    memset(&C.sm, 0, sizeof C.sm);
+    FeatureArgs F; F.cam = cam; F.tiles = tiles; F.q0 = q0; F.npix = npix; F.min_sample = P.min_sample; F.max_sample = P.max_sample;
+    tiles_prepare(F.tiles);
+    F.div_ms = fastdiv_make((uint32_t)(P.max_sample > 0 ? P.max_sample : 1));
+    F.second = second; F.by_walk = by_walk ? 1 : 0;
+    F.normal = out.normal; F.albedo = out.albedo; F.alpha = out.alpha; F.object_id = out.object_id;
+    static_assert(256 * 5 <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
+    const int grid = grid_for(npix, RT_BLOCK, 256 * 5);
+    const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
+#define RT_LAUNCH_FEATURES(M) do { if (tex) hipLaunchKernelGGL((k_features<M, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, F); \
+                                   else hipLaunchKernelGGL((k_features<M, false>), dim3(grid), dim3(RT_BLOCK), 0, st, C, F); } while (0)
+    switch (P.shade_model) {
+    case RT_SHADE_P13: RT_LAUNCH_FEATURES(RT_SHADE_P13); break;
+    case RT_SHADE_P12: RT_LAUNCH_FEATURES(RT_SHADE_P12); break;
+    case RT_SHADE_P6: RT_LAUNCH_FEATURES(RT_SHADE_P6); break;
+    case RT_SHADE_P3: RT_LAUNCH_FEATURES(RT_SHADE_P3); break;
+    default: RT_LAUNCH_FEATURES(RT_SHADE_FIN);
+    }
+#undef RT_LAUNCH_FEATURES
 }
 
 // Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.

@@ -1,0 +1,469 @@
+"""First-hit feature planes -- normal, albedo, alpha, object id -- as optional outputs of a render (rt_outputs,
+rt_render_begin_outputs, rt_render_tiles_outputs_device, k_features), rt::RenderImage's EnableFeatures(), and one-channel
+PFM files.  The planes are averages over a pixel's HIT samples of quantities the oracle computes bit for bit
+(orc.primary_ray -> orc.trace -> orc_textured_color), so they are checked against it on every pixel, and byte for byte
+across entry points, chunk sizes, stream counts and tile ranges."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import orc
+from raytracing_folder_amd import capi, photons
+from tests import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIG = np.float32(1e30)
+PAD = dict(min_sample=4, max_sample=8, threshold=1e-3)          # adaptive 4 -> 8 (the variance gate)
+BG = (0.25, 0.5, 0.75)
+FEATURES = ("normal", "albedo", "alpha", "object_id")
+
+
+# ---- CPU: the ABI, argument checks, Pf files, the shim's header ----------------------------------------------
+def test_new_symbols_and_the_descriptor_layout():
+    L = capi.lib()
+    for name in ("rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
+        assert hasattr(L, name), name
+    # uint32 + padding, then eight pointers
+    assert C.sizeof(capi.Outputs) == 8 + 8 * C.sizeof(C.c_void_p) == 72
+    assert capi.Outputs().struct_size == 72
+    assert [f[0] for f in capi.Outputs._fields_] == ["struct_size", "rgb8", "z", "count", "rgb_linear", "normal", "albedo", "alpha", "object_id"]
+
+
+def test_outputs_entry_points_check_the_descriptor_before_anything_is_rendered():
+    s, cam = scenes.load_cornell(64, 48)
+    p = capi.default_params()
+    t = capi.TileRange(32, 8, 0, 1)
+    L = capi.lib()
+    buf = np.zeros(64 * 48 * 12, np.uint8)
+    ptr = buf.ctypes.data
+
+    def begin(o):
+        job = C.c_void_p()
+        st = L.rt_render_begin_outputs(s._h, C.byref(cam), C.byref(p), C.byref(t), 0, C.byref(o) if o is not None else None, C.byref(job))
+        assert job.value is None
+        return st
+
+    def device(o):
+        return L.rt_render_tiles_outputs_device(s._h, C.byref(cam), C.byref(p), C.byref(t), 0, None, C.byref(o) if o is not None else None, 1, None)
+
+    for call in (begin, device):
+        assert call(None) == -1                                                    # RT_ERR_ARG
+        for size in (0, 71, 64, 80):
+            o = capi.Outputs(rgb8=ptr, z=ptr, count=ptr, alpha=ptr)
+            o.struct_size = size
+            assert call(o) == -1, size
+            assert b"struct_size" in L.rt_last_error()
+        for missing in ("rgb8", "z", "count"):
+            planes = dict(rgb8=ptr, z=ptr, count=ptr, normal=ptr, albedo=ptr, alpha=ptr, object_id=ptr)
+            planes[missing] = None
+            assert call(capi.Outputs(**planes)) == -1, missing
+            assert b"required" in L.rt_last_error()
+    with pytest.raises(KeyError):
+        s.render_outputs(cam, p, planes=("depth",))
+
+
+def test_pf_round_trip_and_header(tmp_path):
+    rng = np.random.default_rng(2)
+    img = rng.normal(0, 3, (5, 7)).astype(np.float32)
+    img[0, 0], img[4, 6] = 1e30, -2.5
+    path = str(tmp_path / "a.pfm")
+    capi.image_write_pfm1(path, img)
+    raw = open(path, "rb").read()
+    head = b"Pf\n7 5\n-1.0\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 5 * 7 * 4
+    body = np.frombuffer(raw[len(head):], "<f4").reshape(5, 7)
+    assert body.tobytes() == img[::-1].tobytes()              # bottom scanline first
+    back = capi.image_read_pfm1(path)
+    assert back.dtype == np.float32 and back.shape == (5, 7) and back.tobytes() == img.tobytes()
+    # hand-written files of either byte order: 2 wide, 3 high; stored row k is image row 2 - k
+    rows = np.arange(6, dtype=np.float32).reshape(3, 2)
+    for scale, dt in ((b"-1.0", "<f4"), (b"1.0", ">f4")):
+        path = str(tmp_path / "h.pfm")
+        open(path, "wb").write(b"Pf\n2 3\n" + scale + b"\n" + rows.astype(dt).tobytes())
+        got = capi.image_read_pfm1(path)
+        assert (got[0] == rows[2]).all() and (got[1] == rows[1]).all() and (got[2] == rows[0]).all(), scale
+
+
+def test_pf_reader_refuses_bad_files_and_each_reader_refuses_the_other_kind(tmp_path):
+    good = b"Pf\n2 2\n-1.0\n" + np.ones(4, "<f4").tobytes()
+    colour = b"PF\n2 2\n-1.0\n" + np.ones(12, "<f4").tobytes()
+    cases = {"truncated.pfm": good[:-1], "colour.pfm": colour, "magic.pfm": b"P5" + good[2:], "header.pfm": b"Pf\n2 x\n-1.0\n" + good[12:],
+             "short.pfm": b"Pf\n2 2\n", "zero.pfm": b"Pf\n2 2\n0\n" + good[12:], "empty.pfm": b""}
+    for name, data in cases.items():
+        path = str(tmp_path / name)
+        open(path, "wb").write(data)
+        with pytest.raises(capi.RtError) as e:
+            capi.image_read_pfm1(path)
+        assert e.value.status == -5, name                      # RT_ERR_IO
+    with pytest.raises(capi.RtError) as e:
+        capi.image_read_pfm1(str(tmp_path / "missing.pfm"))
+    assert e.value.status == -5
+    path = str(tmp_path / "good.pfm")
+    open(path, "wb").write(good)
+    assert (capi.image_read_pfm1(path) == 1).all()
+    with pytest.raises(capi.RtError) as e:                     # the 3-channel reader goes on refusing "Pf"
+        capi.image_read_pfm(path)
+    assert e.value.status == -5
+    w, h = C.c_int32(), C.c_int32()
+    out = np.zeros(4, np.float32)
+    L = capi.lib()
+    assert L.rt_image_read_pfm1(path.encode(), C.byref(w), C.byref(h), capi._p(out), 3) == -1         # RT_ERR_ARG
+    assert L.rt_image_read_pfm1(path.encode(), C.byref(w), C.byref(h), capi._p(out), 4) == 0 and (out == 1).all()
+    assert (w.value, h.value) == (2, 2)
+    assert L.rt_image_write_pfm1(str(tmp_path / "x.pfm").encode(), None, 2, 2) == -1
+    assert L.rt_image_write_pfm1(str(tmp_path / "x.pfm").encode(), capi._p(out), 2, 0) == -1
+
+
+def _build_shim_driver(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_features_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_features_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+def test_shim_driver_builds_against_the_header(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+# ---- GPU ----------------------------------------------------------------------------------------------------
+def _scene(w, h, bal=None):
+    """the Cornell box from a wider view: its open front and the outside show, so some pixels miss everything"""
+    s, cam = scenes.load_cornell(w, h)
+    s.set_environment((0, 0, 0), BG)
+    if bal is not None:
+        s.set_photons(bal)
+    cam.fov = 70.0
+    return s, cam
+
+
+def _oracle_samples(s, cam, ms, kd_of, step=1):
+    """per pixel and sample 0..ms-1: hit flag, node, N and kd of the primary ray, from the oracle alone"""
+    e = s.export()
+    osc, ocam = scenes.oracle_scene(e), scenes.oracle_camera(cam)
+    W, H = cam.width, cam.height
+    ys, xs = range(0, H, step), range(0, W, step)
+    hit = np.zeros((len(ys), len(xs), ms), bool)
+    node = np.full((len(ys), len(xs), ms), -1, np.int32)
+    N = np.zeros((len(ys), len(xs), ms, 3), np.float32)
+    kd = np.zeros((len(ys), len(xs), ms, 3), np.float32)
+    for iy, y in enumerate(ys):
+        rays = np.stack([orc.primary_ray(ocam, x, y, j) for x in xs for j in range(ms)])
+        h, hits = orc.trace(osc, 0, rays)
+        h = h.reshape(len(xs), ms) != 0
+        hit[iy] = h
+        node[iy] = np.where(h, hits["node"].reshape(len(xs), ms), -1)
+        N[iy] = hits["N"].reshape(len(xs), ms, 3)
+        for ix in range(len(xs)):
+            for j in range(ms):
+                if h[ix, j]:
+                    kd[iy, ix, j] = kd_of(e, osc, hits[ix * ms + j])
+    return hit, node, N, kd
+
+
+def _plain_kd(e, osc, h):
+    return e["materials"]["diffuse"][int(e["nodes"]["material"][h["node"]])]
+
+
+def _textured_kd(e, osc, h):
+    """the kd of material_colors: the material's diffuse colour through its diffuse map at the hit's uvw (orc_textured_color)"""
+    mi = int(e["nodes"]["material"][h["node"]])
+    kd = np.ascontiguousarray(e["materials"]["diffuse"][mi], np.float32)
+    uvw = np.ascontiguousarray(h["uvw"], np.float32)
+    out = np.zeros(3, np.float32)
+    maps = e["material_maps"]
+    orc.lib().orc_textured_color(C.byref(osc.c), kd.ctypes.data_as(C.c_void_p), C.c_void_p(maps[2 * mi:2 * mi + 1].ctypes.data),
+                                 uvw.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def _average(vals, hits):
+    """k_resolve's float sum: c += v_j * (1/n) over the hit samples in sample order, in float32"""
+    if not hits:
+        return np.zeros(3, np.float32)
+    inv = np.float32(1) / np.float32(len(hits))
+    c = np.zeros(3, np.float32)
+    for j in hits:
+        c = (c + vals[j] * inv).astype(np.float32)
+    return c
+
+
+def _expected(hit, node, N, kd, ns):
+    """(normal, albedo, alpha, object_id) of one pixel resolved over its first ns samples"""
+    hits = [j for j in range(ns) if hit[j]]
+    return (_average(N, hits), _average(kd, hits), np.float32(len(hits)) / np.float32(ns), int(node[hits[-1]]) if hits else -1)
+
+
+def _close(got, want):
+    return bool((np.abs(got - want) <= 2e-5 * np.abs(want) + 1e-6).all())
+
+
+def _compare_pixel(out, iy, ix, y, x, hit, node, N, kd, p, planes=FEATURES):
+    """Compares pixel (x, y) with the batch its count byte names (count 0 with hits in the first batch: the first batch, or --
+    a second-batch pixel with at most min_sample hits carries count 0 too -- all samples).  Returns the number of samples of
+    the candidate that matched; asserts when none does."""
+    cnt = int(out["count"][y, x])
+    first = _expected(hit[iy, ix], node[iy, ix], N[iy, ix], kd[iy, ix], p.min_sample)
+    full = _expected(hit[iy, ix], node[iy, ix], N[iy, ix], kd[iy, ix], p.max_sample)
+    n_first, n_all = int(hit[iy, ix, :p.min_sample].sum()), int(hit[iy, ix].sum())
+    if cnt == 255:
+        cands = [(p.max_sample, full)]
+    else:
+        cands = [(p.min_sample, first)]
+        if p.max_sample > p.min_sample and 0 < n_first and n_all <= p.min_sample:
+            cands.append((p.max_sample, full))
+    got = {k: out[k][y, x] for k in planes}
+    print(f"pixel ({x},{y}) count {cnt} hits {n_first}/{n_all} got " + " ".join(f"{k}={np.asarray(v).tolist()}" for k, v in got.items()))
+    for ns, (nrm, alb, alpha, oid) in cands:
+        ok = True
+        if "object_id" in got:
+            ok = ok and int(got["object_id"]) == oid
+        if "alpha" in got:
+            ok = ok and got["alpha"] == alpha
+        if "normal" in got:
+            ok = ok and _close(got["normal"], nrm)
+        if "albedo" in got:
+            ok = ok and _close(got["albedo"], alb)
+        if ok:
+            return ns
+    raise AssertionError(f"pixel ({x},{y}) count {cnt}: got {got}, expected one of {cands}")
+
+
+@pytest.fixture(scope="module")
+def cornell():
+    """test 1's frame: Cornell 64 x 48, fov 70, P13, adaptive 4 -> 8, every plane, through the job API"""
+    s, cam = _scene(64, 48)
+    p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, **PAD)
+    out = s.render_outputs(cam, p, planes=FEATURES)
+    assert out["progress"] == 64 * 48
+    return s, cam, p, out
+
+
+@pytest.mark.gpu
+def test_feature_planes_against_the_oracle_on_every_pixel(cornell):
+    s, cam, p, out = cornell
+    W, H = cam.width, cam.height
+    hit, node, N, kd = _oracle_samples(s, cam, p.max_sample, _plain_kd)
+    lengths = np.linalg.norm(N[hit], axis=-1)
+    assert lengths.dtype == np.float32 and 0.99999994 <= lengths.min() and lengths.max() <= 1.0000001     # unit vectors
+    partial = mixed = second = compared = all_miss = 0
+    ids_seen = set()
+    for y in range(H):
+        for x in range(W):
+            ns = _compare_pixel(out, y, x, y, x, hit, node, N, kd, p)
+            compared += 1
+            h = hit[y, x, :ns]
+            n = int(h.sum())
+            second += ns == p.max_sample
+            all_miss += n == 0
+            partial += 0 < n < ns
+            mixed += len(set(node[y, x, :ns][h].tolist())) > 1
+            ids_seen.update(node[y, x, :ns][h].tolist())
+            if n == 0:
+                assert out["object_id"][y, x] == -1 and out["alpha"][y, x] == 0 and out["z"][y, x] == BIG
+                assert (out["normal"][y, x] == 0).all() and (out["albedo"][y, x] == 0).all()
+    print(f"compared {compared} all-miss {all_miss} partial {partial} mixed {mixed} second-batch {second} ids {sorted(ids_seen)}")
+    assert compared == W * H                                      # no pixel excluded
+    assert all_miss > 0 and partial >= 100 and mixed >= 100 and second >= 1
+    assert ids_seen == set(range(2, 10))                          # planes, spheres and the mesh
+    # (z, object_id) describe one surface point: hit pixels have both, all-miss pixels neither
+    assert ((out["z"] == BIG) == (out["object_id"] == -1)).all()
+
+
+@pytest.mark.gpu
+def test_albedo_carries_the_diffuse_texture_maps():
+    s = capi.Scene()
+    s.load_xml(os.path.join(scenes.GOLD, "cornell_textured.xml"))
+    cam = s.camera()
+    p = capi.default_params()
+    assert (cam.width, cam.height) == (160, 120)
+    e = s.export()
+    assert e["material_maps"] is not None and len(e["material_maps"]) == 10 and len(e["textures"]) == 3
+    out = s.render_outputs(cam, p, planes=("albedo", "object_id", "alpha"))
+    hit, node, N, kd = _oracle_samples(s, cam, p.max_sample, _textured_kd)
+    hit_pixels = textured = 0
+    for y in range(cam.height):
+        for x in range(cam.width):
+            ns = _compare_pixel(out, y, x, y, x, hit, node, N, kd, p, planes=("albedo", "object_id", "alpha"))
+            hits = [j for j in range(ns) if hit[y, x, j]]
+            if hits:
+                hit_pixels += 1
+                plain = e["materials"]["diffuse"][e["nodes"]["material"][np.maximum(node[y, x], 0)]]      # per sample, without the maps
+                textured += bool((_average(kd[y, x], hits) != _average(plain, hits)).any())
+    print(f"hit pixels {hit_pixels}, of which with a textured albedo {textured}")
+    assert hit_pixels > 0 and 2 * textured >= hit_pixels
+
+
+@pytest.mark.gpu
+def test_asking_for_features_moves_no_other_plane():
+    bal = photons.synth_cornell_photon_map(20000, seed=3)
+    s, cam = _scene(96, 72, bal)
+    p = capi.default_params(**PAD)
+    # default mode: z and count are exact
+    plain = s.render_linear(cam, p)
+    out = s.render_outputs(cam, p, planes=("linear",) + FEATURES)
+    assert out["z"].tobytes() == plain[1].tobytes() and out["count"].tobytes() == plain[2].tobytes()
+    assert (out["count"] == 255).any() and (out["z"] == BIG).any() and out["stats"].photon_queries > 0
+    # reproducible mode: every plane
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    plain = s.render_linear(cam, p)
+    rep = s.render_outputs(cam, p, planes=("linear",) + FEATURES)
+    for name, a in zip(("rgb", "z", "count", "linear"), plain[:4]):
+        assert rep[name].shape == a.shape and rep[name].tobytes() == a.tobytes(), name
+    # the feature planes do not depend on the mode
+    for name in FEATURES:
+        assert rep[name].tobytes() == out[name].tobytes(), name
+
+
+# one configuration per child process: the environment knobs are read once per process
+_CHILD = r"""
+import json, sys
+import numpy as np
+import torch
+sys.path.insert(0, sys.argv[1])
+from raytracing_folder_amd import capi
+from tests.test_feature_planes import _scene, PAD, FEATURES
+cfg = json.loads(sys.argv[2])
+s, cam = _scene(64, 48)
+p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, **PAD)
+W, H = cam.width, cam.height
+tiles = capi.TileRange(*cfg["tiles"])
+if cfg["entry"] == "job":
+    out = s.render_outputs(cam, p, planes=FEATURES, tiles=tiles, fill=-7.25, id_fill=-9)
+    planes = {k: out[k] for k in FEATURES}
+else:
+    dev = torch.device("cuda", 0)
+    base = [torch.zeros((H, W, 3), dtype=torch.uint8, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev),
+            torch.zeros((H, W), dtype=torch.uint8, device=dev)]
+    t = {"normal": torch.full((H, W, 3), -7.25, dtype=torch.float32, device=dev), "albedo": torch.full((H, W, 3), -7.25, dtype=torch.float32, device=dev),
+         "alpha": torch.full((H, W), -7.25, dtype=torch.float32, device=dev), "object_id": torch.full((H, W), -9, dtype=torch.int32, device=dev)}
+    side = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    s.render_tiles_outputs_device(cam, p, tiles, 0, base[0].data_ptr(), base[1].data_ptr(), base[2].data_ptr(), stream=side.cuda_stream,
+                                  sync=True, want_stats=False, normal_ptr=t["normal"].data_ptr(), albedo_ptr=t["albedo"].data_ptr(),
+                                  alpha_ptr=t["alpha"].data_ptr(), object_id_ptr=t["object_id"].data_ptr())
+    torch.cuda.synchronize()
+    planes = {k: v.cpu().numpy() for k, v in t.items()}
+np.savez(sys.argv[3], **planes)
+"""
+
+
+def _child_planes(tmp_path, name, entry, env=None, tiles=(32, 8, 0, 1)):
+    path = str(tmp_path / (name + ".npz"))
+    e = dict(os.environ)
+    for k in ("RT_CHUNK_SAMPLES", "RT_STREAMS"):
+        e.pop(k, None)
+    e.update(env or {})
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, json.dumps({"entry": entry, "tiles": list(tiles)}), path],
+                       capture_output=True, text=True, timeout=300, env=e, cwd=ROOT)
+    assert r.returncode == 0, (name, r.stdout[-2000:], r.stderr[-2000:])
+    return dict(np.load(path))
+
+
+def _same_planes(a, b, what, mask=None):
+    for k in FEATURES:
+        x, y = (a[k], b[k]) if mask is None else (a[k][mask], b[k][mask])
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), f"{what}: {k}: {(x != y).sum()} values differ"
+
+
+@pytest.mark.gpu
+def test_feature_planes_are_the_same_bytes_whatever_the_entry_point_chunking_streams_and_tiles(cornell, tmp_path):
+    s, cam, p, ref = cornell
+    W, H = cam.width, cam.height
+    # job API against the device entry point (both in fresh processes, and against this process's render)
+    job = _child_planes(tmp_path, "job", "job")
+    _same_planes(job, ref, "job API, fresh process")
+    _same_planes(_child_planes(tmp_path, "device", "device"), ref, "device entry point")
+    # several chunks (512 samples = one 32 x 8 tile of 8 samples... two tiles per chunk) against one chunk
+    chunked = {"RT_CHUNK_SAMPLES": "4096"}
+    _same_planes(_child_planes(tmp_path, "job_chunks", "job", chunked), ref, "job API, 6 chunks")
+    _same_planes(_child_planes(tmp_path, "device_chunks", "device", chunked), ref, "device entry point, 6 chunks")
+    # one stream against two
+    _same_planes(_child_planes(tmp_path, "s1", "device", dict(chunked, RT_STREAMS="1")), ref, "RT_STREAMS=1")
+    _same_planes(_child_planes(tmp_path, "s2", "device", dict(chunked, RT_STREAMS="2")), ref, "RT_STREAMS=2")
+    # a strided tile range: the same pixels of the full frame, the others left at the caller's fill
+    tr = (32, 8, 1, 3)
+    tiles_x = (W + 31) // 32
+    own = np.zeros((H, W), bool)
+    for t in range(1, tiles_x * ((H + 7) // 8), 3):
+        ty, tx = divmod(t, tiles_x)
+        own[ty * 8:ty * 8 + 8, tx * 32:tx * 32 + 32] = True
+    assert 0 < own.sum() < W * H
+    for entry in ("job", "device"):
+        part = _child_planes(tmp_path, "strided_" + entry, entry, tiles=tr)
+        _same_planes(part, ref, "strided tiles, " + entry, own)
+        for k in ("normal", "albedo", "alpha"):
+            assert (part[k][~own] == np.float32(-7.25)).all(), (entry, k)
+        assert (part["object_id"][~own] == -9).all(), entry
+
+
+def _assert_invariants(s, out):
+    nodes = s.export()["nodes"]
+    alpha, z, oid, nrm = out["alpha"], out["z"], out["object_id"], out["normal"]
+    miss = alpha == 0
+    assert miss.any() and (~miss).any()
+    assert (miss == (z == BIG)).all() and (miss == (oid == -1)).all() and (miss == (nrm == 0).all(axis=-1)).all()
+    assert (out["albedo"][miss] == 0).all()
+    assert (alpha[~miss] > 0).all() and (alpha[~miss] <= 1).all()
+    ids = oid[~miss]
+    assert (ids >= 0).all() and (ids < len(nodes)).all() and (nodes["obj_type"][ids] != capi.OBJ_NONE).all()
+    lengths = np.linalg.norm(nrm.astype(np.float64), axis=-1)
+    print("max |normal|", lengths.max(), "partial-coverage pixels", int(((alpha > 0) & (alpha < 1)).sum()))
+    assert (lengths <= 1 + 1e-5).all()
+    assert np.isfinite(nrm).all() and np.isfinite(out["albedo"]).all() and (out["albedo"] >= 0).all()
+
+
+@pytest.mark.gpu
+def test_invariants_for_fin_with_a_photon_map():
+    bal = photons.synth_cornell_photon_map(4000, seed=1)
+    s, cam = _scene(64, 48, bal)
+    out = s.render_outputs(cam, capi.default_params(**PAD))
+    assert out["stats"].photon_queries > 0
+    _assert_invariants(s, out)
+
+
+@pytest.mark.gpu
+def test_invariants_for_p13_with_depth_of_field():
+    s, cam = _scene(64, 48)
+    cam.dof = 0.5
+    out = s.render_outputs(cam, capi.default_params(shade_model=capi.SHADE_P13, bounce=6, **PAD))
+    _assert_invariants(s, out)
+
+
+@pytest.mark.gpu
+def test_a_subset_of_planes_gives_the_same_bytes(cornell):
+    s, cam, p, ref = cornell
+    out = s.render_outputs(cam, p, planes=("alpha",))
+    assert set(out) == {"rgb", "z", "count", "stats", "progress", "alpha"}
+    assert out["alpha"].tobytes() == ref["alpha"].tobytes()
+    assert out["z"].tobytes() == ref["z"].tobytes() and out["count"].tobytes() == ref["count"].tobytes()
+
+
+@pytest.mark.gpu
+def test_cpp_shim_enable_features_saves_the_planes_of_the_same_frame(cornell, tmp_path):
+    s, cam, p, ref = cornell
+    exe = _build_shim_driver(tmp_path)
+    prefix = str(tmp_path / "feat")
+    r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48", "70", *[repr(c) for c in BG], str(p.min_sample), str(p.max_sample),
+                        repr(float(np.float32(p.threshold)))], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    fields = r.stdout.split()
+    assert fields[fields.index("untouched") + 1] == "0", r.stdout
+    assert capi.image_read_pfm(prefix + "_normal.pfm").tobytes() == ref["normal"].tobytes()
+    assert capi.image_read_pfm(prefix + "_albedo.pfm").tobytes() == ref["albedo"].tobytes()
+    assert capi.image_read_pfm1(prefix + "_alpha.pfm").tobytes() == ref["alpha"].tobytes()
+    # the id image: one fixed colour per id, black where there is no object
+    png = capi.image_read_rgb(prefix + "_id.png")
+    assert png.shape == (48, 64, 3)
+    colours = {}
+    for oid, c in zip(ref["object_id"].ravel().tolist(), png.reshape(-1, 3).tolist()):
+        assert colours.setdefault(oid, tuple(c)) == tuple(c)
+    assert colours[-1] == (0, 0, 0) and len(set(colours.values())) == len(colours) == 9
