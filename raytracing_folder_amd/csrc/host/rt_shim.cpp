@@ -125,25 +125,15 @@ bool Renderer::BeginRender()
     std::vector<int> devs = devices;
     if (devs.empty()) for (int i = 0, n = rt_device_count(); i < n; i++) devs.push_back(i);
     if (devs.empty()) devs.push_back(0);              // no gfx950 device: rt_render_begin reports it (there is no CPU path)
+    // the optional planes are NULL unless EnableLinear() / EnableFeatures()
+    const rt_outputs o = {(uint32_t)sizeof(rt_outputs), renderImage.GetPixels(), renderImage.GetZBuffer(), renderImage.GetSampleCount(),
+                          renderImage.GetLinearPixels(), renderImage.GetNormals(), renderImage.GetAlbedo(), renderImage.GetAlpha(),
+                          renderImage.GetObjectIds()};
     const int N = (int)devs.size();
     for (int r = 0; r < N; r++) {
         const rt_tile_range mine = {32, 8, r, N};
         rt_job *job = nullptr;
-        if (renderImage.FeaturesEnabled()) {
-            rt_outputs o;
-            memset(&o, 0, sizeof o);
-            o.struct_size = (uint32_t)sizeof o;
-            o.rgb8 = renderImage.GetPixels(); o.z = renderImage.GetZBuffer(); o.count = renderImage.GetSampleCount();
-            o.rgb_linear = renderImage.GetLinearPixels();           // NULL unless EnableLinear()
-            o.normal = renderImage.GetNormals(); o.albedo = renderImage.GetAlbedo(); o.alpha = renderImage.GetAlpha();
-            o.object_id = renderImage.GetObjectIds();
-            st = rt_render_begin_outputs(handle, &d.camera, &params, &mine, devs[r], &o, &job);
-        } else if (renderImage.LinearEnabled())
-            st = rt_render_begin_linear(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
-                                        renderImage.GetSampleCount(), renderImage.GetLinearPixels(), &job);
-        else
-            st = rt_render_begin(handle, &d.camera, &params, &mine, devs[r], renderImage.GetPixels(), renderImage.GetZBuffer(),
-                                 renderImage.GetSampleCount(), &job);
+        st = rt_render_begin_outputs(handle, &d.camera, &params, &mine, devs[r], &o, &job);
         if (st != RT_OK) {
             error = rt_last_error();
             for (rt_job *j : jobs) { rt_render_stop(j); rt_render_wait(j); }

@@ -39,7 +39,7 @@ public:
     uint8_t *GetSampleCount() { return sampleCount.data(); }
     uint8_t *GetSampleCountImage() { return sampleCountImg.data(); }
     // the linear (pre-gamma) float RGB plane, row-major like GetPixels(); nothing is allocated until EnableLinear(), and
-    // GetLinearPixels() is NULL without it.  Renderer::BeginRender fills it through rt_render_begin_linear.
+    // GetLinearPixels() is NULL without it.  Renderer::BeginRender fills it through rt_render_begin_outputs.
     void EnableLinear();
     bool LinearEnabled() const { return linearEnabled; }
     float *GetLinearPixels() { return linearEnabled ? linear.data() : nullptr; }

@@ -142,6 +142,13 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
+// a DevBuf released when its scope ends (DeviceState releases its own explicitly, on its device)
+struct ScopedDevBuf : DevBuf {
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { release(); }
+};
 
 struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
 
@@ -261,6 +268,40 @@ struct rt_scene {
     }
 };
 
+// ---- render outputs -------------------------------------------------------------------------------------
+// The planes of rt_outputs in field order, with their bytes per pixel.  Internally a render's outputs are one Planes set
+// indexed by this table; a NULL plane is not wanted, and nothing is allocated or launched for it.  PL_NORMAL .. PL_ID are the
+// first-hit features (k_features).
+enum Plane { PL_RGB8, PL_Z, PL_COUNT, PL_LINEAR, PL_NORMAL, PL_ALBEDO, PL_ALPHA, PL_ID, N_PLANES };
+static const size_t PLANE_BYTES[N_PLANES] = {3, 4, 1, 12, 12, 12, 4, 4};
+struct Planes {
+    void *p[N_PLANES] = {};
+    Planes() = default;
+    explicit Planes(const rt_outputs &o) : p{o.rgb8, o.z, o.count, o.rgb_linear, o.normal, o.albedo, o.alpha, o.object_id} {}
+    template <class T> T *at(int i) const { return (T *)p[i]; }
+    DevFeatures features() const            // the planes k_features writes (rtk_launch_features)
+    {
+        DevFeatures f;
+        f.normal = at<float>(PL_NORMAL); f.albedo = at<float>(PL_ALBEDO); f.alpha = at<float>(PL_ALPHA); f.object_id = at<int32_t>(PL_ID);
+        return f;
+    }
+};
+// the three planes of the entry points without a descriptor (the optional ones NULL but for rgb_linear)
+static rt_outputs outputs_of(uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear = nullptr)
+{
+    rt_outputs o = {(uint32_t)sizeof(rt_outputs), rgb8, z, count, rgb_linear};
+    return o;
+}
+// every render entry point with image planes: the caller's sizeof first, then the three required planes
+static rt_status check_outputs(const char *name, const rt_outputs *o)
+{
+    if (!o) return fail(RT_ERR_ARG, "%s: the plane descriptor is NULL", name);
+    if (o->struct_size != (uint32_t)sizeof(rt_outputs))
+        return fail(RT_ERR_ARG, "%s: rt_outputs.struct_size is %u, this library's is %zu", name, o->struct_size, sizeof(rt_outputs));
+    if (!o->rgb8 || !o->z || !o->count) return fail(RT_ERR_ARG, "%s: rgb8, z and count are required", name);
+    return RT_OK;
+}
+
 struct rt_job {
     rt_scene *scene = nullptr;
     std::thread worker;
@@ -270,14 +311,10 @@ struct rt_job {
     rt_status status = RT_OK;
     std::string error;
     rt_stats stats{};
-    // caller-owned host image (rt_render_begin): finished bands are copied back chunk by chunk, so a
+    // the caller-owned host planes (rt_render_begin*): finished bands are copied back chunk by chunk, so a
     // viewer that polls rt_render_progress can show the frame as it fills (viewport.cpp:367 reads
     // renderImage.GetPixels() while the workers run)
-    uint8_t *host_rgb = nullptr, *host_count = nullptr; float *host_z = nullptr;
-    float *host_linear = nullptr;       // rt_render_begin_linear: the linear plane, copied back like the others
-    // rt_render_begin_outputs: the first-hit feature planes that were asked for, copied back like the others
-    float *host_normal = nullptr, *host_albedo = nullptr, *host_alpha = nullptr; int32_t *host_id = nullptr;
-    bool wants_features() const { return host_normal || host_albedo || host_alpha || host_id; }
+    Planes host;
     rt_setup_ms setup{};                // the photon pass this job ran first (all zero when it did not)
 };
 
@@ -1482,51 +1519,76 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
     return RT_OK;
 }
 
-#define RT_ERR_OVERFLOW_RETRY (-1000)     /* internal: queues sized from history overflowed; render again with worst-case queues */
-static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                   hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
-                                   float *lin_dev, const DevFeatures *feat);
-
-// Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
-// half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
-// if that ever overflows, a synchronous render
-// is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
-// library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
-// `linear`: the linear plane is wanted -- into lin_dev (device planes; a job's host copy follows), or as 24-byte packed records.
-// `feat`: the image-sized device planes of the first-hit features that are wanted (NULL: none; a strided job stages its own).
-static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                              bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev = nullptr, bool linear = false,
-                              float *lin_dev = nullptr, const DevFeatures *feat = nullptr)
+// the counting fields of rt_stats from the statistics block (the timing fields, pixels, attempts and streams are left as they are)
+static rt_status read_counters(const void *stats_dev, rt_stats &R)
 {
-    rt_status st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                                     packed_dev, false, linear, lin_dev, feat);
-    int attempts = 1;
-    if (st == RT_ERR_OVERFLOW_RETRY) {
-        attempts = 2;
-        st = render_tiles_once(s, cam, p, tiles, device, user_stream, use_user_stream, rgb8_dev, z_dev, count_dev, sync, stats_out, job,
-                               packed_dev, true, linear, lin_dev, feat);
-    }
-    if (st == RT_OK && stats_out) stats_out->attempts = (uint64_t)attempts;
-    if (st == RT_OK && job) job->stats.attempts = (uint64_t)attempts;
-    return st;
+    unsigned long long hs[ST_COUNT];
+    HIP_TRY(stats_read(stats_dev, 0, ST_COUNT, hs));
+    R.rays_primary = hs[ST_RAYS_PRIMARY]; R.rays_shadow = hs[ST_RAYS_SHADOW]; R.rays_reflect = hs[ST_RAYS_REFLECT];
+    R.rays_refract = hs[ST_RAYS_REFRACT]; R.instance_visits = hs[ST_INSTANCE_VISITS]; R.bvh_nodes_visited = hs[ST_BVH_NODES];
+    R.tris_tested = hs[ST_TRIS]; R.photon_queries = hs[ST_PHOTON_QUERIES]; R.photons_visited = hs[ST_PHOTONS_VISITED];
+    R.samples = hs[ST_RAYS_PRIMARY];
+    R.gather_rounds = hs[ST_GATHER_ROUNDS]; R.gather_slow = hs[ST_GATHER_SLOW]; R.gather_leaf_reads = hs[ST_GATHER_LEAF_READS];
+    R.peak_rays = hs[ST_PEAK_RAYS]; R.peak_queries = hs[ST_PEAK_QUERIES];
+    return RT_OK;
 }
 
+// A call's tile walk: walk index q runs tile-major over the call's tiles (tile_px slots per tile, row-major inside a tile);
+// the slots of a ragged tile that lie outside the image belong to no pixel.
+struct TileWalk {
+    const DevTiles &dt; int width, height; uint64_t tile_px;
+    void tile_origin(uint64_t k, int &x, int &y) const       // top-left pixel of the walk's k-th tile
+    {
+        const int t = dt.first + (int)k * dt.stride;
+        x = (t % dt.tiles_x) * dt.tile_w; y = (t / dt.tiles_x) * dt.tile_h;
+    }
+    int64_t offset(uint64_t q) const                            // image offset of slot q, or -1: outside the image
+    {
+        int x, y;
+        tile_origin(q / tile_px, x, y);
+        const int w = (int)(q % tile_px);
+        x += w % dt.tile_w; y += w / dt.tile_w;
+        return x < width && y < height ? (int64_t)y * width + x : -1;
+    }
+    uint64_t pixels(uint64_t q0, uint64_t q1) const             // image pixels of slots [q0, q1), both on tile boundaries
+    {
+        uint64_t n = 0;
+        for (uint64_t k = q0 / tile_px; k < q1 / tile_px; k++) {
+            int x, y;
+            tile_origin(k, x, y);
+            const int w = std::min(dt.tile_w, width - x), h = std::min(dt.tile_h, height - y);
+            if (w > 0 && h > 0) n += (uint64_t)w * h;
+        }
+        return n;
+    }
+};
+
+// What one render call writes, and how: image-sized device planes (`dev`; rgb_linear selects the linear plane, the features
+// k_features), or packed records of the call's tiles (`packed`: rec_bytes 8, or 24 with the linear plane).  A strided job
+// (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature staging planes of its own.
+struct RenderRequest {
+    Planes dev;
+    void *packed = nullptr;
+    size_t rec_bytes = 8;
+    hipStream_t stream = nullptr;       // the caller's stream; NULL: the device's own
+    bool sync = true;
+    rt_stats *stats_out = nullptr;
+    rt_job *job = nullptr;
+};
+
+#define RT_ERR_OVERFLOW_RETRY (-1000)     /* internal: queues sized from history overflowed; render again with worst-case queues */
 static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                   hipStream_t user_stream, bool use_user_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
-                                   bool sync, rt_stats *stats_out, rt_job *job, void *packed_dev, bool worst_case, bool linear,
-                                   float *lin_dev, const DevFeatures *feat)
+                                   const RenderRequest &req, bool worst_case)
 {
     rt_status st = validate_render(s, cam, p, tiles);
     if (st) return st;
-    if (!packed_dev && (!rgb8_dev || !z_dev || !count_dev)) return fail(RT_ERR_ARG, "render: output buffers are required");
+    const bool sync = req.sync; rt_stats *const stats_out = req.stats_out; rt_job *const job = req.job;
     DeviceState *D = nullptr;
     if ((st = prepare_device(s, device, &D))) return st;
     // one host call at a time per (scene, device): the working sets are not shared between concurrent calls
     DeviceClaim claim(D);
     if (!claim.ok) return fail(RT_ERR_STATE, "render: another call on this scene is using device %d", device);
-    hipStream_t stream = use_user_stream ? user_stream : D->stream;
+    hipStream_t stream = req.stream ? req.stream : D->stream;
     if ((st = order_after_pending(D, stream))) return st;
     if (!D->last_done) HIP_TRY(hipEventCreateWithFlags(&D->last_done, hipEventDisableTiming));
     if (D->last_pending && (sync || stats_out != nullptr || job != nullptr)) {
@@ -1604,7 +1666,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
     const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
     // first-hit feature planes (k_features after each chunk's last resolve): only when a plane was asked for
-    const bool features = (feat && feat->any()) || (job && job->wants_features());
+    const bool features = (job ? job->host : req.dev).features().any();
     DevWork Ws[RT_STREAMS];
     unsigned long long *Fx[RT_STREAMS] = {};
     int n_ready = 0;
@@ -1629,28 +1691,29 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     // a job that owns only some of the tiles renders into packed records of its own (see finish_oldest)
     const bool job_packed = job != nullptr && tiles->stride != 1;
     // bytes per packed record: 8, or 24 with the linear plane (the 8-byte record, linear r, g, b, 4 zero bytes)
-    const size_t rec_bytes = linear ? 24 : 8;
-    DevBuf job_packed_buf;
-    struct Release { DevBuf &b; ~Release() { b.release(); } } job_packed_release{job_packed_buf};
+    const size_t rec_bytes = req.rec_bytes;
+    ScopedDevBuf job_packed_buf;
+    void *packed_dev = req.packed;
     if (job_packed) {
         if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * rec_bytes))) return st;
         packed_dev = job_packed_buf.p;
     }
+    const bool linear = packed_dev ? rec_bytes == 24 : req.dev.p[PL_LINEAR] != nullptr;
     // where k_features writes: the caller's image-sized device planes, or -- a strided job, whose rows are shared with other jobs --
     // staging planes indexed by this call's tile walk, scattered on the host like the packed records (finish_oldest)
-    DevFeatures fdev;
-    if (feat) fdev = *feat;
-    DevBuf feat_stage[4];
-    struct ReleaseStage { DevBuf *b; ~ReleaseStage() { for (int i = 0; i < 4; i++) b[i].release(); } } feat_stage_release{feat_stage};
+    DevFeatures fdev = req.dev.features();
+    ScopedDevBuf stage[N_PLANES];
     const bool feat_by_walk = features && job_packed;
     if (feat_by_walk) {
-        const uint64_t n = std::max<uint64_t>(total_px, 1);
-        fdev = DevFeatures();
-        if (job->host_normal) { if ((st = feat_stage[0].ensure(n * 12))) return st; fdev.normal = (float *)feat_stage[0].p; }
-        if (job->host_albedo) { if ((st = feat_stage[1].ensure(n * 12))) return st; fdev.albedo = (float *)feat_stage[1].p; }
-        if (job->host_alpha) { if ((st = feat_stage[2].ensure(n * 4))) return st; fdev.alpha = (float *)feat_stage[2].p; }
-        if (job->host_id) { if ((st = feat_stage[3].ensure(n * 4))) return st; fdev.object_id = (int32_t *)feat_stage[3].p; }
+        Planes staged;
+        for (int i = PL_NORMAL; i < N_PLANES; i++) {
+            if (!job->host.p[i]) continue;
+            if ((st = stage[i].ensure(std::max<uint64_t>(total_px, 1) * PLANE_BYTES[i]))) return st;
+            staged.p[i] = stage[i].p;
+        }
+        fdev = staged.features();
     }
+    const TileWalk walk{dt, cam->width, cam->height, tile_px};
     const bool want_stats = stats_out != nullptr || job != nullptr;
     Timing tm[RT_STREAMS];
     hipEvent_t e_begin = nullptr, e_end = nullptr;
@@ -1713,75 +1776,51 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         flight.erase(flight.begin());
         HIP_TRY(hipEventSynchronize(f.done));
         (void)hipEventDestroy(f.done);
-        // pixels of this chunk that lie inside the image
-        int done = 0;
-        for (uint64_t q = f.q0; q < f.q0 + f.npix; q += tile_px) {
-            const int t = dt.first + (int)(q / tile_px) * dt.stride;
-            const int tx = t % dt.tiles_x, ty = t / dt.tiles_x;
-            const int w = std::min(dt.tile_w, cam->width - tx * dt.tile_w), h = std::min(dt.tile_h, cam->height - ty * dt.tile_h);
-            if (w > 0 && h > 0) done += w * h;
-        }
-        if (job->host_rgb && job_packed) {
+        if (job_packed) {
             // a strided tile range (one job per device on the same caller-owned image): rows are shared with other jobs' tiles,
             // so only this job's pixels may be written -- the chunk's packed 8-byte (24-byte: linear) records come back in one
             // copy and are scattered on the host
             const size_t words = rec_bytes / 8;
             std::vector<uint2> rec((size_t)f.npix * words);
             HIP_TRY(hipMemcpy(rec.data(), (const uint2 *)packed_dev + f.q0 * words, (size_t)f.npix * rec_bytes, hipMemcpyDeviceToHost));
+            const Planes &h = job->host;
             for (uint32_t i = 0; i < f.npix; i++) {
-                const uint64_t q = f.q0 + i;
-                const int t = dt.first + (int)(q / tile_px) * dt.stride;
-                const int w = (int)(q % tile_px);
-                const int x = (t % dt.tiles_x) * dt.tile_w + w % dt.tile_w, y = (t / dt.tiles_x) * dt.tile_h + w / dt.tile_w;
-                if (x >= cam->width || y >= cam->height) continue;
-                const size_t o = (size_t)y * cam->width + x;
+                const int64_t o = walk.offset(f.q0 + i);
+                if (o < 0) continue;
                 const uint2 v = rec[i * words];
-                job->host_rgb[3 * o] = (uint8_t)(v.x & 255u); job->host_rgb[3 * o + 1] = (uint8_t)((v.x >> 8) & 255u); job->host_rgb[3 * o + 2] = (uint8_t)((v.x >> 16) & 255u);
+                uint8_t *rgb = h.at<uint8_t>(PL_RGB8) + 3 * o;
+                rgb[0] = (uint8_t)(v.x & 255u); rgb[1] = (uint8_t)((v.x >> 8) & 255u); rgb[2] = (uint8_t)((v.x >> 16) & 255u);
                 const uint32_t zb = (v.x >> 24) | (v.y << 8);
-                memcpy(&job->host_z[o], &zb, 4);
-                job->host_count[o] = (uint8_t)(v.y >> 24);
-                if (linear && job->host_linear) memcpy(&job->host_linear[3 * o], &rec[i * words + 1], 12);
+                memcpy(h.at<float>(PL_Z) + o, &zb, 4);
+                h.at<uint8_t>(PL_COUNT)[o] = (uint8_t)(v.y >> 24);
+                if (words == 3) memcpy(h.at<float>(PL_LINEAR) + 3 * o, &rec[i * words + 1], 12);
             }
-            if (feat_by_walk) {
-                // the chunk's run of each staged feature plane, scattered the same way
-                auto scatter = [&](const void *stage, void *host, size_t elem) -> rt_status {
-                    if (!stage || !host) return RT_OK;
-                    std::vector<uint8_t> run((size_t)f.npix * elem);
-                    HIP_TRY(hipMemcpy(run.data(), (const uint8_t *)stage + f.q0 * elem, run.size(), hipMemcpyDeviceToHost));
-                    for (uint32_t i = 0; i < f.npix; i++) {
-                        const uint64_t q = f.q0 + i;
-                        const int t = dt.first + (int)(q / tile_px) * dt.stride;
-                        const int w = (int)(q % tile_px);
-                        const int x = (t % dt.tiles_x) * dt.tile_w + w % dt.tile_w, y = (t / dt.tiles_x) * dt.tile_h + w / dt.tile_w;
-                        if (x >= cam->width || y >= cam->height) continue;
-                        memcpy((uint8_t *)host + ((size_t)y * cam->width + x) * elem, run.data() + (size_t)i * elem, elem);
-                    }
-                    return RT_OK;
-                };
-                rt_status fs;
-                if ((fs = scatter(fdev.normal, job->host_normal, 12)) || (fs = scatter(fdev.albedo, job->host_albedo, 12)) ||
-                    (fs = scatter(fdev.alpha, job->host_alpha, 4)) || (fs = scatter(fdev.object_id, job->host_id, 4))) return fs;
+            // the chunk's run of each staged feature plane, scattered the same way
+            for (int k = PL_NORMAL; k < N_PLANES; k++) {
+                if (!stage[k].p) continue;
+                const size_t b = PLANE_BYTES[k];
+                std::vector<uint8_t> run((size_t)f.npix * b);
+                HIP_TRY(hipMemcpy(run.data(), (const uint8_t *)stage[k].p + f.q0 * b, run.size(), hipMemcpyDeviceToHost));
+                for (uint32_t i = 0; i < f.npix; i++) {
+                    const int64_t o = walk.offset(f.q0 + i);
+                    if (o >= 0) memcpy(h.at<uint8_t>(k) + o * b, run.data() + i * b, b);
+                }
             }
-        } else if (job->host_rgb) {
+        } else {
             // rows spanned by this chunk's tiles (tile-major order: a contiguous band of tile rows; a row shared
             // with a chunk still in flight may arrive torn and is copied again when that chunk finishes)
-            const uint64_t k0 = f.q0 / tile_px, k1 = (f.q0 + f.npix - 1) / tile_px;
-            const int ty0 = (dt.first + (int)k0 * dt.stride) / dt.tiles_x, ty1 = (dt.first + (int)k1 * dt.stride) / dt.tiles_x;
-            const size_t y0 = (size_t)ty0 * dt.tile_h, y1 = std::min<size_t>((size_t)cam->height, (size_t)(ty1 + 1) * dt.tile_h);
-            if (y1 > y0) {
-                const size_t o = y0 * cam->width, n = (y1 - y0) * cam->width;
-                HIP_TRY(hipMemcpy(job->host_rgb + 3 * o, rgb8_dev + 3 * o, 3 * n, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(job->host_z + o, z_dev + o, 4 * n, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(job->host_count + o, count_dev + o, n, hipMemcpyDeviceToHost));
-                if (lin_dev && job->host_linear) HIP_TRY(hipMemcpy(job->host_linear + 3 * o, lin_dev + 3 * o, 12 * n, hipMemcpyDeviceToHost));
-                if (fdev.normal && job->host_normal) HIP_TRY(hipMemcpy(job->host_normal + 3 * o, fdev.normal + 3 * o, 12 * n, hipMemcpyDeviceToHost));
-                if (fdev.albedo && job->host_albedo) HIP_TRY(hipMemcpy(job->host_albedo + 3 * o, fdev.albedo + 3 * o, 12 * n, hipMemcpyDeviceToHost));
-                if (fdev.alpha && job->host_alpha) HIP_TRY(hipMemcpy(job->host_alpha + o, fdev.alpha + o, 4 * n, hipMemcpyDeviceToHost));
-                if (fdev.object_id && job->host_id) HIP_TRY(hipMemcpy(job->host_id + o, fdev.object_id + o, 4 * n, hipMemcpyDeviceToHost));
-            }
+            int x, y0, y1;
+            walk.tile_origin(f.q0 / tile_px, x, y0);
+            walk.tile_origin((f.q0 + f.npix - 1) / tile_px, x, y1);
+            y1 = std::min(cam->height, y1 + dt.tile_h);
+            const size_t o = (size_t)y0 * cam->width, n = y1 > y0 ? (size_t)(y1 - y0) * cam->width : 0;
+            for (int k = 0; k < N_PLANES && n; k++)
+                if (req.dev.p[k])
+                    HIP_TRY(hipMemcpy(job->host.at<uint8_t>(k) + o * PLANE_BYTES[k], req.dev.at<uint8_t>(k) + o * PLANE_BYTES[k],
+                                      n * PLANE_BYTES[k], hipMemcpyDeviceToHost));
         }
         // monotone also when the frame is rendered a second time with larger queues (RT_ERR_OVERFLOW_RETRY)
-        attempt_progress += done;
+        attempt_progress += (int)walk.pixels(f.q0, f.q0 + f.npix);
         int seen = job->progress.load();
         while (attempt_progress > seen && !job->progress.compare_exchange_weak(seen, attempt_progress)) {}
         return RT_OK;
@@ -1800,7 +1839,8 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
             hipEvent_t r0 = nullptr, r1 = nullptr;
             if (want_stats) { HIP_TRY(hipEventCreate(&r0)); HIP_TRY(hipEventCreate(&r1)); HIP_TRY(hipEventRecord(r0, cs)); }
             rtk_launch_resolve(cs, D->scene, W, dc, dt, (uint32_t)q0, npix, p->min_sample, p->max_sample, p->threshold, inv_gamma, phase,
-                               D->scene.bg, rgb8_dev, z_dev, count_dev, packed_dev, 2048, linear, lin_dev);
+                               D->scene.bg, req.dev.at<uint8_t>(PL_RGB8), req.dev.at<float>(PL_Z), req.dev.at<uint8_t>(PL_COUNT), packed_dev,
+                               2048, linear, req.dev.at<float>(PL_LINEAR));
             if (want_stats) { HIP_TRY(hipEventRecord(r1, cs)); resolve_ev.emplace_back(r0, r1); }
             return RT_OK;
         };
@@ -1812,7 +1852,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
             if ((st = timed_resolve(1))) return st;
         }
         // the feature planes of the chunk, from its finished working set (hit flags, pixel list) on the same stream
-        if (features && fdev.any())
+        if (features)
             rtk_launch_features(cs, D->scene, W, *p, dc, dt, (uint32_t)q0, npix, (uint8_t *)D->ws[slot].feat_second.p, fdev, feat_by_walk);
         HIP_TRY(hipGetLastError());
         if (job) {
@@ -1864,14 +1904,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     if (want_stats) {
         rt_stats R;
         memset(&R, 0, sizeof R);
-        unsigned long long hs[ST_COUNT];
-        HIP_TRY(stats_read(Ws[0].stats, 0, ST_COUNT, hs));
-        R.rays_primary = hs[ST_RAYS_PRIMARY]; R.rays_shadow = hs[ST_RAYS_SHADOW]; R.rays_reflect = hs[ST_RAYS_REFLECT];
-        R.rays_refract = hs[ST_RAYS_REFRACT]; R.instance_visits = hs[ST_INSTANCE_VISITS]; R.bvh_nodes_visited = hs[ST_BVH_NODES];
-        R.tris_tested = hs[ST_TRIS]; R.photon_queries = hs[ST_PHOTON_QUERIES]; R.photons_visited = hs[ST_PHOTONS_VISITED];
-        R.pixels = 0; R.samples = hs[ST_RAYS_PRIMARY];
-        R.gather_rounds = hs[ST_GATHER_ROUNDS]; R.gather_slow = hs[ST_GATHER_SLOW]; R.gather_leaf_reads = hs[ST_GATHER_LEAF_READS];
-        R.peak_rays = hs[ST_PEAK_RAYS]; R.peak_queries = hs[ST_PEAK_QUERIES];
+        if ((st = read_counters(Ws[0].stats, R))) return st;
         // per-stream intervals between consecutive marks: with two chunks in flight a kernel shares the GPU
         // with the other stream's kernels, so these are durations under overlap (the same thing rocprofv3 reports)
         for (int sl = 0; sl < n_slots; sl++)
@@ -1895,60 +1928,67 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, e_begin, e_end));
         R.ms_total = ms;
-        for (uint64_t k = 0; k < (uint64_t)dt.n_tiles; k++) {
-            const int t = dt.first + (int)k * dt.stride;
-            const int tx = t % dt.tiles_x, ty = t / dt.tiles_x;
-            const int w = std::min(dt.tile_w, cam->width - tx * dt.tile_w), h = std::min(dt.tile_h, cam->height - ty * dt.tile_h);
-            if (w > 0 && h > 0) R.pixels += (uint64_t)w * h;
-        }
+        R.pixels = walk.pixels(0, total_px);
         if (stats_out) *stats_out = R;
         if (job) job->stats = R;
     }
     return RT_OK;
 }
 
+// Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
+// half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
+// if that ever overflows, a synchronous render
+// is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
+// library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
+static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                              const RenderRequest &req)
+{
+    rt_status st = render_tiles_once(s, cam, p, tiles, device, req, false);
+    int attempts = 1;
+    if (st == RT_ERR_OVERFLOW_RETRY) {
+        attempts = 2;
+        st = render_tiles_once(s, cam, p, tiles, device, req, true);
+    }
+    if (st == RT_OK && req.stats_out) req.stats_out->attempts = (uint64_t)attempts;
+    if (st == RT_OK && req.job) req.job->stats.attempts = (uint64_t)attempts;
+    return st;
+}
+
+// RenderPixel's outputs (FIN/main.cpp:273-338) into the caller's device planes, with the optional ones of rt_outputs: the linear
+// colour and the first hit's normal, albedo, coverage and node (k_features)
+static rt_status render_device(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                               int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out)
+{
+    if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", name);
+    rt_status st = check_outputs(name, device_planes);
+    if (st) return st;
+    RenderRequest req;
+    req.dev = Planes(*device_planes);
+    req.stream = (hipStream_t)hip_stream; req.sync = sync != 0; req.stats_out = stats_out;
+    return render_tiles(s, cam, p, tiles, device, req);
+}
+
 extern "C" rt_status rt_render_tiles_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
                                             int device, void *hip_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
                                             int sync, rt_stats *stats_out)
 {
-    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_device: scene is NULL");
-    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, rgb8_dev, z_dev, count_dev,
-                        sync != 0, stats_out, nullptr);
+    const rt_outputs o = outputs_of(rgb8_dev, z_dev, count_dev);
+    return render_device("rt_render_tiles_device", s, cam, p, tiles, device, hip_stream, &o, sync, stats_out);
 }
 
 extern "C" rt_status rt_render_tiles_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
                                                    int device, void *hip_stream, uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev,
                                                    float *rgb_linear_dev, int sync, rt_stats *stats_out)
 {
-    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_linear_device: scene is NULL");
     if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_render_tiles_linear_device: the linear plane is required");
-    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, rgb8_dev, z_dev, count_dev,
-                        sync != 0, stats_out, nullptr, nullptr, true, rgb_linear_dev);
+    const rt_outputs o = outputs_of(rgb8_dev, z_dev, count_dev, rgb_linear_dev);
+    return render_device("rt_render_tiles_linear_device", s, cam, p, tiles, device, hip_stream, &o, sync, stats_out);
 }
 
-// rt_outputs: the caller's sizeof first, then the three required planes
-static rt_status check_outputs(const char *name, const rt_outputs *o)
-{
-    if (!o) return fail(RT_ERR_ARG, "%s: the plane descriptor is NULL", name);
-    if (o->struct_size != (uint32_t)sizeof(rt_outputs))
-        return fail(RT_ERR_ARG, "%s: rt_outputs.struct_size is %u, this library's is %zu", name, o->struct_size, sizeof(rt_outputs));
-    if (!o->rgb8 || !o->z || !o->count) return fail(RT_ERR_ARG, "%s: rgb8, z and count are required", name);
-    return RT_OK;
-}
-
-// RenderPixel's outputs (FIN/main.cpp:273-338) into device planes, with the optional ones of rt_outputs: the linear colour and
-// the first hit's normal, albedo, coverage and node (k_features)
 extern "C" rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
                                                     int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out)
 {
-    if (!s) return fail(RT_ERR_ARG, "rt_render_tiles_outputs_device: scene is NULL");
-    rt_status st = check_outputs("rt_render_tiles_outputs_device", device_planes);
-    if (st) return st;
-    DevFeatures f;
-    f.normal = device_planes->normal; f.albedo = device_planes->albedo; f.alpha = device_planes->alpha; f.object_id = device_planes->object_id;
-    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, device_planes->rgb8, device_planes->z,
-                        device_planes->count, sync != 0, stats_out, nullptr, nullptr, device_planes->rgb_linear != nullptr,
-                        device_planes->rgb_linear, &f);
+    return render_device("rt_render_tiles_outputs_device", s, cam, p, tiles, device, hip_stream, device_planes, sync, stats_out);
 }
 
 // both packed entry points: 8-byte records, or 24-byte ones with the linear plane (linear)
@@ -1965,8 +2005,10 @@ static rt_status render_packed(const char *name, rt_scene *s, const rt_camera *c
     if (linear) need *= 3;
     if (packed_bytes < need) return fail(RT_ERR_ARG, "%s: buffer of %llu bytes, this call's tiles need %llu", name,
                                          (unsigned long long)packed_bytes, (unsigned long long)need);
-    return render_tiles(s, cam, p, tiles, device, (hipStream_t)hip_stream, hip_stream != nullptr, nullptr, nullptr, nullptr,
-                        sync != 0, stats_out, nullptr, packed_dev, linear);
+    RenderRequest req;
+    req.packed = packed_dev; req.rec_bytes = linear ? 24 : 8;
+    req.stream = (hipStream_t)hip_stream; req.sync = sync != 0; req.stats_out = stats_out;
+    return render_tiles(s, cam, p, tiles, device, req);
 }
 
 extern "C" rt_status rt_render_tiles_packed_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
@@ -2075,14 +2117,8 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
     if (!claim.ok) return fail(RT_ERR_STATE, "rt_render_counters: another call on this scene is using device %d", device);
     // (the verdict of the asynchronous renders stays with rt_render_check: last_pending is left as it is)
     if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
-    unsigned long long hs[ST_COUNT];
-    HIP_TRY(stats_read(D->stats.p, 0, ST_COUNT, hs));
-    out->rays_primary = hs[ST_RAYS_PRIMARY]; out->rays_shadow = hs[ST_RAYS_SHADOW]; out->rays_reflect = hs[ST_RAYS_REFLECT];
-    out->rays_refract = hs[ST_RAYS_REFRACT]; out->instance_visits = hs[ST_INSTANCE_VISITS]; out->bvh_nodes_visited = hs[ST_BVH_NODES];
-    out->tris_tested = hs[ST_TRIS]; out->photon_queries = hs[ST_PHOTON_QUERIES]; out->photons_visited = hs[ST_PHOTONS_VISITED];
-    out->samples = hs[ST_RAYS_PRIMARY];
-    out->gather_rounds = hs[ST_GATHER_ROUNDS]; out->gather_slow = hs[ST_GATHER_SLOW]; out->gather_leaf_reads = hs[ST_GATHER_LEAF_READS];
-    out->peak_rays = hs[ST_PEAK_RAYS]; out->peak_queries = hs[ST_PEAK_QUERIES];
+    rt_status st = read_counters(D->stats.p, *out);
+    if (st) return st;
     if (reset) {
         // the drop counter and the queue peaks belong to the overflow verdict and the queue sizing: not touched
         static_assert(ST_QUEUE_OVERFLOW == ST_PHOTONS_VISITED + 1 && ST_GATHER_ROUNDS == ST_QUEUE_OVERFLOW + 1 && ST_PEAK_RAYS == ST_GATHER_LEAF_READS + 1, "counter layout");
@@ -2095,29 +2131,23 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
 static rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
                                   rt_setup_ms *ms_out, bool own_job);
 
-// rt_render_begin, rt_render_begin_linear (rgb_linear != NULL: the linear plane as a fourth output) and rt_render_begin_outputs
-// (feat: the host planes of the first-hit features that are wanted)
-struct HostFeatures { float *normal = nullptr, *albedo = nullptr, *alpha = nullptr; int32_t *object_id = nullptr; };
+// BeginRender (FIN/main.cpp:984-1010): rt_render_begin, rt_render_begin_linear and rt_render_begin_outputs, with the planes
+// RenderPixel (:273-338) could have kept: its colour before gamma, and the first hit's normal, albedo, coverage and node
 static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out, const HostFeatures &feat = HostFeatures())
+                              const rt_outputs *host_planes, rt_job **out)
 {
     if (!s || !out) return fail(RT_ERR_ARG, "%s: scene/out is NULL", name);
-    rt_status st = validate_render(s, cam, p, tiles);
+    rt_status st = check_outputs(name, host_planes);
     if (st) return st;
-    if (!rgb8 || !z || !count) return fail(RT_ERR_ARG, "%s: output buffers are required", name);
+    if ((st = validate_render(s, cam, p, tiles))) return st;
     DeviceState *D = nullptr;
     if ((st = prepare_device(s, device, &D))) return st;      // fail early (and loudly) when there is no GPU
     rt_job *job = new rt_job;
     job->scene = s;
-    job->host_rgb = rgb8; job->host_z = z; job->host_count = count; job->host_linear = rgb_linear;
-    job->host_normal = feat.normal; job->host_albedo = feat.albedo; job->host_alpha = feat.alpha; job->host_id = feat.object_id;
+    job->host = Planes(*host_planes);
     s->live_jobs.fetch_add(1);
     const rt_camera camv = *cam; const rt_params pv = *p; const rt_tile_range tv = *tiles;
     job->worker = std::thread([=]() {
-        rt_status r = RT_OK;
-        const size_t npx = (size_t)camv.width * camv.height;
-        uint8_t *d_rgb = nullptr, *d_cnt = nullptr; float *d_z = nullptr, *d_lin = nullptr;
-        DevFeatures d_feat;
         auto body = [&]() -> rt_status {
             HIP_TRY(hipSetDevice(device));
             // BeginRender calls generatePhotonMap() before it spawns its workers (FIN/main.cpp:984-998, :350-402); here the
@@ -2140,37 +2170,22 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
                     if (g) return g;
                 }
             }
-            HIP_TRY(hipMalloc((void **)&d_rgb, npx * 3)); HIP_TRY(hipMalloc((void **)&d_z, npx * 4)); HIP_TRY(hipMalloc((void **)&d_cnt, npx));
-            HIP_TRY(hipMemcpy(d_rgb, rgb8, npx * 3, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_z, z, npx * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_cnt, count, npx, hipMemcpyHostToDevice));
-            // the linear plane lives on the device only when it is asked for (a strided job takes it in its packed records)
-            if (rgb_linear && tv.stride == 1) {
-                HIP_TRY(hipMalloc((void **)&d_lin, npx * 12));
-                HIP_TRY(hipMemcpy(d_lin, rgb_linear, npx * 12, hipMemcpyHostToDevice));
-            }
-            // and so do the feature planes (a strided job stages them by its tile walk instead: render_tiles_once)
-            if (tv.stride == 1) {
-                auto plane = [&](void **d, const void *h, size_t bytes) -> rt_status {
-                    if (!h) return RT_OK;
-                    HIP_TRY(hipMalloc(d, bytes));
-                    HIP_TRY(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-                    return RT_OK;
-                };
-                rt_status fs;
-                if ((fs = plane((void **)&d_feat.normal, feat.normal, npx * 12)) || (fs = plane((void **)&d_feat.albedo, feat.albedo, npx * 12)) ||
-                    (fs = plane((void **)&d_feat.alpha, feat.alpha, npx * 4)) || (fs = plane((void **)&d_feat.object_id, feat.object_id, npx * 4))) return fs;
+            // a device copy of every plane that was asked for, starting from the caller's values -- but a strided job takes its
+            // linear plane in its packed records and its features in walk-indexed staging planes (render_tiles_once)
+            RenderRequest req;
+            req.job = job;
+            req.rec_bytes = job->host.p[PL_LINEAR] ? 24 : 8;
+            ScopedDevBuf dev[N_PLANES];
+            const size_t npx = (size_t)camv.width * camv.height;
+            for (int i = 0; i < N_PLANES; i++) {
+                if (!job->host.p[i] || (tv.stride != 1 && i >= PL_LINEAR)) continue;
+                if (rt_status us = dev[i].upload(job->host.p[i], npx * PLANE_BYTES[i])) return us;
+                req.dev.p[i] = dev[i].p;
             }
             // render_tiles copies every finished band of rows back into the caller's buffers
-            return render_tiles(s, &camv, &pv, &tv, device, nullptr, false, d_rgb, d_z, d_cnt, true, nullptr, job, nullptr,
-                                rgb_linear != nullptr, d_lin, &d_feat);
+            return render_tiles(s, &camv, &pv, &tv, device, req);
         };
-        r = body();
-        if (d_rgb) (void)hipFree(d_rgb);
-        if (d_z) (void)hipFree(d_z);
-        if (d_cnt) (void)hipFree(d_cnt);
-        if (d_lin) (void)hipFree(d_lin);
-        for (void *d : {(void *)d_feat.normal, (void *)d_feat.albedo, (void *)d_feat.alpha, (void *)d_feat.object_id}) if (d) (void)hipFree(d);
+        const rt_status r = body();
         job->status = r;
         if (r) job->error = g_err;
         job->done.store(true);
@@ -2183,27 +2198,22 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
 extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                      uint8_t *rgb8, float *z, uint8_t *count, rt_job **out)
 {
-    return render_begin("rt_render_begin", s, cam, p, tiles, device, rgb8, z, count, nullptr, out);
+    const rt_outputs o = outputs_of(rgb8, z, count);
+    return render_begin("rt_render_begin", s, cam, p, tiles, device, &o, out);
 }
 
 extern "C" rt_status rt_render_begin_linear(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                             uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out)
 {
     if (!rgb_linear) return fail(RT_ERR_ARG, "rt_render_begin_linear: the linear plane is required");
-    return render_begin("rt_render_begin_linear", s, cam, p, tiles, device, rgb8, z, count, rgb_linear, out);
+    const rt_outputs o = outputs_of(rgb8, z, count, rgb_linear);
+    return render_begin("rt_render_begin_linear", s, cam, p, tiles, device, &o, out);
 }
 
-// BeginRender (FIN/main.cpp:984-1010) with the planes RenderPixel (:273-338) could have kept: its colour before gamma, and the
-// first hit's normal, albedo, coverage and node
 extern "C" rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                              const rt_outputs *host_planes, rt_job **out)
 {
-    rt_status st = check_outputs("rt_render_begin_outputs", host_planes);
-    if (st) return st;
-    HostFeatures f;
-    f.normal = host_planes->normal; f.albedo = host_planes->albedo; f.alpha = host_planes->alpha; f.object_id = host_planes->object_id;
-    return render_begin("rt_render_begin_outputs", s, cam, p, tiles, device, host_planes->rgb8, host_planes->z, host_planes->count,
-                        host_planes->rgb_linear, out, f);
+    return render_begin("rt_render_begin_outputs", s, cam, p, tiles, device, host_planes, out);
 }
 
 extern "C" int rt_render_progress(rt_job *j) { return j ? j->progress.load() : 0; }
