@@ -18,30 +18,7 @@
 
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
-#include "rt_dev.h"
-
-// launch wrappers defined in rt_kernels.hip
-// (the trailing `fx`: the secondary plane of a reproducible render, RT_RENDER_REPRODUCIBLE; NULL selects the default instantiations)
-void rtk_launch_primary(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &, uint32_t *,
-                        const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int, int, int, const float *, int,
-                        unsigned long long *fx = nullptr);
-void rtk_launch_bounce(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &,
-                       const DevRayQueue &, uint32_t *, int, int, unsigned long long *fx = nullptr);
-void rtk_launch_trace(hipStream_t, const DevScene &, int, const float *, long long, uint8_t *, float *, float *, float *, int32_t *, uint8_t *);
-bool rtk_launch_wavefront_queue(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevRayQueue &, const uint32_t *,
-                                const DevRayQueue &, uint32_t *, const DevCamera &, const DevTiles &, uint32_t, int, int,
-                                unsigned long long *fx = nullptr);
-void rtk_launch_gather(hipStream_t, const DevPhotonMap &, const float4 *, const float4 *, const float4 *, const uint32_t *,
-                       uint32_t, int, float, float *, float *, float *, int, unsigned long long *, int, uint32_t *, float *,
-                       unsigned long long *fx = nullptr);
-void rtk_launch_fold_fx(hipStream_t, float *sample_rgb, unsigned long long *fx, size_t samples);
-bool rtk_wavefront_usable(const DevScene &, const rt_params &);
-void rtk_launch_resolve(hipStream_t, const DevScene &, const DevWork &, const DevCamera &, const DevTiles &, uint32_t, uint32_t, int, int,
-                        float, float, int, const float *, uint8_t *, float *, uint8_t *, void *, int, bool linear = false,
-                        float *rgb_linear = nullptr);
-void rtk_launch_unpack_tiles(hipStream_t, const void *, int, int, int, int, int, int, uint8_t *, float *, uint8_t *, float *rgb_linear = nullptr);
-void rtk_launch_features(hipStream_t, const DevScene &, const DevWork &, const rt_params &, const DevCamera &, const DevTiles &, uint32_t, uint32_t,
-                         uint8_t *second, const DevFeatures &, bool by_walk);
+#include "rt_launch.h"
 
 // k_gather is a persistent grid that pulls query batches from a counter: enough workgroups to fill
 // every CU at the kernel's occupancy (256 CUs x 5 resident workgroups of 4 waves)
@@ -57,22 +34,6 @@ static int gather_blocks()
 }
 static const size_t STATS_BYTES = (size_t)ST_COUNT * RT_STAT_STRIDE * 8;    // the statistics block: counters RT_STAT_STRIDE apart (rt_dev.h)
 #define GATHER_BLOCKS gather_blocks()
-
-void rtk_launch_photon_trace(hipStream_t, const DevScene &, unsigned long long, uint32_t, uint32_t, int, float *, uint32_t *, int);
-// rt_photon_build.hip: the photon set-up on the GPU
-struct PhotonGridOut { float min[3]; float cell; int dim[3]; };
-size_t rtk_photon_compact_scratch(uint32_t n_attempts);
-void rtk_photon_compact(hipStream_t, const float *recs, const uint32_t *count, uint32_t n_attempts, int mode, unsigned long long max_count,
-                        void *state_dev, rt_photon *out, uint32_t out_cap, void *scratch, size_t scratch_bytes);
-void rtk_photon_scale(hipStream_t, rt_photon *ph, uint32_t n, float scale);
-void rtk_photon_copy_skipping(hipStream_t, const rt_photon *in, uint32_t n_in, const uint32_t *skip, uint32_t n_skip, rt_photon *out);
-size_t rtk_photon_structure_scratch(uint32_t n, uint32_t n_sub);
-hipError_t rtk_photon_structure(hipStream_t, const rt_photon *ph, uint32_t n, uint32_t n_sub, float4 *pa, float4 *pb, float4 *box4,
-                                uint32_t *grid, PhotonGridOut *grid_out, void *scratch, size_t scratch_bytes);
-size_t rtk_photon_unreachable_scratch(uint32_t n);
-hipError_t rtk_photon_unreachable(hipStream_t, const rt_photon *ph0, uint32_t n, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes, uint32_t result[16]);
-void rtk_photon_pack_positions(hipStream_t, const rt_photon *ph0, uint32_t n, void *recs16);
-void rtk_photon_cell_start(hipStream_t, const float4 *tbox, uint32_t n_leaves, const float grid_min[3], float cell, const int dim[3], float radius, uint32_t *start);
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -1462,12 +1423,11 @@ static rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float ra
 
 struct Timing { std::vector<hipEvent_t> ev; std::vector<int> cls; };
 
-static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const DevWork &W, const rt_params &P, Timing *tm,
-                              const DevCamera &dc, const DevTiles &dt, uint32_t q0, uint32_t npix, int j0, int ns,
-                              int max_sample, int mode, const float *rays_dev, unsigned long long *fx = nullptr)
+// One tracing pass over a chunk on its stream: primary samples, the levels of the ray tree, the gathers against the photon maps,
+// and (reproducible mode) the fold of the secondary plane -- the chunk's samples are final in W.sample_* behind it.
+static rt_status run_pipeline(DeviceState *D, hipStream_t st, const DevWork &W, const rt_params &P, Timing *tm, const RenderPass &pass)
 {
-    const int max_blocks = 256 * 5;
-    static_assert(256 * 5 <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
+    unsigned long long *const fx = pass.fx;
     auto mark = [&](int cls) -> rt_status {
         if (!tm) return RT_OK;
         hipEvent_t e;
@@ -1481,10 +1441,10 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
     HIP_TRY(hipMemsetAsync(W.counts, 0, CNT_RESET * 4, st));
     // reproducible mode (fx != NULL): the secondary plane of the chunk's slots starts at zero with the chunk's first pass; every
     // pass folds it into sample_rgb at its end and leaves it zero behind (k_fold_fx), which is where a second pass finds it
-    const size_t chunk_slots = (size_t)npix * (size_t)max_sample;
-    if (fx && mode != 1) HIP_TRY(hipMemsetAsync(fx, 0, chunk_slots * 24, st));
+    const size_t chunk_slots = (size_t)pass.npix * (size_t)pass.max_sample;
+    if (fx && pass.mode != 1) HIP_TRY(hipMemsetAsync(fx, 0, chunk_slots * 24, st));
     if ((s = mark(-1))) return s;
-    rtk_launch_primary(st, D->scene, W, P, W.rq[1], W.counts + 1, dc, dt, q0, npix, j0, ns, max_sample, mode, rays_dev, max_blocks, fx);
+    rtk_launch_primary(st, D->scene, W, P, pass, RT_TRACE_BLOCKS);
     if ((s = mark(0))) return s;
     // P6: a side ray is spawned when its refraction ray ARRIVES, one queue level later than a sibling
     // would be, so a path can take up to two levels per bounce
@@ -1492,28 +1452,33 @@ static rt_status run_pipeline(DeviceState *D, int slot, hipStream_t st, const De
     // k_wavefront's overflow (level-1 queue) first goes through a second k_wavefront pass; what overflows again, and the
     // models without that kernel, take one launch per level
     int first_level = 1;
-    if (max_level >= 2 && rtk_launch_wavefront_queue(st, D->scene, W, P, W.rq[1], W.counts + 1, W.rq[0], W.counts + 2, dc, dt, q0, max_sample, mode, fx)) first_level = 2;
+    if (max_level >= 2 && rtk_launch_wavefront_queue(st, D->scene, W, P, pass)) first_level = 2;
     // (further passes of the same kernel over what the second one could not keep were measured: 1 / 2 / 3 / 4 queue passes, tracer ms behind
     // the first pass, Cornell 0.34 / 0.36 / 0.40 / 0.44, C3 13.0 / 13.0 / 13.1 / 13.1 -- the second pass takes everything that matters)
     for (int level = first_level; level <= max_level && level < 15; level++)
-        rtk_launch_bounce(st, D->scene, W, P, W.rq[level & 1], W.rq[(level + 1) & 1], W.counts + level + 1, level, max_blocks, fx);
+        rtk_launch_bounce(st, D->scene, W, P, level, RT_TRACE_BLOCKS, fx);
     if ((s = mark(1))) return s;
     rt_status cs;
     if ((cs = ensure_cell_start(D, false, P.knn_k, P.knn_radius, st))) return cs;
+    // reproducible mode: the per-cell hints are off (they pick which of two exact paths, with two summation orders, a query
+    // takes, from whichever query of the cell was answered last)
+    GatherRequest g = {};
+    g.sample_rgb = W.sample_rgb; g.stats = W.stats; g.fx = fx;
     if (D->scene.pm.n_leaves) {
-        rtk_launch_gather(st, D->scene.pm, W.pq.qa, W.pq.qb, W.pq.qc, W.counts + CNT_PHOTONQ, W.pq.cap, P.knn_k, P.knn_radius,
-                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT, fx ? nullptr : (float *)D->cell_rk2.p, fx);
+        g.pm = D->scene.pm; g.q = W.pq; g.count = W.counts + CNT_PHOTONQ; g.k = P.knn_k; g.radius = P.knn_radius;
+        g.next_batch = W.counts + CNT_GATHER_NEXT; g.cell_rk2 = fx ? nullptr : (float *)D->cell_rk2.p;
+        rtk_launch_gather(st, g, GATHER_BLOCKS);
         if ((s = mark(2))) return s;
     }
-    if (D->scene.cm.n_leaves && P.caustic_k > 0 && W.cq.cap && (cs = ensure_cell_start(D, true, P.caustic_k, P.caustic_radius, st))) return cs;
     if (D->scene.cm.n_leaves && P.caustic_k > 0 && W.cq.cap) {
         // the P13-family models queued their caustic lookups separately: same kernel on the second map
-        rtk_launch_gather(st, D->scene.cm, W.cq.qa, W.cq.qb, W.cq.qc, W.counts + CNT_CAUSTICQ, W.cq.cap, P.caustic_k, P.caustic_radius,
-                          W.sample_rgb, nullptr, nullptr, 0, W.stats, GATHER_BLOCKS, W.counts + CNT_GATHER_NEXT2, fx ? nullptr : (float *)D->ccell_rk2.p, fx);
+        if ((cs = ensure_cell_start(D, true, P.caustic_k, P.caustic_radius, st))) return cs;
+        g.pm = D->scene.cm; g.q = W.cq; g.count = W.counts + CNT_CAUSTICQ; g.k = P.caustic_k; g.radius = P.caustic_radius;
+        g.next_batch = W.counts + CNT_GATHER_NEXT2; g.cell_rk2 = fx ? nullptr : (float *)D->ccell_rk2.p;
+        rtk_launch_gather(st, g, GATHER_BLOCKS);
         if ((s = mark(2))) return s;
     }
-    // reproducible mode: the per-cell hints above are off (they pick which of two exact paths, with two summation orders, a query
-    // takes, from whichever query of the cell was answered last); the secondary plane goes into the samples before k_resolve
+    // the secondary plane goes into the samples before k_resolve
     if (fx) rtk_launch_fold_fx(st, W.sample_rgb, fx, chunk_slots);
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -1657,7 +1622,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
             // sphere, bounce 8) -- four per sample on top of the hemisphere rays, 640 B per sample of queue memory
             // (the kernels' own predicate: a scene k_wavefront does not take -- a BVH beyond its traversal stack, RT_TRACER=levels -- goes
             // through the per-level kernels and gets their figure; P12 through k_wavefront keeps the per-level figure too: its overflow is scene-dependent)
-            const bool wf = (p->shade_model == RT_SHADE_FIN || p->shade_model == RT_SHADE_P13) && rtk_wavefront_usable(D->scene, *p);
+            const bool wf = rtk_wavefront_usable(D->scene, *p) && p->shade_model != RT_SHADE_P12;
             ray_factor = wf ? 1.0 : (p->shade_model == RT_SHADE_P12 ? (double)std::max(p->hemisphere_sample, 1) + 3.0 : 4.0);
             query_factor = 0.5;
         }
@@ -1834,26 +1799,33 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         Timing *tmp = want_stats ? &tm[slot] : nullptr;
         const uint32_t npix = (uint32_t)std::min<uint64_t>(ppc, total_px - q0);
         HIP_TRY(hipMemsetAsync(W.counts + CNT_PIXLIST, 0, 4, cs));
-        if ((st = run_pipeline(D, slot, cs, W, *p, tmp, dc, dt, (uint32_t)q0, npix, 0, p->min_sample, p->max_sample, 0, nullptr, Fx[slot]))) return st;
+        RenderPass pass = {};
+        pass.cam = dc; pass.tiles = dt; pass.q0 = (uint32_t)q0; pass.npix = npix; pass.max_sample = p->max_sample; pass.fx = Fx[slot];
+        pass.mode = 0; pass.j0 = 0; pass.ns = p->min_sample;
+        if ((st = run_pipeline(D, cs, W, *p, tmp, pass))) return st;
+        ResolveArgs ra = {};
+        ra.cam = dc; ra.tiles = dt; ra.q0 = pass.q0; ra.npix = npix; ra.min_sample = p->min_sample; ra.max_sample = p->max_sample;
+        ra.threshold = p->threshold; ra.inv_gamma = inv_gamma; memcpy(ra.bg, D->scene.bg, sizeof ra.bg); ra.S = D->scene;
+        ra.rgb8 = req.dev.at<uint8_t>(PL_RGB8); ra.z = req.dev.at<float>(PL_Z); ra.count = req.dev.at<uint8_t>(PL_COUNT);
+        ra.packed = (uint2 *)packed_dev; ra.rgb_linear = req.dev.at<float>(PL_LINEAR);
         auto timed_resolve = [&](int phase) -> rt_status {
             hipEvent_t r0 = nullptr, r1 = nullptr;
             if (want_stats) { HIP_TRY(hipEventCreate(&r0)); HIP_TRY(hipEventCreate(&r1)); HIP_TRY(hipEventRecord(r0, cs)); }
-            rtk_launch_resolve(cs, D->scene, W, dc, dt, (uint32_t)q0, npix, p->min_sample, p->max_sample, p->threshold, inv_gamma, phase,
-                               D->scene.bg, req.dev.at<uint8_t>(PL_RGB8), req.dev.at<float>(PL_Z), req.dev.at<uint8_t>(PL_COUNT), packed_dev,
-                               2048, linear, req.dev.at<float>(PL_LINEAR));
+            ra.phase = phase;
+            rtk_launch_resolve(cs, W, ra, 2048, linear);
             if (want_stats) { HIP_TRY(hipEventRecord(r1, cs)); resolve_ev.emplace_back(r0, r1); }
             return RT_OK;
         };
         if (resolve_waits[slot]) { HIP_TRY(hipStreamWaitEvent(cs, e_fork, 0)); resolve_waits[slot] = false; }
         if ((st = timed_resolve(0))) return st;
         if (p->max_sample > p->min_sample) {
-            if ((st = run_pipeline(D, slot, cs, W, *p, tmp, dc, dt, (uint32_t)q0, npix, p->min_sample,
-                                   p->max_sample - p->min_sample, p->max_sample, 1, nullptr, Fx[slot]))) return st;
+            pass.mode = 1; pass.j0 = p->min_sample; pass.ns = p->max_sample - p->min_sample;
+            if ((st = run_pipeline(D, cs, W, *p, tmp, pass))) return st;
             if ((st = timed_resolve(1))) return st;
         }
         // the feature planes of the chunk, from its finished working set (hit flags, pixel list) on the same stream
         if (features)
-            rtk_launch_features(cs, D->scene, W, *p, dc, dt, (uint32_t)q0, npix, (uint8_t *)D->ws[slot].feat_second.p, fdev, feat_by_walk);
+            rtk_launch_features(cs, D->scene, W, *p, pass, (uint8_t *)D->ws[slot].feat_second.p, fdev, feat_by_walk);
         HIP_TRY(hipGetLastError());
         if (job) {
             InFlight f; f.q0 = q0; f.npix = npix;
@@ -2050,8 +2022,10 @@ static rt_status tiles_unpack(const char *name, int device, void *hip_stream, co
         return fail(RT_ERR_ARG, "%s: %d tiles per rank x %d ranks cannot hold %lld tiles", name, tiles_per_rank, world, (long long)total);
     if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
     HIP_TRY(hipSetDevice(device));
-    rtk_launch_unpack_tiles((hipStream_t)hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h, rgb8_dev, z_dev, count_dev,
-                            rgb_linear_dev);
+    UnpackRequest u = {};
+    u.gathered = gathered_dev; u.world = world; u.per_rank = tiles_per_rank; u.width = width; u.height = height; u.tile_w = tile_w; u.tile_h = tile_h;
+    u.rgb8 = rgb8_dev; u.z = z_dev; u.count = count_dev; u.rgb_linear = rgb_linear_dev;
+    rtk_launch_unpack_tiles((hipStream_t)hip_stream, u);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -2264,8 +2238,10 @@ extern "C" rt_status rt_trace_rays(rt_scene *s, int shade_model, int device, con
     const size_t sizes[6] = {(size_t)n, (size_t)n * 4, (size_t)n * 12, (size_t)n * 12, (size_t)n * 4, (size_t)n};
     if ((st = D->t_in.upload(rays, (size_t)n * 24))) return st;
     for (int k = 0; k < 6; k++) if ((st = D->t_out[k].ensure(sizes[k]))) return st;
-    rtk_launch_trace(D->stream, D->scene, shade_model, (const float *)D->t_in.p, n, (uint8_t *)D->t_out[0].p, (float *)D->t_out[1].p,
-                     (float *)D->t_out[2].p, (float *)D->t_out[3].p, (int32_t *)D->t_out[4].p, (uint8_t *)D->t_out[5].p);
+    TraceOut o = {};
+    o.hit = (uint8_t *)D->t_out[0].p; o.z = (float *)D->t_out[1].p; o.p = (float *)D->t_out[2].p; o.N = (float *)D->t_out[3].p;
+    o.node = (int32_t *)D->t_out[4].p; o.front = (uint8_t *)D->t_out[5].p;
+    rtk_launch_trace(D->stream, D->scene, shade_model, (const float *)D->t_in.p, n, o);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(D->stream));
     void *dst[6] = {hit, z, p, N, node, front};
@@ -2303,9 +2279,12 @@ extern "C" rt_status rt_estimate_irradiance(rt_scene *s, int device, int32_t k, 
     if ((st = D->t_out[4].ensure((size_t)n * 12))) return st;
     if ((st = D->t_in.upload(cnt.data(), cnt.size() * 4))) return st;
     if ((st = ensure_cell_start(D, false, k, radius, D->stream))) return st;
-    rtk_launch_gather(D->stream, D->scene.pm, (const float4 *)D->t_out[0].p, (const float4 *)D->t_out[1].p, (const float4 *)D->t_out[2].p,
-                      (const uint32_t *)D->t_in.p, cnt[0], k, radius, nullptr, (float *)D->t_out[3].p, (float *)D->t_out[4].p, 1, nullptr, GATHER_BLOCKS,
-                      (uint32_t *)D->t_in.p + 1, nullptr);
+    GatherRequest g = {};
+    g.pm = D->scene.pm; g.k = k; g.radius = radius;
+    g.q.qa = (float4 *)D->t_out[0].p; g.q.qb = (float4 *)D->t_out[1].p; g.q.qc = (float4 *)D->t_out[2].p; g.q.cap = cnt[0];
+    g.count = (const uint32_t *)D->t_in.p; g.next_batch = (uint32_t *)D->t_in.p + 1;
+    g.out_irr = (float *)D->t_out[3].p; g.out_dir = (float *)D->t_out[4].p;
+    rtk_launch_gather(D->stream, g, GATHER_BLOCKS);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(D->stream));
     HIP_TRY(hipMemcpy(irr, D->t_out[3].p, (size_t)n * 12, hipMemcpyDeviceToHost));
@@ -2336,16 +2315,18 @@ extern "C" rt_status rt_shade_rays(rt_scene *s, const rt_params *p, int device, 
     const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
     if ((st = ensure_workspace(D, 0, chunk, pv.bounce, 1, 2, pv.caustic_k > 0 && D->scene.cm.n_leaves != 0, 0, 0, reproducible))) return st;
     const DevWork W = make_work(D, 0);
-    unsigned long long *fx = reproducible ? (unsigned long long *)D->ws[0].sample_fx.p : nullptr;     // run_pipeline folds it before the copy back
-    DevCamera dc; camera_setup(cam, dc);
-    DevTiles dt; memset(&dt, 0, sizeof dt);
+    RenderPass pass = {};
+    camera_setup(cam, pass.cam);
+    pass.ns = pass.max_sample = 1; pass.mode = 2;
+    pass.fx = reproducible ? (unsigned long long *)D->ws[0].sample_fx.p : nullptr;     // run_pipeline folds it before the copy back
     HIP_TRY(stats_zero(W.stats, 0, ST_COUNT, D->stream));
     for (int64_t off = 0; off < n; off += (int64_t)chunk) {
         const uint32_t m = (uint32_t)std::min<int64_t>((int64_t)chunk, n - off);
         if ((st = D->t_in.upload(rays + 6 * off, (size_t)m * 24))) return st;
         HIP_TRY(hipMemsetAsync(W.sample_hit, 0, m, D->stream));
         HIP_TRY(hipMemsetAsync(W.sample_rgb, 0, (size_t)m * 12, D->stream));
-        if ((st = run_pipeline(D, 0, D->stream, W, pv, nullptr, dc, dt, (uint32_t)off, m, 0, 1, 1, 2, (const float *)D->t_in.p, fx))) return st;
+        pass.q0 = (uint32_t)off; pass.npix = m; pass.rays = (const float *)D->t_in.p;      // (the upload above may have moved the buffer)
+        if ((st = run_pipeline(D, D->stream, W, pv, nullptr, pass))) return st;
         HIP_TRY(hipStreamSynchronize(D->stream));
         HIP_TRY(hipMemcpy(hit + off, W.sample_hit, m, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(rgb + 3 * off, W.sample_rgb, (size_t)m * 12, hipMemcpyDeviceToHost));
@@ -2365,7 +2346,6 @@ extern "C" rt_status rt_shade_rays(rt_scene *s, const rt_params *p, int device, 
 // Everything stays on the device: k_photon_trace writes each attempt's photons, rtk_photon_compact (rt_photon_build.hip)
 // consumes the attempts in order and packs the stored photons into D->raw_photons (1-based, [0] zero), then
 // ScalePhotonPowers.  The caller holds the device claim.
-struct CompactStateHost { unsigned long long attempts, counted; uint32_t stored, pad; };
 static rt_status photon_pass_device(rt_scene *s, DeviceState *D, uint32_t max_count, int photon_bounce, uint32_t seed, int mode,
                                     uint32_t *n_out, uint64_t *attempts_out, const char *who)
 {
@@ -2384,18 +2364,21 @@ static rt_status photon_pass_device(rt_scene *s, DeviceState *D, uint32_t max_co
     const uint32_t out_cap = max_count + 8 + 1;                 // index 0 unused, up to 7 photons of overshoot
     if ((st = D->t_out[0].ensure((size_t)batch * 8 * 9 * 4))) return st;
     if ((st = D->t_out[1].ensure((size_t)batch * 4))) return st;
-    if ((st = D->t_out[2].ensure(2 * sizeof(CompactStateHost)))) return st;
+    if ((st = D->t_out[2].ensure(2 * sizeof(CompactState)))) return st;
     const size_t sbytes = rtk_photon_compact_scratch(batch);
     if ((st = D->t_out[3].ensure(sbytes))) return st;
     if ((st = D->raw_photons.ensure((size_t)out_cap * sizeof(rt_photon)))) return st;
     hipStream_t stream = D->stream;
-    HIP_TRY(hipMemsetAsync(D->t_out[2].p, 0, 2 * sizeof(CompactStateHost), stream));
+    HIP_TRY(hipMemsetAsync(D->t_out[2].p, 0, 2 * sizeof(CompactState), stream));
     HIP_TRY(hipMemsetAsync(D->raw_photons.p, 0, sizeof(rt_photon), stream));
-    CompactStateHost h{0, 0, 0, 0};
+    CompactState h{0, 0, 0, 0};
     int empty_batches = 0;
     while (h.counted < max_count) {
-        rtk_launch_photon_trace(stream, D->scene, h.attempts, batch, seed, photon_bounce, (float *)D->t_out[0].p, (uint32_t *)D->t_out[1].p, mode);
-        rtk_photon_compact(stream, (const float *)D->t_out[0].p, (const uint32_t *)D->t_out[1].p, batch, mode, max_count, D->t_out[2].p,
+        PhotonArgs pa = {};
+        pa.first_attempt = h.attempts; pa.n_attempts = batch; pa.seed = seed; pa.max_bounce = photon_bounce; pa.mode = mode;
+        pa.out = (float *)D->t_out[0].p; pa.count = (uint32_t *)D->t_out[1].p;
+        rtk_launch_photon_trace(stream, D->scene, pa);
+        rtk_photon_compact(stream, pa.out, pa.count, batch, mode, max_count, (CompactState *)D->t_out[2].p,
                            (rt_photon *)D->raw_photons.p, out_cap, D->t_out[3].p, sbytes);
         HIP_TRY(hipGetLastError());
         const unsigned long long before = h.counted;

@@ -28,7 +28,7 @@
 
 #define RT_MAX_DEPTH      8      // scene-graph nesting supported on the device
 #define RT_MAX_OBJECTS    4096
-#define RT_BVH_STACK      32     // per-lane traversal stack entries (LDS) of the per-level kernels; k_wavefront keeps 24 (rt_kernels.hip)
+#define RT_BVH_STACK      32     // per-lane traversal stack entries (LDS) of the per-level kernels; k_wavefront keeps RT_BVH_LDS and spills behind them (below)
 #define RT_BLOCK          256    // threads per workgroup of the trace/shade kernels
 #ifndef RT_SUB_PHOTONS
 #define RT_SUB_PHOTONS    16     // photon slots per sub-leaf (16 or 32): a wavefront examines 64 / RT_SUB_PHOTONS sub-leaves per step
@@ -93,6 +93,8 @@ static_assert(sizeof(DevBvhNode) == 128, "one visit = one 128-byte record");
 #define RT_BVH_SPILL 32
 #endif
 #define RT_SPILL_BLOCKS 1280     // workgroups the spill buffer is sized for (every tracing launch stays within it)
+#define RT_TRACE_BLOCKS (256 * 5)    // grid cap of the tracing launches of a render (k_primary, k_bounce, k_features): 256 CUs x 5 workgroups
+static_assert(RT_TRACE_BLOCKS <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
 
 struct DevTri { float A[3], B[3], C[3], N[3]; };   // 48 bytes
 

@@ -21,8 +21,10 @@
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
+#include <assert.h>
 #include <algorithm>
-#include "rt_dev.h"
+#include <type_traits>
+#include "rt_launch.h"
 
 #define BIGFLOAT 1.0e30f
 #define LEAF_BIT 0x80000000u
@@ -1733,14 +1735,7 @@ struct Philox {
     }
 };
 
-struct PhotonArgs {
-    unsigned long long first_attempt; uint32_t n_attempts;
-    uint32_t seed; int max_bounce;
-    float *out;            // [n_attempts][RT_PHOTON_SLOTS][9]: pos, dir, power
-    uint32_t *count;       // [n_attempts]: photons stored | diffuse hits counted << 16
-    int mode;              // 0: photon map (PhotonTracing), 1: caustic map (CausticTracing)
-};
-
+// (PhotonArgs: rt_launch.h)
 
 // MtlBlinn::RandomPhotonBounce, FIN/include/materials.h:99-256 (all branches, incl. the glossy ones)
 __device__ bool random_photon_bounce(const rt_blinn &m, const Hit &h, V3 &rp, V3 &rd, V3 &c, Philox &rng)
@@ -1898,11 +1893,9 @@ __global__ __launch_bounds__(RT_BLOCK) void k_photon_trace(DevScene S, PhotonArg
     A.count[i] = stored | (hits << 16);
 }
 
-void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, unsigned long long first_attempt, uint32_t n_attempts,
-                             uint32_t seed, int max_bounce, float *out, uint32_t *count, int mode)
+void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs &A)
 {
-    PhotonArgs A; A.first_attempt = first_attempt; A.n_attempts = n_attempts; A.seed = seed; A.max_bounce = max_bounce; A.out = out; A.count = count; A.mode = mode;
-    hipLaunchKernelGGL(k_photon_trace, dim3((n_attempts + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, S, A);
+    hipLaunchKernelGGL(k_photon_trace, dim3((A.n_attempts + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, S, A);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2653,24 +2646,7 @@ __global__ __launch_bounds__(64 * RT_GATHER_WAVES) void k_gather(GatherArgs G)
 //   phase 0: after the first batch (samples 0..min-1): either finalise or list the pixel
 //   phase 1: after the second batch: finalise listed pixels with all samples
 // ------------------------------------------------------------------------------------------------
-struct ResolveArgs {
-    DevCamera cam; DevTiles tiles;
-    uint32_t q0, npix;
-    int min_sample, max_sample;
-    float threshold; float inv_gamma;
-    int phase;
-    float bg[3];
-    DevScene S;                 // for the background map
-    uint8_t *rgb8; float *z; uint8_t *count;
-    // packed output (multi-GPU tile exchange): pixel q of this call's tile walk (tile-major, row-major inside
-    // the tile) is ONE 8-byte record {r, g, b, z as 4 little-endian bytes, count} at packed + 8*q -- the very
-    // buffer a rank contributes to the all-gather, written here coalesced instead of being re-packed afterwards
-    uint2 *packed;
-    int direct_mode;            // rt_shade_rays: no image, leave samples as they are
-    // linear plane (k_resolve<true> only): the pre-gamma float RGB of the pixel, row-major like rgb8; in packed mode the
-    // record grows to 24 bytes instead -- {the 8-byte record, linear r, g, b as f32, 4 zero bytes} at packed + 24*q
-    float *rgb_linear;
-};
+// (ResolveArgs: rt_launch.h)
 
 __device__ __forceinline__ uint8_t float_to_byte(float r)
 {
@@ -2938,202 +2914,174 @@ __attribute__((amdgpu_waves_per_eu(TEX ? 3 : 4, TEX ? 3 : 4))) __global__ __laun
 // ------------------------------------------------------------------------------------------------
 static inline int grid_for(unsigned long long work, int block, int max_blocks)
 {
-    unsigned long long b = (work + block - 1) / block;
-    if (b < 1) b = 1;
-    if (b > (unsigned long long)max_blocks) b = max_blocks;
-    return (int)b;
+    const unsigned long long b = (work + block - 1) / block;
+    return (int)std::min<unsigned long long>(std::max<unsigned long long>(b, 1), (unsigned long long)max_blocks);
 }
 
-static SlotMap make_slotmap(const DevCamera &cam, const DevTiles &tiles_prepared, uint32_t q0, int max_sample, int mode)
-{
-    SlotMap m; m.tiles = tiles_prepared; m.width = cam.width; m.height = cam.height; m.q0 = q0; m.max_sample = max_sample; m.mode = mode;
-    m.div_ms = fastdiv_make((uint32_t)(max_sample > 0 ? max_sample : 1));
-    return m;
-}
-// k_wavefront serves the FIN, P13 and P12 models when every mesh's BVH fits its traversal stack (RT_BVH_LDS entries per lane in LDS
-// + RT_BVH_SPILL per thread in HBM; the host refuses meshes beyond that);
-// RT_TRACER=levels forces the per-level structure (A/B)
-// test hook: RT_WF_LDS_RAYS=n makes k_wavefront's workgroup rounds use only n entries of their LDS ray stack, so that a small frame
-// already sends rays through the global queue, the second pass and the per-level launches
-static uint32_t wf_lds_rays()
+// Environment hooks of the launch layer.  The first three are read once per process, RT_WF_LDS_RAYS on every launch.
+//   RT_TRACER=levels       the per-level kernels instead of k_wavefront (A/B)
+//   RT_P12_TRACER=levels   the same for the P12 model alone
+//   RT_WF_QUEUE_PASS=0     no second k_wavefront pass over the overflow queue: straight to the per-level launches
+//   RT_WF_LDS_RAYS=n       test hook: k_wavefront's workgroup rounds use only n entries of their LDS ray stack, so that a small
+//                          frame already sends rays through the global queue, the second pass and the per-level launches
+static bool env_is(const char *name, const char *value) { const char *e = getenv(name); return e && !strcmp(e, value); }
+static bool env_wavefront() { static const bool on = !env_is("RT_TRACER", "levels"); return on; }
+static bool env_p12_wavefront() { static const bool on = !env_is("RT_P12_TRACER", "levels"); return on; }
+static bool env_queue_pass() { static const bool on = !(getenv("RT_WF_QUEUE_PASS") && getenv("RT_WF_QUEUE_PASS")[0] == '0'); return on; }
+static uint32_t env_lds_rays()
 {
     const char *e = getenv("RT_WF_LDS_RAYS");
     const long v = e ? atol(e) : 0;
     return v > 0 ? (uint32_t)v : 0u;
 }
-static bool wavefront_usable(const DevScene &S, const rt_params &P, bool tex)
-{
-    static int wavefront = -1;
-    if (wavefront < 0) { const char *e = getenv("RT_TRACER"); wavefront = (e && !strcmp(e, "levels")) ? 0 : 1; }
-    // P12 (live GI): a hit spawns its hemisphere rays next to the reflection / refraction pair -- one per hit below the first
-    // level, hemisphere_sample on it; with up to two of them the LDS stacks hold the tree like FIN's (what does not fit
-    // takes the global queue as always).  RT_P12_TRACER=levels: the per-level kernels (A/B)
-    static int p12 = -1;
-    if (p12 < 0) { const char *e = getenv("RT_P12_TRACER"); p12 = (e && !strcmp(e, "levels")) ? 0 : 1; }
-    const bool model_ok = P.shade_model == RT_SHADE_FIN || P.shade_model == RT_SHADE_P13 || (P.shade_model == RT_SHADE_P12 && p12 && P.hemisphere_sample <= 2);
-    if (!wavefront || !model_ok) return false;
-    // (the traversal stack: the kernel's LDS part plus, when the scene has the spill buffer, RT_BVH_SPILL entries per thread behind it)
-    return S.max_bvh_depth <= (tex ? WfCfg<true>::BVH : WfCfg<false>::BVH) + (S.max_bvh_depth > RT_BVH_LDS ? RT_BVH_SPILL : 0);
-}
 
+// whether the scene samples textures: selects the TEX instantiations
+static bool scene_textured(const DevScene &S) { return S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE; }
+
+// k_wavefront serves the FIN, P13 and P12 models when every mesh's BVH fits its traversal stack (RT_BVH_LDS entries per lane in LDS
+// + RT_BVH_SPILL per thread in HBM; the host refuses meshes beyond that)
 bool rtk_wavefront_usable(const DevScene &S, const rt_params &P)
 {
-    return wavefront_usable(S, P, S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE);
+    const bool wavefront = env_wavefront(), p12 = env_p12_wavefront();     // both read on the first call, whatever its model
+    // P12 (live GI): a hit spawns its hemisphere rays next to the reflection / refraction pair -- one per hit below the first
+    // level, hemisphere_sample on it; with up to two of them the LDS stacks hold the tree like FIN's (what does not fit
+    // takes the global queue as always)
+    const bool model_ok = P.shade_model == RT_SHADE_FIN || P.shade_model == RT_SHADE_P13 ||
+                          (P.shade_model == RT_SHADE_P12 && p12 && P.hemisphere_sample <= 2);
+    if (!wavefront || !model_ok) return false;
+    // (the traversal stack: the kernel's LDS part plus, when the scene has the spill buffer, RT_BVH_SPILL entries per thread behind it)
+    return S.max_bvh_depth <= (scene_textured(S) ? WfCfg<true>::BVH : WfCfg<false>::BVH) + (S.max_bvh_depth > RT_BVH_LDS ? RT_BVH_SPILL : 0);
+}
+// a full persistent grid of k_wavefront: its resident workgroups per CU (LDS) on 256 CUs
+static int wavefront_blocks(const DevScene &S) { return 256 * (scene_textured(S) ? RT_WF_TEX_WAVES : RT_WF_WAVES); }
+
+// The context of a launch in its neutral state: no output queue, no LDS ray stack, no slot map, no secondary plane.
+static ShadeCtx make_ctx(const DevScene &S, const DevWork &W, const rt_params &P)
+{
+    ShadeCtx C = {};
+    C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P;
+    return C;
+}
+// ... writing the rays it spawns to the queue of tree level `level` (rt_launch.h)
+static ShadeCtx make_ctx(const DevScene &S, const DevWork &W, const rt_params &P, int level, unsigned long long *fx)
+{
+    ShadeCtx C = make_ctx(S, W, P);
+    C.qout = W.rq[level & 1]; C.qout_count = W.counts + level; C.fx = fx;
+    return C;
+}
+static SlotMap make_slotmap(const RenderPass &pass, const DevTiles &tiles_prepared)
+{
+    SlotMap m; m.tiles = tiles_prepared; m.width = pass.cam.width; m.height = pass.cam.height; m.q0 = pass.q0; m.max_sample = pass.max_sample; m.mode = pass.mode;
+    m.div_ms = fastdiv_make((uint32_t)(pass.max_sample > 0 ? pass.max_sample : 1));
+    return m;
 }
 
-// the instantiation of k_wavefront for (model, textures, reproducible mode)
-template <int MODEL>
-static void launch_wavefront_model(hipStream_t st, bool tex, bool fx, int wgrid, const ShadeCtx &C, const PrimaryArgs &A)
+// The one place where the run-time triple (shade model, textures, reproducible mode) becomes template arguments:
+// launch(model, tex, fx) is called with three std::integral_constant values.  A kernel template names the models it exists
+// for -- FALLBACK serves every model outside the list -- and whether it has reproducible (FX) instantiations at all, so that
+// nothing is instantiated that no launch can select.
+template <int M> using Model = std::integral_constant<int, M>;
+template <bool HAS_FX, int M, class F>
+static void dispatch_flags(bool tex, bool fx, F &launch)
 {
-    if (fx) {
-        if (tex) hipLaunchKernelGGL((k_wavefront<MODEL, true, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        else hipLaunchKernelGGL((k_wavefront<MODEL, false, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-    } else {
-        if (tex) hipLaunchKernelGGL((k_wavefront<MODEL, true>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
-        else hipLaunchKernelGGL((k_wavefront<MODEL, false>), dim3(wgrid), dim3(RT_BLOCK), 0, st, C, A);
+    if constexpr (HAS_FX) {
+        if (fx) { if (tex) launch(Model<M>{}, std::true_type{}, std::true_type{}); else launch(Model<M>{}, std::false_type{}, std::true_type{}); return; }
     }
+    if (tex) launch(Model<M>{}, std::true_type{}, std::false_type{}); else launch(Model<M>{}, std::false_type{}, std::false_type{});
 }
-static void launch_wavefront(hipStream_t st, int model, bool tex, bool fx, int wgrid, const ShadeCtx &C, const PrimaryArgs &A)
+template <bool HAS_FX, int FALLBACK, int... MODELS, class F>
+static void dispatch(int model, bool tex, bool fx, F &&launch)
 {
-    if (model == RT_SHADE_FIN) launch_wavefront_model<RT_SHADE_FIN>(st, tex, fx, wgrid, C, A);
-    else if (model == RT_SHADE_P12) launch_wavefront_model<RT_SHADE_P12>(st, tex, fx, wgrid, C, A);
-    else launch_wavefront_model<RT_SHADE_P13>(st, tex, fx, wgrid, C, A);
+    // the first listed model that matches launches; `found` says whether one did
+    const bool found = ((model == MODELS ? (dispatch_flags<HAS_FX, MODELS>(tex, fx, launch), true) : false) || ...);
+    if (!found) dispatch_flags<HAS_FX, FALLBACK>(tex, fx, launch);
+}
+// k_wavefront exists for FIN, P13 and P12; anything that is neither FIN nor P12 takes P13
+static void launch_wavefront(hipStream_t st, int grid, const ShadeCtx &C, const PrimaryArgs &A)
+{
+    dispatch<true, RT_SHADE_P13, RT_SHADE_FIN, RT_SHADE_P12>(C.P.shade_model, scene_textured(C.S), C.fx != nullptr, [&](auto m, auto tex, auto fx) {
+        hipLaunchKernelGGL((k_wavefront<m(), tex(), fx()>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A);
+    });
 }
 
-void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
-                        const DevRayQueue &qout, uint32_t *qout_count, const DevCamera &cam,
-                        const DevTiles &tiles, uint32_t q0, uint32_t npix, int j0, int ns,
-                        int max_sample, int mode, const float *rays, int max_blocks, unsigned long long *fx)
+void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass, int max_blocks)
 {
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
-    PrimaryArgs A; A.cam = cam; A.tiles = tiles; A.q0 = q0; A.npix = npix; A.j0 = j0; A.ns = ns;
-    A.max_sample = max_sample; A.mode = mode; A.rays = rays; A.lds_rays = wf_lds_rays();
+    ShadeCtx C = make_ctx(S, W, P, 1, pass.fx);
+    PrimaryArgs A; A.cam = pass.cam; A.tiles = pass.tiles; A.q0 = pass.q0; A.npix = pass.npix; A.j0 = pass.j0; A.ns = pass.ns;
+    A.max_sample = pass.max_sample; A.mode = pass.mode; A.rays = pass.rays; A.lds_rays = env_lds_rays();
     tiles_prepare(A.tiles);
-    A.div_ns = fastdiv_make((uint32_t)(ns > 0 ? ns : 1));
-    const int grid = grid_for((unsigned long long)npix * ns, RT_BLOCK, max_blocks);
-    const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
-    C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
-    C.sm = make_slotmap(cam, A.tiles, q0, max_sample, mode);
-    // default: the whole ray tree in one persistent launch with LDS ray stacks (FIN / P13 models); RT_TRACER=levels: one
+    A.div_ns = fastdiv_make((uint32_t)(pass.ns > 0 ? pass.ns : 1));
+    C.sm = make_slotmap(pass, A.tiles);
+    const unsigned long long samples = (unsigned long long)pass.npix * pass.ns;
+    // default: the whole ray tree in one persistent launch with LDS ray stacks (FIN / P13 / P12 models); RT_TRACER=levels: one
     // launch per level of the tree (round 1's structure, kept for the other models and for A/B: DESIGN.md section 3)
-    if (wavefront_usable(S, P, tex)) {
-        const int wgrid = grid_for((unsigned long long)npix * ns, RT_BLOCK, 256 * (tex ? RT_WF_TEX_WAVES : RT_WF_WAVES));      // resident workgroups per CU (LDS)
-        launch_wavefront(st, P.shade_model, tex, fx != nullptr, wgrid, C, A);
-        return;
-    }
-#define RT_LAUNCH_PRIMARY(M) do { if (fx) { if (tex) hipLaunchKernelGGL((k_primary<M, true, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); \
-                                            else hipLaunchKernelGGL((k_primary<M, false, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); } \
-                                  else if (tex) hipLaunchKernelGGL((k_primary<M, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); \
-                                  else hipLaunchKernelGGL((k_primary<M, false>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A); } while (0)
-    switch (P.shade_model) {
-    case RT_SHADE_P13: RT_LAUNCH_PRIMARY(RT_SHADE_P13); break;
-    case RT_SHADE_P12: RT_LAUNCH_PRIMARY(RT_SHADE_P12); break;
-    case RT_SHADE_P6: RT_LAUNCH_PRIMARY(RT_SHADE_P6); break;
-    case RT_SHADE_P3: RT_LAUNCH_PRIMARY(RT_SHADE_P3); break;
-    default: RT_LAUNCH_PRIMARY(RT_SHADE_FIN);
-    }
-#undef RT_LAUNCH_PRIMARY
+    if (rtk_wavefront_usable(S, P)) { launch_wavefront(st, grid_for(samples, RT_BLOCK, wavefront_blocks(S)), C, A); return; }
+    const int grid = grid_for(samples, RT_BLOCK, max_blocks);
+    dispatch<true, RT_SHADE_FIN, RT_SHADE_P13, RT_SHADE_P12, RT_SHADE_P6, RT_SHADE_P3>(P.shade_model, scene_textured(S), pass.fx != nullptr, [&](auto m, auto tex, auto fx) {
+        hipLaunchKernelGGL((k_primary<m(), tex(), fx()>), dim3(grid), dim3(RT_BLOCK), 0, st, C, A);
+    });
 }
 
-// The rays a k_wavefront pass could not keep on its LDS stacks, traced by a second pass of the same kernel with the
-// queue as its source (their whole subtrees stay in LDS; what does not fit THIS time goes on to qout and the per-level
-// launches).  Returns false when the model has no wavefront kernel (the caller then starts the level launches at qin).
-bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
-                                const DevRayQueue &qin, const uint32_t *qin_count, const DevRayQueue &qout, uint32_t *qout_count,
-                                const DevCamera &cam, const DevTiles &tiles, uint32_t q0, int max_sample, int mode, unsigned long long *fx)
+bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass)
 {
-    static int queue_pass = -1;
-    if (queue_pass < 0) { const char *q = getenv("RT_WF_QUEUE_PASS"); queue_pass = (q && q[0] == '0') ? 0 : 1; }
-    const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
-    if (!queue_pass || !wavefront_usable(S, P, tex)) return false;
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
-    C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
-    DevTiles tp = tiles;
+    if (!env_queue_pass() || !rtk_wavefront_usable(S, P)) return false;
+    ShadeCtx C = make_ctx(S, W, P, 2, pass.fx);
+    DevTiles tp = pass.tiles;
     tiles_prepare(tp);
-    C.sm = make_slotmap(cam, tp, q0, max_sample, mode);
+    C.sm = make_slotmap(pass, tp);
     PrimaryArgs A;
     memset(&A, 0, sizeof A);
-    A.mode = 3; A.ns = 1; A.qsrc = qin; A.qsrc_count = qin_count; A.lds_rays = wf_lds_rays();
+    A.mode = 3; A.ns = 1; A.qsrc = W.rq[1]; A.qsrc_count = W.counts + 1; A.lds_rays = env_lds_rays();
     A.div_ns = fastdiv_make(1u);
-    const int wgrid = 256 * (tex ? RT_WF_TEX_WAVES : RT_WF_WAVES);       // the count is on the device: a full persistent grid, idle workgroups leave at once
-    launch_wavefront(st, P.shade_model, tex, fx != nullptr, wgrid, C, A);
+    launch_wavefront(st, wavefront_blocks(S), C, A);       // the count is on the device: a full persistent grid, idle workgroups leave at once
     return true;
 }
 
-void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P,
-                       const DevRayQueue &qin, const DevRayQueue &qout, uint32_t *qout_count,
-                       int level, int max_blocks, unsigned long long *fx)
+void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, int level, int max_blocks, unsigned long long *fx)
 {
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.qout = qout; C.qout_count = qout_count; C.fx = fx;
-    C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
-    memset(&C.sm, 0, sizeof C.sm);
-    const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
-#define RT_LAUNCH_BOUNCE(M) do { if (fx) { if (tex) hipLaunchKernelGGL((k_bounce<M, true, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); \
-                                           else hipLaunchKernelGGL((k_bounce<M, false, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); } \
-                                 else if (tex) hipLaunchKernelGGL((k_bounce<M, true>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); \
-                                 else hipLaunchKernelGGL((k_bounce<M, false>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level); } while (0)
-    switch (P.shade_model) {
-    case RT_SHADE_P13: RT_LAUNCH_BOUNCE(RT_SHADE_P13); break;
-    case RT_SHADE_P12: RT_LAUNCH_BOUNCE(RT_SHADE_P12); break;
-    case RT_SHADE_P6: RT_LAUNCH_BOUNCE(RT_SHADE_P6); break;
-    case RT_SHADE_P3: break;                               // P3 has no secondary rays
-    default: RT_LAUNCH_BOUNCE(RT_SHADE_FIN);
-    }
-#undef RT_LAUNCH_BOUNCE
+    if (P.shade_model == RT_SHADE_P3) return;                // P3 has no secondary rays (and no k_bounce)
+    const ShadeCtx C = make_ctx(S, W, P, level + 1, fx);
+    const DevRayQueue &qin = W.rq[level & 1];
+    dispatch<true, RT_SHADE_FIN, RT_SHADE_P13, RT_SHADE_P12, RT_SHADE_P6>(P.shade_model, scene_textured(S), fx != nullptr, [&](auto m, auto tex, auto fx_) {
+        hipLaunchKernelGGL((k_bounce<m(), tex(), fx_()>), dim3(max_blocks), dim3(RT_BLOCK), 0, st, C, qin, level);
+    });
 }
 
-void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float *rays, long long n,
-                      uint8_t *hit, float *z, float *p, float *N, int32_t *node, uint8_t *front)
+void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float *rays, long long n, const TraceOut &o)
 {
     const int grid = grid_for((unsigned long long)n, RT_BLOCK, RT_SPILL_BLOCKS);
-    if (model == RT_SHADE_P3) hipLaunchKernelGGL(k_trace<RT_SHADE_P3>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, hit, z, p, N, node, front);
-    else if (model != RT_SHADE_FIN) hipLaunchKernelGGL(k_trace<RT_SHADE_P13>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, hit, z, p, N, node, front);
-    else hipLaunchKernelGGL(k_trace<RT_SHADE_FIN>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, hit, z, p, N, node, front);
+    if (model == RT_SHADE_P3) hipLaunchKernelGGL(k_trace<RT_SHADE_P3>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
+    else if (model != RT_SHADE_FIN) hipLaunchKernelGGL(k_trace<RT_SHADE_P13>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
+    else hipLaunchKernelGGL(k_trace<RT_SHADE_FIN>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
 }
 
-void rtk_launch_gather(hipStream_t st, const DevPhotonMap &pm, const float4 *qa, const float4 *qb,
-                       const float4 *qc, const uint32_t *count_ptr, uint32_t count_cap, int k,
-                       float radius, float *sample_rgb, float *out_irr, float *out_dir, int mode,
-                       unsigned long long *stats, int blocks, uint32_t *next_batch, float *cell_rk2, unsigned long long *fx)
+void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks)
 {
-    GatherArgs G; G.pm = pm; G.cell_rk2 = cell_rk2; G.fx = fx; G.qa = qa; G.qb = qb; G.qc = qc; G.count_ptr = count_ptr; G.count_cap = count_cap;
-    G.k = k; G.radius = radius; G.sample_rgb = sample_rgb; G.out_irr = out_irr; G.out_dir = out_dir; G.mode = mode; G.stats = stats; G.next_batch = next_batch;
-    if (fx && mode == 0) hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
+    GatherArgs G; G.pm = R.pm; G.cell_rk2 = R.cell_rk2; G.fx = R.fx; G.qa = R.q.qa; G.qb = R.q.qb; G.qc = R.q.qc; G.count_ptr = R.count; G.count_cap = R.q.cap;
+    G.k = R.k; G.radius = R.radius; G.sample_rgb = R.sample_rgb; G.out_irr = R.out_irr; G.out_dir = R.out_dir; G.mode = R.out_irr ? 1 : 0;
+    G.stats = R.stats; G.next_batch = R.next_batch;
+    if (G.fx && G.mode == 0) hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
     else hipLaunchKernelGGL(k_gather<false>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
 }
 
-// The feature planes of one chunk, after its last k_resolve on the same stream: the second-batch flags from the chunk's pixel
-// list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when features are on);
-// by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by image pixel.
-// The grid stays within RT_SPILL_BLOCKS, like every launch that uses the spill part of the traversal stack.
-void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const DevCamera &cam, const DevTiles &tiles,
-                         uint32_t q0, uint32_t npix, uint8_t *second, const DevFeatures &out, bool by_walk)
+// The grid stays within RT_TRACE_BLOCKS <= RT_SPILL_BLOCKS, like every launch that uses the spill part of the traversal stack.
+void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass,
+                         uint8_t *second, const DevFeatures &out, bool by_walk)
 {
+    const uint32_t npix = pass.npix;
     if (npix == 0) return;
     (void)hipMemsetAsync(second, 0, npix, st);
     if (P.max_sample > P.min_sample) hipLaunchKernelGGL(k_mark_second, dim3(grid_for(npix, 256, 1024)), dim3(256), 0, st, W, second, npix);
-    ShadeCtx C; C.S = S; C.S.bvh_spill = W.bvh_spill; C.W = W; C.P = P; C.fx = nullptr;
-    memset(&C.qout, 0, sizeof C.qout); C.qout_count = nullptr;
-    C.lds_a = C.lds_b = C.lds_c = nullptr; C.lds_count = nullptr; C.lds_cap = 0;
-    memset(&C.sm, 0, sizeof C.sm);
-    FeatureArgs F; F.cam = cam; F.tiles = tiles; F.q0 = q0; F.npix = npix; F.min_sample = P.min_sample; F.max_sample = P.max_sample;
+    const ShadeCtx C = make_ctx(S, W, P);
+    FeatureArgs F; F.cam = pass.cam; F.tiles = pass.tiles; F.q0 = pass.q0; F.npix = npix; F.min_sample = P.min_sample; F.max_sample = P.max_sample;
     tiles_prepare(F.tiles);
     F.div_ms = fastdiv_make((uint32_t)(P.max_sample > 0 ? P.max_sample : 1));
     F.second = second; F.by_walk = by_walk ? 1 : 0;
     F.normal = out.normal; F.albedo = out.albedo; F.alpha = out.alpha; F.object_id = out.object_id;
-    static_assert(256 * 5 <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
-    const int grid = grid_for(npix, RT_BLOCK, 256 * 5);
-    const bool tex = S.material_maps != nullptr || S.env_map.texture != RT_MAP_NONE;
-#define RT_LAUNCH_FEATURES(M) do { if (tex) hipLaunchKernelGGL((k_features<M, true>), dim3(grid), dim3(RT_BLOCK), 0, st, C, F); \
-                                   else hipLaunchKernelGGL((k_features<M, false>), dim3(grid), dim3(RT_BLOCK), 0, st, C, F); } while (0)
-    switch (P.shade_model) {
-    case RT_SHADE_P13: RT_LAUNCH_FEATURES(RT_SHADE_P13); break;
-    case RT_SHADE_P12: RT_LAUNCH_FEATURES(RT_SHADE_P12); break;
-    case RT_SHADE_P6: RT_LAUNCH_FEATURES(RT_SHADE_P6); break;
-    case RT_SHADE_P3: RT_LAUNCH_FEATURES(RT_SHADE_P3); break;
-    default: RT_LAUNCH_FEATURES(RT_SHADE_FIN);
-    }
-#undef RT_LAUNCH_FEATURES
+    const int grid = grid_for(npix, RT_BLOCK, RT_TRACE_BLOCKS);
+    dispatch<false, RT_SHADE_FIN, RT_SHADE_P13, RT_SHADE_P12, RT_SHADE_P6, RT_SHADE_P3>(P.shade_model, scene_textured(S), false, [&](auto m, auto tex, auto) {
+        hipLaunchKernelGGL((k_features<m(), tex()>), dim3(grid), dim3(RT_BLOCK), 0, st, C, F);
+    });
 }
 
 // Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
@@ -3182,32 +3130,25 @@ __global__ __launch_bounds__(256) void k_unpack_tiles(const uint2 *gathered, int
     }
 }
 
-void rtk_launch_unpack_tiles(hipStream_t st, const void *gathered, int world, int per_rank, int width, int height, int tile_w, int tile_h,
-                             uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear)
+void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R)
 {
-    const int tiles_x = (width + tile_w - 1) / tile_w;
-    const size_t n = (size_t)width * height;
+    const int tiles_x = (R.width + R.tile_w - 1) / R.tile_w;
+    const size_t n = (size_t)R.width * R.height;
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-    if (rgb_linear)
-        hipLaunchKernelGGL(k_unpack_tiles<true>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)gathered, world, per_rank, width,
-                           height, tile_w, tile_h, tiles_x, rgb8, z, count, rgb_linear);
+    if (R.rgb_linear)
+        hipLaunchKernelGGL(k_unpack_tiles<true>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)R.gathered, R.world, R.per_rank, R.width,
+                           R.height, R.tile_w, R.tile_h, tiles_x, R.rgb8, R.z, R.count, R.rgb_linear);
     else
-        hipLaunchKernelGGL(k_unpack_tiles<false>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)gathered, world, per_rank, width,
-                           height, tile_w, tile_h, tiles_x, rgb8, z, count, nullptr);
+        hipLaunchKernelGGL(k_unpack_tiles<false>, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (const uint2 *)R.gathered, R.world, R.per_rank, R.width,
+                           R.height, R.tile_w, R.tile_h, tiles_x, R.rgb8, R.z, R.count, nullptr);
 }
 
-// linear: the LIN instantiation of k_resolve -- the linear plane rgb_linear, or 24-byte records when `packed` is set
-void rtk_launch_resolve(hipStream_t st, const DevScene &S, const DevWork &W, const DevCamera &cam, const DevTiles &tiles,
-                        uint32_t q0, uint32_t npix, int min_sample, int max_sample, float threshold,
-                        float inv_gamma, int phase, const float bg[3], uint8_t *rgb8, float *z,
-                        uint8_t *count, void *packed, int max_blocks, bool linear, float *rgb_linear)
+void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &R, int max_blocks, bool linear)
 {
-    ResolveArgs A; A.cam = cam; A.tiles = tiles; A.q0 = q0; A.npix = npix; A.min_sample = min_sample;
-    A.max_sample = max_sample; A.threshold = threshold; A.inv_gamma = inv_gamma; A.phase = phase;
-    A.bg[0] = bg[0]; A.bg[1] = bg[1]; A.bg[2] = bg[2]; A.rgb8 = rgb8; A.z = z; A.count = count; A.packed = (uint2 *)packed; A.direct_mode = 0; A.S = S;
-    A.rgb_linear = rgb_linear;
+    assert(!linear || R.rgb_linear || R.packed);     // the LIN instantiation writes the linear plane, or 24-byte records into `packed`
+    ResolveArgs A = R;
     tiles_prepare(A.tiles);
-    const int grid = grid_for(npix, 256, max_blocks);
+    const int grid = grid_for(A.npix, 256, max_blocks);
     if (linear) hipLaunchKernelGGL(k_resolve<true>, dim3(grid), dim3(256), 0, st, W, A);
     else hipLaunchKernelGGL(k_resolve<false>, dim3(grid), dim3(256), 0, st, W, A);
 }

@@ -1,0 +1,146 @@
+// rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip,
+// rt_photon_build.hip): every rtk_* function, the requests they take and the records they exchange.  All three files
+// include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
+// as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
+#ifndef RT_LAUNCH_H
+#define RT_LAUNCH_H
+
+#include <hip/hip_runtime.h>
+#include "rt_dev.h"
+
+// ---- requests ---------------------------------------------------------------------------------------------------------
+// One tracing pass over a chunk's samples (run_pipeline in rt_api.cpp; k_wavefront / k_primary and what follows them):
+//   mode 0: pixels q0..q0+npix of the call's tile walk, samples j0..j0+ns of each
+//   mode 1: the pixels of the working set's pixel list, samples j0..j0+ns   (second batch)
+//   mode 2: rays[] supplied by the caller, one sample each, q0 = index of the first   (rt_shade_rays)
+struct RenderPass {
+    DevCamera cam; DevTiles tiles;      // tiles as the call has them: the wrappers run tiles_prepare on their copy
+    uint32_t q0, npix;
+    int j0, ns, max_sample, mode;
+    const float *rays;                  // mode 2, else NULL
+    unsigned long long *fx;             // the secondary plane of a reproducible render (RT_RENDER_REPRODUCIBLE); NULL selects the default instantiations
+};
+
+// One k_gather launch: the queries of `q` (their number on the device in *count, at most q.cap are answered) against `pm`.
+struct GatherRequest {
+    DevPhotonMap pm;
+    DevPhotonQueue q; const uint32_t *count;
+    int k; float radius;
+    uint32_t *next_batch;               // the launch's RT_GATHER_CTRS work counters, RT_CTR_STRIDE apart, zero at launch
+    float *cell_rk2;                    // per density-grid cell: the k-th squared distance of the last query answered there; may be NULL
+    // either the outputs of a render: w * irr * max(0, N.(-dir)) added into the query's sample slot (into fx instead, when set) ...
+    float *sample_rgb; unsigned long long *stats, *fx;
+    // ... or, when out_irr is set, irr[3] and dir[3] per query (rt_estimate_irradiance)
+    float *out_irr, *out_dir;
+};
+
+// K6, the tail of RenderPixel per pixel of a chunk:
+//   phase 0: after the first batch (samples 0..min-1): either finalise or list the pixel
+//   phase 1: after the second batch: finalise listed pixels with all samples
+struct ResolveArgs {
+    DevCamera cam; DevTiles tiles;
+    uint32_t q0, npix;
+    int min_sample, max_sample;
+    float threshold; float inv_gamma;
+    int phase;
+    float bg[3];
+    DevScene S;                 // for the background map
+    uint8_t *rgb8; float *z; uint8_t *count;
+    // packed output (multi-GPU tile exchange): pixel q of this call's tile walk (tile-major, row-major inside
+    // the tile) is ONE 8-byte record {r, g, b, z as 4 little-endian bytes, count} at packed + 8*q -- the very
+    // buffer a rank contributes to the all-gather, written here coalesced instead of being re-packed afterwards
+    uint2 *packed;
+    int direct_mode;            // rt_shade_rays: no image, leave samples as they are
+    // linear plane (k_resolve<true> only): the pre-gamma float RGB of the pixel, row-major like rgb8; in packed mode the
+    // record grows to 24 bytes instead -- {the 8-byte record, linear r, g, b as f32, 4 zero bytes} at packed + 24*q
+    float *rgb_linear;
+};
+
+// the photon pass: attempts first_attempt .. first_attempt + n_attempts of the counter RNG's sequence
+struct PhotonArgs {
+    unsigned long long first_attempt; uint32_t n_attempts;
+    uint32_t seed; int max_bounce;
+    float *out;            // [n_attempts][RT_PHOTON_SLOTS][9]: pos, dir, power
+    uint32_t *count;       // [n_attempts]: photons stored | diffuse hits counted << 16
+    int mode;              // 0: photon map (PhotonTracing), 1: caustic map (CausticTracing)
+};
+
+// what k_trace writes per ray (rt_trace_rays)
+struct TraceOut { uint8_t *hit; float *z, *p, *N; int32_t *node; uint8_t *front; };
+
+// an all-gathered frame to un-interleave: rank r of `world` contributed its tiles r, r+world, ... as per_rank packed tiles
+// (8-byte records, 24-byte ones when rgb_linear is set) -> the planes of a width x height image
+struct UnpackRequest {
+    const void *gathered; int world, per_rank, width, height, tile_w, tile_h;
+    uint8_t *rgb8; float *z; uint8_t *count; float *rgb_linear;
+};
+
+// ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
+// The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
+// that one and appends the rays it spawns to level l + 1.
+
+// whether k_wavefront (the whole ray tree in one persistent launch) serves this scene and model; else the per-level kernels do
+bool rtk_wavefront_usable(const DevScene &S, const rt_params &P);
+// The primary samples of a pass, shaded: k_wavefront where usable (whole subtrees on LDS stacks; what does not fit goes to the
+// level-1 queue), else k_primary with every secondary ray on the level-1 queue.  Grid of at most max_blocks workgroups.
+void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass, int max_blocks);
+// The rays a k_wavefront pass could not keep on its LDS stacks (level 1), traced by a second pass of the same kernel with the
+// queue as its source; what does not fit THIS time goes on to level 2 and the per-level launches.  Returns false, having done
+// nothing, when the model has no wavefront kernel (the caller then starts the level launches at level 1).
+bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass);
+// one level of the ray tree: k_bounce over the queue of `level` (P3 has no secondary rays: no launch)
+void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, int level, int max_blocks, unsigned long long *fx);
+// closest hits of n caller-supplied rays (6 floats each) with the intersection code of `model`
+void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float *rays, long long n, const TraceOut &out);
+// k_gather as a persistent grid of `blocks` workgroups
+void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks);
+// Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
+void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *fx, size_t samples);
+// k_resolve over A.npix pixels, at most max_blocks workgroups (tiles_prepare is run on a copy of A.tiles).  linear: the LIN
+// instantiation -- the linear plane A.rgb_linear, or 24-byte records when A.packed is set.
+void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &A, int max_blocks, bool linear);
+void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R);
+// The feature planes of one chunk (pass.cam, tiles, q0, npix), after its last k_resolve on the same stream: the second-batch
+// flags from the chunk's pixel list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when
+// features are on); by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by
+// image pixel.
+void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass,
+                         uint8_t *second, const DevFeatures &out, bool by_walk);
+// k_photon_trace, one thread per attempt
+void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs &A);
+
+// ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
+// progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored
+struct CompactState { unsigned long long attempts, counted; uint32_t stored, pad; };
+// origin, cell size and dimensions of the density grid a structure build chose
+struct PhotonGridOut { float min[3]; float cell; int dim[3]; };
+
+// scratch = 4 arrays of n_attempts uint32 + the scan's temporary storage
+size_t rtk_photon_compact_scratch(uint32_t n_attempts);
+// Consumes the attempts of one k_photon_trace batch in order, until max_count is reached (mode 0: photons stored, mode 1:
+// diffuse hits counted), and appends their photons to out (1-based, out_cap entries); state_dev carries on from batch to batch.
+void rtk_photon_compact(hipStream_t st, const float *recs, const uint32_t *count, uint32_t n_attempts, int mode, unsigned long long max_count,
+                        CompactState *state_dev, rt_photon *out, uint32_t out_cap, void *scratch, size_t scratch_bytes);
+// ScalePhotonPowers over photons [1, n]
+void rtk_photon_scale(hipStream_t st, rt_photon *ph, uint32_t n, float scale);
+// out = in without the (at most 8, ascending, 0-based) positions of `skip`: the photons LocatePhotons can reach
+void rtk_photon_copy_skipping(hipStream_t st, const rt_photon *in, uint32_t n_in, const uint32_t *skip, uint32_t n_skip, rt_photon *out);
+// Scratch of a build over n photons with n_sub sub-leaves: perm x2, keys x2, boxu, sort temp.
+size_t rtk_photon_structure_scratch(uint32_t n, uint32_t n_sub);
+// Builds pa / pb ((n_sub + 1) * RT_SUB_PHOTONS slots each), box4 (2 * 2 * n_sub float4: heap node i at [2i, 2i+1]; the
+// tree over the leaves is its head, the sub-leaf boxes the nodes [n_sub, 2 n_sub)) and the density grid (64^3 counters
+// provided; dims / origin / cell come back in grid_out after a stream synchronisation inside this call).
+hipError_t rtk_photon_structure(hipStream_t st, const rt_photon *ph, uint32_t n, uint32_t n_sub, float4 *pa, float4 *pb, float4 *box4,
+                                uint32_t *grid, PhotonGridOut *grid_out, void *scratch, size_t scratch_bytes);
+size_t rtk_photon_unreachable_scratch(uint32_t n);
+// ph0: the photons as generated, 1-based ([0] all zero), on the device.  Heap slots [first, last] are wanted.  result (host):
+// [0] = number of photons found, [1] = 1 when a median's key was not unique (the caller must use the host's exact replay),
+// [2..] = their 1-based raw indices (unsorted).  Returns after the stream has been synchronised.
+hipError_t rtk_photon_unreachable(hipStream_t st, const rt_photon *ph0, uint32_t n, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes,
+                                  uint32_t result[16]);
+// (position, raw index) records of photons [0, n], 16 bytes each: what the host's replay of BalanceSegment works on
+void rtk_photon_pack_positions(hipStream_t st, const rt_photon *ph0, uint32_t n, void *recs16);
+// DevPhotonMap::cell_start for `radius`: one entry per cell of the dim[0] x dim[1] x dim[2] density grid
+void rtk_photon_cell_start(hipStream_t st, const float4 *tbox, uint32_t n_leaves, const float grid_min[3], float cell, const int dim[3], float radius, uint32_t *start);
+
+#endif

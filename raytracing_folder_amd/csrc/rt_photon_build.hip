@@ -20,13 +20,11 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "rt_dev.h"
+#include "rt_launch.h"
 
 #define PB_BLOCK 256
 
-// ---- photon_compact ---------------------------------------------------------------------------------------------
-struct CompactState { unsigned long long attempts, counted; uint32_t stored, pad; };
-
+// ---- photon_compact (CompactState: rt_launch.h) -------------------------------------------------------------------
 __global__ __launch_bounds__(PB_BLOCK) void k_split_counts(const uint32_t *count, uint32_t n, int mode, uint32_t *stored, uint32_t *counted)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -96,7 +94,7 @@ size_t rtk_photon_compact_scratch(uint32_t n_attempts)
     return (size_t)n_attempts * 16 + ((tmp + 255) & ~(size_t)255) + 256;
 }
 void rtk_photon_compact(hipStream_t st, const float *recs, const uint32_t *count, uint32_t n_attempts, int mode, unsigned long long max_count,
-                        void *state_dev, rt_photon *out, uint32_t out_cap, void *scratch, size_t scratch_bytes)
+                        CompactState *state_dev, rt_photon *out, uint32_t out_cap, void *scratch, size_t scratch_bytes)
 {
     uint32_t *stored = (uint32_t *)scratch, *counted = stored + n_attempts, *ex_s = counted + n_attempts, *ex_c = ex_s + n_attempts;
     void *tmp = (char *)scratch + (size_t)n_attempts * 16;
@@ -105,9 +103,8 @@ void rtk_photon_compact(hipStream_t st, const float *recs, const uint32_t *count
     hipLaunchKernelGGL(k_split_counts, dim3(grid), dim3(PB_BLOCK), 0, st, count, n_attempts, mode, stored, counted);
     (void)hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, stored, ex_s, (int)n_attempts, st);
     (void)hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, counted, ex_c, (int)n_attempts, st);
-    CompactState *S = (CompactState *)state_dev;
-    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(PB_BLOCK), 0, st, recs, stored, counted, ex_s, ex_c, n_attempts, max_count, S, out, out_cap);
-    hipLaunchKernelGGL(k_commit_state, dim3(1), dim3(1), 0, st, S);
+    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(PB_BLOCK), 0, st, recs, stored, counted, ex_s, ex_c, n_attempts, max_count, state_dev, out, out_cap);
+    hipLaunchKernelGGL(k_commit_state, dim3(1), dim3(1), 0, st, state_dev);
 }
 void rtk_photon_scale(hipStream_t st, rt_photon *ph, uint32_t n, float scale)
 {
@@ -586,7 +583,6 @@ size_t rtk_photon_structure_scratch(uint32_t n, uint32_t n_sub)
 // Builds pa / pb ((n_sub + 1) * RT_SUB_PHOTONS slots each), box4 (2 * 2 * n_sub float4: heap node i at [2i, 2i+1]; the
 // tree over the leaves is its head, the sub-leaf boxes the nodes [n_sub, 2 n_sub)) and the density grid (64^3 counters
 // provided; dims / origin / cell come back in grid_out after a stream synchronisation inside this call).
-struct PhotonGridOut { float min[3]; float cell; int dim[3]; };
 hipError_t rtk_photon_structure(hipStream_t st, const rt_photon *ph, uint32_t n, uint32_t n_sub, float4 *pa, float4 *pb, float4 *box4,
                                 uint32_t *grid, PhotonGridOut *grid_out, void *scratch, size_t scratch_bytes)
 {
