@@ -1,5 +1,5 @@
 // rt_dev.h -- device-side data layout of a lowered scene, shared by rt_api.cpp (which builds
-// and uploads it) and rt_kernels.hip (which reads it).  gfx950 only.
+// and uploads it) and the kernels in rt_kernels.hip / rt_gather.hip (which read it).  gfx950 only.
 //
 // HBM layout (all arrays are plain hipMalloc allocations owned by the rt_scene):
 //   nodes      DevNodeXf[n_nodes]      96 B each: itm(9) pos(3) tm(9) -- read with scalar loads

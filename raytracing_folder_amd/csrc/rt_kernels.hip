@@ -6,7 +6,7 @@
 //   k_primary   K1+K2+K3+K4  the same for the primary rays only, children to the global SoA ray queues
 //   k_bounce    K2+K3+K4     one level of the reflection/refraction ray tree from a global queue (the other
 //                            shading models; rays k_wavefront could not keep in LDS)
-//   k_gather    K5           k-nearest photon gather, one query per wavefront step
+//   (k_gather   K5           the k-nearest photon gather: rt_gather.hip)
 //   k_resolve   K6           per-pixel average / variance gate / gamma / Color24 pack
 //   k_trace     K2           closest-hit only (parity entry point rt_trace_rays)
 //
@@ -25,40 +25,16 @@
 #include <algorithm>
 #include <type_traits>
 #include "rt_launch.h"
+#include "rt_kernel_util.h"
 
 #define BIGFLOAT 1.0e30f
 #define LEAF_BIT 0x80000000u
-// k_gather tuning knobs (the defaults are the measured best on MI355X)
-#ifndef RT_GATHER_GUESS
-#define RT_GATHER_GUESS 1.2f   // photons expected inside the first trial radius, in units of k (round 2, sub-leaves: 1.1: 42.0 ms, 1.15: 40.8, 1.2: 40.7, 1.3: 41.7, 1.45: 43.3)
-#endif
-#ifndef RT_GATHER_RING
-#define RT_GATHER_RING 128     // LDS entries for the photons around the predicted k-th distance (0: always re-read in pass 2)
-#endif
-#ifndef RT_GATHER_BAND_LO
-#define RT_GATHER_BAND_LO 0.92f   // the ring keeps the photons between BAND_LO and BAND_HI times the predicted k-th squared distance
-                                  // (0.85-1.18: 40.7 ms, 0.88-1.15: 39.7, 0.92-1.10: 39.4, 0.94-1.08: 39.3)
-#endif
-#ifndef RT_GATHER_BAND_HI
-#define RT_GATHER_BAND_HI 1.10f
-#endif
-#ifndef RT_GATHER_BATCH
-#define RT_GATHER_BATCH 32     // queries a wave lists per phase A (40 leaf ids each: lists + ring keep 5 waves/SIMD)
-#endif
-#ifndef RT_GATHER_CELL_GUESS
-#define RT_GATHER_CELL_GUESS RT_GATHER_GUESS    // first trial radius^2 of a query whose cell remembers a k-th distance: that distance times this
-#endif
-// the photon loop of k_gather may contract mul+add into fma (d^2, dir.N, box distances, weighted sums; gate there: 2e-5); the rest of the
-// file stays uncontracted: hit records are bit-exact
-#define RT_FP_CONTRACT _Pragma("clang fp contract(fast)")
 #ifndef RT_WF_GRAB
 #define RT_WF_GRAB 2           // rounds of 256 primary samples (or queued rays) a workgroup of k_wavefront takes per atomic on the work counter
 #endif
 #ifndef RT_WF_PERWAVE
 #define RT_WF_PERWAVE 1        // 1: for the P12 model every wave of k_wavefront runs its own rounds on its own part of the LDS ray stack (no workgroup barriers); 0: the four waves always share stack and rounds
 #endif
-#define RT_SUBS_PER_STEP (64 / RT_SUB_PHOTONS)                  // sub-leaves a wavefront examines per step
-#define RT_SUBLIST_CAP (RT_LEAFLIST_CAP * RT_LEAF_SUBS)         // sub-leaf ids of one query
 
 // ------------------------------------------------------------------------------------------------
 // float3 algebra in the reference's evaluation order (cyPoint.h:259-350, cyMatrix.h:542-546)
@@ -527,12 +503,6 @@ __device__ __forceinline__ void rng2(const RngCtx &c, uint32_t purpose, uint32_t
 __host__ __device__ inline uint32_t child_node(uint32_t node, uint32_t kind) { return node * 0x9E3779B1u + kind * 0x85EBCA6Bu + 0x27D4EB2Fu; }
 
 // ------------------------------------------------------------------------------------------------
-// the lanes where a condition holds: the builtin keeps the condition a lane mask (one s_and with exec); HIP's
-// __ballot(int) round-trips it through a 0/1 register (v_cndmask + v_cmp_ne per call, on the VALU the gather is bound by)
-__device__ __forceinline__ unsigned long long ballot64(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
-// how many lanes of a mask lie below this one: v_mbcnt_lo + v_mbcnt_hi
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-
 // queues: wave-aggregated append (one atomic per wave, __ballot + popcount for the lane offset)
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t wave_push(bool pred, uint32_t *counter)
@@ -753,23 +723,6 @@ __device__ V3 illuminate(const DevScene &S, const rt_params &P, const rt_light &
         shadow /= 16.0f;
     }
     return (I * shadow) / len2(p - position);
-}
-
-// Reproducible mode (RT_RENDER_REPRODUCIBLE): a contribution that is not a sample's primary one goes into the secondary plane as
-// a 32.32 fixed-point integer, rounded to nearest-even, saturated at +-2^31, NaN as 0.  Integer adds are associative, so the
-// sum does not depend on the order the atomics arrive in; the plane is folded into sample_rgb once per pass (k_fold_fx).
-#define RT_FX_ONE 4294967296.0f          /* 2^32: 32 fractional bits */
-__device__ __forceinline__ unsigned long long fx_encode(float c)
-{
-    const float x = rintf(c * RT_FX_ONE);                 // exact scaling (a power of two), then round to an integer
-    if (!(x == x)) return 0ull;
-    if (x >= 9223372036854775807.0f) return 0x7FFFFFFFFFFFFFFFull;       // 2^63 as a float
-    if (x <= -9223372036854775808.0f) return 0x8000000000000000ull;
-    return (unsigned long long)(long long)x;
-}
-__device__ __forceinline__ void fx_add(unsigned long long *dst, float r, float g, float b)
-{
-    atomicAdd(dst, fx_encode(r)); atomicAdd(dst + 1, fx_encode(g)); atomicAdd(dst + 2, fx_encode(b));    // global_atomic_add_u64
 }
 
 template <bool FX = false>
@@ -1899,746 +1852,6 @@ void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs
 }
 
 // ------------------------------------------------------------------------------------------------
-// K5: PhotonMap::EstimateIrradiance<k>(irr, dir, radius, pos, &N, 1, CONSTANT)
-// (FIN/include/cyPhotonMap.h:288-336, LocatePhotons :365-440).
-//
-// The reference walks its heap-ordered kd-tree recursively per query and keeps the k nearest
-// accepted photons (inside the radius, photonDir.N < 0) in a max-heap, shrinking the search radius
-// once the heap is full; the estimate only needs
-//   sum of power, sum of dir*maxPower over that set, and r_k^2 (= radius^2 while at most k photons
-//   qualify, else the k-th smallest squared distance).
-// Here each wavefront serves 64 queries at a time.
-//   Phase A, one query per lane: a stackless walk of the complete binary tree of leaf boxes lists
-//     the leaves within the query's CURRENT trial radius (ids in LDS).
-//   Phase B, the whole wave per query: every listed leaf is one coalesced 64-photon read
-//     (lane = photon).  Pass 1 counts the accepted photons into a 256-bin histogram of a 24-bit
-//     fixed-point distance key (LDS atomics) while summing all of them.  If the trial radius is
-//     smaller than the requested one and at most k photons qualified, the query is retried with a
-//     larger radius predicted from the count (photons lie on surfaces: count ~ r^2); a trial that
-//     finds MORE than k is exact, because the k nearest all lie inside it.  If more than k qualify,
-//     the bin holding the k-th is located with a wave scan, pass 2 sums the bins below it and
-//     collects that bin (<= 64 entries, else one more 8-bit level) for an exact rank selection.
-// Sums are per-lane partials combined by a fixed butterfly: deterministic.
-// ------------------------------------------------------------------------------------------------
-struct GatherArgs {
-    DevPhotonMap pm;
-    const float4 *qa, *qb, *qc;      // query queue
-    const uint32_t *count_ptr;       // number of queries (device)
-    uint32_t *next_batch;            // zero at launch, RT_CTR_STRIDE apart: [seg] = batches handed out of XCD segment seg (8), [8] = mask of the segments used up
-    uint32_t count_cap;
-    int k; float radius;
-    float *sample_rgb;               // mode 0: atomicAdd w * irr * max(0, N.(-dir)) into the slot
-    float *out_irr, *out_dir;        // mode 1: write irr[3], dir[3] per query (rt_estimate_irradiance)
-    int mode;
-    unsigned long long *stats;
-    float *cell_rk2;                 // per density-grid cell: the k-th squared distance of the last query answered there (0 = none yet); may be NULL
-    unsigned long long *fx;          // reproducible instantiation, mode 0: deposit into this secondary plane (fx_add) instead of sample_rgb
-};
-
-// Wave-wide inclusive scans on the DPP path (row_shr 1/2/4/8 inside each row of 16 lanes, then
-// row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3): six VALU instructions, no LDS
-// crossbar traffic (__shfl is ds_bpermute: an LDS round trip per step).  All 64 lanes must be active.
-// Lanes without a source keep `old` = the identity.  Fixed order => deterministic float sums.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float identity, float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(identity), __float_as_int(x), CTRL, ROW_MASK, 0xF, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t identity, uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)x, CTRL, ROW_MASK, 0xF, false);
-}
-#define DPP_ROW_SHR(n) (0x110 + (n))
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
-__device__ __forceinline__ float wave_scan_add(float x)
-{
-    x += dpp_f<DPP_ROW_SHR(1), 0xF>(0.0f, x); x += dpp_f<DPP_ROW_SHR(2), 0xF>(0.0f, x);
-    x += dpp_f<DPP_ROW_SHR(4), 0xF>(0.0f, x); x += dpp_f<DPP_ROW_SHR(8), 0xF>(0.0f, x);
-    x += dpp_f<DPP_ROW_BCAST15, 0xA>(0.0f, x); x += dpp_f<DPP_ROW_BCAST31, 0xC>(0.0f, x);
-    return x;
-}
-__device__ __forceinline__ uint32_t wave_scan_add_u(uint32_t x)
-{
-    x += dpp_u<DPP_ROW_SHR(1), 0xF>(0u, x); x += dpp_u<DPP_ROW_SHR(2), 0xF>(0u, x);
-    x += dpp_u<DPP_ROW_SHR(4), 0xF>(0u, x); x += dpp_u<DPP_ROW_SHR(8), 0xF>(0u, x);
-    x += dpp_u<DPP_ROW_BCAST15, 0xA>(0u, x); x += dpp_u<DPP_ROW_BCAST31, 0xC>(0u, x);
-    return x;
-}
-__device__ __forceinline__ float wave_scan_max0(float x)          // x >= 0
-{
-    x = fmaxf(x, dpp_f<DPP_ROW_SHR(1), 0xF>(0.0f, x)); x = fmaxf(x, dpp_f<DPP_ROW_SHR(2), 0xF>(0.0f, x));
-    x = fmaxf(x, dpp_f<DPP_ROW_SHR(4), 0xF>(0.0f, x)); x = fmaxf(x, dpp_f<DPP_ROW_SHR(8), 0xF>(0.0f, x));
-    x = fmaxf(x, dpp_f<DPP_ROW_BCAST15, 0xA>(0.0f, x)); x = fmaxf(x, dpp_f<DPP_ROW_BCAST31, 0xC>(0.0f, x));
-    return x;
-}
-// totals: lane 63 of the inclusive scan, as a scalar
-__device__ __forceinline__ float wave_sum(float x) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_add(x)), 63)); }
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add_u(x), 63); }
-__device__ __forceinline__ float wave_max0(float x) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_max0(x)), 63)); }
-
-// Six wave totals at once.  v_permlane32_swap / v_permlane16_swap (gfx950) exchange half-waves / odd-even rows of TWO
-// registers, so one swap + one add folds two values at a time: after the 32-lane and the 16-lane fold four values share
-// one register (a row of 16 lanes each), and the last four steps (row_shr 8, 4, 2, 1) run on two registers instead of
-// six: 25 vector instructions instead of 48 for six separate scans.  Fixed order => deterministic.
-__device__ __forceinline__ void fold32(float a, float b, float &ab)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    ab = __uint_as_float(r[0]) + __uint_as_float(r[1]);          // lanes 0-31: a folded, lanes 32-63: b folded
-}
-__device__ __forceinline__ void fold16(float x, float y, float &xy)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    xy = __uint_as_float(r[0]) + __uint_as_float(r[1]);          // rows 0..3: x.lo, y.lo, x.hi, y.hi folded to 16 lanes
-}
-__device__ __forceinline__ float row_total(float x)               // lane 15 of every row: the row's sum
-{
-    x += dpp_f<DPP_ROW_SHR(8), 0xF>(0.0f, x); x += dpp_f<DPP_ROW_SHR(4), 0xF>(0.0f, x);
-    x += dpp_f<DPP_ROW_SHR(2), 0xF>(0.0f, x); x += dpp_f<DPP_ROW_SHR(1), 0xF>(0.0f, x);
-    return x;
-}
-__device__ __forceinline__ void wave_sum6(float v0, float v1, float v2, float v3, float v4, float v5, float out[6])
-{
-    float s01, s23, s45, t0123, t45;
-    fold32(v0, v1, s01); fold32(v2, v3, s23); fold32(v4, v5, s45);
-    fold16(s01, s23, t0123);          // rows: v0, v2, v1, v3
-    fold16(s45, s45, t45);            // rows: v4, v4, v5, v5
-    t0123 = row_total(t0123); t45 = row_total(t45);
-    out[0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t0123), 15));
-    out[2] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t0123), 31));
-    out[1] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t0123), 47));
-    out[3] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t0123), 63));
-    out[4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t45), 15));
-    out[5] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t45), 47));
-}
-
-// value of lane l (wave-uniform l) as a scalar: v_readlane, no LDS traffic, result lives in an SGPR
-__device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ uint32_t lane_u(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-
-// boxes are two aligned 16-byte words (lo.xyz, -), (hi.xyz, -): one visit = two dwordx4 loads
-__device__ __forceinline__ float box_dist2(const float4 *b, float px, float py, float pz)
-{
-    RT_FP_CONTRACT
-    const float4 lo = b[0], hi = b[1];
-    const float dx = fmaxf(fmaxf(lo.x - px, px - hi.x), 0.0f);
-    const float dy = fmaxf(fmaxf(lo.y - py, py - hi.y), 0.0f);
-    const float dz = fmaxf(fmaxf(lo.z - pz, pz - hi.z), 0.0f);
-    return dx * dx + dy * dy + dz * dz;
-}
-
-// LDS hand-off between lanes of ONE wavefront: LDS operations of a wave complete in issue order, so
-// only the compiler has to be kept from reordering, plus a wait for outstanding LDS returns.
-__device__ __forceinline__ void wave_sync()
-{
-    // "wavefront" scope: the hardware already executes one wave's LDS instructions in issue order, so a write by one lane is
-    // seen by a later read of another lane of the SAME wave without waiting for anything; the fences only keep the compiler
-    // from moving LDS accesses across this point.  ("workgroup" scope made every one of the ~10 hand-offs per query an
-    // s_waitcnt vmcnt(0) lgkmcnt(0): it also drained the photon loads in flight.)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct GatherLds {
-    uint16_t leaves[RT_GATHER_BATCH][RT_LEAFLIST_CAP];   // per query (lane) leaf ids
-    uint32_t subs[RT_SUBLIST_CAP + RT_SUBS_PER_STEP];    // the current query's sub-leaf ids, padded to whole steps with the dummy sub-leaf
-    union alignas(16) {                                  // never live at the same time:
-        uint32_t hist[256];                              //   the distance-key histogram while the k-th photon's bin is located
-        struct { float sel_d[64]; uint32_t sel_i[64]; uint32_t sel_n; };   //   then that bin's photons for the exact rank selection
-    };
-    // everything pass 1 read about a photon whose distance lies in the band around the predicted k-th one,
-    // so that the exact selection does not have to read the leaves a second time
-    float4   ring_a[RT_GATHER_RING];      // d2, dir.x, dir.y, dir.z
-    float2   ring_b[RT_GATHER_RING];      // max power, colour bytes
-};
-
-// Color24 -> Color (cyColor.h): byte / 255.0f, correctly rounded, without the ~10-instruction IEEE division and without
-// a table: 1/255 as a two-term constant, r_hi = RN(1/255) and r_lo = RN(1/255 - r_hi); fma(c, r_hi, RN(c * r_lo)) adds the
-// exact product c * r_hi to a correction that is itself good to 2^-48 of the result, and lands on the correctly rounded
-// quotient for every byte value (all 256 checked exactly, in rational arithmetic: tests/test_host.py; on the device:
-// test_gpu_parity.py::test_irradiance_single_photon_colour_bytes).  Two instructions; c * RN(1/255) alone is wrong for
-// 121 of the 256 bytes, and the Newton form used before took three.
-__device__ __forceinline__ float byte_over_255(uint32_t c)
-{
-    const float r_hi = 0x1.010102p-8f, r_lo = -0x1.fdfdfep-33f;
-    const float x = (float)c;
-    return __fmaf_rn(x, r_hi, x * r_lo);
-}
-
-// one lane's photon of one sub-leaf against one query (the test of LocatePhotons :383-392).  d2 is the squared distance
-// for a photon that faces the surface and +infinity for one that does not (or for an empty slot, whose position is
-// 3e38): "accepted" is then the single compare d2 < rq2, and every narrower test (below t_lo, inside the band) is one
-// compare as well -- a compare's lane mask is its ballot, while a ballot of a combined condition costs two more
-// vector instructions, on the unit this kernel is bound by.
-struct Cand { float d2; float4 pa, pb; };
-struct GatherQuery { float px, py, pz, nx, ny, nz, rq2, kscale; };
-__device__ __forceinline__ Cand make_cand(float4 pa, float4 pb, const GatherQuery &Q)
-{
-    RT_FP_CONTRACT
-    Cand c;
-    c.pa = pa; c.pb = pb;
-    const float dfx = pa.x - Q.px, dfy = pa.y - Q.py, dfz = pa.z - Q.pz;       // dif = p.position - np.pos
-    const float d2 = dfx * dfx + dfy * dfy + dfz * dfz;                         // LengthSquared
-    const bool away = (pa.w * Q.nx + pb.x * Q.ny + pb.y * Q.nz) >= 0;           // dir.N >= 0 rejects
-    c.d2 = away ? __builtin_inff() : d2;                                        // dist2 < dist2[0] is tested by the caller
-    return c;
-}
-// 24-bit fixed-point distance key of an ACCEPTED photon: kscale = 16777000 / rq2, so d2 < rq2 gives at most
-// 16777000 * (1 + 2^-22) < 2^24 whatever the roundings
-__device__ __forceinline__ uint32_t cand_key(const Cand &c, const GatherQuery &Q) { return (uint32_t)(c.d2 * Q.kscale); }
-
-// Visit every photon slot of the n_sub sub-leaves listed in LDS (ids[]; padded to whole steps with the dummy sub-leaf,
-// whose slots are all empty), 64 / RT_SUB_PHOTONS sub-leaves per step (lanes 0-31 the first, 32-63 the second):
-// f(candidate, slot) is called wave-uniformly (all 64 lanes) so it may use ballots.  A lane's share of a step is one LDS
-// read (its sub-leaf id), one shift-or (the byte offset, 32 bits) and two coalesced 16-byte loads from scalar bases --
-// nothing else is fetched per photon.  The loads of step it+1 are issued before step it is processed, so a wave
-// always has a step in flight while it works: measured on MI355X the un-pipelined version spent 78 % of its wave
-// cycles parked on s_waitcnt (SQ_WAIT_ANY / SQ_WAVE_CYCLES).
-template <class F>
-__device__ __forceinline__ void scan_subleaves(const DevPhotonMap &pm, const uint32_t *ids, uint32_t n_sub, int lane,
-                                               const GatherQuery &Q, F &&f)
-{
-    if (n_sub == 0) return;
-    const uint32_t n_iter = (n_sub + RT_SUBS_PER_STEP - 1u) / RT_SUBS_PER_STEP;
-    const uint32_t *mine = ids + (uint32_t)lane / RT_SUB_PHOTONS;           // which of a step's sub-leaves this lane reads
-    const uint32_t lane_off = ((uint32_t)lane % RT_SUB_PHOTONS) * 16u;
-    const char *pa = (const char *)pm.pa, *pb = (const char *)pm.pb;
-    auto ld = [&](uint32_t it, float4 &a, float4 &b, uint32_t &slot) {
-        const uint32_t off = (mine[RT_SUBS_PER_STEP * it] * (RT_SUB_PHOTONS * 16u)) | lane_off;   // < 2^32: checked at upload
-        slot = off;
-        a = *(const float4 *)(pa + off);
-        b = *(const float4 *)(pb + off);
-    };
-    // two register sets used alternately, each refilled right after it was consumed; the reload index
-    // is clamped instead of branched over (the last step may be fetched twice) so that neither set
-    // is a loop-carried copy of the other
-    float4 a0, b0, a1, b1;
-    uint32_t s0, s1;
-    ld(0u, a0, b0, s0);
-    uint32_t it = 0;
-    for (; it + 1 < n_iter; it += 2) {
-        ld(it + 1, a1, b1, s1);
-        f(make_cand(a0, b0, Q), s0);
-        ld(min(it + 2, n_iter - 1), a0, b0, s0);
-        f(make_cand(a1, b1, Q), s1);
-    }
-    if (it < n_iter) f(make_cand(a0, b0, Q), s0);
-}
-
-#ifndef RT_GATHER_WAVES_PER_EU
-#define RT_GATHER_WAVES_PER_EU 5     // 96 registers: five waves per SIMD is what the LDS footprint allows too
-#endif
-template <bool FX = false>
-__attribute__((amdgpu_waves_per_eu(RT_GATHER_WAVES_PER_EU, RT_GATHER_WAVES_PER_EU)))
-__global__ __launch_bounds__(64 * RT_GATHER_WAVES) void k_gather(GatherArgs G)
-{
-    __shared__ GatherLds lds_all[RT_GATHER_WAVES];
-    GatherLds &L = lds_all[threadIdx.x >> 6];
-    const int lane = threadIdx.x & 63;
-    uint32_t nq = *G.count_ptr;
-    if (nq > G.count_cap) nq = G.count_cap;
-    if (nq == 0) return;                                 // most chunks of a frame see no photon query at all
-    const uint32_t n_leaves = G.pm.n_leaves;
-    const uint32_t n_sub_total = n_leaves * RT_LEAF_SUBS;
-    const float r2 = G.radius * G.radius;
-    const uint32_t K = (uint32_t)G.k;
-    unsigned long long visited = 0;
-    uint32_t n_rounds = 0, n_slow = 0, n_reads = 0;       // wave-uniform tallies
-    float pred_rk2 = 0.0f;                                // k-th squared distance of this wave's previous query (a hint only)
-
-    // batches of RT_GATHER_BATCH queries are handed out dynamically (one atomic per batch): query cost varies by
-    // two orders of magnitude with the local photon density, so a static split leaves a long tail
-    const uint32_t n_batches = (nq + (uint32_t)RT_GATHER_BATCH - 1u) / (uint32_t)RT_GATHER_BATCH;
-    const float guess_c = RT_GATHER_GUESS * (float)K * G.pm.cell * G.pm.cell / (float)M_PI;
-
-    // XCD affinity: the queue is in sample order, so neighbouring batches look up neighbouring points and read the
-    // same sub-leaves.  The queue is cut into eight contiguous segments, one per XCD: the waves of an XCD (640 of
-    // them) then work inside a narrow window of the queue at any time and share its photons through their XCD's
-    // 4 MB L2 instead of each XCD streaming every window's photons from the Infinity Cache.  A wave whose segment
-    // is used up takes batches from the next ones (query cost varies 100x: no static split).  Speed only: any
-    // assignment gives the same results.
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    const uint32_t seg_len = (n_batches + 7u) / 8u;
-    uint32_t seg = xcc;
-    // A wave that finds a segment used up says so in a mask the others READ before they try it: without it every wave ends with
-    // eight failing atomics -- 41 000 of them queueing at the memory side (device-scope atomics are executed there, one after the
-    // other per channel) while nothing else is left to do.  The counters sit RT_CTR_STRIDE apart for the same reason (rt_dev.h).
-    // Measured and not kept (r4, profiles/r04_experiments.json): the last batches of a segment handed out as 8-query units, a
-    // segment handed out from its end.
-    for (;;) {
-        const uint32_t seg_first = seg * seg_len;
-        const uint32_t seg_size = seg_first >= n_batches ? 0u : min(seg_len, n_batches - seg_first);
-        uint32_t got = 0;
-        if (lane == 0) got = atomicAdd(G.next_batch + seg * RT_CTR_STRIDE, 1u);
-        got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
-        if (got >= seg_size) {                               // this segment is finished: move on to one that is not known to be, or stop
-            uint32_t *const done_mask = G.next_batch + 8 * RT_CTR_STRIDE;
-            uint32_t done = 0;                               // (what this wave marked earlier is in the mask it reads: same address, program order)
-            if (lane == 0) {
-                done = __hip_atomic_load(done_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!((done >> seg) & 1u)) atomicOr(done_mask, 1u << seg);
-            }
-            done = ((uint32_t)__builtin_amdgcn_readfirstlane((int)done) | (1u << seg)) & 255u;
-            if (done == 255u) break;
-            const uint32_t rot = ((done ^ 255u) | ((done ^ 255u) << 8)) >> (seg + 1u);     // segments still open, seen from seg + 1
-            seg = (seg + 1u + ((uint32_t)__ffs((int)rot) - 1u)) & 7u;
-            continue;
-        }
-        const uint32_t qbase = (seg_first + got) * (uint32_t)RT_GATHER_BATCH;
-        const uint32_t qi = qbase + lane;
-        const bool have = lane < RT_GATHER_BATCH && qi < nq;
-        float4 a = make_float4(0, 0, 0, 0), b = make_float4(0, 0, 0, 0), c = make_float4(0, 0, 0, 0);
-        if (have) { a = G.qa[qi]; b = G.qb[qi]; c = G.qc[qi]; }
-        bool pending = have;
-        float f_pr = 0, f_pg = 0, f_pb = 0, f_dx = 0, f_dy = 0, f_dz = 0, f_area = -1.0f;     // a finished query's sums, in its lane
-        bool finish = false;
-        // first trial radius from the density grid: about RT_GATHER_GUESS * k photons expected inside (count ~ r^2
-        // on a surface through a cell of side h: c photons per h^2)
-        float r2cur = r2;
-        float cell_pred = 0.0f;                              // this lane's query: what its grid cell remembers
-        uint32_t cell_index = 0;
-        uint32_t walk_start = 1;                             // where this lane's query starts its tree walk (DevPhotonMap::cell_start)
-        if (have && n_leaves > 1) {
-            const float fx = (a.x - G.pm.grid_min[0]) * G.pm.inv_cell, fy = (a.y - G.pm.grid_min[1]) * G.pm.inv_cell, fz = (a.z - G.pm.grid_min[2]) * G.pm.inv_cell;
-            const int gx = min(max((int)fx, 0), G.pm.grid_dim[0] - 1);
-            const int gy = min(max((int)fy, 0), G.pm.grid_dim[1] - 1);
-            const int gz = min(max((int)fz, 0), G.pm.grid_dim[2] - 1);
-            cell_index = (uint32_t)(((size_t)gz * G.pm.grid_dim[1] + gy) * G.pm.grid_dim[0] + gx);
-            // only for a point that really lies in its cell (points outside the photons' bounding box are clamped to the rim)
-            const bool in_grid = fx >= 0.0f && fy >= 0.0f && fz >= 0.0f && (int)fx == gx && (int)fy == gy && (int)fz == gz;
-            if (G.pm.cell_start && in_grid && G.radius <= G.pm.start_radius) walk_start = G.pm.cell_start[cell_index];
-            const uint32_t cnt = G.pm.grid[cell_index];
-            r2cur = fminf(fmaxf(guess_c / (float)(cnt > 0u ? cnt : 1u), r2 * 1.0e-4f), r2);
-            if (G.cell_rk2) {
-                cell_pred = G.cell_rk2[cell_index];
-                // a cell that has seen a query also knows a better first radius than the density estimate: a little above its k-th distance
-                if (cell_pred > 0.0f) r2cur = fminf(fmaxf(cell_pred * RT_GATHER_CELL_GUESS, r2 * 1.0e-4f), r2);
-                else if (cell_pred < 0.0f) r2cur = r2;       // "sparse here": the full radius at once
-            }
-        }
-
-        while (ballot64(pending)) {
-            // ---------------- phase A: pending lanes list the leaves inside their trial radius ----
-            // Two lanes walk for one query: lane l and lane l + 32 hold the same point and radius, keep the same walk state
-            // and split the box tests of every visit between them (grandchildren 0-1 / 2-3, child 0 / 1); one
-            // v_permlane32_swap per visit gives both the combined result.  The queries sit in lanes 0-31 only (32 per
-            // batch), so the upper half of the wave would otherwise idle through the phase.
-            static_assert(RT_GATHER_BATCH == 32, "phase A pairs lane l with lane l + 32");
-            const bool upper = lane >= 32;
-            auto from_lower = [](float v) { return __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false)[0]); };
-            const float wx = from_lower(a.x), wy = from_lower(a.y), wz = from_lower(a.z), wr2 = from_lower(r2cur);
-            const uint32_t wstart = __builtin_amdgcn_permlane32_swap(walk_start, walk_start, false, false)[0];
-            const bool walking = ((uint32_t)ballot64(pending) >> (lane & 31)) & 1u;
-            auto both_halves = [](uint32_t mine, int bits) {       // my half's result bits -> lower half's | upper half's << bits, in every lane
-                const auto r = __builtin_amdgcn_permlane32_swap(mine, mine, false, false);
-                return r[0] | (r[1] << bits);
-            };
-            uint32_t nl = 0;
-            auto list_leaf = [&](uint32_t leaf) {
-                if (!upper && nl < RT_LEAFLIST_CAP) L.leaves[lane][nl] = (uint16_t)leaf;
-                nl++;
-            };
-            if (walking && n_leaves) {
-                // Depth-first, left to right (ascending leaf ids).  Phase A waits for a chain of dependent box reads, so a
-                // visit reads as much as one aligned line pair gives: the boxes of all four GRANDCHILDREN of an internal node
-                // (heap order: nodes 4n..4n+3, 128 contiguous bytes) -- a grandchild the ball cuts implies its parent is cut,
-                // so the level between needs no test of its own.  Which grandchildren are still to be visited is kept as a
-                // 4-bit mask per pair of levels; no box is fetched twice.  An odd last level is a two-child visit.
-                if (box_dist2(G.pm.tbox + 2, wx, wy, wz) < wr2) {
-                    if (n_leaves == 1) list_leaf(0u);
-                    else {
-                        uint32_t node = wstart;                 // current internal node (the root, or the cell's start node: even depth) ...
-                        uint32_t pd = (31u - (uint32_t)__clz((int)node)) >> 1;      // ... and its pair-depth (tree depth = 2 * pd)
-                        uint32_t todo_mask = 0;                 // nibble pd: grandchildren of the path's node at pair-depth pd still to visit (at most 65536 leaves: 8 nibbles)
-                        for (;;) {
-                            if (4u * node < 2u * n_leaves && 2u * node < n_leaves) {
-                                // grandchildren exist (they are internal nodes, or the leaves themselves)
-                                const float4 *gb = G.pm.tbox + 8 * (size_t)node + (upper ? 4 : 0);      // boxes of 4*node .. 4*node + 3: two of them for me
-                                uint32_t m2 = 0;
-                                if (box_dist2(gb, wx, wy, wz) < wr2) m2 |= 1u;
-                                if (box_dist2(gb + 2, wx, wy, wz) < wr2) m2 |= 2u;
-                                const uint32_t m4 = both_halves(m2, 2);
-                                if (4u * node >= n_leaves) {     // the grandchildren are leaves
-                                    for (int i = 0; i < 4; i++) if ((m4 >> i) & 1u) list_leaf(4u * node + (uint32_t)i - n_leaves);
-                                } else if (m4) {
-                                    const uint32_t i = (uint32_t)__ffs((int)m4) - 1u;
-                                    todo_mask |= (m4 & ~(1u << i)) << (4u * pd);
-                                    node = 4u * node + i; pd++;
-                                    continue;
-                                }
-                            } else {
-                                // one level left: the children are leaves
-                                const float4 *cb = G.pm.tbox + 4 * (size_t)node + (upper ? 2 : 0);
-                                const uint32_t m2 = both_halves(box_dist2(cb, wx, wy, wz) < wr2 ? 1u : 0u, 1);
-                                if (m2 & 1u) list_leaf(2u * node - n_leaves);
-                                if (m2 & 2u) list_leaf(2u * node + 1u - n_leaves);
-                            }
-                            if (!todo_mask) break;
-                            const uint32_t bit = 31u - (uint32_t)__clz((int)todo_mask);            // deepest pair-depth with work left
-                            const uint32_t d = bit >> 2;
-                            const uint32_t nib = (todo_mask >> (4u * d)) & 15u;
-                            const uint32_t i = (uint32_t)__ffs((int)nib) - 1u;                    // its leftmost grandchild not yet visited
-                            todo_mask &= ~(1u << (4u * d + i));
-                            node = ((node >> (2u * (pd - d))) << 2) + i;                          // that ancestor's grandchild i
-                            pd = d + 1u;
-                        }
-                    }
-                }
-            }
-            wave_sync();
-            // ---------------- phase B: the wave takes the pending queries one by one --------------
-            unsigned long long todo = ballot64(pending);
-            while (todo) {
-                const int q = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                GatherQuery Q;
-                Q.px = lane_f(a.x, q); Q.py = lane_f(a.y, q); Q.pz = lane_f(a.z, q);
-                Q.nx = lane_f(a.w, q); Q.ny = lane_f(b.x, q); Q.nz = lane_f(b.y, q);
-                Q.rq2 = lane_f(r2cur, q);
-                Q.kscale = 16777000.0f / Q.rq2;            // 24-bit fixed-point distance key (see cand_key)
-                const float rq2 = Q.rq2;
-                const uint32_t qnl = lane_u(nl, q);
-                const bool final_round = rq2 >= r2;
-                const bool slow = qnl > RT_LEAFLIST_CAP;   // the LDS list overflowed
-                // ---- the query's sub-leaves: RT_LEAF_SUBS boxes per listed leaf, tested 64 at a time, ids compacted in LDS ----
-                // (a leaf holds 128 photon slots; most query balls cut only part of one: testing its four 32-slot
-                // sub-boxes examines about a fifth fewer photons than reading whole 64-slot leaves did)
-                const uint32_t dummy_sub = n_sub_total;    // one more sub-leaf after the real ones, every slot empty
-                uint32_t n_sub = 0;
-                wave_sync();                               // the previous query's passes are done with L.subs
-                if (!slow) {
-                    for (uint32_t base = 0; base < qnl * RT_LEAF_SUBS; base += 64u) {
-                        const uint32_t e = base + (uint32_t)lane;
-                        const bool have_e = (e / RT_LEAF_SUBS) < qnl;
-                        const uint32_t sub = have_e ? (uint32_t)L.leaves[q][e / RT_LEAF_SUBS] * RT_LEAF_SUBS + (e % RT_LEAF_SUBS) : 0u;
-                        const float bd = have_e ? box_dist2(G.pm.sbox + 2 * (size_t)sub, Q.px, Q.py, Q.pz) : __builtin_inff();
-                        const unsigned long long m = ballot64(bd < rq2);
-                        if (bd < rq2) L.subs[n_sub + lanes_below(m)] = sub;
-                        n_sub += (uint32_t)__popcll(m);
-                    }
-                    if (lane < RT_SUBS_PER_STEP) L.subs[n_sub + lane] = dummy_sub;
-                    wave_sync();
-                } else {
-                    // list too long for LDS: every pass walks ALL sub-leaf boxes instead (64 per step) -- no list is kept
-                    for (uint32_t base = 0; base < n_sub_total; base += 64u) {
-                        const uint32_t sub = base + (uint32_t)lane;
-                        const float bd = sub < n_sub_total ? box_dist2(G.pm.sbox + 2 * (size_t)sub, Q.px, Q.py, Q.pz) : __builtin_inff();
-                        n_sub += (uint32_t)__popcll(ballot64(bd < rq2));
-                    }
-                }
-                n_rounds++; n_slow += slow ? 1u : 0u; n_reads += n_sub;
-                // run one pass over the query's sub-leaves
-                auto for_each = [&](auto &&f) {
-                    if (!slow) { scan_subleaves(G.pm, L.subs, n_sub, lane, Q, f); return; }
-                    for (uint32_t base = 0; base < n_sub_total; base += 64u) {
-                        const uint32_t sub = base + (uint32_t)lane;
-                        const float bd = sub < n_sub_total ? box_dist2(G.pm.sbox + 2 * (size_t)sub, Q.px, Q.py, Q.pz) : __builtin_inff();
-                        const unsigned long long m = ballot64(bd < rq2);
-                        if (!m) continue;
-                        wave_sync();
-                        if (bd < rq2) L.subs[lanes_below(m)] = sub;
-                        const uint32_t cnt = (uint32_t)__popcll(m);
-                        if (lane < RT_SUBS_PER_STEP) L.subs[cnt + lane] = dummy_sub;
-                        wave_sync();
-                        scan_subleaves(G.pm, L.subs, cnt, lane, Q, f);
-                    }
-                };
-                float s_pr = 0, s_pg = 0, s_pb = 0, s_dx = 0, s_dy = 0, s_dz = 0;   // pass 1: sums over ALL candidates
-                // sum of power (GetPower = Color24 -> Color times power) and of dir * maxPower for one photon
-                // (branch-free variant: take == false adds exact zeros; measured slower than the branch)
-                auto accumulate5 = [&](float dirx, float diry, float dirz, float maxp, uint32_t cbits, bool take) {
-                    RT_FP_CONTRACT
-                    if (!take) return;
-                    const float mp = take ? maxp : 0.0f;
-                    s_pr += byte_over_255(cbits & 255u) * mp; s_pg += byte_over_255((cbits >> 8) & 255u) * mp; s_pb += byte_over_255((cbits >> 16) & 255u) * mp;
-                    s_dx += dirx * mp; s_dy += diry * mp; s_dz += dirz * mp;
-                };
-                auto accumulate = [&](const float4 &pa, const float4 &pb, bool take) { accumulate5(pa.w, pb.x, pb.y, pb.z, __float_as_uint(pb.w), take); };
-
-                uint32_t M = 0;                            // accepted photons (wave-uniform: popcount of the ballots)
-                float area_d2 = rq2;
-                bool done_plain = false;
-                // "Sparse here": the cell's last query found no more than k photons inside the FULL radius.  Then all accepted
-                // photons count and dist2[0] stays radius^2 (cyPhotonMap.h:309-326): one plain pass sums them -- no histogram, no ring,
-                // no selection.  If more than k turn up after all, the sums are dropped and the normal path below does the query.
-                if (final_round && lane_f(cell_pred, q) < 0.0f) {
-                    for_each([&](const Cand &cd, uint32_t) {
-                        M += (uint32_t)__popcll(ballot64(cd.d2 < rq2));
-                        accumulate(cd.pa, cd.pb, cd.d2 < rq2);
-                    });
-                    visited += n_sub;
-                    if (M <= K) done_plain = true;
-                    else { M = 0; s_pr = s_pg = s_pb = s_dx = s_dy = s_dz = 0; n_reads += n_sub; }
-                }
-                if (!done_plain) {
-                *(uint4 *)&L.hist[4 * lane] = make_uint4(0u, 0u, 0u, 0u);     // the 256 bins in one 16-byte store per lane
-                wave_sync();
-                // pass 1: count + histogram of every accepted photon.  Photons closer than t_lo (safely inside the
-                // k nearest if the prediction holds) are summed right away; those between t_lo and t_hi, the band
-                // the k-th distance is expected in, are parked in the LDS ring with all their data.
-                // The histogram bin is the top 8 bits of the 24-bit key: (uint)(d2 * kscale) >> 16 == (uint)(d2 * (kscale / 65536)),
-                // the scaling by a power of two being exact.
-                const float kscale_bin = Q.kscale * (1.0f / 65536.0f);
-                { const float cp = lane_f(cell_pred, q); if (cp > 0.0f) pred_rk2 = cp; }
-                const float pk = (pred_rk2 > 0.0f && pred_rk2 < rq2) ? pred_rk2 : rq2 * (1.0f / RT_GATHER_GUESS);
-                const float t_lo = RT_GATHER_BAND_LO * pk;
-                const float t_hi = final_round ? rq2 : fminf(RT_GATHER_BAND_HI * pk, rq2);     // <= rq2: inside the band implies accepted
-                uint32_t n_ring = 0;                       // wave-uniform (ballot popcounts)
-                for_each([&](const Cand &cd, uint32_t) {
-                    const unsigned long long m_ok = ballot64(cd.d2 < rq2);
-                    const unsigned long long m_lo = ballot64(cd.d2 < t_lo);
-                    const unsigned long long mr = ballot64(cd.d2 < t_hi) & ~m_lo;
-                    M += (uint32_t)__popcll(m_ok);
-                    if (cd.d2 < rq2) atomicAdd(&L.hist[(uint32_t)(cd.d2 * kscale_bin)], 1u);
-                    accumulate(cd.pa, cd.pb, cd.d2 < t_lo);
-                    if (mr) {
-                        if (cd.d2 < t_hi && !(cd.d2 < t_lo)) {
-                            const uint32_t at = n_ring + lanes_below(mr);
-                            if (at < (uint32_t)RT_GATHER_RING) {
-                                L.ring_a[at] = make_float4(cd.d2, cd.pa.w, cd.pb.x, cd.pb.y);
-                                L.ring_b[at] = make_float2(cd.pb.z, cd.pb.w);
-                            }
-                        }
-                        n_ring += (uint32_t)__popcll(mr);
-                    }
-                });
-                visited += n_sub;
-                if (!final_round && M <= K) {
-                    // not enough inside the trial radius: grow it (count ~ r^2 on a surface) and retry
-                    float grow = 1.5f * (float)K / (float)(M > 0 ? M : 1u);
-                    grow = fminf(fmaxf(grow, 2.0f), 16.0f);
-                    if (lane == q) r2cur = fminf(rq2 * grow, r2);
-                    continue;
-                }
-                area_d2 = rq2;                             // dist2[0]; only reached with rq2 == r2 when M <= K
-                if (M > K) {
-                    // ---- locate the k-th smallest: refine 8 bits of the key per level --------------
-                    uint32_t need = K;                     // rank (1-based) inside the current range
-                    uint32_t prefix = 0;                   // key bits fixed so far
-                    int shift = 16;                        // the level's digit = (key >> shift) & 255
-                    uint32_t in_bin = 0;
-                    for (;;) {
-                        wave_sync();
-                        const uint4 h4 = *(const uint4 *)&L.hist[4 * lane];
-                        const uint32_t h0 = h4.x, h1 = h4.y, h2 = h4.z, h3 = h4.w;
-                        const uint32_t mine = h0 + h1 + h2 + h3;
-                        const uint32_t incl = wave_scan_add_u(mine);
-                        const uint32_t excl = incl - mine;
-                        const unsigned long long m = ballot64(incl >= need);
-                        const int owner = __ffsll((long long)m) - 1;      // first lane whose range reaches `need`
-                        uint32_t digit = 0, before = 0, cntb = 0;
-                        if (lane == owner) {
-                            const uint32_t cum = excl;
-                            if (cum + h0 >= need) { digit = 4 * lane; before = cum; cntb = h0; }
-                            else if (cum + h0 + h1 >= need) { digit = 4 * lane + 1; before = cum + h0; cntb = h1; }
-                            else if (cum + h0 + h1 + h2 >= need) { digit = 4 * lane + 2; before = cum + h0 + h1; cntb = h2; }
-                            else { digit = 4 * lane + 3; before = cum + h0 + h1 + h2; cntb = h3; }
-                        }
-                        digit = lane_u(digit, owner); before = lane_u(before, owner); cntb = lane_u(cntb, owner);
-                        need -= before;
-                        prefix |= digit << shift;
-                        in_bin = cntb;
-                        if (in_bin <= 64u || shift == 0) break;
-                        // one more level: histogram of the next 8 bits over the photons inside this bin
-                        shift -= 8;
-                        wave_sync();
-                        *(uint4 *)&L.hist[4 * lane] = make_uint4(0u, 0u, 0u, 0u);
-                        wave_sync();
-                        const uint32_t hi_mask = ~((1u << (shift + 8)) - 1u) & 0xFFFFFFu;
-                        for_each([&](const Cand &cd, uint32_t) {
-                            const uint32_t key = cand_key(cd, Q);
-                            if (cd.d2 < rq2 && (key & hi_mask) == prefix) atomicAdd(&L.hist[(key >> shift) & 255u], 1u);
-                        });
-                    }
-                    const uint32_t bin_mask = ~((1u << shift) - 1u) & 0xFFFFFFu;
-                    wave_sync();                           // the histogram is dead from here on: its LDS now holds the selection
-                    if (lane == 0) L.sel_n = 0;
-                    wave_sync();
-                    uint32_t tie_taken = 0;                // only used when in_bin > 64 (identical keys)
-                    float tmax = 0.0f;
-                    bool from_ring = false;
-                    {
-                        // The ring serves the selection when (1) it did not overflow, (2) the k-th photon's bin was
-                        // resolved at the first level, (3) every photon below t_lo lies in an earlier bin (so all of
-                        // them count) and (4) every photon of the k-th bin or earlier lies below t_hi (so it is either
-                        // summed already or in the ring).  Keys are monotone in d2, which makes (3) and (4) exact.
-                        const uint32_t bin_lo = (uint32_t)(t_lo * Q.kscale) >> 16, bin_hi = (uint32_t)(t_hi * Q.kscale) >> 16;
-                        const uint32_t kbin = prefix >> 16;
-                        from_ring = shift == 16 && in_bin <= 64u && n_ring <= (uint32_t)RT_GATHER_RING && bin_lo < kbin && (t_hi >= rq2 || kbin < bin_hi);
-                    }
-                    if (from_ring) {
-                        for (uint32_t base = 0; base < n_ring; base += 64u) {
-                            const uint32_t idx = base + (uint32_t)lane;
-                            const bool have = idx < n_ring;
-                            const float4 ra = have ? L.ring_a[idx] : make_float4(3.0e38f, 0, 0, 0);
-                            const float2 rb = have ? L.ring_b[idx] : make_float2(0, 0);
-                            const uint32_t kb = (uint32_t)(ra.x * Q.kscale) & bin_mask;
-                            const bool take = have && kb < prefix;
-                            const bool inb = have && kb == prefix;
-                            const unsigned long long mb = ballot64(inb);
-                            if (mb) {
-                                const uint32_t sbase = lane_u(L.sel_n, 0);
-                                if (inb) {
-                                    const uint32_t at = sbase + lanes_below(mb);
-                                    if (at < 64u) { L.sel_d[at] = ra.x; L.sel_i[at] = idx; }
-                                }
-                                wave_sync();
-                                if (lane == 0) L.sel_n = sbase + (uint32_t)__popcll(mb);
-                                wave_sync();
-                            }
-                            accumulate5(ra.y, ra.z, ra.w, rb.x, __float_as_uint(rb.y), take);
-                        }
-                    }
-                    if (!from_ring) {
-                    n_reads += n_sub;
-                    // ---- pass 2: sum everything below the bin, collect the bin, select `need` of it ----
-                    s_pr = s_pg = s_pb = s_dx = s_dy = s_dz = 0;
-                    for_each([&](const Cand &cd, uint32_t s) {
-                        const bool ok = cd.d2 < rq2;
-                        const uint32_t kb = cand_key(cd, Q) & bin_mask;
-                        bool take = ok && kb < prefix;
-                        const bool inb = ok && kb == prefix;
-                        const unsigned long long mb = ballot64(inb);
-                        if (in_bin <= 64u) {
-                            if (mb) {
-                                uint32_t base = 0;
-                                const int leader = __ffsll((long long)mb) - 1;
-                                if (lane == leader) { base = L.sel_n; L.sel_n = base + (uint32_t)__popcll(mb); }
-                                base = lane_u(base, leader);
-                                if (inb) {
-                                    const uint32_t at = base + lanes_below(mb);
-                                    if (at < 64u) { L.sel_d[at] = cd.d2; L.sel_i[at] = s; }
-                                }
-                            }
-                        } else {
-                            // more than 64 photons share all 24 key bits: take the first `need` in scan order
-                            const uint32_t rank = tie_taken + lanes_below(mb);
-                            if (inb && rank < need) { take = true; tmax = fmaxf(tmax, cd.d2); }
-                            tie_taken += (uint32_t)__popcll(mb);
-                        }
-                        accumulate(cd.pa, cd.pb, take);
-                    });
-                    }
-                    wave_sync();
-                    if (in_bin <= 64u) {
-                        // exact selection: rank by (d2, list position); take ranks < need
-                        const uint32_t n_sel = lane_u(min(L.sel_n, 64u), 0);
-                        const bool mine = (uint32_t)lane < n_sel;
-                        const float md = mine ? L.sel_d[lane] : 3.0e38f;
-                        uint32_t rank = 0;
-                        for (uint32_t j = 0; j < n_sel; j++) {
-                            const float od = L.sel_d[j];
-                            rank += (od < md || (od == md && j < (uint32_t)lane)) ? 1u : 0u;
-                        }
-                        if (mine && rank < need) {
-                            const uint32_t si = L.sel_i[lane];
-                            if (from_ring) {
-                                const float4 ra = L.ring_a[si];
-                                const float2 rb = L.ring_b[si];
-                                accumulate5(ra.y, ra.z, ra.w, rb.x, __float_as_uint(rb.y), true);
-                            } else
-                                accumulate(*(const float4 *)((const char *)G.pm.pa + si), *(const float4 *)((const char *)G.pm.pb + si), true);   // si: byte offset of the slot
-                            tmax = md;
-                        }
-                    }
-                    area_d2 = wave_max0(tmax);                        // np.dist2[0] = largest kept distance
-                    pred_rk2 = area_d2;
-                }
-                else if (M > 0) {
-                    // at most k inside the full radius: all of them count.  Pass 1 summed those below t_lo and, in the
-                    // final round, parked every other one in the ring; if that overflowed, sum them with one more pass
-                    if (n_ring <= (uint32_t)RT_GATHER_RING) {
-                        for (uint32_t base = 0; base < n_ring; base += 64u) {
-                            const uint32_t idx = base + (uint32_t)lane;
-                            if (idx < n_ring) {
-                                const float4 ra = L.ring_a[idx];
-                                const float2 rb = L.ring_b[idx];
-                                accumulate5(ra.y, ra.z, ra.w, rb.x, __float_as_uint(rb.y), true);
-                            }
-                        }
-                    } else {
-                        n_reads += n_sub;
-                        s_pr = s_pg = s_pb = s_dx = s_dy = s_dz = 0;
-                        for_each([&](const Cand &cd, uint32_t) { accumulate(cd.pa, cd.pb, cd.d2 < rq2); });
-                    }
-                }
-                }
-                // the query is done: its six sums and r_k^2 go to ITS lane; what follows from them (area, normalisation, the
-                // weighted add into the sample) is the same scalar arithmetic for every query, so it is done for all the
-                // queries a round finished at once, one per lane, after the loop -- not 64 lanes wide per query
-                {
-                    float t[6];
-                    wave_sum6(s_pr, s_pg, s_pb, s_dx, s_dy, s_dz, t);
-                    if (lane == q) {
-                        f_pr = t[0]; f_pg = t[1]; f_pb = t[2]; f_dx = t[3]; f_dy = t[4]; f_dz = t[5];
-                        f_area = M > 0 ? area_d2 : -1.0f;      // dist2[0] >= 0; negative: no photon at all
-                        finish = true;
-                        pending = false;
-                    }
-                }
-            }
-            if (finish) {
-                float irr_r = f_pr, irr_g = f_pg, irr_b = f_pb, dx = f_dx, dy = f_dy, dz = f_dz;
-                // remember the k-th distance for the next query of this cell (only when more than k qualified: f_area < r2)
-                // (or that no more than k were inside the full radius: f_area is then radius^2, or negative without any photon)
-                if (G.cell_rk2 && n_leaves > 1) {
-                    if (f_area > 0.0f && f_area < r2) G.cell_rk2[cell_index] = f_area;
-                    else if (r2cur >= r2) G.cell_rk2[cell_index] = -1.0f;
-                }
-                if (f_area >= 0.0f) {
-                    const float area = (float)M_PI * f_area;               // :326
-                    if (area > 0) { const float inv = 1.0f / area; irr_r *= inv; irr_g *= inv; irr_b *= inv; }
-                    const float l = sqrtf(dx * dx + dy * dy + dz * dz);    // direction.Normalize() :334
-                    dx /= l; dy /= l; dz /= l;
-                }
-                if (G.mode == 1) {
-                    const size_t qq = (size_t)qi;
-                    G.out_irr[3 * qq] = irr_r; G.out_irr[3 * qq + 1] = irr_g; G.out_irr[3 * qq + 2] = irr_b;
-                    G.out_dir[3 * qq] = dx; G.out_dir[3 * qq + 1] = dy; G.out_dir[3 * qq + 2] = dz;
-                } else {
-                    // idr_Color += kd * photonrad * max(0, N.(-dir)) (FIN/main.cpp:701-704), times the ray weight
-                    const float nx = a.w, ny = b.x, nz = b.y, wr = b.z, wg = b.w, wb = c.x;
-                    const uint32_t slot = __float_as_uint(c.y);
-                    float theta = nx * (-dx) + ny * (-dy) + nz * (-dz);
-                    theta = theta > 0.0f ? theta : 0.0f;
-                    if constexpr (FX) fx_add(G.fx + 3 * (size_t)slot, (wr * irr_r) * theta, (wg * irr_g) * theta, (wb * irr_b) * theta);
-                    else {
-                        float *dst = G.sample_rgb + 3 * (size_t)slot;
-                        atomicAdd(dst, (wr * irr_r) * theta);
-                        atomicAdd(dst + 1, (wg * irr_g) * theta);
-                        atomicAdd(dst + 2, (wb * irr_b) * theta);
-                    }
-                }
-                finish = false;
-            }
-            wave_sync();
-        }
-    }
-    if (G.stats) {                                        // workgroup-uniform; every wave gets here (flush_counters says why it is done this way)
-        __shared__ unsigned long long s_acc[4];
-        if (threadIdx.x < 4) s_acc[threadIdx.x] = 0;
-        __syncthreads();
-        if (lane == 0 && visited) {
-            atomicAdd(&s_acc[0], visited * (unsigned long long)RT_SUB_PHOTONS);
-            atomicAdd(&s_acc[1], (unsigned long long)n_rounds);
-            atomicAdd(&s_acc[2], (unsigned long long)n_slow);
-            atomicAdd(&s_acc[3], (unsigned long long)n_reads * RT_SUB_PHOTONS / 32ull);     // in units of 32 slots = 1 KiB
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            const int slot = threadIdx.x == 0 ? ST_PHOTONS_VISITED : threadIdx.x == 1 ? ST_GATHER_ROUNDS : threadIdx.x == 2 ? ST_GATHER_SLOW : ST_GATHER_LEAF_READS;
-            const unsigned long long x = s_acc[threadIdx.x];
-            if (x) atomicAdd(&G.stats[ST_AT(slot)], x);
-        }
-    }
-    if (G.stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&G.stats[ST_AT(ST_PHOTON_QUERIES)], (unsigned long long)nq);
-}
-
-// ------------------------------------------------------------------------------------------------
 // K6: per pixel, the tail of RenderPixel (FIN/main.cpp:273-338): hits-only average
 // (averageColor :191-199), VariantOverThreshold (:164-189) gate for the second batch, gamma
 // (powf(c, 1.0/gamma) :318-320), Color24 pack (cyColor.h:245-246), z of the last hit sample,
@@ -3053,15 +2266,6 @@ void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float 
     if (model == RT_SHADE_P3) hipLaunchKernelGGL(k_trace<RT_SHADE_P3>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
     else if (model != RT_SHADE_FIN) hipLaunchKernelGGL(k_trace<RT_SHADE_P13>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
     else hipLaunchKernelGGL(k_trace<RT_SHADE_FIN>, dim3(grid), dim3(RT_BLOCK), 0, st, S, rays, n, o.hit, o.z, o.p, o.N, o.node, o.front);
-}
-
-void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks)
-{
-    GatherArgs G; G.pm = R.pm; G.cell_rk2 = R.cell_rk2; G.fx = R.fx; G.qa = R.q.qa; G.qb = R.q.qb; G.qc = R.q.qc; G.count_ptr = R.count; G.count_cap = R.q.cap;
-    G.k = R.k; G.radius = R.radius; G.sample_rgb = R.sample_rgb; G.out_irr = R.out_irr; G.out_dir = R.out_dir; G.mode = R.out_irr ? 1 : 0;
-    G.stats = R.stats; G.next_batch = R.next_batch;
-    if (G.fx && G.mode == 0) hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
-    else hipLaunchKernelGGL(k_gather<false>, dim3(blocks), dim3(64 * RT_GATHER_WAVES), 0, st, G);
 }
 
 // The grid stays within RT_TRACE_BLOCKS <= RT_SPILL_BLOCKS, like every launch that uses the spill part of the traversal stack.

@@ -1,5 +1,5 @@
-// rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip,
-// rt_photon_build.hip): every rtk_* function, the requests they take and the records they exchange.  All three files
+// rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
+// rt_photon_build.hip): every rtk_* function, the requests they take and the records they exchange.  All four files
 // include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
@@ -92,8 +92,6 @@ bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork
 void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, int level, int max_blocks, unsigned long long *fx);
 // closest hits of n caller-supplied rays (6 floats each) with the intersection code of `model`
 void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float *rays, long long n, const TraceOut &out);
-// k_gather as a persistent grid of `blocks` workgroups
-void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks);
 // Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
 void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *fx, size_t samples);
 // k_resolve over A.npix pixels, at most max_blocks workgroups (tiles_prepare is run on a copy of A.tiles).  linear: the LIN
@@ -108,6 +106,10 @@ void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, co
                          uint8_t *second, const DevFeatures &out, bool by_walk);
 // k_photon_trace, one thread per attempt
 void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs &A);
+
+// ---- rt_gather.hip: the photon gather ------------------------------------------------------------------------------------
+// k_gather as a persistent grid of `blocks` workgroups
+void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

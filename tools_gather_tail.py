@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tuning aid (needs the gtail instrumentation build, csrc/experiments/r04_gather_tail.patch, selected with RT_MI355X_LIB): when do the
+"""Tuning aid (needs the gtail instrumentation build, csrc/experiments/r04_gather_tail_and_stat_atomics.patch, selected with RT_MI355X_LIB): when do the
 waves of one k_gather launch start and finish?  One rank's share of the bench frame at N = 8 / 4 / 2 is one chunk = one launch.
 usage: RT_MI355X_LIB=.../librt_gtail.so python tools_gather_tail.py [json-out]"""
 import json
