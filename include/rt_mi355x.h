@@ -536,6 +536,59 @@ rt_status rt_job_stats(rt_job *j, rt_stats *out);
 rt_status rt_job_setup_ms(rt_job *j, rt_setup_ms *out);
 void      rt_job_destroy(rt_job *j);
 
+/* ---- denoising (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) on albedo-demodulated linear colour: the
+ * consumer of the linear plane and of the first-hit planes.  It is an image-space operation on image-sized planes (row-major,
+ * W x H like rgb8) and knows nothing of scenes: it serves whatever wrote the planes -- a job, the device entry points, a
+ * gathered multi-GPU frame.  The reference has no counterpart.  Definition:
+ *   1. A pixel is VALID when object_id >= 0 (id plane given) or z < 1e30 (the render's BIGFLOAT for "nothing hit", no id
+ *      plane).  An invalid pixel's output is its input, bit for bit, and it never contributes to another pixel.
+ *   2. Demodulate per channel: a_c = albedo_c > 1e-3f ? albedo_c : 1.0f (mirrors and black surfaces have kd = 0), d = rgb_linear / a.
+ *   3. Levels i = 0 .. levels-1 with step s = 2^i; taps (dx, dy) in {-2..2}^2, row-major with dy outer, q = p + s * (dx, dy),
+ *      1-D kernel h = {1/16, 1/4, 3/8, 1/4, 1/16}.  A tap is skipped when it lies outside the image, is an invalid pixel, has
+ *      another id than p (id plane given), or when its weight or colour is not finite.  Otherwise
+ *        t = |d_q - d_p|^2 / (sigma_color * 2^-i)^2 + |n_q - n_p|^2 / sigma_normal^2 + ((z_q - z_p) / (sigma_depth * max(z_q, z_p)))^2
+ *        w = h[dx+2] * h[dy+2] * exp(-t)            (the centre tap has t = 0)
+ *      and d'_p = sum(w * d_q) / sum(w).  Every level reads the previous level's complete output; normals are used as stored.
+ *      A pixel whose own colour is not finite passes through (bit for bit, like an invalid one) and contributes nowhere.
+ *   4. Remodulate: out_linear = d * a.
+ *   5. Optionally out_rgb8 = Color24(powf(out_linear, 1/gamma)), k_resolve's rule: for a pixel the filter left alone, the bytes
+ *      k_resolve wrote.  (The exponent is (float)(1.0 / g) with g the double that prints like the float `gamma` to 7 digits:
+ *      for gamma = 2.2f that is k_resolve's (float)(1.0 / 2.2).)
+ * No atomics and a fixed tap order: the output is byte-identical for identical inputs on one build.  out_linear may be
+ * rgb_linear (in place): the input is read completely before anything is written.  No other planes may overlap.
+ * rt_denoise_params: levels 1..8; the sigmas positive and finite; gamma positive and finite (used only for out_rgb8).
+ * rt_denoise_planes: object_id and out_rgb8 are optional (NULL = not given), the other planes are required.  struct_size must be
+ * the caller's sizeof for both structs (anything else: RT_ERR_ARG), so that they can grow.  Arguments are checked before the
+ * GPU is touched: w, h <= 0, a levels or sigma out of range, a missing plane are RT_ERR_ARG, more than 2^30 pixels RT_ERR_LIMIT;
+ * then, without a gfx950 device: RT_ERR_NO_DEVICE (there is no CPU path).
+ * Scratch: 48 bytes per pixel per device, allocated by the first denoise on a device, grown on demand, shared by every later
+ * one (calls on one device are ordered on the GPU one behind the other, whatever their streams) and released when the last
+ * rt_scene of the process is destroyed -- or with the process. */
+typedef struct rt_denoise_params {
+    uint32_t struct_size;
+    int32_t  levels;            /* 5    */
+    float    sigma_color;       /* 1.0  */
+    float    sigma_normal;      /* 0.3  */
+    float    sigma_depth;       /* 0.05 */
+    float    gamma;             /* 2.2  */
+} rt_denoise_params;
+typedef struct rt_denoise_planes {
+    uint32_t struct_size;
+    const float *rgb_linear, *normal, *albedo, *z;
+    const int32_t *object_id;
+    float *out_linear;
+    uint8_t *out_rgb8;
+} rt_denoise_planes;
+void      rt_denoise_default_params(rt_denoise_params *p);
+/* The planes are DEVICE pointers on `device`; the kernels are enqueued on `hip_stream` (NULL = the device's legacy null stream,
+ * as for rt_tiles_unpack_device) and the call returns without waiting for them unless `sync` is non-zero. */
+rt_status rt_denoise_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                            const rt_denoise_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, denoise, download. */
+rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes);
+
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */
 /* n closest-hit queries = n calls of TraceNode(rootNode, ray, hit) (FIN/main.cpp:94-130).

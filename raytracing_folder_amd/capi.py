@@ -61,6 +61,21 @@ class Outputs(C.Structure):
         super().__init__(struct_size=C.sizeof(Outputs), **planes)
 
 
+class DenoiseParams(C.Structure):
+    """rt_denoise_params: the a-trous filter's parameters (rt_denoise_default_params fills 5 / 1.0 / 0.3 / 0.05 / 2.2)"""
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("gamma", C.c_float)]
+
+
+class DenoisePlanes(C.Structure):
+    """rt_denoise_planes: the inputs and outputs of a denoise.  object_id and out_rgb8 are optional (NULL = not given)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
+                ("z", C.c_void_p), ("object_id", C.c_void_p), ("out_linear", C.c_void_p), ("out_rgb8", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(DenoisePlanes), **planes)
+
+
 # the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels)
 OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
                  "alpha": ("alpha", np.float32, 1), "object_id": ("object_id", np.int32, 1)}
@@ -110,6 +125,7 @@ SYMBOLS = [
     "rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device", "rt_tiles_unpack_linear_device",
     "rt_image_write_pfm", "rt_image_read_pfm",
     "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1",
+    "rt_denoise_default_params", "rt_denoise_device", "rt_denoise",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -158,6 +174,12 @@ def lib():
         _lib.rt_render_tiles_outputs_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]
         _lib.rt_image_write_pfm1.argtypes = [C.c_char_p, vp, i32, i32]
         _lib.rt_image_read_pfm1.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), vp, C.c_uint64]
+        # the denoiser (rt_mi355x.h: "denoising")
+        _lib.rt_denoise_default_params.argtypes = [vp]
+        _lib.rt_denoise_default_params.restype = None
+        _lib.rt_denoise_device.argtypes = [C.c_int, vp, i32, i32, vp, vp, C.c_int]
+        _lib.rt_denoise.argtypes = [C.c_int, i32, i32, vp, vp]
+        _lib.rt_denoise_device.restype = _lib.rt_denoise.restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
                      "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
@@ -291,6 +313,46 @@ def image_read_pfm1(path):
     v = np.zeros((h.value, w.value), np.float32)
     _check(lib().rt_image_read_pfm1(os.fsencode(path), C.byref(w), C.byref(h), _p(v), v.size))
     return v
+
+
+def denoise_params(**kw):
+    """rt_denoise_default_params, then the keywords (levels, sigma_color, sigma_normal, sigma_depth, gamma)"""
+    p = DenoiseParams()
+    lib().rt_denoise_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("levels", "sigma_color", "sigma_normal", "sigma_depth", "gamma"):
+            raise TypeError(f"no denoise parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise(linear, normal, albedo, z, object_id=None, rgb8=False, device=0, **params):
+    """The a-trous denoise of a linear frame (rt_denoise; the definition: rt_mi355x.h, "denoising") on host arrays: float32
+    (H, W, 3) linear / normal / albedo, float32 (H, W) z, optionally int32 (H, W) object_id.  Returns the denoised float32
+    (H, W, 3) array -- with rgb8=True the pair (denoised, its gamma-encoded uint8 (H, W, 3) image).  params: denoise_params()."""
+    linear, normal, albedo = (_c(a, np.float32) for a in (linear, normal, albedo))
+    h, w = linear.shape[:2]
+    z = _c(z, np.float32)
+    ids = _c(object_id, np.int32) if object_id is not None else None
+    assert linear.shape == normal.shape == albedo.shape == (h, w, 3) and z.shape == (h, w) and (ids is None or ids.shape == (h, w))
+    out = np.empty((h, w, 3), np.float32)
+    out8 = np.empty((h, w, 3), np.uint8) if rgb8 else None
+    pl = DenoisePlanes(rgb_linear=linear.ctypes.data, normal=normal.ctypes.data, albedo=albedo.ctypes.data, z=z.ctypes.data,
+                       object_id=ids.ctypes.data if ids is not None else None, out_linear=out.ctypes.data,
+                       out_rgb8=out8.ctypes.data if rgb8 else None)
+    p = denoise_params(**params)
+    _check(lib().rt_denoise(int(device), w, h, C.byref(p), C.byref(pl)))
+    return (out, out8) if rgb8 else out
+
+
+def denoise_device(device, stream, w, h, *, linear_ptr, normal_ptr, albedo_ptr, z_ptr, out_ptr, object_id_ptr=None, rgb8_ptr=None,
+                   sync=True, **params):
+    """rt_denoise_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
+    explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr (in place)."""
+    pl = DenoisePlanes(rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, z=z_ptr, object_id=object_id_ptr,
+                       out_linear=out_ptr, out_rgb8=rgb8_ptr)
+    p = denoise_params(**params)
+    _check(lib().rt_denoise_device(int(device), _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
 def identity_map(texture=MAP_NONE):
@@ -569,6 +631,16 @@ class Scene:
             _, dtype, ch = OUTPUT_PLANES[name]          # KeyError: no such plane
             out[name] = np.full((h, w, 3) if ch == 3 else (h, w), id_fill if name == "object_id" else fill, dtype)
         out["rgb"], out["z"], out["count"], out["stats"], out["progress"] = self._render(cam, params, tiles, device, photon_pass, None, dict(out))
+        return out
+
+    def render_denoised(self, cam, params, device=0, photon_pass=False, **denoise_kw):
+        """render_outputs with the linear plane and the four feature planes, then denoise() of that frame guided by them
+        (gamma: the render's): the same dict with "denoised" (float32 (H, W, 3), linear) and "denoised_rgb" (uint8 (H, W, 3))
+        added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth."""
+        out = self.render_outputs(cam, params, planes=("linear",) + FEATURE_PLANES, device=device, photon_pass=photon_pass)
+        denoise_kw.setdefault("gamma", params.gamma)
+        out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
+                                                       rgb8=True, device=device, **denoise_kw)
         return out
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,

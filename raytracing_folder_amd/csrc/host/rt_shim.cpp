@@ -14,6 +14,7 @@ void RenderImage::Init(int w, int h)
     zbufferImg.clear(); sampleCountImg.clear();
     if (linearEnabled) linear.assign((size_t)w * h * 3, 0.0f);
     if (featuresEnabled) { featuresEnabled = false; EnableFeatures(); }
+    denoised.clear(); denoisedImg.clear();
     finalPixels = 0;
 }
 
@@ -48,6 +49,23 @@ void RenderImage::EnableLinear()
 {
     if (!linearEnabled) linear.assign((size_t)width * height * 3, 0.0f);
     linearEnabled = true;
+}
+
+bool RenderImage::Denoise(const rt_denoise_params *params, int device)
+{
+    denoised.clear(); denoisedImg.clear();
+    if (!linearEnabled || !featuresEnabled) { denoiseError = "Denoise() needs EnableLinear() and EnableFeatures() before the render"; return false; }
+    if (!jobs.empty()) { denoiseError = "Denoise() while the render is still running"; return false; }
+    rt_denoise_params defaults;
+    rt_denoise_default_params(&defaults);
+    std::vector<float> out((size_t)width * height * 3);
+    std::vector<uint8_t> out8((size_t)width * height * 3);
+    const rt_denoise_planes pl = {(uint32_t)sizeof(rt_denoise_planes), linear.data(), normals.data(), albedo.data(), zbuffer.data(),
+                                  objectIds.data(), out.data(), out8.data()};
+    if (rt_denoise(device, width, height, params ? params : &defaults, &pl) != RT_OK) { denoiseError = rt_last_error(); return false; }
+    denoised.swap(out); denoisedImg.swap(out8);
+    denoiseError.clear();
+    return true;
 }
 
 int RenderImage::GetNumRenderedPixels() const

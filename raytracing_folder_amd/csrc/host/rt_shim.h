@@ -26,6 +26,10 @@ class RenderImage {
     std::vector<float> normals, albedo, alpha;
     std::vector<int32_t> objectIds;
     bool featuresEnabled = false;
+    // Denoise(): the a-trous filter's outputs -- linear float RGB and its gamma-encoded Color24 image
+    std::vector<float> denoised;
+    std::vector<uint8_t> denoisedImg;
+    std::string denoiseError;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -56,6 +60,16 @@ public:
     int32_t *GetObjectIds() { return featuresEnabled ? objectIds.data() : nullptr; }
     static void ObjectIdColor(int32_t id, uint8_t rgb[3]);      // a fixed colour per id; -1 (no object) is black
     bool SaveFeatureImages(const char *prefix) const;
+    // The denoiser of rt_mi355x.h ("denoising") over the finished frame: the linear plane filtered under the guidance of the
+    // normal, albedo, z and object-id planes, on `device`.  Needs EnableLinear() AND EnableFeatures() before the render;
+    // without them, or when the GPU call fails, it returns false and DenoiseError() says why.  params == NULL: the defaults
+    // of rt_denoise_default_params.  The getters are NULL and the Save functions fail until a Denoise() has succeeded.
+    bool Denoise(const rt_denoise_params *params = nullptr, int device = 0);
+    const std::string &DenoiseError() const { return denoiseError; }
+    float *GetDenoisedPixels() { return denoised.empty() ? nullptr : denoised.data(); }         // linear float RGB
+    uint8_t *GetDenoisedImage() { return denoisedImg.empty() ? nullptr : denoisedImg.data(); }  // Color24 after gamma
+    bool SaveDenoisedImage(const char *filename) const { return !denoised.empty() && WritePFM(filename, denoised.data(), width, height); }    // PFM
+    bool SaveDenoisedPNG(const char *filename) const { return !denoisedImg.empty() && WritePNG(filename, denoisedImg.data(), width, height, 3); }
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

@@ -280,10 +280,13 @@ struct rt_job {
 };
 
 // ---- scene store ---------------------------------------------------------------------------------------
+static std::atomic<int> g_live_scenes{0};
+static void denoise_release_all();         // the denoiser's per-device scratch (below, "denoising")
 extern "C" rt_status rt_scene_create(rt_scene **out)
 {
     if (!out) return fail(RT_ERR_ARG, "rt_scene_create: out is NULL");
     *out = new rt_scene;
+    g_live_scenes.fetch_add(1);
     return RT_OK;
 }
 
@@ -298,6 +301,7 @@ extern "C" void rt_scene_destroy(rt_scene *s)
         delete d;
     }
     delete s;
+    if (g_live_scenes.fetch_sub(1) == 1) denoise_release_all();     // the last scene takes the denoiser's per-device scratch with it
 }
 
 static rt_status check_idle(rt_scene *s, const char *who)
@@ -2045,6 +2049,117 @@ extern "C" rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream,
     if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_tiles_unpack_linear_device: the linear plane is required");
     return tiles_unpack("rt_tiles_unpack_linear_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
                         rgb8_dev, z_dev, count_dev, rgb_linear_dev);
+}
+
+// ---- denoising ----------------------------------------------------------------------------------------------------------
+// rt_denoise_device has no scene, and the device state above belongs to one: the denoiser's scratch is held per device for the
+// process -- the two ping-pong colour buffers and the guide buffer in one allocation, grown on demand.  Every denoise on a
+// device uses the same scratch, so a call orders its stream behind the previous call's `done` event.  Released with the last
+// scene (rt_scene_destroy), like the per-device buffers of the scenes.
+struct DenoiseDevice { DevBuf scratch; hipEvent_t done = nullptr; bool pending = false; };
+static std::mutex g_denoise_mu;
+static std::vector<std::pair<int, DenoiseDevice>> g_denoise;        // (device, its scratch); under g_denoise_mu
+
+static void denoise_release_all()
+{
+    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    for (auto &d : g_denoise) {
+        if (hipSetDevice(d.first) != hipSuccess) continue;
+        d.second.scratch.release();                                 // hipFree waits for the kernels that still use it
+        if (d.second.done) (void)hipEventDestroy(d.second.done);
+    }
+    g_denoise.clear();
+}
+
+extern "C" void rt_denoise_default_params(rt_denoise_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->levels = 5; p->sigma_color = 1.0f; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
+}
+
+#define RT_DENOISE_MAX_PIXELS (1ll << 30)       /* 48 GiB of scratch; keeps the one-dimensional grid of 32 x 8 tiles far below 2^31 */
+// everything that can be refused without a device, for both entry points
+static rt_status denoise_check(const char *name, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *pl)
+{
+    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
+    if (p->struct_size != (uint32_t)sizeof(rt_denoise_params))
+        return fail(RT_ERR_ARG, "%s: rt_denoise_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_denoise_params));
+    if (pl->struct_size != (uint32_t)sizeof(rt_denoise_planes))
+        return fail(RT_ERR_ARG, "%s: rt_denoise_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_denoise_planes));
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, w, h);
+    if (p->levels < 1 || p->levels > 8) return fail(RT_ERR_ARG, "%s: levels is %d, allowed 1..8", name, p->levels);
+    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_depth, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_color, sigma_normal, sigma_depth and gamma must be positive and finite", name);
+    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
+        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
+    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, w, h);
+    return RT_OK;
+}
+
+// k_resolve's exponent is (float)(1.0 / gamma) of a DOUBLE gamma (rt_params); rt_denoise_params carries a float.  Taking the
+// double that prints like that float to 7 digits gives 2.2 for 2.2f, hence the exponent a default render used.
+static float denoise_inv_gamma(float gamma)
+{
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.7g", (double)gamma);
+    return (float)(1.0 / strtod(buf, nullptr));
+}
+
+static rt_status denoise_on_device(const char *name, int device, hipStream_t st, int32_t w, int32_t h, const rt_denoise_params *p,
+                                   const rt_denoise_planes *pl, int sync)
+{
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+    HIP_TRY(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    DenoiseDevice *D = nullptr;
+    for (auto &d : g_denoise) if (d.first == device) D = &d.second;
+    if (!D) { g_denoise.emplace_back(device, DenoiseDevice()); D = &g_denoise.back().second; }
+    const size_t n = (size_t)w * (size_t)h;
+    rt_status rs = D->scratch.ensure(n * RT_DENOISE_SCRATCH_PER_PIXEL);     // growing frees the old one, which waits for its users
+    if (rs) return rs;
+    if (!D->done) HIP_TRY(hipEventCreateWithFlags(&D->done, hipEventDisableTiming));
+    if (D->pending) HIP_TRY(hipStreamWaitEvent(st, D->done, 0));
+    DenoiseRequest R = {};
+    R.width = w; R.height = h; R.levels = p->levels;
+    R.sigma_color = p->sigma_color; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth; R.inv_gamma = denoise_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id;
+    R.out_linear = pl->out_linear; R.out_rgb8 = pl->out_rgb8;
+    R.color[0] = (float4 *)D->scratch.p; R.color[1] = R.color[0] + n; R.guide = R.color[1] + n;
+    rtk_launch_denoise_frame(st, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(D->done, st));
+    D->pending = true;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); D->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_denoise_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                                       const rt_denoise_planes *device_planes, int sync)
+{
+    rt_status st = denoise_check("rt_denoise_device", w, h, p, device_planes);
+    if (st) return st;
+    return denoise_on_device("rt_denoise_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes)
+{
+    rt_status st = denoise_check("rt_denoise", w, h, p, host_planes);
+    if (st) return st;
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_denoise: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)w * (size_t)h;
+    ScopedDevBuf rgb, normal, albedo, z, id, rgb8;                  // the result is written in place into rgb
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
+        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4))) return st;
+    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
+    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
+    rt_denoise_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
+                             (const int32_t *)id.p, (float *)rgb.p, (uint8_t *)rgb8.p};
+    if ((st = denoise_on_device("rt_denoise", device, nullptr, w, h, p, &dev, 1))) return st;
+    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 extern "C" rt_status rt_render_check(rt_scene *s, int device)

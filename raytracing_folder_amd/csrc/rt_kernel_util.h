@@ -1,4 +1,4 @@
-// rt_kernel_util.h -- the few device helpers that both kernel translation units (rt_kernels.hip, rt_gather.hip) use.
+// rt_kernel_util.h -- the few device helpers that more than one kernel translation unit (rt_kernels.hip, rt_gather.hip, rt_denoise.hip) uses.
 // Device code only; nothing here is host-callable.  Not a general utility header: a helper moves here when a second file needs it.
 #ifndef RT_KERNEL_UTIL_H
 #define RT_KERNEL_UTIL_H
@@ -27,6 +27,18 @@ __device__ __forceinline__ unsigned long long fx_encode(float c)
 __device__ __forceinline__ void fx_add(unsigned long long *dst, float r, float g, float b)
 {
     atomicAdd(dst, fx_encode(r)); atomicAdd(dst + 1, fx_encode(g)); atomicAdd(dst + 2, fx_encode(b));    // global_atomic_add_u64
+}
+
+// One channel of the Color24 pack (cyColor.h:245-246) as k_resolve and the denoiser's RGB8 output apply it after gamma:
+// r * 255 truncated, clamped to [0, 255], NaN as 0.
+__device__ __forceinline__ uint8_t float_to_byte(float r)
+{
+    const float s = r * 255;
+    if (!(s == s)) return 0;
+    if (s <= -2147483648.0f) return 0;
+    if (s >= 2147483647.0f) return 255;
+    const int v = (int)s;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
 #endif

@@ -1859,17 +1859,7 @@ void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs
 //   phase 0: after the first batch (samples 0..min-1): either finalise or list the pixel
 //   phase 1: after the second batch: finalise listed pixels with all samples
 // ------------------------------------------------------------------------------------------------
-// (ResolveArgs: rt_launch.h)
-
-__device__ __forceinline__ uint8_t float_to_byte(float r)
-{
-    const float s = r * 255;
-    if (!(s == s)) return 0;
-    if (s <= -2147483648.0f) return 0;
-    if (s >= 2147483647.0f) return 255;
-    const int v = (int)s;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
+// (ResolveArgs: rt_launch.h; float_to_byte: rt_kernel_util.h)
 
 #ifndef RT_RESOLVE_TILE
 #define RT_RESOLVE_TILE 8            // samples per pixel staged through LDS at a time

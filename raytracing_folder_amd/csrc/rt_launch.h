@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip): every rtk_* function, the requests they take and the records they exchange.  All four files
-// include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
+// rt_photon_build.hip, rt_denoise.hip): every rtk_* function, the requests they take and the records they exchange.  All five
+// files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -75,6 +75,18 @@ struct UnpackRequest {
     uint8_t *rgb8; float *z; uint8_t *count; float *rgb_linear;
 };
 
+// One denoise of a width x height frame (rt_denoise.hip; the definition: rt_mi355x.h, "denoising").  The planes are the caller's
+// device pointers (object_id and out_rgb8 may be NULL; out_linear may be rgb_linear), the sigmas are validated by the caller.
+// color[0], color[1] and guide are the per-device scratch, width * height float4 each (RT_DENOISE_SCRATCH_PER_PIXEL bytes a pixel).
+#define RT_DENOISE_SCRATCH_PER_PIXEL 48
+struct DenoiseRequest {
+    int width, height, levels;
+    float sigma_color, sigma_normal, sigma_depth, inv_gamma;
+    const float *rgb_linear, *normal, *albedo, *z; const int32_t *object_id;
+    float *out_linear; uint8_t *out_rgb8;
+    float4 *color[2], *guide;
+};
+
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -110,6 +122,10 @@ void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs
 // ---- rt_gather.hip: the photon gather ------------------------------------------------------------------------------------
 // k_gather as a persistent grid of `blocks` workgroups
 void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks);
+
+// ---- rt_denoise.hip: the image-space denoiser ----------------------------------------------------------------------------
+// k_denoise_prepare, then k_atrous once per level (the last one remodulates and writes the caller's planes), all on `st`
+void rtk_launch_denoise_frame(hipStream_t st, const DenoiseRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

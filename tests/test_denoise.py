@@ -1,0 +1,376 @@
+"""The GPU denoiser: an edge-avoiding a-trous wavelet filter on albedo-demodulated linear colour, guided by the first-hit
+planes (rt_denoise, rt_denoise_device, k_denoise_prepare / k_atrous, capi.denoise, Scene.render_denoised,
+rt::RenderImage::Denoise).  The reference has no denoiser, so the yardstick is `ref_denoise` below: a float64 numpy
+transcription of the definition in include/rt_mi355x.h ("denoising"), itself checked on the CPU.  The GPU is held to the
+project's colour gate against it, |got - want| <= 2e-5 |want| + 1e-6 on every valid pixel."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from raytracing_folder_amd import capi
+from tests import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIG = np.float32(1e30)
+H1 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
+
+
+# ---- the reference filter -------------------------------------------------------------------------------------
+def ref_denoise(lin, normal, albedo, z, ids=None, levels=5, sigma_color=1.0, sigma_normal=0.3, sigma_depth=0.05):
+    """float64 transcription of the definition; the sigmas are taken as the float32 values the ABI carries"""
+    sc, sn, sd = (float(np.float32(v)) for v in (sigma_color, sigma_normal, sigma_depth))
+    h, w = z.shape
+    valid = (ids >= 0) if ids is not None else (z < BIG)
+    a = np.where(albedo > np.float32(1e-3), albedo, np.float32(1)).astype(np.float64)
+    lin64, n64, z64 = lin.astype(np.float64), normal.astype(np.float64), z.astype(np.float64)
+    d = lin64 / a
+    Y, X = np.mgrid[0:h, 0:w]
+    with np.errstate(all="ignore"):
+        for i in range(levels):
+            s = 1 << i
+            num, den = np.zeros((h, w, 3)), np.zeros((h, w))
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    qy, qx = Y + s * dy, X + s * dx
+                    ok = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+                    qy, qx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
+                    ok &= valid[qy, qx]
+                    if ids is not None:
+                        ok &= ids[qy, qx] == ids
+                    dq = d[qy, qx]
+                    if dx == 0 and dy == 0:
+                        t = np.zeros((h, w))
+                    else:
+                        t = (((dq - d) ** 2).sum(-1) / (sc * 2.0 ** -i) ** 2 + ((n64[qy, qx] - n64) ** 2).sum(-1) / sn ** 2 +
+                             ((z64[qy, qx] - z64) / (sd * np.maximum(z64[qy, qx], z64))) ** 2)
+                    wgt = H1[dx + 2] * H1[dy + 2] * np.exp(-t)
+                    ok &= np.isfinite(wgt) & np.isfinite(dq).all(-1)
+                    num += np.where(ok[..., None], wgt[..., None] * dq, 0.0)
+                    den += np.where(ok, wgt, 0.0)
+            centre = valid & np.isfinite(d).all(-1)
+            d = np.where(centre[..., None], num / np.where(den > 0, den, 1.0)[..., None], d)
+        return np.where(valid[..., None], d * a, lin64)
+
+
+def synthetic(w, h, seed=0, noise=0.3):
+    """the issue's input at any size: two ids split at x = 20, an invalid corner block, three normal regions, a 3 x 3 patch of
+    zero albedo, sloped z, colour = clean x (1 + noise N(0, 1)).  Returns (planes dict, clean colour)."""
+    rng = np.random.default_rng(seed)
+    Y, X = np.mgrid[0:h, 0:w]
+    ids = np.where(X < 20, 3, 4).astype(np.int32)
+    z = (5.0 + 0.05 * X + 0.1 * Y).astype(np.float32)
+    ih, iw = min(4, h // 2), min(5, w // 2)
+    ids[:ih, :iw] = -1
+    z[:ih, :iw] = BIG
+    normal = np.zeros((h, w, 3), np.float32)
+    normal[...] = (0, 0, 1)
+    normal[Y >= h // 3] = (0, 1, 0)
+    normal[Y >= 2 * h // 3] = (0.6, 0, 0.8)
+    albedo = np.where((X < 20)[..., None], np.float32([0.8, 0.5, 0.3]), np.float32([0.2, 0.6, 0.9])).astype(np.float32)
+    albedo[10:13, 25:28] = 0                                    # a mirror: kd = 0
+    light = (0.6 + 0.3 * np.sin(X / 5.0) * np.cos(Y / 7.0))[..., None]
+    clean = (np.where(albedo > 1e-3, albedo, 0.35) * light).astype(np.float32)
+    lin = (clean * (1 + noise * rng.normal(0, 1, (h, w, 3)))).astype(np.float32)
+    lin[:ih, :iw] = (0.25, 0.5, 0.75)                           # the background
+    return dict(linear=lin, normal=normal, albedo=albedo, z=z, object_id=ids), clean
+
+
+def _valid(pl, with_ids=True):
+    return pl["object_id"] >= 0 if with_ids else pl["z"] < BIG
+
+
+def _gate(got, want, valid, what=""):
+    """the colour gate on every valid pixel; prints the measured maximum of |got - want| / (2e-5 |want| + 1e-6)"""
+    with np.errstate(invalid="ignore"):                         # pixels outside `valid` may hold NaN or inf
+        err = np.abs(got.astype(np.float64) - want)[valid]
+    tol = (2e-5 * np.abs(want) + 1e-6)[valid]
+    rel = (err / np.maximum(np.abs(want[valid]), 1e-30)).max() if err.size else 0.0
+    print(f"denoise {what}: max |got-want| = {err.max() if err.size else 0:.3e}, max relative = {rel:.3e}, "
+          f"worst err/tolerance = {(err / tol).max() if err.size else 0:.4f}")
+    assert (err <= tol).all(), (what, float((err / tol).max()))
+
+
+# ---- CPU: the ABI ---------------------------------------------------------------------------------------------
+def test_new_symbols_and_struct_layouts():
+    L = capi.lib()
+    for name in ("rt_denoise_default_params", "rt_denoise_device", "rt_denoise"):
+        assert hasattr(L, name), name
+    assert L.rt_abi_version() == 4
+    assert C.sizeof(capi.DenoiseParams) == 24
+    assert [f[0] for f in capi.DenoiseParams._fields_] == ["struct_size", "levels", "sigma_color", "sigma_normal", "sigma_depth", "gamma"]
+    # uint32 + padding, then seven pointers
+    assert C.sizeof(capi.DenoisePlanes) == 8 + 7 * C.sizeof(C.c_void_p) == 64
+    assert capi.DenoisePlanes().struct_size == 64
+    assert [f[0] for f in capi.DenoisePlanes._fields_] == ["struct_size", "rgb_linear", "normal", "albedo", "z", "object_id", "out_linear", "out_rgb8"]
+
+
+def test_default_params():
+    p = capi.DenoiseParams()
+    capi.lib().rt_denoise_default_params(C.byref(p))
+    assert p.struct_size == 24 and p.levels == 5
+    assert (p.sigma_color, p.sigma_normal, p.sigma_depth, p.gamma) == tuple(float(np.float32(v)) for v in (1.0, 0.3, 0.05, 2.2))
+    capi.lib().rt_denoise_default_params(None)                  # ignored
+    assert capi.denoise_params(levels=3, sigma_depth=0.5).levels == 3
+    with pytest.raises(TypeError):
+        capi.denoise_params(sigma=1.0)
+
+
+def test_argument_checks_come_before_any_gpu_call():
+    L = capi.lib()
+    buf = np.zeros(8 * 8 * 3, np.float32)
+    ptr = buf.ctypes.data
+    full = dict(rgb_linear=ptr, normal=ptr, albedo=ptr, z=ptr, object_id=ptr, out_linear=ptr, out_rgb8=ptr)
+
+    def calls(p, pl, w=8, h=8):
+        pp, ppl = (C.byref(p) if p is not None else None), (C.byref(pl) if pl is not None else None)
+        return (L.rt_denoise(0, w, h, pp, ppl), L.rt_denoise_device(0, None, w, h, pp, ppl, 1))
+
+    ARG = (-1, -1)
+    assert calls(None, capi.DenoisePlanes(**full)) == ARG and calls(capi.denoise_params(), None) == ARG
+    for size in (0, 20, 23, 28):
+        p = capi.denoise_params()
+        p.struct_size = size
+        assert calls(p, capi.DenoisePlanes(**full)) == ARG and b"struct_size" in L.rt_last_error()
+    for size in (0, 56, 63, 72):
+        pl = capi.DenoisePlanes(**full)
+        pl.struct_size = size
+        assert calls(capi.denoise_params(), pl) == ARG and b"struct_size" in L.rt_last_error()
+    for w, h in ((0, 8), (8, 0), (-3, 8), (8, -1)):
+        assert calls(capi.denoise_params(), capi.DenoisePlanes(**full), w, h) == ARG
+    for levels in (0, -1, 9, 100):
+        assert calls(capi.denoise_params(levels=levels), capi.DenoisePlanes(**full)) == ARG and b"levels" in L.rt_last_error()
+    for name in ("sigma_color", "sigma_normal", "sigma_depth"):
+        for bad in (0.0, -1.0, float("nan"), float("inf")):
+            assert calls(capi.denoise_params(**{name: bad}), capi.DenoisePlanes(**full)) == ARG, (name, bad)
+    for missing in ("rgb_linear", "normal", "albedo", "z", "out_linear"):
+        planes = dict(full)
+        planes[missing] = None
+        assert calls(capi.denoise_params(), capi.DenoisePlanes(**planes)) == ARG and b"required" in L.rt_last_error()
+    assert calls(capi.denoise_params(), capi.DenoisePlanes(**full), 1 << 16, 1 << 15) == (-6, -6)         # RT_ERR_LIMIT
+    if capi.device_count() == 0:                                # a good call gets as far as looking for the device
+        assert calls(capi.denoise_params(), capi.DenoisePlanes(**full)) == (-3, -3)
+
+
+def _build_shim_driver(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_denoise_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_denoise_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+def test_shim_driver_builds_against_the_header(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+# ---- CPU: the reference itself --------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def planes():
+    pl, clean = synthetic(37, 23)
+    for a in pl.values():
+        a.setflags(write=False)
+    want = ref_denoise(pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"])
+    want.setflags(write=False)
+    return pl, clean, want
+
+
+def test_reference_passes_invalid_pixels_through_and_reduces_the_noise(planes):
+    pl, clean, want = planes
+    valid = _valid(pl)
+    assert (~valid).sum() == 20 and (want[~valid] == pl["linear"][~valid].astype(np.float64)).all()
+    rmse = lambda a: float(np.sqrt(((a[valid] - clean[valid]) ** 2).mean()))
+    assert rmse(want) < 0.5 * rmse(pl["linear"]), (rmse(pl["linear"]), rmse(want))
+    # a tap on an invalid pixel is skipped whatever it holds
+    lin2 = pl["linear"].copy()
+    lin2[~valid] = 1e6
+    assert (ref_denoise(lin2, pl["normal"], pl["albedo"], pl["z"], pl["object_id"])[valid] == want[valid]).all()
+
+
+def test_reference_returns_a_constant_colour_constant():
+    pl, _ = synthetic(19, 11, noise=0.0)
+    lin = (pl["albedo"] * np.float32(0.5)).astype(np.float32)
+    lin[pl["albedo"] <= 1e-3] = 0.5
+    for ids in (pl["object_id"], None):
+        out = ref_denoise(lin, pl["normal"], pl["albedo"], pl["z"], ids, levels=3)
+        valid = _valid(pl, ids is not None)
+        assert np.abs(out - lin)[valid].max() < 1e-12           # d = 0.5 everywhere: any normalised average of it is 0.5
+
+
+def test_reference_lets_nothing_cross_an_id_edge():
+    h, w = 9, 24
+    ids = np.where(np.mgrid[0:h, 0:w][1] < 11, 6, 7).astype(np.int32)
+    rng = np.random.default_rng(5)
+    lin = rng.uniform(0.2, 0.8, (h, w, 3)).astype(np.float32)
+    one = np.ones((h, w, 3), np.float32)
+    z = np.full((h, w), 4, np.float32)
+    base = ref_denoise(lin, one, one, z, ids)
+    lin2 = lin.copy()
+    lin2[ids == 7] += 10                                        # whatever the right half holds ...
+    assert (ref_denoise(lin2, one, one, z, ids)[ids == 6] == base[ids == 6]).all()      # ... the left half does not move
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------
+def _run(pl, with_ids=True, rgb8=False, **kw):
+    return capi.denoise(pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"] if with_ids else None, rgb8=rgb8, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_ids,levels", [(True, 5), (False, 5), (True, 1)])
+def test_against_the_reference_37x23(planes, with_ids, levels):
+    """Neither side a multiple of the 32 x 8 workgroup, step 16 puts most taps outside.  Measured on the MI355X: DESIGN 3."""
+    pl, _, want = planes
+    if not (with_ids and levels == 5):
+        want = ref_denoise(pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"] if with_ids else None, levels=levels)
+    got = _run(pl, with_ids, levels=levels)
+    valid = _valid(pl, with_ids)
+    _gate(got, want, valid, f"37x23 ids={with_ids} levels={levels}")
+    assert got[~valid].tobytes() == pl["linear"][~valid].tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 1), (5, 3)])
+def test_against_the_reference_at_tiny_sizes(w, h):
+    """every off-centre tap of the higher levels is outside the image"""
+    pl, _ = synthetic(w, h, seed=w)
+    for with_ids in (True, False):
+        want = ref_denoise(pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"] if with_ids else None)
+        _gate(_run(pl, with_ids), want, _valid(pl, with_ids), f"{w}x{h} ids={with_ids}")
+
+
+@pytest.mark.gpu
+def test_invalid_and_nan_pixels_pass_through(planes):
+    pl, _, _ = planes
+    lin = pl["linear"].copy()
+    lin[~_valid(pl)] = np.float32([np.nan, -1e30, 7.5])[None]   # invalid pixels hold anything
+    lin[12, 8] = (np.nan, 0.3, 0.2)                             # valid pixels whose colour is not finite
+    lin[5, 30, 1] = np.inf
+    bad = np.zeros(lin.shape[:2], bool)
+    bad[12, 8] = bad[5, 30] = True
+    q = dict(pl, linear=lin)
+    for with_ids in (True, False):
+        got = _run(q, with_ids)
+        valid = _valid(pl, with_ids)
+        assert got[~valid].tobytes() == lin[~valid].tobytes()   # bit for bit, NaN payloads included
+        assert got[bad].tobytes() == lin[bad].tobytes()
+        assert np.isfinite(got[valid & ~bad]).all()             # and they reach no neighbour
+        want = ref_denoise(lin, pl["normal"], pl["albedo"], pl["z"], pl["object_id"] if with_ids else None)
+        _gate(got, want, valid & ~bad, f"pass-through ids={with_ids}")
+
+
+@pytest.mark.gpu
+def test_an_id_edge_is_never_crossed():
+    """two objects whose ids differ by one, two noise-free colours, the same normal and depth: only the id plane separates
+    them, and the output is the input"""
+    h, w = 13, 41
+    ids = np.where(np.mgrid[0:h, 0:w][1] < 17, 6, 7).astype(np.int32)
+    lin = np.where((ids == 6)[..., None], np.float32([0.7, 0.2, 0.1]), np.float32([0.1, 0.3, 0.9])).astype(np.float32)
+    one = np.ones((h, w, 3), np.float32)
+    z = np.full((h, w), 4, np.float32)
+    got = capi.denoise(lin, one, one, z, ids)
+    _gate(got, lin.astype(np.float64), np.ones((h, w), bool), "id edge")
+    blurred = capi.denoise(lin, one, one, z, None, sigma_color=10.0)     # without the plane the two sides do mix
+    assert np.abs(blurred - lin).max() > 0.05
+
+
+@pytest.mark.gpu
+def test_determinism_aliasing_and_the_device_entry(planes):
+    import torch
+    pl, _, _ = planes
+    h, w = pl["z"].shape
+    first, first8 = _run(pl, rgb8=True)
+    again, again8 = _run(pl, rgb8=True)
+    assert first.tobytes() == again.tobytes() and first8.tobytes() == again8.tobytes()
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(device=dev)
+    t = {k: torch.from_numpy(np.array(v)).to(dev) for k, v in pl.items()}
+    out, out8 = torch.zeros((h, w, 3), dtype=torch.float32, device=dev), torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    ptrs = dict(normal_ptr=t["normal"].data_ptr(), albedo_ptr=t["albedo"].data_ptr(), z_ptr=t["z"].data_ptr(),
+                object_id_ptr=t["object_id"].data_ptr())
+    # on the caller's stream, without waiting: the stream's synchronisation is what completes it
+    capi.denoise_device(0, side.cuda_stream, w, h, linear_ptr=t["linear"].data_ptr(), out_ptr=out.data_ptr(), rgb8_ptr=out8.data_ptr(),
+                        sync=False, **ptrs)
+    # ... and in place behind it on the same stream (the scratch is shared: the second call waits for the first)
+    inplace = t["linear"].clone()
+    capi.denoise_device(0, side.cuda_stream, w, h, linear_ptr=inplace.data_ptr(), out_ptr=inplace.data_ptr(), sync=False, **ptrs)
+    side.synchronize()
+    assert out.cpu().numpy().tobytes() == first.tobytes() and out8.cpu().numpy().tobytes() == first8.tobytes()
+    assert inplace.cpu().numpy().tobytes() == first.tobytes()
+    assert t["linear"].cpu().numpy().tobytes() == pl["linear"].tobytes()        # an input that is not the output is left alone
+
+
+def _encode(lin, gamma):
+    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte), as tests/test_linear_output.py has it"""
+    with np.errstate(all="ignore"):
+        g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
+        s = (g * np.float32(255)).astype(np.float32)
+    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
+    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
+
+
+def _assert_rgb8_encodes(lin, rgb, gamma):
+    d = np.abs(_encode(lin, gamma).astype(int) - rgb.astype(int))
+    assert (d == 0).mean() >= 0.999, (d != 0).sum()             # a host powf one ulp off the device's moves a byte at a boundary
+    assert d.max() <= 1
+
+
+@pytest.mark.gpu
+def test_rgb8_is_k_resolves_rule_applied_to_the_denoised_plane(planes):
+    pl, _, _ = planes
+    for gamma in (2.2, 1.0):
+        out, out8 = _run(pl, rgb8=True, gamma=gamma)
+        assert out8.dtype == np.uint8 and out8.shape == out.shape
+        _assert_rgb8_encodes(out, out8, gamma)
+    assert _run(pl).tobytes() == out.tobytes()                  # asking for the bytes moves nothing in the floats
+
+
+@pytest.mark.gpu
+def test_denoising_a_real_4spp_render_brings_it_closer_to_64spp():
+    """cornell_gi.xml (live GI, the noisy model) at 96 x 72: 4 spp denoised against 64 spp.  Measured on the MI355X: DESIGN 3."""
+    s, cam = scenes.load_cornell_gi(96, 72)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    common = dict(shade_model=capi.SHADE_P12, bounce=8, hemisphere_sample=1, photon_count=0)
+    noisy_p = capi.default_params(min_sample=4, max_sample=8, threshold=1e30, seed=1212, **common)        # no variance exceeds it: no second batch
+    ref_p = capi.default_params(min_sample=64, max_sample=64, threshold=-1.0, seed=77, **common)
+    d = s.render_denoised(cam, noisy_p)
+    assert (d["count"] == 0).all() and d["progress"] == 96 * 72
+    ref = s.render_outputs(cam, ref_p, planes=("linear", "object_id"))
+    valid = (d["object_id"] >= 0) & (ref["object_id"] >= 0)
+    assert valid.mean() > 0.9
+    rmse = lambda a: float(np.sqrt(((a[valid].astype(np.float64) - ref["linear"][valid]) ** 2).mean()))
+    noisy, den = rmse(d["linear"]), rmse(d["denoised"])
+    print(f"denoise cornell_gi 96x72: RMSE to 64 spp, 4 spp {noisy:.5f} -> denoised {den:.5f} (ratio {den / noisy:.3f})")
+    assert den < noisy
+    # the denoise changes nothing else: the render's planes are those of a plain render_outputs
+    plain = s.render_outputs(cam, noisy_p, planes=("linear",) + capi.FEATURE_PLANES)
+    for name in ("rgb", "z", "count", "linear") + capi.FEATURE_PLANES:
+        assert d[name].tobytes() == plain[name].tobytes(), name
+    assert d["denoised"].dtype == np.float32 and d["denoised"].shape == (72, 96, 3)
+    _assert_rgb8_encodes(d["denoised"], d["denoised_rgb"], noisy_p.gamma)
+    miss = d["object_id"] < 0
+    assert d["denoised"][miss].tobytes() == d["linear"][miss].tobytes()
+    assert d["denoised_rgb"][miss].tobytes() == d["rgb"][miss].tobytes()       # untouched pixels: the bytes k_resolve wrote
+
+
+@pytest.mark.gpu
+def test_cpp_shim_denoise_equals_capi_denoise_of_the_same_planes(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    prefix = str(tmp_path / "f")
+    r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert r.stdout.split()[1] == str(64 * 48)
+    lin, normal, albedo = (capi.image_read_pfm(prefix + f"_{n}.pfm") for n in ("linear", "normal", "albedo"))
+    z = capi.image_read_pfm1(prefix + "_z.pfm")
+    ids = np.fromfile(prefix + "_id.i32", "<i4").reshape(48, 64)
+    assert (ids >= 0).any() and ((ids < 0) == (z == BIG)).all()
+    want, want8 = capi.denoise(lin, normal, albedo, z, ids, rgb8=True)
+    got = capi.image_read_pfm(prefix + "_denoised.pfm")
+    assert got.tobytes() == want.tobytes()
+    assert capi.image_read_rgb(prefix + "_denoised.png").tobytes() == want8.tobytes()
+    assert np.abs(got - lin).max() > 0                          # it did filter
