@@ -33,7 +33,6 @@ static int gather_blocks()
     return n;
 }
 static const size_t STATS_BYTES = (size_t)ST_COUNT * RT_STAT_STRIDE * 8;    // the statistics block: counters RT_STAT_STRIDE apart (rt_dev.h)
-#define GATHER_BLOCKS gather_blocks()
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -111,6 +110,19 @@ struct ScopedDevBuf : DevBuf {
     ~ScopedDevBuf() { release(); }
 };
 
+// an owned hipEvent_t: destroyed with its owner, handed on by a move
+namespace {
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }      // once per Event
+    operator hipEvent_t() const { return e; }
+};
+}
+
 struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
 
 // Per-chunk working set.  A frame's chunks alternate between RT_STREAMS of these, each on its own HIP
@@ -156,13 +168,17 @@ struct DeviceState {
     // stats: `last_done` is recorded at its join and every later call orders its own stream behind it
     hipEvent_t last_done = nullptr;
     bool last_pending = false;
-    bool last_pipelined = false;        // the render in flight ran every slot on the library's own streams (render_tiles_once)
+    bool last_pipelined = false;        // the render in flight ran every slot on the library's own streams (RenderAttempt::plan_chunks, fork_slots)
     uint64_t frame_seq = 0;             // rotates the slots from one pipelined frame to the next
     bool async_overflow = false;        // an asynchronous render dropped rays and nobody has collected that verdict yet (rt_render_check does)
     // How full the ray / photon-query queues of the last renders got, per sample of a chunk (device-side peaks,
-    // rt_stats.peak_*): the next render of the same kind sizes its queues from that instead of the 2^bounce worst case.
-    struct QueueHistory { bool valid = false; int model = -1, bounce = -1, fan = -1; bool photons = false, caustic = false;
-                          double rays_per_sample = 0, queries_per_sample = 0; } qhist;
+    // rt_stats.peak_*): the next render of the same kind sizes its queues from that instead of the 2^bounce worst case
+    // (choose_queue_sizing / record_queue_peaks below).
+    struct QueueKey {                   // what makes two renders "of the same kind"
+        int model = -1, bounce = -1, fan = -1; bool photons = false, caustic = false;
+        bool operator==(const QueueKey &o) const { return model == o.model && bounce == o.bounce && fan == o.fan && photons == o.photons && caustic == o.caustic; }
+    };
+    struct QueueHistory { bool valid = false; QueueKey key; double rays_per_sample = 0, queries_per_sample = 0; } qhist;
     bool qhist_used = false;            // the render in flight (or last finished) was sized from qhist / the first-frame guess
     // scratch for the single-stage entry points
     DevBuf t_in, t_out[6];
@@ -180,6 +196,58 @@ struct DeviceState {
         last_done = nullptr; last_pending = false;
     }
 };
+
+// Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
+// half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
+// if that ever overflows, a synchronous render
+// is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
+// library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
+struct QueueSizing {
+    DeviceState::QueueKey key;
+    bool hist_ok = false;                       // the device's history is of this kind of render
+    double ray_factor = 0, query_factor = 0;    // queue entries per sample to provide (ensure_workspace); 0 = worst case
+};
+// The factors for the render that is about to start; can_retry: the library itself can render it again when they prove too small.
+static QueueSizing choose_queue_sizing(DeviceState *D, const rt_params &p, bool worst_case, bool can_retry)
+{
+    QueueSizing q;
+    q.key.model = p.shade_model; q.key.bounce = p.bounce;
+    // P12: a diffuse hit spawns hemisphere rays on top of the reflection/refraction pair; in practice one
+    // of the three classes dominates per material, so the queues are sized for a fan-out of 2 and an
+    // overflow is reported as an error rather than silently dropped
+    q.key.fan = p.shade_model == RT_SHADE_P12 && p.hemisphere_sample > 1 ? 1 + p.hemisphere_sample : 2;
+    q.key.photons = D->scene.pm.n_leaves != 0; q.key.caustic = p.caustic_k > 0 && D->scene.cm.n_leaves != 0;
+    const DeviceState::QueueHistory &H = D->qhist;
+    q.hist_ok = H.valid && H.key == q.key;
+    if (!worst_case && getenv("RT_QUEUE_WORST_CASE") == nullptr) {
+        // floors: how many rays k_wavefront cannot keep in LDS depends on timing, and a view change can bring glass into a
+        // frame that had none -- one ray (160 B of queue) and a quarter of a query (12 B) per sample: 1.4 GB per 8 Mi-sample working
+        // set of a job, 11.5 GB per 64 Mi-sample one of a device-side render -- and cover both
+        if (q.hist_ok) { q.ray_factor = std::max(2.0 * H.rays_per_sample, 1.0); q.query_factor = std::max(2.0 * H.queries_per_sample, 0.25); }
+        else if (can_retry) {
+            // first render of a kind: from the model's fan-out.  k_wavefront keeps the ray tree in LDS (the global queue only sees
+            // what does not fit).  The per-level models put a whole level into the queue: about one hemisphere ray per path that
+            // is still alive (P12: hemisphere_sample of them on the first level, RayTracingProj12 main.cpp:393-446) PLUS the
+            // ungated reflection / refraction pairs of the P13-family Shade, which double level by level inside glass
+            // (P13/main.cpp:633-751: measured 2.5 rays per sample on the fullest level of a Cornell chunk that holds the glass
+            // sphere, bounce 8) -- four per sample on top of the hemisphere rays, 640 B per sample of queue memory
+            // (the kernels' own predicate: a scene k_wavefront does not take -- a BVH beyond its traversal stack, RT_TRACER=levels -- goes
+            // through the per-level kernels and gets their figure; P12 through k_wavefront keeps the per-level figure too: its overflow is scene-dependent)
+            const bool wf = rtk_wavefront_usable(D->scene, p) && p.shade_model != RT_SHADE_P12;
+            q.ray_factor = wf ? 1.0 : (p.shade_model == RT_SHADE_P12 ? (double)std::max(p.hemisphere_sample, 1) + 3.0 : 4.0);
+            q.query_factor = 0.5;
+        }
+    }
+    D->qhist_used = q.ray_factor > 0 || q.query_factor > 0;
+    return q;
+}
+// The peaks of a render that finished without a drop, per sample of a chunk, into the history the next one is sized from.
+static void record_queue_peaks(DeviceState *D, const QueueSizing &q, double rays_per_sample, double queries_per_sample)
+{
+    DeviceState::QueueHistory &H = D->qhist;
+    if (q.hist_ok) { H.rays_per_sample = std::max(H.rays_per_sample, rays_per_sample); H.queries_per_sample = std::max(H.queries_per_sample, queries_per_sample); }
+    else { H.valid = true; H.key = q.key; H.rays_per_sample = rays_per_sample; H.queries_per_sample = queries_per_sample; }
+}
 
 // One host call at a time may use a device's working sets, scratch buffers, counters and stats: the render
 // entry points AND the single-stage ones (rt_trace_rays, rt_shade_rays, rt_estimate_irradiance, rt_photon_pass)
@@ -789,6 +857,14 @@ static DeviceState *device_state(rt_scene *s, int device)
     s->devs.push_back(d);
     return d;
 }
+// lookup only, under s->mu: NULL when nothing was ever prepared on that device (device_state above is the creating variant,
+// for callers that hold s->mu)
+static DeviceState *find_device_state(rt_scene *s, int device)
+{
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (DeviceState *d : s->devs) if (d->device == device) return d;
+    return nullptr;
+}
 
 // The tree the kernels walk is built HERE from the triangles (binned surface-area heuristic, leaves of at most four, collapsed
 // four-wide by largest child first): any bounding hierarchy over the same triangles gives the same closest hit -- the
@@ -1332,7 +1408,6 @@ static rt_status order_after_pending(DeviceState *D, hipStream_t st)
     if (D->last_pending && D->last_done) HIP_TRY(hipStreamWaitEvent(st, D->last_done, 0));
     return RT_OK;
 }
-// Dropped rays / photon queries of the renders since the counter was last cleared (host-synchronous read).
 // The statistics block keeps its counters RT_STAT_STRIDE apart (rt_dev.h): counters [first, first + n) as a dense array, and back to zero
 static hipError_t stats_read(const void *dev, int first, int n, unsigned long long *out)
 {
@@ -1346,11 +1421,18 @@ static hipError_t stats_zero(void *dev, int first, int n, hipStream_t st)
     return hipSuccess;
 }
 
-static rt_status read_overflow(DeviceState *D, unsigned long long *drops)
+// The verdict of the asynchronous renders still pending: waits for the last one and reads the drop counter (dropped rays / photon
+// queries of the renders since it was last cleared; a host-synchronous read); drops clear the counter and invalidate the queue history (the next render starts from the worst case again).  What the caller does with the
+// verdict is its own: a render keeps it in async_overflow for rt_render_check, which reports it.
+static rt_status collect_pending_verdict(DeviceState *D, unsigned long long *drops)
 {
     *drops = 0;
+    if (!D->last_pending || !D->last_done) return RT_OK;
+    HIP_TRY(hipEventSynchronize(D->last_done));
+    D->last_pending = false;
     if (!D->stats.p) return RT_OK;
     HIP_TRY(stats_read(D->stats.p, ST_QUEUE_OVERFLOW, 1, drops));
+    if (*drops) { D->qhist.valid = false; HIP_TRY(hipMemset((unsigned long long *)D->stats.p + ST_AT(ST_QUEUE_OVERFLOW), 0, 8)); }
     return RT_OK;
 }
 
@@ -1425,19 +1507,26 @@ static rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float ra
     return RT_OK;
 }
 
-struct Timing { std::vector<hipEvent_t> ev; std::vector<int> cls; };
+// The events run_pipeline leaves on a stream when statistics are wanted: cls[i] is what ran between ev[i - 1] and ev[i]
+// (TM_START: nothing that is counted -- the pass begins there).
+enum TimingClass { TM_START, TM_PRIMARY, TM_BOUNCE, TM_GATHER };
+struct Timing { std::vector<Event> ev; std::vector<TimingClass> cls; };
+
+// Levels of the ray tree below the primary rays.  P6: a side ray is spawned when its refraction ray ARRIVES, one queue level
+// later than a sibling would be, so a path can take up to two levels per bounce.
+static int tree_levels(const rt_params &P) { return P.shade_model == RT_SHADE_P6 ? 2 * P.bounce : P.bounce; }
 
 // One tracing pass over a chunk on its stream: primary samples, the levels of the ray tree, the gathers against the photon maps,
 // and (reproducible mode) the fold of the secondary plane -- the chunk's samples are final in W.sample_* behind it.
 static rt_status run_pipeline(DeviceState *D, hipStream_t st, const DevWork &W, const rt_params &P, Timing *tm, const RenderPass &pass)
 {
     unsigned long long *const fx = pass.fx;
-    auto mark = [&](int cls) -> rt_status {
+    auto mark = [&](TimingClass cls) -> rt_status {
         if (!tm) return RT_OK;
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
+        Event e;
+        HIP_TRY(e.create());
         HIP_TRY(hipEventRecord(e, st));
-        tm->ev.push_back(e); tm->cls.push_back(cls);
+        tm->ev.push_back(std::move(e)); tm->cls.push_back(cls);
         return RT_OK;
     };
     rt_status s;
@@ -1447,12 +1536,10 @@ static rt_status run_pipeline(DeviceState *D, hipStream_t st, const DevWork &W, 
     // pass folds it into sample_rgb at its end and leaves it zero behind (k_fold_fx), which is where a second pass finds it
     const size_t chunk_slots = (size_t)pass.npix * (size_t)pass.max_sample;
     if (fx && pass.mode != 1) HIP_TRY(hipMemsetAsync(fx, 0, chunk_slots * 24, st));
-    if ((s = mark(-1))) return s;
+    if ((s = mark(TM_START))) return s;
     rtk_launch_primary(st, D->scene, W, P, pass, RT_TRACE_BLOCKS);
-    if ((s = mark(0))) return s;
-    // P6: a side ray is spawned when its refraction ray ARRIVES, one queue level later than a sibling
-    // would be, so a path can take up to two levels per bounce
-    const int max_level = P.shade_model == RT_SHADE_P6 ? 2 * P.bounce : P.bounce;
+    if ((s = mark(TM_PRIMARY))) return s;
+    const int max_level = tree_levels(P);
     // k_wavefront's overflow (level-1 queue) first goes through a second k_wavefront pass; what overflows again, and the
     // models without that kernel, take one launch per level
     int first_level = 1;
@@ -1461,26 +1548,24 @@ static rt_status run_pipeline(DeviceState *D, hipStream_t st, const DevWork &W, 
     // the first pass, Cornell 0.34 / 0.36 / 0.40 / 0.44, C3 13.0 / 13.0 / 13.1 / 13.1 -- the second pass takes everything that matters)
     for (int level = first_level; level <= max_level && level < 15; level++)
         rtk_launch_bounce(st, D->scene, W, P, level, RT_TRACE_BLOCKS, fx);
-    if ((s = mark(1))) return s;
-    rt_status cs;
-    if ((cs = ensure_cell_start(D, false, P.knn_k, P.knn_radius, st))) return cs;
-    // reproducible mode: the per-cell hints are off (they pick which of two exact paths, with two summation orders, a query
-    // takes, from whichever query of the cell was answered last)
-    GatherRequest g = {};
-    g.sample_rgb = W.sample_rgb; g.stats = W.stats; g.fx = fx;
-    if (D->scene.pm.n_leaves) {
-        g.pm = D->scene.pm; g.q = W.pq; g.count = W.counts + CNT_PHOTONQ; g.k = P.knn_k; g.radius = P.knn_radius;
-        g.next_batch = W.counts + CNT_GATHER_NEXT; g.cell_rk2 = fx ? nullptr : (float *)D->cell_rk2.p;
-        rtk_launch_gather(st, g, GATHER_BLOCKS);
-        if ((s = mark(2))) return s;
-    }
+    if ((s = mark(TM_BOUNCE))) return s;
+    // one k_gather launch over a queue of the working set against one of the two maps
+    auto gather = [&](const DevPhotonMap &pm, const DevPhotonQueue &q, int count_at, int next_at, int k, float radius, const DevBuf &rk2) -> rt_status {
+        GatherRequest g = {};
+        g.sample_rgb = W.sample_rgb; g.stats = W.stats; g.fx = fx;
+        g.pm = pm; g.q = q; g.count = W.counts + count_at; g.k = k; g.radius = radius;
+        // reproducible mode: the per-cell hints are off (they pick which of two exact paths, with two summation orders, a query
+        // takes, from whichever query of the cell was answered last)
+        g.next_batch = W.counts + next_at; g.cell_rk2 = fx ? nullptr : (float *)rk2.p;
+        rtk_launch_gather(st, g, gather_blocks());
+        return mark(TM_GATHER);
+    };
+    if ((s = ensure_cell_start(D, false, P.knn_k, P.knn_radius, st))) return s;
+    if (D->scene.pm.n_leaves && (s = gather(D->scene.pm, W.pq, CNT_PHOTONQ, CNT_GATHER_NEXT, P.knn_k, P.knn_radius, D->cell_rk2))) return s;
     if (D->scene.cm.n_leaves && P.caustic_k > 0 && W.cq.cap) {
         // the P13-family models queued their caustic lookups separately: same kernel on the second map
-        if ((cs = ensure_cell_start(D, true, P.caustic_k, P.caustic_radius, st))) return cs;
-        g.pm = D->scene.cm; g.q = W.cq; g.count = W.counts + CNT_CAUSTICQ; g.k = P.caustic_k; g.radius = P.caustic_radius;
-        g.next_batch = W.counts + CNT_GATHER_NEXT2; g.cell_rk2 = fx ? nullptr : (float *)D->ccell_rk2.p;
-        rtk_launch_gather(st, g, GATHER_BLOCKS);
-        if ((s = mark(2))) return s;
+        if ((s = ensure_cell_start(D, true, P.caustic_k, P.caustic_radius, st))) return s;
+        if ((s = gather(D->scene.cm, W.cq, CNT_CAUSTICQ, CNT_GATHER_NEXT2, P.caustic_k, P.caustic_radius, D->ccell_rk2))) return s;
     }
     // the secondary plane goes into the samples before k_resolve
     if (fx) rtk_launch_fold_fx(st, W.sample_rgb, fx, chunk_slots);
@@ -1546,257 +1631,218 @@ struct RenderRequest {
 };
 
 #define RT_ERR_OVERFLOW_RETRY (-1000)     /* internal: queues sized from history overflowed; render again with worst-case queues */
-static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                   const RenderRequest &req, bool worst_case)
-{
-    rt_status st = validate_render(s, cam, p, tiles);
-    if (st) return st;
-    const bool sync = req.sync; rt_stats *const stats_out = req.stats_out; rt_job *const job = req.job;
-    DeviceState *D = nullptr;
-    if ((st = prepare_device(s, device, &D))) return st;
+
+namespace {
+// a job's chunk on its way to the caller's planes: slots [q0, q0 + npix) of the tile walk, `done` behind its last kernel
+struct InFlight { uint64_t q0; uint32_t npix; Event done; };
+
+// One attempt at a render call: what the phases of render_tiles_once share.  The members below are those phases, in the order
+// they run.  Every event and scratch buffer of the attempt goes with it, on whichever path the attempt is left, and the device
+// claim after them.
+struct RenderAttempt {
     // one host call at a time per (scene, device): the working sets are not shared between concurrent calls
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "render: another call on this scene is using device %d", device);
-    hipStream_t stream = req.stream ? req.stream : D->stream;
-    if ((st = order_after_pending(D, stream))) return st;
-    if (!D->last_done) HIP_TRY(hipEventCreateWithFlags(&D->last_done, hipEventDisableTiming));
-    if (D->last_pending && (sync || stats_out != nullptr || job != nullptr)) {
-        // this call will clear and read the shared drop counter: the verdict of the asynchronous renders before it is
-        // collected first and kept for rt_render_check ("queue overflow is always reported")
-        HIP_TRY(hipEventSynchronize(D->last_done));
-        unsigned long long drops = 0;
-        if ((st = read_overflow(D, &drops))) return st;
-        if (drops) { D->async_overflow = true; D->qhist.valid = false; HIP_TRY(hipMemset((unsigned long long *)D->stats.p + ST_AT(ST_QUEUE_OVERFLOW), 0, 8)); }
-        D->last_pending = false;
-    }
-
-    DevCamera dc;
-    camera_setup(*cam, dc);
-    DevTiles dt;
-    dt.tile_w = tiles->tile_w; dt.tile_h = tiles->tile_h; dt.first = tiles->first; dt.stride = tiles->stride;
-    dt.tiles_x = (cam->width + dt.tile_w - 1) / dt.tile_w;
-    const int tiles_y = (cam->height + dt.tile_h - 1) / dt.tile_h;
-    dt.tiles_total = dt.tiles_x * tiles_y;
-    dt.n_tiles = dt.first >= dt.tiles_total ? 0 : (dt.tiles_total - dt.first + dt.stride - 1) / dt.stride;
-    const uint64_t tile_px = (uint64_t)dt.tile_w * dt.tile_h;
-    const uint64_t total_px = tile_px * (uint64_t)dt.n_tiles;
-
-    const size_t limit = chunk_samples_limit(job != nullptr);
-    uint64_t ppc = std::max<uint64_t>(1, limit / (uint64_t)p->max_sample);
-    ppc = std::max<uint64_t>(tile_px, ppc / tile_px * tile_px);
-    ppc = std::min<uint64_t>(ppc, std::max<uint64_t>(total_px, 1));
-    // P12: a diffuse hit spawns hemisphere rays on top of the reflection/refraction pair; in practice one
-    // of the three classes dominates per material, so the queues are sized for a fan-out of 2 and an
-    // overflow is reported as an error rather than silently dropped
-    const uint64_t n_chunks = total_px ? (total_px + ppc - 1) / ppc : 0;
-    // FRAME PIPELINING (opt-in: RT_FRAME_PIPELINE=1).  An asynchronous render behind another one that is still in flight runs all of its
-    // slots on the library's own streams and lets its tracing and gathering start at once: they touch nothing but the slot's working
-    // set, which the slot's stream already orders, and read scene tables no stream-ordered work of the caller can change.  Only
-    // k_resolve, which writes the caller's buffers, waits for what the caller's stream holds before this call (e_fork) -- the frame
-    // before it, an all-gather of its tiles, a copy of the image; frames of one chunk alternate between two slots.  What it is for:
-    // the tile exchange of a multi-GPU step sits between two frames, and this puts the next frame's rays beside it.  Why it is not the
-    // default: measured on ONE GPU (r4, profiles/r04_experiments.json) it gains nothing where there is no exchange to hide -- a rank's
-    // share at N = 2 / 4 / 8: 18.73 / 10.14 / 5.39 ms against 18.73 / 10.14 / 5.33 -- and costs the two-chunk frames their lockstep
-    // (both chunks tracing, then both gathering: Cornell 36.4 against 36.0 ms, 102 k triangles 21.75 against 20.64: a tracer and a gather
-    // side by side take each other's LDS); with an exchange beside persistent grids that leave no LDS free it is unmeasured.
-    bool pipelined = false;
-    {
-        const char *e = getenv("RT_FRAME_PIPELINE");
-        pipelined = e && atoi(e) != 0 && !sync && stats_out == nullptr && job == nullptr && D->last_pending && total_px > 0;
-    }
-    const int streams_wanted = render_streams(pipelined ? std::max<uint64_t>(n_chunks, 2) : n_chunks);
-    if (streams_wanted < 2) pipelined = false;              // RT_STREAMS=1: one chunk at a time, as asked
-    int n_slots = pipelined ? streams_wanted : (int)std::min<uint64_t>(std::max<uint64_t>(n_chunks, 1), (uint64_t)streams_wanted);
-    const int fan = p->shade_model == RT_SHADE_P12 && p->hemisphere_sample > 1 ? 1 + p->hemisphere_sample : 2;
-    const bool use_photons = D->scene.pm.n_leaves != 0, use_caustic = p->caustic_k > 0 && D->scene.cm.n_leaves != 0;
-    const DeviceState::QueueHistory &H = D->qhist;
-    const bool hist_ok = H.valid && H.model == p->shade_model && H.bounce == p->bounce && H.fan == fan && H.photons == use_photons && H.caustic == use_caustic;
-    double ray_factor = 0, query_factor = 0;           // 0 = worst case
-    if (!worst_case && getenv("RT_QUEUE_WORST_CASE") == nullptr) {
-        // floors: how many rays k_wavefront cannot keep in LDS depends on timing, and a view change can bring glass into a
-        // frame that had none -- one ray (160 B of queue) and a quarter of a query (12 B) per sample: 1.4 GB per 8 Mi-sample working
-        // set of a job, 11.5 GB per 64 Mi-sample one of a device-side render -- and cover both
-        if (hist_ok) { ray_factor = std::max(2.0 * H.rays_per_sample, 1.0); query_factor = std::max(2.0 * H.queries_per_sample, 0.25); }
-        else if (sync || job) {
-            // first render of a kind: from the model's fan-out.  k_wavefront keeps the ray tree in LDS (the global queue only sees
-            // what does not fit).  The per-level models put a whole level into the queue: about one hemisphere ray per path that
-            // is still alive (P12: hemisphere_sample of them on the first level, RayTracingProj12 main.cpp:393-446) PLUS the
-            // ungated reflection / refraction pairs of the P13-family Shade, which double level by level inside glass
-            // (P13/main.cpp:633-751: measured 2.5 rays per sample on the fullest level of a Cornell chunk that holds the glass
-            // sphere, bounce 8) -- four per sample on top of the hemisphere rays, 640 B per sample of queue memory
-            // (the kernels' own predicate: a scene k_wavefront does not take -- a BVH beyond its traversal stack, RT_TRACER=levels -- goes
-            // through the per-level kernels and gets their figure; P12 through k_wavefront keeps the per-level figure too: its overflow is scene-dependent)
-            const bool wf = rtk_wavefront_usable(D->scene, *p) && p->shade_model != RT_SHADE_P12;
-            ray_factor = wf ? 1.0 : (p->shade_model == RT_SHADE_P12 ? (double)std::max(p->hemisphere_sample, 1) + 3.0 : 4.0);
-            query_factor = 0.5;
-        }
-    }
-    D->qhist_used = ray_factor > 0 || query_factor > 0;
-    // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
-    const bool reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
-    // first-hit feature planes (k_features after each chunk's last resolve): only when a plane was asked for
-    const bool features = (job ? job->host : req.dev).features().any();
+    DeviceClaim claim;
+    rt_scene *const s; DeviceState *const D;
+    const rt_camera *const cam; const rt_params *const p; const rt_tile_range *const tiles; const RenderRequest &req;
+    rt_job *const job;
+    const bool sync, want_stats;
+    hipStream_t stream = nullptr;       // the caller's, or the device's own
+    // the plan (plan_chunks, choose_queue_sizing)
+    DevCamera dc; DevTiles dt;
+    uint64_t tile_px = 0, total_px = 0, ppc = 0, n_chunks = 0;
+    bool pipelined = false, reproducible = false, features = false;
+    QueueSizing qs;
+    // the slots (acquire_slots, fork_slots)
+    int n_slots = 0;
     DevWork Ws[RT_STREAMS];
     unsigned long long *Fx[RT_STREAMS] = {};
-    int n_ready = 0;
-    for (int i = 0; i < n_slots; i++) {
-        if (i > 0 && D->ws[i].samples < (size_t)ppc * p->max_sample) {
-            // an extra working set is an optimisation: take it only while a comfortable share of the HBM stays
-            // free (other ranks rehearsing on the same device, the caller's own tensors)
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); break; }
-            const size_t first = D->ws[0].sample_rgb.bytes + D->ws[0].sample_z.bytes + D->ws[0].sample_hit.bytes + 10 * D->ws[0].rq[0][0].bytes +
-                                 3 * D->ws[0].pq[0].bytes;
-            if (free_b < first + first / 4 + (total_b >> 3)) break;
-        }
-        if ((st = ensure_workspace(D, i, (size_t)ppc * p->max_sample, p->bounce, (size_t)ppc, fan, use_caustic, ray_factor, query_factor,
-                                   reproducible))) return st;
-        Ws[i] = make_work(D, i);
-        if (reproducible) Fx[i] = (unsigned long long *)D->ws[i].sample_fx.p;
-        if (features && (st = D->ws[i].feat_second.ensure(std::max<uint64_t>(ppc, 1)))) return st;
-        n_ready++;
-    }
-    n_slots = n_ready;
-    // a job that owns only some of the tiles renders into packed records of its own (see finish_oldest)
-    const bool job_packed = job != nullptr && tiles->stride != 1;
-    // bytes per packed record: 8, or 24 with the linear plane (the 8-byte record, linear r, g, b, 4 zero bytes)
-    const size_t rec_bytes = req.rec_bytes;
-    ScopedDevBuf job_packed_buf;
-    void *packed_dev = req.packed;
-    if (job_packed) {
-        if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * rec_bytes))) return st;
-        packed_dev = job_packed_buf.p;
-    }
-    const bool linear = packed_dev ? rec_bytes == 24 : req.dev.p[PL_LINEAR] != nullptr;
-    // where k_features writes: the caller's image-sized device planes, or -- a strided job, whose rows are shared with other jobs --
-    // staging planes indexed by this call's tile walk, scattered on the host like the packed records (finish_oldest)
-    DevFeatures fdev = req.dev.features();
-    ScopedDevBuf stage[N_PLANES];
-    const bool feat_by_walk = features && job_packed;
-    if (feat_by_walk) {
-        Planes staged;
-        for (int i = PL_NORMAL; i < N_PLANES; i++) {
-            if (!job->host.p[i]) continue;
-            if ((st = stage[i].ensure(std::max<uint64_t>(total_px, 1) * PLANE_BYTES[i]))) return st;
-            staged.p[i] = stage[i].p;
-        }
-        fdev = staged.features();
-    }
-    const TileWalk walk{dt, cam->width, cam->height, tile_px};
-    const bool want_stats = stats_out != nullptr || job != nullptr;
-    Timing tm[RT_STREAMS];
-    hipEvent_t e_begin = nullptr, e_end = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> resolve_ev;
-    struct InFlight { uint64_t q0; uint32_t npix; hipEvent_t done; };
-    std::vector<InFlight> flight;
-    // every timing / completion event of this attempt is destroyed when the function is left, on whichever path
-    struct EventGuard {
-        Timing *tm; hipEvent_t &b, &e; std::vector<std::pair<hipEvent_t, hipEvent_t>> &rv; std::vector<InFlight> &fl;
-        ~EventGuard()
-        {
-            for (int sl = 0; sl < RT_STREAMS; sl++) for (hipEvent_t x : tm[sl].ev) (void)hipEventDestroy(x);
-            if (b) (void)hipEventDestroy(b);
-            if (e) (void)hipEventDestroy(e);
-            for (auto &pr : rv) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-            for (InFlight &f : fl) (void)hipEventDestroy(f.done);
-        }
-    } event_guard{tm, e_begin, e_end, resolve_ev, flight};
-    if (want_stats) {
-        HIP_TRY(stats_zero(Ws[0].stats, 0, ST_COUNT, stream));
-        HIP_TRY(hipEventCreate(&e_begin)); HIP_TRY(hipEventCreate(&e_end));
-        HIP_TRY(hipEventRecord(e_begin, stream));
-    } else if (!D->last_pending) {
-        // the drop counter is read back after every synchronous render (below) and by rt_render_check after
-        // asynchronous ones; consecutive asynchronous renders accumulate into it until it is checked
-        HIP_TRY(stats_zero(Ws[0].stats, ST_QUEUE_OVERFLOW, 1, stream));
-        HIP_TRY(stats_zero(Ws[0].stats, ST_PEAK_RAYS, 2, stream));
-    }
-    // the gathers' start tables are built on `stream` before the slots fork from it
     bool tables_touched = false;
-    if ((st = ensure_cell_start(D, false, p->knn_k, p->knn_radius, stream, &tables_touched))) return st;
-    if (use_caustic && (st = ensure_cell_start(D, true, p->caustic_k, p->caustic_radius, stream, &tables_touched))) return st;
+    bool resolve_waits[RT_STREAMS] = {};        // the slot's stream is not behind e_fork yet: its first k_resolve waits for it
+    // the output targets (setup_outputs)
+    ScopedDevBuf job_packed_buf, stage[N_PLANES];
+    void *packed_dev = nullptr;
+    size_t rec_bytes = 8;               // bytes per packed record: 8, or 24 with the linear plane (the 8-byte record, linear r, g, b, 4 zero bytes)
+    bool job_packed = false, linear = false, feat_by_walk = false;
+    DevFeatures fdev;
+    // timing and completion events; chunks in flight (job mode), delivered oldest-first for progress and the band copy
+    Timing tm[RT_STREAMS];
+    Event e_begin, e_end, e_fork;
+    std::vector<std::pair<Event, Event>> resolve_ev;
+    std::vector<InFlight> flight;
+    int attempt_progress = 0;
+
+    RenderAttempt(rt_scene *s_, DeviceState *D_, const rt_camera *cam_, const rt_params *p_, const rt_tile_range *tiles_, const RenderRequest &req_)
+        : claim(D_), s(s_), D(D_), cam(cam_), p(p_), tiles(tiles_), req(req_), job(req_.job), sync(req_.sync),
+          want_stats(req_.stats_out != nullptr || req_.job != nullptr) {}
+
+    TileWalk walk() const { return TileWalk{dt, cam->width, cam->height, tile_px}; }
     // slot 0 runs on `stream` itself; the other slots' streams start after everything already queued on
     // `stream` (fork) and `stream` waits for them at the end (join), so the call keeps stream-order semantics
-    auto slot_stream = [&](int slot) { return (slot == 0 && !pipelined) ? stream : D->ws[slot].stream; };
-    hipEvent_t e_fork = nullptr;
-    struct ForkGuard { hipEvent_t &e; ~ForkGuard() { if (e) (void)hipEventDestroy(e); } } fork_guard{e_fork};
-    bool wait_at_start[RT_STREAMS];                      // the slot's stream has not been put behind e_fork yet
-    for (int i = 0; i < RT_STREAMS; i++) wait_at_start[i] = false;
-    bool resolve_waits[RT_STREAMS];
-    for (int i = 0; i < RT_STREAMS; i++) resolve_waits[i] = false;
-    if (n_slots > 1 || pipelined) {
-        HIP_TRY(hipEventCreateWithFlags(&e_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(e_fork, stream));
+    hipStream_t slot_stream(int slot) const { return (slot == 0 && !pipelined) ? stream : D->ws[slot].stream; }
+
+    // The device is prepared and claimed (the constructor): order the call behind the render in flight and collect its verdict.
+    rt_status enter()
+    {
+        if (!claim.ok) return fail(RT_ERR_STATE, "render: another call on this scene is using device %d", D->device);
+        rt_status st;
+        stream = req.stream ? req.stream : D->stream;
+        if ((st = order_after_pending(D, stream))) return st;
+        if (!D->last_done) HIP_TRY(hipEventCreateWithFlags(&D->last_done, hipEventDisableTiming));
+        if (D->last_pending && (sync || want_stats)) {
+            // this call will clear and read the shared drop counter: the verdict of the asynchronous renders before it is
+            // collected first and kept for rt_render_check ("queue overflow is always reported")
+            unsigned long long drops = 0;
+            if ((st = collect_pending_verdict(D, &drops))) return st;
+            if (drops) D->async_overflow = true;
+        }
+        return RT_OK;
+    }
+
+    // The tile walk of the call, cut into chunks of ppc pixels, and how many of them are in flight at once.
+    void plan_chunks()
+    {
+        camera_setup(*cam, dc);
+        dt.tile_w = tiles->tile_w; dt.tile_h = tiles->tile_h; dt.first = tiles->first; dt.stride = tiles->stride;
+        dt.tiles_x = (cam->width + dt.tile_w - 1) / dt.tile_w;
+        const int tiles_y = (cam->height + dt.tile_h - 1) / dt.tile_h;
+        dt.tiles_total = dt.tiles_x * tiles_y;
+        dt.n_tiles = dt.first >= dt.tiles_total ? 0 : (dt.tiles_total - dt.first + dt.stride - 1) / dt.stride;
+        tile_px = (uint64_t)dt.tile_w * dt.tile_h;
+        total_px = tile_px * (uint64_t)dt.n_tiles;
+
+        const size_t limit = chunk_samples_limit(job != nullptr);
+        ppc = std::max<uint64_t>(1, limit / (uint64_t)p->max_sample);
+        ppc = std::max<uint64_t>(tile_px, ppc / tile_px * tile_px);
+        ppc = std::min<uint64_t>(ppc, std::max<uint64_t>(total_px, 1));
+        n_chunks = total_px ? (total_px + ppc - 1) / ppc : 0;
+        // FRAME PIPELINING (opt-in: RT_FRAME_PIPELINE=1).  An asynchronous render behind another one that is still in flight runs all of its
+        // slots on the library's own streams and lets its tracing and gathering start at once: they touch nothing but the slot's working
+        // set, which the slot's stream already orders, and read scene tables no stream-ordered work of the caller can change.  Only
+        // k_resolve, which writes the caller's buffers, waits for what the caller's stream holds before this call (e_fork) -- the frame
+        // before it, an all-gather of its tiles, a copy of the image; frames of one chunk alternate between two slots.  What it is for:
+        // the tile exchange of a multi-GPU step sits between two frames, and this puts the next frame's rays beside it.  Why it is not the
+        // default: measured on ONE GPU (r4, profiles/r04_experiments.json) it gains nothing where there is no exchange to hide -- a rank's
+        // share at N = 2 / 4 / 8: 18.73 / 10.14 / 5.39 ms against 18.73 / 10.14 / 5.33 -- and costs the two-chunk frames their lockstep
+        // (both chunks tracing, then both gathering: Cornell 36.4 against 36.0 ms, 102 k triangles 21.75 against 20.64: a tracer and a gather
+        // side by side take each other's LDS); with an exchange beside persistent grids that leave no LDS free it is unmeasured.
+        const char *e = getenv("RT_FRAME_PIPELINE");
+        pipelined = e && atoi(e) != 0 && !sync && !want_stats && D->last_pending && total_px > 0;
+        const int streams_wanted = render_streams(pipelined ? std::max<uint64_t>(n_chunks, 2) : n_chunks);
+        if (streams_wanted < 2) pipelined = false;              // RT_STREAMS=1: one chunk at a time, as asked
+        n_slots = pipelined ? streams_wanted : (int)std::min<uint64_t>(std::max<uint64_t>(n_chunks, 1), (uint64_t)streams_wanted);
+        // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
+        reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
+        // first-hit feature planes (k_features after each chunk's last resolve): only when a plane was asked for
+        features = (job ? job->host : req.dev).features().any();
+    }
+
+    // A working set per slot; the attempt goes on with as many as it got.
+    rt_status acquire_slots()
+    {
+        rt_status st;
+        const size_t samples = (size_t)ppc * p->max_sample;
+        int n_ready = 0;
         for (int i = 0; i < n_slots; i++) {
-            if (i == 0 && !pipelined) continue;          // slot 0 IS `stream`
+            if (i > 0 && D->ws[i].samples < samples) {
+                // an extra working set is an optimisation: take it only while a comfortable share of the HBM stays
+                // free (other ranks rehearsing on the same device, the caller's own tensors)
+                size_t free_b = 0, total_b = 0;
+                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); break; }
+                const size_t first = D->ws[0].sample_rgb.bytes + D->ws[0].sample_z.bytes + D->ws[0].sample_hit.bytes + 10 * D->ws[0].rq[0][0].bytes +
+                                     3 * D->ws[0].pq[0].bytes;
+                if (free_b < first + first / 4 + (total_b >> 3)) break;
+            }
+            if ((st = ensure_workspace(D, i, samples, p->bounce, (size_t)ppc, qs.key.fan, qs.key.caustic, qs.ray_factor, qs.query_factor,
+                                       reproducible))) return st;
+            Ws[i] = make_work(D, i);
+            if (reproducible) Fx[i] = (unsigned long long *)D->ws[i].sample_fx.p;
+            if (features && (st = D->ws[i].feat_second.ensure(std::max<uint64_t>(ppc, 1)))) return st;
+            n_ready++;
+        }
+        n_slots = n_ready;
+        return RT_OK;
+    }
+
+    // Where k_resolve and k_features write.
+    rt_status setup_outputs()
+    {
+        rt_status st;
+        // a job that owns only some of the tiles renders into packed records of its own (see scatter_packed)
+        job_packed = job != nullptr && tiles->stride != 1;
+        rec_bytes = req.rec_bytes;
+        packed_dev = req.packed;
+        if (job_packed) {
+            if ((st = job_packed_buf.ensure(std::max<uint64_t>(total_px, 1) * rec_bytes))) return st;
+            packed_dev = job_packed_buf.p;
+        }
+        linear = packed_dev ? rec_bytes == 24 : req.dev.p[PL_LINEAR] != nullptr;
+        // where k_features writes: the caller's image-sized device planes, or -- a strided job, whose rows are shared with other jobs --
+        // staging planes indexed by this call's tile walk, scattered on the host like the packed records (scatter_packed)
+        fdev = req.dev.features();
+        feat_by_walk = features && job_packed;
+        if (feat_by_walk) {
+            Planes staged;
+            for (int i = PL_NORMAL; i < N_PLANES; i++) {
+                if (!job->host.p[i]) continue;
+                if ((st = stage[i].ensure(std::max<uint64_t>(total_px, 1) * PLANE_BYTES[i]))) return st;
+                staged.p[i] = stage[i].p;
+            }
+            fdev = staged.features();
+        }
+        return RT_OK;
+    }
+
+    // What goes onto `stream` before the slots fork from it: the statistics' start (or the partial counter reset) and the gathers'
+    // start tables.
+    rt_status begin_on_stream()
+    {
+        rt_status st;
+        if (want_stats) {
+            HIP_TRY(stats_zero(Ws[0].stats, 0, ST_COUNT, stream));
+            HIP_TRY(e_begin.create()); HIP_TRY(e_end.create());
+            HIP_TRY(hipEventRecord(e_begin, stream));
+        } else if (!D->last_pending) {
+            // the drop counter is read back after every synchronous render (finish) and by rt_render_check after
+            // asynchronous ones; consecutive asynchronous renders accumulate into it until it is checked
+            HIP_TRY(stats_zero(Ws[0].stats, ST_QUEUE_OVERFLOW, 1, stream));
+            HIP_TRY(stats_zero(Ws[0].stats, ST_PEAK_RAYS, 2, stream));
+        }
+        if ((st = ensure_cell_start(D, false, p->knn_k, p->knn_radius, stream, &tables_touched))) return st;
+        if (qs.key.caustic && (st = ensure_cell_start(D, true, p->caustic_k, p->caustic_radius, stream, &tables_touched))) return st;
+        return RT_OK;
+    }
+
+    // The slots' own streams go behind what `stream` holds now (e_fork), at once or -- a pipelined frame -- at their first k_resolve.
+    rt_status fork_slots()
+    {
+        if (n_slots <= 1 && !pipelined) return RT_OK;
+        HIP_TRY(e_fork.create(hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(e_fork, stream));
+        for (int i = pipelined ? 0 : 1; i < n_slots; i++) {     // (not pipelined: slot 0 IS `stream`)
             // pipelined: the gathers' tables were just rewritten on `stream`, or the frame before used the slots on other streams
             // (slot 0 on the caller's): start behind everything; otherwise only this slot's k_resolve launches wait
-            if (!pipelined || tables_touched || !D->last_pipelined) wait_at_start[i] = true;
+            if (!pipelined || tables_touched || !D->last_pipelined) HIP_TRY(hipStreamWaitEvent(slot_stream(i), e_fork, 0));
             else resolve_waits[i] = true;
         }
-        for (int i = 0; i < n_slots; i++) if (wait_at_start[i]) HIP_TRY(hipStreamWaitEvent(slot_stream(i), e_fork, 0));
-    }
-    const float inv_gamma = (float)(1.0 / p->gamma);        // powf(x, 1.0/gamma): double quotient narrowed to float
-    double ms_resolve = 0;
-    // chunks in flight (job mode): finished oldest-first for progress and the band copy
-    int attempt_progress = 0;
-    auto finish_oldest = [&]() -> rt_status {
-        const InFlight f = flight.front();
-        flight.erase(flight.begin());
-        HIP_TRY(hipEventSynchronize(f.done));
-        (void)hipEventDestroy(f.done);
-        if (job_packed) {
-            // a strided tile range (one job per device on the same caller-owned image): rows are shared with other jobs' tiles,
-            // so only this job's pixels may be written -- the chunk's packed 8-byte (24-byte: linear) records come back in one
-            // copy and are scattered on the host
-            const size_t words = rec_bytes / 8;
-            std::vector<uint2> rec((size_t)f.npix * words);
-            HIP_TRY(hipMemcpy(rec.data(), (const uint2 *)packed_dev + f.q0 * words, (size_t)f.npix * rec_bytes, hipMemcpyDeviceToHost));
-            const Planes &h = job->host;
-            for (uint32_t i = 0; i < f.npix; i++) {
-                const int64_t o = walk.offset(f.q0 + i);
-                if (o < 0) continue;
-                const uint2 v = rec[i * words];
-                uint8_t *rgb = h.at<uint8_t>(PL_RGB8) + 3 * o;
-                rgb[0] = (uint8_t)(v.x & 255u); rgb[1] = (uint8_t)((v.x >> 8) & 255u); rgb[2] = (uint8_t)((v.x >> 16) & 255u);
-                const uint32_t zb = (v.x >> 24) | (v.y << 8);
-                memcpy(h.at<float>(PL_Z) + o, &zb, 4);
-                h.at<uint8_t>(PL_COUNT)[o] = (uint8_t)(v.y >> 24);
-                if (words == 3) memcpy(h.at<float>(PL_LINEAR) + 3 * o, &rec[i * words + 1], 12);
-            }
-            // the chunk's run of each staged feature plane, scattered the same way
-            for (int k = PL_NORMAL; k < N_PLANES; k++) {
-                if (!stage[k].p) continue;
-                const size_t b = PLANE_BYTES[k];
-                std::vector<uint8_t> run((size_t)f.npix * b);
-                HIP_TRY(hipMemcpy(run.data(), (const uint8_t *)stage[k].p + f.q0 * b, run.size(), hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < f.npix; i++) {
-                    const int64_t o = walk.offset(f.q0 + i);
-                    if (o >= 0) memcpy(h.at<uint8_t>(k) + o * b, run.data() + i * b, b);
-                }
-            }
-        } else {
-            // rows spanned by this chunk's tiles (tile-major order: a contiguous band of tile rows; a row shared
-            // with a chunk still in flight may arrive torn and is copied again when that chunk finishes)
-            int x, y0, y1;
-            walk.tile_origin(f.q0 / tile_px, x, y0);
-            walk.tile_origin((f.q0 + f.npix - 1) / tile_px, x, y1);
-            y1 = std::min(cam->height, y1 + dt.tile_h);
-            const size_t o = (size_t)y0 * cam->width, n = y1 > y0 ? (size_t)(y1 - y0) * cam->width : 0;
-            for (int k = 0; k < N_PLANES && n; k++)
-                if (req.dev.p[k])
-                    HIP_TRY(hipMemcpy(job->host.at<uint8_t>(k) + o * PLANE_BYTES[k], req.dev.at<uint8_t>(k) + o * PLANE_BYTES[k],
-                                      n * PLANE_BYTES[k], hipMemcpyDeviceToHost));
-        }
-        // monotone also when the frame is rendered a second time with larger queues (RT_ERR_OVERFLOW_RETRY)
-        attempt_progress += (int)walk.pixels(f.q0, f.q0 + f.npix);
-        int seen = job->progress.load();
-        while (attempt_progress > seen && !job->progress.compare_exchange_weak(seen, attempt_progress)) {}
         return RT_OK;
-    };
-    uint64_t chunk_index = 0;
-    for (uint64_t q0 = 0; q0 < total_px; q0 += ppc, chunk_index++) {
-        if (job && job->stop.load()) break;
+    }
+
+    // One k_resolve phase over a chunk, between two events when the call wants statistics.
+    rt_status resolve(hipStream_t cs, const DevWork &W, ResolveArgs &ra, int phase)
+    {
+        Event r0, r1;
+        if (want_stats) { HIP_TRY(r0.create()); HIP_TRY(r1.create()); HIP_TRY(hipEventRecord(r0, cs)); }
+        ra.phase = phase;
+        rtk_launch_resolve(cs, W, ra, 2048, linear);
+        if (want_stats) { HIP_TRY(hipEventRecord(r1, cs)); resolve_ev.emplace_back(std::move(r0), std::move(r1)); }
+        return RT_OK;
+    }
+
+    // The chunk that starts at slot q0 of the tile walk, on its slot's stream: the first sample batch and its resolve, the second
+    // batch for the pixels that one listed (adaptive renders), the features; a job's chunk is then queued for delivery.
+    rt_status render_chunk(uint64_t q0, uint64_t chunk_index)
+    {
+        rt_status st;
         const int slot = (int)((chunk_index + (pipelined ? D->frame_seq : 0)) % (uint64_t)n_slots);
         const hipStream_t cs = slot_stream(slot);
         const DevWork &W = Ws[slot];
@@ -1809,23 +1855,16 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         if ((st = run_pipeline(D, cs, W, *p, tmp, pass))) return st;
         ResolveArgs ra = {};
         ra.cam = dc; ra.tiles = dt; ra.q0 = pass.q0; ra.npix = npix; ra.min_sample = p->min_sample; ra.max_sample = p->max_sample;
-        ra.threshold = p->threshold; ra.inv_gamma = inv_gamma; memcpy(ra.bg, D->scene.bg, sizeof ra.bg); ra.S = D->scene;
+        ra.threshold = p->threshold; memcpy(ra.bg, D->scene.bg, sizeof ra.bg); ra.S = D->scene;
+        ra.inv_gamma = (float)(1.0 / p->gamma);                 // powf(x, 1.0/gamma): double quotient narrowed to float
         ra.rgb8 = req.dev.at<uint8_t>(PL_RGB8); ra.z = req.dev.at<float>(PL_Z); ra.count = req.dev.at<uint8_t>(PL_COUNT);
         ra.packed = (uint2 *)packed_dev; ra.rgb_linear = req.dev.at<float>(PL_LINEAR);
-        auto timed_resolve = [&](int phase) -> rt_status {
-            hipEvent_t r0 = nullptr, r1 = nullptr;
-            if (want_stats) { HIP_TRY(hipEventCreate(&r0)); HIP_TRY(hipEventCreate(&r1)); HIP_TRY(hipEventRecord(r0, cs)); }
-            ra.phase = phase;
-            rtk_launch_resolve(cs, W, ra, 2048, linear);
-            if (want_stats) { HIP_TRY(hipEventRecord(r1, cs)); resolve_ev.emplace_back(r0, r1); }
-            return RT_OK;
-        };
         if (resolve_waits[slot]) { HIP_TRY(hipStreamWaitEvent(cs, e_fork, 0)); resolve_waits[slot] = false; }
-        if ((st = timed_resolve(0))) return st;
+        if ((st = resolve(cs, W, ra, 0))) return st;
         if (p->max_sample > p->min_sample) {
             pass.mode = 1; pass.j0 = p->min_sample; pass.ns = p->max_sample - p->min_sample;
             if ((st = run_pipeline(D, cs, W, *p, tmp, pass))) return st;
-            if ((st = timed_resolve(1))) return st;
+            if ((st = resolve(cs, W, ra, 1))) return st;
         }
         // the feature planes of the chunk, from its finished working set (hit flags, pixel list) on the same stream
         if (features)
@@ -1833,63 +1872,137 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         HIP_TRY(hipGetLastError());
         if (job) {
             InFlight f; f.q0 = q0; f.npix = npix;
-            HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+            HIP_TRY(f.done.create(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(f.done, cs));
-            flight.push_back(f);
-            while ((int)flight.size() >= n_slots) if ((st = finish_oldest())) return st;
+            flight.push_back(std::move(f));
+            while ((int)flight.size() >= n_slots) if ((st = deliver_oldest())) return st;
         }
+        return RT_OK;
     }
-    while (job && !flight.empty()) if ((st = finish_oldest())) return st;
-    if (n_slots > 1 || pipelined) {
+
+    // A strided tile range (one job per device on the same caller-owned image): rows are shared with other jobs' tiles,
+    // so only this job's pixels may be written -- the chunk's packed 8-byte (24-byte: linear) records come back in one
+    // copy and are scattered on the host through the tile walk, and so is the chunk's run of each staged feature plane.
+    rt_status scatter_packed(const InFlight &f)
+    {
+        const TileWalk w = walk();
+        const size_t words = rec_bytes / 8;
+        std::vector<uint2> rec((size_t)f.npix * words);
+        HIP_TRY(hipMemcpy(rec.data(), (const uint2 *)packed_dev + f.q0 * words, (size_t)f.npix * rec_bytes, hipMemcpyDeviceToHost));
+        const Planes &h = job->host;
+        for (uint32_t i = 0; i < f.npix; i++) {
+            const int64_t o = w.offset(f.q0 + i);
+            if (o < 0) continue;
+            const uint2 v = rec[i * words];
+            uint8_t *rgb = h.at<uint8_t>(PL_RGB8) + 3 * o;
+            rgb[0] = (uint8_t)(v.x & 255u); rgb[1] = (uint8_t)((v.x >> 8) & 255u); rgb[2] = (uint8_t)((v.x >> 16) & 255u);
+            const uint32_t zb = (v.x >> 24) | (v.y << 8);
+            memcpy(h.at<float>(PL_Z) + o, &zb, 4);
+            h.at<uint8_t>(PL_COUNT)[o] = (uint8_t)(v.y >> 24);
+            if (words == 3) memcpy(h.at<float>(PL_LINEAR) + 3 * o, &rec[i * words + 1], 12);
+        }
+        for (int k = PL_NORMAL; k < N_PLANES; k++) {
+            if (!stage[k].p) continue;
+            const size_t b = PLANE_BYTES[k];
+            std::vector<uint8_t> run((size_t)f.npix * b);
+            HIP_TRY(hipMemcpy(run.data(), (const uint8_t *)stage[k].p + f.q0 * b, run.size(), hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < f.npix; i++) {
+                const int64_t o = w.offset(f.q0 + i);
+                if (o >= 0) memcpy(h.at<uint8_t>(k) + o * b, run.data() + i * b, b);
+            }
+        }
+        return RT_OK;
+    }
+
+    // The rows spanned by the chunk's tiles, per plane (tile-major order: a contiguous band of tile rows; a row shared
+    // with a chunk still in flight may arrive torn and is copied again when that chunk finishes).
+    rt_status copy_band(const InFlight &f)
+    {
+        const TileWalk w = walk();
+        int x, y0, y1;
+        w.tile_origin(f.q0 / tile_px, x, y0);
+        w.tile_origin((f.q0 + f.npix - 1) / tile_px, x, y1);
+        y1 = std::min(cam->height, y1 + dt.tile_h);
+        const size_t o = (size_t)y0 * cam->width, n = y1 > y0 ? (size_t)(y1 - y0) * cam->width : 0;
+        for (int k = 0; k < N_PLANES && n; k++)
+            if (req.dev.p[k])
+                HIP_TRY(hipMemcpy(job->host.at<uint8_t>(k) + o * PLANE_BYTES[k], req.dev.at<uint8_t>(k) + o * PLANE_BYTES[k],
+                                  n * PLANE_BYTES[k], hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
+
+    // Job mode: the oldest chunk in flight, once the GPU is done with it, into the caller's host planes, and the job's progress.
+    rt_status deliver_oldest()
+    {
+        const InFlight f = std::move(flight.front());
+        flight.erase(flight.begin());
+        HIP_TRY(hipEventSynchronize(f.done));
+        if (rt_status st = job_packed ? scatter_packed(f) : copy_band(f)) return st;
+        // monotone also when the frame is rendered a second time with larger queues (RT_ERR_OVERFLOW_RETRY)
+        attempt_progress += (int)walk().pixels(f.q0, f.q0 + f.npix);
+        int seen = job->progress.load();
+        while (attempt_progress > seen && !job->progress.compare_exchange_weak(seen, attempt_progress)) {}
+        return RT_OK;
+    }
+
+    // The chunks still in flight are delivered (also after a stop), and `stream` is put behind every slot's stream.
+    rt_status drain_and_join()
+    {
+        while (job && !flight.empty()) if (rt_status st = deliver_oldest()) return st;
+        if (n_slots <= 1 && !pipelined) return RT_OK;
         for (int i = pipelined ? 0 : 1; i < n_slots; i++) {
-            hipEvent_t e_join;
-            HIP_TRY(hipEventCreateWithFlags(&e_join, hipEventDisableTiming));
+            Event e_join;
+            HIP_TRY(e_join.create(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(e_join, slot_stream(i)));
             HIP_TRY(hipStreamWaitEvent(stream, e_join, 0));
-            (void)hipEventDestroy(e_join);
         }
+        return RT_OK;
     }
-    if (want_stats) HIP_TRY(hipEventRecord(e_end, stream));
-    if (sync || want_stats) {
+
+    // A synchronising call waits for the frame, reads its verdict and records its queue peaks; an asynchronous one leaves
+    // `last_done` behind it for the next call and rt_render_check.
+    rt_status finish()
+    {
+        if (want_stats) HIP_TRY(hipEventRecord(e_end, stream));
+        if (!sync && !want_stats) {
+            HIP_TRY(hipEventRecord(D->last_done, stream));
+            D->last_pending = true;
+            D->last_pipelined = pipelined;
+            if (pipelined) D->frame_seq += n_chunks;
+            return RT_OK;
+        }
         HIP_TRY(hipStreamSynchronize(stream));
         D->last_pending = false;
         D->last_pipelined = false;
-        {
-            // a dropped ray or photon query means a wrong image: never RT_OK, whether or not statistics were asked for
-            unsigned long long tail[ST_COUNT - ST_QUEUE_OVERFLOW];
-            HIP_TRY(stats_read(D->stats.p, ST_QUEUE_OVERFLOW, ST_COUNT - ST_QUEUE_OVERFLOW, tail));
-            const unsigned long long drops = tail[0], peak_r = tail[ST_PEAK_RAYS - ST_QUEUE_OVERFLOW], peak_q = tail[ST_PEAK_QUERIES - ST_QUEUE_OVERFLOW];
-            if (drops) {
-                D->qhist.valid = false;
-                if (D->qhist_used && !(job && job->stop.load())) return RT_ERR_OVERFLOW_RETRY;      // sized from history: once more, worst case
-                return fail(RT_ERR_LIMIT, "render: a ray/photon queue overflowed (%llu drops); lower RT_CHUNK_SAMPLES or the bounce limit", drops);
-            }
-            const double per = (double)std::max<uint64_t>(1, ppc * (uint64_t)p->max_sample);
-            DeviceState::QueueHistory &Hn = D->qhist;
-            const double r = (double)peak_r / per, q = (double)peak_q / per;
-            if (hist_ok) { Hn.rays_per_sample = std::max(Hn.rays_per_sample, r); Hn.queries_per_sample = std::max(Hn.queries_per_sample, q); }
-            else { Hn.valid = true; Hn.model = p->shade_model; Hn.bounce = p->bounce; Hn.fan = fan; Hn.photons = use_photons; Hn.caustic = use_caustic;
-                   Hn.rays_per_sample = r; Hn.queries_per_sample = q; }
+        // a dropped ray or photon query means a wrong image: never RT_OK, whether or not statistics were asked for
+        unsigned long long tail[ST_COUNT - ST_QUEUE_OVERFLOW];
+        HIP_TRY(stats_read(D->stats.p, ST_QUEUE_OVERFLOW, ST_COUNT - ST_QUEUE_OVERFLOW, tail));
+        const unsigned long long drops = tail[0], peak_r = tail[ST_PEAK_RAYS - ST_QUEUE_OVERFLOW], peak_q = tail[ST_PEAK_QUERIES - ST_QUEUE_OVERFLOW];
+        if (drops) {
+            D->qhist.valid = false;
+            if (D->qhist_used && !(job && job->stop.load())) return RT_ERR_OVERFLOW_RETRY;      // sized from history: once more, worst case
+            return fail(RT_ERR_LIMIT, "render: a ray/photon queue overflowed (%llu drops); lower RT_CHUNK_SAMPLES or the bounce limit", drops);
         }
-    } else {
-        HIP_TRY(hipEventRecord(D->last_done, stream));
-        D->last_pending = true;
-        D->last_pipelined = pipelined;
-        if (pipelined) D->frame_seq += n_chunks;
+        const double per = (double)std::max<uint64_t>(1, ppc * (uint64_t)p->max_sample);
+        record_queue_peaks(D, qs, (double)peak_r / per, (double)peak_q / per);
+        return RT_OK;
     }
-    if (want_stats) {
+
+    rt_status assemble_stats()
+    {
+        if (!want_stats) return RT_OK;
         rt_stats R;
         memset(&R, 0, sizeof R);
-        if ((st = read_counters(Ws[0].stats, R))) return st;
+        if (rt_status st = read_counters(Ws[0].stats, R)) return st;
         // per-stream intervals between consecutive marks: with two chunks in flight a kernel shares the GPU
         // with the other stream's kernels, so these are durations under overlap (the same thing rocprofv3 reports)
         for (int sl = 0; sl < n_slots; sl++)
             for (size_t i = 1; i < tm[sl].ev.size(); i++) {
-                if (tm[sl].cls[i] < 0) continue;
+                if (tm[sl].cls[i] == TM_START) continue;
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, tm[sl].ev[i - 1], tm[sl].ev[i]));
-                if (tm[sl].cls[i] == 0) { R.ms_primary += ms; R.launches_primary++; }
-                else if (tm[sl].cls[i] == 1) { R.ms_bounce += ms; R.launches_bounce += (uint64_t)std::max(0, std::min(p->shade_model == RT_SHADE_P6 ? 2 * p->bounce : p->bounce, 14)); }
+                if (tm[sl].cls[i] == TM_PRIMARY) { R.ms_primary += ms; R.launches_primary++; }
+                else if (tm[sl].cls[i] == TM_BOUNCE) { R.ms_bounce += ms; R.launches_bounce += (uint64_t)std::max(0, std::min(tree_levels(*p), 14)); }
                 else { R.ms_gather += ms; R.launches_gather++; }
             }
         R.ms_trace = R.ms_primary + R.ms_bounce;
@@ -1898,24 +2011,44 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
         for (auto &pr : resolve_ev) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
-            ms_resolve += ms; R.launches_resolve++;
+            R.ms_resolve += ms; R.launches_resolve++;
         }
-        R.ms_resolve = ms_resolve;
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, e_begin, e_end));
         R.ms_total = ms;
-        R.pixels = walk.pixels(0, total_px);
-        if (stats_out) *stats_out = R;
+        R.pixels = walk().pixels(0, total_px);
+        if (req.stats_out) *req.stats_out = R;
         if (job) job->stats = R;
+        return RT_OK;
     }
-    return RT_OK;
+};
+}   // namespace
+
+static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                   const RenderRequest &req, bool worst_case)
+{
+    rt_status st = validate_render(s, cam, p, tiles);
+    if (st) return st;
+    DeviceState *D = nullptr;
+    if ((st = prepare_device(s, device, &D))) return st;
+    RenderAttempt A(s, D, cam, p, tiles, req);
+    if ((st = A.enter())) return st;
+    A.plan_chunks();
+    A.qs = choose_queue_sizing(D, *p, worst_case, req.sync || req.job != nullptr);      // (sets D->qhist_used: before anything is launched)
+    if ((st = A.acquire_slots())) return st;
+    if ((st = A.setup_outputs())) return st;
+    if ((st = A.begin_on_stream())) return st;
+    if ((st = A.fork_slots())) return st;
+    uint64_t chunk_index = 0;
+    for (uint64_t q0 = 0; q0 < A.total_px; q0 += A.ppc, chunk_index++) {
+        if (req.job && req.job->stop.load()) break;
+        if ((st = A.render_chunk(q0, chunk_index))) return st;
+    }
+    if ((st = A.drain_and_join())) return st;
+    if ((st = A.finish())) return st;
+    return A.assemble_stats();
 }
 
-// Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
-// half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
-// if that ever overflows, a synchronous render
-// is repeated once with the worst-case size (2^bounce per sample) -- an asynchronous one cannot be repeated by the
-// library: it starts from the worst case unless there is history, and an overflow is reported by rt_render_check.
 static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                               const RenderRequest &req)
 {
@@ -2165,27 +2298,17 @@ extern "C" rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoi
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");
-    DeviceState *D = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        for (DeviceState *d : s->devs) if (d->device == device) D = d;
-    }
+    DeviceState *const D = find_device_state(s, device);
     if (!D) return RT_OK;                                    // nothing was ever rendered there
     HIP_TRY(hipSetDevice(device));
     DeviceClaim claim(D);
     if (!claim.ok) return fail(RT_ERR_STATE, "rt_render_check: another call on this scene is using device %d", device);
     unsigned long long drops = 0;
-    if (D->last_pending && D->last_done) {
-        HIP_TRY(hipEventSynchronize(D->last_done));
-        D->last_pending = false;
-        rt_status st = read_overflow(D, &drops);
-        if (st) return st;
-    }
+    if (rt_status st = collect_pending_verdict(D, &drops)) return st;
     const bool earlier = D->async_overflow;
     D->async_overflow = false;
     if (drops || earlier) {
         D->qhist.valid = false;                             // the next render starts from the worst case again
-        if (drops) HIP_TRY(hipMemset((unsigned long long *)D->stats.p + ST_AT(ST_QUEUE_OVERFLOW), 0, 8));
         return fail(RT_ERR_LIMIT, "rt_render_check: a ray/photon queue overflowed (%llu drops) in an asynchronous render", drops);
     }
     return RT_OK;
@@ -2195,11 +2318,7 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
 {
     if (!s || !out) return fail(RT_ERR_ARG, "rt_render_counters: NULL argument");
     memset(out, 0, sizeof *out);
-    DeviceState *D = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        for (DeviceState *d : s->devs) if (d->device == device) D = d;
-    }
+    DeviceState *const D = find_device_state(s, device);
     if (!D || !D->stats.p) return RT_OK;                     // nothing was ever rendered there
     HIP_TRY(hipSetDevice(device));
     DeviceClaim claim(D);
@@ -2260,7 +2379,7 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
                 }
             }
             // a device copy of every plane that was asked for, starting from the caller's values -- but a strided job takes its
-            // linear plane in its packed records and its features in walk-indexed staging planes (render_tiles_once)
+            // linear plane in its packed records and its features in walk-indexed staging planes (RenderAttempt::setup_outputs)
             RenderRequest req;
             req.job = job;
             req.rec_bytes = job->host.p[PL_LINEAR] ? 24 : 8;
@@ -2399,7 +2518,7 @@ extern "C" rt_status rt_estimate_irradiance(rt_scene *s, int device, int32_t k, 
     g.q.qa = (float4 *)D->t_out[0].p; g.q.qb = (float4 *)D->t_out[1].p; g.q.qc = (float4 *)D->t_out[2].p; g.q.cap = cnt[0];
     g.count = (const uint32_t *)D->t_in.p; g.next_batch = (uint32_t *)D->t_in.p + 1;
     g.out_irr = (float *)D->t_out[3].p; g.out_dir = (float *)D->t_out[4].p;
-    rtk_launch_gather(D->stream, g, GATHER_BLOCKS);
+    rtk_launch_gather(D->stream, g, gather_blocks());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(D->stream));
     HIP_TRY(hipMemcpy(irr, D->t_out[3].p, (size_t)n * 12, hipMemcpyDeviceToHost));
