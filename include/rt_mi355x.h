@@ -518,6 +518,31 @@ rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, const rt_pa
                                   const rt_outputs *host_planes, rt_job **out);
 rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
                                          int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out);
+
+/* ---- the variance plane (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above
+ *      are unchanged -- rt_outputs cannot grow, so the plane is an argument of two new entry points, like the linear plane
+ *      before it) ---------------------------------------------------------------------------------------------------------
+ * variance: float[W*H*3], row-major like rgb_linear: per channel the VARIANCE OF THE MEAN over the samples the colour is
+ * averaged over -- the per-pixel error estimate of the linear plane, and the input of the variance-guided denoiser below.
+ * With H and n as in the feature-plane section above (the hit samples of the pixel's final batch in increasing sample index):
+ *     s1_c = sum over H of (double)x_j,c          s2_c = sum over H of (double)x_j,c * (double)x_j,c      (sample order)
+ *     variance_c = n >= 2 ? (float)( max(0, s2_c - s1_c*s1_c/n) / ((double)n * (n-1)) ) : 0
+ *   - an all-miss pixel holds 0, and so does a pixel with one hit sample (the denoiser's 3 x 3 prefilter makes that usable).
+ *   - pixels of tiles the call does not own, and of chunks not reached before rt_render_stop, keep the caller's values.
+ *   - the one-pass double form is deliberate: products of floats are exact in double, the cancellation is harmless for up to
+ *     2^16 samples, and the sums ride in the pass of k_resolve that already averages the colour (no second pass over the samples).
+ *   - RT_RENDER_REPRODUCIBLE: byte-identical for identical inputs whatever the chunking, streams, tiling, sync / async and
+ *     entry point; in the default mode it inherits the float-atomic last-ulp variation of the samples, like the linear plane.
+ *   - asking for it changes nothing in any other plane (under RT_RENDER_REPRODUCIBLE: the same bytes as without), and nothing
+ *     is allocated or launched for it when it is not asked for.
+ * The two entry points are rt_render_begin_outputs / rt_render_tiles_outputs_device with the plane added: the descriptor checks
+ * are theirs and come before anything is rendered; a NULL variance is RT_ERR_ARG.  The packed (multi-GPU) records do NOT carry
+ * the plane: there is no packed _var entry point, and dist.ShardedRenderer does not know it. */
+rt_status rt_render_begin_outputs_var(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                      const rt_outputs *host_planes, float *variance, rt_job **out);
+rt_status rt_render_tiles_outputs_var_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                             int device, void *hip_stream, const rt_outputs *device_planes, float *variance_dev,
+                                             int sync, rt_stats *stats_out);
 /* Waits for the asynchronous renders (sync == 0) issued so far on (scene, device) and returns
  * RT_ERR_LIMIT if any of them dropped rays or photon queries, RT_OK otherwise. */
 rt_status rt_render_check(rt_scene *s, int device);
@@ -588,6 +613,43 @@ rt_status rt_denoise_device(int device, void *hip_stream, int32_t w, int32_t h, 
                             const rt_denoise_planes *device_planes, int sync);
 /* The planes are HOST arrays: upload, denoise, download. */
 rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes);
+
+/* ---- variance-guided denoising (additive to ABI 4: detected by the presence of the symbols; rt_denoise, rt_denoise_device,
+ *      their structs and their output bytes are unchanged) ---------------------------------------------------------------
+ * The same filter with a per-pixel colour tolerance: each pixel's own standard error (the variance plane above) instead of the
+ * one global sigma_color -- tight where the frame has converged, loose where it is noisy (SVGF's weights, without its temporal
+ * part).  Everything of the "denoising" definition above that is not restated here is unchanged: validity, the id rule,
+ * pass-through, the tap set and order, h, the normal and depth terms, remodulation and the RGB8 rule.
+ *   - Demodulated variance: u_c = variance_c / a_c^2, a the albedo divisor of step 2.  A component of `variance` that is
+ *     negative or not finite counts as 0.
+ *   - Prefilter, per level and per pixel p: ubar_p,c = sum(g * u_q,c) / sum(g) over the 3 x 3 neighbourhood at UNIT step,
+ *     whatever the level, g = {1/4, 1/2, 1/4} in each direction.  The skip rule is the tap's: a neighbour is skipped when it is
+ *     outside the image, invalid, or has another id; the centre is always taken.
+ *   - Colour term, in place of |d_q - d_p|^2 / (sigma_color * 2^-i)^2:
+ *         t_col = sum over c of (d_q,c - d_p,c)^2 / (k_sigma^2 * ubar_p,c + 1e-10)
+ *     sigma_color is validated but not used; there is no 2^-i tightening (the variance shrinks instead).  1e-10 only guards
+ *     0 / 0, it is not a tuning knob.
+ *   - Level output: d'_p = sum(w * d_q) / sum(w) and u'_p,c = sum(w^2 * u_q,c) / sum(w)^2.  Every level reads the previous
+ *     level's complete colour and variance.
+ *   - out_variance_c = u_c * a_c^2 after the last level; for a pass-through pixel it is the input, bit for bit.
+ * No atomics and a fixed tap order: byte-identical for identical inputs on one build.  out_linear may be rgb_linear and
+ * out_variance may be `variance`: the inputs are read completely before any level writes.
+ * rt_denoise_var: struct_size must be the caller's sizeof (anything else: RT_ERR_ARG); `variance` is required; k_sigma positive
+ * and finite.  The checks are rt_denoise's, then these, all before the GPU is touched.  Scratch: 80 bytes per pixel in this mode
+ * (the variance rides in a float4 ping-pong pair of its own), in the same per-device allocation, grown on demand. */
+typedef struct rt_denoise_var {
+    uint32_t struct_size;          /* caller's sizeof, anything else RT_ERR_ARG */
+    const float *variance;         /* required: the variance plane (variance of the mean, per channel) */
+    float *out_variance;           /* optional: the filtered variance, remodulated; may be `variance` */
+    float k_sigma;                 /* 4.0: colour tolerance in standard errors; positive and finite */
+} rt_denoise_var;
+void      rt_denoise_var_default(rt_denoise_var *v);
+/* device planes, like rt_denoise_device */
+rt_status rt_denoise_var_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                                const rt_denoise_planes *device_planes, const rt_denoise_var *v, int sync);
+/* host arrays, like rt_denoise: upload, denoise, download */
+rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise_params *p,
+                              const rt_denoise_planes *host_planes, const rt_denoise_var *v);
 
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */

@@ -76,9 +76,16 @@ class DenoisePlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(DenoisePlanes), **planes)
 
 
-# the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels)
+class DenoiseVar(C.Structure):
+    """rt_denoise_var: the variance block of the variance-guided denoise (rt_denoise_var_default fills k_sigma = 4.0).
+    variance is required, out_variance optional (NULL = not wanted; may be `variance`)."""
+    _fields_ = [("struct_size", C.c_uint32), ("variance", C.c_void_p), ("out_variance", C.c_void_p), ("k_sigma", C.c_float)]
+
+
+# the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels).  "variance" is no field of rt_outputs:
+# it is the extra argument of the _var entry points, which a render takes only when the plane is asked for
 OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
-                 "alpha": ("alpha", np.float32, 1), "object_id": ("object_id", np.int32, 1)}
+                 "alpha": ("alpha", np.float32, 1), "object_id": ("object_id", np.int32, 1), "variance": (None, np.float32, 3)}
 FEATURE_PLANES = ("normal", "albedo", "alpha", "object_id")
 
 
@@ -126,6 +133,8 @@ SYMBOLS = [
     "rt_image_write_pfm", "rt_image_read_pfm",
     "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1",
     "rt_denoise_default_params", "rt_denoise_device", "rt_denoise",
+    "rt_render_begin_outputs_var", "rt_render_tiles_outputs_var_device",
+    "rt_denoise_var_default", "rt_denoise_var_device", "rt_denoise_var_host",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -180,6 +189,15 @@ def lib():
         _lib.rt_denoise_device.argtypes = [C.c_int, vp, i32, i32, vp, vp, C.c_int]
         _lib.rt_denoise.argtypes = [C.c_int, i32, i32, vp, vp]
         _lib.rt_denoise_device.restype = _lib.rt_denoise.restype = C.c_int
+        # the variance plane and the variance-guided denoise (rt_mi355x.h: "the variance plane", "variance-guided denoising")
+        _lib.rt_render_begin_outputs_var.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
+        _lib.rt_render_tiles_outputs_var_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+        _lib.rt_denoise_var_default.argtypes = [vp]
+        _lib.rt_denoise_var_default.restype = None
+        _lib.rt_denoise_var_device.argtypes = [C.c_int, vp, i32, i32, vp, vp, vp, C.c_int]
+        _lib.rt_denoise_var_host.argtypes = [C.c_int, i32, i32, vp, vp, vp]
+        for name in ("rt_render_begin_outputs_var", "rt_render_tiles_outputs_var_device", "rt_denoise_var_device", "rt_denoise_var_host"):
+            getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
                      "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
@@ -326,10 +344,20 @@ def denoise_params(**kw):
     return p
 
 
-def denoise(linear, normal, albedo, z, object_id=None, rgb8=False, device=0, **params):
+def denoise_var(variance_ptr, out_variance_ptr=None, k_sigma=4.0):
+    """rt_denoise_var_default, then the two planes (addresses) and k_sigma"""
+    v = DenoiseVar()
+    lib().rt_denoise_var_default(C.byref(v))
+    v.variance, v.out_variance, v.k_sigma = variance_ptr, out_variance_ptr, k_sigma
+    return v
+
+
+def denoise(linear, normal, albedo, z, object_id=None, rgb8=False, device=0, variance=None, k_sigma=4.0, return_variance=False, **params):
     """The a-trous denoise of a linear frame (rt_denoise; the definition: rt_mi355x.h, "denoising") on host arrays: float32
     (H, W, 3) linear / normal / albedo, float32 (H, W) z, optionally int32 (H, W) object_id.  Returns the denoised float32
-    (H, W, 3) array -- with rgb8=True the pair (denoised, its gamma-encoded uint8 (H, W, 3) image).  params: denoise_params()."""
+    (H, W, 3) array -- with rgb8=True the pair (denoised, its gamma-encoded uint8 (H, W, 3) image).  params: denoise_params().
+    variance (float32 (H, W, 3), the variance plane of the render): the variance-guided filter (rt_denoise_var_host) with a colour
+    tolerance of k_sigma standard errors per pixel; return_variance=True appends the filtered variance (H, W, 3) to the result."""
     linear, normal, albedo = (_c(a, np.float32) for a in (linear, normal, albedo))
     h, w = linear.shape[:2]
     z = _c(z, np.float32)
@@ -341,18 +369,37 @@ def denoise(linear, normal, albedo, z, object_id=None, rgb8=False, device=0, **p
                        object_id=ids.ctypes.data if ids is not None else None, out_linear=out.ctypes.data,
                        out_rgb8=out8.ctypes.data if rgb8 else None)
     p = denoise_params(**params)
-    _check(lib().rt_denoise(int(device), w, h, C.byref(p), C.byref(pl)))
-    return (out, out8) if rgb8 else out
+    if variance is None:
+        if return_variance:
+            raise TypeError("return_variance needs a variance plane")
+        _check(lib().rt_denoise(int(device), w, h, C.byref(p), C.byref(pl)))
+        return (out, out8) if rgb8 else out
+    variance = _c(variance, np.float32)
+    assert variance.shape == (h, w, 3)
+    out_var = np.empty((h, w, 3), np.float32) if return_variance else None
+    v = denoise_var(variance.ctypes.data, out_var.ctypes.data if return_variance else None, k_sigma)
+    _check(lib().rt_denoise_var_host(int(device), w, h, C.byref(p), C.byref(pl), C.byref(v)))
+    res = (out,) + ((out8,) if rgb8 else ()) + ((out_var,) if return_variance else ())
+    return res if len(res) > 1 else out
 
 
 def denoise_device(device, stream, w, h, *, linear_ptr, normal_ptr, albedo_ptr, z_ptr, out_ptr, object_id_ptr=None, rgb8_ptr=None,
-                   sync=True, **params):
+                   sync=True, variance_ptr=None, out_variance_ptr=None, k_sigma=4.0, **params):
     """rt_denoise_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
-    explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr (in place)."""
+    explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr (in place).
+    variance_ptr: the variance-guided filter (rt_denoise_var_device); out_variance_ptr (optional, may be variance_ptr) receives
+    the filtered variance."""
     pl = DenoisePlanes(rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, z=z_ptr, object_id=object_id_ptr,
                        out_linear=out_ptr, out_rgb8=rgb8_ptr)
     p = denoise_params(**params)
-    _check(lib().rt_denoise_device(int(device), _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), 1 if sync else 0))
+    if variance_ptr is None:
+        if out_variance_ptr is not None:
+            raise TypeError("out_variance_ptr needs variance_ptr")
+        _check(lib().rt_denoise_device(int(device), _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), 1 if sync else 0))
+        return
+    v = denoise_var(variance_ptr, out_variance_ptr, k_sigma)
+    _check(lib().rt_denoise_var_device(int(device), _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), C.byref(v),
+                                       1 if sync else 0))
 
 
 def identity_map(texture=MAP_NONE):
@@ -621,10 +668,10 @@ class Scene:
         return rgb, z, cnt, linear, st, progress
 
     def render_outputs(self, cam, params, planes=FEATURE_PLANES, tiles=None, device=0, photon_pass=False, fill=0.0, id_fill=-1):
-        """render() with the optional planes named in `planes` (any of linear, normal, albedo, alpha, object_id), through
-        rt_render_begin_outputs: a dict with rgb, z, count, stats, progress and one array per plane asked for -- float32
-        (H, W, 3) for linear / normal / albedo, float32 (H, W) for alpha, int32 (H, W) for object_id.  Pixels outside
-        `tiles` keep `fill` (object_id: `id_fill`)."""
+        """render() with the optional planes named in `planes` (any of linear, normal, albedo, alpha, object_id, variance),
+        through rt_render_begin_outputs (with "variance": rt_render_begin_outputs_var): a dict with rgb, z, count, stats,
+        progress and one array per plane asked for -- float32 (H, W, 3) for linear / normal / albedo / variance, float32 (H, W)
+        for alpha, int32 (H, W) for object_id.  Pixels outside `tiles` keep `fill` (object_id: `id_fill`)."""
         h, w = cam.height, cam.width
         out = {}
         for name in planes:
@@ -633,24 +680,37 @@ class Scene:
         out["rgb"], out["z"], out["count"], out["stats"], out["progress"] = self._render(cam, params, tiles, device, photon_pass, None, dict(out))
         return out
 
-    def render_denoised(self, cam, params, device=0, photon_pass=False, **denoise_kw):
+    def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, **denoise_kw):
         """render_outputs with the linear plane and the four feature planes, then denoise() of that frame guided by them
         (gamma: the render's): the same dict with "denoised" (float32 (H, W, 3), linear) and "denoised_rgb" (uint8 (H, W, 3))
-        added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth."""
-        out = self.render_outputs(cam, params, planes=("linear",) + FEATURE_PLANES, device=device, photon_pass=photon_pass)
+        added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth.  variance=True: the render also fills
+        out["variance"] and the denoise is the variance-guided one (denoise_kw: also k_sigma); "denoised_variance" is added."""
+        planes = ("linear",) + FEATURE_PLANES + (("variance",) if variance else ())
+        out = self.render_outputs(cam, params, planes=planes, device=device, photon_pass=photon_pass)
         denoise_kw.setdefault("gamma", params.gamma)
+        if variance:
+            out["denoised"], out["denoised_rgb"], out["denoised_variance"] = denoise(
+                out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
+                variance=out["variance"], return_variance=True, **denoise_kw)
+            return out
         out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
                                                        rgb8=True, device=device, **denoise_kw)
         return out
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,
                                     want_stats=True, linear_ptr=None, normal_ptr=None, albedo_ptr=None, alpha_ptr=None,
-                                    object_id_ptr=None):
+                                    object_id_ptr=None, variance_ptr=None):
         """render_tiles_device through rt_render_tiles_outputs_device: every *_ptr that is not None names an image-sized
-        DEVICE plane to fill (float32 x 3 for linear / normal / albedo, float32 for alpha, int32 for object_id)."""
+        DEVICE plane to fill (float32 x 3 for linear / normal / albedo, float32 for alpha, int32 for object_id).
+        variance_ptr (float32 x 3): through rt_render_tiles_outputs_var_device."""
         st = Stats()
         o = Outputs(rgb8=rgb_ptr, z=z_ptr, count=cnt_ptr, rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr,
                     alpha=alpha_ptr, object_id=object_id_ptr)
+        if variance_ptr is not None:
+            _check(lib().rt_render_tiles_outputs_var_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                            _stream_handle(stream), C.byref(o), C.c_void_p(variance_ptr),
+                                                            1 if sync else 0, C.byref(st) if want_stats else None))
+            return st
         _check(lib().rt_render_tiles_outputs_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
                                                     _stream_handle(stream), C.byref(o), 1 if sync else 0,
                                                     C.byref(st) if want_stats else None))
@@ -668,9 +728,13 @@ class Scene:
         job = C.c_void_p()
         if planes is not None:
             o = Outputs(rgb8=rgb.ctypes.data, z=z.ctypes.data, count=cnt.ctypes.data,
-                        **{OUTPUT_PLANES[name][0]: a.ctypes.data for name, a in planes.items()})
-            _check(lib().rt_render_begin_outputs(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
-                                                 C.byref(o), C.byref(job)))
+                        **{OUTPUT_PLANES[name][0]: a.ctypes.data for name, a in planes.items() if name != "variance"})
+            if "variance" in planes:
+                _check(lib().rt_render_begin_outputs_var(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                         C.byref(o), planes["variance"].ctypes.data, C.byref(job)))
+            else:
+                _check(lib().rt_render_begin_outputs(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                     C.byref(o), C.byref(job)))
         elif linear is None:
             _check(lib().rt_render_begin(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
                                          _p(rgb), _p(z), _p(cnt), C.byref(job)))

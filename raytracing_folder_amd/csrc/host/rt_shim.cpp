@@ -14,8 +14,15 @@ void RenderImage::Init(int w, int h)
     zbufferImg.clear(); sampleCountImg.clear();
     if (linearEnabled) linear.assign((size_t)w * h * 3, 0.0f);
     if (featuresEnabled) { featuresEnabled = false; EnableFeatures(); }
-    denoised.clear(); denoisedImg.clear();
+    if (varianceEnabled) variance.assign((size_t)w * h * 3, 0.0f);
+    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
     finalPixels = 0;
+}
+
+void RenderImage::EnableVariance()
+{
+    if (!varianceEnabled) variance.assign((size_t)width * height * 3, 0.0f);
+    varianceEnabled = true;
 }
 
 void RenderImage::EnableFeatures()
@@ -51,9 +58,32 @@ void RenderImage::EnableLinear()
     linearEnabled = true;
 }
 
+bool RenderImage::DenoiseGuided(const rt_denoise_params *params, float k_sigma, int device)
+{
+    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
+    if (!linearEnabled || !featuresEnabled || !varianceEnabled) {
+        denoiseError = "DenoiseGuided() needs EnableLinear(), EnableFeatures() and EnableVariance() before the render";
+        return false;
+    }
+    if (!jobs.empty()) { denoiseError = "DenoiseGuided() while the render is still running"; return false; }
+    rt_denoise_params defaults;
+    rt_denoise_default_params(&defaults);
+    std::vector<float> out((size_t)width * height * 3), outVar((size_t)width * height * 3);
+    std::vector<uint8_t> out8((size_t)width * height * 3);
+    const rt_denoise_planes pl = {(uint32_t)sizeof(rt_denoise_planes), linear.data(), normals.data(), albedo.data(), zbuffer.data(),
+                                  objectIds.data(), out.data(), out8.data()};
+    rt_denoise_var v;
+    rt_denoise_var_default(&v);
+    v.variance = variance.data(); v.out_variance = outVar.data(); v.k_sigma = k_sigma;
+    if (rt_denoise_var_host(device, width, height, params ? params : &defaults, &pl, &v) != RT_OK) { denoiseError = rt_last_error(); return false; }
+    denoised.swap(out); denoisedImg.swap(out8); denoisedVariance.swap(outVar);
+    denoiseError.clear();
+    return true;
+}
+
 bool RenderImage::Denoise(const rt_denoise_params *params, int device)
 {
-    denoised.clear(); denoisedImg.clear();
+    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
     if (!linearEnabled || !featuresEnabled) { denoiseError = "Denoise() needs EnableLinear() and EnableFeatures() before the render"; return false; }
     if (!jobs.empty()) { denoiseError = "Denoise() while the render is still running"; return false; }
     rt_denoise_params defaults;
@@ -137,13 +167,14 @@ bool Renderer::BeginRender()
     if (renderImage.GetWidth() != d.camera.width || renderImage.GetHeight() != d.camera.height)
         renderImage.Init(d.camera.width, d.camera.height);
     if (st == RT_OK) st = rt_scene_set_photon_dump(handle, photonDump.empty() ? nullptr : photonDump.c_str());
+    if (st == RT_OK) st = rt_scene_set_render_flags(handle, renderFlags);
     if (st != RT_OK) { error = rt_last_error(); return false; }
     // one job per device: device r of N renders the interleaved tiles r, r+N, ... into the SAME caller-owned buffers (a job
     // writes only the pixels of its own tiles); whichever job comes first runs the photon pass, the others wait for it
     std::vector<int> devs = devices;
     if (devs.empty()) for (int i = 0, n = rt_device_count(); i < n; i++) devs.push_back(i);
     if (devs.empty()) devs.push_back(0);              // no gfx950 device: rt_render_begin reports it (there is no CPU path)
-    // the optional planes are NULL unless EnableLinear() / EnableFeatures()
+    // the optional planes are NULL unless EnableLinear() / EnableFeatures(); EnableVariance() selects the _var entry point
     const rt_outputs o = {(uint32_t)sizeof(rt_outputs), renderImage.GetPixels(), renderImage.GetZBuffer(), renderImage.GetSampleCount(),
                           renderImage.GetLinearPixels(), renderImage.GetNormals(), renderImage.GetAlbedo(), renderImage.GetAlpha(),
                           renderImage.GetObjectIds()};
@@ -151,7 +182,8 @@ bool Renderer::BeginRender()
     for (int r = 0; r < N; r++) {
         const rt_tile_range mine = {32, 8, r, N};
         rt_job *job = nullptr;
-        st = rt_render_begin_outputs(handle, &d.camera, &params, &mine, devs[r], &o, &job);
+        st = renderImage.GetVariance() ? rt_render_begin_outputs_var(handle, &d.camera, &params, &mine, devs[r], &o, renderImage.GetVariance(), &job)
+                                       : rt_render_begin_outputs(handle, &d.camera, &params, &mine, devs[r], &o, &job);
         if (st != RT_OK) {
             error = rt_last_error();
             for (rt_job *j : jobs) { rt_render_stop(j); rt_render_wait(j); }

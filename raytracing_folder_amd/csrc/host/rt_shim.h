@@ -29,6 +29,10 @@ class RenderImage {
     // Denoise(): the a-trous filter's outputs -- linear float RGB and its gamma-encoded Color24 image
     std::vector<float> denoised;
     std::vector<uint8_t> denoisedImg;
+    // opt-in (EnableVariance): the variance plane of rt_render_begin_outputs_var (variance of the mean, float RGB); after a
+    // DenoiseGuided() denoisedVariance holds the filtered one
+    std::vector<float> variance, denoisedVariance;
+    bool varianceEnabled = false;
     std::string denoiseError;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
@@ -65,6 +69,17 @@ public:
     // without them, or when the GPU call fails, it returns false and DenoiseError() says why.  params == NULL: the defaults
     // of rt_denoise_default_params.  The getters are NULL and the Save functions fail until a Denoise() has succeeded.
     bool Denoise(const rt_denoise_params *params = nullptr, int device = 0);
+    // The variance plane (rt_mi355x.h, "the variance plane"): per channel the variance of the mean of the linear plane, row-major
+    // like GetLinearPixels(); nothing is allocated until EnableVariance() and GetVariance() is NULL without it.
+    // Renderer::BeginRender then renders through rt_render_begin_outputs_var.  SaveVarianceImage writes a three-channel PFM.
+    void EnableVariance();
+    bool VarianceEnabled() const { return varianceEnabled; }
+    float *GetVariance() { return varianceEnabled ? variance.data() : nullptr; }
+    bool SaveVarianceImage(const char *filename) const { return varianceEnabled && WritePFM(filename, variance.data(), width, height); }
+    // Denoise() with each pixel's own standard error as its colour tolerance (rt_denoise_var_host; k_sigma standard errors):
+    // needs EnableVariance() as well before the render.  Fills the same outputs as Denoise(), and GetDenoisedVariance().
+    bool DenoiseGuided(const rt_denoise_params *params = nullptr, float k_sigma = 4.0f, int device = 0);
+    float *GetDenoisedVariance() { return denoisedVariance.empty() ? nullptr : denoisedVariance.data(); }
     const std::string &DenoiseError() const { return denoiseError; }
     float *GetDenoisedPixels() { return denoised.empty() ? nullptr : denoised.data(); }         // linear float RGB
     uint8_t *GetDenoisedImage() { return denoisedImg.empty() ? nullptr : denoisedImg.data(); }  // Color24 after gamma
@@ -91,6 +106,7 @@ public:
     // N takes the interleaved 32 x 8 tiles r, r+N, ... and writes them into the same RenderImage.
     std::vector<int> devices;
     std::string photonDump;      // where generatePhotonMap's .dat goes (FIN/main.cpp:398 hard-codes a path); empty = no dump
+    uint32_t renderFlags = 0;    // rt_scene_set_render_flags at BeginRender: 0, or RT_RENDER_REPRODUCIBLE (byte-identical renders)
 
     Renderer();
     ~Renderer();

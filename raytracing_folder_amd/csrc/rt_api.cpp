@@ -300,13 +300,15 @@ struct rt_scene {
 // ---- render outputs -------------------------------------------------------------------------------------
 // The planes of rt_outputs in field order, with their bytes per pixel.  Internally a render's outputs are one Planes set
 // indexed by this table; a NULL plane is not wanted, and nothing is allocated or launched for it.  PL_NORMAL .. PL_ID are the
-// first-hit features (k_features).
-enum Plane { PL_RGB8, PL_Z, PL_COUNT, PL_LINEAR, PL_NORMAL, PL_ALBEDO, PL_ALPHA, PL_ID, N_PLANES };
-static const size_t PLANE_BYTES[N_PLANES] = {3, 4, 1, 12, 12, 12, 4, 4};
+// first-hit features (k_features).  PL_VARIANCE is not a field of rt_outputs (the struct cannot grow): it is the extra argument
+// of the _var entry points, written by k_resolve's VAR instantiations.
+enum Plane { PL_RGB8, PL_Z, PL_COUNT, PL_LINEAR, PL_NORMAL, PL_ALBEDO, PL_ALPHA, PL_ID, PL_VARIANCE, N_PLANES };
+static const size_t PLANE_BYTES[N_PLANES] = {3, 4, 1, 12, 12, 12, 4, 4, 12};
 struct Planes {
     void *p[N_PLANES] = {};
     Planes() = default;
-    explicit Planes(const rt_outputs &o) : p{o.rgb8, o.z, o.count, o.rgb_linear, o.normal, o.albedo, o.alpha, o.object_id} {}
+    explicit Planes(const rt_outputs &o, float *variance = nullptr)
+        : p{o.rgb8, o.z, o.count, o.rgb_linear, o.normal, o.albedo, o.alpha, o.object_id, variance} {}
     template <class T> T *at(int i) const { return (T *)p[i]; }
     DevFeatures features() const            // the planes k_features writes (rtk_launch_features)
     {
@@ -1619,7 +1621,7 @@ struct TileWalk {
 
 // What one render call writes, and how: image-sized device planes (`dev`; rgb_linear selects the linear plane, the features
 // k_features), or packed records of the call's tiles (`packed`: rec_bytes 8, or 24 with the linear plane).  A strided job
-// (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature staging planes of its own.
+// (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature / variance staging planes of its own.
 struct RenderRequest {
     Planes dev;
     void *packed = nullptr;
@@ -1664,6 +1666,7 @@ struct RenderAttempt {
     size_t rec_bytes = 8;               // bytes per packed record: 8, or 24 with the linear plane (the 8-byte record, linear r, g, b, 4 zero bytes)
     bool job_packed = false, linear = false, feat_by_walk = false;
     DevFeatures fdev;
+    float *variance_dev = nullptr;      // where k_resolve writes the variance plane (NULL: not asked for)
     // timing and completion events; chunks in flight (job mode), delivered oldest-first for progress and the band copy
     Timing tm[RT_STREAMS];
     Event e_begin, e_end, e_fork;
@@ -1778,16 +1781,19 @@ struct RenderAttempt {
         linear = packed_dev ? rec_bytes == 24 : req.dev.p[PL_LINEAR] != nullptr;
         // where k_features writes: the caller's image-sized device planes, or -- a strided job, whose rows are shared with other jobs --
         // staging planes indexed by this call's tile walk, scattered on the host like the packed records (scatter_packed)
+        // the variance plane goes the same two ways (k_resolve indexes it by the walk when it writes packed records)
         fdev = req.dev.features();
+        variance_dev = req.dev.at<float>(PL_VARIANCE);
         feat_by_walk = features && job_packed;
-        if (feat_by_walk) {
+        if (job_packed) {
             Planes staged;
             for (int i = PL_NORMAL; i < N_PLANES; i++) {
                 if (!job->host.p[i]) continue;
                 if ((st = stage[i].ensure(std::max<uint64_t>(total_px, 1) * PLANE_BYTES[i]))) return st;
                 staged.p[i] = stage[i].p;
             }
-            fdev = staged.features();
+            if (feat_by_walk) fdev = staged.features();
+            variance_dev = staged.at<float>(PL_VARIANCE);
         }
         return RT_OK;
     }
@@ -1858,7 +1864,7 @@ struct RenderAttempt {
         ra.threshold = p->threshold; memcpy(ra.bg, D->scene.bg, sizeof ra.bg); ra.S = D->scene;
         ra.inv_gamma = (float)(1.0 / p->gamma);                 // powf(x, 1.0/gamma): double quotient narrowed to float
         ra.rgb8 = req.dev.at<uint8_t>(PL_RGB8); ra.z = req.dev.at<float>(PL_Z); ra.count = req.dev.at<uint8_t>(PL_COUNT);
-        ra.packed = (uint2 *)packed_dev; ra.rgb_linear = req.dev.at<float>(PL_LINEAR);
+        ra.packed = (uint2 *)packed_dev; ra.rgb_linear = req.dev.at<float>(PL_LINEAR); ra.variance = variance_dev;
         if (resolve_waits[slot]) { HIP_TRY(hipStreamWaitEvent(cs, e_fork, 0)); resolve_waits[slot] = false; }
         if ((st = resolve(cs, W, ra, 0))) return st;
         if (p->max_sample > p->min_sample) {
@@ -1882,7 +1888,7 @@ struct RenderAttempt {
 
     // A strided tile range (one job per device on the same caller-owned image): rows are shared with other jobs' tiles,
     // so only this job's pixels may be written -- the chunk's packed 8-byte (24-byte: linear) records come back in one
-    // copy and are scattered on the host through the tile walk, and so is the chunk's run of each staged feature plane.
+    // copy and are scattered on the host through the tile walk, and so is the chunk's run of each staged plane (features, variance).
     rt_status scatter_packed(const InFlight &f)
     {
         const TileWalk w = walk();
@@ -2066,13 +2072,14 @@ static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params
 // RenderPixel's outputs (FIN/main.cpp:273-338) into the caller's device planes, with the optional ones of rt_outputs: the linear
 // colour and the first hit's normal, albedo, coverage and node (k_features)
 static rt_status render_device(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                               int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out)
+                               int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out,
+                               float *variance_dev = nullptr)
 {
     if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", name);
     rt_status st = check_outputs(name, device_planes);
     if (st) return st;
     RenderRequest req;
-    req.dev = Planes(*device_planes);
+    req.dev = Planes(*device_planes, variance_dev);
     req.stream = (hipStream_t)hip_stream; req.sync = sync != 0; req.stats_out = stats_out;
     return render_tiles(s, cam, p, tiles, device, req);
 }
@@ -2098,6 +2105,14 @@ extern "C" rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera
                                                     int device, void *hip_stream, const rt_outputs *device_planes, int sync, rt_stats *stats_out)
 {
     return render_device("rt_render_tiles_outputs_device", s, cam, p, tiles, device, hip_stream, device_planes, sync, stats_out);
+}
+
+extern "C" rt_status rt_render_tiles_outputs_var_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                        int device, void *hip_stream, const rt_outputs *device_planes, float *variance_dev,
+                                                        int sync, rt_stats *stats_out)
+{
+    if (!variance_dev) return fail(RT_ERR_ARG, "rt_render_tiles_outputs_var_device: the variance plane is required");
+    return render_device("rt_render_tiles_outputs_var_device", s, cam, p, tiles, device, hip_stream, device_planes, sync, stats_out, variance_dev);
 }
 
 // both packed entry points: 8-byte records, or 24-byte ones with the linear plane (linear)
@@ -2239,8 +2254,27 @@ static float denoise_inv_gamma(float gamma)
     return (float)(1.0 / strtod(buf, nullptr));
 }
 
+extern "C" void rt_denoise_var_default(rt_denoise_var *v)
+{
+    if (!v) return;
+    v->struct_size = (uint32_t)sizeof *v;
+    v->variance = nullptr; v->out_variance = nullptr; v->k_sigma = 4.0f;
+}
+
+// the variance block of the _var entry points, after denoise_check and like it without a device
+static rt_status denoise_var_check(const char *name, const rt_denoise_var *v)
+{
+    if (!v) return fail(RT_ERR_ARG, "%s: the variance block is NULL", name);
+    if (v->struct_size != (uint32_t)sizeof(rt_denoise_var))
+        return fail(RT_ERR_ARG, "%s: rt_denoise_var.struct_size is %u, this library's is %zu", name, v->struct_size, sizeof(rt_denoise_var));
+    if (!v->variance) return fail(RT_ERR_ARG, "%s: the variance plane is required", name);
+    if (!(v->k_sigma > 0.0f) || !std::isfinite(v->k_sigma)) return fail(RT_ERR_ARG, "%s: k_sigma must be positive and finite", name);
+    return RT_OK;
+}
+
+// v == NULL: the fixed-sigma filter; otherwise the variance-guided one (v is checked by the caller)
 static rt_status denoise_on_device(const char *name, int device, hipStream_t st, int32_t w, int32_t h, const rt_denoise_params *p,
-                                   const rt_denoise_planes *pl, int sync)
+                                   const rt_denoise_planes *pl, int sync, const rt_denoise_var *v = nullptr)
 {
     if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
     HIP_TRY(hipSetDevice(device));
@@ -2249,7 +2283,8 @@ static rt_status denoise_on_device(const char *name, int device, hipStream_t st,
     for (auto &d : g_denoise) if (d.first == device) D = &d.second;
     if (!D) { g_denoise.emplace_back(device, DenoiseDevice()); D = &g_denoise.back().second; }
     const size_t n = (size_t)w * (size_t)h;
-    rt_status rs = D->scratch.ensure(n * RT_DENOISE_SCRATCH_PER_PIXEL);     // growing frees the old one, which waits for its users
+    // growing frees the old one, which waits for its users
+    rt_status rs = D->scratch.ensure(n * (v ? RT_DENOISE_SCRATCH_PER_PIXEL_VAR : RT_DENOISE_SCRATCH_PER_PIXEL));
     if (rs) return rs;
     if (!D->done) HIP_TRY(hipEventCreateWithFlags(&D->done, hipEventDisableTiming));
     if (D->pending) HIP_TRY(hipStreamWaitEvent(st, D->done, 0));
@@ -2259,6 +2294,10 @@ static rt_status denoise_on_device(const char *name, int device, hipStream_t st,
     R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id;
     R.out_linear = pl->out_linear; R.out_rgb8 = pl->out_rgb8;
     R.color[0] = (float4 *)D->scratch.p; R.color[1] = R.color[0] + n; R.guide = R.color[1] + n;
+    if (v) {
+        R.variance = v->variance; R.out_variance = v->out_variance; R.k_sigma = v->k_sigma;
+        R.var[0] = R.guide + n; R.var[1] = R.var[0] + n;
+    }
     rtk_launch_denoise_frame(st, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(D->done, st));
@@ -2292,6 +2331,37 @@ extern "C" rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoi
     if ((st = denoise_on_device("rt_denoise", device, nullptr, w, h, p, &dev, 1))) return st;
     HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
     if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_denoise_var_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                                           const rt_denoise_planes *device_planes, const rt_denoise_var *v, int sync)
+{
+    rt_status st = denoise_check("rt_denoise_var_device", w, h, p, device_planes);
+    if (st || (st = denoise_var_check("rt_denoise_var_device", v))) return st;
+    return denoise_on_device("rt_denoise_var_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync, v);
+}
+
+extern "C" rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes,
+                                         const rt_denoise_var *v)
+{
+    rt_status st = denoise_check("rt_denoise_var_host", w, h, p, host_planes);
+    if (st || (st = denoise_var_check("rt_denoise_var_host", v))) return st;
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_denoise_var_host: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)w * (size_t)h;
+    ScopedDevBuf rgb, normal, albedo, z, id, rgb8, var;             // the results are written in place into rgb and var
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
+        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4)) || (st = var.upload(v->variance, n * 12))) return st;
+    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
+    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
+    rt_denoise_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
+                             (const int32_t *)id.p, (float *)rgb.p, (uint8_t *)rgb8.p};
+    const rt_denoise_var dv = {(uint32_t)sizeof dv, (const float *)var.p, v->out_variance ? (float *)var.p : nullptr, v->k_sigma};
+    if ((st = denoise_on_device("rt_denoise_var_host", device, nullptr, w, h, p, &dev, 1, &dv))) return st;
+    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    if (v->out_variance) HIP_TRY(hipMemcpy(v->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -2342,7 +2412,7 @@ static rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons,
 // BeginRender (FIN/main.cpp:984-1010): rt_render_begin, rt_render_begin_linear and rt_render_begin_outputs, with the planes
 // RenderPixel (:273-338) could have kept: its colour before gamma, and the first hit's normal, albedo, coverage and node
 static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              const rt_outputs *host_planes, rt_job **out)
+                              const rt_outputs *host_planes, rt_job **out, float *variance = nullptr)
 {
     if (!s || !out) return fail(RT_ERR_ARG, "%s: scene/out is NULL", name);
     rt_status st = check_outputs(name, host_planes);
@@ -2352,7 +2422,7 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
     if ((st = prepare_device(s, device, &D))) return st;      // fail early (and loudly) when there is no GPU
     rt_job *job = new rt_job;
     job->scene = s;
-    job->host = Planes(*host_planes);
+    job->host = Planes(*host_planes, variance);
     s->live_jobs.fetch_add(1);
     const rt_camera camv = *cam; const rt_params pv = *p; const rt_tile_range tv = *tiles;
     job->worker = std::thread([=]() {
@@ -2379,7 +2449,8 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
                 }
             }
             // a device copy of every plane that was asked for, starting from the caller's values -- but a strided job takes its
-            // linear plane in its packed records and its features in walk-indexed staging planes (RenderAttempt::setup_outputs)
+            // linear plane in its packed records and its features and variance in walk-indexed staging planes
+            // (RenderAttempt::setup_outputs)
             RenderRequest req;
             req.job = job;
             req.rec_bytes = job->host.p[PL_LINEAR] ? 24 : 8;
@@ -2422,6 +2493,13 @@ extern "C" rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, 
                                              const rt_outputs *host_planes, rt_job **out)
 {
     return render_begin("rt_render_begin_outputs", s, cam, p, tiles, device, host_planes, out);
+}
+
+extern "C" rt_status rt_render_begin_outputs_var(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                                 const rt_outputs *host_planes, float *variance, rt_job **out)
+{
+    if (!variance) return fail(RT_ERR_ARG, "rt_render_begin_outputs_var: the variance plane is required");
+    return render_begin("rt_render_begin_outputs_var", s, cam, p, tiles, device, host_planes, out, variance);
 }
 
 extern "C" int rt_render_progress(rt_job *j) { return j ? j->progress.load() : 0; }

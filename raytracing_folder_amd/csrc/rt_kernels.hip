@@ -1866,7 +1866,8 @@ void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs
 #endif
 // LIN: also the linear plane (ResolveArgs::rgb_linear), or 24-byte packed records; the default instantiation is the kernel
 // as it was
-template <bool LIN = false>
+// VAR: also the variance plane (ResolveArgs::variance): the two double sums of its definition ride in the averaging pass
+template <bool LIN = false, bool VAR = false>
 __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
 {
     // A pixel's samples are contiguous (max_sample slots of 12 B), so a thread walking its own pixel reads 12 B
@@ -1982,11 +1983,24 @@ __global__ __launch_bounds__(256) void k_resolve(DevWork W, ResolveArgs A)
             if (over) W.pixel_list[atomicAdd(&W.counts[CNT_PIXLIST], 1u)] = ql;
         }
         float c0 = 0, c1 = 0, c2 = 0;
+        double s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};                // VAR: sum and sum of squares in sample order (float products are exact in double)
         if (staged || n > 0) {
             const float inv = 1 / (float)(n > 0 ? n : 1);
-            for_hit_samples([&](float r, float g, float b) { c0 += r * inv; c1 += g * inv; c2 += b * inv; });
+            for_hit_samples([&](float r, float g, float b) {
+                c0 += r * inv; c1 += g * inv; c2 += b * inv;
+                if constexpr (VAR) {
+                    s1[0] += (double)r; s1[1] += (double)g; s1[2] += (double)b;
+                    s2[0] += (double)r * (double)r; s2[1] += (double)g * (double)g; s2[2] += (double)b * (double)b;
+                }
+            });
         }
         if (!valid || over) continue;
+        if constexpr (VAR) {
+            // variance of the mean, max(0, s2 - s1^2 / n) / (n (n - 1)); 0 for fewer than two hit samples
+            float *v = A.variance + 3 * (A.packed ? (size_t)A.q0 + ql : index);
+            for (int c = 0; c < 3; c++)
+                v[c] = n >= 2 ? (float)(fmax(0.0, s2[c] - s1[c] * s1[c] / (double)n) / ((double)n * (double)(n - 1))) : 0.0f;
+        }
         float g[3];
         uint8_t cnt_byte = 0;
         float zval = BIGFLOAT;
@@ -2343,6 +2357,10 @@ void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &R, 
     ResolveArgs A = R;
     tiles_prepare(A.tiles);
     const int grid = grid_for(A.npix, 256, max_blocks);
-    if (linear) hipLaunchKernelGGL(k_resolve<true>, dim3(grid), dim3(256), 0, st, W, A);
+    if (A.variance) {
+        if (linear) hipLaunchKernelGGL((k_resolve<true, true>), dim3(grid), dim3(256), 0, st, W, A);
+        else hipLaunchKernelGGL((k_resolve<false, true>), dim3(grid), dim3(256), 0, st, W, A);
+    }
+    else if (linear) hipLaunchKernelGGL(k_resolve<true>, dim3(grid), dim3(256), 0, st, W, A);
     else hipLaunchKernelGGL(k_resolve<false>, dim3(grid), dim3(256), 0, st, W, A);
 }

@@ -54,6 +54,10 @@ struct ResolveArgs {
     // linear plane (k_resolve<true> only): the pre-gamma float RGB of the pixel, row-major like rgb8; in packed mode the
     // record grows to 24 bytes instead -- {the 8-byte record, linear r, g, b as f32, 4 zero bytes} at packed + 24*q
     float *rgb_linear;
+    // variance plane (the VAR instantiations only): the variance of the mean per channel over the samples the colour is averaged
+    // over (rt_mi355x.h, "the variance plane"), float[3] per pixel, row-major like rgb8 -- or, when `packed` is set (a strided
+    // job), indexed like the packed records by the call's tile walk: 12 bytes at variance + 3 * (q0 + q)
+    float *variance;
 };
 
 // the photon pass: attempts first_attempt .. first_attempt + n_attempts of the counter RNG's sequence
@@ -78,13 +82,19 @@ struct UnpackRequest {
 // One denoise of a width x height frame (rt_denoise.hip; the definition: rt_mi355x.h, "denoising").  The planes are the caller's
 // device pointers (object_id and out_rgb8 may be NULL; out_linear may be rgb_linear), the sigmas are validated by the caller.
 // color[0], color[1] and guide are the per-device scratch, width * height float4 each (RT_DENOISE_SCRATCH_PER_PIXEL bytes a pixel).
+// Variance-guided (rt_mi355x.h, "variance-guided denoising"): `variance` is set, var[0] and var[1] are two more float4 buffers of
+// the scratch (the demodulated variance's ping-pong pair: RT_DENOISE_SCRATCH_PER_PIXEL_VAR bytes a pixel in all), out_variance
+// may be NULL or `variance`; sigma_color is not used then.
 #define RT_DENOISE_SCRATCH_PER_PIXEL 48
+#define RT_DENOISE_SCRATCH_PER_PIXEL_VAR 80
 struct DenoiseRequest {
     int width, height, levels;
     float sigma_color, sigma_normal, sigma_depth, inv_gamma;
     const float *rgb_linear, *normal, *albedo, *z; const int32_t *object_id;
     float *out_linear; uint8_t *out_rgb8;
     float4 *color[2], *guide;
+    const float *variance; float *out_variance; float k_sigma;
+    float4 *var[2];
 };
 
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
@@ -107,7 +117,7 @@ void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float 
 // Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
 void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *fx, size_t samples);
 // k_resolve over A.npix pixels, at most max_blocks workgroups (tiles_prepare is run on a copy of A.tiles).  linear: the LIN
-// instantiation -- the linear plane A.rgb_linear, or 24-byte records when A.packed is set.
+// instantiation -- the linear plane A.rgb_linear, or 24-byte records when A.packed is set.  A.variance selects the VAR one.
 void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &A, int max_blocks, bool linear);
 void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R);
 // The feature planes of one chunk (pass.cam, tiles, q0, npix), after its last k_resolve on the same stream: the second-batch
