@@ -651,6 +651,89 @@ rt_status rt_denoise_var_device(int device, void *hip_stream, int32_t w, int32_t
 rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise_params *p,
                               const rt_denoise_planes *host_planes, const rt_denoise_var *v);
 
+/* ---- temporal accumulation (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above
+ *      are unchanged) ------------------------------------------------------------------------------------------------------
+ * The temporal part the variance-guided filter leaves out: a viewer or a fly-through renders the same STATIC scene frame after
+ * frame with independent noise, and an rt_history blends each new frame into what the earlier ones left, reprojected from the
+ * camera of the frame it holds into the new one.  Like the denoiser it is an image-space operation on image-sized planes (row-
+ * major, W x H) and knows nothing of scenes; only the camera may move between frames (no motion vectors).  The accumulated
+ * colour and variance are what rt_denoise_var_* takes as rgb_linear and variance.  The reference has no counterpart.
+ * Definition, per pixel p = (x, y) of the new frame:
+ *   1. Validity and demodulation are the denoiser's steps 1-2: p is VALID when object_id >= 0 (id plane given) or z < 1e30 (no
+ *      id plane); a_c = albedo_c > 1e-3f ? albedo_c : 1.0f; d = rgb_linear / a; u_c = variance_c / a_c^2, where a component of
+ *      `variance` that is negative or not finite counts as 0, and u = 0 without a variance plane.  A pixel that is invalid, or
+ *      whose colour d is not finite, PASSES THROUGH: out_linear and out_variance are its inputs bit for bit, out_history is 0,
+ *      it stores history length 0 and contributes to no later frame.
+ *   2. Camera.  With the quantities of the render's camera set-up -- l = focaldist, h = 2 l tan(fov / 2), w = h W / H,
+ *      u = w / W, v = -h / H, b = (-w/2 + u/2, h/2 + v/2, -l) (the half-pixel shift included), and the orthonormal rows
+ *      x_new = up x (-dir), up, z_new = -dir, M the matrix with these as its columns -- the pixel's representative ray goes
+ *      through s(x, y) = (b.x + (x + 0.5) u, b.y + (y + 0.5) v, -l): the centre of the area its Halton-jittered samples
+ *      cover.  World point: P = pos + z_p * normalize(M s).  `dof` is ignored: z of a depth-of-field frame is measured from a
+ *      point of the lens, so P -- and with it the reprojection -- is off by at most dof.
+ *   3. Reprojection into the STORED camera (primed: the camera of the frame the history holds):
+ *      q = (x_new', up', z_new') . (P - pos'); no history if q.z >= 0; s' = q * (-l' / q.z);
+ *      fx = (s'.x - b'.x) / u' - 0.5, fy = (s'.y - b'.y) / v' - 0.5; z_exp = |P - pos'|.
+ *   4. Bilinear taps: x0 = floor(fx), y0 = floor(fy); the taps (x0 + i, y0 + j) in the order (0,0), (1,0), (0,1), (1,1) with
+ *      the weights (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty, tx = fx - x0, ty = fy - y0.  A tap is ACCEPTED when it lies inside
+ *      the image, its stored length is N > 0, its stored id equals p's (id plane given; a frame without an id plane stores id 0),
+ *      |n_tap - n_p|^2 <= sigma_normal^2 (normals as stored) and |z_tap - z_exp| <= sigma_depth * max(z_tap, z_exp).  W is
+ *      the sum of the accepted weights; p HAS A HISTORY iff the rt_history holds a frame, q.z < 0 and W >= 0.01.
+ *   5. Blend.  With a history: d_h = sum(w d_tap) / W, u_h = sum(w u_tap) / W, N_h = sum(w N_tap) / W (evaluated as
+ *      N_0 + sum(w (N_tap - N_0)) / W with N_0 the first accepted tap's length: taps of equal length give exactly that length);
+ *      N = min(N_h + 1, max_history), beta = max(alpha, 1 / N), d' = (1 - beta) d_h + beta d,
+ *      u' = (1 - beta)^2 u_h + beta^2 u (u is a variance of the mean: it propagates exactly through the blend of independent
+ *      frames).  Without: N = 1, d' = d, u' = u.  Stored for the next frame: d', u', N, z_p, n_p, id_p (0 without an id
+ *      plane) per pixel, and the camera.
+ *   6. Outputs: out_linear = d' a, out_variance = u' a^2, out_history = N (float), out_rgb8 by step 5 of "denoising"
+ *      (Color24(powf(out_linear, 1/gamma)), the same exponent rule).
+ * No atomics and a fixed tap order: the outputs are byte-identical for an identical sequence of calls on one build.  out_linear
+ * may be rgb_linear and out_variance may be `variance`: a pixel's inputs are read, by the one lane that writes it, before
+ * anything of that pixel is written, and the taps read the history only.  No other planes may overlap.
+ * rt_history owns the device planes of one W x H stream of frames on one device: two ping-pong sets of three 16-byte records
+ * per pixel ({d, z}, {u, N}, {n, id}), 96 bytes a pixel in one allocation, and the camera of the frame it holds.  Calls on one
+ * history are ordered on the GPU one behind the other, whatever their streams.  Frames of several histories do not disturb
+ * each other.
+ * rt_temporal_params: alpha in (0, 1]; max_history 1..65535; sigma_normal, sigma_depth and gamma positive and finite (gamma is
+ * used only for out_rgb8).  rt_temporal_planes: rgb_linear, normal, albedo, z and out_linear are required, the others optional
+ * (NULL = not given); out_variance needs variance.  struct_size must be the caller's sizeof for both structs.  Everything is
+ * checked before the GPU is touched and is RT_ERR_ARG: NULL arguments, a struct_size, a parameter out of range or not finite, a
+ * missing plane, out_variance without variance, a NULL history, cam->width or cam->height differing from the history's.
+ * rt_history_create: w, h <= 0 or out == NULL is RT_ERR_ARG, more than 2^30 pixels RT_ERR_LIMIT, no gfx950 device
+ * RT_ERR_NO_DEVICE (there is no CPU path). */
+typedef struct rt_history rt_history;
+rt_status rt_history_create(int device, int32_t w, int32_t h, rt_history **out);
+/* the next frame starts from nothing; ordered behind the earlier calls on this history */
+rt_status rt_history_reset(rt_history *hst);
+/* NULL is ignored; waits for the work that still uses it */
+void      rt_history_destroy(rt_history *hst);
+/* frames accumulated since create / reset (0 for NULL) */
+int32_t   rt_history_frames(const rt_history *hst);
+typedef struct rt_temporal_params {
+    uint32_t struct_size;
+    float    alpha;             /* 0.2  : floor of the blend weight, (0, 1]                        */
+    int32_t  max_history;       /* 32   : cap of the per-pixel history length, 1..65535            */
+    float    sigma_normal;      /* 0.3  : a tap is rejected when |n_tap - n_p|^2 > sigma_normal^2  */
+    float    sigma_depth;       /* 0.05 : ... or |z_tap - z_exp| > sigma_depth * max(z_tap, z_exp) */
+    float    gamma;             /* 2.2  : out_rgb8 only                                            */
+} rt_temporal_params;
+typedef struct rt_temporal_planes {
+    uint32_t struct_size;
+    const float *rgb_linear, *normal, *albedo, *z;
+    const int32_t *object_id;   /* optional */
+    const float *variance;      /* optional */
+    float *out_linear;
+    float *out_variance;        /* optional, needs variance */
+    float *out_history;         /* optional, float W*H: N_p */
+    uint8_t *out_rgb8;          /* optional */
+} rt_temporal_planes;
+void      rt_temporal_default_params(rt_temporal_params *p);
+/* The planes are DEVICE pointers on the history's device; the kernel is enqueued on `hip_stream` (NULL = the device's legacy
+ * null stream) and the call returns without waiting for it unless `sync` is non-zero. */
+rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                             const rt_temporal_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, accumulate, download. */
+rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes);
+
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */
 /* n closest-hit queries = n calls of TraceNode(rootNode, ray, hit) (FIN/main.cpp:94-130).

@@ -82,6 +82,23 @@ class DenoiseVar(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("variance", C.c_void_p), ("out_variance", C.c_void_p), ("k_sigma", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    """rt_temporal_params: the temporal accumulation's parameters (rt_temporal_default_params fills 0.2 / 32 / 0.3 / 0.05 / 2.2)"""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("max_history", C.c_int32), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("gamma", C.c_float)]
+
+
+class TemporalPlanes(C.Structure):
+    """rt_temporal_planes: the inputs and outputs of one accumulated frame.  object_id, variance, out_variance (needs variance),
+    out_history and out_rgb8 are optional (NULL = not given)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
+                ("z", C.c_void_p), ("object_id", C.c_void_p), ("variance", C.c_void_p), ("out_linear", C.c_void_p),
+                ("out_variance", C.c_void_p), ("out_history", C.c_void_p), ("out_rgb8", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(TemporalPlanes), **planes)
+
+
 # the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels).  "variance" is no field of rt_outputs:
 # it is the extra argument of the _var entry points, which a render takes only when the plane is asked for
 OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
@@ -135,6 +152,8 @@ SYMBOLS = [
     "rt_denoise_default_params", "rt_denoise_device", "rt_denoise",
     "rt_render_begin_outputs_var", "rt_render_tiles_outputs_var_device",
     "rt_denoise_var_default", "rt_denoise_var_device", "rt_denoise_var_host",
+    "rt_history_create", "rt_history_reset", "rt_history_destroy", "rt_history_frames",
+    "rt_temporal_default_params", "rt_temporal_device", "rt_temporal",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -197,6 +216,19 @@ def lib():
         _lib.rt_denoise_var_device.argtypes = [C.c_int, vp, i32, i32, vp, vp, vp, C.c_int]
         _lib.rt_denoise_var_host.argtypes = [C.c_int, i32, i32, vp, vp, vp]
         for name in ("rt_render_begin_outputs_var", "rt_render_tiles_outputs_var_device", "rt_denoise_var_device", "rt_denoise_var_host"):
+            getattr(_lib, name).restype = C.c_int
+        # temporal accumulation (rt_mi355x.h: "temporal accumulation")
+        _lib.rt_history_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        _lib.rt_history_reset.argtypes = [vp]
+        _lib.rt_history_destroy.argtypes = [vp]
+        _lib.rt_history_destroy.restype = None
+        _lib.rt_history_frames.argtypes = [vp]
+        _lib.rt_history_frames.restype = i32
+        _lib.rt_temporal_default_params.argtypes = [vp]
+        _lib.rt_temporal_default_params.restype = None
+        _lib.rt_temporal_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
+        _lib.rt_temporal.argtypes = [vp, vp, vp, vp]
+        for name in ("rt_history_create", "rt_history_reset", "rt_temporal_device", "rt_temporal"):
             getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
@@ -400,6 +432,92 @@ def denoise_device(device, stream, w, h, *, linear_ptr, normal_ptr, albedo_ptr, 
     v = denoise_var(variance_ptr, out_variance_ptr, k_sigma)
     _check(lib().rt_denoise_var_device(int(device), _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), C.byref(v),
                                        1 if sync else 0))
+
+
+_denoise = denoise       # for Scene.render_temporal, whose `denoise` argument hides the function
+
+
+def temporal_params(**kw):
+    """rt_temporal_default_params, then the keywords (alpha, max_history, sigma_normal, sigma_depth, gamma)"""
+    p = TemporalParams()
+    lib().rt_temporal_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("alpha", "max_history", "sigma_normal", "sigma_depth", "gamma"):
+            raise TypeError(f"no temporal parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+class History:
+    """rt_history: the accumulated frames of one W x H stream on one device (the definition: rt_mi355x.h, "temporal
+    accumulation").  Every accumulate blends a new frame of a STATIC scene into what the earlier ones left, reprojected from the
+    camera of the previous call into `cam`.  A context manager; close() (or the end of the with block) frees the device planes."""
+
+    def __init__(self, device, w, h):
+        self._h = C.c_void_p()
+        self.device, self.width, self.height = int(device), int(w), int(h)
+        _check(lib().rt_history_create(self.device, self.width, self.height, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rt_history_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """the next frame starts from nothing"""
+        _check(lib().rt_history_reset(self._h))
+
+    @property
+    def frames(self):
+        """frames accumulated since the creation or the last reset()"""
+        return int(lib().rt_history_frames(self._h))
+
+    def accumulate(self, cam, linear, normal, albedo, z, object_id=None, variance=None, rgb8=False, return_history=False, **params):
+        """rt_temporal on host arrays: float32 (H, W, 3) linear / normal / albedo, float32 (H, W) z, optionally int32 (H, W)
+        object_id and float32 (H, W, 3) variance.  Returns the accumulated float32 (H, W, 3) colour, followed -- as a tuple --
+        by the accumulated variance (when `variance` is given), the gamma-encoded uint8 image (rgb8=True) and the per-pixel
+        history length, float32 (H, W) (return_history=True).  params: temporal_params()."""
+        linear, normal, albedo = (_c(a, np.float32) for a in (linear, normal, albedo))
+        h, w = self.height, self.width
+        z = _c(z, np.float32)
+        ids = _c(object_id, np.int32) if object_id is not None else None
+        var = _c(variance, np.float32) if variance is not None else None
+        assert linear.shape == normal.shape == albedo.shape == (h, w, 3) and z.shape == (h, w)
+        assert (ids is None or ids.shape == (h, w)) and (var is None or var.shape == (h, w, 3))
+        out = np.empty((h, w, 3), np.float32)
+        out_var = np.empty((h, w, 3), np.float32) if var is not None else None
+        out8 = np.empty((h, w, 3), np.uint8) if rgb8 else None
+        hist = np.empty((h, w), np.float32) if return_history else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        pl = TemporalPlanes(rgb_linear=ptr(linear), normal=ptr(normal), albedo=ptr(albedo), z=ptr(z), object_id=ptr(ids), variance=ptr(var),
+                            out_linear=ptr(out), out_variance=ptr(out_var), out_history=ptr(hist), out_rgb8=ptr(out8))
+        p = temporal_params(**params)
+        _check(lib().rt_temporal(self._h, C.byref(cam), C.byref(p), C.byref(pl)))
+        res = (out,) + tuple(a for a in (out_var, out8, hist) if a is not None)
+        return res if len(res) > 1 else out
+
+    def accumulate_device(self, stream, cam, *, linear_ptr, normal_ptr, albedo_ptr, z_ptr, out_ptr, object_id_ptr=None, variance_ptr=None,
+                          out_variance_ptr=None, history_ptr=None, rgb8_ptr=None, sync=True, **params):
+        """rt_temporal_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
+        explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr and out_variance_ptr may be
+        variance_ptr (in place)."""
+        pl = TemporalPlanes(rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, z=z_ptr, object_id=object_id_ptr,
+                            variance=variance_ptr, out_linear=out_ptr, out_variance=out_variance_ptr, out_history=history_ptr,
+                            out_rgb8=rgb8_ptr)
+        p = temporal_params(**params)
+        _check(lib().rt_temporal_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
 def identity_map(texture=MAP_NONE):
@@ -695,6 +813,29 @@ class Scene:
             return out
         out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
                                                        rgb8=True, device=device, **denoise_kw)
+        return out
+
+    def render_temporal(self, history, cam, params, device=0, denoise=True, **kw):
+        """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
+        history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
+        "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
+        denoise=True: then the variance-guided denoise() of the accumulated pair, "denoised" and "denoised_rgb" added.
+        kw: photon_pass; alpha, max_history (the accumulation); levels, sigma_color, k_sigma (the denoise); sigma_normal,
+        sigma_depth (both).  gamma is the render's."""
+        photon_pass = kw.pop("photon_pass", False)
+        t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
+        d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
+        unknown = set(kw) - set(t_kw) - set(d_kw)
+        if unknown:
+            raise TypeError(f"no render_temporal parameter {sorted(unknown)[0]!r}")
+        out = self.render_outputs(cam, params, planes=("linear",) + FEATURE_PLANES + ("variance",), device=device, photon_pass=photon_pass)
+        out["accumulated"], out["accumulated_variance"], out["history"] = history.accumulate(
+            cam, out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], variance=out["variance"],
+            return_history=True, gamma=params.gamma, **t_kw)
+        if denoise:
+            out["denoised"], out["denoised_rgb"] = _denoise(
+                out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
+                variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
         return out
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,

@@ -16,7 +16,44 @@ void RenderImage::Init(int w, int h)
     if (featuresEnabled) { featuresEnabled = false; EnableFeatures(); }
     if (varianceEnabled) variance.assign((size_t)w * h * 3, 0.0f);
     denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
+    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear();
+    rt_history_destroy(history);        // a history is of one size
+    history = nullptr;
     finalPixels = 0;
+}
+
+void RenderImage::ResetTemporal()
+{
+    if (history) rt_history_reset(history);
+    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear();
+}
+
+bool RenderImage::AccumulateTemporal(const Camera &c, const rt_temporal_params *params, int device)
+{
+    if (!temporalEnabled || !linearEnabled || !featuresEnabled) {
+        temporalError = "AccumulateTemporal() needs EnableTemporal(), EnableLinear() and EnableFeatures() before the render";
+        return false;
+    }
+    if (!jobs.empty()) { temporalError = "AccumulateTemporal() while the render is still running"; return false; }
+    if (history && historyDevice != device) { rt_history_destroy(history); history = nullptr; }
+    if (!history && rt_history_create(device, width, height, &history) != RT_OK) { temporalError = rt_last_error(); return false; }
+    historyDevice = device;
+    rt_camera rc;                       // as Lower() hands the camera to the render
+    rc.pos[0] = c.pos.x; rc.pos[1] = c.pos.y; rc.pos[2] = c.pos.z;
+    rc.dir[0] = c.dir.x; rc.dir[1] = c.dir.y; rc.dir[2] = c.dir.z;
+    rc.up[0] = c.up.x; rc.up[1] = c.up.y; rc.up[2] = c.up.z;
+    rc.fov = c.fov; rc.focaldist = c.focaldist; rc.dof = c.dof; rc.width = c.imgWidth; rc.height = c.imgHeight;
+    rt_temporal_params defaults;
+    rt_temporal_default_params(&defaults);
+    const size_t n = (size_t)width * height;
+    std::vector<float> out(n * 3), outVar(varianceEnabled ? n * 3 : 0), len(n);
+    const rt_temporal_planes pl = {(uint32_t)sizeof(rt_temporal_planes), linear.data(), normals.data(), albedo.data(), zbuffer.data(),
+                                   objectIds.data(), varianceEnabled ? variance.data() : nullptr, out.data(),
+                                   varianceEnabled ? outVar.data() : nullptr, len.data(), nullptr};
+    if (rt_temporal(history, &rc, params ? params : &defaults, &pl) != RT_OK) { temporalError = rt_last_error(); return false; }
+    accumulated.swap(out); accumulatedVariance.swap(outVar); historyLength.swap(len);
+    temporalError.clear();
+    return true;
 }
 
 void RenderImage::EnableVariance()

@@ -34,10 +34,21 @@ class RenderImage {
     std::vector<float> variance, denoisedVariance;
     bool varianceEnabled = false;
     std::string denoiseError;
+    // opt-in (EnableTemporal): the frames accumulated by AccumulateTemporal() -- linear float RGB, its variance (with
+    // EnableVariance) and the per-pixel history length -- and the rt_history that holds them on the device
+    std::vector<float> accumulated, accumulatedVariance, historyLength;
+    bool temporalEnabled = false;
+    rt_history *history = nullptr;
+    int historyDevice = 0;
+    std::string temporalError;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
 public:
+    RenderImage() = default;
+    RenderImage(const RenderImage &) = delete;
+    RenderImage &operator=(const RenderImage &) = delete;
+    ~RenderImage() { rt_history_destroy(history); }
     void Init(int w, int h);
     int GetWidth() const { return width; }
     int GetHeight() const { return height; }
@@ -85,6 +96,22 @@ public:
     uint8_t *GetDenoisedImage() { return denoisedImg.empty() ? nullptr : denoisedImg.data(); }  // Color24 after gamma
     bool SaveDenoisedImage(const char *filename) const { return !denoised.empty() && WritePFM(filename, denoised.data(), width, height); }    // PFM
     bool SaveDenoisedPNG(const char *filename) const { return !denoisedImg.empty() && WritePNG(filename, denoisedImg.data(), width, height, 3); }
+    // Temporal accumulation (rt_mi355x.h, "temporal accumulation") over the frames of a STATIC scene: after each finished render
+    // AccumulateTemporal(camera the frame was rendered with) blends the frame into the history, reprojected from the previous
+    // call's camera.  Needs EnableTemporal(), EnableLinear() and EnableFeatures() before the render; with EnableVariance() the
+    // variance is accumulated too (GetAccumulatedVariance()).  The history is created by the first call, on `device`, and lives
+    // until the image is destroyed, Init() changes the size, or another device is named; ResetTemporal() makes the next frame
+    // start from nothing.  false + TemporalError() on failure.  params == NULL: the defaults of rt_temporal_default_params.
+    void EnableTemporal() { temporalEnabled = true; }
+    bool TemporalEnabled() const { return temporalEnabled; }
+    bool AccumulateTemporal(const Camera &camera, const rt_temporal_params *params = nullptr, int device = 0);
+    void ResetTemporal();
+    int TemporalFrames() const { return rt_history_frames(history); }
+    const std::string &TemporalError() const { return temporalError; }
+    float *GetAccumulatedPixels() { return accumulated.empty() ? nullptr : accumulated.data(); }                  // linear float RGB
+    float *GetAccumulatedVariance() { return accumulatedVariance.empty() ? nullptr : accumulatedVariance.data(); }
+    float *GetHistoryLength() { return historyLength.empty() ? nullptr : historyLength.data(); }                  // float per pixel
+    bool SaveAccumulatedImage(const char *filename) const { return !accumulated.empty() && WritePFM(filename, accumulated.data(), width, height); }   // PFM
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

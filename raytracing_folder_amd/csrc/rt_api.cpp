@@ -2365,6 +2365,144 @@ extern "C" rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const
     return RT_OK;
 }
 
+// ---- temporal accumulation ----------------------------------------------------------------------------------------------
+// An rt_history owns what one stream of frames needs on its device: the two ping-pong sets in one allocation, the camera of the
+// frame the current set holds, and the event that orders a call behind the previous one on the same history.
+struct rt_history {
+    int device = 0; int32_t w = 0, h = 0;
+    DevBuf sets;                        // RT_TEMPORAL_HISTORY_PER_PIXEL bytes a pixel: set 0, set 1
+    int cur = 0;                        // the set the last frame wrote
+    int32_t frames = 0;                 // since create / reset; 0: the next frame reads no history
+    DevCamera cam = {};                 // of the frame in set `cur`
+    hipEvent_t done = nullptr; bool pending = false;
+    std::mutex mu;
+};
+
+extern "C" rt_status rt_history_create(int device, int32_t w, int32_t h, rt_history **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_history_create: out is NULL");
+    *out = nullptr;
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_history_create: bad image size %d x %d", w, h);
+    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_history_create: %d x %d is more than 2^30 pixels", w, h);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_history_create: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    rt_history *hst = new rt_history;
+    hst->device = device; hst->w = w; hst->h = h;
+    rt_status st = hst->sets.ensure((size_t)w * (size_t)h * RT_TEMPORAL_HISTORY_PER_PIXEL);
+    if (st == RT_OK && hipEventCreateWithFlags(&hst->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_history_create: hipEventCreate failed");
+    if (st) { hst->sets.release(); delete hst; return st; }
+    *out = hst;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_history_reset(rt_history *hst)
+{
+    if (!hst) return fail(RT_ERR_ARG, "rt_history_reset: history is NULL");
+    std::lock_guard<std::mutex> lk(hst->mu);
+    hst->frames = 0;                    // the next frame reads no tap; it still waits for `done` before it writes a set
+    return RT_OK;
+}
+
+extern "C" void rt_history_destroy(rt_history *hst)
+{
+    if (!hst) return;
+    if (hipSetDevice(hst->device) == hipSuccess) {
+        if (hst->pending) (void)hipEventSynchronize(hst->done);
+        hst->sets.release();            // hipFree waits for the kernels that still use it
+        if (hst->done) (void)hipEventDestroy(hst->done);
+    }
+    delete hst;
+}
+
+extern "C" int32_t rt_history_frames(const rt_history *hst) { return hst ? hst->frames : 0; }
+
+extern "C" void rt_temporal_default_params(rt_temporal_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->alpha = 0.2f; p->max_history = 32; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
+}
+
+// everything that can be refused without a device, for both entry points; the history comes last, so that a caller without a
+// device (which has no history) is told about its other arguments too
+static rt_status temporal_check(const char *name, const rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl)
+{
+    if (!cam || !p || !pl) return fail(RT_ERR_ARG, "%s: camera, params or planes is NULL", name);
+    if (p->struct_size != (uint32_t)sizeof(rt_temporal_params))
+        return fail(RT_ERR_ARG, "%s: rt_temporal_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_temporal_params));
+    if (pl->struct_size != (uint32_t)sizeof(rt_temporal_planes))
+        return fail(RT_ERR_ARG, "%s: rt_temporal_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_temporal_planes));
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(RT_ERR_ARG, "%s: alpha must be in (0, 1]", name);
+    if (p->max_history < 1 || p->max_history > 65535) return fail(RT_ERR_ARG, "%s: max_history is %d, allowed 1..65535", name, p->max_history);
+    for (float s : {p->sigma_normal, p->sigma_depth, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_normal, sigma_depth and gamma must be positive and finite", name);
+    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
+        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
+    if (pl->out_variance && !pl->variance) return fail(RT_ERR_ARG, "%s: out_variance needs the variance plane", name);
+    if (!hst) return fail(RT_ERR_ARG, "%s: history is NULL", name);
+    if (cam->width != hst->w || cam->height != hst->h)
+        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the history %d x %d", name, cam->width, cam->height, hst->w, hst->h);
+    return RT_OK;
+}
+
+static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(hst->device));
+    std::lock_guard<std::mutex> lk(hst->mu);
+    if (hst->pending) HIP_TRY(hipStreamWaitEvent(st, hst->done, 0));
+    const size_t n = (size_t)hst->w * (size_t)hst->h;
+    TemporalRequest R = {};
+    R.width = hst->w; R.height = hst->h; R.has_history = hst->frames > 0;
+    camera_setup(*cam, R.cur);
+    R.old = hst->cam;
+    R.alpha = p->alpha; R.max_history = p->max_history; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth;
+    R.inv_gamma = denoise_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id; R.variance = pl->variance;
+    R.out_linear = pl->out_linear; R.out_variance = pl->out_variance; R.out_history = pl->out_history; R.out_rgb8 = pl->out_rgb8;
+    float4 *set0 = (float4 *)hst->sets.p;
+    const int next = hst->cur ^ 1;
+    R.prev = set0 + (size_t)hst->cur * 3 * n; R.next = set0 + (size_t)next * 3 * n;
+    rtk_launch_temporal(st, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(hst->done, st));
+    hst->pending = true;
+    hst->cur = next; hst->cam = R.cur; hst->frames++;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); hst->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                        const rt_temporal_planes *device_planes, int sync)
+{
+    rt_status st = temporal_check("rt_temporal_device", hst, cam, p, device_planes);
+    if (st) return st;
+    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes)
+{
+    rt_status st = temporal_check("rt_temporal", hst, cam, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(hst->device));
+    const size_t n = (size_t)hst->w * (size_t)hst->h;
+    ScopedDevBuf rgb, normal, albedo, z, id, var, hist, rgb8;       // the results are written in place into rgb and var
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
+        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4))) return st;
+    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
+    if (host_planes->variance && (st = var.upload(host_planes->variance, n * 12))) return st;
+    if (host_planes->out_history && (st = hist.ensure(n * 4))) return st;
+    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
+    const rt_temporal_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
+                                    (const int32_t *)id.p, (const float *)var.p, (float *)rgb.p,
+                                    host_planes->out_variance ? (float *)var.p : nullptr, (float *)hist.p, (uint8_t *)rgb8.p};
+    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1))) return st;
+    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_variance) HIP_TRY(hipMemcpy(host_planes->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_history) HIP_TRY(hipMemcpy(host_planes->out_history, hist.p, n * 4, hipMemcpyDeviceToHost));
+    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");

@@ -1,5 +1,5 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip): every rtk_* function, the requests they take and the records they exchange.  All five
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip): every rtk_* function, the requests they take and the records they exchange.  All six
 // files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
@@ -97,6 +97,22 @@ struct DenoiseRequest {
     float4 *var[2];
 };
 
+// One temporal accumulation of a width x height frame (rt_temporal.hip; the definition: rt_mi355x.h, "temporal accumulation").
+// The planes are the caller's device pointers (object_id, variance, out_variance, out_history and out_rgb8 may be NULL;
+// out_linear may be rgb_linear and out_variance may be variance), the parameters are validated by the caller.  `cur` and `old`
+// are camera_setup's quantities of this frame's camera and of the one the history holds; has_history is false for the first
+// frame after a create or a reset, and `prev` is then not read.  prev / next: the two sets of a history, each three planes of
+// width * height float4 (colour, variance, guide: RT_TEMPORAL_HISTORY_PER_PIXEL bytes a pixel for both sets together).
+#define RT_TEMPORAL_HISTORY_PER_PIXEL 96
+struct TemporalRequest {
+    int width, height; bool has_history;
+    DevCamera cur, old;
+    float alpha; int max_history; float sigma_normal, sigma_depth, inv_gamma;
+    const float *rgb_linear, *normal, *albedo, *z; const int32_t *object_id; const float *variance;
+    float *out_linear, *out_variance, *out_history; uint8_t *out_rgb8;
+    const float4 *prev; float4 *next;
+};
+
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -136,6 +152,10 @@ void rtk_launch_gather(hipStream_t st, const GatherRequest &R, int blocks);
 // ---- rt_denoise.hip: the image-space denoiser ----------------------------------------------------------------------------
 // k_denoise_prepare, then k_atrous once per level (the last one remodulates and writes the caller's planes), all on `st`
 void rtk_launch_denoise_frame(hipStream_t st, const DenoiseRequest &R);
+
+// ---- rt_temporal.hip: temporal accumulation with camera reprojection ---------------------------------------------------
+// k_temporal over the frame on `st`: reads the set `prev` (when has_history), writes the set `next` and the caller's planes
+void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

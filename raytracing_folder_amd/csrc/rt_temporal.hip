@@ -1,0 +1,168 @@
+// rt_temporal.hip -- temporal accumulation with camera reprojection: the frame-to-frame stage in front of the denoiser.  The
+// definition the kernel follows step by step is in include/rt_mi355x.h ("temporal accumulation"); the reference has no
+// counterpart.  Like the denoiser it is an image-space operation on image-sized planes and knows nothing of scenes: the scene is
+// taken to be static between two frames, only the camera moves.
+//
+//   k_temporal   one lane per pixel, 32 x 8 pixels per workgroup (the render's tile, as k_atrous): validity and demodulation of
+//                the lane's own pixel, its world point from z and the current camera, that point's position in the STORED
+//                camera's image, four bilinear taps into the previous history set, the blend, the caller's planes and the
+//                lane's three records of the next history set
+//
+// The history is two ping-pong sets of three float4 planes (96 bytes a pixel in all): colour {d.r, d.g, d.b, z}, variance
+// {u.r, u.g, u.b, N} and guide {n.x, n.y, n.z, id}.  A lane gathers from arbitrary pixels of the previous set while every lane
+// writes its own pixel of the other one, hence two sets and no ordering between lanes.  A pixel that takes no part (invalid, or
+// a colour that is not finite) stores N = 0 and id -1: no later tap accepts it.  Every pixel of a set is written by every frame,
+// so in a set "id >= 0" and "N > 0" say the same, and a tap is judged by its guide record (id, normal) first, then by its
+// colour record (z: the depth test); the variance record is loaded only for a tap that was accepted.  After a reset (or in the
+// first frame) no tap is read at all, which is why nothing has to clear the allocation.
+// No atomics, no LDS, fixed tap order: an identical sequence of calls gives identical bytes.
+#include <hip/hip_runtime.h>
+
+#include "rt_kernel_util.h"
+#include "rt_launch.h"
+
+#define RT_TEMPORAL_TILE_W 32
+#define RT_TEMPORAL_TILE_H 8
+#define RT_TEMPORAL_NO_HIT 1.0e30f       /* the z plane's "nothing hit" (BIGFLOAT) */
+#define RT_TEMPORAL_MIN_ALBEDO 1.0e-3f   /* the denoiser's: below it a channel is not demodulated */
+#define RT_TEMPORAL_MIN_WEIGHT 0.01f     /* accepted bilinear weight below which the pixel has no history */
+
+// the kernel's argument: members, order and types are its layout
+struct TemporalArgs {
+    int width, height, tiles_x;
+    int has_history;                    // 0: the first frame after create / reset -- `prev` is not read
+    DevCamera cur, old;                 // this frame's camera and the one of the frame the history holds (camera_setup's quantities)
+    float alpha, max_history, sigma_normal2, sigma_depth, inv_gamma;
+    const float *rgb, *normal, *albedo, *z; const int32_t *object_id; const float *variance;
+    float *out_linear, *out_variance, *out_history; uint8_t *out_rgb8;
+    const float4 *prev; float4 *next;   // a set: colour[n], variance[n], guide[n], n = width * height
+};
+
+__device__ __forceinline__ float temporal_albedo(float a) { return a > RT_TEMPORAL_MIN_ALBEDO ? a : 1.0f; }
+// a component of the variance plane that is negative or not finite counts as 0
+__device__ __forceinline__ float temporal_variance(float v) { return v > 0.0f && v < INFINITY ? v : 0.0f; }
+// x - x is 0 for a finite x and NaN otherwise
+__device__ __forceinline__ bool temporal_finite3(float a, float b, float c) { return (a - a) + (b - b) + (c - c) == 0.0f; }
+
+__global__ __launch_bounds__(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H) void k_temporal(TemporalArgs A)
+{
+    const int tx = (int)(blockIdx.x % (unsigned)A.tiles_x), ty = (int)(blockIdx.x / (unsigned)A.tiles_x);
+    const int x = tx * RT_TEMPORAL_TILE_W + (int)(threadIdx.x % RT_TEMPORAL_TILE_W);
+    const int y = ty * RT_TEMPORAL_TILE_H + (int)(threadIdx.x / RT_TEMPORAL_TILE_W);
+    if (x >= A.width || y >= A.height) return;
+    const size_t n = (size_t)A.width * (size_t)A.height;
+    const size_t p = (size_t)y * A.width + x;
+    float4 *next_color = A.next, *next_var = A.next + n, *next_guide = A.next + 2 * n;
+
+    // 1. validity and demodulation: the lane reads its own pixel of every input plane before it writes anything
+    const float r = A.rgb[3 * p], g = A.rgb[3 * p + 1], b = A.rgb[3 * p + 2], zp = A.z[p];
+    const float ar = temporal_albedo(A.albedo[3 * p]), ag = temporal_albedo(A.albedo[3 * p + 1]), ab = temporal_albedo(A.albedo[3 * p + 2]);
+    const float nx = A.normal[3 * p], ny = A.normal[3 * p + 1], nz = A.normal[3 * p + 2];
+    const float vr = A.variance ? A.variance[3 * p] : 0.0f, vg = A.variance ? A.variance[3 * p + 1] : 0.0f, vb = A.variance ? A.variance[3 * p + 2] : 0.0f;
+    const int idp = A.object_id ? A.object_id[p] : 0;
+    const float dr = r / ar, dg = g / ag, db = b / ab;
+    const bool valid = A.object_id ? idp >= 0 : zp < RT_TEMPORAL_NO_HIT;
+    if (!(valid && temporal_finite3(dr, dg, db))) {         // passes through bit for bit, stores N = 0 and id -1
+        next_color[p] = make_float4(r, g, b, zp);
+        next_var[p] = make_float4(vr, vg, vb, 0.0f);
+        next_guide[p] = make_float4(nx, ny, nz, __int_as_float(-1));
+        A.out_linear[3 * p] = r; A.out_linear[3 * p + 1] = g; A.out_linear[3 * p + 2] = b;
+        if (A.out_variance) { A.out_variance[3 * p] = vr; A.out_variance[3 * p + 1] = vg; A.out_variance[3 * p + 2] = vb; }
+        if (A.out_history) A.out_history[p] = 0.0f;
+        if (A.out_rgb8) {
+            A.out_rgb8[3 * p] = float_to_byte(powf(r, A.inv_gamma));
+            A.out_rgb8[3 * p + 1] = float_to_byte(powf(g, A.inv_gamma));
+            A.out_rgb8[3 * p + 2] = float_to_byte(powf(b, A.inv_gamma));
+        }
+        return;
+    }
+    const float ur = temporal_variance(vr) / (ar * ar), ug = temporal_variance(vg) / (ag * ag), ub = temporal_variance(vb) / (ab * ab);
+
+    float hr = 0, hg = 0, hb = 0, hur = 0, hug = 0, hub = 0, hn = 0, W = 0;     // sums over the accepted taps
+    float n0 = 0;                       // the first accepted tap's length: the lengths are summed as differences to it
+    if (A.has_history) {
+        // 2. the pixel's representative ray through s = (b.x + (x + 0.5) u, b.y + (y + 0.5) v, -l) and its world point
+        const float sx = A.cur.b[0] + ((float)x + 0.5f) * A.cur.u, sy = A.cur.b[1] + ((float)y + 0.5f) * A.cur.v, sz = A.cur.b[2];
+        const float *m = A.cur.m;
+        float rx = sx * m[0] + sy * m[3] + sz * m[6], ry = sx * m[1] + sy * m[4] + sz * m[7], rz = sx * m[2] + sy * m[5] + sz * m[8];
+        const float inv = 1.0f / sqrtf(rx * rx + ry * ry + rz * rz);
+        rx *= inv; ry *= inv; rz *= inv;
+        const float Px = A.cur.pos[0] + zp * rx, Py = A.cur.pos[1] + zp * ry, Pz = A.cur.pos[2] + zp * rz;
+        // 3. into the stored camera: q = (x_new', up', z_new') . (P - pos')
+        const float ex = Px - A.old.pos[0], ey = Py - A.old.pos[1], ez = Pz - A.old.pos[2];
+        const float *o = A.old.m;
+        const float qx = o[0] * ex + o[1] * ey + o[2] * ez, qy = o[3] * ex + o[4] * ey + o[5] * ez, qz = o[6] * ex + o[7] * ey + o[8] * ez;
+        if (qz < 0.0f) {
+            const float t = A.old.b[2] / qz;                // -l' / q.z
+            const float fx = (qx * t - A.old.b[0]) / A.old.u - 0.5f, fy = (qy * t - A.old.b[1]) / A.old.v - 0.5f;
+            const float zexp = sqrtf(ex * ex + ey * ey + ez * ez);
+            // outside (-1, width) x (-1, height) every tap lies outside the image or weighs 0; this also keeps the conversion
+            // to int away from huge and NaN positions
+            if (fx > -1.0f && fx < (float)A.width && fy > -1.0f && fy < (float)A.height) {
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                const float wx1 = fx - x0f, wy1 = fy - y0f, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
+                const float4 *prev_color = A.prev, *prev_var = A.prev + n, *prev_guide = A.prev + 2 * n;
+                // 4. the taps, in the order (0,0), (1,0), (0,1), (1,1)
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int qxk = x0 + (k & 1), qyk = y0 + (k >> 1);
+                    if (qxk < 0 || qxk >= A.width || qyk < 0 || qyk >= A.height) continue;
+                    const size_t q = (size_t)qyk * A.width + qxk;
+                    const float4 gq = prev_guide[q];
+                    const int idq = __float_as_int(gq.w);
+                    if (A.object_id ? idq != idp : idq < 0) continue;      // another object, or a pixel that stored N = 0 (id -1)
+                    const float ax = gq.x - nx, ay = gq.y - ny, az = gq.z - nz;
+                    if (!(ax * ax + ay * ay + az * az <= A.sigma_normal2)) continue;
+                    const float4 cq = prev_color[q];
+                    if (!(fabsf(cq.w - zexp) <= A.sigma_depth * fmaxf(cq.w, zexp))) continue;
+                    const float4 uq = prev_var[q];
+                    const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
+                    hr += w * cq.x; hg += w * cq.y; hb += w * cq.z;
+                    hur += w * uq.x; hug += w * uq.y; hub += w * uq.z;
+                    if (W == 0.0f) n0 = uq.w;               // (a first tap of weight 0 hands the role on: hn is still 0)
+                    hn += w * (uq.w - n0); W += w;
+                }
+            }
+        }
+    }
+
+    // 5. the blend
+    float N = 1.0f, or_ = dr, og = dg, ob = db, our = ur, oug = ug, oub = ub;
+    if (W >= RT_TEMPORAL_MIN_WEIGHT) {
+        N = fminf((n0 + hn / W) + 1.0f, A.max_history);      // taps of equal length give exactly that length + 1
+        const float beta = fmaxf(A.alpha, 1.0f / N), keep = 1.0f - beta;
+        or_ = keep * (hr / W) + beta * dr; og = keep * (hg / W) + beta * dg; ob = keep * (hb / W) + beta * db;
+        our = keep * keep * (hur / W) + beta * beta * ur; oug = keep * keep * (hug / W) + beta * beta * ug; oub = keep * keep * (hub / W) + beta * beta * ub;
+    }
+    next_color[p] = make_float4(or_, og, ob, zp);
+    next_var[p] = make_float4(our, oug, oub, N);
+    next_guide[p] = make_float4(nx, ny, nz, __int_as_float(idp));
+
+    // 6. the caller's planes, remodulated
+    const float lr = or_ * ar, lg = og * ag, lb = ob * ab;
+    A.out_linear[3 * p] = lr; A.out_linear[3 * p + 1] = lg; A.out_linear[3 * p + 2] = lb;
+    if (A.out_variance) { A.out_variance[3 * p] = our * (ar * ar); A.out_variance[3 * p + 1] = oug * (ag * ag); A.out_variance[3 * p + 2] = oub * (ab * ab); }
+    if (A.out_history) A.out_history[p] = N;
+    if (A.out_rgb8) {
+        A.out_rgb8[3 * p] = float_to_byte(powf(lr, A.inv_gamma));
+        A.out_rgb8[3 * p + 1] = float_to_byte(powf(lg, A.inv_gamma));
+        A.out_rgb8[3 * p + 2] = float_to_byte(powf(lb, A.inv_gamma));
+    }
+}
+
+void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R)
+{
+    TemporalArgs A = {};
+    A.width = R.width; A.height = R.height; A.tiles_x = (R.width + RT_TEMPORAL_TILE_W - 1) / RT_TEMPORAL_TILE_W;
+    A.has_history = R.has_history ? 1 : 0;
+    A.cur = R.cur; A.old = R.old;
+    A.alpha = R.alpha; A.max_history = (float)R.max_history;
+    A.sigma_normal2 = (float)((double)R.sigma_normal * (double)R.sigma_normal);
+    A.sigma_depth = R.sigma_depth; A.inv_gamma = R.inv_gamma;
+    A.rgb = R.rgb_linear; A.normal = R.normal; A.albedo = R.albedo; A.z = R.z; A.object_id = R.object_id; A.variance = R.variance;
+    A.out_linear = R.out_linear; A.out_variance = R.out_variance; A.out_history = R.out_history; A.out_rgb8 = R.out_rgb8;
+    A.prev = R.prev; A.next = R.next;
+    const long long tiles = (long long)A.tiles_x * ((R.height + RT_TEMPORAL_TILE_H - 1) / RT_TEMPORAL_TILE_H);
+    hipLaunchKernelGGL(k_temporal, dim3((unsigned)tiles), dim3(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H), 0, st, A);
+}
