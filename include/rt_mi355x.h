@@ -734,6 +734,88 @@ rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera 
 /* The planes are HOST arrays: upload, accumulate, download. */
 rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes);
 
+/* ---- exposure and tone mapping (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs
+ *      above are unchanged) -------------------------------------------------------------------------------------------------
+ * The last stage of the image-space pipeline: every stage above ends in Color24(powf(out_linear, 1/gamma)), the reference's hard
+ * clamp at a white level of 1.0.  This one meters the frame, adapts an exposure from frame to frame, applies a tone curve and
+ * encodes -- on image-sized planes (row-major, W x H), without a host round trip.  The reference has no counterpart.  Definition:
+ *   1. Luminance.  Y = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b), every product and every sum rounded to float on its own
+ *      (no fused multiply-add): Y, and with it the histogram, is an exact function of the input bits.
+ *   2. Metered pixels and bins.  A pixel is METERED when (no id plane is given or object_id >= 0) and Y is finite and
+ *      Y >= 2^-16.  256 bins, eight per octave over 2^-16 .. 2^16, read off the bit pattern:
+ *      bin = min(255, (float_as_uint(Y) >> 20) - 888), 888 = (127 - 16) * 8.  The bin's log2 value is
+ *      L_b = (2 bin + 1) / 16 - 16, the piecewise-linear log2 of the bin's centre.
+ *   3. Metering, in integers.  n = number of metered pixels; lo = floor((double)p_low * n), hi = ceil((double)p_high * n), so
+ *      that lo < hi <= n whenever n > 0 (hi is lo + 1 should the two roundings ever meet).  With the samples in bin order the
+ *      ranks [lo, hi) count: bin b, with c_b samples below it and h_b in it, contributes
+ *      k_b = max(0, min(c_b + h_b, hi) - max(c_b, lo)); S = sum(k_b * (2 b + 1)) as a 64-bit integer;
+ *      Lbar = S / (16 * (hi - lo)) - 16 in double.  Integer sums are associative: the histogram and Lbar do not depend on the
+ *      order in which workgroups or atomics arrive.
+ *   4. Target.  E_t = clamp(log2(key) + ev_bias - Lbar, ev_min, ev_max), log2(key) taken on the host in double.  n == 0 (nothing
+ *      metered): E stays what it was -- with no metered frame since create / reset, E = clamp(ev_bias, ev_min, ev_max), and the
+ *      next metered frame still counts as the first; log2_metered keeps its last value.  auto_exposure == 0: no metering, no
+ *      state, E = ev_bias (not clamped).
+ *   5. Adaptation.  The first metered frame after create / reset: E = E_t.  Otherwise E = E_prev + a * (E_t - E_prev), a =
+ *      adapt_up if E_t > E_prev, else adapt_down, in double.  E is stored as float; scale = (float)exp2((double)E).
+ *   6. Apply, per pixel: x = rgb_linear * scale, then
+ *        RT_TONEMAP_CLAMP     y = x
+ *        RT_TONEMAP_REINHARD  Yx = the luminance of x by step 1; y = x when !(Yx > 0), else y = x * f,
+ *                             f = (1 + Yx / white^2) / (1 + Yx) (white^2 rounded to float once)
+ *        RT_TONEMAP_ACES      per channel y = clamp((x (2.51f x + 0.03f)) / (x (2.43f x + 0.59f) + 0.14f), 0, 1); a NaN stays NaN
+ *      in float, every operation rounded on its own.  out_display = y (float, optional, may be rgb_linear);
+ *      out_rgb8 = Color24(powf(y, 1/gamma)) by step 5 of "denoising", its exponent rule included.  At least one of the two.
+ * Byte-identical outputs, histogram and exposure for an identical sequence of calls on one build.  out_display may be
+ * rgb_linear: the frame is metered before anything is written and a pixel is read, by the one lane that writes it, before it is
+ * written.  No other planes may overlap.
+ * rt_exposure is one per stream of frames on one device and is not tied to an image size.  On the device it holds the 256-bin
+ * working histogram, a copy of the last metered frame's, E, scale, Lbar, n and whether it holds a metered frame.  Calls on one
+ * state are ordered on the GPU one behind the other, whatever their streams; two states share nothing.  The device entry point
+ * never waits for the GPU unless `sync` is set: k_tonemap loads scale from the state.
+ * Everything is checked before the GPU is touched and is RT_ERR_ARG: NULL params or planes, a struct_size that is not the
+ * caller's sizeof, w or h <= 0, an unknown operator, key / white / gamma not positive and finite, ev_bias / ev_min / ev_max not
+ * finite or ev_min > ev_max, not 0 <= p_low < p_high <= 1, adapt_up / adapt_down outside (0, 1], a NULL rgb_linear, no output
+ * plane, a NULL state with auto_exposure != 0, a `device` that is not the state's.  More than 2^30 pixels: RT_ERR_LIMIT.  Then,
+ * without a gfx950 device: RT_ERR_NO_DEVICE (there is no CPU path). */
+enum { RT_TONEMAP_CLAMP = 0, RT_TONEMAP_REINHARD = 1, RT_TONEMAP_ACES = 2 };
+typedef struct rt_exposure rt_exposure;
+/* out == NULL: RT_ERR_ARG; no gfx950 device: RT_ERR_NO_DEVICE */
+rt_status rt_exposure_create(int device, rt_exposure **out);
+/* the next metered frame is the first again; ordered behind the earlier calls on this state */
+rt_status rt_exposure_reset(rt_exposure *e);
+/* NULL is ignored; waits for the work that still uses it */
+void      rt_exposure_destroy(rt_exposure *e);
+/* Waits for the calls issued on the state, then what the last METERED call (auto_exposure != 0) left: E (log2 of its scale), n,
+ * and Lbar of the last frame that metered anything.  A call with auto_exposure == 0 does not touch the state.  Any pointer may be NULL */
+rt_status rt_exposure_get(rt_exposure *e, float *log2_exposure, double *log2_metered, uint32_t *metered_pixels);
+/* Waits likewise; the histogram of the last frame that went through the meter (all zero before the first) */
+rt_status rt_exposure_histogram(rt_exposure *e, uint32_t out[256]);
+typedef struct rt_tonemap_params {
+    uint32_t struct_size;
+    int32_t  op;                /* RT_TONEMAP_ACES */
+    int32_t  auto_exposure;     /* 1    : 0 = fixed exposure ev_bias, no state needed      */
+    float    key;               /* 0.18 : the luminance the metered mean is brought to      */
+    float    ev_bias;           /* 0    : added to the exposure, in stops                   */
+    float    ev_min, ev_max;    /* -16, 16 : the range of the target                        */
+    float    p_low, p_high;     /* 0.10, 0.90 : the percentile window of the meter          */
+    float    adapt_up, adapt_down;  /* 1, 1 : fraction of the way to the target per frame, (0, 1] */
+    float    white;             /* 4    : REINHARD's white point                            */
+    float    gamma;             /* 2.2  : out_rgb8 only                                     */
+} rt_tonemap_params;
+typedef struct rt_tonemap_planes {
+    uint32_t struct_size;
+    const float *rgb_linear;
+    const int32_t *object_id;   /* optional: pixels with id < 0 are not metered */
+    float *out_display;         /* optional, may be rgb_linear */
+    uint8_t *out_rgb8;          /* optional */
+} rt_tonemap_planes;
+void      rt_tonemap_default_params(rt_tonemap_params *p);
+/* The planes are DEVICE pointers on `device`; the kernels are enqueued on `hip_stream` (NULL = the device's legacy null stream)
+ * and the call returns without waiting for them unless `sync` is non-zero.  e may be NULL only with auto_exposure == 0. */
+rt_status rt_tonemap_device(rt_exposure *e, int device, void *hip_stream, int32_t w, int32_t h, const rt_tonemap_params *p,
+                            const rt_tonemap_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, tone-map, download. */
+rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *host_planes);
+
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */
 /* n closest-hit queries = n calls of TraceNode(rootNode, ray, hit) (FIN/main.cpp:94-130).

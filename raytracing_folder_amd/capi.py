@@ -99,6 +99,28 @@ class TemporalPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(TemporalPlanes), **planes)
 
 
+class ToneMapParams(C.Structure):
+    """rt_tonemap_params: exposure and tone mapping (rt_tonemap_default_params fills ACES, auto-exposure on, key 0.18, ev_bias 0,
+    ev -16..16, percentiles 0.10..0.90, adapt 1 / 1, white 4, gamma 2.2)"""
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_int32), ("auto_exposure", C.c_int32), ("key", C.c_float), ("ev_bias", C.c_float),
+                ("ev_min", C.c_float), ("ev_max", C.c_float), ("p_low", C.c_float), ("p_high", C.c_float), ("adapt_up", C.c_float),
+                ("adapt_down", C.c_float), ("white", C.c_float), ("gamma", C.c_float)]
+
+
+class ToneMapPlanes(C.Structure):
+    """rt_tonemap_planes: the input and outputs of one tone-mapped frame.  object_id is optional; one of out_display (may be
+    rgb_linear) and out_rgb8 is required."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("object_id", C.c_void_p), ("out_display", C.c_void_p),
+                ("out_rgb8", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(ToneMapPlanes), **planes)
+
+
+# rt_tonemap_params.op (include/rt_mi355x.h)
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+TONEMAP_OPERATORS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
+
 # the optional planes of Scene.render_outputs: name -> (rt_outputs field, dtype, channels).  "variance" is no field of rt_outputs:
 # it is the extra argument of the _var entry points, which a render takes only when the plane is asked for
 OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
@@ -154,6 +176,8 @@ SYMBOLS = [
     "rt_denoise_var_default", "rt_denoise_var_device", "rt_denoise_var_host",
     "rt_history_create", "rt_history_reset", "rt_history_destroy", "rt_history_frames",
     "rt_temporal_default_params", "rt_temporal_device", "rt_temporal",
+    "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
+    "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -229,6 +253,19 @@ def lib():
         _lib.rt_temporal_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
         _lib.rt_temporal.argtypes = [vp, vp, vp, vp]
         for name in ("rt_history_create", "rt_history_reset", "rt_temporal_device", "rt_temporal"):
+            getattr(_lib, name).restype = C.c_int
+        # exposure and tone mapping (rt_mi355x.h: "exposure and tone mapping")
+        _lib.rt_exposure_create.argtypes = [C.c_int, C.POINTER(vp)]
+        _lib.rt_exposure_reset.argtypes = [vp]
+        _lib.rt_exposure_destroy.argtypes = [vp]
+        _lib.rt_exposure_destroy.restype = None
+        _lib.rt_exposure_get.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+        _lib.rt_exposure_histogram.argtypes = [vp, vp]
+        _lib.rt_tonemap_default_params.argtypes = [vp]
+        _lib.rt_tonemap_default_params.restype = None
+        _lib.rt_tonemap_device.argtypes = [vp, C.c_int, vp, i32, i32, vp, vp, C.c_int]
+        _lib.rt_tonemap.argtypes = [vp, C.c_int, i32, i32, vp, vp]
+        for name in ("rt_exposure_create", "rt_exposure_reset", "rt_exposure_get", "rt_exposure_histogram", "rt_tonemap_device", "rt_tonemap"):
             getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
@@ -520,6 +557,115 @@ class History:
         _check(lib().rt_temporal_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
+def tonemap_params(operator="aces", **kw):
+    """rt_tonemap_default_params, then the operator ("clamp", "reinhard", "aces" or an RT_TONEMAP_* number) and the keywords:
+    auto_exposure, key, ev_bias, ev_min, ev_max, p_low, p_high, adapt_up, adapt_down, white, gamma; exposure_ev is another name
+    for ev_bias (the exposure itself when auto_exposure is 0)."""
+    p = ToneMapParams()
+    lib().rt_tonemap_default_params(C.byref(p))
+    p.op = TONEMAP_OPERATORS[operator] if isinstance(operator, str) else int(operator)
+    for k, v in kw.items():
+        k = "ev_bias" if k == "exposure_ev" else k
+        if k not in ("auto_exposure", "key", "ev_bias", "ev_min", "ev_max", "p_low", "p_high", "adapt_up", "adapt_down", "white", "gamma"):
+            raise TypeError(f"no tone-mapping parameter {k!r}")
+        setattr(p, k, int(v) if k == "auto_exposure" else v)
+    return p
+
+
+def _tonemap_host(handle, device, linear, object_id, display, p):
+    linear = _c(linear, np.float32)
+    assert linear.ndim == 3 and linear.shape[2] == 3
+    h, w = linear.shape[:2]
+    ids = _c(object_id, np.int32) if object_id is not None else None
+    assert ids is None or ids.shape == (h, w)
+    out8 = np.empty((h, w, 3), np.uint8)
+    disp = np.empty((h, w, 3), np.float32) if display else None
+    pl = ToneMapPlanes(rgb_linear=linear.ctypes.data, object_id=ids.ctypes.data if ids is not None else None,
+                       out_display=disp.ctypes.data if display else None, out_rgb8=out8.ctypes.data)
+    _check(lib().rt_tonemap(handle, device, w, h, C.byref(p), C.byref(pl)))
+    return (out8, disp) if display else out8
+
+
+def tonemap(linear, exposure_ev=0.0, operator="aces", display=False, device=0, **params):
+    """rt_tonemap without a state: the fixed exposure 2^exposure_ev, then the operator, on a float32 (H, W, 3) host array.
+    Returns the gamma-encoded uint8 (H, W, 3) image -- and, display=True, the float32 display plane as a tuple's second.
+    params: tonemap_params() (white, gamma)."""
+    p = tonemap_params(operator, **dict(params, auto_exposure=0, ev_bias=exposure_ev))
+    return _tonemap_host(None, device, linear, None, display, p)
+
+
+class Exposure:
+    """rt_exposure: the exposure of one stream of frames on one device, adapted from frame to frame (the definition:
+    rt_mi355x.h, "exposure and tone mapping").  Not tied to an image size.  A context manager; close() (or the end of the with
+    block) frees the device block."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        self.device = int(device)
+        _check(lib().rt_exposure_create(self.device, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rt_exposure_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """the next metered frame is the first again"""
+        _check(lib().rt_exposure_reset(self._h))
+
+    def _get(self):
+        e, m, n = C.c_float(), C.c_double(), C.c_uint32()
+        _check(lib().rt_exposure_get(self._h, C.byref(e), C.byref(m), C.byref(n)))
+        return e.value, m.value, n.value
+
+    @property
+    def log2_exposure(self):
+        """E: log2 of the scale the last METERED call applied (waits for it); a call with auto_exposure=0 leaves the state alone"""
+        return self._get()[0]
+
+    @property
+    def log2_metered(self):
+        """Lbar of the last frame that metered anything (waits)"""
+        return self._get()[1]
+
+    @property
+    def metered_pixels(self):
+        """n of the last metered call (waits)"""
+        return self._get()[2]
+
+    def histogram(self):
+        """the 256-bin luminance histogram of the last metered call, uint32 (waits)"""
+        out = np.zeros(256, np.uint32)
+        _check(lib().rt_exposure_histogram(self._h, out.ctypes.data))
+        return out
+
+    def tonemap(self, linear, object_id=None, operator="aces", display=False, **params):
+        """rt_tonemap on host arrays: float32 (H, W, 3) linear, optionally int32 (H, W) object_id (ids < 0 are not metered).
+        Returns the gamma-encoded uint8 (H, W, 3) image -- and, display=True, the float32 display plane as a tuple's second.
+        params: tonemap_params()."""
+        return _tonemap_host(self._h, self.device, linear, object_id, display, tonemap_params(operator, **params))
+
+    def tonemap_device(self, stream, w, h, *, linear_ptr, object_id_ptr=None, rgb8_ptr=None, display_ptr=None, sync=True, operator="aces", **params):
+        """rt_tonemap_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
+        explicit stream's handle; None = the null stream of the device) without a host round trip.  display_ptr may be
+        linear_ptr (in place)."""
+        pl = ToneMapPlanes(rgb_linear=linear_ptr, object_id=object_id_ptr, out_display=display_ptr, out_rgb8=rgb8_ptr)
+        p = tonemap_params(operator, **params)
+        _check(lib().rt_tonemap_device(self._h, self.device, _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), 1 if sync else 0))
+
+
 def identity_map(texture=MAP_NONE):
     m = np.zeros(1, TEXMAP)
     m["texture"] = texture
@@ -798,11 +944,13 @@ class Scene:
         out["rgb"], out["z"], out["count"], out["stats"], out["progress"] = self._render(cam, params, tiles, device, photon_pass, None, dict(out))
         return out
 
-    def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, **denoise_kw):
+    def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, exposure=None, tonemap_kw=None, **denoise_kw):
         """render_outputs with the linear plane and the four feature planes, then denoise() of that frame guided by them
         (gamma: the render's): the same dict with "denoised" (float32 (H, W, 3), linear) and "denoised_rgb" (uint8 (H, W, 3))
         added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth.  variance=True: the render also fills
-        out["variance"] and the denoise is the variance-guided one (denoise_kw: also k_sigma); "denoised_variance" is added."""
+        out["variance"] and the denoise is the variance-guided one (denoise_kw: also k_sigma); "denoised_variance" is added.
+        exposure: an Exposure on `device` -- the denoised plane is metered (with the frame's object_id) and tone-mapped, and
+        "display_rgb" (uint8 (H, W, 3)) is added; tonemap_kw: a dict of Exposure.tonemap's keywords (operator, key, ...)."""
         planes = ("linear",) + FEATURE_PLANES + (("variance",) if variance else ())
         out = self.render_outputs(cam, params, planes=planes, device=device, photon_pass=photon_pass)
         denoise_kw.setdefault("gamma", params.gamma)
@@ -810,18 +958,23 @@ class Scene:
             out["denoised"], out["denoised_rgb"], out["denoised_variance"] = denoise(
                 out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["variance"], return_variance=True, **denoise_kw)
-            return out
-        out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
-                                                       rgb8=True, device=device, **denoise_kw)
+        else:
+            out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
+                                                           rgb8=True, device=device, **denoise_kw)
+        if exposure is not None:
+            out["display_rgb"] = exposure.tonemap(out["denoised"], out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
-    def render_temporal(self, history, cam, params, device=0, denoise=True, **kw):
+    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
         denoise=True: then the variance-guided denoise() of the accumulated pair, "denoised" and "denoised_rgb" added.
         kw: photon_pass; alpha, max_history (the accumulation); levels, sigma_color, k_sigma (the denoise); sigma_normal,
-        sigma_depth (both).  gamma is the render's."""
+        sigma_depth (both).  gamma is the render's.
+        exposure: an Exposure on `device` -- the final linear plane (the denoised one, or the accumulated one when
+        denoise=False) is metered with the frame's object_id and tone-mapped, "display_rgb" (uint8 (H, W, 3)) added; tonemap_kw:
+        a dict of Exposure.tonemap's keywords (operator, key, adapt_up, ...)."""
         photon_pass = kw.pop("photon_pass", False)
         t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
         d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
@@ -836,6 +989,9 @@ class Scene:
             out["denoised"], out["denoised_rgb"] = _denoise(
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
+        if exposure is not None:
+            out["display_rgb"] = exposure.tonemap(out["denoised" if denoise else "accumulated"], out["object_id"],
+                                                  **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,

@@ -19,7 +19,41 @@ void RenderImage::Init(int w, int h)
     accumulated.clear(); accumulatedVariance.clear(); historyLength.clear();
     rt_history_destroy(history);        // a history is of one size
     history = nullptr;
+    display.clear(); displayImg.clear();
     finalPixels = 0;
+}
+
+void RenderImage::ResetToneMap()
+{
+    if (exposure) rt_exposure_reset(exposure);
+    display.clear(); displayImg.clear();
+}
+
+float RenderImage::ToneMapExposure() const
+{
+    float e = 0.0f;
+    if (exposure) rt_exposure_get(exposure, &e, nullptr, nullptr);
+    return e;
+}
+
+bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
+{
+    if (!toneMapEnabled || !linearEnabled) { toneMapError = "ToneMap() needs EnableToneMap() and EnableLinear() before the render"; return false; }
+    if (!jobs.empty()) { toneMapError = "ToneMap() while the render is still running"; return false; }
+    if (exposure && exposureDevice != device) { rt_exposure_destroy(exposure); exposure = nullptr; }
+    if (!exposure && rt_exposure_create(device, &exposure) != RT_OK) { toneMapError = rt_last_error(); return false; }
+    exposureDevice = device;
+    rt_tonemap_params defaults;
+    rt_tonemap_default_params(&defaults);
+    const size_t n = (size_t)width * height;
+    const std::vector<float> &src = !denoised.empty() ? denoised : (!accumulated.empty() ? accumulated : linear);
+    std::vector<float> out(n * 3);
+    std::vector<uint8_t> out8(n * 3);
+    const rt_tonemap_planes pl = {(uint32_t)sizeof(rt_tonemap_planes), src.data(), featuresEnabled ? objectIds.data() : nullptr, out.data(), out8.data()};
+    if (rt_tonemap(exposure, device, width, height, params ? params : &defaults, &pl) != RT_OK) { toneMapError = rt_last_error(); return false; }
+    display.swap(out); displayImg.swap(out8);
+    toneMapError.clear();
+    return true;
 }
 
 void RenderImage::ResetTemporal()

@@ -41,6 +41,14 @@ class RenderImage {
     rt_history *history = nullptr;
     int historyDevice = 0;
     std::string temporalError;
+    // opt-in (EnableToneMap): ToneMap()'s outputs -- the display-referred float RGB and its gamma-encoded Color24 image -- and
+    // the rt_exposure that carries the exposure from frame to frame on the device
+    std::vector<float> display;
+    std::vector<uint8_t> displayImg;
+    bool toneMapEnabled = false;
+    rt_exposure *exposure = nullptr;
+    int exposureDevice = 0;
+    std::string toneMapError;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -48,7 +56,7 @@ public:
     RenderImage() = default;
     RenderImage(const RenderImage &) = delete;
     RenderImage &operator=(const RenderImage &) = delete;
-    ~RenderImage() { rt_history_destroy(history); }
+    ~RenderImage() { rt_history_destroy(history); rt_exposure_destroy(exposure); }
     void Init(int w, int h);
     int GetWidth() const { return width; }
     int GetHeight() const { return height; }
@@ -112,6 +120,22 @@ public:
     float *GetAccumulatedVariance() { return accumulatedVariance.empty() ? nullptr : accumulatedVariance.data(); }
     float *GetHistoryLength() { return historyLength.empty() ? nullptr : historyLength.data(); }                  // float per pixel
     bool SaveAccumulatedImage(const char *filename) const { return !accumulated.empty() && WritePFM(filename, accumulated.data(), width, height); }   // PFM
+    // Exposure and tone mapping (rt_mi355x.h, "exposure and tone mapping") of the finished frame: ToneMap() meters, adapts the
+    // exposure from the previous call's and tone-maps the most processed linear plane the image holds -- the denoised one, else
+    // the accumulated one, else the render's -- with the object ids when EnableFeatures() was called (the background is then not
+    // metered).  Needs EnableToneMap() and EnableLinear() before the render.  The rt_exposure is created by the first call, on
+    // `device`, and lives until the image is destroyed or another device is named (it is not tied to a size: Init() keeps it);
+    // ResetToneMap() makes the next frame the first again.  false + ToneMapError() on failure.  params == NULL: the defaults of
+    // rt_tonemap_default_params.  The getters are NULL and SaveDisplayImage fails until a ToneMap() has succeeded.
+    void EnableToneMap() { toneMapEnabled = true; }
+    bool ToneMapEnabled() const { return toneMapEnabled; }
+    bool ToneMap(const rt_tonemap_params *params = nullptr, int device = 0);
+    void ResetToneMap();
+    float ToneMapExposure() const;      // log2 of the scale the last METERED ToneMap() applied (auto_exposure != 0; 0 before the first)
+    const std::string &ToneMapError() const { return toneMapError; }
+    float *GetDisplayPixels() { return display.empty() ? nullptr : display.data(); }            // display-referred float RGB
+    uint8_t *GetDisplayImage() { return displayImg.empty() ? nullptr : displayImg.data(); }     // Color24 after gamma
+    bool SaveDisplayImage(const char *filename) const { return !displayImg.empty() && WritePNG(filename, displayImg.data(), width, height, 3); }
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

@@ -2503,6 +2503,184 @@ extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt
     return RT_OK;
 }
 
+// ---- exposure and tone mapping --------------------------------------------------------------------------------------------
+// An rt_exposure owns the device block of one stream of frames (ToneMapRequest::State) and the event that orders a call behind
+// the previous one on the same state.  The host keeps no copy of what the meter computes: the getters read the block back.
+struct rt_exposure {
+    int device = 0;
+    DevBuf block;                       // one ToneMapRequest::State
+    hipEvent_t done = nullptr; bool pending = false;
+    std::mutex mu;
+};
+
+// the block back to all zero (an empty working histogram, no metered frame), behind the calls issued so far
+static rt_status exposure_clear(rt_exposure *e)
+{
+    if (e->pending) HIP_TRY(hipStreamWaitEvent(nullptr, e->done, 0));
+    HIP_TRY(hipMemsetAsync(e->block.p, 0, sizeof(ToneMapRequest::State), nullptr));
+    HIP_TRY(hipEventRecord(e->done, nullptr));
+    e->pending = true;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_create(int device, rt_exposure **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_exposure_create: out is NULL");
+    *out = nullptr;
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_exposure_create: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    rt_exposure *e = new rt_exposure;
+    e->device = device;
+    rt_status st = e->block.ensure(sizeof(ToneMapRequest::State));
+    if (st == RT_OK && hipEventCreateWithFlags(&e->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_exposure_create: hipEventCreate failed");
+    if (st == RT_OK) st = exposure_clear(e);
+    if (st) { rt_exposure_destroy(e); return st; }
+    *out = e;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_reset(rt_exposure *e)
+{
+    if (!e) return fail(RT_ERR_ARG, "rt_exposure_reset: state is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> lk(e->mu);
+    return exposure_clear(e);
+}
+
+extern "C" void rt_exposure_destroy(rt_exposure *e)
+{
+    if (!e) return;
+    if (hipSetDevice(e->device) == hipSuccess) {
+        if (e->pending) (void)hipEventSynchronize(e->done);
+        e->block.release();             // hipFree waits for the kernels that still use it
+        if (e->done) (void)hipEventDestroy(e->done);
+    }
+    delete e;
+}
+
+// waits for the calls issued on the state and copies its block to the host
+static rt_status exposure_read(const char *name, rt_exposure *e, ToneMapRequest::State &out)
+{
+    if (!e) return fail(RT_ERR_ARG, "%s: state is NULL", name);
+    HIP_TRY(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->pending) { HIP_TRY(hipEventSynchronize(e->done)); e->pending = false; }
+    HIP_TRY(hipMemcpy(&out, e->block.p, sizeof out, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_get(rt_exposure *e, float *log2_exposure, double *log2_metered, uint32_t *metered_pixels)
+{
+    ToneMapRequest::State s;
+    rt_status st = exposure_read("rt_exposure_get", e, s);
+    if (st) return st;
+    if (log2_exposure) *log2_exposure = s.E;
+    if (log2_metered) *log2_metered = s.lbar;
+    if (metered_pixels) *metered_pixels = s.n;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_histogram(rt_exposure *e, uint32_t out[256])
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_exposure_histogram: out is NULL");
+    ToneMapRequest::State s;
+    rt_status st = exposure_read("rt_exposure_histogram", e, s);
+    if (st) return st;
+    memcpy(out, s.last, sizeof s.last);
+    return RT_OK;
+}
+
+extern "C" void rt_tonemap_default_params(rt_tonemap_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->op = RT_TONEMAP_ACES; p->auto_exposure = 1;
+    p->key = 0.18f; p->ev_bias = 0.0f; p->ev_min = -16.0f; p->ev_max = 16.0f; p->p_low = 0.10f; p->p_high = 0.90f;
+    p->adapt_up = 1.0f; p->adapt_down = 1.0f; p->white = 4.0f; p->gamma = 2.2f;
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status tonemap_check(const char *name, const rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *pl)
+{
+    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
+    if (p->struct_size != (uint32_t)sizeof(rt_tonemap_params))
+        return fail(RT_ERR_ARG, "%s: rt_tonemap_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_tonemap_params));
+    if (pl->struct_size != (uint32_t)sizeof(rt_tonemap_planes))
+        return fail(RT_ERR_ARG, "%s: rt_tonemap_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_tonemap_planes));
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, w, h);
+    if (p->op != RT_TONEMAP_CLAMP && p->op != RT_TONEMAP_REINHARD && p->op != RT_TONEMAP_ACES) return fail(RT_ERR_ARG, "%s: no operator %d", name, p->op);
+    for (float s : {p->key, p->white, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: key, white and gamma must be positive and finite", name);
+    if (!std::isfinite(p->ev_bias) || !std::isfinite(p->ev_min) || !std::isfinite(p->ev_max) || !(p->ev_min <= p->ev_max))
+        return fail(RT_ERR_ARG, "%s: ev_bias, ev_min and ev_max must be finite and ev_min <= ev_max", name);
+    if (!(p->p_low >= 0.0f && p->p_low < p->p_high && p->p_high <= 1.0f)) return fail(RT_ERR_ARG, "%s: the percentiles must be 0 <= p_low < p_high <= 1", name);
+    for (float a : {p->adapt_up, p->adapt_down})
+        if (!(a > 0.0f && a <= 1.0f)) return fail(RT_ERR_ARG, "%s: adapt_up and adapt_down must be in (0, 1]", name);
+    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
+    if (!pl->out_display && !pl->out_rgb8) return fail(RT_ERR_ARG, "%s: one of out_display and out_rgb8 is required", name);
+    if (p->auto_exposure && !e) return fail(RT_ERR_ARG, "%s: auto-exposure needs an rt_exposure", name);
+    if (e && e->device != device) return fail(RT_ERR_ARG, "%s: the state is on device %d, the call names %d", name, e->device, device);
+    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, w, h);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+    return RT_OK;
+}
+
+static rt_status tonemap_on_device(rt_exposure *e, int device, hipStream_t st, int32_t w, int32_t h, const rt_tonemap_params *p,
+                                   const rt_tonemap_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(device));
+    ToneMapRequest R = {};
+    R.width = w; R.height = h; R.op = p->op; R.meter = p->auto_exposure != 0;
+    R.log2_key = log2((double)p->key);
+    R.ev_bias = p->ev_bias; R.ev_min = p->ev_min; R.ev_max = p->ev_max; R.p_low = p->p_low; R.p_high = p->p_high;
+    R.adapt_up = p->adapt_up; R.adapt_down = p->adapt_down;
+    R.scale = (float)exp2((double)p->ev_bias);
+    R.white2 = (float)((double)p->white * (double)p->white);
+    R.inv_gamma = denoise_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.object_id = pl->object_id; R.out_display = pl->out_display; R.out_rgb8 = pl->out_rgb8;
+    if (!R.meter) {                     // fixed exposure: nothing of the state is read or written, nothing to order
+        rtk_launch_tonemap(st, R);
+        HIP_TRY(hipGetLastError());
+        if (sync) HIP_TRY(hipStreamSynchronize(st));
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->pending) HIP_TRY(hipStreamWaitEvent(st, e->done, 0));
+    R.state = (ToneMapRequest::State *)e->block.p;
+    rtk_launch_tonemap(st, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->done, st));
+    e->pending = true;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); e->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_tonemap_device(rt_exposure *e, int device, void *hip_stream, int32_t w, int32_t h, const rt_tonemap_params *p,
+                                       const rt_tonemap_planes *device_planes, int sync)
+{
+    rt_status st = tonemap_check("rt_tonemap_device", e, device, w, h, p, device_planes);
+    if (st) return st;
+    return tonemap_on_device(e, device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *host_planes)
+{
+    rt_status st = tonemap_check("rt_tonemap", e, device, w, h, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)w * (size_t)h;
+    ScopedDevBuf rgb, id, rgb8;                                     // the display plane is written in place into rgb
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12))) return st;
+    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
+    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
+    const rt_tonemap_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const int32_t *)id.p,
+                                   host_planes->out_display ? (float *)rgb.p : nullptr, (uint8_t *)rgb8.p};
+    if ((st = tonemap_on_device(e, device, nullptr, w, h, p, &dev, 1))) return st;
+    if (host_planes->out_display) HIP_TRY(hipMemcpy(host_planes->out_display, rgb.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");

@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip): every rtk_* function, the requests they take and the records they exchange.  All six
-// files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_tonemap.hip): every rtk_* function, the requests they take and the records they
+// exchange.  All seven files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -113,6 +113,20 @@ struct TemporalRequest {
     const float4 *prev; float4 *next;
 };
 
+// One tone-mapped width x height frame (rt_tonemap.hip; the definition: rt_mi355x.h, "exposure and tone mapping").  The planes are
+// the caller's device pointers (object_id and one of out_display / out_rgb8 may be NULL; out_display may be rgb_linear), the
+// parameters are validated by the caller.  meter: k_luminance_hist and k_exposure_meter run on `state` first and k_tonemap takes
+// the scale they leave there; otherwise only k_tonemap runs, with `scale`, and `state` is not touched.  State is an rt_exposure's
+// block on the device: the working histogram (zero between calls), the last metered frame's, and what the meter left.
+struct ToneMapRequest {
+    struct State { uint32_t hist[256], last[256]; double lbar; float E, scale; uint32_t n, holds; };
+    int width, height, op; bool meter;
+    State *state;
+    double log2_key; float ev_bias, ev_min, ev_max, p_low, p_high, adapt_up, adapt_down;
+    float scale, white2, inv_gamma;
+    const float *rgb_linear; const int32_t *object_id; float *out_display; uint8_t *out_rgb8;
+};
+
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -156,6 +170,10 @@ void rtk_launch_denoise_frame(hipStream_t st, const DenoiseRequest &R);
 // ---- rt_temporal.hip: temporal accumulation with camera reprojection ---------------------------------------------------
 // k_temporal over the frame on `st`: reads the set `prev` (when has_history), writes the set `next` and the caller's planes
 void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R);
+
+// ---- rt_tonemap.hip: exposure and tone mapping ---------------------------------------------------------------------------
+// on `st`: k_luminance_hist and k_exposure_meter (when R.meter), then k_tonemap<R.op>
+void rtk_launch_tonemap(hipStream_t st, const ToneMapRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

@@ -1,0 +1,700 @@
+"""Exposure and tone mapping (include/rt_mi355x.h, "exposure and tone mapping"): rt_exposure_*, rt_tonemap, rt_tonemap_device,
+capi.Exposure / capi.tonemap, Scene.render_denoised / render_temporal with exposure=, the C++ shim's ToneMap().
+
+ref_tonemap is a numpy transcription of the definition: steps 1-2 in float32 exactly as defined (numpy rounds every float32
+product and sum on its own), step 3 in Python integers, steps 4-6 in float64.  The histogram is an exact function of the input
+bits, so it is compared for equality; what is compared with a gate has the gate counted from the chain of operations."""
+import ctypes as C
+import math
+import os
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from raytracing_folder_amd import capi
+from tests import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+U = 2.0 ** -24                  # the relative error of one rounding to float
+DEFAULTS = dict(key=0.18, ev_bias=0.0, ev_min=-16.0, ev_max=16.0, p_low=0.10, p_high=0.90, adapt_up=1.0, adapt_down=1.0, white=4.0, gamma=2.2,
+                auto_exposure=1)
+# log2_exposure against the transcription.  The histogram is exact and Lbar is the same IEEE double division and subtraction on
+# both sides; the target, the adaptation and exp2 are double on both sides (differences of a few 2^-53 * 32).  What is left is
+# the float store of E: a double that differs in its last bits can round to the neighbouring float, one ulp of a float of
+# magnitude <= 32 (2^-19), and a sequence hands that on to the next frame with a factor (1 - a) <= 1: at most one ulp per frame.
+# No sequence here is longer than 4 frames between two resets.
+GATE_E = 4 * 2.0 ** -19
+GATE_LBAR = 2.0 ** -48          # two double roundings at magnitude <= 32 would be 2^-48 -- expected: equal
+# the re-metering bound of the issue: bin quantisation on both sides (2 * 1/16) + max(log2(1 + m) - m)
+REMETER = 1.0 / 8 + 0.0861
+
+
+# ---- the transcription --------------------------------------------------------------------------------------------
+def ref_luminance(rgb):
+    rgb = np.asarray(rgb, F)
+    with np.errstate(all="ignore"):
+        return (F(0.2126) * rgb[..., 0] + F(0.7152) * rgb[..., 1]) + F(0.0722) * rgb[..., 2]
+
+
+def ref_histogram(rgb, ids=None):
+    Y = ref_luminance(rgb)
+    with np.errstate(all="ignore"):
+        m = np.isfinite(Y) & (Y >= F(2.0 ** -16))
+    if ids is not None:
+        m &= np.asarray(ids) >= 0
+    bits = np.ascontiguousarray(Y[m]).view(np.uint32).astype(np.int64)
+    return np.bincount(np.minimum(255, (bits >> 20) - 888), minlength=256).astype(np.uint32)
+
+
+def ref_window(n, p_low, p_high):
+    lo, hi = math.floor(float(F(p_low)) * n), math.ceil(float(F(p_high)) * n)
+    return lo, max(min(hi, n), lo + 1)
+
+
+def ref_sum(hist, p_low=0.10, p_high=0.90):
+    """step 3's integers: (n, S, hi - lo)"""
+    h = [int(v) for v in hist]
+    n = sum(h)
+    if n == 0:
+        return 0, 0, 0
+    lo, hi = ref_window(n, p_low, p_high)
+    S, c = 0, 0
+    for b, hb in enumerate(h):
+        S += max(0, min(c + hb, hi) - max(c, lo)) * (2 * b + 1)
+        c += hb
+    return n, S, hi - lo
+
+
+def ref_lbar(hist, p_low=0.10, p_high=0.90):
+    """step 3: (n, Lbar); Lbar is None when nothing is metered.  The one division is Python's int / int, correctly rounded like
+    the double division of two exactly representable integers"""
+    n, S, m = ref_sum(hist, p_low, p_high)
+    return (n, S / (16 * m) - 16) if n else (0, None)
+
+
+class RefExposure:
+    """steps 4-5 in float64, E stored as float32"""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.E, self.holds, self.lbar, self.n, self.hist = F(0), False, 0.0, 0, np.zeros(256, np.uint32)
+
+    def meter(self, rgb, ids=None, **kw):
+        p = dict(DEFAULTS, **kw)
+        f = lambda k: float(F(p[k]))
+        if not p["auto_exposure"]:
+            return F(2.0 ** f("ev_bias"))
+        self.hist = ref_histogram(rgb, ids)
+        self.n, lbar = ref_lbar(self.hist, p["p_low"], p["p_high"])
+        if lbar is None:
+            if not self.holds:
+                self.E = F(min(max(f("ev_bias"), f("ev_min")), f("ev_max")))
+        else:
+            self.lbar = lbar
+            Et = min(max(math.log2(f("key")) + f("ev_bias") - lbar, f("ev_min")), f("ev_max"))
+            E = Et
+            if self.holds:
+                Ep = float(self.E)
+                E = Ep + (f("adapt_up") if Et > Ep else f("adapt_down")) * (Et - Ep)
+            self.E, self.holds = F(E), True
+        return F(2.0 ** float(self.E))
+
+
+def ref_apply(rgb, scale, operator, white=4.0):
+    """step 6 in float64 with the float coefficients of the definition"""
+    with np.errstate(all="ignore"):
+        x = np.asarray(rgb, F).astype(np.float64) * float(F(scale))
+        if operator == "clamp":
+            return x
+        if operator == "reinhard":
+            Y = (float(F(0.2126)) * x[..., 0] + float(F(0.7152)) * x[..., 1]) + float(F(0.0722)) * x[..., 2]
+            w2 = float(F(float(F(white)) ** 2))
+            f = np.where(Y > 0, (1 + Y / w2) / (1 + Y), 1.0)
+            return x * f[..., None]
+        c = lambda v: float(F(v))
+        y = (x * (c(2.51) * x + c(0.03))) / (x * (c(2.43) * x + c(0.59)) + c(0.14))
+        return np.where(y < 0, 0.0, np.where(y > 1, 1.0, y))
+
+
+def apply_f32(rgb, scale, operator, white=4.0):
+    """step 6 as a device evaluates it: float32, every operation rounded on its own (numpy does just that)"""
+    with np.errstate(all="ignore"):
+        x = np.asarray(rgb, F) * F(scale)
+        if operator == "clamp":
+            return x
+        if operator == "reinhard":
+            Y = ref_luminance(x)
+            f = np.where(Y > 0, (F(1) + Y / F(float(F(white)) ** 2)) / (F(1) + Y), F(1)).astype(F)
+            return x * f[..., None]
+        y = (x * (F(2.51) * x + F(0.03))) / (x * (F(2.43) * x + F(0.59)) + F(0.14))
+        return np.where(y < 0, F(0), np.where(y > 1, F(1), y)).astype(F)
+
+
+# Gate of out_display: C * 2^-24 * |want| + 1e-7, C counted in roundings (u = 2^-24 relative each) along each operator's chain,
+# for channels of one sign (a pixel is a light's colour times a positive scale; the negative test pixels are negative in every
+# channel).  The transcription takes the device's E, so the scale enters only through (float)exp2: the device's double exp2 and
+# numpy's can round to neighbouring floats, 2u.
+#   clamp     x = rgb * scale: 1, + 2 (scale)                                                                          = 3
+#   reinhard  x: 3.  Yx: products 3 + 1, two sums of same-sign terms + 2: 6.  Yx / white^2 (white^2 rounded once: 1) + 1: 8.
+#             1 + that: 9.  1 + Yx: 7.  the quotient: 9 + 7 + 1 = 17.  x * f: 3 + 17 + 1                                = 21
+#   aces      x: 3.  2.51 x: 4.  + 0.03: 5.  x * that: 3 + 5 + 1 = 9.  2.43 x: 4.  + 0.59: 5.  x * that: 9.  + 0.14: 10.
+#             the quotient: 9 + 10 + 1                                                                                 = 20
+#             (x < 0: the sums 2.51 x + 0.03 and 2.43 x + 0.59 cancel, but where they do the result is below 1e-7 or clamped;
+#             test_operator_gates_hold_for_a_float32_evaluation sweeps it)
+GATE_C = {"clamp": 3, "reinhard": 21, "aces": 20}
+
+
+def _display_gate(got, want, operator):
+    """worst error / gate over the finite entries; where the transcription is not finite the device's is the same kind"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    fin = np.isfinite(want)
+    assert (np.isnan(got) == np.isnan(want)).all()
+    assert (got[~fin & ~np.isnan(want)] == want[~fin & ~np.isnan(want)]).all()
+    gate = GATE_C[operator] * U * np.abs(want[fin]) + 1e-7
+    return float((np.abs(got[fin] - want[fin]) / gate).max()) if fin.any() else 0.0
+
+
+def _encode(lin, gamma):
+    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte), as tests/test_linear_output.py has it"""
+    with np.errstate(all="ignore"):
+        g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
+        s = (g * np.float32(255)).astype(np.float32)
+    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
+    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
+
+
+def _assert_rgb8_encodes(lin, rgb, gamma=2.2):
+    d = np.abs(_encode(lin, gamma).astype(int) - rgb.astype(int))
+    assert (d == 0).mean() >= 0.999, (d != 0).sum()             # a host powf one ulp off the device's moves a byte at a boundary
+    assert d.max() <= 1
+
+
+# ---- the synthetic frames -------------------------------------------------------------------------------------------
+def _green_for(Y):
+    """g with fl(0.7152f * g) == Y exactly: the pixel (0, g, 0) has luminance Y (the other terms and sums are exact zeros)"""
+    g = F(float(Y) / float(F(0.7152)))
+    for _ in range(16):
+        got = F(0.7152) * g
+        if got == Y:
+            return g
+        g = np.nextafter(g, F(np.inf) if got < Y else F(-np.inf))
+    raise AssertionError(Y)
+
+
+SPECIAL_Y = (F(2.0 ** -16), np.nextafter(F(2.0 ** -16), F(0)), F(2.0 ** 16), np.nextafter(F(2.0 ** 16), F(0)))
+
+
+def hdr_frame(w, h, seed=1, lo=-20.0, hi=20.0, special=True):
+    """(linear float32 (h, w, 3), object_id int32 (h, w)): luminances log-uniform over 2^lo .. 2^hi, a strip of id -1 and -- where
+    the frame has room -- pixels that are exactly 0, negative, NaN, +inf, and of luminance exactly 2^-16, just below it, exactly
+    2^16 and just below it"""
+    rng = np.random.default_rng(seed)
+    Y = 2.0 ** rng.uniform(lo, hi, (h, w))
+    lin = (Y[..., None] * rng.uniform(0.5, 1.5, (h, w, 3))).astype(F)
+    ids = rng.integers(0, 5, (h, w)).astype(np.int32)
+    ids[:, : max(1, w // 8)] = -1 if w > 1 else 0
+    if special and w * h >= 64:
+        flat, fid = lin.reshape(-1, 3), ids.reshape(-1)
+        at = w * (h // 2) + w // 2              # the middle row, away from the strip
+        vals = [(0, 0, 0), (-1.5, -0.25, -3), (np.nan, 1, 1), (np.inf, 1, 1)] + [(0, _green_for(y), 0) for y in SPECIAL_Y]
+        for k, v in enumerate(vals):
+            flat[at + k] = v
+            fid[at + k] = 1
+    return lin, ids
+
+
+HIST_FRAMES = {
+    "37x23": lambda: hdr_frame(37, 23),
+    "1x1": lambda: hdr_frame(1, 1, lo=-2, hi=2),
+    "3x2": lambda: hdr_frame(3, 2),
+    "5x40": lambda: hdr_frame(5, 40),
+    "257x9": lambda: hdr_frame(257, 9),                         # more than one workgroup, a multiple of nothing
+    "constant64x64": lambda: (np.full((64, 64, 3), 0.5, F), np.zeros((64, 64), np.int32)),      # one bin: the worst contention
+    # k_luminance_hist runs at most 512 workgroups of 256 lanes: one pixel more and a lane goes round its loop twice
+    "3x43691": lambda: hdr_frame(43691, 3, lo=-8, hi=8),
+}
+
+
+# ---- without a GPU -------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ("rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
+               "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap")
+
+
+def test_new_symbols_struct_layout_and_defaults():
+    L = capi.lib()
+    for name in NEW_SYMBOLS:
+        assert hasattr(L, name) and name in capi.SYMBOLS, name
+    assert L.rt_abi_version() == 4
+    assert [f[0] for f in capi.ToneMapParams._fields_] == ["struct_size", "op", "auto_exposure", "key", "ev_bias", "ev_min", "ev_max", "p_low",
+                                                           "p_high", "adapt_up", "adapt_down", "white", "gamma"]
+    assert [f[0] for f in capi.ToneMapPlanes._fields_] == ["struct_size", "rgb_linear", "object_id", "out_display", "out_rgb8"]
+    assert C.sizeof(capi.ToneMapParams) == 52 and C.sizeof(capi.ToneMapPlanes) == 40
+    p = capi.ToneMapParams()
+    L.rt_tonemap_default_params(C.byref(p))
+    assert (p.struct_size, p.op, p.auto_exposure) == (52, capi.TONEMAP_ACES, 1)
+    assert (capi.TONEMAP_CLAMP, capi.TONEMAP_REINHARD, capi.TONEMAP_ACES) == (0, 1, 2)
+    for k, v in DEFAULTS.items():
+        assert getattr(p, k) == (v if k == "auto_exposure" else F(v)), k
+    L.rt_tonemap_default_params(None)                           # ignored
+    q = capi.tonemap_params("reinhard", exposure_ev=1.5, white=2.0, auto_exposure=0)
+    assert (q.op, q.ev_bias, q.white, q.auto_exposure, q.key) == (1, 1.5, 2.0, 0, F(0.18))
+    with pytest.raises(TypeError):
+        capi.tonemap_params(levels=3)
+    with pytest.raises(KeyError):
+        capi.tonemap_params("filmic")
+    # the existing structs did not grow
+    assert C.sizeof(capi.Outputs) == 72 and C.sizeof(capi.DenoiseParams) == 24 and C.sizeof(capi.TemporalParams) == 24 and C.sizeof(capi.TemporalPlanes) == 88
+    L.rt_exposure_destroy(None)                                 # ignored
+
+
+def _arg_cases():
+    buf = np.zeros(8 * 8 * 3, np.float32)
+    ptr = buf.ctypes.data
+    full = lambda **kw: capi.ToneMapPlanes(**{**dict(rgb_linear=ptr, object_id=ptr, out_display=ptr, out_rgb8=ptr), **kw})
+    fixed = lambda **kw: capi.tonemap_params(**dict(dict(auto_exposure=0), **kw))      # a NULL state is allowed: every other check is reached
+    nan, inf = float("nan"), float("inf")
+    cases = []
+    for bad in (0, 51, 56):
+        p = fixed()
+        p.struct_size = bad
+        cases.append((b"struct_size", p, full(), 8, 8))
+    pl = full()
+    pl.struct_size += 8
+    cases.append((b"struct_size", fixed(), pl, 8, 8))
+    for w, h in ((0, 8), (8, 0), (-3, 8)):
+        cases.append((b"bad image size", fixed(), full(), w, h))
+    for bad in (-1, 3, 99):
+        cases.append((b"no operator", capi.tonemap_params(bad, auto_exposure=0), full(), 8, 8))
+    for name in ("key", "white", "gamma"):
+        for bad in (0.0, -1.0, nan, inf):
+            cases.append((b"positive and finite", fixed(**{name: bad}), full(), 8, 8))
+    for name in ("ev_bias", "ev_min", "ev_max"):
+        for bad in (nan, inf, -inf):
+            cases.append((b"ev_min <= ev_max", fixed(**{name: bad}), full(), 8, 8))
+    cases.append((b"ev_min <= ev_max", fixed(ev_min=2.0, ev_max=1.0), full(), 8, 8))
+    for lo, hi in ((-0.1, 0.9), (0.5, 0.5), (0.6, 0.4), (0.1, 1.5), (nan, 0.9), (0.1, nan)):
+        cases.append((b"percentiles", fixed(p_low=lo, p_high=hi), full(), 8, 8))
+    for name in ("adapt_up", "adapt_down"):
+        for bad in (0.0, -0.5, 1.5, nan):
+            cases.append((b"adapt_up and adapt_down", fixed(**{name: bad}), full(), 8, 8))
+    cases.append((b"rgb_linear is required", fixed(), full(rgb_linear=None), 8, 8))
+    cases.append((b"one of out_display and out_rgb8", fixed(), full(out_display=None, out_rgb8=None), 8, 8))
+    cases.append((b"needs an rt_exposure", capi.tonemap_params(), full(), 8, 8))
+    return buf, cases, full, fixed
+
+
+def test_argument_checks_come_before_any_gpu_call():
+    L = capi.lib()
+    buf, cases, full, fixed = _arg_cases()
+    for what, p, pl, w, h in cases:
+        for st in (L.rt_tonemap(None, 0, w, h, C.byref(p), C.byref(pl)), L.rt_tonemap_device(None, 0, None, w, h, C.byref(p), C.byref(pl), 1)):
+            assert st == -1 and what in L.rt_last_error(), (what, L.rt_last_error())
+    p, pl = fixed(), full()
+    for args in ((None, C.byref(pl)), (C.byref(p), None)):
+        assert L.rt_tonemap(None, 0, 8, 8, *args) == -1 and L.rt_tonemap_device(None, 0, None, 8, 8, *args, 1) == -1
+    # more than 2^30 pixels: RT_ERR_LIMIT, after the argument checks and before the device is looked for
+    assert L.rt_tonemap_device(None, 0, None, 1 << 16, (1 << 14) + 1, C.byref(p), C.byref(pl), 1) == -6 and b"2^30" in L.rt_last_error()
+    assert L.rt_tonemap(None, 0, 1 << 16, (1 << 14) + 1, C.byref(p), C.byref(pl)) == -6
+    assert L.rt_exposure_reset(None) == -1 and L.rt_exposure_create(0, None) == -1
+    assert L.rt_exposure_get(None, None, None, None) == -1 and L.rt_exposure_histogram(None, buf.ctypes.data) == -1
+    if capi.device_count() == 0:                                # ... and RT_ERR_NO_DEVICE comes after all of them
+        e = C.c_void_p()
+        assert L.rt_exposure_create(0, C.byref(e)) == -3 and not e
+        assert L.rt_tonemap(None, 0, 8, 8, C.byref(p), C.byref(pl)) == -3
+        assert L.rt_tonemap_device(None, 0, None, 8, 8, C.byref(p), C.byref(pl), 1) == -3
+        with pytest.raises(capi.RtError) as err:
+            capi.Exposure(0)
+        assert err.value.status == -3
+        with pytest.raises(capi.RtError) as err:
+            capi.tonemap(np.zeros((2, 2, 3), F))
+        assert err.value.status == -3
+
+
+def _build_shim_driver(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_tonemap_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_tonemap_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+def test_shim_driver_builds_against_the_header(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+def test_frame_holds_what_the_tests_rely_on():
+    lin, ids = hdr_frame(37, 23)
+    Y = ref_luminance(lin)
+    assert (ids < 0).sum() == 23 * 4 and lin.shape == (23, 37, 3)
+    for y in SPECIAL_Y:
+        assert (Y == y).sum() >= 1
+    assert np.isnan(Y).sum() == 1 and np.isposinf(Y).sum() == 1 and (Y == 0).sum() == 1 and (Y < 0).sum() == 1
+    fin = Y[np.isfinite(Y) & (Y > 0)]
+    assert fin.min() < 2.0 ** -18 and fin.max() > 2.0 ** 18     # both ends of the metered range are exceeded
+    h = ref_histogram(lin, ids)
+    assert h[0] >= 1 and h[255] >= 1 and (h > 0).sum() > 200
+    # 2^-16 is the first bin's first value, the float below it is not metered; 2^16 and everything above land in bin 255,
+    # the float below 2^16 is bin 255's last regular value
+    one = lambda y: ref_histogram(np.array([[[0, _green_for(y), 0]]], F))
+    assert one(SPECIAL_Y[0])[0] == 1 and one(SPECIAL_Y[1]).sum() == 0 and one(SPECIAL_Y[2])[255] == 1 and one(SPECIAL_Y[3])[255] == 1
+    assert one(F(1.0))[128] == 1 and one(F(2.0 ** 19))[255] == 1
+
+
+@pytest.mark.parametrize("name", ["37x23", "5x40", "257x9"])
+def test_reference_histogram_sums_to_the_metered_pixels_and_shifts_with_the_frame(name):
+    lin, ids = HIST_FRAMES[name]()
+    lin, ids = hdr_frame(lin.shape[1], lin.shape[0], lo=-6, hi=6, special=False)       # every pixel stays in range under 2^+-3
+    Y = ref_luminance(lin)
+    for use_ids in (ids, None):
+        h = ref_histogram(lin, use_ids)
+        metered = np.isfinite(Y) & (Y >= F(2.0 ** -16)) & ((use_ids >= 0) if use_ids is not None else True)
+        assert int(h.sum()) == int(metered.sum()) == ref_lbar(h)[0]
+        n, lbar = ref_lbar(h)
+        ex = RefExposure()
+        ex.meter(lin, use_ids)
+        for k in (-3, 1, 3):
+            hk = ref_histogram(lin * F(2.0 ** k), use_ids)     # a power of two: exact, and the bins are read off the exponent
+            assert (np.roll(h, 8 * k) == hk).all() and hk.sum() == h.sum()
+            # Lbar shifts by exactly k and E_t by exactly -k: equality, asserted on the exact values -- the rationals the integers
+            # of step 3 define.  The DOUBLES are not equal bit for bit: S / (16 m) and (S + 16 k m) / (16 m) are rounded in
+            # different binades, so fl(S'/(16 m)) - 16 and (fl(S/(16 m)) - 16) + k can differ in the last bit (DESIGN 3 says so);
+            # they are held to the two roundings they are apart, and the float E to the float stores of both sides.
+            (_, S, m), (_, Sk, mk) = ref_sum(h), ref_sum(hk)
+            assert mk == m and Sk == S + 16 * k * m
+            exact = lambda S_: Fraction(S_, 16 * m) - 16
+            assert exact(Sk) == exact(S) + k
+            target = lambda S_: Fraction(math.log2(float(F(0.18)))) - exact(S_)         # ev_bias 0, far from ev_min / ev_max
+            assert target(Sk) == target(S) - k and -16 < target(Sk) < 16 and -16 < target(S) < 16
+            assert abs(ref_lbar(hk)[1] - (lbar + k)) <= GATE_LBAR and abs(Fraction(ref_lbar(hk)[1]) - exact(Sk)) <= GATE_LBAR
+            exk = RefExposure()
+            exk.meter(lin * F(2.0 ** k), use_ids)
+            assert abs(float(exk.E) - (float(ex.E) - k)) <= 2.0 ** -20      # one ulp of a float below 16, for the two stores
+            assert abs(Fraction(float(exk.E)) - target(Sk)) <= 2.0 ** -21   # and each E is its exact target rounded to float
+
+
+def test_reference_window_and_an_unmetered_frame():
+    for n in (1, 2, 3, 10, 4096, 2 ** 30):
+        lo, hi = ref_window(n, 0.10, 0.90)
+        assert 0 <= lo < hi <= n
+    assert [ref_window(n, 0.10, 0.90) for n in (1, 2, 3)] == [(0, 1), (0, 2), (0, 3)]
+    assert ref_window(10, 0.0, 1.0) == (0, 10)
+    # one sample per bin 10, 20, 30 and the full window: the mean of the three bin centres
+    h = np.zeros(256, np.uint32)
+    h[[10, 20, 30]] = 1
+    assert ref_lbar(h, 0.0, 1.0) == (3, (21 + 41 + 61) / 48 - 16)
+    assert ref_lbar(h, 0.34, 0.66) == (3, 41 / 16 - 16)         # ranks [1, 2): the middle sample alone
+    ex = RefExposure()
+    black = np.zeros((4, 4, 3), F)
+    assert ex.meter(black) == F(1) and ex.E == 0 and not ex.holds           # nothing metered, no earlier frame: clamp(ev_bias)
+    assert ex.meter(black, ev_bias=20.0) == F(2.0 ** 16)
+    lin, ids = hdr_frame(37, 23, lo=-6, hi=6, special=False)                # times 4 the same pixels are metered
+    ex.meter(lin, ids, adapt_up=0.5, adapt_down=0.5)                        # still the first metered frame: E = E_t
+    assert ex.holds and float(ex.E) == float(F(math.log2(float(F(0.18))) - ex.lbar))
+    E = ex.E
+    assert ex.meter(black) == F(2.0 ** float(E)) and ex.E == E and ex.n == 0      # a frame with nothing metered keeps E
+    assert ex.meter(np.full((4, 4, 3), np.nan, F)) == F(2.0 ** float(E)) and ex.E == E
+    ex.meter(lin * F(4), ids, adapt_up=0.5, adapt_down=0.25)                # brighter: the target is 2 lower, a quarter of the way
+    assert abs(float(ex.E) - (float(E) - 0.5)) < 1e-6
+
+
+def test_remetering_bound_holds_for_the_transcription():
+    """CLAMP, then the display plane metered again: Lbar' is within 1/8 + 0.0861 of log2(key) + ev_bias.  Frames whose range
+    stays inside the histogram's after the scaling, so that the same pixels are metered both times."""
+    for seed, (lo, hi), kw in ((1, (-6, 6), {}), (2, (-10, 2), dict(key=0.5)), (3, (0, 9), dict(ev_bias=-1.25)), (4, (3, 3.01), {})):
+        lin, ids = hdr_frame(37, 23, seed=seed, lo=lo, hi=hi, special=False)
+        ex = RefExposure()
+        scale = ex.meter(lin, ids, **kw)
+        disp = apply_f32(lin, scale, "clamp")
+        n2, lbar2 = ref_lbar(ref_histogram(disp, ids))
+        p = dict(DEFAULTS, **kw)
+        assert n2 == ex.n and abs(lbar2 - (math.log2(p["key"]) + p["ev_bias"])) <= REMETER, (seed, lbar2)
+
+
+def test_operator_gates_hold_for_a_float32_evaluation():
+    """the counted gates against the float64 transcription, for an evaluation that rounds every operation to float32: positive
+    pixels over 2^-24 .. 2^24, and pixels that are negative in every channel"""
+    rng = np.random.default_rng(5)
+    mag = 2.0 ** rng.uniform(-24, 24, (200000, 1))
+    for sign in (1.0, -1.0):
+        lin = (sign * mag * rng.uniform(0.5, 1.5, (200000, 3))).astype(F)
+        for scale in (F(1), F(0.3712), F(2.0 ** 7.3)):
+            for op in ("clamp", "reinhard", "aces"):
+                worst = _display_gate(apply_f32(lin, scale, op), ref_apply(lin, scale, op), op)
+                assert worst <= 1.0 * (GATE_C[op] - 2) / GATE_C[op], (sign, scale, op, worst)       # no exp2 in this evaluation: 2u less
+    y = ref_apply(np.array([[np.nan, -1.0, 1e9]], F), 1.0, "aces")
+    assert np.isnan(y[0, 0]) and y[0, 1] == 1.0 and 0.99 < y[0, 2] <= 1.0
+
+
+# ---- on the GPU ----------------------------------------------------------------------------------------------------
+def _check_state(exp, ref, what):
+    assert (exp.histogram() == ref.hist).all(), what
+    assert exp.metered_pixels == ref.n, what
+    dl, de = abs(exp.log2_metered - ref.lbar), abs(exp.log2_exposure - float(ref.E))
+    print(f"tonemap {what}: n {ref.n}, Lbar {ref.lbar:.6f} (error {dl:.3g}, gate {GATE_LBAR:.3g}), "
+          f"E {float(ref.E):.6f} (error / gate {de / GATE_E:.3f})")
+    assert dl <= GATE_LBAR and de <= GATE_E, (what, dl, de)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_ids", [True, False])
+@pytest.mark.parametrize("name", list(HIST_FRAMES))
+def test_histogram_and_exposure_equal_the_transcription(name, with_ids):
+    lin, ids = HIST_FRAMES[name]()
+    ids = ids if with_ids else None
+    ref = RefExposure()
+    ref.meter(lin, ids)
+    with capi.Exposure(0) as exp:
+        assert exp.metered_pixels == 0 and not exp.histogram().any() and exp.log2_exposure == 0.0
+        out8 = exp.tonemap(lin, ids)
+        assert out8.dtype == np.uint8 and out8.shape == lin.shape
+        _check_state(exp, ref, f"{name} ids={with_ids}")
+        if name == "constant64x64":
+            h = exp.histogram()
+            assert h.max() == 4096 and (h > 0).sum() == 1 and h[120] == 4096     # Y = 0.5: bin (126 - 111) * 8
+
+
+@pytest.mark.gpu
+def test_exposure_sequences_reset_black_frame_clamping_and_fixed_exposure():
+    lin, ids = hdr_frame(37, 23, lo=-6, hi=6)
+    bright, dark = lin * F(8), lin * F(0.125)
+    black = np.zeros_like(lin)
+    adapt = dict(adapt_up=0.5, adapt_down=0.25)
+    with capi.Exposure(0) as exp:
+        ref = RefExposure()
+        for rnd in range(2):
+            for k, (fr, kw) in enumerate(((bright, {}), (dark, {}), (dark, adapt), (bright, adapt))):
+                exp.tonemap(fr, ids, **kw)
+                ref.meter(fr, ids, **kw)
+                _check_state(exp, ref, f"sequence round {rnd} frame {k}")
+            assert abs(exp.log2_exposure - float(ref.E)) <= GATE_E and ref.E != F(math.log2(0.18) - ref.lbar)     # part of the way only
+            # an all-black frame in the middle leaves E unchanged bit for bit
+            before = exp.log2_exposure
+            exp.tonemap(black, ids, **adapt)
+            assert exp.log2_exposure == before and exp.metered_pixels == 0 and not exp.histogram().any()
+            ref.meter(black, ids, **adapt)
+            exp.tonemap(dark, ids, **adapt)
+            ref.meter(dark, ids, **adapt)
+            _check_state(exp, ref, f"sequence round {rnd} after the black frame")
+            exp.reset()
+            ref.reset()
+            assert exp.log2_exposure == 0.0 and exp.metered_pixels == 0 and not exp.histogram().any()
+        # black first: clamp(ev_bias), and the next metered frame is still the first (no adaptation from that value)
+        exp.tonemap(black, ids, ev_bias=3.0, ev_max=2.0, **adapt)
+        assert exp.log2_exposure == 2.0
+        ref.meter(black, ids, ev_bias=3.0, ev_max=2.0, **adapt)
+        exp.tonemap(dark, ids, **adapt)
+        ref.meter(dark, ids, **adapt)
+        _check_state(exp, ref, "first metered frame after a black one")
+        assert abs(exp.log2_exposure - (math.log2(0.18) - ref.lbar)) <= GATE_E
+        # ev_min / ev_max
+        exp.reset()
+        ref.reset()
+        exp.tonemap(dark, ids, ev_max=0.25)                     # the dark frame asks for about +0.5, the bright one for about -5.5
+        assert ref.meter(dark, ids, ev_max=0.25) == F(2.0 ** 0.25) and exp.log2_exposure == 0.25
+        exp.tonemap(bright, ids, ev_min=-0.5, ev_max=0.25)
+        assert ref.meter(bright, ids, ev_min=-0.5, ev_max=0.25) == F(2.0 ** -0.5) and exp.log2_exposure == -0.5
+        # auto_exposure=0 with exposure_ev: the state is not touched, the scale is 2^exposure_ev
+        h_before, e_before = exp.histogram(), exp.log2_exposure
+        _, disp = exp.tonemap(lin, ids, operator="clamp", display=True, auto_exposure=0, exposure_ev=-2.0)
+        assert disp.tobytes() == (lin * F(0.25)).tobytes()
+        assert (exp.histogram() == h_before).all() and exp.log2_exposure == e_before
+    _, disp = capi.tonemap(lin, exposure_ev=3.0, operator="clamp", display=True)
+    assert disp.tobytes() == (lin * F(8)).tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("operator", ["clamp", "reinhard", "aces"])
+def test_operators_against_the_float64_transcription(operator):
+    lin, ids = hdr_frame(37, 23)
+    worst = 0.0
+    with capi.Exposure(0) as exp:
+        for kw in ({}, dict(key=0.5, white=2.0), dict(ev_bias=6.0)):
+            out8, disp = exp.tonemap(lin, ids, operator=operator, display=True, **kw)
+            scale = F(2.0 ** float(F(exp.log2_exposure)))       # the device's E: the exposure's rounding is not counted twice
+            want = ref_apply(lin, scale, operator, white=kw.get("white", 4.0))
+            worst = max(worst, _display_gate(disp, want, operator))
+            _assert_rgb8_encodes(disp, out8)
+            nan = np.isnan(disp)
+            assert nan.any() and (out8[nan] == 0).all()         # a NaN gives byte 0
+            if operator == "aces":
+                assert (disp[~nan] >= 0).all() and (disp[~nan] <= 1).all()
+            exp.reset()
+    print(f"tonemap {operator}: worst error / gate {worst:.3f} (gate {GATE_C[operator]} * 2^-24 * |want| + 1e-7)")
+    assert worst <= 1.0
+
+
+def _denoise_planes(w, h, seed=3):
+    rng = np.random.default_rng(seed)
+    lin = (2.0 ** rng.uniform(-6, 2, (h, w, 1)) * rng.uniform(0.5, 1.5, (h, w, 3))).astype(F)
+    normal = np.zeros((h, w, 3), F)
+    normal[..., 2] = 1
+    albedo = np.full((h, w, 3), 0.5, F)
+    z = np.full((h, w), 10.0, F)
+    ids = np.zeros((h, w), np.int32)
+    ids[:, :3], z[:, :3] = -1, 1e30
+    return lin, normal, albedo, z, ids
+
+
+@pytest.mark.gpu
+def test_clamp_at_zero_ev_gives_the_denoisers_bytes():
+    """the anchor: the same rule on the same floats on one build"""
+    lin, normal, albedo, z, ids = _denoise_planes(37, 23)
+    den, out8 = capi.denoise(lin, normal, albedo, z, ids, rgb8=True)
+    assert (den > 1).any() and (out8 == 255).any() and (out8 < 255).any()
+    got, disp = capi.tonemap(den, exposure_ev=0.0, operator="clamp", display=True)
+    assert disp.tobytes() == den.tobytes()
+    assert got.tobytes() == out8.tobytes()
+
+
+@pytest.mark.gpu
+def test_determinism_entry_points_aliasing_and_two_states():
+    import torch
+    w, h = 37, 23
+    lin, ids = hdr_frame(w, h, lo=-6, hi=6)
+    frames = [lin, lin * F(0.125), lin * F(3)]
+    other, other_ids = hdr_frame(90, 60, seed=9)
+    kw = dict(operator="reinhard", adapt_up=0.5, adapt_down=0.25)
+
+    def host_run(disturb=False):
+        outs = []
+        with capi.Exposure(0) as exp, capi.Exposure(0) as second:
+            for fr in frames:
+                out8, disp = exp.tonemap(fr, ids, display=True, **kw)
+                outs.append((out8, disp, exp.histogram(), np.float32(exp.log2_exposure)))
+                if disturb:                                     # another state, fed frames of another size in between
+                    second.tonemap(other, other_ids)
+        return outs
+
+    first, again = host_run(), host_run(disturb=True)
+    for a, b in zip(first, again):
+        for x, y in zip(a, b):
+            assert x.tobytes() == y.tobytes()
+    assert first[0][0].tobytes() != first[1][0].tobytes()
+
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(device=dev)
+    t = [torch.from_numpy(fr).to(dev) for fr in frames]
+    tid = torch.from_numpy(ids).to(dev)
+    torch.cuda.synchronize()
+    with capi.Exposure(0) as out_of_place, capi.Exposure(0) as in_place:
+        for k, tl in enumerate(t):
+            disp = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+            rgb8b = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+            lin2 = tl.clone()
+            side.wait_stream(torch.cuda.current_stream(dev))
+            out_of_place.tonemap_device(side.cuda_stream, w, h, linear_ptr=tl.data_ptr(), object_id_ptr=tid.data_ptr(), rgb8_ptr=rgb8.data_ptr(),
+                                        display_ptr=disp.data_ptr(), sync=False, **kw)
+            in_place.tonemap_device(side.cuda_stream, w, h, linear_ptr=lin2.data_ptr(), object_id_ptr=tid.data_ptr(), rgb8_ptr=rgb8b.data_ptr(),
+                                    display_ptr=lin2.data_ptr(), sync=False, **kw)
+            side.synchronize()
+            want = first[k]
+            assert rgb8.cpu().numpy().tobytes() == want[0].tobytes() and disp.cpu().numpy().tobytes() == want[1].tobytes()
+            assert rgb8b.cpu().numpy().tobytes() == want[0].tobytes() and lin2.cpu().numpy().tobytes() == want[1].tobytes()
+            assert tl.cpu().numpy().tobytes() == frames[k].tobytes() and tid.cpu().numpy().tobytes() == ids.tobytes()       # inputs are left alone
+            assert (out_of_place.histogram() == want[2]).all() and np.float32(in_place.log2_exposure) == want[3]
+        # rgb8 alone, and the display plane alone
+        only8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        out_of_place.reset()
+        out_of_place.tonemap_device(side.cuda_stream, w, h, linear_ptr=t[0].data_ptr(), object_id_ptr=tid.data_ptr(), rgb8_ptr=only8.data_ptr(), **kw)
+        assert only8.cpu().numpy().tobytes() == first[0][0].tobytes()
+        only_d = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+        in_place.reset()
+        in_place.tonemap_device(side.cuda_stream, w, h, linear_ptr=t[0].data_ptr(), object_id_ptr=tid.data_ptr(), display_ptr=only_d.data_ptr(), **kw)
+        assert only_d.cpu().numpy().tobytes() == first[0][1].tobytes()
+        with pytest.raises(capi.RtError) as err:                # the argument checks with a state
+            out_of_place.tonemap_device(side.cuda_stream, w, h, linear_ptr=t[0].data_ptr())
+        assert err.value.status == -1
+        # a device that is not the state's is refused, whether or not such a device exists, and the state is left alone
+        L, p = capi.lib(), capi.tonemap_params()
+        pl = capi.ToneMapPlanes(rgb_linear=t[0].data_ptr(), out_rgb8=only8.data_ptr())
+        before = out_of_place.histogram()
+        for entry in (lambda: L.rt_tonemap_device(out_of_place._h, 1, None, w, h, C.byref(p), C.byref(pl), 1),
+                      lambda: L.rt_tonemap(out_of_place._h, 1, w, h, C.byref(p), C.byref(pl))):
+            assert entry() == -1 and b"the state is on device 0, the call names 1" in L.rt_last_error()
+        assert (out_of_place.histogram() == before).all()
+
+
+# ---- GPU: real frames -------------------------------------------------------------------------------------------
+def _gi_params(seed):
+    return capi.default_params(min_sample=4, max_sample=8, threshold=1e30, seed=seed, shade_model=capi.SHADE_P12, bounce=8, hemisphere_sample=1,
+                               photon_count=0)
+
+
+@pytest.mark.gpu
+def test_render_denoised_and_render_temporal_with_an_exposure():
+    """cornell_gi.xml, live GI, 96 x 72, 4 spp, reproducible mode"""
+    s, cam = scenes.load_cornell_gi(96, 72)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    plain = s.render_denoised(cam, _gi_params(1))
+    with capi.Exposure(0) as exp:
+        out = s.render_denoised(cam, _gi_params(1), exposure=exp, tonemap_kw=dict(operator="clamp"))
+        assert out["display_rgb"].dtype == np.uint8 and out["display_rgb"].shape == (72, 96, 3)
+        assert set(out) == set(plain) | {"display_rgb"}
+        for k, v in plain.items():
+            if isinstance(v, np.ndarray):
+                assert out[k].tobytes() == v.tobytes(), k
+        ref = RefExposure()
+        scale = ref.meter(out["denoised"], out["object_id"])
+        _check_state(exp, ref, "cornell_gi denoised")
+        assert out["display_rgb"].tobytes() == capi.tonemap(out["denoised"], exposure_ev=exp.log2_exposure, operator="clamp").tobytes()
+        assert out["display_rgb"].tobytes() != out["denoised_rgb"].tobytes()
+        # the re-metering bound on the result: the display plane metered again lies at the key
+        _, disp = capi.tonemap(out["denoised"], exposure_ev=exp.log2_exposure, operator="clamp", display=True)
+        with capi.Exposure(0) as again:
+            again.tonemap(disp, out["object_id"], operator="clamp")
+            lbar2 = again.log2_metered
+            assert again.metered_pixels == exp.metered_pixels
+        print(f"tonemap cornell_gi 96x72: E {exp.log2_exposure:.4f}, Lbar {exp.log2_metered:.4f}, re-metered Lbar' - log2(key) "
+              f"{lbar2 - math.log2(0.18):+.4f} (bound {REMETER:.4f})")
+        assert abs(lbar2 - math.log2(0.18)) <= REMETER
+        assert ref.n == exp.metered_pixels == int((out["object_id"] >= 0).sum()) and scale > 0
+    # three frames through render_temporal with adapt 0.5: the exposure follows the transcription fed the same planes
+    tm = dict(adapt_up=0.5, adapt_down=0.5, key=0.18)
+    with capi.History(0, 96, 72) as hst, capi.History(0, 96, 72) as hst_plain, capi.Exposure(0) as exp:
+        ref = RefExposure()
+        for k, (seed, key) in enumerate(((1, 0.18), (2, 0.36), (3, 0.09))):
+            tm["key"] = key                                     # a moving target, so that the adaptation has something to follow
+            denoise = k != 1
+            out = s.render_temporal(hst, cam, _gi_params(seed), denoise=denoise, exposure=exp, tonemap_kw=tm)
+            plain = s.render_temporal(hst_plain, cam, _gi_params(seed), denoise=denoise)
+            assert set(out) == set(plain) | {"display_rgb"} and out["display_rgb"].shape == (72, 96, 3)
+            for name, v in plain.items():
+                if isinstance(v, np.ndarray):
+                    assert out[name].tobytes() == v.tobytes(), name
+            ref.meter(out["denoised" if denoise else "accumulated"], out["object_id"], **tm)
+            _check_state(exp, ref, f"cornell_gi temporal frame {k}")
+
+
+@pytest.mark.gpu
+def test_cpp_shim_tonemap_equals_the_capi_one(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    prefix = str(tmp_path / "f")
+    r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    words = r.stdout.split()
+    assert words[1] == str(64 * 48), r.stdout
+    s, cam = scenes.load_cornell(64, 48)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=11)
+    with capi.Exposure(0) as exp:
+        one = s.render_outputs(cam, p, planes=("linear", "object_id"))
+        rgb1, disp1 = exp.tonemap(one["linear"], one["object_id"], display=True)
+        e1 = exp.log2_exposure
+        p.seed = 12
+        two = s.render_outputs(cam, p, planes=("linear", "object_id"))
+        rgb2, disp2 = exp.tonemap(two["linear"], two["object_id"], operator="reinhard", display=True, adapt_up=0.5, adapt_down=0.5)
+        e2 = exp.log2_exposure
+    assert capi.image_read_pfm(prefix + "_disp1.pfm").tobytes() == disp1.tobytes()
+    assert capi.image_read_pfm(prefix + "_disp2.pfm").tobytes() == disp2.tobytes()
+    assert open(prefix + "_rgb1.bin", "rb").read() == rgb1.tobytes() and open(prefix + "_rgb2.bin", "rb").read() == rgb2.tobytes()
+    assert np.float32(float(words[-2])) == np.float32(e1) and np.float32(float(words[-1])) == np.float32(e2)
+    assert os.path.getsize(prefix + "_2.png") > 0 and rgb1.tobytes() != rgb2.tobytes()
