@@ -150,12 +150,17 @@ __device__ __forceinline__ bool plane_hit(int model, V3 P, V3 d, float &z, V3 &h
 // (accepts boxes behind the ray, never culls by distance); this one culls against the closest
 // hit so far and is padded by 2e-6 relative so that reciprocal rounding never rejects a box
 // whose triangle the exact test would accept.  Returns the entry distance, or BIGFLOAT*2.
+// `inv` comes from slab_inv: NaN where the direction component is zero.  Both products of that axis are then NaN and the fmaxf /
+// fminf below drop them (they return the other operand): a slab the ray runs parallel to does not constrain it, as in
+// Box::IntersectRay, which skips an axis with dir == 0.  (With inv = 1/0 = inf and the origin ON a plane of the slab one
+// product is 0 * inf = NaN and the other +-inf, which min / max keep on BOTH sides: tenter = +inf or texit = -inf, and a box
+// the reference enters was rejected.)  An unused child's bounds are NaN on every axis: tenter and texit NaN, never a hit.
+__device__ __forceinline__ float slab_inv(float d, float rcp) { return d == 0.0f ? __builtin_nanf("") : rcp; }
 __device__ __forceinline__ float box_entry(const float *lo, const float *hi, V3 o, V3 inv, float zbest)
 {
     const float t0x = (lo[0] - o.x) * inv.x, t1x = (hi[0] - o.x) * inv.x;
     const float t0y = (lo[1] - o.y) * inv.y, t1y = (hi[1] - o.y) * inv.y;
     const float t0z = (lo[2] - o.z) * inv.z, t1z = (hi[2] - o.z) * inv.z;
-    // fminf/fmaxf drop NaN operands (0*inf when the origin lies on a slab plane and dir == 0)
     const float tenter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
     const float texit = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
     const bool hit = (texit >= 0.0f) && (tenter <= texit * 1.000002f) && (tenter * 0.999998f <= zbest);
@@ -279,7 +284,7 @@ __device__ bool mesh_hit(const DevMesh *Mp, V3 o, V3 d, float &z, V3 &hp, V3 &hN
     M.nodes = cld(&Mp->nodes); M.tris = cld(&Mp->tris); M.nrm = cld(&Mp->nrm); M.tex = cld(&Mp->tex);
     for (int i = 0; i < 6; i++) M.root_box[i] = cld(Mp->root_box + i);
     M.root_ref = cld(&Mp->root_ref);
-    const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const V3 inv = mk(slab_inv(d.x, 1.0f / d.x), slab_inv(d.y, 1.0f / d.y), slab_inv(d.z, 1.0f / d.z));
     if (box_entry(M.root_box, M.root_box + 3, o, inv, z) > 2.0e30f) return false;
     uint32_t cur = M.root_ref;
     uint32_t sp = 0;
@@ -382,7 +387,7 @@ __device__ bool trace(const DevScene &S, V3 o, V3 d, float zinit, Hit &h, const 
     int cached1 = -1;
     // reciprocal direction (in the root's coordinates) for the bounds cull only: approximate is fine, the
     // bounds are inflated
-    const V3 winv = mk(__builtin_amdgcn_rcpf(d0.x), __builtin_amdgcn_rcpf(d0.y), __builtin_amdgcn_rcpf(d0.z));
+    const V3 winv = mk(slab_inv(d0.x, __builtin_amdgcn_rcpf(d0.x)), slab_inv(d0.y, __builtin_amdgcn_rcpf(d0.y)), slab_inv(d0.z, __builtin_amdgcn_rcpf(d0.z)));
     // any-hit queries: the object that occluded the last shadow ray of this wave is tried first (its neighbours' rays mostly end on
     // the same occluder, and the first accepted hit ends a lane's query: the order of the objects does not change the answer)
     int hint = -1;

@@ -36,6 +36,16 @@ def camera_rays(cam, n, seed=0):
     return np.stack([orc.primary_ray(oc, x, y, j) for x, y, j in zip(xs, ys, js)])
 
 
+def assert_hits_equal(got, hit, hits):
+    """closest-hit records of the product (got) against the oracle's (hit, hits): flag, node, front equal, z / p / N bit-exact"""
+    assert (got["hit"].astype(bool) == hit.astype(bool)).all()
+    h = hit.astype(bool)
+    assert (got["node"][h] == hits["node"][h]).all()
+    assert (got["front"][h] == hits["front"][h]).all()
+    for f in ("z", "p", "N"):
+        assert got[f][h].tobytes() == hits[f][h].tobytes(), f
+
+
 def rebuild(export, materials=None, lights=None):
     """A new product scene from exported arrays, with materials / lights optionally replaced."""
     s = capi.Scene()

@@ -32,13 +32,7 @@ def _rays_inside_box(n, seed):
     return np.concatenate([o, d], 1).astype(np.float32)
 
 
-def _assert_hits_equal(got, hit, hits):
-    assert (got["hit"].astype(bool) == hit.astype(bool)).all()
-    h = hit.astype(bool)
-    assert (got["node"][h] == hits["node"][h]).all()
-    assert (got["front"][h] == hits["front"][h]).all()
-    for f in ("z", "p", "N"):
-        assert got[f][h].tobytes() == hits[f][h].tobytes(), f
+_assert_hits_equal = scenes.assert_hits_equal
 
 
 @pytest.mark.parametrize("model", [capi.SHADE_FIN, capi.SHADE_P13])
