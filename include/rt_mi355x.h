@@ -656,7 +656,9 @@ rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise
  * The temporal part the variance-guided filter leaves out: a viewer or a fly-through renders the same STATIC scene frame after
  * frame with independent noise, and an rt_history blends each new frame into what the earlier ones left, reprojected from the
  * camera of the frame it holds into the new one.  Like the denoiser it is an image-space operation on image-sized planes (row-
- * major, W x H) and knows nothing of scenes; only the camera may move between frames (no motion vectors).  The accumulated
+ * major, W x H) and knows nothing of scenes; rt_temporal reprojects with the camera alone, so only the camera may move between
+ * frames -- when nodes move too, rt_motion ("motion vectors" below) says where each pixel was and rt_temporal_motion takes the
+ * reprojection from that plane.  The accumulated
  * colour and variance are what rt_denoise_var_* takes as rgb_linear and variance.  The reference has no counterpart.
  * Definition, per pixel p = (x, y) of the new frame:
  *   1. Validity and demodulation are the denoiser's steps 1-2: p is VALID when object_id >= 0 (id plane given) or z < 1e30 (no
@@ -733,6 +735,70 @@ rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera 
                              const rt_temporal_planes *device_planes, int sync);
 /* The planes are HOST arrays: upload, accumulate, download. */
 rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes);
+
+/* ---- motion vectors (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) --------------------------------------------------------------------------------------------------------------
+ * rt_scene_set_nodes lets a caller move any node between two frames.  Under a fixed camera a moved node's pixels reproject onto
+ * themselves, find the same object id and normal and (almost always) an acceptable depth: rt_temporal would blend in history
+ * from another surface point.  rt_motion computes, in image space and without tracing a ray, where each pixel's surface point
+ * was in the PREVIOUS frame's image; rt_temporal_motion accumulates with that plane in place of its own reprojection.  Only node
+ * transforms move: meshes do not deform, and lights are not followed.  The reference has no counterpart.
+ * `motion` is float[W*H*3], row-major: for the pixel p = (x, y) of the new frame (fx, fy, z_exp) -- (fx, fy) the position of p's
+ * surface point in the previous frame's image, in the coordinates of step 3 of "temporal accumulation" (an integer coordinate is
+ * a pixel centre: fx = x, fy = y means "did not move"), z_exp the expected depth of that point measured from the previous
+ * camera.  Definition:
+ *   a. World point: step 2 of "temporal accumulation", unchanged: P = pos + z_p * normalize(M s(x, y)) from this frame's camera
+ *      (`dof` is ignored, with the same error).
+ *   b. Node transform.  i = object_id[p]; the ancestor chain of i runs root -> ... -> i through `parent`.  X_obj = TransformTo
+ *      down the chain of the CURRENT nodes (per node itm (X - pos), from the root downwards); P_prev = TransformFrom up the chain
+ *      of the PREVIOUS nodes (per node tm X + pos, from node i up to the root).  The two chains are composed on the host in
+ *      double into one affine map per node, A_i = (R_i, t_i), rounded to float once; a node whose whole chain is bit-identical in
+ *      both arrays gets exactly the identity (R = I, t = 0), so a static node's P_prev is P bit for bit.  The kernel evaluates
+ *      P_prev = R_i P + t_i, per component ((R_k0 P.x + R_k1 P.y) + R_k2 P.z) + t_k.
+ *   c. Step 3 of "temporal accumulation" applied to P_prev with the previous camera (primed): q, fx, fy and
+ *      z_exp = |P_prev - pos'|.  (The device code of a. and c. is the one function k_temporal runs.)
+ *   d. NO PREVIOUS POSITION: the pixel holds (x, y, 0) when object_id[p] < 0, z_p >= 1e30 or z_p is not finite, i >= n_nodes, or
+ *      q.z >= 0.  z_exp <= 0 is the marker.
+ *   e. DID NOT MOVE: when A_i is exactly the identity and the two cameras are bit-identical, the pixel holds (x, y, z_p) --
+ *      what a.-c. give in exact arithmetic -- provided z_p > 0 (otherwise d. would not be told apart: the steps are run).
+ * One lane per pixel, no atomics: the outputs are byte-identical for identical inputs.
+ * rt_temporal_motion / rt_temporal_motion_device are rt_temporal / rt_temporal_device with one more argument, the motion plane
+ * of this frame (W*H*3 floats; the struct cannot grow).  Steps 2-3 of "temporal accumulation" are replaced by reading
+ * (fx, fy, z_exp) of the pixel itself: the pixel has NO HISTORY when z_exp <= 0, when any of the three values is not finite, or
+ * when the history holds no frame.  Steps 1, 4, 5 and 6 are unchanged -- the tap order, the (-1, W) x (-1, H) guard on (fx, fy),
+ * the id, normal and depth tests, and `cam` stored as the history's camera (a later rt_temporal reprojects from it).  Stored
+ * normals are NOT rotated with the object: a node that turns by more than sigma_normal allows between two frames (|n' - n| >
+ * sigma_normal, about 17 degrees at 0.3) loses its history for that frame, which is conservative.  A NULL motion plane is
+ * RT_ERR_ARG.  rt_temporal and rt_temporal_device are unchanged, to the byte.
+ * rt_motion / rt_motion_device: `nodes` and `prev_nodes` are HOST arrays of n_nodes rt_node each (rt_scene_get_nodes' order: the
+ * indices the object_id plane holds), consumed before the call returns; prev_nodes == NULL means "nothing moved": every node
+ * gets the identity.  Checked before the GPU is touched, RT_ERR_ARG: a NULL cam, prev_cam, nodes or planes; a wrong struct_size;
+ * a NULL z, object_id or motion; n_nodes <= 0; in either array a `parent` that is not < its own index or is < -1; a camera of
+ * size <= 0, or cameras whose sizes differ from each other.  No gfx950 device is RT_ERR_NO_DEVICE (there is no CPU path).
+ * The library keeps the node table of the last call on each device (48 bytes a node) and uploads a call's table only when it
+ * differs; calls on one device are therefore ordered on the GPU one behind the other, whatever their streams, like rt_denoise's.
+ * The table is released with the denoiser's scratch, when the last rt_scene is destroyed; a process that never creates a scene
+ * keeps it until it exits. */
+typedef struct rt_motion_planes {
+    uint32_t struct_size;
+    const float *z;
+    const int32_t *object_id;
+    float *motion;              /* float W*H*3: (fx, fy, z_exp) */
+} rt_motion_planes;
+/* The planes are DEVICE pointers on `device`; the kernel is enqueued on `hip_stream` (NULL = the device's legacy null stream)
+ * and the call returns without waiting for it unless `sync` is non-zero. */
+rt_status rt_motion_device(int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam,
+                           const rt_node *nodes, const rt_node *prev_nodes, int32_t n_nodes,
+                           const rt_motion_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, compute, download. */
+rt_status rt_motion(int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
+                    const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *host_planes);
+/* motion_dev: a DEVICE plane on the history's device, read by the kernel (it must stay valid until the call's work is done) */
+rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                    const rt_temporal_planes *device_planes, const float *motion_dev, int sync);
+/* The planes and `motion` are HOST arrays: upload, accumulate, download. */
+rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p,
+                             const rt_temporal_planes *host_planes, const float *motion);
 
 /* ---- exposure and tone mapping (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs
  *      above are unchanged) -------------------------------------------------------------------------------------------------

@@ -99,6 +99,14 @@ class TemporalPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(TemporalPlanes), **planes)
 
 
+class MotionPlanes(C.Structure):
+    """rt_motion_planes: z and object_id of the new frame in, the motion plane (fx, fy, z_exp per pixel) out; all required"""
+    _fields_ = [("struct_size", C.c_uint32), ("z", C.c_void_p), ("object_id", C.c_void_p), ("motion", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(MotionPlanes), **planes)
+
+
 class ToneMapParams(C.Structure):
     """rt_tonemap_params: exposure and tone mapping (rt_tonemap_default_params fills ACES, auto-exposure on, key 0.18, ev_bias 0,
     ev -16..16, percentiles 0.10..0.90, adapt 1 / 1, white 4, gamma 2.2)"""
@@ -176,6 +184,7 @@ SYMBOLS = [
     "rt_denoise_var_default", "rt_denoise_var_device", "rt_denoise_var_host",
     "rt_history_create", "rt_history_reset", "rt_history_destroy", "rt_history_frames",
     "rt_temporal_default_params", "rt_temporal_device", "rt_temporal",
+    "rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion",
     "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
     "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
 ]
@@ -253,6 +262,13 @@ def lib():
         _lib.rt_temporal_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
         _lib.rt_temporal.argtypes = [vp, vp, vp, vp]
         for name in ("rt_history_create", "rt_history_reset", "rt_temporal_device", "rt_temporal"):
+            getattr(_lib, name).restype = C.c_int
+        # motion vectors (rt_mi355x.h: "motion vectors")
+        _lib.rt_motion_device.argtypes = [C.c_int, vp, vp, vp, vp, vp, i32, vp, C.c_int]
+        _lib.rt_motion.argtypes = [C.c_int, vp, vp, vp, vp, i32, vp]
+        _lib.rt_temporal_motion_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int]
+        _lib.rt_temporal_motion.argtypes = [vp, vp, vp, vp, vp]
+        for name in ("rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion"):
             getattr(_lib, name).restype = C.c_int
         # exposure and tone mapping (rt_mi355x.h: "exposure and tone mapping")
         _lib.rt_exposure_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -485,13 +501,55 @@ def temporal_params(**kw):
     return p
 
 
+def _motion_nodes(nodes, prev_nodes):
+    nodes = _c(nodes, NODE)
+    prev = _c(prev_nodes, NODE) if prev_nodes is not None else None
+    if prev is not None and len(prev) != len(nodes):
+        raise ValueError(f"prev_nodes holds {len(prev)} nodes, nodes {len(nodes)}")
+    return nodes, prev
+
+
+def motion(cam, prev_cam, nodes, prev_nodes, z, object_id, device=0):
+    """rt_motion on host arrays: where each pixel's surface point was in the previous frame's image (rt_mi355x.h, "motion
+    vectors").  nodes / prev_nodes: NODE arrays of this frame and the previous one (prev_nodes=None: nothing moved); z float32
+    (H, W) and object_id int32 (H, W) of the new frame.  Returns float32 (H, W, 3): fx, fy, z_exp (z_exp <= 0: no previous
+    position)."""
+    nodes, prev = _motion_nodes(nodes, prev_nodes)
+    z, ids = _c(z, np.float32), _c(object_id, np.int32)
+    h, w = cam.height, cam.width
+    assert z.shape == ids.shape == (h, w)
+    out = np.empty((h, w, 3), np.float32)
+    pl = MotionPlanes(z=z.ctypes.data, object_id=ids.ctypes.data, motion=out.ctypes.data)
+    _check(lib().rt_motion(int(device), C.byref(cam), C.byref(prev_cam), _p(nodes), _p(prev) if prev is not None else None, len(nodes), C.byref(pl)))
+    return out
+
+
+def motion_device(device, stream, cam, prev_cam, nodes, prev_nodes, *, z_ptr, object_id_ptr, motion_ptr, sync=True):
+    """rt_motion_device: the same on image-sized DEVICE planes, enqueued on `stream` (an explicit stream's handle; None = the
+    null stream of the device).  nodes / prev_nodes stay host arrays; they are consumed before the call returns."""
+    nodes, prev = _motion_nodes(nodes, prev_nodes)
+    pl = MotionPlanes(z=z_ptr, object_id=object_id_ptr, motion=motion_ptr)
+    _check(lib().rt_motion_device(int(device), _stream_handle(stream), C.byref(cam), C.byref(prev_cam), _p(nodes),
+                                  _p(prev) if prev is not None else None, len(nodes), C.byref(pl), 1 if sync else 0))
+
+
+def _copy_camera(cam):
+    c = Camera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(Camera))
+    return c
+
+
 class History:
     """rt_history: the accumulated frames of one W x H stream on one device (the definition: rt_mi355x.h, "temporal
-    accumulation").  Every accumulate blends a new frame of a STATIC scene into what the earlier ones left, reprojected from the
-    camera of the previous call into `cam`.  A context manager; close() (or the end of the with block) frees the device planes."""
+    accumulation").  Every accumulate blends a new frame into what the earlier ones left, reprojected from the camera of the
+    previous call into `cam` (a STATIC scene) -- or, with a motion plane (motion() / motion_device()), from where that plane says
+    each pixel was (moving nodes).  A context manager; close() (or the end of the with block) frees the device planes."""
 
     def __init__(self, device, w, h):
         self._h = C.c_void_p()
+        # Scene.render_temporal(moving=True): (camera, nodes) of the frame the history holds -- set by that method alone; any
+        # other accumulate puts a frame into the history whose nodes are not known here, and forgets it
+        self._moving = None
         self.device, self.width, self.height = int(device), int(w), int(h)
         _check(lib().rt_history_create(self.device, self.width, self.height, C.byref(self._h)))
 
@@ -515,17 +573,20 @@ class History:
     def reset(self):
         """the next frame starts from nothing"""
         _check(lib().rt_history_reset(self._h))
+        self._moving = None
 
     @property
     def frames(self):
         """frames accumulated since the creation or the last reset()"""
         return int(lib().rt_history_frames(self._h))
 
-    def accumulate(self, cam, linear, normal, albedo, z, object_id=None, variance=None, rgb8=False, return_history=False, **params):
+    def accumulate(self, cam, linear, normal, albedo, z, object_id=None, variance=None, rgb8=False, return_history=False, motion=None, **params):
         """rt_temporal on host arrays: float32 (H, W, 3) linear / normal / albedo, float32 (H, W) z, optionally int32 (H, W)
         object_id and float32 (H, W, 3) variance.  Returns the accumulated float32 (H, W, 3) colour, followed -- as a tuple --
         by the accumulated variance (when `variance` is given), the gamma-encoded uint8 image (rgb8=True) and the per-pixel
-        history length, float32 (H, W) (return_history=True).  params: temporal_params()."""
+        history length, float32 (H, W) (return_history=True).  params: temporal_params().
+        motion: float32 (H, W, 3), this frame's motion plane (motion()) -- rt_temporal_motion takes the reprojection from it."""
+        self._moving = None
         linear, normal, albedo = (_c(a, np.float32) for a in (linear, normal, albedo))
         h, w = self.height, self.width
         z = _c(z, np.float32)
@@ -541,20 +602,30 @@ class History:
         pl = TemporalPlanes(rgb_linear=ptr(linear), normal=ptr(normal), albedo=ptr(albedo), z=ptr(z), object_id=ptr(ids), variance=ptr(var),
                             out_linear=ptr(out), out_variance=ptr(out_var), out_history=ptr(hist), out_rgb8=ptr(out8))
         p = temporal_params(**params)
-        _check(lib().rt_temporal(self._h, C.byref(cam), C.byref(p), C.byref(pl)))
+        if motion is not None:
+            motion = _c(motion, np.float32)
+            assert motion.shape == (h, w, 3)
+            _check(lib().rt_temporal_motion(self._h, C.byref(cam), C.byref(p), C.byref(pl), motion.ctypes.data))
+        else:
+            _check(lib().rt_temporal(self._h, C.byref(cam), C.byref(p), C.byref(pl)))
         res = (out,) + tuple(a for a in (out_var, out8, hist) if a is not None)
         return res if len(res) > 1 else out
 
     def accumulate_device(self, stream, cam, *, linear_ptr, normal_ptr, albedo_ptr, z_ptr, out_ptr, object_id_ptr=None, variance_ptr=None,
-                          out_variance_ptr=None, history_ptr=None, rgb8_ptr=None, sync=True, **params):
+                          out_variance_ptr=None, history_ptr=None, rgb8_ptr=None, sync=True, motion_ptr=None, **params):
         """rt_temporal_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
         explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr and out_variance_ptr may be
-        variance_ptr (in place)."""
+        variance_ptr (in place).  motion_ptr: this frame's motion plane on the device (rt_temporal_motion_device)."""
+        self._moving = None
         pl = TemporalPlanes(rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, z=z_ptr, object_id=object_id_ptr,
                             variance=variance_ptr, out_linear=out_ptr, out_variance=out_variance_ptr, out_history=history_ptr,
                             out_rgb8=rgb8_ptr)
         p = temporal_params(**params)
-        _check(lib().rt_temporal_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl), 1 if sync else 0))
+        if motion_ptr is not None:
+            _check(lib().rt_temporal_motion_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl),
+                                                   C.c_void_p(motion_ptr), 1 if sync else 0))
+        else:
+            _check(lib().rt_temporal_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
 def tonemap_params(operator="aces", **kw):
@@ -839,6 +910,12 @@ class Scene:
         _check(lib().rt_scene_counts(self._h, *[C.byref(x) for x in n], C.byref(nph)))
         return dict(nodes=n[0].value, meshes=n[1].value, materials=n[2].value, lights=n[3].value, photons=nph.value)
 
+    def get_nodes(self):
+        """the scene's node array (NODE records), as rt_scene_set_nodes took it"""
+        nodes = np.zeros(self.counts()["nodes"], NODE)
+        _check(lib().rt_scene_get_nodes(self._h, _p(nodes), len(nodes)))
+        return nodes
+
     def export(self):
         """All host-side arrays (for handing the same bytes to another consumer)."""
         c = self.counts()
@@ -965,7 +1042,7 @@ class Scene:
             out["display_rgb"] = exposure.tonemap(out["denoised"], out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
-    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, **kw):
+    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
@@ -974,7 +1051,15 @@ class Scene:
         sigma_depth (both).  gamma is the render's.
         exposure: an Exposure on `device` -- the final linear plane (the denoised one, or the accumulated one when
         denoise=False) is metered with the frame's object_id and tone-mapped, "display_rgb" (uint8 (H, W, 3)) added; tonemap_kw:
-        a dict of Exposure.tonemap's keywords (operator, key, adapt_up, ...)."""
+        a dict of Exposure.tonemap's keywords (operator, key, adapt_up, ...).
+        moving=True: nodes may have moved since the previous frame (set_nodes).  `history` remembers the camera and the node
+        array of the frame it last accumulated through this method; the motion plane from there to this frame is computed on
+        the device (motion()) from the scene's current nodes and the accumulation takes its reprojection from it;
+        "motion" (float32 (H, W, 3)) is added.  The first frame (and the first after history.reset()) has nothing to compare
+        with: prev_nodes=None and prev_cam = cam.  A frame that reaches `history` any other way -- render_temporal without
+        moving=True, accumulate(), accumulate_device() -- makes it forget the remembered frame: the next moving=True frame then
+        takes the nodes as not moved since, and the camera from the history as rt_temporal does (prev_cam cannot be known here,
+        so that frame is accumulated WITHOUT a motion plane; "motion" is still added, computed with prev_cam = cam)."""
         photon_pass = kw.pop("photon_pass", False)
         t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
         d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
@@ -982,9 +1067,15 @@ class Scene:
         if unknown:
             raise TypeError(f"no render_temporal parameter {sorted(unknown)[0]!r}")
         out = self.render_outputs(cam, params, planes=("linear",) + FEATURE_PLANES + ("variance",), device=device, photon_pass=photon_pass)
+        if moving:
+            out["motion"], known, remember = self._motion_since(history, cam, out["z"], out["object_id"], device)
+            if known:
+                t_kw["motion"] = out["motion"]
         out["accumulated"], out["accumulated_variance"], out["history"] = history.accumulate(
             cam, out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], variance=out["variance"],
             return_history=True, gamma=params.gamma, **t_kw)
+        if moving:
+            history._moving = remember                  # (accumulate() forgot it: only this method knows the frame's nodes)
         if denoise:
             out["denoised"], out["denoised_rgb"] = _denoise(
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
@@ -993,6 +1084,17 @@ class Scene:
             out["display_rgb"] = exposure.tonemap(out["denoised" if denoise else "accumulated"], out["object_id"],
                                                   **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
+
+    def _motion_since(self, history, cam, z, object_id, device):
+        """render_temporal(moving=True): (the motion plane from the frame `history` remembers to this one, computed on the
+        device; whether the frame the history holds is the remembered one, so that the plane may replace the reprojection; what
+        to remember of this frame)"""
+        nodes = self.get_nodes()
+        first = history.frames == 0
+        known = first or (history._moving is not None and len(history._moving[1]) == len(nodes))
+        prev_cam, prev_nodes = history._moving if known and not first else (cam, None)
+        plane = motion(cam, prev_cam, nodes, prev_nodes, z, object_id, device=device)
+        return plane, known, (_copy_camera(cam), nodes)
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,
                                     want_stats=True, linear_ptr=None, normal_ptr=None, albedo_ptr=None, alpha_ptr=None,

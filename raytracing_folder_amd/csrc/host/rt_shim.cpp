@@ -16,7 +16,7 @@ void RenderImage::Init(int w, int h)
     if (featuresEnabled) { featuresEnabled = false; EnableFeatures(); }
     if (varianceEnabled) variance.assign((size_t)w * h * 3, 0.0f);
     denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
-    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear();
+    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear(); motion.clear();
     rt_history_destroy(history);        // a history is of one size
     history = nullptr;
     display.clear(); displayImg.clear();
@@ -59,10 +59,33 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
 void RenderImage::ResetTemporal()
 {
     if (history) rt_history_reset(history);
-    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear();
+    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear(); motion.clear();
+}
+
+static rt_camera LowerCamera(const Camera &c)       // as Lower() hands the camera to the render
+{
+    rt_camera rc;
+    rc.pos[0] = c.pos.x; rc.pos[1] = c.pos.y; rc.pos[2] = c.pos.z;
+    rc.dir[0] = c.dir.x; rc.dir[1] = c.dir.y; rc.dir[2] = c.dir.z;
+    rc.up[0] = c.up.x; rc.up[1] = c.up.y; rc.up[2] = c.up.z;
+    rc.fov = c.fov; rc.focaldist = c.focaldist; rc.dof = c.dof; rc.width = c.imgWidth; rc.height = c.imgHeight;
+    return rc;
 }
 
 bool RenderImage::AccumulateTemporal(const Camera &c, const rt_temporal_params *params, int device)
+{
+    return Accumulate(c, nullptr, nullptr, nullptr, 0, params, device);
+}
+
+bool RenderImage::AccumulateTemporalMoving(const Camera &c, const Camera &prev, const rt_node *nodes, const rt_node *prevNodes, int n,
+                                           const rt_temporal_params *params, int device)
+{
+    return Accumulate(c, &prev, nodes, prevNodes, n, params, device);
+}
+
+// prev == NULL: rt_temporal; otherwise rt_motion of this frame first, then rt_temporal_motion with its plane
+bool RenderImage::Accumulate(const Camera &c, const Camera *prev, const rt_node *nodes, const rt_node *prevNodes, int nNodes,
+                             const rt_temporal_params *params, int device)
 {
     if (!temporalEnabled || !linearEnabled || !featuresEnabled) {
         temporalError = "AccumulateTemporal() needs EnableTemporal(), EnableLinear() and EnableFeatures() before the render";
@@ -72,11 +95,7 @@ bool RenderImage::AccumulateTemporal(const Camera &c, const rt_temporal_params *
     if (history && historyDevice != device) { rt_history_destroy(history); history = nullptr; }
     if (!history && rt_history_create(device, width, height, &history) != RT_OK) { temporalError = rt_last_error(); return false; }
     historyDevice = device;
-    rt_camera rc;                       // as Lower() hands the camera to the render
-    rc.pos[0] = c.pos.x; rc.pos[1] = c.pos.y; rc.pos[2] = c.pos.z;
-    rc.dir[0] = c.dir.x; rc.dir[1] = c.dir.y; rc.dir[2] = c.dir.z;
-    rc.up[0] = c.up.x; rc.up[1] = c.up.y; rc.up[2] = c.up.z;
-    rc.fov = c.fov; rc.focaldist = c.focaldist; rc.dof = c.dof; rc.width = c.imgWidth; rc.height = c.imgHeight;
+    const rt_camera rc = LowerCamera(c);
     rt_temporal_params defaults;
     rt_temporal_default_params(&defaults);
     const size_t n = (size_t)width * height;
@@ -84,7 +103,17 @@ bool RenderImage::AccumulateTemporal(const Camera &c, const rt_temporal_params *
     const rt_temporal_planes pl = {(uint32_t)sizeof(rt_temporal_planes), linear.data(), normals.data(), albedo.data(), zbuffer.data(),
                                    objectIds.data(), varianceEnabled ? variance.data() : nullptr, out.data(),
                                    varianceEnabled ? outVar.data() : nullptr, len.data(), nullptr};
-    if (rt_temporal(history, &rc, params ? params : &defaults, &pl) != RT_OK) { temporalError = rt_last_error(); return false; }
+    if (prev) {
+        const rt_camera prc = LowerCamera(*prev);
+        std::vector<float> mv(n * 3);
+        const rt_motion_planes mp = {(uint32_t)sizeof(rt_motion_planes), zbuffer.data(), objectIds.data(), mv.data()};
+        if (rt_motion(device, &rc, &prc, nodes, prevNodes, nNodes, &mp) != RT_OK ||
+            rt_temporal_motion(history, &rc, params ? params : &defaults, &pl, mv.data()) != RT_OK) { temporalError = rt_last_error(); return false; }
+        motion.swap(mv);
+    } else {
+        if (rt_temporal(history, &rc, params ? params : &defaults, &pl) != RT_OK) { temporalError = rt_last_error(); return false; }
+        motion.clear();
+    }
     accumulated.swap(out); accumulatedVariance.swap(outVar); historyLength.swap(len);
     temporalError.clear();
     return true;

@@ -37,6 +37,7 @@ class RenderImage {
     // opt-in (EnableTemporal): the frames accumulated by AccumulateTemporal() -- linear float RGB, its variance (with
     // EnableVariance) and the per-pixel history length -- and the rt_history that holds them on the device
     std::vector<float> accumulated, accumulatedVariance, historyLength;
+    std::vector<float> motion;         // AccumulateTemporalMoving(): the frame's motion plane, (fx, fy, z_exp) per pixel
     bool temporalEnabled = false;
     rt_history *history = nullptr;
     int historyDevice = 0;
@@ -52,6 +53,8 @@ class RenderImage {
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
+    bool Accumulate(const Camera &camera, const Camera *prev, const rt_node *nodes, const rt_node *prevNodes, int nNodes,
+                    const rt_temporal_params *params, int device);
 public:
     RenderImage() = default;
     RenderImage(const RenderImage &) = delete;
@@ -113,6 +116,13 @@ public:
     void EnableTemporal() { temporalEnabled = true; }
     bool TemporalEnabled() const { return temporalEnabled; }
     bool AccumulateTemporal(const Camera &camera, const rt_temporal_params *params = nullptr, int device = 0);
+    // The same for a scene whose NODES may have moved since the previous frame (rt_mi355x.h, "motion vectors"): rt_motion from
+    // the frame's z and object ids, the two cameras and the two lowered node arrays (rt::Lower's SceneData::nodes, n each;
+    // prevNodes == NULL: nothing moved -- the first frame, with prevCamera = camera), then rt_temporal_motion with that plane.
+    // The plane is kept next to the others: GetMotion(), (fx, fy, z_exp) per pixel, NULL until a call has succeeded.
+    bool AccumulateTemporalMoving(const Camera &camera, const Camera &prevCamera, const rt_node *nodes, const rt_node *prevNodes, int n,
+                                  const rt_temporal_params *params = nullptr, int device = 0);
+    float *GetMotion() { return motion.empty() ? nullptr : motion.data(); }
     void ResetTemporal();
     int TemporalFrames() const { return rt_history_frames(history); }
     const std::string &TemporalError() const { return temporalError; }

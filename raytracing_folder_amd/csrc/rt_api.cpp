@@ -352,6 +352,7 @@ struct rt_job {
 // ---- scene store ---------------------------------------------------------------------------------------
 static std::atomic<int> g_live_scenes{0};
 static void denoise_release_all();         // the denoiser's per-device scratch (below, "denoising")
+static void motion_release_all();          // the per-device node tables of rt_motion (below, "motion vectors")
 extern "C" rt_status rt_scene_create(rt_scene **out)
 {
     if (!out) return fail(RT_ERR_ARG, "rt_scene_create: out is NULL");
@@ -371,7 +372,7 @@ extern "C" void rt_scene_destroy(rt_scene *s)
         delete d;
     }
     delete s;
-    if (g_live_scenes.fetch_sub(1) == 1) denoise_release_all();     // the last scene takes the denoiser's per-device scratch with it
+    if (g_live_scenes.fetch_sub(1) == 1) { denoise_release_all(); motion_release_all(); }   // the last scene takes the per-device image-space scratch with it
 }
 
 static rt_status check_idle(rt_scene *s, const char *who)
@@ -2445,7 +2446,9 @@ static rt_status temporal_check(const char *name, const rt_history *hst, const r
     return RT_OK;
 }
 
-static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync)
+// motion: NULL (reproject with the two cameras), or the device plane of rt_motion_device for this frame
+static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync,
+                                    const float *motion = nullptr)
 {
     HIP_TRY(hipSetDevice(hst->device));
     std::lock_guard<std::mutex> lk(hst->mu);
@@ -2462,6 +2465,7 @@ static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_ca
     float4 *set0 = (float4 *)hst->sets.p;
     const int next = hst->cur ^ 1;
     R.prev = set0 + (size_t)hst->cur * 3 * n; R.next = set0 + (size_t)next * 3 * n;
+    R.motion = motion;
     rtk_launch_temporal(st, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(hst->done, st));
@@ -2479,27 +2483,206 @@ extern "C" rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const
     return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync);
 }
 
-extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes)
+// the host entry points: upload, accumulate, download.  motion: NULL (rt_temporal), or this frame's plane on the host
+static rt_status temporal_host(const char *name, rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
+                               const float *motion)
 {
-    rt_status st = temporal_check("rt_temporal", hst, cam, p, host_planes);
+    rt_status st = temporal_check(name, hst, cam, p, host_planes);
     if (st) return st;
     HIP_TRY(hipSetDevice(hst->device));
     const size_t n = (size_t)hst->w * (size_t)hst->h;
-    ScopedDevBuf rgb, normal, albedo, z, id, var, hist, rgb8;       // the results are written in place into rgb and var
+    ScopedDevBuf rgb, normal, albedo, z, id, var, hist, rgb8, mv;   // the results are written in place into rgb and var
     if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
         (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4))) return st;
     if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
     if (host_planes->variance && (st = var.upload(host_planes->variance, n * 12))) return st;
+    if (motion && (st = mv.upload(motion, n * 12))) return st;
     if (host_planes->out_history && (st = hist.ensure(n * 4))) return st;
     if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
     const rt_temporal_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
                                     (const int32_t *)id.p, (const float *)var.p, (float *)rgb.p,
                                     host_planes->out_variance ? (float *)var.p : nullptr, (float *)hist.p, (uint8_t *)rgb8.p};
-    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1))) return st;
+    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1, (const float *)mv.p))) return st;
     HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
     if (host_planes->out_variance) HIP_TRY(hipMemcpy(host_planes->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
     if (host_planes->out_history) HIP_TRY(hipMemcpy(host_planes->out_history, hist.p, n * 4, hipMemcpyDeviceToHost));
     if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes)
+{
+    return temporal_host("rt_temporal", hst, cam, p, host_planes, nullptr);
+}
+
+extern "C" rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                               const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
+{
+    if (!motion_dev) return fail(RT_ERR_ARG, "rt_temporal_motion_device: the motion plane is NULL");
+    rt_status st = temporal_check("rt_temporal_motion_device", hst, cam, p, device_planes);
+    if (st) return st;
+    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev);
+}
+
+extern "C" rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
+                                        const float *motion)
+{
+    if (!motion) return fail(RT_ERR_ARG, "rt_temporal_motion: the motion plane is NULL");
+    return temporal_host("rt_temporal_motion", hst, cam, p, host_planes, motion);
+}
+
+// ---- motion vectors ---------------------------------------------------------------------------------------------------------
+// One affine map in double, X -> r X + t (r row-major), and the two steps the node chains are made of.
+namespace {
+struct Affine64 {
+    double r[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+    // this, then M X + c (M column-major float[9], like rt_node's)
+    Affine64 then(const float *M, const double c[3]) const
+    {
+        Affine64 o;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.r[3 * i + j] = (double)M[i] * r[j] + (double)M[3 + i] * r[3 + j] + (double)M[6 + i] * r[6 + j];
+            o.t[i] = (double)M[i] * t[0] + (double)M[3 + i] * t[1] + (double)M[6 + i] * t[2] + c[i];
+        }
+        return o;
+    }
+    // this, then A
+    Affine64 then(const Affine64 &A) const
+    {
+        Affine64 o;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.r[3 * i + j] = A.r[3 * i] * r[j] + A.r[3 * i + 1] * r[3 + j] + A.r[3 * i + 2] * r[6 + j];
+            o.t[i] = A.r[3 * i] * t[0] + A.r[3 * i + 1] * t[1] + A.r[3 * i + 2] * t[2] + A.t[i];
+        }
+        return o;
+    }
+};
+}
+
+// The table of rt_motion: per node i the map A_i of this frame's world into the previous frame's -- TransformTo down the chain
+// root .. i of `nodes` (per node itm (X - pos)), then TransformFrom up the chain i .. root of `prev` (per node tm X + pos) --
+// composed in double and rounded to float once.  A node whose chain is bit-identical in both arrays (and every node when prev
+// is NULL) gets exactly the identity.  The parents were validated by the caller.
+static void motion_table(const rt_node *nodes, const rt_node *prev, int32_t n, std::vector<DevNodeMotion> &table)
+{
+    table.resize((size_t)n);
+    std::vector<Affine64> to, from;     // world -> node i down the current chain; node i -> world up the previous chain
+    std::vector<char> same((size_t)n, 1);
+    if (prev) { to.resize((size_t)n); from.resize((size_t)n); }
+    for (int32_t i = 0; i < n; i++) {
+        Affine64 A;
+        if (prev) {
+            const rt_node &c = nodes[i], &o = prev[i];
+            same[i] = c.parent == o.parent && !memcmp(c.tm, o.tm, 36) && !memcmp(c.itm, o.itm, 36) && !memcmp(c.pos, o.pos, 12) &&
+                      (c.parent < 0 || same[c.parent]);
+            double mp[3];               // itm (X - pos) = itm X - itm pos
+            for (int k = 0; k < 3; k++) mp[k] = -((double)c.itm[k] * c.pos[0] + (double)c.itm[3 + k] * c.pos[1] + (double)c.itm[6 + k] * c.pos[2]);
+            to[i] = (c.parent < 0 ? Affine64() : to[c.parent]).then(c.itm, mp);
+            const double op[3] = {o.pos[0], o.pos[1], o.pos[2]};
+            const Affine64 up = Affine64().then(o.tm, op);
+            from[i] = o.parent < 0 ? up : up.then(from[o.parent]);
+            if (!same[i]) A = to[i].then(from[i]);
+        }
+        for (int k = 0; k < 3; k++) table[i].row[k] = make_float4((float)A.r[3 * k], (float)A.r[3 * k + 1], (float)A.r[3 * k + 2], (float)A.t[k]);
+    }
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status motion_check(const char *name, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
+                              int32_t n_nodes, const rt_motion_planes *pl)
+{
+    if (!cam || !prev_cam || !nodes || !pl) return fail(RT_ERR_ARG, "%s: camera, prev_cam, nodes or planes is NULL", name);
+    if (pl->struct_size != (uint32_t)sizeof(rt_motion_planes))
+        return fail(RT_ERR_ARG, "%s: rt_motion_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_motion_planes));
+    if (!pl->z || !pl->object_id || !pl->motion) return fail(RT_ERR_ARG, "%s: z, object_id and motion are required", name);
+    if (n_nodes <= 0) return fail(RT_ERR_ARG, "%s: n_nodes is %d", name, n_nodes);
+    for (const rt_node *arr : {nodes, prev_nodes})
+        for (int32_t i = 0; arr && i < n_nodes; i++)
+            if (arr[i].parent < -1 || arr[i].parent >= i)
+                return fail(RT_ERR_ARG, "%s: node %d of %s has parent %d (a parent must precede its child; -1: none)", name, i,
+                            arr == nodes ? "nodes" : "prev_nodes", arr[i].parent);
+    if (cam->width <= 0 || cam->height <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, cam->width, cam->height);
+    if (cam->width != prev_cam->width || cam->height != prev_cam->height)
+        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the previous one %d x %d", name, cam->width, cam->height, prev_cam->width, prev_cam->height);
+    if ((long long)cam->width * cam->height > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, cam->width, cam->height);
+    return RT_OK;
+}
+
+// The node table of the last rt_motion call per device: kept between calls (a frame's table is uploaded only when it differs
+// from the one the device holds).  Every call on the device shares it, so -- like the denoiser's scratch -- every call orders its
+// stream behind the previous call's `done` event, whatever that call's stream was and whether or not the table changes: `done`
+// then stands for ALL earlier calls, and waiting for it on the host before an overwrite leaves no kernel that still reads the
+// table.  Released with the last scene (rt_scene_destroy), like the denoiser's scratch.
+struct MotionDevice { DevBuf table; std::vector<DevNodeMotion> held; hipEvent_t done = nullptr; bool pending = false; };
+static std::mutex g_motion_mu;
+static std::vector<std::pair<int, MotionDevice>> g_motion;          // (device, its table); under g_motion_mu
+
+static void motion_release_all()
+{
+    std::lock_guard<std::mutex> lk(g_motion_mu);
+    for (auto &d : g_motion) {
+        if (hipSetDevice(d.first) != hipSuccess) continue;
+        d.second.table.release();                                   // hipFree waits for the kernels that still use it
+        if (d.second.done) (void)hipEventDestroy(d.second.done);
+    }
+    g_motion.clear();
+}
+
+static rt_status motion_on_device(const char *name, int device, hipStream_t st, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
+                                  const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *pl, int sync)
+{
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+    HIP_TRY(hipSetDevice(device));
+    std::vector<DevNodeMotion> table;
+    motion_table(nodes, prev_nodes, n_nodes, table);
+    std::lock_guard<std::mutex> lk(g_motion_mu);
+    MotionDevice *D = nullptr;
+    for (auto &d : g_motion) if (d.first == device) D = &d.second;
+    if (!D) { g_motion.emplace_back(device, MotionDevice()); D = &g_motion.back().second; }
+    if (!D->done) HIP_TRY(hipEventCreateWithFlags(&D->done, hipEventDisableTiming));
+    const size_t bytes = table.size() * sizeof(DevNodeMotion);
+    if (D->pending) HIP_TRY(hipStreamWaitEvent(st, D->done, 0));
+    if (D->held.size() != table.size() || memcmp(D->held.data(), table.data(), bytes) != 0) {
+        if (D->pending) { HIP_TRY(hipEventSynchronize(D->done)); D->pending = false; }
+        D->held.clear();
+        rt_status rs = D->table.upload(table.data(), bytes);
+        if (rs) return rs;
+        D->held = table;
+    }
+    MotionRequest R = {};
+    R.width = cam->width; R.height = cam->height; R.n_nodes = n_nodes;
+    camera_setup(*cam, R.cur);
+    camera_setup(*prev_cam, R.old);
+    R.z = pl->z; R.object_id = pl->object_id; R.table = (const DevNodeMotion *)D->table.p; R.motion = pl->motion;
+    rtk_launch_motion(st, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(D->done, st));
+    D->pending = true;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); D->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_motion_device(int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
+                                      const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *device_planes, int sync)
+{
+    rt_status st = motion_check("rt_motion_device", cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes);
+    if (st) return st;
+    return motion_on_device("rt_motion_device", device, (hipStream_t)hip_stream, cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes, sync);
+}
+
+extern "C" rt_status rt_motion(int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
+                               int32_t n_nodes, const rt_motion_planes *host_planes)
+{
+    rt_status st = motion_check("rt_motion", cam, prev_cam, nodes, prev_nodes, n_nodes, host_planes);
+    if (st) return st;
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_motion: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)cam->width * (size_t)cam->height;
+    ScopedDevBuf z, id, mv;
+    if ((st = z.upload(host_planes->z, n * 4)) || (st = id.upload(host_planes->object_id, n * 4)) || (st = mv.ensure(n * 12))) return st;
+    const rt_motion_planes dev = {(uint32_t)sizeof dev, (const float *)z.p, (const int32_t *)id.p, (float *)mv.p};
+    if ((st = motion_on_device("rt_motion", device, nullptr, cam, prev_cam, nodes, prev_nodes, n_nodes, &dev, 1))) return st;
+    HIP_TRY(hipMemcpy(host_planes->motion, mv.p, n * 12, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_tonemap.hip): every rtk_* function, the requests they take and the records they
-// exchange.  All seven files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip): every rtk_* function, the requests they take and the
+// records they exchange.  All eight files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -103,6 +103,8 @@ struct DenoiseRequest {
 // are camera_setup's quantities of this frame's camera and of the one the history holds; has_history is false for the first
 // frame after a create or a reset, and `prev` is then not read.  prev / next: the two sets of a history, each three planes of
 // width * height float4 (colour, variance, guide: RT_TEMPORAL_HISTORY_PER_PIXEL bytes a pixel for both sets together).
+// motion: NULL, or the device plane of a MotionRequest -- k_temporal<true> then takes each pixel's previous position and expected
+// depth from it and `cur` / `old` are not used by the kernel.
 #define RT_TEMPORAL_HISTORY_PER_PIXEL 96
 struct TemporalRequest {
     int width, height; bool has_history;
@@ -111,6 +113,20 @@ struct TemporalRequest {
     const float *rgb_linear, *normal, *albedo, *z; const int32_t *object_id; const float *variance;
     float *out_linear, *out_variance, *out_history; uint8_t *out_rgb8;
     const float4 *prev; float4 *next;
+    const float *motion;
+};
+
+// One motion plane of a width x height frame (rt_motion.hip; the definition: rt_mi355x.h, "motion vectors").  z, object_id and
+// motion are the caller's device planes.  `cur` and `old` are camera_setup's quantities of this frame's camera and the previous
+// frame's.  table: one DevNodeMotion per node on the device, this frame's world -> the previous frame's, P_prev = R P + t as three
+// 16-byte rows {R_k0, R_k1, R_k2, t_k} (48 bytes a node, three dwordx4 loads); composed on the host in double.
+struct DevNodeMotion { float4 row[3]; };
+struct MotionRequest {
+    int width, height, n_nodes;
+    DevCamera cur, old;
+    const float *z; const int32_t *object_id;
+    const DevNodeMotion *table;
+    float *motion;
 };
 
 // One tone-mapped width x height frame (rt_tonemap.hip; the definition: rt_mi355x.h, "exposure and tone mapping").  The planes are
@@ -170,6 +186,10 @@ void rtk_launch_denoise_frame(hipStream_t st, const DenoiseRequest &R);
 // ---- rt_temporal.hip: temporal accumulation with camera reprojection ---------------------------------------------------
 // k_temporal over the frame on `st`: reads the set `prev` (when has_history), writes the set `next` and the caller's planes
 void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R);
+
+// ---- rt_motion.hip: motion vectors in image space ------------------------------------------------------------------------
+// k_motion over the frame on `st`: reads z, object_id and the node table, writes the motion plane
+void rtk_launch_motion(hipStream_t st, const MotionRequest &R);
 
 // ---- rt_tonemap.hip: exposure and tone mapping ---------------------------------------------------------------------------
 // on `st`: k_luminance_hist and k_exposure_meter (when R.meter), then k_tonemap<R.op>

@@ -1,12 +1,14 @@
 // rt_temporal.hip -- temporal accumulation with camera reprojection: the frame-to-frame stage in front of the denoiser.  The
 // definition the kernel follows step by step is in include/rt_mi355x.h ("temporal accumulation"); the reference has no
 // counterpart.  Like the denoiser it is an image-space operation on image-sized planes and knows nothing of scenes: the scene is
-// taken to be static between two frames, only the camera moves.
+// taken to be static between two frames, only the camera moves -- unless the caller hands in a motion plane (k_motion,
+// rt_motion.hip), which then says where each pixel was instead of the two cameras.
 //
 //   k_temporal   one lane per pixel, 32 x 8 pixels per workgroup (the render's tile, as k_atrous): validity and demodulation of
 //                the lane's own pixel, its world point from z and the current camera, that point's position in the STORED
 //                camera's image, four bilinear taps into the previous history set, the blend, the caller's planes and the
-//                lane's three records of the next history set
+//                lane's three records of the next history set.  k_temporal<true> reads that position and the expected depth
+//                from the motion plane instead (rt_mi355x.h, "motion vectors"); everything else is the same code.
 //
 // The history is two ping-pong sets of three float4 planes (96 bytes a pixel in all): colour {d.r, d.g, d.b, z}, variance
 // {u.r, u.g, u.b, N} and guide {n.x, n.y, n.z, id}.  A lane gathers from arbitrary pixels of the previous set while every lane
@@ -20,6 +22,7 @@
 
 #include "rt_kernel_util.h"
 #include "rt_launch.h"
+#include "rt_reproject.h"
 
 #define RT_TEMPORAL_TILE_W 32
 #define RT_TEMPORAL_TILE_H 8
@@ -36,6 +39,7 @@ struct TemporalArgs {
     const float *rgb, *normal, *albedo, *z; const int32_t *object_id; const float *variance;
     float *out_linear, *out_variance, *out_history; uint8_t *out_rgb8;
     const float4 *prev; float4 *next;   // a set: colour[n], variance[n], guide[n], n = width * height
+    const float *motion;                // k_temporal<true> only: (fx, fy, z_exp) per pixel
 };
 
 __device__ __forceinline__ float temporal_albedo(float a) { return a > RT_TEMPORAL_MIN_ALBEDO ? a : 1.0f; }
@@ -44,6 +48,8 @@ __device__ __forceinline__ float temporal_variance(float v) { return v > 0.0f &&
 // x - x is 0 for a finite x and NaN otherwise
 __device__ __forceinline__ bool temporal_finite3(float a, float b, float c) { return (a - a) + (b - b) + (c - c) == 0.0f; }
 
+// MOTION: steps 2-3 are replaced by the lane's own pixel of the motion plane
+template <bool MOTION>
 __global__ __launch_bounds__(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H) void k_temporal(TemporalArgs A)
 {
     const int tx = (int)(blockIdx.x % (unsigned)A.tiles_x), ty = (int)(blockIdx.x / (unsigned)A.tiles_x);
@@ -81,21 +87,18 @@ __global__ __launch_bounds__(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H) void k_tem
     float hr = 0, hg = 0, hb = 0, hur = 0, hug = 0, hub = 0, hn = 0, W = 0;     // sums over the accepted taps
     float n0 = 0;                       // the first accepted tap's length: the lengths are summed as differences to it
     if (A.has_history) {
-        // 2. the pixel's representative ray through s = (b.x + (x + 0.5) u, b.y + (y + 0.5) v, -l) and its world point
-        const float sx = A.cur.b[0] + ((float)x + 0.5f) * A.cur.u, sy = A.cur.b[1] + ((float)y + 0.5f) * A.cur.v, sz = A.cur.b[2];
-        const float *m = A.cur.m;
-        float rx = sx * m[0] + sy * m[3] + sz * m[6], ry = sx * m[1] + sy * m[4] + sz * m[7], rz = sx * m[2] + sy * m[5] + sz * m[8];
-        const float inv = 1.0f / sqrtf(rx * rx + ry * ry + rz * rz);
-        rx *= inv; ry *= inv; rz *= inv;
-        const float Px = A.cur.pos[0] + zp * rx, Py = A.cur.pos[1] + zp * ry, Pz = A.cur.pos[2] + zp * rz;
-        // 3. into the stored camera: q = (x_new', up', z_new') . (P - pos')
-        const float ex = Px - A.old.pos[0], ey = Py - A.old.pos[1], ez = Pz - A.old.pos[2];
-        const float *o = A.old.m;
-        const float qx = o[0] * ex + o[1] * ey + o[2] * ez, qy = o[3] * ex + o[4] * ey + o[5] * ez, qz = o[6] * ex + o[7] * ey + o[8] * ez;
-        if (qz < 0.0f) {
-            const float t = A.old.b[2] / qz;                // -l' / q.z
-            const float fx = (qx * t - A.old.b[0]) / A.old.u - 0.5f, fy = (qy * t - A.old.b[1]) / A.old.v - 0.5f;
-            const float zexp = sqrtf(ex * ex + ey * ey + ez * ez);
+        // 2.-3. the pixel's world point and its position in the stored camera's image (rt_reproject.h) -- or, with a motion
+        // plane, what k_motion left for this pixel: z_exp <= 0 or a value that is not finite means "no previous position"
+        Reprojected R;
+        bool found;
+        if (MOTION) {
+            R.fx = A.motion[3 * p]; R.fy = A.motion[3 * p + 1]; R.zexp = A.motion[3 * p + 2];
+            found = R.zexp > 0.0f && temporal_finite3(R.fx, R.fy, R.zexp);
+        } else {
+            found = reproject_pixel<false>(A.cur, A.old, x, y, zp, nullptr, R);
+        }
+        if (found) {
+            const float fx = R.fx, fy = R.fy, zexp = R.zexp;
             // outside (-1, width) x (-1, height) every tap lies outside the image or weighs 0; this also keeps the conversion
             // to int away from huge and NaN positions
             if (fx > -1.0f && fx < (float)A.width && fy > -1.0f && fy < (float)A.height) {
@@ -164,5 +167,7 @@ void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R)
     A.out_linear = R.out_linear; A.out_variance = R.out_variance; A.out_history = R.out_history; A.out_rgb8 = R.out_rgb8;
     A.prev = R.prev; A.next = R.next;
     const long long tiles = (long long)A.tiles_x * ((R.height + RT_TEMPORAL_TILE_H - 1) / RT_TEMPORAL_TILE_H);
-    hipLaunchKernelGGL(k_temporal, dim3((unsigned)tiles), dim3(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H), 0, st, A);
+    A.motion = R.motion;
+    if (R.motion) hipLaunchKernelGGL(k_temporal<true>, dim3((unsigned)tiles), dim3(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H), 0, st, A);
+    else hipLaunchKernelGGL(k_temporal<false>, dim3((unsigned)tiles), dim3(RT_TEMPORAL_TILE_W * RT_TEMPORAL_TILE_H), 0, st, A);
 }

@@ -1,0 +1,885 @@
+"""Motion vectors (rt_motion, rt_motion_device, k_motion) and temporal accumulation that follows them (rt_temporal_motion,
+rt_temporal_motion_device, k_temporal<MOTION>; capi.motion, History.accumulate(motion=), Scene.render_temporal(moving=True);
+rt::RenderImage::AccumulateTemporalMoving).  The reference has no counterpart, so the yardsticks are written here from the
+header's definition ("motion vectors") in float64: `ref_motion` applies the node chains node by node (no pre-composed matrix),
+`ref_temporal_motion` is test_temporal's `ref_temporal` with steps 2-3 replaced by the plane.  Both are checked on the CPU through
+properties that do not depend on the transcription.  The input is test_temporal's synthetic frame with the square (id 4) placed
+by a node transform: `frame_nodes`."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from raytracing_folder_amd import capi
+from tests import scenes
+from tests.test_temporal import (BG, BIG, F, MARGIN, MAX_LEFT_OUT, SIZES, SQUARE_HALF, SQUARE_NORMAL, SQUARE_Z, WALL_EDGE, _gate, _planes_for, _valid,
+                                 cam_a, cam_b, cam_c, cam_setup, delta_px, frame, light_affine, light_smooth, make_cam, pixel_rays, ref_temporal)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WALL, SQUARE, PARENT = 3, 4, 2          # node indices = the ids of test_temporal's frame; PARENT: the square's parent in the chain case
+
+
+# ---- nodes --------------------------------------------------------------------------------------------------------
+def rot_z(deg):
+    c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def set_node(nodes, i, tm=np.eye(3), pos=(0.0, 0.0, 0.0), parent=0):
+    """node i: X_parent = tm X + pos (rt_node's matrices are column-major: tm[3 c + r])"""
+    tm = np.asarray(tm, np.float64)
+    nodes[i]["tm"], nodes[i]["itm"] = tm.T.reshape(9), np.linalg.inv(tm).T.reshape(9)
+    nodes[i]["pos"], nodes[i]["parent"] = pos, parent
+    return nodes
+
+
+def make_nodes(n=5):
+    """n nodes under the root, all identity"""
+    nodes = np.zeros(n, capi.NODE)
+    for i in range(n):
+        set_node(nodes, i, parent=-1 if i == 0 else 0)
+    nodes["mesh"] = nodes["material"] = -1
+    return nodes
+
+
+def square_nodes(k, turn=0.0, step=(0.3, 0.1, 0.0), chain=False):
+    """frame k of the moving-square sequence: the square's node translated by k * step from (0, 0, SQUARE_Z) and turned by
+    k * turn degrees about z.  chain=True: the square stays where it is under PARENT, and PARENT makes the move"""
+    nodes = make_nodes()
+    pos = np.array([0.0, 0.0, SQUARE_Z]) + k * np.asarray(step)
+    if chain:
+        set_node(nodes, PARENT, rot_z(k * turn), pos - rot_z(k * turn) @ np.array([1.0, 0.5, SQUARE_Z - 1.0]))
+        set_node(nodes, SQUARE, pos=(1.0, 0.5, SQUARE_Z - 1.0), parent=PARENT)
+    else:
+        set_node(nodes, SQUARE, rot_z(k * turn), pos)
+    return nodes
+
+
+def chain_of(nodes, i):
+    out = []
+    while i >= 0:
+        out.append(i)
+        i = int(nodes[i]["parent"])
+    return out[::-1]                    # root .. i
+
+
+def to_object(nodes, i, X):
+    """TransformTo down the chain, node by node: itm (X - pos), float64 on the float32 records"""
+    for k in chain_of(nodes, i):
+        X = (X - nodes[k]["pos"].astype(np.float64)) @ nodes[k]["itm"].astype(np.float64).reshape(3, 3)       # (itm as rows)^T: column-major
+    return X
+
+
+def from_object(nodes, i, X):
+    """TransformFrom up the chain, node by node: tm X + pos"""
+    for k in chain_of(nodes, i)[::-1]:
+        X = X @ nodes[k]["tm"].astype(np.float64).reshape(3, 3) + nodes[k]["pos"].astype(np.float64)
+    return X
+
+
+# ---- the reference of the motion plane -------------------------------------------------------------------------
+def ref_motion(cam, prev_cam, nodes, prev_nodes, z, ids):
+    """float64 transcription of "motion vectors": (plane (H, W, 3), found (H, W), q.z (H, W) where the steps ran, else -inf)"""
+    cs, old = cam_setup(cam), cam_setup(prev_cam)
+    H, W = cs["H"], cs["W"]
+    Y, X = np.mgrid[0:H, 0:W]
+    out = np.stack([X, Y, np.zeros((H, W))], -1).astype(np.float64)
+    with np.errstate(all="ignore"):
+        ok = (ids >= 0) & (ids < len(nodes)) & np.isfinite(z) & (z < BIG)
+    P = cs["pos"] + np.where(ok, z.astype(np.float64), 1.0)[..., None] * pixel_rays(cs)
+    Pp = P.copy()
+    if prev_nodes is not None:
+        for i in np.unique(ids[ok]):
+            m = ok & (ids == i)
+            Pp[m] = from_object(prev_nodes, int(i), to_object(nodes, int(i), P[m]))
+    e = Pp - old["pos"]
+    q = e @ old["M"]
+    found = ok & (q[..., 2] < 0)
+    t = old["b"][2] / np.where(found, q[..., 2], -1.0)
+    fx, fy = (q[..., 0] * t - old["b"][0]) / old["u"] - 0.5, (q[..., 1] * t - old["b"][1]) / old["v"] - 0.5
+    res = np.stack([fx, fy, np.sqrt((e * e).sum(-1))], -1)
+    return np.where(found[..., None], res, out), found, np.where(ok, q[..., 2], -np.inf)
+
+
+def motion_px(cam, prev_cam, nodes, prev_nodes, ids_used, z_min):
+    """A bound on the float32 error of k_motion's position, |error of fx| + |error of fy| in pixels, from the operation chain
+    the way test_temporal.delta_px derives k_temporal's (every operation rounds once, relative error at most 2^-24):
+      steps 2-3 and the camera quantities, as counted in delta_px     32
+      P_prev = R P + t, one component: three products, three sums      6
+      the one rounding of the composed (R, t) to float                 1
+    39 in all.  The errors made before the subtraction P_prev - pos' are relative to |pos| + z, to |t| and to |pos'|, but count
+    relative to |e| ~ z afterwards -- z the smaller of the depth in this frame and the expected depth in the previous one --
+    hence the factor 1 + (|pos| + |pos'| + |t|) / z_min, |t| the largest translation among the maps of the nodes in use (the
+    test composes it itself, in float64, by sending the origin through the chains):
+      motion_px = 39 * 2^-24 * (W + H) * (1 + (|pos| + |pos'| + |t|) / z_min)"""
+    norm = lambda c: math.sqrt(sum(float(x) ** 2 for x in c.pos))
+    t = 0.0
+    if prev_nodes is not None:
+        for i in ids_used:
+            t = max(t, float(np.linalg.norm(from_object(prev_nodes, int(i), to_object(nodes, int(i), np.zeros(3))))))
+    return 39 * 2.0 ** -24 * (cam.width + cam.height) * (1 + (norm(cam) + norm(prev_cam) + t) / z_min)
+
+
+# ---- the synthetic frame with the square on a node -----------------------------------------------------------
+def frame_nodes(cam, nodes, seed, noise, light=light_smooth, dtype=np.float32):
+    """test_temporal.frame with the square placed by node SQUARE of `nodes`: in its object space the square is |x|, |y| <= 0.8
+    in the plane z = 0 with the normal SQUARE_NORMAL (turned with the node), and its light is evaluated at the OBJECT-space
+    point, so a point of the square keeps its clean colour wherever the node goes.  The wall (node WALL, never moved), the strip
+    beyond it, noise and variance are frame's.  With the square's node at (0, 0, SQUARE_Z) it is frame(), number for number."""
+    cs = cam_setup(cam)
+    d, o = pixel_rays(cs), cs["pos"]
+    down = d[..., 2] < 0
+    dz = np.where(down, d[..., 2], -1.0)
+    t_wall = (0.0 - o[2]) / dz
+    P_wall = o + t_wall[..., None] * d
+    o_obj = to_object(nodes, SQUARE, o[None, :])[0]
+    d_obj = to_object(nodes, SQUARE, (o + d).reshape(-1, 3)).reshape(d.shape) - o_obj
+    front = d_obj[..., 2] < 0
+    t_sq = -o_obj[2] / np.where(front, d_obj[..., 2], -1.0)
+    P_obj = o_obj + t_sq[..., None] * d_obj
+    hit_sq = front & (t_sq > 0) & (np.abs(P_obj[..., 0]) <= SQUARE_HALF) & (np.abs(P_obj[..., 1]) <= SQUARE_HALF)
+    hit_wall = down & (t_wall > 0) & (P_wall[..., 0] < WALL_EDGE) & ~hit_sq
+    hit = hit_sq | hit_wall
+    ids = np.where(hit_sq, SQUARE, np.where(hit_wall, WALL, -1)).astype(np.int32)
+    z = np.where(hit_sq, t_sq, np.where(hit_wall, t_wall, float(BIG)))
+    n_sq = from_object(nodes, SQUARE, np.array([SQUARE_NORMAL]))[0] - from_object(nodes, SQUARE, np.zeros((1, 3)))[0]
+    normal = np.where(hit_sq[..., None], n_sq, np.where(hit_wall[..., None], (0.0, 0.0, 1.0), (0.0, 0.0, 0.0)))
+    albedo = np.where((P_wall[..., 0] < 0)[..., None], (0.8, 0.5, 0.3), (0.2, 0.6, 0.9))
+    patch = hit_wall & (P_wall[..., 0] >= -3.0) & (P_wall[..., 0] <= -2.05) & (P_wall[..., 1] >= 1.0) & (P_wall[..., 1] <= 1.95)
+    albedo = np.where(patch[..., None], 0.0, albedo)
+    albedo = np.where(hit_sq[..., None], 0.7, albedo)
+    albedo = np.where(hit[..., None], albedo, 0.0)
+    # the square's light in its object frame, shifted so that the identity placement sees frame()'s world point
+    lit = np.where(hit_sq, light(P_obj + np.array([0.0, 0.0, SQUARE_Z])), light(P_wall))
+    clean = np.where(albedo > 1e-3, albedo, 1.0) * lit[..., None]
+    clean = np.where(hit[..., None], clean, BG)
+    rng = np.random.default_rng(seed)
+    lin = np.where(hit[..., None], clean * (1 + noise * rng.normal(0, 1, clean.shape)), clean)
+    var = np.where(hit[..., None], (noise * clean) ** 2, 0.0)
+    pl = dict(linear=lin.astype(dtype), normal=normal.astype(dtype), albedo=albedo.astype(dtype), z=z.astype(dtype), object_id=ids,
+              variance=var.astype(dtype))
+    return pl, clean.astype(dtype)
+
+
+# ---- the reference of the accumulation with a motion plane -------------------------------------------------
+def ref_temporal_motion(hist, cam, pl, motion, with_ids=True, with_var=True, alpha=0.2, max_history=32, sigma_normal=0.3, sigma_depth=0.05):
+    """test_temporal.ref_temporal with steps 2-3 replaced by `motion` (H, W, 3): fx, fy, z_exp of the pixel itself; no history
+    when z_exp <= 0, a value is not finite or `hist` is empty.  Steps 1, 4, 5, 6, the returned dict, the margins (without q.z,
+    which is no decision here: z_exp <= 0 is an exact marker of the input) and left_out are ref_temporal's."""
+    al, sn, sd = (float(F(v)) for v in (alpha, sigma_normal, sigma_depth))
+    cs = cam_setup(cam)
+    H, W = cs["H"], cs["W"]
+    lin, n64, z64 = (pl[k].astype(np.float64) for k in ("linear", "normal", "z"))
+    ids = pl["object_id"] if with_ids else None
+    valid = (ids >= 0) if with_ids else (pl["z"] < BIG)
+    a = np.where(pl["albedo"] > F(1e-3), pl["albedo"], 1).astype(np.float64)
+    mv = np.asarray(motion, np.float64)
+    with np.errstate(all="ignore"):
+        d = lin / a
+        part = valid & np.isfinite(d).all(-1)
+        v64 = pl["variance"].astype(np.float64) if with_var else np.zeros_like(lin)
+        u = np.where(np.isfinite(v64) & (v64 > 0), v64, 0.0) / a ** 2
+        idp = ids if with_ids else np.zeros((H, W), np.int32)
+        margin = np.full((H, W), np.inf)
+        tainted = np.zeros((H, W), bool)
+        Wsum, nsum = np.zeros((H, W)), np.zeros((H, W))
+        dsum, usum = np.zeros((H, W, 3)), np.zeros((H, W, 3))
+        lo = dict(d=np.full((H, W, 3), np.inf), u=np.full((H, W, 3), np.inf), N=np.full((H, W), np.inf))
+        hi = {k: -v for k, v in lo.items()}
+        geom = np.zeros((H, W), bool)
+        if hist:
+            geom = np.isfinite(mv).all(-1) & (mv[..., 2] > 0)
+            fx, fy, zexp = (np.where(geom, mv[..., k], 0.0) for k in range(3))
+            for f, size in ((fx, W), (fy, H)):
+                margin = np.minimum(margin, np.where(geom, np.minimum(np.abs(f + 1), np.abs(f - size)), np.inf))
+            geom &= (fx > -1) & (fx < W) & (fy > -1) & (fy < H)
+            x0, y0 = np.floor(fx), np.floor(fy)
+            tx, ty = fx - x0, fy - y0
+            for k in range(4):                                  # (0,0), (1,0), (0,1), (1,1)
+                i, j = k & 1, k >> 1
+                qx, qy = x0 + i, y0 + j
+                inside = geom & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                qx, qy = np.clip(qx, 0, W - 1).astype(int), np.clip(qy, 0, H - 1).astype(int)
+                w = (tx if i else 1 - tx) * (ty if j else 1 - ty)
+                reach = inside & (hist["N"][qy, qx] > 0) & ((hist["id"][qy, qx] == idp) if with_ids else True)
+                dn2 = ((hist["n"][qy, qx] - n64) ** 2).sum(-1)
+                dzq, thr = np.abs(hist["z"][qy, qx] - zexp), sd * np.maximum(hist["z"][qy, qx], zexp)
+                margin = np.minimum(margin, np.where(reach, np.abs(dn2 - sn * sn) / (sn * sn), np.inf))
+                margin = np.minimum(margin, np.where(reach, np.abs(dzq - thr) / np.where(reach, thr, 1.0), np.inf))
+                acc = reach & (dn2 <= sn * sn) & (dzq <= thr)
+                tainted |= inside & (w > 0) & hist["left_out"][qy, qx]
+                wa = np.where(acc, w, 0.0)
+                Wsum += wa
+                nsum += wa * hist["N"][qy, qx]
+                dsum += wa[..., None] * np.where(acc[..., None], hist["d"][qy, qx], 0.0)
+                usum += wa[..., None] * np.where(acc[..., None], hist["u"][qy, qx], 0.0)
+                for key in ("d", "u", "N"):
+                    m = acc if key == "N" else acc[..., None]
+                    lo[key] = np.minimum(lo[key], np.where(m, hist[key][qy, qx], np.inf))
+                    hi[key] = np.maximum(hi[key], np.where(m, hist[key][qy, qx], -np.inf))
+            margin = np.minimum(margin, np.where(geom, np.abs(Wsum - 0.01), np.inf))
+        has = part & geom & (Wsum >= 0.01)
+        safe = np.where(has, Wsum, 1.0)
+        N = np.where(has, np.minimum(nsum / safe + 1, float(max_history)), 1.0)
+        beta = np.maximum(al, 1.0 / N)[..., None]
+        d2 = np.where(has[..., None], (1 - beta) * dsum / safe[..., None] + beta * d, d)
+        u2 = np.where(has[..., None], (1 - beta) ** 2 * usum / safe[..., None] + beta ** 2 * u, u)
+        N = np.where(part, N, 0.0)
+        left_out = part & ((margin < MARGIN) | tainted)
+        spread = {k: np.where(has if k == "N" else has[..., None], hi[k] - lo[k], 0.0) for k in lo}
+        hist.clear()
+        hist.update(cam=cs, d=d2, u=u2, N=N, z=z64, n=n64, id=np.where(part, idp, -1), left_out=left_out)
+        return dict(linear=np.where(part[..., None], d2 * a, lin), variance=np.where(part[..., None], u2 * a ** 2, v64), history=N,
+                    part=part, has=has, weight=np.where(has, Wsum, 0.0), margin=margin, left_out=left_out, s_linear=spread["d"] * a,
+                    s_variance=spread["u"] * a ** 2, s_history=spread["N"])
+
+
+# the moving-square sequences of the GPU tests: name -> (turn in degrees per frame, the square under a moved parent?)
+MOVES = {"translate": (0.0, False), "translate+turn": (5.0, False), "parent": (5.0, True)}
+FRAMES = 3
+
+
+def _moving_sequence(w, h, move, noise, with_ids=True, with_var=True, light=light_smooth, dtype=np.float32, cams=None, seed=200, f32_plane=True, **params):
+    """the motion reference and the accumulation reference over the sequence: [dict(cam, nodes, prev_cam, prev_nodes, pl, clean,
+    motion (float64), found, plane (what the accumulation was fed: float32 when f32_plane), r)]"""
+    turn, chain = MOVES[move]
+    cams = cams or [cam_a(w, h)] * FRAMES
+    hist, out, prev = {}, [], None
+    for k, cam in enumerate(cams):
+        nodes = square_nodes(k, turn, chain=chain)
+        pl, clean = frame_nodes(cam, nodes, seed + k, noise, light, dtype)
+        prev_cam, prev_nodes = (prev["cam"], prev["nodes"]) if prev else (cam, None)
+        mv, found, qz = ref_motion(cam, prev_cam, nodes, prev_nodes, pl["z"], pl["object_id"])
+        plane = mv.astype(np.float32) if f32_plane else mv
+        r = ref_temporal_motion(hist, cam, pl, plane, with_ids, with_var, **params)
+        prev = dict(cam=cam, nodes=nodes, prev_cam=prev_cam, prev_nodes=prev_nodes, pl=pl, clean=clean, motion=mv, found=found, qz=qz, plane=plane, r=r)
+        out.append(prev)
+    return out
+
+
+# ---- CPU: the ABI -------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ("rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion")
+
+
+def test_new_symbols_and_struct_layout():
+    L = capi.lib()
+    for name in NEW_SYMBOLS:
+        assert hasattr(L, name) and name in capi.SYMBOLS, name
+    assert L.rt_abi_version() == 4
+    assert [f[0] for f in capi.MotionPlanes._fields_] == ["struct_size", "z", "object_id", "motion"]
+    assert C.sizeof(capi.MotionPlanes) == 32 and capi.MotionPlanes().struct_size == 32
+    # the existing structs did not grow
+    assert C.sizeof(capi.TemporalParams) == 24 and C.sizeof(capi.TemporalPlanes) == 88 and capi.NODE.itemsize == 100
+
+
+def test_argument_checks_come_before_any_gpu_call():
+    """every refusal is RT_ERR_ARG and names its reason, on a machine with or without a GPU; with valid arguments a machine
+    without one answers RT_ERR_NO_DEVICE"""
+    L = capi.lib()
+    cam, nodes = cam_a(8, 8), make_nodes()
+    buf = np.zeros(8 * 8 * 3, np.float32)
+    ptr = buf.ctypes.data
+    full = lambda **kw: capi.MotionPlanes(**{**dict(z=ptr, object_id=ptr, motion=ptr), **kw})
+    np_ = lambda a: a.ctypes.data if a is not None else None
+
+    def both(c, pc, n, pn, count, pl):
+        sts = (L.rt_motion(0, C.byref(c) if c else None, C.byref(pc) if pc else None, np_(n), np_(pn), count, C.byref(pl) if pl else None),
+               L.rt_motion_device(0, None, C.byref(c) if c else None, C.byref(pc) if pc else None, np_(n), np_(pn), count, C.byref(pl) if pl else None, 1))
+        return sts, L.rt_last_error()
+
+    cases = [(b"NULL", (None, cam, nodes, None, 5, full())), (b"NULL", (cam, None, nodes, None, 5, full())),
+             (b"NULL", (cam, cam, None, None, 5, full())), (b"NULL", (cam, cam, nodes, None, 5, None))]
+    for bad in (0, 24, 40):
+        pl = full()
+        pl.struct_size = bad
+        cases.append((b"struct_size", (cam, cam, nodes, None, 5, pl)))
+    for name in ("z", "object_id", "motion"):
+        cases.append((b"required", (cam, cam, nodes, None, 5, full(**{name: None}))))
+    for bad in (0, -1):
+        cases.append((b"n_nodes", (cam, cam, nodes, None, bad, full())))
+    for i, parent in ((0, 0), (2, 2), (2, 3), (1, -2)):
+        broken = make_nodes()
+        broken[i]["parent"] = parent
+        cases.append((b"parent", (cam, cam, broken, None, 5, full())))
+        cases.append((b"parent", (cam, cam, nodes, broken, 5, full())))
+    for other in (cam_a(9, 8), cam_a(8, 7)):
+        cases.append((b"previous one", (cam, other, nodes, None, 5, full())))
+    for what, args in cases:
+        sts, err = both(*args)
+        assert sts == (-1, -1) and what in err, (what, sts, err)
+    # rt_temporal_motion: the NULL plane first, then rt_temporal's own checks
+    p, pl = capi.temporal_params(), capi.TemporalPlanes(rgb_linear=ptr, normal=ptr, albedo=ptr, z=ptr, out_linear=ptr)
+    assert L.rt_temporal_motion(None, C.byref(cam), C.byref(p), C.byref(pl), None) == -1 and b"motion plane is NULL" in L.rt_last_error()
+    assert L.rt_temporal_motion_device(None, None, C.byref(cam), C.byref(p), C.byref(pl), None, 1) == -1 and b"motion plane is NULL" in L.rt_last_error()
+    assert L.rt_temporal_motion(None, C.byref(cam), C.byref(p), C.byref(pl), ptr) == -1 and b"history is NULL" in L.rt_last_error()
+    assert L.rt_temporal_motion_device(None, None, C.byref(cam), C.byref(p), C.byref(pl), ptr, 1) == -1 and b"history is NULL" in L.rt_last_error()
+    p.alpha = 0.0
+    assert L.rt_temporal_motion(None, C.byref(cam), C.byref(p), C.byref(pl), ptr) == -1 and b"alpha" in L.rt_last_error()
+    if capi.device_count() == 0:
+        sts, _ = both(cam, cam, nodes, nodes, 5, full())
+        assert sts == (-3, -3)
+        with pytest.raises(capi.RtError) as e:
+            capi.motion(cam, cam, nodes, None, np.zeros((8, 8), np.float32), np.zeros((8, 8), np.int32))
+        assert e.value.status == -3
+
+
+def _build_shim_driver(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_motion_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_motion_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+def test_shim_driver_builds_against_the_header(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+# ---- CPU: the references --------------------------------------------------------------------------------------
+def test_frame_nodes_with_the_square_at_rest_is_test_temporals_frame():
+    for cam in (cam_a(37, 23), cam_b(37, 23), cam_c(5, 40)):
+        for light in (light_smooth, light_affine):
+            (pl, clean), (want, want_clean) = frame_nodes(cam, square_nodes(0), 3, 0.3, light, np.float64), frame(cam, 3, 0.3, light, np.float64)
+            assert (pl["object_id"] == want["object_id"]).all()
+            for k in ("linear", "normal", "albedo", "z", "variance"):
+                assert np.allclose(pl[k], want[k], rtol=1e-12, atol=1e-12), k
+            assert np.allclose(clean, want_clean, rtol=1e-12, atol=1e-12)
+    # the chain places the square where the single node does
+    for k in range(FRAMES):
+        (a, _), (b, _) = frame_nodes(cam_a(37, 23), square_nodes(k, 5.0), 3, 0.0), frame_nodes(cam_a(37, 23), square_nodes(k, 5.0, chain=True), 3, 0.0)
+        assert (a["object_id"] == b["object_id"]).all() and np.allclose(a["z"], b["z"], rtol=1e-6) and np.allclose(a["linear"], b["linear"], rtol=1e-5)
+
+
+def test_reference_motion_of_a_world_at_rest_is_the_pixel_itself():
+    cam = cam_b(37, 23)
+    nodes = square_nodes(1, 5.0, chain=True)
+    pl, _ = frame_nodes(cam, nodes, 0, 0.0, dtype=np.float64)
+    for prev in (nodes.copy(), None):
+        mv, found, _ = ref_motion(cam, cam, nodes, prev, pl["z"], pl["object_id"])
+        hit = pl["object_id"] >= 0
+        Y, X = np.mgrid[0:23, 0:37]
+        assert (found == hit).all()
+        # through the chains itm and tm are float32 records, inverse to each other to 2^-24: of |P| ~ 10 that is 6e-7, and a pixel
+        # is 0.2 wide at the square
+        tol = 1e-9 if prev is None else 1e-5
+        assert np.abs(mv[..., 0] - X)[hit].max() < tol and np.abs(mv[..., 1] - Y)[hit].max() < tol and np.abs(mv[..., 2] - pl["z"])[hit].max() < tol
+        assert (mv[~hit] == np.stack([X, Y, 0 * X], -1)[~hit]).all()
+
+
+def test_reference_motion_of_a_static_world_is_what_ref_temporal_computes():
+    """cameras A -> B: fx, fy and z_exp of test_temporal's own step 3, recomputed here the way its disocclusion test does"""
+    camA, camB = cam_a(37, 23), cam_b(37, 23)
+    nodes = square_nodes(0)
+    pl, _ = frame(camB, 0, 0.0, dtype=np.float64)
+    mv, found, _ = ref_motion(camB, camA, nodes, nodes.copy(), pl["z"], pl["object_id"])
+    cs, old = cam_setup(camB), cam_setup(camA)
+    P = cs["pos"] + pl["z"][..., None] * pixel_rays(cs)
+    e = P - old["pos"]
+    q = e @ old["M"]
+    t = old["b"][2] / q[..., 2]
+    want = np.stack([(q[..., 0] * t - old["b"][0]) / old["u"] - 0.5, (q[..., 1] * t - old["b"][1]) / old["v"] - 0.5, np.sqrt((e * e).sum(-1))], -1)
+    hit = pl["object_id"] >= 0
+    assert (found == hit).all() and np.abs(mv - want)[hit].max() < 1e-9
+    # and the accumulation fed with this plane is ref_temporal's
+    h1, h2 = {}, {}
+    plA, _ = frame(camA, 1, 0.3, dtype=np.float64)
+    plB, _ = frame(camB, 2, 0.3, dtype=np.float64)
+    ref_temporal(h1, camA, plA)
+    ref_temporal_motion(h2, camA, plA, ref_motion(camA, camA, nodes, None, plA["z"], plA["object_id"])[0])
+    r1 = ref_temporal(h1, camB, plB)
+    r2 = ref_temporal_motion(h2, camB, plB, ref_motion(camB, camA, nodes, None, plB["z"], plB["object_id"])[0])
+    assert (r1["has"] == r2["has"]).all() and np.abs(r1["linear"] - r2["linear"]).max() < 1e-9 and np.abs(r1["history"] - r2["history"]).max() < 1e-9
+
+
+def test_reference_motion_follows_a_translated_node_and_a_moved_parent():
+    cam = cam_a(37, 23)
+    cs = cam_setup(cam)
+    d = np.array([0.3, 0.1, 0.0])
+    cur, prev = square_nodes(1), square_nodes(0)
+    pl, _ = frame_nodes(cam, cur, 0, 0.0, dtype=np.float64)
+    mv, found, _ = ref_motion(cam, cam, cur, prev, pl["z"], pl["object_id"])
+    sq = pl["object_id"] == SQUARE
+    P = cs["pos"] + pl["z"][..., None] * pixel_rays(cs)
+    # P_prev = P - d: project P - d by hand
+    e = (P - d) - cs["pos"]
+    q = e @ cs["M"]
+    t = cs["b"][2] / q[..., 2]
+    want = np.stack([(q[..., 0] * t - cs["b"][0]) / cs["u"] - 0.5, (q[..., 1] * t - cs["b"][1]) / cs["v"] - 0.5, np.sqrt((e * e).sum(-1))], -1)
+    assert sq.sum() > 50 and found[sq].all() and np.abs(mv - want)[sq].max() < 1e-6         # (the nodes are float32 records)
+    Y, X = np.mgrid[0:23, 0:37]
+    wall = pl["object_id"] == WALL
+    assert np.abs(mv[..., 0] - X)[wall].max() < 1e-9 and np.abs(mv[..., 1] - Y)[wall].max() < 1e-9
+    assert 1.0 < (X - mv[..., 0])[sq].mean() < 2.5           # 0.3 at distance 6 is about 1.6 pixels at 37 x 23
+    # a two-deep chain: only the PARENT's record differs between the frames, and the child moves with it -- by the same
+    # positions as when the square's own node makes that move
+    for k in (1, 2):
+        c_cur, c_prev = square_nodes(k, 5.0, chain=True), square_nodes(k - 1, 5.0, chain=True)
+        assert c_cur[SQUARE].tobytes() == c_prev[SQUARE].tobytes() and c_cur[PARENT].tobytes() != c_prev[PARENT].tobytes()
+        pl, _ = frame_nodes(cam, c_cur, 0, 0.0, dtype=np.float64)
+        chain_mv = ref_motion(cam, cam, c_cur, c_prev, pl["z"], pl["object_id"])[0]
+        own_mv = ref_motion(cam, cam, square_nodes(k, 5.0), square_nodes(k - 1, 5.0), pl["z"], pl["object_id"])[0]
+        sq = pl["object_id"] == SQUARE
+        assert np.abs(chain_mv - own_mv)[sq].max() < 1e-5 and np.abs(chain_mv[..., 0] - X)[sq].max() > 1.0
+        assert (chain_mv[~sq] == own_mv[~sq]).all()
+
+
+def _taps(plane, w, h):
+    """the four taps of every pixel: [(qy, qx, weight, inside)]"""
+    fx, fy = plane[..., 0].astype(np.float64), plane[..., 1].astype(np.float64)
+    x0, y0 = np.floor(fx), np.floor(fy)
+    tx, ty = fx - x0, fy - y0
+    out = []
+    for k in range(4):
+        i, j = k & 1, k >> 1
+        qx, qy = x0 + i, y0 + j
+        inside = (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
+        out.append((np.clip(qy, 0, h - 1).astype(int), np.clip(qx, 0, w - 1).astype(int), (tx if i else 1 - tx) * (ty if j else 1 - ty), inside))
+    return out
+
+
+def _exact_pixels(seq):
+    """per frame, the pixels whose accumulated colour is a bilinear interpolation all the way back: frame 0 every pixel that
+    takes part; later a pixel with all four taps accepted (W = 1) whose taps with weight were themselves exact -- a pixel
+    that renormalised a rejected tap away holds no interpolation, and hands that on"""
+    w, h = seq[0]["cam"].width, seq[0]["cam"].height
+    exact = [seq[0]["r"]["part"]]
+    for s in seq[1:]:
+        e = s["r"]["has"] & (s["r"]["weight"] > 1 - 1e-9)
+        for qy, qx, wgt, inside in _taps(s["plane"], w, h):
+            e &= (wgt <= 0) | (inside & exact[-1][qy, qx])
+        exact.append(e)
+    return exact
+
+
+@pytest.mark.parametrize("move", ["translate", "translate+turn"])
+def test_camera_only_accumulation_ghosts_on_a_moving_square_and_the_motion_path_does_not(move):
+    """fixed camera, zero noise, the affine light in the square's object frame: every point of the square keeps its colour, and
+    that colour is affine in the stored image's pixel coordinates (the square stays in a plane parallel to the image), so
+    bilinear taps at the right place reproduce it exactly"""
+    w, h = 37, 23
+    seq = _moving_sequence(w, h, move, 0.0, light=light_affine, dtype=np.float64, f32_plane=False)
+    exact = _exact_pixels(seq)
+    hist = {}
+    for k, s in enumerate(seq):
+        pl, clean, r = s["pl"], s["clean"], s["r"]
+        ghost = ref_temporal(hist, s["cam"], pl)
+        sq, wall = pl["object_id"] == SQUARE, pl["object_id"] == WALL
+        if k == 0:
+            continue
+        # camera-only: the square's pixels reproject onto themselves, find id 4, the same normal and depth: history kept ...
+        inner = sq & (seq[k - 1]["pl"]["object_id"] == SQUARE)
+        assert inner.sum() > 30 and (ghost["history"][inner] >= 2).all() and ghost["has"][inner].all()
+        # ... from another point of the square: the ghost (the light differs by 0.05 * 0.3 + 0.03 * 0.1 a frame, times the albedo)
+        assert np.abs(ghost["linear"] - clean)[inner].max() > 3e-3
+        # the motion path: the clean colour.  (1e-7, not test_temporal's 1e-9: a node's tm and itm are float32 records, inverse
+        # to each other to 2^-24 of coordinates up to 10, so a point of the square comes back 6e-7 from where it was in its
+        # object frame; times the light's gradient 0.06 and the albedo, against a colour of 0.4: 6e-8)
+        keep = sq & exact[k]
+        assert keep.sum() > 20 and (r["history"][keep] == k + 1).all()
+        assert (np.abs(r["linear"] - clean)[keep] <= 1e-7 * np.abs(clean[keep])).all()
+        assert (np.abs(r["linear"] - clean)[wall & exact[k]] <= 1e-9 * np.abs(clean[wall & exact[k]])).all()
+        # wall pixels the square uncovered: their own position held the square a frame ago -- another id, no history
+        uncovered = wall & (seq[k - 1]["pl"]["object_id"] == SQUARE)
+        assert uncovered.sum() >= 5 and (r["history"][uncovered] == 1).all() and not r["has"][uncovered].any()
+        assert (r["history"][wall & (seq[k - 1]["pl"]["object_id"] == WALL)] >= 2).all()
+
+
+GPU_RUNS = [(move, None, 37, 23) for move in MOVES] + [("translate+turn", "A,B,C", 37, 23)] + [("translate+turn", None, w, h) for w, h in SIZES[1:]]
+
+
+def _cams(name, w, h):
+    return [c(w, h) for c in (cam_a, cam_b, cam_c)] if name == "A,B,C" else None
+
+
+def test_few_pixels_are_left_out_of_the_gpu_comparisons():
+    """at most 2 % of the valid pixels of any frame of any sequence the GPU tests use, on the reference alone"""
+    for move, cams, w, h in GPU_RUNS + [("translate", "affine", 37, 23)]:
+        for with_ids in (True, False):
+            affine = cams == "affine"
+            seq = _moving_sequence(w, h, move, 0.0 if affine else 0.3, with_ids, light=light_affine if affine else light_smooth, cams=_cams(cams, w, h))
+            for k, s in enumerate(seq):
+                share = s["r"]["left_out"].sum() / max(1, _valid(s["pl"], with_ids).sum())
+                assert share <= MAX_LEFT_OUT, (move, cams, w, h, with_ids, k, share)
+                assert (s["qz"][s["pl"]["object_id"] >= 0] < -MARGIN).all()      # no pixel near the q.z decision of k_motion
+
+
+# ---- GPU: k_motion against the reference ------------------------------------------------------------------------
+def _check_plane(got, cam, prev_cam, nodes, prev_nodes, z, ids, what):
+    """got against ref_motion: fx + fy within motion_px, z_exp within 2e-5 |want| + 1e-6, (x, y, 0) exactly where there is no
+    previous position; returns the worst error / tolerance"""
+    want, found, qz = ref_motion(cam, prev_cam, nodes, prev_nodes, z, ids)
+    assert got.shape == want.shape and got.dtype == np.float32
+    assert (np.abs(qz[np.isfinite(qz)]) > MARGIN).all(), what
+    assert got[~found].tobytes() == want[~found].astype(np.float32).tobytes(), what
+    if not found.any():
+        return 0.0
+    z_min = float(min(z[found].min(), want[..., 2][found].min()))
+    tol = motion_px(cam, prev_cam, nodes, prev_nodes, np.unique(ids[found]), z_min)
+    err = (np.abs(got[..., 0] - want[..., 0]) + np.abs(got[..., 1] - want[..., 1]))[found]
+    zerr, ztol = np.abs(got[..., 2] - want[..., 2])[found], (2e-5 * np.abs(want[..., 2]) + 1e-6)[found]
+    worst = max(float(err.max() / tol), float((zerr / ztol).max()))
+    print(f"motion {what}: max |fx|+|fy| error {err.max():.3e} px (bound {tol:.3e}), z_exp worst err/tolerance {(zerr / ztol).max():.4f}")
+    assert (err <= tol).all() and (zerr <= ztol).all(), (what, worst)
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("move,cams,w,h", GPU_RUNS)
+def test_motion_plane_against_the_reference(move, cams, w, h):
+    """static world under cameras A -> B -> C (the wall, and frame 0 -> 1 of every node), the moving square under a fixed camera,
+    both together, and the square under a moved parent.  Measured on the MI355X: DESIGN 3."""
+    for s in _moving_sequence(w, h, move, 0.0, cams=_cams(cams, w, h)):
+        got = capi.motion(s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], s["pl"]["z"], s["pl"]["object_id"])
+        _check_plane(got, s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], s["pl"]["z"], s["pl"]["object_id"], f"{move} {cams} {w}x{h}")
+    if cams:                            # a world at rest under moving cameras: the same nodes twice
+        cl = _cams(cams, w, h)
+        nodes = square_nodes(0)
+        for prev_cam, cam in zip(cl, cl[1:]):
+            pl, _ = frame(cam, 0, 0.0)
+            got = capi.motion(cam, prev_cam, nodes, nodes.copy(), pl["z"], pl["object_id"])
+            _check_plane(got, cam, prev_cam, nodes, nodes.copy(), pl["z"], pl["object_id"], f"static {cams} {w}x{h}")
+
+
+def _seventy_nodes(k):
+    """70 nodes in chains of up to three, every one with a small rigid motion of its own per frame k"""
+    rng = np.random.default_rng(7)
+    nodes = make_nodes(70)
+    for i in range(1, 70):
+        axis_turn, shift = rng.uniform(-4, 4), rng.uniform(-0.3, 0.3, 3)
+        set_node(nodes, i, rot_z(k * axis_turn) * (1.0 + 0.1 * (i % 3)), rng.uniform(-1, 1, 3) + k * shift, parent=0 if i < 24 else i - 23)
+    return nodes
+
+
+@pytest.mark.gpu
+def test_motion_plane_with_a_seventy_node_table():
+    w, h = 37, 23
+    cam, prev_cam = cam_b(w, h), cam_a(w, h)
+    pl, _ = frame(cam, 0, 0.0)
+    Y, X = np.mgrid[0:h, 0:w]
+    ids = np.where(pl["object_id"] >= 0, (X + 7 * Y) % 70, -1).astype(np.int32)
+    assert len(np.unique(ids[ids >= 0])) == 70
+    nodes, prev = _seventy_nodes(1), _seventy_nodes(0)
+    got = capi.motion(cam, prev_cam, nodes, prev, pl["z"], ids)
+    _check_plane(got, cam, prev_cam, nodes, prev, pl["z"], ids, "70 nodes")
+    assert np.abs(got[..., 0] - X)[ids > 0].max() > 1.0
+
+
+@pytest.mark.gpu
+def test_pixels_without_a_previous_position_hold_x_y_0():
+    w, h = 37, 23
+    cam = cam_a(w, h)
+    nodes, prev = square_nodes(1), square_nodes(0)
+    pl, _ = frame_nodes(cam, nodes, 0, 0.0)
+    z, ids = pl["z"].copy(), pl["object_id"].copy()
+    Y, X = np.mgrid[0:h, 0:w]
+    none = np.zeros((h, w), bool)
+    for (y, x), bad_id in zip(((2, 3), (7, 9), (11, 18), (20, 1)), (5, 6, 2 ** 31 - 1, -7)):      # ids >= n_nodes (5 nodes), and below -1
+        ids[y, x], none[y, x] = bad_id, True
+    for (y, x), bad_z in zip(((3, 3), (8, 9), (12, 18), (21, 1), (14, 14)), (np.nan, np.inf, -np.inf, 1e30, 2e30)):
+        z[y, x], none[y, x] = bad_z, True
+    none |= pl["object_id"] < 0         # id -1: the strip where nothing is hit
+    got = capi.motion(cam, cam, nodes, prev, z, ids)
+    want = np.stack([X, Y, 0 * X], -1).astype(np.float32)
+    assert none.sum() > 50 and got[none].tobytes() == want[none].tobytes() and (got[..., 2][~none] > 0).all()
+    _check_plane(got, cam, cam, nodes, prev, z, ids, "special pixels")
+    # q.z >= 0: the previous camera beyond the wall, looking away from it -- every point lies behind it
+    beyond = make_cam(w, h, pos=(0.0, 0.0, -5.0))
+    got = capi.motion(cam, beyond, nodes, prev, pl["z"], pl["object_id"])
+    assert got.tobytes() == want.tobytes()
+    _check_plane(got, cam, beyond, nodes, prev, pl["z"], pl["object_id"], "previous camera beyond the points")
+
+
+@pytest.mark.gpu
+def test_static_nodes_bit_for_bit_and_a_world_at_rest_exactly():
+    w, h = 37, 23
+    nodes = square_nodes(2, 5.0, chain=True)
+    pl, _ = frame_nodes(cam_b(w, h), nodes, 0, 0.0)
+    for prev_cam in (cam_a(w, h), cam_b(w, h)):
+        a = capi.motion(cam_b(w, h), prev_cam, nodes, nodes.copy(), pl["z"], pl["object_id"])
+        b = capi.motion(cam_b(w, h), prev_cam, nodes, None, pl["z"], pl["object_id"])
+        assert a.tobytes() == b.tobytes()
+    # the same camera and nothing moved: (x, y, z) exactly
+    Y, X = np.mgrid[0:h, 0:w]
+    hit = pl["object_id"] >= 0
+    assert (a[..., 0] == X).all() and (a[..., 1] == Y).all() and (a[..., 2][hit] == pl["z"][hit]).all() and (a[..., 2][~hit] == 0).all()
+
+
+# ---- GPU: k_temporal<MOTION> against the reference ---------------------------------------------------------
+def _accumulate_against_reference(seq, w, h, with_ids, with_var, what, planes=None, delta=0.0):
+    """the sequence's frames to a History with a motion plane per frame (the reference's own, float32, unless `planes`), compared
+    after each step through test_temporal's gate"""
+    worst = 0.0
+    with capi.History(0, w, h) as hst:
+        for k, s in enumerate(seq):
+            pl, r = s["pl"], s["r"]
+            res = hst.accumulate(s["cam"], pl["linear"], pl["normal"], pl["albedo"], pl["z"], return_history=True,
+                                 motion=planes[k] if planes else s["plane"], **_planes_for(pl, with_ids, with_var))
+            got, got_hist = res[0], res[-1]
+            assert hst.frames == k + 1
+            part = r["part"]
+            keep = part & ~r["left_out"]
+            assert r["left_out"].sum() <= MAX_LEFT_OUT * max(1, _valid(pl, with_ids).sum())
+            dl = delta if k else 0.0
+            tag = f"motion {what} {w}x{h} ids={with_ids} var={with_var} step {k}"
+            worst = max(worst, _gate(got, r["linear"], r["s_linear"], dl, keep, tag + " colour", 1e-6))
+            worst = max(worst, _gate(got_hist, r["history"], r["s_history"], dl, keep, tag + " history", 1e-6))
+            if with_var:
+                worst = max(worst, _gate(res[1], r["variance"], r["s_variance"], dl, keep, tag + " variance", 1e-12))
+                assert res[1][~part].tobytes() == pl["variance"][~part].tobytes()
+            assert got[~part].tobytes() == pl["linear"][~part].tobytes() and (got_hist[~part] == 0).all()
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("move", ["translate", "translate+turn"])
+@pytest.mark.parametrize("with_ids,with_var", [(True, True), (False, True), (True, False), (False, False)])
+def test_accumulation_with_the_references_motion_plane_37x23(move, with_ids, with_var):
+    """the kernel and the reference read the SAME float32 plane, so the position carries no error of its own (delta_px = 0):
+    what is left is the project's 2e-5 |want| + floor of test_temporal's gate.  Measured on the MI355X: DESIGN 3."""
+    seq = _moving_sequence(37, 23, move, 0.3, with_ids, with_var)
+    assert any((s["r"]["history"] == 3).any() for s in seq)
+    _accumulate_against_reference(seq, 37, 23, with_ids, with_var, move)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", SIZES[1:])
+def test_accumulation_with_the_references_motion_plane_at_small_sizes(w, h):
+    for with_ids in (True, False):
+        _accumulate_against_reference(_moving_sequence(w, h, "translate+turn", 0.3, with_ids), w, h, with_ids, True, "translate+turn")
+
+
+@pytest.mark.gpu
+def test_markers_in_the_motion_plane_mean_no_history():
+    """z_exp <= 0 and values that are not finite: no history, whatever fx and fy say; the reference reads the same plane"""
+    w, h = 37, 23
+    seq = _moving_sequence(w, h, "translate", 0.3)
+    plane = seq[1]["plane"].copy()
+    plane[4, 5, 2], plane[6, 7, 2], plane[9, 9, 0], plane[10, 12, 1], plane[12, 3, 2], plane[15, 20, 0] = 0.0, -1.0, np.nan, np.inf, np.nan, -np.inf
+    marked = np.zeros((h, w), bool)
+    for y, x in ((4, 5), (6, 7), (9, 9), (10, 12), (12, 3), (15, 20)):
+        marked[y, x] = True
+    assert (seq[1]["pl"]["object_id"][marked] >= 0).all()
+    hist = {}
+    ref_temporal_motion(hist, seq[0]["cam"], seq[0]["pl"], seq[0]["plane"])
+    r = ref_temporal_motion(hist, seq[1]["cam"], seq[1]["pl"], plane)
+    with capi.History(0, w, h) as hst:
+        for s, mv in ((seq[0], seq[0]["plane"]), (seq[1], plane)):
+            pl = s["pl"]
+            got, n = hst.accumulate(s["cam"], pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"], return_history=True, motion=mv)
+    assert (n[marked] == 1).all() and not r["has"][marked].any() and (n[seq[1]["pl"]["object_id"] == WALL] == 2).sum() > 400
+    _gate(got, r["linear"], r["s_linear"], 0.0, r["part"] & ~r["left_out"], "motion markers colour", 1e-6)
+
+
+@pytest.mark.gpu
+def test_affine_light_follows_the_moving_square_through_k_motion_and_not_without_it():
+    """End to end: k_motion's own plane into k_temporal<MOTION>.  The property of the CPU test holds on the GPU -- the accumulated
+    square shows the clean colour, within the gate (delta: motion_px, the derived bound of k_motion's position) -- and
+    History.accumulate without motion= on the same frames does not: the ghost this feature removes."""
+    w, h = 37, 23
+    seq = _moving_sequence(w, h, "translate", 0.0, light=light_affine)
+    exact = _exact_pixels(seq)
+    with capi.History(0, w, h) as hst, capi.History(0, w, h) as plain:
+        for k, s in enumerate(seq):
+            pl = s["pl"]
+            mv = capi.motion(s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], pl["z"], pl["object_id"])
+            got = hst.accumulate(s["cam"], pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"], motion=mv)
+            ghost = plain.accumulate(s["cam"], pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"])
+            if k == 0:
+                assert got.tobytes() == ghost.tobytes()
+                continue
+            sq = pl["object_id"] == SQUARE
+            keep = sq & exact[k] & ~s["r"]["left_out"]
+            assert keep.sum() > 20
+            delta = motion_px(s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], [SQUARE], float(pl["z"][sq].min()))
+            # S_p from the reference, the expected values not: the clean colour of this frame (float32 inputs: inside the 2e-5)
+            _gate(got, s["clean"].astype(np.float64), s["r"]["s_linear"], delta, keep, f"affine light, moving square, step {k}", 1e-6)
+            err = np.abs(ghost.astype(np.float64) - s["clean"])[keep]
+            tol = (2e-5 * np.abs(s["clean"]) + 1e-6 + delta * s["r"]["s_linear"])[keep]
+            assert (err > tol).any() and err.max() > 3e-3, "the camera-only path did not ghost"
+
+
+@pytest.mark.gpu
+def test_without_a_motion_plane_nothing_changed_and_entry_points_aliasing_two_histories():
+    import torch
+    w, h = 37, 23
+    seq = _moving_sequence(w, h, "translate+turn", 0.3, cams=_cams("A,B,C", w, h))
+    big_cam = cam_b(90, 60)
+    big, _ = frame(big_cam, 9, 0.3)
+
+    def host_run(with_motion, disturb=False):
+        outs = []
+        with capi.History(0, w, h) as hst, capi.History(0, 90, 60) as other:
+            for s in seq:
+                pl = s["pl"]
+                outs.append(hst.accumulate(s["cam"], pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"], variance=pl["variance"],
+                                           rgb8=True, return_history=True, motion=s["plane"] if with_motion else None))
+                if disturb:
+                    other.accumulate(big_cam, big["linear"], big["normal"], big["albedo"], big["z"], big["object_id"],
+                                     motion=np.zeros((60, 90, 3), np.float32) if with_motion else None)
+        return outs
+
+    same = lambda a, b: all(x.tobytes() == y.tobytes() for fa, fb in zip(a, b) for x, y in zip(fa, fb))
+    plain, moved = host_run(False), host_run(True)
+    assert same(plain, host_run(False, disturb=True)) and same(moved, host_run(True, disturb=True))
+    assert not same(plain[1:], moved[1:]) and same(plain[:1], moved[:1])
+
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(device=dev)
+    mk = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+    torch.cuda.synchronize()
+    with capi.History(0, w, h) as out_of_place, capi.History(0, w, h) as in_place, capi.History(0, w, h) as no_plane:
+        for k, s in enumerate(seq):
+            tp = {key: torch.from_numpy(np.array(v)).to(dev) for key, v in s["pl"].items()}
+            mv_host = torch.from_numpy(s["plane"]).to(dev)
+            ptrs = dict(normal_ptr=tp["normal"].data_ptr(), albedo_ptr=tp["albedo"].data_ptr(), z_ptr=tp["z"].data_ptr(), object_id_ptr=tp["object_id"].data_ptr())
+            out, out_var, hist, rgb8 = mk(h, w, 3), mk(h, w, 3), mk(h, w), mk(h, w, 3, dt=torch.uint8)
+            torch.cuda.synchronize()
+            out_of_place.accumulate_device(side.cuda_stream, s["cam"], linear_ptr=tp["linear"].data_ptr(), out_ptr=out.data_ptr(),
+                                           variance_ptr=tp["variance"].data_ptr(), out_variance_ptr=out_var.data_ptr(), history_ptr=hist.data_ptr(),
+                                           rgb8_ptr=rgb8.data_ptr(), sync=False, motion_ptr=mv_host.data_ptr(), **ptrs)
+            lin2, var2 = tp["linear"].clone(), tp["variance"].clone()
+            side.wait_stream(torch.cuda.current_stream(dev))
+            in_place.accumulate_device(side.cuda_stream, s["cam"], linear_ptr=lin2.data_ptr(), out_ptr=lin2.data_ptr(), variance_ptr=var2.data_ptr(),
+                                       out_variance_ptr=var2.data_ptr(), sync=False, motion_ptr=mv_host.data_ptr(), **ptrs)
+            out3 = mk(h, w, 3)
+            no_plane.accumulate_device(side.cuda_stream, s["cam"], linear_ptr=tp["linear"].data_ptr(), out_ptr=out3.data_ptr(),
+                                       variance_ptr=tp["variance"].data_ptr(), sync=False, **ptrs)
+            side.synchronize()
+            want = moved[k]
+            assert out.cpu().numpy().tobytes() == want[0].tobytes() and out_var.cpu().numpy().tobytes() == want[1].tobytes()
+            assert rgb8.cpu().numpy().tobytes() == want[2].tobytes() and hist.cpu().numpy().tobytes() == want[3].tobytes()
+            assert lin2.cpu().numpy().tobytes() == want[0].tobytes() and var2.cpu().numpy().tobytes() == want[1].tobytes()
+            assert out3.cpu().numpy().tobytes() == plain[k][0].tobytes()
+            # rt_motion_device gives rt_motion's bytes
+            mv_dev = mk(h, w, 3)
+            capi.motion_device(0, side.cuda_stream, s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], z_ptr=tp["z"].data_ptr(),
+                               object_id_ptr=tp["object_id"].data_ptr(), motion_ptr=mv_dev.data_ptr(), sync=True)
+            host_mv = capi.motion(s["cam"], s["prev_cam"], s["nodes"], s["prev_nodes"], s["pl"]["z"], s["pl"]["object_id"])
+            assert mv_dev.cpu().numpy().tobytes() == host_mv.tobytes()
+
+
+@pytest.mark.gpu
+def test_calls_on_two_streams_with_a_changing_node_table_do_not_disturb_each_other():
+    """the node table is one buffer per device: a call queued on one stream behind other work must still read ITS table when a
+    later call on another stream brings another one"""
+    import torch
+    w, h = 37, 23
+    cam = cam_a(w, h)
+    tables = [(square_nodes(k + 1, 5.0, chain=True), square_nodes(k, 5.0, chain=True)) for k in range(3)]
+    pl, _ = frame_nodes(cam, tables[0][0], 0, 0.0)
+    want = [capi.motion(cam, cam, cur, prev, pl["z"], pl["object_id"]) for cur, prev in tables]
+    assert want[0].tobytes() != want[1].tobytes() != want[2].tobytes()
+    dev = torch.device("cuda", 0)
+    a, b = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    z, ids = torch.from_numpy(pl["z"]).to(dev), torch.from_numpy(pl["object_id"]).to(dev)
+    out = [torch.zeros((h, w, 3), dtype=torch.float32, device=dev) for _ in range(4)]
+    busy = torch.ones((2048, 2048), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    ptrs = dict(z_ptr=z.data_ptr(), object_id_ptr=ids.data_ptr())
+    with torch.cuda.stream(a):
+        for _ in range(8):              # a few milliseconds of work in front of the first call
+            busy = busy @ busy * 1e-4
+    capi.motion_device(0, a.cuda_stream, cam, cam, *tables[0], motion_ptr=out[0].data_ptr(), sync=False, **ptrs)
+    capi.motion_device(0, b.cuda_stream, cam, cam, *tables[0], motion_ptr=out[1].data_ptr(), sync=True, **ptrs)     # the same table, waited for
+    capi.motion_device(0, b.cuda_stream, cam, cam, *tables[1], motion_ptr=out[2].data_ptr(), sync=False, **ptrs)    # another one
+    capi.motion_device(0, a.cuda_stream, cam, cam, *tables[2], motion_ptr=out[3].data_ptr(), sync=False, **ptrs)    # and a third
+    torch.cuda.synchronize()
+    for got, k in zip(out, (0, 0, 1, 2)):
+        assert got.cpu().numpy().tobytes() == want[k].tobytes(), k
+
+
+# ---- GPU: a real scene ----------------------------------------------------------------------------------------------
+def _sphere_params(seed):
+    return capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=seed)
+
+
+SPHERE_CHILD, SPHERE_STEP = 2, (2.0, 0.0, 0.5)      # cornell.xml: the root's third child is sphere1
+
+
+def _move_sphere(s):
+    """sphere1 of cornell.xml translated by SPHERE_STEP: (its node index, the node arrays before and after)"""
+    before = s.get_nodes()
+    idx = [i for i in range(len(before)) if before[i]["obj_type"] == capi.OBJ_SPHERE and before[i]["parent"] == 0][0]
+    after = before.copy()
+    after[idx]["pos"] = (after[idx]["pos"] + F(SPHERE_STEP)).astype(np.float32)
+    s.set_nodes(after)
+    return idx, before, after
+
+
+@pytest.mark.gpu
+def test_render_temporal_moving_follows_a_moved_sphere():
+    w, h = 37, 23
+    s, cam = scenes.load_cornell(w, h)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    Y, X = np.mgrid[0:h, 0:w]
+    with capi.History(0, w, h) as hst:
+        one = s.render_temporal(hst, cam, _sphere_params(11), denoise=False, moving=True)
+        hit1 = one["object_id"] >= 0
+        assert (one["motion"][..., 0] == X).all() and (one["motion"][..., 1] == Y).all() and (one["motion"][..., 2][hit1] == one["z"][hit1]).all()
+        idx, before, after = _move_sphere(s)
+        two = s.render_temporal(hst, cam, _sphere_params(12), denoise=False, moving=True)
+        ids, mv = two["object_id"], two["motion"]
+        on = ids == idx
+        assert on.sum() >= 8 and (one["object_id"] == idx).sum() >= 8
+        _check_plane(mv, cam, cam, after, before, two["z"], ids, "cornell, sphere moved")
+        still = (ids >= 0) & ~on
+        assert (mv[..., 0][still] == X[still]).all() and (mv[..., 1][still] == Y[still]).all() and (mv[..., 2][still] == two["z"][still]).all()
+        assert np.abs(mv[..., 0] - X)[on].min() > 0.5
+        # interior pixels of the moved sphere (all four taps on the sphere a frame ago) have two frames, the pixels it uncovered one
+        interior = on.copy()
+        for qy, qx, wgt, inside in _taps(mv, w, h):
+            interior &= inside & (one["object_id"][qy, qx] == idx)
+        uncovered = (one["object_id"] == idx) & ~on & (ids >= 0)
+        assert interior.sum() >= 3 and uncovered.sum() >= 3
+        print(f"cornell 37x23: {on.sum()} sphere pixels, {interior.sum()} interior with history {np.unique(two['history'][interior])}, "
+              f"{uncovered.sum()} uncovered with history {np.unique(two['history'][uncovered])}")
+        assert (two["history"][interior] == 2).all() and (two["history"][uncovered] == 1).all()
+        # reset() clears what render_temporal(moving=True) remembers
+        assert hst._moving is not None
+        hst.reset()
+        assert hst._moving is None and hst.frames == 0
+        three = s.render_temporal(hst, cam, _sphere_params(12), denoise=False, moving=True)
+        hit3 = three["object_id"] >= 0
+        assert (three["motion"][..., 0] == X).all() and (three["motion"][..., 2][hit3] == three["z"][hit3]).all() and (three["history"][hit3] == 1).all()
+        assert hst._moving is not None
+        assert "motion" not in s.render_temporal(hst, cam, _sphere_params(13), denoise=False)
+        # a frame that reached the history another way: its nodes are not known, the remembered frame is forgotten, and the next
+        # moving frame is accumulated from the history's own camera, without a plane -- what accumulate() gives
+        assert hst._moving is None and hst.frames == 2
+        with capi.History(0, w, h) as other:
+            for seed in (12, 13):
+                o = s.render_temporal(other, cam, _sphere_params(seed), denoise=False)
+            want = s.render_temporal(other, cam, _sphere_params(14), denoise=False)
+        four = s.render_temporal(hst, cam, _sphere_params(14), denoise=False, moving=True)
+        assert four["accumulated"].tobytes() == want["accumulated"].tobytes() and four["history"].tobytes() == want["history"].tobytes()
+        assert "motion" in four and hst._moving is not None
+        pl = {k: four[k] for k in ("linear", "normal", "albedo", "z", "object_id")}
+        hst.accumulate(cam, pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"])
+        assert hst._moving is None
+
+
+@pytest.mark.gpu
+def test_cpp_shim_moving_accumulation_equals_the_capi_one(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    prefix = str(tmp_path / "f")
+    w, h = 37, 23
+    r = subprocess.run([exe, scenes.CORNELL, prefix, str(w), str(h), str(SPHERE_CHILD)] + [str(v) for v in SPHERE_STEP], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert r.stdout.split()[1] == str(w * h) and r.stdout.split()[-1] == "2", r.stdout
+    s, cam = scenes.load_cornell(w, h)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    with capi.History(0, w, h) as hst:
+        one = s.render_temporal(hst, cam, _sphere_params(11), denoise=False, moving=True)
+        _move_sphere(s)
+        two = s.render_temporal(hst, cam, _sphere_params(12), denoise=False, moving=True)
+    assert capi.image_read_pfm(prefix + "_mv1.pfm").tobytes() == one["motion"].tobytes()
+    assert capi.image_read_pfm(prefix + "_mv2.pfm").tobytes() == two["motion"].tobytes()
+    assert capi.image_read_pfm(prefix + "_acc2.pfm").tobytes() == two["accumulated"].tobytes()
+    assert capi.image_read_pfm1(prefix + "_len2.pfm").tobytes() == two["history"].tobytes()
+    assert (two["history"] > 1).mean() > 0.5
