@@ -536,13 +536,70 @@ rt_status rt_render_tiles_outputs_device(rt_scene *s, const rt_camera *cam, cons
  *   - asking for it changes nothing in any other plane (under RT_RENDER_REPRODUCIBLE: the same bytes as without), and nothing
  *     is allocated or launched for it when it is not asked for.
  * The two entry points are rt_render_begin_outputs / rt_render_tiles_outputs_device with the plane added: the descriptor checks
- * are theirs and come before anything is rendered; a NULL variance is RT_ERR_ARG.  The packed (multi-GPU) records do NOT carry
- * the plane: there is no packed _var entry point, and dist.ShardedRenderer does not know it. */
+ * are theirs and come before anything is rendered; a NULL variance is RT_ERR_ARG.  The multi-GPU exchange carries the
+ * plane as a section of the packed planes format ("packed planes" below). */
 rt_status rt_render_begin_outputs_var(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
                                       const rt_outputs *host_planes, float *variance, rt_job **out);
 rt_status rt_render_tiles_outputs_var_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
                                              int device, void *hip_stream, const rt_outputs *device_planes, float *variance_dev,
                                              int sync, rt_stats *stats_out);
+/* ---- packed planes: the feature and variance planes in the multi-GPU tile exchange (additive to ABI 4: detected by the
+ *      presence of the symbols; RT_ABI_VERSION, the structs and every entry point above are unchanged) ---------------------
+ * A rank's contribution to the all-gather stays ONE contiguous buffer, moved by ONE collective: the packed records of
+ * rt_render_tiles_packed_device / _packed_linear_device, followed by one SECTION per optional plane.  With
+ *     tile_px = tile_w * tile_h     tiles_total = the tile count of the image     per_rank = ceil(tiles_total / stride)
+ *     Q = per_rank * tile_px
+ * every section has Q slots, slot q being pixel q of the call's tile walk (tile k of the call at k * tile_px, row-major
+ * inside the tile) -- the index of the packed records.  The sections, in this order, each present only when its plane is
+ * in the mask:
+ *     records     24 B per slot with RT_PLANE_LINEAR (the records of _packed_linear_device), 8 B without; always present
+ *     normal      12 B per slot    float x 3   (RT_PLANE_NORMAL)
+ *     albedo      12 B per slot    float x 3   (RT_PLANE_ALBEDO)
+ *     alpha        4 B per slot    float       (RT_PLANE_ALPHA)
+ *     object_id    4 B per slot    int32       (RT_PLANE_OBJECT_ID)
+ *     variance    12 B per slot    float x 3   (RT_PLANE_VARIANCE)
+ * and the contribution is the sum of the sections, rounded up to a multiple of 16 bytes (so that contributions laid end to
+ * end keep the alignment of the first; with the usual 32 x 8 tiles nothing is added).  The records section holds the very
+ * bytes the existing packed entry points write for the same call; the plane values are those of rt_outputs and of the
+ * variance plane above.
+ * The sections are sized by per_rank, NOT by the call's own tile count: the ranks of an interleaved frame own
+ * ceil(tiles_total / stride) tiles or one fewer, and a collective moves the same number of bytes from every rank.  With
+ * sections sized by the call, a short rank's albedo would begin where a full rank's normals still run, and the reader of a
+ * gathered buffer would have to know which ranks were short.  Sized by per_rank, the offset of every section depends only on
+ * (width, height, tile size, stride, mask), never on `first`: one set of offsets reads every rank's block.
+ * Every slot that belongs to no pixel of the call is all zero in every section -- the slots of a ragged tile outside the
+ * image, the whole last tile of a rank that is one tile short, the object_id section included (0, not -1) -- and so is the
+ * rounding.  The buffer is therefore a pure function of the call's inputs (byte-comparable under RT_RENDER_REPRODUCIBLE).
+ * The zeros are written in stream order by every call, not expected from the caller.
+ *
+ * rt_tiles_packed_planes_size: *bytes (required) is the size of one contribution, *n_tiles (may be NULL) is per_rank -- the
+ * tiles_per_rank of the unpack -- and section_offsets (may be NULL) receives the byte offset of the six sections in the
+ * order above, UINT64_MAX for an absent one.  Unknown mask bits, a NULL `bytes`, a bad tile range: RT_ERR_ARG.
+ * rt_render_tiles_packed_outputs_device: rt_render_tiles_packed_device with the planes of `mask`; packed_bytes must be at
+ * least what the size query reports.  A NULL or short buffer and unknown mask bits are RT_ERR_ARG before anything is rendered.
+ * With mask 0 or RT_PLANE_LINEAR the records of the call's own tiles are the existing packed call's, to the byte.
+ * Stream-ordered; `sync` and stats_out as for rt_render_tiles_packed_device.
+ * rt_tiles_unpack_outputs_device: un-interleaves the gathered buffer of `world` ranks (rank r's contribution at
+ * r * bytes, each with the sections of (tiles_per_rank, mask)) into image-sized device planes with one HIP kernel on
+ * `hip_stream` (NULL: the device's legacy null stream, as for rt_tiles_unpack_device).  device_planes: rgb8, z and count are
+ * required as everywhere; every plane in the mask needs a destination (rgb_linear, normal, albedo, alpha, object_id of the
+ * descriptor, variance_dev), otherwise RT_ERR_ARG; destinations of planes outside the mask are not touched.  gathered_dev
+ * must be 16-byte aligned.  The motion plane needs no transport: it is a function of z and object_id (rt_motion_device) and
+ * is computed after the unpack. */
+#define RT_PLANE_LINEAR    1u
+#define RT_PLANE_NORMAL    2u
+#define RT_PLANE_ALBEDO    4u
+#define RT_PLANE_ALPHA     8u
+#define RT_PLANE_OBJECT_ID 16u
+#define RT_PLANE_VARIANCE  32u
+rt_status rt_tiles_packed_planes_size(int32_t width, int32_t height, const rt_tile_range *tiles, uint32_t mask,
+                                      uint64_t *bytes, int32_t *n_tiles, uint64_t section_offsets[6]);
+rt_status rt_render_tiles_packed_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, uint32_t mask,
+                                                int sync, rt_stats *stats_out);
+rt_status rt_tiles_unpack_outputs_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
+                                         int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, uint32_t mask,
+                                         const rt_outputs *device_planes, float *variance_dev);
 /* Waits for the asynchronous renders (sync == 0) issued so far on (scene, device) and returns
  * RT_ERR_LIMIT if any of them dropped rays or photon queries, RT_OK otherwise. */
 rt_status rt_render_check(rt_scene *s, int device);

@@ -134,6 +134,9 @@ TONEMAP_OPERATORS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces
 OUTPUT_PLANES = {"linear": ("rgb_linear", np.float32, 3), "normal": ("normal", np.float32, 3), "albedo": ("albedo", np.float32, 3),
                  "alpha": ("alpha", np.float32, 1), "object_id": ("object_id", np.int32, 1), "variance": (None, np.float32, 3)}
 FEATURE_PLANES = ("normal", "albedo", "alpha", "object_id")
+# the RT_PLANE_* bits of the packed planes format (rt_mi355x.h: "packed planes"), in the order of its sections behind the records
+PLANE_BITS = {"linear": 1, "normal": 2, "albedo": 4, "alpha": 8, "object_id": 16, "variance": 32}
+PACKED_SECTIONS = ("records", "normal", "albedo", "alpha", "object_id", "variance")
 
 
 class SetupMs(C.Structure):
@@ -187,6 +190,7 @@ SYMBOLS = [
     "rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion",
     "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
     "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
+    "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -282,6 +286,12 @@ def lib():
         _lib.rt_tonemap_device.argtypes = [vp, C.c_int, vp, i32, i32, vp, vp, C.c_int]
         _lib.rt_tonemap.argtypes = [vp, C.c_int, i32, i32, vp, vp]
         for name in ("rt_exposure_create", "rt_exposure_reset", "rt_exposure_get", "rt_exposure_histogram", "rt_tonemap_device", "rt_tonemap"):
+            getattr(_lib, name).restype = C.c_int
+        # the packed planes of the multi-GPU exchange (rt_mi355x.h: "packed planes")
+        _lib.rt_tiles_packed_planes_size.argtypes = [i32, i32, vp, C.c_uint32, vp, vp, vp]
+        _lib.rt_render_tiles_packed_outputs_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_uint64, C.c_uint32, C.c_int, vp]
+        _lib.rt_tiles_unpack_outputs_device.argtypes = [C.c_int, vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp]
+        for name in ("rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device"):
             getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
@@ -384,6 +394,39 @@ def tiles_unpack_device(device, stream, gathered_ptr, world, tiles_per_rank, wid
         _check(lib().rt_tiles_unpack_device(*args))
     else:
         _check(lib().rt_tiles_unpack_linear_device(*args, C.c_void_p(linear_ptr)))
+
+
+def plane_mask(planes):
+    """the RT_PLANE_* mask of plane names (those of Scene.render_outputs)"""
+    mask = 0
+    for name in planes:
+        mask |= PLANE_BITS[name]            # KeyError: no such plane
+    return mask
+
+
+def tiles_packed_planes_size(width, height, tiles, planes=()):
+    """One rank's contribution in the packed planes format (rt_tiles_packed_planes_size): (bytes, tiles per rank, offsets) --
+    offsets: section name ("records", then the plane names) -> its byte offset in the contribution, None for a plane that is
+    not in `planes`.  Sized by the per-rank tile count of tiles.stride ranks, so neither depends on tiles.first."""
+    nbytes, n, off = C.c_uint64(), C.c_int32(), (C.c_uint64 * 6)()
+    _check(lib().rt_tiles_packed_planes_size(int(width), int(height), C.byref(tiles), plane_mask(planes), C.byref(nbytes), C.byref(n), off))
+    return nbytes.value, n.value, {name: (None if o == 2 ** 64 - 1 else o) for name, o in zip(PACKED_SECTIONS, off)}
+
+
+def tiles_unpack_outputs_device(device, stream, gathered_ptr, world, tiles_per_rank, width, height, tile_w, tile_h, rgb_ptr, z_ptr, cnt_ptr,
+                                planes=None, linear_ptr=None, normal_ptr=None, albedo_ptr=None, alpha_ptr=None, object_id_ptr=None,
+                                variance_ptr=None):
+    """gathered contributions of `world` ranks in the packed planes format -> image-sized DEVICE planes, one HIP kernel on
+    `stream` (as tiles_unpack_device).  planes: the names the contributions were rendered with; None = those whose *_ptr is
+    given.  A plane in `planes` without a pointer is refused; a pointer whose plane is not in `planes` is left untouched."""
+    ptrs = dict(linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, alpha=alpha_ptr, object_id=object_id_ptr, variance=variance_ptr)
+    if planes is None:
+        planes = [k for k, v in ptrs.items() if v is not None]
+    o = Outputs(rgb8=rgb_ptr, z=z_ptr, count=cnt_ptr, rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, alpha=alpha_ptr,
+                object_id=object_id_ptr)
+    _check(lib().rt_tiles_unpack_outputs_device(int(device), _stream_handle(stream), C.c_void_p(gathered_ptr), int(world), int(tiles_per_rank),
+                                                int(width), int(height), int(tile_w), int(tile_h), plane_mask(planes), C.byref(o),
+                                                C.c_void_p(variance_ptr) if variance_ptr is not None else None))
 
 
 def image_write_pfm(path, rgb):
@@ -1159,6 +1202,17 @@ class Scene:
         _check(fn(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device), handle,
                   C.c_void_p(packed_ptr), C.c_uint64(int(packed_bytes)), 1 if sync else 0,
                   C.byref(st) if want_stats else None))
+        return st
+
+    def render_tiles_packed_outputs_device(self, cam, params, tiles, device, packed_ptr, packed_bytes, stream=None, sync=True,
+                                           want_stats=True, planes=()):
+        """render_tiles_packed_device with the planes named in `planes` (those of render_outputs) as sections behind the records:
+        one rank's contribution in the packed planes format, tiles_packed_planes_size(..., planes) bytes.  Slots of no pixel are
+        zeroed by the call."""
+        st = Stats()
+        _check(lib().rt_render_tiles_packed_outputs_device(self._h, C.byref(cam), C.byref(params), C.byref(tiles), int(device),
+                                                           _stream_handle(stream), C.c_void_p(packed_ptr), C.c_uint64(int(packed_bytes)),
+                                                           plane_mask(planes), 1 if sync else 0, C.byref(st) if want_stats else None))
         return st
 
     def render_counters(self, device=0, reset=False):

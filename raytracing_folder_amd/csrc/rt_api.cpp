@@ -1623,10 +1623,15 @@ struct TileWalk {
 // What one render call writes, and how: image-sized device planes (`dev`; rgb_linear selects the linear plane, the features
 // k_features), or packed records of the call's tiles (`packed`: rec_bytes 8, or 24 with the linear plane).  A strided job
 // (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature / variance staging planes of its own.
+// Packed planes (rt_render_tiles_packed_outputs_device): `walk` names the sections of the caller's buffer behind the records --
+// PL_NORMAL .. PL_VARIANCE, indexed by the call's tile walk like the records -- and packed_bytes is the whole contribution:
+// what lies behind the records of the call's own tiles is zeroed in stream order before any kernel writes into it.
 struct RenderRequest {
     Planes dev;
     void *packed = nullptr;
     size_t rec_bytes = 8;
+    Planes walk;
+    uint64_t packed_bytes = 0;          // packed planes only; 0: the packed entry points as they were
     hipStream_t stream = nullptr;       // the caller's stream; NULL: the device's own
     bool sync = true;
     rt_stats *stats_out = nullptr;
@@ -1737,7 +1742,7 @@ struct RenderAttempt {
         // the render's mode is the scene's flags as they are now: kernels enqueued by this call keep it whatever is set later
         reproducible = (s->render_flags.load() & RT_RENDER_REPRODUCIBLE) != 0;
         // first-hit feature planes (k_features after each chunk's last resolve): only when a plane was asked for
-        features = (job ? job->host : req.dev).features().any();
+        features = (job ? job->host : req.packed ? req.walk : req.dev).features().any();
     }
 
     // A working set per slot; the attempt goes on with as many as it got.
@@ -1795,6 +1800,11 @@ struct RenderAttempt {
             }
             if (feat_by_walk) fdev = staged.features();
             variance_dev = staged.at<float>(PL_VARIANCE);
+        } else if (packed_dev) {
+            // packed planes: the same two pointers, re-aimed into the sections of the caller's buffer
+            fdev = req.walk.features();
+            feat_by_walk = features;
+            variance_dev = req.walk.at<float>(PL_VARIANCE);
         }
         return RT_OK;
     }
@@ -1804,6 +1814,12 @@ struct RenderAttempt {
     rt_status begin_on_stream()
     {
         rt_status st;
+        // packed planes: k_resolve writes (zeros included) the records of the call's own tiles, k_features and the variance only
+        // the slots of image pixels; everything else of the contribution -- the records of a short rank's missing tile, every
+        // section, the rounding -- starts from zero on every call
+        const uint64_t written = total_px * rec_bytes;
+        if (req.packed_bytes > written)
+            HIP_TRY(hipMemsetAsync((uint8_t *)req.packed + written, 0, req.packed_bytes - written, stream));
         if (want_stats) {
             HIP_TRY(stats_zero(Ws[0].stats, 0, ST_COUNT, stream));
             HIP_TRY(e_begin.create()); HIP_TRY(e_end.create());
@@ -2149,6 +2165,102 @@ extern "C" rt_status rt_render_tiles_packed_linear_device(rt_scene *s, const rt_
 {
     return render_packed("rt_render_tiles_packed_linear_device", s, cam, p, tiles, device, hip_stream, packed_dev, packed_bytes, sync,
                          stats_out, true);
+}
+
+// ---- packed planes (rt_mi355x.h, "packed planes") ----
+static const uint32_t RT_PLANE_ALL = RT_PLANE_LINEAR | RT_PLANE_NORMAL | RT_PLANE_ALBEDO | RT_PLANE_ALPHA | RT_PLANE_OBJECT_ID | RT_PLANE_VARIANCE;
+// the sections behind the records, in buffer order: mask bit and plane
+static const struct { uint32_t bit; Plane plane; } PACKED_SECTIONS[5] = {
+    {RT_PLANE_NORMAL, PL_NORMAL}, {RT_PLANE_ALBEDO, PL_ALBEDO}, {RT_PLANE_ALPHA, PL_ALPHA}, {RT_PLANE_OBJECT_ID, PL_ID}, {RT_PLANE_VARIANCE, PL_VARIANCE}};
+
+// one contribution of `per_rank` tiles of tile_px pixels: its bytes and the offsets of the six sections (UINT64_MAX: absent)
+static uint64_t packed_planes_layout(uint64_t per_rank, uint64_t tile_px, uint32_t mask, uint64_t off[6])
+{
+    const uint64_t Q = per_rank * tile_px;
+    uint64_t at = Q * ((mask & RT_PLANE_LINEAR) ? 24u : 8u);
+    off[0] = 0;
+    for (int i = 0; i < 5; i++) {
+        const bool on = (mask & PACKED_SECTIONS[i].bit) != 0;
+        off[1 + i] = on ? at : UINT64_MAX;
+        if (on) at += Q * PLANE_BYTES[PACKED_SECTIONS[i].plane];
+    }
+    return (at + 15u) & ~(uint64_t)15u;
+}
+
+extern "C" rt_status rt_tiles_packed_planes_size(int32_t width, int32_t height, const rt_tile_range *t, uint32_t mask,
+                                                 uint64_t *bytes, int32_t *n_tiles, uint64_t section_offsets[6])
+{
+    if (!t || !bytes || width <= 0 || height <= 0 || t->tile_w <= 0 || t->tile_h <= 0 || t->stride <= 0 || t->first < 0)
+        return fail(RT_ERR_ARG, "rt_tiles_packed_planes_size: bad argument");
+    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "rt_tiles_packed_planes_size: unknown plane bits 0x%x", mask & ~RT_PLANE_ALL);
+    const int64_t tiles_x = (width + t->tile_w - 1) / t->tile_w, tiles_y = (height + t->tile_h - 1) / t->tile_h;
+    const int64_t per_rank = (tiles_x * tiles_y + t->stride - 1) / t->stride;
+    uint64_t off[6];
+    *bytes = packed_planes_layout((uint64_t)per_rank, (uint64_t)t->tile_w * (uint64_t)t->tile_h, mask, off);
+    if (n_tiles) *n_tiles = (int32_t)per_rank;
+    if (section_offsets) memcpy(section_offsets, off, sizeof off);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_render_tiles_packed_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
+                                                           int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, uint32_t mask,
+                                                           int sync, rt_stats *stats_out)
+{
+    const char *name = "rt_render_tiles_packed_outputs_device";
+    if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", name);
+    if (!packed_dev) return fail(RT_ERR_ARG, "%s: the packed buffer is required", name);
+    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "%s: unknown plane bits 0x%x", name, mask & ~RT_PLANE_ALL);
+    rt_status st = validate_render(s, cam, p, tiles);
+    if (st) return st;
+    uint64_t need = 0, off[6];
+    if ((st = rt_tiles_packed_planes_size(cam->width, cam->height, tiles, mask, &need, nullptr, off))) return st;
+    if (packed_bytes < need) return fail(RT_ERR_ARG, "%s: buffer of %llu bytes, a contribution with these planes needs %llu", name,
+                                         (unsigned long long)packed_bytes, (unsigned long long)need);
+    RenderRequest req;
+    req.packed = packed_dev; req.rec_bytes = (mask & RT_PLANE_LINEAR) ? 24 : 8;
+    req.packed_bytes = need;
+    for (int i = 0; i < 5; i++)
+        if (mask & PACKED_SECTIONS[i].bit) req.walk.p[PACKED_SECTIONS[i].plane] = (uint8_t *)packed_dev + off[1 + i];
+    req.stream = (hipStream_t)hip_stream; req.sync = sync != 0; req.stats_out = stats_out;
+    return render_tiles(s, cam, p, tiles, device, req);
+}
+
+extern "C" rt_status rt_tiles_unpack_outputs_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
+                                                    int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, uint32_t mask,
+                                                    const rt_outputs *device_planes, float *variance_dev)
+{
+    const char *name = "rt_tiles_unpack_outputs_device";
+    if (!gathered_dev) return fail(RT_ERR_ARG, "%s: NULL buffer", name);
+    if ((uintptr_t)gathered_dev & 15u) return fail(RT_ERR_ARG, "%s: the gathered buffer must be 16-byte aligned", name);
+    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "%s: unknown plane bits 0x%x", name, mask & ~RT_PLANE_ALL);
+    rt_status st = check_outputs(name, device_planes);
+    if (st) return st;
+    const Planes dst(*device_planes, variance_dev);
+    if ((mask & RT_PLANE_LINEAR) && !dst.p[PL_LINEAR]) return fail(RT_ERR_ARG, "%s: the linear plane is in the mask and has no destination", name);
+    for (int i = 0; i < 5; i++)
+        if ((mask & PACKED_SECTIONS[i].bit) && !dst.p[PACKED_SECTIONS[i].plane])
+            return fail(RT_ERR_ARG, "%s: plane bit 0x%x is in the mask and has no destination", name, PACKED_SECTIONS[i].bit);
+    if (world <= 0 || width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0) return fail(RT_ERR_ARG, "%s: bad geometry", name);
+    const int64_t total = (int64_t)((width + tile_w - 1) / tile_w) * ((height + tile_h - 1) / tile_h);
+    if ((int64_t)tiles_per_rank * world < total || tiles_per_rank < (total + world - 1) / world)
+        return fail(RT_ERR_ARG, "%s: %d tiles per rank x %d ranks cannot hold %lld tiles", name, tiles_per_rank, world, (long long)total);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+    HIP_TRY(hipSetDevice(device));
+    uint64_t off[6];
+    UnpackPlanesRequest u = {};
+    u.rank_bytes = packed_planes_layout((uint64_t)tiles_per_rank, (uint64_t)tile_w * (uint64_t)tile_h, mask, off);
+    u.gathered = gathered_dev; u.world = world; u.per_rank = tiles_per_rank; u.width = width; u.height = height; u.tile_w = tile_w; u.tile_h = tile_h;
+    u.rgb8 = dst.at<uint8_t>(PL_RGB8); u.z = dst.at<float>(PL_Z); u.count = dst.at<uint8_t>(PL_COUNT);
+    // a destination outside the mask is not the kernel's business: it sees NULL there
+    if (mask & RT_PLANE_LINEAR) u.rgb_linear = dst.at<float>(PL_LINEAR);
+    if (mask & RT_PLANE_NORMAL) { u.normal = dst.at<float>(PL_NORMAL); u.off_normal = off[1]; }
+    if (mask & RT_PLANE_ALBEDO) { u.albedo = dst.at<float>(PL_ALBEDO); u.off_albedo = off[2]; }
+    if (mask & RT_PLANE_ALPHA) { u.alpha = dst.at<float>(PL_ALPHA); u.off_alpha = off[3]; }
+    if (mask & RT_PLANE_OBJECT_ID) { u.object_id = dst.at<int32_t>(PL_ID); u.off_object_id = off[4]; }
+    if (mask & RT_PLANE_VARIANCE) { u.variance = dst.at<float>(PL_VARIANCE); u.off_variance = off[5]; }
+    rtk_launch_unpack_planes((hipStream_t)hip_stream, u);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 extern "C" rt_status rt_tiles_packed_size(int32_t width, int32_t height, const rt_tile_range *t, uint64_t *bytes, int32_t *n_tiles)

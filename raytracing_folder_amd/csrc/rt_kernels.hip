@@ -2356,6 +2356,105 @@ void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R)
                            R.height, R.tile_w, R.tile_h, tiles_x, R.rgb8, R.z, R.count, nullptr);
 }
 
+// Un-interleave an all-gathered frame in the packed planes format (rt_mi355x.h, "packed planes"): k_unpack_tiles' walk over
+// the image, with the records AND every plane section of the mask moved in the same pass -- up to 68 bytes read and 68 written
+// per pixel, nothing computed: HBM streaming.  A pixel's slot q (tile k of its rank, row-major inside the tile) is the same in
+// every section, so one index serves all of them; a section the request has no destination for costs one uniform branch.
+//   V4: one thread per FOUR pixels of an image row.  With width and tile_w multiples of 4 the four lie in one tile row, so
+//       they are 4 consecutive slots: 96 (32) bytes of records, 48 of each 12-byte plane, 16 of alpha and of the ids, all
+//       16-byte aligned at both ends -- dwordx4 loads and stores only, lanes side by side (a wave moves 6 KB of a 24-byte
+//       record run, 3 KB of a 12-byte plane per instruction triple).  rgb8 and count leave as 3 + 1 packed dwords.
+//   otherwise (any geometry, any 4-byte-aligned planes): one thread per pixel, 8-byte record loads like k_unpack_tiles and
+//       dword loads for the sections.
+// LIN: 24-byte records and the linear plane.
+template <bool V4, bool LIN>
+__global__ __launch_bounds__(256) void k_unpack_planes(UnpackPlanesRequest R, int tiles_x)
+{
+    constexpr int PX = V4 ? 4 : 1, RW = LIN ? 6 : 2;                // pixels per thread; 32-bit words per record
+    const int tile_px = R.tile_w * R.tile_h;
+    const size_t n = (size_t)R.width * R.height / PX;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = g * PX;                                     // the thread's first pixel
+        const int y = (int)(i / (size_t)R.width), x = (int)(i - (size_t)y * R.width);
+        const int tx = x / R.tile_w, ty = y / R.tile_h;
+        const int t = ty * tiles_x + tx;
+        const int r = t % R.world, k = t / R.world;
+        const size_t q = (size_t)k * tile_px + (size_t)(y - ty * R.tile_h) * R.tile_w + (x - tx * R.tile_w);
+        const uint8_t *base = (const uint8_t *)R.gathered + (size_t)r * R.rank_bytes;
+        if constexpr (V4) {
+            uint32_t w[4 * RW];
+            const uint4 *rec = (const uint4 *)(base + (size_t)(4 * RW) * q);
+#pragma unroll
+            for (int j = 0; j < RW; j++) { const uint4 v = rec[j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
+            const uint32_t c0 = w[0] & 0xFFFFFFu, c1 = w[RW] & 0xFFFFFFu, c2 = w[2 * RW] & 0xFFFFFFu, c3 = w[3 * RW] & 0xFFFFFFu;
+            uint32_t *rgb = (uint32_t *)(R.rgb8 + 3 * i);
+            rgb[0] = c0 | (c1 << 24); rgb[1] = (c1 >> 8) | (c2 << 16); rgb[2] = (c2 >> 16) | (c3 << 8);
+            *(uint4 *)(R.z + i) = make_uint4((w[0] >> 24) | (w[1] << 8), (w[RW] >> 24) | (w[RW + 1] << 8),
+                                             (w[2 * RW] >> 24) | (w[2 * RW + 1] << 8), (w[3 * RW] >> 24) | (w[3 * RW + 1] << 8));
+            *(uint32_t *)(R.count + i) = (w[1] >> 24) | ((w[RW + 1] >> 24) << 8) | ((w[2 * RW + 1] >> 24) << 16) | ((w[3 * RW + 1] >> 24) << 24);
+            if constexpr (LIN) {
+                uint4 *lin = (uint4 *)(R.rgb_linear + 3 * i);
+                lin[0] = make_uint4(w[2], w[3], w[4], w[8]);
+                lin[1] = make_uint4(w[9], w[10], w[14], w[15]);
+                lin[2] = make_uint4(w[16], w[20], w[21], w[22]);
+            }
+            auto move48 = [&](uint64_t off, float *dst) {            // four slots of a 12-byte plane
+                const uint4 *src = (const uint4 *)(base + off + 12 * q);
+                const uint4 a = src[0], b = src[1], c = src[2];
+                uint4 *d = (uint4 *)(dst + 3 * i);
+                d[0] = a; d[1] = b; d[2] = c;
+            };
+            if (R.normal) move48(R.off_normal, R.normal);
+            if (R.albedo) move48(R.off_albedo, R.albedo);
+            if (R.alpha) *(uint4 *)(R.alpha + i) = *(const uint4 *)(base + R.off_alpha + 4 * q);
+            if (R.object_id) *(uint4 *)(R.object_id + i) = *(const uint4 *)(base + R.off_object_id + 4 * q);
+            if (R.variance) move48(R.off_variance, R.variance);
+        } else {
+            const uint2 *rec = (const uint2 *)(base + (size_t)(4 * RW) * q);
+            const uint2 v = rec[0];
+            R.rgb8[3 * i] = (uint8_t)(v.x & 255u); R.rgb8[3 * i + 1] = (uint8_t)((v.x >> 8) & 255u); R.rgb8[3 * i + 2] = (uint8_t)((v.x >> 16) & 255u);
+            R.z[i] = __uint_as_float((v.x >> 24) | (v.y << 8));
+            R.count[i] = (uint8_t)(v.y >> 24);
+            if constexpr (LIN) {
+                const uint2 a = rec[1], b = rec[2];
+                R.rgb_linear[3 * i] = __uint_as_float(a.x); R.rgb_linear[3 * i + 1] = __uint_as_float(a.y); R.rgb_linear[3 * i + 2] = __uint_as_float(b.x);
+            }
+            auto move12 = [&](uint64_t off, float *dst) {
+                const uint32_t *src = (const uint32_t *)(base + off + 12 * q);
+                const uint32_t a = src[0], b = src[1], c = src[2];
+                uint32_t *d = (uint32_t *)(dst + 3 * i);
+                d[0] = a; d[1] = b; d[2] = c;
+            };
+            if (R.normal) move12(R.off_normal, R.normal);
+            if (R.albedo) move12(R.off_albedo, R.albedo);
+            if (R.alpha) *(uint32_t *)(R.alpha + i) = *(const uint32_t *)(base + R.off_alpha + 4 * q);
+            if (R.object_id) *(uint32_t *)(R.object_id + i) = *(const uint32_t *)(base + R.off_object_id + 4 * q);
+            if (R.variance) move12(R.off_variance, R.variance);
+        }
+    }
+}
+
+void rtk_launch_unpack_planes(hipStream_t st, const UnpackPlanesRequest &R)
+{
+    const int tiles_x = (R.width + R.tile_w - 1) / R.tile_w;
+    // the 4-pixel instantiation needs every 4-pixel group inside one tile row and every access 16-byte aligned: the section
+    // offsets and rank_bytes are multiples of 16 once tile_w is a multiple of 4, the planes are the caller's
+    auto aligned16 = [](const void *p) { return ((uintptr_t)p & 15u) == 0; };
+    const bool v4 = R.width % 4 == 0 && R.tile_w % 4 == 0 && R.rank_bytes % 16 == 0 && aligned16(R.gathered) && aligned16(R.rgb8) && aligned16(R.z) &&
+                    aligned16(R.count) && aligned16(R.rgb_linear) && aligned16(R.normal) && aligned16(R.albedo) && aligned16(R.alpha) &&
+                    aligned16(R.object_id) && aligned16(R.variance);
+    const size_t n = (size_t)R.width * R.height / (v4 ? 4 : 1);
+    // a streaming copy: enough workgroups to fill 256 CUs eight deep, a grid stride beyond that
+    const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048))), block(256);
+    if (v4) {
+        if (R.rgb_linear) hipLaunchKernelGGL((k_unpack_planes<true, true>), grid, block, 0, st, R, tiles_x);
+        else hipLaunchKernelGGL((k_unpack_planes<true, false>), grid, block, 0, st, R, tiles_x);
+    } else {
+        if (R.rgb_linear) hipLaunchKernelGGL((k_unpack_planes<false, true>), grid, block, 0, st, R, tiles_x);
+        else hipLaunchKernelGGL((k_unpack_planes<false, false>), grid, block, 0, st, R, tiles_x);
+    }
+}
+
 void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &R, int max_blocks, bool linear)
 {
     assert(!linear || R.rgb_linear || R.packed);     // the LIN instantiation writes the linear plane, or 24-byte records into `packed`

@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip): every rtk_* function, the requests they take and the
-// records they exchange.  All eight files include it, so a declaration and its definition cannot drift apart.  ResolveArgs and PhotonArgs are passed to kernels
+// records they exchange.  All eight files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -77,6 +77,18 @@ struct TraceOut { uint8_t *hit; float *z, *p, *N; int32_t *node; uint8_t *front;
 struct UnpackRequest {
     const void *gathered; int world, per_rank, width, height, tile_w, tile_h;
     uint8_t *rgb8; float *z; uint8_t *count; float *rgb_linear;
+};
+
+// an all-gathered frame in the packed planes format (rt_mi355x.h, "packed planes") to un-interleave: rank r's contribution at
+// gathered + r * rank_bytes; in it the records (24-byte ones when rgb_linear is set, else 8-byte ones) at 0 and the section of
+// each plane whose destination is set at its offset (bytes, from the contribution's start).  Destinations that are NULL are not
+// in the mask: nothing is read or written for them.
+struct UnpackPlanesRequest {
+    const void *gathered; uint64_t rank_bytes;
+    int world, per_rank, width, height, tile_w, tile_h;
+    uint8_t *rgb8; float *z; uint8_t *count; float *rgb_linear;
+    float *normal, *albedo, *alpha; int32_t *object_id; float *variance;
+    uint64_t off_normal, off_albedo, off_alpha, off_object_id, off_variance;
 };
 
 // One denoise of a width x height frame (rt_denoise.hip; the definition: rt_mi355x.h, "denoising").  The planes are the caller's
@@ -166,6 +178,9 @@ void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *f
 // instantiation -- the linear plane A.rgb_linear, or 24-byte records when A.packed is set.  A.variance selects the VAR one.
 void rtk_launch_resolve(hipStream_t st, const DevWork &W, const ResolveArgs &A, int max_blocks, bool linear);
 void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R);
+// k_unpack_planes: one pass over the image that moves the records and every section of R (the 4-pixel instantiation when the
+// geometry keeps every access 16-byte aligned, else one pixel per thread)
+void rtk_launch_unpack_planes(hipStream_t st, const UnpackPlanesRequest &R);
 // The feature planes of one chunk (pass.cam, tiles, q0, npix), after its last k_resolve on the same stream: the second-batch
 // flags from the chunk's pixel list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when
 // features are on); by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by

@@ -1,0 +1,188 @@
+"""The packed planes format of the multi-GPU tile exchange (include/rt_mi355x.h, "packed planes") on the CPU: the C ABI's size
+query against the torch helpers of raytracing_folder_amd/dist.py, the helpers' round trip in one process and under gloo, and
+the argument errors that need no device.  tests/test_packed_planes_gpu.py holds the HIP side to the same helpers."""
+import ctypes as C
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+from raytracing_folder_amd import capi
+from raytracing_folder_amd import dist as rtd
+
+W, H = 100, 37          # ragged in both directions: 4 x 5 = 20 tiles of 32 x 8
+ALL = rtd.ALL_PLANES
+MASKS = ((), ("linear",), ALL, ("alpha", "object_id"), ("variance",))
+
+
+def _frame(w=W, h=H, seed=5):
+    """a random frame with every plane, no value zero (so that a zero in a packed buffer is a slot of no pixel)"""
+    rng = np.random.default_rng(seed)
+    f = {"rgb": rng.integers(1, 256, (h, w, 3), dtype=np.uint8), "z": rng.uniform(1, 100, (h, w)).astype(np.float32),
+         "count": rng.integers(1, 256, (h, w), dtype=np.uint8), "alpha": rng.uniform(0.1, 1, (h, w)).astype(np.float32),
+         "object_id": rng.integers(1, 1000, (h, w), dtype=np.int32)}
+    for name in ("linear", "normal", "albedo", "variance"):
+        f[name] = rng.uniform(0.5, 2, (h, w, 3)).astype(np.float32)
+    return {k: torch.from_numpy(v) for k, v in f.items()}
+
+
+def _same_frame(got, want, planes):
+    for name in ("rgb", "z", "count") + tuple(planes):
+        a, b = got[name], want[name]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.numpy().tobytes() == b.numpy().tobytes(), name
+    assert set(got) == {"rgb", "z", "count"} | set(planes)
+
+
+def test_size_query_agrees_with_the_torch_helpers():
+    for (w, h) in ((100, 37), (64, 48), (33, 9)):
+        _, _, n = rtd.tile_grid(w, h)
+        for world in (1, 2, 3, 8):
+            per_rank = (n + world - 1) // world
+            for planes in MASKS:
+                want = rtd.planes_layout(w, h, world, planes)
+                assert want[1] == per_rank
+                for first in range(world):
+                    nbytes, k, off = capi.tiles_packed_planes_size(w, h, capi.TileRange(32, 8, first, world), planes)
+                    assert (nbytes, k, off) == want, (w, h, world, planes, first)     # in particular: no offset moves with `first`
+                    assert off["records"] == 0 and all((off[p] is not None) == (p in planes) for p in rtd.PLANE_SECTIONS)
+                    if planes == ():
+                        assert nbytes == per_rank * 256 * 8
+                    if planes == ("linear",):
+                        assert nbytes == per_rank * 256 * 24
+                # the helper's buffer is of that size, and its sections follow one another without gaps
+                if (w, h) == (100, 37):
+                    assert rtd.pack_own_planes(_frame(), world - 1, world, planes).numel() == want[0]
+                present = ["records"] + [p for p in rtd.PLANE_SECTIONS if p in planes]
+                size = dict(rtd.PLANE_BYTES, records=24 if "linear" in planes else 8)
+                at = 0
+                for p in present:
+                    assert want[2][p] == at
+                    at += per_rank * 256 * size[p]
+                assert want[0] == at                  # 256-pixel tiles: nothing is added by the rounding to 16
+
+
+def test_odd_tiles_round_the_contribution_up_to_16_bytes():
+    # 3 x 3 tiles on 7 x 5: 6 tiles; 4 ranks -> 2 each, 18 slots: 8 * 18 + 4 * 18 = 216 -> 224
+    nbytes, k, off = capi.tiles_packed_planes_size(7, 5, capi.TileRange(3, 3, 1, 4), ("alpha",))
+    assert (nbytes, k, off["alpha"]) == (224, 2, 144)
+    assert rtd.planes_layout(7, 5, 4, ("alpha",), 3, 3) == (nbytes, k, off)
+    f = _frame(7, 5)
+    packs = torch.stack([rtd.pack_own_planes(f, r, 4, ("alpha",), 3, 3) for r in range(4)])
+    assert packs.shape == (4, 224) and (packs[:, 216:] == 0).all()
+    _same_frame(rtd.unpack_gathered_planes(packs, 7, 5, 4, ("alpha",), 3, 3), f, ("alpha",))
+
+
+def _zero_slots_are_zero(pack, rank, world, planes, w=W, h=H):
+    """every slot of `pack` that belongs to no pixel of the rank's tiles is zero, every other one is not (the frame has no zeros)"""
+    nbytes, per_rank, off = rtd.planes_layout(w, h, world, planes)
+    tx, ty, n = rtd.tile_grid(w, h)
+    live = np.zeros((per_rank, 8, 32), bool)
+    for k, t in enumerate(range(rank, n, world)):
+        x0, y0 = (t % tx) * 32, (t // tx) * 8
+        live[k, :max(0, min(8, h - y0)), :max(0, min(32, w - x0))] = True
+    live = live.reshape(-1)
+    raw = pack.numpy()
+    size = dict(rtd.PLANE_BYTES, records=24 if "linear" in planes else 8)
+    for name in ["records"] + [p for p in rtd.PLANE_SECTIONS if p in planes]:
+        sec = raw[off[name]: off[name] + live.size * size[name]].reshape(live.size, size[name])
+        assert (sec[~live] == 0).all(), name
+        assert sec[live].any(axis=1).all(), name
+    return int((~live).sum())
+
+
+@pytest.mark.parametrize("world,shares", [(3, (7, 7, 6)), (8, (3, 3, 3, 3, 2, 2, 2, 2))])
+def test_round_trip_and_zero_slots(world, shares):
+    f = _frame()
+    _, _, n = rtd.tile_grid(W, H)
+    assert n == 20 and tuple(len(rtd.tiles_of_rank(r, world, n)) for r in range(world)) == shares
+    for planes in MASKS:
+        packs = [rtd.pack_own_planes(f, r, world, planes) for r in range(world)]
+        dead = [_zero_slots_are_zero(p, r, world, planes) for r, p in enumerate(packs)]
+        assert all(d > 0 for d in dead)                                  # ragged tiles on every rank
+        assert all(d >= 256 for d, k in zip(dead, shares) if k < max(shares))      # the short ranks' whole last tile
+        _same_frame(rtd.unpack_gathered_planes(torch.stack(packs), W, H, world, planes), f, planes)
+        # a flat gathered buffer reads the same
+        _same_frame(rtd.unpack_gathered_planes(torch.cat(packs), W, H, world, planes), f, planes)
+    # the records section is the existing helpers' buffer
+    old = rtd.pack_own_tiles(f["rgb"], f["z"], f["count"], 1, world).reshape(-1)
+    assert rtd.pack_own_planes(f, 1, world, ("normal",))[: old.numel()].numpy().tobytes() == old.numpy().tobytes()
+
+
+def _worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.set_num_threads(1)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    f = _frame()
+    mine = rtd.pack_own_planes(f, rank, world, ALL)
+    gathered = torch.empty(world * mine.numel(), dtype=torch.uint8)
+    dist.all_gather_into_tensor(gathered, mine)
+    got = rtd.unpack_gathered_planes(gathered, W, H, world, ALL)
+    ok = all(got[k].numpy().tobytes() == f[k].numpy().tobytes() for k in f)
+    q.put((rank, ok))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_round_trip_under_gloo(world):
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=120) for _ in procs]
+    for p in procs:
+        p.join(60)
+    assert sorted(r for r, _ in res) == list(range(world)) and all(ok for _, ok in res)
+
+
+def test_argument_errors_that_need_no_device():
+    L = capi.lib()
+    t = capi.TileRange(32, 8, 0, 3)
+    nbytes, n, off = C.c_uint64(7), C.c_int32(7), (C.c_uint64 * 6)(*([7] * 6))
+    assert L.rt_tiles_packed_planes_size(W, H, C.byref(t), 64, C.byref(nbytes), C.byref(n), off) == -1        # unknown bit
+    assert b"unknown plane bits" in L.rt_last_error()
+    assert L.rt_tiles_packed_planes_size(W, H, C.byref(t), 0x80000000, C.byref(nbytes), C.byref(n), off) == -1
+    assert L.rt_tiles_packed_planes_size(W, H, C.byref(t), 63, None, None, None) == -1                         # NULL size outputs
+    assert L.rt_tiles_packed_planes_size(W, H, None, 63, C.byref(nbytes), C.byref(n), off) == -1
+    assert L.rt_tiles_packed_planes_size(0, H, C.byref(t), 63, C.byref(nbytes), C.byref(n), off) == -1
+    assert (nbytes.value, n.value, list(off)) == (7, 7, [7] * 6)                                              # a refused call writes nothing
+    # only `bytes` is required
+    assert L.rt_tiles_packed_planes_size(W, H, C.byref(t), 63, C.byref(nbytes), None, None) == 0
+    assert nbytes.value == 7 * 256 * 68
+    with pytest.raises(KeyError):
+        capi.tiles_packed_planes_size(W, H, t, ("depth",))
+    with pytest.raises(KeyError):
+        rtd.planes_layout(W, H, 3, ("depth",))
+    # the render and the unpack refuse a bad mask and a missing buffer before they look for a device
+    from tests import scenes
+    s, cam = scenes.load_cornell(64, 48)
+    p = capi.default_params()
+    buf = np.zeros(1 << 16, np.uint8)
+    t1 = capi.TileRange(32, 8, 0, 1)
+    args = (s._h, C.byref(cam), C.byref(p), C.byref(t1), 0, None)
+    assert L.rt_render_tiles_packed_outputs_device(*args, capi._p(buf), buf.size, 64, 1, None) == -1
+    assert L.rt_render_tiles_packed_outputs_device(*args, None, buf.size, 63, 1, None) == -1
+    assert L.rt_render_tiles_packed_outputs_device(*args, capi._p(buf), 12 * 256 * 68 - 1, 63, 1, None) == -1
+    assert b"needs" in L.rt_last_error()
+    assert (buf == 0).all()
+    o = capi.Outputs(rgb8=buf.ctypes.data, z=buf.ctypes.data, count=buf.ctypes.data)
+    geo = (1, 12, 64, 48, 32, 8)
+    assert L.rt_tiles_unpack_outputs_device(0, None, capi._p(buf), *geo, 64, C.byref(o), None) == -1
+    assert L.rt_tiles_unpack_outputs_device(0, None, capi._p(buf), *geo, 32, C.byref(o), None) == -1             # variance, no destination
+    assert b"no destination" in L.rt_last_error()
+    assert L.rt_tiles_unpack_outputs_device(0, None, capi._p(buf), *geo, 2, C.byref(o), None) == -1              # normal, no destination
+    assert L.rt_tiles_unpack_outputs_device(0, None, None, *geo, 0, C.byref(o), None) == -1
+    assert L.rt_tiles_unpack_outputs_device(0, None, capi._p(buf), *geo, 0, None, None) == -1
