@@ -857,6 +857,65 @@ rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_
 rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p,
                              const rt_temporal_planes *host_planes, const float *motion);
 
+/* ---- history rectification (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above
+ *      are unchanged) ------------------------------------------------------------------------------------------------------
+ * "temporal accumulation" accepts a history tap on geometry alone (id, normal, depth): it is right only while the light a surface
+ * point sends to the camera does not change.  A light that moves or changes, what is seen IN a mirror or a glass surface under a
+ * moving camera, and a moving node's shadow on a static receiver all pass every geometric test and fade out at (1 - alpha)^k.
+ * rt_temporal_clip_* are rt_temporal / rt_temporal_motion with one more step between steps 4 and 5: the reprojected history
+ * colour is clamped into a box built from the CURRENT frame's neighbourhood (variance clipping), and a pixel whose history had to
+ * be clamped keeps only a short history length.  The reference has no counterpart.  Definition:
+ *   4b. For a pixel p = (x, y) that HAS A HISTORY (step 4), with r = radius:
+ *      Window pixels: the q with |qx - x| <= r and |qy - y| <= r.  A window pixel COUNTS when it lies inside the image, is VALID
+ *      (step 1), its demodulated colour d_q (step 1) is finite, and id_q == id_p; without an id plane every valid pixel with a
+ *      finite d_q counts.  p itself always counts (it has a history, so it is valid and finite).
+ *      Order: the window is visited row-major -- qy from y - r to y + r, inside a row qx from x - r to x + r -- and the pixels that
+ *      count are summed in that order, in float, in two passes: m = their number, mu_c = (sum d_q,c) / m, then
+ *      s2_c = (sum (d_q,c - mu_c)^2) / m (the mean first; never E[x^2] - mu^2).
+ *      m < min_count: the step does nothing (the pixel is KEPT).
+ *      Otherwise e_c = k_clip * sqrt(s2_c), lo_c = mu_c - e_c, hi_c = mu_c + e_c and d_h,c := min(max(d_h,c, lo_c), hi_c)
+ *      (fmaxf / fminf: a bound that is NaN -- sums that overflowed -- does not clamp).  p is CLIPPED iff that changed any
+ *      channel; for a clipped pixel N_h := min(N_h, clip_history) before N = min(N_h + 1, max_history).
+ *      u_h is left as it is.  The blend's variance u' = (1 - beta)^2 u_h + beta^2 u is then an APPROXIMATION for a clipped
+ *      pixel: the clamped history is a function of the current frame and no longer independent of it, and a clamp towards
+ *      the frame's own neighbourhood also changes the history's spread.  (The shortened N raises beta, so u' leans on the
+ *      frame's own u, which is exact.)
+ *   Everything else -- pass-through, the taps, the blend, the outputs and what is stored -- is steps 1-6 unchanged, with the
+ *   clamped d_h and the shortened N_h in step 5.  With a box so wide that nothing is clamped (k_clip = 1e9 on a noisy frame) the
+ *   outputs are those of rt_temporal / rt_temporal_motion to the byte.
+ * One more optional output, out_clipped (float W*H): 0 the pixel has no history (pass-through pixels included), 1 it has one and
+ * it was kept (also when m < min_count), 2 it was clipped.  rt_temporal_planes cannot grow, so the pointer travels in
+ * rt_temporal_clip, next to the parameters it reports on: a device plane for rt_temporal_clip_device, a host array for
+ * rt_temporal_clip_host, NULL = not wanted.  It may overlap no other plane.
+ * Rectification BOUNDS the error a changed light leaves in the history by the box; it does not track the light.  A stale value
+ * inside k_clip sigma of a noisy neighbourhood survives and fades at the blend's rate as before.
+ * out_linear may still be rgb_linear and out_variance `variance`.  The kernel reads the neighbours' rgb_linear, so for
+ * out_linear overlapping rgb_linear the library lets it write a plane the history owns (12 bytes a pixel, allocated by the first
+ * such call) and copies it to out_linear on the same stream; the bytes are those of the call with separate planes.  The costs:
+ * every such call -- rt_temporal_clip_host always, rt_temporal_clip_device in place -- pays that 12 B a pixel copy, the history
+ * keeps the plane until it is destroyed, and the FIRST such call on a history allocates device memory although it only
+ * enqueues (sync = 0): it must not be made while its stream is being captured into a graph.  With separate planes there is
+ * neither copy nor allocation.
+ * No atomics, a fixed window order, a fixed tap order: byte-identical outputs for an identical sequence of calls on one build.
+ * Checked before the GPU is touched, RT_ERR_ARG: a NULL clip, a struct_size that is not the caller's sizeof, radius outside
+ * 1..3, k_clip not positive and finite, min_count < 1, clip_history outside 1..65535 -- and every check of rt_temporal.  motion /
+ * motion_dev NULL: reproject with the cameras (rt_temporal); otherwise this frame's motion plane (rt_temporal_motion).  Calls
+ * with and without rectification may be mixed freely on one history. */
+typedef struct rt_temporal_clip {
+    uint32_t struct_size;
+    int32_t  radius;        /* 2   : window (2r+1)^2, 1..3                                  */
+    float    k_clip;        /* 1.5 : half-width of the box in standard deviations, > 0      */
+    int32_t  min_count;     /* 4   : fewer window pixels than this -> no rectification, >=1 */
+    int32_t  clip_history;  /* 2   : N_h of a clipped pixel is at most this, 1..65535       */
+    float   *out_clipped;   /* NULL: optional output, float W*H: 0 no history, 1 kept, 2 clipped */
+} rt_temporal_clip;
+void      rt_temporal_clip_default(rt_temporal_clip *c);
+rt_status rt_temporal_clip_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                  const rt_temporal_clip *clip, const rt_temporal_planes *device_planes,
+                                  const float *motion_dev /* NULL: reproject with the cameras */, int sync);
+rt_status rt_temporal_clip_host(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_clip *clip,
+                                const rt_temporal_planes *host_planes, const float *motion /* NULL allowed */);
+
 /* ---- exposure and tone mapping (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs
  *      above are unchanged) -------------------------------------------------------------------------------------------------
  * The last stage of the image-space pipeline: every stage above ends in Color24(powf(out_linear, 1/gamma)), the reference's hard

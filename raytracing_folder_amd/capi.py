@@ -99,6 +99,12 @@ class TemporalPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(TemporalPlanes), **planes)
 
 
+class TemporalClip(C.Structure):
+    """rt_temporal_clip: history rectification (rt_temporal_clip_default fills 2 / 1.5 / 4 / 2 and no out_clipped)"""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("k_clip", C.c_float), ("min_count", C.c_int32),
+                ("clip_history", C.c_int32), ("out_clipped", C.c_void_p)]
+
+
 class MotionPlanes(C.Structure):
     """rt_motion_planes: z and object_id of the new frame in, the motion plane (fx, fy, z_exp per pixel) out; all required"""
     _fields_ = [("struct_size", C.c_uint32), ("z", C.c_void_p), ("object_id", C.c_void_p), ("motion", C.c_void_p)]
@@ -188,6 +194,7 @@ SYMBOLS = [
     "rt_history_create", "rt_history_reset", "rt_history_destroy", "rt_history_frames",
     "rt_temporal_default_params", "rt_temporal_device", "rt_temporal",
     "rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion",
+    "rt_temporal_clip_default", "rt_temporal_clip_device", "rt_temporal_clip_host",
     "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
     "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
@@ -274,6 +281,12 @@ def lib():
         _lib.rt_temporal_motion.argtypes = [vp, vp, vp, vp, vp]
         for name in ("rt_motion_device", "rt_motion", "rt_temporal_motion_device", "rt_temporal_motion"):
             getattr(_lib, name).restype = C.c_int
+        # history rectification (rt_mi355x.h: "history rectification")
+        _lib.rt_temporal_clip_default.argtypes = [vp]
+        _lib.rt_temporal_clip_default.restype = None
+        _lib.rt_temporal_clip_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int]
+        _lib.rt_temporal_clip_host.argtypes = [vp, vp, vp, vp, vp, vp]
+        _lib.rt_temporal_clip_device.restype = _lib.rt_temporal_clip_host.restype = C.c_int
         # exposure and tone mapping (rt_mi355x.h: "exposure and tone mapping")
         _lib.rt_exposure_create.argtypes = [C.c_int, C.POINTER(vp)]
         _lib.rt_exposure_reset.argtypes = [vp]
@@ -544,6 +557,20 @@ def temporal_params(**kw):
     return p
 
 
+def temporal_clip(clip=True, out_clipped=None):
+    """rt_temporal_clip_default, then `clip`: True keeps the defaults, a dict overrides fields (radius, k_clip, min_count,
+    clip_history).  out_clipped: the address of the optional mask plane (host or device, as the call it goes to)."""
+    c = TemporalClip()
+    lib().rt_temporal_clip_default(C.byref(c))
+    if clip is not True:
+        for k, v in dict(clip).items():
+            if k not in ("radius", "k_clip", "min_count", "clip_history"):
+                raise TypeError(f"no temporal clip parameter {k!r}")
+            setattr(c, k, v)
+    c.out_clipped = out_clipped
+    return c
+
+
 def _motion_nodes(nodes, prev_nodes):
     nodes = _c(nodes, NODE)
     prev = _c(prev_nodes, NODE) if prev_nodes is not None else None
@@ -623,13 +650,19 @@ class History:
         """frames accumulated since the creation or the last reset()"""
         return int(lib().rt_history_frames(self._h))
 
-    def accumulate(self, cam, linear, normal, albedo, z, object_id=None, variance=None, rgb8=False, return_history=False, motion=None, **params):
+    def accumulate(self, cam, linear, normal, albedo, z, object_id=None, variance=None, rgb8=False, return_history=False, motion=None,
+                   clip=None, return_clipped=False, **params):
         """rt_temporal on host arrays: float32 (H, W, 3) linear / normal / albedo, float32 (H, W) z, optionally int32 (H, W)
         object_id and float32 (H, W, 3) variance.  Returns the accumulated float32 (H, W, 3) colour, followed -- as a tuple --
         by the accumulated variance (when `variance` is given), the gamma-encoded uint8 image (rgb8=True) and the per-pixel
         history length, float32 (H, W) (return_history=True).  params: temporal_params().
-        motion: float32 (H, W, 3), this frame's motion plane (motion()) -- rt_temporal_motion takes the reprojection from it."""
+        motion: float32 (H, W, 3), this frame's motion plane (motion()) -- rt_temporal_motion takes the reprojection from it.
+        clip: history rectification (rt_temporal_clip_host) -- True for the defaults, or a dict of radius, k_clip, min_count,
+        clip_history; with or without `motion`.  return_clipped=True (needs clip) appends the mask, float32 (H, W): 0 no history,
+        1 kept, 2 clipped."""
         self._moving = None
+        if return_clipped and clip is None:
+            raise TypeError("return_clipped needs clip")
         linear, normal, albedo = (_c(a, np.float32) for a in (linear, normal, albedo))
         h, w = self.height, self.width
         z = _c(z, np.float32)
@@ -645,26 +678,40 @@ class History:
         pl = TemporalPlanes(rgb_linear=ptr(linear), normal=ptr(normal), albedo=ptr(albedo), z=ptr(z), object_id=ptr(ids), variance=ptr(var),
                             out_linear=ptr(out), out_variance=ptr(out_var), out_history=ptr(hist), out_rgb8=ptr(out8))
         p = temporal_params(**params)
+        mask = np.empty((h, w), np.float32) if return_clipped else None
         if motion is not None:
             motion = _c(motion, np.float32)
             assert motion.shape == (h, w, 3)
+        if clip is not None:
+            c = temporal_clip(clip, ptr(mask))
+            _check(lib().rt_temporal_clip_host(self._h, C.byref(cam), C.byref(p), C.byref(c), C.byref(pl), ptr(motion)))
+        elif motion is not None:
             _check(lib().rt_temporal_motion(self._h, C.byref(cam), C.byref(p), C.byref(pl), motion.ctypes.data))
         else:
             _check(lib().rt_temporal(self._h, C.byref(cam), C.byref(p), C.byref(pl)))
-        res = (out,) + tuple(a for a in (out_var, out8, hist) if a is not None)
+        res = (out,) + tuple(a for a in (out_var, out8, hist, mask) if a is not None)
         return res if len(res) > 1 else out
 
     def accumulate_device(self, stream, cam, *, linear_ptr, normal_ptr, albedo_ptr, z_ptr, out_ptr, object_id_ptr=None, variance_ptr=None,
-                          out_variance_ptr=None, history_ptr=None, rgb8_ptr=None, sync=True, motion_ptr=None, **params):
+                          out_variance_ptr=None, history_ptr=None, rgb8_ptr=None, sync=True, motion_ptr=None, clip=None, clipped_ptr=None,
+                          **params):
         """rt_temporal_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
         explicit stream's handle; None = the null stream of the device).  out_ptr may be linear_ptr and out_variance_ptr may be
-        variance_ptr (in place).  motion_ptr: this frame's motion plane on the device (rt_temporal_motion_device)."""
+        variance_ptr (in place).  motion_ptr: this frame's motion plane on the device (rt_temporal_motion_device).
+        clip: history rectification (rt_temporal_clip_device) -- True or a dict, as accumulate(); clipped_ptr (needs clip): a
+        float32 (H, W) device plane for the mask."""
         self._moving = None
+        if clipped_ptr is not None and clip is None:
+            raise TypeError("clipped_ptr needs clip")
         pl = TemporalPlanes(rgb_linear=linear_ptr, normal=normal_ptr, albedo=albedo_ptr, z=z_ptr, object_id=object_id_ptr,
                             variance=variance_ptr, out_linear=out_ptr, out_variance=out_variance_ptr, out_history=history_ptr,
                             out_rgb8=rgb8_ptr)
         p = temporal_params(**params)
-        if motion_ptr is not None:
+        if clip is not None:
+            c = temporal_clip(clip, clipped_ptr)
+            _check(lib().rt_temporal_clip_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(c), C.byref(pl),
+                                                 C.c_void_p(motion_ptr) if motion_ptr is not None else None, 1 if sync else 0))
+        elif motion_ptr is not None:
             _check(lib().rt_temporal_motion_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl),
                                                    C.c_void_p(motion_ptr), 1 if sync else 0))
         else:
@@ -1085,7 +1132,7 @@ class Scene:
             out["display_rgb"] = exposure.tonemap(out["denoised"], out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
-    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, **kw):
+    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
@@ -1102,7 +1149,9 @@ class Scene:
         with: prev_nodes=None and prev_cam = cam.  A frame that reaches `history` any other way -- render_temporal without
         moving=True, accumulate(), accumulate_device() -- makes it forget the remembered frame: the next moving=True frame then
         takes the nodes as not moved since, and the camera from the history as rt_temporal does (prev_cam cannot be known here,
-        so that frame is accumulated WITHOUT a motion plane; "motion" is still added, computed with prev_cam = cam)."""
+        so that frame is accumulated WITHOUT a motion plane; "motion" is still added, computed with prev_cam = cam).
+        clip: history rectification, as History.accumulate's (True, or a dict of radius, k_clip, min_count, clip_history);
+        "clipped" (float32 (H, W): 0 no history, 1 kept, 2 clipped) is added.  Works with moving=True."""
         photon_pass = kw.pop("photon_pass", False)
         t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
         d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
@@ -1114,9 +1163,13 @@ class Scene:
             out["motion"], known, remember = self._motion_since(history, cam, out["z"], out["object_id"], device)
             if known:
                 t_kw["motion"] = out["motion"]
-        out["accumulated"], out["accumulated_variance"], out["history"] = history.accumulate(
-            cam, out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], variance=out["variance"],
-            return_history=True, gamma=params.gamma, **t_kw)
+        if clip is not None:
+            t_kw.update(clip=clip, return_clipped=True)
+        res = history.accumulate(cam, out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"], variance=out["variance"],
+                                 return_history=True, gamma=params.gamma, **t_kw)
+        out["accumulated"], out["accumulated_variance"], out["history"] = res[:3]
+        if clip is not None:
+            out["clipped"] = res[3]
         if moving:
             history._moving = remember                  # (accumulate() forgot it: only this method knows the frame's nodes)
         if denoise:

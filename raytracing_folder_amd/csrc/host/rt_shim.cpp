@@ -59,7 +59,14 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
 void RenderImage::ResetTemporal()
 {
     if (history) rt_history_reset(history);
-    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear(); motion.clear();
+    accumulated.clear(); accumulatedVariance.clear(); historyLength.clear(); motion.clear(); clipped.clear();
+}
+
+void RenderImage::EnableTemporalClip(const rt_temporal_clip *clip)
+{
+    if (clip) temporalClip = *clip;
+    else rt_temporal_clip_default(&temporalClip);
+    temporalClipEnabled = true;
 }
 
 static rt_camera LowerCamera(const Camera &c)       // as Lower() hands the camera to the render
@@ -83,7 +90,8 @@ bool RenderImage::AccumulateTemporalMoving(const Camera &c, const Camera &prev, 
     return Accumulate(c, &prev, nodes, prevNodes, n, params, device);
 }
 
-// prev == NULL: rt_temporal; otherwise rt_motion of this frame first, then rt_temporal_motion with its plane
+// prev == NULL: rt_temporal; otherwise rt_motion of this frame first, then rt_temporal_motion with its plane.  After
+// EnableTemporalClip(): rt_temporal_clip_host in place of both, with or without the plane
 bool RenderImage::Accumulate(const Camera &c, const Camera *prev, const rt_node *nodes, const rt_node *prevNodes, int nNodes,
                              const rt_temporal_params *params, int device)
 {
@@ -103,17 +111,23 @@ bool RenderImage::Accumulate(const Camera &c, const Camera *prev, const rt_node 
     const rt_temporal_planes pl = {(uint32_t)sizeof(rt_temporal_planes), linear.data(), normals.data(), albedo.data(), zbuffer.data(),
                                    objectIds.data(), varianceEnabled ? variance.data() : nullptr, out.data(),
                                    varianceEnabled ? outVar.data() : nullptr, len.data(), nullptr};
+    std::vector<float> mask(temporalClipEnabled ? n : 0);
+    rt_temporal_clip clip = temporalClip;
+    clip.out_clipped = mask.data();
     if (prev) {
         const rt_camera prc = LowerCamera(*prev);
         std::vector<float> mv(n * 3);
         const rt_motion_planes mp = {(uint32_t)sizeof(rt_motion_planes), zbuffer.data(), objectIds.data(), mv.data()};
         if (rt_motion(device, &rc, &prc, nodes, prevNodes, nNodes, &mp) != RT_OK ||
-            rt_temporal_motion(history, &rc, params ? params : &defaults, &pl, mv.data()) != RT_OK) { temporalError = rt_last_error(); return false; }
+            (temporalClipEnabled ? rt_temporal_clip_host(history, &rc, params ? params : &defaults, &clip, &pl, mv.data())
+                                 : rt_temporal_motion(history, &rc, params ? params : &defaults, &pl, mv.data())) != RT_OK) { temporalError = rt_last_error(); return false; }
         motion.swap(mv);
     } else {
-        if (rt_temporal(history, &rc, params ? params : &defaults, &pl) != RT_OK) { temporalError = rt_last_error(); return false; }
+        if ((temporalClipEnabled ? rt_temporal_clip_host(history, &rc, params ? params : &defaults, &clip, &pl, nullptr)
+                                 : rt_temporal(history, &rc, params ? params : &defaults, &pl)) != RT_OK) { temporalError = rt_last_error(); return false; }
         motion.clear();
     }
+    clipped.swap(mask);
     accumulated.swap(out); accumulatedVariance.swap(outVar); historyLength.swap(len);
     temporalError.clear();
     return true;

@@ -38,7 +38,9 @@ class RenderImage {
     // EnableVariance) and the per-pixel history length -- and the rt_history that holds them on the device
     std::vector<float> accumulated, accumulatedVariance, historyLength;
     std::vector<float> motion;         // AccumulateTemporalMoving(): the frame's motion plane, (fx, fy, z_exp) per pixel
-    bool temporalEnabled = false;
+    std::vector<float> clipped;        // EnableTemporalClip(): the rectification's mask of the last accumulated frame
+    bool temporalEnabled = false, temporalClipEnabled = false;
+    rt_temporal_clip temporalClip = {};
     rt_history *history = nullptr;
     int historyDevice = 0;
     std::string temporalError;
@@ -123,6 +125,14 @@ public:
     bool AccumulateTemporalMoving(const Camera &camera, const Camera &prevCamera, const rt_node *nodes, const rt_node *prevNodes, int n,
                                   const rt_temporal_params *params = nullptr, int device = 0);
     float *GetMotion() { return motion.empty() ? nullptr : motion.data(); }
+    // History rectification (rt_mi355x.h, "history rectification"): from now on AccumulateTemporal() and
+    // AccumulateTemporalMoving() clamp the reprojected history into the current frame's neighbourhood box
+    // (rt_temporal_clip_host).  clip == NULL: the defaults of rt_temporal_clip_default; its out_clipped is ignored -- the mask is
+    // kept next to the other planes: GetClipped(), float per pixel (0 no history, 1 kept, 2 clipped), NULL until a call has
+    // succeeded.
+    void EnableTemporalClip(const rt_temporal_clip *clip = nullptr);
+    bool TemporalClipEnabled() const { return temporalClipEnabled; }
+    float *GetClipped() { return clipped.empty() ? nullptr : clipped.data(); }
     void ResetTemporal();
     int TemporalFrames() const { return rt_history_frames(history); }
     const std::string &TemporalError() const { return temporalError; }

@@ -2487,6 +2487,7 @@ struct rt_history {
     int cur = 0;                        // the set the last frame wrote
     int32_t frames = 0;                 // since create / reset; 0: the next frame reads no history
     DevCamera cam = {};                 // of the frame in set `cur`
+    DevBuf clip_out;                    // rt_temporal_clip_device with out_linear over rgb_linear: 12 bytes a pixel, made on first use
     hipEvent_t done = nullptr; bool pending = false;
     std::mutex mu;
 };
@@ -2522,6 +2523,7 @@ extern "C" void rt_history_destroy(rt_history *hst)
     if (hipSetDevice(hst->device) == hipSuccess) {
         if (hst->pending) (void)hipEventSynchronize(hst->done);
         hst->sets.release();            // hipFree waits for the kernels that still use it
+        hst->clip_out.release();
         if (hst->done) (void)hipEventDestroy(hst->done);
     }
     delete hst;
@@ -2558,9 +2560,30 @@ static rt_status temporal_check(const char *name, const rt_history *hst, const r
     return RT_OK;
 }
 
-// motion: NULL (reproject with the two cameras), or the device plane of rt_motion_device for this frame
+extern "C" void rt_temporal_clip_default(rt_temporal_clip *c)
+{
+    if (!c) return;
+    c->struct_size = (uint32_t)sizeof *c;
+    c->radius = 2; c->k_clip = 1.5f; c->min_count = 4; c->clip_history = 2; c->out_clipped = nullptr;
+}
+
+// what rt_temporal_clip_* check on top of temporal_check, without a device
+static rt_status temporal_clip_check(const char *name, const rt_temporal_clip *c)
+{
+    if (!c) return fail(RT_ERR_ARG, "%s: the rt_temporal_clip is NULL", name);
+    if (c->struct_size != (uint32_t)sizeof(rt_temporal_clip))
+        return fail(RT_ERR_ARG, "%s: rt_temporal_clip.struct_size is %u, this library's is %zu", name, c->struct_size, sizeof(rt_temporal_clip));
+    if (c->radius < 1 || c->radius > 3) return fail(RT_ERR_ARG, "%s: radius is %d, allowed 1..3", name, c->radius);
+    if (!(c->k_clip > 0.0f) || !std::isfinite(c->k_clip)) return fail(RT_ERR_ARG, "%s: k_clip must be positive and finite", name);
+    if (c->min_count < 1) return fail(RT_ERR_ARG, "%s: min_count is %d, allowed >= 1", name, c->min_count);
+    if (c->clip_history < 1 || c->clip_history > 65535) return fail(RT_ERR_ARG, "%s: clip_history is %d, allowed 1..65535", name, c->clip_history);
+    return RT_OK;
+}
+
+// motion: NULL (reproject with the two cameras), or the device plane of rt_motion_device for this frame.  clip: NULL (k_temporal),
+// or the validated rectification (k_temporal_clip), its out_clipped a device plane
 static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync,
-                                    const float *motion = nullptr)
+                                    const float *motion = nullptr, const rt_temporal_clip *clip = nullptr)
 {
     HIP_TRY(hipSetDevice(hst->device));
     std::lock_guard<std::mutex> lk(hst->mu);
@@ -2578,7 +2601,26 @@ static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_ca
     const int next = hst->cur ^ 1;
     R.prev = set0 + (size_t)hst->cur * 3 * n; R.next = set0 + (size_t)next * 3 * n;
     R.motion = motion;
-    rtk_launch_temporal(st, R);
+    if (clip) {
+        // k_temporal_clip's workgroups read their neighbours' pixels of rgb_linear: where out_linear overlaps it, the kernel writes
+        // a plane of the history's and the result is copied behind it on the same stream
+        const char *in = (const char *)pl->rgb_linear, *out = (const char *)pl->out_linear;
+        const bool overlap = out < in + n * 12 && in < out + n * 12;
+        if (overlap) {
+            rt_status rs = hst->clip_out.ensure(n * 12);
+            if (rs) return rs;
+            R.out_linear = (float *)hst->clip_out.p;
+        }
+        TemporalClipRequest CR = {};
+        CR.frame = R;
+        CR.radius = clip->radius; CR.min_count = clip->min_count; CR.k_clip = clip->k_clip; CR.clip_history = clip->clip_history;
+        CR.out_clipped = clip->out_clipped;
+        rtk_launch_temporal_clip(st, CR);
+        HIP_TRY(hipGetLastError());
+        if (overlap) HIP_TRY(hipMemcpyAsync(pl->out_linear, hst->clip_out.p, n * 12, hipMemcpyDeviceToDevice, st));
+    } else {
+        rtk_launch_temporal(st, R);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(hst->done, st));
     hst->pending = true;
@@ -2597,7 +2639,7 @@ extern "C" rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const
 
 // the host entry points: upload, accumulate, download.  motion: NULL (rt_temporal), or this frame's plane on the host
 static rt_status temporal_host(const char *name, rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
-                               const float *motion)
+                               const float *motion, const rt_temporal_clip *clip = nullptr)
 {
     rt_status st = temporal_check(name, hst, cam, p, host_planes);
     if (st) return st;
@@ -2614,7 +2656,15 @@ static rt_status temporal_host(const char *name, rt_history *hst, const rt_camer
     const rt_temporal_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
                                     (const int32_t *)id.p, (const float *)var.p, (float *)rgb.p,
                                     host_planes->out_variance ? (float *)var.p : nullptr, (float *)hist.p, (uint8_t *)rgb8.p};
-    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1, (const float *)mv.p))) return st;
+    ScopedDevBuf mask;
+    rt_temporal_clip dev_clip;
+    if (clip) {
+        dev_clip = *clip;
+        if (clip->out_clipped && (st = mask.ensure(n * 4))) return st;
+        dev_clip.out_clipped = (float *)mask.p;
+    }
+    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1, (const float *)mv.p, clip ? &dev_clip : nullptr))) return st;
+    if (clip && clip->out_clipped) HIP_TRY(hipMemcpy(clip->out_clipped, mask.p, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
     if (host_planes->out_variance) HIP_TRY(hipMemcpy(host_planes->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
     if (host_planes->out_history) HIP_TRY(hipMemcpy(host_planes->out_history, hist.p, n * 4, hipMemcpyDeviceToHost));
@@ -2641,6 +2691,23 @@ extern "C" rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, c
 {
     if (!motion) return fail(RT_ERR_ARG, "rt_temporal_motion: the motion plane is NULL");
     return temporal_host("rt_temporal_motion", hst, cam, p, host_planes, motion);
+}
+
+extern "C" rt_status rt_temporal_clip_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                             const rt_temporal_clip *clip, const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
+{
+    rt_status st = temporal_clip_check("rt_temporal_clip_device", clip);
+    if (st) return st;
+    if ((st = temporal_check("rt_temporal_clip_device", hst, cam, p, device_planes))) return st;
+    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev, clip);
+}
+
+extern "C" rt_status rt_temporal_clip_host(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_clip *clip,
+                                           const rt_temporal_planes *host_planes, const float *motion)
+{
+    rt_status st = temporal_clip_check("rt_temporal_clip_host", clip);
+    if (st) return st;
+    return temporal_host("rt_temporal_clip_host", hst, cam, p, host_planes, motion, clip);
 }
 
 // ---- motion vectors ---------------------------------------------------------------------------------------------------------

@@ -128,6 +128,17 @@ struct TemporalRequest {
     const float *motion;
 };
 
+// One temporal accumulation with history rectification (rt_temporal.hip, k_temporal_clip; the definition: rt_mi355x.h, "history
+// rectification"): `frame` is the plain accumulation's request, with one restriction -- out_linear must not overlap rgb_linear,
+// because the workgroups read their neighbours' pixels of rgb_linear (the caller substitutes a plane of its own and copies).
+// radius 1..3, min_count >= 1, k_clip > 0 and clip_history 1..65535 are validated by the caller; out_clipped: NULL, or the
+// caller's device plane of width * height floats (0 no history, 1 kept, 2 clipped).
+struct TemporalClipRequest {
+    TemporalRequest frame;
+    int radius, min_count; float k_clip; int clip_history;
+    float *out_clipped;
+};
+
 // One motion plane of a width x height frame (rt_motion.hip; the definition: rt_mi355x.h, "motion vectors").  z, object_id and
 // motion are the caller's device planes.  `cur` and `old` are camera_setup's quantities of this frame's camera and the previous
 // frame's.  table: one DevNodeMotion per node on the device, this frame's world -> the previous frame's, P_prev = R P + t as three
@@ -201,6 +212,8 @@ void rtk_launch_denoise_frame(hipStream_t st, const DenoiseRequest &R);
 // ---- rt_temporal.hip: temporal accumulation with camera reprojection ---------------------------------------------------
 // k_temporal over the frame on `st`: reads the set `prev` (when has_history), writes the set `next` and the caller's planes
 void rtk_launch_temporal(hipStream_t st, const TemporalRequest &R);
+// k_temporal_clip over the frame on `st`: the same, with step 4b between the taps and the blend (8512 bytes of LDS a workgroup)
+void rtk_launch_temporal_clip(hipStream_t st, const TemporalClipRequest &R);
 
 // ---- rt_motion.hip: motion vectors in image space ------------------------------------------------------------------------
 // k_motion over the frame on `st`: reads z, object_id and the node table, writes the motion plane

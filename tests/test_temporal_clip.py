@@ -1,0 +1,540 @@
+"""History rectification in temporal accumulation (rt_temporal_clip_default / _device / _host, k_temporal_clip;
+capi.History.accumulate(clip=), Scene.render_temporal(clip=); rt::RenderImage::EnableTemporalClip / GetClipped).  The yardstick is
+`ref_temporal_clip` below: step 4b of the header's "history rectification" in float64 numpy, placed between the taps and the blend
+of tests/test_temporal.py's `ref_temporal`, whose tap logic it reuses.  The frames are that file's analytic scene, with a light
+that switches in mid-sequence: the geometry tests of the plain accumulation all pass there, and only the rectification reacts."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from raytracing_folder_amd import capi
+from tests import scenes
+from tests.test_temporal import (BIG, F, MAX_LEFT_OUT, PAIRS, _gate, _gi_params, _planes_for, _valid, cam_a, cam_b, cam_c, cam_setup,
+                                 delta_px, frame, light_smooth, pixel_rays, ref_temporal)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEAR = 1e-4                     # d_h closer than NEAR (|bound| + s) to lo or hi: the CLIPPED decision may flip on the GPU
+NOISE = 0.3
+SWITCH_AT = 2                   # the GPU sequences hold three frames: two under light_smooth, the third under light_dim
+SMALL = ((33, 9), (70, 17), (1, 1))
+SMALL_CAMS = (cam_a, cam_b, cam_b)
+
+
+def light_dim(P):
+    """a quarter of light_smooth: far outside 1.5 sigma of a frame whose noise is 0.3 of its own (dimmer) colour"""
+    return 0.25 * light_smooth(P)
+
+
+def light_at(k, switch_at):
+    return light_smooth if k < switch_at else light_dim
+
+
+# ---- the reference ----------------------------------------------------------------------------------------------
+def ref_temporal_clip(hist, cam, pl, with_ids=True, with_var=True, radius=2, k_clip=1.5, min_count=4, clip_history=2,
+                      alpha=0.2, max_history=32, **kw):
+    """The definition, step by step in float64.  Steps 1-4 are ref_temporal's: it is run on a copy of `hist` with max_history out
+    of reach, which leaves N_h + 1 uncapped, and d_h, u_h are taken back out of its blend (d' = (1 - b) d_h + b d with its own
+    b = max(alpha, 1 / (N_h + 1)) <= 1/2: an exact inversion up to float64 rounding).  Then 4b -- window, two-pass moments, clamp,
+    shortened N_h -- and step 5 with the real max_history.  `hist` is updated in place like ref_temporal's.  Returns its dict with
+    linear / variance / history replaced and clipped (0 / 1 / 2), m, mu, s, lo, hi, d_h, d, beta added; left_out additionally
+    holds the pixels whose unclamped d_h lies within NEAR (|bound| + s) of lo or hi in some channel."""
+    al, kc = float(F(alpha)), float(F(k_clip))
+    assert al < 1.0
+    probe = dict(hist)
+    r = ref_temporal(probe, cam, pl, with_ids, with_var, alpha=alpha, max_history=10 ** 9, **kw)
+    H, W = r["part"].shape
+    part, has = r["part"], r["has"]
+    a = np.where(pl["albedo"] > F(1e-3), pl["albedo"], 1).astype(np.float64)
+    with np.errstate(all="ignore"):
+        d = pl["linear"].astype(np.float64) / a
+        v64 = pl["variance"].astype(np.float64) if with_var else np.zeros_like(d)
+        u = np.where(np.isfinite(v64) & (v64 > 0), v64, 0.0) / a ** 2
+        n0 = np.where(has, r["history"], 2.0)                   # N_h + 1
+        b0 = np.maximum(al, 1.0 / n0)[..., None]
+        d_h = np.where(has[..., None], (probe["d"] - b0 * d) / (1 - b0), 0.0)
+        u_h = np.where(has[..., None], (probe["u"] - b0 ** 2 * u) / (1 - b0) ** 2, 0.0)
+        n_h = n0 - 1
+        # 4b: the window, row-major; a pixel counts when it takes part (valid, finite d) and carries p's id
+        idp = pl["object_id"] if with_ids else np.zeros((H, W), np.int32)
+        R = radius
+        pad = lambda x, fill: np.pad(x, ((R, R), (R, R)) + ((0, 0),) * (x.ndim - 2), constant_values=fill)
+        part_p, id_p, d_p = pad(part, False), pad(idp, -1), pad(np.where(part[..., None], d, 0.0), 0.0)
+        offsets = [(j, i) for j in range(2 * R + 1) for i in range(2 * R + 1)]
+        counts = [part_p[j:j + H, i:i + W] & (id_p[j:j + H, i:i + W] == idp) for j, i in offsets]
+        m = np.zeros((H, W))
+        total = np.zeros((H, W, 3))
+        for (j, i), c in zip(offsets, counts):
+            m += c
+            total += np.where(c[..., None], d_p[j:j + H, i:i + W], 0.0)
+        mu = total / np.maximum(m, 1)[..., None]
+        sq = np.zeros((H, W, 3))
+        for (j, i), c in zip(offsets, counts):
+            sq += np.where(c[..., None], (d_p[j:j + H, i:i + W] - mu) ** 2, 0.0)
+        s = np.sqrt(sq / np.maximum(m, 1)[..., None])
+        lo, hi = mu - kc * s, mu + kc * s
+        rect = has & (m >= min_count)
+        d_c = np.where(rect[..., None], np.minimum(np.maximum(d_h, lo), hi), d_h)
+        clipped = rect & (d_c != d_h).any(-1)
+        near = rect & ((np.abs(d_h - lo) <= NEAR * (np.abs(lo) + s)) | (np.abs(d_h - hi) <= NEAR * (np.abs(hi) + s))).any(-1)
+        n_h = np.where(clipped, np.minimum(n_h, float(clip_history)), n_h)
+        N = np.where(has, np.minimum(n_h + 1, float(max_history)), 1.0)
+        beta = np.maximum(al, 1.0 / N)[..., None]
+        d2 = np.where(has[..., None], (1 - beta) * d_c + beta * d, d)
+        u2 = np.where(has[..., None], (1 - beta) ** 2 * u_h + beta ** 2 * u, u)
+        N = np.where(part, N, 0.0)
+    left_out = r["left_out"] | (part & near)
+    hist.clear()
+    hist.update(probe)
+    hist.update(d=d2, u=u2, N=N, left_out=left_out)
+    out = dict(r)
+    out.update(linear=np.where(part[..., None], d2 * a, pl["linear"].astype(np.float64)), variance=np.where(part[..., None], u2 * a ** 2, v64),
+               history=N, left_out=left_out, clipped=np.where(has, np.where(clipped, 2.0, 1.0), 0.0), rect=rect, m=m, mu=mu, s=s, lo=lo, hi=hi,
+               d_h=d_h, d=d, beta=beta[..., 0], near=near)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _clip_sequence(cams, w, h, with_ids=True, with_var=True, noise=NOISE, switch_at=SWITCH_AT, seed=300, radius=2, k_clip=1.5, plain=False,
+                   dtype=np.float32, max_history=32):
+    """the reference over a sequence of cameras with fresh noise per frame and the light switched at frame `switch_at`:
+    ((cam, planes, clean, result), ...); plain=True: ref_temporal instead.  Shared by the tests and left unchanged by them."""
+    hist, out = {}, []
+    for k, c in enumerate(cams):
+        cam = c(w, h)
+        pl, clean = frame(cam, seed + k, noise, light_at(k, switch_at), dtype)
+        if plain:
+            res = ref_temporal(hist, cam, pl, with_ids, with_var, max_history=max_history)
+        else:
+            res = ref_temporal_clip(hist, cam, pl, with_ids, with_var, radius=radius, k_clip=k_clip, max_history=max_history)
+        out.append((cam, pl, clean, res))
+    return tuple(out)
+
+
+def motion_plane(cam, old_cam, pl):
+    """(fx, fy, z_exp) of a static scene between two cameras: steps 2-3 of "temporal accumulation" in float64, rounded to the
+    float32 the plane carries (a rounding of 2^-24 of a position, far inside delta_px)"""
+    cs, old = cam_setup(cam), cam_setup(old_cam)
+    z = np.where(pl["z"] < BIG, pl["z"], 1.0).astype(np.float64)
+    e = cs["pos"] + z[..., None] * pixel_rays(cs) - old["pos"]
+    q = e @ old["M"]
+    ok = q[..., 2] < 0
+    t = old["b"][2] / np.where(ok, q[..., 2], -1.0)
+    fx, fy = (q[..., 0] * t - old["b"][0]) / old["u"] - 0.5, (q[..., 1] * t - old["b"][1]) / old["v"] - 0.5
+    zexp = np.where(ok, np.sqrt((e * e).sum(-1)), 0.0)
+    return np.stack([fx, fy, zexp], -1).astype(np.float32)
+
+
+# ---- CPU: the ABI -----------------------------------------------------------------------------------------------
+def test_new_symbols_struct_layout_and_defaults():
+    L = capi.lib()
+    for name in ("rt_temporal_clip_default", "rt_temporal_clip_device", "rt_temporal_clip_host"):
+        assert hasattr(L, name) and name in capi.SYMBOLS, name
+    assert L.rt_abi_version() == 4
+    assert [f[0] for f in capi.TemporalClip._fields_] == ["struct_size", "radius", "k_clip", "min_count", "clip_history", "out_clipped"]
+    assert C.sizeof(capi.TemporalClip) == 32 and capi.TemporalClip.out_clipped.offset == 24
+    c = capi.TemporalClip()
+    L.rt_temporal_clip_default(C.byref(c))
+    assert (c.struct_size, c.radius, c.k_clip, c.min_count, c.clip_history, c.out_clipped) == (32, 2, 1.5, 4, 2, None)
+    L.rt_temporal_clip_default(None)                            # ignored
+    q = capi.temporal_clip({"radius": 3, "k_clip": 2.0})
+    assert (q.radius, q.k_clip, q.min_count, q.clip_history) == (3, 2.0, 4, 2)
+    with pytest.raises(TypeError):
+        capi.temporal_clip({"levels": 3})
+    # the existing structs did not grow
+    assert C.sizeof(capi.TemporalParams) == 24 and C.sizeof(capi.TemporalPlanes) == 88
+
+
+def test_argument_checks_come_before_any_gpu_call():
+    """without a history every check is still reached: the clip's come first, then rt_temporal's, the NULL history last"""
+    L = capi.lib()
+    cam = cam_a(8, 8)
+    buf = np.zeros(8 * 8 * 3, np.float32)
+    ptr = buf.ctypes.data
+    pl = capi.TemporalPlanes(rgb_linear=ptr, normal=ptr, albedo=ptr, z=ptr, object_id=ptr, variance=ptr, out_linear=ptr, out_variance=ptr,
+                             out_history=ptr, out_rgb8=ptr)
+    p = capi.temporal_params()
+
+    def both(c, planes=pl, params=p):
+        cp = C.byref(c) if c is not None else None
+        return (L.rt_temporal_clip_host(None, C.byref(cam), C.byref(params), cp, C.byref(planes), None),
+                L.rt_temporal_clip_device(None, None, C.byref(cam), C.byref(params), cp, C.byref(planes), None, 1))
+
+    cases = [(b"rt_temporal_clip is NULL", None)]
+    for bad in (0, 20, 24, 40):
+        c = capi.temporal_clip()
+        c.struct_size = bad
+        cases.append((b"struct_size", c))
+    cases += [(b"radius", capi.temporal_clip({"radius": v})) for v in (0, -1, 4)]
+    cases += [(b"k_clip", capi.temporal_clip({"k_clip": v})) for v in (0.0, -1.5, float("nan"), float("inf"))]
+    cases += [(b"min_count", capi.temporal_clip({"min_count": v})) for v in (0, -3)]
+    cases += [(b"clip_history", capi.temporal_clip({"clip_history": v})) for v in (0, -1, 65536)]
+    for what, c in cases:
+        for st in both(c):
+            assert st == -1 and what in L.rt_last_error(), (what, L.rt_last_error())
+    # rt_temporal's checks apply too
+    ok = capi.temporal_clip()
+    for st in both(ok, params=capi.temporal_params(alpha=1.5)):
+        assert st == -1 and b"alpha" in L.rt_last_error()
+    for st in both(ok, planes=capi.TemporalPlanes(rgb_linear=ptr, normal=ptr, albedo=ptr, z=ptr, out_linear=None)):
+        assert st == -1 and b"required" in L.rt_last_error()
+    for st in both(ok):
+        assert st == -1 and b"history is NULL" in L.rt_last_error()
+
+
+def _build_shim_driver(tmp_path):
+    exe = os.path.join(str(tmp_path), "shim_temporal_clip_driver")
+    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "shim_temporal_clip_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+def test_shim_driver_builds_against_the_header(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+# ---- CPU: the reference -----------------------------------------------------------------------------------------
+GPU_RUNS = [(name, cams, 37, 23) for name, cams in PAIRS] + [("A,B,B", SMALL_CAMS, w, h) for w, h in SMALL]
+
+
+def test_reference_with_the_clamp_wide_open_is_the_plain_reference():
+    for name, cams, w, h in GPU_RUNS:
+        for with_ids in (True, False):
+            wide = _clip_sequence(cams, w, h, with_ids, k_clip=1e9)
+            plain = _clip_sequence(cams, w, h, with_ids, plain=True)
+            for (_, _, _, a), (_, _, _, b) in zip(wide, plain):
+                assert not (a["clipped"] == 2).any() and ((a["clipped"] == 1) == b["has"]).all()
+                assert (a["history"] == b["history"]).all()
+                for key in ("linear", "variance"):
+                    assert np.abs(a[key] - b[key]).max() <= 1e-12 * max(1.0, np.abs(b[key]).max()), (name, w, h, key)
+
+
+def test_reference_noise_free_light_switch():
+    """a repeated camera, no noise, the light switched at frame 3: the box of a pixel is then the spread of the NEW light over its
+    window, and the history holds the old light"""
+    cams = (cam_a,) * 5
+    seq = _clip_sequence(cams, 37, 23, noise=0.0, switch_at=3, dtype=np.float64)
+    plain = _clip_sequence(cams, 37, 23, noise=0.0, switch_at=3, dtype=np.float64, plain=True)
+    al = float(F(0.2))
+    for k in (0, 1, 2):     # before the switch the history IS the frame: kept, but for the extrema of the light, where a noise-free
+        r = seq[k][3]       # pixel lies outside 1.5 sigma of its own window (a known property of variance clipping)
+        assert ((r["clipped"] > 0) == (r["part"] & (k > 0))).all() and (k == 0 or (r["clipped"][r["part"]] == 1).mean() > 0.7)
+    r, rp = seq[3][3], plain[3][3]
+    rect = r["rect"]
+    assert rect.sum() > 0.9 * r["part"].sum()
+    inside = ((r["d_h"] >= r["lo"]) & (r["d_h"] <= r["hi"])).all(-1)
+    assert ((r["clipped"] == 2) | inside)[rect].all() and (r["clipped"] == 2)[rect].mean() > 0.9
+    assert (r["history"][rect & (r["clipped"] == 2)] == 3).all()          # min(N_h, 2) + 1
+    a = np.where(seq[3][1]["albedo"] > 1e-3, seq[3][1]["albedo"], 1.0)
+    d_out = r["linear"] / a
+    bound = (1 - r["beta"])[..., None] * (np.abs(r["mu"] - r["d"]) + float(F(1.5)) * r["s"])
+    assert (np.abs(d_out - r["d"]) <= bound + 1e-12)[rect].all()
+    # the plain accumulation keeps 1 - beta of the old-new difference: 0.75 in the frame of the switch (N = 4, beta = 1/4), and
+    # from the next frame on 0.8 of what was left, frame after frame (N >= 5: beta = alpha = 0.2)
+    old, new = seq[2][1]["linear"] / a, r["d"]
+    keep_plain = 1 - max(al, 1.0 / 4)
+    assert np.allclose((rp["linear"] / a - new)[rect], keep_plain * (old - new)[rect], rtol=0, atol=1e-12)
+    for k in (4,):                                              # one frame on: the plain one still holds 0.8 of that
+        r4, rp4 = seq[k][3], plain[k][3]
+        assert np.allclose((rp4["linear"] / a - new)[rect], (1 - al) * keep_plain * (old - new)[rect], rtol=0, atol=1e-12)
+        assert (np.abs(r4["linear"] / a - new) <= np.abs(rp4["linear"] / a - new) + 1e-12)[rect].all()
+    big = rect & (np.abs(old - new).min(-1) > 0.05)
+    assert big.sum() > 100 and (np.abs(d_out - new)[big] < 0.5 * np.abs(old - new)[big]).all()
+
+
+def test_few_pixels_are_left_out_of_the_gpu_comparisons():
+    """the condition on the inputs: at most 2 % of the valid pixels of any frame of any sequence the GPU tests use -- the old
+    left_out set plus the pixels within NEAR of a bound of the box"""
+    for name, cams, w, h in GPU_RUNS:
+        for with_ids in (True, False):
+            for radius in (1, 2, 3):
+                for k, (cam, pl, _, r) in enumerate(_clip_sequence(cams, w, h, with_ids, radius=radius)):
+                    valid = _valid(pl, with_ids)
+                    assert (r["left_out"] >= r["near"] & r["part"]).all()
+                    share = r["left_out"].sum() / max(1, valid.sum())
+                    assert share <= MAX_LEFT_OUT, (name, w, h, with_ids, radius, k, share)
+    # the frames of the invalid-neighbours test
+    for with_ids in (True, False):
+        for r, pl in _holes_reference(with_ids)[1]:
+            assert r["left_out"].sum() <= MAX_LEFT_OUT * _valid(pl, with_ids).sum()
+
+
+# ---- GPU: against the reference ---------------------------------------------------------------------------------
+def _run_against_reference(cams, w, h, with_ids, with_var, radius, use_motion, what):
+    """S_p, the sensitivity to the position's error that _gate multiplies delta_px with, is the spread of the accepted taps as
+    ref_temporal reports it for the unclamped d_h and N_h.  It bounds the rectified values too: min / max with a bound that does
+    not depend on the position is 1-Lipschitz, so the clamped d_h and min(N_h, clip_history) move by no more than the unclamped
+    ones (a pixel whose CLIPPED decision itself may flip is left out)."""
+    seen, old = set(), None
+    with capi.History(0, w, h) as hst:
+        for k, (cam, pl, clean, r) in enumerate(_clip_sequence(cams, w, h, with_ids, with_var, radius=radius)):
+            mv = motion_plane(cam, old if old is not None else cam, pl) if use_motion else None
+            res = hst.accumulate(cam, pl["linear"], pl["normal"], pl["albedo"], pl["z"], return_history=True, motion=mv,
+                                 clip={"radius": radius}, return_clipped=True, **_planes_for(pl, with_ids, with_var))
+            got, got_hist, got_mask = res[0], res[-2], res[-1]
+            part = r["part"]
+            keep = part & ~r["left_out"]
+            assert r["left_out"].sum() <= MAX_LEFT_OUT * max(1, _valid(pl, with_ids).sum())
+            delta = delta_px(old, cam, float(pl["z"][part].min())) if old is not None and part.any() else 0.0
+            tag = f"{what} {w}x{h} r={radius} ids={with_ids} var={with_var} motion={use_motion} step {k}"
+            print(f"temporal clip {tag}: kept {int((r['clipped'][keep] == 1).sum())}, clipped {int((r['clipped'][keep] == 2).sum())}")
+            assert got_mask[keep].tobytes() == r["clipped"][keep].astype(np.float32).tobytes(), tag
+            _gate(got, r["linear"], r["s_linear"], delta, keep, tag + " colour", 1e-6)
+            _gate(got_hist, r["history"], r["s_history"], delta, keep, tag + " history", 1e-6)
+            if with_var:
+                _gate(res[1], r["variance"], r["s_variance"], delta, keep, tag + " variance", 1e-12)
+                assert res[1][~part].tobytes() == pl["variance"][~part].tobytes()
+            assert got[~part].tobytes() == pl["linear"][~part].tobytes() and (got_hist[~part] == 0).all() and (got_mask[~part] == 0).all()
+            seen |= set(np.unique(got_mask[keep]).tolist())
+            old = cam
+    return seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("radius", (1, 2, 3))
+@pytest.mark.parametrize("name,cams", PAIRS)
+@pytest.mark.parametrize("with_ids,with_var", [(True, True), (False, True), (True, False), (False, False)])
+def test_rectified_accumulation_against_the_reference_37x23(name, cams, with_ids, with_var, radius):
+    """test_temporal's gate (2e-5 |want| + 1e-6, variance 1e-12, plus delta_px * S_p) on the pixels that are not left out; the mask
+    is compared exactly there; both branches of CLIPPED occur, with and without a motion plane"""
+    for use_motion in (False, True):
+        seen = _run_against_reference(cams, 37, 23, with_ids, with_var, radius, use_motion, name)
+        assert seen == {0.0, 1.0, 2.0}, seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", SMALL)
+@pytest.mark.parametrize("radius", (1, 2, 3))
+def test_rectified_accumulation_against_the_reference_at_other_sizes(w, h, radius):
+    """33 x 9 and 70 x 17: halos across tile edges in both directions and partial tiles, a window taller than what is left of the
+    image; 1 x 1: m = 1 < min_count, never rectified"""
+    for with_ids, with_var, use_motion in ((i, v, m) for i in (True, False) for v in (True, False) for m in (False, True)):
+        seen = _run_against_reference(SMALL_CAMS, w, h, with_ids, with_var, radius, use_motion, "A,B,B")
+        assert seen == {0.0, 1.0, 2.0} if w > 1 else seen <= {0.0, 1.0}, seen
+
+
+def _accumulate_all(hst, seq, with_motion=False, **kw):
+    outs, old = [], None
+    for cam, pl, _, _ in seq:
+        mv = motion_plane(cam, old if old is not None else cam, pl) if with_motion else None
+        outs.append(hst.accumulate(cam, pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"], variance=pl["variance"], rgb8=True,
+                                   return_history=True, motion=mv, **kw))
+        old = cam
+    return outs
+
+
+@pytest.mark.gpu
+def test_wide_open_clamp_gives_the_bytes_of_the_plain_accumulation_and_histories_do_not_disturb_each_other():
+    seq = _clip_sequence(PAIRS[1][1], 37, 23)
+    other = _clip_sequence(SMALL_CAMS, 70, 17)
+    for with_motion in (False, True):
+        with capi.History(0, 37, 23) as hst:
+            plain = _accumulate_all(hst, seq, with_motion)
+        with capi.History(0, 37, 23) as hst:
+            wide = _accumulate_all(hst, seq, with_motion, clip={"k_clip": 1e9}, return_clipped=True)
+        with capi.History(0, 37, 23) as hst:
+            tight = _accumulate_all(hst, seq, with_motion, clip=True)
+        # a plain history, and a rectified one, with the frames of a rectified history of another size between theirs
+        with capi.History(0, 37, 23) as hst, capi.History(0, 37, 23) as hst_c, capi.History(0, 70, 17) as hst_o:
+            old = None
+            for k, (cam, pl, _, _) in enumerate(seq):
+                mv = motion_plane(cam, old if old is not None else cam, pl) if with_motion else None
+                args = (cam, pl["linear"], pl["normal"], pl["albedo"], pl["z"], pl["object_id"])
+                a = hst.accumulate(*args, variance=pl["variance"], rgb8=True, return_history=True, motion=mv)
+                _accumulate_all(hst_o, other[k:k + 1], clip=True)
+                b = hst_c.accumulate(*args, variance=pl["variance"], rgb8=True, return_history=True, motion=mv, clip=True)
+                for x, y in zip(a, plain[k]):
+                    assert x.tobytes() == y.tobytes()
+                for x, y in zip(b, tight[k]):
+                    assert x.tobytes() == y.tobytes()
+                old = cam
+        for k, (a, b) in enumerate(zip(plain, wide)):
+            for x, y in zip(a, b[:4]):
+                assert x.tobytes() == y.tobytes(), (with_motion, k)
+            assert not (b[4] == 2).any() and ((b[4] == 1) == (a[3] > 1)).all()
+        assert tight[2][0].tobytes() != plain[2][0].tobytes()
+
+
+@pytest.mark.gpu
+def test_determinism_aliasing_entry_points_and_reset():
+    import torch
+    w, h = 37, 23
+    seq = _clip_sequence(PAIRS[1][1], w, h)
+    with capi.History(0, w, h) as hst:
+        first = _accumulate_all(hst, seq, clip=True, return_clipped=True)
+        hst.reset()
+        assert hst.frames == 0
+        again = _accumulate_all(hst, seq, clip=True, return_clipped=True)
+    for a, b in zip(first, again):
+        for x, y in zip(a, b):
+            assert x.tobytes() == y.tobytes()
+    assert (first[2][4] == 2).any() and (first[1][4] == 1).any()
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(device=dev)
+    mk = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+    with capi.History(0, w, h) as out_of_place, capi.History(0, w, h) as in_place:
+        for k, (cam, pl, _, _) in enumerate(seq):
+            tp = {key: torch.from_numpy(np.array(v)).to(dev) for key, v in pl.items()}
+            ptrs = dict(normal_ptr=tp["normal"].data_ptr(), albedo_ptr=tp["albedo"].data_ptr(), z_ptr=tp["z"].data_ptr(),
+                        object_id_ptr=tp["object_id"].data_ptr())
+            out, out_var, hist, rgb8, mask = mk(h, w, 3), mk(h, w, 3), mk(h, w), mk(h, w, 3, dt=torch.uint8), mk(h, w)
+            torch.cuda.synchronize()
+            out_of_place.accumulate_device(side.cuda_stream, cam, linear_ptr=tp["linear"].data_ptr(), out_ptr=out.data_ptr(),
+                                           variance_ptr=tp["variance"].data_ptr(), out_variance_ptr=out_var.data_ptr(),
+                                           history_ptr=hist.data_ptr(), rgb8_ptr=rgb8.data_ptr(), sync=False, clip=True,
+                                           clipped_ptr=mask.data_ptr(), **ptrs)
+            lin2, var2, mask2 = tp["linear"].clone(), tp["variance"].clone(), mk(h, w)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            in_place.accumulate_device(side.cuda_stream, cam, linear_ptr=lin2.data_ptr(), out_ptr=lin2.data_ptr(), variance_ptr=var2.data_ptr(),
+                                       out_variance_ptr=var2.data_ptr(), sync=False, clip=True, clipped_ptr=mask2.data_ptr(), **ptrs)
+            side.synchronize()
+            want = first[k]
+            for got, ref in ((out, want[0]), (out_var, want[1]), (rgb8, want[2]), (hist, want[3]), (mask, want[4]), (lin2, want[0]),
+                             (var2, want[1]), (mask2, want[4])):
+                assert got.cpu().numpy().tobytes() == ref.tobytes(), k
+            assert tp["linear"].cpu().numpy().tobytes() == pl["linear"].tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def _holes_reference(with_ids):
+    """two frames under camera A, the light switched between them; the second holds NaN colours and (with ids) id -1 pixels in
+    the middle of the wall and of the square.  Returns (camera, ((result, planes), ...))."""
+    w, h = 37, 23
+    cam = cam_a(w, h)
+    pl0, _ = frame(cam, 500, NOISE, light_smooth)
+    pl1, _ = frame(cam, 501, NOISE, light_dim)
+    lin, ids, z = pl1["linear"].copy(), pl1["object_id"].copy(), pl1["z"].copy()
+    lin[12, 8] = (np.nan, 0.3, 0.2)
+    lin[5, 20, 1] = np.inf
+    lin[11, 18] = np.nan                                        # on the square
+    for y, x in ((14, 9), (6, 25), (12, 19)):                   # holes: nothing hit, whatever the colour holds
+        ids[y, x], z[y, x], lin[y, x] = -1, BIG, F([7.5, np.nan, -1e30])
+    pl1 = dict(pl1, linear=lin, object_id=ids, z=z)
+    hist, out = {}, []
+    for pl in (pl0, pl1):
+        out.append((ref_temporal_clip(hist, cam, pl, with_ids, True), pl))
+    return cam, tuple(out)
+
+
+@pytest.mark.gpu
+def test_invalid_neighbours_stay_out_of_the_moments_and_pass_through():
+    for with_ids in (True, False):
+        cam, steps = _holes_reference(with_ids)
+        with capi.History(0, 37, 23) as hst:
+            for k, (r, pl) in enumerate(steps):
+                got, got_var, got_hist, mask = hst.accumulate(cam, pl["linear"], pl["normal"], pl["albedo"], pl["z"], variance=pl["variance"],
+                                                              object_id=pl["object_id"] if with_ids else None, return_history=True, clip=True,
+                                                              return_clipped=True)
+                part, keep = r["part"], r["part"] & ~r["left_out"]
+                delta = delta_px(cam, cam, float(pl["z"][part].min())) if k else 0.0
+                assert got[~part].tobytes() == pl["linear"][~part].tobytes() and got_var[~part].tobytes() == pl["variance"][~part].tobytes()
+                assert (got_hist[~part] == 0).all() and (mask[~part] == 0).all()
+                assert np.isfinite(got[part]).all() and np.isfinite(got_var[part]).all()
+                assert mask[keep].tobytes() == r["clipped"][keep].astype(np.float32).tobytes()
+                _gate(got, r["linear"], r["s_linear"], delta, keep, f"clip holes ids={with_ids} step {k} colour", 1e-6)
+                _gate(got_hist, r["history"], r["s_history"], delta, keep, f"clip holes ids={with_ids} step {k} history", 1e-6)
+        r, pl = steps[1]
+        bad = ~r["part"] & (np.arange(37)[None, :] < 30)
+        assert bad.sum() >= 6 and (r["clipped"] == 2).sum() > 300
+
+
+# ---- GPU: real frames -------------------------------------------------------------------------------------------
+def moved_light_rmse():
+    """cornell_gi.xml (live GI) at 96 x 72, 4 spp frames, reproducible mode: four frames, then the point light is moved
+    (set_lights), then two more, accumulated plainly and with the default rectification; and eight static frames with it.
+    Returns the RMSEs to 64 spp frames (under the new light; under the old one).  Also called by tools_temporal_clip_timing.py."""
+    s, cam = scenes.load_cornell_gi(96, 72)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    lights = s.export()["lights"].copy()
+    moved = lights.copy()
+    point = np.flatnonzero(moved["type"] == capi.LIGHT_POINT)
+    assert len(point) == 1
+    moved["position"][point[0]] = (9.0, -5.0, 18.0)
+    ref_static = s.render_outputs(cam, _gi_params(77, 64), planes=("linear", "object_id"))
+    with capi.History(0, 96, 72) as plain, capi.History(0, 96, 72) as rect, capi.History(0, 96, 72) as still:
+        for seed in range(1, 9):
+            st = s.render_temporal(still, cam, _gi_params(seed), denoise=False, clip=True)
+        for seed in range(1, 7):
+            if seed == 5:
+                s.set_lights(moved)
+            a = s.render_temporal(plain, cam, _gi_params(seed), denoise=False)
+            b = s.render_temporal(rect, cam, _gi_params(seed), denoise=False, clip=True)
+            assert a["linear"].tobytes() == b["linear"].tobytes()
+        ref_moved = s.render_outputs(cam, _gi_params(77, 64), planes=("linear", "object_id"))
+    s.set_lights(lights)
+
+    def rmse(x, ref):
+        valid = (b["object_id"] >= 0) & (ref["object_id"] >= 0)
+        return float(np.sqrt(((x[valid].astype(np.float64) - ref["linear"][valid]) ** 2).mean()))
+
+    hit = b["object_id"] >= 0
+    assert set(np.unique(b["clipped"][hit])) <= {1.0, 2.0} and (b["clipped"][~hit] == 0).all() and (b["clipped"] == 2).any()
+    e_plain, e_rect, e_frame = rmse(a["accumulated"], ref_moved), rmse(b["accumulated"], ref_moved), rmse(b["linear"], ref_moved)
+    s_rect, s_frame = rmse(st["accumulated"], ref_static), rmse(st["linear"], ref_static)
+    print(f"temporal clip cornell_gi 96x72, light moved after 4 of 6 frames: RMSE to 64 spp under the new light, one 4 spp frame {e_frame:.5f}, "
+          f"plain accumulation {e_plain:.5f}, rectified {e_rect:.5f} (rectified / plain = {e_rect / e_plain:.3f}); static, 8 frames: one frame "
+          f"{s_frame:.5f}, rectified accumulation {s_rect:.5f} (ratio {s_rect / s_frame:.3f}), clipped share in frame 8 "
+          f"{(st['clipped'][hit] == 2).mean():.3f}, mean history {st['history'][hit].mean():.2f}")
+    return dict(moved_light=dict(frame=e_frame, plain=e_plain, rectified=e_rect, rectified_over_plain=e_rect / e_plain),
+                static=dict(frame=s_frame, rectified=s_rect, rectified_over_frame=s_rect / s_frame,
+                            clipped_share_frame_8=float((st["clipped"][hit] == 2).mean()), mean_history=float(st["history"][hit].mean())))
+
+
+@pytest.mark.gpu
+def test_rectification_follows_a_moved_light_and_keeps_the_static_gain():
+    """Against a 64 spp frame under the new light the rectified accumulation is strictly closer than the plain one of the same
+    frames; on eight static frames the rectified accumulation stays closer to the 64 spp frame than one 4 spp frame is.  Only the
+    two orderings are asserted; the ratios are printed (README, profiles/temporal_clip_timing.json)."""
+    e = moved_light_rmse()
+    assert e["moved_light"]["rectified"] < e["moved_light"]["plain"], e
+    assert e["static"]["rectified"] < e["static"]["frame"], e
+
+
+@pytest.mark.gpu
+def test_cpp_shim_rectified_accumulation_equals_the_capi_one(tmp_path):
+    exe = _build_shim_driver(tmp_path)
+    prefix = str(tmp_path / "f")
+    r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert r.stdout.split()[1] == str(64 * 48) and r.stdout.split()[-1] == "2", r.stdout
+    s, cam = scenes.load_cornell(64, 48)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    with capi.History(0, 64, 48) as hst:
+        p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=11)
+        one = s.render_temporal(hst, cam, p, denoise=False, clip=True)
+        cam.pos[0] = float(F(cam.pos[0]) + F(0.3))
+        cam.pos[2] = float(F(cam.pos[2]) + F(0.1))
+        p.seed = 12
+        two = s.render_temporal(hst, cam, p, denoise=False, clip=True, moving=False)
+    assert capi.image_read_pfm(prefix + "_acc1.pfm").tobytes() == one["accumulated"].tobytes()
+    assert capi.image_read_pfm(prefix + "_acc2.pfm").tobytes() == two["accumulated"].tobytes()
+    assert capi.image_read_pfm1(prefix + "_len2.pfm").tobytes() == two["history"].tobytes()
+    assert capi.image_read_pfm1(prefix + "_clip2.pfm").tobytes() == two["clipped"].tobytes()
+    assert (one["clipped"] == 0).all() and (two["clipped"] > 0).mean() > 0.5
+
+
+@pytest.mark.gpu
+def test_render_temporal_rectifies_with_moving_nodes():
+    """render_temporal(moving=True, clip=...): the motion plane and the rectification in one call.  Nothing moved, so the plane
+    says "did not move" exactly where the cameras' reprojection rounds -- the two frames are equal only up to that rounding, so
+    the properties of the mask are checked, not bytes"""
+    s, cam = scenes.load_cornell(64, 48)
+    s.set_render_flags(capi.RENDER_REPRODUCIBLE)
+    p = capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=11)
+    with capi.History(0, 64, 48) as h1, capi.History(0, 64, 48) as h2:
+        for seed in (11, 12):
+            p.seed = seed
+            a = s.render_temporal(h1, cam, p, denoise=False, clip={"radius": 1}, moving=True)
+            b = s.render_temporal(h2, cam, p, denoise=False, clip={"radius": 1})
+        assert h1.frames == 2 and h2.frames == 2
+    assert "motion" in a and "motion" not in b and a["clipped"].shape == (48, 64) and a["clipped"].dtype == np.float32
+    hit = a["object_id"] >= 0
+    assert set(np.unique(a["clipped"])) <= {0.0, 1.0, 2.0} and (a["clipped"][hit] > 0).mean() > 0.5 and (a["clipped"][~hit] == 0).all()
+    assert (a["history"][a["clipped"] == 2] <= 3).all()
