@@ -998,6 +998,80 @@ rt_status rt_tonemap_device(rt_exposure *e, int device, void *hip_stream, int32_
 /* The planes are HOST arrays: upload, tone-map, download. */
 rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *host_planes);
 
+/* ---- bloom (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are unchanged) ----
+ * The stage ahead of "exposure and tone mapping": after the tone curve a light 50 times over white and one twice over white are
+ * the same flat patch.  Bloom spreads the energy above the display range into the neighbourhood BEFORE the curve, so that
+ * brightness stays visible as extent.  A linear float RGB plane (row-major, W x H x 3) in, one out; the reference has no
+ * counterpart.  Definition, in float, every operation rounded on its own (no fused multiply-add):
+ *   1. Exposure.  The threshold is relative to `scale`: scale = (float)exp2((double)exposure_ev) when no rt_exposure is passed
+ *      or the one passed holds no metered frame (since create / reset); otherwise the scale the state holds at that point of the
+ *      stream -- the PREVIOUS frame's when the frame's own rt_tonemap follows.  The kernel loads it from the state (as k_tonemap
+ *      does): the device entry never waits.  The stage does not meter and does not write the state.
+ *   2. Bright pass, per source pixel.  c = the pixel with every channel that is not finite or is negative replaced by 0.
+ *      Y = the luminance of c by step 1 of "exposure and tone mapping"; Ys = scale * Y.  With t = threshold, k = knee * t (rounded to float once):
+ *        x = min(max((Ys - t) + k, 0), 2 k);  s = (x * x) / (4 k + 1e-5f);  wgt = max(s, Ys - t) / max(Ys, 1e-5f)
+ *      (the soft knee: 0 up to Ys = t - k, quadratic up to t + k, Ys - t above; never more than 1).  threshold == 0: wgt = 1 for
+ *      every pixel.  Ys not finite (an overflow of scale * Y): wgt = 1.  The pixel contributes P = c * wgt per channel -- in
+ *      scene-linear units, not multiplied by scale.
+ *   3. Pyramid.  Level 0 is W_0 x H_0 = ceil(W / 2) x ceil(H / 2), level l + 1 is ceil(W_l / 2) x ceil(H_l / 2).  L = min(levels,
+ *      1 + the number of halvings that take level 0 to 1 x 1): no level is computed from a 1 x 1 level.  Downsample (level 0
+ *      from P, level l + 1 from level l): texel (i, j) is the separable 4-tap [1 3 3 1] / 8 over the source texels 2i-1 .. 2i+2
+ *      by 2j-1 .. 2j+2, indices clamped to the source's edge.  With f(a, b, c, d) = ((a + 3 b) + (3 c + d)) * 0.125f: the four
+ *      rows first, r_m = f(the row's four texels, left to right), then B = f(r_0, r_1, r_2, r_3), top to bottom.
+ *      Upsample up(X) of a level X (w x h) at a texel (x, y) of the next finer grid: per axis the near coarse index is x >> 1,
+ *      the far one x >> 1 + 1 when x is odd and x >> 1 - 1 when it is even, the far one clamped to 0 .. w-1; with
+ *      g(n, f) = 0.75f * n + 0.25f * f: the near row and the far row first, each g(near column, far column), then
+ *      g(near row's, far row's).  Every weight is non-negative and the weights of one output texel sum to 1, at edges and odd
+ *      sizes too (a clamped index only moves weight onto the edge texel).
+ *   4. Recombination, from the coarsest level up: U_{L-1} = B_{L-1}; U_l = a * B_l + spread * up(U_{l+1}), a = 1 - spread
+ *      rounded to float once.  A lerp, not a sum: a partition of unity whatever L is.
+ *   5. Output.  out = rgb + intensity * up(U_0), with the ORIGINAL pixel: a NaN pixel stays NaN and changes no other pixel.
+ *      out_bloom (optional) = up(U_0) alone.  A lane reads its own pixel before it writes it: out may be rgb_linear.  No other
+ *      planes may overlap.
+ *   6. No atomics, fixed orders: byte-identical outputs for identical inputs on one build.  A constant frame c with threshold 0
+ *      gives c (1 + intensity) to rounding; a frame wholly below Ys = t - k comes back bit for bit (finite, no -0).
+ *   Sums that overflow float (pixels near FLT_MAX) are outside the definition.
+ * rt_bloom owns the pyramid of one W x H stream of frames on one device (16 bytes per source pixel at most), so the device entry
+ * never allocates.  Calls on one rt_bloom are ordered on the GPU one behind the other, whatever their streams; a call that is
+ * given an rt_exposure is also ordered behind the earlier calls on that state, and the state's later calls behind it.
+ * Everything is checked before the GPU is touched and is RT_ERR_ARG: NULL arguments, a struct_size that is not the caller's
+ * sizeof, w or h <= 0, threshold / knee / intensity / spread not finite or negative, spread > 1, knee > 1, levels < 1,
+ * exposure_ev not finite, an rt_exposure on another device than the rt_bloom, a NULL rgb_linear, no output plane, planes that
+ * overlap other than out == rgb_linear.  More than 2^30 pixels: RT_ERR_LIMIT.  Then, without a gfx950 device:
+ * RT_ERR_NO_DEVICE (there is no CPU path). */
+typedef struct rt_bloom rt_bloom;
+typedef struct rt_bloom_params {
+    uint32_t struct_size;
+    float    threshold;         /* 1    : bright-pass threshold, relative to scale: display white        */
+    float    knee;              /* 0.5  : soft-knee width as a fraction of threshold, 0..1               */
+    float    intensity;         /* 0.25 : weight of the bloom plane in the output                        */
+    float    spread;            /* 0.7  : lerp weight towards the coarser level in the recombination, 0..1 */
+    int32_t  levels;            /* 6    : pyramid levels requested, >= 1 (clipped to what the size allows) */
+    float    exposure_ev;       /* 0    : fixed exposure, in stops, when no metered state applies        */
+} rt_bloom_params;
+typedef struct rt_bloom_planes {
+    uint32_t struct_size;
+    const float *rgb_linear;
+    float *out;                 /* optional, may be rgb_linear */
+    float *out_bloom;           /* optional: up(U_0) alone     */
+} rt_bloom_planes;
+/* w, h <= 0 or out == NULL: RT_ERR_ARG; more than 2^30 pixels: RT_ERR_LIMIT; no gfx950 device: RT_ERR_NO_DEVICE */
+rt_status rt_bloom_create(int device, int32_t w, int32_t h, rt_bloom **out);
+/* NULL is ignored; waits for the work that still uses it */
+void      rt_bloom_destroy(rt_bloom *b);
+void      rt_bloom_default_params(rt_bloom_params *p);
+/* DIAGNOSTIC ONLY, for tests and timing tools; nothing a caller needs.  What a call on a w x h frame runs, without a device:
+ * *levels_used = L of step 3; *tail_level = -1 in the shipped build (every level is a launch of its own), and in a build with
+ * k_bloom_tail (RT_BLOOM_TAIL=1) the level from which its one workgroup runs the rest of the pyramid inside LDS, -1 when no
+ * level is left to it.  tail_level says how a build schedules its launches, never what it computes. */
+rt_status rt_bloom_plan(int32_t w, int32_t h, int32_t levels, int32_t *levels_used, int32_t *tail_level);
+/* The planes are DEVICE pointers on the rt_bloom's device; the kernels are enqueued on `hip_stream` (NULL = the device's legacy
+ * null stream) and the call returns without waiting for them unless `sync` is non-zero.  e may be NULL. */
+rt_status rt_bloom_device(rt_bloom *b, rt_exposure *e, void *hip_stream, const rt_bloom_params *p,
+                          const rt_bloom_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, run, download. */
+rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *host_planes);
+
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */
 /* n closest-hit queries = n calls of TraceNode(rootNode, ray, hit) (FIN/main.cpp:94-130).

@@ -131,6 +131,21 @@ class ToneMapPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(ToneMapPlanes), **planes)
 
 
+class BloomParams(C.Structure):
+    """rt_bloom_params: bloom ahead of tone mapping (rt_bloom_default_params fills threshold 1, knee 0.5, intensity 0.25, spread 0.7,
+    levels 6, exposure_ev 0)"""
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("spread", C.c_float),
+                ("levels", C.c_int32), ("exposure_ev", C.c_float)]
+
+
+class BloomPlanes(C.Structure):
+    """rt_bloom_planes: the input and outputs of one bloomed frame.  One of out (may be rgb_linear) and out_bloom is required."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("out", C.c_void_p), ("out_bloom", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(BloomPlanes), **planes)
+
+
 # rt_tonemap_params.op (include/rt_mi355x.h)
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 TONEMAP_OPERATORS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
@@ -197,6 +212,7 @@ SYMBOLS = [
     "rt_temporal_clip_default", "rt_temporal_clip_device", "rt_temporal_clip_host",
     "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
     "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
+    "rt_bloom_create", "rt_bloom_destroy", "rt_bloom_default_params", "rt_bloom_plan", "rt_bloom_device", "rt_bloom_host",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
 ]
 
@@ -299,6 +315,17 @@ def lib():
         _lib.rt_tonemap_device.argtypes = [vp, C.c_int, vp, i32, i32, vp, vp, C.c_int]
         _lib.rt_tonemap.argtypes = [vp, C.c_int, i32, i32, vp, vp]
         for name in ("rt_exposure_create", "rt_exposure_reset", "rt_exposure_get", "rt_exposure_histogram", "rt_tonemap_device", "rt_tonemap"):
+            getattr(_lib, name).restype = C.c_int
+        # bloom (rt_mi355x.h: "bloom")
+        _lib.rt_bloom_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        _lib.rt_bloom_destroy.argtypes = [vp]
+        _lib.rt_bloom_destroy.restype = None
+        _lib.rt_bloom_default_params.argtypes = [vp]
+        _lib.rt_bloom_default_params.restype = None
+        _lib.rt_bloom_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        _lib.rt_bloom_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
+        _lib.rt_bloom_host.argtypes = [vp, vp, vp, vp]
+        for name in ("rt_bloom_create", "rt_bloom_plan", "rt_bloom_device", "rt_bloom_host"):
             getattr(_lib, name).restype = C.c_int
         # the packed planes of the multi-GPU exchange (rt_mi355x.h: "packed planes")
         _lib.rt_tiles_packed_planes_size.argtypes = [i32, i32, vp, C.c_uint32, vp, vp, vp]
@@ -827,6 +854,73 @@ class Exposure:
         _check(lib().rt_tonemap_device(self._h, self.device, _stream_handle(stream), int(w), int(h), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
+def bloom_params(**kw):
+    """rt_bloom_default_params, then the keywords: threshold, knee, intensity, spread, levels, exposure_ev"""
+    p = BloomParams()
+    lib().rt_bloom_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("threshold", "knee", "intensity", "spread", "levels", "exposure_ev"):
+            raise TypeError(f"no bloom parameter {k!r}")
+        setattr(p, k, int(v) if k == "levels" else v)
+    return p
+
+
+def bloom_plan(w, h, levels=6):
+    """rt_bloom_plan: (the levels a w x h frame gets, the level k_bloom_tail starts at or -1); needs no device"""
+    used, tail = C.c_int32(), C.c_int32()
+    _check(lib().rt_bloom_plan(int(w), int(h), int(levels), C.byref(used), C.byref(tail)))
+    return used.value, tail.value
+
+
+class Bloom:
+    """rt_bloom: the bloom stage of one w x h stream of frames on one device (the definition: rt_mi355x.h, "bloom"); it owns the
+    pyramid's device memory.  A context manager; close() (or the end of the with block) frees it."""
+
+    def __init__(self, device, w, h):
+        self._h = C.c_void_p()
+        self.device, self.w, self.h = int(device), int(w), int(h)
+        _check(lib().rt_bloom_create(self.device, self.w, self.h, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rt_bloom_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, linear, exposure=None, return_bloom=False, **params):
+        """rt_bloom_host on a float32 (H, W, 3) host array: the bloomed plane -- and, return_bloom=True, the bloom plane alone as a
+        tuple's second.  exposure: an Exposure on the same device whose scale the threshold is relative to (it is only read; a
+        state without a metered frame, like None, means 2^exposure_ev).  params: bloom_params()."""
+        linear = _c(linear, np.float32)
+        assert linear.shape == (self.h, self.w, 3)
+        out = np.empty_like(linear)
+        only = np.empty_like(linear) if return_bloom else None
+        pl = BloomPlanes(rgb_linear=linear.ctypes.data, out=out.ctypes.data, out_bloom=only.ctypes.data if return_bloom else None)
+        p = bloom_params(**params)
+        _check(lib().rt_bloom_host(self._h, exposure._h if exposure is not None else None, C.byref(p), C.byref(pl)))
+        return (out, only) if return_bloom else out
+
+    def apply_device(self, stream, *, linear_ptr, out_ptr, bloom_ptr=None, exposure=None, sync=False, **params):
+        """rt_bloom_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
+        explicit stream's handle; None = the null stream of the device) without a host round trip.  out_ptr may be linear_ptr
+        (in place), or None when only bloom_ptr is wanted."""
+        pl = BloomPlanes(rgb_linear=linear_ptr, out=out_ptr, out_bloom=bloom_ptr)
+        p = bloom_params(**params)
+        _check(lib().rt_bloom_device(self._h, exposure._h if exposure is not None else None, _stream_handle(stream), C.byref(p), C.byref(pl),
+                                     1 if sync else 0))
+
+
 def identity_map(texture=MAP_NONE):
     m = np.zeros(1, TEXMAP)
     m["texture"] = texture
@@ -1111,13 +1205,17 @@ class Scene:
         out["rgb"], out["z"], out["count"], out["stats"], out["progress"] = self._render(cam, params, tiles, device, photon_pass, None, dict(out))
         return out
 
-    def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, exposure=None, tonemap_kw=None, **denoise_kw):
+    def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, exposure=None, tonemap_kw=None, bloom=None,
+                        bloom_kw=None, **denoise_kw):
         """render_outputs with the linear plane and the four feature planes, then denoise() of that frame guided by them
         (gamma: the render's): the same dict with "denoised" (float32 (H, W, 3), linear) and "denoised_rgb" (uint8 (H, W, 3))
         added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth.  variance=True: the render also fills
         out["variance"] and the denoise is the variance-guided one (denoise_kw: also k_sigma); "denoised_variance" is added.
         exposure: an Exposure on `device` -- the denoised plane is metered (with the frame's object_id) and tone-mapped, and
-        "display_rgb" (uint8 (H, W, 3)) is added; tonemap_kw: a dict of Exposure.tonemap's keywords (operator, key, ...)."""
+        "display_rgb" (uint8 (H, W, 3)) is added; tonemap_kw: a dict of Exposure.tonemap's keywords (operator, key, ...).
+        bloom: a Bloom of the camera's size on `device` -- the denoised plane is bloomed first (relative to the scale `exposure`
+        holds from the frame before; bloom_kw: a dict of Bloom.apply's keywords), "bloomed" (float32 (H, W, 3)) is added and
+        "display_rgb" is made from it."""
         planes = ("linear",) + FEATURE_PLANES + (("variance",) if variance else ())
         out = self.render_outputs(cam, params, planes=planes, device=device, photon_pass=photon_pass)
         denoise_kw.setdefault("gamma", params.gamma)
@@ -1128,11 +1226,15 @@ class Scene:
         else:
             out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
                                                            rgb8=True, device=device, **denoise_kw)
+        final = out["denoised"]
+        if bloom is not None:
+            final = out["bloomed"] = bloom.apply(final, exposure=exposure, **(bloom_kw or {}))
         if exposure is not None:
-            out["display_rgb"] = exposure.tonemap(out["denoised"], out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
+            out["display_rgb"] = exposure.tonemap(final, out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
-    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None, **kw):
+    def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None,
+                        bloom=None, bloom_kw=None, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
@@ -1151,7 +1253,9 @@ class Scene:
         takes the nodes as not moved since, and the camera from the history as rt_temporal does (prev_cam cannot be known here,
         so that frame is accumulated WITHOUT a motion plane; "motion" is still added, computed with prev_cam = cam).
         clip: history rectification, as History.accumulate's (True, or a dict of radius, k_clip, min_count, clip_history);
-        "clipped" (float32 (H, W): 0 no history, 1 kept, 2 clipped) is added.  Works with moving=True."""
+        "clipped" (float32 (H, W): 0 no history, 1 kept, 2 clipped) is added.  Works with moving=True.
+        bloom: a Bloom of the camera's size on `device` -- the final linear plane is bloomed before it is tone-mapped, as in
+        render_denoised: "bloomed" is added and "display_rgb" is made from it; bloom_kw: a dict of Bloom.apply's keywords."""
         photon_pass = kw.pop("photon_pass", False)
         t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
         d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
@@ -1176,9 +1280,11 @@ class Scene:
             out["denoised"], out["denoised_rgb"] = _denoise(
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
+        final = out["denoised" if denoise else "accumulated"]
+        if bloom is not None:
+            final = out["bloomed"] = bloom.apply(final, exposure=exposure, **(bloom_kw or {}))
         if exposure is not None:
-            out["display_rgb"] = exposure.tonemap(out["denoised" if denoise else "accumulated"], out["object_id"],
-                                                  **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
+            out["display_rgb"] = exposure.tonemap(final, out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
     def _motion_since(self, history, cam, z, object_id, device):

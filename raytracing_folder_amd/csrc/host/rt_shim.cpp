@@ -20,13 +20,23 @@ void RenderImage::Init(int w, int h)
     rt_history_destroy(history);        // a history is of one size
     history = nullptr;
     display.clear(); displayImg.clear();
+    rt_bloom_destroy(bloom);            // a pyramid is of one size
+    bloom = nullptr;
+    bloomed.clear();
     finalPixels = 0;
+}
+
+void RenderImage::EnableBloom(const rt_bloom_params *params)
+{
+    if (params) bloomParams = *params;
+    else rt_bloom_default_params(&bloomParams);
+    bloomEnabled = true;
 }
 
 void RenderImage::ResetToneMap()
 {
     if (exposure) rt_exposure_reset(exposure);
-    display.clear(); displayImg.clear();
+    display.clear(); displayImg.clear(); bloomed.clear();
 }
 
 float RenderImage::ToneMapExposure() const
@@ -46,12 +56,24 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
     rt_tonemap_params defaults;
     rt_tonemap_default_params(&defaults);
     const size_t n = (size_t)width * height;
-    const std::vector<float> &src = !denoised.empty() ? denoised : (!accumulated.empty() ? accumulated : linear);
+    const std::vector<float> *from = !denoised.empty() ? &denoised : (!accumulated.empty() ? &accumulated : &linear);
+    std::vector<float> glare;
+    if (bloomEnabled) {                 // ahead of the curve, relative to the scale the state holds from the call before
+        if (bloom && bloomDevice != device) { rt_bloom_destroy(bloom); bloom = nullptr; }
+        if (!bloom && rt_bloom_create(device, width, height, &bloom) != RT_OK) { toneMapError = rt_last_error(); return false; }
+        bloomDevice = device;
+        glare.resize(n * 3);
+        const rt_bloom_planes bp = {(uint32_t)sizeof(rt_bloom_planes), from->data(), glare.data(), nullptr};
+        if (rt_bloom_host(bloom, exposure, &bloomParams, &bp) != RT_OK) { toneMapError = rt_last_error(); return false; }
+        from = &glare;
+    }
+    const std::vector<float> &src = *from;
     std::vector<float> out(n * 3);
     std::vector<uint8_t> out8(n * 3);
     const rt_tonemap_planes pl = {(uint32_t)sizeof(rt_tonemap_planes), src.data(), featuresEnabled ? objectIds.data() : nullptr, out.data(), out8.data()};
     if (rt_tonemap(exposure, device, width, height, params ? params : &defaults, &pl) != RT_OK) { toneMapError = rt_last_error(); return false; }
     display.swap(out); displayImg.swap(out8);
+    if (bloomEnabled) bloomed.swap(glare);
     toneMapError.clear();
     return true;
 }

@@ -52,6 +52,12 @@ class RenderImage {
     rt_exposure *exposure = nullptr;
     int exposureDevice = 0;
     std::string toneMapError;
+    // opt-in (EnableBloom): ToneMap() blooms the plane first; the bloomed linear plane and the rt_bloom that owns the pyramid
+    std::vector<float> bloomed;
+    bool bloomEnabled = false;
+    rt_bloom_params bloomParams = {};
+    rt_bloom *bloom = nullptr;
+    int bloomDevice = 0;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -61,7 +67,7 @@ public:
     RenderImage() = default;
     RenderImage(const RenderImage &) = delete;
     RenderImage &operator=(const RenderImage &) = delete;
-    ~RenderImage() { rt_history_destroy(history); rt_exposure_destroy(exposure); }
+    ~RenderImage() { rt_history_destroy(history); rt_bloom_destroy(bloom); rt_exposure_destroy(exposure); }
     void Init(int w, int h);
     int GetWidth() const { return width; }
     int GetHeight() const { return height; }
@@ -156,6 +162,14 @@ public:
     float *GetDisplayPixels() { return display.empty() ? nullptr : display.data(); }            // display-referred float RGB
     uint8_t *GetDisplayImage() { return displayImg.empty() ? nullptr : displayImg.data(); }     // Color24 after gamma
     bool SaveDisplayImage(const char *filename) const { return !displayImg.empty() && WritePNG(filename, displayImg.data(), width, height, 3); }
+    // Bloom (rt_mi355x.h, "bloom"): from now on ToneMap() blooms the plane it would tone-map -- relative to the scale the exposure
+    // state holds from the call before -- and tone-maps the result.  params == NULL: the defaults of rt_bloom_default_params.
+    // The rt_bloom is created by the first ToneMap(), on its device, and lives until the image is destroyed, Init() changes the
+    // size or another device is named.  GetBloomed() is the bloomed linear plane, NULL until a ToneMap() has succeeded with it.
+    void EnableBloom(const rt_bloom_params *params = nullptr);
+    bool BloomEnabled() const { return bloomEnabled; }
+    float *GetBloomed() { return bloomed.empty() ? nullptr : bloomed.data(); }                  // linear float RGB
+    bool SaveBloomedImage(const char *filename) const { return !bloomed.empty() && WritePFM(filename, bloomed.data(), width, height); }   // PFM
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

@@ -3043,6 +3043,144 @@ extern "C" rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h
     return RT_OK;
 }
 
+// ---- bloom ------------------------------------------------------------------------------------------------------------------
+// An rt_bloom owns the pyramid of one W x H stream of frames on its device -- every level the size allows, whatever `levels` a
+// call asks for -- and the event that orders a call behind the previous one on the same object.
+struct rt_bloom {
+    int device = 0; int32_t w = 0, h = 0;
+    DevBuf pyramid;
+    hipEvent_t done = nullptr; bool pending = false;
+    std::mutex mu;
+};
+
+extern "C" rt_status rt_bloom_create(int device, int32_t w, int32_t h, rt_bloom **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_bloom_create: out is NULL");
+    *out = nullptr;
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_bloom_create: bad image size %d x %d", w, h);
+    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_bloom_create: %d x %d is more than 2^30 pixels", w, h);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_bloom_create: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    rt_bloom *b = new rt_bloom;
+    b->device = device; b->w = w; b->h = h;
+    const BloomPlan all = rtk_bloom_plan(w, h, RT_BLOOM_MAX_LEVELS);
+    rt_status st = b->pyramid.ensure(all.off[all.levels] * 12);
+    if (st == RT_OK && hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_bloom_create: hipEventCreate failed");
+    if (st) { rt_bloom_destroy(b); return st; }
+    *out = b;
+    return RT_OK;
+}
+
+extern "C" void rt_bloom_destroy(rt_bloom *b)
+{
+    if (!b) return;
+    if (hipSetDevice(b->device) == hipSuccess) {
+        if (b->pending) (void)hipEventSynchronize(b->done);
+        b->pyramid.release();           // hipFree waits for the kernels that still use it
+        if (b->done) (void)hipEventDestroy(b->done);
+    }
+    delete b;
+}
+
+extern "C" void rt_bloom_default_params(rt_bloom_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->threshold = 1.0f; p->knee = 0.5f; p->intensity = 0.25f; p->spread = 0.7f; p->levels = 6; p->exposure_ev = 0.0f;
+}
+
+extern "C" rt_status rt_bloom_plan(int32_t w, int32_t h, int32_t levels, int32_t *levels_used, int32_t *tail_level)
+{
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_bloom_plan: bad image size %d x %d", w, h);
+    if (levels < 1) return fail(RT_ERR_ARG, "rt_bloom_plan: levels is %d, must be at least 1", levels);
+    const BloomPlan P = rtk_bloom_plan(w, h, levels);
+    if (levels_used) *levels_used = P.levels;
+    if (tail_level) *tail_level = P.tail;
+    return RT_OK;
+}
+
+static bool bloom_overlap(const void *a, const void *b, size_t bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + bytes && y < x + bytes;
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status bloom_check(const char *name, const rt_bloom *b, const rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *pl)
+{
+    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
+    if (p->struct_size != (uint32_t)sizeof(rt_bloom_params))
+        return fail(RT_ERR_ARG, "%s: rt_bloom_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_bloom_params));
+    if (pl->struct_size != (uint32_t)sizeof(rt_bloom_planes))
+        return fail(RT_ERR_ARG, "%s: rt_bloom_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_bloom_planes));
+    for (float s : {p->threshold, p->knee, p->intensity, p->spread})
+        if (!(s >= 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: threshold, knee, intensity and spread must be finite and not negative", name);
+    if (p->spread > 1.0f || p->knee > 1.0f) return fail(RT_ERR_ARG, "%s: spread and knee must be at most 1", name);
+    if (p->levels < 1) return fail(RT_ERR_ARG, "%s: levels is %d, must be at least 1", name, p->levels);
+    if (!std::isfinite(p->exposure_ev)) return fail(RT_ERR_ARG, "%s: exposure_ev must be finite", name);
+    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
+    if (!pl->out && !pl->out_bloom) return fail(RT_ERR_ARG, "%s: one of out and out_bloom is required", name);
+    // what needs the object comes last: without a device there is none, and everything above is still refused by name
+    if (!b) return fail(RT_ERR_ARG, "%s: the rt_bloom is NULL", name);
+    if (e && e->device != b->device) return fail(RT_ERR_ARG, "%s: the exposure state is on device %d, the rt_bloom on %d", name, e->device, b->device);
+    const size_t bytes = (size_t)b->w * (size_t)b->h * 12;
+    if ((pl->out != pl->rgb_linear && bloom_overlap(pl->out, pl->rgb_linear, bytes)) || bloom_overlap(pl->out_bloom, pl->rgb_linear, bytes) ||
+        bloom_overlap(pl->out_bloom, pl->out, bytes))
+        return fail(RT_ERR_ARG, "%s: planes overlap (only out == rgb_linear is allowed)", name);
+    return RT_OK;
+}
+
+static rt_status bloom_on_device(rt_bloom *b, rt_exposure *e, hipStream_t st, const rt_bloom_params *p, const rt_bloom_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    BloomRequest R = {};
+    R.width = b->w; R.height = b->h;
+    R.threshold = p->threshold; R.knee_k = p->knee * p->threshold; R.intensity = p->intensity;
+    R.spread = p->spread; R.one_minus_spread = 1.0f - p->spread;
+    R.scale = (float)exp2((double)p->exposure_ev);
+    R.rgb_linear = pl->rgb_linear; R.out = pl->out; R.out_bloom = pl->out_bloom;
+    R.plan = rtk_bloom_plan(b->w, b->h, p->levels);
+    std::lock_guard<std::mutex> lk(b->mu);
+    std::unique_lock<std::mutex> le;
+    if (e) le = std::unique_lock<std::mutex>(e->mu);
+    R.pyramid = (float *)b->pyramid.p;
+    if (b->pending) HIP_TRY(hipStreamWaitEvent(st, b->done, 0));
+    if (e) {                            // the state is read: behind the calls that write it, and the next one of them behind this
+        if (e->pending) HIP_TRY(hipStreamWaitEvent(st, e->done, 0));
+        R.state = (const ToneMapRequest::State *)e->block.p;
+    }
+    HIP_TRY(rtk_launch_bloom(st, R));
+    HIP_TRY(hipEventRecord(b->done, st));
+    b->pending = true;
+    if (e) { HIP_TRY(hipEventRecord(e->done, st)); e->pending = true; }
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); b->pending = false; if (e) e->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_bloom_device(rt_bloom *b, rt_exposure *e, void *hip_stream, const rt_bloom_params *p,
+                                     const rt_bloom_planes *device_planes, int sync)
+{
+    rt_status st = bloom_check("rt_bloom_device", b, e, p, device_planes);
+    if (st) return st;
+    return bloom_on_device(b, e, (hipStream_t)hip_stream, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *host_planes)
+{
+    rt_status st = bloom_check("rt_bloom_host", b, e, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t n = (size_t)b->w * (size_t)b->h;
+    ScopedDevBuf rgb, only;                                         // `out` is written in place into rgb
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12))) return st;
+    if (host_planes->out_bloom && (st = only.ensure(n * 12))) return st;
+    const rt_bloom_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, host_planes->out ? (float *)rgb.p : nullptr, (float *)only.p};
+    if ((st = bloom_on_device(b, e, nullptr, p, &dev, 1))) return st;
+    if (host_planes->out) HIP_TRY(hipMemcpy(host_planes->out, rgb.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_bloom) HIP_TRY(hipMemcpy(host_planes->out_bloom, only.p, n * 12, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");

@@ -41,4 +41,11 @@ __device__ __forceinline__ uint8_t float_to_byte(float r)
     return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// step 1 of "exposure and tone mapping" (rt_mi355x.h), which "bloom" takes its luminance from:
+// Y = ((0.2126 r) + (0.7152 g)) + (0.0722 b), every product and sum rounded to float on its own
+__device__ __forceinline__ float tonemap_luminance(float r, float g, float b)
+{
+    return __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, r), __fmul_rn(0.7152f, g)), __fmul_rn(0.0722f, b));
+}
+
 #endif

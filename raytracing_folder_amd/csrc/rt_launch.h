@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip): every rtk_* function, the requests they take and the
-// records they exchange.  All eight files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip): every rtk_* function, the requests they take and the
+// records they exchange.  All nine files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -166,6 +166,26 @@ struct ToneMapRequest {
     const float *rgb_linear; const int32_t *object_id; float *out_display; uint8_t *out_rgb8;
 };
 
+// One bloomed width x height frame (rt_bloom.hip; the definition: rt_mi355x.h, "bloom").  The planes are the caller's device
+// pointers (one of out / out_bloom may be NULL; out may be rgb_linear), the parameters are validated by the caller.  state: NULL,
+// or an rt_exposure's block -- k_bloom_prefilter takes its scale when it holds a metered frame, else `scale`; it is only read.
+// pyramid: the rt_bloom's scratch, the levels one behind the other, 3 floats a texel (bloom_plan's offsets).
+#define RT_BLOOM_MAX_LEVELS 32
+struct BloomPlan {
+    int levels;                         // L of step 3
+    int tail;                           // k_bloom_tail starts at this level and runs levels tail .. L-1 in LDS; -1: no tail launch
+    int w[RT_BLOOM_MAX_LEVELS], h[RT_BLOOM_MAX_LEVELS];
+    size_t off[RT_BLOOM_MAX_LEVELS + 1];        // in texels; off[levels] = the texels of the whole pyramid
+};
+struct BloomRequest {
+    int width, height;
+    float threshold, knee_k, intensity, spread, one_minus_spread, scale;   // knee_k = knee * threshold; scale = 2^exposure_ev
+    const ToneMapRequest::State *state;
+    const float *rgb_linear; float *out, *out_bloom;
+    float *pyramid;
+    BloomPlan plan;
+};
+
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -222,6 +242,12 @@ void rtk_launch_motion(hipStream_t st, const MotionRequest &R);
 // ---- rt_tonemap.hip: exposure and tone mapping ---------------------------------------------------------------------------
 // on `st`: k_luminance_hist and k_exposure_meter (when R.meter), then k_tonemap<R.op>
 void rtk_launch_tonemap(hipStream_t st, const ToneMapRequest &R);
+
+// ---- rt_bloom.hip: bloom ahead of tone mapping ------------------------------------------------------------------------------
+// the levels a width x height frame gets for `levels` requested, their sizes and offsets, and where the tail kernel starts
+BloomPlan rtk_bloom_plan(int width, int height, int levels);
+// on `st`: k_bloom_prefilter, k_bloom_down per level above the tail, k_bloom_tail, k_bloom_up per level above it, k_bloom_combine
+hipError_t rtk_launch_bloom(hipStream_t st, const BloomRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

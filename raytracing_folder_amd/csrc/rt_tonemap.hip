@@ -39,12 +39,6 @@
 
 typedef ToneMapRequest::State ExposureState;
 
-// step 1: Y = ((0.2126 r) + (0.7152 g)) + (0.0722 b), every product and sum rounded to float on its own
-__device__ __forceinline__ float tonemap_luminance(float r, float g, float b)
-{
-    return __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, r), __fmul_rn(0.7152f, g)), __fmul_rn(0.0722f, b));
-}
-
 __global__ __launch_bounds__(RT_TONEMAP_BLOCK) void k_luminance_hist(const float *rgb, const int32_t *object_id, uint32_t n, uint32_t *hist)
 {
 #if RT_TONEMAP_HIST == 1
