@@ -1072,6 +1072,77 @@ rt_status rt_bloom_device(rt_bloom *b, rt_exposure *e, void *hip_stream, const r
 /* The planes are HOST arrays: upload, run, download. */
 rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *host_planes);
 
+/* ---- motion blur (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are unchanged) ----
+ * The stage between the denoise and "bloom": every frame is an instantaneous shutter, so a fast node strobes from frame to frame, and
+ * temporal accumulation rejects exactly that history.  Motion blur stands in for the open shutter, in image space, from planes the
+ * chain already has (after McGuire et al. 2012, "A reconstruction filter for plausible motion blur"): tile-max velocity,
+ * neighbour-max velocity and a depth-aware gather along the dominant velocity.  The reference has no counterpart.
+ * Inputs, all row-major and W x H: rgb_linear (float x 3), motion (float x 3, the plane of "motion vectors": (fx, fy, z_exp)) and z
+ * (float, this frame's depth).  Parameters: shutter, max_blur (K), samples (N), depth_extent.  Definition, in float, every operation
+ * rounded on its own (no fused multiply-add); sqrtf and the divisions are the correctly rounded ones:
+ *   1. Velocity of the pixel p = (x, y): v = (h * ((float)x - fx), h * ((float)y - fy)) with h = 0.5f * shutter rounded once: the blur
+ *      is shutter times the displacement long and centred on p.  v = (0, 0) when z_exp <= 0 or one of fx, fy, z_exp is not finite
+ *      (the markers of "no previous position").  m = vx * vx + vy * vy.
+ *   2. Tile max.  K x K tiles from (0, 0), partial ones at the right and bottom: TX = ceil(W / K) by TY = ceil(H / K).  A tile's
+ *      value is the v of its pixel with the largest m; among equal m the lowest row-major pixel index wins.  Only m is compared:
+ *      no sqrt, and (max m, then min index) is associative, so any reduction order gives the same bits.
+ *   3. Neighbour max.  Per tile, the tile-max value with the largest m (taken again from the stored v) over the 3 x 3 tiles around
+ *      it; tiles outside the grid are skipped; among equal m the first in row-major order of the 3 x 3.  This is vn, UNCLAMPED.
+ *   4. Clamp, applied only where a velocity is used, never before a selection: clampK(v) = v when m <= K * K, else
+ *      v * (K / sqrtf(m)) per component; its length is lenK(m) = min(sqrtf(m), (float)K).
+ *   5. Early out.  vn's m < 0.25f (half a pixel): out[p] = rgb[p] bit for bit -- a static frame comes back byte-identical.
+ *   6. Gather, otherwise.  c = clampK(vn), L = lenK(vn's m), lp = max(lenK(m of p), 0.5f).  rgb[p] with a channel that is not
+ *      finite: out[p] = rgb[p].  Else N taps i = 0 .. N-1, in this order:
+ *        j = {0, 2, 3, 1}[(y & 1) * 2 + (x & 1)];  a_i = (float)i + (0.125f + 0.25f * j);  t_i = a_i * g - 1 with g = 2 / N rounded once;
+ *        q = ((float)x + t_i * c.x, (float)y + t_i * c.y);  the tap pixel s = (floorf(q.x + 0.5f), floorf(q.y + 0.5f)).
+ *      A tap outside the image, or with a colour channel that is not finite, has weight 0.  Otherwise, with d = |t_i| * L,
+ *      ls = max(lenK(m of s), 0.5f), and every z that is not finite or is >= 1e30 counted as 1e30f:
+ *        cone(d, l) = min(max(1 - d / l, 0), 1)
+ *        cyl(d, l)  = 1 - (u * u) * (3 - 2 * u),  u = min(max((d - 0.95f * l) / (1.05f * l - 0.95f * l), 0), 1)
+ *        near(a, b) = min(max(1 - (a - b) / e, 0), 1),  e = depth_extent * max(min(a, b), 1e-6f)
+ *        w_i = (near(z_s, z_p) * cone(d, ls) + near(z_p, z_s) * cone(d, lp)) + 2 * (cyl(d, ls) * cyl(d, lp))
+ *      The centre: w_p = 1 / lp on rgb[p].  Per channel, sums from the centre term on, taps in order:
+ *        out[p] = (w_p * rgb[p] + sum w_i * rgb[s_i]) / (w_p + sum w_i)
+ *      Every l is at least 0.5 and w_p at least 1 / K, so no NaN arises from finite colours.
+ *   7. No atomics, fixed orders: byte-identical outputs for identical inputs on one build.  The weights are normalised: a frame
+ *      of one colour keeps it to rounding whatever the motion.  out must NOT be rgb_linear (the gather reads neighbours), and no
+ *      two planes may overlap.  Products that overflow float (colours near FLT_MAX) are outside the definition.
+ * rt_motion_blur owns the two tile planes of one W x H stream of frames on one device, sized for the smallest K, so the device entry
+ * never allocates.  Calls on one rt_motion_blur are ordered on the GPU one behind the other, whatever their streams.
+ * Everything is checked before the GPU is touched and is RT_ERR_ARG: NULL arguments, a struct_size that is not the caller's sizeof,
+ * w or h <= 0, shutter not finite, negative or > 2, max_blur outside 2..32, samples outside 3..63 or even, depth_extent not finite
+ * or < 1e-3, a NULL rgb_linear, motion, z or out, planes that overlap.  More than 2^30 pixels: RT_ERR_LIMIT.  Then, without a
+ * gfx950 device: RT_ERR_NO_DEVICE (there is no CPU path). */
+typedef struct rt_motion_blur rt_motion_blur;
+typedef struct rt_motion_blur_params {
+    uint32_t struct_size;
+    float    shutter;           /* 0.5  : the fraction of the frame interval the shutter is open, 0..2      */
+    int32_t  max_blur;          /* 16   : K, the tile size and the longest half-extent of a blur in pixels, 2..32 */
+    int32_t  samples;           /* 15   : N, taps per pixel, odd, 3..63                                     */
+    float    depth_extent;      /* 0.05 : the relative depth difference over which near() falls from 1 to 0 */
+} rt_motion_blur_params;
+typedef struct rt_motion_blur_planes {
+    uint32_t struct_size;
+    const float *rgb_linear;
+    const float *motion;
+    const float *z;
+    float *out;                 /* not rgb_linear */
+    float *out_tiles;           /* optional: float TX*TY*2, the UNCLAMPED neighbour-max vector of each tile */
+} rt_motion_blur_planes;
+/* w, h <= 0 or out == NULL: RT_ERR_ARG; more than 2^30 pixels: RT_ERR_LIMIT; no gfx950 device: RT_ERR_NO_DEVICE */
+rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_motion_blur **out);
+/* NULL is ignored; waits for the work that still uses it */
+void      rt_motion_blur_destroy(rt_motion_blur *mb);
+void      rt_motion_blur_default_params(rt_motion_blur_params *p);
+/* DIAGNOSTIC, needs no device: the tile grid of step 2, *tx = TX and *ty = TY (either may be NULL) */
+rt_status rt_motion_blur_tiles(int32_t w, int32_t h, int32_t max_blur, int32_t *tx, int32_t *ty);
+/* The planes are DEVICE pointers on the rt_motion_blur's device; the kernels are enqueued on `hip_stream` (NULL = the device's
+ * legacy null stream) and the call returns without waiting for them unless `sync` is non-zero. */
+rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_motion_blur_params *p,
+                                const rt_motion_blur_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, run, download. */
+rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *host_planes);
+
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */
 /* n closest-hit queries = n calls of TraceNode(rootNode, ray, hit) (FIN/main.cpp:94-130).

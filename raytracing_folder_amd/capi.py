@@ -146,6 +146,22 @@ class BloomPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(BloomPlanes), **planes)
 
 
+class MotionBlurParams(C.Structure):
+    """rt_motion_blur_params: motion blur between the denoise and bloom (rt_motion_blur_default_params fills shutter 0.5,
+    max_blur 16, samples 15, depth_extent 0.05)"""
+    _fields_ = [("struct_size", C.c_uint32), ("shutter", C.c_float), ("max_blur", C.c_int32), ("samples", C.c_int32),
+                ("depth_extent", C.c_float)]
+
+
+class MotionBlurPlanes(C.Structure):
+    """rt_motion_blur_planes: the inputs and outputs of one blurred frame.  out may not be rgb_linear; out_tiles is optional."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("motion", C.c_void_p), ("z", C.c_void_p), ("out", C.c_void_p),
+                ("out_tiles", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(MotionBlurPlanes), **planes)
+
+
 # rt_tonemap_params.op (include/rt_mi355x.h)
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 TONEMAP_OPERATORS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
@@ -213,6 +229,8 @@ SYMBOLS = [
     "rt_exposure_create", "rt_exposure_reset", "rt_exposure_destroy", "rt_exposure_get", "rt_exposure_histogram",
     "rt_tonemap_default_params", "rt_tonemap_device", "rt_tonemap",
     "rt_bloom_create", "rt_bloom_destroy", "rt_bloom_default_params", "rt_bloom_plan", "rt_bloom_device", "rt_bloom_host",
+    "rt_motion_blur_create", "rt_motion_blur_destroy", "rt_motion_blur_default_params", "rt_motion_blur_tiles", "rt_motion_blur_device",
+    "rt_motion_blur_host",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
 ]
 
@@ -326,6 +344,17 @@ def lib():
         _lib.rt_bloom_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
         _lib.rt_bloom_host.argtypes = [vp, vp, vp, vp]
         for name in ("rt_bloom_create", "rt_bloom_plan", "rt_bloom_device", "rt_bloom_host"):
+            getattr(_lib, name).restype = C.c_int
+        # motion blur (rt_mi355x.h: "motion blur")
+        _lib.rt_motion_blur_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        _lib.rt_motion_blur_destroy.argtypes = [vp]
+        _lib.rt_motion_blur_destroy.restype = None
+        _lib.rt_motion_blur_default_params.argtypes = [vp]
+        _lib.rt_motion_blur_default_params.restype = None
+        _lib.rt_motion_blur_tiles.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        _lib.rt_motion_blur_device.argtypes = [vp, vp, vp, vp, C.c_int]
+        _lib.rt_motion_blur_host.argtypes = [vp, vp, vp]
+        for name in ("rt_motion_blur_create", "rt_motion_blur_tiles", "rt_motion_blur_device", "rt_motion_blur_host"):
             getattr(_lib, name).restype = C.c_int
         # the packed planes of the multi-GPU exchange (rt_mi355x.h: "packed planes")
         _lib.rt_tiles_packed_planes_size.argtypes = [i32, i32, vp, C.c_uint32, vp, vp, vp]
@@ -921,6 +950,76 @@ class Bloom:
                                      1 if sync else 0))
 
 
+def motion_blur_params(**kw):
+    """rt_motion_blur_default_params, then the keywords: shutter, max_blur, samples, depth_extent"""
+    p = MotionBlurParams()
+    lib().rt_motion_blur_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("shutter", "max_blur", "samples", "depth_extent"):
+            raise TypeError(f"no motion blur parameter {k!r}")
+        setattr(p, k, int(v) if k in ("max_blur", "samples") else v)
+    return p
+
+
+def motion_blur_tiles(w, h, max_blur=16):
+    """rt_motion_blur_tiles: (TX, TY), the grid of max_blur x max_blur tiles over a w x h frame; needs no device"""
+    tx, ty = C.c_int32(), C.c_int32()
+    _check(lib().rt_motion_blur_tiles(int(w), int(h), int(max_blur), C.byref(tx), C.byref(ty)))
+    return tx.value, ty.value
+
+
+class MotionBlur:
+    """rt_motion_blur: the motion blur stage of one w x h stream of frames on one device (the definition: rt_mi355x.h, "motion
+    blur"); it owns the tile planes' device memory.  A context manager; close() (or the end of the with block) frees it."""
+
+    def __init__(self, device, w, h):
+        self._h = C.c_void_p()
+        self.device, self.w, self.h = int(device), int(w), int(h)
+        _check(lib().rt_motion_blur_create(self.device, self.w, self.h, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rt_motion_blur_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, linear, motion, z, return_tiles=False, **params):
+        """rt_motion_blur_host on host arrays -- linear and motion float32 (H, W, 3), z float32 (H, W): the blurred plane, and,
+        return_tiles=True, the unclamped neighbour-max vector per tile (float32 (TY, TX, 2)) as a tuple's second.
+        params: motion_blur_params()."""
+        linear, motion, z = _c(linear, np.float32), _c(motion, np.float32), _c(z, np.float32)
+        assert linear.shape == (self.h, self.w, 3) and motion.shape == (self.h, self.w, 3) and z.shape == (self.h, self.w)
+        p = motion_blur_params(**params)
+        out = np.empty_like(linear)
+        tiles = None
+        if return_tiles:
+            tx, ty = motion_blur_tiles(self.w, self.h, p.max_blur)
+            tiles = np.empty((ty, tx, 2), np.float32)
+        pl = MotionBlurPlanes(rgb_linear=linear.ctypes.data, motion=motion.ctypes.data, z=z.ctypes.data, out=out.ctypes.data,
+                              out_tiles=tiles.ctypes.data if return_tiles else None)
+        _check(lib().rt_motion_blur_host(self._h, C.byref(p), C.byref(pl)))
+        return (out, tiles) if return_tiles else out
+
+    def apply_device(self, stream, *, linear_ptr, motion_ptr, z_ptr, out_ptr, tiles_ptr=None, sync=False, **params):
+        """rt_motion_blur_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an
+        explicit stream's handle; None = the null stream of the device) without a host round trip.  out_ptr may not be
+        linear_ptr.  tiles_ptr: TX * TY * 2 floats (motion_blur_tiles)."""
+        pl = MotionBlurPlanes(rgb_linear=linear_ptr, motion=motion_ptr, z=z_ptr, out=out_ptr, out_tiles=tiles_ptr)
+        p = motion_blur_params(**params)
+        _check(lib().rt_motion_blur_device(self._h, _stream_handle(stream), C.byref(p), C.byref(pl), 1 if sync else 0))
+
+
 def identity_map(texture=MAP_NONE):
     m = np.zeros(1, TEXMAP)
     m["texture"] = texture
@@ -1234,7 +1333,7 @@ class Scene:
         return out
 
     def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None,
-                        bloom=None, bloom_kw=None, **kw):
+                        bloom=None, bloom_kw=None, motion_blur=None, motion_blur_kw=None, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
@@ -1255,7 +1354,12 @@ class Scene:
         clip: history rectification, as History.accumulate's (True, or a dict of radius, k_clip, min_count, clip_history);
         "clipped" (float32 (H, W): 0 no history, 1 kept, 2 clipped) is added.  Works with moving=True.
         bloom: a Bloom of the camera's size on `device` -- the final linear plane is bloomed before it is tone-mapped, as in
-        render_denoised: "bloomed" is added and "display_rgb" is made from it; bloom_kw: a dict of Bloom.apply's keywords."""
+        render_denoised: "bloomed" is added and "display_rgb" is made from it; bloom_kw: a dict of Bloom.apply's keywords.
+        motion_blur: a MotionBlur of the camera's size on `device`; needs moving=True (ValueError without it) -- the final linear
+        plane is blurred along the frame's "motion" plane with its "z" (motion_blur_kw: a dict of MotionBlur.apply's keywords),
+        "motion_blurred" (float32 (H, W, 3)) is added, and bloom and tone mapping run on it."""
+        if motion_blur is not None and not moving:
+            raise ValueError("render_temporal: motion_blur needs moving=True (the frame's motion plane)")
         photon_pass = kw.pop("photon_pass", False)
         t_kw = {k: kw[k] for k in ("alpha", "max_history", "sigma_normal", "sigma_depth") if k in kw}
         d_kw = {k: kw[k] for k in ("levels", "sigma_color", "k_sigma", "sigma_normal", "sigma_depth") if k in kw}
@@ -1281,6 +1385,8 @@ class Scene:
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
         final = out["denoised" if denoise else "accumulated"]
+        if motion_blur is not None:
+            final = out["motion_blurred"] = motion_blur.apply(final, out["motion"], out["z"], **(motion_blur_kw or {}))
         if bloom is not None:
             final = out["bloomed"] = bloom.apply(final, exposure=exposure, **(bloom_kw or {}))
         if exposure is not None:

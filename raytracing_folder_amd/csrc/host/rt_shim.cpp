@@ -23,7 +23,17 @@ void RenderImage::Init(int w, int h)
     rt_bloom_destroy(bloom);            // a pyramid is of one size
     bloom = nullptr;
     bloomed.clear();
+    rt_motion_blur_destroy(motionBlur); // tile planes are of one size
+    motionBlur = nullptr;
+    motionBlurred.clear();
     finalPixels = 0;
+}
+
+void RenderImage::EnableMotionBlur(const rt_motion_blur_params *params)
+{
+    if (params) motionBlurParams = *params;
+    else rt_motion_blur_default_params(&motionBlurParams);
+    motionBlurEnabled = true;
 }
 
 void RenderImage::EnableBloom(const rt_bloom_params *params)
@@ -36,7 +46,7 @@ void RenderImage::EnableBloom(const rt_bloom_params *params)
 void RenderImage::ResetToneMap()
 {
     if (exposure) rt_exposure_reset(exposure);
-    display.clear(); displayImg.clear(); bloomed.clear();
+    display.clear(); displayImg.clear(); bloomed.clear(); motionBlurred.clear();
 }
 
 float RenderImage::ToneMapExposure() const
@@ -57,6 +67,16 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
     rt_tonemap_default_params(&defaults);
     const size_t n = (size_t)width * height;
     const std::vector<float> *from = !denoised.empty() ? &denoised : (!accumulated.empty() ? &accumulated : &linear);
+    std::vector<float> smear;
+    if (motionBlurEnabled && !motion.empty()) {     // along the motion plane of the last AccumulateTemporalMoving()
+        if (motionBlur && motionBlurDevice != device) { rt_motion_blur_destroy(motionBlur); motionBlur = nullptr; }
+        if (!motionBlur && rt_motion_blur_create(device, width, height, &motionBlur) != RT_OK) { toneMapError = rt_last_error(); return false; }
+        motionBlurDevice = device;
+        smear.resize(n * 3);
+        const rt_motion_blur_planes mp = {(uint32_t)sizeof(rt_motion_blur_planes), from->data(), motion.data(), zbuffer.data(), smear.data(), nullptr};
+        if (rt_motion_blur_host(motionBlur, &motionBlurParams, &mp) != RT_OK) { toneMapError = rt_last_error(); return false; }
+        from = &smear;
+    }
     std::vector<float> glare;
     if (bloomEnabled) {                 // ahead of the curve, relative to the scale the state holds from the call before
         if (bloom && bloomDevice != device) { rt_bloom_destroy(bloom); bloom = nullptr; }
@@ -74,6 +94,7 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
     if (rt_tonemap(exposure, device, width, height, params ? params : &defaults, &pl) != RT_OK) { toneMapError = rt_last_error(); return false; }
     display.swap(out); displayImg.swap(out8);
     if (bloomEnabled) bloomed.swap(glare);
+    motionBlurred.swap(smear);          // empty again when the stage did not run
     toneMapError.clear();
     return true;
 }

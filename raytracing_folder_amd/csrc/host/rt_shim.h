@@ -58,6 +58,12 @@ class RenderImage {
     rt_bloom_params bloomParams = {};
     rt_bloom *bloom = nullptr;
     int bloomDevice = 0;
+    // opt-in (EnableMotionBlur): ToneMap() blurs the plane along the last AccumulateTemporalMoving()'s motion plane first
+    std::vector<float> motionBlurred;
+    bool motionBlurEnabled = false;
+    rt_motion_blur_params motionBlurParams = {};
+    rt_motion_blur *motionBlur = nullptr;
+    int motionBlurDevice = 0;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -67,7 +73,7 @@ public:
     RenderImage() = default;
     RenderImage(const RenderImage &) = delete;
     RenderImage &operator=(const RenderImage &) = delete;
-    ~RenderImage() { rt_history_destroy(history); rt_bloom_destroy(bloom); rt_exposure_destroy(exposure); }
+    ~RenderImage() { rt_history_destroy(history); rt_motion_blur_destroy(motionBlur); rt_bloom_destroy(bloom); rt_exposure_destroy(exposure); }
     void Init(int w, int h);
     int GetWidth() const { return width; }
     int GetHeight() const { return height; }
@@ -170,6 +176,16 @@ public:
     bool BloomEnabled() const { return bloomEnabled; }
     float *GetBloomed() { return bloomed.empty() ? nullptr : bloomed.data(); }                  // linear float RGB
     bool SaveBloomedImage(const char *filename) const { return !bloomed.empty() && WritePFM(filename, bloomed.data(), width, height); }   // PFM
+    // Motion blur (rt_mi355x.h, "motion blur"): from now on ToneMap() first blurs the plane it would bloom or tone-map, along the
+    // motion plane of the last AccumulateTemporalMoving() and with the frame's z; bloom and the curve then work on the result.
+    // Without such a plane (no moving accumulation yet, or a plain AccumulateTemporal() since) the stage is a no-op and
+    // GetMotionBlurred() is NULL.  params == NULL: the defaults of rt_motion_blur_default_params.  The rt_motion_blur is created
+    // by the first ToneMap() that needs it, on its device, and lives until the image is destroyed, Init() changes the size or
+    // another device is named.
+    void EnableMotionBlur(const rt_motion_blur_params *params = nullptr);
+    bool MotionBlurEnabled() const { return motionBlurEnabled; }
+    float *GetMotionBlurred() { return motionBlurred.empty() ? nullptr : motionBlurred.data(); }    // linear float RGB
+    bool SaveMotionBlurredImage(const char *filename) const { return !motionBlurred.empty() && WritePFM(filename, motionBlurred.data(), width, height); }   // PFM
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

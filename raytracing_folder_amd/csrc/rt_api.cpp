@@ -3181,6 +3181,144 @@ extern "C" rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_p
     return RT_OK;
 }
 
+// ---- motion blur ------------------------------------------------------------------------------------------------------------
+// An rt_motion_blur owns the tile-max and neighbour-max planes of one W x H stream of frames on its device -- sized for K = 2,
+// the most tiles a call can ask for -- and the event that orders a call behind the previous one on the same object.
+#define RT_MBLUR_MIN_K 2
+#define RT_MBLUR_MAX_K 32
+struct rt_motion_blur {
+    int device = 0; int32_t w = 0, h = 0;
+    DevBuf tile_max, tile_nmax;
+    hipEvent_t done = nullptr; bool pending = false;
+    std::mutex mu;
+};
+
+static size_t mblur_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
+{
+    const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
+    if (tx) *tx = x;
+    if (ty) *ty = y;
+    return (size_t)x * (size_t)y;
+}
+
+extern "C" rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_motion_blur **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_motion_blur_create: out is NULL");
+    *out = nullptr;
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_motion_blur_create: bad image size %d x %d", w, h);
+    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_motion_blur_create: %d x %d is more than 2^30 pixels", w, h);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_motion_blur_create: device %d is not gfx950 (no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    rt_motion_blur *mb = new rt_motion_blur;
+    mb->device = device; mb->w = w; mb->h = h;
+    const size_t bytes = mblur_tiles(w, h, RT_MBLUR_MIN_K, nullptr, nullptr) * 8;
+    rt_status st = mb->tile_max.ensure(bytes);
+    if (st == RT_OK) st = mb->tile_nmax.ensure(bytes);
+    if (st == RT_OK && hipEventCreateWithFlags(&mb->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_motion_blur_create: hipEventCreate failed");
+    if (st) { rt_motion_blur_destroy(mb); return st; }
+    *out = mb;
+    return RT_OK;
+}
+
+extern "C" void rt_motion_blur_destroy(rt_motion_blur *mb)
+{
+    if (!mb) return;
+    if (hipSetDevice(mb->device) == hipSuccess) {
+        if (mb->pending) (void)hipEventSynchronize(mb->done);
+        mb->tile_max.release(); mb->tile_nmax.release();        // hipFree waits for the kernels that still use them
+        if (mb->done) (void)hipEventDestroy(mb->done);
+    }
+    delete mb;
+}
+
+extern "C" void rt_motion_blur_default_params(rt_motion_blur_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->shutter = 0.5f; p->max_blur = 16; p->samples = 15; p->depth_extent = 0.05f;
+}
+
+extern "C" rt_status rt_motion_blur_tiles(int32_t w, int32_t h, int32_t max_blur, int32_t *tx, int32_t *ty)
+{
+    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: bad image size %d x %d", w, h);
+    if (max_blur < RT_MBLUR_MIN_K || max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: max_blur is %d, must be 2..32", max_blur);
+    mblur_tiles(w, h, max_blur, tx, ty);
+    return RT_OK;
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status mblur_check(const char *name, const rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl)
+{
+    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
+    if (p->struct_size != (uint32_t)sizeof(rt_motion_blur_params))
+        return fail(RT_ERR_ARG, "%s: rt_motion_blur_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_motion_blur_params));
+    if (pl->struct_size != (uint32_t)sizeof(rt_motion_blur_planes))
+        return fail(RT_ERR_ARG, "%s: rt_motion_blur_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_motion_blur_planes));
+    if (!std::isfinite(p->shutter) || !(p->shutter >= 0.0f) || p->shutter > 2.0f) return fail(RT_ERR_ARG, "%s: shutter must be finite and 0..2", name);
+    if (p->max_blur < RT_MBLUR_MIN_K || p->max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "%s: max_blur is %d, must be 2..32", name, p->max_blur);
+    if (p->samples < 3 || p->samples > 63 || !(p->samples & 1)) return fail(RT_ERR_ARG, "%s: samples is %d, must be odd and 3..63", name, p->samples);
+    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
+    if (!pl->rgb_linear || !pl->motion || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, motion, z and out are required", name);
+    // what needs the object comes last: without a device there is none, and everything above is still refused by name
+    if (!mb) return fail(RT_ERR_ARG, "%s: the rt_motion_blur is NULL", name);
+    const size_t n = (size_t)mb->w * (size_t)mb->h;
+    const struct { const void *p; size_t bytes; } planes[5] = {
+        {pl->rgb_linear, n * 12}, {pl->motion, n * 12}, {pl->z, n * 4}, {pl->out, n * 12},
+        {pl->out_tiles, mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8}};
+    for (int a = 0; a < 5; a++)
+        for (int b = a + 1; b < 5; b++) {
+            const uintptr_t x = (uintptr_t)planes[a].p, y = (uintptr_t)planes[b].p;
+            if (x && y && x < y + planes[b].bytes && y < x + planes[a].bytes)
+                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
+        }
+    return RT_OK;
+}
+
+static rt_status mblur_on_device(rt_motion_blur *mb, hipStream_t st, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(mb->device));
+    MotionBlurRequest R = {};
+    R.width = mb->w; R.height = mb->h; R.K = p->max_blur; R.N = p->samples;
+    mblur_tiles(mb->w, mb->h, p->max_blur, &R.tiles_x, &R.tiles_y);
+    R.half_shutter = 0.5f * p->shutter; R.two_over_n = 2.0f / (float)p->samples; R.depth_extent = p->depth_extent;
+    R.rgb_linear = pl->rgb_linear; R.motion = pl->motion; R.z = pl->z; R.out = pl->out; R.out_tiles = pl->out_tiles;
+    std::lock_guard<std::mutex> lk(mb->mu);
+    R.tile_max = (float *)mb->tile_max.p; R.tile_nmax = (float *)mb->tile_nmax.p;
+    if (mb->pending) HIP_TRY(hipStreamWaitEvent(st, mb->done, 0));
+    HIP_TRY(rtk_launch_motion_blur(st, R));
+    HIP_TRY(hipEventRecord(mb->done, st));
+    mb->pending = true;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); mb->pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_motion_blur_params *p,
+                                           const rt_motion_blur_planes *device_planes, int sync)
+{
+    rt_status st = mblur_check("rt_motion_blur_device", mb, p, device_planes);
+    if (st) return st;
+    return mblur_on_device(mb, (hipStream_t)hip_stream, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *host_planes)
+{
+    rt_status st = mblur_check("rt_motion_blur_host", mb, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(mb->device));
+    const size_t n = (size_t)mb->w * (size_t)mb->h;
+    const size_t tile_bytes = mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8;
+    ScopedDevBuf rgb, motion, z, out, tiles;
+    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = motion.upload(host_planes->motion, n * 12)) ||
+        (st = z.upload(host_planes->z, n * 4)) || (st = out.ensure(n * 12))) return st;
+    if (host_planes->out_tiles && (st = tiles.ensure(tile_bytes))) return st;
+    const rt_motion_blur_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)motion.p, (const float *)z.p,
+                                       (float *)out.p, (float *)tiles.p};
+    if ((st = mblur_on_device(mb, nullptr, p, &dev, 1))) return st;
+    HIP_TRY(hipMemcpy(host_planes->out, out.p, n * 12, hipMemcpyDeviceToHost));
+    if (host_planes->out_tiles) HIP_TRY(hipMemcpy(host_planes->out_tiles, tiles.p, tile_bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");

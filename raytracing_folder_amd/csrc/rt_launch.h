@@ -1,6 +1,6 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip): every rtk_* function, the requests they take and the
-// records they exchange.  All nine files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip): every rtk_* function, the requests they take and the
+// records they exchange.  All ten files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -186,6 +186,20 @@ struct BloomRequest {
     BloomPlan plan;
 };
 
+// One motion-blurred width x height frame (rt_motion_blur.hip; the definition: rt_mi355x.h, "motion blur").  The planes are the
+// caller's device pointers (out_tiles may be NULL), the parameters are validated by the caller.  tile_max and tile_nmax: the
+// rt_motion_blur's scratch, one float2 per tile each (tiles_x * tiles_y of them for this call's K).
+struct MotionBlurRequest {
+    int width, height, K, N;
+    int tiles_x, tiles_y;               // ceil(width / K), ceil(height / K)
+    float half_shutter;                 // h = 0.5f * shutter
+    float two_over_n;                   // g = 2 / N
+    float depth_extent;
+    const float *rgb_linear, *motion, *z;
+    float *out, *out_tiles;
+    float *tile_max, *tile_nmax;
+};
+
 // ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -248,6 +262,10 @@ void rtk_launch_tonemap(hipStream_t st, const ToneMapRequest &R);
 BloomPlan rtk_bloom_plan(int width, int height, int levels);
 // on `st`: k_bloom_prefilter, k_bloom_down per level above the tail, k_bloom_tail, k_bloom_up per level above it, k_bloom_combine
 hipError_t rtk_launch_bloom(hipStream_t st, const BloomRequest &R);
+
+// ---- rt_motion_blur.hip: motion blur between the denoise and bloom ----------------------------------------------------------
+// on `st`: k_mblur_tile_max, k_mblur_neighbour_max, k_mblur_gather
+hipError_t rtk_launch_motion_blur(hipStream_t st, const MotionBlurRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

@@ -201,7 +201,9 @@ class ShardedRenderer:
     What else follows a frame is the caller's, on `sr.stream` with the returned tensors' data_ptr()s: temporal accumulation
     (capi.History.accumulate_device), motion vectors (capi.motion_device -- the motion plane is a function of z and object_id,
     so it needs no transport: compute it after the step), bloom (capi.Bloom.apply_device -- like tone mapping it works on the
-    gathered frame, so nothing of it is transported) and tone mapping (capi.Exposure.tonemap_device).
+    gathered frame, so nothing of it is transported) and tone mapping (capi.Exposure.tonemap_device).  Motion blur
+    (capi.MotionBlur.apply_device) is one more of these post stages: it runs after the exchange on the gathered linear, motion and
+    z planes, ahead of bloom, and nothing of it is transported.
     With planes=None and denoise=False the renderer is what it was: the same bytes exchanged, a tuple as the frame."""
 
     def __init__(self, scene, cam, params, rank, world, device_index, tile_w=32, tile_h=8, host_gather=False, linear=False,
