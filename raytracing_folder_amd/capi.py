@@ -530,15 +530,20 @@ def image_read_pfm1(path):
     return v
 
 
+def _fill_params(struct, default_fn, allowed, int_fields, kw, what):
+    """a `struct` as the library's `default_fn` fills it, then the keywords `kw` (of `allowed`; `int_fields` through int())"""
+    p = struct()
+    getattr(lib(), default_fn)(C.byref(p))
+    for k, v in kw.items():
+        if k not in allowed:
+            raise TypeError(f"no {what} parameter {k!r}")
+        setattr(p, k, int(v) if k in int_fields else v)
+    return p
+
+
 def denoise_params(**kw):
     """rt_denoise_default_params, then the keywords (levels, sigma_color, sigma_normal, sigma_depth, gamma)"""
-    p = DenoiseParams()
-    lib().rt_denoise_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in ("levels", "sigma_color", "sigma_normal", "sigma_depth", "gamma"):
-            raise TypeError(f"no denoise parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _fill_params(DenoiseParams, "rt_denoise_default_params", ("levels", "sigma_color", "sigma_normal", "sigma_depth", "gamma"), (), kw, "denoise")
 
 
 def denoise_var(variance_ptr, out_variance_ptr=None, k_sigma=4.0):
@@ -604,25 +609,14 @@ _denoise = denoise       # for Scene.render_temporal, whose `denoise` argument h
 
 def temporal_params(**kw):
     """rt_temporal_default_params, then the keywords (alpha, max_history, sigma_normal, sigma_depth, gamma)"""
-    p = TemporalParams()
-    lib().rt_temporal_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in ("alpha", "max_history", "sigma_normal", "sigma_depth", "gamma"):
-            raise TypeError(f"no temporal parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _fill_params(TemporalParams, "rt_temporal_default_params", ("alpha", "max_history", "sigma_normal", "sigma_depth", "gamma"), (), kw, "temporal")
 
 
 def temporal_clip(clip=True, out_clipped=None):
     """rt_temporal_clip_default, then `clip`: True keeps the defaults, a dict overrides fields (radius, k_clip, min_count,
     clip_history).  out_clipped: the address of the optional mask plane (host or device, as the call it goes to)."""
-    c = TemporalClip()
-    lib().rt_temporal_clip_default(C.byref(c))
-    if clip is not True:
-        for k, v in dict(clip).items():
-            if k not in ("radius", "k_clip", "min_count", "clip_history"):
-                raise TypeError(f"no temporal clip parameter {k!r}")
-            setattr(c, k, v)
+    c = _fill_params(TemporalClip, "rt_temporal_clip_default", ("radius", "k_clip", "min_count", "clip_history"), (),
+                     {} if clip is True else dict(clip), "temporal clip")
     c.out_clipped = out_clipped
     return c
 
@@ -659,29 +653,14 @@ def motion_device(device, stream, cam, prev_cam, nodes, prev_nodes, *, z_ptr, ob
                                   _p(prev) if prev is not None else None, len(nodes), C.byref(pl), 1 if sync else 0))
 
 
-def _copy_camera(cam):
-    c = Camera()
-    C.memmove(C.byref(c), C.byref(cam), C.sizeof(Camera))
-    return c
-
-
-class History:
-    """rt_history: the accumulated frames of one W x H stream on one device (the definition: rt_mi355x.h, "temporal
-    accumulation").  Every accumulate blends a new frame into what the earlier ones left, reprojected from the camera of the
-    previous call into `cam` (a STATIC scene) -- or, with a motion plane (motion() / motion_device()), from where that plane says
-    each pixel was (moving nodes).  A context manager; close() (or the end of the with block) frees the device planes."""
-
-    def __init__(self, device, w, h):
-        self._h = C.c_void_p()
-        # Scene.render_temporal(moving=True): (camera, nodes) of the frame the history holds -- set by that method alone; any
-        # other accumulate puts a frame into the history whose nodes are not known here, and forgets it
-        self._moving = None
-        self.device, self.width, self.height = int(device), int(w), int(h)
-        _check(lib().rt_history_create(self.device, self.width, self.height, C.byref(self._h)))
+class _Handle:
+    """what the classes that own a library object share: self._h is its handle, close() (or the end of a with block, or the
+    collector) hands it to the library function the subclass names in _destroy"""
+    _destroy = None
 
     def close(self):
         if self._h:
-            lib().rt_history_destroy(self._h)
+            getattr(lib(), self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -695,6 +674,29 @@ class History:
             self.close()
         except Exception:
             pass
+
+
+def _copy_camera(cam):
+    c = Camera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(Camera))
+    return c
+
+
+class History(_Handle):
+    """rt_history: the accumulated frames of one W x H stream on one device (the definition: rt_mi355x.h, "temporal
+    accumulation").  Every accumulate blends a new frame into what the earlier ones left, reprojected from the camera of the
+    previous call into `cam` (a STATIC scene) -- or, with a motion plane (motion() / motion_device()), from where that plane says
+    each pixel was (moving nodes).  A context manager; close() (or the end of the with block) frees the device planes."""
+
+    _destroy = "rt_history_destroy"
+
+    def __init__(self, device, w, h):
+        self._h = C.c_void_p()
+        # Scene.render_temporal(moving=True): (camera, nodes) of the frame the history holds -- set by that method alone; any
+        # other accumulate puts a frame into the history whose nodes are not known here, and forgets it
+        self._moving = None
+        self.device, self.width, self.height = int(device), int(w), int(h)
+        _check(lib().rt_history_create(self.device, self.width, self.height, C.byref(self._h)))
 
     def reset(self):
         """the next frame starts from nothing"""
@@ -778,14 +780,11 @@ def tonemap_params(operator="aces", **kw):
     """rt_tonemap_default_params, then the operator ("clamp", "reinhard", "aces" or an RT_TONEMAP_* number) and the keywords:
     auto_exposure, key, ev_bias, ev_min, ev_max, p_low, p_high, adapt_up, adapt_down, white, gamma; exposure_ev is another name
     for ev_bias (the exposure itself when auto_exposure is 0)."""
-    p = ToneMapParams()
-    lib().rt_tonemap_default_params(C.byref(p))
-    p.op = TONEMAP_OPERATORS[operator] if isinstance(operator, str) else int(operator)
-    for k, v in kw.items():
-        k = "ev_bias" if k == "exposure_ev" else k
-        if k not in ("auto_exposure", "key", "ev_bias", "ev_min", "ev_max", "p_low", "p_high", "adapt_up", "adapt_down", "white", "gamma"):
-            raise TypeError(f"no tone-mapping parameter {k!r}")
-        setattr(p, k, int(v) if k == "auto_exposure" else v)
+    op = TONEMAP_OPERATORS[operator] if isinstance(operator, str) else int(operator)
+    p = _fill_params(ToneMapParams, "rt_tonemap_default_params",
+                     ("auto_exposure", "key", "ev_bias", "ev_min", "ev_max", "p_low", "p_high", "adapt_up", "adapt_down", "white", "gamma"),
+                     ("auto_exposure",), {("ev_bias" if k == "exposure_ev" else k): v for k, v in kw.items()}, "tone-mapping")
+    p.op = op
     return p
 
 
@@ -811,32 +810,17 @@ def tonemap(linear, exposure_ev=0.0, operator="aces", display=False, device=0, *
     return _tonemap_host(None, device, linear, None, display, p)
 
 
-class Exposure:
+class Exposure(_Handle):
     """rt_exposure: the exposure of one stream of frames on one device, adapted from frame to frame (the definition:
     rt_mi355x.h, "exposure and tone mapping").  Not tied to an image size.  A context manager; close() (or the end of the with
     block) frees the device block."""
+
+    _destroy = "rt_exposure_destroy"
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         self.device = int(device)
         _check(lib().rt_exposure_create(self.device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().rt_exposure_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         """the next metered frame is the first again"""
@@ -885,13 +869,7 @@ class Exposure:
 
 def bloom_params(**kw):
     """rt_bloom_default_params, then the keywords: threshold, knee, intensity, spread, levels, exposure_ev"""
-    p = BloomParams()
-    lib().rt_bloom_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in ("threshold", "knee", "intensity", "spread", "levels", "exposure_ev"):
-            raise TypeError(f"no bloom parameter {k!r}")
-        setattr(p, k, int(v) if k == "levels" else v)
-    return p
+    return _fill_params(BloomParams, "rt_bloom_default_params", ("threshold", "knee", "intensity", "spread", "levels", "exposure_ev"), ("levels",), kw, "bloom")
 
 
 def bloom_plan(w, h, levels=6):
@@ -901,31 +879,16 @@ def bloom_plan(w, h, levels=6):
     return used.value, tail.value
 
 
-class Bloom:
+class Bloom(_Handle):
     """rt_bloom: the bloom stage of one w x h stream of frames on one device (the definition: rt_mi355x.h, "bloom"); it owns the
     pyramid's device memory.  A context manager; close() (or the end of the with block) frees it."""
+
+    _destroy = "rt_bloom_destroy"
 
     def __init__(self, device, w, h):
         self._h = C.c_void_p()
         self.device, self.w, self.h = int(device), int(w), int(h)
         _check(lib().rt_bloom_create(self.device, self.w, self.h, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().rt_bloom_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def apply(self, linear, exposure=None, return_bloom=False, **params):
         """rt_bloom_host on a float32 (H, W, 3) host array: the bloomed plane -- and, return_bloom=True, the bloom plane alone as a
@@ -952,13 +915,8 @@ class Bloom:
 
 def motion_blur_params(**kw):
     """rt_motion_blur_default_params, then the keywords: shutter, max_blur, samples, depth_extent"""
-    p = MotionBlurParams()
-    lib().rt_motion_blur_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in ("shutter", "max_blur", "samples", "depth_extent"):
-            raise TypeError(f"no motion blur parameter {k!r}")
-        setattr(p, k, int(v) if k in ("max_blur", "samples") else v)
-    return p
+    return _fill_params(MotionBlurParams, "rt_motion_blur_default_params", ("shutter", "max_blur", "samples", "depth_extent"), ("max_blur", "samples"), kw,
+                        "motion blur")
 
 
 def motion_blur_tiles(w, h, max_blur=16):
@@ -968,31 +926,16 @@ def motion_blur_tiles(w, h, max_blur=16):
     return tx.value, ty.value
 
 
-class MotionBlur:
+class MotionBlur(_Handle):
     """rt_motion_blur: the motion blur stage of one w x h stream of frames on one device (the definition: rt_mi355x.h, "motion
     blur"); it owns the tile planes' device memory.  A context manager; close() (or the end of the with block) frees it."""
+
+    _destroy = "rt_motion_blur_destroy"
 
     def __init__(self, device, w, h):
         self._h = C.c_void_p()
         self.device, self.w, self.h = int(device), int(w), int(h)
         _check(lib().rt_motion_blur_create(self.device, self.w, self.h, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().rt_motion_blur_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def apply(self, linear, motion, z, return_tiles=False, **params):
         """rt_motion_blur_host on host arrays -- linear and motion float32 (H, W, 3), z float32 (H, W): the blurred plane, and,
@@ -1325,12 +1268,7 @@ class Scene:
         else:
             out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
                                                            rgb8=True, device=device, **denoise_kw)
-        final = out["denoised"]
-        if bloom is not None:
-            final = out["bloomed"] = bloom.apply(final, exposure=exposure, **(bloom_kw or {}))
-        if exposure is not None:
-            out["display_rgb"] = exposure.tonemap(final, out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
-        return out
+        return self._finish_frame(out, out["denoised"], params, None, None, bloom, bloom_kw, exposure, tonemap_kw)
 
     def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None,
                         bloom=None, bloom_kw=None, motion_blur=None, motion_blur_kw=None, **kw):
@@ -1384,7 +1322,13 @@ class Scene:
             out["denoised"], out["denoised_rgb"] = _denoise(
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
-        final = out["denoised" if denoise else "accumulated"]
+        return self._finish_frame(out, out["denoised" if denoise else "accumulated"], params, motion_blur, motion_blur_kw, bloom, bloom_kw,
+                                  exposure, tonemap_kw)
+
+    @staticmethod
+    def _finish_frame(out, final, params, motion_blur, motion_blur_kw, bloom, bloom_kw, exposure, tonemap_kw):
+        """the tail of render_denoised and render_temporal on the frame's final linear plane: motion blur, then bloom, then tone
+        mapping, each only where its object is given; adds "motion_blurred", "bloomed" and "display_rgb" to `out`"""
         if motion_blur is not None:
             final = out["motion_blurred"] = motion_blur.apply(final, out["motion"], out["z"], **(motion_blur_kw or {}))
         if bloom is not None:

@@ -1,5 +1,6 @@
 // rt_api.cpp -- implementation of the C ABI in include/rt_mi355x.h: scene store, lowering to the
 // device layout of rt_dev.h, per-chunk wavefront orchestration on a HIP stream, async jobs.
+// The image-space stages (denoise .. motion blur) are in rt_post.cpp; rt_host.h is what the two share.
 // There is no CPU render path in this library: without a gfx950 device the render calls fail.
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,7 @@
 
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
-#include "rt_launch.h"
+#include "rt_host.h"
 
 // k_gather is a persistent grid that pulls query batches from a counter: enough workgroups to fill
 // every CU at the kernel's occupancy (256 CUs x 5 resident workgroups of 4 waves)
@@ -35,8 +36,8 @@ static int gather_blocks()
 static const size_t STATS_BYTES = (size_t)ST_COUNT * RT_STAT_STRIDE * 8;    // the statistics block: counters RT_STAT_STRIDE apart (rt_dev.h)
 
 // ---- errors ---------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-static rt_status fail(rt_status st, const char *fmt, ...)
+static thread_local std::string g_err;       // the one message of rt_last_error(), whichever file failed
+rt_status fail(rt_status st, const char *fmt, ...)
 {
     char buf[1024];
     va_list ap;
@@ -46,16 +47,11 @@ static rt_status fail(rt_status st, const char *fmt, ...)
     g_err = buf;
     return st;
 }
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" const char *rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_abi_version(void) { return RT_ABI_VERSION; }
 
-static bool device_is_gfx950(int dev)
+bool device_is_gfx950(int dev)
 {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
@@ -79,48 +75,6 @@ extern "C" void rt_params_default(rt_params *p)
     p->hemisphere_sample = 30; p->knn_k = 400; p->knn_radius = 1.0f;                // :26, :699
     p->shade_model = RT_SHADE_FIN; p->shadow_samples = 4; p->seed = 20171203u; p->gamma = 2.2;
     p->photon_count = 1000000; p->photon_bounce = 8;                                // MAX_NUM_OF_PHOTON, PHOTON_BOUNCE (:27, :29)
-}
-
-// ---- device buffers --------------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr; size_t bytes = 0;
-    rt_status ensure(size_t n)
-    {
-        if (n <= bytes && p) return RT_OK;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        if (n == 0) n = 16;
-        HIP_TRY(hipMalloc(&p, n));
-        bytes = n;
-        return RT_OK;
-    }
-    rt_status upload(const void *src, size_t n)
-    {
-        rt_status st = ensure(n);
-        if (st) return st;
-        if (n) HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
-        return RT_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-// a DevBuf released when its scope ends (DeviceState releases its own explicitly, on its device)
-struct ScopedDevBuf : DevBuf {
-    ScopedDevBuf() = default;
-    ScopedDevBuf(const ScopedDevBuf &) = delete;
-    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
-    ~ScopedDevBuf() { release(); }
-};
-
-// an owned hipEvent_t: destroyed with its owner, handed on by a move
-namespace {
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }      // once per Event
-    operator hipEvent_t() const { return e; }
-};
 }
 
 struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
@@ -351,8 +305,6 @@ struct rt_job {
 
 // ---- scene store ---------------------------------------------------------------------------------------
 static std::atomic<int> g_live_scenes{0};
-static void denoise_release_all();         // the denoiser's per-device scratch (below, "denoising")
-static void motion_release_all();          // the per-device node tables of rt_motion (below, "motion vectors")
 extern "C" rt_status rt_scene_create(rt_scene **out)
 {
     if (!out) return fail(RT_ERR_ARG, "rt_scene_create: out is NULL");
@@ -372,7 +324,7 @@ extern "C" void rt_scene_destroy(rt_scene *s)
         delete d;
     }
     delete s;
-    if (g_live_scenes.fetch_sub(1) == 1) { denoise_release_all(); motion_release_all(); }   // the last scene takes the per-device image-space scratch with it
+    if (g_live_scenes.fetch_sub(1) == 1) post_release_all();   // the last scene takes the per-device image-space scratch with it
 }
 
 static rt_status check_idle(rt_scene *s, const char *who)
@@ -1440,7 +1392,7 @@ static rt_status collect_pending_verdict(DeviceState *D, unsigned long long *dro
 }
 
 // camera set-up of RenderPixel, FIN/main.cpp:205-224 (tan in double, everything else float)
-static void camera_setup(const rt_camera &cam, DevCamera &dc)
+void camera_setup(const rt_camera &cam, DevCamera &dc)
 {
     using rt::Point3;
     const float theta = cam.fov;
@@ -2310,1013 +2262,6 @@ extern "C" rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream,
     if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_tiles_unpack_linear_device: the linear plane is required");
     return tiles_unpack("rt_tiles_unpack_linear_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
                         rgb8_dev, z_dev, count_dev, rgb_linear_dev);
-}
-
-// ---- denoising ----------------------------------------------------------------------------------------------------------
-// rt_denoise_device has no scene, and the device state above belongs to one: the denoiser's scratch is held per device for the
-// process -- the two ping-pong colour buffers and the guide buffer in one allocation, grown on demand.  Every denoise on a
-// device uses the same scratch, so a call orders its stream behind the previous call's `done` event.  Released with the last
-// scene (rt_scene_destroy), like the per-device buffers of the scenes.
-struct DenoiseDevice { DevBuf scratch; hipEvent_t done = nullptr; bool pending = false; };
-static std::mutex g_denoise_mu;
-static std::vector<std::pair<int, DenoiseDevice>> g_denoise;        // (device, its scratch); under g_denoise_mu
-
-static void denoise_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
-    for (auto &d : g_denoise) {
-        if (hipSetDevice(d.first) != hipSuccess) continue;
-        d.second.scratch.release();                                 // hipFree waits for the kernels that still use it
-        if (d.second.done) (void)hipEventDestroy(d.second.done);
-    }
-    g_denoise.clear();
-}
-
-extern "C" void rt_denoise_default_params(rt_denoise_params *p)
-{
-    if (!p) return;
-    p->struct_size = (uint32_t)sizeof *p;
-    p->levels = 5; p->sigma_color = 1.0f; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
-}
-
-#define RT_DENOISE_MAX_PIXELS (1ll << 30)       /* 48 GiB of scratch; keeps the one-dimensional grid of 32 x 8 tiles far below 2^31 */
-// everything that can be refused without a device, for both entry points
-static rt_status denoise_check(const char *name, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *pl)
-{
-    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
-    if (p->struct_size != (uint32_t)sizeof(rt_denoise_params))
-        return fail(RT_ERR_ARG, "%s: rt_denoise_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_denoise_params));
-    if (pl->struct_size != (uint32_t)sizeof(rt_denoise_planes))
-        return fail(RT_ERR_ARG, "%s: rt_denoise_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_denoise_planes));
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, w, h);
-    if (p->levels < 1 || p->levels > 8) return fail(RT_ERR_ARG, "%s: levels is %d, allowed 1..8", name, p->levels);
-    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_depth, p->gamma})
-        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_color, sigma_normal, sigma_depth and gamma must be positive and finite", name);
-    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
-        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
-    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, w, h);
-    return RT_OK;
-}
-
-// k_resolve's exponent is (float)(1.0 / gamma) of a DOUBLE gamma (rt_params); rt_denoise_params carries a float.  Taking the
-// double that prints like that float to 7 digits gives 2.2 for 2.2f, hence the exponent a default render used.
-static float denoise_inv_gamma(float gamma)
-{
-    char buf[32];
-    snprintf(buf, sizeof buf, "%.7g", (double)gamma);
-    return (float)(1.0 / strtod(buf, nullptr));
-}
-
-extern "C" void rt_denoise_var_default(rt_denoise_var *v)
-{
-    if (!v) return;
-    v->struct_size = (uint32_t)sizeof *v;
-    v->variance = nullptr; v->out_variance = nullptr; v->k_sigma = 4.0f;
-}
-
-// the variance block of the _var entry points, after denoise_check and like it without a device
-static rt_status denoise_var_check(const char *name, const rt_denoise_var *v)
-{
-    if (!v) return fail(RT_ERR_ARG, "%s: the variance block is NULL", name);
-    if (v->struct_size != (uint32_t)sizeof(rt_denoise_var))
-        return fail(RT_ERR_ARG, "%s: rt_denoise_var.struct_size is %u, this library's is %zu", name, v->struct_size, sizeof(rt_denoise_var));
-    if (!v->variance) return fail(RT_ERR_ARG, "%s: the variance plane is required", name);
-    if (!(v->k_sigma > 0.0f) || !std::isfinite(v->k_sigma)) return fail(RT_ERR_ARG, "%s: k_sigma must be positive and finite", name);
-    return RT_OK;
-}
-
-// v == NULL: the fixed-sigma filter; otherwise the variance-guided one (v is checked by the caller)
-static rt_status denoise_on_device(const char *name, int device, hipStream_t st, int32_t w, int32_t h, const rt_denoise_params *p,
-                                   const rt_denoise_planes *pl, int sync, const rt_denoise_var *v = nullptr)
-{
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
-    HIP_TRY(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_denoise_mu);
-    DenoiseDevice *D = nullptr;
-    for (auto &d : g_denoise) if (d.first == device) D = &d.second;
-    if (!D) { g_denoise.emplace_back(device, DenoiseDevice()); D = &g_denoise.back().second; }
-    const size_t n = (size_t)w * (size_t)h;
-    // growing frees the old one, which waits for its users
-    rt_status rs = D->scratch.ensure(n * (v ? RT_DENOISE_SCRATCH_PER_PIXEL_VAR : RT_DENOISE_SCRATCH_PER_PIXEL));
-    if (rs) return rs;
-    if (!D->done) HIP_TRY(hipEventCreateWithFlags(&D->done, hipEventDisableTiming));
-    if (D->pending) HIP_TRY(hipStreamWaitEvent(st, D->done, 0));
-    DenoiseRequest R = {};
-    R.width = w; R.height = h; R.levels = p->levels;
-    R.sigma_color = p->sigma_color; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth; R.inv_gamma = denoise_inv_gamma(p->gamma);
-    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id;
-    R.out_linear = pl->out_linear; R.out_rgb8 = pl->out_rgb8;
-    R.color[0] = (float4 *)D->scratch.p; R.color[1] = R.color[0] + n; R.guide = R.color[1] + n;
-    if (v) {
-        R.variance = v->variance; R.out_variance = v->out_variance; R.k_sigma = v->k_sigma;
-        R.var[0] = R.guide + n; R.var[1] = R.var[0] + n;
-    }
-    rtk_launch_denoise_frame(st, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(D->done, st));
-    D->pending = true;
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); D->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_denoise_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
-                                       const rt_denoise_planes *device_planes, int sync)
-{
-    rt_status st = denoise_check("rt_denoise_device", w, h, p, device_planes);
-    if (st) return st;
-    return denoise_on_device("rt_denoise_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
-}
-
-extern "C" rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes)
-{
-    rt_status st = denoise_check("rt_denoise", w, h, p, host_planes);
-    if (st) return st;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_denoise: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = (size_t)w * (size_t)h;
-    ScopedDevBuf rgb, normal, albedo, z, id, rgb8;                  // the result is written in place into rgb
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
-        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4))) return st;
-    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
-    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
-    rt_denoise_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
-                             (const int32_t *)id.p, (float *)rgb.p, (uint8_t *)rgb8.p};
-    if ((st = denoise_on_device("rt_denoise", device, nullptr, w, h, p, &dev, 1))) return st;
-    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_denoise_var_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
-                                           const rt_denoise_planes *device_planes, const rt_denoise_var *v, int sync)
-{
-    rt_status st = denoise_check("rt_denoise_var_device", w, h, p, device_planes);
-    if (st || (st = denoise_var_check("rt_denoise_var_device", v))) return st;
-    return denoise_on_device("rt_denoise_var_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync, v);
-}
-
-extern "C" rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes,
-                                         const rt_denoise_var *v)
-{
-    rt_status st = denoise_check("rt_denoise_var_host", w, h, p, host_planes);
-    if (st || (st = denoise_var_check("rt_denoise_var_host", v))) return st;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_denoise_var_host: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = (size_t)w * (size_t)h;
-    ScopedDevBuf rgb, normal, albedo, z, id, rgb8, var;             // the results are written in place into rgb and var
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
-        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4)) || (st = var.upload(v->variance, n * 12))) return st;
-    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
-    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
-    rt_denoise_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
-                             (const int32_t *)id.p, (float *)rgb.p, (uint8_t *)rgb8.p};
-    const rt_denoise_var dv = {(uint32_t)sizeof dv, (const float *)var.p, v->out_variance ? (float *)var.p : nullptr, v->k_sigma};
-    if ((st = denoise_on_device("rt_denoise_var_host", device, nullptr, w, h, p, &dev, 1, &dv))) return st;
-    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
-    if (v->out_variance) HIP_TRY(hipMemcpy(v->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// ---- temporal accumulation ----------------------------------------------------------------------------------------------
-// An rt_history owns what one stream of frames needs on its device: the two ping-pong sets in one allocation, the camera of the
-// frame the current set holds, and the event that orders a call behind the previous one on the same history.
-struct rt_history {
-    int device = 0; int32_t w = 0, h = 0;
-    DevBuf sets;                        // RT_TEMPORAL_HISTORY_PER_PIXEL bytes a pixel: set 0, set 1
-    int cur = 0;                        // the set the last frame wrote
-    int32_t frames = 0;                 // since create / reset; 0: the next frame reads no history
-    DevCamera cam = {};                 // of the frame in set `cur`
-    DevBuf clip_out;                    // rt_temporal_clip_device with out_linear over rgb_linear: 12 bytes a pixel, made on first use
-    hipEvent_t done = nullptr; bool pending = false;
-    std::mutex mu;
-};
-
-extern "C" rt_status rt_history_create(int device, int32_t w, int32_t h, rt_history **out)
-{
-    if (!out) return fail(RT_ERR_ARG, "rt_history_create: out is NULL");
-    *out = nullptr;
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_history_create: bad image size %d x %d", w, h);
-    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_history_create: %d x %d is more than 2^30 pixels", w, h);
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_history_create: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    rt_history *hst = new rt_history;
-    hst->device = device; hst->w = w; hst->h = h;
-    rt_status st = hst->sets.ensure((size_t)w * (size_t)h * RT_TEMPORAL_HISTORY_PER_PIXEL);
-    if (st == RT_OK && hipEventCreateWithFlags(&hst->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_history_create: hipEventCreate failed");
-    if (st) { hst->sets.release(); delete hst; return st; }
-    *out = hst;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_history_reset(rt_history *hst)
-{
-    if (!hst) return fail(RT_ERR_ARG, "rt_history_reset: history is NULL");
-    std::lock_guard<std::mutex> lk(hst->mu);
-    hst->frames = 0;                    // the next frame reads no tap; it still waits for `done` before it writes a set
-    return RT_OK;
-}
-
-extern "C" void rt_history_destroy(rt_history *hst)
-{
-    if (!hst) return;
-    if (hipSetDevice(hst->device) == hipSuccess) {
-        if (hst->pending) (void)hipEventSynchronize(hst->done);
-        hst->sets.release();            // hipFree waits for the kernels that still use it
-        hst->clip_out.release();
-        if (hst->done) (void)hipEventDestroy(hst->done);
-    }
-    delete hst;
-}
-
-extern "C" int32_t rt_history_frames(const rt_history *hst) { return hst ? hst->frames : 0; }
-
-extern "C" void rt_temporal_default_params(rt_temporal_params *p)
-{
-    if (!p) return;
-    p->struct_size = (uint32_t)sizeof *p;
-    p->alpha = 0.2f; p->max_history = 32; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
-}
-
-// everything that can be refused without a device, for both entry points; the history comes last, so that a caller without a
-// device (which has no history) is told about its other arguments too
-static rt_status temporal_check(const char *name, const rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl)
-{
-    if (!cam || !p || !pl) return fail(RT_ERR_ARG, "%s: camera, params or planes is NULL", name);
-    if (p->struct_size != (uint32_t)sizeof(rt_temporal_params))
-        return fail(RT_ERR_ARG, "%s: rt_temporal_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_temporal_params));
-    if (pl->struct_size != (uint32_t)sizeof(rt_temporal_planes))
-        return fail(RT_ERR_ARG, "%s: rt_temporal_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_temporal_planes));
-    if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(RT_ERR_ARG, "%s: alpha must be in (0, 1]", name);
-    if (p->max_history < 1 || p->max_history > 65535) return fail(RT_ERR_ARG, "%s: max_history is %d, allowed 1..65535", name, p->max_history);
-    for (float s : {p->sigma_normal, p->sigma_depth, p->gamma})
-        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_normal, sigma_depth and gamma must be positive and finite", name);
-    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
-        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
-    if (pl->out_variance && !pl->variance) return fail(RT_ERR_ARG, "%s: out_variance needs the variance plane", name);
-    if (!hst) return fail(RT_ERR_ARG, "%s: history is NULL", name);
-    if (cam->width != hst->w || cam->height != hst->h)
-        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the history %d x %d", name, cam->width, cam->height, hst->w, hst->h);
-    return RT_OK;
-}
-
-extern "C" void rt_temporal_clip_default(rt_temporal_clip *c)
-{
-    if (!c) return;
-    c->struct_size = (uint32_t)sizeof *c;
-    c->radius = 2; c->k_clip = 1.5f; c->min_count = 4; c->clip_history = 2; c->out_clipped = nullptr;
-}
-
-// what rt_temporal_clip_* check on top of temporal_check, without a device
-static rt_status temporal_clip_check(const char *name, const rt_temporal_clip *c)
-{
-    if (!c) return fail(RT_ERR_ARG, "%s: the rt_temporal_clip is NULL", name);
-    if (c->struct_size != (uint32_t)sizeof(rt_temporal_clip))
-        return fail(RT_ERR_ARG, "%s: rt_temporal_clip.struct_size is %u, this library's is %zu", name, c->struct_size, sizeof(rt_temporal_clip));
-    if (c->radius < 1 || c->radius > 3) return fail(RT_ERR_ARG, "%s: radius is %d, allowed 1..3", name, c->radius);
-    if (!(c->k_clip > 0.0f) || !std::isfinite(c->k_clip)) return fail(RT_ERR_ARG, "%s: k_clip must be positive and finite", name);
-    if (c->min_count < 1) return fail(RT_ERR_ARG, "%s: min_count is %d, allowed >= 1", name, c->min_count);
-    if (c->clip_history < 1 || c->clip_history > 65535) return fail(RT_ERR_ARG, "%s: clip_history is %d, allowed 1..65535", name, c->clip_history);
-    return RT_OK;
-}
-
-// motion: NULL (reproject with the two cameras), or the device plane of rt_motion_device for this frame.  clip: NULL (k_temporal),
-// or the validated rectification (k_temporal_clip), its out_clipped a device plane
-static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync,
-                                    const float *motion = nullptr, const rt_temporal_clip *clip = nullptr)
-{
-    HIP_TRY(hipSetDevice(hst->device));
-    std::lock_guard<std::mutex> lk(hst->mu);
-    if (hst->pending) HIP_TRY(hipStreamWaitEvent(st, hst->done, 0));
-    const size_t n = (size_t)hst->w * (size_t)hst->h;
-    TemporalRequest R = {};
-    R.width = hst->w; R.height = hst->h; R.has_history = hst->frames > 0;
-    camera_setup(*cam, R.cur);
-    R.old = hst->cam;
-    R.alpha = p->alpha; R.max_history = p->max_history; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth;
-    R.inv_gamma = denoise_inv_gamma(p->gamma);
-    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id; R.variance = pl->variance;
-    R.out_linear = pl->out_linear; R.out_variance = pl->out_variance; R.out_history = pl->out_history; R.out_rgb8 = pl->out_rgb8;
-    float4 *set0 = (float4 *)hst->sets.p;
-    const int next = hst->cur ^ 1;
-    R.prev = set0 + (size_t)hst->cur * 3 * n; R.next = set0 + (size_t)next * 3 * n;
-    R.motion = motion;
-    if (clip) {
-        // k_temporal_clip's workgroups read their neighbours' pixels of rgb_linear: where out_linear overlaps it, the kernel writes
-        // a plane of the history's and the result is copied behind it on the same stream
-        const char *in = (const char *)pl->rgb_linear, *out = (const char *)pl->out_linear;
-        const bool overlap = out < in + n * 12 && in < out + n * 12;
-        if (overlap) {
-            rt_status rs = hst->clip_out.ensure(n * 12);
-            if (rs) return rs;
-            R.out_linear = (float *)hst->clip_out.p;
-        }
-        TemporalClipRequest CR = {};
-        CR.frame = R;
-        CR.radius = clip->radius; CR.min_count = clip->min_count; CR.k_clip = clip->k_clip; CR.clip_history = clip->clip_history;
-        CR.out_clipped = clip->out_clipped;
-        rtk_launch_temporal_clip(st, CR);
-        HIP_TRY(hipGetLastError());
-        if (overlap) HIP_TRY(hipMemcpyAsync(pl->out_linear, hst->clip_out.p, n * 12, hipMemcpyDeviceToDevice, st));
-    } else {
-        rtk_launch_temporal(st, R);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(hst->done, st));
-    hst->pending = true;
-    hst->cur = next; hst->cam = R.cur; hst->frames++;
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); hst->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
-                                        const rt_temporal_planes *device_planes, int sync)
-{
-    rt_status st = temporal_check("rt_temporal_device", hst, cam, p, device_planes);
-    if (st) return st;
-    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync);
-}
-
-// the host entry points: upload, accumulate, download.  motion: NULL (rt_temporal), or this frame's plane on the host
-static rt_status temporal_host(const char *name, rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
-                               const float *motion, const rt_temporal_clip *clip = nullptr)
-{
-    rt_status st = temporal_check(name, hst, cam, p, host_planes);
-    if (st) return st;
-    HIP_TRY(hipSetDevice(hst->device));
-    const size_t n = (size_t)hst->w * (size_t)hst->h;
-    ScopedDevBuf rgb, normal, albedo, z, id, var, hist, rgb8, mv;   // the results are written in place into rgb and var
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = normal.upload(host_planes->normal, n * 12)) ||
-        (st = albedo.upload(host_planes->albedo, n * 12)) || (st = z.upload(host_planes->z, n * 4))) return st;
-    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
-    if (host_planes->variance && (st = var.upload(host_planes->variance, n * 12))) return st;
-    if (motion && (st = mv.upload(motion, n * 12))) return st;
-    if (host_planes->out_history && (st = hist.ensure(n * 4))) return st;
-    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
-    const rt_temporal_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)normal.p, (const float *)albedo.p, (const float *)z.p,
-                                    (const int32_t *)id.p, (const float *)var.p, (float *)rgb.p,
-                                    host_planes->out_variance ? (float *)var.p : nullptr, (float *)hist.p, (uint8_t *)rgb8.p};
-    ScopedDevBuf mask;
-    rt_temporal_clip dev_clip;
-    if (clip) {
-        dev_clip = *clip;
-        if (clip->out_clipped && (st = mask.ensure(n * 4))) return st;
-        dev_clip.out_clipped = (float *)mask.p;
-    }
-    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1, (const float *)mv.p, clip ? &dev_clip : nullptr))) return st;
-    if (clip && clip->out_clipped) HIP_TRY(hipMemcpy(clip->out_clipped, mask.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host_planes->out_linear, rgb.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_variance) HIP_TRY(hipMemcpy(host_planes->out_variance, var.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_history) HIP_TRY(hipMemcpy(host_planes->out_history, hist.p, n * 4, hipMemcpyDeviceToHost));
-    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes)
-{
-    return temporal_host("rt_temporal", hst, cam, p, host_planes, nullptr);
-}
-
-extern "C" rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
-                                               const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
-{
-    if (!motion_dev) return fail(RT_ERR_ARG, "rt_temporal_motion_device: the motion plane is NULL");
-    rt_status st = temporal_check("rt_temporal_motion_device", hst, cam, p, device_planes);
-    if (st) return st;
-    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev);
-}
-
-extern "C" rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
-                                        const float *motion)
-{
-    if (!motion) return fail(RT_ERR_ARG, "rt_temporal_motion: the motion plane is NULL");
-    return temporal_host("rt_temporal_motion", hst, cam, p, host_planes, motion);
-}
-
-extern "C" rt_status rt_temporal_clip_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
-                                             const rt_temporal_clip *clip, const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
-{
-    rt_status st = temporal_clip_check("rt_temporal_clip_device", clip);
-    if (st) return st;
-    if ((st = temporal_check("rt_temporal_clip_device", hst, cam, p, device_planes))) return st;
-    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev, clip);
-}
-
-extern "C" rt_status rt_temporal_clip_host(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_clip *clip,
-                                           const rt_temporal_planes *host_planes, const float *motion)
-{
-    rt_status st = temporal_clip_check("rt_temporal_clip_host", clip);
-    if (st) return st;
-    return temporal_host("rt_temporal_clip_host", hst, cam, p, host_planes, motion, clip);
-}
-
-// ---- motion vectors ---------------------------------------------------------------------------------------------------------
-// One affine map in double, X -> r X + t (r row-major), and the two steps the node chains are made of.
-namespace {
-struct Affine64 {
-    double r[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-    // this, then M X + c (M column-major float[9], like rt_node's)
-    Affine64 then(const float *M, const double c[3]) const
-    {
-        Affine64 o;
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) o.r[3 * i + j] = (double)M[i] * r[j] + (double)M[3 + i] * r[3 + j] + (double)M[6 + i] * r[6 + j];
-            o.t[i] = (double)M[i] * t[0] + (double)M[3 + i] * t[1] + (double)M[6 + i] * t[2] + c[i];
-        }
-        return o;
-    }
-    // this, then A
-    Affine64 then(const Affine64 &A) const
-    {
-        Affine64 o;
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) o.r[3 * i + j] = A.r[3 * i] * r[j] + A.r[3 * i + 1] * r[3 + j] + A.r[3 * i + 2] * r[6 + j];
-            o.t[i] = A.r[3 * i] * t[0] + A.r[3 * i + 1] * t[1] + A.r[3 * i + 2] * t[2] + A.t[i];
-        }
-        return o;
-    }
-};
-}
-
-// The table of rt_motion: per node i the map A_i of this frame's world into the previous frame's -- TransformTo down the chain
-// root .. i of `nodes` (per node itm (X - pos)), then TransformFrom up the chain i .. root of `prev` (per node tm X + pos) --
-// composed in double and rounded to float once.  A node whose chain is bit-identical in both arrays (and every node when prev
-// is NULL) gets exactly the identity.  The parents were validated by the caller.
-static void motion_table(const rt_node *nodes, const rt_node *prev, int32_t n, std::vector<DevNodeMotion> &table)
-{
-    table.resize((size_t)n);
-    std::vector<Affine64> to, from;     // world -> node i down the current chain; node i -> world up the previous chain
-    std::vector<char> same((size_t)n, 1);
-    if (prev) { to.resize((size_t)n); from.resize((size_t)n); }
-    for (int32_t i = 0; i < n; i++) {
-        Affine64 A;
-        if (prev) {
-            const rt_node &c = nodes[i], &o = prev[i];
-            same[i] = c.parent == o.parent && !memcmp(c.tm, o.tm, 36) && !memcmp(c.itm, o.itm, 36) && !memcmp(c.pos, o.pos, 12) &&
-                      (c.parent < 0 || same[c.parent]);
-            double mp[3];               // itm (X - pos) = itm X - itm pos
-            for (int k = 0; k < 3; k++) mp[k] = -((double)c.itm[k] * c.pos[0] + (double)c.itm[3 + k] * c.pos[1] + (double)c.itm[6 + k] * c.pos[2]);
-            to[i] = (c.parent < 0 ? Affine64() : to[c.parent]).then(c.itm, mp);
-            const double op[3] = {o.pos[0], o.pos[1], o.pos[2]};
-            const Affine64 up = Affine64().then(o.tm, op);
-            from[i] = o.parent < 0 ? up : up.then(from[o.parent]);
-            if (!same[i]) A = to[i].then(from[i]);
-        }
-        for (int k = 0; k < 3; k++) table[i].row[k] = make_float4((float)A.r[3 * k], (float)A.r[3 * k + 1], (float)A.r[3 * k + 2], (float)A.t[k]);
-    }
-}
-
-// everything that can be refused without a device, for both entry points
-static rt_status motion_check(const char *name, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
-                              int32_t n_nodes, const rt_motion_planes *pl)
-{
-    if (!cam || !prev_cam || !nodes || !pl) return fail(RT_ERR_ARG, "%s: camera, prev_cam, nodes or planes is NULL", name);
-    if (pl->struct_size != (uint32_t)sizeof(rt_motion_planes))
-        return fail(RT_ERR_ARG, "%s: rt_motion_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_motion_planes));
-    if (!pl->z || !pl->object_id || !pl->motion) return fail(RT_ERR_ARG, "%s: z, object_id and motion are required", name);
-    if (n_nodes <= 0) return fail(RT_ERR_ARG, "%s: n_nodes is %d", name, n_nodes);
-    for (const rt_node *arr : {nodes, prev_nodes})
-        for (int32_t i = 0; arr && i < n_nodes; i++)
-            if (arr[i].parent < -1 || arr[i].parent >= i)
-                return fail(RT_ERR_ARG, "%s: node %d of %s has parent %d (a parent must precede its child; -1: none)", name, i,
-                            arr == nodes ? "nodes" : "prev_nodes", arr[i].parent);
-    if (cam->width <= 0 || cam->height <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, cam->width, cam->height);
-    if (cam->width != prev_cam->width || cam->height != prev_cam->height)
-        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the previous one %d x %d", name, cam->width, cam->height, prev_cam->width, prev_cam->height);
-    if ((long long)cam->width * cam->height > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, cam->width, cam->height);
-    return RT_OK;
-}
-
-// The node table of the last rt_motion call per device: kept between calls (a frame's table is uploaded only when it differs
-// from the one the device holds).  Every call on the device shares it, so -- like the denoiser's scratch -- every call orders its
-// stream behind the previous call's `done` event, whatever that call's stream was and whether or not the table changes: `done`
-// then stands for ALL earlier calls, and waiting for it on the host before an overwrite leaves no kernel that still reads the
-// table.  Released with the last scene (rt_scene_destroy), like the denoiser's scratch.
-struct MotionDevice { DevBuf table; std::vector<DevNodeMotion> held; hipEvent_t done = nullptr; bool pending = false; };
-static std::mutex g_motion_mu;
-static std::vector<std::pair<int, MotionDevice>> g_motion;          // (device, its table); under g_motion_mu
-
-static void motion_release_all()
-{
-    std::lock_guard<std::mutex> lk(g_motion_mu);
-    for (auto &d : g_motion) {
-        if (hipSetDevice(d.first) != hipSuccess) continue;
-        d.second.table.release();                                   // hipFree waits for the kernels that still use it
-        if (d.second.done) (void)hipEventDestroy(d.second.done);
-    }
-    g_motion.clear();
-}
-
-static rt_status motion_on_device(const char *name, int device, hipStream_t st, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
-                                  const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *pl, int sync)
-{
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
-    HIP_TRY(hipSetDevice(device));
-    std::vector<DevNodeMotion> table;
-    motion_table(nodes, prev_nodes, n_nodes, table);
-    std::lock_guard<std::mutex> lk(g_motion_mu);
-    MotionDevice *D = nullptr;
-    for (auto &d : g_motion) if (d.first == device) D = &d.second;
-    if (!D) { g_motion.emplace_back(device, MotionDevice()); D = &g_motion.back().second; }
-    if (!D->done) HIP_TRY(hipEventCreateWithFlags(&D->done, hipEventDisableTiming));
-    const size_t bytes = table.size() * sizeof(DevNodeMotion);
-    if (D->pending) HIP_TRY(hipStreamWaitEvent(st, D->done, 0));
-    if (D->held.size() != table.size() || memcmp(D->held.data(), table.data(), bytes) != 0) {
-        if (D->pending) { HIP_TRY(hipEventSynchronize(D->done)); D->pending = false; }
-        D->held.clear();
-        rt_status rs = D->table.upload(table.data(), bytes);
-        if (rs) return rs;
-        D->held = table;
-    }
-    MotionRequest R = {};
-    R.width = cam->width; R.height = cam->height; R.n_nodes = n_nodes;
-    camera_setup(*cam, R.cur);
-    camera_setup(*prev_cam, R.old);
-    R.z = pl->z; R.object_id = pl->object_id; R.table = (const DevNodeMotion *)D->table.p; R.motion = pl->motion;
-    rtk_launch_motion(st, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(D->done, st));
-    D->pending = true;
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); D->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_motion_device(int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
-                                      const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *device_planes, int sync)
-{
-    rt_status st = motion_check("rt_motion_device", cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes);
-    if (st) return st;
-    return motion_on_device("rt_motion_device", device, (hipStream_t)hip_stream, cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes, sync);
-}
-
-extern "C" rt_status rt_motion(int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
-                               int32_t n_nodes, const rt_motion_planes *host_planes)
-{
-    rt_status st = motion_check("rt_motion", cam, prev_cam, nodes, prev_nodes, n_nodes, host_planes);
-    if (st) return st;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_motion: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = (size_t)cam->width * (size_t)cam->height;
-    ScopedDevBuf z, id, mv;
-    if ((st = z.upload(host_planes->z, n * 4)) || (st = id.upload(host_planes->object_id, n * 4)) || (st = mv.ensure(n * 12))) return st;
-    const rt_motion_planes dev = {(uint32_t)sizeof dev, (const float *)z.p, (const int32_t *)id.p, (float *)mv.p};
-    if ((st = motion_on_device("rt_motion", device, nullptr, cam, prev_cam, nodes, prev_nodes, n_nodes, &dev, 1))) return st;
-    HIP_TRY(hipMemcpy(host_planes->motion, mv.p, n * 12, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// ---- exposure and tone mapping --------------------------------------------------------------------------------------------
-// An rt_exposure owns the device block of one stream of frames (ToneMapRequest::State) and the event that orders a call behind
-// the previous one on the same state.  The host keeps no copy of what the meter computes: the getters read the block back.
-struct rt_exposure {
-    int device = 0;
-    DevBuf block;                       // one ToneMapRequest::State
-    hipEvent_t done = nullptr; bool pending = false;
-    std::mutex mu;
-};
-
-// the block back to all zero (an empty working histogram, no metered frame), behind the calls issued so far
-static rt_status exposure_clear(rt_exposure *e)
-{
-    if (e->pending) HIP_TRY(hipStreamWaitEvent(nullptr, e->done, 0));
-    HIP_TRY(hipMemsetAsync(e->block.p, 0, sizeof(ToneMapRequest::State), nullptr));
-    HIP_TRY(hipEventRecord(e->done, nullptr));
-    e->pending = true;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_exposure_create(int device, rt_exposure **out)
-{
-    if (!out) return fail(RT_ERR_ARG, "rt_exposure_create: out is NULL");
-    *out = nullptr;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_exposure_create: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    rt_exposure *e = new rt_exposure;
-    e->device = device;
-    rt_status st = e->block.ensure(sizeof(ToneMapRequest::State));
-    if (st == RT_OK && hipEventCreateWithFlags(&e->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_exposure_create: hipEventCreate failed");
-    if (st == RT_OK) st = exposure_clear(e);
-    if (st) { rt_exposure_destroy(e); return st; }
-    *out = e;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_exposure_reset(rt_exposure *e)
-{
-    if (!e) return fail(RT_ERR_ARG, "rt_exposure_reset: state is NULL");
-    HIP_TRY(hipSetDevice(e->device));
-    std::lock_guard<std::mutex> lk(e->mu);
-    return exposure_clear(e);
-}
-
-extern "C" void rt_exposure_destroy(rt_exposure *e)
-{
-    if (!e) return;
-    if (hipSetDevice(e->device) == hipSuccess) {
-        if (e->pending) (void)hipEventSynchronize(e->done);
-        e->block.release();             // hipFree waits for the kernels that still use it
-        if (e->done) (void)hipEventDestroy(e->done);
-    }
-    delete e;
-}
-
-// waits for the calls issued on the state and copies its block to the host
-static rt_status exposure_read(const char *name, rt_exposure *e, ToneMapRequest::State &out)
-{
-    if (!e) return fail(RT_ERR_ARG, "%s: state is NULL", name);
-    HIP_TRY(hipSetDevice(e->device));
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (e->pending) { HIP_TRY(hipEventSynchronize(e->done)); e->pending = false; }
-    HIP_TRY(hipMemcpy(&out, e->block.p, sizeof out, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_exposure_get(rt_exposure *e, float *log2_exposure, double *log2_metered, uint32_t *metered_pixels)
-{
-    ToneMapRequest::State s;
-    rt_status st = exposure_read("rt_exposure_get", e, s);
-    if (st) return st;
-    if (log2_exposure) *log2_exposure = s.E;
-    if (log2_metered) *log2_metered = s.lbar;
-    if (metered_pixels) *metered_pixels = s.n;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_exposure_histogram(rt_exposure *e, uint32_t out[256])
-{
-    if (!out) return fail(RT_ERR_ARG, "rt_exposure_histogram: out is NULL");
-    ToneMapRequest::State s;
-    rt_status st = exposure_read("rt_exposure_histogram", e, s);
-    if (st) return st;
-    memcpy(out, s.last, sizeof s.last);
-    return RT_OK;
-}
-
-extern "C" void rt_tonemap_default_params(rt_tonemap_params *p)
-{
-    if (!p) return;
-    p->struct_size = (uint32_t)sizeof *p;
-    p->op = RT_TONEMAP_ACES; p->auto_exposure = 1;
-    p->key = 0.18f; p->ev_bias = 0.0f; p->ev_min = -16.0f; p->ev_max = 16.0f; p->p_low = 0.10f; p->p_high = 0.90f;
-    p->adapt_up = 1.0f; p->adapt_down = 1.0f; p->white = 4.0f; p->gamma = 2.2f;
-}
-
-// everything that can be refused without a device, for both entry points
-static rt_status tonemap_check(const char *name, const rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *pl)
-{
-    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
-    if (p->struct_size != (uint32_t)sizeof(rt_tonemap_params))
-        return fail(RT_ERR_ARG, "%s: rt_tonemap_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_tonemap_params));
-    if (pl->struct_size != (uint32_t)sizeof(rt_tonemap_planes))
-        return fail(RT_ERR_ARG, "%s: rt_tonemap_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_tonemap_planes));
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, w, h);
-    if (p->op != RT_TONEMAP_CLAMP && p->op != RT_TONEMAP_REINHARD && p->op != RT_TONEMAP_ACES) return fail(RT_ERR_ARG, "%s: no operator %d", name, p->op);
-    for (float s : {p->key, p->white, p->gamma})
-        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: key, white and gamma must be positive and finite", name);
-    if (!std::isfinite(p->ev_bias) || !std::isfinite(p->ev_min) || !std::isfinite(p->ev_max) || !(p->ev_min <= p->ev_max))
-        return fail(RT_ERR_ARG, "%s: ev_bias, ev_min and ev_max must be finite and ev_min <= ev_max", name);
-    if (!(p->p_low >= 0.0f && p->p_low < p->p_high && p->p_high <= 1.0f)) return fail(RT_ERR_ARG, "%s: the percentiles must be 0 <= p_low < p_high <= 1", name);
-    for (float a : {p->adapt_up, p->adapt_down})
-        if (!(a > 0.0f && a <= 1.0f)) return fail(RT_ERR_ARG, "%s: adapt_up and adapt_down must be in (0, 1]", name);
-    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
-    if (!pl->out_display && !pl->out_rgb8) return fail(RT_ERR_ARG, "%s: one of out_display and out_rgb8 is required", name);
-    if (p->auto_exposure && !e) return fail(RT_ERR_ARG, "%s: auto-exposure needs an rt_exposure", name);
-    if (e && e->device != device) return fail(RT_ERR_ARG, "%s: the state is on device %d, the call names %d", name, e->device, device);
-    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, w, h);
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
-    return RT_OK;
-}
-
-static rt_status tonemap_on_device(rt_exposure *e, int device, hipStream_t st, int32_t w, int32_t h, const rt_tonemap_params *p,
-                                   const rt_tonemap_planes *pl, int sync)
-{
-    HIP_TRY(hipSetDevice(device));
-    ToneMapRequest R = {};
-    R.width = w; R.height = h; R.op = p->op; R.meter = p->auto_exposure != 0;
-    R.log2_key = log2((double)p->key);
-    R.ev_bias = p->ev_bias; R.ev_min = p->ev_min; R.ev_max = p->ev_max; R.p_low = p->p_low; R.p_high = p->p_high;
-    R.adapt_up = p->adapt_up; R.adapt_down = p->adapt_down;
-    R.scale = (float)exp2((double)p->ev_bias);
-    R.white2 = (float)((double)p->white * (double)p->white);
-    R.inv_gamma = denoise_inv_gamma(p->gamma);
-    R.rgb_linear = pl->rgb_linear; R.object_id = pl->object_id; R.out_display = pl->out_display; R.out_rgb8 = pl->out_rgb8;
-    if (!R.meter) {                     // fixed exposure: nothing of the state is read or written, nothing to order
-        rtk_launch_tonemap(st, R);
-        HIP_TRY(hipGetLastError());
-        if (sync) HIP_TRY(hipStreamSynchronize(st));
-        return RT_OK;
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (e->pending) HIP_TRY(hipStreamWaitEvent(st, e->done, 0));
-    R.state = (ToneMapRequest::State *)e->block.p;
-    rtk_launch_tonemap(st, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->done, st));
-    e->pending = true;
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); e->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_tonemap_device(rt_exposure *e, int device, void *hip_stream, int32_t w, int32_t h, const rt_tonemap_params *p,
-                                       const rt_tonemap_planes *device_planes, int sync)
-{
-    rt_status st = tonemap_check("rt_tonemap_device", e, device, w, h, p, device_planes);
-    if (st) return st;
-    return tonemap_on_device(e, device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
-}
-
-extern "C" rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *host_planes)
-{
-    rt_status st = tonemap_check("rt_tonemap", e, device, w, h, p, host_planes);
-    if (st) return st;
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = (size_t)w * (size_t)h;
-    ScopedDevBuf rgb, id, rgb8;                                     // the display plane is written in place into rgb
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12))) return st;
-    if (host_planes->object_id && (st = id.upload(host_planes->object_id, n * 4))) return st;
-    if (host_planes->out_rgb8 && (st = rgb8.ensure(n * 3))) return st;
-    const rt_tonemap_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const int32_t *)id.p,
-                                   host_planes->out_display ? (float *)rgb.p : nullptr, (uint8_t *)rgb8.p};
-    if ((st = tonemap_on_device(e, device, nullptr, w, h, p, &dev, 1))) return st;
-    if (host_planes->out_display) HIP_TRY(hipMemcpy(host_planes->out_display, rgb.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_rgb8) HIP_TRY(hipMemcpy(host_planes->out_rgb8, rgb8.p, n * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// ---- bloom ------------------------------------------------------------------------------------------------------------------
-// An rt_bloom owns the pyramid of one W x H stream of frames on its device -- every level the size allows, whatever `levels` a
-// call asks for -- and the event that orders a call behind the previous one on the same object.
-struct rt_bloom {
-    int device = 0; int32_t w = 0, h = 0;
-    DevBuf pyramid;
-    hipEvent_t done = nullptr; bool pending = false;
-    std::mutex mu;
-};
-
-extern "C" rt_status rt_bloom_create(int device, int32_t w, int32_t h, rt_bloom **out)
-{
-    if (!out) return fail(RT_ERR_ARG, "rt_bloom_create: out is NULL");
-    *out = nullptr;
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_bloom_create: bad image size %d x %d", w, h);
-    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_bloom_create: %d x %d is more than 2^30 pixels", w, h);
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_bloom_create: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    rt_bloom *b = new rt_bloom;
-    b->device = device; b->w = w; b->h = h;
-    const BloomPlan all = rtk_bloom_plan(w, h, RT_BLOOM_MAX_LEVELS);
-    rt_status st = b->pyramid.ensure(all.off[all.levels] * 12);
-    if (st == RT_OK && hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_bloom_create: hipEventCreate failed");
-    if (st) { rt_bloom_destroy(b); return st; }
-    *out = b;
-    return RT_OK;
-}
-
-extern "C" void rt_bloom_destroy(rt_bloom *b)
-{
-    if (!b) return;
-    if (hipSetDevice(b->device) == hipSuccess) {
-        if (b->pending) (void)hipEventSynchronize(b->done);
-        b->pyramid.release();           // hipFree waits for the kernels that still use it
-        if (b->done) (void)hipEventDestroy(b->done);
-    }
-    delete b;
-}
-
-extern "C" void rt_bloom_default_params(rt_bloom_params *p)
-{
-    if (!p) return;
-    p->struct_size = (uint32_t)sizeof *p;
-    p->threshold = 1.0f; p->knee = 0.5f; p->intensity = 0.25f; p->spread = 0.7f; p->levels = 6; p->exposure_ev = 0.0f;
-}
-
-extern "C" rt_status rt_bloom_plan(int32_t w, int32_t h, int32_t levels, int32_t *levels_used, int32_t *tail_level)
-{
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_bloom_plan: bad image size %d x %d", w, h);
-    if (levels < 1) return fail(RT_ERR_ARG, "rt_bloom_plan: levels is %d, must be at least 1", levels);
-    const BloomPlan P = rtk_bloom_plan(w, h, levels);
-    if (levels_used) *levels_used = P.levels;
-    if (tail_level) *tail_level = P.tail;
-    return RT_OK;
-}
-
-static bool bloom_overlap(const void *a, const void *b, size_t bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + bytes && y < x + bytes;
-}
-
-// everything that can be refused without a device, for both entry points
-static rt_status bloom_check(const char *name, const rt_bloom *b, const rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *pl)
-{
-    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
-    if (p->struct_size != (uint32_t)sizeof(rt_bloom_params))
-        return fail(RT_ERR_ARG, "%s: rt_bloom_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_bloom_params));
-    if (pl->struct_size != (uint32_t)sizeof(rt_bloom_planes))
-        return fail(RT_ERR_ARG, "%s: rt_bloom_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_bloom_planes));
-    for (float s : {p->threshold, p->knee, p->intensity, p->spread})
-        if (!(s >= 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: threshold, knee, intensity and spread must be finite and not negative", name);
-    if (p->spread > 1.0f || p->knee > 1.0f) return fail(RT_ERR_ARG, "%s: spread and knee must be at most 1", name);
-    if (p->levels < 1) return fail(RT_ERR_ARG, "%s: levels is %d, must be at least 1", name, p->levels);
-    if (!std::isfinite(p->exposure_ev)) return fail(RT_ERR_ARG, "%s: exposure_ev must be finite", name);
-    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
-    if (!pl->out && !pl->out_bloom) return fail(RT_ERR_ARG, "%s: one of out and out_bloom is required", name);
-    // what needs the object comes last: without a device there is none, and everything above is still refused by name
-    if (!b) return fail(RT_ERR_ARG, "%s: the rt_bloom is NULL", name);
-    if (e && e->device != b->device) return fail(RT_ERR_ARG, "%s: the exposure state is on device %d, the rt_bloom on %d", name, e->device, b->device);
-    const size_t bytes = (size_t)b->w * (size_t)b->h * 12;
-    if ((pl->out != pl->rgb_linear && bloom_overlap(pl->out, pl->rgb_linear, bytes)) || bloom_overlap(pl->out_bloom, pl->rgb_linear, bytes) ||
-        bloom_overlap(pl->out_bloom, pl->out, bytes))
-        return fail(RT_ERR_ARG, "%s: planes overlap (only out == rgb_linear is allowed)", name);
-    return RT_OK;
-}
-
-static rt_status bloom_on_device(rt_bloom *b, rt_exposure *e, hipStream_t st, const rt_bloom_params *p, const rt_bloom_planes *pl, int sync)
-{
-    HIP_TRY(hipSetDevice(b->device));
-    BloomRequest R = {};
-    R.width = b->w; R.height = b->h;
-    R.threshold = p->threshold; R.knee_k = p->knee * p->threshold; R.intensity = p->intensity;
-    R.spread = p->spread; R.one_minus_spread = 1.0f - p->spread;
-    R.scale = (float)exp2((double)p->exposure_ev);
-    R.rgb_linear = pl->rgb_linear; R.out = pl->out; R.out_bloom = pl->out_bloom;
-    R.plan = rtk_bloom_plan(b->w, b->h, p->levels);
-    std::lock_guard<std::mutex> lk(b->mu);
-    std::unique_lock<std::mutex> le;
-    if (e) le = std::unique_lock<std::mutex>(e->mu);
-    R.pyramid = (float *)b->pyramid.p;
-    if (b->pending) HIP_TRY(hipStreamWaitEvent(st, b->done, 0));
-    if (e) {                            // the state is read: behind the calls that write it, and the next one of them behind this
-        if (e->pending) HIP_TRY(hipStreamWaitEvent(st, e->done, 0));
-        R.state = (const ToneMapRequest::State *)e->block.p;
-    }
-    HIP_TRY(rtk_launch_bloom(st, R));
-    HIP_TRY(hipEventRecord(b->done, st));
-    b->pending = true;
-    if (e) { HIP_TRY(hipEventRecord(e->done, st)); e->pending = true; }
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); b->pending = false; if (e) e->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_bloom_device(rt_bloom *b, rt_exposure *e, void *hip_stream, const rt_bloom_params *p,
-                                     const rt_bloom_planes *device_planes, int sync)
-{
-    rt_status st = bloom_check("rt_bloom_device", b, e, p, device_planes);
-    if (st) return st;
-    return bloom_on_device(b, e, (hipStream_t)hip_stream, p, device_planes, sync);
-}
-
-extern "C" rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *host_planes)
-{
-    rt_status st = bloom_check("rt_bloom_host", b, e, p, host_planes);
-    if (st) return st;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t n = (size_t)b->w * (size_t)b->h;
-    ScopedDevBuf rgb, only;                                         // `out` is written in place into rgb
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12))) return st;
-    if (host_planes->out_bloom && (st = only.ensure(n * 12))) return st;
-    const rt_bloom_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, host_planes->out ? (float *)rgb.p : nullptr, (float *)only.p};
-    if ((st = bloom_on_device(b, e, nullptr, p, &dev, 1))) return st;
-    if (host_planes->out) HIP_TRY(hipMemcpy(host_planes->out, rgb.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_bloom) HIP_TRY(hipMemcpy(host_planes->out_bloom, only.p, n * 12, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// ---- motion blur ------------------------------------------------------------------------------------------------------------
-// An rt_motion_blur owns the tile-max and neighbour-max planes of one W x H stream of frames on its device -- sized for K = 2,
-// the most tiles a call can ask for -- and the event that orders a call behind the previous one on the same object.
-#define RT_MBLUR_MIN_K 2
-#define RT_MBLUR_MAX_K 32
-struct rt_motion_blur {
-    int device = 0; int32_t w = 0, h = 0;
-    DevBuf tile_max, tile_nmax;
-    hipEvent_t done = nullptr; bool pending = false;
-    std::mutex mu;
-};
-
-static size_t mblur_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
-{
-    const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
-    if (tx) *tx = x;
-    if (ty) *ty = y;
-    return (size_t)x * (size_t)y;
-}
-
-extern "C" rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_motion_blur **out)
-{
-    if (!out) return fail(RT_ERR_ARG, "rt_motion_blur_create: out is NULL");
-    *out = nullptr;
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_motion_blur_create: bad image size %d x %d", w, h);
-    if ((long long)w * h > RT_DENOISE_MAX_PIXELS) return fail(RT_ERR_LIMIT, "rt_motion_blur_create: %d x %d is more than 2^30 pixels", w, h);
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_motion_blur_create: device %d is not gfx950 (no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
-    rt_motion_blur *mb = new rt_motion_blur;
-    mb->device = device; mb->w = w; mb->h = h;
-    const size_t bytes = mblur_tiles(w, h, RT_MBLUR_MIN_K, nullptr, nullptr) * 8;
-    rt_status st = mb->tile_max.ensure(bytes);
-    if (st == RT_OK) st = mb->tile_nmax.ensure(bytes);
-    if (st == RT_OK && hipEventCreateWithFlags(&mb->done, hipEventDisableTiming) != hipSuccess) st = fail(RT_ERR_DEVICE, "rt_motion_blur_create: hipEventCreate failed");
-    if (st) { rt_motion_blur_destroy(mb); return st; }
-    *out = mb;
-    return RT_OK;
-}
-
-extern "C" void rt_motion_blur_destroy(rt_motion_blur *mb)
-{
-    if (!mb) return;
-    if (hipSetDevice(mb->device) == hipSuccess) {
-        if (mb->pending) (void)hipEventSynchronize(mb->done);
-        mb->tile_max.release(); mb->tile_nmax.release();        // hipFree waits for the kernels that still use them
-        if (mb->done) (void)hipEventDestroy(mb->done);
-    }
-    delete mb;
-}
-
-extern "C" void rt_motion_blur_default_params(rt_motion_blur_params *p)
-{
-    if (!p) return;
-    p->struct_size = (uint32_t)sizeof *p;
-    p->shutter = 0.5f; p->max_blur = 16; p->samples = 15; p->depth_extent = 0.05f;
-}
-
-extern "C" rt_status rt_motion_blur_tiles(int32_t w, int32_t h, int32_t max_blur, int32_t *tx, int32_t *ty)
-{
-    if (w <= 0 || h <= 0) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: bad image size %d x %d", w, h);
-    if (max_blur < RT_MBLUR_MIN_K || max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: max_blur is %d, must be 2..32", max_blur);
-    mblur_tiles(w, h, max_blur, tx, ty);
-    return RT_OK;
-}
-
-// everything that can be refused without a device, for both entry points
-static rt_status mblur_check(const char *name, const rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl)
-{
-    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
-    if (p->struct_size != (uint32_t)sizeof(rt_motion_blur_params))
-        return fail(RT_ERR_ARG, "%s: rt_motion_blur_params.struct_size is %u, this library's is %zu", name, p->struct_size, sizeof(rt_motion_blur_params));
-    if (pl->struct_size != (uint32_t)sizeof(rt_motion_blur_planes))
-        return fail(RT_ERR_ARG, "%s: rt_motion_blur_planes.struct_size is %u, this library's is %zu", name, pl->struct_size, sizeof(rt_motion_blur_planes));
-    if (!std::isfinite(p->shutter) || !(p->shutter >= 0.0f) || p->shutter > 2.0f) return fail(RT_ERR_ARG, "%s: shutter must be finite and 0..2", name);
-    if (p->max_blur < RT_MBLUR_MIN_K || p->max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "%s: max_blur is %d, must be 2..32", name, p->max_blur);
-    if (p->samples < 3 || p->samples > 63 || !(p->samples & 1)) return fail(RT_ERR_ARG, "%s: samples is %d, must be odd and 3..63", name, p->samples);
-    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
-    if (!pl->rgb_linear || !pl->motion || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, motion, z and out are required", name);
-    // what needs the object comes last: without a device there is none, and everything above is still refused by name
-    if (!mb) return fail(RT_ERR_ARG, "%s: the rt_motion_blur is NULL", name);
-    const size_t n = (size_t)mb->w * (size_t)mb->h;
-    const struct { const void *p; size_t bytes; } planes[5] = {
-        {pl->rgb_linear, n * 12}, {pl->motion, n * 12}, {pl->z, n * 4}, {pl->out, n * 12},
-        {pl->out_tiles, mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8}};
-    for (int a = 0; a < 5; a++)
-        for (int b = a + 1; b < 5; b++) {
-            const uintptr_t x = (uintptr_t)planes[a].p, y = (uintptr_t)planes[b].p;
-            if (x && y && x < y + planes[b].bytes && y < x + planes[a].bytes)
-                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
-        }
-    return RT_OK;
-}
-
-static rt_status mblur_on_device(rt_motion_blur *mb, hipStream_t st, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl, int sync)
-{
-    HIP_TRY(hipSetDevice(mb->device));
-    MotionBlurRequest R = {};
-    R.width = mb->w; R.height = mb->h; R.K = p->max_blur; R.N = p->samples;
-    mblur_tiles(mb->w, mb->h, p->max_blur, &R.tiles_x, &R.tiles_y);
-    R.half_shutter = 0.5f * p->shutter; R.two_over_n = 2.0f / (float)p->samples; R.depth_extent = p->depth_extent;
-    R.rgb_linear = pl->rgb_linear; R.motion = pl->motion; R.z = pl->z; R.out = pl->out; R.out_tiles = pl->out_tiles;
-    std::lock_guard<std::mutex> lk(mb->mu);
-    R.tile_max = (float *)mb->tile_max.p; R.tile_nmax = (float *)mb->tile_nmax.p;
-    if (mb->pending) HIP_TRY(hipStreamWaitEvent(st, mb->done, 0));
-    HIP_TRY(rtk_launch_motion_blur(st, R));
-    HIP_TRY(hipEventRecord(mb->done, st));
-    mb->pending = true;
-    if (sync) { HIP_TRY(hipStreamSynchronize(st)); mb->pending = false; }
-    return RT_OK;
-}
-
-extern "C" rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_motion_blur_params *p,
-                                           const rt_motion_blur_planes *device_planes, int sync)
-{
-    rt_status st = mblur_check("rt_motion_blur_device", mb, p, device_planes);
-    if (st) return st;
-    return mblur_on_device(mb, (hipStream_t)hip_stream, p, device_planes, sync);
-}
-
-extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *host_planes)
-{
-    rt_status st = mblur_check("rt_motion_blur_host", mb, p, host_planes);
-    if (st) return st;
-    HIP_TRY(hipSetDevice(mb->device));
-    const size_t n = (size_t)mb->w * (size_t)mb->h;
-    const size_t tile_bytes = mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8;
-    ScopedDevBuf rgb, motion, z, out, tiles;
-    if ((st = rgb.upload(host_planes->rgb_linear, n * 12)) || (st = motion.upload(host_planes->motion, n * 12)) ||
-        (st = z.upload(host_planes->z, n * 4)) || (st = out.ensure(n * 12))) return st;
-    if (host_planes->out_tiles && (st = tiles.ensure(tile_bytes))) return st;
-    const rt_motion_blur_planes dev = {(uint32_t)sizeof dev, (const float *)rgb.p, (const float *)motion.p, (const float *)z.p,
-                                       (float *)out.p, (float *)tiles.p};
-    if ((st = mblur_on_device(mb, nullptr, p, &dev, 1))) return st;
-    HIP_TRY(hipMemcpy(host_planes->out, out.p, n * 12, hipMemcpyDeviceToHost));
-    if (host_planes->out_tiles) HIP_TRY(hipMemcpy(host_planes->out_tiles, tiles.p, tile_bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
 }
 
 extern "C" rt_status rt_render_check(rt_scene *s, int device)

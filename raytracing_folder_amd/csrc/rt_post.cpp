@@ -1,0 +1,981 @@
+// rt_post.cpp -- the image-space stages of the C ABI in include/rt_mi355x.h: denoising, temporal accumulation, motion vectors,
+// exposure and tone mapping, bloom, motion blur.  None of them knows a scene.  Every stage is the same few steps -- check the
+// versioned structs and the image size, find the device, order the stream behind the previous call on the same object, launch,
+// record -- and its host entry point is the device one between an upload and a download; the pieces they share come first.
+// There is no CPU path: without a gfx950 device the calls fail.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <mutex>
+#include <vector>
+
+#include "rt_host.h"
+
+// ---- the shared skeleton --------------------------------------------------------------------------------------------------
+// a versioned struct carries its caller's sizeof first
+static rt_status check_struct(const char *name, const char *type, uint32_t given, size_t ours)
+{
+    if (given != (uint32_t)ours) return fail(RT_ERR_ARG, "%s: %s.struct_size is %u, this library's is %zu", name, type, given, ours);
+    return RT_OK;
+}
+// the head of four stages' checks: both structs given, both of this library's size
+template <class P, class L>
+static rt_status check_params_planes(const char *name, const char *p_type, const P *p, const char *pl_type, const L *pl)
+{
+    if (!p || !pl) return fail(RT_ERR_ARG, "%s: params or planes is NULL", name);
+    rt_status st = check_struct(name, p_type, p->struct_size, sizeof *p);
+    return st ? st : check_struct(name, pl_type, pl->struct_size, sizeof *pl);
+}
+
+#define RT_IMAGE_MAX_PIXELS (1ll << 30)         /* 48 GiB of denoiser scratch; keeps the one-dimensional grid of 32 x 8 tiles far below 2^31 */
+static rt_status check_image_dims(const char *name, int32_t w, int32_t h)
+{
+    return w <= 0 || h <= 0 ? fail(RT_ERR_ARG, "%s: bad image size %d x %d", name, w, h) : RT_OK;
+}
+static rt_status check_image_limit(const char *name, int32_t w, int32_t h)
+{
+    return (long long)w * h > RT_IMAGE_MAX_PIXELS ? fail(RT_ERR_LIMIT, "%s: %d x %d is more than 2^30 pixels", name, w, h) : RT_OK;
+}
+// both, where nothing is checked between them
+static rt_status check_image_size(const char *name, int32_t w, int32_t h)
+{
+    rt_status st = check_image_dims(name, w, h);
+    return st ? st : check_image_limit(name, w, h);
+}
+
+static rt_status need_gfx950(const char *name, int device)
+{
+    return device_is_gfx950(device) ? RT_OK : fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
+}
+
+static bool planes_overlap(const void *a, size_t bytes_a, const void *b, size_t bytes_b)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + bytes_b && y < x + bytes_a;
+}
+
+// k_resolve's exponent is (float)(1.0 / gamma) of a DOUBLE gamma (rt_params); the stages' params carry a float.  Taking the
+// double that prints like that float to 7 digits gives 2.2 for 2.2f, hence the exponent a default render used.
+static float display_inv_gamma(float gamma)
+{
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.7g", (double)gamma);
+    return (float)(1.0 / strtod(buf, nullptr));
+}
+
+namespace {                             // (internal linkage: the dynamic symbol table does not see these)
+// What orders the calls that share one object or one device's scratch: each call makes its stream wait for the event the call
+// before it recorded, whatever stream that one ran on, and records the event behind its own work.  The owner's mutex is held.
+struct StageSync {
+    Event done; bool pending = false;
+    hipError_t create() { return done.create(hipEventDisableTiming); }
+    rt_status wait(hipStream_t st) { if (pending) HIP_TRY(hipStreamWaitEvent(st, done, 0)); return RT_OK; }
+    rt_status record(hipStream_t st) { HIP_TRY(hipEventRecord(done, st)); pending = true; return RT_OK; }
+    // the end of a call: record, and a synchronous call leaves nothing pending
+    rt_status settle(hipStream_t st, int sync)
+    {
+        rt_status rs = record(st);
+        if (rs == RT_OK && sync) { HIP_TRY(hipStreamSynchronize(st)); pending = false; }
+        return rs;
+    }
+    // on the host, before the owner's memory is overwritten or read back
+    rt_status wait_host() { if (pending) { HIP_TRY(hipEventSynchronize(done)); pending = false; } return RT_OK; }
+};
+
+// The objects of the stages that keep state between frames (rt_history, rt_exposure, rt_bloom, rt_motion_blur) start like
+// this; each adds its buffers and a release() that frees them.
+struct StageObject {
+    int device = 0; int32_t w = 0, h = 0;
+    StageSync sync;
+    std::mutex mu;
+};
+template <class T> static void stage_destroy(T *o)
+{
+    if (!o) return;
+    if (hipSetDevice(o->device) == hipSuccess) {
+        if (o->sync.pending) (void)hipEventSynchronize(o->sync.done);
+        o->release();                   // hipFree waits for the kernels that still use the buffers
+    }
+    delete o;
+}
+// after the argument checks of a create: the device, the object, its buffers (`size` ensures them), its event
+template <class T, class F> static rt_status stage_create(const char *name, int device, int32_t w, int32_t h, T **out, F size)
+{
+    rt_status st = need_gfx950(name, device);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(device));
+    T *o = new T;
+    o->device = device; o->w = w; o->h = h;
+    st = size(*o);
+    if (st == RT_OK && o->sync.create() != hipSuccess) st = fail(RT_ERR_DEVICE, "%s: hipEventCreate failed", name);
+    if (st) { stage_destroy(o); return st; }
+    *out = o;
+    return RT_OK;
+}
+
+// rt_denoise_device and rt_motion_device have no object, and the device state of rt_api.cpp belongs to a scene: their scratch
+// (a T with a release()) is held per device for the process, and every call on a device shares it under the registry's mutex.
+// Released with the last scene (rt_scene_destroy), like the per-device buffers of the scenes.
+template <class T> using PerDevice = std::vector<std::pair<int, T>>;
+template <class T> static T &device_entry(PerDevice<T> &all, int device)      // under the registry's mutex
+{
+    for (auto &d : all) if (d.first == device) return d.second;
+    all.emplace_back(device, T());
+    return all.back().second;
+}
+template <class T> static void release_devices(std::mutex &mu, PerDevice<T> &all)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto &d : all)
+        if (hipSetDevice(d.first) == hipSuccess) d.second.release();        // hipFree waits for the kernels that still use it
+    all.clear();
+}
+
+// The round trip of a host entry point: its planes in device buffers that live as long as this does.  in() uploads a plane,
+// out() makes room for one; both return a slot (-1 for a plane that is not given) and stop at the first failure, which `st`
+// keeps.  An input whose buffer the stage overwrites in place names the host plane that receives it afterwards.
+struct HostPlanes {
+    enum { MAX = 12 };
+    ScopedDevBuf buf[MAX]; void *back[MAX] = {}; size_t bytes[MAX] = {};
+    int n = 0; rt_status st = RT_OK;
+    int add(const void *src, void *dst, size_t nbytes)
+    {
+        if (st || !(src || dst)) return -1;
+        st = src ? buf[n].upload(src, nbytes) : buf[n].ensure(nbytes);
+        back[n] = dst; bytes[n] = nbytes;
+        return n++;
+    }
+    int in(const void *host, size_t nbytes, void *in_place_out = nullptr) { return host ? add(host, in_place_out, nbytes) : -1; }
+    int out(void *host, size_t nbytes) { return add(nullptr, host, nbytes); }
+    template <class T> T *dev(int slot) const { return slot < 0 ? nullptr : (T *)buf[slot].p; }
+    // ... as an output: NULL when the caller does not want that plane back
+    template <class T> T *dev_out(int slot) const { return slot < 0 || !back[slot] ? nullptr : (T *)buf[slot].p; }
+    // after the synchronous call: the wanted outputs among `slots`, in that order
+    rt_status download(std::initializer_list<int> slots)
+    {
+        for (int s : slots)
+            if (s >= 0 && back[s]) HIP_TRY(hipMemcpy(back[s], buf[s].p, bytes[s], hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
+};
+}
+
+// ---- denoising ----------------------------------------------------------------------------------------------------------
+// The denoiser's scratch: the two ping-pong colour buffers and the guide buffer in one allocation, grown on demand.  Every
+// denoise on a device uses the same scratch, so a call orders its stream behind the previous call's event.
+namespace { struct DenoiseDevice { DevBuf scratch; StageSync sync; void release() { scratch.release(); } }; }
+static std::mutex g_denoise_mu;
+static PerDevice<DenoiseDevice> g_denoise;        // under g_denoise_mu
+
+extern "C" void rt_denoise_default_params(rt_denoise_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->levels = 5; p->sigma_color = 1.0f; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
+}
+
+extern "C" void rt_denoise_var_default(rt_denoise_var *v)
+{
+    if (!v) return;
+    v->struct_size = (uint32_t)sizeof *v;
+    v->variance = nullptr; v->out_variance = nullptr; v->k_sigma = 4.0f;
+}
+
+// everything that can be refused without a device, for every entry point; `v`: the variance block of the _var ones
+static rt_status denoise_check(const char *name, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *pl,
+                               bool with_var = false, const rt_denoise_var *v = nullptr)
+{
+    rt_status st = check_params_planes(name, "rt_denoise_params", p, "rt_denoise_planes", pl);
+    if (st || (st = check_image_dims(name, w, h))) return st;
+    if (p->levels < 1 || p->levels > 8) return fail(RT_ERR_ARG, "%s: levels is %d, allowed 1..8", name, p->levels);
+    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_depth, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_color, sigma_normal, sigma_depth and gamma must be positive and finite", name);
+    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
+        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
+    if ((st = check_image_limit(name, w, h)) || !with_var) return st;
+    if (!v) return fail(RT_ERR_ARG, "%s: the variance block is NULL", name);
+    if ((st = check_struct(name, "rt_denoise_var", v->struct_size, sizeof *v))) return st;
+    if (!v->variance) return fail(RT_ERR_ARG, "%s: the variance plane is required", name);
+    if (!(v->k_sigma > 0.0f) || !std::isfinite(v->k_sigma)) return fail(RT_ERR_ARG, "%s: k_sigma must be positive and finite", name);
+    return RT_OK;
+}
+
+// v == NULL: the fixed-sigma filter; otherwise the variance-guided one (v is checked by the caller)
+static rt_status denoise_on_device(const char *name, int device, hipStream_t st, int32_t w, int32_t h, const rt_denoise_params *p,
+                                   const rt_denoise_planes *pl, int sync, const rt_denoise_var *v = nullptr)
+{
+    rt_status rs = need_gfx950(name, device);
+    if (rs) return rs;
+    HIP_TRY(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    DenoiseDevice &D = device_entry(g_denoise, device);
+    const size_t n = (size_t)w * (size_t)h;
+    // growing frees the old one, which waits for its users
+    if ((rs = D.scratch.ensure(n * (v ? RT_DENOISE_SCRATCH_PER_PIXEL_VAR : RT_DENOISE_SCRATCH_PER_PIXEL)))) return rs;
+    if (!D.sync.done) HIP_TRY(D.sync.create());
+    if ((rs = D.sync.wait(st))) return rs;
+    DenoiseRequest R = {};
+    R.width = w; R.height = h; R.levels = p->levels;
+    R.sigma_color = p->sigma_color; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth; R.inv_gamma = display_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id;
+    R.out_linear = pl->out_linear; R.out_rgb8 = pl->out_rgb8;
+    R.color[0] = (float4 *)D.scratch.p; R.color[1] = R.color[0] + n; R.guide = R.color[1] + n;
+    if (v) {
+        R.variance = v->variance; R.out_variance = v->out_variance; R.k_sigma = v->k_sigma;
+        R.var[0] = R.guide + n; R.var[1] = R.var[0] + n;
+    }
+    rtk_launch_denoise_frame(st, R);
+    HIP_TRY(hipGetLastError());
+    return D.sync.settle(st, sync);
+}
+
+// rt_denoise and rt_denoise_var_host: upload, filter, download.  The results are written in place into the uploaded planes
+static rt_status denoise_host(const char *name, int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *pl,
+                              bool with_var, const rt_denoise_var *v)
+{
+    rt_status st = denoise_check(name, w, h, p, pl, with_var, v);
+    if (st || (st = need_gfx950(name, device))) return st;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)w * (size_t)h;
+    HostPlanes S;
+    const int rgb = S.in(pl->rgb_linear, n * 12, pl->out_linear), normal = S.in(pl->normal, n * 12), albedo = S.in(pl->albedo, n * 12), z = S.in(pl->z, n * 4);
+    const int var = v ? S.in(v->variance, n * 12, v->out_variance) : -1;
+    const int id = S.in(pl->object_id, n * 4), rgb8 = S.out(pl->out_rgb8, n * 3);
+    if (S.st) return S.st;
+    const rt_denoise_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev<float>(normal), S.dev<float>(albedo), S.dev<float>(z),
+                                   S.dev<int32_t>(id), S.dev<float>(rgb), S.dev<uint8_t>(rgb8)};
+    rt_denoise_var dv;
+    if (v) dv = {(uint32_t)sizeof dv, S.dev<float>(var), S.dev_out<float>(var), v->k_sigma};
+    if ((st = denoise_on_device(name, device, nullptr, w, h, p, &dev, 1, v ? &dv : nullptr))) return st;
+    return S.download({rgb, rgb8, var});
+}
+
+extern "C" rt_status rt_denoise_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                                       const rt_denoise_planes *device_planes, int sync)
+{
+    rt_status st = denoise_check("rt_denoise_device", w, h, p, device_planes);
+    return st ? st : denoise_on_device("rt_denoise_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_denoise(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes)
+{
+    return denoise_host("rt_denoise", device, w, h, p, host_planes, false, nullptr);
+}
+
+extern "C" rt_status rt_denoise_var_device(int device, void *hip_stream, int32_t w, int32_t h, const rt_denoise_params *p,
+                                           const rt_denoise_planes *device_planes, const rt_denoise_var *v, int sync)
+{
+    rt_status st = denoise_check("rt_denoise_var_device", w, h, p, device_planes, true, v);
+    return st ? st : denoise_on_device("rt_denoise_var_device", device, (hipStream_t)hip_stream, w, h, p, device_planes, sync, v);
+}
+
+extern "C" rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise_params *p, const rt_denoise_planes *host_planes,
+                                         const rt_denoise_var *v)
+{
+    return denoise_host("rt_denoise_var_host", device, w, h, p, host_planes, true, v);
+}
+
+// ---- temporal accumulation ----------------------------------------------------------------------------------------------
+// An rt_history owns what one stream of frames needs on its device: the two ping-pong sets in one allocation, the camera of the
+// frame the current set holds, and the event that orders a call behind the previous one on the same history.
+struct rt_history : StageObject {
+    DevBuf sets;                        // RT_TEMPORAL_HISTORY_PER_PIXEL bytes a pixel: set 0, set 1
+    int cur = 0;                        // the set the last frame wrote
+    int32_t frames = 0;                 // since create / reset; 0: the next frame reads no history
+    DevCamera cam = {};                 // of the frame in set `cur`
+    DevBuf clip_out;                    // rt_temporal_clip_device with out_linear over rgb_linear: 12 bytes a pixel, made on first use
+    void release() { sets.release(); clip_out.release(); }
+};
+
+extern "C" rt_status rt_history_create(int device, int32_t w, int32_t h, rt_history **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_history_create: out is NULL");
+    *out = nullptr;
+    rt_status st = check_image_size("rt_history_create", w, h);
+    if (st) return st;
+    return stage_create("rt_history_create", device, w, h, out,
+                        [](rt_history &hst) { return hst.sets.ensure((size_t)hst.w * (size_t)hst.h * RT_TEMPORAL_HISTORY_PER_PIXEL); });
+}
+
+extern "C" rt_status rt_history_reset(rt_history *hst)
+{
+    if (!hst) return fail(RT_ERR_ARG, "rt_history_reset: history is NULL");
+    std::lock_guard<std::mutex> lk(hst->mu);
+    hst->frames = 0;                    // the next frame reads no tap; it still waits for the event before it writes a set
+    return RT_OK;
+}
+
+extern "C" void rt_history_destroy(rt_history *hst) { stage_destroy(hst); }
+
+extern "C" int32_t rt_history_frames(const rt_history *hst) { return hst ? hst->frames : 0; }
+
+extern "C" void rt_temporal_default_params(rt_temporal_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->alpha = 0.2f; p->max_history = 32; p->sigma_normal = 0.3f; p->sigma_depth = 0.05f; p->gamma = 2.2f;
+}
+
+// everything that can be refused without a device, for every entry point; the history comes last, so that a caller without a
+// device (which has no history) is told about its other arguments too
+static rt_status temporal_check(const char *name, const rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl)
+{
+    if (!cam || !p || !pl) return fail(RT_ERR_ARG, "%s: camera, params or planes is NULL", name);
+    rt_status st = check_struct(name, "rt_temporal_params", p->struct_size, sizeof *p);
+    if (st || (st = check_struct(name, "rt_temporal_planes", pl->struct_size, sizeof *pl))) return st;
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(RT_ERR_ARG, "%s: alpha must be in (0, 1]", name);
+    if (p->max_history < 1 || p->max_history > 65535) return fail(RT_ERR_ARG, "%s: max_history is %d, allowed 1..65535", name, p->max_history);
+    for (float s : {p->sigma_normal, p->sigma_depth, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: sigma_normal, sigma_depth and gamma must be positive and finite", name);
+    if (!pl->rgb_linear || !pl->normal || !pl->albedo || !pl->z || !pl->out_linear)
+        return fail(RT_ERR_ARG, "%s: rgb_linear, normal, albedo, z and out_linear are required", name);
+    if (pl->out_variance && !pl->variance) return fail(RT_ERR_ARG, "%s: out_variance needs the variance plane", name);
+    if (!hst) return fail(RT_ERR_ARG, "%s: history is NULL", name);
+    if (cam->width != hst->w || cam->height != hst->h)
+        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the history %d x %d", name, cam->width, cam->height, hst->w, hst->h);
+    return RT_OK;
+}
+
+extern "C" void rt_temporal_clip_default(rt_temporal_clip *c)
+{
+    if (!c) return;
+    c->struct_size = (uint32_t)sizeof *c;
+    c->radius = 2; c->k_clip = 1.5f; c->min_count = 4; c->clip_history = 2; c->out_clipped = nullptr;
+}
+
+// what rt_temporal_clip_* check before temporal_check, without a device
+static rt_status temporal_clip_check(const char *name, const rt_temporal_clip *c)
+{
+    if (!c) return fail(RT_ERR_ARG, "%s: the rt_temporal_clip is NULL", name);
+    rt_status st = check_struct(name, "rt_temporal_clip", c->struct_size, sizeof *c);
+    if (st) return st;
+    if (c->radius < 1 || c->radius > 3) return fail(RT_ERR_ARG, "%s: radius is %d, allowed 1..3", name, c->radius);
+    if (!(c->k_clip > 0.0f) || !std::isfinite(c->k_clip)) return fail(RT_ERR_ARG, "%s: k_clip must be positive and finite", name);
+    if (c->min_count < 1) return fail(RT_ERR_ARG, "%s: min_count is %d, allowed >= 1", name, c->min_count);
+    if (c->clip_history < 1 || c->clip_history > 65535) return fail(RT_ERR_ARG, "%s: clip_history is %d, allowed 1..65535", name, c->clip_history);
+    return RT_OK;
+}
+
+// motion: NULL (reproject with the two cameras), or the device plane of rt_motion_device for this frame.  clip: NULL (k_temporal),
+// or the validated rectification (k_temporal_clip), its out_clipped a device plane
+static rt_status temporal_on_device(rt_history *hst, hipStream_t st, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl, int sync,
+                                    const float *motion = nullptr, const rt_temporal_clip *clip = nullptr)
+{
+    HIP_TRY(hipSetDevice(hst->device));
+    std::lock_guard<std::mutex> lk(hst->mu);
+    rt_status rs = hst->sync.wait(st);
+    if (rs) return rs;
+    const size_t n = (size_t)hst->w * (size_t)hst->h;
+    TemporalRequest R = {};
+    R.width = hst->w; R.height = hst->h; R.has_history = hst->frames > 0;
+    camera_setup(*cam, R.cur);
+    R.old = hst->cam;
+    R.alpha = p->alpha; R.max_history = p->max_history; R.sigma_normal = p->sigma_normal; R.sigma_depth = p->sigma_depth;
+    R.inv_gamma = display_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.normal = pl->normal; R.albedo = pl->albedo; R.z = pl->z; R.object_id = pl->object_id; R.variance = pl->variance;
+    R.out_linear = pl->out_linear; R.out_variance = pl->out_variance; R.out_history = pl->out_history; R.out_rgb8 = pl->out_rgb8;
+    float4 *set0 = (float4 *)hst->sets.p;
+    const int next = hst->cur ^ 1;
+    R.prev = set0 + (size_t)hst->cur * 3 * n; R.next = set0 + (size_t)next * 3 * n;
+    R.motion = motion;
+    if (clip) {
+        // k_temporal_clip's workgroups read their neighbours' pixels of rgb_linear: where out_linear overlaps it, the kernel writes
+        // a plane of the history's and the result is copied behind it on the same stream
+        const bool overlap = planes_overlap(pl->rgb_linear, n * 12, pl->out_linear, n * 12);
+        if (overlap) {
+            if ((rs = hst->clip_out.ensure(n * 12))) return rs;
+            R.out_linear = (float *)hst->clip_out.p;
+        }
+        TemporalClipRequest CR = {};
+        CR.frame = R;
+        CR.radius = clip->radius; CR.min_count = clip->min_count; CR.k_clip = clip->k_clip; CR.clip_history = clip->clip_history;
+        CR.out_clipped = clip->out_clipped;
+        rtk_launch_temporal_clip(st, CR);
+        HIP_TRY(hipGetLastError());
+        if (overlap) HIP_TRY(hipMemcpyAsync(pl->out_linear, hst->clip_out.p, n * 12, hipMemcpyDeviceToDevice, st));
+    } else {
+        rtk_launch_temporal(st, R);
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rs = hst->sync.record(st))) return rs;
+    hst->cur = next; hst->cam = R.cur; hst->frames++;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); hst->sync.pending = false; }
+    return RT_OK;
+}
+
+// the host entry points: upload, accumulate, download.  motion: NULL (rt_temporal), or this frame's plane on the host.  The
+// results are written in place into the uploaded colour and variance
+static rt_status temporal_host(const char *name, rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *pl,
+                               const float *motion, const rt_temporal_clip *clip = nullptr)
+{
+    rt_status st = temporal_check(name, hst, cam, p, pl);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(hst->device));
+    const size_t n = (size_t)hst->w * (size_t)hst->h;
+    HostPlanes S;
+    const int rgb = S.in(pl->rgb_linear, n * 12, pl->out_linear), normal = S.in(pl->normal, n * 12), albedo = S.in(pl->albedo, n * 12), z = S.in(pl->z, n * 4);
+    const int id = S.in(pl->object_id, n * 4), var = S.in(pl->variance, n * 12, pl->out_variance), mv = S.in(motion, n * 12);
+    const int hist = S.out(pl->out_history, n * 4), rgb8 = S.out(pl->out_rgb8, n * 3);
+    const int mask = clip ? S.out(clip->out_clipped, n * 4) : -1;
+    if (S.st) return S.st;
+    const rt_temporal_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev<float>(normal), S.dev<float>(albedo), S.dev<float>(z),
+                                    S.dev<int32_t>(id), S.dev<float>(var), S.dev<float>(rgb),
+                                    S.dev_out<float>(var), S.dev<float>(hist), S.dev<uint8_t>(rgb8)};
+    rt_temporal_clip dev_clip;
+    if (clip) { dev_clip = *clip; dev_clip.out_clipped = S.dev<float>(mask); }
+    if ((st = temporal_on_device(hst, nullptr, cam, p, &dev, 1, S.dev<float>(mv), clip ? &dev_clip : nullptr))) return st;
+    return S.download({mask, rgb, var, hist, rgb8});
+}
+
+extern "C" rt_status rt_temporal_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                        const rt_temporal_planes *device_planes, int sync)
+{
+    rt_status st = temporal_check("rt_temporal_device", hst, cam, p, device_planes);
+    return st ? st : temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes)
+{
+    return temporal_host("rt_temporal", hst, cam, p, host_planes, nullptr);
+}
+
+extern "C" rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                               const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
+{
+    if (!motion_dev) return fail(RT_ERR_ARG, "rt_temporal_motion_device: the motion plane is NULL");
+    rt_status st = temporal_check("rt_temporal_motion_device", hst, cam, p, device_planes);
+    return st ? st : temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev);
+}
+
+extern "C" rt_status rt_temporal_motion(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_planes *host_planes,
+                                        const float *motion)
+{
+    if (!motion) return fail(RT_ERR_ARG, "rt_temporal_motion: the motion plane is NULL");
+    return temporal_host("rt_temporal_motion", hst, cam, p, host_planes, motion);
+}
+
+extern "C" rt_status rt_temporal_clip_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
+                                             const rt_temporal_clip *clip, const rt_temporal_planes *device_planes, const float *motion_dev, int sync)
+{
+    rt_status st = temporal_clip_check("rt_temporal_clip_device", clip);
+    if (st) return st;
+    if ((st = temporal_check("rt_temporal_clip_device", hst, cam, p, device_planes))) return st;
+    return temporal_on_device(hst, (hipStream_t)hip_stream, cam, p, device_planes, sync, motion_dev, clip);
+}
+
+extern "C" rt_status rt_temporal_clip_host(rt_history *hst, const rt_camera *cam, const rt_temporal_params *p, const rt_temporal_clip *clip,
+                                           const rt_temporal_planes *host_planes, const float *motion)
+{
+    rt_status st = temporal_clip_check("rt_temporal_clip_host", clip);
+    return st ? st : temporal_host("rt_temporal_clip_host", hst, cam, p, host_planes, motion, clip);
+}
+
+// ---- motion vectors ---------------------------------------------------------------------------------------------------------
+// One affine map in double, X -> r X + t (r row-major), and the two steps the node chains are made of.
+namespace {
+struct Affine64 {
+    double r[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+    // this, then M X + c (M column-major float[9], like rt_node's)
+    Affine64 then(const float *M, const double c[3]) const
+    {
+        Affine64 o;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.r[3 * i + j] = (double)M[i] * r[j] + (double)M[3 + i] * r[3 + j] + (double)M[6 + i] * r[6 + j];
+            o.t[i] = (double)M[i] * t[0] + (double)M[3 + i] * t[1] + (double)M[6 + i] * t[2] + c[i];
+        }
+        return o;
+    }
+    // this, then A
+    Affine64 then(const Affine64 &A) const
+    {
+        Affine64 o;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.r[3 * i + j] = A.r[3 * i] * r[j] + A.r[3 * i + 1] * r[3 + j] + A.r[3 * i + 2] * r[6 + j];
+            o.t[i] = A.r[3 * i] * t[0] + A.r[3 * i + 1] * t[1] + A.r[3 * i + 2] * t[2] + A.t[i];
+        }
+        return o;
+    }
+};
+}
+
+// The table of rt_motion: per node i the map A_i of this frame's world into the previous frame's -- TransformTo down the chain
+// root .. i of `nodes` (per node itm (X - pos)), then TransformFrom up the chain i .. root of `prev` (per node tm X + pos) --
+// composed in double and rounded to float once.  A node whose chain is bit-identical in both arrays (and every node when prev
+// is NULL) gets exactly the identity.  The parents were validated by the caller.
+static void motion_table(const rt_node *nodes, const rt_node *prev, int32_t n, std::vector<DevNodeMotion> &table)
+{
+    table.resize((size_t)n);
+    std::vector<Affine64> to, from;     // world -> node i down the current chain; node i -> world up the previous chain
+    std::vector<char> same((size_t)n, 1);
+    if (prev) { to.resize((size_t)n); from.resize((size_t)n); }
+    for (int32_t i = 0; i < n; i++) {
+        Affine64 A;
+        if (prev) {
+            const rt_node &c = nodes[i], &o = prev[i];
+            same[i] = c.parent == o.parent && !memcmp(c.tm, o.tm, 36) && !memcmp(c.itm, o.itm, 36) && !memcmp(c.pos, o.pos, 12) &&
+                      (c.parent < 0 || same[c.parent]);
+            double mp[3];               // itm (X - pos) = itm X - itm pos
+            for (int k = 0; k < 3; k++) mp[k] = -((double)c.itm[k] * c.pos[0] + (double)c.itm[3 + k] * c.pos[1] + (double)c.itm[6 + k] * c.pos[2]);
+            to[i] = (c.parent < 0 ? Affine64() : to[c.parent]).then(c.itm, mp);
+            const double op[3] = {o.pos[0], o.pos[1], o.pos[2]};
+            const Affine64 up = Affine64().then(o.tm, op);
+            from[i] = o.parent < 0 ? up : up.then(from[o.parent]);
+            if (!same[i]) A = to[i].then(from[i]);
+        }
+        for (int k = 0; k < 3; k++) table[i].row[k] = make_float4((float)A.r[3 * k], (float)A.r[3 * k + 1], (float)A.r[3 * k + 2], (float)A.t[k]);
+    }
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status motion_check(const char *name, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
+                              int32_t n_nodes, const rt_motion_planes *pl)
+{
+    if (!cam || !prev_cam || !nodes || !pl) return fail(RT_ERR_ARG, "%s: camera, prev_cam, nodes or planes is NULL", name);
+    rt_status st = check_struct(name, "rt_motion_planes", pl->struct_size, sizeof *pl);
+    if (st) return st;
+    if (!pl->z || !pl->object_id || !pl->motion) return fail(RT_ERR_ARG, "%s: z, object_id and motion are required", name);
+    if (n_nodes <= 0) return fail(RT_ERR_ARG, "%s: n_nodes is %d", name, n_nodes);
+    for (const rt_node *arr : {nodes, prev_nodes})
+        for (int32_t i = 0; arr && i < n_nodes; i++)
+            if (arr[i].parent < -1 || arr[i].parent >= i)
+                return fail(RT_ERR_ARG, "%s: node %d of %s has parent %d (a parent must precede its child; -1: none)", name, i,
+                            arr == nodes ? "nodes" : "prev_nodes", arr[i].parent);
+    if ((st = check_image_dims(name, cam->width, cam->height))) return st;
+    if (cam->width != prev_cam->width || cam->height != prev_cam->height)
+        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the previous one %d x %d", name, cam->width, cam->height, prev_cam->width, prev_cam->height);
+    return check_image_limit(name, cam->width, cam->height);
+}
+
+// The node table of the last rt_motion call per device: kept between calls (a frame's table is uploaded only when it differs
+// from the one the device holds).  Every call on the device shares it, so -- like the denoiser's scratch -- every call orders its
+// stream behind the previous call's event, whatever that call's stream was and whether or not the table changes: the event
+// then stands for ALL earlier calls, and waiting for it on the host before an overwrite leaves no kernel that still reads the
+// table.
+namespace { struct MotionDevice { DevBuf table; std::vector<DevNodeMotion> held; StageSync sync; void release() { table.release(); } }; }
+static std::mutex g_motion_mu;
+static PerDevice<MotionDevice> g_motion;          // under g_motion_mu
+
+void post_release_all()
+{
+    release_devices(g_denoise_mu, g_denoise);
+    release_devices(g_motion_mu, g_motion);
+}
+
+static rt_status motion_on_device(const char *name, int device, hipStream_t st, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
+                                  const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *pl, int sync)
+{
+    rt_status rs = need_gfx950(name, device);
+    if (rs) return rs;
+    HIP_TRY(hipSetDevice(device));
+    std::vector<DevNodeMotion> table;
+    motion_table(nodes, prev_nodes, n_nodes, table);
+    std::lock_guard<std::mutex> lk(g_motion_mu);
+    MotionDevice &D = device_entry(g_motion, device);
+    if (!D.sync.done) HIP_TRY(D.sync.create());
+    const size_t bytes = table.size() * sizeof(DevNodeMotion);
+    if ((rs = D.sync.wait(st))) return rs;
+    if (D.held.size() != table.size() || memcmp(D.held.data(), table.data(), bytes) != 0) {
+        if ((rs = D.sync.wait_host())) return rs;
+        D.held.clear();
+        if ((rs = D.table.upload(table.data(), bytes))) return rs;
+        D.held = table;
+    }
+    MotionRequest R = {};
+    R.width = cam->width; R.height = cam->height; R.n_nodes = n_nodes;
+    camera_setup(*cam, R.cur);
+    camera_setup(*prev_cam, R.old);
+    R.z = pl->z; R.object_id = pl->object_id; R.table = (const DevNodeMotion *)D.table.p; R.motion = pl->motion;
+    rtk_launch_motion(st, R);
+    HIP_TRY(hipGetLastError());
+    return D.sync.settle(st, sync);
+}
+
+extern "C" rt_status rt_motion_device(int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
+                                      const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *device_planes, int sync)
+{
+    rt_status st = motion_check("rt_motion_device", cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes);
+    return st ? st : motion_on_device("rt_motion_device", device, (hipStream_t)hip_stream, cam, prev_cam, nodes, prev_nodes, n_nodes, device_planes, sync);
+}
+
+extern "C" rt_status rt_motion(int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes, const rt_node *prev_nodes,
+                               int32_t n_nodes, const rt_motion_planes *host_planes)
+{
+    rt_status st = motion_check("rt_motion", cam, prev_cam, nodes, prev_nodes, n_nodes, host_planes);
+    if (st || (st = need_gfx950("rt_motion", device))) return st;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)cam->width * (size_t)cam->height;
+    HostPlanes S;
+    const int z = S.in(host_planes->z, n * 4), id = S.in(host_planes->object_id, n * 4), mv = S.out(host_planes->motion, n * 12);
+    if (S.st) return S.st;
+    const rt_motion_planes dev = {(uint32_t)sizeof dev, S.dev<float>(z), S.dev<int32_t>(id), S.dev<float>(mv)};
+    if ((st = motion_on_device("rt_motion", device, nullptr, cam, prev_cam, nodes, prev_nodes, n_nodes, &dev, 1))) return st;
+    return S.download({mv});
+}
+
+// ---- exposure and tone mapping --------------------------------------------------------------------------------------------
+// An rt_exposure owns the device block of one stream of frames (ToneMapRequest::State) and the event that orders a call behind
+// the previous one on the same state.  The host keeps no copy of what the meter computes: the getters read the block back.
+struct rt_exposure : StageObject {      // (not tied to an image size: w and h stay 0)
+    DevBuf block;                       // one ToneMapRequest::State
+    void release() { block.release(); }
+};
+
+// the block back to all zero (an empty working histogram, no metered frame), behind the calls issued so far
+static rt_status exposure_clear(rt_exposure *e)
+{
+    rt_status rs = e->sync.wait(nullptr);
+    if (rs) return rs;
+    HIP_TRY(hipMemsetAsync(e->block.p, 0, sizeof(ToneMapRequest::State), nullptr));
+    return e->sync.record(nullptr);
+}
+
+extern "C" rt_status rt_exposure_create(int device, rt_exposure **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_exposure_create: out is NULL");
+    *out = nullptr;
+    rt_status st = stage_create("rt_exposure_create", device, 0, 0, out, [](rt_exposure &e) { return e.block.ensure(sizeof(ToneMapRequest::State)); });
+    if (st == RT_OK && (st = exposure_clear(*out))) { stage_destroy(*out); *out = nullptr; }
+    return st;
+}
+
+extern "C" rt_status rt_exposure_reset(rt_exposure *e)
+{
+    if (!e) return fail(RT_ERR_ARG, "rt_exposure_reset: state is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> lk(e->mu);
+    return exposure_clear(e);
+}
+
+extern "C" void rt_exposure_destroy(rt_exposure *e) { stage_destroy(e); }
+
+// waits for the calls issued on the state and copies its block to the host
+static rt_status exposure_read(const char *name, rt_exposure *e, ToneMapRequest::State &out)
+{
+    if (!e) return fail(RT_ERR_ARG, "%s: state is NULL", name);
+    HIP_TRY(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> lk(e->mu);
+    rt_status rs = e->sync.wait_host();
+    if (rs) return rs;
+    HIP_TRY(hipMemcpy(&out, e->block.p, sizeof out, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_get(rt_exposure *e, float *log2_exposure, double *log2_metered, uint32_t *metered_pixels)
+{
+    ToneMapRequest::State s;
+    rt_status st = exposure_read("rt_exposure_get", e, s);
+    if (st) return st;
+    if (log2_exposure) *log2_exposure = s.E;
+    if (log2_metered) *log2_metered = s.lbar;
+    if (metered_pixels) *metered_pixels = s.n;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_exposure_histogram(rt_exposure *e, uint32_t out[256])
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_exposure_histogram: out is NULL");
+    ToneMapRequest::State s;
+    rt_status st = exposure_read("rt_exposure_histogram", e, s);
+    if (st) return st;
+    memcpy(out, s.last, sizeof s.last);
+    return RT_OK;
+}
+
+extern "C" void rt_tonemap_default_params(rt_tonemap_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->op = RT_TONEMAP_ACES; p->auto_exposure = 1;
+    p->key = 0.18f; p->ev_bias = 0.0f; p->ev_min = -16.0f; p->ev_max = 16.0f; p->p_low = 0.10f; p->p_high = 0.90f;
+    p->adapt_up = 1.0f; p->adapt_down = 1.0f; p->white = 4.0f; p->gamma = 2.2f;
+}
+
+// everything that can be refused before a launch, for both entry points: the device is looked for last
+static rt_status tonemap_check(const char *name, const rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *pl)
+{
+    rt_status st = check_params_planes(name, "rt_tonemap_params", p, "rt_tonemap_planes", pl);
+    if (st || (st = check_image_dims(name, w, h))) return st;
+    if (p->op != RT_TONEMAP_CLAMP && p->op != RT_TONEMAP_REINHARD && p->op != RT_TONEMAP_ACES) return fail(RT_ERR_ARG, "%s: no operator %d", name, p->op);
+    for (float s : {p->key, p->white, p->gamma})
+        if (!(s > 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: key, white and gamma must be positive and finite", name);
+    if (!std::isfinite(p->ev_bias) || !std::isfinite(p->ev_min) || !std::isfinite(p->ev_max) || !(p->ev_min <= p->ev_max))
+        return fail(RT_ERR_ARG, "%s: ev_bias, ev_min and ev_max must be finite and ev_min <= ev_max", name);
+    if (!(p->p_low >= 0.0f && p->p_low < p->p_high && p->p_high <= 1.0f)) return fail(RT_ERR_ARG, "%s: the percentiles must be 0 <= p_low < p_high <= 1", name);
+    for (float a : {p->adapt_up, p->adapt_down})
+        if (!(a > 0.0f && a <= 1.0f)) return fail(RT_ERR_ARG, "%s: adapt_up and adapt_down must be in (0, 1]", name);
+    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
+    if (!pl->out_display && !pl->out_rgb8) return fail(RT_ERR_ARG, "%s: one of out_display and out_rgb8 is required", name);
+    if (p->auto_exposure && !e) return fail(RT_ERR_ARG, "%s: auto-exposure needs an rt_exposure", name);
+    if (e && e->device != device) return fail(RT_ERR_ARG, "%s: the state is on device %d, the call names %d", name, e->device, device);
+    if ((st = check_image_limit(name, w, h))) return st;
+    return need_gfx950(name, device);
+}
+
+static rt_status tonemap_on_device(rt_exposure *e, int device, hipStream_t st, int32_t w, int32_t h, const rt_tonemap_params *p,
+                                   const rt_tonemap_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(device));
+    ToneMapRequest R = {};
+    R.width = w; R.height = h; R.op = p->op; R.meter = p->auto_exposure != 0;
+    R.log2_key = log2((double)p->key);
+    R.ev_bias = p->ev_bias; R.ev_min = p->ev_min; R.ev_max = p->ev_max; R.p_low = p->p_low; R.p_high = p->p_high;
+    R.adapt_up = p->adapt_up; R.adapt_down = p->adapt_down;
+    R.scale = (float)exp2((double)p->ev_bias);
+    R.white2 = (float)((double)p->white * (double)p->white);
+    R.inv_gamma = display_inv_gamma(p->gamma);
+    R.rgb_linear = pl->rgb_linear; R.object_id = pl->object_id; R.out_display = pl->out_display; R.out_rgb8 = pl->out_rgb8;
+    if (!R.meter) {                     // fixed exposure: nothing of the state is read or written, nothing to order
+        rtk_launch_tonemap(st, R);
+        HIP_TRY(hipGetLastError());
+        if (sync) HIP_TRY(hipStreamSynchronize(st));
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    rt_status rs = e->sync.wait(st);
+    if (rs) return rs;
+    R.state = (ToneMapRequest::State *)e->block.p;
+    rtk_launch_tonemap(st, R);
+    HIP_TRY(hipGetLastError());
+    return e->sync.settle(st, sync);
+}
+
+extern "C" rt_status rt_tonemap_device(rt_exposure *e, int device, void *hip_stream, int32_t w, int32_t h, const rt_tonemap_params *p,
+                                       const rt_tonemap_planes *device_planes, int sync)
+{
+    rt_status st = tonemap_check("rt_tonemap_device", e, device, w, h, p, device_planes);
+    return st ? st : tonemap_on_device(e, device, (hipStream_t)hip_stream, w, h, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_tonemap(rt_exposure *e, int device, int32_t w, int32_t h, const rt_tonemap_params *p, const rt_tonemap_planes *host_planes)
+{
+    rt_status st = tonemap_check("rt_tonemap", e, device, w, h, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)w * (size_t)h;
+    HostPlanes S;                                                   // the display plane is written in place into the uploaded colour
+    const int rgb = S.in(host_planes->rgb_linear, n * 12, host_planes->out_display), id = S.in(host_planes->object_id, n * 4);
+    const int rgb8 = S.out(host_planes->out_rgb8, n * 3);
+    if (S.st) return S.st;
+    const rt_tonemap_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev<int32_t>(id), S.dev_out<float>(rgb), S.dev<uint8_t>(rgb8)};
+    if ((st = tonemap_on_device(e, device, nullptr, w, h, p, &dev, 1))) return st;
+    return S.download({rgb, rgb8});
+}
+
+// ---- bloom ------------------------------------------------------------------------------------------------------------------
+// An rt_bloom owns the pyramid of one W x H stream of frames on its device -- every level the size allows, whatever `levels` a
+// call asks for -- and the event that orders a call behind the previous one on the same object.
+struct rt_bloom : StageObject { DevBuf pyramid; void release() { pyramid.release(); } };
+
+extern "C" rt_status rt_bloom_create(int device, int32_t w, int32_t h, rt_bloom **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_bloom_create: out is NULL");
+    *out = nullptr;
+    rt_status st = check_image_size("rt_bloom_create", w, h);
+    if (st) return st;
+    return stage_create("rt_bloom_create", device, w, h, out, [](rt_bloom &b) {
+        const BloomPlan all = rtk_bloom_plan(b.w, b.h, RT_BLOOM_MAX_LEVELS);
+        return b.pyramid.ensure(all.off[all.levels] * 12);
+    });
+}
+
+extern "C" void rt_bloom_destroy(rt_bloom *b) { stage_destroy(b); }
+
+extern "C" void rt_bloom_default_params(rt_bloom_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->threshold = 1.0f; p->knee = 0.5f; p->intensity = 0.25f; p->spread = 0.7f; p->levels = 6; p->exposure_ev = 0.0f;
+}
+
+extern "C" rt_status rt_bloom_plan(int32_t w, int32_t h, int32_t levels, int32_t *levels_used, int32_t *tail_level)
+{
+    rt_status st = check_image_dims("rt_bloom_plan", w, h);
+    if (st) return st;
+    if (levels < 1) return fail(RT_ERR_ARG, "rt_bloom_plan: levels is %d, must be at least 1", levels);
+    const BloomPlan P = rtk_bloom_plan(w, h, levels);
+    if (levels_used) *levels_used = P.levels;
+    if (tail_level) *tail_level = P.tail;
+    return RT_OK;
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status bloom_check(const char *name, const rt_bloom *b, const rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *pl)
+{
+    rt_status st = check_params_planes(name, "rt_bloom_params", p, "rt_bloom_planes", pl);
+    if (st) return st;
+    for (float s : {p->threshold, p->knee, p->intensity, p->spread})
+        if (!(s >= 0.0f) || !std::isfinite(s)) return fail(RT_ERR_ARG, "%s: threshold, knee, intensity and spread must be finite and not negative", name);
+    if (p->spread > 1.0f || p->knee > 1.0f) return fail(RT_ERR_ARG, "%s: spread and knee must be at most 1", name);
+    if (p->levels < 1) return fail(RT_ERR_ARG, "%s: levels is %d, must be at least 1", name, p->levels);
+    if (!std::isfinite(p->exposure_ev)) return fail(RT_ERR_ARG, "%s: exposure_ev must be finite", name);
+    if (!pl->rgb_linear) return fail(RT_ERR_ARG, "%s: rgb_linear is required", name);
+    if (!pl->out && !pl->out_bloom) return fail(RT_ERR_ARG, "%s: one of out and out_bloom is required", name);
+    // what needs the object comes last: without a device there is none, and everything above is still refused by name
+    if (!b) return fail(RT_ERR_ARG, "%s: the rt_bloom is NULL", name);
+    if (e && e->device != b->device) return fail(RT_ERR_ARG, "%s: the exposure state is on device %d, the rt_bloom on %d", name, e->device, b->device);
+    const size_t bytes = (size_t)b->w * (size_t)b->h * 12;
+    if ((pl->out != pl->rgb_linear && planes_overlap(pl->out, bytes, pl->rgb_linear, bytes)) || planes_overlap(pl->out_bloom, bytes, pl->rgb_linear, bytes) ||
+        planes_overlap(pl->out_bloom, bytes, pl->out, bytes))
+        return fail(RT_ERR_ARG, "%s: planes overlap (only out == rgb_linear is allowed)", name);
+    return RT_OK;
+}
+
+static rt_status bloom_on_device(rt_bloom *b, rt_exposure *e, hipStream_t st, const rt_bloom_params *p, const rt_bloom_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    BloomRequest R = {};
+    R.width = b->w; R.height = b->h;
+    R.threshold = p->threshold; R.knee_k = p->knee * p->threshold; R.intensity = p->intensity;
+    R.spread = p->spread; R.one_minus_spread = 1.0f - p->spread;
+    R.scale = (float)exp2((double)p->exposure_ev);
+    R.rgb_linear = pl->rgb_linear; R.out = pl->out; R.out_bloom = pl->out_bloom;
+    R.plan = rtk_bloom_plan(b->w, b->h, p->levels);
+    std::lock_guard<std::mutex> lk(b->mu);          // two objects: the bloom's mutex first, then the state's
+    std::unique_lock<std::mutex> le;
+    if (e) le = std::unique_lock<std::mutex>(e->mu);
+    R.pyramid = (float *)b->pyramid.p;
+    rt_status rs = b->sync.wait(st);
+    if (rs) return rs;
+    if (e) {                            // the state is read: behind the calls that write it, and the next one of them behind this
+        if ((rs = e->sync.wait(st))) return rs;
+        R.state = (const ToneMapRequest::State *)e->block.p;
+    }
+    HIP_TRY(rtk_launch_bloom(st, R));
+    if ((rs = b->sync.record(st)) || (e && (rs = e->sync.record(st)))) return rs;
+    if (sync) { HIP_TRY(hipStreamSynchronize(st)); b->sync.pending = false; if (e) e->sync.pending = false; }
+    return RT_OK;
+}
+
+extern "C" rt_status rt_bloom_device(rt_bloom *b, rt_exposure *e, void *hip_stream, const rt_bloom_params *p,
+                                     const rt_bloom_planes *device_planes, int sync)
+{
+    rt_status st = bloom_check("rt_bloom_device", b, e, p, device_planes);
+    return st ? st : bloom_on_device(b, e, (hipStream_t)hip_stream, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_params *p, const rt_bloom_planes *host_planes)
+{
+    rt_status st = bloom_check("rt_bloom_host", b, e, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t n = (size_t)b->w * (size_t)b->h;
+    HostPlanes S;                                                   // `out` is written in place into the uploaded colour
+    const int rgb = S.in(host_planes->rgb_linear, n * 12, host_planes->out), only = S.out(host_planes->out_bloom, n * 12);
+    if (S.st) return S.st;
+    const rt_bloom_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev_out<float>(rgb), S.dev<float>(only)};
+    if ((st = bloom_on_device(b, e, nullptr, p, &dev, 1))) return st;
+    return S.download({rgb, only});
+}
+
+// ---- motion blur ------------------------------------------------------------------------------------------------------------
+// An rt_motion_blur owns the tile-max and neighbour-max planes of one W x H stream of frames on its device -- sized for K = 2,
+// the most tiles a call can ask for -- and the event that orders a call behind the previous one on the same object.
+#define RT_MBLUR_MIN_K 2
+#define RT_MBLUR_MAX_K 32
+struct rt_motion_blur : StageObject { DevBuf tile_max, tile_nmax; void release() { tile_max.release(); tile_nmax.release(); } };
+
+static size_t mblur_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
+{
+    const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
+    if (tx) *tx = x;
+    if (ty) *ty = y;
+    return (size_t)x * (size_t)y;
+}
+
+extern "C" rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_motion_blur **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_motion_blur_create: out is NULL");
+    *out = nullptr;
+    rt_status st = check_image_size("rt_motion_blur_create", w, h);
+    if (st) return st;
+    return stage_create("rt_motion_blur_create", device, w, h, out, [](rt_motion_blur &mb) {
+        const size_t bytes = mblur_tiles(mb.w, mb.h, RT_MBLUR_MIN_K, nullptr, nullptr) * 8;
+        rt_status rs = mb.tile_max.ensure(bytes);
+        return rs ? rs : mb.tile_nmax.ensure(bytes);
+    });
+}
+
+extern "C" void rt_motion_blur_destroy(rt_motion_blur *mb) { stage_destroy(mb); }
+
+extern "C" void rt_motion_blur_default_params(rt_motion_blur_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->shutter = 0.5f; p->max_blur = 16; p->samples = 15; p->depth_extent = 0.05f;
+}
+
+extern "C" rt_status rt_motion_blur_tiles(int32_t w, int32_t h, int32_t max_blur, int32_t *tx, int32_t *ty)
+{
+    rt_status st = check_image_dims("rt_motion_blur_tiles", w, h);
+    if (st) return st;
+    if (max_blur < RT_MBLUR_MIN_K || max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: max_blur is %d, must be 2..32", max_blur);
+    mblur_tiles(w, h, max_blur, tx, ty);
+    return RT_OK;
+}
+
+// everything that can be refused without a device, for both entry points
+static rt_status mblur_check(const char *name, const rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl)
+{
+    rt_status st = check_params_planes(name, "rt_motion_blur_params", p, "rt_motion_blur_planes", pl);
+    if (st) return st;
+    if (!std::isfinite(p->shutter) || !(p->shutter >= 0.0f) || p->shutter > 2.0f) return fail(RT_ERR_ARG, "%s: shutter must be finite and 0..2", name);
+    if (p->max_blur < RT_MBLUR_MIN_K || p->max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "%s: max_blur is %d, must be 2..32", name, p->max_blur);
+    if (p->samples < 3 || p->samples > 63 || !(p->samples & 1)) return fail(RT_ERR_ARG, "%s: samples is %d, must be odd and 3..63", name, p->samples);
+    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
+    if (!pl->rgb_linear || !pl->motion || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, motion, z and out are required", name);
+    // what needs the object comes last: without a device there is none, and everything above is still refused by name
+    if (!mb) return fail(RT_ERR_ARG, "%s: the rt_motion_blur is NULL", name);
+    const size_t n = (size_t)mb->w * (size_t)mb->h;
+    const struct { const void *p; size_t bytes; } planes[5] = {
+        {pl->rgb_linear, n * 12}, {pl->motion, n * 12}, {pl->z, n * 4}, {pl->out, n * 12},
+        {pl->out_tiles, mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8}};
+    for (int a = 0; a < 5; a++)
+        for (int b = a + 1; b < 5; b++)
+            if (planes_overlap(planes[a].p, planes[a].bytes, planes[b].p, planes[b].bytes))
+                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
+    return RT_OK;
+}
+
+static rt_status mblur_on_device(rt_motion_blur *mb, hipStream_t st, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(mb->device));
+    MotionBlurRequest R = {};
+    R.width = mb->w; R.height = mb->h; R.K = p->max_blur; R.N = p->samples;
+    mblur_tiles(mb->w, mb->h, p->max_blur, &R.tiles_x, &R.tiles_y);
+    R.half_shutter = 0.5f * p->shutter; R.two_over_n = 2.0f / (float)p->samples; R.depth_extent = p->depth_extent;
+    R.rgb_linear = pl->rgb_linear; R.motion = pl->motion; R.z = pl->z; R.out = pl->out; R.out_tiles = pl->out_tiles;
+    std::lock_guard<std::mutex> lk(mb->mu);
+    R.tile_max = (float *)mb->tile_max.p; R.tile_nmax = (float *)mb->tile_nmax.p;
+    rt_status rs = mb->sync.wait(st);
+    if (rs) return rs;
+    HIP_TRY(rtk_launch_motion_blur(st, R));
+    return mb->sync.settle(st, sync);
+}
+
+extern "C" rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_motion_blur_params *p,
+                                           const rt_motion_blur_planes *device_planes, int sync)
+{
+    rt_status st = mblur_check("rt_motion_blur_device", mb, p, device_planes);
+    return st ? st : mblur_on_device(mb, (hipStream_t)hip_stream, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *host_planes)
+{
+    rt_status st = mblur_check("rt_motion_blur_host", mb, p, host_planes);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(mb->device));
+    const size_t n = (size_t)mb->w * (size_t)mb->h;
+    const size_t tile_bytes = mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8;
+    HostPlanes S;
+    const int rgb = S.in(host_planes->rgb_linear, n * 12), motion = S.in(host_planes->motion, n * 12), z = S.in(host_planes->z, n * 4);
+    const int out = S.out(host_planes->out, n * 12), tiles = S.out(host_planes->out_tiles, tile_bytes);
+    if (S.st) return S.st;
+    const rt_motion_blur_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev<float>(motion), S.dev<float>(z),
+                                       S.dev<float>(out), S.dev<float>(tiles)};
+    if ((st = mblur_on_device(mb, nullptr, p, &dev, 1))) return st;
+    return S.download({out, tiles});
+}

@@ -402,3 +402,85 @@ def test_reference_side_binding_compiles_against_the_reference_headers():
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "binding-check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "syntax OK" in r.stdout
+
+
+def _struct_size_cases():
+    """(entry point, struct name, key of the struct to spoil, call): every pair of an image-space entry point and a versioned
+    struct it takes.  `call(L, S)` passes the structs of S with NULL objects and dummy planes; everything before the struct_size
+    checks is valid, so each of them is reached."""
+    ref = C.byref
+    stages = {
+        "denoise": [(e, lambda L, S, e=e, t=t: getattr(L, e)(0, *t, 8, 8, ref(S["params"]), ref(S["planes"]), *([ref(S["var"])] if "var" in e else []),
+                                                               *([1] if t else [])))
+                    for e, t in (("rt_denoise", ()), ("rt_denoise_device", (None,)), ("rt_denoise_var_host", ()), ("rt_denoise_var_device", (None,)))],
+        "temporal": [(e, lambda L, S, e=e, t=t: getattr(L, e)(None, *t, ref(S["cam"]), ref(S["params"]), *([ref(S["clip"])] if "clip" in e else []),
+                                                                ref(S["planes"]), *([S["addr"]] if "clip" in e or "motion" in e else []), *([1] if t else [])))
+                     for e, t in (("rt_temporal", ()), ("rt_temporal_device", (None,)), ("rt_temporal_motion", ()), ("rt_temporal_motion_device", (None,)),
+                                  ("rt_temporal_clip_host", ()), ("rt_temporal_clip_device", (None,)))],
+        "motion": [(e, lambda L, S, e=e, t=t: getattr(L, e)(0, *t, ref(S["cam"]), ref(S["cam"]), S["nodes"].ctypes.data, None, 1, ref(S["planes"]),
+                                                              *([1] if t else [])))
+                   for e, t in (("rt_motion", ()), ("rt_motion_device", (None,)))],
+        "tonemap": [(e, lambda L, S, e=e, t=t: getattr(L, e)(None, 0, *t, 8, 8, ref(S["params"]), ref(S["planes"]), *([1] if t else [])))
+                    for e, t in (("rt_tonemap", ()), ("rt_tonemap_device", (None,)))],
+        "bloom": [(e, lambda L, S, e=e, t=t: getattr(L, e)(None, None, *t, ref(S["params"]), ref(S["planes"]), *([1] if t else [])))
+                  for e, t in (("rt_bloom_host", ()), ("rt_bloom_device", (None,)))],
+        "motion_blur": [(e, lambda L, S, e=e, t=t: getattr(L, e)(None, *t, ref(S["params"]), ref(S["planes"]), *([1] if t else [])))
+                        for e, t in (("rt_motion_blur_host", ()), ("rt_motion_blur_device", (None,)))],
+    }
+    names = {"denoise": {"params": "rt_denoise_params", "planes": "rt_denoise_planes", "var": "rt_denoise_var"},
+             "temporal": {"params": "rt_temporal_params", "planes": "rt_temporal_planes", "clip": "rt_temporal_clip"},
+             "motion": {"planes": "rt_motion_planes"},
+             "tonemap": {"params": "rt_tonemap_params", "planes": "rt_tonemap_planes"},
+             "bloom": {"params": "rt_bloom_params", "planes": "rt_bloom_planes"},
+             "motion_blur": {"params": "rt_motion_blur_params", "planes": "rt_motion_blur_planes"}}
+    cases = []
+    for stage, entries in stages.items():
+        for entry, call in entries:
+            for key, struct in names[stage].items():
+                if key in ("var", "clip") and key not in entry:
+                    continue
+                cases.append(pytest.param(stage, entry, struct, key, call, id=f"{entry}-{struct}"))
+    return cases
+
+
+def _stage_structs(stage, buf):
+    """valid structs for `stage`, every plane pointing into the host array `buf` (never read: the calls are refused first)"""
+    a = buf.ctypes.data
+    S = {"addr": a, "cam": capi.Camera(width=8, height=8), "nodes": np.zeros(1, capi.NODE)}
+    S["nodes"]["parent"] = -1
+    if stage == "denoise":
+        S["params"] = capi.denoise_params()
+        S["planes"] = capi.DenoisePlanes(rgb_linear=a, normal=a, albedo=a, z=a, out_linear=a)
+        S["var"] = capi.denoise_var(a)
+    elif stage == "temporal":
+        S["params"] = capi.temporal_params()
+        S["planes"] = capi.TemporalPlanes(rgb_linear=a, normal=a, albedo=a, z=a, out_linear=a)
+        S["clip"] = capi.temporal_clip()
+    elif stage == "motion":
+        S["planes"] = capi.MotionPlanes(z=a, object_id=a, motion=a)
+    elif stage == "tonemap":
+        S["params"] = capi.tonemap_params(auto_exposure=0)
+        S["planes"] = capi.ToneMapPlanes(rgb_linear=a, out_rgb8=a)
+    elif stage == "bloom":
+        S["params"] = capi.bloom_params()
+        S["planes"] = capi.BloomPlanes(rgb_linear=a, out=a)
+    else:
+        S["params"] = capi.motion_blur_params()
+        S["planes"] = capi.MotionBlurPlanes(rgb_linear=a, motion=a, z=a, out=a)
+    return S
+
+
+@pytest.mark.parametrize("stage, entry, struct, key, call", _struct_size_cases())
+def test_struct_size_mismatch_is_refused_by_name(stage, entry, struct, key, call):
+    """Every image-space entry point, host and device, refuses each of its versioned structs whose struct_size is off by 4 with
+    RT_ERR_ARG and exactly "<entry>: <struct>.struct_size is <given>, this library's is <sizeof>" -- before it looks at an
+    object or a device (the objects are NULL here)."""
+    L = capi.lib()
+    buf = np.zeros(8 * 8 * 3, np.float32)
+    for off in (4, -4):
+        S = _stage_structs(stage, buf)
+        size = C.sizeof(type(S[key]))
+        assert S[key].struct_size == size                       # what the library's own default wrote / the binding's mirror
+        S[key].struct_size = size + off
+        assert call(L, S) == -1
+        assert L.rt_last_error() == f"{entry}: {struct}.struct_size is {size + off}, this library's is {size}".encode()
