@@ -1,4 +1,4 @@
-// rt_dev.h -- device-side data layout of a lowered scene, shared by rt_api.cpp (which builds
+// rt_dev.h -- device-side data layout of a lowered scene, shared by rt_lower.cpp (which builds
 // and uploads it) and the kernels in rt_kernels.hip / rt_gather.hip (which read it).  gfx950 only.
 //
 // HBM layout (all arrays are plain hipMalloc allocations owned by the rt_scene):
@@ -71,7 +71,7 @@ struct DevObjectBack {
 static_assert(sizeof(DevObjectBack) == 16 + 96 * RT_BACK_LEVELS, "layout");
 
 // 128 bytes: the boxes of up to four children, one axis after the other (lox[4], loy[4], loz[4], hix[4], hiy[4], hiz[4]: six
-// 16-byte loads), and their refs.  Built on the host from the mesh's triangles (rt_api.cpp: binned surface-area heuristic,
+// 16-byte loads), and their refs.  Built on the host from the mesh's triangles (rt_lower.cpp: binned surface-area heuristic,
 // leaves of at most four triangles, collapsed four-wide by the largest child first).  An unused child has NaN bounds (never
 // entered).  One visit = ONE dependent read for two levels of a binary tree.
 struct DevBvhNode {
@@ -124,7 +124,7 @@ struct DevPhotonMap {
     // `start_radius` of ANY point of the cell -- every sibling subtree on the way down lies farther from the cell than that.
     // A query inside the grid with a radius <= start_radius starts its walk there instead of at the root (the levels above
     // are a chain of dependent box reads with one survivor each).  NULL / 0: start at the root.  Rebuilt when the gather
-    // radius grows (rt_api.cpp).
+    // radius grows (ensure_cell_start in rt_lower.cpp).
     const uint32_t *cell_start;
     float start_radius;
 };

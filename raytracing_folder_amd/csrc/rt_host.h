@@ -1,12 +1,22 @@
-// rt_host.h -- private to the two host files of the C ABI (not installed): what rt_api.cpp (scenes, renders, jobs) and
-// rt_post.cpp (the image-space stages) both need.  Everything here that has external linkage only so that the two files can
-// share it is hidden: the library's dynamic symbol table does not know it.
+// rt_host.h -- private to the host files of the C ABI (not installed): what more than one of them needs.
+//   rt_api.cpp     what needs no device state: errors, the scene store and its getters, the image and .dat wrappers
+//   rt_lower.cpp   a scene and its photon maps onto a device (prepare_device), the photon pass, generate_photons
+//   rt_render.cpp  render orchestration: working sets, run_pipeline, the render / packed / unpack entry points, jobs, the
+//                  single-stage entry points
+//   rt_post.cpp    the image-space stages (denoise .. motion blur)
+// Everything here that has external linkage only so that these files can share it is hidden: the library's dynamic symbol
+// table does not know it.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <mutex>
+#include <string>
 #include <utility>
+#include <vector>
 
 #include "../../include/rt_mi355x.h"
+#include "host/rt_scene.h"
 #include "rt_launch.h"
 
 #define RT_HIDDEN __attribute__((visibility("hidden")))
@@ -19,8 +29,8 @@ RT_HIDDEN rt_status fail(rt_status st, const char *fmt, ...);
         if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-RT_HIDDEN bool device_is_gfx950(int dev);
-RT_HIDDEN void camera_setup(const rt_camera &cam, DevCamera &dc);      // of RenderPixel (rt_api.cpp)
+RT_HIDDEN bool device_is_gfx950(int dev);                              // rt_api.cpp
+RT_HIDDEN void camera_setup(const rt_camera &cam, DevCamera &dc);      // of RenderPixel (rt_render.cpp)
 // rt_scene_destroy of the last scene: the per-device scratch of the image-space stages goes with it (rt_post.cpp)
 RT_HIDDEN void post_release_all();
 
@@ -62,3 +72,148 @@ struct RT_HIDDEN Event {
     hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }      // once per Event
     operator hipEvent_t() const { return e; }
 };
+
+// ---- a scene on one device (rt_lower.cpp fills it, rt_render.cpp renders from it) ---------------------------
+struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
+
+static const size_t SPILL_BYTES = (size_t)RT_SPILL_BLOCKS * RT_BLOCK * RT_BVH_SPILL * 4;     // DevScene::bvh_spill / DevWork::bvh_spill
+
+// Per-chunk working set.  A frame's chunks alternate between RT_STREAMS of these, each on its own HIP
+// stream, so that the short launches of one chunk (deep bounce levels with few rays, whose duration is
+// the latency of one ray's path) overlap the wide launches of the other.
+#define RT_STREAMS 4                    /* slots compiled in; render_streams() says how many are used */
+struct Workspace {
+    DevBuf sample_rgb, sample_z, sample_hit, rq[2][5], pq[3], cq[3], counts, pixel_list;
+    DevBuf bvh_spill;                   // traversal-stack entries beyond the kernels' LDS stacks (only for scenes whose BVHs can need them)
+    DevBuf sample_fx;                   // reproducible renders only: 3 x int64 fixed-point secondary colour per sample (allocated on first use)
+    DevBuf feat_second;                 // renders with feature planes only: one byte per chunk pixel, 1 = it took the second batch (k_mark_second)
+    size_t samples = 0; uint32_t rq_cap = 0, pq_cap = 0;
+    hipStream_t stream = nullptr;       // slot 0 runs on the caller's / the device's main stream instead
+    void release()
+    {
+        for (DevBuf *b : {&sample_rgb, &sample_z, &sample_hit, &counts, &pixel_list, &bvh_spill, &sample_fx, &feat_second}) b->release();
+        for (int i = 0; i < 2; i++) for (int k = 0; k < 5; k++) rq[i][k].release();
+        for (int k = 0; k < 3; k++) { pq[k].release(); cq[k].release(); }
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
+
+// the device side of one photon map; what the kernels see of it is its DevPhotonMap (DeviceState::map pairs the two)
+struct RT_HIDDEN PhotonStore {
+    DevBuf pa, pb, box4, grid;          // the gather structure (rt_photon_build.hip)
+    // per density-grid cell, the k-th squared distance of the last query k_gather answered there: predicts the next one's (a
+    // hint that only steers which of two exact paths a query takes); zeroed whenever the structure is rebuilt
+    DevBuf cell_rk2;
+    int rk2_k = 0; float rk2_radius = 0;        // the gather parameters the hint table was filled under (0: empty)
+    DevBuf cell_start;                  // DevPhotonMap::cell_start (built for the gather radius in use)
+    bool valid = false;                 // the structure is the scene's map as it is now
+    void release() { for (DevBuf *b : {&pa, &pb, &box4, &grid, &cell_rk2, &cell_start}) b->release(); }
+};
+struct PhotonMapRef { PhotonStore &store; DevPhotonMap &pm; };
+
+struct DeviceState {
+    int device = -1;
+    bool scene_valid = false;
+    DevBuf nodes, objects, objects_back, meshes, materials, lights, node_material, textures, texels, material_maps;
+    std::vector<DevMeshBufs> mesh_bufs;
+    PhotonStore maps[2];                        // [0] the photon map (scene.pm), [1] the caustic map (scene.cm)
+    DevBuf raw_photons;                         // 24-byte photons of the last photon pass on this device (1-based)
+    DevBuf bvh_spill;                           // DevScene::bvh_spill of the single-stage entry points (rt_trace_rays, the photon pass); renders use their working set's
+    DevScene scene{};
+    Workspace ws[RT_STREAMS];
+    DevBuf stats;
+    std::atomic<int> busy{0};           // a host call is using the working sets of this device
+    // an asynchronous render (sync == 0) returns while the GPU still uses the working sets, counters and
+    // stats: `last_done` is recorded at its join and every later call orders its own stream behind it
+    hipEvent_t last_done = nullptr;
+    bool last_pending = false;
+    bool last_pipelined = false;        // the render in flight ran every slot on the library's own streams (RenderAttempt::plan_chunks, fork_slots)
+    uint64_t frame_seq = 0;             // rotates the slots from one pipelined frame to the next
+    bool async_overflow = false;        // an asynchronous render dropped rays and nobody has collected that verdict yet (rt_render_check does)
+    // How full the ray / photon-query queues of the last renders got, per sample of a chunk (device-side peaks,
+    // rt_stats.peak_*): the next render of the same kind sizes its queues from that instead of the 2^bounce worst case
+    // (choose_queue_sizing / record_queue_peaks in rt_render.cpp).
+    struct QueueKey {                   // what makes two renders "of the same kind"
+        int model = -1, bounce = -1, fan = -1; bool photons = false, caustic = false;
+        bool operator==(const QueueKey &o) const { return model == o.model && bounce == o.bounce && fan == o.fan && photons == o.photons && caustic == o.caustic; }
+    };
+    struct QueueHistory { bool valid = false; QueueKey key; double rays_per_sample = 0, queries_per_sample = 0; } qhist;
+    bool qhist_used = false;            // the render in flight (or last finished) was sized from qhist / the first-frame guess
+    // scratch for the single-stage entry points
+    DevBuf t_in, t_out[6];
+    hipStream_t stream = nullptr;
+    // one of the two maps: its buffers with what the kernels see of it
+    PhotonMapRef map(bool caustic) { return {maps[caustic], caustic ? scene.cm : scene.pm}; }
+    void release()
+    {
+        for (DevBuf *b : {&nodes, &objects, &objects_back, &meshes, &materials, &lights, &node_material, &textures, &texels, &material_maps,
+                          &raw_photons, &bvh_spill, &stats, &t_in}) b->release();
+        for (PhotonStore &m : maps) m.release();
+        for (auto &m : mesh_bufs) { m.nodes.release(); m.tris.release(); m.nrm.release(); m.tex.release(); }
+        for (Workspace &w : ws) w.release();
+        for (int k = 0; k < 6; k++) t_out[k].release();
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+        if (last_done) (void)hipEventDestroy(last_done);
+        last_done = nullptr; last_pending = false;
+    }
+};
+
+// One host call at a time may use a device's working sets, scratch buffers, counters and stats: the render
+// entry points AND the single-stage ones (rt_trace_rays, rt_shade_rays, rt_estimate_irradiance, rt_photon_pass)
+// claim the device for their duration and fail with RT_ERR_STATE while another call (or a live job) holds it.
+struct DeviceClaim {
+    DeviceState *D; bool ok;
+    explicit DeviceClaim(DeviceState *d) : D(d), ok(d->busy.exchange(1) == 0) {}
+    ~DeviceClaim() { if (ok) D->busy.store(0); }
+    DeviceClaim(const DeviceClaim &) = delete;
+    DeviceClaim &operator=(const DeviceClaim &) = delete;
+};
+
+struct rt_scene {
+    rt::SceneData data;
+    // A photon map made by rt_scene_generate_photons is kept as generatePhotonMap leaves it BEFORE balancing (1-based,
+    // [0] zero) together with the indices of the few photons LocatePhotons could not reach after balancing
+    // (rt::UnreachablePhotons); data.photons (the balanced form) is produced from it only when somebody asks for it.
+    // Non-empty photons_raw takes precedence over data.photons; rt_scene_set_photons clears it.
+    std::vector<rt_photon> photons_raw;
+    std::vector<uint32_t> photons_skip;
+    // A map made by the photon pass (rt_scene_generate_photons, rt_render_begin) is DERIVED from the scene: whatever it was
+    // traced through (nodes, meshes, materials, lights, another XML) changing drops it, and rt_render_begin makes a new one when
+    // there is none or when the render asks for another count / bounce limit / seed -- the reference runs generatePhotonMap() on
+    // every BeginRender (FIN/main.cpp:984-990).  A map handed over with rt_scene_set_photons is the caller's: it stays.
+    struct Generated { bool valid = false; uint32_t count = 0; int bounce = 0; uint32_t seed = 0; } gen;
+    // ... and it STAYS on the device that generated it (DeviceState::raw_photons of gen_dev, gen_n photons) until somebody needs it
+    // on the host: the .dat dump, rt_scene_get_photons, another device, the host's replay of BalanceSegment when a median is not
+    // unique (raw_to_host in rt_lower.cpp).  gen_n != 0 with an empty photons_raw = "on gen_dev only".
+    DeviceState *gen_dev = nullptr; uint32_t gen_n = 0;
+    std::string photon_dump;            // where rt_render_begin's photon pass writes its .dat ("" = nowhere)
+    std::mutex gen_mu;                  // jobs started together on several devices: ONE of them runs the photon pass, the others wait for it
+    std::mutex mu;
+    std::vector<DeviceState *> devs;
+    std::atomic<int> live_jobs{0};
+    std::atomic<uint32_t> render_flags{0};      // RT_RENDER_*: read once at the start of every render call
+    uint32_t photon_count() const { return gen_n ? gen_n : (!photons_raw.empty() ? (uint32_t)photons_raw.size() - 1 : (data.photons.empty() ? 0u : (uint32_t)data.photons.size() - 1)); }
+    void drop_generated() { photons_raw.clear(); photons_skip.clear(); gen.valid = false; gen_dev = nullptr; gen_n = 0; }
+    void invalidate(bool scene, bool photons, bool caustic = false)
+    {
+        for (DeviceState *d : devs) { if (scene) d->scene_valid = false; if (photons) d->maps[0].valid = false; if (caustic) d->maps[1].valid = false; }
+    }
+    // geometry, materials or lights changed (caller holds mu): re-upload, and a generated photon map is no longer this scene's
+    void geometry_changed()
+    {
+        if (gen.valid) { drop_generated(); data.photons.clear(); invalidate(true, true); }
+        else invalidate(true, false);
+    }
+};
+
+// ---- what crosses the host files ----------------------------------------------------------------------------
+RT_HIDDEN rt_status check_idle(rt_scene *s, const char *who);                                   // rt_api.cpp
+// rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
+RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
+RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);
+RT_HIDDEN rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float radius, hipStream_t st, bool *did_work = nullptr);
+RT_HIDDEN rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
+                                     rt_setup_ms *ms_out, bool own_job);
+RT_HIDDEN rt_status order_after_pending(DeviceState *D, hipStream_t st);                        // rt_render.cpp

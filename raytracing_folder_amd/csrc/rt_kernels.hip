@@ -2132,7 +2132,7 @@ __attribute__((amdgpu_waves_per_eu(TEX ? 3 : 4, TEX ? 3 : 4))) __global__ __laun
 }
 
 // ------------------------------------------------------------------------------------------------
-// host-callable launch wrappers (C++ linkage, used by rt_api.cpp)
+// host-callable launch wrappers (C++ linkage, used by rt_lower.cpp and rt_render.cpp)
 // ------------------------------------------------------------------------------------------------
 static inline int grid_for(unsigned long long work, int block, int max_blocks)
 {

@@ -1,6 +1,6 @@
-// rt_launch.h -- the boundary between the host orchestration (rt_api.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
+// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip): every rtk_* function, the requests they take and the
-// records they exchange.  All ten files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
+// records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -9,7 +9,7 @@
 #include "rt_dev.h"
 
 // ---- requests ---------------------------------------------------------------------------------------------------------
-// One tracing pass over a chunk's samples (run_pipeline in rt_api.cpp; k_wavefront / k_primary and what follows them):
+// One tracing pass over a chunk's samples (run_pipeline in rt_render.cpp; k_wavefront / k_primary and what follows them):
 //   mode 0: pixels q0..q0+npix of the call's tile walk, samples j0..j0+ns of each
 //   mode 1: the pixels of the working set's pixel list, samples j0..j0+ns   (second batch)
 //   mode 2: rays[] supplied by the caller, one sample each, q0 = index of the first   (rt_shade_rays)

@@ -1,0 +1,742 @@
+// rt_lower.cpp -- what puts a scene and its photon maps on a device: the lowering of the scene store (rt_api.cpp) to the device
+// layout of rt_dev.h, the gather structures of the two photon maps, and the photon pass that generates a map on the device.
+// rt_render.cpp renders from what prepare_device leaves here; rt_host.h is what the host files share.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/rt_mi355x.h"
+#include "host/rt_scene.h"
+#include "rt_host.h"
+
+// ---- lowering to the device ---------------------------------------------------------------------------
+static DeviceState *device_state(rt_scene *s, int device)
+{
+    for (DeviceState *d : s->devs) if (d->device == device) return d;
+    DeviceState *d = new DeviceState;
+    d->device = device;
+    s->devs.push_back(d);
+    return d;
+}
+// lookup only, under s->mu: NULL when nothing was ever prepared on that device (device_state above is the creating variant,
+// for callers that hold s->mu)
+DeviceState *find_device_state(rt_scene *s, int device)
+{
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (DeviceState *d : s->devs) if (d->device == device) return d;
+    return nullptr;
+}
+
+// The tree the kernels walk is built HERE from the triangles (binned surface-area heuristic, leaves of at most four, collapsed
+// four-wide by largest child first): any bounding hierarchy over the same triangles gives the same closest hit -- the
+// triangle tests are the reference's, operation by operation, and `t < z` keeps the nearest whatever the order (only two
+// hits at EXACTLY equal t depend on it) -- so the reference's mean-split tree (rt_bvh_build, rt_scene_set_mesh: kept bit-identical
+// for whoever reads it back) is not what limits traversal any more.  slot_face: the face of every triangle slot (leaf order).
+static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &out, std::vector<uint32_t> &slot_face, uint32_t &root_ref, int &stack_need)
+{
+    const size_t nf = m.f.size() / 3;
+    struct TB { float lo[3], hi[3], c[3]; };
+    std::vector<TB> tb(nf);
+    for (size_t f = 0; f < nf; f++) {
+        TB &t = tb[f];
+        for (int a = 0; a < 3; a++) { t.lo[a] = 3.0e38f; t.hi[a] = -3.0e38f; }
+        for (int k = 0; k < 3; k++) {
+            const float *q = &m.v[3 * (size_t)m.f[3 * f + k]];
+            for (int a = 0; a < 3; a++) { t.lo[a] = std::min(t.lo[a], q[a]); t.hi[a] = std::max(t.hi[a], q[a]); }
+        }
+        for (int a = 0; a < 3; a++) t.c[a] = 0.5f * (t.lo[a] + t.hi[a]);
+    }
+    struct BN { float lo[3], hi[3]; int32_t left, right; uint32_t first, count; };      // binary tree: leaf when left < 0
+    std::vector<BN> bn;
+    std::vector<uint32_t> idx(nf);
+    for (size_t i = 0; i < nf; i++) idx[i] = (uint32_t)i;
+    auto area = [](const float *lo, const float *hi) { const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2]; return 2.0f * (dx * dy + dy * dz + dz * dx); };
+    struct Rec {
+        std::vector<TB> &tb; std::vector<BN> &bn; std::vector<uint32_t> &idx; decltype(area) &area;
+        int32_t go(uint32_t b, uint32_t e, int depth)
+        {
+            BN n;
+            for (int a = 0; a < 3; a++) { n.lo[a] = 3.0e38f; n.hi[a] = -3.0e38f; }
+            float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+            for (uint32_t i = b; i < e; i++) {
+                const TB &t = tb[idx[i]];
+                for (int a = 0; a < 3; a++) { n.lo[a] = std::min(n.lo[a], t.lo[a]); n.hi[a] = std::max(n.hi[a], t.hi[a]); clo[a] = std::min(clo[a], t.c[a]); chi[a] = std::max(chi[a], t.c[a]); }
+            }
+            n.left = n.right = -1; n.first = b; n.count = e - b;
+            const int32_t me = (int32_t)bn.size();
+            bn.push_back(n);
+            // leaves of at most four triangles (measured on MI355X, tracer ms Cornell / 102 k triangles / C3: 2: 15.45 / 21.77 / 202.4, 3: 15.46 / 21.79 /
+            // 201.1, 4: 15.51 / 22.22 / 196.5, 6: 15.62 / 22.63 / 202.6, 8: 15.87 / 23.65 / 213.6), its triangles by face id
+            if (e - b <= 4) { std::sort(idx.begin() + b, idx.begin() + e); return me; }
+            uint32_t mid = 0;
+            if (depth < 28) {
+                // binned SAH over the centroids, 16 bins per axis
+                const int NB = 16;
+                float best = 3.0e38f; int best_axis = -1, best_bin = 0;
+                for (int a = 0; a < 3; a++) {
+                    const float ext = chi[a] - clo[a];
+                    if (!(ext > 0)) continue;
+                    struct Bin { float lo[3], hi[3]; uint32_t n; } bins[NB];
+                    for (int k = 0; k < NB; k++) { bins[k].n = 0; for (int c = 0; c < 3; c++) { bins[k].lo[c] = 3.0e38f; bins[k].hi[c] = -3.0e38f; } }
+                    const float scale = (float)NB / ext;
+                    for (uint32_t i = b; i < e; i++) {
+                        const TB &t = tb[idx[i]];
+                        int k = (int)((t.c[a] - clo[a]) * scale);
+                        k = k < 0 ? 0 : (k >= NB ? NB - 1 : k);
+                        bins[k].n++;
+                        for (int c = 0; c < 3; c++) { bins[k].lo[c] = std::min(bins[k].lo[c], t.lo[c]); bins[k].hi[c] = std::max(bins[k].hi[c], t.hi[c]); }
+                    }
+                    float rlo[NB][3], rhi[NB][3]; uint32_t rn[NB];
+                    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}; uint32_t cnt = 0;
+                    for (int k = NB - 1; k >= 1; k--) {
+                        cnt += bins[k].n;
+                        for (int c = 0; c < 3; c++) { lo[c] = std::min(lo[c], bins[k].lo[c]); hi[c] = std::max(hi[c], bins[k].hi[c]); }
+                        rn[k] = cnt; for (int c = 0; c < 3; c++) { rlo[k][c] = lo[c]; rhi[k][c] = hi[c]; }
+                    }
+                    for (int c = 0; c < 3; c++) { lo[c] = 3.0e38f; hi[c] = -3.0e38f; }
+                    cnt = 0;
+                    for (int k = 0; k + 1 < NB; k++) {               // split between bin k and k + 1
+                        cnt += bins[k].n;
+                        for (int c = 0; c < 3; c++) { lo[c] = std::min(lo[c], bins[k].lo[c]); hi[c] = std::max(hi[c], bins[k].hi[c]); }
+                        if (cnt == 0 || rn[k + 1] == 0) continue;
+                        const float cost = area(lo, hi) * (float)cnt + area(rlo[k + 1], rhi[k + 1]) * (float)rn[k + 1];
+                        if (cost < best) { best = cost; best_axis = a; best_bin = k; }
+                    }
+                }
+                if (best_axis >= 0) {
+                    const int a = best_axis;
+                    const float scale = 16.0f / (chi[a] - clo[a]);
+                    auto it = std::partition(idx.begin() + b, idx.begin() + e, [&](uint32_t f) {
+                        int k = (int)((tb[f].c[a] - clo[a]) * scale);
+                        k = k < 0 ? 0 : (k >= 16 ? 15 : k);
+                        return k <= best_bin;
+                    });
+                    mid = (uint32_t)(it - idx.begin());
+                }
+            }
+            if (mid <= b || mid >= e) {
+                // no usable plane (all centroids in one bin, or the tree got deep): halves by the widest centroid axis
+                int a = 0;
+                if (chi[1] - clo[1] > chi[a] - clo[a]) a = 1;
+                if (chi[2] - clo[2] > chi[a] - clo[a]) a = 2;
+                mid = b + (e - b) / 2;
+                std::nth_element(idx.begin() + b, idx.begin() + mid, idx.begin() + e, [&](uint32_t x, uint32_t y) { return tb[x].c[a] < tb[y].c[a] || (tb[x].c[a] == tb[y].c[a] && x < y); });
+            }
+            const int32_t l = go(b, mid, depth + 1);
+            const int32_t r = go(mid, e, depth + 1);
+            bn[me].left = l; bn[me].right = r;
+            return me;
+        }
+    } rec{tb, bn, idx, area};
+    const int32_t root = rec.go(0, (uint32_t)nf, 0);
+    auto leafref = [](uint32_t off, uint32_t cnt) { return 0x80000000u | ((cnt - 1) << 28) | (off & 0x0FFFFFFFu); };
+    slot_face = idx;
+    if (nf >= 0x10000000ull) return fail(RT_ERR_LIMIT, "mesh too large");
+    int max_levels = 0;
+    // four-wide: a device node holds up to four descendants of the binary node it stands for -- starting from its two children, the
+    // internal one with the largest surface is replaced by its own two children until there are four (or only leaves)
+    struct Col {
+        std::vector<BN> &bn; std::vector<DevBvhNode> &out; decltype(area) &area; decltype(leafref) &leafref; int &max_levels;
+        uint32_t go(int32_t id, int level)
+        {
+            if (level > max_levels) max_levels = level;
+            const uint32_t me = (uint32_t)out.size();
+            out.push_back(DevBvhNode{});
+            int32_t ch[4]; int n = 0;
+            ch[n++] = bn[id].left; ch[n++] = bn[id].right;
+            while (n < 4) {
+                int pick = -1; float big = -1.0f;
+                for (int i = 0; i < n; i++) if (bn[ch[i]].left >= 0) { const float s = area(bn[ch[i]].lo, bn[ch[i]].hi); if (s > big) { big = s; pick = i; } }
+                if (pick < 0) break;
+                const int32_t c = ch[pick];
+                for (int i = n; i > pick + 1; i--) ch[i] = ch[i - 1];
+                ch[pick] = bn[c].left; ch[pick + 1] = bn[c].right;
+                n++;
+            }
+            DevBvhNode d;
+            memset(&d, 0, sizeof d);
+            const float nan = std::nanf("");
+            for (int i = 0; i < 4; i++) {
+                for (int a = 0; a < 3; a++) { d.lo[a][i] = i < n ? bn[ch[i]].lo[a] : nan; d.hi[a][i] = i < n ? bn[ch[i]].hi[a] : nan; }
+                if (i >= n) d.c[i] = leafref(0, 1);
+                else if (bn[ch[i]].left < 0) d.c[i] = leafref(bn[ch[i]].first, bn[ch[i]].count);
+                else d.c[i] = go(ch[i], level + 1);
+            }
+            out[me] = d;
+            return me;
+        }
+    } col{bn, out, area, leafref, max_levels};
+    if (bn[root].left < 0) { root_ref = leafref(bn[root].first, bn[root].count); stack_need = 0; }
+    else { root_ref = col.go(root, 1); stack_need = 3 * max_levels; }
+    return RT_OK;
+}
+
+static rt_status upload_scene(rt_scene *s, DeviceState *D)
+{
+    const rt::SceneData &sd = s->data;
+    if (sd.nodes.empty()) return fail(RT_ERR_STATE, "scene has no nodes");
+    if (sd.nodes.size() > 65535) return fail(RT_ERR_LIMIT, "too many scene nodes (%zu)", sd.nodes.size());
+    if (sd.materials.size() > 65535) return fail(RT_ERR_LIMIT, "too many materials (%zu): ray records carry 16-bit material indices", sd.materials.size());
+    const int nn = (int)sd.nodes.size();
+    std::vector<DevNodeXf> xf(nn);
+    std::vector<int32_t> node_mat(nn, 0);
+    std::vector<DevObject> objs;
+    std::vector<DevObjectBack> backs;
+    auto xf_of = [](const rt_node &n) { DevNodeXf x; memcpy(x.itm, n.itm, 36); memcpy(x.pos, n.pos, 12); memcpy(x.tm, n.tm, 36); x.pad[0] = x.pad[1] = x.pad[2] = 0; return x; };
+    for (int i = 0; i < nn; i++) {
+        const rt_node &n = sd.nodes[i];
+        xf[i] = xf_of(n);
+        if (n.obj_type == RT_OBJ_NONE) continue;
+        if (n.material < 0 || (size_t)n.material >= sd.materials.size())
+            return fail(RT_ERR_ARG, "node %d carries an object but its material index %d is invalid", i, n.material);
+        node_mat[i] = n.material;
+        DevObject o{};
+        o.type = n.obj_type; o.mesh = -1; o.material = n.material; o.node = i;
+        if (n.obj_type == RT_OBJ_MESH) {
+            if (n.mesh < 0 || (size_t)n.mesh >= sd.meshes.size() || sd.meshes[n.mesh].f.empty())
+                return fail(RT_ERR_ARG, "node %d references mesh %d which was never set", i, n.mesh);
+            o.mesh = n.mesh;
+        }
+        int chain[64], len = 0;
+        for (int a = i; a >= 0; a = sd.nodes[a].parent) { if (len >= 64) break; chain[len++] = a; }
+        if (len > RT_MAX_DEPTH) return fail(RT_ERR_LIMIT, "node %d is nested %d deep; the device supports %d levels", i, len, RT_MAX_DEPTH);
+        o.chain_len = len;
+        for (int c = 0; c < len; c++) o.chain[c] = chain[len - 1 - c];      // root .. self
+        memcpy(o.own_itm, n.itm, 36); memcpy(o.own_pos, n.pos, 12);         // the node's own ToNodeCoords transform, beside the rest
+        {   // bounds in the ROOT node's coordinates (where every ray is taken first): the 8 corners of the
+            // local extent through tm*p + pos of self .. the root's child (double), inflated by 1e-3 of
+            // the extent (the exact test runs in float in local space)
+            double lo[3] = {-1, -1, -1}, hi[3] = {1, 1, 1};                 // unit sphere; unit square at z = 0
+            if (n.obj_type == RT_OBJ_PLANE) lo[2] = hi[2] = 0;
+            if (n.obj_type == RT_OBJ_MESH) {
+                const float *b = sd.meshes[n.mesh].nodes[1].box;
+                for (int a = 0; a < 3; a++) { lo[a] = b[a]; hi[a] = b[a + 3]; }
+            }
+            double wlo[3] = {1e300, 1e300, 1e300}, whi[3] = {-1e300, -1e300, -1e300};
+            bool finite = true;
+            for (int corner = 0; corner < 8; corner++) {
+                double q[3] = {(corner & 1) ? hi[0] : lo[0], (corner & 2) ? hi[1] : lo[1], (corner & 4) ? hi[2] : lo[2]};
+                for (int c = 0; c + 1 < len; c++) {                          // chain[] here is still self .. root
+                    const rt_node &X = sd.nodes[chain[c]];
+                    const double r[3] = {q[0] * X.tm[0] + q[1] * X.tm[3] + q[2] * X.tm[6] + X.pos[0],
+                                         q[0] * X.tm[1] + q[1] * X.tm[4] + q[2] * X.tm[7] + X.pos[1],
+                                         q[0] * X.tm[2] + q[1] * X.tm[5] + q[2] * X.tm[8] + X.pos[2]};
+                    q[0] = r[0]; q[1] = r[1]; q[2] = r[2];
+                }
+                for (int a = 0; a < 3; a++) { if (!std::isfinite(q[a])) finite = false; wlo[a] = std::min(wlo[a], q[a]); whi[a] = std::max(whi[a], q[a]); }
+            }
+            const double ext = std::max(std::max(whi[0] - wlo[0], whi[1] - wlo[1]), whi[2] - wlo[2]);
+            const double pad = 1e-3 * ext + 1e-5;
+            for (int a = 0; a < 3; a++) {
+                // a degenerate transform (non-finite corner) disables the cull for this object
+                o.wlo[a] = finite ? (float)(wlo[a] - pad) : -3.0e38f;
+                o.whi[a] = finite ? (float)(whi[a] + pad) : 3.0e38f;
+            }
+        }
+        objs.push_back(o);
+        DevObjectBack b;
+        memset(&b, 0, sizeof b);
+        b.chain_len = len; b.node = i;
+        for (int k = 0; k < RT_BACK_LEVELS && k < len - 1; k++) b.lvl[k] = xf_of(sd.nodes[chain[k]]);     // chain[] is self .. root
+        backs.push_back(b);
+    }
+    if (objs.size() > RT_MAX_OBJECTS) return fail(RT_ERR_LIMIT, "too many objects (%zu)", objs.size());
+
+    rt_status st;
+    if ((st = D->nodes.upload(xf.data(), xf.size() * sizeof(DevNodeXf)))) return st;
+    if ((st = D->objects.upload(objs.data(), objs.size() * sizeof(DevObject)))) return st;
+    if ((st = D->objects_back.upload(backs.data(), backs.size() * sizeof(DevObjectBack)))) return st;
+    if ((st = D->node_material.upload(node_mat.data(), node_mat.size() * 4))) return st;
+    if ((st = D->materials.upload(sd.materials.data(), sd.materials.size() * sizeof(rt_blinn)))) return st;
+    if ((st = D->lights.upload(sd.lights.data(), sd.lights.size() * sizeof(rt_light)))) return st;
+
+    for (auto &mb : D->mesh_bufs) { mb.nodes.release(); mb.tris.release(); mb.nrm.release(); mb.tex.release(); }
+    D->mesh_bufs.assign(sd.meshes.size(), DevMeshBufs());
+    std::vector<DevMesh> dm(sd.meshes.size());
+    int max_depth = 0;
+    for (size_t mi = 0; mi < sd.meshes.size(); mi++) {
+        const rt::MeshData &m = sd.meshes[mi];
+        memset(&dm[mi], 0, sizeof(DevMesh));
+        if (m.f.empty()) continue;
+        std::vector<DevBvhNode> bn;
+        uint32_t root_ref = 0;
+        int depth = 0;
+        std::vector<uint32_t> slot_face;
+        if ((st = build_sah_bvh(m, bn, slot_face, root_ref, depth))) return st;
+        // (the smallest LDS stack of any tracing kernel is RT_BVH_LDS entries; RT_BVH_SPILL more per thread wait in HBM: spill buffers below)
+        if (depth > RT_BVH_LDS + RT_BVH_SPILL) return fail(RT_ERR_LIMIT, "mesh %zu: the BVH can need %d traversal-stack entries, the device provides %d", mi, depth, RT_BVH_LDS + RT_BVH_SPILL);
+        max_depth = std::max(max_depth, depth);
+        const size_t nf = m.f.size() / 3;
+        std::vector<DevTri> tris(nf);
+        std::vector<uint32_t> tri_face(nf);
+        std::vector<float> nrm(9 * nf);
+        for (size_t sidx = 0; sidx < nf; sidx++) {
+            const uint32_t face = slot_face[sidx];
+            tri_face[sidx] = face;
+            rt::Point3 P[3];
+            for (int k = 0; k < 3; k++) { const float *q = &m.v[3 * (size_t)m.f[3 * (size_t)face + k]]; P[k] = rt::Point3(q[0], q[1], q[2]); }
+            rt::Point3 N = (P[1] - P[0]).Cross(P[2] - P[0]);      // FIN/include/objects.h:234-235
+            N.Normalize();
+            DevTri &T = tris[sidx];
+            T.A[0] = P[0].x; T.A[1] = P[0].y; T.A[2] = P[0].z; T.B[0] = P[1].x; T.B[1] = P[1].y; T.B[2] = P[1].z;
+            T.C[0] = P[2].x; T.C[1] = P[2].y; T.C[2] = P[2].z; T.N[0] = N.x; T.N[1] = N.y; T.N[2] = N.z;
+        }
+        for (size_t sidx = 0; sidx < nf; sidx++)                 // per triangle SLOT (leaf order), like tris
+            for (int k = 0; k < 3; k++) memcpy(&nrm[9 * sidx + 3 * k], &m.vn[3 * (size_t)m.fn[3 * (size_t)tri_face[sidx] + k]], 12);
+        DevMeshBufs &mb = D->mesh_bufs[mi];
+        if ((st = mb.nodes.upload(bn.data(), bn.size() * sizeof(DevBvhNode)))) return st;
+        if ((st = mb.tris.upload(tris.data(), tris.size() * sizeof(DevTri)))) return st;
+        if ((st = mb.nrm.upload(nrm.data(), nrm.size() * 4))) return st;
+        dm[mi].tex = nullptr;
+        if (!m.vt.empty() && m.ft.size() == m.f.size()) {      // vt[ft0], vt[ft1], vt[ft2] per triangle slot, like nrm
+            std::vector<float> tex(9 * nf);
+            for (size_t sidx = 0; sidx < nf; sidx++)
+                for (int k = 0; k < 3; k++) memcpy(&tex[9 * sidx + 3 * k], &m.vt[3 * (size_t)m.ft[3 * (size_t)tri_face[sidx] + k]], 12);
+            if ((st = mb.tex.upload(tex.data(), tex.size() * 4))) return st;
+            dm[mi].tex = (const float *)mb.tex.p;
+        }
+        dm[mi].nodes = (const DevBvhNode *)mb.nodes.p; dm[mi].tris = (const DevTri *)mb.tris.p;
+        dm[mi].nrm = (const float *)mb.nrm.p;
+        memcpy(dm[mi].root_box, m.nodes[1].box, 24);
+        dm[mi].root_ref = root_ref; dm[mi].n_tris = (uint32_t)nf;
+    }
+    if ((st = D->meshes.upload(dm.data(), dm.size() * sizeof(DevMesh)))) return st;
+
+    DevScene &S = D->scene;
+    S.nodes = (const DevNodeXf *)D->nodes.p; S.objects = (const DevObject *)D->objects.p; S.objects_back = (const DevObjectBack *)D->objects_back.p;
+    S.meshes = (const DevMesh *)D->meshes.p; S.materials = (const rt_blinn *)D->materials.p;
+    S.lights = (const rt_light *)D->lights.p; S.node_material = (const int32_t *)D->node_material.p;
+    S.n_nodes = nn; S.n_objects = (int)objs.size(); S.n_meshes = (int)sd.meshes.size();
+    S.n_materials = (int)sd.materials.size(); S.n_lights = (int)sd.lights.size();
+    memcpy(S.env, sd.env, 12); memcpy(S.bg, sd.bg, 12);
+    // textures and maps
+    for (const rt_texture &t : sd.textures)
+        if (t.type == RT_TEX_FILE && (t.width < 0 || t.height < 0 || (uint64_t)t.texel_offset + 3ull * t.width * t.height > sd.texels.size()))
+            return fail(RT_ERR_ARG, "texture texels out of range");
+    if (!sd.material_maps.empty() && sd.material_maps.size() != 2 * sd.materials.size())
+        return fail(RT_ERR_ARG, "material maps: need 2 per material (%zu given for %zu materials)", sd.material_maps.size(), sd.materials.size());
+    auto check_map = [&](const rt_texmap &m) { return m.texture == RT_MAP_NONE || m.texture == RT_MAP_EMPTY || (m.texture >= 0 && (size_t)m.texture < sd.textures.size()); };
+    for (const rt_texmap &m : sd.material_maps) if (!check_map(m)) return fail(RT_ERR_ARG, "material map refers to texture %d", m.texture);
+    if (!check_map(sd.env_map) || !check_map(sd.bg_map)) return fail(RT_ERR_ARG, "environment/background map refers to a missing texture");
+    if ((st = D->textures.upload(sd.textures.data(), sd.textures.size() * sizeof(rt_texture)))) return st;
+    if ((st = D->texels.upload(sd.texels.data(), sd.texels.size()))) return st;
+    if ((st = D->material_maps.upload(sd.material_maps.data(), sd.material_maps.size() * sizeof(rt_texmap)))) return st;
+    S.textures = (const rt_texture *)D->textures.p; S.texels = (const uint8_t *)D->texels.p; S.n_textures = (int)sd.textures.size();
+    S.material_maps = sd.material_maps.empty() ? nullptr : (const rt_texmap *)D->material_maps.p;
+    S.env_map = sd.env_map; S.bg_map = sd.bg_map;
+    S.use_uvw = sd.material_maps.empty() ? 0 : 1;
+    S.max_bvh_depth = max_depth;
+    S.bvh_spill = nullptr;
+    if (max_depth > RT_BVH_LDS) {
+        if ((st = D->bvh_spill.ensure(SPILL_BYTES))) return st;
+        S.bvh_spill = (uint32_t *)D->bvh_spill.p;
+    }
+    S.stochastic = 0;
+    for (const rt_light &l : sd.lights) if (l.type == RT_LIGHT_POINT && l.size != 0) S.stochastic = 1;
+    for (const rt_blinn &m : sd.materials) if (m.reflection_glossiness != 0 || m.refraction_glossiness != 0) S.stochastic = 1;
+    D->scene_valid = true;
+    return RT_OK;
+}
+
+// Gather structure of a photon map (rt_dev.h, built by rt_photon_build.hip on the GPU): the photons LocatePhotons can reach
+// -- it descends only while index < halfStoredPhotons = n/2 - 1, cyPhotonMap.h:217,371, so heap slots >= 2*half are never
+// visited: for a balanced array that is a prefix, for an unbalanced one everything but the `skip` indices -- re-sorted by
+// recursive median splits into 2^D sub-leaves of <= RT_SUB_PHOTONS photons with their tight boxes; RT_LEAF_SUBS consecutive
+// sub-leaves are one leaf (128 slots) of the tree the queries walk (boxes of all heap nodes in `box4`: the tree over the
+// leaves is its head, the sub-leaf boxes its last level).  `src_dev` != NULL: the photons already sit on this device
+// (n_src records, 0-based); else they are uploaded from `src_host`.  skip: ascending 0-based positions to leave out.
+static rt_status build_photon_structure(DeviceState *D, bool caustic, const rt_photon *src_dev, const rt_photon *src_host, uint32_t n_src,
+                                        const uint32_t *skip, uint32_t n_skip, double *ms_upload, double *ms_build)
+{
+    using clk = std::chrono::steady_clock;
+    auto [M, pm] = D->map(caustic);
+    // nothing is published before the build and its final synchronisation have succeeded: a failure leaves the device WITHOUT a
+    // valid map, so the next render tries again (and fails as loudly) instead of rendering without global illumination
+    memset(&pm, 0, sizeof pm);
+    M.valid = false;
+    struct TempBuf : DevBuf { ~TempBuf() { release(); } };      // released on every path out of this function
+    if (n_src <= n_skip) { M.valid = true; return RT_OK; }
+    if (n_skip > 8) return fail(RT_ERR_LIMIT, "photon structure: %u photons to leave out, the device copy takes at most 8 (rt::UnreachablePhotons yields at most 4)", n_skip);
+    const uint32_t n = n_src - n_skip;
+    uint32_t n_leaves = 1;
+    while ((size_t)n_leaves * RT_LEAF_SUBS * RT_SUB_PHOTONS < n) n_leaves <<= 1;
+    // leaf ids travel as 16-bit values through the kernel's LDS lists; slots are addressed by 32-bit byte offsets
+    if (n_leaves > 65536) return fail(RT_ERR_LIMIT, "photon map too large for the gather structure (%u photons, at most 8 Mi)", n);
+    static_assert((65536ull * RT_LEAF_SUBS + 1) * RT_SUB_PHOTONS * sizeof(float4) <= 0xFFFFFFFFull, "photon slots are addressed by 32-bit byte offsets");
+    const uint32_t n_sub = n_leaves * RT_LEAF_SUBS;
+    rt_status st;
+    hipStream_t stream = D->stream;
+    const auto t0 = clk::now();
+    TempBuf staged, compacted, scratch;
+    const rt_photon *ph = src_dev;
+    if (!ph) {
+        if ((st = staged.ensure((size_t)n_src * sizeof(rt_photon)))) return st;
+        HIP_TRY(hipMemcpyAsync(staged.p, src_host, (size_t)n_src * sizeof(rt_photon), hipMemcpyHostToDevice, stream));
+        ph = (const rt_photon *)staged.p;
+    }
+    if (n_skip) {
+        if ((st = compacted.ensure((size_t)n * sizeof(rt_photon)))) return st;
+        rtk_photon_copy_skipping(stream, ph, n_src, skip, n_skip, (rt_photon *)compacted.p);
+        ph = (const rt_photon *)compacted.p;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    const auto t1 = clk::now();
+    // one more sub-leaf than the tree has, every slot empty: the kernel pads its sub-leaf lists with it
+    const size_t slots = ((size_t)n_sub + 1) * RT_SUB_PHOTONS;
+    const size_t sbytes = rtk_photon_structure_scratch(n, n_sub);
+    if ((st = M.pa.ensure(slots * sizeof(float4))) || (st = M.pb.ensure(slots * sizeof(float4))) || (st = M.box4.ensure((size_t)4 * n_sub * sizeof(float4))) ||
+        (st = M.grid.ensure((size_t)64 * 64 * 64 * 4)) || (st = scratch.ensure(sbytes))) return st;
+    PhotonGridOut g;
+    const hipError_t e = rtk_photon_structure(stream, ph, n, n_sub, (float4 *)M.pa.p, (float4 *)M.pb.p, (float4 *)M.box4.p, (uint32_t *)M.grid.p, &g, scratch.p, sbytes);
+    hipError_t e2 = hipStreamSynchronize(stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(RT_ERR_DEVICE, "photon structure build failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    DevPhotonMap built;
+    memset(&built, 0, sizeof built);
+    built.pa = (const float4 *)M.pa.p; built.pb = (const float4 *)M.pb.p;
+    built.tbox = (const float4 *)M.box4.p; built.sbox = (const float4 *)M.box4.p + 2 * (size_t)n_sub;
+    built.n_leaves = n_leaves; built.n_photons = n;
+    built.grid = (const uint32_t *)M.grid.p;
+    for (int a = 0; a < 3; a++) { built.grid_min[a] = g.min[a]; built.grid_dim[a] = g.dim[a]; }
+    built.cell = g.cell; built.inv_cell = 1.0f / g.cell;
+    if ((st = M.cell_rk2.ensure((size_t)64 * 64 * 64 * 4))) return st;
+    HIP_TRY(hipMemsetAsync(M.cell_rk2.p, 0, (size_t)64 * 64 * 64 * 4, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    pm = built;
+    M.valid = true;
+    M.rk2_k = 0;                                    // the hint table is empty: no gather parameters recorded yet
+    const auto t2 = clk::now();
+    if (ms_upload) *ms_upload += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    if (ms_build) *ms_build += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return RT_OK;
+}
+
+// the generated photons on the host (caller holds s->mu): copied from the device that made them, once
+static rt_status raw_to_host(rt_scene *s)
+{
+    if (!s->gen_n || !s->photons_raw.empty()) return RT_OK;
+    if (!s->gen_dev || !s->gen_dev->raw_photons.p) return fail(RT_ERR_STATE, "the generated photon map is gone from its device");
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    HIP_TRY(hipSetDevice(s->gen_dev->device));
+    std::vector<rt_photon> raw((size_t)s->gen_n + 1);
+    HIP_TRY(hipMemcpy(raw.data(), s->gen_dev->raw_photons.p, raw.size() * sizeof(rt_photon), hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(cur));
+    s->photons_raw.swap(raw);
+    return RT_OK;
+}
+
+static rt_status upload_photons(rt_scene *s, DeviceState *D, bool caustic)
+{
+    if (!caustic && s->gen_n) {
+        std::vector<uint32_t> skip0;
+        for (uint32_t i : s->photons_skip) skip0.push_back(i - 1);              // 1-based raw index -> position in [1..n]
+        if (D == s->gen_dev && D->raw_photons.p)                                 // still on this device
+            return build_photon_structure(D, false, (const rt_photon *)D->raw_photons.p + 1, nullptr, s->gen_n, skip0.data(), (uint32_t)skip0.size(), nullptr, nullptr);
+        rt_status st = raw_to_host(s);                                           // another device: through the host
+        if (st) return st;
+        HIP_TRY(hipSetDevice(D->device));
+    }
+    if (!caustic && !s->photons_raw.empty()) {
+        // as generated (unbalanced): everything but the photons balancing would put out of LocatePhotons' reach
+        std::vector<uint32_t> skip0;
+        for (uint32_t i : s->photons_skip) skip0.push_back(i - 1);              // 1-based raw index -> position in [1..n]
+        return build_photon_structure(D, false, nullptr, s->photons_raw.data() + 1, (uint32_t)s->photons_raw.size() - 1, skip0.data(), (uint32_t)skip0.size(), nullptr, nullptr);
+    }
+    const std::vector<rt_photon> &ph = caustic ? s->data.caustic_photons : s->data.photons;
+    if (ph.size() < 2) { auto [M, pm] = D->map(caustic); memset(&pm, 0, sizeof(DevPhotonMap)); M.valid = true; return RT_OK; }
+    const uint32_t n = (uint32_t)ph.size() - 1;
+    return build_photon_structure(D, caustic, nullptr, ph.data() + 1, rt::ReachablePhotonSlots(n), nullptr, 0, nullptr, nullptr);
+}
+
+rt_status prepare_device(rt_scene *s, int device, DeviceState **out)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return fail(RT_ERR_NO_DEVICE, "no HIP device is visible (this library has no CPU path)"); }
+    if (device < 0 || device >= n) return fail(RT_ERR_ARG, "device %d out of range (0..%d)", device, n - 1);
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "device %d is not gfx950 (MI355X); kernels are built for gfx950 only", device);
+    HIP_TRY(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceState *D = device_state(s, device);
+    if (!D->stream) HIP_TRY(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
+    rt_status st;
+    // an asynchronous render (sync == 0) may still be reading the buffers an upload is about to overwrite (scene tables and
+    // photon structure are re-used in place when the new data fits): wait for it on the host first
+    if ((!D->scene_valid || !D->maps[0].valid || !D->maps[1].valid) && D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
+    if (!D->scene_valid) { const DevPhotonMap keep = D->scene.pm, keepc = D->scene.cm; if ((st = upload_scene(s, D))) return st; D->scene.pm = keep; D->scene.cm = keepc; }
+    for (int caustic = 0; caustic < 2; caustic++)
+        if (!D->maps[caustic].valid && (st = upload_photons(s, D, caustic != 0))) return st;
+    *out = D;
+    return RT_OK;
+}
+
+// DevPhotonMap::cell_start for the radius the gather is about to use: built on first use and again when a larger radius comes
+// (a table built for a radius serves every smaller one), on the stream the gather will run on
+rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float radius, hipStream_t st, bool *did_work)
+{
+    auto [M, pm] = D->map(caustic);
+    // the per-cell k-th distances (PhotonStore::cell_rk2) are hints of ONE gather configuration: what queries with another k
+    // or radius left there is dropped, so that it cannot steer this render's choice between the (exact) gather paths
+    if (M.cell_rk2.p && M.rk2_k != 0 && (M.rk2_k != k || M.rk2_radius != radius)) {
+        HIP_TRY(hipMemsetAsync(M.cell_rk2.p, 0, (size_t)64 * 64 * 64 * 4, st));
+        if (did_work) *did_work = true;
+    }
+    M.rk2_k = k; M.rk2_radius = radius;
+    if (pm.n_leaves < 2 || (pm.cell_start && radius <= pm.start_radius)) return RT_OK;
+    rt_status s = M.cell_start.ensure((size_t)64 * 64 * 64 * 4);
+    if (s) return s;
+    rtk_photon_cell_start(st, pm.tbox, pm.n_leaves, pm.grid_min, pm.cell, pm.grid_dim, radius, (uint32_t *)M.cell_start.p);
+    HIP_TRY(hipGetLastError());
+    if (did_work) *did_work = true;
+    pm.cell_start = (const uint32_t *)M.cell_start.p; pm.start_radius = radius;
+    return RT_OK;
+}
+
+// ---- photon pass ----------------------------------------------------------------------------------------
+// generatePhotonMap's two loops (P13/main.cpp:338-404): mode 0 = the photon map (stop when max_count photons are STORED),
+// mode 1 = the caustic map (stop when max_count diffuse hits are COUNTED; only those behind more than one specular
+// hit are stored).  Attempts are consumed in order, the count checked between attempts like the reference's while().
+// Everything stays on the device: k_photon_trace writes each attempt's photons, rtk_photon_compact (rt_photon_build.hip)
+// consumes the attempts in order and packs the stored photons into D->raw_photons (1-based, [0] zero), then
+// ScalePhotonPowers.  The caller holds the device claim.
+static rt_status photon_pass_device(rt_scene *s, DeviceState *D, uint32_t max_count, int photon_bounce, uint32_t seed, int mode,
+                                    uint32_t *n_out, uint64_t *attempts_out, const char *who)
+{
+    if (max_count == 0 || photon_bounce < 1 || photon_bounce > 8) return fail(RT_ERR_ARG, "%s: need a positive count and 1 <= photon_bounce <= 8", who);
+    if (max_count > (1u << 28)) return fail(RT_ERR_LIMIT, "%s: at most 2^28 photons", who);
+    bool have_source = false;
+    for (const rt_light &l : s->data.lights) if (l.type == RT_LIGHT_POINT) have_source = true;
+    if (!have_source) return fail(RT_ERR_STATE, "%s: the scene has no photon source (point light)", who);
+    rt_status st;
+    {   // D->raw_photons is about to be overwritten: a generated map that lives only there goes to the host first
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->gen_dev == D && s->gen_n && s->photons_raw.empty() && (st = raw_to_host(s))) return st;
+    }
+    const uint32_t batch = 1u << 18;
+    static_assert((1u << 18) / RT_BLOCK <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
+    const uint32_t out_cap = max_count + 8 + 1;                 // index 0 unused, up to 7 photons of overshoot
+    if ((st = D->t_out[0].ensure((size_t)batch * 8 * 9 * 4))) return st;
+    if ((st = D->t_out[1].ensure((size_t)batch * 4))) return st;
+    if ((st = D->t_out[2].ensure(2 * sizeof(CompactState)))) return st;
+    const size_t sbytes = rtk_photon_compact_scratch(batch);
+    if ((st = D->t_out[3].ensure(sbytes))) return st;
+    if ((st = D->raw_photons.ensure((size_t)out_cap * sizeof(rt_photon)))) return st;
+    hipStream_t stream = D->stream;
+    HIP_TRY(hipMemsetAsync(D->t_out[2].p, 0, 2 * sizeof(CompactState), stream));
+    HIP_TRY(hipMemsetAsync(D->raw_photons.p, 0, sizeof(rt_photon), stream));
+    CompactState h{0, 0, 0, 0};
+    int empty_batches = 0;
+    while (h.counted < max_count) {
+        PhotonArgs pa = {};
+        pa.first_attempt = h.attempts; pa.n_attempts = batch; pa.seed = seed; pa.max_bounce = photon_bounce; pa.mode = mode;
+        pa.out = (float *)D->t_out[0].p; pa.count = (uint32_t *)D->t_out[1].p;
+        rtk_launch_photon_trace(stream, D->scene, pa);
+        rtk_photon_compact(stream, pa.out, pa.count, batch, mode, max_count, (CompactState *)D->t_out[2].p,
+                           (rt_photon *)D->raw_photons.p, out_cap, D->t_out[3].p, sbytes);
+        HIP_TRY(hipGetLastError());
+        const unsigned long long before = h.counted;
+        HIP_TRY(hipMemcpyAsync(&h, D->t_out[2].p, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (h.counted == before && ++empty_batches >= 4) return fail(RT_ERR_STATE, "%s: no photon is ever stored in this scene", who);
+    }
+    uint32_t n = h.stored;
+    if (n + 1 > out_cap) n = out_cap - 1;
+    if (n > 0) rtk_photon_scale(stream, (rt_photon *)D->raw_photons.p, n, (float)(1.0 * 4 * M_PI / n));      // ScalePhotonPowers(1.0*4*M_PI/NumPhotons), :366 / :400
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n_out = n;
+    if (attempts_out) *attempts_out = h.attempts;
+    return RT_OK;
+}
+
+static rt_status photon_pass(rt_scene *s, int device, uint32_t max_count, int photon_bounce, uint32_t seed, int mode,
+                             rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out, const char *who)
+{
+    if (!s || !out || !n_out) return fail(RT_ERR_ARG, "%s: NULL argument", who);
+    if (max_count == 0 || photon_bounce < 1 || photon_bounce > 8) return fail(RT_ERR_ARG, "%s: need a positive count and 1 <= photon_bounce <= 8", who);
+    if (out_cap < max_count + 8 + 1) return fail(RT_ERR_ARG, "%s: out must hold the count + 9 records (index 0 unused, up to 7 photons of overshoot)", who);
+    DeviceState *D = nullptr;
+    rt_status st = prepare_device(s, device, &D);
+    if (st) return st;
+    DeviceClaim claim(D);
+    if (!claim.ok) return fail(RT_ERR_STATE, "%s: another call on this scene is using device %d", who, device);
+    if ((st = order_after_pending(D, D->stream))) return st;
+    uint32_t n = 0;
+    if ((st = photon_pass_device(s, D, max_count, photon_bounce, seed, mode, &n, attempts_out, who))) return st;
+    HIP_TRY(hipMemcpy(out, D->raw_photons.p, ((size_t)n + 1) * sizeof(rt_photon), hipMemcpyDeviceToHost));
+    *n_out = n;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_photon_pass(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed,
+                                    rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out)
+{
+    return photon_pass(s, device, max_photons, photon_bounce, seed, 0, out, out_cap, n_out, attempts_out, "rt_photon_pass");
+}
+
+extern "C" rt_status rt_caustic_pass(rt_scene *s, int device, uint32_t max_diffuse_hits, int photon_bounce, uint32_t seed,
+                                     rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out)
+{
+    return photon_pass(s, device, max_diffuse_hits, photon_bounce, seed, 1, out, out_cap, n_out, attempts_out, "rt_caustic_pass");
+}
+
+// generatePhotonMap as a whole (FIN/main.cpp:350-402).  `own_job`: called from the job thread of rt_render_begin (the scene
+// counts that job as live; no other caller can be inside the scene then).
+rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
+                           rt_setup_ms *ms_out, bool own_job)
+{
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (!s) return fail(RT_ERR_ARG, "rt_scene_generate_photons: scene is NULL");
+    rt_status st;
+    if (!own_job && (st = check_idle(s, "rt_scene_generate_photons"))) return st;
+    rt_setup_ms T;
+    memset(&T, 0, sizeof T);
+    const auto t_begin = clk::now();
+    DeviceState *D = nullptr;
+    if ((st = prepare_device(s, device, &D))) return st;
+    DeviceClaim claim(D);
+    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_generate_photons: another call on this scene is using device %d", device);
+    if ((st = order_after_pending(D, D->stream))) return st;
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));       // the structure is rebuilt in place
+    {   // the map this call replaces: if it lives only on this device, it is simply dropped (not fetched to the host first)
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->gen_n && s->gen_dev == D && s->photons_raw.empty()) { s->drop_generated(); s->invalidate(false, true); }
+    }
+    const auto t0 = clk::now();
+    uint32_t n = 0;
+    if ((st = photon_pass_device(s, D, max_photons, photon_bounce, seed, 0, &n, nullptr, "rt_scene_generate_photons"))) return st;
+    const auto t1 = clk::now();
+    T.photon_pass = ms(t0, t1);
+    // Which photons balancing would put out of LocatePhotons' reach (heap slots > ReachablePhotonSlots(n): the last three or four):
+    // found ON THE DEVICE along the root paths of those slots (rt_photon_build.hip: photon_unreachable); the photons stay where
+    // they are.  They come to the host only for the .dat dump, or when a median's key is not unique in its segment (then the
+    // reference's swap sequence decides and the host replays it: rt::UnreachablePhotons).
+    std::vector<rt_photon> raw;
+    auto fetch = [&]() -> rt_status {
+        if (!raw.empty()) return RT_OK;
+        raw.resize((size_t)n + 1);
+        HIP_TRY(hipMemcpy(raw.data(), D->raw_photons.p, raw.size() * sizeof(rt_photon), hipMemcpyDeviceToHost));
+        return RT_OK;
+    };
+    const auto t2 = clk::now();
+    if (dat_path && dat_path[0]) {
+        if ((st = fetch())) return st;
+        if ((st = rt_photons_write_dat(dat_path, raw.data(), n))) return st;
+    }
+    const auto t2b = clk::now();
+    T.upload = ms(t2, t2b);
+    std::vector<uint32_t> skip;
+    const uint32_t reach = rt::ReachablePhotonSlots(n);
+    if (n && reach < n) {
+        bool on_device = false;
+        {
+            struct TempBuf : DevBuf { ~TempBuf() { release(); } } scratch;
+            const size_t sbytes = rtk_photon_unreachable_scratch(n);
+            uint32_t res[16];
+            if (getenv("RT_UNREACHABLE_ON_HOST") == nullptr && scratch.ensure(sbytes) == RT_OK &&
+                rtk_photon_unreachable(D->stream, (const rt_photon *)D->raw_photons.p, n, reach + 1, n, scratch.p, sbytes, res) == hipSuccess &&
+                res[1] == 0 && res[0] == n - reach) {
+                skip.assign(res + 2, res + 2 + res[0]);
+                std::sort(skip.begin(), skip.end());
+                on_device = true;
+            } else (void)hipGetLastError();
+        }
+        if (!on_device) {
+            // the host's replay of BalanceSegment on (position, index) records packed on the device: 16 bytes per photon come over
+            struct TempBuf : DevBuf { ~TempBuf() { release(); } } packed;
+            if ((st = packed.ensure(((size_t)n + 1) * 16))) return st;
+            rtk_photon_pack_positions(D->stream, (const rt_photon *)D->raw_photons.p, n, packed.p);
+            std::vector<rt::PhotonPosRec> recs((size_t)n + 1);
+            HIP_TRY(hipMemcpyAsync(recs.data(), packed.p, recs.size() * 16, hipMemcpyDeviceToHost, D->stream));
+            HIP_TRY(hipStreamSynchronize(D->stream));
+            rt::UnreachablePhotonRecs(recs.data(), n, skip);
+        }
+    }
+    const auto t3 = clk::now();
+    T.balance = ms(t2b, t3);
+    std::vector<uint32_t> skip0;
+    for (uint32_t i : skip) skip0.push_back(i - 1);
+    double up = 0, build = 0;
+    if ((st = build_photon_structure(D, false, (const rt_photon *)D->raw_photons.p + 1, nullptr, n, skip0.data(), (uint32_t)skip0.size(), &up, &build))) return st;
+    T.upload += up; T.structure_build = build;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->data.photons.clear();
+        s->photons_raw.swap(raw);                 // empty unless the photons had to come to the host
+        s->photons_skip.swap(skip);
+        s->gen.valid = true; s->gen.count = max_photons; s->gen.bounce = photon_bounce; s->gen.seed = seed;
+        s->gen_dev = D; s->gen_n = n;
+        for (DeviceState *d : s->devs) if (d != D) d->maps[0].valid = false;
+    }
+    T.total = ms(t_begin, clk::now());
+    if (ms_out) *ms_out = T;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed,
+                                               const char *dat_path, rt_setup_ms *ms_out)
+{
+    return generate_photons(s, device, max_photons, photon_bounce, seed, dat_path, ms_out, false);
+}
+
+extern "C" rt_status rt_scene_set_photon_dump(rt_scene *s, const char *dat_path)
+{
+    rt_status st = check_idle(s, "rt_scene_set_photon_dump");
+    if (st) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->photon_dump = dat_path ? dat_path : "";
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_get_photons(rt_scene *s, rt_photon *out, uint32_t cap, uint32_t *n_stored)
+{
+    if (!s) return fail(RT_ERR_ARG, "rt_scene_get_photons: scene is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    const uint32_t n = s->photon_count();
+    if (n_stored) *n_stored = n;
+    if (!out) return RT_OK;
+    if (cap < n + 1) return fail(RT_ERR_ARG, "rt_scene_get_photons: buffer of %u records, %u needed", cap, n + 1);
+    if (n == 0) { memset(out, 0, sizeof(rt_photon)); return RT_OK; }
+    { rt_status st = raw_to_host(s); if (st) return st; }
+    if (!s->photons_raw.empty() && s->data.photons.empty()) {
+        // PrepareForIrradianceEstimation (cyPhotonMap.h:196-218) of the generated photons, bit for bit, on first request
+        std::vector<rt_photon> tmp = s->photons_raw;
+        s->data.photons.resize(tmp.size());
+        rt::BalancePhotons(tmp.data(), n, s->data.photons.data());
+    }
+    memcpy(out, s->data.photons.data(), ((size_t)n + 1) * sizeof(rt_photon));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_photon_unreachable_device(int device, const rt_photon *in, uint32_t n, uint32_t *raw_indices, uint32_t cap, uint32_t *count, int32_t *exact)
+{
+    if (!in || !count || !exact) return fail(RT_ERR_ARG, "rt_photon_unreachable_device: NULL argument");
+    *count = 0; *exact = 1;
+    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_photon_unreachable_device: device %d is not gfx950 (no CPU path: rt_photon_unreachable is the host's)", device);
+    const uint32_t reach = rt::ReachablePhotonSlots(n);
+    if (n == 0 || reach >= n) return RT_OK;
+    HIP_TRY(hipSetDevice(device));
+    struct TempBuf : DevBuf { ~TempBuf() { release(); } } ph, scratch;
+    rt_status st;
+    if ((st = ph.upload(in, ((size_t)n + 1) * sizeof(rt_photon)))) return st;
+    HIP_TRY(hipMemset(ph.p, 0, sizeof(rt_photon)));                  // slot 0 is the unused all-zero photon
+    const size_t sbytes = rtk_photon_unreachable_scratch(n);
+    if ((st = scratch.ensure(sbytes))) return st;
+    uint32_t res[16];
+    const hipError_t e = rtk_photon_unreachable(nullptr, (const rt_photon *)ph.p, n, reach + 1, n, scratch.p, sbytes, res);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_photon_unreachable_device: %s", hipGetErrorString(e));
+    if (res[1] != 0 || res[0] != n - reach) { *exact = 0; return RT_OK; }
+    std::vector<uint32_t> idx(res + 2, res + 2 + res[0]);
+    std::sort(idx.begin(), idx.end());
+    *count = (uint32_t)idx.size();
+    if (raw_indices) {
+        if (cap < idx.size()) return fail(RT_ERR_ARG, "rt_photon_unreachable_device: room for %u indices, %zu needed", cap, idx.size());
+        memcpy(raw_indices, idx.data(), idx.size() * 4);
+    }
+    return RT_OK;
+}

@@ -11,7 +11,7 @@
 //
 // k_gather returns the exact k nearest photons whatever the partition, so this build only has to be a GOOD partition
 // (balanced, tight boxes), not the reference's left-balanced heap: the heap order is only needed to know which photons
-// LocatePhotons can never reach (cyPhotonMap.h:217,371) and is found on the host for those few (rt_api.cpp).
+// LocatePhotons can never reach (cyPhotonMap.h:217,371) and is found on the host for those few (rt_lower.cpp).
 // Sort and scan are rocPRIM's (hipcub front end); everything else is written here.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>

@@ -117,7 +117,7 @@ template <class T, class F> static rt_status stage_create(const char *name, int 
     return RT_OK;
 }
 
-// rt_denoise_device and rt_motion_device have no object, and the device state of rt_api.cpp belongs to a scene: their scratch
+// rt_denoise_device and rt_motion_device have no object, and the DeviceState of rt_host.h belongs to a scene: their scratch
 // (a T with a release()) is held per device for the process, and every call on a device shares it under the registry's mutex.
 // Released with the last scene (rt_scene_destroy), like the per-device buffers of the scenes.
 template <class T> using PerDevice = std::vector<std::pair<int, T>>;

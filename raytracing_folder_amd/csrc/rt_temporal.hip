@@ -35,7 +35,7 @@
 //                VGPRs and 8 waves a SIMD (74 and 6 otherwise).
 //                Still no atomics and a fixed order: identical calls give identical bytes.  The halo is read from the caller's
 //                rgb_linear, so out_linear must NOT be rgb_linear here (a neighbouring workgroup may already have written it):
-//                the launch boundary's caller hands in a plane of its own in that case (rt_api.cpp).
+//                the launch boundary's caller hands in a plane of its own in that case (rt_post.cpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_kernel_util.h"

@@ -107,7 +107,7 @@ def test_trace_100k_triangle_mesh_bit_exact():
 
 
 def test_device_bvh_on_awkward_meshes_bit_exact():
-    """The kernels walk a tree of their own (binned surface-area heuristic, four-wide; rt_api.cpp) while the oracle walks the
+    """The kernels walk a tree of their own (binned surface-area heuristic, four-wide; rt_lower.cpp) while the oracle walks the
     reference's mean-split tree: the closest hit must not depend on which -- on meshes that push the builder off its main path: a
     single triangle, fewer triangles than a node has children, hundreds of triangles with ONE centroid (no split plane: halves
     by index), a sliver strip (one centroid axis), a flat grid (coplanar neighbours: equal t on shared edges) and a random soup of
@@ -1027,7 +1027,7 @@ def test_async_device_renders_keep_stream_order(cornell, monkeypatch):
 
 @pytest.mark.parametrize("chunk", [None, "16384"])
 def test_pipelined_frames_stay_behind_the_callers_stream(cornell, monkeypatch, chunk):
-    """Frame pipelining (rt_api.cpp, render_tiles_once): an asynchronous frame behind one that is still in flight traces and gathers
+    """Frame pipelining (rt_render.cpp, render_tiles_once): an asynchronous frame behind one that is still in flight traces and gathers
     at once on the library's streams, but its k_resolve -- the only kernel that writes the caller's buffers -- waits for everything the
     caller's stream held before the call.  Six frames from two alternating cameras go into the SAME buffers; behind each one the stream
     first does slow work of its own and then copies the image.  Every copy must hold exactly its own frame (the next frame may not

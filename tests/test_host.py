@@ -484,3 +484,55 @@ def test_struct_size_mismatch_is_refused_by_name(stage, entry, struct, key, call
         S[key].struct_size = size + off
         assert call(L, S) == -1
         assert L.rt_last_error() == f"{entry}: {struct}.struct_size is {size + off}, this library's is {size}".encode()
+
+
+_UNPACK_ENTRIES = ("rt_tiles_unpack_device", "rt_tiles_unpack_linear_device", "rt_tiles_unpack_outputs_device")
+_PACKED_ENTRIES = ("rt_render_tiles_packed_device", "rt_render_tiles_packed_linear_device", "rt_render_tiles_packed_outputs_device")
+
+
+def _unpack(entry, gathered, world, per_rank, width, height, tile_w, tile_h, planes):
+    """one of the three unpack entry points on device 0 and the NULL stream, every destination plane at `planes`"""
+    vp, i32 = C.c_void_p, C.c_int32
+    head = [C.c_int(0), vp(None), vp(gathered), i32(world), i32(per_rank), i32(width), i32(height), i32(tile_w), i32(tile_h)]
+    if entry == "rt_tiles_unpack_outputs_device":
+        o = capi.Outputs(rgb8=planes, z=planes, count=planes)
+        return getattr(capi.lib(), entry)(*head, C.c_uint32(0), C.byref(o), vp(None))
+    tail = [vp(planes)] * (4 if entry == "rt_tiles_unpack_linear_device" else 3)
+    return getattr(capi.lib(), entry)(*head, *tail)
+
+
+def test_unpack_and_packed_entry_points_refuse_bad_arguments_by_name():
+    """The three unpack entry points share their geometry checks, the three packed render entry points their first two; status
+    and full message of each refusal, all of them made before a device is looked up (so there is none here).  Unpack: a NULL
+    gathered buffer, no ranks, a tile without width, and a contribution one tile short of the image (37x23 in 32x8 tiles: 6
+    tiles, 2 a rank at world 3).  Packed renders: a NULL scene, then a NULL packed buffer, before camera, parameters or tiles
+    (all NULL here) are looked at."""
+    L = capi.lib()
+    vp = C.c_void_p
+    buf = np.zeros(64, np.uint8)
+    a = (buf.ctypes.data + 15) & ~15                        # the packed-planes unpack wants 16-byte alignment before the geometry
+    for entry in _UNPACK_ENTRIES:
+        assert _unpack(entry, None, 3, 2, 37, 23, 32, 8, a) == -1
+        assert L.rt_last_error() == f"{entry}: NULL buffer".encode()
+        assert _unpack(entry, a, 0, 2, 37, 23, 32, 8, a) == -1
+        assert L.rt_last_error() == f"{entry}: bad geometry".encode()
+        assert _unpack(entry, a, 3, 2, 37, 23, 0, 8, a) == -1
+        assert L.rt_last_error() == f"{entry}: bad geometry".encode()
+        assert _unpack(entry, a, 3, 1, 37, 23, 32, 8, a) == -1
+        assert L.rt_last_error() == f"{entry}: 1 tiles per rank x 3 ranks cannot hold 6 tiles".encode()
+    s = vp()
+    assert L.rt_scene_create(C.byref(s)) == 0
+    try:
+        for entry in _PACKED_ENTRIES:
+            mask = [C.c_uint32(0)] if entry.endswith("_outputs_device") else []
+
+            def call(scene, packed):
+                return getattr(L, entry)(scene, vp(None), vp(None), vp(None), C.c_int(0), vp(None), vp(packed), C.c_uint64(1 << 20),
+                                         *mask, C.c_int(1), vp(None))
+
+            assert call(vp(None), a) == -1
+            assert L.rt_last_error() == f"{entry}: scene is NULL".encode()
+            assert call(s, None) == -1
+            assert L.rt_last_error() == f"{entry}: the packed buffer is required".encode()
+    finally:
+        L.rt_scene_destroy(s)
