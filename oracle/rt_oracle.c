@@ -33,7 +33,7 @@ void orc_counters_reset(void) { memset(&g_cnt, 0, sizeof g_cnt); }
 void orc_counters_get(orc_counters *out) { *out = g_cnt; }
 
 /* ---- counter RNG for the stochastic effects (replaces libc rand(); same generator and same
- * (sample, node, purpose, index) addressing as the HIP kernels, see rt_kernels.hip) ------------ */
+ * (sample, node, purpose, index) addressing as the HIP kernels, see rt_shade.h) --------------- */
 static void philox4x32(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t out[4])
 {
     for (int r = 0; r < 10; r++) {

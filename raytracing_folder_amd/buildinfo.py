@@ -6,7 +6,8 @@ import os
 import re
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-KERNEL_SOURCES = ("rt_kernels.hip", "rt_gather.hip", "rt_photon_build.hip", "rt_kernel_util.h", "rt_dev.h", "rt_launch.h")
+KERNEL_SOURCES = ("rt_kernels.hip", "rt_trace.hip", "rt_resolve.hip", "rt_trace.h", "rt_shade.h", "rt_gather.hip", "rt_photon_build.hip",
+                  "rt_kernel_util.h", "rt_dev.h", "rt_launch.h")
 
 
 def build_flags():

@@ -1,5 +1,6 @@
 // rt_dev.h -- device-side data layout of a lowered scene, shared by rt_lower.cpp (which builds
-// and uploads it) and the kernels in rt_kernels.hip / rt_gather.hip (which read it).  gfx950 only.
+// and uploads it) and the kernels in rt_kernels.hip / rt_trace.hip / rt_resolve.hip (with the device headers
+// rt_trace.h and rt_shade.h) / rt_gather.hip (which read it).  gfx950 only.
 //
 // HBM layout (all arrays are plain hipMalloc allocations owned by the rt_scene):
 //   nodes      DevNodeXf[n_nodes]      96 B each: itm(9) pos(3) tm(9) -- read with scalar loads

@@ -844,7 +844,7 @@ __device__ __forceinline__ void finish_queries(const GatherArgs &G, LaneQuery &q
 }
 
 // The wave's tallies into the launch's statistics: a workgroup adds its counters up in LDS and ONE thread per counter
-// flushes them (flush_counters in rt_kernels.hip says why).  Workgroup-uniform; every wave of the workgroup gets here.
+// flushes them (flush_counters in rt_shade.h says why).  Workgroup-uniform; every wave of the workgroup gets here.
 __device__ __forceinline__ void flush_gather_stats(const GatherArgs &G, int lane, const GatherTally &T, uint32_t nq)
 {
     if (!G.stats) return;

@@ -1,10 +1,19 @@
-// rt_kernel_util.h -- the few device helpers that more than one kernel translation unit (rt_kernels.hip, rt_gather.hip, rt_denoise.hip) uses.
-// Device code only; nothing here is host-callable.  Not a general utility header: a helper moves here when a second file needs it.
+// rt_kernel_util.h -- the few helpers that more than one kernel translation unit (rt_kernels.hip through rt_trace.h, rt_trace.hip,
+// rt_resolve.hip, rt_gather.hip, rt_denoise.hip, ...) uses.  Device code, except grid_for, which the launch wrappers of three units
+// size their grids with.  Not a general utility header: a helper moves here when a second file needs it.
 #ifndef RT_KERNEL_UTIL_H
 #define RT_KERNEL_UTIL_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+
+// workgroups for `work` items at `block` per workgroup: at least one, at most max_blocks (the kernels stride over the rest)
+static inline int grid_for(unsigned long long work, int block, int max_blocks)
+{
+    const unsigned long long b = (work + block - 1) / block;
+    return (int)std::min<unsigned long long>(std::max<unsigned long long>(b, 1), (unsigned long long)max_blocks);
+}
 
 // the lanes where a condition holds: the builtin keeps the condition a lane mask (one s_and with exec); HIP's
 // __ballot(int) round-trips it through a 0/1 register (v_cndmask + v_cmp_ne per call, on the VALU the gather is bound by)

@@ -1,4 +1,4 @@
-// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_gather.hip,
+// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
@@ -200,7 +200,7 @@ struct MotionBlurRequest {
     float *tile_max, *tile_nmax;
 };
 
-// ---- rt_kernels.hip ---------------------------------------------------------------------------------------------------
+// ---- rt_kernels.hip: the kernels that shade -----------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
 
@@ -215,8 +215,20 @@ void rtk_launch_primary(hipStream_t st, const DevScene &S, const DevWork &W, con
 bool rtk_launch_wavefront_queue(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass);
 // one level of the ray tree: k_bounce over the queue of `level` (P3 has no secondary rays: no launch)
 void rtk_launch_bounce(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, int level, int max_blocks, unsigned long long *fx);
+// The feature planes of one chunk (pass.cam, tiles, q0, npix), after its last k_resolve on the same stream: the second-batch
+// flags from the chunk's pixel list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when
+// features are on); by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by
+// image pixel.
+void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass,
+                         uint8_t *second, const DevFeatures &out, bool by_walk);
+
+// ---- rt_trace.hip: the kernels that only trace ----------------------------------------------------------------------
 // closest hits of n caller-supplied rays (6 floats each) with the intersection code of `model`
 void rtk_launch_trace(hipStream_t st, const DevScene &S, int model, const float *rays, long long n, const TraceOut &out);
+// k_photon_trace, one thread per attempt
+void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs &A);
+
+// ---- rt_resolve.hip: resolve, fold and unpack (no rays) -------------------------------------------------------------
 // Reproducible mode, once per pass: sample_rgb (the primary contributions) += the secondary plane, and the plane back to zero.
 void rtk_launch_fold_fx(hipStream_t st, float *sample_rgb, unsigned long long *fx, size_t samples);
 // k_resolve over A.npix pixels, at most max_blocks workgroups (tiles_prepare is run on a copy of A.tiles).  linear: the LIN
@@ -226,14 +238,6 @@ void rtk_launch_unpack_tiles(hipStream_t st, const UnpackRequest &R);
 // k_unpack_planes: one pass over the image that moves the records and every section of R (the 4-pixel instantiation when the
 // geometry keeps every access 16-byte aligned, else one pixel per thread)
 void rtk_launch_unpack_planes(hipStream_t st, const UnpackPlanesRequest &R);
-// The feature planes of one chunk (pass.cam, tiles, q0, npix), after its last k_resolve on the same stream: the second-batch
-// flags from the chunk's pixel list, then k_features.  `second` is the working set's flag buffer ([npix] bytes, exists only when
-// features are on); by_walk: the planes are indexed by the call's tile walk (a strided job's staging buffers) instead of by
-// image pixel.
-void rtk_launch_features(hipStream_t st, const DevScene &S, const DevWork &W, const rt_params &P, const RenderPass &pass,
-                         uint8_t *second, const DevFeatures &out, bool by_walk);
-// k_photon_trace, one thread per attempt
-void rtk_launch_photon_trace(hipStream_t st, const DevScene &S, const PhotonArgs &A);
 
 // ---- rt_gather.hip: the photon gather ------------------------------------------------------------------------------------
 // k_gather as a persistent grid of `blocks` workgroups

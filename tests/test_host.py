@@ -536,3 +536,31 @@ def test_unpack_and_packed_entry_points_refuse_bad_arguments_by_name():
             assert L.rt_last_error() == f"{entry}: the packed buffer is required".encode()
     finally:
         L.rt_scene_destroy(s)
+
+
+def test_build_hash_covers_every_header_its_kernel_files_include():
+    """buildinfo.KERNEL_SOURCES is what the build hash on the benchmark line is taken over: every name in it exists in csrc/, and it
+    holds every csrc/-local header that an #include "..." chain starting at one of its .hip files reaches (a header outside the
+    list could change the kernels without changing the hash)."""
+    from raytracing_folder_amd import buildinfo
+
+    csrc = os.path.realpath(buildinfo.CSRC)
+    listed = set(buildinfo.KERNEL_SOURCES)
+    assert len(listed) == len(buildinfo.KERNEL_SOURCES)
+    for name in listed:
+        assert os.path.isfile(os.path.join(csrc, name)), name
+    hips = [n for n in listed if n.endswith(".hip")]
+    assert hips
+    reached, todo = set(), [os.path.join(csrc, n) for n in hips]
+    while todo:
+        path = todo.pop()
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), re.M):
+            target = os.path.realpath(os.path.join(os.path.dirname(path), inc))
+            if os.path.dirname(target) != csrc or target in reached:      # the public header and host/ are not kernel sources
+                continue
+            assert os.path.isfile(target), (path, inc)
+            reached.add(target)
+            todo.append(target)
+    assert reached, "the include scan found nothing"
+    missing = {os.path.basename(t) for t in reached} - listed
+    assert not missing, missing
