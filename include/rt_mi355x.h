@@ -339,6 +339,27 @@ rt_status rt_scene_set_photon_dump(rt_scene *s, const char *dat_path);
  * (*n_stored); cap counts records including [0]. */
 rt_status rt_scene_get_photons(rt_scene *s, rt_photon *out, uint32_t cap, uint32_t *n_stored);
 
+/* The tree the kernels walk for one mesh of the scene, as the host builds it at upload time (additive to ABI 4; needs no GPU and
+ * makes no HIP call): 128-byte node records -- the boxes of up to four children, one axis after the other (float lo[3][4],
+ * hi[3][4]), then four child refs (uint32: bit 31 = leaf, bits 28-30 its triangle count - 1, bits 0-27 its first triangle slot;
+ * else the index of a node record), then 16 bytes of padding; an unused child has NaN bounds and is never entered -- and the
+ * face of every triangle slot.  root_ref is a child ref (a mesh of at most four triangles is one leaf and has no node).
+ * stack_need is the largest number of traversal-stack entries a ray can hold in this tree (over root-to-leaf paths, the sum of
+ * children - 1): a scene loads when it is at most bvh_lds + bvh_spill.  bvh_lds / bvh_stack are the per-lane LDS entries of
+ * k_wavefront / of the other tracing kernels, bvh_spill the entries per thread behind either in HBM, spill_blocks x block the
+ * threads the spill buffer has room for.
+ * info is required, info->struct_size must be the caller's sizeof (anything else: RT_ERR_ARG).  nodes and slot_face may be NULL
+ * (sizes only); otherwise nodes_cap counts 128-byte records, slots_cap faces, and a too small one is RT_ERR_ARG (nothing is written then). */
+typedef struct rt_device_bvh_info {
+    uint32_t struct_size;
+    uint32_t n_nodes, n_slots;
+    uint32_t root_ref;
+    int32_t stack_need;
+    int32_t bvh_lds, bvh_stack, bvh_spill, spill_blocks, block;
+} rt_device_bvh_info;
+rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
+                                   uint32_t *slot_face, uint64_t slots_cap);
+
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
  * (maxElementsPerNode = 4, FIN/include/objects.h:143).  nodes_out needs room for 2*nf+1

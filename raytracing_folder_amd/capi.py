@@ -176,6 +176,17 @@ PLANE_BITS = {"linear": 1, "normal": 2, "albedo": 4, "alpha": 8, "object_id": 16
 PACKED_SECTIONS = ("records", "normal", "albedo", "alpha", "object_id", "variance")
 
 
+# one 128-byte node record of the tree the kernels walk (rt_scene_mesh_device_bvh): lo[axis][child], hi[axis][child], child refs
+DEVBVHNODE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("c", "<u4", 4), ("pad", "<u4", 4)])
+DEVBVH_LEAF = 0x80000000
+
+
+class DeviceBvhInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_uint32), ("n_slots", C.c_uint32), ("root_ref", C.c_uint32),
+                ("stack_need", C.c_int32), ("bvh_lds", C.c_int32), ("bvh_stack", C.c_int32), ("bvh_spill", C.c_int32),
+                ("spill_blocks", C.c_int32), ("block", C.c_int32)]
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -232,6 +243,7 @@ SYMBOLS = [
     "rt_motion_blur_create", "rt_motion_blur_destroy", "rt_motion_blur_default_params", "rt_motion_blur_tiles", "rt_motion_blur_device",
     "rt_motion_blur_host",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
+    "rt_scene_mesh_device_bvh",
 ]
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
@@ -362,6 +374,9 @@ def lib():
         _lib.rt_tiles_unpack_outputs_device.argtypes = [C.c_int, vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp]
         for name in ("rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device"):
             getattr(_lib, name).restype = C.c_int
+        # the device tree of a mesh, on the host (rt_mi355x.h: rt_scene_mesh_device_bvh)
+        _lib.rt_scene_mesh_device_bvh.argtypes = [vp, i32, vp, vp, C.c_uint64, vp, C.c_uint64]
+        _lib.rt_scene_mesh_device_bvh.restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
                      "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
@@ -1180,6 +1195,15 @@ class Scene:
         _check(lib().rt_scene_get_environment(self._h, _p(env), _p(bg)))
         return dict(nodes=nodes, materials=mats, lights=lights, meshes=meshes, textures=textures, texels=texels,
                     material_maps=maps if has_maps else None, env_map=env_map, bg_map=bg_map, env=env, bg=bg)
+
+    def mesh_device_bvh(self, index):
+        """the tree the kernels walk for mesh `index`, built on the host (no GPU): (DEVBVHNODE records, face of every triangle
+        slot, DeviceBvhInfo with root_ref, stack_need and the compiled stack sizes)"""
+        info = DeviceBvhInfo(struct_size=C.sizeof(DeviceBvhInfo))
+        _check(lib().rt_scene_mesh_device_bvh(self._h, int(index), C.byref(info), None, 0, None, 0))
+        nodes, slot_face = np.zeros(info.n_nodes, DEVBVHNODE), np.zeros(info.n_slots, np.uint32)
+        _check(lib().rt_scene_mesh_device_bvh(self._h, int(index), C.byref(info), _p(nodes), len(nodes), _p(slot_face), len(slot_face)))
+        return nodes, slot_face, info
 
     # -- GPU work -------------------------------------------------------------------------------
     def trace_rays(self, rays, shade_model=SHADE_FIN, device=0):

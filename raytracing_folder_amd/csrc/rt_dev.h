@@ -29,7 +29,7 @@
 
 #define RT_MAX_DEPTH      8      // scene-graph nesting supported on the device
 #define RT_MAX_OBJECTS    4096
-#define RT_BVH_STACK      32     // per-lane traversal stack entries (LDS) of the per-level kernels; k_wavefront keeps RT_BVH_LDS and spills behind them (below)
+#define RT_BVH_STACK      32     // per-lane traversal stack entries (LDS) of the per-level kernels, k_trace and k_photon_trace, RT_BVH_SPILL more behind them in HBM; k_wavefront keeps RT_BVH_LDS in LDS (below)
 #define RT_BLOCK          256    // threads per workgroup of the trace/shade kernels
 #ifndef RT_SUB_PHOTONS
 #define RT_SUB_PHOTONS    16     // photon slots per sub-leaf (16 or 32): a wavefront examines 64 / RT_SUB_PHOTONS sub-leaves per step
@@ -147,7 +147,7 @@ struct DevScene {
     const rt_texmap *material_maps;          // 2 per material, or NULL
     rt_texmap env_map, bg_map;
     int32_t use_uvw;
-    int32_t max_bvh_depth;       // traversal-stack entries the deepest mesh BVH can need (binary tree: its depth; four-wide: 3 per level): which tracer kernels' stacks it fits
+    int32_t max_bvh_depth;       // traversal-stack entries the deepest mesh BVH can need (the largest sum of children - 1 over a root-to-leaf path; at most RT_BVH_LDS + RT_BVH_SPILL): more than RT_BVH_LDS = the spill buffers exist
     uint32_t *bvh_spill;         // [RT_SPILL_BLOCKS * RT_BLOCK][RT_BVH_SPILL]: stack entries beyond a kernel's LDS stack; set per launch (NULL: the LDS stack always suffices)
     int32_t stochastic;          // some light has a size or some material a glossy reflection/refraction: shading draws random numbers
 };

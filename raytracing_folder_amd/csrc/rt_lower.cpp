@@ -38,6 +38,13 @@ DeviceState *find_device_state(rt_scene *s, int device)
 // triangle tests are the reference's, operation by operation, and `t < z` keeps the nearest whatever the order (only two
 // hits at EXACTLY equal t depend on it) -- so the reference's mean-split tree (rt_bvh_build, rt_scene_set_mesh: kept bit-identical
 // for whoever reads it back) is not what limits traversal any more.  slot_face: the face of every triangle slot (leaf order).
+// stack_need: the most traversal-stack entries a ray can hold in this tree -- a visited node leaves (children - 1) entries behind
+// while the ray is below it, so the maximum over root-to-leaf paths of the sum of (children - 1).  It never exceeds RT_BVH_LDS +
+// RT_BVH_SPILL, what every tracing kernel provides: binned SAH over skewed geometry (sizes in geometric progression) peels one bin
+// per binary level, far deeper than log2(n), and the collapse follows it down; when the tree does not fit it is built again with
+// SAH splits only above a lower depth and balanced halves below (28, 26, .. 0).  The last resort, halves all the way, collapsed
+// evenly (BOTH children replaced by theirs: every device level stands for two binary ones), always fits: halves over fewer
+// than 2^28 faces with leaves of four are at most 26 binary levels deep, 13 device levels of at most 3 entries each.
 static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &out, std::vector<uint32_t> &slot_face, uint32_t &root_ref, int &stack_need)
 {
     const size_t nf = m.f.size() / 3;
@@ -52,13 +59,13 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
         }
         for (int a = 0; a < 3; a++) t.c[a] = 0.5f * (t.lo[a] + t.hi[a]);
     }
+    if (nf >= 0x10000000ull) return fail(RT_ERR_LIMIT, "mesh too large");
     struct BN { float lo[3], hi[3]; int32_t left, right; uint32_t first, count; };      // binary tree: leaf when left < 0
     std::vector<BN> bn;
     std::vector<uint32_t> idx(nf);
-    for (size_t i = 0; i < nf; i++) idx[i] = (uint32_t)i;
     auto area = [](const float *lo, const float *hi) { const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2]; return 2.0f * (dx * dy + dy * dz + dz * dx); };
     struct Rec {
-        std::vector<TB> &tb; std::vector<BN> &bn; std::vector<uint32_t> &idx; decltype(area) &area;
+        std::vector<TB> &tb; std::vector<BN> &bn; std::vector<uint32_t> &idx; decltype(area) &area; int sah_depth;
         int32_t go(uint32_t b, uint32_t e, int depth)
         {
             BN n;
@@ -75,7 +82,7 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
             // 201.1, 4: 15.51 / 22.22 / 196.5, 6: 15.62 / 22.63 / 202.6, 8: 15.87 / 23.65 / 213.6), its triangles by face id
             if (e - b <= 4) { std::sort(idx.begin() + b, idx.begin() + e); return me; }
             uint32_t mid = 0;
-            if (depth < 28) {
+            if (depth < sah_depth) {
                 // binned SAH over the centroids, 16 bins per axis
                 const int NB = 16;
                 float best = 3.0e38f; int best_axis = -1, best_bin = 0;
@@ -133,24 +140,25 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
             bn[me].left = l; bn[me].right = r;
             return me;
         }
-    } rec{tb, bn, idx, area};
-    const int32_t root = rec.go(0, (uint32_t)nf, 0);
+    };
     auto leafref = [](uint32_t off, uint32_t cnt) { return 0x80000000u | ((cnt - 1) << 28) | (off & 0x0FFFFFFFu); };
-    slot_face = idx;
-    if (nf >= 0x10000000ull) return fail(RT_ERR_LIMIT, "mesh too large");
-    int max_levels = 0;
     // four-wide: a device node holds up to four descendants of the binary node it stands for -- starting from its two children, the
     // internal one with the largest surface is replaced by its own two children until there are four (or only leaves)
+    // (evenly: both children replaced by theirs, see above.)  held: the stack entries of a ray that arrives at this node
     struct Col {
-        std::vector<BN> &bn; std::vector<DevBvhNode> &out; decltype(area) &area; decltype(leafref) &leafref; int &max_levels;
-        uint32_t go(int32_t id, int level)
+        std::vector<BN> &bn; std::vector<DevBvhNode> &out; decltype(area) &area; decltype(leafref) &leafref; bool evenly; int &need;
+        uint32_t go(int32_t id, int held)
         {
-            if (level > max_levels) max_levels = level;
             const uint32_t me = (uint32_t)out.size();
             out.push_back(DevBvhNode{});
             int32_t ch[4]; int n = 0;
-            ch[n++] = bn[id].left; ch[n++] = bn[id].right;
-            while (n < 4) {
+            if (evenly) {
+                for (const int32_t c : {bn[id].left, bn[id].right}) {
+                    if (bn[c].left >= 0) { ch[n++] = bn[c].left; ch[n++] = bn[c].right; }
+                    else ch[n++] = c;
+                }
+            } else { ch[n++] = bn[id].left; ch[n++] = bn[id].right; }
+            while (!evenly && n < 4) {
                 int pick = -1; float big = -1.0f;
                 for (int i = 0; i < n; i++) if (bn[ch[i]].left >= 0) { const float s = area(bn[ch[i]].lo, bn[ch[i]].hi); if (s > big) { big = s; pick = i; } }
                 if (pick < 0) break;
@@ -159,6 +167,8 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
                 ch[pick] = bn[c].left; ch[pick + 1] = bn[c].right;
                 n++;
             }
+            held += n - 1;
+            if (held > need) need = held;
             DevBvhNode d;
             memset(&d, 0, sizeof d);
             const float nan = std::nanf("");
@@ -166,14 +176,54 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
                 for (int a = 0; a < 3; a++) { d.lo[a][i] = i < n ? bn[ch[i]].lo[a] : nan; d.hi[a][i] = i < n ? bn[ch[i]].hi[a] : nan; }
                 if (i >= n) d.c[i] = leafref(0, 1);
                 else if (bn[ch[i]].left < 0) d.c[i] = leafref(bn[ch[i]].first, bn[ch[i]].count);
-                else d.c[i] = go(ch[i], level + 1);
+                else d.c[i] = go(ch[i], held);
             }
             out[me] = d;
             return me;
         }
-    } col{bn, out, area, leafref, max_levels};
-    if (bn[root].left < 0) { root_ref = leafref(bn[root].first, bn[root].count); stack_need = 0; }
-    else { root_ref = col.go(root, 1); stack_need = 3 * max_levels; }
+    };
+    for (int sah_depth = 28; ; sah_depth -= 2) {
+        bn.clear(); out.clear();
+        for (size_t i = 0; i < nf; i++) idx[i] = (uint32_t)i;
+        Rec rec{tb, bn, idx, area, sah_depth};
+        const int32_t root = rec.go(0, (uint32_t)nf, 0);
+        stack_need = 0;
+        Col col{bn, out, area, leafref, sah_depth == 0, stack_need};
+        if (bn[root].left < 0) root_ref = leafref(bn[root].first, bn[root].count);
+        else root_ref = col.go(root, 0);
+        if (stack_need <= RT_BVH_LDS + RT_BVH_SPILL) break;
+        if (sah_depth == 0) return fail(RT_ERR_LIMIT, "the BVH can need %d traversal-stack entries, the device provides %d", stack_need, RT_BVH_LDS + RT_BVH_SPILL);      // not reached: see above
+    }
+    slot_face = idx;
+    return RT_OK;
+}
+
+// the tree of one mesh as upload_scene would build it, for whoever wants to look at it on the host (no device, no HIP call)
+extern "C" rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
+                                              uint32_t *slot_face, uint64_t slots_cap)
+{
+    if (!s || !info) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: NULL argument");
+    if (info->struct_size != sizeof(rt_device_bvh_info))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: rt_device_bvh_info.struct_size is %u, this library's is %zu", info->struct_size, sizeof(rt_device_bvh_info));
+    std::vector<DevBvhNode> bn;
+    std::vector<uint32_t> faces;
+    uint32_t root_ref = 0;
+    int need = 0;
+    {
+        std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: mesh %d was never set", mesh);
+        rt_status st = build_sah_bvh(s->data.meshes[mesh], bn, faces, root_ref, need);
+        if (st) return st;
+    }
+    // both capacities before anything is written: a refused call leaves info and both buffers as they were
+    if (nodes && nodes_cap < bn.size()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, bn.size());
+    if (slot_face && slots_cap < faces.size()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, faces.size());
+    info->n_nodes = (uint32_t)bn.size(); info->n_slots = (uint32_t)faces.size();
+    info->root_ref = root_ref; info->stack_need = need;
+    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
+    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
+    if (nodes) memcpy(nodes, bn.data(), bn.size() * sizeof(DevBvhNode));
+    if (slot_face) memcpy(slot_face, faces.data(), faces.size() * 4);
     return RT_OK;
 }
 
@@ -269,7 +319,8 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         int depth = 0;
         std::vector<uint32_t> slot_face;
         if ((st = build_sah_bvh(m, bn, slot_face, root_ref, depth))) return st;
-        // (the smallest LDS stack of any tracing kernel is RT_BVH_LDS entries; RT_BVH_SPILL more per thread wait in HBM: spill buffers below)
+        // (the smallest LDS stack of any tracing kernel is RT_BVH_LDS entries; RT_BVH_SPILL more per thread wait in HBM: spill buffers
+        // below.  The builder keeps every tree within that: this only guards the kernels against a builder that does not.)
         if (depth > RT_BVH_LDS + RT_BVH_SPILL) return fail(RT_ERR_LIMIT, "mesh %zu: the BVH can need %d traversal-stack entries, the device provides %d", mi, depth, RT_BVH_LDS + RT_BVH_SPILL);
         max_depth = std::max(max_depth, depth);
         const size_t nf = m.f.size() / 3;

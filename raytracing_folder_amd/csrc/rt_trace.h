@@ -239,7 +239,7 @@ __device__ __forceinline__ M9 cld9(const float *p) { M9 r; for (int i = 0; i < 9
 // A thread's BVH traversal stack: `cap` entries in LDS (entry i of this thread at lds[i * RT_BLOCK]) and RT_BVH_SPILL more in
 // HBM behind them (spill, this thread's own 64 bytes; NULL when the scene's trees cannot outgrow the LDS part -- the host
 // checks DevScene::max_bvh_depth against cap + RT_BVH_SPILL).  The spill part is touched only by a traversal that is
-// deeper than the LDS part: a four-wide node can leave three entries per level.
+// deeper than the LDS part: a four-wide node leaves up to three entries behind.
 typedef __attribute__((address_space(3))) uint32_t lds_u32;      // the LDS part is addressed as LDS (ds_read / ds_write), never through flat instructions
 struct BvhStack { lds_u32 *lds; uint32_t *spill; uint32_t cap; };
 __device__ __forceinline__ BvhStack bvh_stack(uint32_t *lds_base, uint32_t cap, uint32_t *spill_base)

@@ -34,6 +34,7 @@ def test_struct_sizes_match_header():
     assert p.threshold == np.float32(1e-3) and p.gamma == 2.2 and p.knn_radius == 1.0
     assert (p.photon_count, p.photon_bounce) == (1000000, 8)       # MAX_NUM_OF_PHOTON, PHOTON_BOUNCE (FIN/main.cpp:27,29)
     assert C.sizeof(capi.SetupMs) == 5 * 8
+    assert C.sizeof(capi.DeviceBvhInfo) == 10 * 4 and capi.DEVBVHNODE.itemsize == 128      # rt_device_bvh_info, one node record
 
 
 def test_xml_loader_reproduces_reference_transforms(gold):
