@@ -749,7 +749,8 @@ rt_status rt_denoise_var_host(int device, int32_t w, int32_t h, const rt_denoise
  *      x_new = up x (-dir), up, z_new = -dir, M the matrix with these as its columns -- the pixel's representative ray goes
  *      through s(x, y) = (b.x + (x + 0.5) u, b.y + (y + 0.5) v, -l): the centre of the area its Halton-jittered samples
  *      cover.  World point: P = pos + z_p * normalize(M s).  `dof` is ignored: z of a depth-of-field frame is measured from a
- *      point of the lens, so P -- and with it the reprojection -- is off by at most dof.
+ *      point of the lens, so P -- and with it the reprojection -- is off by at most dof.  To have both a lens and an exact
+ *      reprojection, render with dof = 0 and defocus the final plane with the stage of "depth of field" below.
  *   3. Reprojection into the STORED camera (primed: the camera of the frame the history holds):
  *      q = (x_new', up', z_new') . (P - pos'); no history if q.z >= 0; s' = q * (-l' / q.z);
  *      fx = (s'.x - b'.x) / u' - 0.5, fy = (s'.y - b'.y) / v' - 0.5; z_exp = |P - pos'|.
@@ -826,7 +827,7 @@ rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_p
  * a pixel centre: fx = x, fy = y means "did not move"), z_exp the expected depth of that point measured from the previous
  * camera.  Definition:
  *   a. World point: step 2 of "temporal accumulation", unchanged: P = pos + z_p * normalize(M s(x, y)) from this frame's camera
- *      (`dof` is ignored, with the same error).
+ *      (`dof` is ignored, with the same error; "depth of field" below is the way to a lens with exact motion vectors).
  *   b. Node transform.  i = object_id[p]; the ancestor chain of i runs root -> ... -> i through `parent`.  X_obj = TransformTo
  *      down the chain of the CURRENT nodes (per node itm (X - pos), from the root downwards); P_prev = TransformFrom up the chain
  *      of the PREVIOUS nodes (per node tm X + pos, from node i up to the root).  The two chains are composed on the host in
@@ -1163,6 +1164,98 @@ rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_m
                                 const rt_motion_blur_planes *device_planes, int sync);
 /* The planes are HOST arrays: upload, run, download. */
 rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blur_params *p, const rt_motion_blur_planes *host_planes);
+
+/* ---- depth of field (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are unchanged) ----
+ * The stage between the denoise / temporal accumulation and "motion blur": the lens, in image space.  rt_camera.dof rendered as a
+ * lens (a disk of radius dof at the camera position, focused at focaldist) is the noisiest part of a 4 spp frame, smears the
+ * first-hit planes every other stage uses as guides, and moves the point z is measured from.  Rendered pinhole (dof = 0) and
+ * defocused here from the exact z plane, the chain keeps crisp guides and an exact reprojection.  The circle of confusion is the
+ * renderer's own lens model, so the result is comparable with a lens render.  The reference has no counterpart.
+ * Inputs, row-major and W x H: rgb_linear (float x 3), z (float, the render's depth plane: distance along the pixel's ray, >= 1e30 =
+ * nothing hit) and the frame's rt_camera, of which only fov, focaldist, dof, width and height are used.  Parameters: max_coc (K),
+ * samples (N), depth_extent, aperture_scale, focus.  Definition, in float, every operation rounded on its own (no fused multiply-
+ * add); sqrtf and the divisions are the correctly rounded ones; no transcendental function runs on the device:
+ *   0. Host set-up.  fd = focus, or focaldist when focus is 0, as a float; in double, from the floats widened,
+ *      A = (aperture_scale * |dof| * H) / (2 * fd * tan(fov / 2 * (pi / 180))), rounded to float once: the radius in pixels of a
+ *      point at infinity.  l, u, v, b are the camera quantities of "temporal accumulation" step 2 (l = focaldist there: cos(theta)
+ *      below does not depend on it).
+ *   1. Circle of confusion of the pixel p = (x, y): sx = b.x + ((float)x + 0.5f) * u, sy = b.y + ((float)y + 0.5f) * v,
+ *      cos(theta) = l / sqrtf((sx * sx + sy * sy) + l * l); the axial depth D = max(z * cos(theta), 1e-6f); the signed radius
+ *      c = A * (1 - fd / D), negative: nearer than the focus.  A z that is not finite, is <= 0 or is >= 1e30 counts as infinitely
+ *      far: c = A and D = 1e30f.  r = min(|c|, (float)K).
+ *   2. Tile max.  K x K tiles from (0, 0), partial ones at the right and bottom: TX = ceil(W / K) by TY = ceil(H / K).  A tile's
+ *      value is the largest r of its pixels (a float max is associative: any reduction order gives the same bits).
+ *   3. Neighbour max.  Per tile, the largest tile-max value over the 3 x 3 tiles around it; tiles outside the grid are skipped.
+ *      This is R.
+ *   4. Early out.  R < 0.5f: out[p] = rgb[p] bit for bit -- a frame with dof = 0, aperture_scale = 0 or everything in focus comes
+ *      back byte-identical.
+ *   5. Gather, otherwise: scatter-as-gather in one layer.  rgb[p] with a channel that is not finite: out[p] = rgb[p].
+ *      The tap table: N unit-disk offsets of a Vogel spiral, rho_i = sqrt((i + 0.5) / N), phi_i = i * pi * (3 - sqrt(5)),
+ *      (ox_i, oy_i) = (rho_i cos(phi_i), rho_i sin(phi_i)), computed on the host in double and rounded to float (rt_dof_taps
+ *      returns these bits).  Per pixel the table is turned by j quarter turns, j = {0, 2, 3, 1}[(y & 1) * 2 + (x & 1)]:
+ *      (ox, oy), (-oy, ox), (-ox, -oy), (oy, -ox) for j = 0, 1, 2, 3 -- exact.  Taps i = 0 .. N-1, in this order:
+ *        the tap pixel s = (floorf(((float)x + R * ox) + 0.5f), floorf(((float)y + R * oy) + 0.5f)).
+ *      A tap outside the image, on p itself, or with a colour channel that is not finite, has weight 0.  Otherwise, with
+ *      d = sqrtf(dx * dx + dy * dy) the distance of the two pixel centres and rp = r of p, rs = r of s:
+ *        behind = min(max((D_s - D_p) / (depth_extent * max(min(D_s, D_p), 1e-6f)), 0), 1)
+ *        r_e    = max(rs + behind * (min(rs, rp) - rs), 0.5f)
+ *        cov    = min(max((r_e - d) + 0.5f, 0), 1)
+ *        w_i    = (((R * R) / (float)N) * cov) / (r_e * r_e)
+ *      -- the tap's share of the gathered disk's area times the energy density of its own disk; a tap that lies behind p cannot
+ *      spread further over p than p's own blur, so an in-focus foreground stays sharp against a blurred background.
+ *      The centre: w_p = 1 / (q * q), q = max(rp, 0.5f), on rgb[p].  Per channel, sums from the centre term on, taps in order:
+ *        out[p] = (w_p * rgb[p] + sum w_i * rgb[s_i]) / (w_p + sum w_i)
+ *      If no tap has a weight > 0 (that is, cov > 0): out[p] = rgb[p] bit for bit.
+ *      Settled constants: N = 32 by default (the spiral then has a tap per 25 pixels of the largest default disk, K = 16, and
+ *      the quarter turns quadruple that over a 2 x 2 block); a half-pixel linear edge on the disks (the + 0.5f of cov); 0.5f as
+ *      the floor of every radius (a sharp pixel is a disk of one pixel's area to within pi / 4).
+ *   6. No atomics, fixed orders: byte-identical outputs for identical inputs on one build.  The weights are normalised: a frame
+ *      of one colour keeps it to rounding whatever z is.  out must NOT be rgb_linear (the gather reads neighbours), and no two
+ *      planes may overlap.  Products that overflow float (colours near FLT_MAX) are outside the definition.
+ * The stage's limit: it has ONE layer.  What a blurred foreground hides is not in the frame and is not recovered -- the background
+ * seen through the soft edge of a near object is what lies beside it, not behind it -- and a blurred foreground over a sharp
+ * background is an approximation by normalised weights.
+ * rt_dof owns the (c, D) plane (8 bytes a pixel) and the two tile planes of one W x H stream of frames on one device, sized for the
+ * smallest K, so the device entry never allocates.  Calls on one rt_dof are ordered on the GPU one behind the other, whatever
+ * their streams.
+ * Everything is checked before the GPU is touched and is RT_ERR_ARG: NULL arguments, a struct_size that is not the caller's sizeof,
+ * max_coc outside 2..32, samples outside 8..64, depth_extent not finite or < 1e-3, aperture_scale not finite or negative, focus
+ * not 0 and not in (0, 1e20], a NULL rgb_linear, z or out, a camera whose fov is not in (0, 180), whose dof is not finite, whose
+ * focaldist (used when focus is 0) is not in (0, 1e20], whose size is <= 0 or differs from the rt_dof's, or whose A is not finite,
+ * planes that overlap.  More than 2^30 pixels: RT_ERR_LIMIT.  Then, without a gfx950 device: RT_ERR_NO_DEVICE (there is no CPU
+ * path). */
+typedef struct rt_dof rt_dof;
+typedef struct rt_dof_params {
+    uint32_t struct_size;
+    int32_t  max_coc;           /* 16   : K, the tile size and the largest radius of a circle of confusion in pixels, 2..32 */
+    int32_t  samples;           /* 32   : N, taps per pixel, 8..64                                                          */
+    float    depth_extent;      /* 0.05 : the relative depth difference over which `behind` rises from 0 to 1               */
+    float    aperture_scale;    /* 1    : multiplies the camera's dof; 0 switches the stage off                             */
+    float    focus;             /* 0    : the camera's focaldist; otherwise the distance in focus (a focus pull without a new render) */
+} rt_dof_params;
+typedef struct rt_dof_planes {
+    uint32_t struct_size;
+    const float *rgb_linear;
+    const float *z;
+    float *out;                 /* not rgb_linear */
+    float *out_coc;             /* optional: float W*H, the signed UNCLAMPED c of each pixel */
+    float *out_tiles;           /* optional: float TX*TY, R of each tile                     */
+} rt_dof_planes;
+/* w, h <= 0 or out == NULL: RT_ERR_ARG; more than 2^30 pixels: RT_ERR_LIMIT; no gfx950 device: RT_ERR_NO_DEVICE */
+rt_status rt_dof_create(int device, int32_t w, int32_t h, rt_dof **out);
+/* NULL is ignored; waits for the work that still uses it */
+void      rt_dof_destroy(rt_dof *d);
+void      rt_dof_default_params(rt_dof_params *p);
+/* DIAGNOSTIC, needs no device: the tile grid of step 2, *tx = TX and *ty = TY (either may be NULL) */
+rt_status rt_dof_tiles(int32_t w, int32_t h, int32_t max_coc, int32_t *tx, int32_t *ty);
+/* DIAGNOSTIC, needs no device: the tap table of step 5 for N = samples (8..64), xy[2 * i] = ox_i and xy[2 * i + 1] = oy_i */
+rt_status rt_dof_taps(int32_t samples, float *xy);
+/* The planes are DEVICE pointers on the rt_dof's device; the kernels are enqueued on `hip_stream` (NULL = the device's legacy null
+ * stream) and the call returns without waiting for them unless `sync` is non-zero. */
+rt_status rt_dof_device(rt_dof *d, void *hip_stream, const rt_camera *cam, const rt_dof_params *p,
+                        const rt_dof_planes *device_planes, int sync);
+/* The planes are HOST arrays: upload, run, download. */
+rt_status rt_dof_host(rt_dof *d, const rt_camera *cam, const rt_dof_params *p, const rt_dof_planes *host_planes);
 
 /* ---- single-stage entry points (used by parity tests and by hosts that keep their own
  *      RenderPixel): inputs/outputs are HOST arrays, the work runs on the GPU -------------- */

@@ -162,6 +162,22 @@ class MotionBlurPlanes(C.Structure):
         super().__init__(struct_size=C.sizeof(MotionBlurPlanes), **planes)
 
 
+class DofParams(C.Structure):
+    """rt_dof_params: depth of field between the denoise and motion blur (rt_dof_default_params fills max_coc 16, samples 32,
+    depth_extent 0.05, aperture_scale 1, focus 0 = the camera's focaldist)"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_coc", C.c_int32), ("samples", C.c_int32), ("depth_extent", C.c_float),
+                ("aperture_scale", C.c_float), ("focus", C.c_float)]
+
+
+class DofPlanes(C.Structure):
+    """rt_dof_planes: the inputs and outputs of one defocused frame.  out may not be rgb_linear; out_coc and out_tiles are optional."""
+    _fields_ = [("struct_size", C.c_uint32), ("rgb_linear", C.c_void_p), ("z", C.c_void_p), ("out", C.c_void_p), ("out_coc", C.c_void_p),
+                ("out_tiles", C.c_void_p)]
+
+    def __init__(self, **planes):
+        super().__init__(struct_size=C.sizeof(DofPlanes), **planes)
+
+
 # rt_tonemap_params.op (include/rt_mi355x.h)
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 TONEMAP_OPERATORS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
@@ -242,6 +258,7 @@ SYMBOLS = [
     "rt_bloom_create", "rt_bloom_destroy", "rt_bloom_default_params", "rt_bloom_plan", "rt_bloom_device", "rt_bloom_host",
     "rt_motion_blur_create", "rt_motion_blur_destroy", "rt_motion_blur_default_params", "rt_motion_blur_tiles", "rt_motion_blur_device",
     "rt_motion_blur_host",
+    "rt_dof_create", "rt_dof_destroy", "rt_dof_default_params", "rt_dof_tiles", "rt_dof_taps", "rt_dof_device", "rt_dof_host",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
     "rt_scene_mesh_device_bvh",
 ]
@@ -367,6 +384,18 @@ def lib():
         _lib.rt_motion_blur_device.argtypes = [vp, vp, vp, vp, C.c_int]
         _lib.rt_motion_blur_host.argtypes = [vp, vp, vp]
         for name in ("rt_motion_blur_create", "rt_motion_blur_tiles", "rt_motion_blur_device", "rt_motion_blur_host"):
+            getattr(_lib, name).restype = C.c_int
+        # depth of field (rt_mi355x.h: "depth of field")
+        _lib.rt_dof_create.argtypes = [C.c_int, i32, i32, C.POINTER(vp)]
+        _lib.rt_dof_destroy.argtypes = [vp]
+        _lib.rt_dof_destroy.restype = None
+        _lib.rt_dof_default_params.argtypes = [vp]
+        _lib.rt_dof_default_params.restype = None
+        _lib.rt_dof_tiles.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        _lib.rt_dof_taps.argtypes = [i32, vp]
+        _lib.rt_dof_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
+        _lib.rt_dof_host.argtypes = [vp, vp, vp, vp]
+        for name in ("rt_dof_create", "rt_dof_tiles", "rt_dof_taps", "rt_dof_device", "rt_dof_host"):
             getattr(_lib, name).restype = C.c_int
         # the packed planes of the multi-GPU exchange (rt_mi355x.h: "packed planes")
         _lib.rt_tiles_packed_planes_size.argtypes = [i32, i32, vp, C.c_uint32, vp, vp, vp]
@@ -697,6 +726,13 @@ def _copy_camera(cam):
     return c
 
 
+def _pinhole(cam):
+    """a copy of `cam` without its lens: what a frame is rendered with when a DepthOfField stage stands in for it"""
+    c = _copy_camera(cam)
+    c.dof = 0.0
+    return c
+
+
 class History(_Handle):
     """rt_history: the accumulated frames of one W x H stream on one device (the definition: rt_mi355x.h, "temporal
     accumulation").  Every accumulate blends a new frame into what the earlier ones left, reprojected from the camera of the
@@ -976,6 +1012,67 @@ class MotionBlur(_Handle):
         pl = MotionBlurPlanes(rgb_linear=linear_ptr, motion=motion_ptr, z=z_ptr, out=out_ptr, out_tiles=tiles_ptr)
         p = motion_blur_params(**params)
         _check(lib().rt_motion_blur_device(self._h, _stream_handle(stream), C.byref(p), C.byref(pl), 1 if sync else 0))
+
+
+def dof_params(**kw):
+    """rt_dof_default_params, then the keywords: max_coc, samples, depth_extent, aperture_scale, focus"""
+    return _fill_params(DofParams, "rt_dof_default_params", ("max_coc", "samples", "depth_extent", "aperture_scale", "focus"), ("max_coc", "samples"), kw,
+                        "depth of field")
+
+
+def dof_tiles(w, h, max_coc=16):
+    """rt_dof_tiles: (TX, TY), the grid of max_coc x max_coc tiles over a w x h frame; needs no device"""
+    tx, ty = C.c_int32(), C.c_int32()
+    _check(lib().rt_dof_tiles(int(w), int(h), int(max_coc), C.byref(tx), C.byref(ty)))
+    return tx.value, ty.value
+
+
+def dof_taps(samples=32):
+    """rt_dof_taps: the stage's tap table, float32 (samples, 2) unit-disk offsets (ox, oy); needs no device"""
+    xy = np.zeros((max(int(samples), 0), 2), np.float32)
+    _check(lib().rt_dof_taps(int(samples), xy.ctypes.data))
+    return xy
+
+
+class DepthOfField(_Handle):
+    """rt_dof: the depth-of-field stage of one w x h stream of frames on one device (the definition: rt_mi355x.h, "depth of
+    field"); it owns the (c, D) plane's and the tile planes' device memory.  A context manager; close() (or the end of the with
+    block) frees it."""
+
+    _destroy = "rt_dof_destroy"
+
+    def __init__(self, device, w, h):
+        self._h = C.c_void_p()
+        self.device, self.w, self.h = int(device), int(w), int(h)
+        _check(lib().rt_dof_create(self.device, self.w, self.h, C.byref(self._h)))
+
+    def apply(self, linear, z, cam, return_coc=False, return_tiles=False, **params):
+        """rt_dof_host on host arrays -- linear float32 (H, W, 3), z float32 (H, W), cam the frame's Camera (its fov, focaldist,
+        dof and size are used): the defocused plane, then -- return_coc=True -- the signed unclamped circle of confusion per
+        pixel (float32 (H, W)) and -- return_tiles=True -- R per tile (float32 (TY, TX)) as a tuple's further members.
+        params: dof_params()."""
+        linear, z = _c(linear, np.float32), _c(z, np.float32)
+        assert linear.shape == (self.h, self.w, 3) and z.shape == (self.h, self.w)
+        p = dof_params(**params)
+        out = np.empty_like(linear)
+        coc = np.empty((self.h, self.w), np.float32) if return_coc else None
+        tiles = None
+        if return_tiles:
+            tx, ty = dof_tiles(self.w, self.h, p.max_coc)
+            tiles = np.empty((ty, tx), np.float32)
+        pl = DofPlanes(rgb_linear=linear.ctypes.data, z=z.ctypes.data, out=out.ctypes.data, out_coc=coc.ctypes.data if return_coc else None,
+                       out_tiles=tiles.ctypes.data if return_tiles else None)
+        _check(lib().rt_dof_host(self._h, C.byref(cam), C.byref(p), C.byref(pl)))
+        res = (out,) + ((coc,) if return_coc else ()) + ((tiles,) if return_tiles else ())
+        return res if len(res) > 1 else out
+
+    def apply_device(self, stream, cam, *, linear_ptr, z_ptr, out_ptr, coc_ptr=None, tiles_ptr=None, sync=False, **params):
+        """rt_dof_device: the same on image-sized DEVICE planes (e.g. torch tensors' data_ptr()), enqueued on `stream` (an explicit
+        stream's handle; None = the null stream of the device) without a host round trip.  out_ptr may not be linear_ptr.
+        coc_ptr: W * H floats; tiles_ptr: TX * TY floats (dof_tiles)."""
+        pl = DofPlanes(rgb_linear=linear_ptr, z=z_ptr, out=out_ptr, out_coc=coc_ptr, out_tiles=tiles_ptr)
+        p = dof_params(**params)
+        _check(lib().rt_dof_device(self._h, _stream_handle(stream), C.byref(cam), C.byref(p), C.byref(pl), 1 if sync else 0))
 
 
 def identity_map(texture=MAP_NONE):
@@ -1272,7 +1369,7 @@ class Scene:
         return out
 
     def render_denoised(self, cam, params, device=0, photon_pass=False, variance=False, exposure=None, tonemap_kw=None, bloom=None,
-                        bloom_kw=None, **denoise_kw):
+                        bloom_kw=None, depth_of_field=None, dof_kw=None, **denoise_kw):
         """render_outputs with the linear plane and the four feature planes, then denoise() of that frame guided by them
         (gamma: the render's): the same dict with "denoised" (float32 (H, W, 3), linear) and "denoised_rgb" (uint8 (H, W, 3))
         added.  denoise_kw: levels, sigma_color, sigma_normal, sigma_depth.  variance=True: the render also fills
@@ -1281,9 +1378,13 @@ class Scene:
         "display_rgb" (uint8 (H, W, 3)) is added; tonemap_kw: a dict of Exposure.tonemap's keywords (operator, key, ...).
         bloom: a Bloom of the camera's size on `device` -- the denoised plane is bloomed first (relative to the scale `exposure`
         holds from the frame before; bloom_kw: a dict of Bloom.apply's keywords), "bloomed" (float32 (H, W, 3)) is added and
-        "display_rgb" is made from it."""
+        "display_rgb" is made from it.
+        depth_of_field: a DepthOfField of the camera's size on `device` -- the frame is rendered PINHOLE (a copy of `cam` with
+        dof = 0: exact planes) and the denoised plane is defocused from "z" with cam's own dof (dof_kw: a dict of
+        DepthOfField.apply's keywords); "defocused" (float32 (H, W, 3)) and "coc" (float32 (H, W), the signed circle of confusion
+        in pixels) are added, and bloom and tone mapping run on the defocused plane."""
         planes = ("linear",) + FEATURE_PLANES + (("variance",) if variance else ())
-        out = self.render_outputs(cam, params, planes=planes, device=device, photon_pass=photon_pass)
+        out = self.render_outputs(_pinhole(cam) if depth_of_field is not None else cam, params, planes=planes, device=device, photon_pass=photon_pass)
         denoise_kw.setdefault("gamma", params.gamma)
         if variance:
             out["denoised"], out["denoised_rgb"], out["denoised_variance"] = denoise(
@@ -1292,10 +1393,10 @@ class Scene:
         else:
             out["denoised"], out["denoised_rgb"] = denoise(out["linear"], out["normal"], out["albedo"], out["z"], out["object_id"],
                                                            rgb8=True, device=device, **denoise_kw)
-        return self._finish_frame(out, out["denoised"], params, None, None, bloom, bloom_kw, exposure, tonemap_kw)
+        return self._finish_frame(out, out["denoised"], params, None, None, bloom, bloom_kw, exposure, tonemap_kw, depth_of_field, dof_kw, cam)
 
     def render_temporal(self, history, cam, params, device=0, denoise=True, exposure=None, tonemap_kw=None, moving=False, clip=None,
-                        bloom=None, bloom_kw=None, motion_blur=None, motion_blur_kw=None, **kw):
+                        bloom=None, bloom_kw=None, motion_blur=None, motion_blur_kw=None, depth_of_field=None, dof_kw=None, **kw):
         """One frame of a stream of frames: render_outputs with the linear, feature and variance planes, then
         history.accumulate() of that frame (a History of the camera's size on `device`): the same dict with "accumulated" and
         "accumulated_variance" (float32 (H, W, 3)) and "history" (float32 (H, W), the per-pixel history length) added.
@@ -1319,7 +1420,10 @@ class Scene:
         render_denoised: "bloomed" is added and "display_rgb" is made from it; bloom_kw: a dict of Bloom.apply's keywords.
         motion_blur: a MotionBlur of the camera's size on `device`; needs moving=True (ValueError without it) -- the final linear
         plane is blurred along the frame's "motion" plane with its "z" (motion_blur_kw: a dict of MotionBlur.apply's keywords),
-        "motion_blurred" (float32 (H, W, 3)) is added, and bloom and tone mapping run on it."""
+        "motion_blurred" (float32 (H, W, 3)) is added, and bloom and tone mapping run on it.
+        depth_of_field: a DepthOfField of the camera's size on `device`, as in render_denoised: the frame is rendered pinhole, so
+        the planes, the reprojection and the motion vectors are exact, and the final linear plane is defocused with cam's own
+        dof ahead of the motion blur; "defocused" and "coc" are added (dof_kw: a dict of DepthOfField.apply's keywords)."""
         if motion_blur is not None and not moving:
             raise ValueError("render_temporal: motion_blur needs moving=True (the frame's motion plane)")
         photon_pass = kw.pop("photon_pass", False)
@@ -1328,7 +1432,8 @@ class Scene:
         unknown = set(kw) - set(t_kw) - set(d_kw)
         if unknown:
             raise TypeError(f"no render_temporal parameter {sorted(unknown)[0]!r}")
-        out = self.render_outputs(cam, params, planes=("linear",) + FEATURE_PLANES + ("variance",), device=device, photon_pass=photon_pass)
+        out = self.render_outputs(_pinhole(cam) if depth_of_field is not None else cam, params, planes=("linear",) + FEATURE_PLANES + ("variance",),
+                                  device=device, photon_pass=photon_pass)
         if moving:
             out["motion"], known, remember = self._motion_since(history, cam, out["z"], out["object_id"], device)
             if known:
@@ -1347,12 +1452,17 @@ class Scene:
                 out["accumulated"], out["normal"], out["albedo"], out["z"], out["object_id"], rgb8=True, device=device,
                 variance=out["accumulated_variance"], gamma=params.gamma, **d_kw)
         return self._finish_frame(out, out["denoised" if denoise else "accumulated"], params, motion_blur, motion_blur_kw, bloom, bloom_kw,
-                                  exposure, tonemap_kw)
+                                  exposure, tonemap_kw, depth_of_field, dof_kw, cam)
 
     @staticmethod
-    def _finish_frame(out, final, params, motion_blur, motion_blur_kw, bloom, bloom_kw, exposure, tonemap_kw):
-        """the tail of render_denoised and render_temporal on the frame's final linear plane: motion blur, then bloom, then tone
-        mapping, each only where its object is given; adds "motion_blurred", "bloomed" and "display_rgb" to `out`"""
+    def _finish_frame(out, final, params, motion_blur, motion_blur_kw, bloom, bloom_kw, exposure, tonemap_kw, depth_of_field=None, dof_kw=None,
+                      cam=None):
+        """the tail of render_denoised and render_temporal on the frame's final linear plane: depth of field (with `cam`, the
+        caller's camera and its dof), then motion blur, then bloom, then tone mapping, each only where its object is given; adds
+        "defocused" and "coc", "motion_blurred", "bloomed" and "display_rgb" to `out`"""
+        if depth_of_field is not None:
+            final, out["coc"] = depth_of_field.apply(final, out["z"], cam, return_coc=True, **(dof_kw or {}))
+            out["defocused"] = final
         if motion_blur is not None:
             final = out["motion_blurred"] = motion_blur.apply(final, out["motion"], out["z"], **(motion_blur_kw or {}))
         if bloom is not None:

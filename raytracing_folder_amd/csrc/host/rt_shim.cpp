@@ -26,7 +26,17 @@ void RenderImage::Init(int w, int h)
     rt_motion_blur_destroy(motionBlur); // tile planes are of one size
     motionBlur = nullptr;
     motionBlurred.clear();
+    rt_dof_destroy(dof);                // the (c, D) plane and the tile planes are of one size
+    dof = nullptr;
+    defocused.clear(); coc.clear();
     finalPixels = 0;
+}
+
+void RenderImage::EnableDepthOfField(const rt_dof_params *params)
+{
+    if (params) dofParams = *params;
+    else rt_dof_default_params(&dofParams);
+    dofEnabled = true;
 }
 
 void RenderImage::EnableMotionBlur(const rt_motion_blur_params *params)
@@ -66,7 +76,7 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
     rt_tonemap_params defaults;
     rt_tonemap_default_params(&defaults);
     const size_t n = (size_t)width * height;
-    const std::vector<float> *from = !denoised.empty() ? &denoised : (!accumulated.empty() ? &accumulated : &linear);
+    const std::vector<float> *from = !defocused.empty() ? &defocused : (!denoised.empty() ? &denoised : (!accumulated.empty() ? &accumulated : &linear));
     std::vector<float> smear;
     if (motionBlurEnabled && !motion.empty()) {     // along the motion plane of the last AccumulateTemporalMoving()
         if (motionBlur && motionBlurDevice != device) { rt_motion_blur_destroy(motionBlur); motionBlur = nullptr; }
@@ -96,6 +106,29 @@ bool RenderImage::ToneMap(const rt_tonemap_params *params, int device)
     if (bloomEnabled) bloomed.swap(glare);
     motionBlurred.swap(smear);          // empty again when the stage did not run
     toneMapError.clear();
+    return true;
+}
+
+static rt_camera LowerCamera(const Camera &c);
+
+// the lens over the most processed linear plane the image holds, from the z-buffer
+bool RenderImage::DepthOfField(const Camera &c, int device)
+{
+    defocused.clear(); coc.clear();
+    if (!dofEnabled || !linearEnabled) { dofError = "DepthOfField() needs EnableDepthOfField() and EnableLinear() before the render"; return false; }
+    if (!jobs.empty()) { dofError = "DepthOfField() while the render is still running"; return false; }
+    if (dof && dofDevice != device) { rt_dof_destroy(dof); dof = nullptr; }
+    if (!dof && rt_dof_create(device, width, height, &dof) != RT_OK) { dofError = rt_last_error(); return false; }
+    dofDevice = device;
+    rt_camera rc = LowerCamera(c);
+    rc.width = width; rc.height = height;
+    const size_t n = (size_t)width * height;
+    const std::vector<float> &from = !denoised.empty() ? denoised : (!accumulated.empty() ? accumulated : linear);
+    std::vector<float> out(n * 3), radius(n);
+    const rt_dof_planes pl = {(uint32_t)sizeof(rt_dof_planes), from.data(), zbuffer.data(), out.data(), radius.data(), nullptr};
+    if (rt_dof_host(dof, &rc, &dofParams, &pl) != RT_OK) { dofError = rt_last_error(); return false; }
+    defocused.swap(out); coc.swap(radius);
+    dofError.clear();
     return true;
 }
 
@@ -171,6 +204,7 @@ bool RenderImage::Accumulate(const Camera &c, const Camera *prev, const rt_node 
         motion.clear();
     }
     clipped.swap(mask);
+    defocused.clear(); coc.clear();     // of the plane before this one
     accumulated.swap(out); accumulatedVariance.swap(outVar); historyLength.swap(len);
     temporalError.clear();
     return true;
@@ -217,7 +251,7 @@ void RenderImage::EnableLinear()
 
 bool RenderImage::DenoiseGuided(const rt_denoise_params *params, float k_sigma, int device)
 {
-    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
+    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear(); defocused.clear(); coc.clear();
     if (!linearEnabled || !featuresEnabled || !varianceEnabled) {
         denoiseError = "DenoiseGuided() needs EnableLinear(), EnableFeatures() and EnableVariance() before the render";
         return false;
@@ -240,7 +274,7 @@ bool RenderImage::DenoiseGuided(const rt_denoise_params *params, float k_sigma, 
 
 bool RenderImage::Denoise(const rt_denoise_params *params, int device)
 {
-    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear();
+    denoised.clear(); denoisedImg.clear(); denoisedVariance.clear(); defocused.clear(); coc.clear();
     if (!linearEnabled || !featuresEnabled) { denoiseError = "Denoise() needs EnableLinear() and EnableFeatures() before the render"; return false; }
     if (!jobs.empty()) { denoiseError = "Denoise() while the render is still running"; return false; }
     rt_denoise_params defaults;

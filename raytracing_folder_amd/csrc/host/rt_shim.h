@@ -64,6 +64,14 @@ class RenderImage {
     rt_motion_blur_params motionBlurParams = {};
     rt_motion_blur *motionBlur = nullptr;
     int motionBlurDevice = 0;
+    // opt-in (EnableDepthOfField): DepthOfField()'s outputs -- the defocused linear plane and the signed circle of confusion per
+    // pixel -- and the rt_dof that owns the stage's device planes
+    std::vector<float> defocused, coc;
+    bool dofEnabled = false;
+    rt_dof_params dofParams = {};
+    rt_dof *dof = nullptr;
+    int dofDevice = 0;
+    std::string dofError;
     int width = 0, height = 0;
     std::vector<rt_job *> jobs;        // progress sources while a render is live (one job per device)
     int finalPixels = 0;
@@ -73,7 +81,7 @@ public:
     RenderImage() = default;
     RenderImage(const RenderImage &) = delete;
     RenderImage &operator=(const RenderImage &) = delete;
-    ~RenderImage() { rt_history_destroy(history); rt_motion_blur_destroy(motionBlur); rt_bloom_destroy(bloom); rt_exposure_destroy(exposure); }
+    ~RenderImage() { rt_history_destroy(history); rt_dof_destroy(dof); rt_motion_blur_destroy(motionBlur); rt_bloom_destroy(bloom); rt_exposure_destroy(exposure); }
     void Init(int w, int h);
     int GetWidth() const { return width; }
     int GetHeight() const { return height; }
@@ -186,6 +194,22 @@ public:
     bool MotionBlurEnabled() const { return motionBlurEnabled; }
     float *GetMotionBlurred() { return motionBlurred.empty() ? nullptr : motionBlurred.data(); }    // linear float RGB
     bool SaveMotionBlurredImage(const char *filename) const { return !motionBlurred.empty() && WritePFM(filename, motionBlurred.data(), width, height); }   // PFM
+    // Depth of field (rt_mi355x.h, "depth of field"): the lens as an image-space stage.  Render with the scene camera's dof set to 0
+    // (exact planes), run Denoise() / AccumulateTemporal() as wanted, then DepthOfField(camera) with the camera WITH its dof: the
+    // most processed linear plane the image holds -- the denoised one, else the accumulated one, else the render's -- is defocused
+    // from the z-buffer.  From then on ToneMap() starts from the defocused plane (ahead of motion blur, bloom and the curve),
+    // until a new Denoise(), accumulation or Init() discards it: the order of stages is denoise / accumulate -> depth of field
+    // -> motion blur -> bloom -> tone map.  Needs EnableDepthOfField() and EnableLinear() before the render.  params == NULL: the
+    // defaults of rt_dof_default_params.  The rt_dof is created by the first call, on `device`, and lives until the image is
+    // destroyed, Init() changes the size or another device is named.  false + DepthOfFieldError() on failure.  GetDefocused() is
+    // linear float RGB and GetCoc() the signed circle of confusion in pixels, both NULL until a call has succeeded.
+    void EnableDepthOfField(const rt_dof_params *params = nullptr);
+    bool DepthOfFieldEnabled() const { return dofEnabled; }
+    bool DepthOfField(const Camera &camera, int device = 0);
+    const std::string &DepthOfFieldError() const { return dofError; }
+    float *GetDefocused() { return defocused.empty() ? nullptr : defocused.data(); }            // linear float RGB
+    float *GetCoc() { return coc.empty() ? nullptr : coc.data(); }                              // float per pixel
+    bool SaveDefocusedImage(const char *filename) const { return !defocused.empty() && WritePFM(filename, defocused.data(), width, height); }   // PFM
     int GetNumRenderedPixels() const;
     bool IsRenderDone() const { return GetNumRenderedPixels() >= width * height; }
     void ComputeZBufferImage();        // scene.h:591-613

@@ -1,5 +1,5 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip): every rtk_* function, the requests they take and the
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
@@ -200,6 +200,24 @@ struct MotionBlurRequest {
     float *tile_max, *tile_nmax;
 };
 
+// One defocused width x height frame (rt_dof.hip; the definition: rt_mi355x.h, "depth of field").  The planes are the caller's device
+// pointers (out_coc and out_tiles may be NULL), the parameters are validated by the caller.  A and focus are step 0's A and focus
+// distance; bx, by, u, v, l the camera quantities of step 1 (camera_setup's).  taps: step 5's table on the HOST, 2 N floats -- it
+// travels in the kernel argument.  coc: the rt_dof's (c, D) plane, one float2 per pixel; tile_max and tile_nmax: its two tile
+// planes, one float per tile each (tiles_x * tiles_y of them for this call's K).
+#define RT_DOF_MAX_TAPS 64
+struct DofRequest {
+    int width, height, K, N;
+    int tiles_x, tiles_y;               // ceil(width / K), ceil(height / K)
+    float A, focus, depth_extent;
+    float bx, by, u, v, l;
+    const float *taps;
+    const float *rgb_linear, *z;
+    float *out, *out_coc, *out_tiles;
+    float2 *coc;
+    float *tile_max, *tile_nmax;
+};
+
 // ---- rt_kernels.hip: the kernels that shade -----------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -270,6 +288,10 @@ hipError_t rtk_launch_bloom(hipStream_t st, const BloomRequest &R);
 // ---- rt_motion_blur.hip: motion blur between the denoise and bloom ----------------------------------------------------------
 // on `st`: k_mblur_tile_max, k_mblur_neighbour_max, k_mblur_gather
 hipError_t rtk_launch_motion_blur(hipStream_t st, const MotionBlurRequest &R);
+
+// ---- rt_dof.hip: depth of field between the denoise and motion blur ---------------------------------------------------------
+// on `st`: k_dof_coc, k_dof_neighbour_max, k_dof_gather
+hipError_t rtk_launch_dof(hipStream_t st, const DofRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

@@ -1,5 +1,5 @@
 // rt_post.cpp -- the image-space stages of the C ABI in include/rt_mi355x.h: denoising, temporal accumulation, motion vectors,
-// exposure and tone mapping, bloom, motion blur.  None of them knows a scene.  Every stage is the same few steps -- check the
+// exposure and tone mapping, bloom, motion blur, depth of field.  None of them knows a scene.  Every stage is the same few steps -- check the
 // versioned structs and the image size, find the device, order the stream behind the previous call on the same object, launch,
 // record -- and its host entry point is the device one between an upload and a download; the pieces they share come first.
 // There is no CPU path: without a gfx950 device the calls fail.
@@ -86,7 +86,7 @@ struct StageSync {
     rt_status wait_host() { if (pending) { HIP_TRY(hipEventSynchronize(done)); pending = false; } return RT_OK; }
 };
 
-// The objects of the stages that keep state between frames (rt_history, rt_exposure, rt_bloom, rt_motion_blur) start like
+// The objects of the stages that keep state between frames (rt_history, rt_exposure, rt_bloom, rt_motion_blur, rt_dof) start like
 // this; each adds its buffers and a release() that frees them.
 struct StageObject {
     int device = 0; int32_t w = 0, h = 0;
@@ -978,4 +978,155 @@ extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blu
                                        S.dev<float>(out), S.dev<float>(tiles)};
     if ((st = mblur_on_device(mb, nullptr, p, &dev, 1))) return st;
     return S.download({out, tiles});
+}
+
+// ---- depth of field -------------------------------------------------------------------------------------------------------
+// An rt_dof owns the (c, D) plane and the tile-max and neighbour-max planes of one W x H stream of frames on its device -- the
+// tile planes sized for K = 2, the most tiles a call can ask for -- and the event that orders a call behind the previous one on
+// the same object.
+#define RT_DOF_MIN_K 2
+#define RT_DOF_MAX_K 32
+#define RT_DOF_MIN_N 8
+#define RT_DOF_MAX_FOCUS 1e20f
+struct rt_dof : StageObject { DevBuf coc, tile_max, tile_nmax; void release() { coc.release(); tile_max.release(); tile_nmax.release(); } };
+
+static size_t dof_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
+{
+    const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
+    if (tx) *tx = x;
+    if (ty) *ty = y;
+    return (size_t)x * (size_t)y;
+}
+
+// step 5's table: a Vogel spiral in double, rounded to float once per coordinate
+static void dof_tap_table(int32_t N, float *xy)
+{
+    const double golden = M_PI * (3.0 - sqrt(5.0));
+    for (int32_t i = 0; i < N; i++) {
+        const double rho = sqrt(((double)i + 0.5) / (double)N), phi = (double)i * golden;
+        xy[2 * i] = (float)(rho * cos(phi)); xy[2 * i + 1] = (float)(rho * sin(phi));
+    }
+}
+
+extern "C" rt_status rt_dof_create(int device, int32_t w, int32_t h, rt_dof **out)
+{
+    if (!out) return fail(RT_ERR_ARG, "rt_dof_create: out is NULL");
+    *out = nullptr;
+    rt_status st = check_image_size("rt_dof_create", w, h);
+    if (st) return st;
+    return stage_create("rt_dof_create", device, w, h, out, [](rt_dof &d) {
+        const size_t bytes = dof_tiles(d.w, d.h, RT_DOF_MIN_K, nullptr, nullptr) * 4;
+        rt_status rs = d.coc.ensure((size_t)d.w * (size_t)d.h * 8);
+        if (!rs) rs = d.tile_max.ensure(bytes);
+        return rs ? rs : d.tile_nmax.ensure(bytes);
+    });
+}
+
+extern "C" void rt_dof_destroy(rt_dof *d) { stage_destroy(d); }
+
+extern "C" void rt_dof_default_params(rt_dof_params *p)
+{
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof *p;
+    p->max_coc = 16; p->samples = 32; p->depth_extent = 0.05f; p->aperture_scale = 1.0f; p->focus = 0.0f;
+}
+
+extern "C" rt_status rt_dof_tiles(int32_t w, int32_t h, int32_t max_coc, int32_t *tx, int32_t *ty)
+{
+    rt_status st = check_image_dims("rt_dof_tiles", w, h);
+    if (st) return st;
+    if (max_coc < RT_DOF_MIN_K || max_coc > RT_DOF_MAX_K) return fail(RT_ERR_ARG, "rt_dof_tiles: max_coc is %d, must be 2..32", max_coc);
+    dof_tiles(w, h, max_coc, tx, ty);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_dof_taps(int32_t samples, float *xy)
+{
+    if (!xy) return fail(RT_ERR_ARG, "rt_dof_taps: xy is NULL");
+    if (samples < RT_DOF_MIN_N || samples > RT_DOF_MAX_TAPS) return fail(RT_ERR_ARG, "rt_dof_taps: samples is %d, must be 8..64", samples);
+    dof_tap_table(samples, xy);
+    return RT_OK;
+}
+
+// everything that can be refused without a device, for both entry points; on success *A and *fd are step 0's
+static rt_status dof_check(const char *name, const rt_dof *d, const rt_camera *cam, const rt_dof_params *p, const rt_dof_planes *pl, float *A, float *fd)
+{
+    if (!cam) return fail(RT_ERR_ARG, "%s: the camera is NULL", name);
+    rt_status st = check_params_planes(name, "rt_dof_params", p, "rt_dof_planes", pl);
+    if (st) return st;
+    if (p->max_coc < RT_DOF_MIN_K || p->max_coc > RT_DOF_MAX_K) return fail(RT_ERR_ARG, "%s: max_coc is %d, must be 2..32", name, p->max_coc);
+    if (p->samples < RT_DOF_MIN_N || p->samples > RT_DOF_MAX_TAPS) return fail(RT_ERR_ARG, "%s: samples is %d, must be 8..64", name, p->samples);
+    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
+    if (!std::isfinite(p->aperture_scale) || !(p->aperture_scale >= 0.0f)) return fail(RT_ERR_ARG, "%s: aperture_scale must be finite and not negative", name);
+    if (p->focus != 0.0f && !(p->focus > 0.0f && p->focus <= RT_DOF_MAX_FOCUS)) return fail(RT_ERR_ARG, "%s: focus must be 0 (the camera's focaldist) or in (0, 1e20]", name);
+    if (!pl->rgb_linear || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, z and out are required", name);
+    if (!(cam->fov > 0.0f && cam->fov < 180.0f)) return fail(RT_ERR_ARG, "%s: the camera's fov must be in (0, 180)", name);
+    if (!std::isfinite(cam->dof)) return fail(RT_ERR_ARG, "%s: the camera's dof must be finite", name);
+    *fd = p->focus != 0.0f ? p->focus : cam->focaldist;
+    if (!(*fd > 0.0f && *fd <= RT_DOF_MAX_FOCUS)) return fail(RT_ERR_ARG, "%s: the camera's focaldist must be in (0, 1e20]", name);
+    if ((st = check_image_dims(name, cam->width, cam->height))) return st;
+    const double a = ((double)p->aperture_scale * fabs((double)cam->dof) * (double)cam->height) /
+                     (2.0 * (double)*fd * tan((double)cam->fov / 2 * (M_PI / 180)));
+    *A = (float)a;
+    if (!std::isfinite(*A)) return fail(RT_ERR_ARG, "%s: the camera's aperture in pixels (A) is not finite", name);
+    if ((st = check_image_limit(name, cam->width, cam->height))) return st;
+    const size_t n = (size_t)cam->width * (size_t)cam->height;
+    const struct { const void *p; size_t bytes; } planes[5] = {
+        {pl->rgb_linear, n * 12}, {pl->z, n * 4}, {pl->out, n * 12}, {pl->out_coc, n * 4},
+        {pl->out_tiles, dof_tiles(cam->width, cam->height, p->max_coc, nullptr, nullptr) * 4}};
+    for (int a_ = 0; a_ < 5; a_++)
+        for (int b = a_ + 1; b < 5; b++)
+            if (planes_overlap(planes[a_].p, planes[a_].bytes, planes[b].p, planes[b].bytes))
+                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
+    // what needs the object comes last: without a device there is none, and everything above is still refused by name
+    if (!d) return fail(RT_ERR_ARG, "%s: the rt_dof is NULL", name);
+    if (cam->width != d->w || cam->height != d->h)
+        return fail(RT_ERR_ARG, "%s: the camera is %d x %d, the rt_dof %d x %d", name, cam->width, cam->height, d->w, d->h);
+    return RT_OK;
+}
+
+static rt_status dof_on_device(rt_dof *d, hipStream_t st, const rt_camera *cam, float A, float fd, const rt_dof_params *p, const rt_dof_planes *pl, int sync)
+{
+    HIP_TRY(hipSetDevice(d->device));
+    DofRequest R = {};
+    R.width = d->w; R.height = d->h; R.K = p->max_coc; R.N = p->samples;
+    dof_tiles(d->w, d->h, p->max_coc, &R.tiles_x, &R.tiles_y);
+    R.A = A; R.focus = fd; R.depth_extent = p->depth_extent;
+    DevCamera dc;
+    camera_setup(*cam, dc);
+    R.bx = dc.b[0]; R.by = dc.b[1]; R.u = dc.u; R.v = dc.v; R.l = -dc.b[2];
+    float taps[2 * RT_DOF_MAX_TAPS];
+    dof_tap_table(p->samples, taps);
+    R.taps = taps;
+    R.rgb_linear = pl->rgb_linear; R.z = pl->z; R.out = pl->out; R.out_coc = pl->out_coc; R.out_tiles = pl->out_tiles;
+    std::lock_guard<std::mutex> lk(d->mu);
+    R.coc = (float2 *)d->coc.p; R.tile_max = (float *)d->tile_max.p; R.tile_nmax = (float *)d->tile_nmax.p;
+    rt_status rs = d->sync.wait(st);
+    if (rs) return rs;
+    HIP_TRY(rtk_launch_dof(st, R));
+    return d->sync.settle(st, sync);
+}
+
+extern "C" rt_status rt_dof_device(rt_dof *d, void *hip_stream, const rt_camera *cam, const rt_dof_params *p, const rt_dof_planes *device_planes, int sync)
+{
+    float A, fd;
+    rt_status st = dof_check("rt_dof_device", d, cam, p, device_planes, &A, &fd);
+    return st ? st : dof_on_device(d, (hipStream_t)hip_stream, cam, A, fd, p, device_planes, sync);
+}
+
+extern "C" rt_status rt_dof_host(rt_dof *d, const rt_camera *cam, const rt_dof_params *p, const rt_dof_planes *host_planes)
+{
+    float A, fd;
+    rt_status st = dof_check("rt_dof_host", d, cam, p, host_planes, &A, &fd);
+    if (st) return st;
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t n = (size_t)d->w * (size_t)d->h;
+    const size_t tile_bytes = dof_tiles(d->w, d->h, p->max_coc, nullptr, nullptr) * 4;
+    HostPlanes S;
+    const int rgb = S.in(host_planes->rgb_linear, n * 12), z = S.in(host_planes->z, n * 4);
+    const int out = S.out(host_planes->out, n * 12), coc = S.out(host_planes->out_coc, n * 4), tiles = S.out(host_planes->out_tiles, tile_bytes);
+    if (S.st) return S.st;
+    const rt_dof_planes dev = {(uint32_t)sizeof dev, S.dev<float>(rgb), S.dev<float>(z), S.dev<float>(out), S.dev<float>(coc), S.dev<float>(tiles)};
+    if ((st = dof_on_device(d, nullptr, cam, A, fd, p, &dev, 1))) return st;
+    return S.download({out, coc, tiles});
 }

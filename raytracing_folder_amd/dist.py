@@ -203,7 +203,9 @@ class ShardedRenderer:
     so it needs no transport: compute it after the step), bloom (capi.Bloom.apply_device -- like tone mapping it works on the
     gathered frame, so nothing of it is transported) and tone mapping (capi.Exposure.tonemap_device).  Motion blur
     (capi.MotionBlur.apply_device) is one more of these post stages: it runs after the exchange on the gathered linear, motion and
-    z planes, ahead of bloom, and nothing of it is transported.
+    z planes, ahead of bloom, and nothing of it is transported.  Depth of field (capi.DepthOfField.apply_device) likewise: render
+    with a camera whose dof is 0 and defocus the gathered linear plane from the gathered z after the un-interleave, ahead of
+    motion blur; nothing of it is exchanged.
     With planes=None and denoise=False the renderer is what it was: the same bytes exchanged, a tuple as the frame."""
 
     def __init__(self, scene, cam, params, rank, world, device_index, tile_w=32, tile_h=8, host_gather=False, linear=False,
