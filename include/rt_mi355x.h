@@ -232,7 +232,12 @@ void         rt_params_default(rt_params *p);
 rt_status rt_scene_create(rt_scene **out);
 void      rt_scene_destroy(rt_scene *s);
 
-/* Node tree as LoadScene builds it (FIN/xmlload.cpp:65-132,168-261). */
+/* Node tree as LoadScene builds it (FIN/xmlload.cpp:65-132,168-261).  nodes[0] is the root (parent -1); every other node's
+ * parent precedes it in the array -- nothing more is asked of the array's order.  Rays visit the tree as the reference's
+ * TraceNode does, whatever that order is: depth-first from node 0, a node's own object first, then its children by ascending
+ * index.  (Where two objects are hit at exactly the same distance the first one visited is the hit; under RT_SHADE_FIN a mesh
+ * hit is textured with the uvw of the sphere / plane hit accepted before it.)  A chain root .. node of more than 8 nodes that
+ * ends in an object is accepted here and refused with RT_ERR_LIMIT by the first call that lowers the scene for a device. */
 rt_status rt_scene_set_nodes(rt_scene *s, const rt_node *nodes, int32_t n);
 /* One TriObj (FIN/include/objects.h:124-303): cyTriMesh arrays V/F/VN/FN
  * (FIN/include/cyTriMesh.h:104-111) and its cyBVH node/element arrays

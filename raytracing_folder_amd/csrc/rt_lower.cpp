@@ -239,9 +239,30 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     std::vector<DevObject> objs;
     std::vector<DevObjectBack> backs;
     auto xf_of = [](const rt_node &n) { DevNodeXf x; memcpy(x.itm, n.itm, 36); memcpy(x.pos, n.pos, 12); memcpy(x.tm, n.tm, 36); x.pad[0] = x.pad[1] = x.pad[2] = 0; return x; };
-    for (int i = 0; i < nn; i++) {
+    // The objects are emitted in the order TraceNode visits them (FIN/main.cpp:108-130): depth-first from node 0, a node's own
+    // object first, then its children by ascending index -- NOT in the order of the array, which only has to put parents before
+    // children.  The order shows in the results: every comparison of the object loop is strict, so of two objects at exactly
+    // the same distance the first one tested wins, and a FIN mesh hit keeps the uvw of the sphere / plane hit accepted before
+    // it.  (An array in depth-first pre-order, like every array the XML loader makes, is visited in index order.)
+    std::vector<int> visit;
+    {
+        std::vector<int> first_child(nn, -1), last_child(nn, -1), next_sibling(nn, -1);
+        for (int i = 1; i < nn; i++) {                                       // ascending i: the sibling lists come out ascending
+            const int p = sd.nodes[i].parent;                                 // 0 <= p < i: rt_scene_set_nodes checked it
+            if (last_child[p] < 0) first_child[p] = i; else next_sibling[last_child[p]] = i;
+            last_child[p] = i;
+        }
+        visit.reserve(nn);
+        for (int i = 0; i >= 0; ) {
+            visit.push_back(i);
+            if (first_child[i] >= 0) { i = first_child[i]; continue; }
+            while (i >= 0 && next_sibling[i] < 0) i = sd.nodes[i].parent;     // up to the nearest ancestor with a sibling left
+            if (i >= 0) i = next_sibling[i];
+        }
+    }
+    for (int i = 0; i < nn; i++) xf[i] = xf_of(sd.nodes[i]);
+    for (const int i : visit) {
         const rt_node &n = sd.nodes[i];
-        xf[i] = xf_of(n);
         if (n.obj_type == RT_OBJ_NONE) continue;
         if (n.material < 0 || (size_t)n.material >= sd.materials.size())
             return fail(RT_ERR_ARG, "node %d carries an object but its material index %d is invalid", i, n.material);

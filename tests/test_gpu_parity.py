@@ -1215,15 +1215,18 @@ def test_async_render_keeps_its_inputs_and_its_overflow_verdict(monkeypatch):
 
 def test_single_stage_calls_are_refused_while_a_job_owns_the_device(monkeypatch):
     """rt_trace_rays / rt_shade_rays / rt_estimate_irradiance / rt_photon_pass share the device's scratch buffers,
-    counters and statistics with a render: while a job is live they fail with RT_ERR_STATE instead of racing"""
+    counters and statistics with a render: while a job is live they fail with RT_ERR_STATE instead of racing.
+    The calls have to arrive while the job is live: it renders 512 x 384 at 16 spp in 384 chunks and, measured on the MI355X,
+    stays live for 50 ms after its progress first shows (the 96 chunks of a 256 x 192 frame were over in 14 ms, which a
+    garbage collection or a descheduled thread between the poll and the calls can outlast: then nothing is refused)."""
     import ctypes as C
     import time
     monkeypatch.setenv("RT_CHUNK_SAMPLES", "8192")
-    s, cam = scenes.load_cornell(256, 192)
+    s, cam = scenes.load_cornell(512, 384)
     s.set_photons(photons.synth_cornell_photon_map(20000, seed=4))
     p = capi.default_params(min_sample=16, max_sample=16, threshold=-1.0)
     rays = scenes.camera_rays(cam, 64, seed=1)
-    rgb, z, cnt = np.zeros((192, 256, 3), np.uint8), np.zeros((192, 256), np.float32), np.zeros((192, 256), np.uint8)
+    rgb, z, cnt = np.zeros((384, 512, 3), np.uint8), np.zeros((384, 512), np.float32), np.zeros((384, 512), np.uint8)
     job = C.c_void_p()
     tiles = capi.TileRange(32, 8, 0, 1)
     capi._check(capi.lib().rt_render_begin(s._h, C.byref(cam), C.byref(p), C.byref(tiles), 0, capi._p(rgb), capi._p(z),
@@ -1244,8 +1247,8 @@ def test_single_stage_calls_are_refused_while_a_job_owns_the_device(monkeypatch)
         done = capi.lib().rt_render_progress(job)
     finally:
         capi.lib().rt_job_destroy(job)
-    assert done == 256 * 192
-    # the job was still rendering when the calls came (a frame of 48 chunks): all four were turned away,
+    assert done == 512 * 384
+    # the job was still rendering when the calls came (a frame of 384 chunks): all four were turned away,
     # and the frame it produced is the undisturbed one
     assert refused == 4
     full, zfull, _, _, _ = s.render(cam, p)

@@ -570,6 +570,56 @@ def test_motion_plane_with_a_seventy_node_table():
     assert np.abs(got[..., 0] - X)[ids > 0].max() > 1.0
 
 
+def _ladder_nodes(moved):
+    """the eight-level ladder of tests/graph_scenes.py; moved: its spine group of chain length 4, a MIDDLE level of the chains of
+    levels 5 .. 8, turned by 3 degrees and shifted.  Returns (nodes, node of level k at [k - 1])"""
+    from tests import graph_scenes as gs
+    case = gs.ladder(gs.LADDER_SEED)
+    nodes = case["nodes"].copy()
+    g = chain_of(nodes, int(case["levels"][7]))[3]
+    assert nodes[g]["obj_type"] == capi.OBJ_NONE and all(g in chain_of(nodes, int(n)) and chain_of(nodes, int(n))[-1] != g for n in case["levels"][4:])
+    if moved:
+        tm = nodes[g]["tm"].astype(np.float64).reshape(3, 3).T
+        set_node(nodes, g, rot_z(3.0) @ tm, nodes[g]["pos"] + np.array([0.05, -0.03, 0.02], np.float32), parent=int(nodes[g]["parent"]))
+    return nodes, case["levels"]
+
+
+def _ladder_ids(w, h, levels):
+    pl, _ = frame(cam_a(w, h), 0, 0.0)
+    Y, X = np.mgrid[0:h, 0:w]
+    return pl, np.where(pl["object_id"] >= 0, levels[(X + 3 * Y) % 8], -1).astype(np.int32)
+
+
+def test_reference_motion_on_a_chain_of_eight_moves_the_levels_below_the_moved_group_only():
+    w, h = 37, 23
+    cam = cam_a(w, h)
+    (nodes, levels), (prev, _) = _ladder_nodes(True), _ladder_nodes(False)
+    assert [len(chain_of(nodes, int(n))) for n in levels] == list(range(1, 9))
+    pl, ids = _ladder_ids(w, h, levels)
+    want, found, qz = ref_motion(cam, cam, nodes, prev, pl["z"], ids)
+    Y, X = np.mgrid[0:h, 0:w]
+    shift = np.abs(want[..., 0] - X) + np.abs(want[..., 1] - Y)
+    below, above = np.isin(ids, levels[4:]), np.isin(ids, levels[:4])
+    assert below.sum() > 200 and above.sum() > 200 and found[below | above].all()
+    # (at rest: itm tm is the identity to float32 only, 1e-7 per level on positions of a few tens of units a few units deep)
+    assert shift[above].max() < 1e-4 and shift[below].min() > 0.05 and shift[below].max() > 1.0
+    assert (np.abs(qz[np.isfinite(qz)]) > MARGIN).all()
+
+
+@pytest.mark.gpu
+def test_motion_plane_on_a_chain_of_eight_with_a_middle_group_moved():
+    """chains of 5 .. 8 nodes whose fourth node moved between the frames (and the chains of 1 .. 4 beside them, at rest), at the
+    tolerance of every other plane here"""
+    w, h = 37, 23
+    cam = cam_a(w, h)
+    (nodes, levels), (prev, _) = _ladder_nodes(True), _ladder_nodes(False)
+    pl, ids = _ladder_ids(w, h, levels)
+    got = capi.motion(cam, cam, nodes, prev, pl["z"], ids)
+    _check_plane(got, cam, cam, nodes, prev, pl["z"], ids, "ladder, level 4 moved")
+    Y, X = np.mgrid[0:h, 0:w]
+    assert np.abs(got[..., 0] - X)[np.isin(ids, levels[4:])].max() > 1.0
+
+
 @pytest.mark.gpu
 def test_pixels_without_a_previous_position_hold_x_y_0():
     w, h = 37, 23
