@@ -365,6 +365,43 @@ typedef struct rt_device_bvh_info {
 rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
                                    uint32_t *slot_face, uint64_t slots_cap);
 
+/* ---- mesh vertex updates (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------------
+ * New positions (and, optionally, normals) for a mesh whose faces stay as they are: a deforming surface, frame after frame.
+ * nv and nvn must be the stored counts (anything else: RT_ERR_ARG, nothing changes); vn == NULL keeps the stored normals.  The
+ * scene must be idle (no live job).  flags: 0, or RT_MESH_UPDATE_REBUILD.
+ *   0        On every device that holds this scene as it is now, the mesh is updated IN PLACE: the vertices are uploaded,
+ *            k_mesh_retri writes every triangle slot (A, B, C, the unit face normal computed operation by operation as the host
+ *            computes it, the three vertex normals) and k_bvh_refit_level, once per level of the tree from the deepest up, sets
+ *            every child box to the exact float min / max of the vertices beneath it.  The tree keeps its topology (refs and
+ *            slot order); every box of it is as tight as a fresh build's, so the closest hit of every ray is the fresh build's --
+ *            only how many boxes a ray enters can grow as the shape moves away from the one the tree was built for.  The mesh's
+ *            root box and the cull boxes of the objects that use it follow; the call returns after the device has finished.
+ *            Devices that do not hold the scene (never rendered on, or invalidated by another setter) lower it as usual later.
+ *   REBUILD  what rt_scene_set_mesh does: every device builds the tree again at its next use.  For the caller that decides a
+ *            refitted tree has degraded (this library offers no measure of that).
+ * Either way the stored cyBVH arrays are built again for the new vertices when somebody reads them (rt_scene_get_mesh returns
+ * what rt_bvh_build with leaves of four gives), and a photon map made by the photon pass is dropped, as by rt_scene_set_mesh. */
+#define RT_MESH_UPDATE_REBUILD 1u
+rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                        uint32_t flags);
+/* What sits on `device` for one mesh right now (the scene is lowered there first if it is not): info, nodes, slot_face as
+ * rt_scene_mesh_device_bvh describes them -- after an in-place update the refitted tree, not the one a fresh build would give --
+ * and per triangle slot its 12 floats of A, B, C, N and its 9 floats of vertex normals, and the mesh's root box (lo[3], hi[3]).
+ * info is required and its struct_size checked; every other pointer may be NULL.  nodes_cap counts node records; slots_cap counts
+ * slots and holds for slot_face, tris and nrm alike.  A too small capacity is RT_ERR_ARG and nothing is written. */
+rt_status rt_scene_mesh_device_read(rt_scene *s, int device, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
+                                    uint32_t *slot_face, uint64_t slots_cap, float *tris, float *nrm, float root_box[6]);
+/* The last in-place update on `device`, timed with events on the library's stream: milliseconds of the vertex upload, of
+ * k_mesh_retri and of the refit launches, and how many of those there were (one per level of the tree).  RT_ERR_STATE when that
+ * device has not run one. */
+typedef struct rt_mesh_update_ms {
+    uint32_t struct_size;
+    int32_t level_launches;
+    float upload, retri, refit;
+} rt_mesh_update_ms;
+rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out);
+
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
  * (maxElementsPerNode = 4, FIN/include/objects.h:143).  nodes_out needs room for 2*nf+1

@@ -203,6 +203,11 @@ class DeviceBvhInfo(C.Structure):
                 ("spill_blocks", C.c_int32), ("block", C.c_int32)]
 
 
+class MeshUpdateMs(C.Structure):
+    """rt_mesh_update_ms: the last in-place mesh update on a device, by events on the library's stream (milliseconds)"""
+    _fields_ = [("struct_size", C.c_uint32), ("level_launches", C.c_int32), ("upload", C.c_float), ("retri", C.c_float), ("refit", C.c_float)]
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -261,7 +266,11 @@ SYMBOLS = [
     "rt_dof_create", "rt_dof_destroy", "rt_dof_default_params", "rt_dof_tiles", "rt_dof_taps", "rt_dof_device", "rt_dof_host",
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
     "rt_scene_mesh_device_bvh",
+    "rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms",
 ]
+
+# rt_scene_update_mesh_vertices flags (include/rt_mi355x.h): build the tree again instead of refitting it in place
+MESH_UPDATE_REBUILD = 1
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -406,6 +415,12 @@ def lib():
         # the device tree of a mesh, on the host (rt_mi355x.h: rt_scene_mesh_device_bvh)
         _lib.rt_scene_mesh_device_bvh.argtypes = [vp, i32, vp, vp, C.c_uint64, vp, C.c_uint64]
         _lib.rt_scene_mesh_device_bvh.restype = C.c_int
+        # mesh vertex updates (rt_mi355x.h: "mesh vertex updates")
+        _lib.rt_scene_update_mesh_vertices.argtypes = [vp, i32, vp, i32, vp, i32, C.c_uint32]
+        _lib.rt_scene_mesh_device_read.argtypes = [vp, C.c_int, i32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
+        _lib.rt_scene_mesh_update_ms.argtypes = [vp, C.c_int, vp]
+        for name in ("rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms"):
+            getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
                      "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
@@ -1158,6 +1173,20 @@ class Scene:
         if vt is not None and len(vt):
             self.set_mesh_texcoords(index, vt, ft)
 
+    def update_mesh_vertices(self, index, v, vn=None, rebuild=False):
+        """new positions (and normals, unless vn is None) for a mesh whose faces stay: refitted in place on the devices that hold
+        the scene; rebuild=True takes set_mesh's path instead (the tree is built again at the next use)"""
+        v = _c(v, np.float32).reshape(-1, 3)
+        vn = _c(vn, np.float32).reshape(-1, 3) if vn is not None else None
+        _check(lib().rt_scene_update_mesh_vertices(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
+                                                   len(vn) if vn is not None else 0, C.c_uint32(MESH_UPDATE_REBUILD if rebuild else 0)))
+
+    def mesh_update_ms(self, device=0):
+        """the last in-place update on `device`: dict(upload, retri, refit in ms by HIP events, level_launches)"""
+        t = MeshUpdateMs(struct_size=C.sizeof(MeshUpdateMs))
+        _check(lib().rt_scene_mesh_update_ms(self._h, int(device), C.byref(t)))
+        return dict(upload=t.upload, retri=t.retri, refit=t.refit, level_launches=t.level_launches)
+
     def set_mesh_texcoords(self, index, vt, ft):
         """cyTriMesh VT/FT of a mesh already set (read by the PROJ13-family triangle)."""
         vt, ft = _c(vt, np.float32).reshape(-1, 3), _c(ft, np.uint32).reshape(-1, 3)
@@ -1301,6 +1330,18 @@ class Scene:
         nodes, slot_face = np.zeros(info.n_nodes, DEVBVHNODE), np.zeros(info.n_slots, np.uint32)
         _check(lib().rt_scene_mesh_device_bvh(self._h, int(index), C.byref(info), _p(nodes), len(nodes), _p(slot_face), len(slot_face)))
         return nodes, slot_face, info
+
+    def mesh_device_read(self, index, device=0):
+        """what sits on `device` for mesh `index` right now (the scene is lowered there first if need be): dict(info, nodes,
+        slot_face, tris [slots, 12]: A B C N, nrm [slots, 9], root_box [6])"""
+        info = DeviceBvhInfo(struct_size=C.sizeof(DeviceBvhInfo))
+        _check(lib().rt_scene_mesh_device_read(self._h, int(device), int(index), C.byref(info), None, 0, None, 0, None, None, None))
+        n = info.n_slots
+        out = dict(info=info, nodes=np.zeros(info.n_nodes, DEVBVHNODE), slot_face=np.zeros(n, np.uint32),
+                   tris=np.zeros((n, 12), np.float32), nrm=np.zeros((n, 9), np.float32), root_box=np.zeros(6, np.float32))
+        _check(lib().rt_scene_mesh_device_read(self._h, int(device), int(index), C.byref(info), _p(out["nodes"]), len(out["nodes"]),
+                                               _p(out["slot_face"]), n, _p(out["tris"]), _p(out["nrm"]), _p(out["root_box"])))
+        return out
 
     # -- GPU work -------------------------------------------------------------------------------
     def trace_rays(self, rays, shade_model=SHADE_FIN, device=0):

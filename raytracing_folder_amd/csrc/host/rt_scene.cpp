@@ -427,6 +427,15 @@ void BuildMeanSplitBVH(const float *v, const uint32_t *f, unsigned nf, unsigned 
     c.Convert(nodes, 1, 0, 2);
 }
 
+void MeshRootBox(const float *v, const uint32_t *f, unsigned nf, float box[6])
+{
+    BuildCtx c{};
+    c.v = v; c.f = f;
+    BuildCtx::Empty(box);
+    float eb[6];
+    for (unsigned i = 0; i < nf; i++) { c.Bounds(i, eb); BuildCtx::Grow(box, eb); }      // the root's loop of BuildMeanSplitBVH
+}
+
 // ---- photon map balancing ------------------------------------------------------------------------
 // PhotonMap::PrepareForIrradianceEstimation + BalanceSegment, FIN/include/cyPhotonMap.h:196-284:
 // left-balanced kd-tree in heap order (children of i at 2i, 2i+1), split axis = widest extent

@@ -311,6 +311,10 @@ struct MeshData {
     std::vector<uint32_t> f, fn, ft;
     std::vector<rt_bvh_node> nodes;
     std::vector<uint32_t> elements;
+    // rt_scene_update_mesh_vertices replaced v since nodes / elements were built: they are built again (BuildMeanSplitBVH, leaves
+    // of four) when somebody reads them; until then root_box is what the new nodes[1].box will be (MeshRootBox)
+    bool tree_stale = false;
+    float root_box[6] = {0, 0, 0, 0, 0, 0};
 };
 struct SceneData {
     std::vector<rt_node> nodes;
@@ -333,6 +337,8 @@ bool Lower(const Scene &scene, SceneData &out, std::string *err);
 // cyBVH::Build with MeanSplit (FIN/include/cyBVH.h:122-142,242-328)
 void BuildMeanSplitBVH(const float *v, const uint32_t *f, unsigned nf, unsigned maxPerLeaf,
                        std::vector<rt_bvh_node> &nodes, std::vector<uint32_t> &elements);
+// the box BuildMeanSplitBVH gives its root (nodes[1].box), bit for bit, without building the tree: lo[3], hi[3]
+void MeshRootBox(const float *v, const uint32_t *f, unsigned nf, float box[6]);
 // PhotonMap::PrepareForIrradianceEstimation (FIN/include/cyPhotonMap.h:196-284)
 void BalancePhotons(rt_photon *in, uint32_t n, rt_photon *out);
 // heap slots 1..ReachablePhotonSlots(n) are the ones LocatePhotons can visit (cyPhotonMap.h:217,371)

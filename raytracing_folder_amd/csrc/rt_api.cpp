@@ -146,9 +146,48 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     m.v.assign(v, v + 3 * (size_t)nv); m.f.assign(f, f + 3 * (size_t)nf);
     m.vn.assign(vn, vn + 3 * (size_t)nvn); m.fn.assign(fn, fn + 3 * (size_t)nf);
     m.nodes.assign(nodes, nodes + nnodes); m.elements.assign(elements, elements + nf);
+    m.tree_stale = false;
     m.vt.clear(); m.ft.clear();
     s->geometry_changed();
     return RT_OK;
+}
+
+void ensure_reference_tree(rt::MeshData &m)
+{
+    if (!m.tree_stale) return;
+    rt::BuildMeanSplitBVH(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), 4, m.nodes, m.elements);      // TriObj::Load's leaves of four
+    m.tree_stale = false;
+}
+// for the getters, which take the scene const: the tree is a cache of what the vertices determine
+static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
+{
+    rt_scene *w = const_cast<rt_scene *>(s);
+    std::lock_guard<std::mutex> lk(w->mu);
+    ensure_reference_tree(w->data.meshes[mesh]);
+    return w->data.meshes[mesh];
+}
+
+extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
+{
+    rt_status st = check_idle(s, "rt_scene_update_mesh_vertices");
+    if (st) return st;
+    if (flags & ~RT_MESH_UPDATE_REBUILD) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: unknown flag bits 0x%x", flags & ~RT_MESH_UPDATE_REBUILD);
+    if (!v) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: v is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
+        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: mesh %d was never set", mesh);
+    rt::MeshData &m = s->data.meshes[mesh];
+    if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: nv is %d, the mesh has %zu vertices (the faces stay as they are)", nv, m.v.size() / 3);
+    if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
+        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: nvn is %d, the mesh has %zu normals", nvn, m.vn.size() / 3);
+    m.v.assign(v, v + 3 * (size_t)nv);
+    if (vn) m.vn.assign(vn, vn + 3 * (size_t)nvn);
+    m.tree_stale = true;
+    rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
+    // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
+    if (s->gen.valid) { s->drop_generated(); s->data.photons.clear(); s->invalidate(false, true); }
+    if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }
+    return refit_mesh_on_devices(s, mesh, vn != nullptr);
 }
 
 extern "C" rt_status rt_scene_set_mesh_texcoords(rt_scene *s, int32_t mesh, const float *vt, int32_t nvt, const uint32_t *ft)
@@ -443,7 +482,7 @@ extern "C" rt_status rt_scene_get_lights(const rt_scene *s, rt_light *out, int32
 extern "C" rt_status rt_scene_mesh_counts(const rt_scene *s, int32_t mesh, int32_t *nv, int32_t *nf, int32_t *nvn, int32_t *nnodes)
 {
     if (!s || mesh < 0 || (size_t)mesh >= s->data.meshes.size()) return fail(RT_ERR_ARG, "rt_scene_mesh_counts: bad mesh index");
-    const rt::MeshData &m = s->data.meshes[mesh];
+    const rt::MeshData &m = mesh_with_tree(s, mesh);
     if (nv) *nv = (int32_t)(m.v.size() / 3);
     if (nf) *nf = (int32_t)(m.f.size() / 3);
     if (nvn) *nvn = (int32_t)(m.vn.size() / 3);
@@ -455,7 +494,7 @@ extern "C" rt_status rt_scene_get_mesh(const rt_scene *s, int32_t mesh, float *v
                                        rt_bvh_node *nodes, uint32_t *elements)
 {
     if (!s || mesh < 0 || (size_t)mesh >= s->data.meshes.size()) return fail(RT_ERR_ARG, "rt_scene_get_mesh: bad mesh index");
-    const rt::MeshData &m = s->data.meshes[mesh];
+    const rt::MeshData &m = mesh_with_tree(s, mesh);
     if (v) memcpy(v, m.v.data(), m.v.size() * 4);
     if (f) memcpy(f, m.f.data(), m.f.size() * 4);
     if (vn) memcpy(vn, m.vn.data(), m.vn.size() * 4);

@@ -74,7 +74,17 @@ struct RT_HIDDEN Event {
 };
 
 // ---- a scene on one device (rt_lower.cpp fills it, rt_render.cpp renders from it) ---------------------------
-struct DevMeshBufs { DevBuf nodes, tris, nrm, tex; };
+// nodes .. tex are what DevMesh points to.  The rest serves rt_scene_update_mesh_vertices (rt_refit.hip) and is written at upload
+// time with them: per triangle slot the three vertex and three normal indices of its face; the indices of the tree's nodes by
+// depth, the deepest level first (level k is level_nodes[level_off[k] .. level_off[k + 1]), the root's level last); on the host,
+// what rt_scene_mesh_device_read reports.  v and vn exist from the first update on.
+struct DevMeshBufs {
+    DevBuf nodes, tris, nrm, tex;
+    DevBuf slot_idx, level_nodes, v, vn;
+    std::vector<uint32_t> level_off, slot_face;
+    uint32_t root_ref = 0; int stack_need = 0;
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn}) b->release(); }
+};
 
 static const size_t SPILL_BYTES = (size_t)RT_SPILL_BLOCKS * RT_BLOCK * RT_BVH_SPILL * 4;     // DevScene::bvh_spill / DevWork::bvh_spill
 
@@ -143,6 +153,8 @@ struct DeviceState {
     // scratch for the single-stage entry points
     DevBuf t_in, t_out[6];
     hipStream_t stream = nullptr;
+    // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
+    Event upd_ev[4]; int upd_levels = -1;
     // one of the two maps: its buffers with what the kernels see of it
     PhotonMapRef map(bool caustic) { return {maps[caustic], caustic ? scene.cm : scene.pm}; }
     void release()
@@ -150,7 +162,9 @@ struct DeviceState {
         for (DevBuf *b : {&nodes, &objects, &objects_back, &meshes, &materials, &lights, &node_material, &textures, &texels, &material_maps,
                           &raw_photons, &bvh_spill, &stats, &t_in}) b->release();
         for (PhotonStore &m : maps) m.release();
-        for (auto &m : mesh_bufs) { m.nodes.release(); m.tris.release(); m.nrm.release(); m.tex.release(); }
+        for (auto &m : mesh_bufs) m.release();
+        for (Event &e : upd_ev) e = Event();
+        upd_levels = -1;
         for (Workspace &w : ws) w.release();
         for (int k = 0; k < 6; k++) t_out[k].release();
         if (stream) (void)hipStreamDestroy(stream);
@@ -210,6 +224,10 @@ struct rt_scene {
 
 // ---- what crosses the host files ----------------------------------------------------------------------------
 RT_HIDDEN rt_status check_idle(rt_scene *s, const char *who);                                   // rt_api.cpp
+// rt_api.cpp: the stored cyBVH arrays of a mesh, built again if a vertex update left them stale (caller holds s->mu)
+RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
+// rt_lower.cpp: what rt_scene_update_mesh_vertices does on the devices that hold the scene (caller holds s->mu, the store has the new vertices)
+RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed);
 // rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
 RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
 RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);

@@ -1,5 +1,5 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip): every rtk_* function, the requests they take and the
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
@@ -218,6 +218,20 @@ struct DofRequest {
     float *tile_max, *tile_nmax;
 };
 
+// One in-place update of a mesh on a device (rt_refit.hip; the definition: rt_mi355x.h, "mesh vertex updates").  Everything is the
+// mesh's own device memory (DevMeshBufs in rt_host.h): v / vn the new vertices and normals, slot_idx six uint32 per triangle slot
+// (the face's three indices into v, then its three into vn), level_nodes the node indices by depth, the deepest level first, and
+// level_off (on the HOST, n_levels + 1 entries) where each level starts in it.  n_levels == 0: the mesh is one leaf, only
+// k_mesh_retri runs.  after_retri: NULL, or an event recorded between k_mesh_retri and the first refit launch.
+struct MeshRefitRequest {
+    const float *v, *vn;
+    const uint32_t *slot_idx; uint32_t n_slots;
+    DevTri *tris; float *nrm;
+    DevBvhNode *nodes;
+    const uint32_t *level_nodes; const uint32_t *level_off; int n_levels;
+    hipEvent_t after_retri;
+};
+
 // ---- rt_kernels.hip: the kernels that shade -----------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -292,6 +306,10 @@ hipError_t rtk_launch_motion_blur(hipStream_t st, const MotionBlurRequest &R);
 // ---- rt_dof.hip: depth of field between the denoise and motion blur ---------------------------------------------------------
 // on `st`: k_dof_coc, k_dof_neighbour_max, k_dof_gather
 hipError_t rtk_launch_dof(hipStream_t st, const DofRequest &R);
+
+// ---- rt_refit.hip: mesh vertex updates ------------------------------------------------------------------------------------
+// on `st`: k_mesh_retri over the slots, then k_bvh_refit_level once per level, the deepest first
+hipError_t rtk_launch_mesh_refit(hipStream_t st, const MeshRefitRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

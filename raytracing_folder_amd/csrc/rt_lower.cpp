@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -45,7 +46,9 @@ DeviceState *find_device_state(rt_scene *s, int device)
 // SAH splits only above a lower depth and balanced halves below (28, 26, .. 0).  The last resort, halves all the way, collapsed
 // evenly (BOTH children replaced by theirs: every device level stands for two binary ones), always fits: halves over fewer
 // than 2^28 faces with leaves of four are at most 26 binary levels deep, 13 device levels of at most 3 entries each.
-static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &out, std::vector<uint32_t> &slot_face, uint32_t &root_ref, int &stack_need)
+// node_depth (may be NULL): the depth of every device node, the root's 0 -- what the refit orders its launches by.
+static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &out, std::vector<uint32_t> &slot_face, uint32_t &root_ref, int &stack_need,
+                               std::vector<uint32_t> *node_depth = nullptr)
 {
     const size_t nf = m.f.size() / 3;
     struct TB { float lo[3], hi[3], c[3]; };
@@ -147,10 +150,12 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
     // (evenly: both children replaced by theirs, see above.)  held: the stack entries of a ray that arrives at this node
     struct Col {
         std::vector<BN> &bn; std::vector<DevBvhNode> &out; decltype(area) &area; decltype(leafref) &leafref; bool evenly; int &need;
-        uint32_t go(int32_t id, int held)
+        std::vector<uint32_t> *node_depth;
+        uint32_t go(int32_t id, int held, uint32_t depth)
         {
             const uint32_t me = (uint32_t)out.size();
             out.push_back(DevBvhNode{});
+            if (node_depth) node_depth->push_back(depth);
             int32_t ch[4]; int n = 0;
             if (evenly) {
                 for (const int32_t c : {bn[id].left, bn[id].right}) {
@@ -176,7 +181,7 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
                 for (int a = 0; a < 3; a++) { d.lo[a][i] = i < n ? bn[ch[i]].lo[a] : nan; d.hi[a][i] = i < n ? bn[ch[i]].hi[a] : nan; }
                 if (i >= n) d.c[i] = leafref(0, 1);
                 else if (bn[ch[i]].left < 0) d.c[i] = leafref(bn[ch[i]].first, bn[ch[i]].count);
-                else d.c[i] = go(ch[i], held);
+                else d.c[i] = go(ch[i], held, depth + 1);
             }
             out[me] = d;
             return me;
@@ -184,13 +189,14 @@ static rt_status build_sah_bvh(const rt::MeshData &m, std::vector<DevBvhNode> &o
     };
     for (int sah_depth = 28; ; sah_depth -= 2) {
         bn.clear(); out.clear();
+        if (node_depth) node_depth->clear();
         for (size_t i = 0; i < nf; i++) idx[i] = (uint32_t)i;
         Rec rec{tb, bn, idx, area, sah_depth};
         const int32_t root = rec.go(0, (uint32_t)nf, 0);
         stack_need = 0;
-        Col col{bn, out, area, leafref, sah_depth == 0, stack_need};
+        Col col{bn, out, area, leafref, sah_depth == 0, stack_need, node_depth};
         if (bn[root].left < 0) root_ref = leafref(bn[root].first, bn[root].count);
-        else root_ref = col.go(root, 0);
+        else root_ref = col.go(root, 0, 0);
         if (stack_need <= RT_BVH_LDS + RT_BVH_SPILL) break;
         if (sah_depth == 0) return fail(RT_ERR_LIMIT, "the BVH can need %d traversal-stack entries, the device provides %d", stack_need, RT_BVH_LDS + RT_BVH_SPILL);      // not reached: see above
     }
@@ -227,18 +233,24 @@ extern "C" rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, r
     return RT_OK;
 }
 
-static rt_status upload_scene(rt_scene *s, DeviceState *D)
+static DevNodeXf xf_of(const rt_node &n)
 {
-    const rt::SceneData &sd = s->data;
-    if (sd.nodes.empty()) return fail(RT_ERR_STATE, "scene has no nodes");
-    if (sd.nodes.size() > 65535) return fail(RT_ERR_LIMIT, "too many scene nodes (%zu)", sd.nodes.size());
-    if (sd.materials.size() > 65535) return fail(RT_ERR_LIMIT, "too many materials (%zu): ray records carry 16-bit material indices", sd.materials.size());
+    DevNodeXf x;
+    memcpy(x.itm, n.itm, 36); memcpy(x.pos, n.pos, 12); memcpy(x.tm, n.tm, 36);
+    x.pad[0] = x.pad[1] = x.pad[2] = 0;
+    return x;
+}
+
+// the local extent of a mesh, lo[3] hi[3]: the root box of its cyBVH arrays (of the ones a vertex update will have built again)
+static const float *mesh_root_box(const rt::MeshData &m) { return m.tree_stale ? m.root_box : m.nodes[1].box; }
+
+// The DevObject / DevObjectBack records of the scene's objects and the material of every node: shared by upload_scene and by the
+// in-place mesh update (refit_mesh_on_devices), which moves the cull boxes of the objects whose mesh changed.
+static rt_status lower_objects(const rt::SceneData &sd, std::vector<DevObject> &objs, std::vector<DevObjectBack> &backs, std::vector<int32_t> &node_mat)
+{
     const int nn = (int)sd.nodes.size();
-    std::vector<DevNodeXf> xf(nn);
-    std::vector<int32_t> node_mat(nn, 0);
-    std::vector<DevObject> objs;
-    std::vector<DevObjectBack> backs;
-    auto xf_of = [](const rt_node &n) { DevNodeXf x; memcpy(x.itm, n.itm, 36); memcpy(x.pos, n.pos, 12); memcpy(x.tm, n.tm, 36); x.pad[0] = x.pad[1] = x.pad[2] = 0; return x; };
+    objs.clear(); backs.clear();
+    node_mat.assign(nn, 0);
     // The objects are emitted in the order TraceNode visits them (FIN/main.cpp:108-130): depth-first from node 0, a node's own
     // object first, then its children by ascending index -- NOT in the order of the array, which only has to put parents before
     // children.  The order shows in the results: every comparison of the object loop is strict, so of two objects at exactly
@@ -260,7 +272,6 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
             if (i >= 0) i = next_sibling[i];
         }
     }
-    for (int i = 0; i < nn; i++) xf[i] = xf_of(sd.nodes[i]);
     for (const int i : visit) {
         const rt_node &n = sd.nodes[i];
         if (n.obj_type == RT_OBJ_NONE) continue;
@@ -286,7 +297,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
             double lo[3] = {-1, -1, -1}, hi[3] = {1, 1, 1};                 // unit sphere; unit square at z = 0
             if (n.obj_type == RT_OBJ_PLANE) lo[2] = hi[2] = 0;
             if (n.obj_type == RT_OBJ_MESH) {
-                const float *b = sd.meshes[n.mesh].nodes[1].box;
+                const float *b = mesh_root_box(sd.meshes[n.mesh]);
                 for (int a = 0; a < 3; a++) { lo[a] = b[a]; hi[a] = b[a + 3]; }
             }
             double wlo[3] = {1e300, 1e300, 1e300}, whi[3] = {-1e300, -1e300, -1e300};
@@ -318,8 +329,23 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         backs.push_back(b);
     }
     if (objs.size() > RT_MAX_OBJECTS) return fail(RT_ERR_LIMIT, "too many objects (%zu)", objs.size());
+    return RT_OK;
+}
 
+static rt_status upload_scene(rt_scene *s, DeviceState *D)
+{
+    const rt::SceneData &sd = s->data;
+    if (sd.nodes.empty()) return fail(RT_ERR_STATE, "scene has no nodes");
+    if (sd.nodes.size() > 65535) return fail(RT_ERR_LIMIT, "too many scene nodes (%zu)", sd.nodes.size());
+    if (sd.materials.size() > 65535) return fail(RT_ERR_LIMIT, "too many materials (%zu): ray records carry 16-bit material indices", sd.materials.size());
+    const int nn = (int)sd.nodes.size();
+    std::vector<DevNodeXf> xf(nn);
+    std::vector<int32_t> node_mat;
+    std::vector<DevObject> objs;
+    std::vector<DevObjectBack> backs;
+    for (int i = 0; i < nn; i++) xf[i] = xf_of(sd.nodes[i]);
     rt_status st;
+    if ((st = lower_objects(sd, objs, backs, node_mat))) return st;
     if ((st = D->nodes.upload(xf.data(), xf.size() * sizeof(DevNodeXf)))) return st;
     if ((st = D->objects.upload(objs.data(), objs.size() * sizeof(DevObject)))) return st;
     if ((st = D->objects_back.upload(backs.data(), backs.size() * sizeof(DevObjectBack)))) return st;
@@ -327,7 +353,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     if ((st = D->materials.upload(sd.materials.data(), sd.materials.size() * sizeof(rt_blinn)))) return st;
     if ((st = D->lights.upload(sd.lights.data(), sd.lights.size() * sizeof(rt_light)))) return st;
 
-    for (auto &mb : D->mesh_bufs) { mb.nodes.release(); mb.tris.release(); mb.nrm.release(); mb.tex.release(); }
+    for (auto &mb : D->mesh_bufs) mb.release();
     D->mesh_bufs.assign(sd.meshes.size(), DevMeshBufs());
     std::vector<DevMesh> dm(sd.meshes.size());
     int max_depth = 0;
@@ -338,8 +364,8 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         std::vector<DevBvhNode> bn;
         uint32_t root_ref = 0;
         int depth = 0;
-        std::vector<uint32_t> slot_face;
-        if ((st = build_sah_bvh(m, bn, slot_face, root_ref, depth))) return st;
+        std::vector<uint32_t> slot_face, node_depth;
+        if ((st = build_sah_bvh(m, bn, slot_face, root_ref, depth, &node_depth))) return st;
         // (the smallest LDS stack of any tracing kernel is RT_BVH_LDS entries; RT_BVH_SPILL more per thread wait in HBM: spill buffers
         // below.  The builder keeps every tree within that: this only guards the kernels against a builder that does not.)
         if (depth > RT_BVH_LDS + RT_BVH_SPILL) return fail(RT_ERR_LIMIT, "mesh %zu: the BVH can need %d traversal-stack entries, the device provides %d", mi, depth, RT_BVH_LDS + RT_BVH_SPILL);
@@ -365,6 +391,21 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         if ((st = mb.nodes.upload(bn.data(), bn.size() * sizeof(DevBvhNode)))) return st;
         if ((st = mb.tris.upload(tris.data(), tris.size() * sizeof(DevTri)))) return st;
         if ((st = mb.nrm.upload(nrm.data(), nrm.size() * 4))) return st;
+        {   // what an in-place vertex update works from (DevMeshBufs): the slots' indices, and the nodes by depth, deepest first
+            std::vector<uint32_t> slot_idx(6 * nf);
+            for (size_t sidx = 0; sidx < nf; sidx++)
+                for (int k = 0; k < 3; k++) { slot_idx[6 * sidx + k] = m.f[3 * (size_t)tri_face[sidx] + k]; slot_idx[6 * sidx + 3 + k] = m.fn[3 * (size_t)tri_face[sidx] + k]; }
+            uint32_t levels = 0;
+            for (const uint32_t d : node_depth) levels = std::max(levels, d + 1);
+            mb.level_off.assign((size_t)levels + 1, 0);
+            for (const uint32_t d : node_depth) mb.level_off[levels - d]++;                   // level k = depth levels - 1 - k: counts at [k + 1]
+            for (uint32_t k = 0; k < levels; k++) mb.level_off[k + 1] += mb.level_off[k];
+            std::vector<uint32_t> level_nodes(node_depth.size()), at(mb.level_off.begin(), mb.level_off.end() - 1);
+            for (size_t i = 0; i < node_depth.size(); i++) level_nodes[at[levels - 1 - node_depth[i]]++] = (uint32_t)i;
+            if ((st = mb.slot_idx.upload(slot_idx.data(), slot_idx.size() * 4))) return st;
+            if ((st = mb.level_nodes.upload(level_nodes.data(), level_nodes.size() * 4))) return st;
+            mb.slot_face = tri_face; mb.root_ref = root_ref; mb.stack_need = depth;
+        }
         dm[mi].tex = nullptr;
         if (!m.vt.empty() && m.ft.size() == m.f.size()) {      // vt[ft0], vt[ft1], vt[ft2] per triangle slot, like nrm
             std::vector<float> tex(9 * nf);
@@ -375,7 +416,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         }
         dm[mi].nodes = (const DevBvhNode *)mb.nodes.p; dm[mi].tris = (const DevTri *)mb.tris.p;
         dm[mi].nrm = (const float *)mb.nrm.p;
-        memcpy(dm[mi].root_box, m.nodes[1].box, 24);
+        memcpy(dm[mi].root_box, mesh_root_box(m), 24);
         dm[mi].root_ref = root_ref; dm[mi].n_tris = (uint32_t)nf;
     }
     if ((st = D->meshes.upload(dm.data(), dm.size() * sizeof(DevMesh)))) return st;
@@ -413,6 +454,116 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     for (const rt_light &l : sd.lights) if (l.type == RT_LIGHT_POINT && l.size != 0) S.stochastic = 1;
     for (const rt_blinn &m : sd.materials) if (m.reflection_glossiness != 0 || m.refraction_glossiness != 0) S.stochastic = 1;
     D->scene_valid = true;
+    return RT_OK;
+}
+
+// ---- mesh vertex updates -------------------------------------------------------------------------------
+// One device's share of rt_scene_update_mesh_vertices: everything upload_scene derived from this mesh's vertices, set again in
+// place -- DevTri and nrm of every slot and every box of the tree (rt_refit.hip), DevMesh::root_box, and the objects' cull boxes
+// (objs: the scene's objects lowered again by the caller).  Nothing else on the device depends on a mesh's vertices: the tree's
+// topology, stack_need (DevScene::max_bvh_depth, the spill buffers) and tex follow the faces, which stay.
+static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs)
+{
+    HIP_TRY(hipSetDevice(D->device));
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
+    const size_t nf = m.f.size() / 3;
+    if ((size_t)mesh >= D->mesh_bufs.size() || D->mesh_bufs[mesh].slot_face.size() != nf || objs.size() != (size_t)D->scene.n_objects)
+        return fail(RT_ERR_STATE, "rt_scene_update_mesh_vertices: device %d does not hold mesh %d as the scene has it", D->device, mesh);
+    DevMeshBufs &mb = D->mesh_bufs[mesh];
+    hipStream_t st = D->stream;
+    for (Event &e : D->upd_ev) if (!e.e) HIP_TRY(e.create());
+    rt_status rs;
+    const bool first = mb.vn.p == nullptr;
+    if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    HIP_TRY(hipEventRecord(D->upd_ev[0], st));
+    HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
+    if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(D->upd_ev[1], st));
+    MeshRefitRequest R = {};
+    R.v = (const float *)mb.v.p; R.vn = (const float *)mb.vn.p;
+    R.slot_idx = (const uint32_t *)mb.slot_idx.p; R.n_slots = (uint32_t)nf;
+    R.tris = (DevTri *)mb.tris.p; R.nrm = (float *)mb.nrm.p; R.nodes = (DevBvhNode *)mb.nodes.p;
+    R.level_nodes = (const uint32_t *)mb.level_nodes.p; R.level_off = mb.level_off.data(); R.n_levels = (int)mb.level_off.size() - 1;
+    R.after_retri = D->upd_ev[2];
+    HIP_TRY(rtk_launch_mesh_refit(st, R));
+    HIP_TRY(hipEventRecord(D->upd_ev[3], st));
+    D->upd_levels = R.n_levels;
+    HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), m.root_box, 24, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed)
+{
+    const rt::MeshData &m = s->data.meshes[mesh];
+    bool any = false;
+    for (DeviceState *D : s->devs) any = any || D->scene_valid;
+    if (!any) return RT_OK;
+    std::vector<DevObject> objs;
+    std::vector<DevObjectBack> backs;
+    std::vector<int32_t> node_mat;
+    rt_status st = lower_objects(s->data, objs, backs, node_mat);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    rt_status ret = RT_OK;
+    for (DeviceState *D : s->devs) {
+        if (!D->scene_valid) continue;
+        // a device another call is using, or one the update fails on, lowers the scene again at its next use instead
+        DeviceClaim claim(D);
+        rt_status r = st;
+        if (!r && claim.ok) r = refit_mesh_on_device(D, m, mesh, normals_changed, objs);
+        if (r || !claim.ok) D->scene_valid = false;
+        if (r && !ret) ret = r;
+    }
+    (void)hipSetDevice(cur);
+    return ret;
+}
+
+extern "C" rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out)
+{
+    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_update_ms: NULL argument");
+    if (out->struct_size != sizeof(rt_mesh_update_ms))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_update_ms: rt_mesh_update_ms.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_update_ms));
+    DeviceState *D = find_device_state(s, device);
+    if (!D || D->upd_levels < 0) return fail(RT_ERR_STATE, "rt_scene_mesh_update_ms: device %d has not updated a mesh in place", device);
+    HIP_TRY(hipEventElapsedTime(&out->upload, D->upd_ev[0], D->upd_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out->retri, D->upd_ev[1], D->upd_ev[2]));
+    HIP_TRY(hipEventElapsedTime(&out->refit, D->upd_ev[2], D->upd_ev[3]));
+    out->level_launches = D->upd_levels;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_device_read(rt_scene *s, int device, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
+                                               uint32_t *slot_face, uint64_t slots_cap, float *tris, float *nrm, float root_box[6])
+{
+    if (!s || !info) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: NULL argument");
+    if (info->struct_size != sizeof(rt_device_bvh_info))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: rt_device_bvh_info.struct_size is %u, this library's is %zu", info->struct_size, sizeof(rt_device_bvh_info));
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: mesh %d was never set", mesh);
+    }
+    DeviceState *D = nullptr;
+    rt_status st = prepare_device(s, device, &D);
+    if (st) return st;
+    DeviceClaim claim(D);
+    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_device_read: another call on this scene is using device %d", device);
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
+    const DevMeshBufs &mb = D->mesh_bufs[mesh];
+    const size_t n_slots = mb.slot_face.size(), n_nodes = mb.level_off.empty() ? 0 : mb.level_off.back();
+    if (nodes && nodes_cap < n_nodes) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, n_nodes);
+    if ((slot_face || tris || nrm) && slots_cap < n_slots) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, n_slots);
+    HIP_TRY(hipStreamSynchronize(D->stream));
+    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, mb.nodes.p, n_nodes * sizeof(DevBvhNode), hipMemcpyDeviceToHost));
+    if (tris) HIP_TRY(hipMemcpy(tris, mb.tris.p, n_slots * sizeof(DevTri), hipMemcpyDeviceToHost));
+    if (nrm) HIP_TRY(hipMemcpy(nrm, mb.nrm.p, n_slots * 36, hipMemcpyDeviceToHost));
+    if (root_box) HIP_TRY(hipMemcpy(root_box, (const char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), 24, hipMemcpyDeviceToHost));
+    if (slot_face) memcpy(slot_face, mb.slot_face.data(), n_slots * 4);
+    info->n_nodes = (uint32_t)n_nodes; info->n_slots = (uint32_t)n_slots;
+    info->root_ref = mb.root_ref; info->stack_need = mb.stack_need;
+    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
+    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
     return RT_OK;
 }
 

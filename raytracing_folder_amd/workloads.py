@@ -80,6 +80,19 @@ def balls_scene(n_balls=128, nu=20, nv=21, seed=1):
     return np.concatenate(vs).astype(np.float32), np.concatenate(fs).astype(np.uint32)
 
 
+def deform_wave(v, phase, amplitude):
+    """the vertices of a deforming surface: along every axis a smooth sinusoidal displacement of `amplitude` (in the units of v)
+    driven by the other two coordinates, about one wavelength across the mesh's extent; `phase` (radians) moves the wave.
+    float32 in, float32 out, the same bytes for the same arguments."""
+    v = np.asarray(v, np.float32).reshape(-1, 3).astype(np.float64)
+    lo, hi = v.min(0), v.max(0)
+    u = (v - lo) / np.where(hi > lo, hi - lo, 1.0)                  # every coordinate in [0, 1]
+    d = np.stack([np.sin(2 * np.pi * (u[:, 1] + 0.37 * u[:, 2]) + phase + 0.4),
+                  np.sin(2 * np.pi * (u[:, 2] + 0.53 * u[:, 0]) + 1.7 * phase + 1.3),
+                  np.sin(2 * np.pi * (u[:, 0] + 0.71 * u[:, 1]) + 0.6 * phase + 2.2)], 1)
+    return (v + float(amplitude) * d).astype(np.float32)
+
+
 def write_obj(path, v, f):
     with open(path, "w") as o:
         for p in v:
