@@ -1,7 +1,7 @@
 // rt_api.cpp -- the part of the C ABI in include/rt_mi355x.h that needs no device state: errors, version, default parameters,
 // the scene store and its getters, the image and .dat wrappers, the host-side BVH and photon helpers.
-// Lowering a scene to the device layout of rt_dev.h is rt_lower.cpp, rendering from it rt_render.cpp, the image-space stages
-// rt_post.cpp; rt_host.h is what they share.
+// Lowering a scene to the device layout of rt_dev.h is rt_lower.cpp, the photon maps rt_photons.cpp, rendering rt_render.cpp, the
+// image-space stages rt_post.cpp; rt_host.h is what they share.
 // There is no CPU render path in this library: without a gfx950 device the render calls fail.
 #include <hip/hip_runtime.h>
 
@@ -185,7 +185,7 @@ extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, co
     m.tree_stale = true;
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
     // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
-    if (s->gen.valid) { s->drop_generated(); s->data.photons.clear(); s->invalidate(false, true); }
+    s->drop_generated_photons();
     if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }
     return refit_mesh_on_devices(s, mesh, vn != nullptr);
 }
@@ -406,31 +406,6 @@ extern "C" rt_status rt_image_sample_count(const uint8_t *sample_count, int32_t 
     return RT_OK;
 }
 
-extern "C" rt_status rt_scene_set_photons(rt_scene *s, const rt_photon *photons, uint32_t n_stored)
-{
-    rt_status st = check_idle(s, "rt_scene_set_photons");
-    if (st) return st;
-    if (n_stored > 0 && !photons) return fail(RT_ERR_ARG, "rt_scene_set_photons: photons is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->drop_generated();
-    if (n_stored == 0) s->data.photons.clear();
-    else s->data.photons.assign(photons, photons + (size_t)n_stored + 1);
-    s->invalidate(false, true);
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_set_caustic_photons(rt_scene *s, const rt_photon *photons, uint32_t n_stored)
-{
-    rt_status st = check_idle(s, "rt_scene_set_caustic_photons");
-    if (st) return st;
-    if (n_stored > 0 && !photons) return fail(RT_ERR_ARG, "rt_scene_set_caustic_photons: photons is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (n_stored == 0) s->data.caustic_photons.clear();
-    else s->data.caustic_photons.assign(photons, photons + (size_t)n_stored + 1);
-    s->invalidate(false, false, true);
-    return RT_OK;
-}
-
 extern "C" rt_status rt_scene_load_xml(rt_scene *s, const char *path)
 {
     rt_status st = check_idle(s, "rt_scene_load_xml");
@@ -442,7 +417,7 @@ extern "C" rt_status rt_scene_load_xml(rt_scene *s, const char *path)
     rt::SceneData d;
     if (!rt::Lower(graph, d, &err)) return fail(RT_ERR_ARG, "rt_scene_load_xml(%s): %s", path, err.c_str());
     std::lock_guard<std::mutex> lk(s->mu);
-    if (!s->gen.valid) d.photons = s->data.photons;      // a map the caller set stays; a generated one belonged to the old scene
+    if (!s->global_photons.is_generated()) d.photons = s->data.photons;      // a map the caller set stays; a generated one belonged to the old scene
     s->data = std::move(d);
     s->geometry_changed();
     return RT_OK;
@@ -464,7 +439,7 @@ extern "C" rt_status rt_scene_counts(const rt_scene *s, int32_t *n_nodes, int32_
     if (n_meshes) *n_meshes = (int32_t)s->data.meshes.size();
     if (n_materials) *n_materials = (int32_t)s->data.materials.size();
     if (n_lights) *n_lights = (int32_t)s->data.lights.size();
-    if (n_photons) *n_photons = s->photon_count();
+    if (n_photons) *n_photons = s->global_photons.count();
     return RT_OK;
 }
 

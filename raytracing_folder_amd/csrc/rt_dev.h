@@ -125,7 +125,7 @@ struct DevPhotonMap {
     // `start_radius` of ANY point of the cell -- every sibling subtree on the way down lies farther from the cell than that.
     // A query inside the grid with a radius <= start_radius starts its walk there instead of at the root (the levels above
     // are a chain of dependent box reads with one survivor each).  NULL / 0: start at the root.  Rebuilt when the gather
-    // radius grows (ensure_cell_start in rt_lower.cpp).
+    // radius grows (ensure_cell_start in rt_photons.cpp).
     const uint32_t *cell_start;
     float start_radius;
 };

@@ -1,6 +1,8 @@
 // rt_host.h -- private to the host files of the C ABI (not installed): what more than one of them needs.
 //   rt_api.cpp     what needs no device state: errors, the scene store and its getters, the image and .dat wrappers
-//   rt_lower.cpp   a scene and its photon maps onto a device (prepare_device), the photon pass, generate_photons
+//   rt_lower.cpp   a scene onto a device (prepare_device): SAH BVH, objects, mesh refit
+//   rt_photons.cpp the photon maps: their setters, the gather structures (upload_photons), the photon and caustic passes,
+//                  generate_photons, the global map's state (rt_photon_map.h) with its two device copies
 //   rt_render.cpp  render orchestration: working sets, run_pipeline, the render / packed / unpack entry points, jobs, the
 //                  single-stage entry points
 //   rt_post.cpp    the image-space stages (denoise .. motion blur)
@@ -18,6 +20,7 @@
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
 #include "rt_launch.h"
+#include "rt_photon_map.h"
 
 #define RT_HIDDEN __attribute__((visibility("hidden")))
 
@@ -187,39 +190,21 @@ struct DeviceClaim {
 
 struct rt_scene {
     rt::SceneData data;
-    // A photon map made by rt_scene_generate_photons is kept as generatePhotonMap leaves it BEFORE balancing (1-based,
-    // [0] zero) together with the indices of the few photons LocatePhotons could not reach after balancing
-    // (rt::UnreachablePhotons); data.photons (the balanced form) is produced from it only when somebody asks for it.
-    // Non-empty photons_raw takes precedence over data.photons; rt_scene_set_photons clears it.
-    std::vector<rt_photon> photons_raw;
-    std::vector<uint32_t> photons_skip;
-    // A map made by the photon pass (rt_scene_generate_photons, rt_render_begin) is DERIVED from the scene: whatever it was
-    // traced through (nodes, meshes, materials, lights, another XML) changing drops it, and rt_render_begin makes a new one when
-    // there is none or when the render asks for another count / bounce limit / seed -- the reference runs generatePhotonMap() on
-    // every BeginRender (FIN/main.cpp:984-990).  A map handed over with rt_scene_set_photons is the caller's: it stays.
-    struct Generated { bool valid = false; uint32_t count = 0; int bounce = 0; uint32_t seed = 0; } gen;
-    // ... and it STAYS on the device that generated it (DeviceState::raw_photons of gen_dev, gen_n photons) until somebody needs it
-    // on the host: the .dat dump, rt_scene_get_photons, another device, the host's replay of BalanceSegment when a median is not
-    // unique (raw_to_host in rt_lower.cpp).  gen_n != 0 with an empty photons_raw = "on gen_dev only".
-    DeviceState *gen_dev = nullptr; uint32_t gen_n = 0;
+    GlobalPhotons global_photons;       // the global photon map: whose it is and where it lies (rt_photon_map.h); its balanced form is data.photons
     std::string photon_dump;            // where rt_render_begin's photon pass writes its .dat ("" = nowhere)
     std::mutex gen_mu;                  // jobs started together on several devices: ONE of them runs the photon pass, the others wait for it
     std::mutex mu;
     std::vector<DeviceState *> devs;
     std::atomic<int> live_jobs{0};
     std::atomic<uint32_t> render_flags{0};      // RT_RENDER_*: read once at the start of every render call
-    uint32_t photon_count() const { return gen_n ? gen_n : (!photons_raw.empty() ? (uint32_t)photons_raw.size() - 1 : (data.photons.empty() ? 0u : (uint32_t)data.photons.size() - 1)); }
-    void drop_generated() { photons_raw.clear(); photons_skip.clear(); gen.valid = false; gen_dev = nullptr; gen_n = 0; }
     void invalidate(bool scene, bool photons, bool caustic = false)
     {
         for (DeviceState *d : devs) { if (scene) d->scene_valid = false; if (photons) d->maps[0].valid = false; if (caustic) d->maps[1].valid = false; }
     }
-    // geometry, materials or lights changed (caller holds mu): re-upload, and a generated photon map is no longer this scene's
-    void geometry_changed()
-    {
-        if (gen.valid) { drop_generated(); data.photons.clear(); invalidate(true, true); }
-        else invalidate(true, false);
-    }
+    // a generated photon map is no longer this scene's (caller holds mu): gone, with the structures built from it
+    void drop_generated_photons() { if (global_photons.drop_generated(data.photons)) invalidate(false, true); }
+    // geometry, materials or lights changed (caller holds mu): re-upload, and a generated photon map was traced through the old ones
+    void geometry_changed() { drop_generated_photons(); invalidate(true, false); }
 };
 
 // ---- what crosses the host files ----------------------------------------------------------------------------
@@ -231,6 +216,9 @@ RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normal
 // rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
 RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
 RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);
+// rt_photons.cpp: the gather structure of one of the two maps on D (prepare_device calls it for a map that is not valid there,
+// caller holds s->mu); the gather's cell table for a radius; generatePhotonMap as a whole
+RT_HIDDEN rt_status upload_photons(rt_scene *s, DeviceState *D, bool caustic);
 RT_HIDDEN rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float radius, hipStream_t st, bool *did_work = nullptr);
 RT_HIDDEN rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
                                      rt_setup_ms *ms_out, bool own_job);

@@ -1,4 +1,4 @@
-// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
+// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_photons.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
@@ -336,8 +336,9 @@ hipError_t rtk_photon_structure(hipStream_t st, const rt_photon *ph, uint32_t n,
                                 uint32_t *grid, PhotonGridOut *grid_out, void *scratch, size_t scratch_bytes);
 size_t rtk_photon_unreachable_scratch(uint32_t n);
 // ph0: the photons as generated, 1-based ([0] all zero), on the device.  Heap slots [first, last] are wanted.  result (host):
-// [0] = number of photons found, [1] = 1 when a median's key was not unique (the caller must use the host's exact replay),
-// [2..] = their 1-based raw indices (unsorted).  Returns after the stream has been synchronised.
+// [0] = number of photons found, [1] = 1 when a median's key was not unique, 2 when the root paths need more levels or segments
+// than the search holds (either way the caller must use the host's exact replay), [2..] = their 1-based raw indices (unsorted).
+// Returns after the stream has been synchronised.
 hipError_t rtk_photon_unreachable(hipStream_t st, const rt_photon *ph0, uint32_t n, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes,
                                   uint32_t result[16]);
 // (position, raw index) records of photons [0, n], 16 bytes each: what the host's replay of BalanceSegment works on

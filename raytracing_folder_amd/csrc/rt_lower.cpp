@@ -1,13 +1,11 @@
-// rt_lower.cpp -- what puts a scene and its photon maps on a device: the lowering of the scene store (rt_api.cpp) to the device
-// layout of rt_dev.h, the gather structures of the two photon maps, and the photon pass that generates a map on the device.
-// rt_render.cpp renders from what prepare_device leaves here; rt_host.h is what the host files share.
+// rt_lower.cpp -- what puts a scene on a device: the lowering of the scene store (rt_api.cpp) to the device layout of rt_dev.h,
+// the tree the kernels walk, in-place mesh updates.  prepare_device has rt_photons.cpp put the two photon maps beside it;
+// rt_render.cpp renders from what it leaves; rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -567,116 +565,6 @@ extern "C" rt_status rt_scene_mesh_device_read(rt_scene *s, int device, int32_t 
     return RT_OK;
 }
 
-// Gather structure of a photon map (rt_dev.h, built by rt_photon_build.hip on the GPU): the photons LocatePhotons can reach
-// -- it descends only while index < halfStoredPhotons = n/2 - 1, cyPhotonMap.h:217,371, so heap slots >= 2*half are never
-// visited: for a balanced array that is a prefix, for an unbalanced one everything but the `skip` indices -- re-sorted by
-// recursive median splits into 2^D sub-leaves of <= RT_SUB_PHOTONS photons with their tight boxes; RT_LEAF_SUBS consecutive
-// sub-leaves are one leaf (128 slots) of the tree the queries walk (boxes of all heap nodes in `box4`: the tree over the
-// leaves is its head, the sub-leaf boxes its last level).  `src_dev` != NULL: the photons already sit on this device
-// (n_src records, 0-based); else they are uploaded from `src_host`.  skip: ascending 0-based positions to leave out.
-static rt_status build_photon_structure(DeviceState *D, bool caustic, const rt_photon *src_dev, const rt_photon *src_host, uint32_t n_src,
-                                        const uint32_t *skip, uint32_t n_skip, double *ms_upload, double *ms_build)
-{
-    using clk = std::chrono::steady_clock;
-    auto [M, pm] = D->map(caustic);
-    // nothing is published before the build and its final synchronisation have succeeded: a failure leaves the device WITHOUT a
-    // valid map, so the next render tries again (and fails as loudly) instead of rendering without global illumination
-    memset(&pm, 0, sizeof pm);
-    M.valid = false;
-    struct TempBuf : DevBuf { ~TempBuf() { release(); } };      // released on every path out of this function
-    if (n_src <= n_skip) { M.valid = true; return RT_OK; }
-    if (n_skip > 8) return fail(RT_ERR_LIMIT, "photon structure: %u photons to leave out, the device copy takes at most 8 (rt::UnreachablePhotons yields at most 4)", n_skip);
-    const uint32_t n = n_src - n_skip;
-    uint32_t n_leaves = 1;
-    while ((size_t)n_leaves * RT_LEAF_SUBS * RT_SUB_PHOTONS < n) n_leaves <<= 1;
-    // leaf ids travel as 16-bit values through the kernel's LDS lists; slots are addressed by 32-bit byte offsets
-    if (n_leaves > 65536) return fail(RT_ERR_LIMIT, "photon map too large for the gather structure (%u photons, at most 8 Mi)", n);
-    static_assert((65536ull * RT_LEAF_SUBS + 1) * RT_SUB_PHOTONS * sizeof(float4) <= 0xFFFFFFFFull, "photon slots are addressed by 32-bit byte offsets");
-    const uint32_t n_sub = n_leaves * RT_LEAF_SUBS;
-    rt_status st;
-    hipStream_t stream = D->stream;
-    const auto t0 = clk::now();
-    TempBuf staged, compacted, scratch;
-    const rt_photon *ph = src_dev;
-    if (!ph) {
-        if ((st = staged.ensure((size_t)n_src * sizeof(rt_photon)))) return st;
-        HIP_TRY(hipMemcpyAsync(staged.p, src_host, (size_t)n_src * sizeof(rt_photon), hipMemcpyHostToDevice, stream));
-        ph = (const rt_photon *)staged.p;
-    }
-    if (n_skip) {
-        if ((st = compacted.ensure((size_t)n * sizeof(rt_photon)))) return st;
-        rtk_photon_copy_skipping(stream, ph, n_src, skip, n_skip, (rt_photon *)compacted.p);
-        ph = (const rt_photon *)compacted.p;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    const auto t1 = clk::now();
-    // one more sub-leaf than the tree has, every slot empty: the kernel pads its sub-leaf lists with it
-    const size_t slots = ((size_t)n_sub + 1) * RT_SUB_PHOTONS;
-    const size_t sbytes = rtk_photon_structure_scratch(n, n_sub);
-    if ((st = M.pa.ensure(slots * sizeof(float4))) || (st = M.pb.ensure(slots * sizeof(float4))) || (st = M.box4.ensure((size_t)4 * n_sub * sizeof(float4))) ||
-        (st = M.grid.ensure((size_t)64 * 64 * 64 * 4)) || (st = scratch.ensure(sbytes))) return st;
-    PhotonGridOut g;
-    const hipError_t e = rtk_photon_structure(stream, ph, n, n_sub, (float4 *)M.pa.p, (float4 *)M.pb.p, (float4 *)M.box4.p, (uint32_t *)M.grid.p, &g, scratch.p, sbytes);
-    hipError_t e2 = hipStreamSynchronize(stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(RT_ERR_DEVICE, "photon structure build failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    DevPhotonMap built;
-    memset(&built, 0, sizeof built);
-    built.pa = (const float4 *)M.pa.p; built.pb = (const float4 *)M.pb.p;
-    built.tbox = (const float4 *)M.box4.p; built.sbox = (const float4 *)M.box4.p + 2 * (size_t)n_sub;
-    built.n_leaves = n_leaves; built.n_photons = n;
-    built.grid = (const uint32_t *)M.grid.p;
-    for (int a = 0; a < 3; a++) { built.grid_min[a] = g.min[a]; built.grid_dim[a] = g.dim[a]; }
-    built.cell = g.cell; built.inv_cell = 1.0f / g.cell;
-    if ((st = M.cell_rk2.ensure((size_t)64 * 64 * 64 * 4))) return st;
-    HIP_TRY(hipMemsetAsync(M.cell_rk2.p, 0, (size_t)64 * 64 * 64 * 4, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    pm = built;
-    M.valid = true;
-    M.rk2_k = 0;                                    // the hint table is empty: no gather parameters recorded yet
-    const auto t2 = clk::now();
-    if (ms_upload) *ms_upload += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (ms_build) *ms_build += std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return RT_OK;
-}
-
-// the generated photons on the host (caller holds s->mu): copied from the device that made them, once
-static rt_status raw_to_host(rt_scene *s)
-{
-    if (!s->gen_n || !s->photons_raw.empty()) return RT_OK;
-    if (!s->gen_dev || !s->gen_dev->raw_photons.p) return fail(RT_ERR_STATE, "the generated photon map is gone from its device");
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    HIP_TRY(hipSetDevice(s->gen_dev->device));
-    std::vector<rt_photon> raw((size_t)s->gen_n + 1);
-    HIP_TRY(hipMemcpy(raw.data(), s->gen_dev->raw_photons.p, raw.size() * sizeof(rt_photon), hipMemcpyDeviceToHost));
-    HIP_TRY(hipSetDevice(cur));
-    s->photons_raw.swap(raw);
-    return RT_OK;
-}
-
-static rt_status upload_photons(rt_scene *s, DeviceState *D, bool caustic)
-{
-    if (!caustic && s->gen_n) {
-        std::vector<uint32_t> skip0;
-        for (uint32_t i : s->photons_skip) skip0.push_back(i - 1);              // 1-based raw index -> position in [1..n]
-        if (D == s->gen_dev && D->raw_photons.p)                                 // still on this device
-            return build_photon_structure(D, false, (const rt_photon *)D->raw_photons.p + 1, nullptr, s->gen_n, skip0.data(), (uint32_t)skip0.size(), nullptr, nullptr);
-        rt_status st = raw_to_host(s);                                           // another device: through the host
-        if (st) return st;
-        HIP_TRY(hipSetDevice(D->device));
-    }
-    if (!caustic && !s->photons_raw.empty()) {
-        // as generated (unbalanced): everything but the photons balancing would put out of LocatePhotons' reach
-        std::vector<uint32_t> skip0;
-        for (uint32_t i : s->photons_skip) skip0.push_back(i - 1);              // 1-based raw index -> position in [1..n]
-        return build_photon_structure(D, false, nullptr, s->photons_raw.data() + 1, (uint32_t)s->photons_raw.size() - 1, skip0.data(), (uint32_t)skip0.size(), nullptr, nullptr);
-    }
-    const std::vector<rt_photon> &ph = caustic ? s->data.caustic_photons : s->data.photons;
-    if (ph.size() < 2) { auto [M, pm] = D->map(caustic); memset(&pm, 0, sizeof(DevPhotonMap)); M.valid = true; return RT_OK; }
-    const uint32_t n = (uint32_t)ph.size() - 1;
-    return build_photon_structure(D, caustic, nullptr, ph.data() + 1, rt::ReachablePhotonSlots(n), nullptr, 0, nullptr, nullptr);
-}
-
 rt_status prepare_device(rt_scene *s, int device, DeviceState **out)
 {
     int n = 0;
@@ -695,271 +583,5 @@ rt_status prepare_device(rt_scene *s, int device, DeviceState **out)
     for (int caustic = 0; caustic < 2; caustic++)
         if (!D->maps[caustic].valid && (st = upload_photons(s, D, caustic != 0))) return st;
     *out = D;
-    return RT_OK;
-}
-
-// DevPhotonMap::cell_start for the radius the gather is about to use: built on first use and again when a larger radius comes
-// (a table built for a radius serves every smaller one), on the stream the gather will run on
-rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float radius, hipStream_t st, bool *did_work)
-{
-    auto [M, pm] = D->map(caustic);
-    // the per-cell k-th distances (PhotonStore::cell_rk2) are hints of ONE gather configuration: what queries with another k
-    // or radius left there is dropped, so that it cannot steer this render's choice between the (exact) gather paths
-    if (M.cell_rk2.p && M.rk2_k != 0 && (M.rk2_k != k || M.rk2_radius != radius)) {
-        HIP_TRY(hipMemsetAsync(M.cell_rk2.p, 0, (size_t)64 * 64 * 64 * 4, st));
-        if (did_work) *did_work = true;
-    }
-    M.rk2_k = k; M.rk2_radius = radius;
-    if (pm.n_leaves < 2 || (pm.cell_start && radius <= pm.start_radius)) return RT_OK;
-    rt_status s = M.cell_start.ensure((size_t)64 * 64 * 64 * 4);
-    if (s) return s;
-    rtk_photon_cell_start(st, pm.tbox, pm.n_leaves, pm.grid_min, pm.cell, pm.grid_dim, radius, (uint32_t *)M.cell_start.p);
-    HIP_TRY(hipGetLastError());
-    if (did_work) *did_work = true;
-    pm.cell_start = (const uint32_t *)M.cell_start.p; pm.start_radius = radius;
-    return RT_OK;
-}
-
-// ---- photon pass ----------------------------------------------------------------------------------------
-// generatePhotonMap's two loops (P13/main.cpp:338-404): mode 0 = the photon map (stop when max_count photons are STORED),
-// mode 1 = the caustic map (stop when max_count diffuse hits are COUNTED; only those behind more than one specular
-// hit are stored).  Attempts are consumed in order, the count checked between attempts like the reference's while().
-// Everything stays on the device: k_photon_trace writes each attempt's photons, rtk_photon_compact (rt_photon_build.hip)
-// consumes the attempts in order and packs the stored photons into D->raw_photons (1-based, [0] zero), then
-// ScalePhotonPowers.  The caller holds the device claim.
-static rt_status photon_pass_device(rt_scene *s, DeviceState *D, uint32_t max_count, int photon_bounce, uint32_t seed, int mode,
-                                    uint32_t *n_out, uint64_t *attempts_out, const char *who)
-{
-    if (max_count == 0 || photon_bounce < 1 || photon_bounce > 8) return fail(RT_ERR_ARG, "%s: need a positive count and 1 <= photon_bounce <= 8", who);
-    if (max_count > (1u << 28)) return fail(RT_ERR_LIMIT, "%s: at most 2^28 photons", who);
-    bool have_source = false;
-    for (const rt_light &l : s->data.lights) if (l.type == RT_LIGHT_POINT) have_source = true;
-    if (!have_source) return fail(RT_ERR_STATE, "%s: the scene has no photon source (point light)", who);
-    rt_status st;
-    {   // D->raw_photons is about to be overwritten: a generated map that lives only there goes to the host first
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->gen_dev == D && s->gen_n && s->photons_raw.empty() && (st = raw_to_host(s))) return st;
-    }
-    const uint32_t batch = 1u << 18;
-    static_assert((1u << 18) / RT_BLOCK <= RT_SPILL_BLOCKS, "DevScene::bvh_spill is sized for RT_SPILL_BLOCKS workgroups");
-    const uint32_t out_cap = max_count + 8 + 1;                 // index 0 unused, up to 7 photons of overshoot
-    if ((st = D->t_out[0].ensure((size_t)batch * 8 * 9 * 4))) return st;
-    if ((st = D->t_out[1].ensure((size_t)batch * 4))) return st;
-    if ((st = D->t_out[2].ensure(2 * sizeof(CompactState)))) return st;
-    const size_t sbytes = rtk_photon_compact_scratch(batch);
-    if ((st = D->t_out[3].ensure(sbytes))) return st;
-    if ((st = D->raw_photons.ensure((size_t)out_cap * sizeof(rt_photon)))) return st;
-    hipStream_t stream = D->stream;
-    HIP_TRY(hipMemsetAsync(D->t_out[2].p, 0, 2 * sizeof(CompactState), stream));
-    HIP_TRY(hipMemsetAsync(D->raw_photons.p, 0, sizeof(rt_photon), stream));
-    CompactState h{0, 0, 0, 0};
-    int empty_batches = 0;
-    while (h.counted < max_count) {
-        PhotonArgs pa = {};
-        pa.first_attempt = h.attempts; pa.n_attempts = batch; pa.seed = seed; pa.max_bounce = photon_bounce; pa.mode = mode;
-        pa.out = (float *)D->t_out[0].p; pa.count = (uint32_t *)D->t_out[1].p;
-        rtk_launch_photon_trace(stream, D->scene, pa);
-        rtk_photon_compact(stream, pa.out, pa.count, batch, mode, max_count, (CompactState *)D->t_out[2].p,
-                           (rt_photon *)D->raw_photons.p, out_cap, D->t_out[3].p, sbytes);
-        HIP_TRY(hipGetLastError());
-        const unsigned long long before = h.counted;
-        HIP_TRY(hipMemcpyAsync(&h, D->t_out[2].p, sizeof h, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (h.counted == before && ++empty_batches >= 4) return fail(RT_ERR_STATE, "%s: no photon is ever stored in this scene", who);
-    }
-    uint32_t n = h.stored;
-    if (n + 1 > out_cap) n = out_cap - 1;
-    if (n > 0) rtk_photon_scale(stream, (rt_photon *)D->raw_photons.p, n, (float)(1.0 * 4 * M_PI / n));      // ScalePhotonPowers(1.0*4*M_PI/NumPhotons), :366 / :400
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = n;
-    if (attempts_out) *attempts_out = h.attempts;
-    return RT_OK;
-}
-
-static rt_status photon_pass(rt_scene *s, int device, uint32_t max_count, int photon_bounce, uint32_t seed, int mode,
-                             rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out, const char *who)
-{
-    if (!s || !out || !n_out) return fail(RT_ERR_ARG, "%s: NULL argument", who);
-    if (max_count == 0 || photon_bounce < 1 || photon_bounce > 8) return fail(RT_ERR_ARG, "%s: need a positive count and 1 <= photon_bounce <= 8", who);
-    if (out_cap < max_count + 8 + 1) return fail(RT_ERR_ARG, "%s: out must hold the count + 9 records (index 0 unused, up to 7 photons of overshoot)", who);
-    DeviceState *D = nullptr;
-    rt_status st = prepare_device(s, device, &D);
-    if (st) return st;
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "%s: another call on this scene is using device %d", who, device);
-    if ((st = order_after_pending(D, D->stream))) return st;
-    uint32_t n = 0;
-    if ((st = photon_pass_device(s, D, max_count, photon_bounce, seed, mode, &n, attempts_out, who))) return st;
-    HIP_TRY(hipMemcpy(out, D->raw_photons.p, ((size_t)n + 1) * sizeof(rt_photon), hipMemcpyDeviceToHost));
-    *n_out = n;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_photon_pass(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed,
-                                    rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out)
-{
-    return photon_pass(s, device, max_photons, photon_bounce, seed, 0, out, out_cap, n_out, attempts_out, "rt_photon_pass");
-}
-
-extern "C" rt_status rt_caustic_pass(rt_scene *s, int device, uint32_t max_diffuse_hits, int photon_bounce, uint32_t seed,
-                                     rt_photon *out, uint32_t out_cap, uint32_t *n_out, uint64_t *attempts_out)
-{
-    return photon_pass(s, device, max_diffuse_hits, photon_bounce, seed, 1, out, out_cap, n_out, attempts_out, "rt_caustic_pass");
-}
-
-// generatePhotonMap as a whole (FIN/main.cpp:350-402).  `own_job`: called from the job thread of rt_render_begin (the scene
-// counts that job as live; no other caller can be inside the scene then).
-rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
-                           rt_setup_ms *ms_out, bool own_job)
-{
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    if (!s) return fail(RT_ERR_ARG, "rt_scene_generate_photons: scene is NULL");
-    rt_status st;
-    if (!own_job && (st = check_idle(s, "rt_scene_generate_photons"))) return st;
-    rt_setup_ms T;
-    memset(&T, 0, sizeof T);
-    const auto t_begin = clk::now();
-    DeviceState *D = nullptr;
-    if ((st = prepare_device(s, device, &D))) return st;
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_generate_photons: another call on this scene is using device %d", device);
-    if ((st = order_after_pending(D, D->stream))) return st;
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));       // the structure is rebuilt in place
-    {   // the map this call replaces: if it lives only on this device, it is simply dropped (not fetched to the host first)
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (s->gen_n && s->gen_dev == D && s->photons_raw.empty()) { s->drop_generated(); s->invalidate(false, true); }
-    }
-    const auto t0 = clk::now();
-    uint32_t n = 0;
-    if ((st = photon_pass_device(s, D, max_photons, photon_bounce, seed, 0, &n, nullptr, "rt_scene_generate_photons"))) return st;
-    const auto t1 = clk::now();
-    T.photon_pass = ms(t0, t1);
-    // Which photons balancing would put out of LocatePhotons' reach (heap slots > ReachablePhotonSlots(n): the last three or four):
-    // found ON THE DEVICE along the root paths of those slots (rt_photon_build.hip: photon_unreachable); the photons stay where
-    // they are.  They come to the host only for the .dat dump, or when a median's key is not unique in its segment (then the
-    // reference's swap sequence decides and the host replays it: rt::UnreachablePhotons).
-    std::vector<rt_photon> raw;
-    auto fetch = [&]() -> rt_status {
-        if (!raw.empty()) return RT_OK;
-        raw.resize((size_t)n + 1);
-        HIP_TRY(hipMemcpy(raw.data(), D->raw_photons.p, raw.size() * sizeof(rt_photon), hipMemcpyDeviceToHost));
-        return RT_OK;
-    };
-    const auto t2 = clk::now();
-    if (dat_path && dat_path[0]) {
-        if ((st = fetch())) return st;
-        if ((st = rt_photons_write_dat(dat_path, raw.data(), n))) return st;
-    }
-    const auto t2b = clk::now();
-    T.upload = ms(t2, t2b);
-    std::vector<uint32_t> skip;
-    const uint32_t reach = rt::ReachablePhotonSlots(n);
-    if (n && reach < n) {
-        bool on_device = false;
-        {
-            struct TempBuf : DevBuf { ~TempBuf() { release(); } } scratch;
-            const size_t sbytes = rtk_photon_unreachable_scratch(n);
-            uint32_t res[16];
-            if (getenv("RT_UNREACHABLE_ON_HOST") == nullptr && scratch.ensure(sbytes) == RT_OK &&
-                rtk_photon_unreachable(D->stream, (const rt_photon *)D->raw_photons.p, n, reach + 1, n, scratch.p, sbytes, res) == hipSuccess &&
-                res[1] == 0 && res[0] == n - reach) {
-                skip.assign(res + 2, res + 2 + res[0]);
-                std::sort(skip.begin(), skip.end());
-                on_device = true;
-            } else (void)hipGetLastError();
-        }
-        if (!on_device) {
-            // the host's replay of BalanceSegment on (position, index) records packed on the device: 16 bytes per photon come over
-            struct TempBuf : DevBuf { ~TempBuf() { release(); } } packed;
-            if ((st = packed.ensure(((size_t)n + 1) * 16))) return st;
-            rtk_photon_pack_positions(D->stream, (const rt_photon *)D->raw_photons.p, n, packed.p);
-            std::vector<rt::PhotonPosRec> recs((size_t)n + 1);
-            HIP_TRY(hipMemcpyAsync(recs.data(), packed.p, recs.size() * 16, hipMemcpyDeviceToHost, D->stream));
-            HIP_TRY(hipStreamSynchronize(D->stream));
-            rt::UnreachablePhotonRecs(recs.data(), n, skip);
-        }
-    }
-    const auto t3 = clk::now();
-    T.balance = ms(t2b, t3);
-    std::vector<uint32_t> skip0;
-    for (uint32_t i : skip) skip0.push_back(i - 1);
-    double up = 0, build = 0;
-    if ((st = build_photon_structure(D, false, (const rt_photon *)D->raw_photons.p + 1, nullptr, n, skip0.data(), (uint32_t)skip0.size(), &up, &build))) return st;
-    T.upload += up; T.structure_build = build;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        s->data.photons.clear();
-        s->photons_raw.swap(raw);                 // empty unless the photons had to come to the host
-        s->photons_skip.swap(skip);
-        s->gen.valid = true; s->gen.count = max_photons; s->gen.bounce = photon_bounce; s->gen.seed = seed;
-        s->gen_dev = D; s->gen_n = n;
-        for (DeviceState *d : s->devs) if (d != D) d->maps[0].valid = false;
-    }
-    T.total = ms(t_begin, clk::now());
-    if (ms_out) *ms_out = T;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed,
-                                               const char *dat_path, rt_setup_ms *ms_out)
-{
-    return generate_photons(s, device, max_photons, photon_bounce, seed, dat_path, ms_out, false);
-}
-
-extern "C" rt_status rt_scene_set_photon_dump(rt_scene *s, const char *dat_path)
-{
-    rt_status st = check_idle(s, "rt_scene_set_photon_dump");
-    if (st) return st;
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->photon_dump = dat_path ? dat_path : "";
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_get_photons(rt_scene *s, rt_photon *out, uint32_t cap, uint32_t *n_stored)
-{
-    if (!s) return fail(RT_ERR_ARG, "rt_scene_get_photons: scene is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    const uint32_t n = s->photon_count();
-    if (n_stored) *n_stored = n;
-    if (!out) return RT_OK;
-    if (cap < n + 1) return fail(RT_ERR_ARG, "rt_scene_get_photons: buffer of %u records, %u needed", cap, n + 1);
-    if (n == 0) { memset(out, 0, sizeof(rt_photon)); return RT_OK; }
-    { rt_status st = raw_to_host(s); if (st) return st; }
-    if (!s->photons_raw.empty() && s->data.photons.empty()) {
-        // PrepareForIrradianceEstimation (cyPhotonMap.h:196-218) of the generated photons, bit for bit, on first request
-        std::vector<rt_photon> tmp = s->photons_raw;
-        s->data.photons.resize(tmp.size());
-        rt::BalancePhotons(tmp.data(), n, s->data.photons.data());
-    }
-    memcpy(out, s->data.photons.data(), ((size_t)n + 1) * sizeof(rt_photon));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_photon_unreachable_device(int device, const rt_photon *in, uint32_t n, uint32_t *raw_indices, uint32_t cap, uint32_t *count, int32_t *exact)
-{
-    if (!in || !count || !exact) return fail(RT_ERR_ARG, "rt_photon_unreachable_device: NULL argument");
-    *count = 0; *exact = 1;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "rt_photon_unreachable_device: device %d is not gfx950 (no CPU path: rt_photon_unreachable is the host's)", device);
-    const uint32_t reach = rt::ReachablePhotonSlots(n);
-    if (n == 0 || reach >= n) return RT_OK;
-    HIP_TRY(hipSetDevice(device));
-    struct TempBuf : DevBuf { ~TempBuf() { release(); } } ph, scratch;
-    rt_status st;
-    if ((st = ph.upload(in, ((size_t)n + 1) * sizeof(rt_photon)))) return st;
-    HIP_TRY(hipMemset(ph.p, 0, sizeof(rt_photon)));                  // slot 0 is the unused all-zero photon
-    const size_t sbytes = rtk_photon_unreachable_scratch(n);
-    if ((st = scratch.ensure(sbytes))) return st;
-    uint32_t res[16];
-    const hipError_t e = rtk_photon_unreachable(nullptr, (const rt_photon *)ph.p, n, reach + 1, n, scratch.p, sbytes, res);
-    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_photon_unreachable_device: %s", hipGetErrorString(e));
-    if (res[1] != 0 || res[0] != n - reach) { *exact = 0; return RT_OK; }
-    std::vector<uint32_t> idx(res + 2, res + 2 + res[0]);
-    std::sort(idx.begin(), idx.end());
-    *count = (uint32_t)idx.size();
-    if (raw_indices) {
-        if (cap < idx.size()) return fail(RT_ERR_ARG, "rt_photon_unreachable_device: room for %u indices, %zu needed", cap, idx.size());
-        memcpy(raw_indices, idx.data(), idx.size() * 4);
-    }
     return RT_OK;
 }

@@ -11,7 +11,7 @@
 //
 // k_gather returns the exact k nearest photons whatever the partition, so this build only has to be a GOOD partition
 // (balanced, tight boxes), not the reference's left-balanced heap: the heap order is only needed to know which photons
-// LocatePhotons can never reach (cyPhotonMap.h:217,371) and is found on the host for those few (rt_lower.cpp).
+// LocatePhotons can never reach (cyPhotonMap.h:217,371) and is found on the host for those few (rt_photons.cpp).
 // Sort and scan are rocPRIM's (hipcub front end); everything else is written here.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -281,8 +281,9 @@ size_t rtk_photon_unreachable_scratch(uint32_t n)
     return (((size_t)n + 1) * 4 + 255 & ~(size_t)255) + (size_t)UR_MAX_LEVELS * UR_MAX_SEGS * (sizeof(UrSeg) + 3 * UR_BINS * 4) + 1024;
 }
 // ph0: the photons as generated, 1-based ([0] all zero), on the device.  Heap slots [first, last] are wanted.  result (host):
-// [0] = number of photons found, [1] = 1 when a median's key was not unique (the caller must use the host's exact replay),
-// [2..] = their 1-based raw indices (unsorted).  Returns after the stream has been synchronised.
+// [0] = number of photons found, [1] = 1 when a median's key was not unique, 2 when the root paths need more levels or segments
+// than the search holds (either way the caller must use the host's exact replay), [2..] = their 1-based raw indices (unsorted).
+// Returns after the stream has been synchronised.
 hipError_t rtk_photon_unreachable(hipStream_t st, const rt_photon *ph0, uint32_t n, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes,
                                   uint32_t result[16])
 {
@@ -312,7 +313,7 @@ hipError_t rtk_photon_unreachable(hipStream_t st, const rt_photon *ph0, uint32_t
             else if (nright >= 2 && holds(2 * S.index + 1)) { UrSeg c; memset(&c, 0, sizeof c); c.index = 2 * S.index + 1; c.count = nright; c.left_next = c.right_next = -1; S.right_next = (int32_t)nxt.size(); nxt.push_back(c); }
         }
         if (!nxt.empty()) sched.push_back(nxt);
-        if (sched.size() > UR_MAX_LEVELS || nxt.size() > UR_MAX_SEGS) return hipErrorInvalidValue;
+        if (sched.size() > UR_MAX_LEVELS || nxt.size() > UR_MAX_SEGS) { result[1] = 2; return hipSuccess; }      // not a runtime error: nothing was started
     }
     // ---- device buffers inside `scratch` ----
     char *base = (char *)scratch;

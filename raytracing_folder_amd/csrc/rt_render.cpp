@@ -1196,9 +1196,8 @@ static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *ca
                 std::string dump;
                 {
                     std::lock_guard<std::mutex> lk(s->mu);
-                    // a generated map serves only the parameters it was generated with (see rt_scene::gen)
-                    const bool stale = s->gen.valid && (s->gen.count != (uint32_t)pv.photon_count || s->gen.bounce != pv.photon_bounce || s->gen.seed != pv.seed);
-                    have_map = s->photon_count() != 0 && !stale;
+                    // a generated map serves only the parameters it was generated with (rt_photon_map.h)
+                    have_map = s->global_photons.serves((uint32_t)pv.photon_count, pv.photon_bounce, pv.seed);
                     dump = s->photon_dump;
                 }
                 for (const rt_light &l : s->data.lights) if (l.type == RT_LIGHT_POINT) have_source = true;

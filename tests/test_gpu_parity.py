@@ -1505,6 +1505,34 @@ def test_unreachable_photons_found_on_the_device_equal_the_host_replay():
     assert s1.get_photons().tobytes() == s2.get_photons().tobytes() and np.array_equal(i1, i2) and np.array_equal(d1, d2)
 
 
+def test_generated_photon_map_survives_a_later_pass_on_its_device():
+    """A generated map lies only in the buffer its photon pass left on the device.  rt_photon_pass and rt_caustic_pass on the same
+    scene and device overwrite that buffer with another photon set: the scene's map must come to the host first and stay what it
+    was -- its count, its photons (against the long way round: a fresh scene's photon pass, balanced on the host) and every estimate
+    from it -- and the next rt_scene_generate_photons must replace it as usual.  The same device code runs on the same bytes, so
+    every comparison is exact."""
+    want = {}
+    for seed in (5, 7):
+        raw, _ = scenes.load_cornell()[0].photon_pass(3000, 8, seed=seed)
+        want[seed] = capi.photon_balance(raw)
+    pos = want[5]["position"][1:41] + np.float32(0.01)
+    nrm = np.tile(np.array([[0, 0, 1]], np.float32), (len(pos), 1))
+    for later_pass in ("photon_pass", "caustic_pass"):
+        s, _ = scenes.load_cornell()
+        s.generate_photons(3000, 8, seed=5)
+        n = s.counts()["photons"]
+        assert n == len(want[5]) - 1
+        i0, d0 = s.estimate_irradiance(50, 2.0, pos, nrm)
+        assert (i0.max(axis=1) > 0).any()
+        getattr(s, later_pass)(1000, 8, seed=6)                          # overwrites the buffer the map was generated into
+        assert s.counts()["photons"] == n
+        assert s.get_photons().tobytes() == want[5].tobytes()
+        i1, d1 = s.estimate_irradiance(50, 2.0, pos, nrm)
+        assert np.array_equal(i0, i1) and np.array_equal(d0, d1)
+        s.generate_photons(3000, 8, seed=7)
+        assert s.get_photons().tobytes() == want[7].tobytes()
+
+
 def test_full_size_frame_properties():
     """BASELINE size (1920 x 1080) with 2 fixed samples: size-independent properties"""
     s, cam = scenes.load_cornell(1920, 1080)

@@ -274,6 +274,17 @@ def scenes_mod():
     return scenes
 
 
+def test_global_photon_map_record_holds_its_invariant_through_every_transition(tmp_path):
+    """tests/photon_map_states.cpp: csrc/rt_photon_map.h compiled alone (no HIP, devices as fake addresses) and walked from no map
+    through the caller's, a generated one on its device, off it to the host, adopted on another device, dropped by a geometry
+    change, and replaced by set_photons -- after every step the invariant, count(), serves() and source_on()"""
+    exe = str(tmp_path / "photon_map_states")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "photon_map_states.cpp")],
+                   check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stderr
+
+
 def test_synthetic_photon_map_is_well_formed():
     bal = photons.synth_cornell_photon_map(5000, seed=3)
     assert len(bal) == 5001
