@@ -470,8 +470,20 @@ rt_status rt_caustic_pass(rt_scene *s, int device, uint32_t max_diffuse_hits, in
  * rt_render_begin job on the scene is live: RT_ERR_STATE.  The flags survive scene edits; a render reads them when it
  * is called, so asynchronous renders already enqueued keep the mode they were enqueued with. */
 #define RT_RENDER_REPRODUCIBLE 1u
+/* RT_RENDER_GENERAL_SHADING (a test hook, not a tuning knob; bit 1 stays unassigned): the lowering of the scene leaves every
+ * material's class word clear (rt_scene_material_classes), so the FIN shading kernels run MtlBlinn::Shade in full for every hit
+ * instead of leaving out the terms a material class makes exactly +0.  Promised: the same bytes in every plane and the same
+ * rt_stats as without the flag -- which is what the flag is there to check, inside one library build.  Changing this bit
+ * makes the next use of a device lower the scene again. */
+#define RT_RENDER_GENERAL_SHADING 4u
 rt_status rt_scene_set_render_flags(rt_scene *s, uint32_t flags);
 rt_status rt_scene_get_render_flags(const rt_scene *s, uint32_t *flags);
+/* The class word of every material as the lowering sets it (host only: no device, no HIP call): RT_MAT_NO_SPEC_TREE (1) =
+ * reflection and refraction are +0.0f in every channel and ior is finite and > 0; RT_MAT_NO_SPECULAR (2) = specular is +0.0f in
+ * every channel, it has no texture map and glossiness is finite and in [0, 2^20].  Bit patterns are compared: -0.0f or a NaN
+ * leaves the bit clear.  All words are 0 under RT_RENDER_GENERAL_SHADING.  *n_out (may be NULL) = number of materials; out (may
+ * be NULL with cap 0) needs room for that many words, else RT_ERR_ARG. */
+rt_status rt_scene_material_classes(const rt_scene *s, uint32_t *out, int32_t cap, int32_t *n_out);
 
 /* ---- rendering: replaces BeginRender/StopRender + RenderPixel + RenderImage progress
  *      (FIN/main.cpp:202-344,984-1012; FIN/include/scene.h:586-589) ---------------------- */

@@ -267,6 +267,7 @@ SYMBOLS = [
     "rt_tiles_packed_planes_size", "rt_render_tiles_packed_outputs_device", "rt_tiles_unpack_outputs_device",
     "rt_scene_mesh_device_bvh",
     "rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms",
+    "rt_scene_material_classes",
 ]
 
 # rt_scene_update_mesh_vertices flags (include/rt_mi355x.h): build the tree again instead of refitting it in place
@@ -274,6 +275,11 @@ MESH_UPDATE_REBUILD = 1
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
+# ... and the test hook that leaves every material's class word clear (FIN shading runs in full for every hit)
+RENDER_GENERAL_SHADING = 4
+# class bits of a material (rt_scene_material_classes; RT_MAT_* in csrc/rt_dev.h)
+MAT_NO_SPEC_TREE = 1
+MAT_NO_SPECULAR = 2
 
 
 class RtError(RuntimeError):
@@ -305,6 +311,8 @@ def lib():
         _lib.rt_scene_set_render_flags.restype = C.c_int
         _lib.rt_scene_get_render_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.rt_scene_get_render_flags.restype = C.c_int
+        _lib.rt_scene_material_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        _lib.rt_scene_material_classes.restype = C.c_int
         # the linear plane (rt_mi355x.h: "the linear plane")
         vp, i32 = C.c_void_p, C.c_int32
         _lib.rt_render_begin_linear.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
@@ -1241,13 +1249,22 @@ class Scene:
         return ms
 
     def set_render_flags(self, flags):
-        """RENDER_REPRODUCIBLE or 0 (the default); refused while a job on this scene is live"""
+        """RENDER_* bits or 0 (the default); refused while a job on this scene is live"""
         _check(lib().rt_scene_set_render_flags(self._h, C.c_uint32(int(flags))))
 
     def render_flags(self):
         f = C.c_uint32()
         _check(lib().rt_scene_get_render_flags(self._h, C.byref(f)))
         return f.value
+
+    def material_classes(self):
+        """the class word of every material as the lowering sets it (MAT_* bits; all 0 under RENDER_GENERAL_SHADING): host only"""
+        n = C.c_int32()
+        _check(lib().rt_scene_material_classes(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        if n.value:
+            _check(lib().rt_scene_material_classes(self._h, _p(out), n.value, None))
+        return out
 
     def set_photon_dump(self, dat_path):
         _check(lib().rt_scene_set_photon_dump(self._h, os.fsencode(dat_path) if dat_path else None))

@@ -95,9 +95,13 @@ rt_status check_idle(rt_scene *s, const char *who)
 extern "C" rt_status rt_scene_set_render_flags(rt_scene *s, uint32_t flags)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_scene_set_render_flags: scene is NULL");
-    if (flags & ~(uint32_t)RT_RENDER_REPRODUCIBLE) return fail(RT_ERR_ARG, "rt_scene_set_render_flags: unknown flag bits 0x%x", flags & ~(uint32_t)RT_RENDER_REPRODUCIBLE);
+    const uint32_t known = RT_RENDER_REPRODUCIBLE | RT_RENDER_GENERAL_SHADING;
+    if (flags & ~known) return fail(RT_ERR_ARG, "rt_scene_set_render_flags: unknown flag bits 0x%x", flags & ~known);
     rt_status st = check_idle(s, "rt_scene_set_render_flags");
     if (st) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    // the material classes are part of the lowered scene: the next use of a device lowers it again (behind a render still in flight)
+    if ((s->render_flags.load() ^ flags) & RT_RENDER_GENERAL_SHADING) s->invalidate(true, false);
     s->render_flags.store(flags);
     return RT_OK;
 }

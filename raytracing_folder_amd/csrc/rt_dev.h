@@ -130,12 +130,19 @@ struct DevPhotonMap {
     float start_radius;
 };
 
+// Class word of a material (DevScene::material_class, one per entry of `materials`): what the lowering (material_class_of in
+// rt_lower.cpp, which holds the argument) found out ONCE about a material that lets FIN shading leave arithmetic out whose
+// result is exactly +0 for every hit on it.  0 = nothing known, the general path.
+#define RT_MAT_NO_SPEC_TREE 1u   // reflection and refraction are +0: no child rays, the refraction frame and the Fresnel term have no reader
+#define RT_MAT_NO_SPECULAR  2u   // ks is +0: the Blinn lobe (half vector, powf) multiplies a zero
+
 struct DevScene {
     const DevNodeXf *nodes;
     const DevObject *objects;
     const DevObjectBack *objects_back;   // [n_objects], see DevObjectBack
     const DevMesh   *meshes;
     const rt_blinn  *materials;
+    const uint32_t  *material_class;     // [n_materials], RT_MAT_* bits
     const rt_light  *lights;
     const int32_t   *node_material;   // material index per node
     int32_t n_nodes, n_objects, n_meshes, n_materials, n_lights;

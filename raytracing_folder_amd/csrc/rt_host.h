@@ -128,7 +128,7 @@ struct PhotonMapRef { PhotonStore &store; DevPhotonMap &pm; };
 struct DeviceState {
     int device = -1;
     bool scene_valid = false;
-    DevBuf nodes, objects, objects_back, meshes, materials, lights, node_material, textures, texels, material_maps;
+    DevBuf nodes, objects, objects_back, meshes, materials, material_class, lights, node_material, textures, texels, material_maps;
     std::vector<DevMeshBufs> mesh_bufs;
     PhotonStore maps[2];                        // [0] the photon map (scene.pm), [1] the caustic map (scene.cm)
     DevBuf raw_photons;                         // 24-byte photons of the last photon pass on this device (1-based)
@@ -162,7 +162,7 @@ struct DeviceState {
     PhotonMapRef map(bool caustic) { return {maps[caustic], caustic ? scene.cm : scene.pm}; }
     void release()
     {
-        for (DevBuf *b : {&nodes, &objects, &objects_back, &meshes, &materials, &lights, &node_material, &textures, &texels, &material_maps,
+        for (DevBuf *b : {&nodes, &objects, &objects_back, &meshes, &materials, &material_class, &lights, &node_material, &textures, &texels, &material_maps,
                           &raw_photons, &bvh_spill, &stats, &t_in}) b->release();
         for (PhotonStore &m : maps) m.release();
         for (auto &m : mesh_bufs) m.release();

@@ -231,6 +231,52 @@ extern "C" rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, r
     return RT_OK;
 }
 
+// The class word of a material (RT_MAT_*, rt_dev.h): decided here, once per material, so that shade_fin can leave out arithmetic
+// whose result is exactly +0 for EVERY hit on that material.  Bit patterns are compared, not values: -0.0f and NaN keep the
+// general path (a -0 weight changes the sign of a zero sum, a NaN must reach the pixel).
+//   RT_MAT_NO_SPEC_TREE: reflection and refraction are +0 in all channels (they are plain colours in rt_blinn: no texture map can
+//     scale them) and ior is finite and > 0.  Shade's rK / tK are then (+0) + (+0) * rC and (+0) * tC (FIN/main.cpp:601-610); rC is
+//     finite for a finite ray when ior > 0 (eta and C0 are finite, powf(1 - |cosI|, 5) lies in [0, 1]), so both are zeros,
+//     neither exceeds the 0.001 threshold, no child ray exists and nobody reads the two directions.  (A NaN weight would fail
+//     the threshold test the same way.)
+//   RT_MAT_NO_SPECULAR: ks is +0 in all channels, the specular colour has no texture map, glossiness is finite and in [0, 2^20].
+//     The lobe is powf(cosNH, gloss) with cosNH = max(0, N.H) of two unit vectors: in [0, 1] up to the rounding of two
+//     normalisations and a dot product (1 + 1e-6 at the very most), so the power is finite and >= 0 -- [0, 1] for cosNH <= 1,
+//     below exp(2^20 * 1e-6) < 3 beyond; 0^0 = 1 -- and (ks * intensity) * power has the bits of ks * intensity, a zero or, for
+//     a non-finite intensity, a NaN.  The upper bound on glossiness is what keeps the power from overflowing to +inf (0 * inf = NaN).
+static uint32_t material_class_of(const rt_blinn &m, const rt_texmap *maps)
+{
+    auto pos_zero3 = [](const float *c) { uint32_t b[3]; memcpy(b, c, 12); return (b[0] | b[1] | b[2]) == 0u; };
+    uint32_t cls = 0;
+    if (pos_zero3(m.reflection) && pos_zero3(m.refraction) && std::isfinite(m.ior) && m.ior > 0.0f) cls |= RT_MAT_NO_SPEC_TREE;
+    const bool spec_map = maps && maps[1].texture != RT_MAP_NONE;
+    if (pos_zero3(m.specular) && !spec_map && std::isfinite(m.glossiness) && m.glossiness >= 0.0f && m.glossiness <= 1048576.0f) cls |= RT_MAT_NO_SPECULAR;
+    return cls;
+}
+// one word per material as upload_scene puts it on a device; all clear under RT_RENDER_GENERAL_SHADING (caller holds s->mu)
+static void lower_material_classes(const rt_scene *s, std::vector<uint32_t> &out)
+{
+    const rt::SceneData &sd = s->data;
+    const bool general = (s->render_flags.load() & RT_RENDER_GENERAL_SHADING) != 0;
+    const bool mapped = sd.material_maps.size() == 2 * sd.materials.size();
+    out.assign(sd.materials.size(), 0u);
+    if (!general) for (size_t i = 0; i < sd.materials.size(); i++) out[i] = material_class_of(sd.materials[i], mapped ? &sd.material_maps[2 * i] : nullptr);
+}
+// the class words as upload_scene would set them, for whoever wants to look at them on the host (no device, no HIP call)
+extern "C" rt_status rt_scene_material_classes(const rt_scene *s, uint32_t *out, int32_t cap, int32_t *n_out)
+{
+    if (!s || (!out && cap > 0)) return fail(RT_ERR_ARG, "rt_scene_material_classes: NULL argument");
+    std::vector<uint32_t> cls;
+    {
+        std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+        lower_material_classes(s, cls);
+    }
+    if (n_out) *n_out = (int32_t)cls.size();
+    if (cap < 0 || (out && (size_t)cap < cls.size())) return fail(RT_ERR_ARG, "rt_scene_material_classes: room for %d words, %zu needed", cap, cls.size());
+    if (out && !cls.empty()) memcpy(out, cls.data(), cls.size() * 4);
+    return RT_OK;
+}
+
 static DevNodeXf xf_of(const rt_node &n)
 {
     DevNodeXf x;
@@ -349,6 +395,9 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     if ((st = D->objects_back.upload(backs.data(), backs.size() * sizeof(DevObjectBack)))) return st;
     if ((st = D->node_material.upload(node_mat.data(), node_mat.size() * 4))) return st;
     if ((st = D->materials.upload(sd.materials.data(), sd.materials.size() * sizeof(rt_blinn)))) return st;
+    std::vector<uint32_t> mat_class;
+    lower_material_classes(s, mat_class);
+    if ((st = D->material_class.upload(mat_class.data(), mat_class.size() * 4))) return st;
     if ((st = D->lights.upload(sd.lights.data(), sd.lights.size() * sizeof(rt_light)))) return st;
 
     for (auto &mb : D->mesh_bufs) mb.release();
@@ -421,7 +470,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
 
     DevScene &S = D->scene;
     S.nodes = (const DevNodeXf *)D->nodes.p; S.objects = (const DevObject *)D->objects.p; S.objects_back = (const DevObjectBack *)D->objects_back.p;
-    S.meshes = (const DevMesh *)D->meshes.p; S.materials = (const rt_blinn *)D->materials.p;
+    S.meshes = (const DevMesh *)D->meshes.p; S.materials = (const rt_blinn *)D->materials.p; S.material_class = (const uint32_t *)D->material_class.p;
     S.lights = (const rt_light *)D->lights.p; S.node_material = (const int32_t *)D->node_material.p;
     S.n_nodes = nn; S.n_objects = (int)objs.size(); S.n_meshes = (int)sd.meshes.size();
     S.n_materials = (int)sd.materials.size(); S.n_lights = (int)sd.lights.size();

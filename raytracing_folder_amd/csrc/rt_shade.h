@@ -335,7 +335,12 @@ template <bool TEX>
 __device__ void shade_fin(const DevScene &S, const rt_params &P, const Hit &h, V3 ray_d, int bounce, const RngCtx &rc,
                           ShadeOut &o, const BvhStack &stack, Counters &cnt)
 {
-    const rt_blinn &m = S.materials[S.node_material[h.node]];
+    const int mi = S.node_material[h.node];
+    const rt_blinn &m = S.materials[mi];
+    // what the lowering found out about this material (RT_MAT_*, rt_dev.h; the argument is at material_class_of in rt_lower.cpp):
+    // terms that are exactly +0 for every hit on it are left out below.  A per-lane branch on a per-material value -- the 64
+    // samples of a pixel nearly always agree on it
+    const uint32_t cls = S.material_class[mi];
     V3 color = ld3(m.emission);                                         // :517
     const V3 p = h.p;
     const V3 N = normalize(h.N);                                        // :521-522
@@ -356,16 +361,35 @@ __device__ void shade_fin(const DevScene &S, const rt_params &P, const Hit &h, V
             const V3 intensity = Il * coef;                             // :551
             V3 L = light_direction(light, p) * (float)(-1);             // :556
             L = normalize(L);
-            const V3 H = normalize(L + direction);
+            const V3 LpD = L + direction;
             const float cosNL = RMAX(0.f, dot(N, L));
-            const float cosNH = RMAX(0.f, dot(N, H));
             const V3 diffuse = (kd * intensity) * cosNL;                // :563
-            const V3 specular = ((ks * intensity) * powf(cosNH, gloss)) * cosNL;   // :564 (std::pow(float,float))
+            V3 specular = ks * intensity;
+            // RT_MAT_NO_SPECULAR: ks is +0, the lobe finite and >= 0, so (ks * intensity) * lobe has the bits of ks * intensity (a
+            // zero of either sign, or the NaN of an infinite intensity): H, cosNH and powf are left out, the multiplications
+            // around them and the additions below stay, so every sum rounds -- and signs its zeros -- as before.  L == -direction
+            // (the light straight behind the hit) is the one case whose lobe is a NaN: it keeps the general path
+            if (!(cls & RT_MAT_NO_SPECULAR) || (LpD.x == 0.f && LpD.y == 0.f && LpD.z == 0.f)) {
+                const V3 H = normalize(LpD);
+                const float cosNH = RMAX(0.f, dot(N, H));
+                specular = specular * powf(cosNH, gloss);               // :564 (std::pow(float,float))
+            }
+            specular = specular * cosNL;
             color = color + (diffuse + specular);                       // :566
         } else {
             color = color + kd * Il;                                    // :568-569
         }
     }
+    // :642-693: at bounceCount == BOUNCE the hemisphere loop's result is assigned to a shadowing
+    // variable and contributes exactly 0 -- not traced.  :695-705: every other hit adds
+    // kd * irradiance * max(0, N.(-dir)); queued for k_gather.
+    o.want_photon = (bounce != P.bounce) && S.pm.n_leaves != 0;
+    o.color = color; o.kd = kd; o.N = N;
+    o.child_absorb = ld3(m.absorption);      // children: K *= Attenuation(absorption, z) on a back-face hit (:620,:632)
+    o.mat = (uint32_t)mi;
+    // RT_MAT_NO_SPEC_TREE: rK and tK below would be zeros (reflection and refraction are +0, rC is finite), no child ray passes the
+    // threshold and nobody reads the directions: rK, tK, rdir, tdir and the two flags keep what shade_path initialised them to
+    if (cls & RT_MAT_NO_SPEC_TREE) return;
     // reflection / refraction set-up, :577-610
     float ein = 1, eout = ior;
     if (!h.front) { ein = ior; eout = 1; }
@@ -390,13 +414,6 @@ __device__ void shade_fin(const DevScene &S, const rt_params &P, const Hit &h, V
     const float th = 0.001f;                                            // materials.h:21-22
     o.want_refl = bounce > 0 && (o.rK.x > th || o.rK.y > th || o.rK.z > th);   // :613
     o.want_refr = bounce > 0 && (o.tK.x > th || o.tK.y > th || o.tK.z > th);   // :625
-    // :642-693: at bounceCount == BOUNCE the hemisphere loop's result is assigned to a shadowing
-    // variable and contributes exactly 0 -- not traced.  :695-705: every other hit adds
-    // kd * irradiance * max(0, N.(-dir)); queued for k_gather.
-    o.want_photon = (bounce != P.bounce) && S.pm.n_leaves != 0;
-    o.color = color; o.kd = kd; o.N = N;
-    o.child_absorb = ld3(m.absorption);      // children: K *= Attenuation(absorption, z) on a back-face hit (:620,:632)
-    o.mat = (uint32_t)S.node_material[h.node];
 }
 
 // MtlBlinn::Shade, P13/main.cpp:485-756 (reflectionGlossiness == refractionGlossiness == 0).

@@ -14,7 +14,10 @@ python3 -c "import json; from raytracing_folder_amd import buildinfo as b; json.
 run() {  # name, extra rocprof args...
   local name=$1; shift
   timeout -k 10 400 rocprofv3 --kernel-trace "$@" --output-format csv -d $out/$name -o $name -- python3 bench.py --no-cpu-baseline --profile-frames 0 "${BENCH_ARGS[@]}" > $out/$name.log 2>&1
-  echo "$name rc=$?"
+  local rc=$?
+  echo "$name rc=$rc"
+  # a pass that failed, faulted or ran into its time limit ends the script: nothing more is started on that GPU
+  [ $rc -eq 0 ] || { tail -20 $out/$name.log; exit $rc; }
 }
 BENCH_ARGS=(--steps 2 --warmup 1 "$@")
 case ",$groups," in *,stats,*) run stats --stats ;; esac
