@@ -379,7 +379,8 @@ rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bv
  *            root box and the cull boxes of the objects that use it follow; the call returns after the device has finished.
  *            Devices that do not hold the scene (never rendered on, or invalidated by another setter) lower it as usual later.
  *   REBUILD  what rt_scene_set_mesh does: every device builds the tree again at its next use.  For the caller that decides a
- *            refitted tree has degraded (this library offers no measure of that).
+ *            refitted tree has degraded ("mesh tree quality" below is the measure of that, and
+ *            rt_scene_update_mesh_vertices_auto the call that acts on it).
  * Either way the stored cyBVH arrays are built again for the new vertices when somebody reads them (rt_scene_get_mesh returns
  * what rt_bvh_build with leaves of four gives), and a photon map made by the photon pass is dropped, as by rt_scene_set_mesh. */
 #define RT_MESH_UPDATE_REBUILD 1u
@@ -401,6 +402,66 @@ typedef struct rt_mesh_update_ms {
     float upload, retri, refit;
 } rt_mesh_update_ms;
 rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out);
+
+/* ---- mesh tree quality (additive to ABI 4: detected by the presence of the symbols) --------------------------------------------
+ * A refitted tree keeps the topology of the shape it was built for and gets slower to trace as the mesh moves away from it.  The
+ * measure of that is the surface-area-heuristic (SAH) cost of the tree that sits on the device, against the cost the same mesh's
+ * tree had when it was last built.  The definition fixes every operation and the order of every addition, so that the GPU
+ * (k_bvh_cost) and the host mirror (rt_device_bvh_cost) give the same eight bytes.
+ *
+ * For a mesh whose tree has a root node (root_ref is not a leaf ref), over its n_nodes node records:
+ *   term(n, c)  for record n and child c in 0..3: 0 when the child is unused (its lo bound on x is NaN); otherwise h(box(n, c)) * w
+ *               as ONE float32 product, where
+ *                 h    is half the surface area in float32: d = hi - lo per axis, then (dx*dy + dy*dz) + dz*dx, no contraction;
+ *                 w    is 1.0f for an internal child and the leaf's triangle count (1..4: bits 28-30 of the ref, plus 1) for a leaf.
+ *               The float32 term is converted to double before any summing.
+ *   S           the sum of the 4 * n_nodes terms in double, in term order t = 4 n + c, with THIS order of additions: the terms
+ *               are cut into blocks of 256 consecutive ones (the last padded with +0.0); a block is summed as the balanced binary
+ *               tree over the bits of the index inside the block, lowest bit first --
+ *                 ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7)), and so on up to the two halves of 128 --
+ *               which is what an xor-butterfly over the lane index leaves in lane 0 of a wave of 64 and, above it, (w0 + w1) +
+ *               (w2 + w3) over the four waves of a workgroup; the block sums are then added one after the other in block order,
+ *               starting from +0.0.
+ *   H_R         h of the root box: per axis the smallest lo and the largest hi over the used children of the root record.
+ *   cost        1 + S / (double)H_R
+ * A mesh that is one leaf (root_ref is a leaf ref, no node records) has cost = 1 + its triangle count.
+ * RT_MESH_QUALITY_DEGENERATE: H_R is 0, or S or H_R is not finite (a tree without extent, or one whose areas overflow float32).
+ * A degenerate result has cost = 0 and ratio = 1 and never triggers a rebuild.
+ *
+ * rt_device_bvh_cost is the host mirror: plain C++, no HIP call, on the records rt_scene_mesh_device_bvh and
+ * rt_scene_mesh_device_read return.  RT_ERR_ARG: cost or flags NULL; root_ref not a leaf ref and its index >= n_nodes, or
+ * nodes NULL.  *flags: 0 or RT_MESH_QUALITY_DEGENERATE. */
+#define RT_MESH_QUALITY_DEGENERATE    1u
+#define RT_MESH_QUALITY_REBUILT       2u   /* rt_scene_update_mesh_vertices_auto went on to RT_MESH_UPDATE_REBUILD's path        */
+#define RT_MESH_QUALITY_NOT_ON_DEVICE 4u   /* no device held the scene: nothing was refitted or measured                        */
+rt_status rt_device_bvh_cost(const void *nodes, uint64_t n_nodes, uint32_t root_ref, double *cost, uint32_t *flags);
+/* The query: the scene is lowered on `device` first if it is not there (as by rt_scene_mesh_device_read, and with its
+ * discipline: the device is claimed, a pending render waited for), k_bvh_cost runs on the library's stream -- one launch over all
+ * levels, one double per 256 terms, folded on the host after one small copy -- and the call returns after it.  built_cost is the
+ * cost of the tree as the host built it when the mesh was last lowered there (from the host mirror on the host's records: no
+ * launch); it changes whenever the mesh is built again.  ratio = cost / built_cost, exactly 1 for a tree nobody has refitted.
+ * A degenerate cost OR built_cost flags the result degenerate.  struct_size must be the caller's sizeof (else RT_ERR_ARG).
+ * measure_ms: HIP events around k_bvh_cost and the copies that bring its block sums and the root record to the host. */
+typedef struct rt_mesh_quality {
+    uint32_t struct_size;
+    uint32_t flags;          /* RT_MESH_QUALITY_DEGENERATE | _REBUILT | _NOT_ON_DEVICE */
+    double   cost;           /* of the tree on the device now */
+    double   built_cost;     /* of the tree as it was last built for this mesh */
+    double   ratio;          /* cost / built_cost */
+    float    measure_ms;     /* HIP events around k_bvh_cost and its fold */
+} rt_mesh_quality;
+rt_status rt_scene_mesh_quality(rt_scene *s, int device, int32_t mesh, rt_mesh_quality *out);
+/* The update that uses it.  Arguments and their checks are rt_scene_update_mesh_vertices's, and max_ratio must be finite and
+ * >= 1 (else RT_ERR_ARG, nothing changes); out may be NULL, otherwise its struct_size is checked the same way.  The call does
+ * exactly what flags 0 does -- upload, k_mesh_retri, the refit launches, root box and cull boxes -- and measures the refitted
+ * tree behind the refit, in the same stream, before the final synchronise: on the first device that holds the scene (every
+ * device holds the same tree: the same host build, the same exact refit).  If ratio > max_ratio it then does what
+ * RT_MESH_UPDATE_REBUILD does -- every device builds the tree again at its next use -- and sets RT_MESH_QUALITY_REBUILT; out holds
+ * the REFITTED tree's cost, the one that triggered the rebuild.  If no device holds the scene there is nothing to refit or
+ * measure: flags = RT_MESH_QUALITY_NOT_ON_DEVICE, cost = built_cost = 0, ratio = 1, and the next lowering builds a fresh tree
+ * anyway.  There is no default for max_ratio: README.md has the measured table of SAH ratio against frame time to choose from. */
+rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                             double max_ratio, rt_mesh_quality *out);
 
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it

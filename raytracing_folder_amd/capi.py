@@ -208,6 +208,17 @@ class MeshUpdateMs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("level_launches", C.c_int32), ("upload", C.c_float), ("retri", C.c_float), ("refit", C.c_float)]
 
 
+class MeshQuality(C.Structure):
+    """rt_mesh_quality: the SAH cost of a mesh's tree on a device against the cost it had when it was last built"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("cost", C.c_double), ("built_cost", C.c_double),
+                ("ratio", C.c_double), ("measure_ms", C.c_float)]
+
+    def as_dict(self):
+        return dict(cost=self.cost, built_cost=self.built_cost, ratio=self.ratio, measure_ms=self.measure_ms,
+                    degenerate=bool(self.flags & MESH_QUALITY_DEGENERATE), rebuilt=bool(self.flags & MESH_QUALITY_REBUILT),
+                    not_on_device=bool(self.flags & MESH_QUALITY_NOT_ON_DEVICE))
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -268,10 +279,15 @@ SYMBOLS = [
     "rt_scene_mesh_device_bvh",
     "rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms",
     "rt_scene_material_classes",
+    "rt_device_bvh_cost", "rt_scene_mesh_quality", "rt_scene_update_mesh_vertices_auto",
 ]
 
 # rt_scene_update_mesh_vertices flags (include/rt_mi355x.h): build the tree again instead of refitting it in place
 MESH_UPDATE_REBUILD = 1
+# rt_mesh_quality flags (include/rt_mi355x.h, "mesh tree quality")
+MESH_QUALITY_DEGENERATE = 1
+MESH_QUALITY_REBUILT = 2
+MESH_QUALITY_NOT_ON_DEVICE = 4
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -429,6 +445,12 @@ def lib():
         _lib.rt_scene_mesh_update_ms.argtypes = [vp, C.c_int, vp]
         for name in ("rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms"):
             getattr(_lib, name).restype = C.c_int
+        # mesh tree quality (rt_mi355x.h: "mesh tree quality")
+        _lib.rt_device_bvh_cost.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
+        _lib.rt_scene_mesh_quality.argtypes = [vp, C.c_int, i32, vp]
+        _lib.rt_scene_update_mesh_vertices_auto.argtypes = [vp, i32, vp, i32, vp, i32, C.c_double, vp]
+        for name in ("rt_device_bvh_cost", "rt_scene_mesh_quality", "rt_scene_update_mesh_vertices_auto"):
+            getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
                      "rt_render_begin_outputs", "rt_render_tiles_outputs_device", "rt_image_write_pfm1", "rt_image_read_pfm1"):
@@ -447,6 +469,14 @@ def _p(a):
 
 def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+def device_bvh_cost(nodes, root_ref):
+    """rt_device_bvh_cost, the host mirror of k_bvh_cost (no GPU): (cost, degenerate) of DEVBVHNODE records and their root ref"""
+    nodes = _c(nodes, DEVBVHNODE)
+    cost, flags = C.c_double(0.0), C.c_uint32(0)
+    _check(lib().rt_device_bvh_cost(_p(nodes), len(nodes), C.c_uint32(int(root_ref)), C.byref(cost), C.byref(flags)))
+    return cost.value, bool(flags.value & MESH_QUALITY_DEGENERATE)
 
 
 def _stream_handle(stream):
@@ -1181,13 +1211,29 @@ class Scene:
         if vt is not None and len(vt):
             self.set_mesh_texcoords(index, vt, ft)
 
-    def update_mesh_vertices(self, index, v, vn=None, rebuild=False):
+    def update_mesh_vertices(self, index, v, vn=None, rebuild=False, max_ratio=None):
         """new positions (and normals, unless vn is None) for a mesh whose faces stay: refitted in place on the devices that hold
-        the scene; rebuild=True takes set_mesh's path instead (the tree is built again at the next use)"""
+        the scene; rebuild=True takes set_mesh's path instead (the tree is built again at the next use).  max_ratio (>= 1): the
+        refitted tree is measured as well (rt_scene_update_mesh_vertices_auto) and built again at the next use when its SAH cost
+        has grown beyond max_ratio times the built tree's; the call then returns mesh_quality()'s dict, else None"""
+        if max_ratio is not None and rebuild:
+            raise ValueError("update_mesh_vertices: rebuild=True and max_ratio exclude each other")
         v = _c(v, np.float32).reshape(-1, 3)
         vn = _c(vn, np.float32).reshape(-1, 3) if vn is not None else None
+        if max_ratio is not None:
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_update_mesh_vertices_auto(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
+                                                            len(vn) if vn is not None else 0, C.c_double(max_ratio), C.byref(q)))
+            return q.as_dict()
         _check(lib().rt_scene_update_mesh_vertices(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
                                                    len(vn) if vn is not None else 0, C.c_uint32(MESH_UPDATE_REBUILD if rebuild else 0)))
+
+    def mesh_quality(self, index, device=0):
+        """the SAH cost of mesh `index`'s tree as it sits on `device` (lowered there first if need be), by k_bvh_cost:
+        dict(cost, built_cost, ratio, measure_ms, degenerate, rebuilt, not_on_device)"""
+        q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+        _check(lib().rt_scene_mesh_quality(self._h, int(device), int(index), C.byref(q)))
+        return q.as_dict()
 
     def mesh_update_ms(self, device=0):
         """the last in-place update on `device`: dict(upload, retri, refit in ms by HIP events, level_launches)"""

@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -171,6 +172,25 @@ static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
     return w->data.meshes[mesh];
 }
 
+// What rt_scene_update_mesh_vertices and rt_scene_update_mesh_vertices_auto share: the argument checks (`who` names the entry
+// point in the message) and, once they pass, the new vertices in the store.  The caller holds s->mu.
+static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, const char *who)
+{
+    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
+        return fail(RT_ERR_ARG, "%s: mesh %d was never set", who, mesh);
+    rt::MeshData &m = s->data.meshes[mesh];
+    if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, nv, m.v.size() / 3);
+    if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
+        return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
+    m.v.assign(v, v + 3 * (size_t)nv);
+    if (vn) m.vn.assign(vn, vn + 3 * (size_t)nvn);
+    m.tree_stale = true;
+    rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
+    // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
+    s->drop_generated_photons();
+    return RT_OK;
+}
+
 extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
 {
     rt_status st = check_idle(s, "rt_scene_update_mesh_vertices");
@@ -178,20 +198,30 @@ extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, co
     if (flags & ~RT_MESH_UPDATE_REBUILD) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: unknown flag bits 0x%x", flags & ~RT_MESH_UPDATE_REBUILD);
     if (!v) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: v is NULL");
     std::lock_guard<std::mutex> lk(s->mu);
-    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
-        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: mesh %d was never set", mesh);
-    rt::MeshData &m = s->data.meshes[mesh];
-    if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: nv is %d, the mesh has %zu vertices (the faces stay as they are)", nv, m.v.size() / 3);
-    if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
-        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: nvn is %d, the mesh has %zu normals", nvn, m.vn.size() / 3);
-    m.v.assign(v, v + 3 * (size_t)nv);
-    if (vn) m.vn.assign(vn, vn + 3 * (size_t)nvn);
-    m.tree_stale = true;
-    rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
-    // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
-    s->drop_generated_photons();
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, "rt_scene_update_mesh_vertices"))) return st;
     if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }
     return refit_mesh_on_devices(s, mesh, vn != nullptr);
+}
+
+// flags 0 of the call above, the refitted tree measured behind the refit (rt_lower.cpp), and REBUILD's path taken when the measure says so
+extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                        double max_ratio, rt_mesh_quality *out)
+{
+    rt_status st = check_idle(s, "rt_scene_update_mesh_vertices_auto");
+    if (st) return st;
+    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: max_ratio is %g (it must be finite and at least 1)", max_ratio);
+    if (out && out->struct_size != sizeof(rt_mesh_quality))
+        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: rt_mesh_quality.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_quality));
+    if (!v) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: v is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, "rt_scene_update_mesh_vertices_auto"))) return st;
+    rt_mesh_quality q = {};
+    q.struct_size = sizeof q;
+    st = refit_mesh_on_devices(s, mesh, vn != nullptr, &q);
+    // a degenerate measure has ratio 1, and so has a scene no device holds: neither asks for a rebuild
+    if (!st && q.ratio > max_ratio) { s->invalidate(true, false); q.flags |= RT_MESH_QUALITY_REBUILT; }
+    if (out) *out = q;
+    return st;
 }
 
 extern "C" rt_status rt_scene_set_mesh_texcoords(rt_scene *s, int32_t mesh, const float *vt, int32_t nvt, const uint32_t *ft)

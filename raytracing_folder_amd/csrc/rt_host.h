@@ -1,6 +1,6 @@
 // rt_host.h -- private to the host files of the C ABI (not installed): what more than one of them needs.
 //   rt_api.cpp     what needs no device state: errors, the scene store and its getters, the image and .dat wrappers
-//   rt_lower.cpp   a scene onto a device (prepare_device): SAH BVH, objects, mesh refit
+//   rt_lower.cpp   a scene onto a device (prepare_device): SAH BVH, objects, mesh refit, mesh tree quality
 //   rt_photons.cpp the photon maps: their setters, the gather structures (upload_photons), the photon and caustic passes,
 //                  generate_photons, the global map's state (rt_photon_map.h) with its two device copies
 //   rt_render.cpp  render orchestration: working sets, run_pipeline, the render / packed / unpack entry points, jobs, the
@@ -86,7 +86,14 @@ struct DevMeshBufs {
     DevBuf slot_idx, level_nodes, v, vn;
     std::vector<uint32_t> level_off, slot_face;
     uint32_t root_ref = 0; int stack_need = 0;
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn}) b->release(); }
+    // mesh tree quality (rt_scene_mesh_quality): the cost of the tree as the host built it, from the host mirror on the host's own
+    // records at upload time (no launch: the GPU's figure is the mirror's bit for bit) -- the only moment those records exist, and
+    // after an update the store no longer has the vertices they were built for; k_bvh_cost's block sums on the device (from the
+    // first measurement on) and where they land on the host: the block sums, then the root's 128-byte record as 16 doubles
+    double built_cost = 0; uint32_t built_flags = 0;
+    DevBuf cost_partials;
+    std::vector<double> cost_host;
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &cost_partials}) b->release(); }
 };
 
 static const size_t SPILL_BYTES = (size_t)RT_SPILL_BLOCKS * RT_BLOCK * RT_BVH_SPILL * 4;     // DevScene::bvh_spill / DevWork::bvh_spill
@@ -158,6 +165,7 @@ struct DeviceState {
     hipStream_t stream = nullptr;
     // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
     Event upd_ev[4]; int upd_levels = -1;
+    Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
     // one of the two maps: its buffers with what the kernels see of it
     PhotonMapRef map(bool caustic) { return {maps[caustic], caustic ? scene.cm : scene.pm}; }
     void release()
@@ -167,6 +175,7 @@ struct DeviceState {
         for (PhotonStore &m : maps) m.release();
         for (auto &m : mesh_bufs) m.release();
         for (Event &e : upd_ev) e = Event();
+        for (Event &e : cost_ev) e = Event();
         upd_levels = -1;
         for (Workspace &w : ws) w.release();
         for (int k = 0; k < 6; k++) t_out[k].release();
@@ -212,7 +221,9 @@ RT_HIDDEN rt_status check_idle(rt_scene *s, const char *who);                   
 // rt_api.cpp: the stored cyBVH arrays of a mesh, built again if a vertex update left them stale (caller holds s->mu)
 RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
 // rt_lower.cpp: what rt_scene_update_mesh_vertices does on the devices that hold the scene (caller holds s->mu, the store has the new vertices)
-RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed);
+// quality: NULL, or where the first device that holds the scene leaves the refitted tree's measure (rt_scene_update_mesh_vertices_auto;
+// flags RT_MESH_QUALITY_NOT_ON_DEVICE when none did)
+RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality = nullptr);
 // rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
 RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
 RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);

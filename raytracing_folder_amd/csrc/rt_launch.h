@@ -232,6 +232,17 @@ struct MeshRefitRequest {
     hipEvent_t after_retri;
 };
 
+// One measurement of a mesh's tree on a device (rt_refit.hip, k_bvh_cost; the definition: rt_mi355x.h, "mesh tree quality"): the
+// n_nodes (> 0, at most 2^28) records at `nodes`, one double per block of 256 terms to partials[0 .. ceil(4 n_nodes / 256)).
+// partials has room for one double more: under RT_COST_FOLD_DEVICE k_bvh_cost_fold leaves the sum of the others there.
+#ifndef RT_COST_FOLD_DEVICE
+#define RT_COST_FOLD_DEVICE 0           /* 1: fold the block sums on the device (the variant that was measured and not kept) */
+#endif
+struct BvhCostRequest {
+    const DevBvhNode *nodes; uint32_t n_nodes;
+    double *partials;
+};
+
 // ---- rt_kernels.hip: the kernels that shade -----------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -310,6 +321,8 @@ hipError_t rtk_launch_dof(hipStream_t st, const DofRequest &R);
 // ---- rt_refit.hip: mesh vertex updates ------------------------------------------------------------------------------------
 // on `st`: k_mesh_retri over the slots, then k_bvh_refit_level once per level, the deepest first
 hipError_t rtk_launch_mesh_refit(hipStream_t st, const MeshRefitRequest &R);
+// on `st`: k_bvh_cost over all the tree's records in one launch
+hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

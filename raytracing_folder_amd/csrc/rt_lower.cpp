@@ -13,6 +13,7 @@
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
 #include "rt_host.h"
+#include "rt_bvh_cost.h"
 
 // ---- lowering to the device ---------------------------------------------------------------------------
 static DeviceState *device_state(rt_scene *s, int device)
@@ -452,6 +453,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
             if ((st = mb.slot_idx.upload(slot_idx.data(), slot_idx.size() * 4))) return st;
             if ((st = mb.level_nodes.upload(level_nodes.data(), level_nodes.size() * 4))) return st;
             mb.slot_face = tri_face; mb.root_ref = root_ref; mb.stack_need = depth;
+            bvh_cost_host(bn.data(), bn.size(), root_ref, &mb.built_cost, &mb.built_flags);      // (root_ref is the builder's own: always there)
         }
         dm[mi].tex = nullptr;
         if (!m.vt.empty() && m.ft.size() == m.f.size()) {      // vt[ft0], vt[ft1], vt[ft2] per triangle slot, like nrm
@@ -509,7 +511,11 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
 // place -- DevTri and nrm of every slot and every box of the tree (rt_refit.hip), DevMesh::root_box, and the objects' cull boxes
 // (objs: the scene's objects lowered again by the caller).  Nothing else on the device depends on a mesh's vertices: the tree's
 // topology, stack_need (DevScene::max_bvh_depth, the spill buffers) and tex follow the faces, which stay.
-static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs)
+static rt_status enqueue_mesh_cost(DeviceState *D, DevMeshBufs &mb);
+static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh_quality *q);
+
+static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
+                                      rt_mesh_quality *quality)
 {
     HIP_TRY(hipSetDevice(D->device));
     if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
@@ -537,14 +543,16 @@ static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
     D->upd_levels = R.n_levels;
     HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), m.root_box, 24, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
+    if (quality && (rs = enqueue_mesh_cost(D, mb))) return rs;      // the refitted tree, measured behind the refit on the same stream
     HIP_TRY(hipStreamSynchronize(st));
-    return RT_OK;
+    return quality ? finish_mesh_cost(D, mb, quality) : RT_OK;
 }
 
-rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed)
+rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality)
 {
     const rt::MeshData &m = s->data.meshes[mesh];
-    bool any = false;
+    bool any = false, measured = false;
+    if (quality) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
     for (DeviceState *D : s->devs) any = any || D->scene_valid;
     if (!any) return RT_OK;
     std::vector<DevObject> objs;
@@ -559,12 +567,99 @@ rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed)
         // a device another call is using, or one the update fails on, lowers the scene again at its next use instead
         DeviceClaim claim(D);
         rt_status r = st;
-        if (!r && claim.ok) r = refit_mesh_on_device(D, m, mesh, normals_changed, objs);
+        if (!r && claim.ok) {
+            // every device holds the same tree (the same host build, the same exact refit): the first one that refits measures it
+            r = refit_mesh_on_device(D, m, mesh, normals_changed, objs, quality && !measured ? quality : nullptr);
+            measured = measured || !r;
+        }
         if (r || !claim.ok) D->scene_valid = false;
         if (r && !ret) ret = r;
     }
     (void)hipSetDevice(cur);
+    // no device got as far as a measurement (all in use, or failed: they lower the scene again at their next use)
+    if (quality && !measured) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
     return ret;
+}
+
+// ---- mesh tree quality (rt_mi355x.h, "mesh tree quality") ------------------------------------------------------------------
+// the host mirror: bvh_cost_host of rt_bvh_cost.h, the functions k_bvh_cost is made of, behind the ABI's argument checks
+extern "C" rt_status rt_device_bvh_cost(const void *nodes, uint64_t n_nodes, uint32_t root_ref, double *cost, uint32_t *flags)
+{
+    if (!cost || !flags) return fail(RT_ERR_ARG, "rt_device_bvh_cost: NULL argument");
+    if (!(root_ref & RT_COST_LEAF)) {
+        if (root_ref >= n_nodes) return fail(RT_ERR_ARG, "rt_device_bvh_cost: root_ref names node %u of %llu", root_ref, (unsigned long long)n_nodes);
+        if (!nodes) return fail(RT_ERR_ARG, "rt_device_bvh_cost: nodes is NULL");
+        if (n_nodes > (1ull << 28)) return fail(RT_ERR_ARG, "rt_device_bvh_cost: %llu node records (a mesh has at most 2^28)", (unsigned long long)n_nodes);
+    }
+    bvh_cost_host(nodes, n_nodes, root_ref, cost, flags);
+    return RT_OK;
+}
+
+// The measurement of mb's tree as it sits on D, queued on D's stream (the caller has claimed D and synchronises the stream before
+// finish_mesh_cost): k_bvh_cost, then the block sums and the root's record to the host.  A mesh that is one leaf has nothing to launch.
+static rt_status enqueue_mesh_cost(DeviceState *D, DevMeshBufs &mb)
+{
+    hipStream_t st = D->stream;
+    for (Event &e : D->cost_ev) if (!e.e) HIP_TRY(e.create());
+    HIP_TRY(hipEventRecord(D->cost_ev[0], st));
+    if (!(mb.root_ref & RT_COST_LEAF)) {
+        const uint64_t n_nodes = mb.level_off.back(), n_blocks = bvh_cost_blocks(n_nodes);
+        rt_status rs;
+        if ((rs = mb.cost_partials.ensure((n_blocks + 1) * sizeof(double)))) return rs;
+        mb.cost_host.resize(n_blocks + 1 + sizeof(DevBvhNode) / sizeof(double));
+        BvhCostRequest R = {};
+        R.nodes = (const DevBvhNode *)mb.nodes.p; R.n_nodes = (uint32_t)n_nodes; R.partials = (double *)mb.cost_partials.p;
+        HIP_TRY(rtk_launch_bvh_cost(st, R));
+#if RT_COST_FOLD_DEVICE
+        HIP_TRY(hipMemcpyAsync(mb.cost_host.data() + n_blocks, (const double *)mb.cost_partials.p + n_blocks, sizeof(double), hipMemcpyDeviceToHost, st));
+#else
+        HIP_TRY(hipMemcpyAsync(mb.cost_host.data(), mb.cost_partials.p, n_blocks * sizeof(double), hipMemcpyDeviceToHost, st));
+#endif
+        HIP_TRY(hipMemcpyAsync(mb.cost_host.data() + n_blocks + 1, (const DevBvhNode *)mb.nodes.p + mb.root_ref, sizeof(DevBvhNode), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipEventRecord(D->cost_ev[1], st));
+    return RT_OK;
+}
+// ... and, the stream synchronised, what it says: the fold of the block sums in index order, the root box, the cost and its ratio
+static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh_quality *q)
+{
+    uint32_t flags = 0;
+    if (mb.root_ref & RT_COST_LEAF) bvh_cost_host(nullptr, 0, mb.root_ref, &q->cost, &flags);
+    else {
+        const uint64_t n_blocks = bvh_cost_blocks(mb.level_off.back());
+#if RT_COST_FOLD_DEVICE
+        const double S = mb.cost_host[n_blocks];
+#else
+        const double S = bvh_cost_fold(mb.cost_host.data(), n_blocks);
+#endif
+        bvh_cost_finish(S, bvh_cost_root_half_area((const float *)(mb.cost_host.data() + n_blocks + 1)), &q->cost, &flags);
+    }
+    q->built_cost = mb.built_cost;
+    if (flags || mb.built_flags) { q->flags = RT_MESH_QUALITY_DEGENERATE; q->cost = 0.0; q->ratio = 1.0; }
+    else { q->flags = 0; q->ratio = q->cost / q->built_cost; }
+    HIP_TRY(hipEventElapsedTime(&q->measure_ms, D->cost_ev[0], D->cost_ev[1]));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_quality(rt_scene *s, int device, int32_t mesh, rt_mesh_quality *out)
+{
+    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_quality: NULL argument");
+    if (out->struct_size != sizeof(rt_mesh_quality))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_quality: rt_mesh_quality.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_quality));
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_quality: mesh %d was never set", mesh);
+    }
+    DeviceState *D = nullptr;
+    rt_status st = prepare_device(s, device, &D);
+    if (st) return st;
+    DeviceClaim claim(D);
+    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_quality: another call on this scene is using device %d", device);
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
+    DevMeshBufs &mb = D->mesh_bufs[mesh];
+    if ((st = enqueue_mesh_cost(D, mb))) return st;
+    HIP_TRY(hipStreamSynchronize(D->stream));
+    return finish_mesh_cost(D, mb, out);
 }
 
 extern "C" rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out)

@@ -18,12 +18,26 @@
 //                       A bound equal to the stored one is left alone, so the sign of a zero bound stays the build's: the host's fold
 //                       keeps the first of -0 and +0 it meets, in an order the refit cannot know; fminf / fmaxf would pick by sign.
 //
-// One launch per level, nothing else: no cross-workgroup synchronisation, no atomics, nothing that waits.  Min and max do not depend
+//   k_bvh_cost          the surface-area-heuristic cost of the tree as it sits on the device (rt_mi355x.h, "mesh tree quality"): one
+//                       lane per (node, child) over ALL levels at once, 256 lanes a workgroup like k_bvh_refit_level.  A lane reads
+//                       its child's six bounds and its ref (seven 4-byte loads, 128 bytes a node between the four lanes of a
+//                       node) and forms its term in float32 (bvh_cost_term, rt_bvh_cost.h -- the host mirror calls the same
+//                       function), converts it to double, and the workgroup adds its 256 doubles in the FIXED order the header
+//                       writes down: an xor-butterfly over the lane index inside each wave (strides 1 .. 32; a double travels as
+//                       two 32-bit ds_bpermute), which leaves in lane 0 the balanced tree ((t0 + t1) + (t2 + t3)) + ..., then the
+//                       four wave sums through 32 bytes of LDS as (w0 + w1) + (w2 + w3) -- strides 64 and 128 of the same tree.
+//                       One double per workgroup goes to the partials buffer; the host adds those in index order after one small
+//                       copy (RT_COST_FOLD_DEVICE: k_bvh_cost_fold does it in one lane instead -- the alternative that was
+//                       measured and not kept).  No atomics, nothing that waits: IEEE additions in an order that
+//                       does not depend on scheduling, so the same records give the same eight bytes on every launch and on the host.
+//
+// The refit is one launch per level, nothing else: no cross-workgroup synchronisation, no atomics, nothing that waits.  Min and max do not depend
 // on the order of their operands, so identical inputs give identical bytes.  The four lanes of a node write disjoint floats of its
 // record (lo[a][child], hi[a][child]) and read only records of the level below.
 #include <hip/hip_runtime.h>
 
 #include "rt_launch.h"
+#include "rt_bvh_cost.h"
 
 #define RT_REFIT_BLOCK 256
 #define RT_REFIT_LEAF 0x80000000u
@@ -104,5 +118,41 @@ hipError_t rtk_launch_mesh_refit(hipStream_t st, const MeshRefitRequest &R)
         hipLaunchKernelGGL(k_bvh_refit_level, dim3((4 * n + RT_REFIT_BLOCK - 1) / RT_REFIT_BLOCK), dim3(RT_REFIT_BLOCK), 0, st,
                            R.nodes, R.level_nodes + R.level_off[k], n, (const DevTri *)R.tris);
     }
+    return hipGetLastError();
+}
+
+static_assert(RT_REFIT_BLOCK == RT_COST_BLOCK && RT_REFIT_BLOCK == 4 * 64, "a block of the cost's summation order is one workgroup of four waves");
+
+__global__ __launch_bounds__(RT_REFIT_BLOCK) void k_bvh_cost(const DevBvhNode *__restrict__ nodes, uint32_t n_terms, double *__restrict__ partials)
+{
+    __shared__ double wave_sum[RT_REFIT_BLOCK / 64];
+    const uint32_t t = blockIdx.x * RT_REFIT_BLOCK + threadIdx.x;
+    // every lane stays to the end: the lanes past the last term carry the zeros the definition pads a short block with
+    double x = t < n_terms ? bvh_cost_term((const float *)(nodes + (t >> 2)), t & 3u) : 0.0;
+    for (int stride = 1; stride < 64; stride *= 2) x = x + __shfl_xor(x, stride, 64);
+    if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
+#if RT_COST_FOLD_DEVICE
+// the block sums added in index order by one lane, into the slot behind them
+__global__ void k_bvh_cost_fold(double *partials, uint32_t n_blocks)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double S = 0.0;
+    for (uint32_t b = 0; b < n_blocks; b++) S = S + partials[b];
+    partials[n_blocks] = S;
+}
+#endif
+
+hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R)
+{
+    if (R.n_nodes == 0) return hipSuccess;
+    const uint32_t n_terms = 4 * R.n_nodes, n_blocks = (n_terms + RT_REFIT_BLOCK - 1) / RT_REFIT_BLOCK;
+    hipLaunchKernelGGL(k_bvh_cost, dim3(n_blocks), dim3(RT_REFIT_BLOCK), 0, st, R.nodes, n_terms, R.partials);
+#if RT_COST_FOLD_DEVICE
+    hipLaunchKernelGGL(k_bvh_cost_fold, dim3(1), dim3(64), 0, st, R.partials, n_blocks);
+#endif
     return hipGetLastError();
 }
