@@ -369,7 +369,8 @@ rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bv
  *      unchanged) ---------------------------------------------------------------------------------------------------------------
  * New positions (and, optionally, normals) for a mesh whose faces stay as they are: a deforming surface, frame after frame.
  * nv and nvn must be the stored counts (anything else: RT_ERR_ARG, nothing changes); vn == NULL keeps the stored normals.  The
- * scene must be idle (no live job).  flags: 0, or RT_MESH_UPDATE_REBUILD.
+ * scene must be idle (no live job).  flags: 0, or RT_MESH_UPDATE_REBUILD; rt_scene_update_mesh_vertices_flags takes either with or
+ * without RT_MESH_UPDATE_KEEP_PREVIOUS.  Any other bit is RT_ERR_ARG.
  *   0        On every device that holds this scene as it is now, the mesh is updated IN PLACE: the vertices are uploaded,
  *            k_mesh_retri writes every triangle slot (A, B, C, the unit face normal computed operation by operation as the host
  *            computes it, the three vertex normals) and k_bvh_refit_level, once per level of the tree from the deepest up, sets
@@ -382,10 +383,25 @@ rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bv
  *            refitted tree has degraded ("mesh tree quality" below is the measure of that, and
  *            rt_scene_update_mesh_vertices_auto the call that acts on it).
  * Either way the stored cyBVH arrays are built again for the new vertices when somebody reads them (rt_scene_get_mesh returns
- * what rt_bvh_build with leaves of four gives), and a photon map made by the photon pass is dropped, as by rt_scene_set_mesh. */
+ * what rt_bvh_build with leaves of four gives), and a photon map made by the photon pass is dropped, as by rt_scene_set_mesh.
+ *   KEEP_PREVIOUS  (rt_scene_update_mesh_vertices_flags and rt_scene_update_mesh_vertices_auto_flags only: the two calls that came
+ *            before the flag take the bits they always took, so a caller that relied on RT_ERR_ARG for it still gets it.  Combines
+ *            with either of the above.)  The positions the mesh had before this call become its PREVIOUS POSITIONS: nv x 3 floats,
+ *            indexed like v, which "motion vectors for deforming meshes" below follows a pixel through.  They are kept in the scene
+ *            store, so that a later lowering or rebuild uploads them, and on every device that holds the scene: uploaded from the
+ *            store ahead of the new vertices, in the update's stream.  They are per vertex, not per triangle slot, so they survive
+ *            REBUILD and rt_scene_update_mesh_vertices_auto's rebuild.  rt_scene_set_mesh drops them (the faces may have changed),
+ *            and so does an update WITHOUT the flag (the caller no longer vouches for the pairing): the mesh is rigid again.  The
+ *            contract is one flagged update per mesh per frame; the previous positions are those before the LAST flagged update.
+ *            Without the flag an update does what it always did, launch for launch, and nothing is allocated for a mesh that
+ *            never used it. */
 #define RT_MESH_UPDATE_REBUILD 1u
+#define RT_MESH_UPDATE_KEEP_PREVIOUS 2u
 rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                         uint32_t flags);
+/* the same call, taking RT_MESH_UPDATE_KEEP_PREVIOUS as well (flags 0 and RT_MESH_UPDATE_REBUILD do what they do above) */
+rt_status rt_scene_update_mesh_vertices_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                              uint32_t flags);
 /* What sits on `device` for one mesh right now (the scene is lowered there first if it is not): info, nodes, slot_face as
  * rt_scene_mesh_device_bvh describes them -- after an in-place update the refitted tree, not the one a fresh build would give --
  * and per triangle slot its 12 floats of A, B, C, N and its 9 floats of vertex normals, and the mesh's root box (lo[3], hi[3]).
@@ -462,6 +478,15 @@ rt_status rt_scene_mesh_quality(rt_scene *s, int device, int32_t mesh, rt_mesh_q
  * anyway.  There is no default for max_ratio: README.md has the measured table of SAH ratio against frame time to choose from. */
 rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                              double max_ratio, rt_mesh_quality *out);
+/* ... with flags: 0 (the call above) or RT_MESH_UPDATE_KEEP_PREVIOUS; any other bit is RT_ERR_ARG (REBUILD is what max_ratio decides) */
+rt_status rt_scene_update_mesh_vertices_auto_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                   double max_ratio, uint32_t flags, rt_mesh_quality *out);
+/* How many meshes of the scene hold previous positions, from the scene store (no GPU, no HIP call). */
+rt_status rt_scene_previous_positions(const rt_scene *s, int32_t *n_meshes);
+/* The previous positions of one mesh as they sit on `device` (the scene is lowered there first if it is not, with
+ * rt_scene_mesh_device_read's discipline): *nv_out = their number, the mesh's nv, or 0 when the mesh holds none (nothing is written
+ * then).  v_prev may be NULL (the count only); otherwise nv_cap counts vertices and a too small one is RT_ERR_ARG. */
+rt_status rt_scene_mesh_device_previous(rt_scene *s, int device, int32_t mesh, float *v_prev, uint64_t nv_cap, uint32_t *nv_out);
 
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
@@ -936,7 +961,8 @@ rt_status rt_temporal(rt_history *hst, const rt_camera *cam, const rt_temporal_p
  * themselves, find the same object id and normal and (almost always) an acceptable depth: rt_temporal would blend in history
  * from another surface point.  rt_motion computes, in image space and without tracing a ray, where each pixel's surface point
  * was in the PREVIOUS frame's image; rt_temporal_motion accumulates with that plane in place of its own reprojection.  Only node
- * transforms move: meshes do not deform, and lights are not followed.  The reference has no counterpart.
+ * transforms move here: deforming meshes are followed by rt_scene_motion ("motion vectors for deforming meshes" below), and lights
+ * are not followed.  The reference has no counterpart.
  * `motion` is float[W*H*3], row-major: for the pixel p = (x, y) of the new frame (fx, fy, z_exp) -- (fx, fy) the position of p's
  * surface point in the previous frame's image, in the coordinates of step 3 of "temporal accumulation" (an integer coordinate is
  * a pixel centre: fx = x, fy = y means "did not move"), z_exp the expected depth of that point measured from the previous
@@ -987,6 +1013,53 @@ rt_status rt_motion_device(int device, void *hip_stream, const rt_camera *cam, c
 /* The planes are HOST arrays: upload, compute, download. */
 rt_status rt_motion(int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
                     const rt_node *prev_nodes, int32_t n_nodes, const rt_motion_planes *host_planes);
+
+/* ---- motion vectors for deforming meshes (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the
+ *      structs above are unchanged) ----------------------------------------------------------------------------------------------
+ * "motion vectors" follows node transforms only: a pixel of a mesh whose vertices were moved between two frames
+ * (rt_scene_update_mesh_vertices) gets the motion of its node, and under a fixed node and camera that is "did not move".
+ * rt_scene_motion is rt_motion for a scene: the same plane, with the pixels of every mesh that holds PREVIOUS POSITIONS
+ * (RT_MESH_UPDATE_KEEP_PREVIOUS) followed through the deformation -- the one motion call that traces rays (k_motion_mesh: one lane
+ * per pixel, workgroups of 256, the per-lane traversal stack of the tracing kernels).  The current nodes are the scene's; the
+ * planes, the cameras and prev_nodes are rt_motion's.  For a pixel p = (x, y) with object id i:
+ *   RIGID   node i carries no mesh, or its mesh holds no previous positions: the pixel is exactly what rt_motion writes, to the
+ *           byte -- steps a.-e. of "motion vectors", markers and the DID NOT MOVE shortcut included (the same device function).
+ *   d. applies unchanged to every pixel: object_id[p] < 0, z_p >= 1e30 or not finite, or i >= n_nodes hold (x, y, 0).
+ *   Otherwise, for a MESH pixel:
+ *   a'. The ray: the pinhole ray through the pixel centre, o = pos, d = normalize(M s(x, y)) as in step 2 of "temporal
+ *       accumulation", taken into the object's coordinates down the chain of the CURRENT nodes as the lowered scene holds them,
+ *       the way the renderer takes a ray: per node p' = itm (p - pos), d' = itm ((p + d) - pos) - p', from the root downwards.
+ *       The direction is not renormalised, so the ray parameter t is a world distance.
+ *   b'. The hit: the closest hit of that ray with the mesh's tree on the device, by the triangle test of `shade_model`, the model
+ *       the frame was rendered with (as for rt_trace_rays: RT_SHADE_FIN's two-sided test, or the back-face-culled one of every other
+ *       model) -- the slot s of the triangle, its barycentrics bc and the distance t.
+ *   c'. The gate: the pixel has NO PREVIOUS POSITION and holds (x, y, 0) when the ray misses the mesh or |t - z_p| >
+ *       depth_tol * z_p (one float32 difference against one float32 product).  z_p belongs to a jittered sample: a centre ray that
+ *       slips past a silhouette onto a farther layer must not borrow that layer's motion.
+ *   d'. The previous point: X'_obj = (bc.x A' + bc.y B') + bc.z C' per component, in this order, without contraction; A', B', C'
+ *       the previous positions of the three vertices of slot s's face.  P_prev = F_i X'_obj, F_i the object-to-world map up the
+ *       chain of the PREVIOUS nodes (per node tm X + pos, from node i up to the root; the current nodes when prev_nodes is
+ *       NULL), composed on the host in double into one affine map per node, rounded to float once -- a second 48-byte table
+ *       beside rt_motion's, uploaded only when it differs -- and evaluated per component ((R_k0 X + R_k1 Y) + R_k2 Z) + t_k.
+ *   e'. Step c. of "motion vectors" with the previous camera: q, fx, fy and z_exp = |P_prev - pos'|.  q.z >= 0: (x, y, 0).
+ * A mesh pixel ALWAYS runs a'.-e'.: there is no DID NOT MOVE shortcut for it (a mesh at rest under a camera at rest comes out
+ * as (x, y, t) within rounding, not exactly).  No atomics: the outputs are byte-identical for identical inputs.
+ * Checked before the GPU is touched, RT_ERR_ARG: a NULL scene; a shade_model that is no RT_SHADE_*; n_nodes other than the scene's node count; every check of rt_motion
+ * (on the scene's nodes and prev_nodes); depth_tol not finite or <= 0 (0.05, sigma_depth's default, is the usual value).  A scene
+ * with a live job is RT_ERR_STATE.  The scene is lowered on `device` first if it is not there, with rt_scene_mesh_device_read's
+ * discipline (the device is claimed, a pending render waited for).  Calls on one device are ordered one behind the other like
+ * rt_motion_device's, with which they share the node table.  A call with sync == 0 may still be reading the lowered scene when
+ * it returns: every setter and update that changes the scene on the device waits for it first.
+ * rt_motion, rt_motion_device and every rt_temporal_* call are unchanged, to the byte. */
+/* The planes are DEVICE pointers on `device`; the kernel is enqueued on `hip_stream` (NULL = the device's legacy null stream)
+ * and the call returns without waiting for it unless `sync` is non-zero. */
+rt_status rt_scene_motion_device(rt_scene *s, int shade_model, int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam,
+                                 const rt_node *prev_nodes, int32_t n_nodes, float depth_tol, const rt_motion_planes *device_planes,
+                                 int sync);
+/* The planes are HOST arrays: upload, compute, download. */
+rt_status rt_scene_motion(rt_scene *s, int shade_model, int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *prev_nodes,
+                          int32_t n_nodes, float depth_tol, const rt_motion_planes *host_planes);
+
 /* motion_dev: a DEVICE plane on the history's device, read by the kernel (it must stay valid until the call's work is done) */
 rt_status rt_temporal_motion_device(rt_history *hst, void *hip_stream, const rt_camera *cam, const rt_temporal_params *p,
                                     const rt_temporal_planes *device_planes, const float *motion_dev, int sync);

@@ -280,10 +280,14 @@ SYMBOLS = [
     "rt_scene_update_mesh_vertices", "rt_scene_mesh_device_read", "rt_scene_mesh_update_ms",
     "rt_scene_material_classes",
     "rt_device_bvh_cost", "rt_scene_mesh_quality", "rt_scene_update_mesh_vertices_auto",
+    "rt_scene_update_mesh_vertices_flags", "rt_scene_update_mesh_vertices_auto_flags", "rt_scene_previous_positions", "rt_scene_mesh_device_previous",
+    "rt_scene_motion_device", "rt_scene_motion",
 ]
 
 # rt_scene_update_mesh_vertices flags (include/rt_mi355x.h): build the tree again instead of refitting it in place
 MESH_UPDATE_REBUILD = 1
+# ... and keep the positions the mesh had as its previous positions ("motion vectors for deforming meshes")
+MESH_UPDATE_KEEP_PREVIOUS = 2
 # rt_mesh_quality flags (include/rt_mi355x.h, "mesh tree quality")
 MESH_QUALITY_DEGENERATE = 1
 MESH_QUALITY_REBUILT = 2
@@ -450,6 +454,16 @@ def lib():
         _lib.rt_scene_mesh_quality.argtypes = [vp, C.c_int, i32, vp]
         _lib.rt_scene_update_mesh_vertices_auto.argtypes = [vp, i32, vp, i32, vp, i32, C.c_double, vp]
         for name in ("rt_device_bvh_cost", "rt_scene_mesh_quality", "rt_scene_update_mesh_vertices_auto"):
+            getattr(_lib, name).restype = C.c_int
+        # motion vectors for deforming meshes (rt_mi355x.h)
+        _lib.rt_scene_update_mesh_vertices_flags.argtypes = [vp, i32, vp, i32, vp, i32, C.c_uint32]
+        _lib.rt_scene_update_mesh_vertices_auto_flags.argtypes = [vp, i32, vp, i32, vp, i32, C.c_double, C.c_uint32, vp]
+        _lib.rt_scene_previous_positions.argtypes = [vp, C.POINTER(i32)]
+        _lib.rt_scene_mesh_device_previous.argtypes = [vp, C.c_int, i32, vp, C.c_uint64, C.POINTER(C.c_uint32)]
+        _lib.rt_scene_motion_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, i32, C.c_float, vp, C.c_int]
+        _lib.rt_scene_motion.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, i32, C.c_float, vp]
+        for name in ("rt_scene_update_mesh_vertices_flags", "rt_scene_update_mesh_vertices_auto_flags", "rt_scene_previous_positions", "rt_scene_mesh_device_previous",
+                     "rt_scene_motion_device", "rt_scene_motion"):
             getattr(_lib, name).restype = C.c_int
         for name in ("rt_render_begin_linear", "rt_render_tiles_linear_device", "rt_render_tiles_packed_linear_device",
                      "rt_tiles_unpack_linear_device", "rt_image_write_pfm", "rt_image_read_pfm",
@@ -1211,22 +1225,69 @@ class Scene:
         if vt is not None and len(vt):
             self.set_mesh_texcoords(index, vt, ft)
 
-    def update_mesh_vertices(self, index, v, vn=None, rebuild=False, max_ratio=None):
+    def update_mesh_vertices(self, index, v, vn=None, rebuild=False, max_ratio=None, keep_previous=False):
         """new positions (and normals, unless vn is None) for a mesh whose faces stay: refitted in place on the devices that hold
         the scene; rebuild=True takes set_mesh's path instead (the tree is built again at the next use).  max_ratio (>= 1): the
         refitted tree is measured as well (rt_scene_update_mesh_vertices_auto) and built again at the next use when its SAH cost
-        has grown beyond max_ratio times the built tree's; the call then returns mesh_quality()'s dict, else None"""
+        has grown beyond max_ratio times the built tree's; the call then returns mesh_quality()'s dict, else None.
+        keep_previous=True (RT_MESH_UPDATE_KEEP_PREVIOUS; goes with either): the positions the mesh had become its previous
+        positions, which motion() follows its pixels through; an update without it makes the mesh rigid again"""
         if max_ratio is not None and rebuild:
             raise ValueError("update_mesh_vertices: rebuild=True and max_ratio exclude each other")
         v = _c(v, np.float32).reshape(-1, 3)
         vn = _c(vn, np.float32).reshape(-1, 3) if vn is not None else None
         if max_ratio is not None:
             q = MeshQuality(struct_size=C.sizeof(MeshQuality))
-            _check(lib().rt_scene_update_mesh_vertices_auto(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
-                                                            len(vn) if vn is not None else 0, C.c_double(max_ratio), C.byref(q)))
+            _check(lib().rt_scene_update_mesh_vertices_auto_flags(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
+                                                                  len(vn) if vn is not None else 0, C.c_double(max_ratio),
+                                                                  C.c_uint32(MESH_UPDATE_KEEP_PREVIOUS if keep_previous else 0), C.byref(q)))
             return q.as_dict()
-        _check(lib().rt_scene_update_mesh_vertices(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
-                                                   len(vn) if vn is not None else 0, C.c_uint32(MESH_UPDATE_REBUILD if rebuild else 0)))
+        flags = (MESH_UPDATE_REBUILD if rebuild else 0) | (MESH_UPDATE_KEEP_PREVIOUS if keep_previous else 0)
+        _check(lib().rt_scene_update_mesh_vertices_flags(self._h, int(index), _p(v), len(v), _p(vn) if vn is not None else None,
+                                                         len(vn) if vn is not None else 0, C.c_uint32(flags)))
+
+    def previous_positions(self):
+        """how many meshes of the scene hold previous positions (from the scene store: no GPU)"""
+        n = C.c_int32()
+        _check(lib().rt_scene_previous_positions(self._h, C.byref(n)))
+        return n.value
+
+    def mesh_device_previous(self, index, device=0):
+        """the previous positions of mesh `index` as they sit on `device` (lowered there first if need be): float32 (nv, 3), or
+        None when the mesh holds none"""
+        n = C.c_uint32()
+        _check(lib().rt_scene_mesh_device_previous(self._h, int(device), int(index), None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, 3), np.float32)
+        _check(lib().rt_scene_mesh_device_previous(self._h, int(device), int(index), _p(out), len(out), C.byref(n)))
+        return out
+
+    def motion(self, cam, prev_cam, prev_nodes, z, object_id, depth_tol=0.05, device=0, shade_model=SHADE_FIN):
+        """rt_scene_motion on host arrays: capi.motion() with the scene's own nodes as this frame's, and the pixels of every mesh
+        that holds previous positions (update_mesh_vertices(keep_previous=True)) followed through the deformation (rt_mi355x.h,
+        "motion vectors for deforming meshes").  shade_model: the model the frame was rendered with (whose triangle test walks the
+        meshes: SHADE_FIN's two-sided one, or the back-face-culled one of every other model).  prev_nodes: the NODE array of the previous frame (None: the nodes did not move).
+        Returns float32 (H, W, 3): fx, fy, z_exp (z_exp <= 0: no previous position)."""
+        prev = _c(prev_nodes, NODE) if prev_nodes is not None else None
+        z, ids = _c(z, np.float32), _c(object_id, np.int32)
+        h, w = cam.height, cam.width
+        assert z.shape == ids.shape == (h, w)
+        out = np.empty((h, w, 3), np.float32)
+        pl = MotionPlanes(z=z.ctypes.data, object_id=ids.ctypes.data, motion=out.ctypes.data)
+        _check(lib().rt_scene_motion(self._h, int(shade_model), int(device), C.byref(cam), C.byref(prev_cam), _p(prev) if prev is not None else None,
+                                     len(prev) if prev is not None else self.counts()["nodes"], C.c_float(depth_tol), C.byref(pl)))
+        return out
+
+    def motion_device(self, device, stream, cam, prev_cam, prev_nodes, *, z_ptr, object_id_ptr, motion_ptr, depth_tol=0.05, sync=True,
+                      shade_model=SHADE_FIN):
+        """rt_scene_motion_device: the same on image-sized DEVICE planes, enqueued on `stream` (an explicit stream's handle; None =
+        the null stream of the device).  prev_nodes stays a host array; it is consumed before the call returns."""
+        prev = _c(prev_nodes, NODE) if prev_nodes is not None else None
+        pl = MotionPlanes(z=z_ptr, object_id=object_id_ptr, motion=motion_ptr)
+        _check(lib().rt_scene_motion_device(self._h, int(shade_model), int(device), _stream_handle(stream), C.byref(cam), C.byref(prev_cam),
+                                            _p(prev) if prev is not None else None, len(prev) if prev is not None else self.counts()["nodes"],
+                                            C.c_float(depth_tol), C.byref(pl), 1 if sync else 0))
 
     def mesh_quality(self, index, device=0):
         """the SAH cost of mesh `index`'s tree as it sits on `device` (lowered there first if need be), by k_bvh_cost:
@@ -1518,6 +1579,9 @@ class Scene:
         moving=True, accumulate(), accumulate_device() -- makes it forget the remembered frame: the next moving=True frame then
         takes the nodes as not moved since, and the camera from the history as rt_temporal does (prev_cam cannot be known here,
         so that frame is accumulated WITHOUT a motion plane; "motion" is still added, computed with prev_cam = cam).
+        When a mesh of the scene holds previous positions (update_mesh_vertices(keep_previous=True)) the plane is the scene's
+        own (Scene.motion, with params.shade_model), which follows the deformed surface; for every other
+        scene it is capi.motion's, as it always was.
         clip: history rectification, as History.accumulate's (True, or a dict of radius, k_clip, min_count, clip_history);
         "clipped" (float32 (H, W): 0 no history, 1 kept, 2 clipped) is added.  Works with moving=True.
         bloom: a Bloom of the camera's size on `device` -- the final linear plane is bloomed before it is tone-mapped, as in
@@ -1539,7 +1603,7 @@ class Scene:
         out = self.render_outputs(_pinhole(cam) if depth_of_field is not None else cam, params, planes=("linear",) + FEATURE_PLANES + ("variance",),
                                   device=device, photon_pass=photon_pass)
         if moving:
-            out["motion"], known, remember = self._motion_since(history, cam, out["z"], out["object_id"], device)
+            out["motion"], known, remember = self._motion_since(history, cam, out["z"], out["object_id"], device, params.shade_model)
             if known:
                 t_kw["motion"] = out["motion"]
         if clip is not None:
@@ -1575,7 +1639,7 @@ class Scene:
             out["display_rgb"] = exposure.tonemap(final, out["object_id"], **dict({"gamma": params.gamma}, **(tonemap_kw or {})))
         return out
 
-    def _motion_since(self, history, cam, z, object_id, device):
+    def _motion_since(self, history, cam, z, object_id, device, shade_model=SHADE_FIN):
         """render_temporal(moving=True): (the motion plane from the frame `history` remembers to this one, computed on the
         device; whether the frame the history holds is the remembered one, so that the plane may replace the reprojection; what
         to remember of this frame)"""
@@ -1583,7 +1647,10 @@ class Scene:
         first = history.frames == 0
         known = first or (history._moving is not None and len(history._moving[1]) == len(nodes))
         prev_cam, prev_nodes = history._moving if known and not first else (cam, None)
-        plane = motion(cam, prev_cam, nodes, prev_nodes, z, object_id, device=device)
+        if self.previous_positions():            # a mesh was deformed with keep_previous: the scene form, which follows its pixels
+            plane = self.motion(cam, prev_cam, prev_nodes, z, object_id, device=device, shade_model=shade_model)
+        else:
+            plane = motion(cam, prev_cam, nodes, prev_nodes, z, object_id, device=device)
         return plane, known, (_copy_camera(cam), nodes)
 
     def render_tiles_outputs_device(self, cam, params, tiles, device, rgb_ptr, z_ptr, cnt_ptr, stream=None, sync=True,

@@ -315,6 +315,9 @@ struct MeshData {
     // of four) when somebody reads them; until then root_box is what the new nodes[1].box will be (MeshRootBox)
     bool tree_stale = false;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
+    // the positions before the last rt_scene_update_mesh_vertices with RT_MESH_UPDATE_KEEP_PREVIOUS, indexed like v; empty: the
+    // mesh holds none (never flagged, or set again, or updated without the flag since)
+    std::vector<float> v_prev;
 };
 struct SceneData {
     std::vector<rt_node> nodes;

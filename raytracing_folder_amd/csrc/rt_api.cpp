@@ -153,6 +153,7 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     m.nodes.assign(nodes, nodes + nnodes); m.elements.assign(elements, elements + nf);
     m.tree_stale = false;
     m.vt.clear(); m.ft.clear();
+    m.v_prev.clear();                   // the faces may have changed: no pairing of old and new vertices is vouched for
     s->geometry_changed();
     return RT_OK;
 }
@@ -173,8 +174,10 @@ static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
 }
 
 // What rt_scene_update_mesh_vertices and rt_scene_update_mesh_vertices_auto share: the argument checks (`who` names the entry
-// point in the message) and, once they pass, the new vertices in the store.  The caller holds s->mu.
-static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, const char *who)
+// point in the message) and, once they pass, the new vertices in the store.  keep_previous (RT_MESH_UPDATE_KEEP_PREVIOUS): the
+// positions the mesh had become its previous positions; without it the mesh holds none afterwards.  The caller holds s->mu.
+static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, bool keep_previous,
+                                     const char *who)
 {
     if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
         return fail(RT_ERR_ARG, "%s: mesh %d was never set", who, mesh);
@@ -182,6 +185,7 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
     if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, nv, m.v.size() / 3);
     if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
         return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
+    if (keep_previous) m.v_prev.swap(m.v); else std::vector<float>().swap(m.v_prev);
     m.v.assign(v, v + 3 * (size_t)nv);
     if (vn) m.vn.assign(vn, vn + 3 * (size_t)nvn);
     m.tree_stale = true;
@@ -191,30 +195,47 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
     return RT_OK;
 }
 
+// known: the flag bits the entry point `who` takes
+static rt_status update_mesh_vertices(const char *who, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                      uint32_t flags, uint32_t known)
+{
+    rt_status st = check_idle(s, who);
+    if (st) return st;
+    if (flags & ~known) return fail(RT_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags & ~known);
+    const bool keep = (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0;
+    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep, who))) return st;
+    if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }      // (the next lowering uploads the previous positions from the store)
+    return refit_mesh_on_devices(s, mesh, vn != nullptr, nullptr);
+}
+
+// takes what it always took: any bit but RT_MESH_UPDATE_REBUILD stays RT_ERR_ARG, and the mesh holds no previous positions afterwards
 extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
 {
-    rt_status st = check_idle(s, "rt_scene_update_mesh_vertices");
-    if (st) return st;
-    if (flags & ~RT_MESH_UPDATE_REBUILD) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: unknown flag bits 0x%x", flags & ~RT_MESH_UPDATE_REBUILD);
-    if (!v) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices: v is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, "rt_scene_update_mesh_vertices"))) return st;
-    if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }
-    return refit_mesh_on_devices(s, mesh, vn != nullptr);
+    return update_mesh_vertices("rt_scene_update_mesh_vertices", s, mesh, v, nv, vn, nvn, flags, RT_MESH_UPDATE_REBUILD);
+}
+
+// ... and the entry point that takes RT_MESH_UPDATE_KEEP_PREVIOUS as well
+extern "C" rt_status rt_scene_update_mesh_vertices_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
+{
+    return update_mesh_vertices("rt_scene_update_mesh_vertices_flags", s, mesh, v, nv, vn, nvn, flags, RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS);
 }
 
 // flags 0 of the call above, the refitted tree measured behind the refit (rt_lower.cpp), and REBUILD's path taken when the measure says so
-extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                                        double max_ratio, rt_mesh_quality *out)
+static rt_status update_mesh_vertices_auto(const char *who, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                           double max_ratio, uint32_t flags, rt_mesh_quality *out)
 {
-    rt_status st = check_idle(s, "rt_scene_update_mesh_vertices_auto");
+    rt_status st = check_idle(s, who);
     if (st) return st;
-    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: max_ratio is %g (it must be finite and at least 1)", max_ratio);
+    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS)
+        return fail(RT_ERR_ARG, "%s: flag bits 0x%x (only RT_MESH_UPDATE_KEEP_PREVIOUS goes with max_ratio)", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
+    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "%s: max_ratio is %g (it must be finite and at least 1)", who, max_ratio);
     if (out && out->struct_size != sizeof(rt_mesh_quality))
-        return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: rt_mesh_quality.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_quality));
-    if (!v) return fail(RT_ERR_ARG, "rt_scene_update_mesh_vertices_auto: v is NULL");
+        return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", who, out->struct_size, sizeof(rt_mesh_quality));
+    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
     std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, "rt_scene_update_mesh_vertices_auto"))) return st;
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
     rt_mesh_quality q = {};
     q.struct_size = sizeof q;
     st = refit_mesh_on_devices(s, mesh, vn != nullptr, &q);
@@ -223,6 +244,30 @@ extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mes
     if (out) *out = q;
     return st;
 }
+
+extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                        double max_ratio, rt_mesh_quality *out)
+{
+    return update_mesh_vertices_auto("rt_scene_update_mesh_vertices_auto", s, mesh, v, nv, vn, nvn, max_ratio, 0u, out);
+}
+
+extern "C" rt_status rt_scene_update_mesh_vertices_auto_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                              double max_ratio, uint32_t flags, rt_mesh_quality *out)
+{
+    return update_mesh_vertices_auto("rt_scene_update_mesh_vertices_auto_flags", s, mesh, v, nv, vn, nvn, max_ratio, flags, out);
+}
+
+// how many meshes of the scene hold previous positions, from the store (no device, no HIP call)
+extern "C" rt_status rt_scene_previous_positions(const rt_scene *s, int32_t *n_meshes)
+{
+    if (!s || !n_meshes) return fail(RT_ERR_ARG, "rt_scene_previous_positions: NULL argument");
+    std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+    int32_t n = 0;
+    for (const rt::MeshData &m : s->data.meshes) n += !m.f.empty() && !m.v_prev.empty();
+    *n_meshes = n;
+    return RT_OK;
+}
+
 
 extern "C" rt_status rt_scene_set_mesh_texcoords(rt_scene *s, int32_t mesh, const float *vt, int32_t nvt, const uint32_t *ft)
 {

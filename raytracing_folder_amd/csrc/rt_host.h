@@ -36,6 +36,9 @@ RT_HIDDEN bool device_is_gfx950(int dev);                              // rt_api
 RT_HIDDEN void camera_setup(const rt_camera &cam, DevCamera &dc);      // of RenderPixel (rt_render.cpp)
 // rt_scene_destroy of the last scene: the per-device scratch of the image-space stages goes with it (rt_post.cpp)
 RT_HIDDEN void post_release_all();
+// rt_post.cpp: an rt_scene_motion_device call that did not synchronise may still be reading the lowered scene on `device`; waited
+// for on the host before that scene is overwritten (prepare_device, the in-place mesh update)
+RT_HIDDEN rt_status motion_wait_host(int device);
 
 struct DevBuf {
     void *p = nullptr; size_t bytes = 0;
@@ -80,10 +83,11 @@ struct RT_HIDDEN Event {
 // nodes .. tex are what DevMesh points to.  The rest serves rt_scene_update_mesh_vertices (rt_refit.hip) and is written at upload
 // time with them: per triangle slot the three vertex and three normal indices of its face; the indices of the tree's nodes by
 // depth, the deepest level first (level k is level_nodes[level_off[k] .. level_off[k + 1]), the root's level last); on the host,
-// what rt_scene_mesh_device_read reports.  v and vn exist from the first update on.
+// what rt_scene_mesh_device_read reports.  v and vn exist from the first update on.  v_prev: the mesh's previous positions
+// (RT_MESH_UPDATE_KEEP_PREVIOUS; nv x 3 floats, indexed like v), there exactly while the store holds some: k_motion_mesh reads them.
 struct DevMeshBufs {
     DevBuf nodes, tris, nrm, tex;
-    DevBuf slot_idx, level_nodes, v, vn;
+    DevBuf slot_idx, level_nodes, v, vn, v_prev;
     std::vector<uint32_t> level_off, slot_face;
     uint32_t root_ref = 0; int stack_need = 0;
     // mesh tree quality (rt_scene_mesh_quality): the cost of the tree as the host built it, from the host mirror on the host's own
@@ -93,7 +97,7 @@ struct DevMeshBufs {
     double built_cost = 0; uint32_t built_flags = 0;
     DevBuf cost_partials;
     std::vector<double> cost_host;
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &cost_partials}) b->release(); }
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials}) b->release(); }
 };
 
 static const size_t SPILL_BYTES = (size_t)RT_SPILL_BLOCKS * RT_BLOCK * RT_BVH_SPILL * 4;     // DevScene::bvh_spill / DevWork::bvh_spill
@@ -137,6 +141,7 @@ struct DeviceState {
     bool scene_valid = false;
     DevBuf nodes, objects, objects_back, meshes, materials, material_class, lights, node_material, textures, texels, material_maps;
     std::vector<DevMeshBufs> mesh_bufs;
+    std::vector<int32_t> node_object;           // per node: its object in the lowered scene (DevScene::objects), -1 when it carries none
     PhotonStore maps[2];                        // [0] the photon map (scene.pm), [1] the caustic map (scene.cm)
     DevBuf raw_photons;                         // 24-byte photons of the last photon pass on this device (1-based)
     DevBuf bvh_spill;                           // DevScene::bvh_spill of the single-stage entry points (rt_trace_rays, the photon pass); renders use their working set's

@@ -1,5 +1,5 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_photons.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
-// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
+// rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_motion_mesh.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
 #ifndef RT_LAUNCH_H
@@ -152,6 +152,23 @@ struct MotionRequest {
     float *motion;
 };
 
+// One motion plane of a scene whose meshes may have deformed (rt_motion_mesh.hip; the definition: rt_mi355x.h, "motion vectors for
+// deforming meshes").  `rigid` is the MotionRequest of the same frame: a pixel whose node has no entry in `mesh_nodes` is k_motion's.
+// mesh_nodes: one record per node on the device -- object < 0: rigid; otherwise the node's object in the lowered scene S (whose
+// chain takes the ray into the mesh's coordinates), its mesh, that mesh's previous positions (nv x 3 floats, indexed like v) and
+// its slots' indices (six uint32 per triangle slot, the first three into v).  from: one DevNodeMotion per node, the PREVIOUS
+// chain's object-to-world map, composed on the host in double.  p13: the scene's triangle test is tri_hit_p13, else tri_hit_fin.
+// spill: NULL, or RT_SPILL_BLOCKS * RT_BLOCK threads' RT_BVH_SPILL entries (required when S.max_bvh_depth > RT_BVH_STACK).
+struct DevMotionMeshNode { int32_t object, mesh; const float *v_prev; const uint32_t *slot_idx; };
+struct MotionMeshRequest {
+    MotionRequest rigid;
+    DevScene S;
+    const DevMotionMeshNode *mesh_nodes;        // [rigid.n_nodes]
+    const DevNodeMotion *from;                  // [rigid.n_nodes]
+    float depth_tol; bool p13;
+    uint32_t *spill;
+};
+
 // One tone-mapped width x height frame (rt_tonemap.hip; the definition: rt_mi355x.h, "exposure and tone mapping").  The planes are
 // the caller's device pointers (object_id and one of out_display / out_rgb8 may be NULL; out_display may be rgb_linear), the
 // parameters are validated by the caller.  meter: k_luminance_hist and k_exposure_meter run on `state` first and k_tonemap takes
@@ -299,6 +316,10 @@ void rtk_launch_temporal_clip(hipStream_t st, const TemporalClipRequest &R);
 // ---- rt_motion.hip: motion vectors in image space ------------------------------------------------------------------------
 // k_motion over the frame on `st`: reads z, object_id and the node table, writes the motion plane
 void rtk_launch_motion(hipStream_t st, const MotionRequest &R);
+
+// ---- rt_motion_mesh.hip: motion vectors for deforming meshes ---------------------------------------------------------------
+// k_motion_mesh over the frame on `st`, at most RT_SPILL_BLOCKS workgroups of RT_BLOCK lanes walking the 32 x 8 tiles
+void rtk_launch_motion_mesh(hipStream_t st, const MotionMeshRequest &R);
 
 // ---- rt_tonemap.hip: exposure and tone mapping ---------------------------------------------------------------------------
 // on `st`: k_luminance_hist and k_exposure_meter (when R.meter), then k_tonemap<R.op>

@@ -395,6 +395,8 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     if ((st = D->objects.upload(objs.data(), objs.size() * sizeof(DevObject)))) return st;
     if ((st = D->objects_back.upload(backs.data(), backs.size() * sizeof(DevObjectBack)))) return st;
     if ((st = D->node_material.upload(node_mat.data(), node_mat.size() * 4))) return st;
+    D->node_object.assign((size_t)nn, -1);
+    for (size_t k = 0; k < objs.size(); k++) D->node_object[objs[k].node] = (int32_t)k;
     if ((st = D->materials.upload(sd.materials.data(), sd.materials.size() * sizeof(rt_blinn)))) return st;
     std::vector<uint32_t> mat_class;
     lower_material_classes(s, mat_class);
@@ -439,6 +441,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
         if ((st = mb.nodes.upload(bn.data(), bn.size() * sizeof(DevBvhNode)))) return st;
         if ((st = mb.tris.upload(tris.data(), tris.size() * sizeof(DevTri)))) return st;
         if ((st = mb.nrm.upload(nrm.data(), nrm.size() * 4))) return st;
+        if (!m.v_prev.empty() && (st = mb.v_prev.upload(m.v_prev.data(), m.v_prev.size() * 4))) return st;      // survives a rebuild: per vertex, not per slot
         {   // what an in-place vertex update works from (DevMeshBufs): the slots' indices, and the nodes by depth, deepest first
             std::vector<uint32_t> slot_idx(6 * nf);
             for (size_t sidx = 0; sidx < nf; sidx++)
@@ -519,16 +522,22 @@ static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
 {
     HIP_TRY(hipSetDevice(D->device));
     if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
+    rt_status rs;
+    if ((rs = motion_wait_host(D->device))) return rs;                                      // ... or k_motion_mesh walking it
     const size_t nf = m.f.size() / 3;
     if ((size_t)mesh >= D->mesh_bufs.size() || D->mesh_bufs[mesh].slot_face.size() != nf || objs.size() != (size_t)D->scene.n_objects)
         return fail(RT_ERR_STATE, "rt_scene_update_mesh_vertices: device %d does not hold mesh %d as the scene has it", D->device, mesh);
     DevMeshBufs &mb = D->mesh_bufs[mesh];
     hipStream_t st = D->stream;
     for (Event &e : D->upd_ev) if (!e.e) HIP_TRY(e.create());
-    rt_status rs;
     const bool first = mb.vn.p == nullptr;
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    // the previous positions follow the store: uploaded from it ahead of the new vertices, in the update's stream, by a flagged
+    // update; released by an unflagged one (nothing is allocated, copied or freed for a mesh that never used the flag)
+    if (m.v_prev.empty()) mb.v_prev.release();
+    else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
     HIP_TRY(hipEventRecord(D->upd_ev[0], st));
+    if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
     if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(D->upd_ev[1], st));
@@ -709,6 +718,31 @@ extern "C" rt_status rt_scene_mesh_device_read(rt_scene *s, int device, int32_t 
     return RT_OK;
 }
 
+// the previous positions of one mesh as they sit on `device`, with rt_scene_mesh_device_read's discipline
+extern "C" rt_status rt_scene_mesh_device_previous(rt_scene *s, int device, int32_t mesh, float *v_prev, uint64_t nv_cap, uint32_t *nv_out)
+{
+    if (!s || !nv_out) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: NULL argument");
+    size_t nv = 0;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: mesh %d was never set", mesh);
+        nv = s->data.meshes[mesh].v.size() / 3;
+    }
+    DeviceState *D = nullptr;
+    rt_status st = prepare_device(s, device, &D);
+    if (st) return st;
+    DeviceClaim claim(D);
+    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_device_previous: another call on this scene is using device %d", device);
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
+    const DevMeshBufs &mb = D->mesh_bufs[mesh];
+    if (!mb.v_prev.p) { *nv_out = 0; return RT_OK; }
+    if (v_prev && nv_cap < nv) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: room for %llu vertices, %zu needed", (unsigned long long)nv_cap, nv);
+    HIP_TRY(hipStreamSynchronize(D->stream));
+    if (v_prev) HIP_TRY(hipMemcpy(v_prev, mb.v_prev.p, nv * 12, hipMemcpyDeviceToHost));
+    *nv_out = (uint32_t)nv;
+    return RT_OK;
+}
+
 rt_status prepare_device(rt_scene *s, int device, DeviceState **out)
 {
     int n = 0;
@@ -723,6 +757,7 @@ rt_status prepare_device(rt_scene *s, int device, DeviceState **out)
     // an asynchronous render (sync == 0) may still be reading the buffers an upload is about to overwrite (scene tables and
     // photon structure are re-used in place when the new data fits): wait for it on the host first
     if ((!D->scene_valid || !D->maps[0].valid || !D->maps[1].valid) && D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
+    if (!D->scene_valid && (st = motion_wait_host(device))) return st;      // (k_motion_mesh reads the scene tables and the meshes, not the photon maps)
     if (!D->scene_valid) { const DevPhotonMap keep = D->scene.pm, keepc = D->scene.cm; if ((st = upload_scene(s, D))) return st; D->scene.pm = keep; D->scene.cm = keepc; }
     for (int caustic = 0; caustic < 2; caustic++)
         if (!D->maps[caustic].valid && (st = upload_photons(s, D, caustic != 0))) return st;

@@ -41,18 +41,8 @@ __global__ __launch_bounds__(RT_MOTION_TILE_W * RT_MOTION_TILE_H) void k_motion(
     const int id = A.object_id[p];
     float fx = (float)x, fy = (float)y, zexp = 0.0f;        // "no previous position"
     // (zp < 1e30 is false for NaN and +inf; -inf fails zp - zp == 0)
-    if (id >= 0 && id < A.n_nodes && zp < RT_MOTION_NO_HIT && zp - zp == 0.0f) {
-        const float4 *rows = A.table[id].row;
-        DevNodeMotion a;
-        a.row[0] = rows[0]; a.row[1] = rows[1]; a.row[2] = rows[2];
-        Reprojected r;
-        const bool still = A.same_camera && zp > 0.0f &&
-                           a.row[0].x == 1.0f && a.row[0].y == 0.0f && a.row[0].z == 0.0f && a.row[0].w == 0.0f &&
-                           a.row[1].x == 0.0f && a.row[1].y == 1.0f && a.row[1].z == 0.0f && a.row[1].w == 0.0f &&
-                           a.row[2].x == 0.0f && a.row[2].y == 0.0f && a.row[2].z == 1.0f && a.row[2].w == 0.0f;
-        if (still) zexp = zp;           // did not move: (x, y, z) exactly
-        else if (reproject_pixel<true>(A.cur, A.old, x, y, zp, &a, r)) { fx = r.fx; fy = r.fy; zexp = r.zexp; }
-    }
+    if (id >= 0 && id < A.n_nodes && zp < RT_MOTION_NO_HIT && zp - zp == 0.0f)
+        motion_rigid_pixel(A.cur, A.old, A.same_camera, A.table + id, x, y, zp, fx, fy, zexp);
     A.motion[3 * p] = fx; A.motion[3 * p + 1] = fy; A.motion[3 * p + 2] = zexp;
 }
 

@@ -1,5 +1,6 @@
 // rt_post.cpp -- the image-space stages of the C ABI in include/rt_mi355x.h: denoising, temporal accumulation, motion vectors,
-// exposure and tone mapping, bloom, motion blur, depth of field.  None of them knows a scene.  Every stage is the same few steps -- check the
+// exposure and tone mapping, bloom, motion blur, depth of field.  None of them knows a scene, but for the scene form of the motion
+// vectors (rt_scene_motion: "motion vectors for deforming meshes", which walks a lowered scene's meshes).  Every stage is the same few steps -- check the
 // versioned structs and the image size, find the device, order the stream behind the previous call on the same object, launch,
 // record -- and its host entry point is the device one between an upload and a download; the pieces they share come first.
 // There is no CPU path: without a gfx950 device the calls fail.
@@ -555,7 +556,17 @@ static rt_status motion_check(const char *name, const rt_camera *cam, const rt_c
 // stream behind the previous call's event, whatever that call's stream was and whether or not the table changes: the event
 // then stands for ALL earlier calls, and waiting for it on the host before an overwrite leaves no kernel that still reads the
 // table.
-namespace { struct MotionDevice { DevBuf table; std::vector<DevNodeMotion> held; StageSync sync; void release() { table.release(); } }; }
+// rt_scene_motion_device keeps two more tables beside it under the same discipline -- the previous chains' object-to-world maps
+// and the per-node mesh records -- and, for a scene whose trees can outgrow the LDS stack, k_motion_mesh's spill buffer.
+namespace {
+struct MotionDevice {
+    DevBuf table, from, mesh_nodes, spill;
+    std::vector<DevNodeMotion> held, held_from;
+    std::vector<DevMotionMeshNode> held_mesh;
+    StageSync sync;
+    void release() { for (DevBuf *b : {&table, &from, &mesh_nodes, &spill}) b->release(); held.clear(); held_from.clear(); held_mesh.clear(); }
+};
+}
 static std::mutex g_motion_mu;
 static PerDevice<MotionDevice> g_motion;          // under g_motion_mu
 
@@ -563,6 +574,27 @@ void post_release_all()
 {
     release_devices(g_denoise_mu, g_denoise);
     release_devices(g_motion_mu, g_motion);
+}
+
+rt_status motion_wait_host(int device)
+{
+    std::lock_guard<std::mutex> lk(g_motion_mu);
+    for (auto &d : g_motion) if (d.first == device) return d.second.sync.wait_host();
+    return RT_OK;
+}
+
+// a call's table onto the device when it differs from the one held there (the caller holds g_motion_mu and has made its stream
+// wait for sync's event: waiting for that event on the host leaves no kernel that still reads the table)
+template <class T> static rt_status motion_upload_if_different(DevBuf &buf, std::vector<T> &held, const std::vector<T> &table, StageSync &sync)
+{
+    const size_t bytes = table.size() * sizeof(T);
+    if (held.size() == table.size() && memcmp(held.data(), table.data(), bytes) == 0) return RT_OK;
+    rt_status rs = sync.wait_host();
+    if (rs) return rs;
+    held.clear();
+    if ((rs = buf.upload(table.data(), bytes))) return rs;
+    held = table;
+    return RT_OK;
 }
 
 static rt_status motion_on_device(const char *name, int device, hipStream_t st, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *nodes,
@@ -576,14 +608,8 @@ static rt_status motion_on_device(const char *name, int device, hipStream_t st, 
     std::lock_guard<std::mutex> lk(g_motion_mu);
     MotionDevice &D = device_entry(g_motion, device);
     if (!D.sync.done) HIP_TRY(D.sync.create());
-    const size_t bytes = table.size() * sizeof(DevNodeMotion);
     if ((rs = D.sync.wait(st))) return rs;
-    if (D.held.size() != table.size() || memcmp(D.held.data(), table.data(), bytes) != 0) {
-        if ((rs = D.sync.wait_host())) return rs;
-        D.held.clear();
-        if ((rs = D.table.upload(table.data(), bytes))) return rs;
-        D.held = table;
-    }
+    if ((rs = motion_upload_if_different(D.table, D.held, table, D.sync))) return rs;
     MotionRequest R = {};
     R.width = cam->width; R.height = cam->height; R.n_nodes = n_nodes;
     camera_setup(*cam, R.cur);
@@ -613,6 +639,116 @@ extern "C" rt_status rt_motion(int device, const rt_camera *cam, const rt_camera
     if (S.st) return S.st;
     const rt_motion_planes dev = {(uint32_t)sizeof dev, S.dev<float>(z), S.dev<int32_t>(id), S.dev<float>(mv)};
     if ((st = motion_on_device("rt_motion", device, nullptr, cam, prev_cam, nodes, prev_nodes, n_nodes, &dev, 1))) return st;
+    return S.download({mv});
+}
+
+// ---- motion vectors for deforming meshes ------------------------------------------------------------------------------------
+// The one image-space stage that knows a scene: the pixels of a mesh that holds previous positions are traced (rt_motion_mesh.hip).
+// The second table: per node i the object-to-world map up the chain i .. root of `nodes` (per node tm X + pos), composed in double
+// and rounded to float once.  The parents were validated by the caller.
+static void motion_from_table(const rt_node *nodes, int32_t n, std::vector<DevNodeMotion> &table)
+{
+    table.resize((size_t)n);
+    std::vector<Affine64> from((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const rt_node &o = nodes[i];
+        const double op[3] = {o.pos[0], o.pos[1], o.pos[2]};
+        const Affine64 up = Affine64().then(o.tm, op);
+        const Affine64 &A = from[i] = o.parent < 0 ? up : up.then(from[o.parent]);
+        for (int k = 0; k < 3; k++) table[i].row[k] = make_float4((float)A.r[3 * k], (float)A.r[3 * k + 1], (float)A.r[3 * k + 2], (float)A.t[k]);
+    }
+}
+
+// everything that can be refused without a device, for both entry points; leaves the scene's nodes in `nodes`
+static rt_status scene_motion_check(const char *name, rt_scene *s, int shade_model, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *prev_nodes,
+                                    int32_t n_nodes, float depth_tol, const rt_motion_planes *pl, std::vector<rt_node> &nodes)
+{
+    if (!s) return fail(RT_ERR_ARG, "%s: the scene is NULL", name);
+    if (shade_model < RT_SHADE_FIN || shade_model > RT_SHADE_P3) return fail(RT_ERR_ARG, "%s: unknown shading model %d", name, shade_model);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        nodes = s->data.nodes;
+    }
+    if (n_nodes <= 0 || (size_t)n_nodes != nodes.size()) return fail(RT_ERR_ARG, "%s: n_nodes is %d, the scene has %zu nodes", name, n_nodes, nodes.size());
+    rt_status st = motion_check(name, cam, prev_cam, nodes.data(), prev_nodes, n_nodes, pl);
+    if (st) return st;
+    if (!(depth_tol > 0.0f) || !std::isfinite(depth_tol)) return fail(RT_ERR_ARG, "%s: depth_tol must be positive and finite", name);
+    return check_idle(s, name);
+}
+
+static rt_status scene_motion_on_device(const char *name, rt_scene *s, int shade_model, int device, hipStream_t st, const rt_camera *cam, const rt_camera *prev_cam,
+                                        const std::vector<rt_node> &nodes, const rt_node *prev_nodes, float depth_tol, const rt_motion_planes *pl, int sync)
+{
+    DeviceState *DS = nullptr;
+    rt_status rs = prepare_device(s, device, &DS);        // (device range, gfx950, hipSetDevice; lowers the scene if it is not there)
+    if (rs) return rs;
+    DeviceClaim claim(DS);
+    if (!claim.ok) return fail(RT_ERR_STATE, "%s: another call on this scene is using device %d", name, device);
+    if (DS->last_pending && DS->last_done) HIP_TRY(hipEventSynchronize(DS->last_done));
+    const int32_t n_nodes = (int32_t)nodes.size();
+    if (DS->scene.n_nodes != n_nodes || DS->node_object.size() != nodes.size())
+        return fail(RT_ERR_STATE, "%s: device %d does not hold the scene as it is now", name, device);
+    std::vector<DevNodeMotion> table, from;
+    motion_table(nodes.data(), prev_nodes, n_nodes, table);
+    motion_from_table(prev_nodes ? prev_nodes : nodes.data(), n_nodes, from);
+    // a node is a mesh node while its mesh holds previous positions on this device (they follow the store: rt_lower.cpp)
+    std::vector<DevMotionMeshNode> mesh_nodes((size_t)n_nodes);
+    for (int32_t i = 0; i < n_nodes; i++) {
+        DevMotionMeshNode &m = mesh_nodes[i];
+        m.object = m.mesh = -1; m.v_prev = nullptr; m.slot_idx = nullptr;
+        const rt_node &n = nodes[i];
+        if (n.obj_type != RT_OBJ_MESH || DS->node_object[i] < 0 || n.mesh < 0 || (size_t)n.mesh >= DS->mesh_bufs.size()) continue;
+        const DevMeshBufs &mb = DS->mesh_bufs[n.mesh];
+        if (!mb.v_prev.p) continue;
+        m.object = DS->node_object[i]; m.mesh = n.mesh;
+        m.v_prev = (const float *)mb.v_prev.p; m.slot_idx = (const uint32_t *)mb.slot_idx.p;
+    }
+    std::lock_guard<std::mutex> lk(g_motion_mu);
+    MotionDevice &D = device_entry(g_motion, device);
+    if (!D.sync.done) HIP_TRY(D.sync.create());
+    if ((rs = D.sync.wait(st))) return rs;
+    if ((rs = motion_upload_if_different(D.table, D.held, table, D.sync)) || (rs = motion_upload_if_different(D.from, D.held_from, from, D.sync)) ||
+        (rs = motion_upload_if_different(D.mesh_nodes, D.held_mesh, mesh_nodes, D.sync))) return rs;
+    MotionMeshRequest R = {};
+    R.rigid.width = cam->width; R.rigid.height = cam->height; R.rigid.n_nodes = n_nodes;
+    camera_setup(*cam, R.rigid.cur);
+    camera_setup(*prev_cam, R.rigid.old);
+    R.rigid.z = pl->z; R.rigid.object_id = pl->object_id; R.rigid.table = (const DevNodeMotion *)D.table.p; R.rigid.motion = pl->motion;
+    R.S = DS->scene;
+    R.mesh_nodes = (const DevMotionMeshNode *)D.mesh_nodes.p; R.from = (const DevNodeMotion *)D.from.p;
+    R.depth_tol = depth_tol; R.p13 = shade_model != RT_SHADE_FIN;
+    // the traversal stack behind the LDS part: this stage's own, because a call that does not synchronise outlives its claim on
+    // the scene's device state (whose spill buffer the single-stage entry points use)
+    if (DS->scene.max_bvh_depth > RT_BVH_STACK) {
+        if ((rs = D.spill.ensure(SPILL_BYTES))) return rs;
+        R.spill = (uint32_t *)D.spill.p;
+    }
+    rtk_launch_motion_mesh(st, R);
+    HIP_TRY(hipGetLastError());
+    return D.sync.settle(st, sync);
+}
+
+extern "C" rt_status rt_scene_motion_device(rt_scene *s, int shade_model, int device, void *hip_stream, const rt_camera *cam, const rt_camera *prev_cam,
+                                            const rt_node *prev_nodes, int32_t n_nodes, float depth_tol, const rt_motion_planes *device_planes, int sync)
+{
+    std::vector<rt_node> nodes;
+    rt_status st = scene_motion_check("rt_scene_motion_device", s, shade_model, cam, prev_cam, prev_nodes, n_nodes, depth_tol, device_planes, nodes);
+    return st ? st : scene_motion_on_device("rt_scene_motion_device", s, shade_model, device, (hipStream_t)hip_stream, cam, prev_cam, nodes, prev_nodes, depth_tol, device_planes, sync);
+}
+
+extern "C" rt_status rt_scene_motion(rt_scene *s, int shade_model, int device, const rt_camera *cam, const rt_camera *prev_cam, const rt_node *prev_nodes,
+                                     int32_t n_nodes, float depth_tol, const rt_motion_planes *host_planes)
+{
+    std::vector<rt_node> nodes;
+    rt_status st = scene_motion_check("rt_scene_motion", s, shade_model, cam, prev_cam, prev_nodes, n_nodes, depth_tol, host_planes, nodes);
+    if (st || (st = need_gfx950("rt_scene_motion", device))) return st;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)cam->width * (size_t)cam->height;
+    HostPlanes S;
+    const int z = S.in(host_planes->z, n * 4), id = S.in(host_planes->object_id, n * 4), mv = S.out(host_planes->motion, n * 12);
+    if (S.st) return S.st;
+    const rt_motion_planes dev = {(uint32_t)sizeof dev, S.dev<float>(z), S.dev<int32_t>(id), S.dev<float>(mv)};
+    if ((st = scene_motion_on_device("rt_scene_motion", s, shade_model, device, nullptr, cam, prev_cam, nodes, prev_nodes, depth_tol, &dev, 1))) return st;
     return S.download({mv});
 }
 

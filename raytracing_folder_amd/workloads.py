@@ -93,6 +93,19 @@ def deform_wave(v, phase, amplitude):
     return (v + float(amplitude) * d).astype(np.float32)
 
 
+def sheet(n, extent):
+    """an open sheet of n x n quads in the plane z = 0, |x|, |y| <= extent / 2: (n + 1)^2 shared vertices, 2 n^2 triangles wound
+    so that the face normals point to +z.  float32 (nv, 3), uint32 (nf, 3); sheet(1) is one leaf of the device tree"""
+    n = int(n)
+    t = np.linspace(-0.5 * float(extent), 0.5 * float(extent), n + 1)
+    x, y = np.meshgrid(t, t)
+    v = np.stack([x.ravel(), y.ravel(), np.zeros((n + 1) ** 2)], 1).astype(np.float32)
+    j, i = np.mgrid[0:n, 0:n]
+    a = (j * (n + 1) + i).ravel()
+    f = np.concatenate([np.stack([a, a + 1, a + n + 2], 1), np.stack([a, a + n + 2, a + n + 1], 1)]).astype(np.uint32)
+    return v, f
+
+
 def write_obj(path, v, f):
     with open(path, "w") as o:
         for p in v:
