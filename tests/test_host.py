@@ -15,14 +15,51 @@ from tests import scenes
 ROOT = scenes.ROOT
 
 
+# how include/rt_mi355x.h's C types appear in capi.SIGNATURES; every pointer or array parameter but `const char *` is c_void_p
+_HEADER_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+                   "float": C.c_float, "double": C.c_double}
+_HEADER_RETURNS = {"rt_status": C.c_int, "int": C.c_int, "int32_t": C.c_int32, "void": None, "const char *": C.c_char_p}
+
+
+def _header_signatures():
+    """name -> (return type, parameter types) of every function include/rt_mi355x.h declares, in ctypes classes"""
+    text = open(os.path.join(ROOT, "include", "rt_mi355x.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def param(p):
+        p = " ".join(p.split())
+        if "*" in p or "[" in p:
+            return C.c_char_p if re.fullmatch(r"const char \*\s*\w*", p) else C.c_void_p
+        return _HEADER_SCALARS[" ".join(w for w in p.split()[:-1] if w != "const")]      # the last word is the parameter's name
+
+    found = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s*]+)(rt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in found, name
+        ret = re.sub(r"\s*\*", " *", " ".join(ret.split()))
+        params = params.strip()
+        found[name] = (_HEADER_RETURNS[ret], [] if params in ("", "void") else [param(p) for p in params.split(",")])
+    return found
+
+
 def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "rt_mi355x.h")).read()
-    declared = set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"rt_status"}
-    assert declared == set(capi.SYMBOLS), declared ^ set(capi.SYMBOLS)
+    """capi.SIGNATURES against the header: the same functions, and for each the same number of parameters, the same ctypes class
+    for every parameter and the same return type; lib() has resolved every one and given it that signature"""
+    declared = _header_signatures()
+    names = set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "rt_mi355x.h")).read())) - {"rt_status"}
+    assert set(declared) == names, set(declared) ^ names              # the declaration parser missed nothing the old name scan saw
+    assert len(declared) >= 138
+    assert set(declared) == set(capi.SIGNATURES) == set(capi.SYMBOLS), set(declared) ^ set(capi.SIGNATURES)
     lib = capi.lib()
-    for name in declared:
-        assert getattr(lib, name)
+    for name, (ret, params) in declared.items():
+        t_ret, t_params = capi.SIGNATURES[name]
+        assert len(t_params) == len(params), (name, len(t_params), len(params))
+        for i, (have, want) in enumerate(zip(t_params, params)):
+            assert have is want, (name, i, have, want)
+        assert t_ret is ret, (name, t_ret, ret)
+        fn = getattr(lib, name)
+        assert fn.restype is ret and list(fn.argtypes) == params, name
     assert lib.rt_abi_version() == 4
 
 
