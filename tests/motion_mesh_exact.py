@@ -6,9 +6,9 @@ import math
 import numpy as np
 
 from tests.test_motion import from_object, ref_motion, to_object
-from tests.test_temporal import BIG, cam_setup
+from tests.stage_support import BIG, F
+from tests.test_temporal import cam_setup
 
-F = np.float32
 BIAS_FIN = 1e-3                         # tri_hit_fin accepts t > 0.001
 EDGE_PX = 0.01                          # a pixel is left out when a ray 0.01 px beside its centre decides otherwise (see near_decision)
 GATE_MARGIN = 1e-4                      # ... or when | |t - z| / z - depth_tol | is below this

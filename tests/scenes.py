@@ -5,8 +5,8 @@ import numpy as np
 
 from oracle import orc
 from raytracing_folder_amd import capi, workloads
+from tests.stage_support import ROOT, build_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 CORNELL = workloads.CORNELL_XML
 
@@ -60,23 +60,11 @@ def rebuild(export, materials=None, lights=None):
 def build_shim_driver(tmp_path):
     """g++ build of tests/shim_driver.cpp (the reference's BeginRender / StopRender / saveImage contract in
     C++, on top of the product library); returns the executable's path"""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "shim_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
+    return build_driver(tmp_path, "shim_driver")
 
 
 def build_dist_driver(tmp_path):
     """g++ build of tests/dist_driver.cpp: the C++ multi-GPU host (rt_render_tiles_packed_device -> ncclAllGather ->
     rt_tiles_unpack_device) against the C ABI header and /opt/rocm/include/rccl; returns the executable's path"""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "dist_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "dist_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib,
-                    "-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
+    return build_driver(tmp_path, "dist_driver", ("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lrccl", "-lamdhip64",
+                                                  "-Wl,-rpath,/opt/rocm/lib"))

@@ -8,26 +8,9 @@
 // writes <prefix>_bloom1.pfm, <prefix>_bloom2.pfm (SaveBloomedImage) and <prefix>_rgb1.bin, <prefix>_rgb2.bin (the Color24 bytes
 // of the display image as they are in memory).
 // Renders with the P13 model, adaptive 4 -> 8, no photon pass, seeds 11 and 12; bloom with threshold 0.5 and intensity 0.5.
-#include <cstdio>
 #include <cstdlib>
-#include <string>
 
-#include "../raytracing_folder_amd/csrc/host/rt_shim.h"
-
-static bool render(rt::Renderer &r)
-{
-    if (!r.BeginRender()) { fprintf(stderr, "BeginRender failed: %s\n", r.LastError().c_str()); return false; }
-    if (!r.WaitRender()) { fprintf(stderr, "render failed: %s\n", r.LastError().c_str()); return false; }
-    return true;
-}
-
-static bool dump(const std::string &name, const uint8_t *p, size_t n)
-{
-    FILE *f = fopen(name.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = fwrite(p, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
+#include "shim_driver_util.h"
 
 int main(int argc, char **argv)
 {

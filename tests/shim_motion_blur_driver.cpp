@@ -9,18 +9,9 @@
 // writes <prefix>_mb1.pfm, <prefix>_mb2.pfm (SaveMotionBlurredImage after each frame) and <prefix>_acc2.pfm (the plane the second
 // was made from).
 // Renders with the P13 model, adaptive 4 -> 8, no photon pass, seeds 11 and 12; motion blur with shutter 1 and max_blur 8.
-#include <cstdio>
 #include <cstdlib>
-#include <string>
 
-#include "../raytracing_folder_amd/csrc/host/rt_shim.h"
-
-static bool render(rt::Renderer &r)
-{
-    if (!r.BeginRender()) { fprintf(stderr, "BeginRender failed: %s\n", r.LastError().c_str()); return false; }
-    if (!r.WaitRender()) { fprintf(stderr, "render failed: %s\n", r.LastError().c_str()); return false; }
-    return true;
-}
+#include "shim_driver_util.h"
 
 int main(int argc, char **argv)
 {

@@ -8,18 +8,9 @@
 // writes <prefix>_mv1.pfm, <prefix>_mv2.pfm (the motion plane of each frame), <prefix>_acc2.pfm and <prefix>_len2.pfm (the
 // accumulated colour and the one-channel history length after the second).
 // Renders with the P13 model, adaptive 4 -> 8, no photon pass, seeds 11 and 12.
-#include <cstdio>
 #include <cstdlib>
-#include <string>
 
-#include "../raytracing_folder_amd/csrc/host/rt_shim.h"
-
-static bool render(rt::Renderer &r)
-{
-    if (!r.BeginRender()) { fprintf(stderr, "BeginRender failed: %s\n", r.LastError().c_str()); return false; }
-    if (!r.WaitRender()) { fprintf(stderr, "render failed: %s\n", r.LastError().c_str()); return false; }
-    return true;
-}
+#include "shim_driver_util.h"
 
 int main(int argc, char **argv)
 {

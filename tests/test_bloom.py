@@ -32,10 +32,8 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import F, ROOT, U, assert_driver_usage, build_driver, gi_params as _gi_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-U = 2.0 ** -24
 DEFAULTS = dict(threshold=1.0, knee=0.5, intensity=0.25, spread=0.7, levels=6, exposure_ev=0.0)
 CSRC = os.path.join(ROOT, "raytracing_folder_amd", "csrc")
 TAIL_LIB = os.path.join(ROOT, "raytracing_folder_amd", "lib", "variants", "librt_bloom_tail.so")      # `make -C csrc bloom_tail`
@@ -283,19 +281,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert err.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_bloom_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_bloom_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_bloom_driver"))
 
 
 def test_frame_holds_what_the_tests_rely_on():
@@ -527,11 +514,6 @@ def test_the_build_with_the_tail_kernel_agrees(tmp_path):
     assert worst <= 1.0
 
 
-def _gi_params(seed):
-    return capi.default_params(min_sample=4, max_sample=8, threshold=1e30, seed=seed, shade_model=capi.SHADE_P12, bounce=8, hemisphere_sample=1,
-                               photon_count=0)
-
-
 @pytest.mark.gpu
 def test_render_denoised_and_render_temporal_with_a_bloom():
     """cornell_gi.xml, live GI, 96 x 72, 4 spp, reproducible mode"""
@@ -572,7 +554,7 @@ def test_render_denoised_and_render_temporal_with_a_bloom():
 
 @pytest.mark.gpu
 def test_cpp_shim_bloom_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_bloom_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

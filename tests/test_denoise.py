@@ -4,7 +4,6 @@ rt::RenderImage::Denoise).  The reference has no denoiser, so the yardstick is `
 transcription of the definition in include/rt_mi355x.h ("denoising"), itself checked on the CPU.  The GPU is held to the
 project's colour gate against it, |got - want| <= 2e-5 |want| + 1e-6 on every valid pixel."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,9 +11,8 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import BIG, assert_driver_usage, assert_rgb8_encodes as _assert_rgb8_encodes, build_driver, valid as _valid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIG = np.float32(1e30)
 H1 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
 
 
@@ -76,10 +74,6 @@ def synthetic(w, h, seed=0, noise=0.3):
     lin = (clean * (1 + noise * rng.normal(0, 1, (h, w, 3)))).astype(np.float32)
     lin[:ih, :iw] = (0.25, 0.5, 0.75)                           # the background
     return dict(linear=lin, normal=normal, albedo=albedo, z=z, object_id=ids), clean
-
-
-def _valid(pl, with_ids=True):
-    return pl["object_id"] >= 0 if with_ids else pl["z"] < BIG
 
 
 def _gate(got, want, valid, what=""):
@@ -154,19 +148,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert calls(capi.denoise_params(), capi.DenoisePlanes(**full)) == (-3, -3)
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_denoise_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_denoise_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_denoise_driver"))
 
 
 # ---- CPU: the reference itself --------------------------------------------------------------------------------
@@ -305,21 +288,6 @@ def test_determinism_aliasing_and_the_device_entry(planes):
     assert t["linear"].cpu().numpy().tobytes() == pl["linear"].tobytes()        # an input that is not the output is left alone
 
 
-def _encode(lin, gamma):
-    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte), as tests/test_linear_output.py has it"""
-    with np.errstate(all="ignore"):
-        g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
-        s = (g * np.float32(255)).astype(np.float32)
-    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
-    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
-
-
-def _assert_rgb8_encodes(lin, rgb, gamma):
-    d = np.abs(_encode(lin, gamma).astype(int) - rgb.astype(int))
-    assert (d == 0).mean() >= 0.999, (d != 0).sum()             # a host powf one ulp off the device's moves a byte at a boundary
-    assert d.max() <= 1
-
-
 @pytest.mark.gpu
 def test_rgb8_is_k_resolves_rule_applied_to_the_denoised_plane(planes):
     pl, _, _ = planes
@@ -360,7 +328,7 @@ def test_denoising_a_real_4spp_render_brings_it_closer_to_64spp():
 
 @pytest.mark.gpu
 def test_cpp_shim_denoise_equals_capi_denoise_of_the_same_planes(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_denoise_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

@@ -32,7 +32,6 @@ against a lens render: a second lens render 0.0381 (e_noise), the pinhole render
 below).  The asserted bound is halfway between the measured ratio and 1."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
@@ -40,10 +39,8 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import F, U, assert_driver_usage, build_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-U = 2.0 ** -24
 DEFAULTS = dict(max_coc=16, samples=32, depth_extent=0.05, aperture_scale=1.0, focus=0.0)
 JITTER = (0, 2, 3, 1)
 FAR = F(1e30)
@@ -367,19 +364,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert err.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_dof_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_dof_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_dof_driver"))
 
 
 def test_frames_hold_what_the_tests_rely_on():
@@ -638,7 +624,7 @@ def test_render_chain_with_a_depth_of_field():
 
 @pytest.mark.gpu
 def test_cpp_shim_defocused_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_dof_driver")
     prefix = str(tmp_path / "f")
     w, h, K = 64, 48, 8
     r = subprocess.run([exe, scenes.CORNELL, prefix, str(w), str(h), str(LENS_FOCUS), str(LENS_DOF), str(K)], capture_output=True, text=True, timeout=300)

@@ -15,9 +15,8 @@ import pytest
 from oracle import orc
 from raytracing_folder_amd import capi, photons
 from tests import scenes
+from tests.stage_support import BIG, ROOT, assert_driver_usage, build_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIG = np.float32(1e30)
 PAD = dict(min_sample=4, max_sample=8, threshold=1e-3)          # adaptive 4 -> 8 (the variance gate)
 BG = (0.25, 0.5, 0.75)
 FEATURES = ("normal", "albedo", "alpha", "object_id")
@@ -119,19 +118,8 @@ def test_pf_reader_refuses_bad_files_and_each_reader_refuses_the_other_kind(tmp_
     assert L.rt_image_write_pfm1(str(tmp_path / "x.pfm").encode(), capi._p(out), 2, 0) == -1
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_features_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_features_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_features_driver"))
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------
@@ -450,7 +438,7 @@ def test_a_subset_of_planes_gives_the_same_bytes(cornell):
 @pytest.mark.gpu
 def test_cpp_shim_enable_features_saves_the_planes_of_the_same_frame(cornell, tmp_path):
     s, cam, p, ref = cornell
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_features_driver")
     prefix = str(tmp_path / "feat")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48", "70", *[repr(c) for c in BG], str(p.min_sample), str(p.max_sample),
                         repr(float(np.float32(p.threshold)))], capture_output=True, text=True, timeout=300)

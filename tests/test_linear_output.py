@@ -3,7 +3,6 @@ records of the multi-GPU exchange, rt::RenderImage's EnableLinear(), and PFM fil
 k_resolve computes before powf(c, 1/gamma), so it is checked against the oracle's per-sample colours in float, against
 the RGB8 plane it is gamma-encoded into, and (reproducible mode) byte for byte across entry points."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,9 +11,8 @@ import pytest
 from oracle import orc
 from raytracing_folder_amd import capi, photons
 from tests import scenes
+from tests.stage_support import BIG, assert_rgb8_encodes as _assert_consistent_with_rgb8, build_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIG = np.float32(1e30)
 PAD = dict(min_sample=4, max_sample=8, threshold=1e-3)          # adaptive 4 -> 8 (the variance gate)
 BG = (0.25, 0.5, 0.75)                                          # a background that shows in the linear plane
 
@@ -165,21 +163,6 @@ def _check_against_oracle(s, cam, p, lin, cnt, z, bal=None, n_pick=160, seed=0):
         assert (lin[y, x] == np.asarray(BG, np.float32)).all(), (x, y, lin[y, x])
         assert _expected_linear(osc, ocam, op, x, y, 0)[0] is None
     return np.array(rels), np.array(tight), len(second)
-
-
-def _encode(lin, gamma):
-    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte)"""
-    g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
-    s = (g * np.float32(255)).astype(np.float32)
-    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
-    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
-
-
-def _assert_consistent_with_rgb8(lin, rgb, gamma):
-    enc = _encode(lin, gamma)
-    d = np.abs(enc.astype(int) - rgb.astype(int))
-    assert (d == 0).mean() >= 0.999, (d != 0).sum()
-    assert d.max() <= 1
 
 
 def _scene(w, h, bal=None):
@@ -349,11 +332,7 @@ def test_pixels_of_tiles_not_rendered_keep_the_callers_linear_values(repro):
 
 @pytest.mark.gpu
 def test_cpp_shim_enable_linear_writes_a_pfm_consistent_with_its_png(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_linear_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_linear_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
+    exe = build_driver(tmp_path, "shim_linear_driver")
     png, pfm = str(tmp_path / "img.png"), str(tmp_path / "lin.pfm")
     r = subprocess.run([exe, scenes.CORNELL, png, pfm, "photons=20000"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

@@ -7,7 +7,6 @@ properties that do not depend on the transcription.  The input is test_temporal'
 by a node transform: `frame_nodes`."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
@@ -15,10 +14,11 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
-from tests.test_temporal import (BG, BIG, F, MARGIN, MAX_LEFT_OUT, SIZES, SQUARE_HALF, SQUARE_NORMAL, SQUARE_Z, WALL_EDGE, _gate, _planes_for, _valid,
+from tests.stage_support import (BIG, F, SPHERE_CHILD, SPHERE_STEP, assert_driver_usage, build_driver, move_sphere as _move_sphere,
+                                 sphere_params as _sphere_params, valid as _valid)
+from tests.test_temporal import (BG, MARGIN, MAX_LEFT_OUT, SIZES, SQUARE_HALF, SQUARE_NORMAL, SQUARE_Z, WALL_EDGE, _gate, _planes_for,
                                  cam_a, cam_b, cam_c, cam_setup, delta_px, frame, light_affine, light_smooth, make_cam, pixel_rays, ref_temporal)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WALL, SQUARE, PARENT = 3, 4, 2          # node indices = the ids of test_temporal's frame; PARENT: the square's parent in the chain case
 
 
@@ -326,19 +326,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert e.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_motion_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_motion_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_motion_driver"))
 
 
 # ---- CPU: the references --------------------------------------------------------------------------------------
@@ -845,23 +834,6 @@ def test_calls_on_two_streams_with_a_changing_node_table_do_not_disturb_each_oth
 
 
 # ---- GPU: a real scene ----------------------------------------------------------------------------------------------
-def _sphere_params(seed):
-    return capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=seed)
-
-
-SPHERE_CHILD, SPHERE_STEP = 2, (2.0, 0.0, 0.5)      # cornell.xml: the root's third child is sphere1
-
-
-def _move_sphere(s):
-    """sphere1 of cornell.xml translated by SPHERE_STEP: (its node index, the node arrays before and after)"""
-    before = s.get_nodes()
-    idx = [i for i in range(len(before)) if before[i]["obj_type"] == capi.OBJ_SPHERE and before[i]["parent"] == 0][0]
-    after = before.copy()
-    after[idx]["pos"] = (after[idx]["pos"] + F(SPHERE_STEP)).astype(np.float32)
-    s.set_nodes(after)
-    return idx, before, after
-
-
 @pytest.mark.gpu
 def test_render_temporal_moving_follows_a_moved_sphere():
     w, h = 37, 23
@@ -916,7 +888,7 @@ def test_render_temporal_moving_follows_a_moved_sphere():
 
 @pytest.mark.gpu
 def test_cpp_shim_moving_accumulation_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_motion_driver")
     prefix = str(tmp_path / "f")
     w, h = 37, 23
     r = subprocess.run([exe, scenes.CORNELL, prefix, str(w), str(h), str(SPHERE_CHILD)] + [str(v) for v in SPHERE_STEP], capture_output=True, text=True, timeout=300)

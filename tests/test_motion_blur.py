@@ -25,7 +25,6 @@ normalised average, out = S / W with S = sum w_k c_k, so an ABSOLUTE error dw_k 
   closed bound is 2 N + 8 + 2 N K (620 K + 420), which is of no use as a gate at K = 32; hence the count per pixel."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
@@ -33,10 +32,9 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import (F, SPHERE_CHILD, SPHERE_STEP, U, assert_driver_usage, build_driver, move_sphere as _move_sphere,
+                                 sphere_params as _sphere_params)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-U = 2.0 ** -24
 DEFAULTS = dict(shutter=0.5, max_blur=16, samples=15, depth_extent=0.05)
 JITTER = (0, 2, 3, 1)
 FAR = F(1e30)
@@ -348,19 +346,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert err.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_motion_blur_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_motion_blur_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_motion_blur_driver"))
 
 
 def test_frames_hold_what_the_tests_rely_on():
@@ -519,22 +506,6 @@ def test_argument_checks_with_an_object():
         assert L.rt_motion_blur_device(mb._h, None, C.byref(p), C.byref(capi.MotionBlurPlanes(**dict(good, out_tiles=None))), 1) == 0
 
 
-def _sphere_params(seed):
-    return capi.default_params(shade_model=capi.SHADE_P13, bounce=6, photon_count=0, min_sample=4, max_sample=8, threshold=1e-3, seed=seed)
-
-
-SPHERE_CHILD, SPHERE_STEP = 2, (2.0, 0.0, 0.5)      # cornell.xml: the root's third child is sphere1 (as tests/test_motion.py moves it)
-
-
-def _move_sphere(s):
-    before = s.get_nodes()
-    idx = [i for i in range(len(before)) if before[i]["obj_type"] == capi.OBJ_SPHERE and before[i]["parent"] == 0][0]
-    after = before.copy()
-    after[idx]["pos"] = (after[idx]["pos"] + F(SPHERE_STEP)).astype(np.float32)
-    s.set_nodes(after)
-    return idx
-
-
 @pytest.mark.gpu
 def test_render_temporal_with_a_motion_blur():
     """cornell.xml at 96 x 72 with sphere1 moved between two frames, reproducible mode"""
@@ -554,7 +525,7 @@ def test_render_temporal_with_a_motion_blur():
             if isinstance(v, np.ndarray):
                 assert one[k].tobytes() == v.tobytes(), k
         assert one["motion_blurred"].tobytes() == one["denoised"].tobytes()     # nothing has moved yet
-        idx = _move_sphere(s)
+        idx = _move_sphere(s)[0]
         two = s.render_temporal(hst, cam, _sphere_params(12), moving=True, motion_blur=mb, motion_blur_kw=kw, bloom=bl, exposure=exp)
         plain = s.render_temporal(hst_plain, cam, _sphere_params(12), moving=True)
         assert set(two) == set(plain) | {"motion_blurred", "bloomed", "display_rgb"}
@@ -582,7 +553,7 @@ def test_render_temporal_with_a_motion_blur():
 
 @pytest.mark.gpu
 def test_cpp_shim_motion_blur_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_motion_blur_driver")
     prefix = str(tmp_path / "f")
     w, h = 64, 48
     r = subprocess.run([exe, scenes.CORNELL, prefix, str(w), str(h), str(SPHERE_CHILD)] + [str(v) for v in SPHERE_STEP], capture_output=True,

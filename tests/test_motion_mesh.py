@@ -13,9 +13,9 @@ from raytracing_folder_amd import capi, workloads
 from tests import deep_meshes, scenes
 from tests import motion_mesh_exact as mx
 from tests.test_motion import make_nodes, ref_motion, rot_z, set_node
-from tests.test_temporal import BIG, MAX_LEFT_OUT, make_cam
+from tests.stage_support import BIG, F
+from tests.test_temporal import MAX_LEFT_OUT, make_cam
 
-F = np.float32
 MESH = 1                                # the mesh's node in every scene here
 SIZES = ((37, 23), (64, 48))
 EXTENT = 16.0                           # a sheet of this extent at z = 0 overfills the frustum of the cameras below (fov 40 from z = 10)

@@ -6,7 +6,6 @@ on the transcription (a repeated camera, the closed form of the blend weights, a
 is `frame`: an analytic scene -- a wall, a square in front of it, a strip where nothing is hit -- seen through any rt_camera."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
@@ -14,10 +13,8 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import BIG, F, assert_driver_usage, build_driver, gi_params as _gi_params, valid as _valid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIG = np.float32(1e30)
-F = np.float32
 BG = (0.25, 0.5, 0.75)
 MARGIN = 1e-3                   # a pixel closer than this to a decision of the definition is left out of GPU comparisons ...
 MAX_LEFT_OUT = 0.02             # ... and at most this share of a frame's valid pixels may be
@@ -227,10 +224,6 @@ def _planes_for(pl, with_ids, with_var):
     return dict(object_id=pl["object_id"] if with_ids else None, variance=pl["variance"] if with_var else None)
 
 
-def _valid(pl, with_ids=True):
-    return pl["object_id"] >= 0 if with_ids else pl["z"] < BIG
-
-
 def _sequence(cams, noise, with_ids=True, with_var=True, light=light_smooth, dtype=np.float32, seed=100, **params):
     """the reference over a sequence of cameras with fresh noise per frame: [(cam, planes, clean, result)]"""
     hist, out = {}, []
@@ -320,19 +313,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert e.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_temporal_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_temporal_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_temporal_driver"))
 
 
 # ---- CPU: the reference and the synthetic frame -----------------------------------------------------------------
@@ -656,13 +638,6 @@ def test_determinism_aliasing_entry_points_two_histories_and_reset():
 
 
 # ---- GPU: real frames -------------------------------------------------------------------------------------------
-def _gi_params(seed, spp=4):
-    common = dict(shade_model=capi.SHADE_P12, bounce=8, hemisphere_sample=1, photon_count=0)
-    if spp == 4:
-        return capi.default_params(min_sample=4, max_sample=8, threshold=1e30, seed=seed, **common)
-    return capi.default_params(min_sample=spp, max_sample=spp, threshold=-1.0, seed=seed, **common)
-
-
 @pytest.mark.gpu
 def test_eight_accumulated_4spp_frames_come_closer_to_64spp():
     """cornell_gi.xml (live GI) at 96 x 72, reproducible mode: eight 4 spp frames, seeds 1..8, fixed camera, accumulated; the
@@ -707,7 +682,7 @@ def test_eight_accumulated_4spp_frames_come_closer_to_64spp():
 
 @pytest.mark.gpu
 def test_cpp_shim_accumulation_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_temporal_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

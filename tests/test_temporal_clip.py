@@ -5,7 +5,6 @@ of tests/test_temporal.py's `ref_temporal`, whose tap logic it reuses.  The fram
 that switches in mid-sequence: the geometry tests of the plain accumulation all pass there, and only the rectification reacts."""
 import ctypes as C
 import functools
-import os
 import subprocess
 
 import numpy as np
@@ -13,10 +12,10 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
-from tests.test_temporal import (BIG, F, MAX_LEFT_OUT, PAIRS, _gate, _gi_params, _planes_for, _valid, cam_a, cam_b, cam_c, cam_setup,
+from tests.stage_support import BIG, F, assert_driver_usage, build_driver, gi_params as _gi_params, valid as _valid
+from tests.test_temporal import (MAX_LEFT_OUT, PAIRS, _gate, _planes_for, cam_a, cam_b, cam_c, cam_setup,
                                  delta_px, frame, light_smooth, pixel_rays, ref_temporal)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEAR = 1e-4                     # d_h closer than NEAR (|bound| + s) to lo or hi: the CLIPPED decision may flip on the GPU
 NOISE = 0.3
 SWITCH_AT = 2                   # the GPU sequences hold three frames: two under light_smooth, the third under light_dim
@@ -185,19 +184,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert st == -1 and b"history is NULL" in L.rt_last_error()
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_temporal_clip_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_temporal_clip_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_temporal_clip_driver"))
 
 
 # ---- CPU: the reference -----------------------------------------------------------------------------------------
@@ -499,7 +487,7 @@ def test_rectification_follows_a_moved_light_and_keeps_the_static_gain():
 
 @pytest.mark.gpu
 def test_cpp_shim_rectified_accumulation_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_temporal_clip_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

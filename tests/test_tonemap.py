@@ -15,10 +15,8 @@ import pytest
 
 from raytracing_folder_amd import capi
 from tests import scenes
+from tests.stage_support import F, U, assert_driver_usage, assert_rgb8_encodes as _assert_rgb8_encodes, build_driver, gi_params as _gi_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-U = 2.0 ** -24                  # the relative error of one rounding to float
 DEFAULTS = dict(key=0.18, ev_bias=0.0, ev_min=-16.0, ev_max=16.0, p_low=0.10, p_high=0.90, adapt_up=1.0, adapt_down=1.0, white=4.0, gamma=2.2,
                 auto_exposure=1)
 # log2_exposure against the transcription.  The histogram is exact and Lbar is the same IEEE double division and subtraction on
@@ -157,21 +155,6 @@ def _display_gate(got, want, operator):
     assert (got[~fin & ~np.isnan(want)] == want[~fin & ~np.isnan(want)]).all()
     gate = GATE_C[operator] * U * np.abs(want[fin]) + 1e-7
     return float((np.abs(got[fin] - want[fin]) / gate).max()) if fin.any() else 0.0
-
-
-def _encode(lin, gamma):
-    """host-side powf(linear, (float)(1.0/gamma)) and Color24 (float_to_byte), as tests/test_linear_output.py has it"""
-    with np.errstate(all="ignore"):
-        g = np.power(lin.astype(np.float32), np.float32(1.0 / gamma))
-        s = (g * np.float32(255)).astype(np.float32)
-    s = np.nan_to_num(s, nan=0.0, posinf=255.0, neginf=0.0)
-    return np.clip(np.trunc(s), 0, 255).astype(np.uint8)
-
-
-def _assert_rgb8_encodes(lin, rgb, gamma=2.2):
-    d = np.abs(_encode(lin, gamma).astype(int) - rgb.astype(int))
-    assert (d == 0).mean() >= 0.999, (d != 0).sum()             # a host powf one ulp off the device's moves a byte at a boundary
-    assert d.max() <= 1
 
 
 # ---- the synthetic frames -------------------------------------------------------------------------------------------
@@ -315,19 +298,8 @@ def test_argument_checks_come_before_any_gpu_call():
         assert err.value.status == -3
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_tonemap_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_tonemap_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_tonemap_driver"))
 
 
 def test_frame_holds_what_the_tests_rely_on():
@@ -624,11 +596,6 @@ def test_determinism_entry_points_aliasing_and_two_states():
 
 
 # ---- GPU: real frames -------------------------------------------------------------------------------------------
-def _gi_params(seed):
-    return capi.default_params(min_sample=4, max_sample=8, threshold=1e30, seed=seed, shade_model=capi.SHADE_P12, bounce=8, hemisphere_sample=1,
-                               photon_count=0)
-
-
 @pytest.mark.gpu
 def test_render_denoised_and_render_temporal_with_an_exposure():
     """cornell_gi.xml, live GI, 96 x 72, 4 spp, reproducible mode"""
@@ -676,7 +643,7 @@ def test_render_denoised_and_render_temporal_with_an_exposure():
 
 @pytest.mark.gpu
 def test_cpp_shim_tonemap_equals_the_capi_one(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_tonemap_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

@@ -6,7 +6,6 @@ derived from the per-sample colour gate, and byte for byte across chunkings, til
 the filter against `ref_denoise_var` below, a float64 numpy transcription of the header's definition ("variance-guided
 denoising"), itself checked on the CPU."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -15,9 +14,8 @@ import pytest
 from oracle import orc
 from raytracing_folder_amd import capi, photons
 from tests import scenes
+from tests.stage_support import BIG, assert_driver_usage, build_driver, valid as _valid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIG = np.float32(1e30)
 H1 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
 G1 = (1 / 4, 1 / 2, 1 / 4)
 FLOOR = float(np.float32(1e-10))
@@ -104,10 +102,6 @@ def synthetic(w, h, seed=0, noise=0.3):
     lin[:ih, :iw] = (0.25, 0.5, 0.75)                           # the background
     var = ((noise * clean) ** 2).astype(np.float32)
     return dict(linear=lin, normal=normal, albedo=albedo, z=z, object_id=ids, variance=var), clean
-
-
-def _valid(pl, with_ids=True):
-    return pl["object_id"] >= 0 if with_ids else pl["z"] < BIG
 
 
 def _gate(got, want, valid, what, floor):
@@ -203,19 +197,8 @@ def test_denoise_var_argument_checks_come_before_any_gpu_call():
         assert calls(capi.denoise_var(ptr, ptr)) == (-3, -3) and calls(capi.denoise_var(ptr)) == (-3, -3)
 
 
-def _build_shim_driver(tmp_path):
-    exe = os.path.join(str(tmp_path), "shim_variance_driver")
-    lib = os.path.join(ROOT, "raytracing_folder_amd", "lib")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "shim_variance_driver.cpp"), "-L" + lib, "-lrt_mi355x", "-Wl,-rpath," + lib, "-lpthread"],
-                   check=True, capture_output=True)
-    return exe
-
-
 def test_shim_driver_builds_against_the_header(tmp_path):
-    exe = _build_shim_driver(tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert_driver_usage(build_driver(tmp_path, "shim_variance_driver"))
 
 
 # ---- CPU: the reference itself --------------------------------------------------------------------------------
@@ -610,7 +593,7 @@ def test_guided_denoise_of_a_real_4spp_render_brings_it_closer_to_64spp():
 
 @pytest.mark.gpu
 def test_cpp_shim_variance_and_guided_denoise_equal_the_capi_ones(tmp_path):
-    exe = _build_shim_driver(tmp_path)
+    exe = build_driver(tmp_path, "shim_variance_driver")
     prefix = str(tmp_path / "f")
     r = subprocess.run([exe, scenes.CORNELL, prefix, "64", "48"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout, r.stderr)

@@ -14,19 +14,9 @@
   every kernel's own duration -- "kernel_trace_us": per kernel the median over its full-frame dispatches and their number per call.
 usage: python tools_bloom_timing.py [--calls 200] [--libs a=path,b=path] [--trace-calls 50] [--out profiles/bloom_timing.json]"""
 import argparse
-import json
-import os
-import shutil
-import sqlite3
 import statistics
-import subprocess
-import sys
-import tempfile
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, kernel_durations_us, kernel_trace_db, per_library, repo_on_path, spread
 
 
 def pyramid_bytes(w, h, levels):
@@ -42,7 +32,7 @@ def pyramid_bytes(w, h, levels):
 
 
 def measure(a):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import torch
     from raytracing_folder_amd import capi, workloads
     if capi.device_count() < 1:
@@ -64,21 +54,7 @@ def measure(a):
             bloom=lambda: bl.apply_device(stream.cuda_stream, linear_ptr=lin.data_ptr(), out_ptr=dst.data_ptr(), **kw),
             in_place=lambda: bl.apply_device(stream.cuda_stream, linear_ptr=work.data_ptr(), out_ptr=work.data_ptr(), intensity=0.0, **kw),
             tiny=lambda: tiny.apply_device(stream.cuda_stream, linear_ptr=one.data_ptr(), out_ptr=one_out.data_ptr(), **kw))
-        ms = {k: [] for k in calls}
-        with torch.cuda.stream(stream):
-            for _ in range(10):
-                for c in calls.values():
-                    c()
-            stream.synchronize()
-            for _ in range(a.calls):
-                for k, c in calls.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    c()
-                    e1.record(stream)
-                    e1.synchronize()
-                    ms[k].append(e0.elapsed_time(e1))
-        res = {k: spread(v) for k, v in ms.items()}
+        res = {k: spread(v) for k, v in event_times(stream, calls, a.calls).items()}
     used, tail = capi.bloom_plan(w, h, a.levels)
     launches = (2 + tail + 1 + tail) if tail >= 0 else 2 + 2 * (used - 1)
     full, pyr = pyramid_bytes(w, h, a.levels)
@@ -97,64 +73,35 @@ def kernel_trace(a, env):
     """one child under rocprofv3 --kernel-trace: {kernel: median us over the dispatches of the full frame, dispatches per call}.
     The 1 x 1 calls are one workgroup per kernel; the full frame's prefilter and combine are told from them by their grid, and
     the 1 x 1 frame has no other kernel."""
-    tmp = tempfile.mkdtemp(prefix="bloom_trace_")
-    cmd = ["rocprofv3", "--kernel-trace", "-d", tmp, "-o", "trace", "--", sys.executable, os.path.abspath(__file__), "--calls", str(a.trace_calls),
-           "--width", str(a.width), "--height", str(a.height), "--levels", str(a.levels)]
-    try:
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        if r.returncode != 0:
-            raise SystemExit(f"kernel trace: exit {r.returncode}\n{r.stdout}\n{r.stderr}")
-        dbs = [os.path.join(d, f) for d, _, fs in os.walk(tmp) for f in fs if f.endswith(".db")]
-        if not dbs:
-            raise SystemExit("kernel trace: rocprofv3 left no database")
-        db = sqlite3.connect(dbs[0])
+    child = ["--calls", a.trace_calls, "--width", a.width, "--height", a.height, "--levels", a.levels]
+    with kernel_trace_db(__file__, child, env, prefix="bloom_trace_") as db:
         out, total = {}, 0.0
         calls = 2 * (a.trace_calls + 10) + 0.0                  # bloom and in_place, warm-up included
         for k in KERNELS:
-            full = " and grid_x > 256" if k in ("k_bloom_prefilter", "k_bloom_combine") else ""
-            t = [row[0] / 1000.0 for row in db.execute(f"select end - start from kernels where name like '%{k}%'{full} order by start")]
+            t = kernel_durations_us(db, k, " and grid_x > 256" if k in ("k_bloom_prefilter", "k_bloom_combine") else "")
             if t:
                 per_call = len(t) / calls
                 out[k] = dict(median_us=round(statistics.median(t), 2), per_call=round(per_call, 2), sum_us_per_call=round(sum(t) / calls, 2))
                 total += sum(t) / calls
         out["kernels_sum_us_per_call"] = round(total, 2)
-        db.close()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     return dict(command="rocprofv3 --kernel-trace -d DIR -o trace -- python tools_bloom_timing.py --calls %d" % a.trace_calls, **out)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap)
     ap.add_argument("--levels", type=int, default=6)
     ap.add_argument("--peak-gbs", type=float, default=8685.0, help="the streaming peak the byte floor is set against (profiles/r04_peaks.json)")
     ap.add_argument("--libs", default=None, help="name=path,...: measure each library in a child process")
     ap.add_argument("--trace-calls", type=int, default=0, help="(--libs) calls of the extra child run under rocprofv3 --kernel-trace; 0: none")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.libs:
-        res = dict(what="tools_bloom_timing.py", libraries={})
-        for item in a.libs.split(","):
-            name, path = item.split("=", 1)
-            env = dict(os.environ, RT_MI355X_LIB=os.path.abspath(path))
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--calls", str(a.calls), "--width", str(a.width), "--height", str(a.height),
-                                "--levels", str(a.levels), "--peak-gbs", str(a.peak_gbs)], env=env, capture_output=True, text=True, timeout=600)
-            if r.returncode != 0:       # a child that died says why, and nothing more is started on the device
-                raise SystemExit(f"{name}: exit {r.returncode}\n{r.stdout}\n{r.stderr}")
-            res["libraries"][name] = json.loads(r.stdout.strip().splitlines()[-1])
-            if a.trace_calls:
-                res["libraries"][name]["kernel_trace_us"] = kernel_trace(a, env)
+        child = ["--calls", a.calls, "--width", a.width, "--height", a.height, "--levels", a.levels, "--peak-gbs", a.peak_gbs]
+        trace = (lambda name, env, doc: doc.update(kernel_trace_us=kernel_trace(a, env))) if a.trace_calls else None
+        res = dict(what="tools_bloom_timing.py", libraries=per_library(__file__, a.libs, child, trace))
     else:
         res = dict(what="tools_bloom_timing.py", **measure(a))
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

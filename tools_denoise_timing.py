@@ -16,6 +16,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from raytracing_folder_amd import capi
+from tools_timing import emit, event_times
 
 
 def planes(w, h, seed=0):
@@ -61,19 +62,7 @@ def main():
                             object_id_ptr=None if a.no_ids else t["object_id"].data_ptr(),
                             rgb8_ptr=out8.data_ptr() if a.rgb8 else None, sync=False, levels=a.levels)
 
-    with torch.cuda.stream(stream):
-        for _ in range(a.warmup):
-            call()
-        stream.synchronize()
-        ms = []
-        for _ in range(a.repeat):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            call()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ms.sort()
+    ms = sorted(event_times(stream, dict(call=call), a.repeat, warmup=a.warmup)["call"])
     med = statistics.median(ms)
     level_bytes = 25 * 32 * w * h                               # requested by the taps of one level (served mostly from cache)
     unique_bytes = (32 + 16) * w * h                            # what a level must move at least: read both records once, write one
@@ -85,11 +74,7 @@ def main():
                tap_bytes_per_level=level_bytes, unique_bytes_per_level=unique_bytes,
                tap_GBps_at_median=round(a.levels * level_bytes / (med * 1e-3) / 1e9, 1),
                l1_peak_GBps=peaks.get("l1_peak_GBps"), scratch_bytes=48 * w * h)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

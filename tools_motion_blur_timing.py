@@ -13,22 +13,12 @@
   gives every kernel's own duration -- "kernel_trace_us": per kernel the median over its dispatches.
 usage: python tools_motion_blur_timing.py [--calls 200] [--trace-calls 50] [--out profiles/motion_blur_timing.json]"""
 import argparse
-import json
-import os
-import shutil
-import sqlite3
 import statistics
-import subprocess
-import sys
-import tempfile
+
+from tools_timing import add_common_args, emit, event_times, kernel_durations_us, kernel_trace_db, repo_on_path, spread
 
 FRAMES = ("static", "object", "all")
 KERNELS = ("k_mblur_tile_max", "k_mblur_neighbour_max", "k_mblur_gather")
-
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
 
 
 def make_frame(kind, w, h, K, shutter):
@@ -67,7 +57,7 @@ def gathered_fraction(motion, K, shutter):
 
 
 def measure(a):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import torch
     from raytracing_folder_amd import capi
     if capi.device_count() < 1:
@@ -86,20 +76,7 @@ def measure(a):
     with capi.MotionBlur(0, w, h) as mb:
         calls = {kind: (lambda p=p: mb.apply_device(stream.cuda_stream, linear_ptr=p[0].data_ptr(), motion_ptr=p[1].data_ptr(),
                                                       z_ptr=p[2].data_ptr(), out_ptr=p[3].data_ptr(), **kw)) for kind, p in planes.items()}
-        ms = {k: [] for k in calls}
-        with torch.cuda.stream(stream):
-            for _ in range(10):
-                for c in calls.values():
-                    c()
-            stream.synchronize()
-            for _ in range(a.calls):
-                for k, c in calls.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    c()
-                    e1.record(stream)
-                    e1.synchronize()
-                    ms[k].append(e0.elapsed_time(e1))
+        ms = event_times(stream, calls, a.calls)
     res = {}
     for kind in kinds:
         n = w * h
@@ -113,55 +90,35 @@ def measure(a):
 
 def kernel_trace(a, kind):
     """one child under rocprofv3 --kernel-trace running `kind` alone: {kernel: median us over its dispatches}"""
-    tmp = tempfile.mkdtemp(prefix="mblur_trace_")
-    cmd = ["rocprofv3", "--kernel-trace", "-d", tmp, "-o", "trace", "--", sys.executable, os.path.abspath(__file__), "--calls", str(a.trace_calls),
-           "--width", str(a.width), "--height", str(a.height), "--max-blur", str(a.max_blur), "--samples", str(a.samples),
-           "--shutter", str(a.shutter), "--frame", kind]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        if r.returncode != 0:           # a child that died says why, and nothing more is started on the device
-            raise SystemExit(f"kernel trace ({kind}): exit {r.returncode}\n{r.stdout}\n{r.stderr}")
-        dbs = [os.path.join(d, f) for d, _, fs in os.walk(tmp) for f in fs if f.endswith(".db")]
-        if not dbs:
-            raise SystemExit("kernel trace: rocprofv3 left no database")
-        db = sqlite3.connect(dbs[0])
+    child = ["--calls", a.trace_calls, "--width", a.width, "--height", a.height, "--max-blur", a.max_blur, "--samples", a.samples,
+             "--shutter", a.shutter, "--frame", kind]
+    with kernel_trace_db(__file__, child, prefix="mblur_trace_") as db:
         out, total = {}, 0.0
         for k in KERNELS:
-            t = [row[0] / 1000.0 for row in db.execute(f"select end - start from kernels where name like '%{k}%' order by start")]
+            t = kernel_durations_us(db, k)
             if t:
                 out[k] = dict(median_us=round(statistics.median(t), 2), min_us=round(min(t), 2), dispatches=len(t))
                 total += statistics.median(t)
         out["kernels_sum_us_per_call"] = round(total, 2)
-        db.close()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap)
     ap.add_argument("--max-blur", type=int, default=16)
     ap.add_argument("--samples", type=int, default=15)
     ap.add_argument("--shutter", type=float, default=0.5)
     ap.add_argument("--frame", default=None, choices=FRAMES, help="measure this frame alone (what the trace children do)")
     ap.add_argument("--peak-gbs", type=float, default=8685.0, help="the streaming peak the byte floor is set against (profiles/r04_peaks.json)")
     ap.add_argument("--trace-calls", type=int, default=0, help="calls of the extra children run under rocprofv3 --kernel-trace; 0: none")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = dict(what="tools_motion_blur_timing.py", **measure(a))
     if a.trace_calls and not a.frame:
         res["kernel_trace_command"] = "rocprofv3 --kernel-trace -d DIR -o trace -- python tools_motion_blur_timing.py --calls %d --frame FRAME" % a.trace_calls
         for kind in FRAMES:
             res["frames"][kind]["kernel_trace_us"] = kernel_trace(a, kind)
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -15,28 +15,19 @@ divided by their number -- the closer upper bound of a kernel's time (a pair aro
                         events around the upload (Scene.mesh_update_ms), inside which the previous positions travel
 usage: python tools_motion_mesh_timing.py [--calls 100] [--reps 3] [--batch 100] [--out profiles/motion_mesh_timing.json]"""
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, repo_on_path, spread
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--batch", type=int, default=100)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, calls=100)
     a = ap.parse_args()
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import numpy as np
     import torch
     from raytracing_folder_amd import capi, workloads
@@ -64,33 +55,9 @@ def main():
     mv = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
 
     def measure(kinds, call):
-        reps = []
-        with torch.cuda.stream(stream):
-            for _ in range(10):
-                for kind in kinds:
-                    call(kind)
-            stream.synchronize()
-            for _ in range(a.reps):
-                ms = {k: [] for k in kinds}
-                for _ in range(a.calls):
-                    for kind in kinds:
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(stream)
-                        call(kind)
-                        e1.record(stream)
-                        e1.synchronize()
-                        ms[kind].append(e0.elapsed_time(e1))
-                reps.append({k: spread(v) for k, v in ms.items()})
-            batch = {k: [] for k in kinds}
-            for _ in range(a.reps):
-                for kind in kinds:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    for _ in range(a.batch):
-                        call(kind)
-                    e1.record(stream)
-                    e1.synchronize()
-                    batch[kind].append(e0.elapsed_time(e1) / a.batch)
+        calls = {k: (lambda k=k: call(k)) for k in kinds}
+        reps = [{k: spread(v) for k, v in event_times(stream, calls, a.calls, warmup=0 if r else 10).items()} for r in range(a.reps)]
+        batch = {k: [t / a.batch for t in v] for k, v in event_times(stream, calls, a.reps, warmup=0, batch=a.batch).items()}
         return {k: dict(repetitions=[r[k] for r in reps], median_of_medians=round(statistics.median(r[k]["median"] for r in reps), 4),
                         batch_ms_per_call=dict(calls=a.batch, median=round(statistics.median(batch[k]), 4), min=round(min(batch[k]), 4),
                                                max=round(max(batch[k]), 4))) for k in kinds}
@@ -143,12 +110,7 @@ def main():
     res.update(measure(("k_motion_mesh_filled",), call))
     res["filled_mesh_pixels_with_a_previous_position"] = round(float((mv[..., 2][ids == mesh_node] > 0).float().mean().item()), 4)
     s.close()
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

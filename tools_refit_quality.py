@@ -14,11 +14,8 @@ Per scene:
 sums are folded by k_bvh_cost_fold on the device instead of by the host); with --skip-table such a run measures (a) and (b) only.
 usage: python tools_refit_quality.py [--calls 20] [--warmup 3] [--fold host] [--skip-table] [--out profiles/refit_quality.json]"""
 import argparse
-import json
-import os
-import sys
 
-from tools_refit_timing import spread, timed
+from tools_timing import emit, repo_on_path, spread, timed
 
 AMPLITUDES = (0.0, 0.05, 0.1, 0.2, 0.3)
 
@@ -83,19 +80,14 @@ def main():
     ap.add_argument("--skip-table", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     from raytracing_folder_amd import capi, workloads
     if capi.device_count() < 1:
         raise SystemExit("no gfx950 device: nothing is measured (there is no CPU path)")
     res = dict(what="tools_refit_quality.py", calls=a.calls, warmup=a.warmup, fold=a.fold,
                balls_102k=measure_scene(lambda: workloads.make_balls_scene(400, 300), a),
                cornell_teapot=measure_scene(lambda: workloads.load_cornell(400, 300), a))
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -11,28 +11,10 @@
                   fresh scene given the same vertices: what the refitted tree's looser topology costs the tracer
 usage: python tools_refit_timing.py [--calls 20] [--warmup 3] [--out profiles/refit_timing.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
-import time
+
+from tools_timing import emit, repo_on_path, spread, timed
 
 AMPLITUDES = (0.0, 0.05, 0.3)
-
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
-
-
-def timed(fn, calls, warmup):
-    out = []
-    for i in range(warmup + calls):
-        t0 = time.perf_counter()
-        fn(i)
-        if i >= warmup:
-            out.append((time.perf_counter() - t0) * 1e3)
-    return spread(out)
 
 
 def measure_scene(name, make, a):
@@ -85,19 +67,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     from raytracing_folder_amd import capi, workloads
     if capi.device_count() < 1:
         raise SystemExit("no gfx950 device: nothing is measured (there is no CPU path)")
     res = dict(what="tools_refit_timing.py", calls=a.calls, warmup=a.warmup,
                balls_102k=measure_scene("balls", lambda: workloads.make_balls_scene(400, 300), a),
                cornell_teapot=measure_scene("cornell", lambda: workloads.load_cornell(400, 300), a))
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -18,15 +18,8 @@ document.  The method is tools_temporal_timing.py's:
               into the document.
 usage: python tools_temporal_clip_timing.py [--calls 200] [--no-quality] [--asm-remarks FILE] [--out profiles/temporal_clip_timing.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, repo_on_path, spread
 
 
 def kernel_resources(path, only="k_temporal"):
@@ -49,14 +42,11 @@ def kernel_resources(path, only="k_temporal"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap)
     ap.add_argument("--no-quality", action="store_true")
     ap.add_argument("--asm-remarks", default=None)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import numpy as np
     import torch
     from raytracing_folder_amd import capi
@@ -113,21 +103,9 @@ def main():
                                        albedo_ptr=t["albedo"].data_ptr(), z_ptr=t["z"].data_ptr(), object_id_ptr=t["object_id"].data_ptr(),
                                        out_ptr=out.data_ptr(), history_ptr=hist.data_ptr(), sync=False, **extra)
 
-    ms = {v: [] for v in variants}
+    ms = event_times(stream, {v: (lambda v=v: call(v)) for v in variants}, a.calls)
     clipped_share = {}
     with torch.cuda.stream(stream):
-        for _ in range(10):
-            for v in variants:
-                call(v)
-        stream.synchronize()
-        for _ in range(a.calls):
-            for v in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                call(v)
-                e1.record(stream)
-                e1.synchronize()
-                ms[v].append(e0.elapsed_time(e1))
         for v in variants:
             if v[0]:
                 call(v)
@@ -148,12 +126,7 @@ def main():
     if not a.no_quality:
         q = tc.moved_light_rmse()
         res["quality_cornell_gi_96x72"] = {k: {n: round(x, 6) for n, x in v.items()} for k, v in q.items()}
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

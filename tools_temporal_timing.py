@@ -11,15 +11,8 @@
               of the scene's width) between frames.
 usage: python tools_temporal_timing.py [--calls 200] [--no-quality] [--out profiles/temporal_timing.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, repo_on_path, spread
 
 
 def quality(capi, workloads, np):
@@ -47,13 +40,10 @@ def quality(capi, workloads, np):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap)
     ap.add_argument("--no-quality", action="store_true")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import numpy as np
     import torch
     from raytracing_folder_amd import capi, workloads
@@ -98,19 +88,7 @@ def main():
                                               object_id_ptr=t["object_id"].data_ptr(), out_ptr=out.data_ptr(), history_ptr=hist.data_ptr(),
                                               sync=False, **extra)
 
-    ms = {False: [], True: []}
-    with torch.cuda.stream(stream):
-        for _ in range(10):
-            call(False), call(True)
-        stream.synchronize()
-        for _ in range(a.calls):
-            for with_var in (False, True):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                call(with_var)
-                e1.record(stream)
-                e1.synchronize()
-                ms[with_var].append(e0.elapsed_time(e1))
+    ms = event_times(stream, {False: lambda: call(False), True: lambda: call(True)}, a.calls)
     res["accumulate_ms"] = {("with_variance" if k else "without_variance"): spread(v) for k, v in ms.items()}
     res["mean_history"] = float(hist.mean().item())
     # per pixel: rgb, normal, albedo 12 each, z 4, id 4 (+ variance 12) in; linear 12, history 4 (+ variance 12) out; 48 of records
@@ -120,12 +98,7 @@ def main():
         k.close()
     if not a.no_quality:
         res["quality_cornell_gi_96x72"] = quality(capi, workloads, np)
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -18,23 +18,13 @@
   every kernel's own duration -- "kernel_trace_us" per frame, the median over the full-frame dispatches, beside the command.
 usage: python tools_tonemap_timing.py [--calls 200] [--libs a=path,b=path] [--trace-calls 50] [--out profiles/tonemap_timing.json]"""
 import argparse
-import json
-import os
 import statistics
-import shutil
-import sqlite3
-import subprocess
-import sys
-import tempfile
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, kernel_durations_us, kernel_trace_db, per_library, repo_on_path, spread
 
 
 def measure(a):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import numpy as np
     import torch
     from raytracing_folder_amd import capi, workloads
@@ -61,20 +51,7 @@ def measure(a):
                 tonemap_only=lambda: exp.tonemap_device(stream.cuda_stream, w, h, linear_ptr=tl.data_ptr(), rgb8_ptr=rgb8.data_ptr(), sync=False,
                                                         auto_exposure=0, exposure_ev=1.0),
                 fixed=lambda: exp.tonemap_device(stream.cuda_stream, 1, 1, linear_ptr=one.data_ptr(), rgb8_ptr=one8.data_ptr(), sync=False))
-            ms = {k: [] for k in calls}
-            with torch.cuda.stream(stream):
-                for _ in range(10):
-                    for c in calls.values():
-                        c()
-                stream.synchronize()
-                for _ in range(a.calls):
-                    for k, c in calls.items():
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(stream)
-                        c()
-                        e1.record(stream)
-                        e1.synchronize()
-                        ms[k].append(e0.elapsed_time(e1))
+            ms = event_times(stream, calls, a.calls)
             exp.tonemap_device(stream.cuda_stream, w, h, linear_ptr=tl.data_ptr(), object_id_ptr=ti.data_ptr(), rgb8_ptr=rgb8.data_ptr())
             r = {k: spread(v) for k, v in ms.items()}
             r["hist_and_meter_derived_ms"] = round(r["all"]["median"] - r["tonemap_only"]["median"], 4)
@@ -92,58 +69,28 @@ def kernel_trace(a, env):
     measured one after the other (cornell, constant) with the same number of dispatches, so the dispatches of a kernel on the
     full frame, in start order, fall into halves; the 1 x 1 calls (one workgroup) are left out except for the meter, which is
     always one workgroup."""
-    tmp = tempfile.mkdtemp(prefix="tonemap_trace_")
-    cmd = ["rocprofv3", "--kernel-trace", "-d", tmp, "-o", "trace", "--", sys.executable, os.path.abspath(__file__), "--calls", str(a.trace_calls),
-           "--width", str(a.width), "--height", str(a.height)]
-    try:
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        if r.returncode != 0:
-            raise SystemExit(f"kernel trace: exit {r.returncode}\n{r.stdout}\n{r.stderr}")
-        dbs = [os.path.join(d, f) for d, _, fs in os.walk(tmp) for f in fs if f.endswith(".db")]
-        if not dbs:
-            raise SystemExit("kernel trace: rocprofv3 left no database")
-        db = sqlite3.connect(dbs[0])
+    with kernel_trace_db(__file__, ["--calls", a.trace_calls, "--width", a.width, "--height", a.height], env, prefix="tonemap_trace_") as db:
         out = {"cornell": {}, "constant": {}}
         for k in KERNELS:
-            full = "" if k == "k_exposure_meter" else " and grid_x > 256"
-            t = [row[0] / 1000.0 for row in db.execute(f"select end - start from kernels where name like '%{k}%'{full} order by start")]
+            t = kernel_durations_us(db, k, "" if k == "k_exposure_meter" else " and grid_x > 256")
             half = len(t) // 2
             out["cornell"][k], out["constant"][k] = round(statistics.median(t[:half]), 2), round(statistics.median(t[half:]), 2)
-        db.close()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     return dict(command="rocprofv3 --kernel-trace -d DIR -o trace -- python tools_tonemap_timing.py --calls %d" % a.trace_calls, **out)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap)
     ap.add_argument("--libs", default=None, help="name=path,...: measure each library in a child process")
     ap.add_argument("--trace-calls", type=int, default=0, help="(--libs) calls of the extra child run under rocprofv3 --kernel-trace; 0: none")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.libs:
-        res = dict(what="tools_tonemap_timing.py", libraries={})
-        for item in a.libs.split(","):
-            name, path = item.split("=", 1)
-            env = dict(os.environ, RT_MI355X_LIB=os.path.abspath(path))
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--calls", str(a.calls), "--width", str(a.width), "--height", str(a.height)],
-                               env=env, capture_output=True, text=True, timeout=600)
-            if r.returncode != 0:       # a child that died says why, and nothing more is started on the device
-                raise SystemExit(f"{name}: exit {r.returncode}\n{r.stdout}\n{r.stderr}")
-            res["libraries"][name] = json.loads(r.stdout.strip().splitlines()[-1])
-            if a.trace_calls:
-                res["libraries"][name]["kernel_trace_us"] = kernel_trace(a, env)
+        trace = (lambda name, env, doc: doc.update(kernel_trace_us=kernel_trace(a, env))) if a.trace_calls else None
+        res = dict(what="tools_tonemap_timing.py",
+                   libraries=per_library(__file__, a.libs, ["--calls", a.calls, "--width", a.width, "--height", a.height], trace))
     else:
         res = dict(what="tools_tonemap_timing.py", **measure(a))
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

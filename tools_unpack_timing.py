@@ -13,18 +13,11 @@
   linear_parent's byte for byte before anything is timed.
 usage: python tools_unpack_timing.py [--reps 50] [--batch 20] [--out profiles/unpack_planes_timing.json]"""
 import argparse
-import json
-import os
-import statistics
-import sys
+
+from tools_timing import add_common_args, emit, event_times, repo_on_path, spread
 
 ALL = ("linear", "normal", "albedo", "alpha", "object_id", "variance")
 PLANE_BYTES = {"linear": 12, "normal": 12, "albedo": 12, "alpha": 4, "object_id": 4, "variance": 12}
-
-
-def spread(us):
-    us = sorted(us)
-    return dict(median=round(statistics.median(us), 3), min=round(us[0], 3), max=round(us[-1], 3), n=len(us))
 
 
 def bytes_per_pixel(planes):
@@ -35,7 +28,7 @@ def bytes_per_pixel(planes):
 
 
 def measure(a):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    repo_on_path()
     import torch
     from raytracing_folder_amd import capi
     if capi.device_count() < 1:
@@ -79,25 +72,11 @@ def measure(a):
     same = all(torch.equal(out_parent[k].view(torch.uint8), out_new[k].view(torch.uint8)) for k in ("rgb", "z", "count", "linear"))
     if not same:
         raise SystemExit("planes_linear and linear_parent disagree: nothing is timed")
-    us = {k: [] for k in calls}
-    with torch.cuda.stream(stream):
-        for _ in range(10):
-            for c in calls.values():
-                c()
-        stream.synchronize()
-        for _ in range(a.reps):
-            for k, c in calls.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(a.batch):
-                    c()
-                e1.record(stream)
-                e1.synchronize()
-                us[k].append(e0.elapsed_time(e1) * 1e3 / a.batch)
+    us = {k: [t * 1e3 / a.batch for t in v] for k, v in event_times(stream, calls, a.reps, batch=a.batch).items()}
     res = {}
     for k, names in (("linear_parent", ("linear",)), ("planes_all", ALL), ("planes_linear", ("linear",))):
         rd, wr = bytes_per_pixel(names)
-        r = dict(us_per_launch=spread(us[k]), bytes_read_per_pixel=rd, bytes_written_per_pixel=wr)
+        r = dict(us_per_launch=spread(us[k], 3), bytes_read_per_pixel=rd, bytes_written_per_pixel=wr)
         moved = (rd + wr) * w * h
         r["ps_per_byte"] = round(r["us_per_launch"]["median"] * 1e6 / moved, 3)
         r["gb_per_s"] = round(moved / (r["us_per_launch"]["median"] * 1e-6) / 1e9, 1)
@@ -111,18 +90,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--batch", type=int, default=20)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap, calls=None)
     ap.add_argument("--world", type=int, default=8)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = dict(what="tools_unpack_timing.py", **measure(a))
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,10 @@ built, with --no-variance: only the frame without the plane).  profiles/variance
 one session.
 usage: python tools_variance_timing.py [--root DIR] [--no-variance] [--frames 10] [--no-denoise] [--out FILE]"""
 import argparse
-import json
 import os
-import statistics
 import sys
 
-
-def spread(ms):
-    ms = sorted(ms)
-    return dict(median=round(statistics.median(ms), 4), min=round(ms[0], 4), max=round(ms[-1], 4), n=len(ms))
+from tools_timing import add_common_args, emit, event_times, spread
 
 
 def main():
@@ -27,11 +22,9 @@ def main():
     ap.add_argument("--no-variance", action="store_true")
     ap.add_argument("--no-denoise", action="store_true")
     ap.add_argument("--frames", type=int, default=10)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    add_common_args(ap, calls=None)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--photons", type=int, default=1000000)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import numpy as np
@@ -102,26 +95,10 @@ def main():
                                 object_id_ptr=t["object_id"].data_ptr(), sync=False, levels=5, **extra)
 
         res["denoise_ms"] = {}
-        for guided in kinds:
-            with torch.cuda.stream(stream):
-                for _ in range(10):
-                    call(guided)
-                stream.synchronize()
-                ms = []
-                for _ in range(50):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    call(guided)
-                    e1.record(stream)
-                    e1.synchronize()
-                    ms.append(e0.elapsed_time(e1))
-            res["denoise_ms"]["guided" if guided else "fixed_sigma"] = spread(ms)
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+        for guided in kinds:                                    # one kind after the other, not interleaved
+            name = "guided" if guided else "fixed_sigma"
+            res["denoise_ms"][name] = spread(event_times(stream, {name: lambda: call(guided)}, 50)[name])
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
