@@ -488,6 +488,84 @@ rt_status rt_scene_previous_positions(const rt_scene *s, int32_t *n_meshes);
  * then).  v_prev may be NULL (the count only); otherwise nv_cap counts vertices and a too small one is RT_ERR_ARG. */
 rt_status rt_scene_mesh_device_previous(rt_scene *s, int device, int32_t mesh, float *v_prev, uint64_t nv_cap, uint32_t *nv_out);
 
+/* ---- device tree build (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------------
+ * A mesh's tree built again ON THE DEVICE that holds the mesh, for the caller whose refitted tree has degraded and who cannot
+ * afford what RT_MESH_UPDATE_REBUILD costs (binned SAH on one host thread, then the whole scene lowered again).  The tree is a
+ * linear BVH: a binary radix tree over Morton-sorted triangles, collapsed four-wide into the node records described at
+ * rt_scene_mesh_device_bvh.  It is a worse tree than the host's (DESIGN.md section 3 has the measured costs) and it is opt-in:
+ * nothing above changes what it does.  The definition fixes every choice, so that the kernels (csrc/rt_bvh_build.hip) and the host
+ * mirror (rt_device_lbvh_build) produce the same tree; the arithmetic is written once, in csrc/rt_lbvh.h.  No product is fused
+ * into a sum; every min / max keeps the value held so far unless the new one is smaller / larger (std::min / std::max).
+ *
+ * For a mesh of nf faces over the vertices v:
+ *   1. boxes     per face, lo / hi are the min / max of its three vertices and its centroid is c = 0.5f * (lo + hi) (what the host
+ *                builder uses); clo / chi are the min / max over all centroids.
+ *   2. key       per axis q = clamp((int)((c - clo) * (1024.0f / (chi - clo))), 0, 1023), and q = 0 when chi - clo is not > 0 or
+ *                not finite (flat and degenerate meshes).  The 30-bit Morton code interleaves qx, qy, qz (x highest); the 64-bit
+ *                key is morton << 32 | face.  No two keys are equal, so every correct ascending sort gives the same order.
+ *   3. slots     slot i holds the face of the i-th key (slot_face[i]).  A leaf's triangles are a contiguous slot range, in KEY
+ *                order -- not by face index as in the host builder's leaves.  The closest hit does not depend on it; only two
+ *                triangles at a bit-equal closest t could show the difference.
+ *   4. tree      the binary radix tree of Karras (2012) over the sorted keys, delta(i, j) = clz64(k_i ^ k_j) and -1 out of range.
+ *                A subtree whose key range holds at most 4 keys while its parent's holds more is a leaf (1..4 triangles).  nf <= 4
+ *                is a root leaf and no node record.
+ *   5. boxes     every box is the exact min / max of the vertices beneath it: no rounding, no padding.  A bound is defined up
+ *                to the sign of a zero.
+ *   6. collapse  a record stands for a binary node: it starts from that node's two children; while it has fewer than four and an
+ *                internal one is left, the internal child with the largest 2 (dx dy + dy dz + dz dx) -- the first of equals -- is
+ *                replaced by its two children, in place.  Unused children have NaN bounds and the ref of a leaf of one triangle at slot 0.
+ *   7. numbering breadth-first: the root is record 0, the records of depth d + 1 follow those of depth d, ordered by (parent
+ *                record, child position).
+ *   8. stack_need  the maximum over root-to-leaf paths of the sum of (children - 1), as everywhere.  Nothing bounds it below
+ *                bvh_lds + bvh_spill for every mesh (the radix tree can be 58 levels deep): a tree that needs more is not accepted
+ *                by the build calls below, which fall back to RT_MESH_UPDATE_REBUILD's path and say so.
+ *
+ * rt_device_lbvh_build is the host mirror: plain C++, no GPU, no HIP call, on bare arrays (v: nv x 3 floats, f: nf x 3 indices
+ * below nv, both required and positive in number, else RT_ERR_ARG).  info, nodes, nodes_cap, slot_face and slots_cap are those of
+ * rt_scene_mesh_device_bvh: sizes only with NULL buffers, RT_ERR_ARG and nothing written when a capacity is too small. */
+rt_status rt_device_lbvh_build(const float *v, int32_t nv, const uint32_t *f, int32_t nf, rt_device_bvh_info *info, void *nodes,
+                               uint64_t nodes_cap, uint32_t *slot_face, uint64_t slots_cap);
+/* What a build call reports.  struct_size must be the caller's sizeof (else RT_ERR_ARG).  flags is exactly one of
+ *   ON_DEVICE      every device that held the scene built the tree; the figures are the first such device's;
+ *   FELL_BACK      that device's tree came out with stack_need above the limit: the call took RT_MESH_UPDATE_REBUILD's path
+ *                  (every device lowers the scene again at its next use); stack_need is the refused tree's;
+ *   NOT_ON_DEVICE  no device held the scene: there was nothing to build on, the next lowering builds the host's tree.
+ * The milliseconds are HIP events on the library's stream: the vertex (and, the first time, index) upload; centroid box, keys and
+ * the sort; the radix tree and its boxes; the collapse; the slots with k_mesh_retri; k_bvh_cost.  launches counts the kernel
+ * launches of the build (the sort's own included as one), syncs its host synchronisations. */
+#define RT_MESH_BUILD_ON_DEVICE     1u
+#define RT_MESH_BUILD_FELL_BACK     2u
+#define RT_MESH_BUILD_NOT_ON_DEVICE 4u
+typedef struct rt_mesh_build_info {
+    uint32_t struct_size;
+    uint32_t flags;
+    uint32_t n_nodes, n_slots, root_ref;
+    int32_t  stack_need, levels;
+    int32_t  launches, syncs;
+    uint32_t pad;
+    double   cost;           /* of the tree just built (k_bvh_cost): the device's built_cost from now on */
+    float    upload_ms, sort_ms, hierarchy_ms, collapse_ms, slots_ms, cost_ms;
+} rt_mesh_build_info;
+/* The update that builds.  Arguments, their checks and their messages are rt_scene_update_mesh_vertices_flags's; flags is 0 or
+ * RT_MESH_UPDATE_KEEP_PREVIOUS, any other bit RT_ERR_ARG; out may be NULL.  The store takes the new vertices as for REBUILD (the
+ * cyBVH arrays go stale, a generated photon map is dropped, the previous positions follow the flag); then every device that holds
+ * the scene builds the mesh's tree from the vertices it has just been sent -- per-face index arrays and texture vertices go to a
+ * device once, at the mesh's first build there -- writes the slots in the new order (k_mesh_retri, and tex where the mesh has
+ * texture vertices), takes the root box and the cull boxes, and measures the new tree with k_bvh_cost: that cost is the device's
+ * built_cost from then on, so rt_scene_mesh_quality's ratio is exactly 1 after a build.  A later flags-0 update refits the
+ * device-built tree and rt_scene_mesh_device_read returns it.  A device that is in use or fails lowers the scene again at its
+ * next use, as after an in-place update.  A device that lowers the scene LATER gets the host's SAH tree: the devices of one scene
+ * can hold different trees from then on, and rt_scene_update_mesh_vertices_auto's measurement speaks for the first device only.
+ * The limit on stack_need is bvh_lds + bvh_spill; the test hook RT_LBVH_STACK_CAP (environment, read at call time, like
+ * RT_QUEUE_CAP) lowers it. */
+rt_status rt_scene_update_mesh_vertices_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                              uint32_t flags, rt_mesh_build_info *out);
+/* rt_scene_update_mesh_vertices_auto_flags, building on the device instead of invalidating when ratio > max_ratio: q is as there
+ * (RT_MESH_QUALITY_REBUILT set, the REFITTED tree's cost), out as above (flags 0 when nothing was built).  Either may be NULL. */
+rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                   double max_ratio, uint32_t flags, rt_mesh_quality *q, rt_mesh_build_info *out);
+
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
  * (maxElementsPerNode = 4, FIN/include/objects.h:143).  nodes_out needs room for 2*nf+1

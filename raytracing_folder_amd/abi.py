@@ -203,6 +203,19 @@ class MeshQuality(C.Structure):
                     not_on_device=bool(self.flags & MESH_QUALITY_NOT_ON_DEVICE))
 
 
+class MeshBuildInfo(C.Structure):
+    """rt_mesh_build_info: what a device tree build reports (rt_scene_update_mesh_vertices_build)"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_nodes", C.c_uint32), ("n_slots", C.c_uint32), ("root_ref", C.c_uint32),
+                ("stack_need", C.c_int32), ("levels", C.c_int32), ("launches", C.c_int32), ("syncs", C.c_int32), ("pad", C.c_uint32),
+                ("cost", C.c_double)] + [(n, C.c_float) for n in ("upload_ms", "sort_ms", "hierarchy_ms", "collapse_ms", "slots_ms", "cost_ms")]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "flags", "pad")}
+        d.update(on_device=bool(self.flags & MESH_BUILD_ON_DEVICE), fell_back=bool(self.flags & MESH_BUILD_FELL_BACK),
+                 not_on_device=bool(self.flags & MESH_BUILD_NOT_ON_DEVICE))
+        return d
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -237,6 +250,10 @@ MESH_UPDATE_KEEP_PREVIOUS = 2
 MESH_QUALITY_DEGENERATE = 1
 MESH_QUALITY_REBUILT = 2
 MESH_QUALITY_NOT_ON_DEVICE = 4
+# rt_mesh_build_info flags (include/rt_mi355x.h, "device tree build")
+MESH_BUILD_ON_DEVICE = 1
+MESH_BUILD_FELL_BACK = 2
+MESH_BUILD_NOT_ON_DEVICE = 4
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -306,6 +323,9 @@ SIGNATURES = {
     "rt_scene_update_mesh_vertices_auto_flags": (st, [vp, i32, vp, i32, vp, i32, f64, u32, vp]),
     "rt_scene_previous_positions": (st, [vp, vp]),
     "rt_scene_mesh_device_previous": (st, [vp, i32, i32, vp, u64, vp]),
+    "rt_device_lbvh_build": (st, [vp, i32, vp, i32, vp, vp, u64, vp, u64]),
+    "rt_scene_update_mesh_vertices_build": (st, [vp, i32, vp, i32, vp, i32, u32, vp]),
+    "rt_scene_update_mesh_vertices_auto_build": (st, [vp, i32, vp, i32, vp, i32, f64, u32, vp, vp]),
     "rt_bvh_build": (st, [vp, i32, vp, i32, i32, vp, vp, vp]),
     "rt_photon_balance": (st, [vp, u32, vp]),
     "rt_photon_unreachable": (st, [vp, u32, vp, u32, vp]),

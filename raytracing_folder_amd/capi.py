@@ -20,6 +20,17 @@ def device_bvh_cost(nodes, root_ref):
     return cost.value, bool(flags.value & MESH_QUALITY_DEGENERATE)
 
 
+def device_lbvh_build(v, f):
+    """rt_device_lbvh_build, the host mirror of the device tree build (no GPU): (DeviceBvhInfo, DEVBVHNODE records, face of every
+    triangle slot) of bare triangles, in the form of Scene.mesh_device_read's info / nodes / slot_face"""
+    v, f = _c(v, np.float32).reshape(-1, 3), _c(f, np.uint32).reshape(-1, 3)
+    info = DeviceBvhInfo(struct_size=C.sizeof(DeviceBvhInfo))
+    _check(lib().rt_device_lbvh_build(_p(v), len(v), _p(f), len(f), C.byref(info), None, 0, None, 0))
+    nodes, slot_face = np.zeros(info.n_nodes, DEVBVHNODE), np.zeros(info.n_slots, np.uint32)
+    _check(lib().rt_device_lbvh_build(_p(v), len(v), _p(f), len(f), C.byref(info), _p(nodes), len(nodes), _p(slot_face), len(slot_face)))
+    return info, nodes, slot_face
+
+
 def default_params(**kw):
     p = Params()
     lib().rt_params_default(C.byref(p))
@@ -249,13 +260,30 @@ class Scene(_Handle):
         refitted tree is measured as well (rt_scene_update_mesh_vertices_auto) and built again at the next use when its SAH cost
         has grown beyond max_ratio times the built tree's; the call then returns mesh_quality()'s dict, else None.
         keep_previous=True (RT_MESH_UPDATE_KEEP_PREVIOUS; goes with either): the positions the mesh had become its previous
-        positions, which motion() follows its pixels through; an update without it makes the mesh rigid again"""
-        if max_ratio is not None and rebuild:
+        positions, which motion() follows its pixels through; an update without it makes the mesh rigid again.
+        rebuild="device" (rt_mi355x.h, "device tree build"): the tree is built again on every device that holds the scene, by the
+        device; the call returns the build-info dict.  With max_ratio the device build takes the place of the rebuild at the next
+        use, and the quality dict has a "build" entry when it happened."""
+        device_build = isinstance(rebuild, str)
+        if device_build and rebuild != "device":
+            raise ValueError(f"update_mesh_vertices: rebuild is {rebuild!r} (False, True or 'device')")
+        if max_ratio is not None and rebuild and not device_build:
             raise ValueError("update_mesh_vertices: rebuild=True and max_ratio exclude each other")
         v = _c(v, np.float32).reshape(-1, 3)
         vn = _c(vn, np.float32).reshape(-1, 3) if vn is not None else None
         mesh = (self._h, int(index), _p(v), len(v), _p(vn), len(vn) if vn is not None else 0)
         keep = MESH_UPDATE_KEEP_PREVIOUS if keep_previous else 0
+        if device_build:
+            b = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
+            if max_ratio is None:
+                _check(lib().rt_scene_update_mesh_vertices_build(*mesh, keep, C.byref(b)))
+                return b.as_dict()
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_update_mesh_vertices_auto_build(*mesh, max_ratio, keep, C.byref(q), C.byref(b)))
+            out = q.as_dict()
+            if b.flags:
+                out["build"] = b.as_dict()
+            return out
         if max_ratio is not None:
             q = MeshQuality(struct_size=C.sizeof(MeshQuality))
             _check(lib().rt_scene_update_mesh_vertices_auto_flags(*mesh, max_ratio, keep, C.byref(q)))

@@ -257,6 +257,58 @@ extern "C" rt_status rt_scene_update_mesh_vertices_auto_flags(rt_scene *s, int32
     return update_mesh_vertices_auto("rt_scene_update_mesh_vertices_auto_flags", s, mesh, v, nv, vn, nvn, max_ratio, flags, out);
 }
 
+// ---- device tree build: the updates that build (rt_mi355x.h, "device tree build"; the build itself: rt_lower.cpp) -------------
+static rt_status check_build_info(const char *who, const rt_mesh_build_info *out)
+{
+    if (out && out->struct_size != sizeof(rt_mesh_build_info))
+        return fail(RT_ERR_ARG, "%s: rt_mesh_build_info.struct_size is %u, this library's is %zu", who, out->struct_size, sizeof(rt_mesh_build_info));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_update_mesh_vertices_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                         uint32_t flags, rt_mesh_build_info *out)
+{
+    const char *who = "rt_scene_update_mesh_vertices_build";
+    rt_status st = check_idle(s, who);
+    if (st) return st;
+    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS) return fail(RT_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
+    if ((st = check_build_info(who, out))) return st;
+    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
+    rt_mesh_build_info b;
+    st = build_mesh_on_devices(s, mesh, vn != nullptr, &b);
+    if (out) *out = b;
+    return st;
+}
+
+extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
+                                                              double max_ratio, uint32_t flags, rt_mesh_quality *q_out, rt_mesh_build_info *out)
+{
+    const char *who = "rt_scene_update_mesh_vertices_auto_build";
+    rt_status st = check_idle(s, who);
+    if (st) return st;
+    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS)
+        return fail(RT_ERR_ARG, "%s: flag bits 0x%x (only RT_MESH_UPDATE_KEEP_PREVIOUS goes with max_ratio)", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
+    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "%s: max_ratio is %g (it must be finite and at least 1)", who, max_ratio);
+    if (q_out && q_out->struct_size != sizeof(rt_mesh_quality))
+        return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", who, q_out->struct_size, sizeof(rt_mesh_quality));
+    if ((st = check_build_info(who, out))) return st;
+    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
+    rt_mesh_quality q = {};
+    q.struct_size = sizeof q;
+    rt_mesh_build_info b = {};
+    b.struct_size = sizeof b;
+    st = refit_mesh_on_devices(s, mesh, vn != nullptr, &q);
+    // the vertices are on the devices already; the build sends them again with everything else it does (normals only if this call brought some)
+    if (!st && q.ratio > max_ratio) { q.flags |= RT_MESH_QUALITY_REBUILT; st = build_mesh_on_devices(s, mesh, vn != nullptr, &b); }
+    if (q_out) *q_out = q;
+    if (out) *out = b;
+    return st;
+}
+
 // how many meshes of the scene hold previous positions, from the store (no device, no HIP call)
 extern "C" rt_status rt_scene_previous_positions(const rt_scene *s, int32_t *n_meshes)
 {

@@ -97,7 +97,16 @@ struct DevMeshBufs {
     double built_cost = 0; uint32_t built_flags = 0;
     DevBuf cost_partials;
     std::vector<double> cost_host;
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials}) b->release(); }
+    // device tree build (rt_bvh_build.hip): the per-face index arrays and the texture vertices, on the device from the mesh's first build there
+    DevBuf f, fn, ft, vt;
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt}) b->release(); }
+};
+// the scratch of a device tree build (MeshBuildScratch of rt_launch.h), the device's own: grown to the largest mesh built there
+struct MeshBuildBufs {
+    DevBuf cbox, keys[2], sort_tmp, bin, parent, visit, rec_bin, rec_held, result, slot_face;
+    std::vector<uint32_t> result_host, slot_face_host, level_nodes_host;
+    Event ev[7];                        // upload | keys + sort | hierarchy + boxes | collapse | slots + retri | (host) | cost
+    void release() { for (DevBuf *b : {&cbox, &keys[0], &keys[1], &sort_tmp, &bin, &parent, &visit, &rec_bin, &rec_held, &result, &slot_face}) b->release(); for (Event &e : ev) e = Event(); }
 };
 
 static const size_t SPILL_BYTES = (size_t)RT_SPILL_BLOCKS * RT_BLOCK * RT_BVH_SPILL * 4;     // DevScene::bvh_spill / DevWork::bvh_spill
@@ -171,6 +180,7 @@ struct DeviceState {
     // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
     Event upd_ev[4]; int upd_levels = -1;
     Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
+    MeshBuildBufs build;                // device tree builds here
     // one of the two maps: its buffers with what the kernels see of it
     PhotonMapRef map(bool caustic) { return {maps[caustic], caustic ? scene.cm : scene.pm}; }
     void release()
@@ -179,6 +189,7 @@ struct DeviceState {
                           &raw_photons, &bvh_spill, &stats, &t_in}) b->release();
         for (PhotonStore &m : maps) m.release();
         for (auto &m : mesh_bufs) m.release();
+        build.release();
         for (Event &e : upd_ev) e = Event();
         for (Event &e : cost_ev) e = Event();
         upd_levels = -1;
@@ -229,6 +240,10 @@ RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
 // quality: NULL, or where the first device that holds the scene leaves the refitted tree's measure (rt_scene_update_mesh_vertices_auto;
 // flags RT_MESH_QUALITY_NOT_ON_DEVICE when none did)
 RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality = nullptr);
+// rt_lower.cpp: what rt_scene_update_mesh_vertices_build does on the devices that hold the scene, under the same conditions: the
+// mesh's tree built by every such device (rt_bvh_build.hip).  info (struct_size set): the first building device's figures; flags
+// ON_DEVICE, NOT_ON_DEVICE, or FELL_BACK -- a tree with stack_need above the limit: the caller takes RT_MESH_UPDATE_REBUILD's path
+RT_HIDDEN rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info);
 // rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
 RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
 RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);

@@ -260,6 +260,32 @@ struct BvhCostRequest {
     double *partials;
 };
 
+// One build of a mesh's tree on a device (rt_bvh_build.hip; the definition: rt_mi355x.h, "device tree build").  v, f, fn (and vt, ft
+// where the mesh has texture vertices, else NULL with tex) are the mesh on the device, n_faces > 0 of them.  The scratch is the
+// caller's (rtk_mesh_build_scratch says how much): two key arrays and the sort's temporary storage, the binary nodes with their
+// parents and visit counters, the records' binary nodes and held entries.  nodes has room for n_faces records -- a record stands
+// for a binary node with more than four keys beneath it, of which there are fewer than n_faces.  result (device, RT_LBVH_RESULT_WORDS
+// words): [0] the record count, [1] the levels, [2] stack_need, [3] 1 when the collapse stopped at RT_LBVH_MAX_LEVELS or at the
+// capacity (never for a tree of the definition), [4 + d] where depth d starts (n_levels + 1 entries).  after_*: events recorded
+// behind the phases (sort, boxes, collapse); the slots follow the collapse.  A mesh of at most four faces has no hierarchy, boxes
+// or collapse launch and a result of zeros.
+#define RT_LBVH_MAX_LEVELS 64
+#define RT_LBVH_RESULT_WORDS (4 + RT_LBVH_MAX_LEVELS + 1)
+struct LbvhBin;
+struct MeshBuildScratch {
+    float *cbox;                            // [blocks + 1][6]: the workgroups' centroid boxes, then the mesh's
+    unsigned long long *keys[2]; void *sort_tmp; size_t sort_tmp_bytes;
+    LbvhBin *bin; uint32_t *parent, *visit; // n_faces - 1 each
+    uint32_t *rec_bin; int32_t *rec_held;   // n_faces each
+};
+struct MeshBuildRequest {
+    const float *v; const uint32_t *f, *fn; const float *vt; const uint32_t *ft; uint32_t n_faces;
+    MeshBuildScratch scratch;
+    DevBvhNode *nodes; uint32_t *result;
+    uint32_t *slot_face, *slot_idx; float *tex;
+    hipEvent_t after_sort, after_boxes, after_collapse;
+};
+
 // ---- rt_kernels.hip: the kernels that shade -----------------------------------------------------------------------------
 // The ray queue of tree level l >= 1 is W.rq[l & 1] with its count in W.counts[l]: a launch that works on level l reads
 // that one and appends the rays it spawns to level l + 1.
@@ -344,6 +370,12 @@ hipError_t rtk_launch_dof(hipStream_t st, const DofRequest &R);
 hipError_t rtk_launch_mesh_refit(hipStream_t st, const MeshRefitRequest &R);
 // on `st`: k_bvh_cost over all the tree's records in one launch
 hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R);
+
+// ---- rt_bvh_build.hip: a mesh's tree built on the device ------------------------------------------------------------------
+// bytes of the sort's temporary storage for n_faces keys
+size_t rtk_mesh_build_sort_bytes(uint32_t n_faces);
+// on `st`: centroid box, keys, sort, radix tree, boxes, collapse, slots (k_mesh_retri is the caller's next launch); *launches: how many
+hipError_t rtk_launch_mesh_build(hipStream_t st, const MeshBuildRequest &R, int *launches);
 
 // ---- rt_photon_build.hip: the photon set-up on the GPU ------------------------------------------------------------------
 // progress of a photon pass on the device (state_dev[0], and [1] as the shadow a batch writes): attempts consumed, hits counted, photons stored

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -14,6 +15,7 @@
 #include "host/rt_scene.h"
 #include "rt_host.h"
 #include "rt_bvh_cost.h"
+#include "rt_lbvh.h"
 
 // ---- lowering to the device ---------------------------------------------------------------------------
 static DeviceState *device_state(rt_scene *s, int device)
@@ -228,6 +230,34 @@ extern "C" rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, r
     info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
     info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
     if (nodes) memcpy(nodes, bn.data(), bn.size() * sizeof(DevBvhNode));
+    if (slot_face) memcpy(slot_face, faces.data(), faces.size() * 4);
+    return RT_OK;
+}
+
+// ---- device tree build: the host mirror (rt_mi355x.h, "device tree build") ----------------------------------------------------
+// lbvh_build_host of rt_lbvh.h, the functions the kernels of rt_bvh_build.hip are made of in plain loops, behind the ABI's argument checks
+extern "C" rt_status rt_device_lbvh_build(const float *v, int32_t nv, const uint32_t *f, int32_t nf, rt_device_bvh_info *info, void *nodes,
+                                          uint64_t nodes_cap, uint32_t *slot_face, uint64_t slots_cap)
+{
+    if (!v || !f || !info) return fail(RT_ERR_ARG, "rt_device_lbvh_build: NULL argument");
+    if (info->struct_size != sizeof(rt_device_bvh_info))
+        return fail(RT_ERR_ARG, "rt_device_lbvh_build: rt_device_bvh_info.struct_size is %u, this library's is %zu", info->struct_size, sizeof(rt_device_bvh_info));
+    if (nv <= 0 || nf <= 0) return fail(RT_ERR_ARG, "rt_device_lbvh_build: nv is %d and nf is %d (both must be positive)", nv, nf);
+    if ((uint32_t)nf >= 0x10000000u) return fail(RT_ERR_LIMIT, "mesh too large");
+    for (int64_t i = 0; i < 3LL * nf; i++) if (f[i] >= (uint32_t)nv) return fail(RT_ERR_ARG, "rt_device_lbvh_build: face index %u >= nv", f[i]);
+    std::vector<LbvhRecord> bn;
+    std::vector<uint32_t> faces;
+    uint32_t root_ref = 0;
+    int need = 0;
+    lbvh_build_host(v, f, (size_t)nf, bn, faces, root_ref, need);
+    // both capacities before anything is written: a refused call leaves info and both buffers as they were
+    if (nodes && nodes_cap < bn.size()) return fail(RT_ERR_ARG, "rt_device_lbvh_build: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, bn.size());
+    if (slot_face && slots_cap < faces.size()) return fail(RT_ERR_ARG, "rt_device_lbvh_build: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, faces.size());
+    info->n_nodes = (uint32_t)bn.size(); info->n_slots = (uint32_t)faces.size();
+    info->root_ref = root_ref; info->stack_need = need;
+    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
+    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
+    if (nodes && !bn.empty()) memcpy(nodes, bn.data(), bn.size() * sizeof(DevBvhNode));
     if (slot_face) memcpy(slot_face, faces.data(), faces.size() * 4);
     return RT_OK;
 }
@@ -648,6 +678,178 @@ static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh
     else { q->flags = 0; q->ratio = q->cost / q->built_cost; }
     HIP_TRY(hipEventElapsedTime(&q->measure_ms, D->cost_ev[0], D->cost_ev[1]));
     return RT_OK;
+}
+
+// ---- device tree build (rt_mi355x.h, "device tree build") ---------------------------------------------------------------------
+// the limit on a device-built tree's stack_need: what the kernels provide, or less under the test hook RT_LBVH_STACK_CAP (read at call time)
+static int lbvh_stack_cap()
+{
+    int cap = RT_BVH_LDS + RT_BVH_SPILL;
+    if (const char *e = getenv("RT_LBVH_STACK_CAP")) { const long v = strtol(e, nullptr, 10); if (v >= 0 && v < cap) cap = (int)v; }
+    return cap;
+}
+
+// One device's share of rt_scene_update_mesh_vertices_build, modelled on refit_mesh_on_device: the same waits, the same uploads,
+// then the tree built from the vertices just uploaded (rt_bvh_build.hip) in place of the refit, the slots written in its order, and
+// everything that follows a tree's topology set again -- the record count and DevMesh::nodes / root_ref, slot_face, level_off and
+// level_nodes, stack_need with DevScene::max_bvh_depth and the spill buffers, built_cost.  Two host synchronisations: one for
+// the record count, the levels and stack_need (the cost launch and the fallback decision need them), one at the end.
+// *fell_back: the tree needs more stack than `cap`; the device is left for the caller to invalidate.
+static rt_status build_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
+                                      int cap, rt_mesh_build_info *info, bool *fell_back)
+{
+    HIP_TRY(hipSetDevice(D->device));
+    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
+    rt_status rs;
+    if ((rs = motion_wait_host(D->device))) return rs;                                      // ... or k_motion_mesh walking it
+    const size_t nf = m.f.size() / 3;
+    if ((size_t)mesh >= D->mesh_bufs.size() || D->mesh_bufs[mesh].slot_face.size() != nf || objs.size() != (size_t)D->scene.n_objects)
+        return fail(RT_ERR_STATE, "rt_scene_update_mesh_vertices_build: device %d does not hold mesh %d as the scene has it", D->device, mesh);
+    DevMeshBufs &mb = D->mesh_bufs[mesh];
+    MeshBuildBufs &B = D->build;
+    hipStream_t st = D->stream;
+    for (Event &e : B.ev) if (!e.e) HIP_TRY(e.create());
+    const bool first = mb.vn.p == nullptr, first_build = mb.f.p == nullptr;
+    const bool textured = mb.tex.p != nullptr && !m.vt.empty() && m.ft.size() == m.f.size();
+    if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    if (m.v_prev.empty()) mb.v_prev.release();
+    else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
+    if (first_build) {
+        if ((rs = mb.f.ensure(m.f.size() * 4)) || (rs = mb.fn.ensure(m.fn.size() * 4))) return rs;
+        if (textured && ((rs = mb.ft.ensure(m.ft.size() * 4)) || (rs = mb.vt.ensure(m.vt.size() * 4)))) return rs;
+    }
+    // the scratch, and room for the records: fewer than nf (a record stands for a binary node with more than four keys beneath it)
+    const uint32_t blocks = (uint32_t)((nf + 255) / 256);
+    const size_t sort_bytes = rtk_mesh_build_sort_bytes((uint32_t)nf);
+    if ((rs = B.cbox.ensure(((size_t)blocks + 1) * 24)) || (rs = B.keys[0].ensure(nf * 8)) || (rs = B.keys[1].ensure(nf * 8)) || (rs = B.sort_tmp.ensure(sort_bytes)) ||
+        (rs = B.bin.ensure(nf * sizeof(LbvhBin))) || (rs = B.parent.ensure(nf * 4)) || (rs = B.visit.ensure(nf * 4)) || (rs = B.rec_bin.ensure(nf * 4)) ||
+        (rs = B.rec_held.ensure(nf * 4)) || (rs = B.result.ensure(RT_LBVH_RESULT_WORDS * 4)) || (rs = B.slot_face.ensure(nf * 4))) return rs;
+    if (nf > RT_LBVH_LEAF_TRIS && (rs = mb.nodes.ensure(nf * sizeof(DevBvhNode)))) return rs;      // (may move: DevMesh::nodes is set again below)
+    if ((rs = mb.level_nodes.ensure(nf * 4))) return rs;
+    HIP_TRY(hipEventRecord(B.ev[0], st));
+    if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
+    if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
+    if (first_build) {
+        HIP_TRY(hipMemcpyAsync(mb.f.p, m.f.data(), m.f.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(mb.fn.p, m.fn.data(), m.fn.size() * 4, hipMemcpyHostToDevice, st));
+        if (textured) {
+            HIP_TRY(hipMemcpyAsync(mb.ft.p, m.ft.data(), m.ft.size() * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(mb.vt.p, m.vt.data(), m.vt.size() * 4, hipMemcpyHostToDevice, st));
+        }
+    }
+    HIP_TRY(hipEventRecord(B.ev[1], st));
+    MeshBuildRequest R = {};
+    R.v = (const float *)mb.v.p; R.f = (const uint32_t *)mb.f.p; R.fn = (const uint32_t *)mb.fn.p; R.n_faces = (uint32_t)nf;
+    if (textured) { R.vt = (const float *)mb.vt.p; R.ft = (const uint32_t *)mb.ft.p; R.tex = (float *)mb.tex.p; }
+    R.scratch.cbox = (float *)B.cbox.p; R.scratch.keys[0] = (unsigned long long *)B.keys[0].p; R.scratch.keys[1] = (unsigned long long *)B.keys[1].p;
+    R.scratch.sort_tmp = B.sort_tmp.p; R.scratch.sort_tmp_bytes = sort_bytes;
+    R.scratch.bin = (LbvhBin *)B.bin.p; R.scratch.parent = (uint32_t *)B.parent.p; R.scratch.visit = (uint32_t *)B.visit.p;
+    R.scratch.rec_bin = (uint32_t *)B.rec_bin.p; R.scratch.rec_held = (int32_t *)B.rec_held.p;
+    R.nodes = (DevBvhNode *)mb.nodes.p; R.result = (uint32_t *)B.result.p;
+    R.slot_face = (uint32_t *)B.slot_face.p; R.slot_idx = (uint32_t *)mb.slot_idx.p;
+    R.after_sort = B.ev[2]; R.after_boxes = B.ev[3]; R.after_collapse = B.ev[4];
+    int launches = 0;
+    HIP_TRY(rtk_launch_mesh_build(st, R, &launches));
+    MeshRefitRequest T = {};                                     // k_mesh_retri alone: no level of the old tree is refitted
+    T.v = R.v; T.vn = (const float *)mb.vn.p; T.slot_idx = R.slot_idx; T.n_slots = (uint32_t)nf;
+    T.tris = (DevTri *)mb.tris.p; T.nrm = (float *)mb.nrm.p;
+    HIP_TRY(rtk_launch_mesh_refit(st, T));
+    launches++;
+    HIP_TRY(hipEventRecord(B.ev[5], st));
+    B.result_host.assign(RT_LBVH_RESULT_WORDS, 0u);
+    B.slot_face_host.resize(nf);
+    HIP_TRY(hipMemcpyAsync(B.result_host.data(), B.result.p, RT_LBVH_RESULT_WORDS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(B.slot_face_host.data(), B.slot_face.p, nf * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t n_nodes = B.result_host[0], levels = B.result_host[1];
+    const int need = (int)B.result_host[2];
+    if (info) {
+        info->n_nodes = n_nodes; info->n_slots = (uint32_t)nf; info->stack_need = need; info->levels = (int32_t)levels;
+        info->root_ref = nf <= RT_LBVH_LEAF_TRIS ? lbvh_leafref(0, (uint32_t)nf) : 0u;
+        info->launches = launches; info->syncs = 1;
+        HIP_TRY(hipEventElapsedTime(&info->upload_ms, B.ev[0], B.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&info->sort_ms, B.ev[1], B.ev[2]));
+        HIP_TRY(hipEventElapsedTime(&info->hierarchy_ms, B.ev[2], B.ev[3]));
+        HIP_TRY(hipEventElapsedTime(&info->collapse_ms, B.ev[3], B.ev[4]));
+        HIP_TRY(hipEventElapsedTime(&info->slots_ms, B.ev[4], B.ev[5]));
+    }
+    if (B.result_host[3] || need > cap || n_nodes > nf || levels > RT_LBVH_MAX_LEVELS) { *fell_back = true; return RT_OK; }
+    // what follows the topology, on the host: slot order, root, need, the levels as the refit wants them (deepest first; numbering
+    // is breadth-first, so depth d is the index range [at[d], at[d + 1]) and level_nodes is those ranges in reverse order)
+    const uint32_t *at = B.result_host.data() + 4;
+    mb.slot_face = B.slot_face_host;
+    mb.root_ref = nf <= RT_LBVH_LEAF_TRIS ? lbvh_leafref(0, (uint32_t)nf) : 0u;
+    mb.stack_need = need;
+    mb.level_off.assign((size_t)levels + 1, 0u);
+    B.level_nodes_host.resize(n_nodes);
+    for (uint32_t k = 0, w = 0; k < levels; k++) {
+        const uint32_t d = levels - 1 - k;
+        for (uint32_t i = at[d]; i < at[d + 1]; i++) B.level_nodes_host[w++] = i;
+        mb.level_off[k + 1] = mb.level_off[k] + (at[d + 1] - at[d]);
+    }
+    if (n_nodes) HIP_TRY(hipMemcpyAsync(mb.level_nodes.p, B.level_nodes_host.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
+    DevMesh dm;
+    memset(&dm, 0, sizeof dm);
+    dm.nodes = (const DevBvhNode *)mb.nodes.p; dm.tris = (const DevTri *)mb.tris.p; dm.nrm = (const float *)mb.nrm.p;
+    dm.tex = textured ? (const float *)mb.tex.p : nullptr;
+    dm.root_ref = mb.root_ref; dm.n_tris = (uint32_t)nf;
+    memcpy(dm.root_box, m.root_box, 24);
+    HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh), &dm, sizeof(DevMesh), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
+    if (need > D->scene.max_bvh_depth) {                        // the spill buffers come into being as in upload_scene and ensure_workspace
+        D->scene.max_bvh_depth = need;
+        if (need > RT_BVH_LDS) {
+            if ((rs = D->bvh_spill.ensure(SPILL_BYTES))) return rs;
+            D->scene.bvh_spill = (uint32_t *)D->bvh_spill.p;
+            for (Workspace &w : D->ws) if (w.samples && (rs = w.bvh_spill.ensure(SPILL_BYTES))) return rs;
+        }
+    }
+    D->upd_levels = -1;                                         // (rt_scene_mesh_update_ms speaks of refits)
+    if ((rs = enqueue_mesh_cost(D, mb))) return rs;
+    HIP_TRY(hipStreamSynchronize(st));
+    rt_mesh_quality q = {};
+    mb.built_cost = 1.0; mb.built_flags = 0;
+    if ((rs = finish_mesh_cost(D, mb, &q))) return rs;
+    mb.built_cost = q.cost; mb.built_flags = (q.flags & RT_MESH_QUALITY_DEGENERATE) ? RT_COST_DEGENERATE : 0u;
+    if (info) { info->cost = q.cost; info->cost_ms = q.measure_ms; info->launches = launches + (n_nodes ? 1 : 0); info->syncs = 2; }
+    return RT_OK;
+}
+
+rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info)
+{
+    const rt::MeshData &m = s->data.meshes[mesh];
+    rt_mesh_build_info none = {};
+    none.struct_size = sizeof none; none.flags = RT_MESH_BUILD_NOT_ON_DEVICE;
+    *info = none;
+    bool any = false, reported = false, fell_back = false;
+    for (DeviceState *D : s->devs) any = any || D->scene_valid;
+    if (!any) return RT_OK;
+    std::vector<DevObject> objs;
+    std::vector<DevObjectBack> backs;
+    std::vector<int32_t> node_mat;
+    rt_status st = lower_objects(s->data, objs, backs, node_mat);
+    const int cap = lbvh_stack_cap();
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    rt_status ret = RT_OK;
+    for (DeviceState *D : s->devs) {
+        if (!D->scene_valid) continue;
+        // a device another call is using, or one the build fails on, lowers the scene again at its next use instead
+        DeviceClaim claim(D);
+        rt_status r = st;
+        if (!r && claim.ok && !fell_back) {
+            rt_mesh_build_info mine = none;
+            r = build_mesh_on_device(D, m, mesh, normals_changed, objs, cap, &mine, &fell_back);
+            if (!r && !reported) { *info = mine; info->flags = fell_back ? RT_MESH_BUILD_FELL_BACK : RT_MESH_BUILD_ON_DEVICE; reported = true; }
+        }
+        if (r || !claim.ok || fell_back) D->scene_valid = false;
+        if (r && !ret) ret = r;
+    }
+    (void)hipSetDevice(cur);
+    // the same mesh gives the same tree on every device: one that does not fit fits nowhere, and the call takes REBUILD's path
+    if (fell_back) { s->invalidate(true, false); info->flags = RT_MESH_BUILD_FELL_BACK; }
+    return ret;
 }
 
 extern "C" rt_status rt_scene_mesh_quality(rt_scene *s, int device, int32_t mesh, rt_mesh_quality *out)
