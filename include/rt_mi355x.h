@@ -368,7 +368,8 @@ rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, rt_device_bv
 /* ---- mesh vertex updates (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
  *      unchanged) ---------------------------------------------------------------------------------------------------------------
  * New positions (and, optionally, normals) for a mesh whose faces stay as they are: a deforming surface, frame after frame.
- * nv and nvn must be the stored counts (anything else: RT_ERR_ARG, nothing changes); vn == NULL keeps the stored normals.  The
+ * nv and nvn must be the stored counts (anything else: RT_ERR_ARG, nothing changes); vn == NULL keeps the stored normals (or, for a mesh in RT_MESH_NORMALS_SMOOTH mode, computes them again for
+ * the new v: "smooth normals" below).  The
  * scene must be idle (no live job).  flags: 0, or RT_MESH_UPDATE_REBUILD; rt_scene_update_mesh_vertices_flags takes either with or
  * without RT_MESH_UPDATE_KEEP_PREVIOUS.  Any other bit is RT_ERR_ARG.
  *   0        On every device that holds this scene as it is now, the mesh is updated IN PLACE: the vertices are uploaded,
@@ -565,6 +566,50 @@ rt_status rt_scene_update_mesh_vertices_build(rt_scene *s, int32_t mesh, const f
  * (RT_MESH_QUALITY_REBUILT set, the REFITTED tree's cost), out as above (flags 0 when nothing was built).  Either may be NULL. */
 rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                                    double max_ratio, uint32_t flags, rt_mesh_quality *q, rt_mesh_build_info *out);
+
+/* ---- smooth normals (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------------
+ * The vertex normals of a deforming mesh, computed again from its new positions at every update, on the device that refits it:
+ * the normals a mesh gets when it brings none (cyTriMesh::ComputeNormals), with the order of every addition fixed, so that the
+ * kernel (csrc/rt_mesh_normals.hip) and the host mirror (rt_mesh_smooth_normals) give the same bytes.  The arithmetic is written
+ * once, in csrc/rt_mesh_normals.h.
+ *
+ * For a mesh with faces f, normal indices fn (both nf x 3) and positions v:
+ *   corner    c = 3 i + k (k in 0..2) belongs to face i.
+ *   N_i       the face's unnormalised normal cross(v[f[3i+1]] - v[f[3i]], v[f[3i+2]] - v[f[3i]]), operation by operation as
+ *             k_mesh_retri and rt::Point3 compute it: float32, no product fused into a sum, with u and w the two differences the
+ *             components uy*wz - uz*wy, uz*wx - ux*wz, ux*wy - uy*wx.
+ *   S_j       starts at (0, 0, 0); N_i is added per component for every corner c with fn[c] == j, IN ASCENDING c (a face that
+ *             names j at two corners is added twice, as ComputeNormals adds it).
+ *   normal j  S_j / sqrtf(S_j.x^2 + S_j.y^2 + S_j.z^2): the sum of squares left to right, / and sqrtf correctly rounded.
+ *   kept      a normal that no corner refers to keeps its stored value, and so does one whose length is 0 or not finite.
+ * With fn == f and no degenerate input this is ComputeNormals byte for byte; with an OBJ's own fn != f it keeps the OBJ's seams.
+ *
+ * rt_mesh_smooth_normals is the host mirror: plain C++, no GPU, no HIP call, on bare arrays.  fn == NULL stands for f (nvn must
+ * be able to hold its indices).  vn_inout holds the stored values on entry (nvn x 3 floats) and the normals on return.  RT_ERR_ARG
+ * and nothing written: a NULL or empty array, a face index >= nv, a normal index >= nvn. */
+rt_status rt_mesh_smooth_normals(const float *v, int32_t nv, const uint32_t *f, const uint32_t *fn, int32_t nf, float *vn_inout,
+                                 int32_t nvn);
+/* The mode of one mesh: what an update that brings no normals (vn == NULL) leaves the mesh with.
+ *   STORED  (the default) the normals it had: everything above is what it was, launch for launch, and nothing is allocated.
+ *   SMOOTH  the normals defined above for the new v -- after every one of the six update calls, in the store (rt_scene_get_mesh,
+ *           and every later lowering: the store runs the mirror when its normals are next read, not inside the update) and on
+ *           every device that holds the scene: k_mesh_normals writes the mesh's normals between the vertex upload and
+ *           k_mesh_retri, which copies them into the slots; the refit or the build follows.  What the kernel works from -- the
+ *           corners of every normal, nadj_off[nvn + 1] and nadj_corner[3 nf] with the corners of a row ascending, and the
+ *           faces -- goes to a device once, at the mesh's first such update there.  A kept normal is not written: it keeps
+ *           what the device's array held, the value last uploaded or computed there.
+ * An update that does bring vn uses them for that call, in either mode.  Setting the mode touches no normal: it takes effect at
+ * the next update.  rt_scene_set_mesh resets the mode to STORED, as it drops previous positions.  The scene must be idle; an
+ * unknown mode or a mesh never set is RT_ERR_ARG and nothing changes. */
+#define RT_MESH_NORMALS_STORED 0u
+#define RT_MESH_NORMALS_SMOOTH 1u
+rt_status rt_scene_set_mesh_normals_mode(rt_scene *s, int32_t mesh, uint32_t mode);
+rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t mesh, uint32_t *mode);
+/* Milliseconds of the last k_mesh_normals launch on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that
+ * device has run none (rt_mesh_update_ms does not grow: its struct_size is checked).  The launch sits behind the uploads and
+ * ahead of the event that ends them: in SMOOTH mode rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms include it. */
+rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms);
 
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it

@@ -254,6 +254,9 @@ MESH_QUALITY_NOT_ON_DEVICE = 4
 MESH_BUILD_ON_DEVICE = 1
 MESH_BUILD_FELL_BACK = 2
 MESH_BUILD_NOT_ON_DEVICE = 4
+# rt_scene_set_mesh_normals_mode modes (include/rt_mi355x.h, "smooth normals")
+MESH_NORMALS_STORED = 0
+MESH_NORMALS_SMOOTH = 1
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -326,6 +329,10 @@ SIGNATURES = {
     "rt_device_lbvh_build": (st, [vp, i32, vp, i32, vp, vp, u64, vp, u64]),
     "rt_scene_update_mesh_vertices_build": (st, [vp, i32, vp, i32, vp, i32, u32, vp]),
     "rt_scene_update_mesh_vertices_auto_build": (st, [vp, i32, vp, i32, vp, i32, f64, u32, vp, vp]),
+    "rt_mesh_smooth_normals": (st, [vp, i32, vp, vp, i32, vp, i32]),
+    "rt_scene_set_mesh_normals_mode": (st, [vp, i32, u32]),
+    "rt_scene_get_mesh_normals_mode": (st, [vp, i32, vp]),
+    "rt_scene_mesh_normals_ms": (st, [vp, i32, vp]),
     "rt_bvh_build": (st, [vp, i32, vp, i32, i32, vp, vp, vp]),
     "rt_photon_balance": (st, [vp, u32, vp]),
     "rt_photon_unreachable": (st, [vp, u32, vp, u32, vp]),

@@ -31,6 +31,17 @@ def device_lbvh_build(v, f):
     return info, nodes, slot_face
 
 
+def mesh_smooth_normals(v, f, fn=None, vn=None):
+    """rt_mesh_smooth_normals, the host mirror of k_mesh_normals (no GPU): the smooth normals of positions v under faces f and
+    normal indices fn (None: f), float32 (nvn, 3).  vn holds the stored values, which a normal without a corner or without a
+    direction keeps (it is not modified); None: as many normals as vertices, stored values 0."""
+    v, f = _c(v, np.float32).reshape(-1, 3), _c(f, np.uint32).reshape(-1, 3)
+    fn = _c(fn, np.uint32).reshape(-1, 3) if fn is not None else None
+    out = np.array(vn, np.float32).reshape(-1, 3) if vn is not None else np.zeros((len(v), 3), np.float32)
+    _check(lib().rt_mesh_smooth_normals(_p(v), len(v), _p(f), _p(fn), len(f), _p(out), len(out)))
+    return out
+
+
 def default_params(**kw):
     p = Params()
     lib().rt_params_default(C.byref(p))
@@ -289,6 +300,26 @@ class Scene(_Handle):
             _check(lib().rt_scene_update_mesh_vertices_auto_flags(*mesh, max_ratio, keep, C.byref(q)))
             return q.as_dict()
         _check(lib().rt_scene_update_mesh_vertices_flags(*mesh, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
+
+    def set_mesh_normals(self, index, mode):
+        """what an update without normals leaves mesh `index` with: "stored" (the default: the normals it had) or "smooth" -- its
+        smooth normals computed again for the new positions, on the devices that hold the scene (rt_mi355x.h, "smooth normals")"""
+        modes = {"stored": MESH_NORMALS_STORED, "smooth": MESH_NORMALS_SMOOTH}
+        if mode not in modes:
+            raise ValueError(f"set_mesh_normals: mode is {mode!r} ('stored' or 'smooth')")
+        _check(lib().rt_scene_set_mesh_normals_mode(self._h, int(index), modes[mode]))
+
+    def mesh_normals(self, index):
+        """the mode of mesh `index`: "stored" or "smooth" """
+        mode = C.c_uint32()
+        _check(lib().rt_scene_get_mesh_normals_mode(self._h, int(index), C.byref(mode)))
+        return {MESH_NORMALS_STORED: "stored", MESH_NORMALS_SMOOTH: "smooth"}[mode.value]
+
+    def mesh_normals_ms(self, device=0):
+        """milliseconds of the last k_mesh_normals launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
+        ms = C.c_float()
+        _check(lib().rt_scene_mesh_normals_ms(self._h, device, C.byref(ms)))
+        return ms.value
 
     def previous_positions(self):
         """how many meshes of the scene hold previous positions (from the scene store: no GPU)"""

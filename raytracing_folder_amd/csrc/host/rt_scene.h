@@ -318,6 +318,10 @@ struct MeshData {
     // the positions before the last rt_scene_update_mesh_vertices with RT_MESH_UPDATE_KEEP_PREVIOUS, indexed like v; empty: the
     // mesh holds none (never flagged, or set again, or updated without the flag since)
     std::vector<float> v_prev;
+    // rt_scene_set_mesh_normals_mode (RT_MESH_NORMALS_*), and -- SMOOTH mode only -- vn_stale: an update without normals replaced
+    // v since vn was computed; vn is computed again for the v of now (rt_mesh_smooth_normals's arithmetic) when somebody reads it
+    uint32_t normals_mode = 0;
+    bool vn_stale = false;
 };
 struct SceneData {
     std::vector<rt_node> nodes;

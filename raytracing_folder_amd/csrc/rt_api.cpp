@@ -19,6 +19,7 @@
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
 #include "rt_host.h"
+#include "rt_mesh_normals.h"
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;       // the one message of rt_last_error(), whichever file failed
@@ -154,6 +155,7 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     m.tree_stale = false;
     m.vt.clear(); m.ft.clear();
     m.v_prev.clear();                   // the faces may have changed: no pairing of old and new vertices is vouched for
+    m.normals_mode = RT_MESH_NORMALS_STORED; m.vn_stale = false;      // ... and the caller has just brought the normals it wants
     s->geometry_changed();
     return RT_OK;
 }
@@ -164,12 +166,31 @@ void ensure_reference_tree(rt::MeshData &m)
     rt::BuildMeanSplitBVH(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), 4, m.nodes, m.elements);      // TriObj::Load's leaves of four
     m.tree_stale = false;
 }
-// for the getters, which take the scene const: the tree is a cache of what the vertices determine
+// the definition of "smooth normals" (rt_mi355x.h) on arrays whose indices have been checked: the adjacency, then every row
+// walked by the function k_mesh_normals walks it with (rt_mesh_normals.h); vn holds the stored values and keeps those of the
+// normals that have no corner or no direction
+static void smooth_normals_host(const float *v, const uint32_t *f, const uint32_t *fn, size_t nf, size_t nvn, float *vn)
+{
+    std::vector<uint32_t> off(nvn + 1), corner(3 * nf);
+    mesh_normal_adjacency(fn, nf, nvn, off.data(), corner.data());
+    for (size_t j = 0; j < nvn; j++) {
+        float n[3];
+        if (mesh_smooth_normal(v, f, corner.data(), off[j], off[j + 1], n)) memcpy(vn + 3 * j, n, 12);
+    }
+}
+void ensure_normals(rt::MeshData &m)
+{
+    if (!m.vn_stale) return;
+    smooth_normals_host(m.v.data(), m.f.data(), m.fn.data(), m.f.size() / 3, m.vn.size() / 3, m.vn.data());
+    m.vn_stale = false;
+}
+// for the getters, which take the scene const: the tree and, in SMOOTH mode, the normals are caches of what the vertices determine
 static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
 {
     rt_scene *w = const_cast<rt_scene *>(s);
     std::lock_guard<std::mutex> lk(w->mu);
     ensure_reference_tree(w->data.meshes[mesh]);
+    ensure_normals(w->data.meshes[mesh]);
     return w->data.meshes[mesh];
 }
 
@@ -187,7 +208,9 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
         return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
     if (keep_previous) m.v_prev.swap(m.v); else std::vector<float>().swap(m.v_prev);
     m.v.assign(v, v + 3 * (size_t)nv);
-    if (vn) m.vn.assign(vn, vn + 3 * (size_t)nvn);
+    // SMOOTH mode without normals: the devices compute them (rt_lower.cpp), the store when they are next read -- not here
+    if (vn) { m.vn.assign(vn, vn + 3 * (size_t)nvn); m.vn_stale = false; }
+    else if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
     m.tree_stale = true;
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
     // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
@@ -307,6 +330,46 @@ extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32
     if (q_out) *q_out = q;
     if (out) *out = b;
     return st;
+}
+
+// ---- smooth normals (rt_mi355x.h, "smooth normals"; the kernel: rt_mesh_normals.hip, its launches: rt_lower.cpp) ----------------
+extern "C" rt_status rt_mesh_smooth_normals(const float *v, int32_t nv, const uint32_t *f, const uint32_t *fn, int32_t nf, float *vn_inout, int32_t nvn)
+{
+    if (!v || !f || !vn_inout || nv <= 0 || nf <= 0 || nvn <= 0)
+        return fail(RT_ERR_ARG, "rt_mesh_smooth_normals: v, f and vn_inout are required (nv=%d nf=%d nvn=%d)", nv, nf, nvn);
+    if (!fn) fn = f;
+    for (int64_t i = 0; i < 3LL * nf; i++) {
+        if (f[i] >= (uint32_t)nv) return fail(RT_ERR_ARG, "rt_mesh_smooth_normals: face index %u >= nv", f[i]);
+        if (fn[i] >= (uint32_t)nvn) return fail(RT_ERR_ARG, "rt_mesh_smooth_normals: normal index %u >= nvn", fn[i]);
+    }
+    smooth_normals_host(v, f, fn, (size_t)nf, (size_t)nvn, vn_inout);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_set_mesh_normals_mode(rt_scene *s, int32_t mesh, uint32_t mode)
+{
+    rt_status st = check_idle(s, "rt_scene_set_mesh_normals_mode");
+    if (st) return st;
+    if (mode != RT_MESH_NORMALS_STORED && mode != RT_MESH_NORMALS_SMOOTH) return fail(RT_ERR_ARG, "rt_scene_set_mesh_normals_mode: unknown mode %u", mode);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
+        return fail(RT_ERR_ARG, "rt_scene_set_mesh_normals_mode: mesh %d was never set", mesh);
+    rt::MeshData &m = s->data.meshes[mesh];
+    // leaving SMOOTH: the normals the devices hold are those of the v of now, and a later update in STORED mode is to keep
+    // exactly them -- the store's copy is brought up to date while it still has that v (no normal changes: a cache is filled)
+    if (mode != RT_MESH_NORMALS_SMOOTH) ensure_normals(m);
+    m.normals_mode = mode;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t mesh, uint32_t *mode)
+{
+    if (!s || !mode) return fail(RT_ERR_ARG, "rt_scene_get_mesh_normals_mode: NULL argument");
+    std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
+        return fail(RT_ERR_ARG, "rt_scene_get_mesh_normals_mode: mesh %d was never set", mesh);
+    *mode = s->data.meshes[mesh].normals_mode;
+    return RT_OK;
 }
 
 // how many meshes of the scene hold previous positions, from the store (no device, no HIP call)

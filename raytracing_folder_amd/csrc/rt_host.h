@@ -99,7 +99,11 @@ struct DevMeshBufs {
     std::vector<double> cost_host;
     // device tree build (rt_bvh_build.hip): the per-face index arrays and the texture vertices, on the device from the mesh's first build there
     DevBuf f, fn, ft, vt;
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt}) b->release(); }
+    // smooth normals (rt_mesh_normals.hip): the corners of every normal in CSR form, nadj_off[nvn + 1] and nadj_corner[3 nf] with the
+    // corners of a row ascending, on the device from the mesh's first update in SMOOTH mode there (with f, which that kernel reads
+    // too).  They follow the faces and fn, which stay: a device build keeps them.
+    DevBuf nadj_off, nadj_corner;
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt, &nadj_off, &nadj_corner}) b->release(); }
 };
 // the scratch of a device tree build (MeshBuildScratch of rt_launch.h), the device's own: grown to the largest mesh built there
 struct MeshBuildBufs {
@@ -179,6 +183,7 @@ struct DeviceState {
     hipStream_t stream = nullptr;
     // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
     Event upd_ev[4]; int upd_levels = -1;
+    Event nrm_ev[2]; bool nrm_timed = false;        // around the last k_mesh_normals here (rt_scene_mesh_normals_ms)
     Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
     MeshBuildBufs build;                // device tree builds here
     // one of the two maps: its buffers with what the kernels see of it
@@ -192,6 +197,8 @@ struct DeviceState {
         build.release();
         for (Event &e : upd_ev) e = Event();
         for (Event &e : cost_ev) e = Event();
+        for (Event &e : nrm_ev) e = Event();
+        nrm_timed = false;
         upd_levels = -1;
         for (Workspace &w : ws) w.release();
         for (int k = 0; k < 6; k++) t_out[k].release();
@@ -236,6 +243,9 @@ struct rt_scene {
 RT_HIDDEN rt_status check_idle(rt_scene *s, const char *who);                                   // rt_api.cpp
 // rt_api.cpp: the stored cyBVH arrays of a mesh, built again if a vertex update left them stale (caller holds s->mu)
 RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
+// rt_api.cpp: the stored normals of a mesh, computed again if an update in SMOOTH mode left them stale (caller holds s->mu); to
+// be called wherever m.vn is read
+RT_HIDDEN void ensure_normals(rt::MeshData &m);
 // rt_lower.cpp: what rt_scene_update_mesh_vertices does on the devices that hold the scene (caller holds s->mu, the store has the new vertices)
 // quality: NULL, or where the first device that holds the scene leaves the refitted tree's measure (rt_scene_update_mesh_vertices_auto;
 // flags RT_MESH_QUALITY_NOT_ON_DEVICE when none did)

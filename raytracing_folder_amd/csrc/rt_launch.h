@@ -249,6 +249,16 @@ struct MeshRefitRequest {
     hipEvent_t after_retri;
 };
 
+// One mesh's smooth normals computed again on a device (rt_mesh_normals.hip; the definition: rt_mi355x.h, "smooth normals").  v
+// and f are the mesh's positions and face indices on the device, nadj_off (n_normals + 1 entries) and nadj_corner (three per
+// face) the corners of every normal with the corners of a row ascending; vn (n_normals x 3 floats) holds the stored values and
+// receives every normal that is not to keep its own.
+struct MeshNormalsRequest {
+    const float *v; const uint32_t *f;
+    const uint32_t *nadj_off, *nadj_corner; uint32_t n_normals;
+    float *vn;
+};
+
 // One measurement of a mesh's tree on a device (rt_refit.hip, k_bvh_cost; the definition: rt_mi355x.h, "mesh tree quality"): the
 // n_nodes (> 0, at most 2^28) records at `nodes`, one double per block of 256 terms to partials[0 .. ceil(4 n_nodes / 256)).
 // partials has room for one double more: under RT_COST_FOLD_DEVICE k_bvh_cost_fold leaves the sum of the others there.
@@ -370,6 +380,10 @@ hipError_t rtk_launch_dof(hipStream_t st, const DofRequest &R);
 hipError_t rtk_launch_mesh_refit(hipStream_t st, const MeshRefitRequest &R);
 // on `st`: k_bvh_cost over all the tree's records in one launch
 hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R);
+
+// ---- rt_mesh_normals.hip: smooth normals of a deforming mesh -------------------------------------------------------------
+// on `st`: k_mesh_normals over the mesh's normals (ahead of k_mesh_retri, which copies them into the slots)
+hipError_t rtk_launch_mesh_normals(hipStream_t st, const MeshNormalsRequest &R);
 
 // ---- rt_bvh_build.hip: a mesh's tree built on the device ------------------------------------------------------------------
 // bytes of the sort's temporary storage for n_faces keys

@@ -16,6 +16,7 @@
 #include "rt_host.h"
 #include "rt_bvh_cost.h"
 #include "rt_lbvh.h"
+#include "rt_mesh_normals.h"
 
 // ---- lowering to the device ---------------------------------------------------------------------------
 static DeviceState *device_state(rt_scene *s, int device)
@@ -438,6 +439,7 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     std::vector<DevMesh> dm(sd.meshes.size());
     int max_depth = 0;
     for (size_t mi = 0; mi < sd.meshes.size(); mi++) {
+        ensure_normals(s->data.meshes[mi]);      // SMOOTH mode: the normals of the v of now, which a device updated in place holds already
         const rt::MeshData &m = sd.meshes[mi];
         memset(&dm[mi], 0, sizeof(DevMesh));
         if (m.f.empty()) continue;
@@ -547,7 +549,36 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
 static rt_status enqueue_mesh_cost(DeviceState *D, DevMeshBufs &mb);
 static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh_quality *q);
 
-static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
+// Smooth normals (rt_mi355x.h, "smooth normals"), one device's share in two steps.  prepare: what k_mesh_normals works from, on
+// the device from the mesh's first update in SMOOTH mode there -- the adjacency over normal indices, built here by a counting
+// sort that follows the faces, and the face indices (which a device build may have brought already).  enqueue: the launch on the
+// update's stream, behind the vertex upload and ahead of k_mesh_retri, between the events rt_scene_mesh_normals_ms reads.
+static rt_status prepare_mesh_normals(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    rt_status rs;
+    for (Event &e : D->nrm_ev) if (!e.e) HIP_TRY(e.create());
+    if (!mb.f.p && (rs = mb.f.upload(m.f.data(), m.f.size() * 4))) return rs;
+    if (mb.nadj_off.p && mb.nadj_corner.p) return RT_OK;
+    const size_t nvn = m.vn.size() / 3;
+    std::vector<uint32_t> off(nvn + 1), corner(m.fn.size());
+    mesh_normal_adjacency(m.fn.data(), m.fn.size() / 3, nvn, off.data(), corner.data());
+    if ((rs = mb.nadj_corner.upload(corner.data(), corner.size() * 4))) return rs;
+    return mb.nadj_off.upload(off.data(), off.size() * 4);
+}
+static rt_status enqueue_mesh_normals(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    MeshNormalsRequest N = {};
+    N.v = (const float *)mb.v.p; N.f = (const uint32_t *)mb.f.p;
+    N.nadj_off = (const uint32_t *)mb.nadj_off.p; N.nadj_corner = (const uint32_t *)mb.nadj_corner.p;
+    N.n_normals = (uint32_t)(m.vn.size() / 3); N.vn = (float *)mb.vn.p;
+    HIP_TRY(hipEventRecord(D->nrm_ev[0], D->stream));
+    HIP_TRY(rtk_launch_mesh_normals(D->stream, N));
+    HIP_TRY(hipEventRecord(D->nrm_ev[1], D->stream));
+    D->nrm_timed = true;
+    return RT_OK;
+}
+
+static rt_status refit_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
                                       rt_mesh_quality *quality)
 {
     HIP_TRY(hipSetDevice(D->device));
@@ -561,7 +592,13 @@ static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
     hipStream_t st = D->stream;
     for (Event &e : D->upd_ev) if (!e.e) HIP_TRY(e.create());
     const bool first = mb.vn.p == nullptr;
+    // SMOOTH mode and no normals brought: the device computes them from the vertices it is about to be sent
+    const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
+    // the store's normals are about to be read: never stale ones over what k_mesh_normals wrote here (the first time they are
+    // the values the kernel's kept normals keep)
+    if (first || normals_changed) ensure_normals(m);
     // the previous positions follow the store: uploaded from it ahead of the new vertices, in the update's stream, by a flagged
     // update; released by an unflagged one (nothing is allocated, copied or freed for a mesh that never used the flag)
     if (m.v_prev.empty()) mb.v_prev.release();
@@ -570,6 +607,7 @@ static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
     if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
     if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
+    if (smooth && (rs = enqueue_mesh_normals(D, m, mb))) return rs;
     HIP_TRY(hipEventRecord(D->upd_ev[1], st));
     MeshRefitRequest R = {};
     R.v = (const float *)mb.v.p; R.vn = (const float *)mb.vn.p;
@@ -589,7 +627,7 @@ static rt_status refit_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
 
 rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality)
 {
-    const rt::MeshData &m = s->data.meshes[mesh];
+    rt::MeshData &m = s->data.meshes[mesh];
     bool any = false, measured = false;
     if (quality) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
     for (DeviceState *D : s->devs) any = any || D->scene_valid;
@@ -695,7 +733,7 @@ static int lbvh_stack_cap()
 // level_nodes, stack_need with DevScene::max_bvh_depth and the spill buffers, built_cost.  Two host synchronisations: one for
 // the record count, the levels and stack_need (the cost launch and the fallback decision need them), one at the end.
 // *fell_back: the tree needs more stack than `cap`; the device is left for the caller to invalidate.
-static rt_status build_mesh_on_device(DeviceState *D, const rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
+static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
                                       int cap, rt_mesh_build_info *info, bool *fell_back)
 {
     HIP_TRY(hipSetDevice(D->device));
@@ -709,9 +747,12 @@ static rt_status build_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
     MeshBuildBufs &B = D->build;
     hipStream_t st = D->stream;
     for (Event &e : B.ev) if (!e.e) HIP_TRY(e.create());
-    const bool first = mb.vn.p == nullptr, first_build = mb.f.p == nullptr;
+    const bool first = mb.vn.p == nullptr, first_build = mb.fn.p == nullptr;      // (f alone may be there already: k_mesh_normals reads it too)
+    const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;      // as in refit_mesh_on_device
     const bool textured = mb.tex.p != nullptr && !m.vt.empty() && m.ft.size() == m.f.size();
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
+    if (first || normals_changed) ensure_normals(m);
     if (m.v_prev.empty()) mb.v_prev.release();
     else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
     if (first_build) {
@@ -738,6 +779,7 @@ static rt_status build_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
             HIP_TRY(hipMemcpyAsync(mb.vt.p, m.vt.data(), m.vt.size() * 4, hipMemcpyHostToDevice, st));
         }
     }
+    if (smooth && (rs = enqueue_mesh_normals(D, m, mb))) return rs;      // k_mesh_retri, behind the build, copies them into the slots
     HIP_TRY(hipEventRecord(B.ev[1], st));
     MeshBuildRequest R = {};
     R.v = (const float *)mb.v.p; R.f = (const uint32_t *)mb.f.p; R.fn = (const uint32_t *)mb.fn.p; R.n_faces = (uint32_t)nf;
@@ -818,7 +860,7 @@ static rt_status build_mesh_on_device(DeviceState *D, const rt::MeshData &m, int
 
 rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info)
 {
-    const rt::MeshData &m = s->data.meshes[mesh];
+    rt::MeshData &m = s->data.meshes[mesh];
     rt_mesh_build_info none = {};
     none.struct_size = sizeof none; none.flags = RT_MESH_BUILD_NOT_ON_DEVICE;
     *info = none;
@@ -884,6 +926,15 @@ extern "C" rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_up
     HIP_TRY(hipEventElapsedTime(&out->retri, D->upd_ev[1], D->upd_ev[2]));
     HIP_TRY(hipEventElapsedTime(&out->refit, D->upd_ev[2], D->upd_ev[3]));
     out->level_launches = D->upd_levels;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms)
+{
+    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_normals_ms: NULL argument");
+    DeviceState *D = find_device_state(s, device);
+    if (!D || !D->nrm_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_normals_ms: device %d has not computed a mesh's normals", device);
+    HIP_TRY(hipEventElapsedTime(ms, D->nrm_ev[0], D->nrm_ev[1]));
     return RT_OK;
 }
 
