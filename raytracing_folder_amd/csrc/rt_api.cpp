@@ -1,7 +1,8 @@
 // rt_api.cpp -- the part of the C ABI in include/rt_mi355x.h that needs no device state: errors, version, default parameters,
 // the scene store and its getters, the image and .dat wrappers, the host-side BVH and photon helpers.
-// Lowering a scene to the device layout of rt_dev.h is rt_lower.cpp, the photon maps rt_photons.cpp, rendering rt_render.cpp, the
-// image-space stages rt_post.cpp; rt_host.h is what they share.
+// Lowering a scene to the device layout of rt_dev.h is rt_lower.cpp, changing a lowered mesh in place rt_mesh_update.cpp (the
+// store's part of a vertex update with it), the photon maps rt_photons.cpp, rendering rt_render.cpp, the image-space stages
+// rt_post.cpp; rt_host.h is what they share.
 // There is no CPU render path in this library: without a gfx950 device the render calls fail.
 #include <hip/hip_runtime.h>
 
@@ -194,145 +195,14 @@ static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
     return w->data.meshes[mesh];
 }
 
-// What rt_scene_update_mesh_vertices and rt_scene_update_mesh_vertices_auto share: the argument checks (`who` names the entry
-// point in the message) and, once they pass, the new vertices in the store.  keep_previous (RT_MESH_UPDATE_KEEP_PREVIOUS): the
-// positions the mesh had become its previous positions; without it the mesh holds none afterwards.  The caller holds s->mu.
-static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, bool keep_previous,
-                                     const char *who)
+// the one answer to a mesh index nobody set (`who` names the entry point; caller holds s->mu)
+rt_status check_mesh_set(const rt_scene *s, int32_t mesh, const char *who)
 {
-    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
-        return fail(RT_ERR_ARG, "%s: mesh %d was never set", who, mesh);
-    rt::MeshData &m = s->data.meshes[mesh];
-    if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, nv, m.v.size() / 3);
-    if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
-        return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
-    if (keep_previous) m.v_prev.swap(m.v); else std::vector<float>().swap(m.v_prev);
-    m.v.assign(v, v + 3 * (size_t)nv);
-    // SMOOTH mode without normals: the devices compute them (rt_lower.cpp), the store when they are next read -- not here
-    if (vn) { m.vn.assign(vn, vn + 3 * (size_t)nvn); m.vn_stale = false; }
-    else if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
-    m.tree_stale = true;
-    rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
-    // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
-    s->drop_generated_photons();
+    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "%s: mesh %d was never set", who, mesh);
     return RT_OK;
 }
 
-// known: the flag bits the entry point `who` takes
-static rt_status update_mesh_vertices(const char *who, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                      uint32_t flags, uint32_t known)
-{
-    rt_status st = check_idle(s, who);
-    if (st) return st;
-    if (flags & ~known) return fail(RT_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags & ~known);
-    const bool keep = (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0;
-    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
-    std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep, who))) return st;
-    if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }      // (the next lowering uploads the previous positions from the store)
-    return refit_mesh_on_devices(s, mesh, vn != nullptr, nullptr);
-}
-
-// takes what it always took: any bit but RT_MESH_UPDATE_REBUILD stays RT_ERR_ARG, and the mesh holds no previous positions afterwards
-extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
-{
-    return update_mesh_vertices("rt_scene_update_mesh_vertices", s, mesh, v, nv, vn, nvn, flags, RT_MESH_UPDATE_REBUILD);
-}
-
-// ... and the entry point that takes RT_MESH_UPDATE_KEEP_PREVIOUS as well
-extern "C" rt_status rt_scene_update_mesh_vertices_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
-{
-    return update_mesh_vertices("rt_scene_update_mesh_vertices_flags", s, mesh, v, nv, vn, nvn, flags, RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS);
-}
-
-// flags 0 of the call above, the refitted tree measured behind the refit (rt_lower.cpp), and REBUILD's path taken when the measure says so
-static rt_status update_mesh_vertices_auto(const char *who, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                           double max_ratio, uint32_t flags, rt_mesh_quality *out)
-{
-    rt_status st = check_idle(s, who);
-    if (st) return st;
-    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS)
-        return fail(RT_ERR_ARG, "%s: flag bits 0x%x (only RT_MESH_UPDATE_KEEP_PREVIOUS goes with max_ratio)", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
-    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "%s: max_ratio is %g (it must be finite and at least 1)", who, max_ratio);
-    if (out && out->struct_size != sizeof(rt_mesh_quality))
-        return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", who, out->struct_size, sizeof(rt_mesh_quality));
-    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
-    std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
-    rt_mesh_quality q = {};
-    q.struct_size = sizeof q;
-    st = refit_mesh_on_devices(s, mesh, vn != nullptr, &q);
-    // a degenerate measure has ratio 1, and so has a scene no device holds: neither asks for a rebuild
-    if (!st && q.ratio > max_ratio) { s->invalidate(true, false); q.flags |= RT_MESH_QUALITY_REBUILT; }
-    if (out) *out = q;
-    return st;
-}
-
-extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                                        double max_ratio, rt_mesh_quality *out)
-{
-    return update_mesh_vertices_auto("rt_scene_update_mesh_vertices_auto", s, mesh, v, nv, vn, nvn, max_ratio, 0u, out);
-}
-
-extern "C" rt_status rt_scene_update_mesh_vertices_auto_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                                              double max_ratio, uint32_t flags, rt_mesh_quality *out)
-{
-    return update_mesh_vertices_auto("rt_scene_update_mesh_vertices_auto_flags", s, mesh, v, nv, vn, nvn, max_ratio, flags, out);
-}
-
-// ---- device tree build: the updates that build (rt_mi355x.h, "device tree build"; the build itself: rt_lower.cpp) -------------
-static rt_status check_build_info(const char *who, const rt_mesh_build_info *out)
-{
-    if (out && out->struct_size != sizeof(rt_mesh_build_info))
-        return fail(RT_ERR_ARG, "%s: rt_mesh_build_info.struct_size is %u, this library's is %zu", who, out->struct_size, sizeof(rt_mesh_build_info));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_update_mesh_vertices_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                                         uint32_t flags, rt_mesh_build_info *out)
-{
-    const char *who = "rt_scene_update_mesh_vertices_build";
-    rt_status st = check_idle(s, who);
-    if (st) return st;
-    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS) return fail(RT_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
-    if ((st = check_build_info(who, out))) return st;
-    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
-    std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
-    rt_mesh_build_info b;
-    st = build_mesh_on_devices(s, mesh, vn != nullptr, &b);
-    if (out) *out = b;
-    return st;
-}
-
-extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                                              double max_ratio, uint32_t flags, rt_mesh_quality *q_out, rt_mesh_build_info *out)
-{
-    const char *who = "rt_scene_update_mesh_vertices_auto_build";
-    rt_status st = check_idle(s, who);
-    if (st) return st;
-    if (flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS)
-        return fail(RT_ERR_ARG, "%s: flag bits 0x%x (only RT_MESH_UPDATE_KEEP_PREVIOUS goes with max_ratio)", who, flags & ~RT_MESH_UPDATE_KEEP_PREVIOUS);
-    if (!std::isfinite(max_ratio) || max_ratio < 1.0) return fail(RT_ERR_ARG, "%s: max_ratio is %g (it must be finite and at least 1)", who, max_ratio);
-    if (q_out && q_out->struct_size != sizeof(rt_mesh_quality))
-        return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", who, q_out->struct_size, sizeof(rt_mesh_quality));
-    if ((st = check_build_info(who, out))) return st;
-    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", who);
-    std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, who))) return st;
-    rt_mesh_quality q = {};
-    q.struct_size = sizeof q;
-    rt_mesh_build_info b = {};
-    b.struct_size = sizeof b;
-    st = refit_mesh_on_devices(s, mesh, vn != nullptr, &q);
-    // the vertices are on the devices already; the build sends them again with everything else it does (normals only if this call brought some)
-    if (!st && q.ratio > max_ratio) { q.flags |= RT_MESH_QUALITY_REBUILT; st = build_mesh_on_devices(s, mesh, vn != nullptr, &b); }
-    if (q_out) *q_out = q;
-    if (out) *out = b;
-    return st;
-}
-
-// ---- smooth normals (rt_mi355x.h, "smooth normals"; the kernel: rt_mesh_normals.hip, its launches: rt_lower.cpp) ----------------
+// ---- smooth normals (rt_mi355x.h, "smooth normals"; the kernel: rt_mesh_normals.hip, its launches: rt_mesh_update.cpp) ----------
 extern "C" rt_status rt_mesh_smooth_normals(const float *v, int32_t nv, const uint32_t *f, const uint32_t *fn, int32_t nf, float *vn_inout, int32_t nvn)
 {
     if (!v || !f || !vn_inout || nv <= 0 || nf <= 0 || nvn <= 0)
@@ -352,8 +222,7 @@ extern "C" rt_status rt_scene_set_mesh_normals_mode(rt_scene *s, int32_t mesh, u
     if (st) return st;
     if (mode != RT_MESH_NORMALS_STORED && mode != RT_MESH_NORMALS_SMOOTH) return fail(RT_ERR_ARG, "rt_scene_set_mesh_normals_mode: unknown mode %u", mode);
     std::lock_guard<std::mutex> lk(s->mu);
-    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
-        return fail(RT_ERR_ARG, "rt_scene_set_mesh_normals_mode: mesh %d was never set", mesh);
+    if ((st = check_mesh_set(s, mesh, "rt_scene_set_mesh_normals_mode"))) return st;
     rt::MeshData &m = s->data.meshes[mesh];
     // leaving SMOOTH: the normals the devices hold are those of the v of now, and a later update in STORED mode is to keep
     // exactly them -- the store's copy is brought up to date while it still has that v (no normal changes: a cache is filled)
@@ -366,8 +235,7 @@ extern "C" rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t m
 {
     if (!s || !mode) return fail(RT_ERR_ARG, "rt_scene_get_mesh_normals_mode: NULL argument");
     std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
-    if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty())
-        return fail(RT_ERR_ARG, "rt_scene_get_mesh_normals_mode: mesh %d was never set", mesh);
+    if (rt_status st = check_mesh_set(s, mesh, "rt_scene_get_mesh_normals_mode")) return st;
     *mode = s->data.meshes[mesh].normals_mode;
     return RT_OK;
 }

@@ -1,5 +1,5 @@
 // rt_bvh_cost.h -- the surface-area-heuristic cost of a mesh's device tree (the definition: include/rt_mi355x.h, "mesh tree
-// quality"), as the arithmetic k_bvh_cost (rt_refit.hip) and the host mirror rt_device_bvh_cost (rt_lower.cpp) share: one term,
+// quality"), as the arithmetic k_bvh_cost (rt_refit.hip) and the host mirror rt_device_bvh_cost (rt_mesh_update.cpp) share: one term,
 // one block's summation tree, the fold of the block sums and the last division are each written ONCE here, so the two cannot
 // drift apart.  The kernel runs the block tree as an xor-butterfly instead of bvh_cost_block_sum's loop; the additions and their
 // order are the same (below).  Nothing here needs HIP or any other header of the library: tests/bvh_cost_mirror.cpp compiles it alone.

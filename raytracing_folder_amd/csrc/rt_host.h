@@ -1,6 +1,8 @@
 // rt_host.h -- private to the host files of the C ABI (not installed): what more than one of them needs.
 //   rt_api.cpp     what needs no device state: errors, the scene store and its getters, the image and .dat wrappers
-//   rt_lower.cpp   a scene onto a device (prepare_device): SAH BVH, objects, mesh refit, mesh tree quality
+//   rt_lower.cpp   a scene onto a device (prepare_device): SAH BVH, objects, materials, textures
+//   rt_mesh_update.cpp  a lowered mesh changed in place: the vertex-update entry points, refit, tree quality, device tree build,
+//                  smooth normals, and the calls that read a mesh back from a device
 //   rt_photons.cpp the photon maps: their setters, the gather structures (upload_photons), the photon and caustic passes,
 //                  generate_photons, the global map's state (rt_photon_map.h) with its two device copies
 //   rt_render.cpp  render orchestration: working sets, run_pipeline, the render / packed / unpack entry points, jobs, the
@@ -79,7 +81,7 @@ struct RT_HIDDEN Event {
     operator hipEvent_t() const { return e; }
 };
 
-// ---- a scene on one device (rt_lower.cpp fills it, rt_render.cpp renders from it) ---------------------------
+// ---- a scene on one device (rt_lower.cpp fills it, rt_mesh_update.cpp changes its meshes in place, rt_render.cpp renders from it) ----
 // nodes .. tex are what DevMesh points to.  The rest serves rt_scene_update_mesh_vertices (rt_refit.hip) and is written at upload
 // time with them: per triangle slot the three vertex and three normal indices of its face; the indices of the tree's nodes by
 // depth, the deepest level first (level k is level_nodes[level_off[k] .. level_off[k + 1]), the root's level last); on the host,
@@ -109,7 +111,7 @@ struct DevMeshBufs {
 struct MeshBuildBufs {
     DevBuf cbox, keys[2], sort_tmp, bin, parent, visit, rec_bin, rec_held, result, slot_face;
     std::vector<uint32_t> result_host, slot_face_host, level_nodes_host;
-    Event ev[7];                        // upload | keys + sort | hierarchy + boxes | collapse | slots + retri | (host) | cost
+    Event ev[6];                        // between them: upload | keys + sort | hierarchy + boxes | collapse | slots + retri (the cost: DeviceState::cost_ev)
     void release() { for (DevBuf *b : {&cbox, &keys[0], &keys[1], &sort_tmp, &bin, &parent, &visit, &rec_bin, &rec_held, &result, &slot_face}) b->release(); for (Event &e : ev) e = Event(); }
 };
 
@@ -246,14 +248,19 @@ RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
 // rt_api.cpp: the stored normals of a mesh, computed again if an update in SMOOTH mode left them stale (caller holds s->mu); to
 // be called wherever m.vn is read
 RT_HIDDEN void ensure_normals(rt::MeshData &m);
-// rt_lower.cpp: what rt_scene_update_mesh_vertices does on the devices that hold the scene (caller holds s->mu, the store has the new vertices)
-// quality: NULL, or where the first device that holds the scene leaves the refitted tree's measure (rt_scene_update_mesh_vertices_auto;
-// flags RT_MESH_QUALITY_NOT_ON_DEVICE when none did)
-RT_HIDDEN rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality = nullptr);
-// rt_lower.cpp: what rt_scene_update_mesh_vertices_build does on the devices that hold the scene, under the same conditions: the
-// mesh's tree built by every such device (rt_bvh_build.hip).  info (struct_size set): the first building device's figures; flags
-// ON_DEVICE, NOT_ON_DEVICE, or FELL_BACK -- a tree with stack_need above the limit: the caller takes RT_MESH_UPDATE_REBUILD's path
-RT_HIDDEN rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info);
+// rt_api.cpp: RT_ERR_ARG "<who>: mesh <mesh> was never set" unless rt_scene_set_mesh has given the scene that mesh (caller holds s->mu)
+RT_HIDDEN rt_status check_mesh_set(const rt_scene *s, int32_t mesh, const char *who);
+// rt_lower.cpp: the scene's objects as upload_scene lowers them, with the material of every node; an in-place mesh update sends the
+// objects again for their cull boxes (caller holds s->mu)
+RT_HIDDEN rt_status lower_objects(const rt::SceneData &sd, std::vector<DevObject> &objs, std::vector<DevObjectBack> &backs, std::vector<int32_t> &node_mat);
+// what every call that hands out a device tree says beside the records: its sizes, root and stack need, and the kernels' limits
+inline void fill_device_bvh_info(rt_device_bvh_info *info, size_t n_nodes, size_t n_slots, uint32_t root_ref, int stack_need)
+{
+    info->n_nodes = (uint32_t)n_nodes; info->n_slots = (uint32_t)n_slots;
+    info->root_ref = root_ref; info->stack_need = stack_need;
+    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
+    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
+}
 // rt_lower.cpp: the scene and both photon maps as they are now on `device`, under s->mu; the lookup alone (NULL: never prepared)
 RT_HIDDEN rt_status prepare_device(rt_scene *s, int device, DeviceState **out);
 RT_HIDDEN DeviceState *find_device_state(rt_scene *s, int device);

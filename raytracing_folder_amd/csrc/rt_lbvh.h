@@ -1,5 +1,5 @@
 // rt_lbvh.h -- the tree a device builds for a mesh by itself (the definition: include/rt_mi355x.h, "device tree build"), as the
-// arithmetic the kernels of rt_bvh_build.hip and the host mirror rt_device_lbvh_build (rt_lower.cpp) share: a triangle's box and
+// arithmetic the kernels of rt_bvh_build.hip and the host mirror rt_device_lbvh_build (rt_mesh_update.cpp) share: a triangle's box and
 // centroid, its key, the binary radix tree over the sorted keys (Karras 2012), the four-wide collapse of one node and its
 // 128-byte record are each written ONCE here, so the two cannot drift apart.  Nothing here needs HIP or any other header of the
 // library: tests/lbvh_mirror_driver.cpp compiles it alone.  Every unit is built with -ffp-contract=off: no product is fused into a sum.

@@ -1,12 +1,10 @@
-// rt_lower.cpp -- what puts a scene on a device: the lowering of the scene store (rt_api.cpp) to the device layout of rt_dev.h,
-// the tree the kernels walk, in-place mesh updates.  prepare_device has rt_photons.cpp put the two photon maps beside it;
-// rt_render.cpp renders from what it leaves; rt_host.h is what the host files share.
+// rt_lower.cpp -- what puts a scene on a device: the lowering of the scene store (rt_api.cpp) to the device layout of rt_dev.h and
+// the tree the kernels walk.  prepare_device has rt_photons.cpp put the two photon maps beside it; rt_render.cpp renders from
+// what it leaves, rt_mesh_update.cpp changes a mesh of it in place; rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstddef>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -15,8 +13,6 @@
 #include "host/rt_scene.h"
 #include "rt_host.h"
 #include "rt_bvh_cost.h"
-#include "rt_lbvh.h"
-#include "rt_mesh_normals.h"
 
 // ---- lowering to the device ---------------------------------------------------------------------------
 static DeviceState *device_state(rt_scene *s, int device)
@@ -219,46 +215,16 @@ extern "C" rt_status rt_scene_mesh_device_bvh(const rt_scene *s, int32_t mesh, r
     int need = 0;
     {
         std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
-        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: mesh %d was never set", mesh);
-        rt_status st = build_sah_bvh(s->data.meshes[mesh], bn, faces, root_ref, need);
+        rt_status st = check_mesh_set(s, mesh, "rt_scene_mesh_device_bvh");
+        if (st) return st;
+        st = build_sah_bvh(s->data.meshes[mesh], bn, faces, root_ref, need);
         if (st) return st;
     }
     // both capacities before anything is written: a refused call leaves info and both buffers as they were
     if (nodes && nodes_cap < bn.size()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, bn.size());
     if (slot_face && slots_cap < faces.size()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_bvh: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, faces.size());
-    info->n_nodes = (uint32_t)bn.size(); info->n_slots = (uint32_t)faces.size();
-    info->root_ref = root_ref; info->stack_need = need;
-    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
-    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
+    fill_device_bvh_info(info, bn.size(), faces.size(), root_ref, need);
     if (nodes) memcpy(nodes, bn.data(), bn.size() * sizeof(DevBvhNode));
-    if (slot_face) memcpy(slot_face, faces.data(), faces.size() * 4);
-    return RT_OK;
-}
-
-// ---- device tree build: the host mirror (rt_mi355x.h, "device tree build") ----------------------------------------------------
-// lbvh_build_host of rt_lbvh.h, the functions the kernels of rt_bvh_build.hip are made of in plain loops, behind the ABI's argument checks
-extern "C" rt_status rt_device_lbvh_build(const float *v, int32_t nv, const uint32_t *f, int32_t nf, rt_device_bvh_info *info, void *nodes,
-                                          uint64_t nodes_cap, uint32_t *slot_face, uint64_t slots_cap)
-{
-    if (!v || !f || !info) return fail(RT_ERR_ARG, "rt_device_lbvh_build: NULL argument");
-    if (info->struct_size != sizeof(rt_device_bvh_info))
-        return fail(RT_ERR_ARG, "rt_device_lbvh_build: rt_device_bvh_info.struct_size is %u, this library's is %zu", info->struct_size, sizeof(rt_device_bvh_info));
-    if (nv <= 0 || nf <= 0) return fail(RT_ERR_ARG, "rt_device_lbvh_build: nv is %d and nf is %d (both must be positive)", nv, nf);
-    if ((uint32_t)nf >= 0x10000000u) return fail(RT_ERR_LIMIT, "mesh too large");
-    for (int64_t i = 0; i < 3LL * nf; i++) if (f[i] >= (uint32_t)nv) return fail(RT_ERR_ARG, "rt_device_lbvh_build: face index %u >= nv", f[i]);
-    std::vector<LbvhRecord> bn;
-    std::vector<uint32_t> faces;
-    uint32_t root_ref = 0;
-    int need = 0;
-    lbvh_build_host(v, f, (size_t)nf, bn, faces, root_ref, need);
-    // both capacities before anything is written: a refused call leaves info and both buffers as they were
-    if (nodes && nodes_cap < bn.size()) return fail(RT_ERR_ARG, "rt_device_lbvh_build: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, bn.size());
-    if (slot_face && slots_cap < faces.size()) return fail(RT_ERR_ARG, "rt_device_lbvh_build: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, faces.size());
-    info->n_nodes = (uint32_t)bn.size(); info->n_slots = (uint32_t)faces.size();
-    info->root_ref = root_ref; info->stack_need = need;
-    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
-    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
-    if (nodes && !bn.empty()) memcpy(nodes, bn.data(), bn.size() * sizeof(DevBvhNode));
     if (slot_face) memcpy(slot_face, faces.data(), faces.size() * 4);
     return RT_OK;
 }
@@ -321,8 +287,8 @@ static DevNodeXf xf_of(const rt_node &n)
 static const float *mesh_root_box(const rt::MeshData &m) { return m.tree_stale ? m.root_box : m.nodes[1].box; }
 
 // The DevObject / DevObjectBack records of the scene's objects and the material of every node: shared by upload_scene and by the
-// in-place mesh update (refit_mesh_on_devices), which moves the cull boxes of the objects whose mesh changed.
-static rt_status lower_objects(const rt::SceneData &sd, std::vector<DevObject> &objs, std::vector<DevObjectBack> &backs, std::vector<int32_t> &node_mat)
+// in-place mesh update (rt_mesh_update.cpp), which moves the cull boxes of the objects whose mesh changed.
+rt_status lower_objects(const rt::SceneData &sd, std::vector<DevObject> &objs, std::vector<DevObjectBack> &backs, std::vector<int32_t> &node_mat)
 {
     const int nn = (int)sd.nodes.size();
     objs.clear(); backs.clear();
@@ -538,461 +504,6 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     for (const rt_light &l : sd.lights) if (l.type == RT_LIGHT_POINT && l.size != 0) S.stochastic = 1;
     for (const rt_blinn &m : sd.materials) if (m.reflection_glossiness != 0 || m.refraction_glossiness != 0) S.stochastic = 1;
     D->scene_valid = true;
-    return RT_OK;
-}
-
-// ---- mesh vertex updates -------------------------------------------------------------------------------
-// One device's share of rt_scene_update_mesh_vertices: everything upload_scene derived from this mesh's vertices, set again in
-// place -- DevTri and nrm of every slot and every box of the tree (rt_refit.hip), DevMesh::root_box, and the objects' cull boxes
-// (objs: the scene's objects lowered again by the caller).  Nothing else on the device depends on a mesh's vertices: the tree's
-// topology, stack_need (DevScene::max_bvh_depth, the spill buffers) and tex follow the faces, which stay.
-static rt_status enqueue_mesh_cost(DeviceState *D, DevMeshBufs &mb);
-static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh_quality *q);
-
-// Smooth normals (rt_mi355x.h, "smooth normals"), one device's share in two steps.  prepare: what k_mesh_normals works from, on
-// the device from the mesh's first update in SMOOTH mode there -- the adjacency over normal indices, built here by a counting
-// sort that follows the faces, and the face indices (which a device build may have brought already).  enqueue: the launch on the
-// update's stream, behind the vertex upload and ahead of k_mesh_retri, between the events rt_scene_mesh_normals_ms reads.
-static rt_status prepare_mesh_normals(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
-{
-    rt_status rs;
-    for (Event &e : D->nrm_ev) if (!e.e) HIP_TRY(e.create());
-    if (!mb.f.p && (rs = mb.f.upload(m.f.data(), m.f.size() * 4))) return rs;
-    if (mb.nadj_off.p && mb.nadj_corner.p) return RT_OK;
-    const size_t nvn = m.vn.size() / 3;
-    std::vector<uint32_t> off(nvn + 1), corner(m.fn.size());
-    mesh_normal_adjacency(m.fn.data(), m.fn.size() / 3, nvn, off.data(), corner.data());
-    if ((rs = mb.nadj_corner.upload(corner.data(), corner.size() * 4))) return rs;
-    return mb.nadj_off.upload(off.data(), off.size() * 4);
-}
-static rt_status enqueue_mesh_normals(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
-{
-    MeshNormalsRequest N = {};
-    N.v = (const float *)mb.v.p; N.f = (const uint32_t *)mb.f.p;
-    N.nadj_off = (const uint32_t *)mb.nadj_off.p; N.nadj_corner = (const uint32_t *)mb.nadj_corner.p;
-    N.n_normals = (uint32_t)(m.vn.size() / 3); N.vn = (float *)mb.vn.p;
-    HIP_TRY(hipEventRecord(D->nrm_ev[0], D->stream));
-    HIP_TRY(rtk_launch_mesh_normals(D->stream, N));
-    HIP_TRY(hipEventRecord(D->nrm_ev[1], D->stream));
-    D->nrm_timed = true;
-    return RT_OK;
-}
-
-static rt_status refit_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
-                                      rt_mesh_quality *quality)
-{
-    HIP_TRY(hipSetDevice(D->device));
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
-    rt_status rs;
-    if ((rs = motion_wait_host(D->device))) return rs;                                      // ... or k_motion_mesh walking it
-    const size_t nf = m.f.size() / 3;
-    if ((size_t)mesh >= D->mesh_bufs.size() || D->mesh_bufs[mesh].slot_face.size() != nf || objs.size() != (size_t)D->scene.n_objects)
-        return fail(RT_ERR_STATE, "rt_scene_update_mesh_vertices: device %d does not hold mesh %d as the scene has it", D->device, mesh);
-    DevMeshBufs &mb = D->mesh_bufs[mesh];
-    hipStream_t st = D->stream;
-    for (Event &e : D->upd_ev) if (!e.e) HIP_TRY(e.create());
-    const bool first = mb.vn.p == nullptr;
-    // SMOOTH mode and no normals brought: the device computes them from the vertices it is about to be sent
-    const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;
-    if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
-    if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
-    // the store's normals are about to be read: never stale ones over what k_mesh_normals wrote here (the first time they are
-    // the values the kernel's kept normals keep)
-    if (first || normals_changed) ensure_normals(m);
-    // the previous positions follow the store: uploaded from it ahead of the new vertices, in the update's stream, by a flagged
-    // update; released by an unflagged one (nothing is allocated, copied or freed for a mesh that never used the flag)
-    if (m.v_prev.empty()) mb.v_prev.release();
-    else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
-    HIP_TRY(hipEventRecord(D->upd_ev[0], st));
-    if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
-    if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
-    if (smooth && (rs = enqueue_mesh_normals(D, m, mb))) return rs;
-    HIP_TRY(hipEventRecord(D->upd_ev[1], st));
-    MeshRefitRequest R = {};
-    R.v = (const float *)mb.v.p; R.vn = (const float *)mb.vn.p;
-    R.slot_idx = (const uint32_t *)mb.slot_idx.p; R.n_slots = (uint32_t)nf;
-    R.tris = (DevTri *)mb.tris.p; R.nrm = (float *)mb.nrm.p; R.nodes = (DevBvhNode *)mb.nodes.p;
-    R.level_nodes = (const uint32_t *)mb.level_nodes.p; R.level_off = mb.level_off.data(); R.n_levels = (int)mb.level_off.size() - 1;
-    R.after_retri = D->upd_ev[2];
-    HIP_TRY(rtk_launch_mesh_refit(st, R));
-    HIP_TRY(hipEventRecord(D->upd_ev[3], st));
-    D->upd_levels = R.n_levels;
-    HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), m.root_box, 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
-    if (quality && (rs = enqueue_mesh_cost(D, mb))) return rs;      // the refitted tree, measured behind the refit on the same stream
-    HIP_TRY(hipStreamSynchronize(st));
-    return quality ? finish_mesh_cost(D, mb, quality) : RT_OK;
-}
-
-rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality)
-{
-    rt::MeshData &m = s->data.meshes[mesh];
-    bool any = false, measured = false;
-    if (quality) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
-    for (DeviceState *D : s->devs) any = any || D->scene_valid;
-    if (!any) return RT_OK;
-    std::vector<DevObject> objs;
-    std::vector<DevObjectBack> backs;
-    std::vector<int32_t> node_mat;
-    rt_status st = lower_objects(s->data, objs, backs, node_mat);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    rt_status ret = RT_OK;
-    for (DeviceState *D : s->devs) {
-        if (!D->scene_valid) continue;
-        // a device another call is using, or one the update fails on, lowers the scene again at its next use instead
-        DeviceClaim claim(D);
-        rt_status r = st;
-        if (!r && claim.ok) {
-            // every device holds the same tree (the same host build, the same exact refit): the first one that refits measures it
-            r = refit_mesh_on_device(D, m, mesh, normals_changed, objs, quality && !measured ? quality : nullptr);
-            measured = measured || !r;
-        }
-        if (r || !claim.ok) D->scene_valid = false;
-        if (r && !ret) ret = r;
-    }
-    (void)hipSetDevice(cur);
-    // no device got as far as a measurement (all in use, or failed: they lower the scene again at their next use)
-    if (quality && !measured) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
-    return ret;
-}
-
-// ---- mesh tree quality (rt_mi355x.h, "mesh tree quality") ------------------------------------------------------------------
-// the host mirror: bvh_cost_host of rt_bvh_cost.h, the functions k_bvh_cost is made of, behind the ABI's argument checks
-extern "C" rt_status rt_device_bvh_cost(const void *nodes, uint64_t n_nodes, uint32_t root_ref, double *cost, uint32_t *flags)
-{
-    if (!cost || !flags) return fail(RT_ERR_ARG, "rt_device_bvh_cost: NULL argument");
-    if (!(root_ref & RT_COST_LEAF)) {
-        if (root_ref >= n_nodes) return fail(RT_ERR_ARG, "rt_device_bvh_cost: root_ref names node %u of %llu", root_ref, (unsigned long long)n_nodes);
-        if (!nodes) return fail(RT_ERR_ARG, "rt_device_bvh_cost: nodes is NULL");
-        if (n_nodes > (1ull << 28)) return fail(RT_ERR_ARG, "rt_device_bvh_cost: %llu node records (a mesh has at most 2^28)", (unsigned long long)n_nodes);
-    }
-    bvh_cost_host(nodes, n_nodes, root_ref, cost, flags);
-    return RT_OK;
-}
-
-// The measurement of mb's tree as it sits on D, queued on D's stream (the caller has claimed D and synchronises the stream before
-// finish_mesh_cost): k_bvh_cost, then the block sums and the root's record to the host.  A mesh that is one leaf has nothing to launch.
-static rt_status enqueue_mesh_cost(DeviceState *D, DevMeshBufs &mb)
-{
-    hipStream_t st = D->stream;
-    for (Event &e : D->cost_ev) if (!e.e) HIP_TRY(e.create());
-    HIP_TRY(hipEventRecord(D->cost_ev[0], st));
-    if (!(mb.root_ref & RT_COST_LEAF)) {
-        const uint64_t n_nodes = mb.level_off.back(), n_blocks = bvh_cost_blocks(n_nodes);
-        rt_status rs;
-        if ((rs = mb.cost_partials.ensure((n_blocks + 1) * sizeof(double)))) return rs;
-        mb.cost_host.resize(n_blocks + 1 + sizeof(DevBvhNode) / sizeof(double));
-        BvhCostRequest R = {};
-        R.nodes = (const DevBvhNode *)mb.nodes.p; R.n_nodes = (uint32_t)n_nodes; R.partials = (double *)mb.cost_partials.p;
-        HIP_TRY(rtk_launch_bvh_cost(st, R));
-#if RT_COST_FOLD_DEVICE
-        HIP_TRY(hipMemcpyAsync(mb.cost_host.data() + n_blocks, (const double *)mb.cost_partials.p + n_blocks, sizeof(double), hipMemcpyDeviceToHost, st));
-#else
-        HIP_TRY(hipMemcpyAsync(mb.cost_host.data(), mb.cost_partials.p, n_blocks * sizeof(double), hipMemcpyDeviceToHost, st));
-#endif
-        HIP_TRY(hipMemcpyAsync(mb.cost_host.data() + n_blocks + 1, (const DevBvhNode *)mb.nodes.p + mb.root_ref, sizeof(DevBvhNode), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipEventRecord(D->cost_ev[1], st));
-    return RT_OK;
-}
-// ... and, the stream synchronised, what it says: the fold of the block sums in index order, the root box, the cost and its ratio
-static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh_quality *q)
-{
-    uint32_t flags = 0;
-    if (mb.root_ref & RT_COST_LEAF) bvh_cost_host(nullptr, 0, mb.root_ref, &q->cost, &flags);
-    else {
-        const uint64_t n_blocks = bvh_cost_blocks(mb.level_off.back());
-#if RT_COST_FOLD_DEVICE
-        const double S = mb.cost_host[n_blocks];
-#else
-        const double S = bvh_cost_fold(mb.cost_host.data(), n_blocks);
-#endif
-        bvh_cost_finish(S, bvh_cost_root_half_area((const float *)(mb.cost_host.data() + n_blocks + 1)), &q->cost, &flags);
-    }
-    q->built_cost = mb.built_cost;
-    if (flags || mb.built_flags) { q->flags = RT_MESH_QUALITY_DEGENERATE; q->cost = 0.0; q->ratio = 1.0; }
-    else { q->flags = 0; q->ratio = q->cost / q->built_cost; }
-    HIP_TRY(hipEventElapsedTime(&q->measure_ms, D->cost_ev[0], D->cost_ev[1]));
-    return RT_OK;
-}
-
-// ---- device tree build (rt_mi355x.h, "device tree build") ---------------------------------------------------------------------
-// the limit on a device-built tree's stack_need: what the kernels provide, or less under the test hook RT_LBVH_STACK_CAP (read at call time)
-static int lbvh_stack_cap()
-{
-    int cap = RT_BVH_LDS + RT_BVH_SPILL;
-    if (const char *e = getenv("RT_LBVH_STACK_CAP")) { const long v = strtol(e, nullptr, 10); if (v >= 0 && v < cap) cap = (int)v; }
-    return cap;
-}
-
-// One device's share of rt_scene_update_mesh_vertices_build, modelled on refit_mesh_on_device: the same waits, the same uploads,
-// then the tree built from the vertices just uploaded (rt_bvh_build.hip) in place of the refit, the slots written in its order, and
-// everything that follows a tree's topology set again -- the record count and DevMesh::nodes / root_ref, slot_face, level_off and
-// level_nodes, stack_need with DevScene::max_bvh_depth and the spill buffers, built_cost.  Two host synchronisations: one for
-// the record count, the levels and stack_need (the cost launch and the fallback decision need them), one at the end.
-// *fell_back: the tree needs more stack than `cap`; the device is left for the caller to invalidate.
-static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
-                                      int cap, rt_mesh_build_info *info, bool *fell_back)
-{
-    HIP_TRY(hipSetDevice(D->device));
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
-    rt_status rs;
-    if ((rs = motion_wait_host(D->device))) return rs;                                      // ... or k_motion_mesh walking it
-    const size_t nf = m.f.size() / 3;
-    if ((size_t)mesh >= D->mesh_bufs.size() || D->mesh_bufs[mesh].slot_face.size() != nf || objs.size() != (size_t)D->scene.n_objects)
-        return fail(RT_ERR_STATE, "rt_scene_update_mesh_vertices_build: device %d does not hold mesh %d as the scene has it", D->device, mesh);
-    DevMeshBufs &mb = D->mesh_bufs[mesh];
-    MeshBuildBufs &B = D->build;
-    hipStream_t st = D->stream;
-    for (Event &e : B.ev) if (!e.e) HIP_TRY(e.create());
-    const bool first = mb.vn.p == nullptr, first_build = mb.fn.p == nullptr;      // (f alone may be there already: k_mesh_normals reads it too)
-    const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;      // as in refit_mesh_on_device
-    const bool textured = mb.tex.p != nullptr && !m.vt.empty() && m.ft.size() == m.f.size();
-    if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
-    if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
-    if (first || normals_changed) ensure_normals(m);
-    if (m.v_prev.empty()) mb.v_prev.release();
-    else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
-    if (first_build) {
-        if ((rs = mb.f.ensure(m.f.size() * 4)) || (rs = mb.fn.ensure(m.fn.size() * 4))) return rs;
-        if (textured && ((rs = mb.ft.ensure(m.ft.size() * 4)) || (rs = mb.vt.ensure(m.vt.size() * 4)))) return rs;
-    }
-    // the scratch, and room for the records: fewer than nf (a record stands for a binary node with more than four keys beneath it)
-    const uint32_t blocks = (uint32_t)((nf + 255) / 256);
-    const size_t sort_bytes = rtk_mesh_build_sort_bytes((uint32_t)nf);
-    if ((rs = B.cbox.ensure(((size_t)blocks + 1) * 24)) || (rs = B.keys[0].ensure(nf * 8)) || (rs = B.keys[1].ensure(nf * 8)) || (rs = B.sort_tmp.ensure(sort_bytes)) ||
-        (rs = B.bin.ensure(nf * sizeof(LbvhBin))) || (rs = B.parent.ensure(nf * 4)) || (rs = B.visit.ensure(nf * 4)) || (rs = B.rec_bin.ensure(nf * 4)) ||
-        (rs = B.rec_held.ensure(nf * 4)) || (rs = B.result.ensure(RT_LBVH_RESULT_WORDS * 4)) || (rs = B.slot_face.ensure(nf * 4))) return rs;
-    if (nf > RT_LBVH_LEAF_TRIS && (rs = mb.nodes.ensure(nf * sizeof(DevBvhNode)))) return rs;      // (may move: DevMesh::nodes is set again below)
-    if ((rs = mb.level_nodes.ensure(nf * 4))) return rs;
-    HIP_TRY(hipEventRecord(B.ev[0], st));
-    if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
-    if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
-    if (first_build) {
-        HIP_TRY(hipMemcpyAsync(mb.f.p, m.f.data(), m.f.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(mb.fn.p, m.fn.data(), m.fn.size() * 4, hipMemcpyHostToDevice, st));
-        if (textured) {
-            HIP_TRY(hipMemcpyAsync(mb.ft.p, m.ft.data(), m.ft.size() * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(mb.vt.p, m.vt.data(), m.vt.size() * 4, hipMemcpyHostToDevice, st));
-        }
-    }
-    if (smooth && (rs = enqueue_mesh_normals(D, m, mb))) return rs;      // k_mesh_retri, behind the build, copies them into the slots
-    HIP_TRY(hipEventRecord(B.ev[1], st));
-    MeshBuildRequest R = {};
-    R.v = (const float *)mb.v.p; R.f = (const uint32_t *)mb.f.p; R.fn = (const uint32_t *)mb.fn.p; R.n_faces = (uint32_t)nf;
-    if (textured) { R.vt = (const float *)mb.vt.p; R.ft = (const uint32_t *)mb.ft.p; R.tex = (float *)mb.tex.p; }
-    R.scratch.cbox = (float *)B.cbox.p; R.scratch.keys[0] = (unsigned long long *)B.keys[0].p; R.scratch.keys[1] = (unsigned long long *)B.keys[1].p;
-    R.scratch.sort_tmp = B.sort_tmp.p; R.scratch.sort_tmp_bytes = sort_bytes;
-    R.scratch.bin = (LbvhBin *)B.bin.p; R.scratch.parent = (uint32_t *)B.parent.p; R.scratch.visit = (uint32_t *)B.visit.p;
-    R.scratch.rec_bin = (uint32_t *)B.rec_bin.p; R.scratch.rec_held = (int32_t *)B.rec_held.p;
-    R.nodes = (DevBvhNode *)mb.nodes.p; R.result = (uint32_t *)B.result.p;
-    R.slot_face = (uint32_t *)B.slot_face.p; R.slot_idx = (uint32_t *)mb.slot_idx.p;
-    R.after_sort = B.ev[2]; R.after_boxes = B.ev[3]; R.after_collapse = B.ev[4];
-    int launches = 0;
-    HIP_TRY(rtk_launch_mesh_build(st, R, &launches));
-    MeshRefitRequest T = {};                                     // k_mesh_retri alone: no level of the old tree is refitted
-    T.v = R.v; T.vn = (const float *)mb.vn.p; T.slot_idx = R.slot_idx; T.n_slots = (uint32_t)nf;
-    T.tris = (DevTri *)mb.tris.p; T.nrm = (float *)mb.nrm.p;
-    HIP_TRY(rtk_launch_mesh_refit(st, T));
-    launches++;
-    HIP_TRY(hipEventRecord(B.ev[5], st));
-    B.result_host.assign(RT_LBVH_RESULT_WORDS, 0u);
-    B.slot_face_host.resize(nf);
-    HIP_TRY(hipMemcpyAsync(B.result_host.data(), B.result.p, RT_LBVH_RESULT_WORDS * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(B.slot_face_host.data(), B.slot_face.p, nf * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t n_nodes = B.result_host[0], levels = B.result_host[1];
-    const int need = (int)B.result_host[2];
-    if (info) {
-        info->n_nodes = n_nodes; info->n_slots = (uint32_t)nf; info->stack_need = need; info->levels = (int32_t)levels;
-        info->root_ref = nf <= RT_LBVH_LEAF_TRIS ? lbvh_leafref(0, (uint32_t)nf) : 0u;
-        info->launches = launches; info->syncs = 1;
-        HIP_TRY(hipEventElapsedTime(&info->upload_ms, B.ev[0], B.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&info->sort_ms, B.ev[1], B.ev[2]));
-        HIP_TRY(hipEventElapsedTime(&info->hierarchy_ms, B.ev[2], B.ev[3]));
-        HIP_TRY(hipEventElapsedTime(&info->collapse_ms, B.ev[3], B.ev[4]));
-        HIP_TRY(hipEventElapsedTime(&info->slots_ms, B.ev[4], B.ev[5]));
-    }
-    if (B.result_host[3] || need > cap || n_nodes > nf || levels > RT_LBVH_MAX_LEVELS) { *fell_back = true; return RT_OK; }
-    // what follows the topology, on the host: slot order, root, need, the levels as the refit wants them (deepest first; numbering
-    // is breadth-first, so depth d is the index range [at[d], at[d + 1]) and level_nodes is those ranges in reverse order)
-    const uint32_t *at = B.result_host.data() + 4;
-    mb.slot_face = B.slot_face_host;
-    mb.root_ref = nf <= RT_LBVH_LEAF_TRIS ? lbvh_leafref(0, (uint32_t)nf) : 0u;
-    mb.stack_need = need;
-    mb.level_off.assign((size_t)levels + 1, 0u);
-    B.level_nodes_host.resize(n_nodes);
-    for (uint32_t k = 0, w = 0; k < levels; k++) {
-        const uint32_t d = levels - 1 - k;
-        for (uint32_t i = at[d]; i < at[d + 1]; i++) B.level_nodes_host[w++] = i;
-        mb.level_off[k + 1] = mb.level_off[k] + (at[d + 1] - at[d]);
-    }
-    if (n_nodes) HIP_TRY(hipMemcpyAsync(mb.level_nodes.p, B.level_nodes_host.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
-    DevMesh dm;
-    memset(&dm, 0, sizeof dm);
-    dm.nodes = (const DevBvhNode *)mb.nodes.p; dm.tris = (const DevTri *)mb.tris.p; dm.nrm = (const float *)mb.nrm.p;
-    dm.tex = textured ? (const float *)mb.tex.p : nullptr;
-    dm.root_ref = mb.root_ref; dm.n_tris = (uint32_t)nf;
-    memcpy(dm.root_box, m.root_box, 24);
-    HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh), &dm, sizeof(DevMesh), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
-    if (need > D->scene.max_bvh_depth) {                        // the spill buffers come into being as in upload_scene and ensure_workspace
-        D->scene.max_bvh_depth = need;
-        if (need > RT_BVH_LDS) {
-            if ((rs = D->bvh_spill.ensure(SPILL_BYTES))) return rs;
-            D->scene.bvh_spill = (uint32_t *)D->bvh_spill.p;
-            for (Workspace &w : D->ws) if (w.samples && (rs = w.bvh_spill.ensure(SPILL_BYTES))) return rs;
-        }
-    }
-    D->upd_levels = -1;                                         // (rt_scene_mesh_update_ms speaks of refits)
-    if ((rs = enqueue_mesh_cost(D, mb))) return rs;
-    HIP_TRY(hipStreamSynchronize(st));
-    rt_mesh_quality q = {};
-    mb.built_cost = 1.0; mb.built_flags = 0;
-    if ((rs = finish_mesh_cost(D, mb, &q))) return rs;
-    mb.built_cost = q.cost; mb.built_flags = (q.flags & RT_MESH_QUALITY_DEGENERATE) ? RT_COST_DEGENERATE : 0u;
-    if (info) { info->cost = q.cost; info->cost_ms = q.measure_ms; info->launches = launches + (n_nodes ? 1 : 0); info->syncs = 2; }
-    return RT_OK;
-}
-
-rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info)
-{
-    rt::MeshData &m = s->data.meshes[mesh];
-    rt_mesh_build_info none = {};
-    none.struct_size = sizeof none; none.flags = RT_MESH_BUILD_NOT_ON_DEVICE;
-    *info = none;
-    bool any = false, reported = false, fell_back = false;
-    for (DeviceState *D : s->devs) any = any || D->scene_valid;
-    if (!any) return RT_OK;
-    std::vector<DevObject> objs;
-    std::vector<DevObjectBack> backs;
-    std::vector<int32_t> node_mat;
-    rt_status st = lower_objects(s->data, objs, backs, node_mat);
-    const int cap = lbvh_stack_cap();
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    rt_status ret = RT_OK;
-    for (DeviceState *D : s->devs) {
-        if (!D->scene_valid) continue;
-        // a device another call is using, or one the build fails on, lowers the scene again at its next use instead
-        DeviceClaim claim(D);
-        rt_status r = st;
-        if (!r && claim.ok && !fell_back) {
-            rt_mesh_build_info mine = none;
-            r = build_mesh_on_device(D, m, mesh, normals_changed, objs, cap, &mine, &fell_back);
-            if (!r && !reported) { *info = mine; info->flags = fell_back ? RT_MESH_BUILD_FELL_BACK : RT_MESH_BUILD_ON_DEVICE; reported = true; }
-        }
-        if (r || !claim.ok || fell_back) D->scene_valid = false;
-        if (r && !ret) ret = r;
-    }
-    (void)hipSetDevice(cur);
-    // the same mesh gives the same tree on every device: one that does not fit fits nowhere, and the call takes REBUILD's path
-    if (fell_back) { s->invalidate(true, false); info->flags = RT_MESH_BUILD_FELL_BACK; }
-    return ret;
-}
-
-extern "C" rt_status rt_scene_mesh_quality(rt_scene *s, int device, int32_t mesh, rt_mesh_quality *out)
-{
-    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_quality: NULL argument");
-    if (out->struct_size != sizeof(rt_mesh_quality))
-        return fail(RT_ERR_ARG, "rt_scene_mesh_quality: rt_mesh_quality.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_quality));
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_quality: mesh %d was never set", mesh);
-    }
-    DeviceState *D = nullptr;
-    rt_status st = prepare_device(s, device, &D);
-    if (st) return st;
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_quality: another call on this scene is using device %d", device);
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
-    DevMeshBufs &mb = D->mesh_bufs[mesh];
-    if ((st = enqueue_mesh_cost(D, mb))) return st;
-    HIP_TRY(hipStreamSynchronize(D->stream));
-    return finish_mesh_cost(D, mb, out);
-}
-
-extern "C" rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out)
-{
-    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_update_ms: NULL argument");
-    if (out->struct_size != sizeof(rt_mesh_update_ms))
-        return fail(RT_ERR_ARG, "rt_scene_mesh_update_ms: rt_mesh_update_ms.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_update_ms));
-    DeviceState *D = find_device_state(s, device);
-    if (!D || D->upd_levels < 0) return fail(RT_ERR_STATE, "rt_scene_mesh_update_ms: device %d has not updated a mesh in place", device);
-    HIP_TRY(hipEventElapsedTime(&out->upload, D->upd_ev[0], D->upd_ev[1]));
-    HIP_TRY(hipEventElapsedTime(&out->retri, D->upd_ev[1], D->upd_ev[2]));
-    HIP_TRY(hipEventElapsedTime(&out->refit, D->upd_ev[2], D->upd_ev[3]));
-    out->level_launches = D->upd_levels;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms)
-{
-    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_normals_ms: NULL argument");
-    DeviceState *D = find_device_state(s, device);
-    if (!D || !D->nrm_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_normals_ms: device %d has not computed a mesh's normals", device);
-    HIP_TRY(hipEventElapsedTime(ms, D->nrm_ev[0], D->nrm_ev[1]));
-    return RT_OK;
-}
-
-extern "C" rt_status rt_scene_mesh_device_read(rt_scene *s, int device, int32_t mesh, rt_device_bvh_info *info, void *nodes, uint64_t nodes_cap,
-                                               uint32_t *slot_face, uint64_t slots_cap, float *tris, float *nrm, float root_box[6])
-{
-    if (!s || !info) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: NULL argument");
-    if (info->struct_size != sizeof(rt_device_bvh_info))
-        return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: rt_device_bvh_info.struct_size is %u, this library's is %zu", info->struct_size, sizeof(rt_device_bvh_info));
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: mesh %d was never set", mesh);
-    }
-    DeviceState *D = nullptr;
-    rt_status st = prepare_device(s, device, &D);
-    if (st) return st;
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_device_read: another call on this scene is using device %d", device);
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
-    const DevMeshBufs &mb = D->mesh_bufs[mesh];
-    const size_t n_slots = mb.slot_face.size(), n_nodes = mb.level_off.empty() ? 0 : mb.level_off.back();
-    if (nodes && nodes_cap < n_nodes) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: room for %llu node records, %zu needed", (unsigned long long)nodes_cap, n_nodes);
-    if ((slot_face || tris || nrm) && slots_cap < n_slots) return fail(RT_ERR_ARG, "rt_scene_mesh_device_read: room for %llu triangle slots, %zu needed", (unsigned long long)slots_cap, n_slots);
-    HIP_TRY(hipStreamSynchronize(D->stream));
-    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, mb.nodes.p, n_nodes * sizeof(DevBvhNode), hipMemcpyDeviceToHost));
-    if (tris) HIP_TRY(hipMemcpy(tris, mb.tris.p, n_slots * sizeof(DevTri), hipMemcpyDeviceToHost));
-    if (nrm) HIP_TRY(hipMemcpy(nrm, mb.nrm.p, n_slots * 36, hipMemcpyDeviceToHost));
-    if (root_box) HIP_TRY(hipMemcpy(root_box, (const char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), 24, hipMemcpyDeviceToHost));
-    if (slot_face) memcpy(slot_face, mb.slot_face.data(), n_slots * 4);
-    info->n_nodes = (uint32_t)n_nodes; info->n_slots = (uint32_t)n_slots;
-    info->root_ref = mb.root_ref; info->stack_need = mb.stack_need;
-    info->bvh_lds = RT_BVH_LDS; info->bvh_stack = RT_BVH_STACK; info->bvh_spill = RT_BVH_SPILL;
-    info->spill_blocks = RT_SPILL_BLOCKS; info->block = RT_BLOCK;
-    return RT_OK;
-}
-
-// the previous positions of one mesh as they sit on `device`, with rt_scene_mesh_device_read's discipline
-extern "C" rt_status rt_scene_mesh_device_previous(rt_scene *s, int device, int32_t mesh, float *v_prev, uint64_t nv_cap, uint32_t *nv_out)
-{
-    if (!s || !nv_out) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: NULL argument");
-    size_t nv = 0;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (mesh < 0 || (size_t)mesh >= s->data.meshes.size() || s->data.meshes[mesh].f.empty()) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: mesh %d was never set", mesh);
-        nv = s->data.meshes[mesh].v.size() / 3;
-    }
-    DeviceState *D = nullptr;
-    rt_status st = prepare_device(s, device, &D);
-    if (st) return st;
-    DeviceClaim claim(D);
-    if (!claim.ok) return fail(RT_ERR_STATE, "rt_scene_mesh_device_previous: another call on this scene is using device %d", device);
-    if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));
-    const DevMeshBufs &mb = D->mesh_bufs[mesh];
-    if (!mb.v_prev.p) { *nv_out = 0; return RT_OK; }
-    if (v_prev && nv_cap < nv) return fail(RT_ERR_ARG, "rt_scene_mesh_device_previous: room for %llu vertices, %zu needed", (unsigned long long)nv_cap, nv);
-    HIP_TRY(hipStreamSynchronize(D->stream));
-    if (v_prev) HIP_TRY(hipMemcpy(v_prev, mb.v_prev.p, nv * 12, hipMemcpyDeviceToHost));
-    *nv_out = (uint32_t)nv;
     return RT_OK;
 }
 

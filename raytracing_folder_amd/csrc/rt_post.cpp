@@ -691,7 +691,7 @@ static rt_status scene_motion_on_device(const char *name, rt_scene *s, int shade
     std::vector<DevNodeMotion> table, from;
     motion_table(nodes.data(), prev_nodes, n_nodes, table);
     motion_from_table(prev_nodes ? prev_nodes : nodes.data(), n_nodes, from);
-    // a node is a mesh node while its mesh holds previous positions on this device (they follow the store: rt_lower.cpp)
+    // a node is a mesh node while its mesh holds previous positions on this device (they follow the store: rt_lower.cpp, rt_mesh_update.cpp)
     std::vector<DevMotionMeshNode> mesh_nodes((size_t)n_nodes);
     for (int32_t i = 0; i < n_nodes; i++) {
         DevMotionMeshNode &m = mesh_nodes[i];
