@@ -114,7 +114,17 @@ typedef struct rt_photon {
 
 /* Textures (FIN/include/texture.h, FIN/texture.cpp, FIN/include/scene.h:323-434).
  * RT_TEX_FILE: width x height RGB8 texels at texel_offset (bytes) of the texel array, sampled
- * bilinearly with tiling (TextureFile::Sample); RT_TEX_CHECKER: TextureChecker (color1/color2). */
+ * bilinearly with tiling (TextureFile::Sample); RT_TEX_CHECKER: TextureChecker (color1/color2).
+ *
+ * Three texture coordinates are undefined in the reference (a NaN, then a NaN converted to int); the library defines them,
+ * and agrees with the reference wherever the reference is defined:
+ *  - The sphere's v = 0.5 + asin(p.z) / pi is taken from the un-normalised float hit point p, whose |p.z| rounding lifts
+ *    above 1 next to a pole: the argument of asin is clamped to [-1, 1], so such a hit has the pole's v.
+ *  - The environment coordinate of a direction straight along +-z, where dir.x / (|dir.x| + |dir.y|) is 0/0, takes
+ *    x = y = 0, which is the centre (0.5, 0.5) of the environment map; the argument of its asinf is clamped to [-1, 1] too.
+ *  - A lookup (file or checker) at a coordinate with a component that is not finite -- a singular map transform can still
+ *    make one -- returns black, as RT_MAP_EMPTY does.  Coordinates of magnitude >= 2^31 remain out of scope: their
+ *    conversion to int is as undefined here as in the reference. */
 #define RT_TEX_FILE    1
 #define RT_TEX_CHECKER 2
 typedef struct rt_texture {

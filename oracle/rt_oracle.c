@@ -167,11 +167,13 @@ void orc_color24(const float rgb[3], uint8_t out[3])
 }
 
 /* ---- primitives -------------------------------------------------------------------------- */
-/* sphere texture coordinate, FIN/include/objects.h:49-51: atan2/asin on floats promote to double */
+/* sphere texture coordinate, FIN/include/objects.h:49-51: atan2/asin on floats promote to double.  p is the
+ * un-normalised hit point: next to a pole rounding lifts |p.z| above 1, where the reference's asin is NaN; the
+ * library clamps the argument (rt_mi355x.h, "Textures"), which is the identity wherever the reference is defined */
 static void sphere_uvw(v3 p, float uvw[3])
 {
     uvw[0] = (float)(0.5 - atan2(p.x, p.y) / (2 * M_PI));
-    uvw[1] = (float)(0.5 + asin(p.z) / M_PI);
+    uvw[1] = (float)(0.5 + asin(fmin(1.0, fmax(-1.0, (double)p.z))) / M_PI);
     uvw[2] = 0;
 }
 
@@ -632,6 +634,8 @@ static v3 tile_clamp(v3 uvw)
 /* TextureFile::Sample (FIN/texture.cpp:95-121), TextureChecker::Sample (:125-133) */
 void orc_texture_sample(const rt_texture *t, const uint8_t *texels, const float uvw_[3], float rgb[3])
 {
+    /* a coordinate that is not finite samples black (rt_mi355x.h): the reference converts it to int, which is undefined */
+    if (!(isfinite(uvw_[0]) && isfinite(uvw_[1]) && isfinite(uvw_[2]))) { rgb[0] = rgb[1] = rgb[2] = 0; return; }
     v3 u = tile_clamp(v3p(uvw_));
     if (t->type == RT_TEX_CHECKER) {
         const float *c = (u.x <= 0.5f) ? (u.y <= 0.5f ? t->color1 : t->color2) : (u.y <= 0.5f ? t->color2 : t->color1);
@@ -669,9 +673,14 @@ void orc_texmap_transform(const rt_texmap *m, const float uvw[3], float out[3])
 /* the coordinate TexturedColor::SampleEnvironment looks up, scene.h:426-432 */
 void orc_environment_coord(const float dir[3], float uvw[3])
 {
+    /* where the reference is undefined the library defines (rt_mi355x.h): a direction straight along +-z (0/0 below) takes
+     * x = y = 0.  asinf is the reference's here, NaN beyond [-1, 1] as the golden vectors (tests/golden/texture.npz, which
+     * hold vectors that are no unit vectors) pin it: the clamp of its argument is environment_color's, which is where the
+     * library looks a (normalised) direction up */
     float z = asinf(-dir[2]) / (float)M_PI + 0.5f;
-    float x = dir[0] / (fabsf(dir[0]) + fabsf(dir[1]));
-    float y = dir[1] / (fabsf(dir[0]) + fabsf(dir[1]));
+    float l1 = fabsf(dir[0]) + fabsf(dir[1]);
+    float x = l1 == 0 ? 0.0f : dir[0] / l1;
+    float y = l1 == 0 ? 0.0f : dir[1] / l1;
     /* Point3(0.5,0.5,0) + z*(x*Point3(0.5,0.5,0) + y*Point3(-0.5,0.5,0)) */
     v3 a = vadd(vscale(V3(0.5f, 0.5f, 0), x), vscale(V3(-0.5f, 0.5f, 0), y));
     st3(uvw, vadd(V3(0.5f, 0.5f, 0.0f), vscale(a, z)));
@@ -691,6 +700,7 @@ void orc_textured_color(const orc_scene *s, const float color[3], const rt_texma
 static v3 environment_color(const orc_scene *s, v3 dir)
 {
     float uvw[3], c[3];
+    dir.z = -fminf(1.0f, fmaxf(-1.0f, -dir.z));          /* asinf's argument -dir.z clamped, written as the kernel writes it (rt_mi355x.h) */
     orc_environment_coord((const float *)&dir, uvw);
     orc_textured_color(s, s->env, s->env_map, uvw, c);
     return v3p(c);

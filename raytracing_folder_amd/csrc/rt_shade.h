@@ -104,9 +104,12 @@ template <bool TEX>
 __device__ V3 environment_color(const DevScene &S, V3 dir)
 {
     if (!TEX || S.env_map.texture == RT_MAP_NONE) return ld3(S.env);
-    const float z = asinf(-dir.z) / (float)M_PI + 0.5f;
-    const float x = dir.x / (fabsf(dir.x) + fabsf(dir.y));
-    const float y = dir.y / (fabsf(dir.x) + fabsf(dir.y));
+    // the library's two departures from the reference's undefined results (rt_mi355x.h): asinf's argument is clamped, and a ray
+    // straight along +-z (0/0 below) takes x = y = 0
+    const float z = asinf(fminf(1.0f, fmaxf(-1.0f, -dir.z))) / (float)M_PI + 0.5f;
+    const float l1 = fabsf(dir.x) + fabsf(dir.y);
+    const float x = l1 == 0 ? 0.0f : dir.x / l1;
+    const float y = l1 == 0 ? 0.0f : dir.y / l1;
     const V3 uvw = mk(0.5f, 0.5f, 0.0f) + (mk(0.5f, 0.5f, 0) * x + mk(-0.5f, 0.5f, 0) * y) * z;
     return textured_color(S, ld3(S.env), S.env_map, uvw);
 }

@@ -426,8 +426,9 @@ __device__ bool trace(const DevScene &S, V3 o, V3 d, float zinit, Hit &h, const 
             if (ANY) { cnt.occ = (uint32_t)oi + 1u; return true; }
             best = oi; bp = hp; bN = hN; bfront = fr;
             if (TEX && S.use_uvw) {
-                if (ob_type == RT_OBJ_SPHERE)               // objects.h:49-51, atan2/asin in double
-                    uvw = mk((float)(0.5 - atan2((double)hp.x, (double)hp.y) / (2 * M_PI)), (float)(0.5 + asin((double)hp.z) / M_PI), 0);
+                if (ob_type == RT_OBJ_SPHERE)               // objects.h:49-51, atan2/asin in double; hp is not normalised and rounding
+                                                            // lifts |hp.z| above 1 next to a pole: asin's argument is clamped (rt_mi355x.h)
+                    uvw = mk((float)(0.5 - atan2((double)hp.x, (double)hp.y) / (2 * M_PI)), (float)(0.5 + asin(fmin(1.0, fmax(-1.0, (double)hp.z))) / M_PI), 0);
                 else if (ob_type == RT_OBJ_PLANE) uvw = mk((hp.x + 1) / 2, (hp.y + 1) / 2, 0);    // objects.h:103
             }
         }
@@ -476,6 +477,8 @@ __device__ __forceinline__ V3 tile_clamp(V3 uvw)
 }
 __device__ V3 texture_sample(const rt_texture &t, const uint8_t *texels, V3 uvw)
 {
+    // a coordinate that is not finite (a singular map transform can make one) samples black, like RT_MAP_EMPTY: rt_mi355x.h
+    if (!(isfinite(uvw.x) && isfinite(uvw.y) && isfinite(uvw.z))) return mk(0, 0, 0);
     const V3 u = tile_clamp(uvw);
     if (t.type == RT_TEX_CHECKER) {
         const float *c = (u.x <= 0.5f) ? (u.y <= 0.5f ? t.color1 : t.color2) : (u.y <= 0.5f ? t.color2 : t.color1);
