@@ -1,6 +1,7 @@
 // rt_kernel_util.h -- the few helpers that more than one kernel translation unit (rt_kernels.hip through rt_trace.h, rt_trace.hip,
 // rt_resolve.hip, rt_gather.hip, rt_denoise.hip, ...) uses.  Device code, except grid_for, which the launch wrappers of three units
-// size their grids with.  Not a general utility header: a helper moves here when a second file needs it.
+// size their grids with.  Not a general utility header: a helper moves here when a second file needs it (what only the two
+// tile-gather stages share is in rt_tile_gather.h).
 #ifndef RT_KERNEL_UTIL_H
 #define RT_KERNEL_UTIL_H
 

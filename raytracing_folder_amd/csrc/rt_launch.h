@@ -1,7 +1,8 @@
 // rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_mesh_update.cpp, rt_photons.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_motion_mesh.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
-// as they stand here (members, order and types are the kernels' argument layout); everything else is host-side only.
+// as they stand here (members, order and types are the kernels' argument layout), MotionBlurRequest and DofRequest as a member of
+// their kernels' argument; everything else is host-side only.
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
 
@@ -203,36 +204,38 @@ struct BloomRequest {
     BloomPlan plan;
 };
 
-// One motion-blurred width x height frame (rt_motion_blur.hip; the definition: rt_mi355x.h, "motion blur").  The planes are the
-// caller's device pointers (out_tiles may be NULL), the parameters are validated by the caller.  tile_max and tile_nmax: the
-// rt_motion_blur's scratch, one float2 per tile each (tiles_x * tiles_y of them for this call's K).
-struct MotionBlurRequest {
+// What the requests of the two tile-gather stages (rt_tile_gather.h) start with: the frame, the tile size K and the taps N, the
+// tiles for this call's K, and the object's tile-max and neighbour-max planes (tiles_x * tiles_y entries each).
+struct TileGatherHead {
     int width, height, K, N;
     int tiles_x, tiles_y;               // ceil(width / K), ceil(height / K)
+    float *tile_max, *tile_nmax;
+};
+
+// One motion-blurred width x height frame (rt_motion_blur.hip; the definition: rt_mi355x.h, "motion blur").  The planes are the
+// caller's device pointers (out_tiles may be NULL), the parameters are validated by the caller.  tile_max and tile_nmax: the
+// rt_motion_blur's scratch, one float2 per tile each.
+struct MotionBlurRequest : TileGatherHead {
     float half_shutter;                 // h = 0.5f * shutter
     float two_over_n;                   // g = 2 / N
     float depth_extent;
     const float *rgb_linear, *motion, *z;
     float *out, *out_tiles;
-    float *tile_max, *tile_nmax;
 };
 
 // One defocused width x height frame (rt_dof.hip; the definition: rt_mi355x.h, "depth of field").  The planes are the caller's device
 // pointers (out_coc and out_tiles may be NULL), the parameters are validated by the caller.  A and focus are step 0's A and focus
 // distance; bx, by, u, v, l the camera quantities of step 1 (camera_setup's).  taps: step 5's table on the HOST, 2 N floats -- it
 // travels in the kernel argument.  coc: the rt_dof's (c, D) plane, one float2 per pixel; tile_max and tile_nmax: its two tile
-// planes, one float per tile each (tiles_x * tiles_y of them for this call's K).
+// planes, one float per tile each.
 #define RT_DOF_MAX_TAPS 64
-struct DofRequest {
-    int width, height, K, N;
-    int tiles_x, tiles_y;               // ceil(width / K), ceil(height / K)
+struct DofRequest : TileGatherHead {
     float A, focus, depth_extent;
     float bx, by, u, v, l;
     const float *taps;
     const float *rgb_linear, *z;
     float *out, *out_coc, *out_tiles;
     float2 *coc;
-    float *tile_max, *tile_nmax;
 };
 
 // One in-place update of a mesh on a device (rt_refit.hip; the definition: rt_mi355x.h, "mesh vertex updates").  Everything is the

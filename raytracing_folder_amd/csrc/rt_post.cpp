@@ -1007,20 +1007,72 @@ extern "C" rt_status rt_bloom_host(rt_bloom *b, rt_exposure *e, const rt_bloom_p
     return S.download({rgb, only});
 }
 
-// ---- motion blur ------------------------------------------------------------------------------------------------------------
-// An rt_motion_blur owns the tile-max and neighbour-max planes of one W x H stream of frames on its device -- sized for K = 2,
-// the most tiles a call can ask for -- and the event that orders a call behind the previous one on the same object.
-#define RT_MBLUR_MIN_K 2
-#define RT_MBLUR_MAX_K 32
-struct rt_motion_blur : StageObject { DevBuf tile_max, tile_nmax; void release() { tile_max.release(); tile_nmax.release(); } };
-
-static size_t mblur_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
+// ---- the tile-gather stages: what motion blur and depth of field share ------------------------------------------------------
+// Both cut the image into K x K tiles, K (max_blur, max_coc) in 2..32, and keep a tile-max and a neighbour-max plane.
+#define RT_TILE_MIN_K 2
+#define RT_TILE_MAX_K 32
+static size_t stage_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
 {
     const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
     if (tx) *tx = x;
     if (ty) *ty = y;
     return (size_t)x * (size_t)y;
 }
+namespace {
+// the two tile planes of an object: sized for K = 2, the most tiles a call can ask for
+struct TilePlanes {
+    DevBuf tile_max, tile_nmax;
+    rt_status ensure(int32_t w, int32_t h, size_t bytes_per_tile)
+    {
+        const size_t bytes = stage_tiles(w, h, RT_TILE_MIN_K, nullptr, nullptr) * bytes_per_tile;
+        rt_status rs = tile_max.ensure(bytes);
+        return rs ? rs : tile_nmax.ensure(bytes);
+    }
+    void release() { tile_max.release(); tile_nmax.release(); }
+};
+}
+// `field`: what the stage calls its K
+static rt_status check_tile_size(const char *name, const char *field, int32_t K)
+{
+    return K < RT_TILE_MIN_K || K > RT_TILE_MAX_K ? fail(RT_ERR_ARG, "%s: %s is %d, must be 2..32", name, field, K) : RT_OK;
+}
+static rt_status check_depth_extent(const char *name, float e)
+{
+    return !std::isfinite(e) || !(e >= 1e-3f) ? fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name) : RT_OK;
+}
+// no two of the (plane, bytes) that are given may share a byte; `why`: what the message says in brackets
+#define RT_GATHER_READS_NEIGHBOURS "out may not be rgb_linear: the gather reads neighbours"
+static rt_status check_planes_disjoint(const char *name, std::initializer_list<std::pair<const void *, size_t>> planes, const char *why)
+{
+    for (auto a = planes.begin(); a != planes.end(); a++)
+        for (auto b = a + 1; b != planes.end(); b++)
+            if (planes_overlap(a->first, a->second, b->first, b->second)) return fail(RT_ERR_ARG, "%s: planes overlap (%s)", name, why);
+    return RT_OK;
+}
+// rt_motion_blur_tiles and rt_dof_tiles
+static rt_status tiles_entry(const char *name, const char *field, int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
+{
+    rt_status st = check_image_dims(name, w, h);
+    if (!st && !(st = check_tile_size(name, field, K))) stage_tiles(w, h, K, tx, ty);
+    return st;
+}
+// the end of both _on_device functions: under the object's mutex the request's head, the wait, the launch and the record
+template <class T, class R, class L> static rt_status tile_stage_run(T *o, hipStream_t st, int sync, int32_t K, int32_t N, R &req, L launch)
+{
+    std::lock_guard<std::mutex> lk(o->mu);
+    req.width = o->w; req.height = o->h; req.K = K; req.N = N;
+    stage_tiles(o->w, o->h, K, &req.tiles_x, &req.tiles_y);
+    req.tile_max = (float *)o->tiles.tile_max.p; req.tile_nmax = (float *)o->tiles.tile_nmax.p;
+    rt_status rs = o->sync.wait(st);
+    if (rs) return rs;
+    HIP_TRY(launch(st, req));
+    return o->sync.settle(st, sync);
+}
+
+// ---- motion blur ------------------------------------------------------------------------------------------------------------
+// An rt_motion_blur owns the tile planes of one W x H stream of frames on its device, a float2 per tile, and the event that
+// orders a call behind the previous one on the same object.
+struct rt_motion_blur : StageObject { TilePlanes tiles; void release() { tiles.release(); } };
 
 extern "C" rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_motion_blur **out)
 {
@@ -1028,11 +1080,7 @@ extern "C" rt_status rt_motion_blur_create(int device, int32_t w, int32_t h, rt_
     *out = nullptr;
     rt_status st = check_image_size("rt_motion_blur_create", w, h);
     if (st) return st;
-    return stage_create("rt_motion_blur_create", device, w, h, out, [](rt_motion_blur &mb) {
-        const size_t bytes = mblur_tiles(mb.w, mb.h, RT_MBLUR_MIN_K, nullptr, nullptr) * 8;
-        rt_status rs = mb.tile_max.ensure(bytes);
-        return rs ? rs : mb.tile_nmax.ensure(bytes);
-    });
+    return stage_create("rt_motion_blur_create", device, w, h, out, [](rt_motion_blur &mb) { return mb.tiles.ensure(mb.w, mb.h, 8); });
 }
 
 extern "C" void rt_motion_blur_destroy(rt_motion_blur *mb) { stage_destroy(mb); }
@@ -1046,11 +1094,7 @@ extern "C" void rt_motion_blur_default_params(rt_motion_blur_params *p)
 
 extern "C" rt_status rt_motion_blur_tiles(int32_t w, int32_t h, int32_t max_blur, int32_t *tx, int32_t *ty)
 {
-    rt_status st = check_image_dims("rt_motion_blur_tiles", w, h);
-    if (st) return st;
-    if (max_blur < RT_MBLUR_MIN_K || max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "rt_motion_blur_tiles: max_blur is %d, must be 2..32", max_blur);
-    mblur_tiles(w, h, max_blur, tx, ty);
-    return RT_OK;
+    return tiles_entry("rt_motion_blur_tiles", "max_blur", w, h, max_blur, tx, ty);
 }
 
 // everything that can be refused without a device, for both entry points
@@ -1059,37 +1103,24 @@ static rt_status mblur_check(const char *name, const rt_motion_blur *mb, const r
     rt_status st = check_params_planes(name, "rt_motion_blur_params", p, "rt_motion_blur_planes", pl);
     if (st) return st;
     if (!std::isfinite(p->shutter) || !(p->shutter >= 0.0f) || p->shutter > 2.0f) return fail(RT_ERR_ARG, "%s: shutter must be finite and 0..2", name);
-    if (p->max_blur < RT_MBLUR_MIN_K || p->max_blur > RT_MBLUR_MAX_K) return fail(RT_ERR_ARG, "%s: max_blur is %d, must be 2..32", name, p->max_blur);
+    if ((st = check_tile_size(name, "max_blur", p->max_blur))) return st;
     if (p->samples < 3 || p->samples > 63 || !(p->samples & 1)) return fail(RT_ERR_ARG, "%s: samples is %d, must be odd and 3..63", name, p->samples);
-    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
+    if ((st = check_depth_extent(name, p->depth_extent))) return st;
     if (!pl->rgb_linear || !pl->motion || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, motion, z and out are required", name);
     // what needs the object comes last: without a device there is none, and everything above is still refused by name
     if (!mb) return fail(RT_ERR_ARG, "%s: the rt_motion_blur is NULL", name);
     const size_t n = (size_t)mb->w * (size_t)mb->h;
-    const struct { const void *p; size_t bytes; } planes[5] = {
-        {pl->rgb_linear, n * 12}, {pl->motion, n * 12}, {pl->z, n * 4}, {pl->out, n * 12},
-        {pl->out_tiles, mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8}};
-    for (int a = 0; a < 5; a++)
-        for (int b = a + 1; b < 5; b++)
-            if (planes_overlap(planes[a].p, planes[a].bytes, planes[b].p, planes[b].bytes))
-                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
-    return RT_OK;
+    return check_planes_disjoint(name, {{pl->rgb_linear, n * 12}, {pl->motion, n * 12}, {pl->z, n * 4}, {pl->out, n * 12},
+                                        {pl->out_tiles, stage_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8}}, RT_GATHER_READS_NEIGHBOURS);
 }
 
 static rt_status mblur_on_device(rt_motion_blur *mb, hipStream_t st, const rt_motion_blur_params *p, const rt_motion_blur_planes *pl, int sync)
 {
     HIP_TRY(hipSetDevice(mb->device));
     MotionBlurRequest R = {};
-    R.width = mb->w; R.height = mb->h; R.K = p->max_blur; R.N = p->samples;
-    mblur_tiles(mb->w, mb->h, p->max_blur, &R.tiles_x, &R.tiles_y);
     R.half_shutter = 0.5f * p->shutter; R.two_over_n = 2.0f / (float)p->samples; R.depth_extent = p->depth_extent;
     R.rgb_linear = pl->rgb_linear; R.motion = pl->motion; R.z = pl->z; R.out = pl->out; R.out_tiles = pl->out_tiles;
-    std::lock_guard<std::mutex> lk(mb->mu);
-    R.tile_max = (float *)mb->tile_max.p; R.tile_nmax = (float *)mb->tile_nmax.p;
-    rt_status rs = mb->sync.wait(st);
-    if (rs) return rs;
-    HIP_TRY(rtk_launch_motion_blur(st, R));
-    return mb->sync.settle(st, sync);
+    return tile_stage_run(mb, st, sync, p->max_blur, p->samples, R, rtk_launch_motion_blur);
 }
 
 extern "C" rt_status rt_motion_blur_device(rt_motion_blur *mb, void *hip_stream, const rt_motion_blur_params *p,
@@ -1105,7 +1136,7 @@ extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blu
     if (st) return st;
     HIP_TRY(hipSetDevice(mb->device));
     const size_t n = (size_t)mb->w * (size_t)mb->h;
-    const size_t tile_bytes = mblur_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8;
+    const size_t tile_bytes = stage_tiles(mb->w, mb->h, p->max_blur, nullptr, nullptr) * 8;
     HostPlanes S;
     const int rgb = S.in(host_planes->rgb_linear, n * 12), motion = S.in(host_planes->motion, n * 12), z = S.in(host_planes->z, n * 4);
     const int out = S.out(host_planes->out, n * 12), tiles = S.out(host_planes->out_tiles, tile_bytes);
@@ -1117,22 +1148,11 @@ extern "C" rt_status rt_motion_blur_host(rt_motion_blur *mb, const rt_motion_blu
 }
 
 // ---- depth of field -------------------------------------------------------------------------------------------------------
-// An rt_dof owns the (c, D) plane and the tile-max and neighbour-max planes of one W x H stream of frames on its device -- the
-// tile planes sized for K = 2, the most tiles a call can ask for -- and the event that orders a call behind the previous one on
-// the same object.
-#define RT_DOF_MIN_K 2
-#define RT_DOF_MAX_K 32
+// An rt_dof owns the (c, D) plane and the tile planes of one W x H stream of frames on its device, a float per tile, and the
+// event that orders a call behind the previous one on the same object.
 #define RT_DOF_MIN_N 8
 #define RT_DOF_MAX_FOCUS 1e20f
-struct rt_dof : StageObject { DevBuf coc, tile_max, tile_nmax; void release() { coc.release(); tile_max.release(); tile_nmax.release(); } };
-
-static size_t dof_tiles(int32_t w, int32_t h, int32_t K, int32_t *tx, int32_t *ty)
-{
-    const int32_t x = (w + K - 1) / K, y = (h + K - 1) / K;
-    if (tx) *tx = x;
-    if (ty) *ty = y;
-    return (size_t)x * (size_t)y;
-}
+struct rt_dof : StageObject { DevBuf coc; TilePlanes tiles; void release() { coc.release(); tiles.release(); } };
 
 // step 5's table: a Vogel spiral in double, rounded to float once per coordinate
 static void dof_tap_table(int32_t N, float *xy)
@@ -1151,10 +1171,8 @@ extern "C" rt_status rt_dof_create(int device, int32_t w, int32_t h, rt_dof **ou
     rt_status st = check_image_size("rt_dof_create", w, h);
     if (st) return st;
     return stage_create("rt_dof_create", device, w, h, out, [](rt_dof &d) {
-        const size_t bytes = dof_tiles(d.w, d.h, RT_DOF_MIN_K, nullptr, nullptr) * 4;
         rt_status rs = d.coc.ensure((size_t)d.w * (size_t)d.h * 8);
-        if (!rs) rs = d.tile_max.ensure(bytes);
-        return rs ? rs : d.tile_nmax.ensure(bytes);
+        return rs ? rs : d.tiles.ensure(d.w, d.h, 4);
     });
 }
 
@@ -1169,11 +1187,7 @@ extern "C" void rt_dof_default_params(rt_dof_params *p)
 
 extern "C" rt_status rt_dof_tiles(int32_t w, int32_t h, int32_t max_coc, int32_t *tx, int32_t *ty)
 {
-    rt_status st = check_image_dims("rt_dof_tiles", w, h);
-    if (st) return st;
-    if (max_coc < RT_DOF_MIN_K || max_coc > RT_DOF_MAX_K) return fail(RT_ERR_ARG, "rt_dof_tiles: max_coc is %d, must be 2..32", max_coc);
-    dof_tiles(w, h, max_coc, tx, ty);
-    return RT_OK;
+    return tiles_entry("rt_dof_tiles", "max_coc", w, h, max_coc, tx, ty);
 }
 
 extern "C" rt_status rt_dof_taps(int32_t samples, float *xy)
@@ -1190,9 +1204,9 @@ static rt_status dof_check(const char *name, const rt_dof *d, const rt_camera *c
     if (!cam) return fail(RT_ERR_ARG, "%s: the camera is NULL", name);
     rt_status st = check_params_planes(name, "rt_dof_params", p, "rt_dof_planes", pl);
     if (st) return st;
-    if (p->max_coc < RT_DOF_MIN_K || p->max_coc > RT_DOF_MAX_K) return fail(RT_ERR_ARG, "%s: max_coc is %d, must be 2..32", name, p->max_coc);
+    if ((st = check_tile_size(name, "max_coc", p->max_coc))) return st;
     if (p->samples < RT_DOF_MIN_N || p->samples > RT_DOF_MAX_TAPS) return fail(RT_ERR_ARG, "%s: samples is %d, must be 8..64", name, p->samples);
-    if (!std::isfinite(p->depth_extent) || !(p->depth_extent >= 1e-3f)) return fail(RT_ERR_ARG, "%s: depth_extent must be finite and at least 1e-3", name);
+    if ((st = check_depth_extent(name, p->depth_extent))) return st;
     if (!std::isfinite(p->aperture_scale) || !(p->aperture_scale >= 0.0f)) return fail(RT_ERR_ARG, "%s: aperture_scale must be finite and not negative", name);
     if (p->focus != 0.0f && !(p->focus > 0.0f && p->focus <= RT_DOF_MAX_FOCUS)) return fail(RT_ERR_ARG, "%s: focus must be 0 (the camera's focaldist) or in (0, 1e20]", name);
     if (!pl->rgb_linear || !pl->z || !pl->out) return fail(RT_ERR_ARG, "%s: rgb_linear, z and out are required", name);
@@ -1207,13 +1221,9 @@ static rt_status dof_check(const char *name, const rt_dof *d, const rt_camera *c
     if (!std::isfinite(*A)) return fail(RT_ERR_ARG, "%s: the camera's aperture in pixels (A) is not finite", name);
     if ((st = check_image_limit(name, cam->width, cam->height))) return st;
     const size_t n = (size_t)cam->width * (size_t)cam->height;
-    const struct { const void *p; size_t bytes; } planes[5] = {
-        {pl->rgb_linear, n * 12}, {pl->z, n * 4}, {pl->out, n * 12}, {pl->out_coc, n * 4},
-        {pl->out_tiles, dof_tiles(cam->width, cam->height, p->max_coc, nullptr, nullptr) * 4}};
-    for (int a_ = 0; a_ < 5; a_++)
-        for (int b = a_ + 1; b < 5; b++)
-            if (planes_overlap(planes[a_].p, planes[a_].bytes, planes[b].p, planes[b].bytes))
-                return fail(RT_ERR_ARG, "%s: planes overlap (out may not be rgb_linear: the gather reads neighbours)", name);
+    if ((st = check_planes_disjoint(name, {{pl->rgb_linear, n * 12}, {pl->z, n * 4}, {pl->out, n * 12}, {pl->out_coc, n * 4},
+                                           {pl->out_tiles, stage_tiles(cam->width, cam->height, p->max_coc, nullptr, nullptr) * 4}}, RT_GATHER_READS_NEIGHBOURS)))
+        return st;
     // what needs the object comes last: without a device there is none, and everything above is still refused by name
     if (!d) return fail(RT_ERR_ARG, "%s: the rt_dof is NULL", name);
     if (cam->width != d->w || cam->height != d->h)
@@ -1225,8 +1235,6 @@ static rt_status dof_on_device(rt_dof *d, hipStream_t st, const rt_camera *cam, 
 {
     HIP_TRY(hipSetDevice(d->device));
     DofRequest R = {};
-    R.width = d->w; R.height = d->h; R.K = p->max_coc; R.N = p->samples;
-    dof_tiles(d->w, d->h, p->max_coc, &R.tiles_x, &R.tiles_y);
     R.A = A; R.focus = fd; R.depth_extent = p->depth_extent;
     DevCamera dc;
     camera_setup(*cam, dc);
@@ -1235,12 +1243,8 @@ static rt_status dof_on_device(rt_dof *d, hipStream_t st, const rt_camera *cam, 
     dof_tap_table(p->samples, taps);
     R.taps = taps;
     R.rgb_linear = pl->rgb_linear; R.z = pl->z; R.out = pl->out; R.out_coc = pl->out_coc; R.out_tiles = pl->out_tiles;
-    std::lock_guard<std::mutex> lk(d->mu);
-    R.coc = (float2 *)d->coc.p; R.tile_max = (float *)d->tile_max.p; R.tile_nmax = (float *)d->tile_nmax.p;
-    rt_status rs = d->sync.wait(st);
-    if (rs) return rs;
-    HIP_TRY(rtk_launch_dof(st, R));
-    return d->sync.settle(st, sync);
+    R.coc = (float2 *)d->coc.p;                                 // (set once, by the create)
+    return tile_stage_run(d, st, sync, p->max_coc, p->samples, R, rtk_launch_dof);
 }
 
 extern "C" rt_status rt_dof_device(rt_dof *d, void *hip_stream, const rt_camera *cam, const rt_dof_params *p, const rt_dof_planes *device_planes, int sync)
@@ -1257,7 +1261,7 @@ extern "C" rt_status rt_dof_host(rt_dof *d, const rt_camera *cam, const rt_dof_p
     if (st) return st;
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)d->w * (size_t)d->h;
-    const size_t tile_bytes = dof_tiles(d->w, d->h, p->max_coc, nullptr, nullptr) * 4;
+    const size_t tile_bytes = stage_tiles(d->w, d->h, p->max_coc, nullptr, nullptr) * 4;
     HostPlanes S;
     const int rgb = S.in(host_planes->rgb_linear, n * 12), z = S.in(host_planes->z, n * 4);
     const int out = S.out(host_planes->out, n * 12), coc = S.out(host_planes->out_coc, n * 4), tiles = S.out(host_planes->out_tiles, tile_bytes);

@@ -476,6 +476,28 @@ def test_device_against_the_float64_transcription(case):
         assert a.tobytes() == b.tobytes()
 
 
+# (w, h, K) at the edges of the tile-gather geometry (csrc/rt_tile_gather.h; G = the tiles along a gather workgroup's square):
+# the smallest image; narrower than one tile, one tile column, G = 1; G = 8 with a ragged last square and tile in x and one tile
+# row; G = 3, a square of 15 pixels, ragged in both axes; the first K with G = 1, one workgroup of 81 pixels; everything divides;
+# one pixel over in both axes
+GEOMETRY = [(1, 1, 2), (3, 70, 32), (70, 3, 2), (33, 17, 5), (31, 33, 9), (64, 48, 8), (65, 49, 16)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", GEOMETRY, ids=lambda s: f"{s[0]}x{s[1]}-K{s[2]}")
+def test_device_at_the_edges_of_the_tile_geometry(shape):
+    w, h, K = shape
+    rgb, z, cam = frame(w, h, K)
+    ref = reference((w, h, K, 32))
+    with capi.DepthOfField(0, w, h) as d:
+        out, coc, tiles = d.apply(rgb, z, cam, return_coc=True, return_tiles=True, max_coc=K, samples=32)
+    assert coc.shape == ref["coc"].shape and coc.tobytes() == ref["coc"].tobytes()
+    assert tiles.shape == ref["tiles"].shape and tiles.tobytes() == ref["tiles"].tobytes()
+    worst = over_gate(out, ref)
+    print(f"dof {w}x{h} K {K}: worst error / gate {worst:.3f}")
+    assert worst <= 1.0
+
+
 @pytest.mark.gpu
 def test_exact_properties_on_the_device():
     import torch
