@@ -5,8 +5,12 @@
 //                  smooth normals, and the calls that read a mesh back from a device
 //   rt_photons.cpp the photon maps: their setters, the gather structures (upload_photons), the photon and caustic passes,
 //                  generate_photons, the global map's state (rt_photon_map.h) with its two device copies
-//   rt_render.cpp  render orchestration: working sets, run_pipeline, the render / packed / unpack entry points, jobs, the
+//   rt_render.cpp  render orchestration: working sets, run_pipeline, render_tiles, the image-plane render entry points, the
 //                  single-stage entry points
+//   rt_exchange.cpp  the multi-GPU tile exchange: the packed layouts and their size queries, the packed render and the unpack
+//                  entry points
+//   rt_jobs.cpp    asynchronous jobs: the rt_render_begin* entry points, progress / stop / wait / statistics / destroy (struct
+//                  rt_job itself is below: the orchestration of rt_render.cpp reads and writes it)
 //   rt_post.cpp    the image-space stages (denoise .. motion blur)
 // Everything here that has external linkage only so that these files can share it is hidden: the library's dynamic symbol
 // table does not know it.
@@ -16,6 +20,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -271,3 +276,73 @@ RT_HIDDEN rt_status ensure_cell_start(DeviceState *D, bool caustic, int k, float
 RT_HIDDEN rt_status generate_photons(rt_scene *s, int device, uint32_t max_photons, int photon_bounce, uint32_t seed, const char *dat_path,
                                      rt_setup_ms *ms_out, bool own_job);
 RT_HIDDEN rt_status order_after_pending(DeviceState *D, hipStream_t st);                        // rt_render.cpp
+
+// ---- render outputs (rt_render.cpp, rt_exchange.cpp, rt_jobs.cpp) -------------------------------------------
+// The planes of rt_outputs in field order, with their bytes per pixel.  Internally a render's outputs are one Planes set
+// indexed by this table; a NULL plane is not wanted, and nothing is allocated or launched for it.  PL_NORMAL .. PL_ID are the
+// first-hit features (k_features).  PL_VARIANCE is not a field of rt_outputs (the struct cannot grow): it is the extra argument
+// of the _var entry points, written by k_resolve's VAR instantiations.
+enum Plane { PL_RGB8, PL_Z, PL_COUNT, PL_LINEAR, PL_NORMAL, PL_ALBEDO, PL_ALPHA, PL_ID, PL_VARIANCE, N_PLANES };
+static const size_t PLANE_BYTES[N_PLANES] = {3, 4, 1, 12, 12, 12, 4, 4, 12};
+struct Planes {
+    void *p[N_PLANES] = {};
+    Planes() = default;
+    explicit Planes(const rt_outputs &o, float *variance = nullptr)
+        : p{o.rgb8, o.z, o.count, o.rgb_linear, o.normal, o.albedo, o.alpha, o.object_id, variance} {}
+    template <class T> T *at(int i) const { return (T *)p[i]; }
+    DevFeatures features() const            // the planes k_features writes (rtk_launch_features)
+    {
+        DevFeatures f;
+        f.normal = at<float>(PL_NORMAL); f.albedo = at<float>(PL_ALBEDO); f.alpha = at<float>(PL_ALPHA); f.object_id = at<int32_t>(PL_ID);
+        return f;
+    }
+};
+// the three planes of the entry points without a descriptor (the optional ones NULL but for rgb_linear)
+inline rt_outputs outputs_of(uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear = nullptr)
+{
+    rt_outputs o = {(uint32_t)sizeof(rt_outputs), rgb8, z, count, rgb_linear};
+    return o;
+}
+// rt_render.cpp: every entry point with image planes: the caller's sizeof first, then the three required planes
+RT_HIDDEN rt_status check_outputs(const char *name, const rt_outputs *o);
+
+// An asynchronous job.  rt_jobs.cpp starts, answers for and ends it; the struct is here because the orchestration reads and
+// writes it while the job's thread renders (RenderAttempt in rt_render.cpp: stop and host read, progress and stats written).
+struct rt_job {
+    rt_scene *scene = nullptr;
+    std::thread worker;
+    std::atomic<int> progress{0};
+    std::atomic<bool> stop{false};
+    std::atomic<bool> done{false};
+    rt_status status = RT_OK;
+    std::string error;
+    rt_stats stats{};
+    // the caller-owned host planes (rt_render_begin*): finished bands are copied back chunk by chunk, so a
+    // viewer that polls rt_render_progress can show the frame as it fills (viewport.cpp:367 reads
+    // renderImage.GetPixels() while the workers run)
+    Planes host;
+    rt_setup_ms setup{};                // the photon pass this job ran first (all zero when it did not)
+};
+
+// What one render call writes, and how: image-sized device planes (`dev`; rgb_linear selects the linear plane, the features
+// k_features), or packed records of the call's tiles (`packed`: rec_bytes 8, or 24 with the linear plane).  A strided job
+// (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature / variance staging planes of its own.
+// Packed planes (rt_render_tiles_packed_outputs_device): `walk` names the sections of the caller's buffer behind the records --
+// PL_NORMAL .. PL_VARIANCE, indexed by the call's tile walk like the records -- and packed_bytes is the whole contribution:
+// what lies behind the records of the call's own tiles is zeroed in stream order before any kernel writes into it.
+struct RenderRequest {
+    Planes dev;
+    void *packed = nullptr;
+    size_t rec_bytes = 8;
+    Planes walk;
+    uint64_t packed_bytes = 0;          // packed planes only; 0: the packed entry points as they were
+    hipStream_t stream = nullptr;       // the caller's stream; NULL: the device's own
+    bool sync = true;
+    rt_stats *stats_out = nullptr;
+    rt_job *job = nullptr;
+};
+// rt_render.cpp: what every render call requires of its arguments, and the render itself -- what the entry points of all three
+// files end in (a render whose history-sized queues overflowed is repeated once with worst-case queues)
+RT_HIDDEN rt_status validate_render(const rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *t);
+RT_HIDDEN rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
+                                 const RenderRequest &req);

@@ -1,4 +1,4 @@
-// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_mesh_update.cpp, rt_photons.cpp, rt_render.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
+// rt_launch.h -- the boundary between the host orchestration (rt_lower.cpp, rt_mesh_update.cpp, rt_photons.cpp, rt_render.cpp, rt_exchange.cpp, rt_jobs.cpp, rt_post.cpp) and the kernels (rt_kernels.hip, rt_trace.hip, rt_resolve.hip, rt_gather.hip,
 // rt_photon_build.hip, rt_denoise.hip, rt_temporal.hip, rt_motion.hip, rt_motion_mesh.hip, rt_tonemap.hip, rt_bloom.hip, rt_motion_blur.hip, rt_dof.hip, rt_refit.hip): every rtk_* function, the requests they take and the
 // records they exchange.  All of these files include it, so a declaration and its definition cannot drift apart.  ResolveArgs, PhotonArgs and UnpackPlanesRequest are passed to kernels
 // as they stand here (members, order and types are the kernels' argument layout), MotionBlurRequest and DofRequest as a member of

@@ -1,6 +1,7 @@
-// rt_render.cpp -- rendering from a prepared device (rt_lower.cpp): per-chunk wavefront orchestration on HIP streams, the render,
-// packed and unpack entry points of the C ABI in include/rt_mi355x.h, async jobs, and the single-stage entry points.
-// rt_host.h is what the host files share.
+// rt_render.cpp -- rendering from a prepared device (rt_lower.cpp): per-chunk wavefront orchestration on HIP streams behind
+// render_tiles, the image-plane render entry points of the C ABI in include/rt_mi355x.h, rt_render_check / rt_render_counters, and
+// the single-stage entry points.  The tile exchange (rt_exchange.cpp) and the asynchronous jobs (rt_jobs.cpp) render through
+// render_tiles.  rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,9 +9,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
@@ -30,58 +28,6 @@ static int gather_blocks()
     return n;
 }
 static const size_t STATS_BYTES = (size_t)ST_COUNT * RT_STAT_STRIDE * 8;    // the statistics block: counters RT_STAT_STRIDE apart (rt_dev.h)
-
-// ---- render outputs -------------------------------------------------------------------------------------
-// The planes of rt_outputs in field order, with their bytes per pixel.  Internally a render's outputs are one Planes set
-// indexed by this table; a NULL plane is not wanted, and nothing is allocated or launched for it.  PL_NORMAL .. PL_ID are the
-// first-hit features (k_features).  PL_VARIANCE is not a field of rt_outputs (the struct cannot grow): it is the extra argument
-// of the _var entry points, written by k_resolve's VAR instantiations.
-enum Plane { PL_RGB8, PL_Z, PL_COUNT, PL_LINEAR, PL_NORMAL, PL_ALBEDO, PL_ALPHA, PL_ID, PL_VARIANCE, N_PLANES };
-static const size_t PLANE_BYTES[N_PLANES] = {3, 4, 1, 12, 12, 12, 4, 4, 12};
-struct Planes {
-    void *p[N_PLANES] = {};
-    Planes() = default;
-    explicit Planes(const rt_outputs &o, float *variance = nullptr)
-        : p{o.rgb8, o.z, o.count, o.rgb_linear, o.normal, o.albedo, o.alpha, o.object_id, variance} {}
-    template <class T> T *at(int i) const { return (T *)p[i]; }
-    DevFeatures features() const            // the planes k_features writes (rtk_launch_features)
-    {
-        DevFeatures f;
-        f.normal = at<float>(PL_NORMAL); f.albedo = at<float>(PL_ALBEDO); f.alpha = at<float>(PL_ALPHA); f.object_id = at<int32_t>(PL_ID);
-        return f;
-    }
-};
-// the three planes of the entry points without a descriptor (the optional ones NULL but for rgb_linear)
-static rt_outputs outputs_of(uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear = nullptr)
-{
-    rt_outputs o = {(uint32_t)sizeof(rt_outputs), rgb8, z, count, rgb_linear};
-    return o;
-}
-// every render entry point with image planes: the caller's sizeof first, then the three required planes
-static rt_status check_outputs(const char *name, const rt_outputs *o)
-{
-    if (!o) return fail(RT_ERR_ARG, "%s: the plane descriptor is NULL", name);
-    if (o->struct_size != (uint32_t)sizeof(rt_outputs))
-        return fail(RT_ERR_ARG, "%s: rt_outputs.struct_size is %u, this library's is %zu", name, o->struct_size, sizeof(rt_outputs));
-    if (!o->rgb8 || !o->z || !o->count) return fail(RT_ERR_ARG, "%s: rgb8, z and count are required", name);
-    return RT_OK;
-}
-
-struct rt_job {
-    rt_scene *scene = nullptr;
-    std::thread worker;
-    std::atomic<int> progress{0};
-    std::atomic<bool> stop{false};
-    std::atomic<bool> done{false};
-    rt_status status = RT_OK;
-    std::string error;
-    rt_stats stats{};
-    // the caller-owned host planes (rt_render_begin*): finished bands are copied back chunk by chunk, so a
-    // viewer that polls rt_render_progress can show the frame as it fills (viewport.cpp:367 reads
-    // renderImage.GetPixels() while the workers run)
-    Planes host;
-    rt_setup_ms setup{};                // the photon pass this job ran first (all zero when it did not)
-};
 
 // Queue sizing policy: the first render of a kind (shading model, bounce limit, fan-out, maps in use) provides one ray and
 // half a photon query per sample, later ones twice what the fullest chunk so far needed (at least 1 ray and 0.25 queries per sample);
@@ -283,7 +229,7 @@ void camera_setup(const rt_camera &cam, DevCamera &dc)
     dc.u = u; dc.v = v; dc.dof = cam.dof; dc.width = cam.width; dc.height = cam.height;
 }
 
-static rt_status validate_render(const rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *t)
+rt_status validate_render(const rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *t)
 {
     if (!cam || !p || !t) return fail(RT_ERR_ARG, "render: camera, params and tile range are required");
     if (cam->width <= 0 || cam->height <= 0 || (long long)cam->width * cam->height > (1LL << 28)) return fail(RT_ERR_ARG, "render: bad image size %dx%d", cam->width, cam->height);
@@ -413,24 +359,6 @@ struct TileWalk {
         }
         return n;
     }
-};
-
-// What one render call writes, and how: image-sized device planes (`dev`; rgb_linear selects the linear plane, the features
-// k_features), or packed records of the call's tiles (`packed`: rec_bytes 8, or 24 with the linear plane).  A strided job
-// (rt_render_begin*, tile stride != 1) renders into packed records of rec_bytes and feature / variance staging planes of its own.
-// Packed planes (rt_render_tiles_packed_outputs_device): `walk` names the sections of the caller's buffer behind the records --
-// PL_NORMAL .. PL_VARIANCE, indexed by the call's tile walk like the records -- and packed_bytes is the whole contribution:
-// what lies behind the records of the call's own tiles is zeroed in stream order before any kernel writes into it.
-struct RenderRequest {
-    Planes dev;
-    void *packed = nullptr;
-    size_t rec_bytes = 8;
-    Planes walk;
-    uint64_t packed_bytes = 0;          // packed planes only; 0: the packed entry points as they were
-    hipStream_t stream = nullptr;       // the caller's stream; NULL: the device's own
-    bool sync = true;
-    rt_stats *stats_out = nullptr;
-    rt_job *job = nullptr;
 };
 
 #define RT_ERR_OVERFLOW_RETRY (-1000)     /* internal: queues sized from history overflowed; render again with worst-case queues */
@@ -867,8 +795,7 @@ static rt_status render_tiles_once(rt_scene *s, const rt_camera *cam, const rt_p
     return A.assemble_stats();
 }
 
-static rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              const RenderRequest &req)
+rt_status render_tiles(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device, const RenderRequest &req)
 {
     rt_status st = render_tiles_once(s, cam, p, tiles, device, req, false);
     int attempts = 1;
@@ -887,6 +814,16 @@ static RenderRequest device_request(void *hip_stream, int sync, rt_stats *stats_
     RenderRequest req;
     req.stream = (hipStream_t)hip_stream; req.sync = sync != 0; req.stats_out = stats_out;
     return req;
+}
+
+// every entry point with image planes (here, rt_exchange.cpp, rt_jobs.cpp): the caller's sizeof first, then the three required planes
+rt_status check_outputs(const char *name, const rt_outputs *o)
+{
+    if (!o) return fail(RT_ERR_ARG, "%s: the plane descriptor is NULL", name);
+    if (o->struct_size != (uint32_t)sizeof(rt_outputs))
+        return fail(RT_ERR_ARG, "%s: rt_outputs.struct_size is %u, this library's is %zu", name, o->struct_size, sizeof(rt_outputs));
+    if (!o->rgb8 || !o->z || !o->count) return fail(RT_ERR_ARG, "%s: rgb8, z and count are required", name);
+    return RT_OK;
 }
 
 // RenderPixel's outputs (FIN/main.cpp:273-338) into the caller's device planes, with the optional ones of rt_outputs: the linear
@@ -934,200 +871,6 @@ extern "C" rt_status rt_render_tiles_outputs_var_device(rt_scene *s, const rt_ca
     return render_device("rt_render_tiles_outputs_var_device", s, cam, p, tiles, device, hip_stream, device_planes, sync, stats_out, variance_dev);
 }
 
-// What every packed entry point (the two below and the packed-planes one) checks first, and the request it ends with: 8-byte
-// records into packed_dev, or 24-byte ones with the linear plane (linear).  How much of the buffer a call needs, and whether the
-// rest of it is zeroed, differs between them and stays with each.
-static rt_status check_packed(const char *name, const rt_scene *s, const void *packed_dev)
-{
-    if (!s) return fail(RT_ERR_ARG, "%s: scene is NULL", name);
-    if (!packed_dev) return fail(RT_ERR_ARG, "%s: the packed buffer is required", name);
-    return RT_OK;
-}
-static RenderRequest packed_request(void *hip_stream, int sync, rt_stats *stats_out, void *packed_dev, bool linear)
-{
-    RenderRequest req = device_request(hip_stream, sync, stats_out);
-    req.packed = packed_dev; req.rec_bytes = linear ? 24 : 8;
-    return req;
-}
-
-// both packed entry points: the buffer holds the records of the call's own tiles
-static rt_status render_packed(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                               int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, int sync, rt_stats *stats_out,
-                               bool linear)
-{
-    rt_status st = check_packed(name, s, packed_dev);
-    if (st) return st;
-    if ((st = validate_render(s, cam, p, tiles))) return st;
-    uint64_t need = 0;
-    if ((st = rt_tiles_packed_size(cam->width, cam->height, tiles, &need, nullptr))) return st;
-    if (linear) need *= 3;
-    if (packed_bytes < need) return fail(RT_ERR_ARG, "%s: buffer of %llu bytes, this call's tiles need %llu", name,
-                                         (unsigned long long)packed_bytes, (unsigned long long)need);
-    return render_tiles(s, cam, p, tiles, device, packed_request(hip_stream, sync, stats_out, packed_dev, linear));
-}
-
-extern "C" rt_status rt_render_tiles_packed_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                                                   int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes,
-                                                   int sync, rt_stats *stats_out)
-{
-    return render_packed("rt_render_tiles_packed_device", s, cam, p, tiles, device, hip_stream, packed_dev, packed_bytes, sync, stats_out, false);
-}
-
-extern "C" rt_status rt_render_tiles_packed_linear_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                                                          int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes,
-                                                          int sync, rt_stats *stats_out)
-{
-    return render_packed("rt_render_tiles_packed_linear_device", s, cam, p, tiles, device, hip_stream, packed_dev, packed_bytes, sync,
-                         stats_out, true);
-}
-
-// ---- packed planes (rt_mi355x.h, "packed planes") ----
-static const uint32_t RT_PLANE_ALL = RT_PLANE_LINEAR | RT_PLANE_NORMAL | RT_PLANE_ALBEDO | RT_PLANE_ALPHA | RT_PLANE_OBJECT_ID | RT_PLANE_VARIANCE;
-// the sections behind the records, in buffer order: mask bit and plane
-static const struct { uint32_t bit; Plane plane; } PACKED_SECTIONS[5] = {
-    {RT_PLANE_NORMAL, PL_NORMAL}, {RT_PLANE_ALBEDO, PL_ALBEDO}, {RT_PLANE_ALPHA, PL_ALPHA}, {RT_PLANE_OBJECT_ID, PL_ID}, {RT_PLANE_VARIANCE, PL_VARIANCE}};
-
-// one contribution of `per_rank` tiles of tile_px pixels: its bytes and the offsets of the six sections (UINT64_MAX: absent)
-static uint64_t packed_planes_layout(uint64_t per_rank, uint64_t tile_px, uint32_t mask, uint64_t off[6])
-{
-    const uint64_t Q = per_rank * tile_px;
-    uint64_t at = Q * ((mask & RT_PLANE_LINEAR) ? 24u : 8u);
-    off[0] = 0;
-    for (int i = 0; i < 5; i++) {
-        const bool on = (mask & PACKED_SECTIONS[i].bit) != 0;
-        off[1 + i] = on ? at : UINT64_MAX;
-        if (on) at += Q * PLANE_BYTES[PACKED_SECTIONS[i].plane];
-    }
-    return (at + 15u) & ~(uint64_t)15u;
-}
-
-extern "C" rt_status rt_tiles_packed_planes_size(int32_t width, int32_t height, const rt_tile_range *t, uint32_t mask,
-                                                 uint64_t *bytes, int32_t *n_tiles, uint64_t section_offsets[6])
-{
-    if (!t || !bytes || width <= 0 || height <= 0 || t->tile_w <= 0 || t->tile_h <= 0 || t->stride <= 0 || t->first < 0)
-        return fail(RT_ERR_ARG, "rt_tiles_packed_planes_size: bad argument");
-    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "rt_tiles_packed_planes_size: unknown plane bits 0x%x", mask & ~RT_PLANE_ALL);
-    const int64_t tiles_x = (width + t->tile_w - 1) / t->tile_w, tiles_y = (height + t->tile_h - 1) / t->tile_h;
-    const int64_t per_rank = (tiles_x * tiles_y + t->stride - 1) / t->stride;
-    uint64_t off[6];
-    *bytes = packed_planes_layout((uint64_t)per_rank, (uint64_t)t->tile_w * (uint64_t)t->tile_h, mask, off);
-    if (n_tiles) *n_tiles = (int32_t)per_rank;
-    if (section_offsets) memcpy(section_offsets, off, sizeof off);
-    return RT_OK;
-}
-
-extern "C" rt_status rt_render_tiles_packed_outputs_device(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles,
-                                                           int device, void *hip_stream, void *packed_dev, uint64_t packed_bytes, uint32_t mask,
-                                                           int sync, rt_stats *stats_out)
-{
-    const char *name = "rt_render_tiles_packed_outputs_device";
-    rt_status st = check_packed(name, s, packed_dev);
-    if (st) return st;
-    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "%s: unknown plane bits 0x%x", name, mask & ~RT_PLANE_ALL);
-    if ((st = validate_render(s, cam, p, tiles))) return st;
-    uint64_t need = 0, off[6];
-    if ((st = rt_tiles_packed_planes_size(cam->width, cam->height, tiles, mask, &need, nullptr, off))) return st;
-    if (packed_bytes < need) return fail(RT_ERR_ARG, "%s: buffer of %llu bytes, a contribution with these planes needs %llu", name,
-                                         (unsigned long long)packed_bytes, (unsigned long long)need);
-    RenderRequest req = packed_request(hip_stream, sync, stats_out, packed_dev, (mask & RT_PLANE_LINEAR) != 0);
-    req.packed_bytes = need;
-    for (int i = 0; i < 5; i++)
-        if (mask & PACKED_SECTIONS[i].bit) req.walk.p[PACKED_SECTIONS[i].plane] = (uint8_t *)packed_dev + off[1 + i];
-    return render_tiles(s, cam, p, tiles, device, req);
-}
-
-// every unpack entry point: `world` contributions of tiles_per_rank tiles each must hold the image's tiles, dealt round-robin
-static rt_status check_unpack_geometry(const char *name, int32_t world, int32_t tiles_per_rank, int32_t width, int32_t height,
-                                       int32_t tile_w, int32_t tile_h)
-{
-    if (world <= 0 || width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0) return fail(RT_ERR_ARG, "%s: bad geometry", name);
-    const int64_t total = (int64_t)((width + tile_w - 1) / tile_w) * ((height + tile_h - 1) / tile_h);
-    if ((int64_t)tiles_per_rank * world < total || tiles_per_rank < (total + world - 1) / world)
-        return fail(RT_ERR_ARG, "%s: %d tiles per rank x %d ranks cannot hold %lld tiles", name, tiles_per_rank, world, (long long)total);
-    return RT_OK;
-}
-
-extern "C" rt_status rt_tiles_unpack_outputs_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
-                                                    int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, uint32_t mask,
-                                                    const rt_outputs *device_planes, float *variance_dev)
-{
-    const char *name = "rt_tiles_unpack_outputs_device";
-    if (!gathered_dev) return fail(RT_ERR_ARG, "%s: NULL buffer", name);
-    if ((uintptr_t)gathered_dev & 15u) return fail(RT_ERR_ARG, "%s: the gathered buffer must be 16-byte aligned", name);
-    if (mask & ~RT_PLANE_ALL) return fail(RT_ERR_ARG, "%s: unknown plane bits 0x%x", name, mask & ~RT_PLANE_ALL);
-    rt_status st = check_outputs(name, device_planes);
-    if (st) return st;
-    const Planes dst(*device_planes, variance_dev);
-    if ((mask & RT_PLANE_LINEAR) && !dst.p[PL_LINEAR]) return fail(RT_ERR_ARG, "%s: the linear plane is in the mask and has no destination", name);
-    for (int i = 0; i < 5; i++)
-        if ((mask & PACKED_SECTIONS[i].bit) && !dst.p[PACKED_SECTIONS[i].plane])
-            return fail(RT_ERR_ARG, "%s: plane bit 0x%x is in the mask and has no destination", name, PACKED_SECTIONS[i].bit);
-    if ((st = check_unpack_geometry(name, world, tiles_per_rank, width, height, tile_w, tile_h))) return st;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
-    HIP_TRY(hipSetDevice(device));
-    uint64_t off[6];
-    UnpackPlanesRequest u = {};
-    u.rank_bytes = packed_planes_layout((uint64_t)tiles_per_rank, (uint64_t)tile_w * (uint64_t)tile_h, mask, off);
-    u.gathered = gathered_dev; u.world = world; u.per_rank = tiles_per_rank; u.width = width; u.height = height; u.tile_w = tile_w; u.tile_h = tile_h;
-    u.rgb8 = dst.at<uint8_t>(PL_RGB8); u.z = dst.at<float>(PL_Z); u.count = dst.at<uint8_t>(PL_COUNT);
-    // a destination outside the mask is not the kernel's business: it sees NULL there
-    if (mask & RT_PLANE_LINEAR) u.rgb_linear = dst.at<float>(PL_LINEAR);
-    if (mask & RT_PLANE_NORMAL) { u.normal = dst.at<float>(PL_NORMAL); u.off_normal = off[1]; }
-    if (mask & RT_PLANE_ALBEDO) { u.albedo = dst.at<float>(PL_ALBEDO); u.off_albedo = off[2]; }
-    if (mask & RT_PLANE_ALPHA) { u.alpha = dst.at<float>(PL_ALPHA); u.off_alpha = off[3]; }
-    if (mask & RT_PLANE_OBJECT_ID) { u.object_id = dst.at<int32_t>(PL_ID); u.off_object_id = off[4]; }
-    if (mask & RT_PLANE_VARIANCE) { u.variance = dst.at<float>(PL_VARIANCE); u.off_variance = off[5]; }
-    rtk_launch_unpack_planes((hipStream_t)hip_stream, u);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-extern "C" rt_status rt_tiles_packed_size(int32_t width, int32_t height, const rt_tile_range *t, uint64_t *bytes, int32_t *n_tiles)
-{
-    if (!t || width <= 0 || height <= 0 || t->tile_w <= 0 || t->tile_h <= 0 || t->stride <= 0 || t->first < 0)
-        return fail(RT_ERR_ARG, "rt_tiles_packed_size: bad argument");
-    const int64_t tiles_x = (width + t->tile_w - 1) / t->tile_w, tiles_y = (height + t->tile_h - 1) / t->tile_h;
-    const int64_t total = tiles_x * tiles_y;
-    const int64_t n = t->first >= total ? 0 : (total - t->first + t->stride - 1) / t->stride;
-    if (bytes) *bytes = (uint64_t)n * (uint64_t)t->tile_w * (uint64_t)t->tile_h * 8ull;
-    if (n_tiles) *n_tiles = (int32_t)n;
-    return RT_OK;
-}
-
-// both unpack entry points: rgb_linear_dev == NULL reads 8-byte records, otherwise 24-byte ones
-static rt_status tiles_unpack(const char *name, int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
-                              int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
-                              uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev)
-{
-    if (!gathered_dev || !rgb8_dev || !z_dev || !count_dev) return fail(RT_ERR_ARG, "%s: NULL buffer", name);
-    if (rt_status st = check_unpack_geometry(name, world, tiles_per_rank, width, height, tile_w, tile_h)) return st;
-    if (!device_is_gfx950(device)) return fail(RT_ERR_NO_DEVICE, "%s: device %d is not gfx950 (no CPU path)", name, device);
-    HIP_TRY(hipSetDevice(device));
-    UnpackRequest u = {};
-    u.gathered = gathered_dev; u.world = world; u.per_rank = tiles_per_rank; u.width = width; u.height = height; u.tile_w = tile_w; u.tile_h = tile_h;
-    u.rgb8 = rgb8_dev; u.z = z_dev; u.count = count_dev; u.rgb_linear = rgb_linear_dev;
-    rtk_launch_unpack_tiles((hipStream_t)hip_stream, u);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-extern "C" rt_status rt_tiles_unpack_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
-                                            int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
-                                            uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev)
-{
-    return tiles_unpack("rt_tiles_unpack_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
-                        rgb8_dev, z_dev, count_dev, nullptr);
-}
-
-extern "C" rt_status rt_tiles_unpack_linear_device(int device, void *hip_stream, const void *gathered_dev, int32_t world, int32_t tiles_per_rank,
-                                                   int32_t width, int32_t height, int32_t tile_w, int32_t tile_h,
-                                                   uint8_t *rgb8_dev, float *z_dev, uint8_t *count_dev, float *rgb_linear_dev)
-{
-    if (!rgb_linear_dev) return fail(RT_ERR_ARG, "rt_tiles_unpack_linear_device: the linear plane is required");
-    return tiles_unpack("rt_tiles_unpack_linear_device", device, hip_stream, gathered_dev, world, tiles_per_rank, width, height, tile_w, tile_h,
-                        rgb8_dev, z_dev, count_dev, rgb_linear_dev);
-}
-
 extern "C" rt_status rt_render_check(rt_scene *s, int device)
 {
     if (!s) return fail(RT_ERR_ARG, "rt_render_check: scene is NULL");
@@ -1167,129 +910,6 @@ extern "C" rt_status rt_render_counters(rt_scene *s, int device, int reset, rt_s
         HIP_TRY(hipMemset((unsigned long long *)D->stats.p + ST_AT(ST_GATHER_ROUNDS), 0, ST_AT(ST_PEAK_RAYS - ST_GATHER_ROUNDS) * 8));
     }
     return RT_OK;
-}
-
-// BeginRender (FIN/main.cpp:984-1010): rt_render_begin, rt_render_begin_linear and rt_render_begin_outputs, with the planes
-// RenderPixel (:273-338) could have kept: its colour before gamma, and the first hit's normal, albedo, coverage and node
-static rt_status render_begin(const char *name, rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                              const rt_outputs *host_planes, rt_job **out, float *variance = nullptr)
-{
-    if (!s || !out) return fail(RT_ERR_ARG, "%s: scene/out is NULL", name);
-    rt_status st = check_outputs(name, host_planes);
-    if (st) return st;
-    if ((st = validate_render(s, cam, p, tiles))) return st;
-    DeviceState *D = nullptr;
-    if ((st = prepare_device(s, device, &D))) return st;      // fail early (and loudly) when there is no GPU
-    rt_job *job = new rt_job;
-    job->scene = s;
-    job->host = Planes(*host_planes, variance);
-    s->live_jobs.fetch_add(1);
-    const rt_camera camv = *cam; const rt_params pv = *p; const rt_tile_range tv = *tiles;
-    job->worker = std::thread([=]() {
-        auto body = [&]() -> rt_status {
-            HIP_TRY(hipSetDevice(device));
-            // BeginRender calls generatePhotonMap() before it spawns its workers (FIN/main.cpp:984-998, :350-402); here the
-            // photon pass runs on the job's thread, so the call itself still returns at once and progress stays 0 meanwhile
-            if (pv.shade_model == RT_SHADE_FIN && pv.photon_count > 0) {
-                std::lock_guard<std::mutex> gen(s->gen_mu);         // one job per device may have been started: the first one generates
-                bool have_map, have_source = false;
-                std::string dump;
-                {
-                    std::lock_guard<std::mutex> lk(s->mu);
-                    // a generated map serves only the parameters it was generated with (rt_photon_map.h)
-                    have_map = s->global_photons.serves((uint32_t)pv.photon_count, pv.photon_bounce, pv.seed);
-                    dump = s->photon_dump;
-                }
-                for (const rt_light &l : s->data.lights) if (l.type == RT_LIGHT_POINT) have_source = true;
-                if (!have_map && have_source && !job->stop.load()) {
-                    const rt_status g = generate_photons(s, device, (uint32_t)pv.photon_count, pv.photon_bounce, pv.seed, dump.empty() ? nullptr : dump.c_str(),
-                                                         &job->setup, true);
-                    if (g) return g;
-                }
-            }
-            // a device copy of every plane that was asked for, starting from the caller's values -- but a strided job takes its
-            // linear plane in its packed records and its features and variance in walk-indexed staging planes
-            // (RenderAttempt::setup_outputs)
-            RenderRequest req;
-            req.job = job;
-            req.rec_bytes = job->host.p[PL_LINEAR] ? 24 : 8;
-            ScopedDevBuf dev[N_PLANES];
-            const size_t npx = (size_t)camv.width * camv.height;
-            for (int i = 0; i < N_PLANES; i++) {
-                if (!job->host.p[i] || (tv.stride != 1 && i >= PL_LINEAR)) continue;
-                if (rt_status us = dev[i].upload(job->host.p[i], npx * PLANE_BYTES[i])) return us;
-                req.dev.p[i] = dev[i].p;
-            }
-            // render_tiles copies every finished band of rows back into the caller's buffers
-            return render_tiles(s, &camv, &pv, &tv, device, req);
-        };
-        const rt_status r = body();
-        job->status = r;
-        if (r) job->error = rt_last_error();
-        job->done.store(true);
-        s->live_jobs.fetch_sub(1);
-    });
-    *out = job;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_render_begin(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                     uint8_t *rgb8, float *z, uint8_t *count, rt_job **out)
-{
-    const rt_outputs o = outputs_of(rgb8, z, count);
-    return render_begin("rt_render_begin", s, cam, p, tiles, device, &o, out);
-}
-
-extern "C" rt_status rt_render_begin_linear(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                            uint8_t *rgb8, float *z, uint8_t *count, float *rgb_linear, rt_job **out)
-{
-    if (!rgb_linear) return fail(RT_ERR_ARG, "rt_render_begin_linear: the linear plane is required");
-    const rt_outputs o = outputs_of(rgb8, z, count, rgb_linear);
-    return render_begin("rt_render_begin_linear", s, cam, p, tiles, device, &o, out);
-}
-
-extern "C" rt_status rt_render_begin_outputs(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                             const rt_outputs *host_planes, rt_job **out)
-{
-    return render_begin("rt_render_begin_outputs", s, cam, p, tiles, device, host_planes, out);
-}
-
-extern "C" rt_status rt_render_begin_outputs_var(rt_scene *s, const rt_camera *cam, const rt_params *p, const rt_tile_range *tiles, int device,
-                                                 const rt_outputs *host_planes, float *variance, rt_job **out)
-{
-    if (!variance) return fail(RT_ERR_ARG, "rt_render_begin_outputs_var: the variance plane is required");
-    return render_begin("rt_render_begin_outputs_var", s, cam, p, tiles, device, host_planes, out, variance);
-}
-
-extern "C" int rt_render_progress(rt_job *j) { return j ? j->progress.load() : 0; }
-extern "C" rt_status rt_render_stop(rt_job *j) { if (!j) return fail(RT_ERR_ARG, "rt_render_stop: job is NULL"); j->stop.store(true); return RT_OK; }
-extern "C" rt_status rt_render_wait(rt_job *j)
-{
-    if (!j) return fail(RT_ERR_ARG, "rt_render_wait: job is NULL");
-    if (j->worker.joinable()) j->worker.join();
-    if (j->status) return fail(j->status, "%s", j->error.c_str());      // the worker's message, on the waiting thread
-    return j->status;
-}
-extern "C" rt_status rt_job_stats(rt_job *j, rt_stats *out)
-{
-    if (!j || !out) return fail(RT_ERR_ARG, "rt_job_stats: NULL argument");
-    if (!j->done.load()) return fail(RT_ERR_STATE, "rt_job_stats: job still running");
-    *out = j->stats;
-    return RT_OK;
-}
-extern "C" rt_status rt_job_setup_ms(rt_job *j, rt_setup_ms *out)
-{
-    if (!j || !out) return fail(RT_ERR_ARG, "rt_job_setup_ms: NULL argument");
-    if (!j->done.load()) return fail(RT_ERR_STATE, "rt_job_setup_ms: job still running");
-    *out = j->setup;
-    return RT_OK;
-}
-extern "C" void rt_job_destroy(rt_job *j)
-{
-    if (!j) return;
-    j->stop.store(true);
-    if (j->worker.joinable()) j->worker.join();
-    delete j;
 }
 
 // ---- single-stage entry points --------------------------------------------------------------------------

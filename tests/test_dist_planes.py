@@ -76,6 +76,34 @@ def test_odd_tiles_round_the_contribution_up_to_16_bytes():
     _same_frame(rtd.unpack_gathered_planes(packs, 7, 5, 4, ("alpha",), 3, 3), f, ("alpha",))
 
 
+def test_the_two_size_queries_count_the_same_tiles():
+    """rt_tiles_packed_size counts the call's own tiles, first, first + stride, ... (8 bytes a slot; a walk that starts at or beyond
+    the tile count has none and needs no bytes); rt_tiles_packed_planes_size counts the largest share of `stride` ranks whatever
+    `first` is, and rounds the contribution up to 16 bytes.  Both against each other, against dist.planes_layout and against the
+    tile numbers themselves: an image no multiple of the tile (7 x 5 in 3 x 3 tiles: 6 tiles), strides that do not divide the tile
+    count, that equal it and that exceed it."""
+    for (w, h, tw, th) in ((7, 5, 3, 3), (100, 37, 32, 8), (64, 48, 32, 8)):
+        _, _, n = rtd.tile_grid(w, h, tw, th)
+        assert n == -(-w // tw) * -(-h // th)
+        for stride in (1, 2, 3, 4, 5, n, n + 1, 3 * n):
+            per_rank = -(-n // stride)
+            for planes in ((), ("alpha",), ALL):
+                want = rtd.planes_layout(w, h, stride, planes, tw, th)
+                assert want[1] == per_rank and want[0] % 16 == 0
+                if planes == ():
+                    assert 0 <= want[0] - per_rank * tw * th * 8 < 16
+                for first in (0, 1, stride - 1, n - 1, n, n + 1, n + stride):
+                    assert capi.tiles_packed_planes_size(w, h, capi.TileRange(tw, th, first, stride), planes) == want
+            for first in (0, 1, stride - 1, n - 1, n, n + 1, n + stride):
+                t = capi.TileRange(tw, th, first, stride)
+                nbytes, k = capi.tiles_packed_size(w, h, t)
+                assert k == len(range(first, n, stride)) <= per_rank and nbytes == k * tw * th * 8
+                assert capi.tiles_packed_size(w, h, t, linear=True) == (3 * nbytes, k)
+            # the ranks' own tiles make up the image, and the largest share is what every contribution is sized for
+            shares = [capi.tiles_packed_size(w, h, capi.TileRange(tw, th, r, stride))[1] for r in range(stride)]
+            assert sum(shares) == n and max(shares) == per_rank
+
+
 def _zero_slots_are_zero(pack, rank, world, planes, w=W, h=H):
     """every slot of `pack` that belongs to no pixel of the rank's tiles is zero, every other one is not (the frame has no zeros)"""
     nbytes, per_rank, off = rtd.planes_layout(w, h, world, planes)
