@@ -621,6 +621,78 @@ rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t mesh, uint32
  * ahead of the event that ends them: in SMOOTH mode rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms include it. */
 rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms);
 
+/* ---- mesh skinning (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------------
+ * A second source of new vertices for the in-place update: linear-blend skinning on the device.  A skin is bound to a mesh once;
+ * after that a frame brings a pose -- a few dozen matrices instead of a vertex array -- and k_mesh_skin (csrc/rt_mesh_skin.hip)
+ * writes the posed positions where the refit, the device build, k_mesh_normals and k_motion_mesh read them.  The definition fixes
+ * every operation and its order, so that the kernel and the host mirror (rt_mesh_skin) give the same bytes; the arithmetic is
+ * written once, in csrc/rt_mesh_skin.h.
+ *
+ * A skin    belongs to one mesh of a scene: n_bones (1 .. RT_MESH_SKIN_MAX_BONES); per vertex four influences, bone_index as
+ *           uint16[nv][4] and weight as float32[nv][4]; and the REST POSE, a copy of the positions the mesh holds when the skin
+ *           is bound.  Every index must be < n_bones, every weight finite and >= 0.  Weights are used as given: the library does
+ *           not normalise them.  An unused influence is weight 0 on any valid bone.
+ * A pose    is n_bones matrices, float32[n_bones][3][4], row-major, in the mesh's object space (the space its vertices are in,
+ *           under its node).  Every one of the 12 n_bones floats must be finite (checked on the host), n_bones must be the skin's.
+ * The posed position of vertex i with rest position (x, y, z), for each row r of the output:
+ *           for k = 0, 1, 2, 3 (ascending; all four always evaluated), with M = bones[bone_index[i][k]], w = weight[i][k]:
+ *               t   = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3]
+ *               acc = (k == 0) ? w*t : acc + w*t
+ *           p[r] = acc
+ *           Every * and + is one IEEE float32 operation, rounded to nearest; nothing is fused.
+ * Normals   A pose brings none: it behaves exactly as an update with vn == NULL.  RT_MESH_NORMALS_STORED keeps the stored normals;
+ *           RT_MESH_NORMALS_SMOOTH recomputes them from the posed positions (k_mesh_normals on the devices, the mirror in the
+ *           store).  Skinned meshes are expected to use SMOOTH mode.
+ *
+ * rt_mesh_skin is the host mirror: plain C++, no scene, no GPU, no HIP call, on bare arrays; v_out (nv x 3 floats) may be v_rest.
+ * RT_ERR_ARG and nothing written: a NULL array, nv <= 0, n_bones outside 1 .. RT_MESH_SKIN_MAX_BONES, an index >= n_bones, a
+ * weight that is negative or not finite, a bone entry that is not finite. */
+#define RT_MESH_SKIN_MAX_BONES 1024
+rt_status rt_mesh_skin(const float *v_rest, int32_t nv, const uint16_t *bone_index, const float *weight, const float *bones,
+                       int32_t n_bones, float *v_out);
+/* Binds a skin to a mesh: the arrays are copied, the rest pose is taken from the store's current vertices, and nv must be the
+ * mesh's.  A refused argument is RT_ERR_ARG and nothing changes.  A skin already bound is replaced.  rt_scene_set_mesh drops the
+ * skin; a plain rt_scene_update_mesh_vertices* call on a skinned mesh keeps the skin and the rest pose and simply replaces the
+ * current positions (the next pose starts from the rest pose again).  The scene must be idle. */
+rt_status rt_scene_set_mesh_skin(rt_scene *s, int32_t mesh, int32_t n_bones, const uint16_t *bone_index, const float *weight, int32_t nv);
+/* Unbinds it (RT_OK when there is none): the mesh keeps the positions it has, and what the devices held of the skin is released. */
+rt_status rt_scene_clear_mesh_skin(rt_scene *s, int32_t mesh);
+/* bound: 0 / 1, with n_bones and nv of the skin (0 when none is bound).  store_current: 1 when the store's per-vertex positions
+ * are those of the last pose, 0 while they are still owed by the mirror -- a pose leaves the store with the matrices only, and
+ * the mirror runs when the positions are next read (rt_scene_get_mesh, a lowering, rt_scene_set_mesh_skin).  struct_size must be
+ * the caller's sizeof (else RT_ERR_ARG). */
+typedef struct rt_mesh_skin_info {
+    uint32_t struct_size;
+    uint32_t bound;
+    int32_t  n_bones, nv;
+    uint32_t store_current;
+} rt_mesh_skin_info;
+rt_status rt_scene_mesh_skin_info(const rt_scene *s, int32_t mesh, rt_mesh_skin_info *out);
+/* The pose: rt_scene_update_mesh_vertices_flags with the vertices of the definition above in place of v and with vn == NULL, on the
+ * same entry path -- the same flags (RT_MESH_UPDATE_REBUILD, RT_MESH_UPDATE_KEEP_PREVIOUS; any other bit RT_ERR_ARG), the same
+ * statuses, the same store discipline (tree stale, a generated photon map dropped).  On every device that holds the scene the
+ * vertex upload is replaced by an upload of the bones (48 n_bones bytes) and one launch of k_mesh_skin ahead of k_mesh_normals;
+ * rest pose, indices and weights go to a device once, at the mesh's first pose there.  With KEEP_PREVIOUS the device's previous
+ * positions become the buffer its positions were in and the kernel writes the other one: two pointers are swapped, nothing is
+ * uploaded or copied.  The mesh's root box and the objects' cull boxes come from the root record of the first device's refitted
+ * (or built) tree, which holds the exact min / max of the vertices under the faces -- a second short synchronise in the refit; a
+ * mesh whose tree is a single leaf has no such record and is posed by the mirror and uploaded as before.  With no device holding
+ * the scene the store records the pose and the next lowering resolves it.  A pose on a mesh without a skin is RT_ERR_STATE, a
+ * wrong n_bones or a bone that is not finite RT_ERR_ARG; nothing changes then. */
+rt_status rt_scene_pose_mesh(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags);
+/* ... as rt_scene_update_mesh_vertices_auto_flags (flags: 0 or RT_MESH_UPDATE_KEEP_PREVIOUS) */
+rt_status rt_scene_pose_mesh_auto(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
+                                  rt_mesh_quality *out);
+/* ... as rt_scene_update_mesh_vertices_build */
+rt_status rt_scene_pose_mesh_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, rt_mesh_build_info *out);
+/* ... as rt_scene_update_mesh_vertices_auto_build */
+rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
+                                        rt_mesh_quality *q, rt_mesh_build_info *out);
+/* Milliseconds of the last k_mesh_skin launch on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
+ * has run none.  Like k_mesh_normals it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
+rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms);
+
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
  * (maxElementsPerNode = 4, FIN/include/objects.h:143).  nodes_out needs room for 2*nf+1

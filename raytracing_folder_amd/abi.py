@@ -216,6 +216,11 @@ class MeshBuildInfo(C.Structure):
         return d
 
 
+class MeshSkinInfo(C.Structure):
+    """rt_mesh_skin_info: the skin bound to a mesh, and whether the store's positions are the last pose's (rt_scene_mesh_skin_info)"""
+    _fields_ = [("struct_size", C.c_uint32), ("bound", C.c_uint32), ("n_bones", C.c_int32), ("nv", C.c_int32), ("store_current", C.c_uint32)]
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -257,6 +262,9 @@ MESH_BUILD_NOT_ON_DEVICE = 4
 # rt_scene_set_mesh_normals_mode modes (include/rt_mi355x.h, "smooth normals")
 MESH_NORMALS_STORED = 0
 MESH_NORMALS_SMOOTH = 1
+
+# the most bones a skin can have (include/rt_mi355x.h, "mesh skinning")
+MESH_SKIN_MAX_BONES = 1024
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -333,6 +341,15 @@ SIGNATURES = {
     "rt_scene_set_mesh_normals_mode": (st, [vp, i32, u32]),
     "rt_scene_get_mesh_normals_mode": (st, [vp, i32, vp]),
     "rt_scene_mesh_normals_ms": (st, [vp, i32, vp]),
+    "rt_mesh_skin": (st, [vp, i32, vp, vp, vp, i32, vp]),
+    "rt_scene_set_mesh_skin": (st, [vp, i32, i32, vp, vp, i32]),
+    "rt_scene_clear_mesh_skin": (st, [vp, i32]),
+    "rt_scene_mesh_skin_info": (st, [vp, i32, vp]),
+    "rt_scene_pose_mesh": (st, [vp, i32, vp, i32, u32]),
+    "rt_scene_pose_mesh_auto": (st, [vp, i32, vp, i32, u32, f64, vp]),
+    "rt_scene_pose_mesh_build": (st, [vp, i32, vp, i32, u32, vp]),
+    "rt_scene_pose_mesh_auto_build": (st, [vp, i32, vp, i32, u32, f64, vp, vp]),
+    "rt_scene_mesh_skin_ms": (st, [vp, i32, vp]),
     "rt_bvh_build": (st, [vp, i32, vp, i32, i32, vp, vp, vp]),
     "rt_photon_balance": (st, [vp, u32, vp]),
     "rt_photon_unreachable": (st, [vp, u32, vp, u32, vp]),

@@ -42,6 +42,19 @@ def mesh_smooth_normals(v, f, fn=None, vn=None):
     return out
 
 
+def mesh_skin(v_rest, bone_index, weight, bones):
+    """rt_mesh_skin, the host mirror of k_mesh_skin (no GPU): the posed positions, float32 (nv, 3), of rest positions v_rest under
+    four influences a vertex -- bone_index uint16 (nv, 4), weight float32 (nv, 4) -- and the pose bones, float32 (n_bones, 3, 4)"""
+    v = _c(v_rest, np.float32).reshape(-1, 3)
+    idx, w = _c(bone_index, np.uint16).reshape(-1, 4), _c(weight, np.float32).reshape(-1, 4)
+    bones = _c(bones, np.float32).reshape(-1, 3, 4)
+    if not len(idx) == len(w) == len(v):
+        raise ValueError(f"mesh_skin: {len(v)} vertices, {len(idx)} index rows, {len(w)} weight rows")
+    out = np.zeros((len(v), 3), np.float32)
+    _check(lib().rt_mesh_skin(_p(v), len(v), _p(idx), _p(w), _p(bones), len(bones), _p(out)))
+    return out
+
+
 def default_params(**kw):
     p = Params()
     lib().rt_params_default(C.byref(p))
@@ -300,6 +313,62 @@ class Scene(_Handle):
             _check(lib().rt_scene_update_mesh_vertices_auto_flags(*mesh, max_ratio, keep, C.byref(q)))
             return q.as_dict()
         _check(lib().rt_scene_update_mesh_vertices_flags(*mesh, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
+
+    def set_mesh_skin(self, index, bone_index, weight, n_bones=None):
+        """binds a skin to mesh `index` (rt_mi355x.h, "mesh skinning"): four influences a vertex -- bone_index uint16 (nv, 4), weight
+        float32 (nv, 4), used as given -- with the positions the mesh holds now as the rest pose.  n_bones: None = the largest
+        index + 1."""
+        idx, w = _c(bone_index, np.uint16).reshape(-1, 4), _c(weight, np.float32).reshape(-1, 4)
+        if len(idx) != len(w):
+            raise ValueError(f"set_mesh_skin: {len(idx)} index rows, {len(w)} weight rows")
+        n = int(idx.max()) + 1 if n_bones is None else int(n_bones)
+        _check(lib().rt_scene_set_mesh_skin(self._h, int(index), n, _p(idx), _p(w), len(idx)))
+
+    def clear_mesh_skin(self, index):
+        """unbinds the skin of mesh `index`; the mesh keeps the positions it has"""
+        _check(lib().rt_scene_clear_mesh_skin(self._h, int(index)))
+
+    def mesh_skin(self, index):
+        """dict(bound, n_bones, nv, store_current): the skin of mesh `index`, and whether the store's positions are the last pose's
+        (0 while the host mirror still owes them: it runs when they are next read)"""
+        info = MeshSkinInfo(struct_size=C.sizeof(MeshSkinInfo))
+        _check(lib().rt_scene_mesh_skin_info(self._h, int(index), C.byref(info)))
+        return dict(bound=bool(info.bound), n_bones=info.n_bones, nv=info.nv, store_current=int(info.store_current))
+
+    def pose_mesh(self, index, bones, keep_previous=False, rebuild=False, max_ratio=None):
+        """poses the skinned mesh `index`: bones is float32 (n_bones, 3, 4), row-major, in the mesh's object space.  Everything else
+        is update_mesh_vertices(v=the posed positions, vn=None, ...) -- the same arguments, the same return values -- but the
+        positions are computed by k_mesh_skin on the devices that hold the scene, from 48 bytes a bone."""
+        device_build = isinstance(rebuild, str)
+        if device_build and rebuild != "device":
+            raise ValueError(f"pose_mesh: rebuild is {rebuild!r} (False, True or 'device')")
+        if max_ratio is not None and rebuild and not device_build:
+            raise ValueError("pose_mesh: rebuild=True and max_ratio exclude each other")
+        bones = _c(bones, np.float32).reshape(-1, 3, 4)
+        pose = (self._h, int(index), _p(bones), len(bones))
+        keep = MESH_UPDATE_KEEP_PREVIOUS if keep_previous else 0
+        if device_build:
+            b = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
+            if max_ratio is None:
+                _check(lib().rt_scene_pose_mesh_build(*pose, keep, C.byref(b)))
+                return b.as_dict()
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_pose_mesh_auto_build(*pose, keep, max_ratio, C.byref(q), C.byref(b)))
+            out = q.as_dict()
+            if b.flags:
+                out["build"] = b.as_dict()
+            return out
+        if max_ratio is not None:
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_pose_mesh_auto(*pose, keep, max_ratio, C.byref(q)))
+            return q.as_dict()
+        _check(lib().rt_scene_pose_mesh(*pose, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
+
+    def mesh_skin_ms(self, device=0):
+        """milliseconds of the last k_mesh_skin launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
+        ms = C.c_float()
+        _check(lib().rt_scene_mesh_skin_ms(self._h, device, C.byref(ms)))
+        return ms.value
 
     def set_mesh_normals(self, index, mode):
         """what an update without normals leaves mesh `index` with: "stored" (the default: the normals it had) or "smooth" -- its

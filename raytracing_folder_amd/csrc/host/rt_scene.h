@@ -322,6 +322,15 @@ struct MeshData {
     // v since vn was computed; vn is computed again for the v of now (rt_mesh_smooth_normals's arithmetic) when somebody reads it
     uint32_t normals_mode = 0;
     bool vn_stale = false;
+    // rt_scene_set_mesh_skin (rt_mi355x.h, "mesh skinning"): the skin -- n_bones (0: none bound), four influences a vertex, the
+    // rest pose -- and the last pose, 12 floats a bone.  v_stale: a pose replaced v since it was last written; v (whose size stays)
+    // is computed again from rest and pose (rt_mesh_skin's arithmetic) with root_box when somebody reads it (ensure_vertices).
+    // v_prev_stale: the same for v_prev, owed from pose_prev -- a flagged pose on a stale v hands the pose on, not the vertices.
+    int32_t skin_bones = 0;
+    std::vector<uint16_t> skin_index;
+    std::vector<float> skin_weight, skin_rest, pose, pose_prev;
+    bool v_stale = false, v_prev_stale = false;
+    uint32_t skin_serial = 0;            // counts the skins bound to this mesh: a device's copy of another one is uploaded again
 };
 struct SceneData {
     std::vector<rt_node> nodes;

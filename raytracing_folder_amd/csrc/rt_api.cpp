@@ -21,6 +21,7 @@
 #include "host/rt_scene.h"
 #include "rt_host.h"
 #include "rt_mesh_normals.h"
+#include "rt_mesh_skin.h"
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;       // the one message of rt_last_error(), whichever file failed
@@ -133,6 +134,7 @@ extern "C" rt_status rt_scene_set_nodes(rt_scene *s, const rt_node *nodes, int32
     return RT_OK;
 }
 
+static void drop_mesh_skin(rt::MeshData &m);
 extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const uint32_t *f, int32_t nf,
                                        const float *vn, int32_t nvn, const uint32_t *fn, const rt_bvh_node *nodes,
                                        int32_t nnodes, const uint32_t *elements)
@@ -157,13 +159,33 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     m.vt.clear(); m.ft.clear();
     m.v_prev.clear();                   // the faces may have changed: no pairing of old and new vertices is vouched for
     m.normals_mode = RT_MESH_NORMALS_STORED; m.vn_stale = false;      // ... and the caller has just brought the normals it wants
+    drop_mesh_skin(m);                  // ... and the vertex count may have: a skin is bound again by the caller
     s->geometry_changed();
     return RT_OK;
 }
 
+// the skin of a mesh and everything a pose left behind (caller holds s->mu, and has resolved v if the mesh is to keep its positions)
+static void drop_mesh_skin(rt::MeshData &m)
+{
+    m.skin_bones = 0;
+    for (std::vector<float> *a : {&m.skin_weight, &m.skin_rest, &m.pose, &m.pose_prev}) std::vector<float>().swap(*a);
+    std::vector<uint16_t>().swap(m.skin_index);
+    m.v_stale = m.v_prev_stale = false;
+    m.skin_serial++;
+}
+void ensure_vertices(rt::MeshData &m)
+{
+    if (m.v_prev_stale) mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), m.pose_prev.data(), m.v_prev.data());
+    m.v_prev_stale = false;
+    if (!m.v_stale) return;
+    mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), m.pose.data(), m.v.data());
+    rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
+    m.v_stale = false;
+}
 void ensure_reference_tree(rt::MeshData &m)
 {
     if (!m.tree_stale) return;
+    ensure_vertices(m);
     rt::BuildMeanSplitBVH(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), 4, m.nodes, m.elements);      // TriObj::Load's leaves of four
     m.tree_stale = false;
 }
@@ -182,6 +204,7 @@ static void smooth_normals_host(const float *v, const uint32_t *f, const uint32_
 void ensure_normals(rt::MeshData &m)
 {
     if (!m.vn_stale) return;
+    ensure_vertices(m);
     smooth_normals_host(m.v.data(), m.f.data(), m.fn.data(), m.f.size() / 3, m.vn.size() / 3, m.vn.data());
     m.vn_stale = false;
 }
@@ -190,6 +213,7 @@ static const rt::MeshData &mesh_with_tree(const rt_scene *s, int32_t mesh)
 {
     rt_scene *w = const_cast<rt_scene *>(s);
     std::lock_guard<std::mutex> lk(w->mu);
+    ensure_vertices(w->data.meshes[mesh]);
     ensure_reference_tree(w->data.meshes[mesh]);
     ensure_normals(w->data.meshes[mesh]);
     return w->data.meshes[mesh];
@@ -237,6 +261,82 @@ extern "C" rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t m
     std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
     if (rt_status st = check_mesh_set(s, mesh, "rt_scene_get_mesh_normals_mode")) return st;
     *mode = s->data.meshes[mesh].normals_mode;
+    return RT_OK;
+}
+
+// ---- mesh skinning (rt_mi355x.h, "mesh skinning"; the kernel: rt_mesh_skin.hip, the pose entry points: rt_mesh_update.cpp) -----
+// what the mirror and rt_scene_set_mesh_skin require of a skin (`who` names the entry point)
+static rt_status check_skin(const char *who, int32_t n_bones, const uint16_t *bone_index, const float *weight, int32_t nv)
+{
+    if (!bone_index || !weight || nv <= 0) return fail(RT_ERR_ARG, "%s: bone_index and weight are required (nv=%d)", who, nv);
+    if (n_bones < 1 || n_bones > RT_MESH_SKIN_MAX_BONES) return fail(RT_ERR_ARG, "%s: n_bones is %d (1 .. %d)", who, n_bones, RT_MESH_SKIN_MAX_BONES);
+    for (int64_t i = 0; i < 4LL * nv; i++) {
+        if (bone_index[i] >= n_bones) return fail(RT_ERR_ARG, "%s: vertex %lld names bone %u of %d", who, (long long)(i / 4), bone_index[i], n_bones);
+        if (!std::isfinite(weight[i]) || weight[i] < 0.0f) return fail(RT_ERR_ARG, "%s: vertex %lld has weight %g (weights must be finite and >= 0)", who, (long long)(i / 4), weight[i]);
+    }
+    return RT_OK;
+}
+rt_status check_pose(const char *who, const float *bones, int32_t n_bones)
+{
+    if (!bones) return fail(RT_ERR_ARG, "%s: bones is NULL", who);
+    for (int64_t i = 0; i < 12LL * n_bones; i++)
+        if (!std::isfinite(bones[i])) return fail(RT_ERR_ARG, "%s: bone %lld has an entry that is not finite", who, (long long)(i / 12));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_mesh_skin(const float *v_rest, int32_t nv, const uint16_t *bone_index, const float *weight, const float *bones, int32_t n_bones,
+                                  float *v_out)
+{
+    if (!v_rest || !v_out) return fail(RT_ERR_ARG, "rt_mesh_skin: v_rest and v_out are required");
+    rt_status st = check_skin("rt_mesh_skin", n_bones, bone_index, weight, nv);
+    if (st || (st = check_pose("rt_mesh_skin", bones, n_bones))) return st;
+    mesh_skin_host(v_rest, (uint64_t)nv, bone_index, weight, bones, v_out);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_set_mesh_skin(rt_scene *s, int32_t mesh, int32_t n_bones, const uint16_t *bone_index, const float *weight, int32_t nv)
+{
+    rt_status st = check_idle(s, "rt_scene_set_mesh_skin");
+    if (st || (st = check_skin("rt_scene_set_mesh_skin", n_bones, bone_index, weight, nv))) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = check_mesh_set(s, mesh, "rt_scene_set_mesh_skin"))) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    if ((size_t)nv != m.v.size() / 3) return fail(RT_ERR_ARG, "rt_scene_set_mesh_skin: nv is %d, the mesh has %zu vertices", nv, m.v.size() / 3);
+    ensure_vertices(m);                 // the rest pose is the positions of now
+    drop_mesh_skin(m);
+    release_mesh_skin_on_devices(s, mesh);
+    m.skin_bones = n_bones;
+    m.skin_index.assign(bone_index, bone_index + 4 * (size_t)nv);
+    m.skin_weight.assign(weight, weight + 4 * (size_t)nv);
+    m.skin_rest = m.v;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_clear_mesh_skin(rt_scene *s, int32_t mesh)
+{
+    rt_status st = check_idle(s, "rt_scene_clear_mesh_skin");
+    if (st) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = check_mesh_set(s, mesh, "rt_scene_clear_mesh_skin"))) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    ensure_vertices(m);                 // the mesh keeps the positions it has
+    drop_mesh_skin(m);
+    release_mesh_skin_on_devices(s, mesh);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_skin_info(const rt_scene *s, int32_t mesh, rt_mesh_skin_info *out)
+{
+    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_skin_info: NULL argument");
+    if (out->struct_size != sizeof(rt_mesh_skin_info))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_skin_info: rt_mesh_skin_info.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_skin_info));
+    std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+    if (rt_status st = check_mesh_set(s, mesh, "rt_scene_mesh_skin_info")) return st;
+    const rt::MeshData &m = s->data.meshes[mesh];
+    out->bound = m.skin_bones > 0;
+    out->n_bones = m.skin_bones;
+    out->nv = m.skin_bones > 0 ? (int32_t)(m.skin_rest.size() / 3) : 0;
+    out->store_current = !m.v_stale;
     return RT_OK;
 }
 

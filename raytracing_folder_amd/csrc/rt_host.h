@@ -110,7 +110,13 @@ struct DevMeshBufs {
     // corners of a row ascending, on the device from the mesh's first update in SMOOTH mode there (with f, which that kernel reads
     // too).  They follow the faces and fn, which stay: a device build keeps them.
     DevBuf nadj_off, nadj_corner;
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt, &nadj_off, &nadj_corner}) b->release(); }
+    // mesh skinning (rt_mesh_skin.hip): the skin -- rest pose, bone indices, weights -- on the device from the mesh's first pose there
+    // (skin_serial: which of the mesh's skins it is, MeshData::skin_serial), and the root record of the tree as a pose's tail reads it back
+    DevBuf skin_rest, skin_index, skin_weight;
+    uint32_t skin_serial = 0;
+    float root_rec_host[32];
+    void release_skin() { for (DevBuf *b : {&skin_rest, &skin_index, &skin_weight}) b->release(); }
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt, &nadj_off, &nadj_corner}) b->release(); release_skin(); }
 };
 // the scratch of a device tree build (MeshBuildScratch of rt_launch.h), the device's own: grown to the largest mesh built there
 struct MeshBuildBufs {
@@ -191,6 +197,8 @@ struct DeviceState {
     // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
     Event upd_ev[4]; int upd_levels = -1;
     Event nrm_ev[2]; bool nrm_timed = false;        // around the last k_mesh_normals here (rt_scene_mesh_normals_ms)
+    Event skin_ev[2]; bool skin_timed = false;      // around the last k_mesh_skin here (rt_scene_mesh_skin_ms)
+    DevBuf skin_bones;                  // the pose k_mesh_skin stages from: 48 bytes a bone, uploaded at every pose
     Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
     MeshBuildBufs build;                // device tree builds here
     // one of the two maps: its buffers with what the kernels see of it
@@ -206,6 +214,9 @@ struct DeviceState {
         for (Event &e : cost_ev) e = Event();
         for (Event &e : nrm_ev) e = Event();
         nrm_timed = false;
+        for (Event &e : skin_ev) e = Event();
+        skin_timed = false;
+        skin_bones.release();
         upd_levels = -1;
         for (Workspace &w : ws) w.release();
         for (int k = 0; k < 6; k++) t_out[k].release();
@@ -253,6 +264,13 @@ RT_HIDDEN void ensure_reference_tree(rt::MeshData &m);
 // rt_api.cpp: the stored normals of a mesh, computed again if an update in SMOOTH mode left them stale (caller holds s->mu); to
 // be called wherever m.vn is read
 RT_HIDDEN void ensure_normals(rt::MeshData &m);
+// rt_api.cpp: the stored positions of a skinned mesh (and its previous positions, and root_box), computed again if a pose left them
+// owed (caller holds s->mu); to be called wherever m.v or m.v_prev is read -- ensure_reference_tree and ensure_normals do
+RT_HIDDEN void ensure_vertices(rt::MeshData &m);
+// rt_api.cpp: RT_ERR_ARG unless every one of the pose's 12 n_bones floats is finite
+RT_HIDDEN rt_status check_pose(const char *who, const float *bones, int32_t n_bones);
+// rt_mesh_update.cpp: what the devices hold of one mesh's skin, released (caller holds s->mu; the scene is idle)
+RT_HIDDEN void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh);
 // rt_api.cpp: RT_ERR_ARG "<who>: mesh <mesh> was never set" unless rt_scene_set_mesh has given the scene that mesh (caller holds s->mu)
 RT_HIDDEN rt_status check_mesh_set(const rt_scene *s, int32_t mesh, const char *who);
 // rt_lower.cpp: the scene's objects as upload_scene lowers them, with the material of every node; an in-place mesh update sends the

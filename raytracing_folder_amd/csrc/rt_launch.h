@@ -262,6 +262,16 @@ struct MeshNormalsRequest {
     float *vn;
 };
 
+// One skinned mesh posed on a device (rt_mesh_skin.hip; the definition: rt_mi355x.h, "mesh skinning").  rest (nv x 3 floats),
+// bone_index (nv x 4 uint16, 8-byte aligned) and weight (nv x 4 floats, 16-byte aligned) are the skin as the store checked it:
+// every index below n_bones.  bones: the pose, n_bones x 12 floats, 16-byte aligned, n_bones in 1 .. 1024.  out (nv x 3 floats, not
+// rest) receives every posed position.
+struct MeshSkinRequest {
+    const float *rest; const uint16_t *bone_index; const float *weight;
+    const float *bones; uint32_t n_bones;
+    uint32_t nv; float *out;
+};
+
 // One measurement of a mesh's tree on a device (rt_refit.hip, k_bvh_cost; the definition: rt_mi355x.h, "mesh tree quality"): the
 // n_nodes (> 0, at most 2^28) records at `nodes`, one double per block of 256 terms to partials[0 .. ceil(4 n_nodes / 256)).
 // partials has room for one double more: under RT_COST_FOLD_DEVICE k_bvh_cost_fold leaves the sum of the others there.
@@ -387,6 +397,10 @@ hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R);
 // ---- rt_mesh_normals.hip: smooth normals of a deforming mesh -------------------------------------------------------------
 // on `st`: k_mesh_normals over the mesh's normals (ahead of k_mesh_retri, which copies them into the slots)
 hipError_t rtk_launch_mesh_normals(hipStream_t st, const MeshNormalsRequest &R);
+
+// ---- rt_mesh_skin.hip: a skinned mesh posed on the device ------------------------------------------------------------------
+// on `st`: k_mesh_skin over the mesh's vertices (ahead of k_mesh_normals and everything else that reads them)
+hipError_t rtk_launch_mesh_skin(hipStream_t st, const MeshSkinRequest &R);
 
 // ---- rt_bvh_build.hip: a mesh's tree built on the device ------------------------------------------------------------------
 // bytes of the sort's temporary storage for n_faces keys

@@ -386,6 +386,8 @@ static rt_status upload_scene(rt_scene *s, DeviceState *D)
     std::vector<DevObject> objs;
     std::vector<DevObjectBack> backs;
     for (int i = 0; i < nn; i++) xf[i] = xf_of(sd.nodes[i]);
+    // a posed mesh (rt_mi355x.h, "mesh skinning"): its positions and root box, which everything below reads, are the pose's
+    for (rt::MeshData &m : s->data.meshes) ensure_vertices(m);
     rt_status st;
     if ((st = lower_objects(sd, objs, backs, node_mat))) return st;
     if ((st = D->nodes.upload(xf.data(), xf.size() * sizeof(DevNodeXf)))) return st;

@@ -1,6 +1,7 @@
-// rt_mesh_update.cpp -- everything that changes a lowered mesh in place: the six rt_scene_update_mesh_vertices* entry points on one
-// entry path, their share of the scene store, and what they do on the devices that hold the scene -- the refit (rt_refit.hip), the
-// refitted tree's quality (k_bvh_cost), the device tree build (rt_bvh_build.hip), smooth normals (rt_mesh_normals.hip) -- behind
+// rt_mesh_update.cpp -- everything that changes a lowered mesh in place: the six rt_scene_update_mesh_vertices* and the four
+// rt_scene_pose_mesh* entry points on one entry path, their share of the scene store, and what they do on the devices that hold the
+// scene -- the refit (rt_refit.hip), the refitted tree's quality (k_bvh_cost), the device tree build (rt_bvh_build.hip), smooth
+// normals (rt_mesh_normals.hip), a skinned mesh's pose (rt_mesh_skin.hip) -- behind
 // one per-device upload and one loop over the devices; the host mirrors of the cost and of the build; the calls that read a mesh
 // back from a device.  rt_lower.cpp put the mesh there (upload_scene); rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
@@ -34,14 +35,45 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
     if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, nv, m.v.size() / 3);
     if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
         return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
-    if (keep_previous) m.v_prev.swap(m.v); else std::vector<float>().swap(m.v_prev);
+    // (a posed mesh: positions a pose still owes are resolved before they become the previous ones, and dropped otherwise)
+    if (keep_previous) { ensure_vertices(m); m.v_prev.swap(m.v); } else { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
     m.v.assign(v, v + 3 * (size_t)nv);
+    m.v_stale = false;
     // SMOOTH mode without normals: the devices compute them (begin_mesh_update), the store when they are next read -- not here
     if (vn) { m.vn.assign(vn, vn + 3 * (size_t)nvn); m.vn_stale = false; }
     else if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
     m.tree_stale = true;
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
     // a generated photon map was traced through the old shape (geometry_changed); the scene itself stays where it is refitted
+    s->drop_generated_photons();
+    return RT_OK;
+}
+
+// ... and a pose in the store (rt_mi355x.h, "mesh skinning"): the matrices and a mark, no per-vertex work -- v is owed from then on
+// (ensure_vertices), and so is root_box unless a device reports it.  keep_previous: the previous positions are the ones the mesh
+// had -- v itself where the store has it, the pose it is owed from where it does not.
+static rt_status store_mesh_pose(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, bool keep_previous, const char *who)
+{
+    rt_status st = check_mesh_set(s, mesh, who);
+    if (st) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    if (m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
+    if (n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, n_bones, m.skin_bones);
+    if ((st = check_pose(who, bones, n_bones))) return st;
+    if (!keep_previous) { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
+    else if (m.v_stale) {
+        m.pose_prev = m.pose;
+        if (m.v_prev.size() != m.v.size()) m.v_prev.resize(m.v.size());
+        m.v_prev_stale = true;
+    } else {
+        m.v_prev.swap(m.v);
+        m.v_prev_stale = false;
+        if (m.v.size() != m.v_prev.size()) m.v.resize(m.v_prev.size());
+    }
+    m.pose.assign(bones, bones + 12 * (size_t)n_bones);
+    m.v_stale = true;
+    if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
+    m.tree_stale = true;
     s->drop_generated_photons();
     return RT_OK;
 }
@@ -76,6 +108,69 @@ static rt_status enqueue_mesh_normals(DeviceState *D, const rt::MeshData &m, Dev
     return RT_OK;
 }
 
+// Skinning (rt_mi355x.h, "mesh skinning"), one device's share in the same two steps.  prepare: the skin -- rest pose, indices,
+// weights -- on the device from the mesh's first pose there, and room for the pose.  enqueue: the pose and the launch on the
+// update's stream, in place of the vertex upload and ahead of k_mesh_normals, between the events rt_scene_mesh_skin_ms reads.
+static rt_status prepare_mesh_skin(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    rt_status rs;
+    for (Event &e : D->skin_ev) if (!e.e) HIP_TRY(e.create());
+    if ((rs = D->skin_bones.ensure(m.pose.size() * 4))) return rs;
+    if (mb.skin_rest.p && mb.skin_serial == m.skin_serial) return RT_OK;
+    if ((rs = mb.skin_rest.upload(m.skin_rest.data(), m.skin_rest.size() * 4)) || (rs = mb.skin_index.upload(m.skin_index.data(), m.skin_index.size() * 2)) ||
+        (rs = mb.skin_weight.upload(m.skin_weight.data(), m.skin_weight.size() * 4))) return rs;
+    mb.skin_serial = m.skin_serial;
+    return RT_OK;
+}
+static rt_status enqueue_mesh_skin(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    MeshSkinRequest K = {};
+    K.rest = (const float *)mb.skin_rest.p; K.bone_index = (const uint16_t *)mb.skin_index.p; K.weight = (const float *)mb.skin_weight.p;
+    K.bones = (const float *)D->skin_bones.p; K.n_bones = (uint32_t)m.skin_bones;
+    K.nv = (uint32_t)(m.skin_rest.size() / 3); K.out = (float *)mb.v.p;
+    HIP_TRY(hipMemcpyAsync(D->skin_bones.p, m.pose.data(), m.pose.size() * 4, hipMemcpyHostToDevice, D->stream));
+    HIP_TRY(hipEventRecord(D->skin_ev[0], D->stream));
+    HIP_TRY(rtk_launch_mesh_skin(D->stream, K));
+    HIP_TRY(hipEventRecord(D->skin_ev[1], D->stream));
+    D->skin_timed = true;
+    return RT_OK;
+}
+void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh)
+{
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    for (DeviceState *D : s->devs)
+        if ((size_t)mesh < D->mesh_bufs.size() && D->mesh_bufs[mesh].skin_rest.p && hipSetDevice(D->device) == hipSuccess) D->mesh_bufs[mesh].release_skin();
+    if (!s->devs.empty()) (void)hipSetDevice(cur);
+}
+
+// Where an update's new vertices come from on a device: the store (uploaded), the skin (k_mesh_skin writes them from the pose the
+// store holds), or nowhere -- they are on the device already, behind the refit of the same call.
+enum VertexSource { VERTICES_FROM_STORE, VERTICES_FROM_SKIN, VERTICES_ON_DEVICE };
+
+// the box of a tree's root record: per axis the smallest lo and the largest hi over its used children (lo[axis][child],
+// hi[axis][child]; an unused child has a NaN lo on x) -- the exact min / max of the vertices under the faces, MeshRootBox's box
+static void root_box_of_record(const float *rec, float box[6])
+{
+    bool any = false;
+    for (uint32_t c = 0; c < 4; c++) {
+        if (rec[c] != rec[c]) continue;
+        for (int a = 0; a < 3; a++) {
+            const float l = rec[4 * a + c], h = rec[12 + 4 * a + c];
+            if (!any || l < box[a]) box[a] = l;
+            if (!any || h > box[a + 3]) box[a + 3] = h;
+        }
+        any = true;
+    }
+}
+// the objects lowered again once a posed mesh's root box is known (the first device's tail; the later devices get these)
+static rt_status relower_objects(const rt::SceneData &sd, std::vector<DevObject> &objs)
+{
+    std::vector<DevObjectBack> backs;
+    std::vector<int32_t> node_mat;
+    return lower_objects(sd, objs, backs, node_mat);
+}
+
 // tex of the mesh follows texture vertices the store still has (a device build writes it again from them)
 static bool mesh_textured(const DevMeshBufs &mb, const rt::MeshData &m) { return mb.tex.p != nullptr && !m.vt.empty() && m.ft.size() == m.f.size(); }
 
@@ -84,9 +179,12 @@ static bool mesh_textured(const DevMeshBufs &mb, const rt::MeshData &m) { return
 // buffers, the upload between ev[0] and ev[1] (ev: the caller's n_ev events, all made here), smooth normals behind it.
 // with_faces: the device build's arrays -- f, fn and, for a textured mesh, ft and vt -- on the device from the mesh's first build
 // there.  reserve (may be empty): what else the caller's tail allocates, ahead of ev[0] so that nothing is allocated between
-// the events.
+// the events.  src: VERTICES_FROM_SKIN puts the pose's 48 bytes a bone and k_mesh_skin in the vertex upload's place, and a flagged
+// pose makes the buffer the positions were in the previous positions' -- two pointers swapped, nothing uploaded; VERTICES_ON_DEVICE
+// leaves positions and previous positions as the refit of the same call left them.
 static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, size_t n_objects, const char *who,
-                                   Event *ev, size_t n_ev, bool with_faces, const std::function<rt_status()> &reserve)
+                                   Event *ev, size_t n_ev, bool with_faces, const std::function<rt_status()> &reserve,
+                                   VertexSource src = VERTICES_FROM_STORE)
 {
     HIP_TRY(hipSetDevice(D->device));
     if (D->last_pending && D->last_done) HIP_TRY(hipEventSynchronize(D->last_done));      // an asynchronous render may still be tracing this mesh
@@ -102,23 +200,30 @@ static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh
     const bool textured = mesh_textured(mb, m);
     // SMOOTH mode and no normals brought: the device computes them from the vertices it is about to be sent
     const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;
+    const bool skin = src == VERTICES_FROM_SKIN;
+    // a flagged pose on a device that has the positions: they become the previous ones where they are
+    const bool swap_prev = skin && !m.v_prev.empty() && mb.v.p != nullptr;
+    const bool upload_prev = src != VERTICES_ON_DEVICE && !m.v_prev.empty() && !swap_prev;
+    if (swap_prev) std::swap(mb.v, mb.v_prev);
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
+    if (skin && (rs = prepare_mesh_skin(D, m, mb))) return rs;
     if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
     // the store's normals are about to be read: never stale ones over what k_mesh_normals wrote here (the first time they are
-    // the values the kernel's kept normals keep)
-    if (first || normals_changed) ensure_normals(m);
+    // the values the kernel's kept normals keep -- which stale ones are as well: a pose does not resolve the store for them)
+    if ((first || normals_changed) && !(skin && smooth)) ensure_normals(m);
     // the previous positions follow the store: uploaded from it ahead of the new vertices, in the update's stream, by a flagged
     // update; released by an unflagged one (nothing is allocated, copied or freed for a mesh that never used the flag)
-    if (m.v_prev.empty()) mb.v_prev.release();
-    else if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs;
+    if (upload_prev) { if (m.v_prev_stale) ensure_vertices(m); if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs; }
+    else if (m.v_prev.empty() && src != VERTICES_ON_DEVICE) mb.v_prev.release();
     if (faces) {
         if ((rs = mb.f.ensure(m.f.size() * 4)) || (rs = mb.fn.ensure(m.fn.size() * 4))) return rs;
         if (textured && ((rs = mb.ft.ensure(m.ft.size() * 4)) || (rs = mb.vt.ensure(m.vt.size() * 4)))) return rs;
     }
     if (reserve && (rs = reserve())) return rs;
     HIP_TRY(hipEventRecord(ev[0], st));
-    if (!m.v_prev.empty()) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
+    if (upload_prev) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
+    if (skin) { if ((rs = enqueue_mesh_skin(D, m, mb))) return rs; }
+    else if (src == VERTICES_FROM_STORE) HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
     if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
     if (faces) {
         HIP_TRY(hipMemcpyAsync(mb.f.p, m.f.data(), m.f.size() * 4, hipMemcpyHostToDevice, st));
@@ -198,12 +303,14 @@ static rt_status finish_mesh_cost(DeviceState *D, const DevMeshBufs &mb, rt_mesh
 // DevTri and nrm of every slot and every box of the tree (rt_refit.hip), DevMesh::root_box, and the objects' cull boxes (objs: the
 // scene's objects lowered again by the caller).  Nothing else on the device depends on a mesh's vertices: the tree's topology,
 // stack_need (DevScene::max_bvh_depth, the spill buffers) and tex follow the faces, which stay.  quality (may be NULL): the
-// refitted tree, measured behind the refit on the same stream.
-static rt_status refit_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
-                                      rt_mesh_quality *quality)
+// refitted tree, measured behind the refit on the same stream.  box_for (NULL, or the scene of a pose no device has reported for
+// yet): the host does not have the posed vertices, so m.root_box is read from the refitted tree's root record -- a second short
+// synchronise -- and objs is lowered again from it, for this device and the ones after it.
+static rt_status refit_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, std::vector<DevObject> &objs,
+                                      rt_mesh_quality *quality, VertexSource src, const rt::SceneData *box_for)
 {
     rt_status rs;
-    if ((rs = begin_mesh_update(D, m, mesh, normals_changed, objs.size(), "rt_scene_update_mesh_vertices", D->upd_ev, 4, false, nullptr))) return rs;
+    if ((rs = begin_mesh_update(D, m, mesh, normals_changed, objs.size(), "rt_scene_update_mesh_vertices", D->upd_ev, 4, false, nullptr, src))) return rs;
     DevMeshBufs &mb = D->mesh_bufs[mesh];
     hipStream_t st = D->stream;
     MeshRefitRequest R = {};
@@ -215,9 +322,16 @@ static rt_status refit_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t m
     HIP_TRY(rtk_launch_mesh_refit(st, R));
     HIP_TRY(hipEventRecord(D->upd_ev[3], st));
     D->upd_levels = R.n_levels;
+    if (box_for) {
+        HIP_TRY(hipMemcpyAsync(mb.root_rec_host, (const DevBvhNode *)mb.nodes.p + mb.root_ref, sizeof(DevBvhNode), hipMemcpyDeviceToHost, st));
+        if (quality && (rs = enqueue_mesh_cost(D, mb))) return rs;
+        HIP_TRY(hipStreamSynchronize(st));
+        root_box_of_record(mb.root_rec_host, m.root_box);
+        if ((rs = relower_objects(*box_for, objs))) return rs;
+    }
     HIP_TRY(hipMemcpyAsync((char *)D->meshes.p + (size_t)mesh * sizeof(DevMesh) + offsetof(DevMesh, root_box), m.root_box, 24, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(D->objects.p, objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice, st));
-    if (quality && (rs = enqueue_mesh_cost(D, mb))) return rs;
+    if (quality && !box_for && (rs = enqueue_mesh_cost(D, mb))) return rs;
     HIP_TRY(hipStreamSynchronize(st));
     return quality ? finish_mesh_cost(D, mb, quality) : RT_OK;
 }
@@ -260,9 +374,10 @@ static int lbvh_stack_cap()
 // again -- the record count and DevMesh::nodes / root_ref, slot_face, level_off and level_nodes, stack_need with
 // DevScene::max_bvh_depth and the spill buffers, built_cost.  Two host synchronisations: one for the record count, the levels and
 // stack_need (the cost launch and the fallback decision need them), one at the end.
-// *fell_back: the tree needs more stack than `cap`; the device is left for the caller to invalidate.
-static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, const std::vector<DevObject> &objs,
-                                      int cap, rt_mesh_build_info *info, bool *fell_back)
+// *fell_back: the tree needs more stack than `cap`; the device is left for the caller to invalidate.  src and box_for: as in the
+// refit -- here the root record comes with the first synchronise's copies, so a pose costs this tail no further one.
+static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, std::vector<DevObject> &objs,
+                                      int cap, rt_mesh_build_info *info, bool *fell_back, VertexSource src, const rt::SceneData *box_for)
 {
     MeshBuildBufs &B = D->build;
     const size_t nf = m.f.size() / 3;
@@ -279,7 +394,7 @@ static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t m
         if (nf > RT_LBVH_LEAF_TRIS && (r = mb.nodes.ensure(nf * sizeof(DevBvhNode)))) return r;      // (may move: DevMesh::nodes is set again below)
         return mb.level_nodes.ensure(nf * 4);
     };
-    if ((rs = begin_mesh_update(D, m, mesh, normals_changed, objs.size(), "rt_scene_update_mesh_vertices_build", B.ev, 6, true, reserve))) return rs;
+    if ((rs = begin_mesh_update(D, m, mesh, normals_changed, objs.size(), "rt_scene_update_mesh_vertices_build", B.ev, 6, true, reserve, src))) return rs;
     DevMeshBufs &mb = D->mesh_bufs[mesh];
     hipStream_t st = D->stream;
     const bool textured = mesh_textured(mb, m);
@@ -305,6 +420,7 @@ static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t m
     B.slot_face_host.resize(nf);
     HIP_TRY(hipMemcpyAsync(B.result_host.data(), B.result.p, RT_LBVH_RESULT_WORDS * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(B.slot_face_host.data(), B.slot_face.p, nf * 4, hipMemcpyDeviceToHost, st));
+    if (box_for) HIP_TRY(hipMemcpyAsync(mb.root_rec_host, mb.nodes.p, sizeof(DevBvhNode), hipMemcpyDeviceToHost, st));      // (record 0 is the root: the caller keeps a root leaf away)
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t n_nodes = B.result_host[0], levels = B.result_host[1];
     const int need = (int)B.result_host[2];
@@ -319,6 +435,10 @@ static rt_status build_mesh_on_device(DeviceState *D, rt::MeshData &m, int32_t m
         HIP_TRY(hipEventElapsedTime(&info->slots_ms, B.ev[4], B.ev[5]));
     }
     if (B.result_host[3] || need > cap || n_nodes > nf || levels > RT_LBVH_MAX_LEVELS) { *fell_back = true; return RT_OK; }
+    if (box_for) {
+        root_box_of_record(mb.root_rec_host, m.root_box);
+        if ((rs = relower_objects(*box_for, objs))) return rs;
+    }
     // what follows the topology, on the host: slot order, root, need, the levels as the refit wants them (deepest first; numbering
     // is breadth-first, so depth d is the index range [at[d], at[d + 1]) and level_nodes is those ranges in reverse order)
     const uint32_t *at = B.result_host.data() + 4;
@@ -383,7 +503,7 @@ template <class Step> static rt_status on_devices_holding_scene(rt_scene *s, Ste
         DeviceClaim claim(D);
         rt_status r = st;
         if (!r && claim.ok && !stop) {
-            r = step(D, objs, !succeeded, &stop);
+            r = step(D, objs, !succeeded, &stop);      // (objs by reference: a pose's first step lowers them again)
             succeeded = succeeded || !r;
         }
         if (r || !claim.ok || stop) D->scene_valid = false;
@@ -396,13 +516,14 @@ template <class Step> static rt_status on_devices_holding_scene(rt_scene *s, Ste
 
 // the refit on those devices.  quality: NULL, or where the first device that refits leaves the refitted tree's measure; flags
 // RT_MESH_QUALITY_NOT_ON_DEVICE when none got as far (none holds the scene, all in use, or failed)
-static rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality)
+static rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_quality *quality, VertexSource src)
 {
     if (quality) { quality->flags = RT_MESH_QUALITY_NOT_ON_DEVICE; quality->cost = quality->built_cost = 0.0; quality->ratio = 1.0; quality->measure_ms = 0.0f; }
-    return on_devices_holding_scene(s, [&](DeviceState *D, const std::vector<DevObject> &objs, bool first, bool *) {
+    return on_devices_holding_scene(s, [&](DeviceState *D, std::vector<DevObject> &objs, bool first, bool *) {
         rt_mesh_quality mine = {};
         const bool measure = quality && first;
-        const rt_status r = refit_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, measure ? &mine : nullptr);
+        const rt_status r = refit_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, measure ? &mine : nullptr, src,
+                                                 src == VERTICES_FROM_SKIN && first ? &s->data : nullptr);
         if (!r && measure) { mine.struct_size = quality->struct_size; *quality = mine; }
         return r;
     });
@@ -411,15 +532,16 @@ static rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_c
 // the device build on those devices.  info: the first building device's figures; flags ON_DEVICE, NOT_ON_DEVICE, or FELL_BACK -- a
 // tree with stack_need above the limit.  The same mesh gives the same tree on every device: one that does not fit fits nowhere, no
 // further device builds, and the call takes RT_MESH_UPDATE_REBUILD's path
-static rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info)
+static rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_changed, rt_mesh_build_info *info, VertexSource src)
 {
     const rt_mesh_build_info none = {sizeof(rt_mesh_build_info), RT_MESH_BUILD_NOT_ON_DEVICE};
     *info = none;
     const int cap = lbvh_stack_cap();
     bool fell_back = false;
-    const rt_status ret = on_devices_holding_scene(s, [&](DeviceState *D, const std::vector<DevObject> &objs, bool first, bool *stop) {
+    const rt_status ret = on_devices_holding_scene(s, [&](DeviceState *D, std::vector<DevObject> &objs, bool first, bool *stop) {
         rt_mesh_build_info mine = none;
-        const rt_status r = build_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, cap, &mine, stop);
+        const rt_status r = build_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, cap, &mine, stop, src,
+                                                 src == VERTICES_FROM_SKIN && first ? &s->data : nullptr);
         if (!r && first) { *info = mine; info->flags = *stop ? RT_MESH_BUILD_FELL_BACK : RT_MESH_BUILD_ON_DEVICE; }
         return r;
     }, &fell_back);
@@ -435,9 +557,24 @@ enum UpdateAfter { UPDATE_REFIT, UPDATE_REFIT_MEASURE, UPDATE_BUILD, UPDATE_REFI
 // of it (the entry points it is one of word a refused flag their own way), and `after`.  The out-structs need no column: an
 // entry point passes NULL for the one it does not have.
 struct UpdateEntry { const char *who; uint32_t known; bool takes_ratio; UpdateAfter after; };
+// the other way the new vertices arrive: a pose of the mesh's skin (rt_scene_pose_mesh*) in place of v, nv, vn, nvn
+struct MeshPose { const float *bones; int32_t n_bones; };
+
+// A pose is skinned on the devices unless the mesh's tree there is a single leaf -- no root record to read the box from; the mesh is
+// tiny -- in which case the store resolves it now and the update goes the way of one that brought the vertices (caller holds s->mu)
+static VertexSource pose_source(rt_scene *s, int32_t mesh)
+{
+    rt::MeshData &m = s->data.meshes[mesh];
+    bool leaf = false;
+    for (DeviceState *D : s->devs)
+        if (D->scene_valid) leaf = leaf || m.f.size() / 3 <= RT_LBVH_LEAF_TRIS || ((size_t)mesh < D->mesh_bufs.size() && (D->mesh_bufs[mesh].root_ref & RT_COST_LEAF));
+    if (!leaf) return VERTICES_FROM_SKIN;
+    ensure_vertices(m);
+    return VERTICES_FROM_STORE;
+}
 
 static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                      uint32_t flags, double max_ratio, rt_mesh_quality *q_out, rt_mesh_build_info *b_out)
+                                      uint32_t flags, double max_ratio, rt_mesh_quality *q_out, rt_mesh_build_info *b_out, const MeshPose *pose = nullptr)
 {
     rt_status st = check_idle(s, e.who);
     if (st) return st;
@@ -448,23 +585,25 @@ static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t
         return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", e.who, q_out->struct_size, sizeof(rt_mesh_quality));
     if (b_out && b_out->struct_size != sizeof(rt_mesh_build_info))
         return fail(RT_ERR_ARG, "%s: rt_mesh_build_info.struct_size is %u, this library's is %zu", e.who, b_out->struct_size, sizeof(rt_mesh_build_info));
-    if (!v) return fail(RT_ERR_ARG, "%s: v is NULL", e.who);
+    if (!pose && !v) return fail(RT_ERR_ARG, "%s: v is NULL", e.who);
     std::lock_guard<std::mutex> lk(s->mu);
-    if ((st = store_mesh_vertices(s, mesh, v, nv, vn, nvn, (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0, e.who))) return st;
+    const bool keep_previous = (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0;
+    if ((st = pose ? store_mesh_pose(s, mesh, pose->bones, pose->n_bones, keep_previous, e.who) : store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep_previous, e.who))) return st;
     if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }      // (the next lowering uploads the previous positions from the store)
+    const VertexSource src = pose ? pose_source(s, mesh) : VERTICES_FROM_STORE;
     const bool normals_changed = vn != nullptr, measure = e.after == UPDATE_REFIT_MEASURE || e.after == UPDATE_REFIT_MEASURE_BUILD;
     rt_mesh_quality q = {sizeof(rt_mesh_quality)};
     rt_mesh_build_info b = {sizeof(rt_mesh_build_info)};
     bool build = e.after == UPDATE_BUILD;
-    if (!build) st = refit_mesh_on_devices(s, mesh, normals_changed, measure ? &q : nullptr);
+    if (!build) st = refit_mesh_on_devices(s, mesh, normals_changed, measure ? &q : nullptr, src);
     // a degenerate measure has ratio 1, and so has a scene no device holds: neither asks for a rebuild
     if (measure && !st && q.ratio > max_ratio) {
         q.flags |= RT_MESH_QUALITY_REBUILT;
         if (e.after == UPDATE_REFIT_MEASURE_BUILD) build = true; else s->invalidate(true, false);
     }
     // (behind a refit the vertices are on the devices already; the build sends them again with everything else it does, normals
-    // only if this call brought some)
-    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b);
+    // only if this call brought some; a pose is not skinned twice: its vertices stay where the refit's k_mesh_skin wrote them)
+    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b, src == VERTICES_FROM_SKIN && e.after != UPDATE_BUILD ? VERTICES_ON_DEVICE : src);
     if (q_out) *q_out = q;
     if (b_out) *b_out = b;
     return st;
@@ -507,6 +646,34 @@ extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32
     return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, max_ratio, q_out, out);
 }
 
+// the same four forms fed by a pose (rt_mi355x.h, "mesh skinning"): the flag bits and out-structs of their counterparts above
+extern "C" rt_status rt_scene_pose_mesh(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags)
+{
+    static const UpdateEntry e = {"rt_scene_pose_mesh", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
+    const MeshPose pose = {bones, n_bones};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, nullptr, &pose);
+}
+extern "C" rt_status rt_scene_pose_mesh_auto(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
+                                             rt_mesh_quality *out)
+{
+    static const UpdateEntry e = {"rt_scene_pose_mesh_auto", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
+    const MeshPose pose = {bones, n_bones};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, out, nullptr, &pose);
+}
+extern "C" rt_status rt_scene_pose_mesh_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, rt_mesh_build_info *out)
+{
+    static const UpdateEntry e = {"rt_scene_pose_mesh_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
+    const MeshPose pose = {bones, n_bones};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, out, &pose);
+}
+extern "C" rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
+                                                   rt_mesh_quality *q_out, rt_mesh_build_info *out)
+{
+    static const UpdateEntry e = {"rt_scene_pose_mesh_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
+    const MeshPose pose = {bones, n_bones};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, q_out, out, &pose);
+}
+
 // ---- what the last update took ---------------------------------------------------------------------------------------------
 extern "C" rt_status rt_scene_mesh_update_ms(rt_scene *s, int device, rt_mesh_update_ms *out)
 {
@@ -528,6 +695,15 @@ extern "C" rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms
     DeviceState *D = find_device_state(s, device);
     if (!D || !D->nrm_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_normals_ms: device %d has not computed a mesh's normals", device);
     HIP_TRY(hipEventElapsedTime(ms, D->nrm_ev[0], D->nrm_ev[1]));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms)
+{
+    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_skin_ms: NULL argument");
+    DeviceState *D = find_device_state(s, device);
+    if (!D || !D->skin_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_skin_ms: device %d has not posed a mesh", device);
+    HIP_TRY(hipEventElapsedTime(ms, D->skin_ev[0], D->skin_ev[1]));
     return RT_OK;
 }
 

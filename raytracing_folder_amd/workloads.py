@@ -93,6 +93,43 @@ def deform_wave(v, phase, amplitude):
     return (v + float(amplitude) * d).astype(np.float32)
 
 
+def bone_chain(v, n_bones, axis=0):
+    """a skin for vertices v (Scene.set_mesh_skin): n_bones bones evenly spaced along `axis` over the mesh's extent, every vertex
+    weighted linearly between its two nearest bones, the other two influences weight 0 (on bone 0).  Returns bone_index uint16
+    (nv, 4) and weight float32 (nv, 4)."""
+    v = np.asarray(v, np.float32).reshape(-1, 3).astype(np.float64)
+    n_bones = int(n_bones)
+    x = v[:, axis]
+    lo, hi = x.min(), x.max()
+    t = (x - lo) / (hi - lo if hi > lo else 1.0) * (n_bones - 1)       # the vertex in bone spacings: bone b sits at t = b
+    b0 = np.clip(np.floor(t).astype(np.int64), 0, max(n_bones - 2, 0))
+    b1 = np.minimum(b0 + 1, n_bones - 1)
+    w1 = (t - b0) if n_bones > 1 else np.zeros_like(t)
+    index = np.zeros((len(v), 4), np.uint16)
+    weight = np.zeros((len(v), 4), np.float32)
+    index[:, 0], index[:, 1] = b0, b1
+    weight[:, 0], weight[:, 1] = 1.0 - w1, w1
+    return index, weight
+
+
+def chain_pose(n_bones, angle, origin, axis):
+    """a pose for bone_chain's skin (Scene.pose_mesh): a cumulative bend of `angle` radians per joint about the direction `axis`
+    through `origin` -- bone 0 stays, bone b is bone b - 1's transform followed by one more rotation -- composed in float64 and
+    rounded once.  float32 (n_bones, 3, 4), row-major [R | t]."""
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    o = np.asarray(origin, np.float64)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)     # Rodrigues
+    step = np.eye(4)
+    step[:3, :3], step[:3, 3] = R, o - R @ o
+    out, M = np.zeros((int(n_bones), 3, 4), np.float64), np.eye(4)
+    for b in range(int(n_bones)):
+        out[b] = M[:3]
+        M = step @ M
+    return out.astype(np.float32)
+
+
 def sheet(n, extent):
     """an open sheet of n x n quads in the plane z = 0, |x|, |y| <= extent / 2: (n + 1)^2 shared vertices, 2 n^2 triangles wound
     so that the face normals point to +z.  float32 (nv, 3), uint32 (nf, 3); sheet(1) is one leaf of the device tree"""
