@@ -693,6 +693,75 @@ rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *
  * has run none.  Like k_mesh_normals it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
 rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms);
 
+/* ---- morph targets (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
+ *      unchanged) ---------------------------------------------------------------------------------------------------------------
+ * A third source of new vertices for the in-place update: blend shapes on the device, ahead of the skin.  A morph set is bound to a
+ * mesh once; after that a frame brings one weight a target -- and, for a skinned mesh, its bones -- and k_mesh_morph
+ * (csrc/rt_mesh_morph.hip) writes the positions where the refit, the device build, k_mesh_normals and k_motion_mesh read them.
+ * The definition fixes every operation and its order, so that the kernel and the host mirror (rt_mesh_morph) give the same bytes;
+ * the arithmetic is written once, in csrc/rt_mesh_morph.h.
+ *
+ * A morph set belongs to one mesh of a scene: n_targets (1 .. RT_MESH_MORPH_MAX_TARGETS); the deltas, float32[n_targets][nv][3],
+ *           dense, in the mesh's object space, every one finite; and the BASE, a copy of the positions the mesh holds when the
+ *           set is bound.
+ * Weights   A frame brings float32[n_targets], every one finite, of any sign and size: negative weights and weights above 1 are
+ *           used as given.
+ * The morphed position of vertex i with base (x, y, z), for each component c:
+ *               acc = base[i][c]
+ *               for t ascending over the targets with weights[t] != 0:   acc = acc + weights[t] * deltas[t][i][c]
+ *           Every * and + is one IEEE float32 operation, rounded to nearest; nothing is fused.  A target whose weight is +0 or -0
+ *           is SKIPPED, not multiplied: with every weight zero the result is the base byte for byte, a -0.0 coordinate included
+ *           (-0 + (+0) would be +0).
+ * With a skin   When the pose also brings bones, the posed position is the formula of "mesh skinning" applied to the morphed
+ *           position in place of the skin's rest position (x, y, z); the skin's own rest pose is not read.
+ * Normals   A morph pose brings none, exactly as a bone pose: RT_MESH_NORMALS_STORED keeps the stored normals,
+ *           RT_MESH_NORMALS_SMOOTH recomputes them from the new positions (k_mesh_normals on the devices, the mirror in the store).
+ *
+ * rt_mesh_morph is the host mirror: plain C++, no scene, no GPU, no HIP call, on bare arrays; v_out (nv x 3 floats) may be v_base.
+ * RT_ERR_ARG and nothing written: a NULL array, nv <= 0, n_targets outside 1 .. RT_MESH_MORPH_MAX_TARGETS, a delta or a weight
+ * that is not finite. */
+#define RT_MESH_MORPH_MAX_TARGETS 256
+rt_status rt_mesh_morph(const float *v_base, int32_t nv, const float *deltas, int32_t n_targets, const float *weights, float *v_out);
+/* Binds a morph set to a mesh: the deltas are copied, the base is taken from the store's current vertices (positions a pose still
+ * owes are resolved first), and nv must be the mesh's.  A refused argument is RT_ERR_ARG and nothing changes.  A set already bound
+ * is replaced.  rt_scene_set_mesh drops the set; a plain rt_scene_update_mesh_vertices* call keeps it and simply replaces the
+ * current positions (the next morph starts from the base again); a plain rt_scene_pose_mesh* call on a mesh with a set bound does
+ * what it does without one (it skins the skin's rest pose).  The scene must be idle. */
+rt_status rt_scene_set_mesh_morphs(rt_scene *s, int32_t mesh, int32_t n_targets, const float *deltas, int32_t nv);
+/* Unbinds it (RT_OK when there is none): the mesh keeps the positions it has, and what the devices held of the set is released. */
+rt_status rt_scene_clear_mesh_morphs(rt_scene *s, int32_t mesh);
+/* bound: 0 / 1, with n_targets and nv of the set (0 when none is bound).  store_current: as rt_mesh_skin_info's -- 0 while the
+ * store's positions are still owed by the mirrors (rt_mesh_morph, then rt_mesh_skin if bones came), which run when the positions
+ * are next read.  struct_size must be the caller's sizeof (else RT_ERR_ARG). */
+typedef struct rt_mesh_morph_info {
+    uint32_t struct_size;
+    uint32_t bound;
+    int32_t  n_targets, nv;
+    uint32_t store_current;
+} rt_mesh_morph_info;
+rt_status rt_scene_mesh_morph_info(const rt_scene *s, int32_t mesh, rt_mesh_morph_info *out);
+/* The morph pose: rt_scene_pose_mesh with the vertices of the definition above, on the same entry path -- the same flags, the same
+ * statuses, the same store discipline.  bones == NULL with n_bones == 0 is morph only; bones given is morph, then skin, and a skin
+ * must be bound (n_bones the skin's).  On every device that holds the scene the base and the deltas go up once, at the mesh's first
+ * morph pose there; a pose uploads the ACTIVE LIST -- (target, weight) of the non-zero weights, ascending, at most 2 KB -- and with
+ * bones their 48 bytes each, and launches k_mesh_morph once.  KEEP_PREVIOUS, the root box, the single-leaf mesh and a scene no
+ * device holds are as for rt_scene_pose_mesh.  RT_ERR_STATE: no morph set, or bones and no skin; RT_ERR_ARG: n_targets is not the
+ * set's, n_bones not the skin's (or not 0 without bones), a weight or a bone that is not finite; nothing changes then. */
+rt_status rt_scene_morph_mesh(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                              uint32_t flags);
+/* ... as rt_scene_pose_mesh_auto */
+rt_status rt_scene_morph_mesh_auto(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                   uint32_t flags, double max_ratio, rt_mesh_quality *out);
+/* ... as rt_scene_pose_mesh_build */
+rt_status rt_scene_morph_mesh_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                    uint32_t flags, rt_mesh_build_info *out);
+/* ... as rt_scene_pose_mesh_auto_build */
+rt_status rt_scene_morph_mesh_auto_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones,
+                                         int32_t n_bones, uint32_t flags, double max_ratio, rt_mesh_quality *q, rt_mesh_build_info *out);
+/* Milliseconds of the last k_mesh_morph launch on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
+ * has run none.  Like k_mesh_skin it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
+rt_status rt_scene_mesh_morph_ms(rt_scene *s, int device, float *ms);
+
 /* ---- host helpers that mirror reference host code --------------------------------------- */
 /* cyBVH build with MeanSplit (FIN/include/cyBVH.h:122-142,295-328) as TriObj::Load calls it
  * (maxElementsPerNode = 4, FIN/include/objects.h:143).  nodes_out needs room for 2*nf+1

@@ -221,6 +221,11 @@ class MeshSkinInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bound", C.c_uint32), ("n_bones", C.c_int32), ("nv", C.c_int32), ("store_current", C.c_uint32)]
 
 
+class MeshMorphInfo(C.Structure):
+    """rt_mesh_morph_info: the morph set bound to a mesh, and whether the store's positions are the last pose's (rt_scene_mesh_morph_info)"""
+    _fields_ = [("struct_size", C.c_uint32), ("bound", C.c_uint32), ("n_targets", C.c_int32), ("nv", C.c_int32), ("store_current", C.c_uint32)]
+
+
 class SetupMs(C.Structure):
     """rt_setup_ms: wall time of the stages of rt_scene_generate_photons, milliseconds"""
     _fields_ = [(n, C.c_double) for n in ("photon_pass", "balance", "structure_build", "upload", "total")]
@@ -265,6 +270,8 @@ MESH_NORMALS_SMOOTH = 1
 
 # the most bones a skin can have (include/rt_mi355x.h, "mesh skinning")
 MESH_SKIN_MAX_BONES = 1024
+# the most targets a morph set can have (include/rt_mi355x.h, "morph targets")
+MESH_MORPH_MAX_TARGETS = 256
 
 # rt_scene_set_render_flags bits (include/rt_mi355x.h): byte-identical renders for identical inputs
 RENDER_REPRODUCIBLE = 1
@@ -350,6 +357,15 @@ SIGNATURES = {
     "rt_scene_pose_mesh_build": (st, [vp, i32, vp, i32, u32, vp]),
     "rt_scene_pose_mesh_auto_build": (st, [vp, i32, vp, i32, u32, f64, vp, vp]),
     "rt_scene_mesh_skin_ms": (st, [vp, i32, vp]),
+    "rt_mesh_morph": (st, [vp, i32, vp, i32, vp, vp]),
+    "rt_scene_set_mesh_morphs": (st, [vp, i32, i32, vp, i32]),
+    "rt_scene_clear_mesh_morphs": (st, [vp, i32]),
+    "rt_scene_mesh_morph_info": (st, [vp, i32, vp]),
+    "rt_scene_morph_mesh": (st, [vp, i32, vp, i32, vp, i32, u32]),
+    "rt_scene_morph_mesh_auto": (st, [vp, i32, vp, i32, vp, i32, u32, f64, vp]),
+    "rt_scene_morph_mesh_build": (st, [vp, i32, vp, i32, vp, i32, u32, vp]),
+    "rt_scene_morph_mesh_auto_build": (st, [vp, i32, vp, i32, vp, i32, u32, f64, vp, vp]),
+    "rt_scene_mesh_morph_ms": (st, [vp, i32, vp]),
     "rt_bvh_build": (st, [vp, i32, vp, i32, i32, vp, vp, vp]),
     "rt_photon_balance": (st, [vp, u32, vp]),
     "rt_photon_unreachable": (st, [vp, u32, vp, u32, vp]),

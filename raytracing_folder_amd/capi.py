@@ -55,6 +55,19 @@ def mesh_skin(v_rest, bone_index, weight, bones):
     return out
 
 
+def mesh_morph(v_base, deltas, weights):
+    """rt_mesh_morph, the host mirror of k_mesh_morph (no GPU): the morphed positions, float32 (nv, 3), of base positions v_base under
+    the targets deltas, float32 (n_targets, nv, 3), and one weight a target -- a zero weight skips its target"""
+    v = _c(v_base, np.float32).reshape(-1, 3)
+    w = _c(weights, np.float32).reshape(-1)
+    d = _c(deltas, np.float32).reshape(-1, len(v), 3)
+    if len(d) != len(w):
+        raise ValueError(f"mesh_morph: {len(d)} targets, {len(w)} weights")
+    out = np.zeros((len(v), 3), np.float32)
+    _check(lib().rt_mesh_morph(_p(v), len(v), _p(d), len(d), _p(w), _p(out)))
+    return out
+
+
 def default_params(**kw):
     p = Params()
     lib().rt_params_default(C.byref(p))
@@ -335,10 +348,41 @@ class Scene(_Handle):
         _check(lib().rt_scene_mesh_skin_info(self._h, int(index), C.byref(info)))
         return dict(bound=bool(info.bound), n_bones=info.n_bones, nv=info.nv, store_current=int(info.store_current))
 
-    def pose_mesh(self, index, bones, keep_previous=False, rebuild=False, max_ratio=None):
+    def set_mesh_morphs(self, index, deltas):
+        """binds a morph set to mesh `index` (rt_mi355x.h, "morph targets"): deltas float32 (n_targets, nv, 3), dense, with the
+        positions the mesh holds now as the base"""
+        d = _c(deltas, np.float32)
+        if d.ndim != 3 or d.shape[2] != 3:
+            raise ValueError(f"set_mesh_morphs: deltas has shape {d.shape} ((n_targets, nv, 3))")
+        _check(lib().rt_scene_set_mesh_morphs(self._h, int(index), d.shape[0], _p(d), d.shape[1]))
+
+    def clear_mesh_morphs(self, index):
+        """unbinds the morph set of mesh `index`; the mesh keeps the positions it has"""
+        _check(lib().rt_scene_clear_mesh_morphs(self._h, int(index)))
+
+    def mesh_morphs(self, index):
+        """dict(bound, n_targets, nv, store_current): the morph set of mesh `index`, and whether the store's positions are the last
+        pose's (0 while the host mirrors still owe them: they run when the positions are next read)"""
+        info = MeshMorphInfo(struct_size=C.sizeof(MeshMorphInfo))
+        _check(lib().rt_scene_mesh_morph_info(self._h, int(index), C.byref(info)))
+        return dict(bound=bool(info.bound), n_targets=info.n_targets, nv=info.nv, store_current=int(info.store_current))
+
+    def mesh_morph_ms(self, device=0):
+        """milliseconds of the last k_mesh_morph launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
+        ms = C.c_float()
+        _check(lib().rt_scene_mesh_morph_ms(self._h, device, C.byref(ms)))
+        return ms.value
+
+    def pose_mesh(self, index, bones=None, keep_previous=False, rebuild=False, max_ratio=None, morph_weights=None):
         """poses the skinned mesh `index`: bones is float32 (n_bones, 3, 4), row-major, in the mesh's object space.  Everything else
         is update_mesh_vertices(v=the posed positions, vn=None, ...) -- the same arguments, the same return values -- but the
-        positions are computed by k_mesh_skin on the devices that hold the scene, from 48 bytes a bone."""
+        positions are computed by k_mesh_skin on the devices that hold the scene, from 48 bytes a bone.
+        morph_weights (float32 (n_targets,), one a target of the set set_mesh_morphs bound): the morph targets are applied first, and
+        bones, which may then be None, to the morphed positions -- k_mesh_morph, from 8 bytes a non-zero weight."""
+        if morph_weights is not None:
+            return self._morph_mesh(index, morph_weights, bones, keep_previous, rebuild, max_ratio)
+        if bones is None:
+            raise ValueError("pose_mesh: bones is required without morph_weights")
         device_build = isinstance(rebuild, str)
         if device_build and rebuild != "device":
             raise ValueError(f"pose_mesh: rebuild is {rebuild!r} (False, True or 'device')")
@@ -363,6 +407,34 @@ class Scene(_Handle):
             _check(lib().rt_scene_pose_mesh_auto(*pose, keep, max_ratio, C.byref(q)))
             return q.as_dict()
         _check(lib().rt_scene_pose_mesh(*pose, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
+
+    def _morph_mesh(self, index, weights, bones, keep_previous, rebuild, max_ratio):
+        """pose_mesh with morph_weights: the rt_scene_morph_mesh* forms"""
+        device_build = isinstance(rebuild, str)
+        if device_build and rebuild != "device":
+            raise ValueError(f"pose_mesh: rebuild is {rebuild!r} (False, True or 'device')")
+        if max_ratio is not None and rebuild and not device_build:
+            raise ValueError("pose_mesh: rebuild=True and max_ratio exclude each other")
+        w = _c(weights, np.float32).reshape(-1)
+        bones = None if bones is None else _c(bones, np.float32).reshape(-1, 3, 4)
+        pose = (self._h, int(index), _p(w), len(w), _p(bones), 0 if bones is None else len(bones))
+        keep = MESH_UPDATE_KEEP_PREVIOUS if keep_previous else 0
+        if device_build:
+            b = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
+            if max_ratio is None:
+                _check(lib().rt_scene_morph_mesh_build(*pose, keep, C.byref(b)))
+                return b.as_dict()
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_morph_mesh_auto_build(*pose, keep, max_ratio, C.byref(q), C.byref(b)))
+            out = q.as_dict()
+            if b.flags:
+                out["build"] = b.as_dict()
+            return out
+        if max_ratio is not None:
+            q = MeshQuality(struct_size=C.sizeof(MeshQuality))
+            _check(lib().rt_scene_morph_mesh_auto(*pose, keep, max_ratio, C.byref(q)))
+            return q.as_dict()
+        _check(lib().rt_scene_morph_mesh(*pose, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
 
     def mesh_skin_ms(self, device=0):
         """milliseconds of the last k_mesh_skin launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""

@@ -331,6 +331,14 @@ struct MeshData {
     std::vector<float> skin_weight, skin_rest, pose, pose_prev;
     bool v_stale = false, v_prev_stale = false;
     uint32_t skin_serial = 0;            // counts the skins bound to this mesh: a device's copy of another one is uploaded again
+    // rt_scene_set_mesh_morphs (rt_mi355x.h, "morph targets"): the set -- morph_targets (0: none bound), the base, the deltas
+    // (morph_targets x nv x 3) -- and the last morph pose's weights.  v_morphed: the pose v is owed from (v_stale) is a morph pose --
+    // morph_weights over the base, and then, v_morph_skinned, the skin with `pose` over that; else it is a bone pose over skin_rest.
+    // The same three for v_prev (v_prev_stale): morph_weights_prev, pose_prev.
+    int32_t morph_targets = 0;
+    std::vector<float> morph_base, morph_deltas, morph_weights, morph_weights_prev;
+    bool v_morphed = false, v_morph_skinned = false, v_prev_morphed = false, v_prev_morph_skinned = false;
+    uint32_t morph_serial = 0;           // counts the sets bound to this mesh, as skin_serial the skins
 };
 struct SceneData {
     std::vector<rt_node> nodes;

@@ -22,6 +22,8 @@
 #include "rt_host.h"
 #include "rt_mesh_normals.h"
 #include "rt_mesh_skin.h"
+#include "rt_mesh_morph.h"
+static_assert(RT_MORPH_MAX_TARGETS == RT_MESH_MORPH_MAX_TARGETS, "rt_mesh_morph.h and rt_mi355x.h disagree on the target cap");
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;       // the one message of rt_last_error(), whichever file failed
@@ -135,6 +137,7 @@ extern "C" rt_status rt_scene_set_nodes(rt_scene *s, const rt_node *nodes, int32
 }
 
 static void drop_mesh_skin(rt::MeshData &m);
+static void drop_mesh_morphs(rt::MeshData &m);
 extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const uint32_t *f, int32_t nf,
                                        const float *vn, int32_t nvn, const uint32_t *fn, const rt_bvh_node *nodes,
                                        int32_t nnodes, const uint32_t *elements)
@@ -160,6 +163,7 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     m.v_prev.clear();                   // the faces may have changed: no pairing of old and new vertices is vouched for
     m.normals_mode = RT_MESH_NORMALS_STORED; m.vn_stale = false;      // ... and the caller has just brought the normals it wants
     drop_mesh_skin(m);                  // ... and the vertex count may have: a skin is bound again by the caller
+    drop_mesh_morphs(m);                // ... and so is a morph set
     s->geometry_changed();
     return RT_OK;
 }
@@ -173,12 +177,29 @@ static void drop_mesh_skin(rt::MeshData &m)
     m.v_stale = m.v_prev_stale = false;
     m.skin_serial++;
 }
+// ... and the morph set with the weights a morph pose left (the same caller)
+static void drop_mesh_morphs(rt::MeshData &m)
+{
+    m.morph_targets = 0;
+    for (std::vector<float> *a : {&m.morph_base, &m.morph_deltas, &m.morph_weights, &m.morph_weights_prev}) std::vector<float>().swap(*a);
+    m.v_morphed = m.v_morph_skinned = m.v_prev_morphed = m.v_prev_morph_skinned = false;
+    m.morph_serial++;
+}
+// positions a pose owes, by the mirrors: a bone pose skins the skin's rest pose; a morph pose morphs the base and then, if bones
+// came with it, skins the result in place
+static void resolve_pose(const rt::MeshData &m, bool morphed, bool morph_skinned, const std::vector<float> &weights, const std::vector<float> &bones, float *out)
+{
+    if (!morphed) { mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), bones.data(), out); return; }
+    const uint64_t nv = m.morph_base.size() / 3;
+    mesh_morph_host(m.morph_base.data(), nv, m.morph_deltas.data(), (uint32_t)m.morph_targets, weights.data(), out);
+    if (morph_skinned) mesh_skin_host(out, nv, m.skin_index.data(), m.skin_weight.data(), bones.data(), out);
+}
 void ensure_vertices(rt::MeshData &m)
 {
-    if (m.v_prev_stale) mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), m.pose_prev.data(), m.v_prev.data());
+    if (m.v_prev_stale) resolve_pose(m, m.v_prev_morphed, m.v_prev_morph_skinned, m.morph_weights_prev, m.pose_prev, m.v_prev.data());
     m.v_prev_stale = false;
     if (!m.v_stale) return;
-    mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), m.pose.data(), m.v.data());
+    resolve_pose(m, m.v_morphed, m.v_morph_skinned, m.morph_weights, m.pose, m.v.data());
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
     m.v_stale = false;
 }
@@ -336,6 +357,77 @@ extern "C" rt_status rt_scene_mesh_skin_info(const rt_scene *s, int32_t mesh, rt
     out->bound = m.skin_bones > 0;
     out->n_bones = m.skin_bones;
     out->nv = m.skin_bones > 0 ? (int32_t)(m.skin_rest.size() / 3) : 0;
+    out->store_current = !m.v_stale;
+    return RT_OK;
+}
+
+// ---- morph targets (rt_mi355x.h, "morph targets"; the kernel: rt_mesh_morph.hip, the pose entry points: rt_mesh_update.cpp) -----
+// RT_ERR_ARG unless every one of n floats is finite (`what` names them)
+rt_status check_finite(const char *who, const char *what, const float *a, int64_t n)
+{
+    if (!a) return fail(RT_ERR_ARG, "%s: %s is NULL", who, what);
+    for (int64_t i = 0; i < n; i++)
+        if (!std::isfinite(a[i])) return fail(RT_ERR_ARG, "%s: %s has an entry that is not finite (at %lld)", who, what, (long long)i);
+    return RT_OK;
+}
+// what the mirror and rt_scene_set_mesh_morphs require of a set
+static rt_status check_morphs(const char *who, int32_t n_targets, const float *deltas, int32_t nv)
+{
+    if (!deltas || nv <= 0) return fail(RT_ERR_ARG, "%s: deltas is required (nv=%d)", who, nv);
+    if (n_targets < 1 || n_targets > RT_MESH_MORPH_MAX_TARGETS) return fail(RT_ERR_ARG, "%s: n_targets is %d (1 .. %d)", who, n_targets, RT_MESH_MORPH_MAX_TARGETS);
+    return check_finite(who, "deltas", deltas, 3LL * nv * n_targets);
+}
+
+extern "C" rt_status rt_mesh_morph(const float *v_base, int32_t nv, const float *deltas, int32_t n_targets, const float *weights, float *v_out)
+{
+    if (!v_base || !v_out) return fail(RT_ERR_ARG, "rt_mesh_morph: v_base and v_out are required");
+    rt_status st = check_morphs("rt_mesh_morph", n_targets, deltas, nv);
+    if (st || (st = check_finite("rt_mesh_morph", "weights", weights, n_targets))) return st;
+    mesh_morph_host(v_base, (uint64_t)nv, deltas, (uint32_t)n_targets, weights, v_out);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_set_mesh_morphs(rt_scene *s, int32_t mesh, int32_t n_targets, const float *deltas, int32_t nv)
+{
+    rt_status st = check_idle(s, "rt_scene_set_mesh_morphs");
+    if (st || (st = check_morphs("rt_scene_set_mesh_morphs", n_targets, deltas, nv))) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = check_mesh_set(s, mesh, "rt_scene_set_mesh_morphs"))) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    if ((size_t)nv != m.v.size() / 3) return fail(RT_ERR_ARG, "rt_scene_set_mesh_morphs: nv is %d, the mesh has %zu vertices", nv, m.v.size() / 3);
+    ensure_vertices(m);                 // the base is the positions of now
+    drop_mesh_morphs(m);
+    release_mesh_morphs_on_devices(s, mesh);
+    m.morph_targets = n_targets;
+    m.morph_deltas.assign(deltas, deltas + 3 * (size_t)nv * (size_t)n_targets);
+    m.morph_base = m.v;
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_clear_mesh_morphs(rt_scene *s, int32_t mesh)
+{
+    rt_status st = check_idle(s, "rt_scene_clear_mesh_morphs");
+    if (st) return st;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if ((st = check_mesh_set(s, mesh, "rt_scene_clear_mesh_morphs"))) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    ensure_vertices(m);                 // the mesh keeps the positions it has
+    drop_mesh_morphs(m);
+    release_mesh_morphs_on_devices(s, mesh);
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_morph_info(const rt_scene *s, int32_t mesh, rt_mesh_morph_info *out)
+{
+    if (!s || !out) return fail(RT_ERR_ARG, "rt_scene_mesh_morph_info: NULL argument");
+    if (out->struct_size != sizeof(rt_mesh_morph_info))
+        return fail(RT_ERR_ARG, "rt_scene_mesh_morph_info: rt_mesh_morph_info.struct_size is %u, this library's is %zu", out->struct_size, sizeof(rt_mesh_morph_info));
+    std::lock_guard<std::mutex> lk(const_cast<rt_scene *>(s)->mu);
+    if (rt_status st = check_mesh_set(s, mesh, "rt_scene_mesh_morph_info")) return st;
+    const rt::MeshData &m = s->data.meshes[mesh];
+    out->bound = m.morph_targets > 0;
+    out->n_targets = m.morph_targets;
+    out->nv = m.morph_targets > 0 ? (int32_t)(m.morph_base.size() / 3) : 0;
     out->store_current = !m.v_stale;
     return RT_OK;
 }

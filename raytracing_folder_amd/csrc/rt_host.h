@@ -27,6 +27,7 @@
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
 #include "rt_launch.h"
+#include "rt_mesh_morph.h"
 #include "rt_photon_map.h"
 
 #define RT_HIDDEN __attribute__((visibility("hidden")))
@@ -116,7 +117,12 @@ struct DevMeshBufs {
     uint32_t skin_serial = 0;
     float root_rec_host[32];
     void release_skin() { for (DevBuf *b : {&skin_rest, &skin_index, &skin_weight}) b->release(); }
-    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt, &nadj_off, &nadj_corner}) b->release(); release_skin(); }
+    // morph targets (rt_mesh_morph.hip): the set -- base, deltas -- on the device from the mesh's first morph pose there
+    // (morph_serial: MeshData::morph_serial)
+    DevBuf morph_base, morph_deltas;
+    uint32_t morph_serial = 0;
+    void release_morphs() { morph_base.release(); morph_deltas.release(); }
+    void release() { for (DevBuf *b : {&nodes, &tris, &nrm, &tex, &slot_idx, &level_nodes, &v, &vn, &v_prev, &cost_partials, &f, &fn, &ft, &vt, &nadj_off, &nadj_corner}) b->release(); release_skin(); release_morphs(); }
 };
 // the scratch of a device tree build (MeshBuildScratch of rt_launch.h), the device's own: grown to the largest mesh built there
 struct MeshBuildBufs {
@@ -199,6 +205,9 @@ struct DeviceState {
     Event nrm_ev[2]; bool nrm_timed = false;        // around the last k_mesh_normals here (rt_scene_mesh_normals_ms)
     Event skin_ev[2]; bool skin_timed = false;      // around the last k_mesh_skin here (rt_scene_mesh_skin_ms)
     DevBuf skin_bones;                  // the pose k_mesh_skin stages from: 48 bytes a bone, uploaded at every pose
+    Event morph_ev[2]; bool morph_timed = false;    // around the last k_mesh_morph here (rt_scene_mesh_morph_ms)
+    DevBuf morph_active;                // the active list k_mesh_morph reads: 8 bytes a non-zero weight, uploaded at every morph pose
+    MeshMorphActive morph_active_host[RT_MORPH_MAX_TARGETS];      // ... where the host compacts it (the source of an asynchronous copy)
     Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
     MeshBuildBufs build;                // device tree builds here
     // one of the two maps: its buffers with what the kernels see of it
@@ -217,6 +226,9 @@ struct DeviceState {
         for (Event &e : skin_ev) e = Event();
         skin_timed = false;
         skin_bones.release();
+        for (Event &e : morph_ev) e = Event();
+        morph_timed = false;
+        morph_active.release();
         upd_levels = -1;
         for (Workspace &w : ws) w.release();
         for (int k = 0; k < 6; k++) t_out[k].release();
@@ -271,6 +283,10 @@ RT_HIDDEN void ensure_vertices(rt::MeshData &m);
 RT_HIDDEN rt_status check_pose(const char *who, const float *bones, int32_t n_bones);
 // rt_mesh_update.cpp: what the devices hold of one mesh's skin, released (caller holds s->mu; the scene is idle)
 RT_HIDDEN void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh);
+// rt_api.cpp: RT_ERR_ARG unless `a` is there and every one of its n floats is finite (`what` names the array in the message)
+RT_HIDDEN rt_status check_finite(const char *who, const char *what, const float *a, int64_t n);
+// rt_mesh_update.cpp: ... and of its morph set
+RT_HIDDEN void release_mesh_morphs_on_devices(rt_scene *s, int32_t mesh);
 // rt_api.cpp: RT_ERR_ARG "<who>: mesh <mesh> was never set" unless rt_scene_set_mesh has given the scene that mesh (caller holds s->mu)
 RT_HIDDEN rt_status check_mesh_set(const rt_scene *s, int32_t mesh, const char *who);
 // rt_lower.cpp: the scene's objects as upload_scene lowers them, with the material of every node; an in-place mesh update sends the

@@ -272,6 +272,19 @@ struct MeshSkinRequest {
     uint32_t nv; float *out;
 };
 
+// One mesh with morph targets posed on a device (rt_mesh_morph.hip; the definition: rt_mi355x.h, "morph targets").  base (nv x 3
+// floats) and deltas (n_targets x nv x 3 floats) are the set as the store checked it.  active: n_active (0 .. 256) pairs of
+// (uint32 target, float weight), 8 bytes each, ascending by target, every target below the set's n_targets, every weight non-zero.
+// n_bones == 0: morph only, and bone_index, weight and bones are not read; else they are MeshSkinRequest's, and the skin is
+// applied to the morphed position.  out (nv x 3 floats, not base) receives every position.
+struct MeshMorphRequest {
+    const float *base; const float *deltas;
+    const void *active; uint32_t n_active;
+    const uint16_t *bone_index; const float *weight;
+    const float *bones; uint32_t n_bones;
+    uint32_t nv; float *out;
+};
+
 // One measurement of a mesh's tree on a device (rt_refit.hip, k_bvh_cost; the definition: rt_mi355x.h, "mesh tree quality"): the
 // n_nodes (> 0, at most 2^28) records at `nodes`, one double per block of 256 terms to partials[0 .. ceil(4 n_nodes / 256)).
 // partials has room for one double more: under RT_COST_FOLD_DEVICE k_bvh_cost_fold leaves the sum of the others there.
@@ -401,6 +414,10 @@ hipError_t rtk_launch_mesh_normals(hipStream_t st, const MeshNormalsRequest &R);
 // ---- rt_mesh_skin.hip: a skinned mesh posed on the device ------------------------------------------------------------------
 // on `st`: k_mesh_skin over the mesh's vertices (ahead of k_mesh_normals and everything else that reads them)
 hipError_t rtk_launch_mesh_skin(hipStream_t st, const MeshSkinRequest &R);
+
+// ---- rt_mesh_morph.hip: a mesh with morph targets posed on the device -------------------------------------------------------
+// on `st`: k_mesh_morph over the mesh's vertices (in k_mesh_skin's place: one launch, whether or not bones came)
+hipError_t rtk_launch_mesh_morph(hipStream_t st, const MeshMorphRequest &R);
 
 // ---- rt_bvh_build.hip: a mesh's tree built on the device ------------------------------------------------------------------
 // bytes of the sort's temporary storage for n_faces keys

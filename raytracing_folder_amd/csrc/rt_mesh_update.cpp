@@ -1,7 +1,8 @@
-// rt_mesh_update.cpp -- everything that changes a lowered mesh in place: the six rt_scene_update_mesh_vertices* and the four
-// rt_scene_pose_mesh* entry points on one entry path, their share of the scene store, and what they do on the devices that hold the
-// scene -- the refit (rt_refit.hip), the refitted tree's quality (k_bvh_cost), the device tree build (rt_bvh_build.hip), smooth
-// normals (rt_mesh_normals.hip), a skinned mesh's pose (rt_mesh_skin.hip) -- behind
+// rt_mesh_update.cpp -- everything that changes a lowered mesh in place: the six rt_scene_update_mesh_vertices*, the four
+// rt_scene_pose_mesh* and the four rt_scene_morph_mesh* entry points on one entry path, their share of the scene store, and what
+// they do on the devices that hold the scene -- the refit (rt_refit.hip), the refitted tree's quality (k_bvh_cost), the device tree
+// build (rt_bvh_build.hip), smooth normals (rt_mesh_normals.hip), a skinned mesh's pose (rt_mesh_skin.hip), morph targets
+// (rt_mesh_morph.hip) -- behind
 // one per-device upload and one loop over the devices; the host mirrors of the cost and of the build; the calls that read a mesh
 // back from a device.  rt_lower.cpp put the mesh there (upload_scene); rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
@@ -52,6 +53,31 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
 // ... and a pose in the store (rt_mi355x.h, "mesh skinning"): the matrices and a mark, no per-vertex work -- v is owed from then on
 // (ensure_vertices), and so is root_box unless a device reports it.  keep_previous: the previous positions are the ones the mesh
 // had -- v itself where the store has it, the pose it is owed from where it does not.
+// (the three cases of keep_previous, for a bone pose and a morph pose alike: none kept; the pose v is owed from handed on -- bones,
+// morph weights and which of the two kinds it was; v itself where the store has it)
+static void pose_keeps_previous(rt::MeshData &m, bool keep_previous)
+{
+    if (!keep_previous) { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
+    else if (m.v_stale) {
+        m.pose_prev = m.pose;
+        m.morph_weights_prev = m.morph_weights;
+        m.v_prev_morphed = m.v_morphed; m.v_prev_morph_skinned = m.v_morph_skinned;
+        if (m.v_prev.size() != m.v.size()) m.v_prev.resize(m.v.size());
+        m.v_prev_stale = true;
+    } else {
+        m.v_prev.swap(m.v);
+        m.v_prev_stale = false;
+        if (m.v.size() != m.v_prev.size()) m.v.resize(m.v_prev.size());
+    }
+}
+// (what every pose leaves behind the pose itself)
+static void pose_marks_store(rt_scene *s, rt::MeshData &m)
+{
+    m.v_stale = true;
+    if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
+    m.tree_stale = true;
+    s->drop_generated_photons();
+}
 static rt_status store_mesh_pose(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, bool keep_previous, const char *who)
 {
     rt_status st = check_mesh_set(s, mesh, who);
@@ -60,21 +86,31 @@ static rt_status store_mesh_pose(rt_scene *s, int32_t mesh, const float *bones, 
     if (m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
     if (n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, n_bones, m.skin_bones);
     if ((st = check_pose(who, bones, n_bones))) return st;
-    if (!keep_previous) { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
-    else if (m.v_stale) {
-        m.pose_prev = m.pose;
-        if (m.v_prev.size() != m.v.size()) m.v_prev.resize(m.v.size());
-        m.v_prev_stale = true;
-    } else {
-        m.v_prev.swap(m.v);
-        m.v_prev_stale = false;
-        if (m.v.size() != m.v_prev.size()) m.v.resize(m.v_prev.size());
-    }
+    pose_keeps_previous(m, keep_previous);
     m.pose.assign(bones, bones + 12 * (size_t)n_bones);
-    m.v_stale = true;
-    if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
-    m.tree_stale = true;
-    s->drop_generated_photons();
+    m.v_morphed = m.v_morph_skinned = false;
+    pose_marks_store(s, m);
+    return RT_OK;
+}
+
+// ... and a morph pose (rt_mi355x.h, "morph targets"): the weights, the bones if any came, and the same mark
+static rt_status store_mesh_morph_pose(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                       bool keep_previous, const char *who)
+{
+    rt_status st = check_mesh_set(s, mesh, who);
+    if (st) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    if (m.morph_targets == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no morph set (rt_scene_set_mesh_morphs binds one)", who, mesh);
+    if (bones && m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: bones given and mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
+    if (n_targets != m.morph_targets) return fail(RT_ERR_ARG, "%s: n_targets is %d, the morph set has %d", who, n_targets, m.morph_targets);
+    if (!bones && n_bones != 0) return fail(RT_ERR_ARG, "%s: bones is NULL and n_bones is %d", who, n_bones);
+    if (bones && n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, n_bones, m.skin_bones);
+    if ((st = check_finite(who, "weights", weights, n_targets)) || (bones && (st = check_pose(who, bones, n_bones)))) return st;
+    pose_keeps_previous(m, keep_previous);
+    m.morph_weights.assign(weights, weights + n_targets);
+    if (bones) m.pose.assign(bones, bones + 12 * (size_t)n_bones);
+    m.v_morphed = true; m.v_morph_skinned = bones != nullptr;
+    pose_marks_store(s, m);
     return RT_OK;
 }
 
@@ -144,9 +180,54 @@ void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh)
     if (!s->devs.empty()) (void)hipSetDevice(cur);
 }
 
+// Morph targets (rt_mi355x.h, "morph targets"), one device's share in the same two steps.  prepare: the set -- base, deltas -- on
+// the device from the mesh's first morph pose there, room for the active list, and, if bones came, the skin and room for them
+// (prepare_mesh_skin).  enqueue: the active list (compacted here: 8 bytes a non-zero weight), the bones if any, and ONE launch of
+// k_mesh_morph in the vertex upload's place, between the events rt_scene_mesh_morph_ms reads.
+static rt_status prepare_mesh_morph(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    rt_status rs;
+    for (Event &e : D->morph_ev) if (!e.e) HIP_TRY(e.create());
+    if ((rs = D->morph_active.ensure(sizeof(D->morph_active_host)))) return rs;
+    if (m.v_morph_skinned && (rs = prepare_mesh_skin(D, m, mb))) return rs;
+    if (mb.morph_base.p && mb.morph_serial == m.morph_serial) return RT_OK;
+    if ((rs = mb.morph_base.upload(m.morph_base.data(), m.morph_base.size() * 4)) || (rs = mb.morph_deltas.upload(m.morph_deltas.data(), m.morph_deltas.size() * 4))) return rs;
+    mb.morph_serial = m.morph_serial;
+    return RT_OK;
+}
+static rt_status enqueue_mesh_morph(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+{
+    MeshMorphRequest K = {};
+    K.base = (const float *)mb.morph_base.p; K.deltas = (const float *)mb.morph_deltas.p;
+    K.active = D->morph_active.p; K.n_active = mesh_morph_compact(m.morph_weights.data(), (uint32_t)m.morph_targets, D->morph_active_host);
+    K.nv = (uint32_t)(m.morph_base.size() / 3); K.out = (float *)mb.v.p;
+    if (K.n_active) HIP_TRY(hipMemcpyAsync(D->morph_active.p, D->morph_active_host, K.n_active * sizeof(MeshMorphActive), hipMemcpyHostToDevice, D->stream));
+    if (m.v_morph_skinned) {
+        K.bone_index = (const uint16_t *)mb.skin_index.p; K.weight = (const float *)mb.skin_weight.p;
+        K.bones = (const float *)D->skin_bones.p; K.n_bones = (uint32_t)m.skin_bones;
+        HIP_TRY(hipMemcpyAsync(D->skin_bones.p, m.pose.data(), m.pose.size() * 4, hipMemcpyHostToDevice, D->stream));
+    }
+    HIP_TRY(hipEventRecord(D->morph_ev[0], D->stream));
+    HIP_TRY(rtk_launch_mesh_morph(D->stream, K));
+    HIP_TRY(hipEventRecord(D->morph_ev[1], D->stream));
+    D->morph_timed = true;
+    return RT_OK;
+}
+void release_mesh_morphs_on_devices(rt_scene *s, int32_t mesh)
+{
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    for (DeviceState *D : s->devs)
+        if ((size_t)mesh < D->mesh_bufs.size() && D->mesh_bufs[mesh].morph_base.p && hipSetDevice(D->device) == hipSuccess) D->mesh_bufs[mesh].release_morphs();
+    if (!s->devs.empty()) (void)hipSetDevice(cur);
+}
+
 // Where an update's new vertices come from on a device: the store (uploaded), the skin (k_mesh_skin writes them from the pose the
-// store holds), or nowhere -- they are on the device already, behind the refit of the same call.
-enum VertexSource { VERTICES_FROM_STORE, VERTICES_FROM_SKIN, VERTICES_ON_DEVICE };
+// store holds), the morph set (k_mesh_morph, from the weights and, if any came, the bones), or nowhere -- they are on the device
+// already, behind the refit of the same call.
+enum VertexSource { VERTICES_FROM_STORE, VERTICES_FROM_SKIN, VERTICES_FROM_MORPH, VERTICES_ON_DEVICE };
+// ... computed on the device: the host has no positions, so a flagged pose swaps pointers and the root box is read back
+static bool vertices_computed(VertexSource src) { return src == VERTICES_FROM_SKIN || src == VERTICES_FROM_MORPH; }
 
 // the box of a tree's root record: per axis the smallest lo and the largest hi over its used children (lo[axis][child],
 // hi[axis][child]; an unused child has a NaN lo on x) -- the exact min / max of the vertices under the faces, MeshRootBox's box
@@ -179,7 +260,8 @@ static bool mesh_textured(const DevMeshBufs &mb, const rt::MeshData &m) { return
 // buffers, the upload between ev[0] and ev[1] (ev: the caller's n_ev events, all made here), smooth normals behind it.
 // with_faces: the device build's arrays -- f, fn and, for a textured mesh, ft and vt -- on the device from the mesh's first build
 // there.  reserve (may be empty): what else the caller's tail allocates, ahead of ev[0] so that nothing is allocated between
-// the events.  src: VERTICES_FROM_SKIN puts the pose's 48 bytes a bone and k_mesh_skin in the vertex upload's place, and a flagged
+// the events.  src: VERTICES_FROM_SKIN puts the pose's 48 bytes a bone and k_mesh_skin in the vertex upload's place
+// (VERTICES_FROM_MORPH: the active list, the bones if any, and k_mesh_morph), and a flagged
 // pose makes the buffer the positions were in the previous positions' -- two pointers swapped, nothing uploaded; VERTICES_ON_DEVICE
 // leaves positions and previous positions as the refit of the same call left them.
 static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, size_t n_objects, const char *who,
@@ -200,17 +282,17 @@ static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh
     const bool textured = mesh_textured(mb, m);
     // SMOOTH mode and no normals brought: the device computes them from the vertices it is about to be sent
     const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;
-    const bool skin = src == VERTICES_FROM_SKIN;
+    const bool posed = vertices_computed(src), morph = src == VERTICES_FROM_MORPH;
     // a flagged pose on a device that has the positions: they become the previous ones where they are
-    const bool swap_prev = skin && !m.v_prev.empty() && mb.v.p != nullptr;
+    const bool swap_prev = posed && !m.v_prev.empty() && mb.v.p != nullptr;
     const bool upload_prev = src != VERTICES_ON_DEVICE && !m.v_prev.empty() && !swap_prev;
     if (swap_prev) std::swap(mb.v, mb.v_prev);
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
-    if (skin && (rs = prepare_mesh_skin(D, m, mb))) return rs;
+    if (posed && (rs = morph ? prepare_mesh_morph(D, m, mb) : prepare_mesh_skin(D, m, mb))) return rs;
     if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
     // the store's normals are about to be read: never stale ones over what k_mesh_normals wrote here (the first time they are
     // the values the kernel's kept normals keep -- which stale ones are as well: a pose does not resolve the store for them)
-    if ((first || normals_changed) && !(skin && smooth)) ensure_normals(m);
+    if ((first || normals_changed) && !(posed && smooth)) ensure_normals(m);
     // the previous positions follow the store: uploaded from it ahead of the new vertices, in the update's stream, by a flagged
     // update; released by an unflagged one (nothing is allocated, copied or freed for a mesh that never used the flag)
     if (upload_prev) { if (m.v_prev_stale) ensure_vertices(m); if ((rs = mb.v_prev.ensure(m.v_prev.size() * 4))) return rs; }
@@ -222,7 +304,7 @@ static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh
     if (reserve && (rs = reserve())) return rs;
     HIP_TRY(hipEventRecord(ev[0], st));
     if (upload_prev) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
-    if (skin) { if ((rs = enqueue_mesh_skin(D, m, mb))) return rs; }
+    if (posed) { if ((rs = morph ? enqueue_mesh_morph(D, m, mb) : enqueue_mesh_skin(D, m, mb))) return rs; }
     else if (src == VERTICES_FROM_STORE) HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
     if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
     if (faces) {
@@ -523,7 +605,7 @@ static rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_c
         rt_mesh_quality mine = {};
         const bool measure = quality && first;
         const rt_status r = refit_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, measure ? &mine : nullptr, src,
-                                                 src == VERTICES_FROM_SKIN && first ? &s->data : nullptr);
+                                                 vertices_computed(src) && first ? &s->data : nullptr);
         if (!r && measure) { mine.struct_size = quality->struct_size; *quality = mine; }
         return r;
     });
@@ -541,7 +623,7 @@ static rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_c
     const rt_status ret = on_devices_holding_scene(s, [&](DeviceState *D, std::vector<DevObject> &objs, bool first, bool *stop) {
         rt_mesh_build_info mine = none;
         const rt_status r = build_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, cap, &mine, stop, src,
-                                                 src == VERTICES_FROM_SKIN && first ? &s->data : nullptr);
+                                                 vertices_computed(src) && first ? &s->data : nullptr);
         if (!r && first) { *info = mine; info->flags = *stop ? RT_MESH_BUILD_FELL_BACK : RT_MESH_BUILD_ON_DEVICE; }
         return r;
     }, &fell_back);
@@ -557,18 +639,19 @@ enum UpdateAfter { UPDATE_REFIT, UPDATE_REFIT_MEASURE, UPDATE_BUILD, UPDATE_REFI
 // of it (the entry points it is one of word a refused flag their own way), and `after`.  The out-structs need no column: an
 // entry point passes NULL for the one it does not have.
 struct UpdateEntry { const char *who; uint32_t known; bool takes_ratio; UpdateAfter after; };
-// the other way the new vertices arrive: a pose of the mesh's skin (rt_scene_pose_mesh*) in place of v, nv, vn, nvn
-struct MeshPose { const float *bones; int32_t n_bones; };
+// the other way the new vertices arrive: a pose of the mesh's skin (rt_scene_pose_mesh*) in place of v, nv, vn, nvn -- or, morph
+// set, a morph pose (rt_scene_morph_mesh*): weights, and bones that may be NULL
+struct MeshPose { const float *bones; int32_t n_bones; bool morph; const float *weights; int32_t n_targets; };
 
 // A pose is skinned on the devices unless the mesh's tree there is a single leaf -- no root record to read the box from; the mesh is
 // tiny -- in which case the store resolves it now and the update goes the way of one that brought the vertices (caller holds s->mu)
-static VertexSource pose_source(rt_scene *s, int32_t mesh)
+static VertexSource pose_source(rt_scene *s, int32_t mesh, bool morph)
 {
     rt::MeshData &m = s->data.meshes[mesh];
     bool leaf = false;
     for (DeviceState *D : s->devs)
         if (D->scene_valid) leaf = leaf || m.f.size() / 3 <= RT_LBVH_LEAF_TRIS || ((size_t)mesh < D->mesh_bufs.size() && (D->mesh_bufs[mesh].root_ref & RT_COST_LEAF));
-    if (!leaf) return VERTICES_FROM_SKIN;
+    if (!leaf) return morph ? VERTICES_FROM_MORPH : VERTICES_FROM_SKIN;
     ensure_vertices(m);
     return VERTICES_FROM_STORE;
 }
@@ -588,9 +671,11 @@ static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t
     if (!pose && !v) return fail(RT_ERR_ARG, "%s: v is NULL", e.who);
     std::lock_guard<std::mutex> lk(s->mu);
     const bool keep_previous = (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0;
-    if ((st = pose ? store_mesh_pose(s, mesh, pose->bones, pose->n_bones, keep_previous, e.who) : store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep_previous, e.who))) return st;
+    if ((st = !pose ? store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep_previous, e.who)
+              : pose->morph ? store_mesh_morph_pose(s, mesh, pose->weights, pose->n_targets, pose->bones, pose->n_bones, keep_previous, e.who)
+              : store_mesh_pose(s, mesh, pose->bones, pose->n_bones, keep_previous, e.who))) return st;
     if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }      // (the next lowering uploads the previous positions from the store)
-    const VertexSource src = pose ? pose_source(s, mesh) : VERTICES_FROM_STORE;
+    const VertexSource src = pose ? pose_source(s, mesh, pose->morph) : VERTICES_FROM_STORE;
     const bool normals_changed = vn != nullptr, measure = e.after == UPDATE_REFIT_MEASURE || e.after == UPDATE_REFIT_MEASURE_BUILD;
     rt_mesh_quality q = {sizeof(rt_mesh_quality)};
     rt_mesh_build_info b = {sizeof(rt_mesh_build_info)};
@@ -603,7 +688,7 @@ static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t
     }
     // (behind a refit the vertices are on the devices already; the build sends them again with everything else it does, normals
     // only if this call brought some; a pose is not skinned twice: its vertices stay where the refit's k_mesh_skin wrote them)
-    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b, src == VERTICES_FROM_SKIN && e.after != UPDATE_BUILD ? VERTICES_ON_DEVICE : src);
+    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b, vertices_computed(src) && e.after != UPDATE_BUILD ? VERTICES_ON_DEVICE : src);
     if (q_out) *q_out = q;
     if (b_out) *b_out = b;
     return st;
@@ -650,27 +735,57 @@ extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32
 extern "C" rt_status rt_scene_pose_mesh(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags)
 {
     static const UpdateEntry e = {"rt_scene_pose_mesh", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
-    const MeshPose pose = {bones, n_bones};
+    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
     return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, nullptr, &pose);
 }
 extern "C" rt_status rt_scene_pose_mesh_auto(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
                                              rt_mesh_quality *out)
 {
     static const UpdateEntry e = {"rt_scene_pose_mesh_auto", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
-    const MeshPose pose = {bones, n_bones};
+    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
     return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, out, nullptr, &pose);
 }
 extern "C" rt_status rt_scene_pose_mesh_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, rt_mesh_build_info *out)
 {
     static const UpdateEntry e = {"rt_scene_pose_mesh_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
-    const MeshPose pose = {bones, n_bones};
+    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
     return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, out, &pose);
 }
 extern "C" rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
                                                    rt_mesh_quality *q_out, rt_mesh_build_info *out)
 {
     static const UpdateEntry e = {"rt_scene_pose_mesh_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
-    const MeshPose pose = {bones, n_bones};
+    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, q_out, out, &pose);
+}
+
+// ... and by a morph pose (rt_mi355x.h, "morph targets"): weights, and bones that may be NULL with n_bones 0
+extern "C" rt_status rt_scene_morph_mesh(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                         uint32_t flags)
+{
+    static const UpdateEntry e = {"rt_scene_morph_mesh", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
+    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, nullptr, &pose);
+}
+extern "C" rt_status rt_scene_morph_mesh_auto(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                              uint32_t flags, double max_ratio, rt_mesh_quality *out)
+{
+    static const UpdateEntry e = {"rt_scene_morph_mesh_auto", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
+    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, out, nullptr, &pose);
+}
+extern "C" rt_status rt_scene_morph_mesh_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
+                                               uint32_t flags, rt_mesh_build_info *out)
+{
+    static const UpdateEntry e = {"rt_scene_morph_mesh_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
+    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
+    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, out, &pose);
+}
+extern "C" rt_status rt_scene_morph_mesh_auto_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones,
+                                                    int32_t n_bones, uint32_t flags, double max_ratio, rt_mesh_quality *q_out, rt_mesh_build_info *out)
+{
+    static const UpdateEntry e = {"rt_scene_morph_mesh_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
+    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
     return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, q_out, out, &pose);
 }
 
@@ -704,6 +819,15 @@ extern "C" rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms)
     DeviceState *D = find_device_state(s, device);
     if (!D || !D->skin_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_skin_ms: device %d has not posed a mesh", device);
     HIP_TRY(hipEventElapsedTime(ms, D->skin_ev[0], D->skin_ev[1]));
+    return RT_OK;
+}
+
+extern "C" rt_status rt_scene_mesh_morph_ms(rt_scene *s, int device, float *ms)
+{
+    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_morph_ms: NULL argument");
+    DeviceState *D = find_device_state(s, device);
+    if (!D || !D->morph_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_morph_ms: device %d has not morphed a mesh", device);
+    HIP_TRY(hipEventElapsedTime(ms, D->morph_ev[0], D->morph_ev[1]));
     return RT_OK;
 }
 

@@ -130,6 +130,26 @@ def chain_pose(n_bones, angle, origin, axis):
     return out.astype(np.float32)
 
 
+def morph_targets(v, n_targets, amplitude=0.15, seed=0):
+    """a morph set for vertices v (Scene.set_mesh_morphs): target t moves the vertices within a seeded radius (0.15 .. 0.45 of the
+    mesh's extent, its largest side) of a seeded centre vertex along a seeded unit direction, by amplitude x extent at the centre
+    with the smooth falloff (1 - (d / radius)^2)^2 that is exactly 0 from the radius on -- dense and mostly zero, as real blend
+    shapes are.  Returns deltas float32 (n_targets, nv, 3)."""
+    v = np.asarray(v, np.float32).reshape(-1, 3).astype(np.float64)
+    rng = np.random.default_rng(seed)
+    extent = float((v.max(0) - v.min(0)).max()) or 1.0
+    out = np.zeros((int(n_targets), len(v), 3), np.float32)
+    for t in range(int(n_targets)):
+        centre = v[rng.integers(0, len(v))]
+        radius = rng.uniform(0.15, 0.45) * extent
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        r2 = ((v - centre) ** 2).sum(1) / (radius * radius)
+        fall = np.where(r2 < 1.0, (1.0 - r2) ** 2, 0.0)
+        out[t] = (float(amplitude) * extent * fall[:, None] * d).astype(np.float32)
+    return out
+
+
 def sheet(n, extent):
     """an open sheet of n x n quads in the plane z = 0, |x|, |y| <= extent / 2: (n + 1)^2 shared vertices, 2 n^2 triangles wound
     so that the face normals point to +z.  float32 (nv, 3), uint32 (nf, 3); sheet(1) is one leaf of the device tree"""
