@@ -624,10 +624,10 @@ rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms);
 /* ---- mesh skinning (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
  *      unchanged) ---------------------------------------------------------------------------------------------------------------
  * A second source of new vertices for the in-place update: linear-blend skinning on the device.  A skin is bound to a mesh once;
- * after that a frame brings a pose -- a few dozen matrices instead of a vertex array -- and k_mesh_skin (csrc/rt_mesh_skin.hip)
+ * after that a frame brings a pose -- a few dozen matrices instead of a vertex array -- and k_mesh_pose (csrc/rt_mesh_pose.hip)
  * writes the posed positions where the refit, the device build, k_mesh_normals and k_motion_mesh read them.  The definition fixes
  * every operation and its order, so that the kernel and the host mirror (rt_mesh_skin) give the same bytes; the arithmetic is
- * written once, in csrc/rt_mesh_skin.h.
+ * written once, in csrc/rt_mesh_pose.h.
  *
  * A skin    belongs to one mesh of a scene: n_bones (1 .. RT_MESH_SKIN_MAX_BONES); per vertex four influences, bone_index as
  *           uint16[nv][4] and weight as float32[nv][4]; and the REST POSE, a copy of the positions the mesh holds when the skin
@@ -672,7 +672,7 @@ rt_status rt_scene_mesh_skin_info(const rt_scene *s, int32_t mesh, rt_mesh_skin_
 /* The pose: rt_scene_update_mesh_vertices_flags with the vertices of the definition above in place of v and with vn == NULL, on the
  * same entry path -- the same flags (RT_MESH_UPDATE_REBUILD, RT_MESH_UPDATE_KEEP_PREVIOUS; any other bit RT_ERR_ARG), the same
  * statuses, the same store discipline (tree stale, a generated photon map dropped).  On every device that holds the scene the
- * vertex upload is replaced by an upload of the bones (48 n_bones bytes) and one launch of k_mesh_skin ahead of k_mesh_normals;
+ * vertex upload is replaced by an upload of the bones (48 n_bones bytes) and one launch of k_mesh_pose ahead of k_mesh_normals;
  * rest pose, indices and weights go to a device once, at the mesh's first pose there.  With KEEP_PREVIOUS the device's previous
  * positions become the buffer its positions were in and the kernel writes the other one: two pointers are swapped, nothing is
  * uploaded or copied.  The mesh's root box and the objects' cull boxes come from the root record of the first device's refitted
@@ -689,17 +689,17 @@ rt_status rt_scene_pose_mesh_build(rt_scene *s, int32_t mesh, const float *bones
 /* ... as rt_scene_update_mesh_vertices_auto_build */
 rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
                                         rt_mesh_quality *q, rt_mesh_build_info *out);
-/* Milliseconds of the last k_mesh_skin launch on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
+/* Milliseconds of the last k_mesh_pose launch for a bone pose on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
  * has run none.  Like k_mesh_normals it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
 rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms);
 
 /* ---- morph targets (additive to ABI 4: detected by the presence of the symbols; RT_ABI_VERSION and the structs above are
  *      unchanged) ---------------------------------------------------------------------------------------------------------------
  * A third source of new vertices for the in-place update: blend shapes on the device, ahead of the skin.  A morph set is bound to a
- * mesh once; after that a frame brings one weight a target -- and, for a skinned mesh, its bones -- and k_mesh_morph
- * (csrc/rt_mesh_morph.hip) writes the positions where the refit, the device build, k_mesh_normals and k_motion_mesh read them.
+ * mesh once; after that a frame brings one weight a target -- and, for a skinned mesh, its bones -- and k_mesh_pose
+ * (csrc/rt_mesh_pose.hip) writes the positions where the refit, the device build, k_mesh_normals and k_motion_mesh read them.
  * The definition fixes every operation and its order, so that the kernel and the host mirror (rt_mesh_morph) give the same bytes;
- * the arithmetic is written once, in csrc/rt_mesh_morph.h.
+ * the arithmetic, and the order of morph and skin, is written once, in csrc/rt_mesh_pose.h.
  *
  * A morph set belongs to one mesh of a scene: n_targets (1 .. RT_MESH_MORPH_MAX_TARGETS); the deltas, float32[n_targets][nv][3],
  *           dense, in the mesh's object space, every one finite; and the BASE, a copy of the positions the mesh holds when the
@@ -744,7 +744,7 @@ rt_status rt_scene_mesh_morph_info(const rt_scene *s, int32_t mesh, rt_mesh_morp
  * statuses, the same store discipline.  bones == NULL with n_bones == 0 is morph only; bones given is morph, then skin, and a skin
  * must be bound (n_bones the skin's).  On every device that holds the scene the base and the deltas go up once, at the mesh's first
  * morph pose there; a pose uploads the ACTIVE LIST -- (target, weight) of the non-zero weights, ascending, at most 2 KB -- and with
- * bones their 48 bytes each, and launches k_mesh_morph once.  KEEP_PREVIOUS, the root box, the single-leaf mesh and a scene no
+ * bones their 48 bytes each, and launches k_mesh_pose once.  KEEP_PREVIOUS, the root box, the single-leaf mesh and a scene no
  * device holds are as for rt_scene_pose_mesh.  RT_ERR_STATE: no morph set, or bones and no skin; RT_ERR_ARG: n_targets is not the
  * set's, n_bones not the skin's (or not 0 without bones), a weight or a bone that is not finite; nothing changes then. */
 rt_status rt_scene_morph_mesh(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
@@ -758,8 +758,8 @@ rt_status rt_scene_morph_mesh_build(rt_scene *s, int32_t mesh, const float *weig
 /* ... as rt_scene_pose_mesh_auto_build */
 rt_status rt_scene_morph_mesh_auto_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones,
                                          int32_t n_bones, uint32_t flags, double max_ratio, rt_mesh_quality *q, rt_mesh_build_info *out);
-/* Milliseconds of the last k_mesh_morph launch on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
- * has run none.  Like k_mesh_skin it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
+/* Milliseconds of the last k_mesh_pose launch for a morph pose (with bones or without) on `device`, by HIP events on the library's stream.  RT_ERR_STATE when that device
+ * has run none.  Like a bone pose's it sits inside rt_mesh_update_ms.upload and rt_mesh_build_info.upload_ms. */
 rt_status rt_scene_mesh_morph_ms(rt_scene *s, int device, float *ms);
 
 /* ---- host helpers that mirror reference host code --------------------------------------- */

@@ -43,7 +43,7 @@ def mesh_smooth_normals(v, f, fn=None, vn=None):
 
 
 def mesh_skin(v_rest, bone_index, weight, bones):
-    """rt_mesh_skin, the host mirror of k_mesh_skin (no GPU): the posed positions, float32 (nv, 3), of rest positions v_rest under
+    """rt_mesh_skin, the host mirror of k_mesh_pose's skinning (no GPU): the posed positions, float32 (nv, 3), of rest positions v_rest under
     four influences a vertex -- bone_index uint16 (nv, 4), weight float32 (nv, 4) -- and the pose bones, float32 (n_bones, 3, 4)"""
     v = _c(v_rest, np.float32).reshape(-1, 3)
     idx, w = _c(bone_index, np.uint16).reshape(-1, 4), _c(weight, np.float32).reshape(-1, 4)
@@ -56,7 +56,7 @@ def mesh_skin(v_rest, bone_index, weight, bones):
 
 
 def mesh_morph(v_base, deltas, weights):
-    """rt_mesh_morph, the host mirror of k_mesh_morph (no GPU): the morphed positions, float32 (nv, 3), of base positions v_base under
+    """rt_mesh_morph, the host mirror of k_mesh_pose's morph targets (no GPU): the morphed positions, float32 (nv, 3), of base positions v_base under
     the targets deltas, float32 (n_targets, nv, 3), and one weight a target -- a zero weight skips its target"""
     v = _c(v_base, np.float32).reshape(-1, 3)
     w = _c(weights, np.float32).reshape(-1)
@@ -368,7 +368,7 @@ class Scene(_Handle):
         return dict(bound=bool(info.bound), n_targets=info.n_targets, nv=info.nv, store_current=int(info.store_current))
 
     def mesh_morph_ms(self, device=0):
-        """milliseconds of the last k_mesh_morph launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
+        """milliseconds of the last k_mesh_pose launch for a morph pose on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
         ms = C.c_float()
         _check(lib().rt_scene_mesh_morph_ms(self._h, device, C.byref(ms)))
         return ms.value
@@ -376,9 +376,9 @@ class Scene(_Handle):
     def pose_mesh(self, index, bones=None, keep_previous=False, rebuild=False, max_ratio=None, morph_weights=None):
         """poses the skinned mesh `index`: bones is float32 (n_bones, 3, 4), row-major, in the mesh's object space.  Everything else
         is update_mesh_vertices(v=the posed positions, vn=None, ...) -- the same arguments, the same return values -- but the
-        positions are computed by k_mesh_skin on the devices that hold the scene, from 48 bytes a bone.
+        positions are computed by k_mesh_pose on the devices that hold the scene, from 48 bytes a bone.
         morph_weights (float32 (n_targets,), one a target of the set set_mesh_morphs bound): the morph targets are applied first, and
-        bones, which may then be None, to the morphed positions -- k_mesh_morph, from 8 bytes a non-zero weight."""
+        bones, which may then be None, to the morphed positions -- the same kernel, from 8 bytes a non-zero weight."""
         if morph_weights is not None:
             return self._morph_mesh(index, morph_weights, bones, keep_previous, rebuild, max_ratio)
         if bones is None:
@@ -437,7 +437,7 @@ class Scene(_Handle):
         _check(lib().rt_scene_morph_mesh(*pose, (MESH_UPDATE_REBUILD if rebuild else 0) | keep))
 
     def mesh_skin_ms(self, device=0):
-        """milliseconds of the last k_mesh_skin launch on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
+        """milliseconds of the last k_mesh_pose launch for a bone pose on `device`, by HIP events (RtError RT_ERR_STATE when it ran none)"""
         ms = C.c_float()
         _check(lib().rt_scene_mesh_skin_ms(self._h, device, C.byref(ms)))
         return ms.value

@@ -306,6 +306,12 @@ struct Scene {
 int LoadScene(Scene &scene, const char *filename, std::string *err = nullptr);
 
 // ---- lowered form: exactly what the C ABI setters take -------------------------------------
+// A pose positions can be owed from: a bone pose (skinned alone: bones, 12 floats each, over the skin's rest pose), or a morph pose
+// (morphed: weights over the morph set's base, and then, skinned, bones over that)
+struct MeshPose {
+    bool morphed = false, skinned = false;
+    std::vector<float> weights, bones;
+};
 struct MeshData {
     std::vector<float> v, vn, vt;        // vt/ft empty: the mesh has no texture vertices
     std::vector<uint32_t> f, fn, ft;
@@ -323,22 +329,21 @@ struct MeshData {
     uint32_t normals_mode = 0;
     bool vn_stale = false;
     // rt_scene_set_mesh_skin (rt_mi355x.h, "mesh skinning"): the skin -- n_bones (0: none bound), four influences a vertex, the
-    // rest pose -- and the last pose, 12 floats a bone.  v_stale: a pose replaced v since it was last written; v (whose size stays)
-    // is computed again from rest and pose (rt_mesh_skin's arithmetic) with root_box when somebody reads it (ensure_vertices).
-    // v_prev_stale: the same for v_prev, owed from pose_prev -- a flagged pose on a stale v hands the pose on, not the vertices.
+    // rest pose
     int32_t skin_bones = 0;
     std::vector<uint16_t> skin_index;
-    std::vector<float> skin_weight, skin_rest, pose, pose_prev;
-    bool v_stale = false, v_prev_stale = false;
+    std::vector<float> skin_weight, skin_rest;
     uint32_t skin_serial = 0;            // counts the skins bound to this mesh: a device's copy of another one is uploaded again
     // rt_scene_set_mesh_morphs (rt_mi355x.h, "morph targets"): the set -- morph_targets (0: none bound), the base, the deltas
-    // (morph_targets x nv x 3) -- and the last morph pose's weights.  v_morphed: the pose v is owed from (v_stale) is a morph pose --
-    // morph_weights over the base, and then, v_morph_skinned, the skin with `pose` over that; else it is a bone pose over skin_rest.
-    // The same three for v_prev (v_prev_stale): morph_weights_prev, pose_prev.
+    // (morph_targets x nv x 3)
     int32_t morph_targets = 0;
-    std::vector<float> morph_base, morph_deltas, morph_weights, morph_weights_prev;
-    bool v_morphed = false, v_morph_skinned = false, v_prev_morphed = false, v_prev_morph_skinned = false;
+    std::vector<float> morph_base, morph_deltas;
     uint32_t morph_serial = 0;           // counts the sets bound to this mesh, as skin_serial the skins
+    // The last pose.  v_stale: a pose replaced v since it was last written; v (whose size stays) is computed again from `pose`
+    // (mesh_pose_host's arithmetic) with root_box when somebody reads it (ensure_vertices).  v_prev_stale: the same for v_prev, owed
+    // from pose_prev -- a flagged pose on a stale v hands the pose on, not the vertices.
+    MeshPose pose, pose_prev;
+    bool v_stale = false, v_prev_stale = false;
 };
 struct SceneData {
     std::vector<rt_node> nodes;

@@ -21,9 +21,8 @@
 #include "host/rt_scene.h"
 #include "rt_host.h"
 #include "rt_mesh_normals.h"
-#include "rt_mesh_skin.h"
-#include "rt_mesh_morph.h"
-static_assert(RT_MORPH_MAX_TARGETS == RT_MESH_MORPH_MAX_TARGETS, "rt_mesh_morph.h and rt_mi355x.h disagree on the target cap");
+#include "rt_mesh_pose.h"
+static_assert(RT_POSE_MAX_TARGETS == RT_MESH_MORPH_MAX_TARGETS, "rt_mesh_pose.h and rt_mi355x.h disagree on the target cap");
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local std::string g_err;       // the one message of rt_last_error(), whichever file failed
@@ -136,8 +135,7 @@ extern "C" rt_status rt_scene_set_nodes(rt_scene *s, const rt_node *nodes, int32
     return RT_OK;
 }
 
-static void drop_mesh_skin(rt::MeshData &m);
-static void drop_mesh_morphs(rt::MeshData &m);
+static void drop_mesh_skin(rt::MeshData &m), drop_mesh_morphs(rt::MeshData &m);
 extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const uint32_t *f, int32_t nf,
                                        const float *vn, int32_t nvn, const uint32_t *fn, const rt_bvh_node *nodes,
                                        int32_t nnodes, const uint32_t *elements)
@@ -168,38 +166,37 @@ extern "C" rt_status rt_scene_set_mesh(rt_scene *s, int32_t mesh, const float *v
     return RT_OK;
 }
 
-// the skin of a mesh and everything a pose left behind (caller holds s->mu, and has resolved v if the mesh is to keep its positions)
+// A binding of a mesh dropped (its skin, its morph set), and with either what a pose left behind: nothing stays owed (the callers,
+// s->mu held, have resolved v if the mesh is to keep its positions, so owed positions never outlive what they are owed from)
+static void drop_mesh_poses(rt::MeshData &m) { m.pose = m.pose_prev = rt::MeshPose(); m.v_stale = m.v_prev_stale = false; }
 static void drop_mesh_skin(rt::MeshData &m)
 {
     m.skin_bones = 0;
-    for (std::vector<float> *a : {&m.skin_weight, &m.skin_rest, &m.pose, &m.pose_prev}) std::vector<float>().swap(*a);
+    for (std::vector<float> *a : {&m.skin_weight, &m.skin_rest}) std::vector<float>().swap(*a);
     std::vector<uint16_t>().swap(m.skin_index);
-    m.v_stale = m.v_prev_stale = false;
     m.skin_serial++;
+    drop_mesh_poses(m);
 }
-// ... and the morph set with the weights a morph pose left (the same caller)
 static void drop_mesh_morphs(rt::MeshData &m)
 {
     m.morph_targets = 0;
-    for (std::vector<float> *a : {&m.morph_base, &m.morph_deltas, &m.morph_weights, &m.morph_weights_prev}) std::vector<float>().swap(*a);
-    m.v_morphed = m.v_morph_skinned = m.v_prev_morphed = m.v_prev_morph_skinned = false;
+    for (std::vector<float> *a : {&m.morph_base, &m.morph_deltas}) std::vector<float>().swap(*a);
     m.morph_serial++;
+    drop_mesh_poses(m);
 }
-// positions a pose owes, by the mirrors: a bone pose skins the skin's rest pose; a morph pose morphs the base and then, if bones
-// came with it, skins the result in place
-static void resolve_pose(const rt::MeshData &m, bool morphed, bool morph_skinned, const std::vector<float> &weights, const std::vector<float> &bones, float *out)
+// positions a pose owes: mesh_pose_host over the base of the pose's kind -- a bone pose skins the skin's rest pose; a morph pose
+// morphs the set's base and, if bones came with it, skins that
+static void resolve_pose(const rt::MeshData &m, const rt::MeshPose &p, float *out)
 {
-    if (!morphed) { mesh_skin_host(m.skin_rest.data(), m.skin_rest.size() / 3, m.skin_index.data(), m.skin_weight.data(), bones.data(), out); return; }
-    const uint64_t nv = m.morph_base.size() / 3;
-    mesh_morph_host(m.morph_base.data(), nv, m.morph_deltas.data(), (uint32_t)m.morph_targets, weights.data(), out);
-    if (morph_skinned) mesh_skin_host(out, nv, m.skin_index.data(), m.skin_weight.data(), bones.data(), out);
+    mesh_pose_host(p.morphed ? m.morph_base.data() : m.skin_rest.data(), m.v.size() / 3, m.morph_deltas.data(), p.morphed ? (uint32_t)m.morph_targets : 0u,
+                   p.weights.data(), m.skin_index.data(), m.skin_weight.data(), p.bones.data(), p.skinned ? (uint32_t)m.skin_bones : 0u, out);
 }
 void ensure_vertices(rt::MeshData &m)
 {
-    if (m.v_prev_stale) resolve_pose(m, m.v_prev_morphed, m.v_prev_morph_skinned, m.morph_weights_prev, m.pose_prev, m.v_prev.data());
+    if (m.v_prev_stale) resolve_pose(m, m.pose_prev, m.v_prev.data());
     m.v_prev_stale = false;
     if (!m.v_stale) return;
-    resolve_pose(m, m.v_morphed, m.v_morph_skinned, m.morph_weights, m.pose, m.v.data());
+    resolve_pose(m, m.pose, m.v.data());
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
     m.v_stale = false;
 }
@@ -285,7 +282,7 @@ extern "C" rt_status rt_scene_get_mesh_normals_mode(const rt_scene *s, int32_t m
     return RT_OK;
 }
 
-// ---- mesh skinning (rt_mi355x.h, "mesh skinning"; the kernel: rt_mesh_skin.hip, the pose entry points: rt_mesh_update.cpp) -----
+// ---- mesh skinning (rt_mi355x.h, "mesh skinning"; the kernel: rt_mesh_pose.hip, the pose entry points: rt_mesh_update.cpp) -----
 // what the mirror and rt_scene_set_mesh_skin require of a skin (`who` names the entry point)
 static rt_status check_skin(const char *who, int32_t n_bones, const uint16_t *bone_index, const float *weight, int32_t nv)
 {
@@ -311,7 +308,7 @@ extern "C" rt_status rt_mesh_skin(const float *v_rest, int32_t nv, const uint16_
     if (!v_rest || !v_out) return fail(RT_ERR_ARG, "rt_mesh_skin: v_rest and v_out are required");
     rt_status st = check_skin("rt_mesh_skin", n_bones, bone_index, weight, nv);
     if (st || (st = check_pose("rt_mesh_skin", bones, n_bones))) return st;
-    mesh_skin_host(v_rest, (uint64_t)nv, bone_index, weight, bones, v_out);
+    mesh_skin_host(v_rest, (uint64_t)nv, bone_index, weight, bones, (uint32_t)n_bones, v_out);
     return RT_OK;
 }
 
@@ -325,7 +322,7 @@ extern "C" rt_status rt_scene_set_mesh_skin(rt_scene *s, int32_t mesh, int32_t n
     if ((size_t)nv != m.v.size() / 3) return fail(RT_ERR_ARG, "rt_scene_set_mesh_skin: nv is %d, the mesh has %zu vertices", nv, m.v.size() / 3);
     ensure_vertices(m);                 // the rest pose is the positions of now
     drop_mesh_skin(m);
-    release_mesh_skin_on_devices(s, mesh);
+    release_mesh_binding_on_devices(s, mesh, BINDING_SKIN);
     m.skin_bones = n_bones;
     m.skin_index.assign(bone_index, bone_index + 4 * (size_t)nv);
     m.skin_weight.assign(weight, weight + 4 * (size_t)nv);
@@ -342,7 +339,7 @@ extern "C" rt_status rt_scene_clear_mesh_skin(rt_scene *s, int32_t mesh)
     rt::MeshData &m = s->data.meshes[mesh];
     ensure_vertices(m);                 // the mesh keeps the positions it has
     drop_mesh_skin(m);
-    release_mesh_skin_on_devices(s, mesh);
+    release_mesh_binding_on_devices(s, mesh, BINDING_SKIN);
     return RT_OK;
 }
 
@@ -361,7 +358,7 @@ extern "C" rt_status rt_scene_mesh_skin_info(const rt_scene *s, int32_t mesh, rt
     return RT_OK;
 }
 
-// ---- morph targets (rt_mi355x.h, "morph targets"; the kernel: rt_mesh_morph.hip, the pose entry points: rt_mesh_update.cpp) -----
+// ---- morph targets (rt_mi355x.h, "morph targets"; the kernel: rt_mesh_pose.hip, the pose entry points: rt_mesh_update.cpp) -----
 // RT_ERR_ARG unless every one of n floats is finite (`what` names them)
 rt_status check_finite(const char *who, const char *what, const float *a, int64_t n)
 {
@@ -397,7 +394,7 @@ extern "C" rt_status rt_scene_set_mesh_morphs(rt_scene *s, int32_t mesh, int32_t
     if ((size_t)nv != m.v.size() / 3) return fail(RT_ERR_ARG, "rt_scene_set_mesh_morphs: nv is %d, the mesh has %zu vertices", nv, m.v.size() / 3);
     ensure_vertices(m);                 // the base is the positions of now
     drop_mesh_morphs(m);
-    release_mesh_morphs_on_devices(s, mesh);
+    release_mesh_binding_on_devices(s, mesh, BINDING_MORPHS);
     m.morph_targets = n_targets;
     m.morph_deltas.assign(deltas, deltas + 3 * (size_t)nv * (size_t)n_targets);
     m.morph_base = m.v;
@@ -413,7 +410,7 @@ extern "C" rt_status rt_scene_clear_mesh_morphs(rt_scene *s, int32_t mesh)
     rt::MeshData &m = s->data.meshes[mesh];
     ensure_vertices(m);                 // the mesh keeps the positions it has
     drop_mesh_morphs(m);
-    release_mesh_morphs_on_devices(s, mesh);
+    release_mesh_binding_on_devices(s, mesh, BINDING_MORPHS);
     return RT_OK;
 }
 

@@ -27,7 +27,7 @@
 #include "../../include/rt_mi355x.h"
 #include "host/rt_scene.h"
 #include "rt_launch.h"
-#include "rt_mesh_morph.h"
+#include "rt_mesh_pose.h"
 #include "rt_photon_map.h"
 
 #define RT_HIDDEN __attribute__((visibility("hidden")))
@@ -111,13 +111,13 @@ struct DevMeshBufs {
     // corners of a row ascending, on the device from the mesh's first update in SMOOTH mode there (with f, which that kernel reads
     // too).  They follow the faces and fn, which stay: a device build keeps them.
     DevBuf nadj_off, nadj_corner;
-    // mesh skinning (rt_mesh_skin.hip): the skin -- rest pose, bone indices, weights -- on the device from the mesh's first pose there
+    // mesh skinning (rt_mesh_pose.hip): the skin -- rest pose, bone indices, weights -- on the device from the mesh's first pose there
     // (skin_serial: which of the mesh's skins it is, MeshData::skin_serial), and the root record of the tree as a pose's tail reads it back
     DevBuf skin_rest, skin_index, skin_weight;
     uint32_t skin_serial = 0;
     float root_rec_host[32];
     void release_skin() { for (DevBuf *b : {&skin_rest, &skin_index, &skin_weight}) b->release(); }
-    // morph targets (rt_mesh_morph.hip): the set -- base, deltas -- on the device from the mesh's first morph pose there
+    // morph targets (rt_mesh_pose.hip): the set -- base, deltas -- on the device from the mesh's first morph pose there
     // (morph_serial: MeshData::morph_serial)
     DevBuf morph_base, morph_deltas;
     uint32_t morph_serial = 0;
@@ -203,11 +203,12 @@ struct DeviceState {
     // the last in-place mesh update here (rt_scene_mesh_update_ms): events around its upload, k_mesh_retri and the refit launches
     Event upd_ev[4]; int upd_levels = -1;
     Event nrm_ev[2]; bool nrm_timed = false;        // around the last k_mesh_normals here (rt_scene_mesh_normals_ms)
-    Event skin_ev[2]; bool skin_timed = false;      // around the last k_mesh_skin here (rt_scene_mesh_skin_ms)
-    DevBuf skin_bones;                  // the pose k_mesh_skin stages from: 48 bytes a bone, uploaded at every pose
-    Event morph_ev[2]; bool morph_timed = false;    // around the last k_mesh_morph here (rt_scene_mesh_morph_ms)
-    DevBuf morph_active;                // the active list k_mesh_morph reads: 8 bytes a non-zero weight, uploaded at every morph pose
-    MeshMorphActive morph_active_host[RT_MORPH_MAX_TARGETS];      // ... where the host compacts it (the source of an asynchronous copy)
+    // around the last k_mesh_pose here of either kind: [0] a bone pose (rt_scene_mesh_skin_ms), [1] a morph pose, with or without
+    // bones (rt_scene_mesh_morph_ms)
+    Event pose_ev[2][2]; bool pose_timed[2] = {false, false};
+    DevBuf skin_bones;                  // the bones k_mesh_pose stages from: 48 bytes a bone, uploaded at every pose that has any
+    DevBuf morph_active;                // the active list k_mesh_pose reads: 8 bytes a non-zero weight, uploaded at every morph pose
+    MeshMorphActive morph_active_host[RT_POSE_MAX_TARGETS];       // ... where the host compacts it (the source of an asynchronous copy)
     Event cost_ev[2];                   // around the last k_bvh_cost here and the copies behind it (rt_mesh_quality.measure_ms)
     MeshBuildBufs build;                // device tree builds here
     // one of the two maps: its buffers with what the kernels see of it
@@ -223,11 +224,9 @@ struct DeviceState {
         for (Event &e : cost_ev) e = Event();
         for (Event &e : nrm_ev) e = Event();
         nrm_timed = false;
-        for (Event &e : skin_ev) e = Event();
-        skin_timed = false;
+        for (auto &kind : pose_ev) for (Event &e : kind) e = Event();
+        pose_timed[0] = pose_timed[1] = false;
         skin_bones.release();
-        for (Event &e : morph_ev) e = Event();
-        morph_timed = false;
         morph_active.release();
         upd_levels = -1;
         for (Workspace &w : ws) w.release();
@@ -281,12 +280,12 @@ RT_HIDDEN void ensure_normals(rt::MeshData &m);
 RT_HIDDEN void ensure_vertices(rt::MeshData &m);
 // rt_api.cpp: RT_ERR_ARG unless every one of the pose's 12 n_bones floats is finite
 RT_HIDDEN rt_status check_pose(const char *who, const float *bones, int32_t n_bones);
-// rt_mesh_update.cpp: what the devices hold of one mesh's skin, released (caller holds s->mu; the scene is idle)
-RT_HIDDEN void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh);
+// rt_mesh_update.cpp: what the devices hold of one binding of a mesh -- its skin, or its morph set -- released (caller holds s->mu;
+// the scene is idle)
+enum MeshBinding { BINDING_SKIN, BINDING_MORPHS };
+RT_HIDDEN void release_mesh_binding_on_devices(rt_scene *s, int32_t mesh, MeshBinding which);
 // rt_api.cpp: RT_ERR_ARG unless `a` is there and every one of its n floats is finite (`what` names the array in the message)
 RT_HIDDEN rt_status check_finite(const char *who, const char *what, const float *a, int64_t n);
-// rt_mesh_update.cpp: ... and of its morph set
-RT_HIDDEN void release_mesh_morphs_on_devices(rt_scene *s, int32_t mesh);
 // rt_api.cpp: RT_ERR_ARG "<who>: mesh <mesh> was never set" unless rt_scene_set_mesh has given the scene that mesh (caller holds s->mu)
 RT_HIDDEN rt_status check_mesh_set(const rt_scene *s, int32_t mesh, const char *who);
 // rt_lower.cpp: the scene's objects as upload_scene lowers them, with the material of every node; an in-place mesh update sends the

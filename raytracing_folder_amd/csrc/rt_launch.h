@@ -262,22 +262,15 @@ struct MeshNormalsRequest {
     float *vn;
 };
 
-// One skinned mesh posed on a device (rt_mesh_skin.hip; the definition: rt_mi355x.h, "mesh skinning").  rest (nv x 3 floats),
-// bone_index (nv x 4 uint16, 8-byte aligned) and weight (nv x 4 floats, 16-byte aligned) are the skin as the store checked it:
-// every index below n_bones.  bones: the pose, n_bones x 12 floats, 16-byte aligned, n_bones in 1 .. 1024.  out (nv x 3 floats, not
-// rest) receives every posed position.
-struct MeshSkinRequest {
-    const float *rest; const uint16_t *bone_index; const float *weight;
-    const float *bones; uint32_t n_bones;
-    uint32_t nv; float *out;
-};
-
-// One mesh with morph targets posed on a device (rt_mesh_morph.hip; the definition: rt_mi355x.h, "morph targets").  base (nv x 3
-// floats) and deltas (n_targets x nv x 3 floats) are the set as the store checked it.  active: n_active (0 .. 256) pairs of
-// (uint32 target, float weight), 8 bytes each, ascending by target, every target below the set's n_targets, every weight non-zero.
-// n_bones == 0: morph only, and bone_index, weight and bones are not read; else they are MeshSkinRequest's, and the skin is
-// applied to the morphed position.  out (nv x 3 floats, not base) receives every position.
-struct MeshMorphRequest {
+// One mesh posed on a device (rt_mesh_pose.hip; the definitions: rt_mi355x.h, "mesh skinning" and "morph targets").  base: nv x 3
+// floats.  A MORPH pose: base and deltas (n_targets x nv x 3 floats) are the set as the store checked it; active: n_active
+// (0 .. 256) pairs of (uint32 target, float weight), 8 bytes each, ascending by target, every target below the set's n_targets,
+// every weight non-zero.  A BONE pose: n_active is 0, deltas and active may be NULL, base is the skin's rest positions.
+// n_bones == 0 (only with deltas): no skin, and bone_index, weight and bones are not read; else bone_index (nv x 4 uint16, 8-byte
+// aligned) and weight (nv x 4 floats, 16-byte aligned) are the skin as the store checked it -- every index below n_bones -- bones
+// the pose, n_bones (1 .. 1024) x 12 floats, 16-byte aligned, and the skin is applied to the morphed position.  out (nv x 3
+// floats, not base) receives every position.
+struct MeshPoseRequest {
     const float *base; const float *deltas;
     const void *active; uint32_t n_active;
     const uint16_t *bone_index; const float *weight;
@@ -411,13 +404,9 @@ hipError_t rtk_launch_bvh_cost(hipStream_t st, const BvhCostRequest &R);
 // on `st`: k_mesh_normals over the mesh's normals (ahead of k_mesh_retri, which copies them into the slots)
 hipError_t rtk_launch_mesh_normals(hipStream_t st, const MeshNormalsRequest &R);
 
-// ---- rt_mesh_skin.hip: a skinned mesh posed on the device ------------------------------------------------------------------
-// on `st`: k_mesh_skin over the mesh's vertices (ahead of k_mesh_normals and everything else that reads them)
-hipError_t rtk_launch_mesh_skin(hipStream_t st, const MeshSkinRequest &R);
-
-// ---- rt_mesh_morph.hip: a mesh with morph targets posed on the device -------------------------------------------------------
-// on `st`: k_mesh_morph over the mesh's vertices (in k_mesh_skin's place: one launch, whether or not bones came)
-hipError_t rtk_launch_mesh_morph(hipStream_t st, const MeshMorphRequest &R);
+// ---- rt_mesh_pose.hip: a mesh posed on the device by bones, morph targets or both ------------------------------------------
+// on `st`: k_mesh_pose over the mesh's vertices (ahead of k_mesh_normals and everything else that reads them): one launch a pose
+hipError_t rtk_launch_mesh_pose(hipStream_t st, const MeshPoseRequest &R);
 
 // ---- rt_bvh_build.hip: a mesh's tree built on the device ------------------------------------------------------------------
 // bytes of the sort's temporary storage for n_faces keys

@@ -1,8 +1,7 @@
 // rt_mesh_update.cpp -- everything that changes a lowered mesh in place: the six rt_scene_update_mesh_vertices*, the four
 // rt_scene_pose_mesh* and the four rt_scene_morph_mesh* entry points on one entry path, their share of the scene store, and what
 // they do on the devices that hold the scene -- the refit (rt_refit.hip), the refitted tree's quality (k_bvh_cost), the device tree
-// build (rt_bvh_build.hip), smooth normals (rt_mesh_normals.hip), a skinned mesh's pose (rt_mesh_skin.hip), morph targets
-// (rt_mesh_morph.hip) -- behind
+// build (rt_bvh_build.hip), smooth normals (rt_mesh_normals.hip), a pose by bones, morph targets or both (rt_mesh_pose.hip) -- behind
 // one per-device upload and one loop over the devices; the host mirrors of the cost and of the build; the calls that read a mesh
 // back from a device.  rt_lower.cpp put the mesh there (upload_scene); rt_host.h is what the host files share.
 #include <hip/hip_runtime.h>
@@ -24,24 +23,38 @@
 #include "rt_mesh_normals.h"
 
 // ---- the store's share -----------------------------------------------------------------------------------------------------
-// What the six entry points share once their arguments have passed: the checks against the mesh (`who` names the entry point in
+// Where an entry point's new vertices come from: the array it brought (with normals, or without), a bone pose of the mesh's skin
+// (rt_scene_pose_mesh*), or a morph pose of its morph set (rt_scene_morph_mesh*): weights, and bones that may be NULL
+enum InputKind { INPUT_VERTICES, INPUT_BONE_POSE, INPUT_MORPH_POSE };
+struct MeshInput {
+    InputKind kind;
+    const float *v; int32_t nv; const float *vn; int32_t nvn;
+    const float *bones; int32_t n_bones; const float *weights; int32_t n_targets;
+};
+static MeshInput input_vertices(const float *v, int32_t nv, const float *vn, int32_t nvn) { return {INPUT_VERTICES, v, nv, vn, nvn, nullptr, 0, nullptr, 0}; }
+static MeshInput input_bones(const float *bones, int32_t n_bones) { return {INPUT_BONE_POSE, nullptr, 0, nullptr, 0, bones, n_bones, nullptr, 0}; }
+static MeshInput input_morphs(const float *weights, int32_t n_targets, const float *bones, int32_t n_bones)
+{
+    return {INPUT_MORPH_POSE, nullptr, 0, nullptr, 0, bones, n_bones, weights, n_targets};
+}
+
+// What the entry points share once their arguments have passed: the checks against the mesh (`who` names the entry point in
 // the message) and the new vertices in the store.  keep_previous (RT_MESH_UPDATE_KEEP_PREVIOUS): the positions the mesh had
 // become its previous positions; without it the mesh holds none afterwards.  The caller holds s->mu.
-static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, bool keep_previous,
-                                     const char *who)
+static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const MeshInput &in, bool keep_previous, const char *who)
 {
     rt_status st = check_mesh_set(s, mesh, who);
     if (st) return st;
     rt::MeshData &m = s->data.meshes[mesh];
-    if ((size_t)nv != m.v.size() / 3 || nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, nv, m.v.size() / 3);
-    if ((vn || nvn != 0) && ((size_t)nvn != m.vn.size() / 3 || nvn < 0))
-        return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, nvn, m.vn.size() / 3);
+    if ((size_t)in.nv != m.v.size() / 3 || in.nv < 0) return fail(RT_ERR_ARG, "%s: nv is %d, the mesh has %zu vertices (the faces stay as they are)", who, in.nv, m.v.size() / 3);
+    if ((in.vn || in.nvn != 0) && ((size_t)in.nvn != m.vn.size() / 3 || in.nvn < 0))
+        return fail(RT_ERR_ARG, "%s: nvn is %d, the mesh has %zu normals", who, in.nvn, m.vn.size() / 3);
     // (a posed mesh: positions a pose still owes are resolved before they become the previous ones, and dropped otherwise)
     if (keep_previous) { ensure_vertices(m); m.v_prev.swap(m.v); } else { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
-    m.v.assign(v, v + 3 * (size_t)nv);
+    m.v.assign(in.v, in.v + 3 * (size_t)in.nv);
     m.v_stale = false;
     // SMOOTH mode without normals: the devices compute them (begin_mesh_update), the store when they are next read -- not here
-    if (vn) { m.vn.assign(vn, vn + 3 * (size_t)nvn); m.vn_stale = false; }
+    if (in.vn) { m.vn.assign(in.vn, in.vn + 3 * (size_t)in.nvn); m.vn_stale = false; }
     else if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
     m.tree_stale = true;
     rt::MeshRootBox(m.v.data(), m.f.data(), (unsigned)(m.f.size() / 3), m.root_box);
@@ -50,18 +63,32 @@ static rt_status store_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, 
     return RT_OK;
 }
 
-// ... and a pose in the store (rt_mi355x.h, "mesh skinning"): the matrices and a mark, no per-vertex work -- v is owed from then on
-// (ensure_vertices), and so is root_box unless a device reports it.  keep_previous: the previous positions are the ones the mesh
-// had -- v itself where the store has it, the pose it is owed from where it does not.
-// (the three cases of keep_previous, for a bone pose and a morph pose alike: none kept; the pose v is owed from handed on -- bones,
-// morph weights and which of the two kinds it was; v itself where the store has it)
-static void pose_keeps_previous(rt::MeshData &m, bool keep_previous)
+// ... and a pose in the store (rt_mi355x.h, "mesh skinning", "morph targets"): each kind's checks, then the pose -- bones, or
+// weights and the bones if any came -- and a mark, no per-vertex work: v is owed from then on (ensure_vertices), and so is root_box
+// unless a device reports it.
+static rt_status store_mesh_pose(rt_scene *s, int32_t mesh, const MeshInput &in, bool keep_previous, const char *who)
 {
+    rt_status st = check_mesh_set(s, mesh, who);
+    if (st) return st;
+    rt::MeshData &m = s->data.meshes[mesh];
+    const bool morph = in.kind == INPUT_MORPH_POSE, skinned = !morph || in.bones;
+    if (!morph) {
+        if (m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
+        if (in.n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, in.n_bones, m.skin_bones);
+        if ((st = check_pose(who, in.bones, in.n_bones))) return st;
+    } else {
+        if (m.morph_targets == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no morph set (rt_scene_set_mesh_morphs binds one)", who, mesh);
+        if (in.bones && m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: bones given and mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
+        if (in.n_targets != m.morph_targets) return fail(RT_ERR_ARG, "%s: n_targets is %d, the morph set has %d", who, in.n_targets, m.morph_targets);
+        if (!in.bones && in.n_bones != 0) return fail(RT_ERR_ARG, "%s: bones is NULL and n_bones is %d", who, in.n_bones);
+        if (in.bones && in.n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, in.n_bones, m.skin_bones);
+        if ((st = check_finite(who, "weights", in.weights, in.n_targets)) || (in.bones && (st = check_pose(who, in.bones, in.n_bones)))) return st;
+    }
+    // keep_previous, three cases: none kept; v is owed itself, and the pose it is owed from is handed on, not the vertices; the
+    // store has v, which becomes v_prev where it is
     if (!keep_previous) { std::vector<float>().swap(m.v_prev); m.v_prev_stale = false; }
     else if (m.v_stale) {
         m.pose_prev = m.pose;
-        m.morph_weights_prev = m.morph_weights;
-        m.v_prev_morphed = m.v_morphed; m.v_prev_morph_skinned = m.v_morph_skinned;
         if (m.v_prev.size() != m.v.size()) m.v_prev.resize(m.v.size());
         m.v_prev_stale = true;
     } else {
@@ -69,48 +96,13 @@ static void pose_keeps_previous(rt::MeshData &m, bool keep_previous)
         m.v_prev_stale = false;
         if (m.v.size() != m.v_prev.size()) m.v.resize(m.v_prev.size());
     }
-}
-// (what every pose leaves behind the pose itself)
-static void pose_marks_store(rt_scene *s, rt::MeshData &m)
-{
+    m.pose.morphed = morph; m.pose.skinned = skinned;
+    if (morph) m.pose.weights.assign(in.weights, in.weights + in.n_targets);      // (the other kind's last array stays: it is not read)
+    if (skinned) m.pose.bones.assign(in.bones, in.bones + 12 * (size_t)in.n_bones);
     m.v_stale = true;
     if (m.normals_mode == RT_MESH_NORMALS_SMOOTH) m.vn_stale = true;
     m.tree_stale = true;
     s->drop_generated_photons();
-}
-static rt_status store_mesh_pose(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, bool keep_previous, const char *who)
-{
-    rt_status st = check_mesh_set(s, mesh, who);
-    if (st) return st;
-    rt::MeshData &m = s->data.meshes[mesh];
-    if (m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
-    if (n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, n_bones, m.skin_bones);
-    if ((st = check_pose(who, bones, n_bones))) return st;
-    pose_keeps_previous(m, keep_previous);
-    m.pose.assign(bones, bones + 12 * (size_t)n_bones);
-    m.v_morphed = m.v_morph_skinned = false;
-    pose_marks_store(s, m);
-    return RT_OK;
-}
-
-// ... and a morph pose (rt_mi355x.h, "morph targets"): the weights, the bones if any came, and the same mark
-static rt_status store_mesh_morph_pose(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
-                                       bool keep_previous, const char *who)
-{
-    rt_status st = check_mesh_set(s, mesh, who);
-    if (st) return st;
-    rt::MeshData &m = s->data.meshes[mesh];
-    if (m.morph_targets == 0) return fail(RT_ERR_STATE, "%s: mesh %d has no morph set (rt_scene_set_mesh_morphs binds one)", who, mesh);
-    if (bones && m.skin_bones == 0) return fail(RT_ERR_STATE, "%s: bones given and mesh %d has no skin (rt_scene_set_mesh_skin binds one)", who, mesh);
-    if (n_targets != m.morph_targets) return fail(RT_ERR_ARG, "%s: n_targets is %d, the morph set has %d", who, n_targets, m.morph_targets);
-    if (!bones && n_bones != 0) return fail(RT_ERR_ARG, "%s: bones is NULL and n_bones is %d", who, n_bones);
-    if (bones && n_bones != m.skin_bones) return fail(RT_ERR_ARG, "%s: n_bones is %d, the skin has %d", who, n_bones, m.skin_bones);
-    if ((st = check_finite(who, "weights", weights, n_targets)) || (bones && (st = check_pose(who, bones, n_bones)))) return st;
-    pose_keeps_previous(m, keep_previous);
-    m.morph_weights.assign(weights, weights + n_targets);
-    if (bones) m.pose.assign(bones, bones + 12 * (size_t)n_bones);
-    m.v_morphed = true; m.v_morph_skinned = bones != nullptr;
-    pose_marks_store(s, m);
     return RT_OK;
 }
 
@@ -144,90 +136,71 @@ static rt_status enqueue_mesh_normals(DeviceState *D, const rt::MeshData &m, Dev
     return RT_OK;
 }
 
-// Skinning (rt_mi355x.h, "mesh skinning"), one device's share in the same two steps.  prepare: the skin -- rest pose, indices,
-// weights -- on the device from the mesh's first pose there, and room for the pose.  enqueue: the pose and the launch on the
-// update's stream, in place of the vertex upload and ahead of k_mesh_normals, between the events rt_scene_mesh_skin_ms reads.
-static rt_status prepare_mesh_skin(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+// A pose (rt_mi355x.h, "mesh skinning", "morph targets"), one device's share in the same two steps, whatever the pose's kind.
+// prepare: what the kind reads, on the device from the mesh's first pose of that kind there -- the skin (rest pose, indices,
+// weights) and room for the bones if the pose has bones, the morph set (base, deltas) and room for the active list if it has
+// weights.  enqueue: the active list (compacted here: 8 bytes a non-zero weight), the bones (48 bytes each), and ONE launch of
+// k_mesh_pose on the update's stream, in place of the vertex upload and ahead of k_mesh_normals, between the events of the kind:
+// a bone pose times into rt_scene_mesh_skin_ms, a morph pose -- with bones or without -- into rt_scene_mesh_morph_ms.
+static rt_status prepare_mesh_pose(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
 {
+    const rt::MeshPose &p = m.pose;
     rt_status rs;
-    for (Event &e : D->skin_ev) if (!e.e) HIP_TRY(e.create());
-    if ((rs = D->skin_bones.ensure(m.pose.size() * 4))) return rs;
-    if (mb.skin_rest.p && mb.skin_serial == m.skin_serial) return RT_OK;
-    if ((rs = mb.skin_rest.upload(m.skin_rest.data(), m.skin_rest.size() * 4)) || (rs = mb.skin_index.upload(m.skin_index.data(), m.skin_index.size() * 2)) ||
-        (rs = mb.skin_weight.upload(m.skin_weight.data(), m.skin_weight.size() * 4))) return rs;
-    mb.skin_serial = m.skin_serial;
+    for (Event &e : D->pose_ev[p.morphed]) if (!e.e) HIP_TRY(e.create());
+    if (p.morphed && (rs = D->morph_active.ensure(sizeof(D->morph_active_host)))) return rs;
+    if (p.skinned) {
+        if ((rs = D->skin_bones.ensure(p.bones.size() * 4))) return rs;
+        if (!mb.skin_rest.p || mb.skin_serial != m.skin_serial) {
+            if ((rs = mb.skin_rest.upload(m.skin_rest.data(), m.skin_rest.size() * 4)) || (rs = mb.skin_index.upload(m.skin_index.data(), m.skin_index.size() * 2)) ||
+                (rs = mb.skin_weight.upload(m.skin_weight.data(), m.skin_weight.size() * 4))) return rs;
+            mb.skin_serial = m.skin_serial;
+        }
+    }
+    if (p.morphed && (!mb.morph_base.p || mb.morph_serial != m.morph_serial)) {
+        if ((rs = mb.morph_base.upload(m.morph_base.data(), m.morph_base.size() * 4)) || (rs = mb.morph_deltas.upload(m.morph_deltas.data(), m.morph_deltas.size() * 4))) return rs;
+        mb.morph_serial = m.morph_serial;
+    }
     return RT_OK;
 }
-static rt_status enqueue_mesh_skin(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
+static rt_status enqueue_mesh_pose(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
 {
-    MeshSkinRequest K = {};
-    K.rest = (const float *)mb.skin_rest.p; K.bone_index = (const uint16_t *)mb.skin_index.p; K.weight = (const float *)mb.skin_weight.p;
-    K.bones = (const float *)D->skin_bones.p; K.n_bones = (uint32_t)m.skin_bones;
-    K.nv = (uint32_t)(m.skin_rest.size() / 3); K.out = (float *)mb.v.p;
-    HIP_TRY(hipMemcpyAsync(D->skin_bones.p, m.pose.data(), m.pose.size() * 4, hipMemcpyHostToDevice, D->stream));
-    HIP_TRY(hipEventRecord(D->skin_ev[0], D->stream));
-    HIP_TRY(rtk_launch_mesh_skin(D->stream, K));
-    HIP_TRY(hipEventRecord(D->skin_ev[1], D->stream));
-    D->skin_timed = true;
-    return RT_OK;
-}
-void release_mesh_skin_on_devices(rt_scene *s, int32_t mesh)
-{
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (DeviceState *D : s->devs)
-        if ((size_t)mesh < D->mesh_bufs.size() && D->mesh_bufs[mesh].skin_rest.p && hipSetDevice(D->device) == hipSuccess) D->mesh_bufs[mesh].release_skin();
-    if (!s->devs.empty()) (void)hipSetDevice(cur);
-}
-
-// Morph targets (rt_mi355x.h, "morph targets"), one device's share in the same two steps.  prepare: the set -- base, deltas -- on
-// the device from the mesh's first morph pose there, room for the active list, and, if bones came, the skin and room for them
-// (prepare_mesh_skin).  enqueue: the active list (compacted here: 8 bytes a non-zero weight), the bones if any, and ONE launch of
-// k_mesh_morph in the vertex upload's place, between the events rt_scene_mesh_morph_ms reads.
-static rt_status prepare_mesh_morph(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
-{
-    rt_status rs;
-    for (Event &e : D->morph_ev) if (!e.e) HIP_TRY(e.create());
-    if ((rs = D->morph_active.ensure(sizeof(D->morph_active_host)))) return rs;
-    if (m.v_morph_skinned && (rs = prepare_mesh_skin(D, m, mb))) return rs;
-    if (mb.morph_base.p && mb.morph_serial == m.morph_serial) return RT_OK;
-    if ((rs = mb.morph_base.upload(m.morph_base.data(), m.morph_base.size() * 4)) || (rs = mb.morph_deltas.upload(m.morph_deltas.data(), m.morph_deltas.size() * 4))) return rs;
-    mb.morph_serial = m.morph_serial;
-    return RT_OK;
-}
-static rt_status enqueue_mesh_morph(DeviceState *D, const rt::MeshData &m, DevMeshBufs &mb)
-{
-    MeshMorphRequest K = {};
-    K.base = (const float *)mb.morph_base.p; K.deltas = (const float *)mb.morph_deltas.p;
-    K.active = D->morph_active.p; K.n_active = mesh_morph_compact(m.morph_weights.data(), (uint32_t)m.morph_targets, D->morph_active_host);
-    K.nv = (uint32_t)(m.morph_base.size() / 3); K.out = (float *)mb.v.p;
-    if (K.n_active) HIP_TRY(hipMemcpyAsync(D->morph_active.p, D->morph_active_host, K.n_active * sizeof(MeshMorphActive), hipMemcpyHostToDevice, D->stream));
-    if (m.v_morph_skinned) {
+    const rt::MeshPose &p = m.pose;
+    MeshPoseRequest K = {};
+    K.base = (const float *)(p.morphed ? mb.morph_base.p : mb.skin_rest.p);
+    K.nv = (uint32_t)(m.v.size() / 3); K.out = (float *)mb.v.p;
+    if (p.morphed) {
+        K.deltas = (const float *)mb.morph_deltas.p; K.active = D->morph_active.p;
+        K.n_active = mesh_morph_compact(p.weights.data(), (uint32_t)m.morph_targets, D->morph_active_host);
+        if (K.n_active) HIP_TRY(hipMemcpyAsync(D->morph_active.p, D->morph_active_host, K.n_active * sizeof(MeshMorphActive), hipMemcpyHostToDevice, D->stream));
+    }
+    if (p.skinned) {
         K.bone_index = (const uint16_t *)mb.skin_index.p; K.weight = (const float *)mb.skin_weight.p;
         K.bones = (const float *)D->skin_bones.p; K.n_bones = (uint32_t)m.skin_bones;
-        HIP_TRY(hipMemcpyAsync(D->skin_bones.p, m.pose.data(), m.pose.size() * 4, hipMemcpyHostToDevice, D->stream));
+        HIP_TRY(hipMemcpyAsync(D->skin_bones.p, p.bones.data(), p.bones.size() * 4, hipMemcpyHostToDevice, D->stream));
     }
-    HIP_TRY(hipEventRecord(D->morph_ev[0], D->stream));
-    HIP_TRY(rtk_launch_mesh_morph(D->stream, K));
-    HIP_TRY(hipEventRecord(D->morph_ev[1], D->stream));
-    D->morph_timed = true;
+    HIP_TRY(hipEventRecord(D->pose_ev[p.morphed][0], D->stream));
+    HIP_TRY(rtk_launch_mesh_pose(D->stream, K));
+    HIP_TRY(hipEventRecord(D->pose_ev[p.morphed][1], D->stream));
+    D->pose_timed[p.morphed] = true;
     return RT_OK;
 }
-void release_mesh_morphs_on_devices(rt_scene *s, int32_t mesh)
+void release_mesh_binding_on_devices(rt_scene *s, int32_t mesh, MeshBinding which)
 {
+    const bool morphs = which == BINDING_MORPHS;
     int cur = 0;
     (void)hipGetDevice(&cur);
-    for (DeviceState *D : s->devs)
-        if ((size_t)mesh < D->mesh_bufs.size() && D->mesh_bufs[mesh].morph_base.p && hipSetDevice(D->device) == hipSuccess) D->mesh_bufs[mesh].release_morphs();
+    for (DeviceState *D : s->devs) {
+        if ((size_t)mesh >= D->mesh_bufs.size()) continue;
+        DevMeshBufs &mb = D->mesh_bufs[mesh];
+        if ((morphs ? mb.morph_base.p : mb.skin_rest.p) && hipSetDevice(D->device) == hipSuccess) { if (morphs) mb.release_morphs(); else mb.release_skin(); }
+    }
     if (!s->devs.empty()) (void)hipSetDevice(cur);
 }
 
-// Where an update's new vertices come from on a device: the store (uploaded), the skin (k_mesh_skin writes them from the pose the
-// store holds), the morph set (k_mesh_morph, from the weights and, if any came, the bones), or nowhere -- they are on the device
-// already, behind the refit of the same call.
-enum VertexSource { VERTICES_FROM_STORE, VERTICES_FROM_SKIN, VERTICES_FROM_MORPH, VERTICES_ON_DEVICE };
-// ... computed on the device: the host has no positions, so a flagged pose swaps pointers and the root box is read back
-static bool vertices_computed(VertexSource src) { return src == VERTICES_FROM_SKIN || src == VERTICES_FROM_MORPH; }
+// Where an update's new vertices come from on a device: the store (uploaded), the pose the store holds (k_mesh_pose writes them
+// from its bones, its weights or both), or nowhere -- they are on the device already, behind the refit of the same call.  From a
+// pose the host has no positions, so a flagged pose swaps pointers and the root box is read back.
+enum VertexSource { VERTICES_FROM_STORE, VERTICES_FROM_POSE, VERTICES_ON_DEVICE };
 
 // the box of a tree's root record: per axis the smallest lo and the largest hi over its used children (lo[axis][child],
 // hi[axis][child]; an unused child has a NaN lo on x) -- the exact min / max of the vertices under the faces, MeshRootBox's box
@@ -260,10 +233,9 @@ static bool mesh_textured(const DevMeshBufs &mb, const rt::MeshData &m) { return
 // buffers, the upload between ev[0] and ev[1] (ev: the caller's n_ev events, all made here), smooth normals behind it.
 // with_faces: the device build's arrays -- f, fn and, for a textured mesh, ft and vt -- on the device from the mesh's first build
 // there.  reserve (may be empty): what else the caller's tail allocates, ahead of ev[0] so that nothing is allocated between
-// the events.  src: VERTICES_FROM_SKIN puts the pose's 48 bytes a bone and k_mesh_skin in the vertex upload's place
-// (VERTICES_FROM_MORPH: the active list, the bones if any, and k_mesh_morph), and a flagged
-// pose makes the buffer the positions were in the previous positions' -- two pointers swapped, nothing uploaded; VERTICES_ON_DEVICE
-// leaves positions and previous positions as the refit of the same call left them.
+// the events.  src: VERTICES_FROM_POSE puts the pose -- the active list, 48 bytes a bone -- and k_mesh_pose in the vertex upload's
+// place, and a flagged pose makes the buffer the positions were in the previous positions' -- two pointers swapped, nothing
+// uploaded; VERTICES_ON_DEVICE leaves positions and previous positions as the refit of the same call left them.
 static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh, bool normals_changed, size_t n_objects, const char *who,
                                    Event *ev, size_t n_ev, bool with_faces, const std::function<rt_status()> &reserve,
                                    VertexSource src = VERTICES_FROM_STORE)
@@ -282,13 +254,13 @@ static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh
     const bool textured = mesh_textured(mb, m);
     // SMOOTH mode and no normals brought: the device computes them from the vertices it is about to be sent
     const bool smooth = m.normals_mode == RT_MESH_NORMALS_SMOOTH && !normals_changed;
-    const bool posed = vertices_computed(src), morph = src == VERTICES_FROM_MORPH;
+    const bool posed = src == VERTICES_FROM_POSE;
     // a flagged pose on a device that has the positions: they become the previous ones where they are
     const bool swap_prev = posed && !m.v_prev.empty() && mb.v.p != nullptr;
     const bool upload_prev = src != VERTICES_ON_DEVICE && !m.v_prev.empty() && !swap_prev;
     if (swap_prev) std::swap(mb.v, mb.v_prev);
     if ((rs = mb.v.ensure(m.v.size() * 4)) || (rs = mb.vn.ensure(m.vn.size() * 4))) return rs;
-    if (posed && (rs = morph ? prepare_mesh_morph(D, m, mb) : prepare_mesh_skin(D, m, mb))) return rs;
+    if (posed && (rs = prepare_mesh_pose(D, m, mb))) return rs;
     if (smooth && (rs = prepare_mesh_normals(D, m, mb))) return rs;
     // the store's normals are about to be read: never stale ones over what k_mesh_normals wrote here (the first time they are
     // the values the kernel's kept normals keep -- which stale ones are as well: a pose does not resolve the store for them)
@@ -304,7 +276,7 @@ static rt_status begin_mesh_update(DeviceState *D, rt::MeshData &m, int32_t mesh
     if (reserve && (rs = reserve())) return rs;
     HIP_TRY(hipEventRecord(ev[0], st));
     if (upload_prev) HIP_TRY(hipMemcpyAsync(mb.v_prev.p, m.v_prev.data(), m.v_prev.size() * 4, hipMemcpyHostToDevice, st));
-    if (posed) { if ((rs = morph ? enqueue_mesh_morph(D, m, mb) : enqueue_mesh_skin(D, m, mb))) return rs; }
+    if (posed) { if ((rs = enqueue_mesh_pose(D, m, mb))) return rs; }
     else if (src == VERTICES_FROM_STORE) HIP_TRY(hipMemcpyAsync(mb.v.p, m.v.data(), m.v.size() * 4, hipMemcpyHostToDevice, st));
     if (first || normals_changed) HIP_TRY(hipMemcpyAsync(mb.vn.p, m.vn.data(), m.vn.size() * 4, hipMemcpyHostToDevice, st));
     if (faces) {
@@ -605,7 +577,7 @@ static rt_status refit_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_c
         rt_mesh_quality mine = {};
         const bool measure = quality && first;
         const rt_status r = refit_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, measure ? &mine : nullptr, src,
-                                                 vertices_computed(src) && first ? &s->data : nullptr);
+                                                 src == VERTICES_FROM_POSE && first ? &s->data : nullptr);
         if (!r && measure) { mine.struct_size = quality->struct_size; *quality = mine; }
         return r;
     });
@@ -623,7 +595,7 @@ static rt_status build_mesh_on_devices(rt_scene *s, int32_t mesh, bool normals_c
     const rt_status ret = on_devices_holding_scene(s, [&](DeviceState *D, std::vector<DevObject> &objs, bool first, bool *stop) {
         rt_mesh_build_info mine = none;
         const rt_status r = build_mesh_on_device(D, s->data.meshes[mesh], mesh, normals_changed, objs, cap, &mine, stop, src,
-                                                 vertices_computed(src) && first ? &s->data : nullptr);
+                                                 src == VERTICES_FROM_POSE && first ? &s->data : nullptr);
         if (!r && first) { *info = mine; info->flags = *stop ? RT_MESH_BUILD_FELL_BACK : RT_MESH_BUILD_ON_DEVICE; }
         return r;
     }, &fell_back);
@@ -639,26 +611,48 @@ enum UpdateAfter { UPDATE_REFIT, UPDATE_REFIT_MEASURE, UPDATE_BUILD, UPDATE_REFI
 // of it (the entry points it is one of word a refused flag their own way), and `after`.  The out-structs need no column: an
 // entry point passes NULL for the one it does not have.
 struct UpdateEntry { const char *who; uint32_t known; bool takes_ratio; UpdateAfter after; };
-// the other way the new vertices arrive: a pose of the mesh's skin (rt_scene_pose_mesh*) in place of v, nv, vn, nvn -- or, morph
-// set, a morph pose (rt_scene_morph_mesh*): weights, and bones that may be NULL
-struct MeshPose { const float *bones; int32_t n_bones; bool morph; const float *weights; int32_t n_targets; };
+// every form there is, a row each, in EntryForm's order: six fed by vertices, and the same four fed by a bone pose and by a morph pose
+enum EntryForm { ENTRY_VERTICES, ENTRY_VERTICES_FLAGS, ENTRY_VERTICES_AUTO, ENTRY_VERTICES_AUTO_FLAGS, ENTRY_VERTICES_BUILD, ENTRY_VERTICES_AUTO_BUILD,
+                 ENTRY_POSE, ENTRY_POSE_AUTO, ENTRY_POSE_BUILD, ENTRY_POSE_AUTO_BUILD,
+                 ENTRY_MORPH, ENTRY_MORPH_AUTO, ENTRY_MORPH_BUILD, ENTRY_MORPH_AUTO_BUILD, ENTRY_FORMS };
+static const uint32_t FLAG_REBUILD = RT_MESH_UPDATE_REBUILD, FLAG_KEEP = RT_MESH_UPDATE_KEEP_PREVIOUS;
+static const UpdateEntry ENTRIES[] = {
+    // (takes what it always took: any bit but REBUILD stays RT_ERR_ARG, and the mesh holds no previous positions afterwards)
+    {"rt_scene_update_mesh_vertices", FLAG_REBUILD, false, UPDATE_REFIT},
+    {"rt_scene_update_mesh_vertices_flags", FLAG_REBUILD | FLAG_KEEP, false, UPDATE_REFIT},
+    {"rt_scene_update_mesh_vertices_auto", 0u, true, UPDATE_REFIT_MEASURE},                    // (has no flags argument)
+    {"rt_scene_update_mesh_vertices_auto_flags", FLAG_KEEP, true, UPDATE_REFIT_MEASURE},
+    {"rt_scene_update_mesh_vertices_build", FLAG_KEEP, false, UPDATE_BUILD},
+    {"rt_scene_update_mesh_vertices_auto_build", FLAG_KEEP, true, UPDATE_REFIT_MEASURE_BUILD},
+    {"rt_scene_pose_mesh", FLAG_REBUILD | FLAG_KEEP, false, UPDATE_REFIT},
+    {"rt_scene_pose_mesh_auto", FLAG_KEEP, true, UPDATE_REFIT_MEASURE},
+    {"rt_scene_pose_mesh_build", FLAG_KEEP, false, UPDATE_BUILD},
+    {"rt_scene_pose_mesh_auto_build", FLAG_KEEP, true, UPDATE_REFIT_MEASURE_BUILD},
+    {"rt_scene_morph_mesh", FLAG_REBUILD | FLAG_KEEP, false, UPDATE_REFIT},
+    {"rt_scene_morph_mesh_auto", FLAG_KEEP, true, UPDATE_REFIT_MEASURE},
+    {"rt_scene_morph_mesh_build", FLAG_KEEP, false, UPDATE_BUILD},
+    {"rt_scene_morph_mesh_auto_build", FLAG_KEEP, true, UPDATE_REFIT_MEASURE_BUILD},
+};
+static_assert(sizeof(ENTRIES) / sizeof(ENTRIES[0]) == ENTRY_FORMS, "a row for every EntryForm");
 
-// A pose is skinned on the devices unless the mesh's tree there is a single leaf -- no root record to read the box from; the mesh is
-// tiny -- in which case the store resolves it now and the update goes the way of one that brought the vertices (caller holds s->mu)
-static VertexSource pose_source(rt_scene *s, int32_t mesh, bool morph)
+// A pose is computed on the devices unless the mesh's tree there is a single leaf -- no root record to read the box from; the mesh
+// is tiny -- in which case the store resolves it now and the update goes the way of one that brought the vertices (caller holds s->mu)
+static VertexSource pose_source(rt_scene *s, int32_t mesh)
 {
     rt::MeshData &m = s->data.meshes[mesh];
     bool leaf = false;
     for (DeviceState *D : s->devs)
         if (D->scene_valid) leaf = leaf || m.f.size() / 3 <= RT_LBVH_LEAF_TRIS || ((size_t)mesh < D->mesh_bufs.size() && (D->mesh_bufs[mesh].root_ref & RT_COST_LEAF));
-    if (!leaf) return morph ? VERTICES_FROM_MORPH : VERTICES_FROM_SKIN;
+    if (!leaf) return VERTICES_FROM_POSE;
     ensure_vertices(m);
     return VERTICES_FROM_STORE;
 }
 
-static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
-                                      uint32_t flags, double max_ratio, rt_mesh_quality *q_out, rt_mesh_build_info *b_out, const MeshPose *pose = nullptr)
+static rt_status update_mesh_vertices(EntryForm form, rt_scene *s, int32_t mesh, const MeshInput &in, uint32_t flags, double max_ratio,
+                                      rt_mesh_quality *q_out, rt_mesh_build_info *b_out)
 {
+    const UpdateEntry &e = ENTRIES[form];
+    const bool pose = in.kind != INPUT_VERTICES;
     rt_status st = check_idle(s, e.who);
     if (st) return st;
     if (flags & ~e.known)
@@ -668,15 +662,13 @@ static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t
         return fail(RT_ERR_ARG, "%s: rt_mesh_quality.struct_size is %u, this library's is %zu", e.who, q_out->struct_size, sizeof(rt_mesh_quality));
     if (b_out && b_out->struct_size != sizeof(rt_mesh_build_info))
         return fail(RT_ERR_ARG, "%s: rt_mesh_build_info.struct_size is %u, this library's is %zu", e.who, b_out->struct_size, sizeof(rt_mesh_build_info));
-    if (!pose && !v) return fail(RT_ERR_ARG, "%s: v is NULL", e.who);
+    if (!pose && !in.v) return fail(RT_ERR_ARG, "%s: v is NULL", e.who);
     std::lock_guard<std::mutex> lk(s->mu);
     const bool keep_previous = (flags & RT_MESH_UPDATE_KEEP_PREVIOUS) != 0;
-    if ((st = !pose ? store_mesh_vertices(s, mesh, v, nv, vn, nvn, keep_previous, e.who)
-              : pose->morph ? store_mesh_morph_pose(s, mesh, pose->weights, pose->n_targets, pose->bones, pose->n_bones, keep_previous, e.who)
-              : store_mesh_pose(s, mesh, pose->bones, pose->n_bones, keep_previous, e.who))) return st;
+    if ((st = pose ? store_mesh_pose(s, mesh, in, keep_previous, e.who) : store_mesh_vertices(s, mesh, in, keep_previous, e.who))) return st;
     if (flags & RT_MESH_UPDATE_REBUILD) { s->invalidate(true, false); return RT_OK; }      // (the next lowering uploads the previous positions from the store)
-    const VertexSource src = pose ? pose_source(s, mesh, pose->morph) : VERTICES_FROM_STORE;
-    const bool normals_changed = vn != nullptr, measure = e.after == UPDATE_REFIT_MEASURE || e.after == UPDATE_REFIT_MEASURE_BUILD;
+    const VertexSource src = pose ? pose_source(s, mesh) : VERTICES_FROM_STORE;
+    const bool normals_changed = in.vn != nullptr, measure = e.after == UPDATE_REFIT_MEASURE || e.after == UPDATE_REFIT_MEASURE_BUILD;
     rt_mesh_quality q = {sizeof(rt_mesh_quality)};
     rt_mesh_build_info b = {sizeof(rt_mesh_build_info)};
     bool build = e.after == UPDATE_BUILD;
@@ -687,106 +679,82 @@ static rt_status update_mesh_vertices(const UpdateEntry &e, rt_scene *s, int32_t
         if (e.after == UPDATE_REFIT_MEASURE_BUILD) build = true; else s->invalidate(true, false);
     }
     // (behind a refit the vertices are on the devices already; the build sends them again with everything else it does, normals
-    // only if this call brought some; a pose is not skinned twice: its vertices stay where the refit's k_mesh_skin wrote them)
-    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b, vertices_computed(src) && e.after != UPDATE_BUILD ? VERTICES_ON_DEVICE : src);
+    // only if this call brought some; a pose is not computed twice: its vertices stay where the refit's k_mesh_pose wrote them)
+    if (build) st = build_mesh_on_devices(s, mesh, normals_changed, &b, src == VERTICES_FROM_POSE && e.after != UPDATE_BUILD ? VERTICES_ON_DEVICE : src);
     if (q_out) *q_out = q;
     if (b_out) *b_out = b;
     return st;
 }
 
-// takes what it always took: any bit but RT_MESH_UPDATE_REBUILD stays RT_ERR_ARG, and the mesh holds no previous positions afterwards
 extern "C" rt_status rt_scene_update_mesh_vertices(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices", RT_MESH_UPDATE_REBUILD, false, UPDATE_REFIT};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, 0.0, nullptr, nullptr);
+    return update_mesh_vertices(ENTRY_VERTICES, s, mesh, input_vertices(v, nv, vn, nvn), flags, 0.0, nullptr, nullptr);
 }
-// ... and the entry point that takes RT_MESH_UPDATE_KEEP_PREVIOUS as well
 extern "C" rt_status rt_scene_update_mesh_vertices_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn, uint32_t flags)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices_flags", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, 0.0, nullptr, nullptr);
+    return update_mesh_vertices(ENTRY_VERTICES_FLAGS, s, mesh, input_vertices(v, nv, vn, nvn), flags, 0.0, nullptr, nullptr);
 }
 extern "C" rt_status rt_scene_update_mesh_vertices_auto(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                                         double max_ratio, rt_mesh_quality *out)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices_auto", 0u, true, UPDATE_REFIT_MEASURE};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, 0u, max_ratio, out, nullptr);
+    return update_mesh_vertices(ENTRY_VERTICES_AUTO, s, mesh, input_vertices(v, nv, vn, nvn), 0u, max_ratio, out, nullptr);
 }
 extern "C" rt_status rt_scene_update_mesh_vertices_auto_flags(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                                               double max_ratio, uint32_t flags, rt_mesh_quality *out)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices_auto_flags", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, max_ratio, out, nullptr);
+    return update_mesh_vertices(ENTRY_VERTICES_AUTO_FLAGS, s, mesh, input_vertices(v, nv, vn, nvn), flags, max_ratio, out, nullptr);
 }
 extern "C" rt_status rt_scene_update_mesh_vertices_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                                          uint32_t flags, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, 0.0, nullptr, out);
+    return update_mesh_vertices(ENTRY_VERTICES_BUILD, s, mesh, input_vertices(v, nv, vn, nvn), flags, 0.0, nullptr, out);
 }
 extern "C" rt_status rt_scene_update_mesh_vertices_auto_build(rt_scene *s, int32_t mesh, const float *v, int32_t nv, const float *vn, int32_t nvn,
                                                               double max_ratio, uint32_t flags, rt_mesh_quality *q_out, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_update_mesh_vertices_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
-    return update_mesh_vertices(e, s, mesh, v, nv, vn, nvn, flags, max_ratio, q_out, out);
+    return update_mesh_vertices(ENTRY_VERTICES_AUTO_BUILD, s, mesh, input_vertices(v, nv, vn, nvn), flags, max_ratio, q_out, out);
 }
 
-// the same four forms fed by a pose (rt_mi355x.h, "mesh skinning"): the flag bits and out-structs of their counterparts above
+// the same four forms fed by a bone pose (rt_mi355x.h, "mesh skinning") ...
 extern "C" rt_status rt_scene_pose_mesh(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags)
 {
-    static const UpdateEntry e = {"rt_scene_pose_mesh", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
-    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, nullptr, &pose);
+    return update_mesh_vertices(ENTRY_POSE, s, mesh, input_bones(bones, n_bones), flags, 0.0, nullptr, nullptr);
 }
 extern "C" rt_status rt_scene_pose_mesh_auto(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
                                              rt_mesh_quality *out)
 {
-    static const UpdateEntry e = {"rt_scene_pose_mesh_auto", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
-    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, out, nullptr, &pose);
+    return update_mesh_vertices(ENTRY_POSE_AUTO, s, mesh, input_bones(bones, n_bones), flags, max_ratio, out, nullptr);
 }
 extern "C" rt_status rt_scene_pose_mesh_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_pose_mesh_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
-    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, out, &pose);
+    return update_mesh_vertices(ENTRY_POSE_BUILD, s, mesh, input_bones(bones, n_bones), flags, 0.0, nullptr, out);
 }
 extern "C" rt_status rt_scene_pose_mesh_auto_build(rt_scene *s, int32_t mesh, const float *bones, int32_t n_bones, uint32_t flags, double max_ratio,
                                                    rt_mesh_quality *q_out, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_pose_mesh_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
-    const MeshPose pose = {bones, n_bones, false, nullptr, 0};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, q_out, out, &pose);
+    return update_mesh_vertices(ENTRY_POSE_AUTO_BUILD, s, mesh, input_bones(bones, n_bones), flags, max_ratio, q_out, out);
 }
 
 // ... and by a morph pose (rt_mi355x.h, "morph targets"): weights, and bones that may be NULL with n_bones 0
 extern "C" rt_status rt_scene_morph_mesh(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
                                          uint32_t flags)
 {
-    static const UpdateEntry e = {"rt_scene_morph_mesh", RT_MESH_UPDATE_REBUILD | RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_REFIT};
-    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, nullptr, &pose);
+    return update_mesh_vertices(ENTRY_MORPH, s, mesh, input_morphs(weights, n_targets, bones, n_bones), flags, 0.0, nullptr, nullptr);
 }
 extern "C" rt_status rt_scene_morph_mesh_auto(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
                                               uint32_t flags, double max_ratio, rt_mesh_quality *out)
 {
-    static const UpdateEntry e = {"rt_scene_morph_mesh_auto", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE};
-    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, out, nullptr, &pose);
+    return update_mesh_vertices(ENTRY_MORPH_AUTO, s, mesh, input_morphs(weights, n_targets, bones, n_bones), flags, max_ratio, out, nullptr);
 }
 extern "C" rt_status rt_scene_morph_mesh_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones, int32_t n_bones,
                                                uint32_t flags, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_morph_mesh_build", RT_MESH_UPDATE_KEEP_PREVIOUS, false, UPDATE_BUILD};
-    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, 0.0, nullptr, out, &pose);
+    return update_mesh_vertices(ENTRY_MORPH_BUILD, s, mesh, input_morphs(weights, n_targets, bones, n_bones), flags, 0.0, nullptr, out);
 }
 extern "C" rt_status rt_scene_morph_mesh_auto_build(rt_scene *s, int32_t mesh, const float *weights, int32_t n_targets, const float *bones,
                                                     int32_t n_bones, uint32_t flags, double max_ratio, rt_mesh_quality *q_out, rt_mesh_build_info *out)
 {
-    static const UpdateEntry e = {"rt_scene_morph_mesh_auto_build", RT_MESH_UPDATE_KEEP_PREVIOUS, true, UPDATE_REFIT_MEASURE_BUILD};
-    const MeshPose pose = {bones, n_bones, true, weights, n_targets};
-    return update_mesh_vertices(e, s, mesh, nullptr, 0, nullptr, 0, flags, max_ratio, q_out, out, &pose);
+    return update_mesh_vertices(ENTRY_MORPH_AUTO_BUILD, s, mesh, input_morphs(weights, n_targets, bones, n_bones), flags, max_ratio, q_out, out);
 }
 
 // ---- what the last update took ---------------------------------------------------------------------------------------------
@@ -813,23 +781,17 @@ extern "C" rt_status rt_scene_mesh_normals_ms(rt_scene *s, int device, float *ms
     return RT_OK;
 }
 
-extern "C" rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms)
+// the last k_mesh_pose of one kind on a device (DeviceState::pose_ev): a bone pose's, or, morph, a morph pose's
+static rt_status mesh_pose_ms(rt_scene *s, int device, float *ms, bool morph, const char *who, const char *never)
 {
-    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_skin_ms: NULL argument");
+    if (!s || !ms) return fail(RT_ERR_ARG, "%s: NULL argument", who);
     DeviceState *D = find_device_state(s, device);
-    if (!D || !D->skin_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_skin_ms: device %d has not posed a mesh", device);
-    HIP_TRY(hipEventElapsedTime(ms, D->skin_ev[0], D->skin_ev[1]));
+    if (!D || !D->pose_timed[morph]) return fail(RT_ERR_STATE, "%s: device %d has not %s a mesh", who, device, never);
+    HIP_TRY(hipEventElapsedTime(ms, D->pose_ev[morph][0], D->pose_ev[morph][1]));
     return RT_OK;
 }
-
-extern "C" rt_status rt_scene_mesh_morph_ms(rt_scene *s, int device, float *ms)
-{
-    if (!s || !ms) return fail(RT_ERR_ARG, "rt_scene_mesh_morph_ms: NULL argument");
-    DeviceState *D = find_device_state(s, device);
-    if (!D || !D->morph_timed) return fail(RT_ERR_STATE, "rt_scene_mesh_morph_ms: device %d has not morphed a mesh", device);
-    HIP_TRY(hipEventElapsedTime(ms, D->morph_ev[0], D->morph_ev[1]));
-    return RT_OK;
-}
+extern "C" rt_status rt_scene_mesh_skin_ms(rt_scene *s, int device, float *ms) { return mesh_pose_ms(s, device, ms, false, "rt_scene_mesh_skin_ms", "posed"); }
+extern "C" rt_status rt_scene_mesh_morph_ms(rt_scene *s, int device, float *ms) { return mesh_pose_ms(s, device, ms, true, "rt_scene_mesh_morph_ms", "morphed"); }
 
 // ---- a mesh as it sits on a device ------------------------------------------------------------------------------------------
 // What the three calls below share once their own arguments have passed: the mesh is one the scene has (*nv, if asked for: its

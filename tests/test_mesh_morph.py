@@ -1,11 +1,11 @@
-"""Morph targets on the device (include/rt_mi355x.h, "morph targets": k_mesh_morph in csrc/rt_mesh_morph.hip behind the four
+"""Morph targets on the device (include/rt_mi355x.h, "morph targets": k_mesh_pose in csrc/rt_mesh_pose.hip behind the four
 rt_scene_morph_mesh* entry points).  The yardsticks are tests/test_mesh_skin.py's, neither of them the code under test: the host
 mirrors' positions (which tests/test_mesh_morph_host.py and tests/test_mesh_skin_host.py hold against independent transcriptions
 of the definitions) given to a FRESH scene through set_mesh -- with capi.mesh_smooth_normals of them where the mode is SMOOTH --
 and the same positions driven through update_mesh_vertices with the same arguments.  Every comparison is byte equality.
 
 Meshes and sets are tests/test_mesh_morph_host.py's, rigs and bone poses tests/test_mesh_skin_host.py's, scene, rays and frame
-tests/test_mesh_skin.py's.  The pose of the fresh-scene test has 12 of 256 targets active: one full batch of k_mesh_morph's loads
+tests/test_mesh_skin.py's.  The pose of the fresh-scene test has 12 of 256 targets active: one full batch of k_mesh_pose's loads
 and a tail of four."""
 import numpy as np
 import pytest
@@ -124,7 +124,7 @@ def test_active_list_edges(weights_name):
     ref.update_mesh_vertices(0, want)
     skin_gpu._same_read(s.mesh_device_read(0), ref.mesh_device_read(0), weights_name)
     s.pose_mesh(0, morph_weights=host.weights(256, "zero"), keep_previous=True)
-    assert s.mesh_device_previous(0).tobytes() == want.tobytes()      # the vertices k_mesh_morph wrote, where it wrote them
+    assert s.mesh_device_previous(0).tobytes() == want.tobytes()      # the vertices k_mesh_pose wrote, where it wrote them
     assert s.mesh_morphs(0)["store_current"] == 0
 
 
@@ -136,7 +136,8 @@ def test_active_list_edges(weights_name):
                                                                       ("teapot", "full", "all", None, "smooth"), ("teapot", "five", "last", "chain1024", "stored")])
 def test_every_form_leaves_what_the_update_leaves(name, set_name, weights_name, rig_name, mode, form, monkeypatch):
     """device state byte for byte (the trees are the same trees: the same refit, the same build), the same dict keys and flags;
-    tri3 and strip5 are single leaves: the store resolves the pose and the call goes the way of an update"""
+    tri3 is a single leaf: the store resolves the pose and the call goes the way of an update (strip5, five faces, has a root
+    record: the kernel runs)"""
     if form == "device_fallback":
         monkeypatch.setenv("RT_LBVH_STACK_CAP", "0")
     FORMS, FLAGS = skin_gpu.FORMS, skin_gpu.FLAGS
@@ -216,6 +217,44 @@ def test_two_owed_poses_hand_the_first_on():
         fresh = nrm._scene(name, want[1])
         a, b = nrm._by_face(s.mesh_device_read(0)), nrm._by_face(fresh.mesh_device_read(0))
         assert a[0].tobytes() == b[0].tobytes()
+
+
+# ---- the kinds of pose alternating ------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_kinds_alternate():
+    """sheet3 with rig chain3 and the 256-target set bound: a bone pose, then flagged a morph pose without bones, a bone pose and a
+    morph pose with bones.  After each step the device's previous positions are the mirror's of the step before (none after the
+    first, which is not flagged) and its state is a reference scene's, driven through update_mesh_vertices with the same flag and
+    the mirror's positions.  The two timers stay apart: mesh_morph_ms raises RT_ERR_STATE until the first morph pose and keeps its
+    value across the bone pose behind it; mesh_skin_ms keeps its value across either morph pose"""
+    name, rig_name = "sheet3", "chain3"
+    s, ref = _scene(name, "full", rig_name), _scene(name, "full", rig_name)
+    w2, w4 = host.weights(256, "alternating"), _pose_weights()
+    steps = ((dict(bones=_bones(name, rig_name, "bend")), skin.mirror(name, rig_name, "bend")),
+             (dict(morph_weights=w2), _posed(name, "full", w2)),
+             (dict(bones=_bones(name, rig_name, "shear")), skin.mirror(name, rig_name, "shear")),
+             (dict(bones=_bones(name, rig_name, "bend"), morph_weights=w4), _posed(name, "full", w4, rig_name, "bend")))
+    skin_ms = morph_ms = before = None
+    for k, (args, posed) in enumerate(steps):
+        if morph_ms is None:
+            with pytest.raises(capi.RtError) as e:
+                s.mesh_morph_ms()
+            assert e.value.status == -2
+        s.pose_mesh(0, args.get("bones"), morph_weights=args.get("morph_weights"), keep_previous=k > 0)
+        ref.update_mesh_vertices(0, posed, keep_previous=k > 0)
+        prev = s.mesh_device_previous(0)
+        assert (prev is None) if k == 0 else (prev.tobytes() == before.tobytes()), k
+        skin_gpu._same_read(s.mesh_device_read(0), ref.mesh_device_read(0), k)
+        if "morph_weights" in args:
+            assert s.mesh_skin_ms() == skin_ms, k
+            morph_ms = s.mesh_morph_ms()
+            assert morph_ms > 0.0
+        else:
+            assert morph_ms is None or s.mesh_morph_ms() == morph_ms, k
+            skin_ms = s.mesh_skin_ms()
+            assert skin_ms > 0.0
+        before = posed
+    assert s.mesh_morphs(0)["store_current"] == 0
 
 
 # ---- sequences -----------------------------------------------------------------------------------------------------------

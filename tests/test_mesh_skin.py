@@ -1,4 +1,4 @@
-"""Mesh skinning on the device (include/rt_mi355x.h, "mesh skinning": k_mesh_skin in csrc/rt_mesh_skin.hip behind the four
+"""Mesh skinning on the device (include/rt_mi355x.h, "mesh skinning": k_mesh_pose in csrc/rt_mesh_pose.hip behind the four
 rt_scene_pose_mesh* entry points).  Two yardsticks, neither of them the code under test: the host mirror's positions (which
 tests/test_mesh_skin_host.py holds against an independent transcription of the definition) given to a FRESH scene through set_mesh
 -- with capi.mesh_smooth_normals of them where the mode is SMOOTH -- and the same positions driven through update_mesh_vertices
@@ -163,6 +163,33 @@ def test_every_form_leaves_what_the_update_leaves(name, rig_name, pose_name, mod
         assert got["nodes"].tobytes() == lbvh[1].tobytes() and got["slot_face"].tobytes() == lbvh[2].tobytes()
     a, b = s.mesh_device_previous(0), ref.mesh_device_previous(0)
     assert (a is None) == (b is None) == (form != "keep_previous") and (a is None or a.tobytes() == b.tobytes())
+    assert nrm._get_mesh(s)["v"].tobytes() == posed.tobytes()
+
+
+# ---- the bone cap ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_the_bone_cap_on_one_partial_workgroup():
+    """strip5 -- eight vertices, one workgroup most of whose lanes only stage -- under a rig of 1024 bones, the cap: 48 KB of LDS
+    staged for a pose with no morph target.  Every vertex blends bones 0, 1, 1022 and 1023 (the rest are unused); the device holds
+    what update_mesh_vertices with the mirror's positions leaves, and the kernel did run (the store was asked for nothing)"""
+    name, n = "strip5", capi.MESH_SKIN_MAX_BONES
+    v = nrm._mesh(name)[0]
+    i = np.arange(len(v))
+    idx = np.tile(np.array([0, 1, n - 2, n - 1], np.uint16), (len(v), 1))
+    w = np.stack([0.1 + 0.05 * (i % 3), 0.4 - 0.03 * i, 0.2 + 0.02 * i, 0.3 - 0.05 * (i % 3) + 0.01 * i], 1).astype(F)
+    assert n == 1024 and (w > 0).all() and len(v) < 256
+    bones = host.pose(name, n, "shear")
+    posed = capi.mesh_skin(v, idx, w, bones)
+    assert (posed != v).any()
+    s, ref = nrm._scene(name), nrm._scene(name)
+    s.set_mesh_skin(0, idx, w, n)
+    for x in (s, ref):
+        x.mesh_device_read(0)
+    assert s.pose_mesh(0, bones) is None
+    assert s.mesh_skin_ms() > 0.0 and s.mesh_skin(0)["store_current"] == 0
+    ref.update_mesh_vertices(0, posed)
+    _same_read(s.mesh_device_read(0), ref.mesh_device_read(0), name)
+    assert s.mesh_skin(0)["store_current"] == 0
     assert nrm._get_mesh(s)["v"].tobytes() == posed.tobytes()
 
 

@@ -9,7 +9,7 @@ do before, and writes one JSON document.
   finished):
     (a) host      capi.mesh_morph (and capi.mesh_skin) on the host, then Scene.update_mesh_vertices with the positions: what a user
                   does without the feature; the host part alone is timed too
-    (b) pose      Scene.pose_mesh(morph_weights=...): 8 bytes an active target and 48 a bone go up, k_mesh_morph writes the
+    (b) pose      Scene.pose_mesh(morph_weights=...): 8 bytes an active target and 48 a bone go up, k_mesh_pose writes the
                   positions; and that kernel's own time by the library's HIP events (Scene.mesh_morph_ms), with the update's other
                   events beside it
   The kernel against its bytes: 12 (n_active + 2) a vertex, + 24 with a skin, at a rate taken from profiles/r04_peaks.json.  That

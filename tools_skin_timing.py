@@ -8,7 +8,7 @@ and writes one JSON document.
   (it returns after the device has finished):
     (a) host      capi.mesh_skin on the host, then Scene.update_mesh_vertices with its positions: what a user does without the
                   feature; the host part alone is timed too
-    (b) pose      Scene.pose_mesh: 48 bytes a bone go up, k_mesh_skin writes the positions; and that kernel's own time by the
+    (b) pose      Scene.pose_mesh: 48 bytes a bone go up, k_mesh_pose writes the positions; and that kernel's own time by the
                   library's HIP events (Scene.mesh_skin_ms), with the update's other events beside it
   One kernel, no variants.
 usage: python tools_skin_timing.py [--calls 30] [--warmup 5] [--bones 32] [--out profiles/skin_timing.json]"""
